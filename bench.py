@@ -1,6 +1,10 @@
 """bench.py -- CEM rollout row-steps/s of the PE-TS+CaDM planner on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run times the headline only: set-up, W warmup steps, K timed steps, one JSON line (`value`, `ms_per_step`).
+  --dump-outputs DIR writes the plan of the last timed step as DIR/plan.npy (float32; inputs and seeds are fixed, so two
+  builds compare output for output).  --full adds everything else below (`device_resident`, `roofline`, `legs`,
+  `cpu_baseline` / `parity`, `train_step`, `context_batched`); --legs / --no-cpu-baseline / --no-extras refine --full.
   N > 1 without WORLD_SIZE in the environment: bench.py launches its own N ranks (re-executes itself under
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>`); launched BY
   torch.distributed.run (WORLD_SIZE / RANK / LOCAL_RANK set) it is one of the ranks.  Rank 0 prints the one JSON line.
@@ -94,6 +98,8 @@ def cpu_baseline(prob, n, p, budget_s=15.0):
     N = 1) is the ONLY place bench.py touches oracle/: the timing here, and `parity_block` below which uses it as the checker."""
     from oracle import torch_baseline as tb
     cores = min(usable_cores(), 64)   # [5,800,200] batched matmuls stop scaling long before 64 threads
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        cores = max(1, min(cores, int(os.environ["OMP_NUM_THREADS"])))     # the job's share of a shared host
     tp = tb.prepare(prob)
     torch.manual_seed(0)
     rs = prob["m"] * n * p * prob["H"] * 5
@@ -211,6 +217,7 @@ class DryRunPlanner:
     test_bench_launcher.py: the N > 1 path must not rot between the rare runs on a multi-GPU node).  Every number it produces
     is a placeholder and the line says so (`data: "dry-run"`)."""
     RAMP_PLANS = 0
+    last_outputs = None        # no planner: nothing to dump
 
     def __init__(self, cfg, m, n_per_gpu, world, rank, dist):
         self.cfg, self.m, self.world, self.rank, self.dist = cfg, m, world, rank, dist
@@ -352,7 +359,8 @@ class Planner:
         return self.eng.cem_plan(self.obs, cp_obs, cp_act, self.init_mean, self.init_var, self.n, seed=0, call=c)
 
     def run_api(self, steps, warmup):
-        """K get_action calls through the class, warm start shifted between calls (sampler.py:118-120)."""
+        """K get_action calls through the class, warm start shifted between calls (sampler.py:118-120).  The plan of the last
+        timed call is kept as `last_outputs` (--dump-outputs)."""
         prev = self.prob["init_mean"].copy()
         self.ramp()
         for _ in range(warmup):
@@ -367,6 +375,7 @@ class Planner:
         self.barrier()
         elapsed = self._max_over_ranks(time.perf_counter() - t0)
         assert np.isfinite(plan).all() and np.abs(plan).max() <= 1.0
+        self.last_outputs = {"plan": np.array(plan, dtype=np.float32)}
         return elapsed
 
     def run_device(self, steps, warmup, profile=True):
@@ -453,6 +462,13 @@ def pmc_block(config, build_id):
         "from the committed rocprofv3 --pmc passes of this command on THIS build (build id %s), not measured in this run" % build_id)
 
 
+def dump_outputs(directory, outputs):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/<name>.npy per array (float32)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -460,12 +476,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="cfg2", help="headline workload: cfg2 (BASELINE metric) | cfg3 | cfg4 | cfg5 | m10")
     ap.add_argument("--cand-per-gpu", type=int, default=None)
-    ap.add_argument("--legs", default=None, help="comma list of extra legs (default: cfg3,cfg4,cfg5,m10 at N=1; cfg5 at N>1; 'none')")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline leg (and the parity block measured inside it)")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: no legs, no training-step leg, no cpu baseline / parity")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: device-resident pass, hipEvent-bracketed kernel pass (roofline, "
+                    "PMC quote), legs, cpu baseline / parity, training-step and context legs (default: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the plan of the last timed get_action as DIR/plan.npy (float32)")
+    ap.add_argument("--legs", default=None, help="with --full: comma list of extra legs (default: cfg3,cfg4,cfg5,m10 at N=1; cfg5 at N>1; 'none')")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg (and the parity block measured inside it)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no legs, no training-step leg, no cpu baseline / parity")
     ap.add_argument("--lib", default=None, help="DEVELOPER: bind the run to another build of the library (tools/ab.sh); default = the product")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rank / JSON plumbing only, on CPU over gloo, no planner (tests/test_bench_launcher.py)")
     args = ap.parse_args()
+    if args.legs is not None and not args.full:
+        ap.error("--legs needs --full")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs a planner (not --dry-run)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -498,36 +521,22 @@ def main():
             return DryRunPlanner(dict(synth.CONFIGS[cfgname]), m, cand or n_per_gpu, world, rank, dist), cfgname, m
         return Planner(dict(synth.CONFIGS[cfgname]), m, cand or n_per_gpu, world, rank, local_rank, dist, lib), cfgname, m
 
+    # the headline: K get_action calls through the class (`value`, `ms_per_step`)
     head, cfgname, m = make(args.config, args.cand_per_gpu)
     api_elapsed = head.run_api(args.steps, args.warmup)
-    plain = head.run_device(args.steps, args.warmup, profile=False)      # device-resident wall time: no event bracketing
-    # kernel / collective times from hipEvents: its own pass of at least 60 get_actions behind 20 bracketed warmup ones -- the brackets read
-    # 166-169 us per rollout over the first 100 launches of a bracketed pass and 160 over 500 (rocprofv3 of the same command: 155-157);
-    # `roofline.launches` says how many launches the average is over.  The K timed steps of the headline are the two passes above.
-    ksteps = max(args.steps, 60)
-    r = head.run_device(ksteps, max(args.warmup, 20), profile=True)
-    s = head.summary(r, ksteps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head.last_outputs)
     cfg = head.cfg
     api_ms = api_elapsed / args.steps * 1e3
-    dev_ms = plain["elapsed"] / args.steps * 1e3
-    api_value = s["row_steps_per_get_action"] * args.steps / api_elapsed
-
-    traffic = mfma_busy = pmc_src = None
-    pmc_note = "PMC passes are recorded for the default single-GPU workloads only"
-    if world == 1 and args.cand_per_gpu is None and not args.dry_run:
-        traffic, mfma_busy, pmc_src, pmc_note = pmc_block(args.config, build_id)
-    peak_equiv = F16_MFMA_PEAK_TFLOPS / 3.0
+    row_steps = m * head.n * head.p * head.H * head.iters
+    api_value = row_steps * args.steps / api_elapsed
     out = {
         "metric": "CEM rollout row-steps/s (cand x part x horizon x 5 CEM iters per get_action; ens=%d members)" % cfg["E"],
         "value": api_value, "unit": "row-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": api_ms, "get_action_latency_ms": api_ms, "plans_per_s": 1e3 / api_ms, "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "per_gpu_value": api_value / world,
         "value_note": "wall time of the drop-in class's get_action, numpy in -> numpy out, warm-start shift between calls (SURVEY.md 8d); "
-                      "`device_resident` = the same planner with inputs already in HBM",
-        "device_resident": {"value": s["row_steps_per_get_action"] / (dev_ms * 1e-3), "unit": "row-steps/s", "device_ms_per_get_action": dev_ms,
-                            "note": "cadm_cem_plan back to back on HBM-resident inputs, no hipEvent bracketing; the pass that yields the "
-                                    "kernel times (events on) took %.4f ms per get_action" % s["ms_per_get_action"]},
-        "api_overhead_us": (api_ms - dev_ms) * 1e3,
+                      "with --full, `device_resident` = the same planner with inputs already in HBM",
         "dtype": "f32 (each fp32 product as 3 f16 MFMA products of 2-way split operands, fp32 accumulate; error <= 2^-22 per product; "
                  "measured parity: see `parity`)",
         "data": "dry-run (placeholders: no planner ran)" if args.dry_run else "synthetic",
@@ -535,24 +544,57 @@ def main():
         "config": {"workload": "%s: %s PE-TS+CaDM get_action, ens=%d part=%d cand=%d (%d/GPU) H=%d m=%d, random-init weights"
                                % (args.config, cfg["env"], cfg["E"], cfg["p"], head.n, head.n_per_gpu, cfg["H"], m),
                    "global_candidates": head.n, "parallelism": "candidate-shard x%d" % world, "collective": head.collective,
-                   "rccl_nranks": head.rccl_nranks, "allgather_us": s["allgather_us"], "allgathers_timed": s["allgather_calls"]},
-        "roofline": {"bound": "mfma", "achieved": s["achieved_tflops"], "peak": peak_equiv, "unit": "TFLOP/s",
-                     "frac": s["achieved_tflops"] / peak_equiv,
-                     "peak_note": "fp32-equivalent ceiling of the pipe the kernel executes on: dense f16 MFMA peak 2500 TFLOP/s / 3 split "
-                                  "products per fp32 product (v_mfma_f32_16x16x32_f16); `achieved` counts the algorithmic fp32 FLOPs of SURVEY 8d",
-                     "pipe": "v_mfma_f32_16x16x32_f16", "pipe_peak": F16_MFMA_PEAK_TFLOPS,
-                     "pipe_executed": s["executed_f16_mfma_tflops"], "pipe_frac": s["executed_f16_mfma_tflops"] / F16_MFMA_PEAK_TFLOPS,
-                     "mfma_busy": mfma_busy, "traffic": traffic, "pmc_source": pmc_src, "pmc_note": pmc_note,
-                     "traffic_note": "fabric bytes per launch summed over the 8 XCD L2s; algorithmic: the packed weight stream once per chip, ~3.4 MB incl. "
-                                     "actions and returns.  A member's workgroups sit on two or three XCDs (XCD-affine work items since round 6: ~9 MB; with "
-                                     "every member on every XCD it was 28 MB); < 0.1 TB/s, not what bounds the kernel",
-                     "fp32_matrix_peak_for_context": FP32_MFMA_PEAK_TFLOPS,
-                     "kernel": "rollout_xdl_kernel", "avg_launch_ms": s["kernel_avg_launch_ms"], "launches": s["launches"],
-                     "launch_note": "one 'launch' = one rollout of all rows over the horizon, bracketed by hipEvents inside libcadm_hip.so on "
-                                    "the launch stream (a single kernel at cfg2; at >= 2 row tiles per workgroup slot the launcher issues a "
-                                    "tile-pair kernel plus a single-tile kernel for the remainder)",
-                     "flops_per_row_step": s["flops_per_row_step"], "row_steps_per_launch": s["row_steps_per_launch"]},
+                   "rccl_nranks": head.rccl_nranks},
     }
+    if args.full:
+        full_passes(args, out, head, make, world, rank, local_rank, build_id, lib)
+    else:
+        head.close()
+    if rank == 0:
+        print(json.dumps(out))
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_passes(args, out, head, make, world, rank, local_rank, build_id, lib):
+    """--full: everything the headline does not need, added to `out` (closes `head`)."""
+    plain = head.run_device(args.steps, args.warmup, profile=False)      # device-resident wall time: no event bracketing
+    # kernel / collective times from hipEvents: its own pass of at least 60 get_actions behind 20 bracketed warmup ones -- the brackets read
+    # 166-169 us per rollout over the first 100 launches of a bracketed pass and 160 over 500 (rocprofv3 of the same command: 155-157);
+    # `roofline.launches` says how many launches the average is over.
+    ksteps = max(args.steps, 60)
+    r = head.run_device(ksteps, max(args.warmup, 20), profile=True)
+    s = head.summary(r, ksteps)
+    api_ms = out["ms_per_step"]
+    dev_ms = plain["elapsed"] / args.steps * 1e3
+
+    traffic = mfma_busy = pmc_src = None
+    pmc_note = "PMC passes are recorded for the default single-GPU workloads only"
+    if world == 1 and args.cand_per_gpu is None and not args.dry_run:
+        traffic, mfma_busy, pmc_src, pmc_note = pmc_block(args.config, build_id)
+    peak_equiv = F16_MFMA_PEAK_TFLOPS / 3.0
+    out["device_resident"] = {"value": s["row_steps_per_get_action"] / (dev_ms * 1e-3), "unit": "row-steps/s", "device_ms_per_get_action": dev_ms,
+                              "note": "cadm_cem_plan back to back on HBM-resident inputs, no hipEvent bracketing; the pass that yields the "
+                                      "kernel times (events on) took %.4f ms per get_action" % s["ms_per_get_action"]}
+    out["api_overhead_us"] = (api_ms - dev_ms) * 1e3
+    out["config"].update(allgather_us=s["allgather_us"], allgathers_timed=s["allgather_calls"])
+    out["roofline"] = {"bound": "mfma", "achieved": s["achieved_tflops"], "peak": peak_equiv, "unit": "TFLOP/s",
+                       "frac": s["achieved_tflops"] / peak_equiv,
+                       "peak_note": "fp32-equivalent ceiling of the pipe the kernel executes on: dense f16 MFMA peak 2500 TFLOP/s / 3 split "
+                                    "products per fp32 product (v_mfma_f32_16x16x32_f16); `achieved` counts the algorithmic fp32 FLOPs of SURVEY 8d",
+                       "pipe": "v_mfma_f32_16x16x32_f16", "pipe_peak": F16_MFMA_PEAK_TFLOPS,
+                       "pipe_executed": s["executed_f16_mfma_tflops"], "pipe_frac": s["executed_f16_mfma_tflops"] / F16_MFMA_PEAK_TFLOPS,
+                       "mfma_busy": mfma_busy, "traffic": traffic, "pmc_source": pmc_src, "pmc_note": pmc_note,
+                       "traffic_note": "fabric bytes per launch summed over the 8 XCD L2s; algorithmic: the packed weight stream once per chip, ~3.4 MB incl. "
+                                       "actions and returns.  A member's workgroups sit on two or three XCDs (XCD-affine work items since round 6: ~9 MB; with "
+                                       "every member on every XCD it was 28 MB); < 0.1 TB/s, not what bounds the kernel",
+                       "fp32_matrix_peak_for_context": FP32_MFMA_PEAK_TFLOPS,
+                       "kernel": "rollout_xdl_kernel", "avg_launch_ms": s["kernel_avg_launch_ms"], "launches": s["launches"],
+                       "launch_note": "one 'launch' = one rollout of all rows over the horizon, bracketed by hipEvents inside libcadm_hip.so on "
+                                      "the launch stream (a single kernel at cfg2; at >= 2 row tiles per workgroup slot the launcher issues a "
+                                      "tile-pair kernel plus a single-tile kernel for the remainder)",
+                       "flops_per_row_step": s["flops_per_row_step"], "row_steps_per_launch": s["row_steps_per_launch"]}
     prob_head, n_head, p_head = head.prob, head.n, head.p
     head.close()
 
@@ -583,10 +625,6 @@ def main():
         if world == 1 and not args.no_extras and not args.dry_run:
             out["train_step"] = train_step_bench("cuda:%d" % local_rank, lib)
             out["context_batched"] = context_bench("cuda:%d" % local_rank, lib)
-        print(json.dumps(out))
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

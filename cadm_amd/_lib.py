@@ -127,7 +127,8 @@ def build(verbose=False):
     to tell that from a build that exercised the compiler."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     before = subprocess.run(["make", "-C", CSRC, "-q", "HIPCC=" + hipcc], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL).returncode == 0
-    r = subprocess.run(["make", "-C", CSRC, "-j", str(os.cpu_count() or 4), "HIPCC=" + hipcc],
+    jobs = int(os.environ.get("MAX_JOBS") or min(os.cpu_count() or 4, 16))     # os.cpu_count() is the host's, not this job's share
+    r = subprocess.run(["make", "-C", CSRC, "-j", str(jobs), "HIPCC=" + hipcc],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or r.returncode != 0:
         print(r.stdout)

@@ -28,7 +28,8 @@ def _env():
 
 @pytest.mark.parametrize("n", [1, 2])
 def test_bench_self_launches_its_ranks(n):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--dry-run"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--dry-run",
+                        "--full"],
                        env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -54,11 +55,33 @@ def test_bench_under_torch_distributed_run():
     s.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--dry-run", "--legs", "none"],
+                        "--dry-run", "--full", "--legs", "none"],
                        env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["legs"] == {}
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_run_is_the_headline_only(n):
+    """Without --full the line carries the headline only: --steps sets the timed steps, nothing beyond it is measured."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "4", "--warmup", "2", "--dry-run"],
+                       env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    out = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert k in out, k
+    assert out["n_gpus"] == n and out["steps"] == 4 and out["warmup"] == 2 and out["ms_per_step"] > 0
+    for k in ("legs", "roofline", "device_resident", "cpu_baseline", "parity", "train_step", "context_batched"):
+        assert k not in out, k
+
+
+def test_legs_need_full():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--legs", "cfg3"], env=_env(),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
 
 
 def test_gpus_mismatch_is_refused():

@@ -5,7 +5,7 @@
 A=$1; B=$2; N=${3:-3}; shift 3
 for i in $(seq $N); do
   for L in $A $B; do
-    python bench.py --steps 100 --legs none --no-cpu-baseline --no-extras --lib $L "$@" | python -c "
+    python bench.py --full --steps 100 --legs none --no-cpu-baseline --no-extras --lib $L "$@" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', round(d['device_resident']['value']/1e6,1), 'M', round(d['roofline']['avg_launch_ms']*1e3,1), 'us')"
   done

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=$(cd $(dirname $0)/.. && pwd)
 OUT=/tmp/kstats_$$
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python $R/bench.py --legs none --no-cpu-baseline --no-extras "$@" > $OUT.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python $R/bench.py --full --legs none --no-cpu-baseline --no-extras "$@" > $OUT.log 2>&1
 python - $OUT $OUT.log <<'PY'
 import csv, glob, json, sys
 out, log = sys.argv[1], sys.argv[2]

@@ -2,7 +2,7 @@
 # Runs ON THE GPU BOX: latency / pipe-occupancy counters of the rollout kernel.  usage: tools/pmc_latency.sh <tag>
 set -u
 OUT=$PWD/gpurun_out/${1:-lat}; mkdir -p $OUT; export TMPDIR=/tmp
-BENCH="python $PWD/bench.py --no-cpu-baseline --legs none --steps 20 --warmup 3"
+BENCH="python $PWD/bench.py --full --no-cpu-baseline --legs none --steps 20 --warmup 3"
 cd /tmp
 for grp in "SQ_INST_LEVEL_LDS SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS" "SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_VMEM_TA_ADDR_FIFO_FULL" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_VALU_MFMA_COEXEC_CYCLES" "SQ_INST_CYCLES_SALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INST_LEVEL_SMEM" \
