@@ -324,9 +324,7 @@ __global__ void cem_refit_kernel(const float* __restrict__ cand, const float* __
 // `actions`: the elites' values of these elements were read before).  Arithmetic = cem_refit_kernel + sample_actions_kernel
 // (same summation order, same Philox counters): the fused planner equals the stepwise composition bit for bit.
 // ---------------------------------------------------------------------------------------------
-#ifndef CADM_FUSED_EPW
-#define CADM_FUSED_EPW 4      // elements per workgroup: n x EPW <= 1024 samples = one round of the workgroup's threads at n <= 256
-#endif
+constexpr int FUSED_EPW = 4;      // elements per workgroup: n x EPW <= 1024 samples = one round of the workgroup's threads at n <= 256
 // how many of the 64 keys at `q` (LDS, 16-byte aligned, every lane the same address: broadcast reads) are below ki -- the reads are
 // independent and issued 16 keys at a time (a rolled loop with a run-time bound waited out one LDS round trip per key: 2.9 us of the kernel)
 __device__ __forceinline__ int count_below_64(const uint64_t* q, uint64_t ki) {
@@ -366,12 +364,12 @@ __global__ __launch_bounds__(1024) void cem_refit_sample_kernel(const float* __r
     __shared__ __attribute__((aligned(16))) uint64_t raw[256];
     __shared__ uint64_t keys[64];
     __shared__ int rank_q[4][256];
-    __shared__ float vals[CADM_FUSED_EPW][64];       // [EPW][K <= 64] elite values of this workgroup's elements
-    __shared__ float nd[2 * CADM_FUSED_EPW];
+    __shared__ float vals[FUSED_EPW][64];       // [EPW][K <= 64] elite values of this workgroup's elements
+    __shared__ float nd[2 * FUSED_EPW];
     const int HA = H * A, n = G * n_local, tid = threadIdx.x;
-    const int NS = (HA + CADM_FUSED_EPW - 1) / CADM_FUSED_EPW;
-    const int mi = blockIdx.x / NS, ta0 = (blockIdx.x % NS) * CADM_FUSED_EPW;
-    const int ne = HA - ta0 < CADM_FUSED_EPW ? HA - ta0 : CADM_FUSED_EPW;
+    const int NS = (HA + FUSED_EPW - 1) / FUSED_EPW;
+    const int mi = blockIdx.x / NS, ta0 = (blockIdx.x % NS) * FUSED_EPW;
+    const int ne = HA - ta0 < FUSED_EPW ? HA - ta0 : FUSED_EPW;
     const int wave = tid >> 6, lane = tid & 63;
     // (requested now, consumed behind the statistics: their round trip used to sit at the end of the kernel's dependent chain)
     float mean_pre = 0.0f, var_pre = 0.0f;
@@ -437,7 +435,7 @@ __global__ __launch_bounds__(1024) void cem_refit_sample_kernel(const float* __r
             const float mo = mean_pre * alpha + (1.0f - alpha) * nm;               // :485
             const float vo = var_pre * alpha + (1.0f - alpha) * nv;                // :486
             mean_out[o] = mo; var_out[o] = vo;
-            nd[e] = mo; nd[CADM_FUSED_EPW + e] = vo;
+            nd[e] = mo; nd[FUSED_EPW + e] = vo;
         }
     }
     __syncthreads();
@@ -445,7 +443,7 @@ __global__ __launch_bounds__(1024) void cem_refit_sample_kernel(const float* __r
     for (int q = tid; q < n * ne; q += blockDim.x) {
         const int c = q / ne, e = q % ne;
         const size_t L = ((size_t)mi * n + c) * HA + ta0 + e;
-        actions[L] = sample_action(nd[e], nd[CADM_FUSED_EPW + e], nullptr, L, seed, call, next_it, lb, ub);
+        actions[L] = sample_action(nd[e], nd[FUSED_EPW + e], nullptr, L, seed, call, next_it, lb, ub);
     }
 }
 
@@ -455,7 +453,7 @@ int cadm_launch_refit_sample(cadm_ctx* ctx, const float* cand_returns, const flo
     // (the LAST refit of a call stays cem_refit_kernel, one workgroup per env: the same element-parallel form with the plan and the
     //  completion flags written by 45 workgroups -- a system-scope fence and a few PCIe stores each, a per-env arrival counter -- measured
     //  ~16 us against its 10.0, round 6)
-    const int HA = ctx->H * ctx->A, NS = (HA + CADM_FUSED_EPW - 1) / CADM_FUSED_EPW;
+    const int HA = ctx->H * ctx->A, NS = (HA + FUSED_EPW - 1) / FUSED_EPW;
     hipLaunchKernelGGL(cem_refit_sample_kernel, dim3(m * NS), dim3(1024), 0, stream, cand_returns, rows, ctx->p, G, n_local, actions, m,
                        ctx->H, ctx->A, ctx->cfg.num_elites, ctx->cfg.alpha, mean_in, var_in, mean_out, var_out, ctx->cfg.lower_bound,
                        ctx->cfg.upper_bound, seed, call, next_it);

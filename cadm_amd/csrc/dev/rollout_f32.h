@@ -41,10 +41,7 @@ struct RC {
     static constexpr int NF = NT / 4, NS = NT % 4;                     // full tiles per wave / split tiles
     static constexpr int NTO = (D + 7) / 8;                            // head tiles (8 dims: mu|lv)
     static constexpr int NFO = NTO / 4, NSO = NTO % 4;
-#ifndef CADM_PF
-#define CADM_PF 3
-#endif
-    static constexpr int PF = CADM_PF;                                 // weight ring depth (chunks)
+    static constexpr int PF = 3;                                       // weight ring depth (chunks)
     // head layer with only K-split tiles: split K by CHUNK instead of by k-step (see head_pass_csplit);
     // must match make_geo() in capi.hip
     static constexpr bool OCS = NFO == 0 && NSO > 0 && NS == 1;
@@ -78,9 +75,6 @@ struct Ring {
 // one chunk of this wave's stream: NFO float4 blocks + NSO dword blocks, lane-linear
 template <int SLOT, int NFO, int NSO, class G>
 __device__ __forceinline__ void ring_load(Ring<G>& ring, __amdgpu_buffer_rsrc_t rsrc, unsigned soff, int lane) {
-#ifdef CADM_ABLATE_SAME_LINES
-    soff = 0;      // developer ablation: every ring load re-reads the same few KB (L1 hits): issue cost without memory time
-#endif
 #pragma unroll
     for (int i = 0; i < NFO; ++i)
         ring.f[SLOT][i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16 + i * 1024, soff, 0));

@@ -50,8 +50,8 @@ __global__ void pack_xdl_kernel(const XdlPackArgs a) {
         const int grp = lane >> 4, m = lane & 15;
         int tile, c;
         if (invf) { tile = g.tstart(w) + fj; c = g.NC0 - 1; }      // the invariant chunk: one fragment per tile, in tile order
-        else if (layer < g.NH) {              // hidden-type outputs: tiles in groups of xdl_group(w), chunk-major inside a group
-            const int gsz = xdl_group(w);
+        else if (layer < g.NH) {              // hidden-type outputs: tiles in groups of xdl_group(), chunk-major inside a group
+            const int gsz = xdl_group();
             const int gi = fj / (gsz * nchl), jj = fj - gsz * gi * nchl;
             const int gs = (ntw - gsz * gi) < gsz ? (ntw - gsz * gi) : gsz;
             c = jj / gs;

@@ -9,16 +9,9 @@
 // plain item = linear id, every member's workgroups sit on all eight XCDs and each L2 fetches every member's weight stream (28 MB of fabric
 // reads per cfg2 launch for 3.4 MB of weights).  XCD x takes the x-th CONTIGUOUS eighth of the member-major item list instead (as the training
 // kernels do, train.hip: xcd_spread_item): an L2 then holds the streams of two or three members.  A bijection on [0, gridDim.x).
-#ifndef CADM_ROLLOUT_XCD_AFFINE
-#define CADM_ROLLOUT_XCD_AFFINE 1
-#endif
 __device__ __forceinline__ int rollout_item() {
-#if CADM_ROLLOUT_XCD_AFFINE
     const int lin = (int)blockIdx.x, total = (int)gridDim.x, x = lin & 7;
     return x * (total >> 3) + (x < (total & 7) ? x : (total & 7)) + (lin >> 3);
-#else
-    return (int)blockIdx.x;
-#endif
 }
 #ifdef CADM_PHASE_TIMING
 #define NPH 24
@@ -182,13 +175,8 @@ __device__ __forceinline__ float head_sd(float lv, float enmax, float emin, floa
 // clamps in front of every conversion (4 v_min per hidden tile epilogue of 30 instructions; a v_med3 per input feature): the kernels
 // are bound by their VALU instructions as much as by their MFMAs.  fp32 arithmetic and MFMAs are not affected.  Set once per wave, at
 // kernel entry (the register is per wave and does not outlive it).
-#ifndef CADM_FP16_SATURATE
-#define CADM_FP16_SATURATE 1
-#endif
 __device__ __forceinline__ void fp16_saturate_on() {
-#if CADM_FP16_SATURATE
     __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);      // hwreg(HW_REG_MODE, 23, 1) = 1
-#endif
 }
 
 template <int R0, int R1>

@@ -22,10 +22,6 @@
 // may cut a batch between them freely (xdl_launch).
 //
 // Included by rollout_xdl.h (uses its geometry class XC, epilogue arithmetic XHiddenEpi and helpers).
-
-// TIMING EXPERIMENTS ONLY (tools/build_variant.sh; wrong results): CADM_WT_EXPERIMENT_NOMFMA / _NOFRAG (fragments not read from LDS) /
-// _NOSTATE (no state update, noise, input assembly) / _NOBAR (no block barriers) / _NOGLDS (no weight requests);
-// CADM_XDL_EXPERIMENT_NOEPI also applies (profiles/r4_wave_tile.md).
 namespace {
 
 template <class G>
@@ -40,10 +36,7 @@ struct WT {
     static constexpr int TABW = 28;
     // two register sets for the weight fragments (chunk c + 1 requested from LDS before chunk c's MFMAs) where the registers allow:
     // wide observation spaces keep more rollout state and head output per lane (slim humanoid: 6 pair slots)
-#ifndef CADM_WT_NBUF
-#define CADM_WT_NBUF 2
-#endif
-    static constexpr int DBUF = (NTO > 4 || (NTO > 3 && NCH > 7)) ? 1 : CADM_WT_NBUF;      // register sets of weight fragments
+    static constexpr int DBUF = (NTO > 4 || (NTO > 3 && NCH > 7)) ? 1 : 2;      // register sets of weight fragments
     // LDS carve (bytes)
     static constexpr int SLOTS = 2;                                      // ring depth: the block requested at a boundary is the one right behind the block computed
     static constexpr int RING = 0;                                       // [SLOTS][BLK]
@@ -88,7 +81,6 @@ __device__ __forceinline__ void wt_glds16(const WTRing& rg, unsigned off, int la
 template <class G, int NF>
 __device__ __forceinline__ void wt_request(WTRing& rg, unsigned char* sm, int slot_idx, int wave, int lane) {
     using W = WT<G>;
-#ifndef CADM_WT_EXPERIMENT_NOGLDS
     unsigned char* dst = sm + W::RING + slot_idx * W::BLK;
     static_for(std::make_integer_sequence<int, (2 * NF + W::NW - 1) / W::NW>{}, [&](auto ic) {
         constexpr int i = decltype(ic)::value;
@@ -97,7 +89,6 @@ __device__ __forceinline__ void wt_request(WTRing& rg, unsigned char* sm, int sl
         if constexpr (W::NW * i + W::NW - 1 < 2 * NF) wt_glds16(rg, rg.next + (unsigned)piece * 1024u, lane, dst + piece * 1024);
         else { if (piece < 2 * NF) wt_glds16(rg, rg.next + (unsigned)piece * 1024u, lane, dst + piece * 1024); }
     });
-#endif
     rg.next += (unsigned)NF * CADM_XDL_FRAG_BYTES;
     if (rg.next >= rg.bytes) rg.next = 0;
 }
@@ -111,12 +102,10 @@ __device__ __forceinline__ void wt_request(WTRing& rg, unsigned char* sm, int sl
 template <class G, int NF_NEXT>
 __device__ __forceinline__ const unsigned char* wt_block_boundary(WTRing& rg, unsigned char* sm, int wave, int lane) {
     using W = WT<G>;
-#if !defined(CADM_WT_EXPERIMENT_NOBAR)
     // every wave's share of the requests issued one block ago must be IN LDS before any wave reads the block: the wait is stated here and not
     // left to hipcc (a workgroup-scope barrier does not have to drain vmcnt; tests/test_isa_hygiene.py checks the shipped code for it)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#endif
     const int ahead = rg.par + W::SLOTS - 1;
     wt_request<G, NF_NEXT>(rg, sm, ahead >= W::SLOTS ? ahead - W::SLOTS : ahead, wave, lane);
     const unsigned char* cur = sm + W::RING + rg.par * W::BLK;
@@ -134,12 +123,6 @@ __device__ __forceinline__ void wt_accumulate(const unsigned char* slot, int lan
     // the fragments of chunk c + 1 are requested before chunk c's MFMAs (two register sets): a wave alone on its SIMD otherwise
     // waits out the LDS latency at every chunk
     uintx4 w[DBUF][GS][2];
-#ifdef CADM_WT_EXPERIMENT_NOFRAG
-#pragma unroll
-    for (int q = 0; q < DBUF; ++q)
-#pragma unroll
-        for (int k = 0; k < GS; ++k) { w[q][k][0] = uintx4{1u, 2u, 3u, 4u}; w[q][k][1] = uintx4{1u, 2u, 3u, 4u}; }
-#endif
     auto wload = [&](auto cc) {      // the cc-th chunk in processing order
         constexpr int c = decltype(cc)::value;
         constexpr int co = LASTFIRST ? (c == 0 ? NCHL - 1 : c - 1) : c;
@@ -148,11 +131,7 @@ __device__ __forceinline__ void wt_accumulate(const unsigned char* slot, int lan
 #pragma unroll
             for (int part = 0; part < 2; ++part) {
                 const int fi = HEAD ? k * NCHL + co : co * GS + k;
-#ifndef CADM_WT_EXPERIMENT_NOFRAG
                 w[c % DBUF][k][part] = *reinterpret_cast<const uintx4*>(slot + (fi * 2 + part) * 1024 + lane * 16);
-#else
-                (void)fi;
-#endif
             }
     };
     static_for(std::make_integer_sequence<int, (DBUF - 1 < NCHL ? DBUF - 1 : NCHL)>{}, [&](auto cc) { wload(cc); });
@@ -160,17 +139,12 @@ __device__ __forceinline__ void wt_accumulate(const unsigned char* slot, int lan
         constexpr int c = decltype(cc)::value;
         constexpr int co = LASTFIRST ? (c == 0 ? NCHL - 1 : c - 1) : c;      // the chunk whose operands these MFMAs read
         if constexpr (c + DBUF - 1 < NCHL) wload(std::integral_constant<int, c + DBUF - 1>{});
-#ifdef CADM_WT_EXPERIMENT_NOMFMA
-#pragma unroll
-        for (int k = 0; k < GS; ++k) asm volatile("" : "+v"(hi[k]), "+v"(lo[k]) : "v"(w[c % DBUF][k][0]), "v"(w[c % DBUF][k][1]), "v"(X1[co]), "v"(X2[co]));
-#else
 #pragma unroll
         for (int k = 0; k < GS; ++k) hi[k] = xmfma(w[c % DBUF][k][0], X1[co], hi[k]);
 #pragma unroll
         for (int k = 0; k < GS; ++k) lo[k] = xmfma(w[c % DBUF][k][1], X1[co], lo[k]);
 #pragma unroll
         for (int k = 0; k < GS; ++k) hi[k] = xmfma(w[c % DBUF][k][0], X2[co], hi[k]);
-#endif
         if constexpr (DBUF > 1) __builtin_amdgcn_sched_barrier(0);      // pin the pipeline: no load sinking / hoisting across chunks
     });
 }
@@ -313,18 +287,7 @@ __global__ __launch_bounds__(WT<G>::NTHR) void rollout_wt_kernel(const RolloutAr
 
         for (int t = 0; t <= H; ++t) {
             f16x8 X1[NCH], X2[NCH];
-#ifdef CADM_WT_EXPERIMENT_NOSTATE
             if (active) {
-#pragma unroll
-                for (int c = 0; c < NC0; ++c) {
-                    X1[c] = *reinterpret_cast<const f16x8*>(xw + ((0 * NC0 + c) * 64 + lane) * 16);
-                    X2[c] = *reinterpret_cast<const f16x8*>(xw + ((1 * NC0 + c) * 64 + lane) * 16);
-                }
-            }
-            if (false) {
-#else
-            if (active) {
-#endif
                 // ===== state update from step t-1's head (:348-365,463-466) + reward (:469-471) + input assembly (:442-460), in-lane =====
                 // Everything lane-dependent is derived HERE from opaque copies: hipcc otherwise hoists ~45 loop-invariant LDS
                 // addresses / row pointers out of the step loop and keeps them in registers through the layers, where the
@@ -460,8 +423,8 @@ __global__ __launch_bounds__(WT<G>::NTHR) void rollout_wt_kernel(const RolloutAr
                     constexpr int g = decltype(gc)::value, GS = W::gs_hidden(g);
                     static_assert(W::SLOTS == 2, "a block boundary names the block right behind the current one");
                     auto epilogue = [&](floatx4 (&hi)[2], floatx4 (&lo)[2]) __attribute__((always_inline)) {
-                        const XHiddenEpi<G, CADM_EPI_PACKED_WT> epi{nullptr, nullptr, 0, 0, 0, 0, 0};
-                        typename XHiddenEpi<G, CADM_EPI_PACKED_WT>::State st[2];
+                        const XHiddenEpi<G, false> epi{nullptr, nullptr, 0, 0, 0, 0, 0};      // (scalar arithmetic: rollout_xdl.h XHiddenEpi)
+                        typename XHiddenEpi<G, false>::State st[2];
                         const floatx4 zero = floatx4{0.f, 0.f, 0.f, 0.f};
                         static_for(std::make_integer_sequence<int, 5>{}, [&](auto sc) {
 #pragma unroll

@@ -17,8 +17,8 @@
 //     streamed from L2 in consumption order through a register ring), the 16 rows of a tile are the B / D columns.  A
 //     lane's D fragments of tiles (2c, 2c+1) are its B fragment of chunk c of the next layer: activations cross layers
 //     through LDS with lane-linear accesses;
-//   * wave w owns BASE + (w < EXTRA) hidden tiles and computes them CADM_XDL_GROUP at a time over the whole K (the B
-//     operand is read chunk by chunk from LDS, ahead of its use); the last group's epilogue (swish, f16 split, LDS store)
+//   * wave w owns BASE + (w < EXTRA) hidden tiles and computes them two at a time (xdl_geo.h: xdl_group) over the whole K (the
+//     B operand is read chunk by chunk from LDS, ahead of its use); the last group's epilogue (swish, f16 split, LDS store)
 //     overlaps with the SIMD's other wave, earlier groups' with the next group's MFMAs;
 //   * MT = 1: the rollout state lives in registers of the 256 "feature threads" (waves 0-3), their twins in waves 4-7
 //     produce the Gaussian-head noise; MT = 2: all 512 threads hold state (waves 4-7: the second row tile).
@@ -32,20 +32,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float floatx2 __attribute__((ext_vector_type(2)));
-
-#ifndef CADM_XDL_RING
-#define CADM_XDL_RING 4
-#endif
-// TIMING EXPERIMENTS ONLY (tools/build_variant.sh; wrong results, never in the product build): what a part of the kernel costs.
-//   CADM_XDL_EXPERIMENT_NOBAR   no barriers between the dense layers (an upper bound for any finer-grained layer hand-off)
-//   CADM_XDL_EXPERIMENT_NOMFMA  the sweeps issue no MFMAs (everything else -- streams, LDS traffic, epilogues, state phase -- stays)
-//   CADM_XDL_EXPERIMENT_NOSTREAM the streamed weight fragments are not loaded (the ring keeps stale registers)
-//   CADM_XDL_EXPERIMENT_NOEPI   the hidden tiles' epilogue arithmetic is skipped (stages 0-4: nonlinearity and f16 split; the LDS store stays)
-#ifdef CADM_XDL_EXPERIMENT_NOBAR
-#define XDL_LAYER_SYNC() ((void)0)
-#else
-#define XDL_LAYER_SYNC() __syncthreads()
-#endif
 
 // MT = row tiles (of 16 rows) a workgroup advances together.  2 for large batches: every weight fragment then feeds two sets
 // of MFMAs (half the weight stream, half the barriers and sweep start-ups per row), all 512 threads hold rollout state.
@@ -64,10 +50,7 @@ struct XC {
     // are UNCONDITIONAL -- a dim that feeds fewer than two features writes 0.0 there instead of branching around the write (hipcc turned
     // the guarded writes + the id / sin / cos select into nested exec-mask regions with out-of-line blocks: ~25 control instructions per
     // feature, 300 per step of the wave-tile kernel).  Exists unless K0 is a multiple of 32.
-#ifndef CADM_XDL_SPARE
-#define CADM_XDL_SPARE 1
-#endif
-    static constexpr bool SPARE = CADM_XDL_SPARE && (K0 % 32) != 0;
+    static constexpr bool SPARE = (K0 % 32) != 0;
     static constexpr int NT = (HID + 15) / 16;            // hidden tiles
     // invariant last chunk of layer 0 (xdl_geo.h): accumulated FIRST by every flavour, once per row tile by this kernel (NC0S chunks per step)
     static constexpr bool INV = xdl_inv0(K0, P + A, HID);
@@ -78,7 +61,7 @@ struct XC {
     static constexpr int BASE = NT / NW, EXTRA = NT % NW;
     static constexpr int NTOW = (NTO + NW - 1) / NW;      // head tile slots per wave
     static_assert(NTOW == 1, "one head tile per wave at most (obs dim <= 64)");
-    static constexpr int R = CADM_XDL_RING;               // ring depth (fragments)
+    static constexpr int R = 4;                           // ring depth (fragments)
     // products per 16x16x32 block: hi += w1 x1 + w1 x2, lo += w2 x1 [+ w2 x2] (xdl_geo.h).  The dropped w2 x2 term is 2^-22 of a
     // product; wide layers (K > 256) accumulate enough of them to show at the 1e-5 parity bar, so they take the 4th product.
     static constexpr int NPROD = HID > 256 ? 4 : 3;
@@ -100,10 +83,7 @@ struct XC {
     // thread (row, d) with d = tid / 16 < D owns dim d, the LAST NP of the 32 dim slots make the Gaussian-head noise of one pair
     // each.  The state update is one wave's dependent chain (softplus -> exp -> .. -> f16 split): half the dims per thread halve
     // it, over 4.5 of the 8 waves instead of 2.25.  A row's arithmetic is unchanged (bit-identical to the pair layout).
-#ifndef CADM_XDL_ONED
-#define CADM_XDL_ONED 1
-#endif
-    static constexpr bool ONED = CADM_XDL_ONED && MT == 1 && NPI == 1 && D + NP <= 32 && A <= D;
+    static constexpr bool ONED = MT == 1 && NPI == 1 && D + NP <= 32 && A <= D;
     static constexpr int TABD = 16;                                     // ONED: floats per dim entry
     static constexpr int TAB_BYTES = ONED ? 32 * TABD * 4 : NPI * 16 * TABW * 4;
     // Gaussian-head noise, produced by waves 4-7 while waves 0-3 run the state update: [step parity][pair slot][fg][row] x 2
@@ -113,37 +93,28 @@ struct XC {
     // Bias tiles (fp32, D layout) live in LDS when they fit next to the rest (a bias read from global memory in a tile's
     // epilogue would sit BEHIND the ring's weight loads in the in-order vmcnt queue and drain the whole ring);
     // otherwise they are fetched at the start of a sweep, ahead of that sweep's ring loads.
-#ifndef CADM_XDL_RES
-#define CADM_XDL_RES 1
-#endif
     // register-resident weights (loaded once per workgroup, never re-read from L2): hidden layer 1 on every wave and
     // the head tile on the waves that own BASE hidden tiles -- ~100 of a wave's 256 registers at HID = 200.
-    // RES_FRAGS leaves room for the ring, the accumulators and what hipcc parks in AGPRs itself
+    // res_frags leaves room for the ring, the accumulators and what hipcc parks in AGPRs itself
     // (tests/test_isa_hygiene.py checks the ISA for AGPR<->VGPR shuffles of resident fragments, which would also be an
     // undetected MFMA operand hazard).
-#ifndef CADM_XDL_RES_FRAGS
-#define CADM_XDL_RES_FRAGS 16       // waves with one hidden tile (+ a head tile)
-#endif
-#ifndef CADM_XDL_RES_MT2_LESS
-#define CADM_XDL_RES_MT2_LESS 6     // two row tiles: twice the accumulators, operand registers and rollout state
-#endif
+    static constexpr int RES_1 = 16;         // waves with one hidden tile (+ a head tile)
+    static constexpr int RES_MT2_LESS = 6;   // two row tiles: twice the accumulators, operand registers and rollout state
     // waves with two or more hidden tiles (more accumulators / epilogue state live): 14 until round 5.  Round 6 took the f16-range clamps and
     // the exec-mask regions out of the epilogue and the state phase; what that freed holds one more fragment in every compiled-in geometry
     // (15: all 240 kernels of the library free of scratch and of AGPR copies, tests/test_isa_hygiene.py) and two more in the reference's
     // own geometry (halfcheetah, context 10, hidden 200: 16; the same count spills 2-24 registers in four other geometries).  Same-box:
     // cfg2 153.2 -> 152.2 -> 151.1 us per launch.  Geometries built on demand (jit.py) keep 14: nobody has looked at their code.
-#ifdef CADM_XDL_RES_FRAGS_X
-    static constexpr int RES_X = CADM_XDL_RES_FRAGS_X;
-#elif defined(CADM_JIT_MODULE)
+#ifdef CADM_JIT_MODULE
     static constexpr int RES_X = 14;
 #else
     static constexpr int RES_X = (INV && NPI > 1) ? 14 : 15;      // (the reference's own geometry held 16 until the invariant-chunk prologue took the registers' last slack; wide observations with it: one less)
 #endif
-    static constexpr bool ASM_MFMA = CADM_XDL_RES && NCH <= 8;     // asm MFMAs (AGPR-resident operands) vs builtins
+    static constexpr bool ASM_MFMA = NCH <= 8;     // asm MFMAs (AGPR-resident operands) vs builtins
     static constexpr int res_frags(int ntw) {      // (wide observations keep two pair slots of rollout state per thread)
-        return (!CADM_XDL_RES || NCH > 8) ? 0
-               : MT > 1 ? (ntw >= 2 ? RES_X : CADM_XDL_RES_FRAGS) - (NPI > 1 ? 2 : 0) - CADM_XDL_RES_MT2_LESS - (NT >= 15 ? 1 : 0)
-                        : (ntw >= 2 ? RES_X : CADM_XDL_RES_FRAGS) - (NPI > 1 ? 2 : 0) - (NT >= 15 ? 2 : 0);
+        return NCH > 8 ? 0
+               : MT > 1 ? (ntw >= 2 ? RES_X : RES_1) - (NPI > 1 ? 2 : 0) - RES_MT2_LESS - (NT >= 15 ? 1 : 0)
+                        : (ntw >= 2 ? RES_X : RES_1) - (NPI > 1 ? 2 : 0) - (NT >= 15 ? 2 : 0);
     }
     static constexpr int MAX_NH_LDS = NH_;
     // (a bias tile in D layout repeats each of its 16 values over the tile's 16 data rows: LDS keeps one copy, 64 B per tile)
@@ -154,23 +125,17 @@ struct XC {
     //  fragment: every streamed fragment costs ~0.6 us per launch at cfg2 -- the L2 -> CU weight stream is what the one-tile kernel waits for)
     static constexpr int XDEPTH = 2;                       // B-operand chunks in registers (lookahead XDEPTH - 1)
     // One-tile sweeps (the head tile; the hidden tiles of the waves that own one): a chunk is 3 MFMAs = 48 cycles of this wave's
-    // own work against ~130 cycles of LDS latency, so with one chunk of lookahead the sweep runs at the LDS latency (7 x 130
-    // cycles where the MFMAs need 336) -- and the HEAD sweep is on the step's critical path (every other wave waits for it:
-    // profiles/r4_phase_timing_skeleton.txt).  They keep more operand chunks in flight.
-#ifndef CADM_XDL_XD1
-#define CADM_XDL_XD1 2      // (measured, same box: 3 / 4 chunks +-0, 7 chunks +1 %: the head is not waiting for its operands)
-#endif
-    static constexpr int XDEPTH1 = MT > 1 ? 2 : CADM_XDL_XD1;
+    // own work against ~130 cycles of LDS latency, and the HEAD sweep is on the step's critical path (every other wave waits for it:
+    // profiles/r4_phase_timing_skeleton.txt).  More operand chunks in flight for the head sweep were measured and dropped (same box:
+    // 3 / 4 chunks +-0, 7 chunks +1 %): the head is not waiting for its operands.
     // LDS-resident weight fragments: what is left of the 160 KiB (at horizons <= 128; one row tile per workgroup) holds the LAST
     // LQ_SLOTS fragments of hidden layers 1..3 of every wave with two or more tiles -- the waves a layer waits for.  The one-tile
     // kernel is bound by the L2 -> CU weight stream (every streamed fragment costs ~0.6 us per launch at cfg2).
-#ifndef CADM_XDL_LQ_MAX
-#define CADM_XDL_LQ_MAX 2       // (a third slot measured +-0: the stream is no longer what the layer waits for)
-#endif
+    static constexpr int LQ_MAX = 2;      // (a third slot measured +-0: the stream is no longer what the layer waits for)
     static constexpr int NEL = BASE >= 2 ? NW : EXTRA;                 // waves with >= 2 tiles (waves 0 .. NEL-1)
     static constexpr int INV_BYTES = INV ? MT * NT * CADM_XDL_FRAG_BYTES : 0;      // (HI, LO) of "bias + invariant chunk" per (row tile, tile): 64 lanes x 16 B each
     static constexpr int LQ_FREE = 160 * 1024 - (CTRL + rup(MT * 16 * 128 * 4, 16) + (BIAS_LDS ? BIAS_BYTES : 0)) - INV_BYTES;
-    static constexpr int LQ_SLOTS = (MT > 1 || NEL == 0 || !ASM_MFMA || LQ_FREE <= 0) ? 0 : cmin(CADM_XDL_LQ_MAX, LQ_FREE / (NEL * 3 * CADM_XDL_FRAG_BYTES));
+    static constexpr int LQ_SLOTS = (MT > 1 || NEL == 0 || !ASM_MFMA || LQ_FREE <= 0) ? 0 : cmin(LQ_MAX, LQ_FREE / (NEL * 3 * CADM_XDL_FRAG_BYTES));
     static constexpr int LQ_BYTES = NEL * 3 * LQ_SLOTS * CADM_XDL_FRAG_BYTES;
     static size_t lds_bytes(int H) {                       // dynamic LDS of a launch
         return (size_t)CTRL + (size_t)rup(MT * 16 * H * 4, 16) + (BIAS_LDS ? (size_t)BIAS_BYTES : 0) + LQ_BYTES + INV_BYTES;
@@ -184,12 +149,8 @@ struct XRing {
 
 template <int SLOT, class G>
 __device__ __forceinline__ void xring_load(XRing<G>& ring, __amdgpu_buffer_rsrc_t rsrc, unsigned soff, int lane) {
-#ifdef CADM_XDL_EXPERIMENT_NOSTREAM      // (timing experiment: the L2 -> CU weight stream is not issued; the ring holds whatever it held)
-    asm volatile("" : "+v"(ring.w[SLOT][0]), "+v"(ring.w[SLOT][1]));
-#else
     ring.w[SLOT][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, soff, 0);
     ring.w[SLOT][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16 + 1024, soff, 0);
-#endif
 }
 
 __device__ __forceinline__ floatx4 xmfma(uintx4 a, f16x8 b, floatx4 c) {
@@ -209,11 +170,7 @@ __device__ __forceinline__ void xres_load(uintx4& dst, __amdgpu_buffer_rsrc_t rs
                  : "=a"(dst) : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(soff)) : "memory");
 }
 __device__ __forceinline__ void xmfma_res(floatx4& acc, const uintx4& w, const f16x8& x) {
-#ifdef CADM_XDL_EXPERIMENT_NOMFMA
-    asm volatile("" : "+v"(acc) : "a"(w), "v"(x));
-#else
     asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(x));
-#endif
 }
 // Streamed fragments (ring registers, VGPRs) go through the same asm form so that ALL MFMAs of a sweep keep their
 // accumulators in VGPRs: a mix of asm and builtin MFMAs makes hipcc shuttle accumulators between VGPRs and AGPRs
@@ -227,12 +184,8 @@ __device__ __forceinline__ void xmfma_res(floatx4& acc, const uintx4& w, const f
 // cycles hide behind the SIMD's other wave: measured neutral.
 template <bool ASM>
 __device__ __forceinline__ void xmfma_ring(floatx4& acc, const uintx4& w, const f16x8& x) {
-#ifdef CADM_XDL_EXPERIMENT_NOMFMA
-    asm volatile("" : "+v"(acc) : "v"(w), "v"(x));
-#else
     if constexpr (ASM) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(x));
     else acc = xmfma(w, x, acc);
-#endif
 }
 // Hazard padding the compiler cannot place for asm MFMAs.  The accumulators are "+v" operands of the padding statement,
 // so every instruction that defines them (the zeroing moves) stays before it and every reader (the epilogue) after it.
@@ -268,13 +221,7 @@ __device__ __forceinline__ void xsplit(float v, _Float16& hi, _Float16& lo) {
 // the wave-tile kernel's waves drift apart inside a block, an epilogue meets the partner's MFMAs: scalar, cfg3 -1.8 %; the cooperative
 // kernel's waves run the same phase between the same barriers, the shorter epilogue wins: packed, cfg2 -0.5..1.5 % (same-box A/B,
 // profiles/r5_wave_tile_experiments.md).  The rollout translation units are compiled with -fno-slp-vectorize so hipcc does not re-pack scalars.
-#ifndef CADM_EPI_PACKED_COOP
-#define CADM_EPI_PACKED_COOP 1
-#endif
-#ifndef CADM_EPI_PACKED_WT
-#define CADM_EPI_PACKED_WT 0
-#endif
-template <class G, bool PACKED = CADM_EPI_PACKED_COOP>
+template <class G, bool PACKED = true>      // (packed in the cooperative kernel, scalar in the wave-tile kernel)
 struct XHiddenEpi {
     static constexpr int NSTAGE = 6;
     struct StateP { floatx2 v[2], s[2]; f16x4 h1, h2; };
@@ -301,12 +248,6 @@ struct XHiddenEpi {
     static __device__ __forceinline__ floatx2 hi2(const floatx4& x) { return __builtin_shufflevector(x, x, 2, 3); }
     template <int S>
     __device__ __forceinline__ void stage(int ti, int hh, const floatx4& hi, const floatx4& lo, const floatx4& ll, State& st) const {
-#ifdef CADM_XDL_EXPERIMENT_NOEPI
-        if constexpr (S < 5) {      // (one compare keeps the wait for the accumulators; the stored activations are zeros)
-            if constexpr (S == 0) { const _Float16 z = (_Float16)((hi[0] == 12345.678f && lo[0] == 1.5f) ? 1.0f : 0.0f); st.h1 = f16x4{z, z, z, z}; st.h2 = st.h1; }
-            return;
-        }
-#endif
         constexpr float KE = G::ACT == CADM_ACT_TANH ? -2.0f * 1.4426950408889634f : -1.4426950408889634f;
         constexpr bool SIG = G::ACT != CADM_ACT_RELU && G::ACT != CADM_ACT_NONE;       // nonlinearities built on sigmoid
         if constexpr (PACKED) {
@@ -317,7 +258,7 @@ struct XHiddenEpi {
             for (int q = 0; q < 2; ++q) {
                 const floatx2 pre = __builtin_elementwise_fma(q ? hi2(lo) : lo2(lo), c11, q ? hi2(hi) : lo2(hi));
                 st.v[q] = pre;                 // (no f16-range clamp: the conversions below saturate, fp16_saturate_on)
-                // swish: the packed weights carry log2(e) (xdl_geo.h: CADM_XDL_SWISH_FOLD), pre IS the exp2 argument up to its sign
+                // swish: the packed weights carry log2(e) (xdl_geo.h), pre IS the exp2 argument up to its sign
                 if constexpr (G::ACT == CADM_ACT_SWISH) st.s[q] = -pre;
                 else st.s[q] = pre * ke;
             }
@@ -457,8 +398,7 @@ __device__ __forceinline__ void xdl_sweep(XRing<G>& ring, const uintx4 (*res)[2]
     constexpr int R = G::R, NF = NTW * NCHL, NFS = NF - NRES, NFSPAD = rup(NFS, R);
     static_assert(NRES >= 0 && NRES <= NF, "bad resident fragment count");
     static_assert(NLDS == 0 || NFS - NLDS >= R, "the first R ring fragments of a layer are streamed");
-    constexpr int MT = G::MT, XDW = (NTW == 1 && GS == 1 && !SIDE) ? G::XDEPTH1 : G::XDEPTH,      // (the head sweep)
-                   XD = NCHL < XDW ? NCHL : XDW;
+    constexpr int MT = G::MT, XD = NCHL < G::XDEPTH ? NCHL : G::XDEPTH;
     constexpr int IN_T = 2 * NCB * 1024;                   // bytes of one row tile's operand block (NCB chunks per split part, the first NCHL of them swept)
     f16x8 X1[XD][MT], X2[XD][MT];
     auto xload = [&](auto cc) {
@@ -562,7 +502,7 @@ __device__ __forceinline__ void xdl_sweep(XRing<G>& ring, const uintx4 (*res)[2]
     });
 }
 
-template <class G, int NOISE, int NTW, bool SEQ>
+template <class G, int NOISE, int NTW>
 __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsmem) {
     constexpr int D = G::D, A = G::A, P = G::P, C = G::C, K0 = G::K0, NC0 = G::NC0, NCH = G::NCH, NTO = G::NTO;
     constexpr int NP = G::NP, NPI = G::NPI, NAI = G::NAI, ENV = G::ENV, R = G::R;
@@ -705,7 +645,7 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
     // spare, and the first Q_l fragments of hidden layers l = 1..3 -- spread EVENLY, so that every layer streams about the
     // same number of bytes: the L2 -> CU path (~50 B/clk) is the scarce resource, and a layer that streams nothing
     // leaves it idle while its neighbours wait for it.  The STREAMED part of a layer is the tail of its stream region.
-    constexpr int GSZ = SEQ ? 1 : CADM_XDL_GROUP;                       // tiles per group (xdl_geo.h: xdl_group(wave))
+    constexpr int GSZ = xdl_group();                                    // tiles per group (xdl_geo.h)
     constexpr int NFH = NTW * NCH;                                      // fragments of a hidden layer (this wave)
     constexpr bool RESO = NTW == G::BASE && G::res_frags(NTW) >= NCH + 3;
     constexpr int RREM = G::res_frags(NTW) - (RESO ? NCH : 0);
@@ -1013,10 +953,7 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
             // One row tile: made here by the twin thread in waves 4-7, which have nothing else to do while waves 0-3 update
             // the state.  Two row tiles: every thread owns state and makes its own noise, but not here, where it would
             // lengthen the state phase that everything waits for -- see the hidden layers / the head below.
-#ifndef CADM_XDL_NOISE_IN_HIDDEN
-#define CADM_XDL_NOISE_IN_HIDDEN 0
-#endif
-            if constexpr (NOISE != CADM_NOISE_NONE && MT == 1 && !CADM_XDL_NOISE_IN_HIDDEN) {
+            if constexpr (NOISE != CADM_NOISE_NONE && MT == 1) {
                 if (ONED ? nzt : !feat) gen_noise(t);
             }
             TS(0)
@@ -1033,11 +970,11 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
                     const int nx = next_streamed(0);
                     XHiddenEpi<G> epi0 = hidden_epi(0, act_out);
                     if constexpr (G::INV) epi0.inv = xsmem + inv_off;      // accumulators start from "bias + invariant chunk" (made once per row tile, below the tile prologue)
-                    xdl_sweep<G, NTW, G::NC0S, 0, GSZ, !SEQ, 0, NC0>(ring, nullptr, rsrc, w_l0, lay_off(nx), lay_nf(nx), xsmem + act_in, lane,
+                    xdl_sweep<G, NTW, G::NC0S, 0, GSZ, true, 0, NC0>(ring, nullptr, rsrc, w_l0, lay_off(nx), lay_nf(nx), xsmem + act_in, lane,
                                               epi0, nullptr TS_ARGS);
                 }
                 TS(2)
-                XDL_LAYER_SYNC();
+                __syncthreads();
                 TS(3)
                 if constexpr (ONED && XNH == 1) {      // one hidden layer: no hidden-layer-1 sweep to carry the next step's action features (see actt)
                     if (actt && t + 1 < H) act_put(t + 1);
@@ -1051,21 +988,18 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
                     // (layers 1..3: distinct instantiations with their LDS-resident tail; deeper layers stream everything)
                     constexpr int NL = decltype(lq_c)::value ? LQ : 0;
                     TR_ON(t == 10 && l == 2, wave)      // (CADM_PHASE_TIMING builds: raw stamps of this one sweep, tools/sweep_trace.py)
-                    xdl_sweep<G, NTW, NCH, NRES, GSZ, !SEQ, NL>(ring, resH + RBASE, rsrc, lay_off(l), lay_off(nx), lay_nf(nx), xsmem + act_in, lane,
+                    xdl_sweep<G, NTW, NCH, NRES, GSZ, true, NL>(ring, resH + RBASE, rsrc, lay_off(l), lay_off(nx), lay_nf(nx), xsmem + act_in, lane,
                                                  hidden_epi(l, act_out), xsmem + lq_off + (l - 1) * LQ * CADM_XDL_FRAG_BYTES TS_ARGS);
                     // two row tiles: the waves that have a head tile (and one hidden tile less than the others: they would
                     // wait at this barrier anyway) make their noise now
                     if constexpr (NOISE != CADM_NOISE_NONE && MT > 1) {
                         if (l == 1 && nhead) gen_noise(t);
                     }
-                    if constexpr (NOISE != CADM_NOISE_NONE && MT == 1 && CADM_XDL_NOISE_IN_HIDDEN) {      // (experiment: noise in the one-tile waves' slack)
-                        if (l == CADM_XDL_NOISE_IN_HIDDEN && (ONED ? nzt : !feat)) gen_noise(t);
-                    }
                     if constexpr (ONED) {      // next step's action features (see actt)
                         if (l == 1 && actt && t + 1 < H) act_put(t + 1);
                     }
                     if (l == 1) { TS(4) } else if (l == 2) { TS(8) } else { TS(9) }
-                    XDL_LAYER_SYNC();
+                    __syncthreads();
                     TR_LATE(11)
                     TR_ON(false, 0)
                     TS(5)
@@ -1129,29 +1063,19 @@ __global__ __launch_bounds__(G::NTHR) void rollout_xdl_kernel(const RolloutArgs 
     extern __shared__ __attribute__((aligned(16))) unsigned char xsmem_raw[];
     fp16_saturate_on();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // waves [0, EXTRA) own one hidden tile more than the others: two specialisations of the whole body, chosen per wave
-    // (a scalar branch; every wave executes the same number of barriers)
-    // and waves 4-7 go tile by tile (xdl_geo.h: xdl_group)
-    constexpr int HALF = G::NW / 2;
-    const bool seq = CADM_XDL_SEQ && wave >= HALF;
     // Static issue priority for the second-dispatched wave of every SIMD (waves 4-7): VALU issue between the two waves of a SIMD is
     // arbitrated by priority, then AGE, so the younger wave loses every contested slot and is the last to reach each layer's barrier
     // (profiles/r3_c_phase_timing_cfg3.txt: wave 4).  Measured, same box, interleaved (profiles/r4_s3_experiments.md): two row tiles
     // -1.5 % (1343 -> 1322 us at cfg3), one row tile +-0.3 % (left alone there); priority for the OLDER half instead: +0.5 % / -0.2 %.
-#ifndef CADM_XDL_PRIO
-#define CADM_XDL_PRIO (G::MT > 1 ? 1 : 0)
-#endif
-    if constexpr ((CADM_XDL_PRIO) != 0) {
-        if ((CADM_XDL_PRIO) > 0 ? wave >= HALF : wave < HALF) __builtin_amdgcn_s_setprio((CADM_XDL_PRIO) > 0 ? (CADM_XDL_PRIO) : -(CADM_XDL_PRIO));
+    if constexpr (G::MT > 1) {
+        if (wave >= G::NW / 2) __builtin_amdgcn_s_setprio(1);
     }
+    // waves [0, EXTRA) own one hidden tile more than the others: two specialisations of the whole body, chosen per wave
+    // (a scalar branch; every wave executes the same number of barriers)
     if (wave < G::EXTRA) {
-        if constexpr (G::EXTRA > 0) {
-            if (!seq) xdl_run<G, NOISE, G::BASE + 1, false>(a, xsmem_raw);
-            else if constexpr (CADM_XDL_SEQ && G::EXTRA > HALF) xdl_run<G, NOISE, G::BASE + 1, true>(a, xsmem_raw);
-        }
+        if constexpr (G::EXTRA > 0) xdl_run<G, NOISE, G::BASE + 1>(a, xsmem_raw);
     } else {
-        if (seq) { if constexpr (CADM_XDL_SEQ) xdl_run<G, NOISE, G::BASE, true>(a, xsmem_raw); }
-        else if constexpr (!CADM_XDL_SEQ || G::EXTRA < HALF) xdl_run<G, NOISE, G::BASE, false>(a, xsmem_raw);
+        xdl_run<G, NOISE, G::BASE>(a, xsmem_raw);
     }
 }
 

@@ -179,18 +179,6 @@ typedef __attribute__((address_space(1))) float* gptr;
 __device__ __forceinline__ gcptr as_global(const float* p) { return (gcptr)p; }
 __device__ __forceinline__ gptr as_global(float* p) { return (gptr)p; }
 #define CH_ROWS 16
-#ifndef CADM_Q0_8
-#define CADM_Q0_8 8
-#endif
-#ifndef CADM_Q0_4
-#define CADM_Q0_4 12
-#endif
-#ifndef CADM_Q1_4
-#define CADM_Q1_4 4
-#endif
-#ifndef CADM_Q2_4
-#define CADM_Q2_4 2
-#endif
 // Two flavours of the chain kernel (template parameter NW = waves per workgroup), chosen per launch by the number of work items:
 //   NW = 8  ONE workgroup per CU, two waves per SIMD: one wave's LDS / load / scalar work overlaps the other's MFMAs.  The latency
 //           flavour: a step at the reference's batch size (256 rows x 5 members x 2 nets = 160 work items) is one partial round of the chip.
@@ -978,7 +966,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 3) void chain_kernel(const C
         // input tiles (180 + 60 history columns, 20 + 6) in ONE round trip to HBM; wider tiles loop.  The 4-wave flavour's 84 VGPRs do not
         // hold that: hipcc parks values in AGPRs here -- harmless in front of the first ring load, and only there
         // (tests/test_isa_hygiene.py checks from the first ring load on).
-        constexpr int Q0 = NW == 8 ? CADM_Q0_8 : CADM_Q0_4, Q1 = NW == 8 ? 4 : CADM_Q1_4, Q2 = NW == 8 ? 2 : CADM_Q2_4;
+        constexpr int Q0 = NW == 8 ? 8 : 12, Q1 = 4, Q2 = 2;
         ChainIn<Q0> q0;
         ChainIn<Q1> q1;
         ChainIn<Q2> q2, q3;
@@ -1066,9 +1054,6 @@ static_assert(sizeof(DwArgs) <= 4096, "kernel argument block");
 #define TK 32
 #define LDA (TM + 4)
 #define LDB (TN + 4)
-#ifndef CADM_DW_EXPERIMENT
-#define CADM_DW_EXPERIMENT 0
-#endif
 #define DW_NSLAB 1                   // slabs per K panel in flight (registers): one keeps the kernel at 120 VGPRs = 4 workgroups per CU
 
 // One 48 x 64 tile of one job per workgroup, reduction over the batch: the whole step's ~925 tiles then fit the chip's
@@ -1174,7 +1159,6 @@ __global__ __launch_bounds__(256) void dw_adam_kernel(const DwArgs a) {
     const int Mq = (M + 3) & ~3, Nq = (N + 3) & ~3;
     const bool vec = KP > 0 && (K % TK) == 0 && ((jb.ldx | jb.ldz) & 3) == 0 && Mq <= jb.ldx && Nq <= jb.ldz &&
                      ((reinterpret_cast<size_t>(jb.X) | reinterpret_cast<size_t>(jb.dZ) | reinterpret_cast<size_t>(jb.dZ2)) & 15) == 0;
-#ifndef CADM_DW_NO_DMA
     // Slabs by LDS-DMA (one gradient source; the jobs that add a second one on load keep the register path below): a slab goes
     // global -> LDS in 16 buffer_load_dwordx4 .. lds of the workgroup (4 per wave: 4 batch rows x 12 / 16 quads each), no registers, no
     // ds_write, in the tensors' own [row][feature] order; operands are then single dwords (lane (c, q): feature c of row q of a 4-row
@@ -1240,9 +1224,6 @@ __global__ __launch_bounds__(256) void dw_adam_kernel(const DwArgs a) {
         }
     }
     if (vec && !dma) {
-#else
-    if (vec) {
-#endif
         float* const At = dw_smem;
         float* const Bt = dw_smem + TM * LDK;
         const int c = lane & 15, q = lane >> 4;
@@ -1275,9 +1256,6 @@ __global__ __launch_bounds__(256) void dw_adam_kernel(const DwArgs a) {
         // reads of slab s - 1.  (Single-buffered until round 5: two barriers per 24 MFMAs.)
         auto slab = [&](Slab& d, int k0, int par) {
             const int bo = par * DW_SLAB;
-#if CADM_DW_EXPERIMENT == 3      // (timing experiments, tools/build_variant.sh: what a part of the slab loop costs -- results are wrong)
-            if (k0 < 2 * TK)
-#endif
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 wA0[bo + j * LDK] = d.a0[j];
@@ -1286,9 +1264,7 @@ __global__ __launch_bounds__(256) void dw_adam_kernel(const DwArgs a) {
                 wB1[bo + j * LDK] = two ? d.b1[j] + d.c1[j] : d.b1[j];
             }
             __syncthreads();
-#if CADM_DW_EXPERIMENT != 2
             if (k0 + 2 * TK < KP) fetch(d);
-#endif
             if (do_colsum) {
 #pragma unroll
                 for (int x = 0; x < TK / 4; ++x) {
@@ -1306,12 +1282,8 @@ __global__ __launch_bounds__(256) void dw_adam_kernel(const DwArgs a) {
                         if (mb + 16 * i >= M) continue;
                         const int fa = 16 * i + c;
                         const floatx4 a4 = *reinterpret_cast<const floatx4*>(At + bo + fa * LDK + 4 * ((4 * g + q) ^ ((fa >> 2) & 7)));
-#if CADM_DW_EXPERIMENT == 1
-                        acc[i] += a4 * b4;
-#else
 #pragma unroll
                         for (int u = 0; u < 4; ++u) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[u], b4[u], acc[i], 0, 0, 0);
-#endif
                     }
                 }
             }

@@ -19,22 +19,12 @@
 //     tiles); head tiles (8 obs dims: mu0 mu1 lv0 lv1 per lane) go to the waves with the fewest hidden tiles first.
 //   * A "fragment" = one (tile, chunk) of weights = 2 split parts x 64 lanes x 16 B = 2 KB.  Per (member, wave) the
 //     stream stores the fragments in EXACTLY the order that wave consumes them during one rollout step:
-//     [layer 0][hidden 1 .. NH-1][head]; inside a layer tiles go in groups of xdl_group(wave), chunk-major inside a group
+//     [layer 0][hidden 1 .. NH-1][head]; inside a layer tiles go in groups of xdl_group(), chunk-major inside a group
 //     (xdl_frag_index), so the kernel addresses the stream linearly.
 #pragma once
 
 #define CADM_XDL_FRAG_BYTES 2048
 #define CADM_XDL_LOG2E 1.4426950408889634f
-// Tiles a wave accumulates at a time.  Waves 0-3 (the first wave of each SIMD) take their tiles two at a time and run
-// the epilogues at the end; waves 4-7 go tile by tile, each tile's epilogue right behind its MFMAs.  The two waves of a
-// SIMD are thereby out of phase: one wave's epilogue (VALU) meets the other's MFMAs instead of its epilogue
-// (a 16-cycle f16 MFMA hides only ~1 VALU op of its own wave, profiles/r2_issue_microbench.md).
-#ifndef CADM_XDL_GROUP
-#define CADM_XDL_GROUP 2
-#endif
-#ifndef CADM_XDL_SEQ
-#define CADM_XDL_SEQ 0                // measured: 211 vs 203 us per launch at cfg2 -- off
-#endif
 #define CADM_XDL_WAVES 8          // two waves per SIMD: one wave's waits (LDS, L2, epilogue chains) hide behind the other's MFMAs
 
 // Narrow nets: the 8-wave tile split needs at least 8 hidden tiles (113 units).  A narrower net (the reference accepts any
@@ -53,11 +43,8 @@ __host__ __device__ constexpr int xdl_kernel_hid(int hid) { return hid < CADM_XD
 // instructions on the same operands in the same order as a flavour that runs the chunk in every step (the wave-tile kernel): bit-identical.
 // Stream of the cooperative kernels: layer 0 holds NC0 - 1 chunks per tile; the invariant chunk's fragments (one per tile) follow the head's.
 // A timing build on a vanilla model (K0 = 24: one chunk): cfg2 152.8 -> 144.9 us per rollout (tools/ctx_fold_bound.py).
-#ifndef CADM_XDL_INV0
-#define CADM_XDL_INV0 1
-#endif
 __host__ __device__ constexpr bool xdl_inv0(int k0, int kdyn, int hid_kernel) {      // kdyn = P + A: the inputs that change from step to step
-    return CADM_XDL_INV0 && k0 > kdyn && (k0 + 31) / 32 >= 2 && ((k0 + 31) / 32 - 1) * 32 >= kdyn && (hid_kernel + 15) / 16 <= 13;
+    return k0 > kdyn && (k0 + 31) / 32 >= 2 && ((k0 + 31) / 32 - 1) * 32 >= kdyn && (hid_kernel + 15) / 16 <= 13;
 }
 
 struct XdlGeo {
@@ -98,7 +85,10 @@ inline XdlGeo make_xdl_geo(int K0, int hid_model, int D, int NH, int nw = CADM_X
     return g;
 }
 
-__host__ __device__ constexpr int xdl_group(int w) { return (CADM_XDL_SEQ && w >= CADM_XDL_WAVES / 2) ? 1 : CADM_XDL_GROUP; }
+// Tiles a wave accumulates at a time: every wave takes its tiles two at a time, and a group's epilogue runs stage by stage between the
+// MFMAs of the next group (rollout_xdl.h: xdl_sweep).  Measured and dropped: the second wave of each SIMD going tile by tile, each tile's
+// epilogue right behind its MFMAs, to put the two waves out of phase (211 against 203 us per launch at cfg2).
+__host__ __device__ constexpr int xdl_group() { return 2; }
 
 // position of fragment (local tile ti, chunk c) in a layer's consumption order, for a wave with ntw tiles taken in
 // groups of gsz: chunk-major inside a group
@@ -111,9 +101,9 @@ __host__ __device__ constexpr int xdl_frag_index(int ntw, int nchl, int ti, int 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The launcher's plan (rollout_xdl.h: xdl_launch): how a member's row tiles are cut between the kernel flavours.
 //   flavour 0: cooperative kernel, one row tile per workgroup   cap 1 unit   cost 1
-//           1: cooperative kernel, two row tiles per workgroup  cap 2        CADM_COST_MT2
-//           2: wave-tile kernel, 4 tiles per workgroup           cap 4        CADM_COST_WT4   (one wave per SIMD: never wins, exists for the tests)
-//           3: wave-tile kernel, 8 tiles per workgroup           cap 8        CADM_COST_WT8   (per round)
+//           1: cooperative kernel, two row tiles per workgroup  cap 2        xdl_costs(..).c[1]
+//           2: wave-tile kernel, 4 tiles per workgroup           cap 4        .c[2]   (one wave per SIMD: never wins, exists for the tests)
+//           3: wave-tile kernel, 8 tiles per workgroup           cap 8        .c[3]   (per round)
 // 1 unit = one CU share of the member (n_cus / E tiles); costs in units of the one-tile launch (halfcheetah at the cfg2 / cfg3 geometry,
 // 51 workgroups per member: 165 / 261 / 600 / 876 us, profiles/r4_s3_flavour_table.txt).  The cheapest cover is a small
 // dynamic programme, f(u) = min over flavours (cost + f(u - cap)); count[o] = launches (rounds) of flavour o.
@@ -125,24 +115,11 @@ __host__ __device__ constexpr int xdl_frag_index(int ntw, int nchl, int ti, int 
 // A wave-tile round that is NOT full is cheaper than a full one -- its workgroups run 5, 6 or 7 waves instead of 8 (wt_launch gives a
 // partly filled round the member's whole CU share): wt8p[k - 5] = cost of a round that covers k = 5, 6, 7 units (halfcheetah 735.6 /
 // 741.8 / 794.0 us: 4.48 / 4.52 / 4.84; at 6 units one partial round beats three two-tile launches, 741.8 against 776.9 us).
-// Geometries nobody measured use halfcheetah's.  -DCADM_COST_MT2=.. etc. override every instantiation (tools/build_variant.sh experiments).
+// Geometries nobody measured use halfcheetah's.
 struct XdlCosts { float c[4]; float wt8p[3]; };
 __host__ __device__ constexpr XdlCosts xdl_costs(int env_kind, int hid) {
-#if defined(CADM_COST_MT2) || defined(CADM_COST_WT4) || defined(CADM_COST_WT8)
-#ifndef CADM_COST_MT2
-#define CADM_COST_MT2 1.6f
-#endif
-#ifndef CADM_COST_WT4
-#define CADM_COST_WT4 3.6f
-#endif
-#ifndef CADM_COST_WT8
-#define CADM_COST_WT8 5.3f
-#endif
-    return XdlCosts{{1.0f, CADM_COST_MT2, CADM_COST_WT4, CADM_COST_WT8}, {CADM_COST_WT8, CADM_COST_WT8, CADM_COST_WT8}};
-#else
     return env_kind == 2 /* CADM_ENV_SLIM_HUMANOID */ ? XdlCosts{{1.0f, 1.62f, 3.62f, 5.5f}, {4.78f, 4.80f, 5.15f}}
                                                       : XdlCosts{{1.0f, 1.59f, 3.2f, 5.19f}, {4.48f, 4.52f, 4.84f}};
-#endif
 }
 inline void xdl_plan_units(int units, bool mt2_ok, bool wt_ok, int (&count)[4], XdlCosts costs = xdl_costs(0, 200)) {
     const int capu[4] = {1, mt2_ok ? 2 : 0, wt_ok ? 4 : 0, wt_ok ? 8 : 0};

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Build an experimental variant of the DEVELOPER library next to the tree's own build (for tools/ab.sh / tools/compare_libs.py):
+# Build another configuration of the DEVELOPER library next to the tree's own build: extra compiler flags (-DCADM_DW_TIMING for
+# tools/chain_timing.py) and / or other instantiated hidden / context widths (narrow HIDS builds for tools/fuzz_rollout.py):
 #   tools/build_variant.sh NAME "-DFLAG=.." [HIDS] [CTXS]   ->  cadm_amd/libcadm_hip_var_NAME.so
 # The sources are copied to /tmp so the tree's objects stay those of the product build.
 set -e

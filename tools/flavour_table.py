@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Rollout time by kernel flavour and batch size, in units of one CU share (51 tiles per member at E = 5, 256 CUs): the table the
-launcher's plan costs (CADM_COST_*, rollout_xdl.h: xdl_launch) were read from.   python tools/flavour_table.py [max_units]"""
+launcher's plan costs (xdl_geo.h: xdl_costs) were read from.   python tools/flavour_table.py [max_units]"""
 import os
 import sys
 
@@ -12,7 +12,7 @@ from cadm_amd import _lib, synth
 
 cfg = dict(synth.CONFIGS["cfg2"])
 maxu = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-libp = os.path.join(ROOT, "cadm_amd", sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2] != "-" else None      # (a variant build, tools/build_variant.sh)
+libp = os.path.join(ROOT, "cadm_amd", sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2] != "-" else None      # (another build of the developer library, tools/build_variant.sh)
 ENV = sys.argv[3] if len(sys.argv) > 3 else cfg["env"]      # python tools/flavour_table.py 6 - slim_humanoid
 HID = int(sys.argv[4]) if len(sys.argv) > 4 else 200
 prob = synth.make_problem(env=ENV, context=cfg["context"], E=cfg["E"], m=1, H=cfg["H"], seed=0, hidden_sizes=(HID,) * 4)

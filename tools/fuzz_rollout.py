@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised differential test of the rollout kernels (developer tool; needs a GPU):  python tools/fuzz_rollout.py [seconds] [seed] [variant library]
+"""Randomised differential test of the rollout kernels (developer tool; needs a GPU):  python tools/fuzz_rollout.py [seconds] [seed] [library]
 
 Every round draws a random problem (env kind, context / vanilla, hidden width, ensemble size, particles, candidates, batch of
 envs m, horizon, noise mode, CEM iteration parity) and checks
@@ -109,7 +109,7 @@ def fuzz(seconds=60.0, seed=0, hids=(128, 200, 200, 256, 512), lib_path=None):
 
 
 def main():
-    # (argv[3]: a variant build of the developer library, tools/build_variant.sh -- built for HID 200 only unless told otherwise)
+    # (argv[3]: another build of the developer library, tools/build_variant.sh -- built for HID 200 only unless told otherwise)
     lib_path = os.path.join(ROOT, "cadm_amd", sys.argv[3]) if len(sys.argv) > 3 else None
     rounds, worst = fuzz(float(sys.argv[1]) if len(sys.argv) > 1 else 60.0, int(sys.argv[2]) if len(sys.argv) > 2 else 0,
                          hids=(200,) if lib_path else (128, 200, 200, 256, 512), lib_path=lib_path)

@@ -26,7 +26,7 @@ def main():
     cfg = synth.CONFIGS[cfgname]
     prob = synth.make_problem(env=cfg["env"], context=cfg["context"], E=cfg["E"], m=1, H=cfg["H"], seed=0)
     f32 = len(sys.argv) > 2 and sys.argv[2] == "f32"
-    libname = sys.argv[3] if len(sys.argv) > 3 else "libcadm_hip_timing.so"      # (a CADM_PHASE_TIMING build of an experiment variant)
+    libname = sys.argv[3] if len(sys.argv) > 3 else "libcadm_hip_timing.so"      # (another CADM_PHASE_TIMING build, relative to cadm_amd/)
     eng = make_engine(prob, p=cfg["p"], deterministic=cfg["deterministic"], lib=_lib.load_dev(os.path.join(ROOT, "cadm_amd", libname)))
     if f32:
         eng.dev_set_rollout("f32")

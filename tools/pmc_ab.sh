@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (on GPU box): pmc_ab.sh cfg lib...   -> icache / wait counters of the rollout kernel per library
+# usage (on GPU box): pmc_ab.sh cfg lib...   -> icache / wait counters of the rollout kernel per library (paths relative to cadm_amd/)
 export TMPDIR=/tmp
 ROOT=$PWD
 CFG=$1; shift
@@ -8,7 +8,7 @@ for lib in "$@"; do
     n=$(echo $grp | cut -c1-12)
     out=/tmp/pmc_${lib}_$n
     rm -rf $out
-    (cd /tmp && rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $out -- python $ROOT/tools/variant_time.py $CFG $lib > /dev/null 2> $out.err)
+    (cd /tmp && rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $out -- python $ROOT/bench.py --config $CFG --steps 20 --lib $ROOT/cadm_amd/$lib > /dev/null 2> $out.err)
     python - <<PY
 import csv,glob
 acc={};cnt={}
