@@ -19,6 +19,8 @@ MAX_CP_LAYERS = 8
 
 ENV_KINDS = {"halfcheetah": 0, "cripple_halfcheetah": 0, "ant": 1, "slim_humanoid": 2,
              "cartpole": 3, "pendulum": 4}
+ENV_SPEC = 5              # CADM_ENV_SPEC: a user-declared env (cadm_amd/env_spec.py EnvDecl)
+SPEC_MAX_D, SPEC_MAX_TERMS = 48, 32
 NET_FF, NET_BACK, NET_CTX = 0, 1, 2
 # hidden nonlinearity codes (include/cadm_hip.h CADM_ACT_*; the reference's `_activations`, dynamics.py:17-24)
 ACT_KINDS = {"swish": 0, "relu": 1, "tanh": 2, "sigmoid": 3, None: 4}
@@ -43,6 +45,16 @@ class Config(C.Structure):
     ]
 
 
+class EnvSpecC(C.Structure):          # include/cadm_hip.h cadm_env_spec
+    _fields_ = [
+        ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("proc_obs_dim", C.c_int32),
+        ("preproc", C.c_int32 * SPEC_MAX_D), ("postproc", C.c_int32 * SPEC_MAX_D), ("n_terms", C.c_int32),
+        ("term_kind", C.c_int32 * SPEC_MAX_TERMS), ("term_dim", C.c_int32 * SPEC_MAX_TERMS), ("term_when", C.c_int32 * SPEC_MAX_TERMS),
+        ("term_w", C.c_float * SPEC_MAX_TERMS), ("term_lo", C.c_float * SPEC_MAX_TERMS), ("term_hi", C.c_float * SPEC_MAX_TERMS),
+        ("ctrl_cost", C.c_float), ("bonus", C.c_float), ("hash_lo", C.c_uint32), ("hash_hi", C.c_uint32),
+    ]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -62,6 +74,7 @@ SIGNATURES = {
     "cadm_build_id": (C.c_char_p, []),
     "cadm_ctx_create": (_i, [C.POINTER(Config), C.POINTER(_P)]),
     "cadm_ctx_destroy": (_i, [_P]),
+    "cadm_set_env_spec": (_i, [_P, C.POINTER(EnvSpecC)]),
     "cadm_set_weights": (_i, [_P, _i, _i, _P, _P]),
     "cadm_set_logvar_bounds": (_i, [_P, _i, _P, _P]),
     "cadm_repack": (_i, [_P, _P]),

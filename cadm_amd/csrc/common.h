@@ -27,7 +27,7 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_HID_LIST 200              // the reference default --hidden_size (run_cadm_pets.py:129)
 #endif
 // bumped whenever cadm_ctx / RolloutArgs change: a side module built against another layout is refused
-#define CADM_CTX_LAYOUT_TAG 3004
+#define CADM_CTX_LAYOUT_TAG 3005
 
 #define CADM_CHECK_HIP(expr)                                                                   \
     do {                                                                                       \
@@ -49,9 +49,19 @@ void cadm_set_error(const char* fmt, ...);
 // ---------------------------------------------------------------------------------------------
 // env tables
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ constexpr int env_D(int k) { return k == 0 ? 18 : k == 1 ? 28 : k == 2 ? 45 : k == 3 ? 4 : 3; }
-__host__ __device__ constexpr int env_A(int k) { return k == 0 ? 6 : k == 1 ? 8 : k == 2 ? 17 : k == 3 ? 2 : 1; }
-__host__ __device__ constexpr int env_P(int k) { return k == 0 ? 18 : k == 1 ? 27 : k == 2 ? 45 : k == 3 ? 4 : 3; }
+// CADM_ENV_SPEC: a side module built for one user-declared env carries its dims as compile-time constants (the generated
+// cadm_spec_tables.h, cadm_amd/jit.py); the library takes them from the ctx config (cadm_ctx_create) and never instantiates a kernel
+// for the spec kind.
+#ifdef CADM_JIT_SPEC
+#include "cadm_spec_tables.h"
+#else
+#define CADM_SPEC_D 0
+#define CADM_SPEC_A 0
+#define CADM_SPEC_P 0
+#endif
+__host__ __device__ constexpr int env_D(int k) { return k == CADM_ENV_SPEC ? CADM_SPEC_D : k == 0 ? 18 : k == 1 ? 28 : k == 2 ? 45 : k == 3 ? 4 : 3; }
+__host__ __device__ constexpr int env_A(int k) { return k == CADM_ENV_SPEC ? CADM_SPEC_A : k == 0 ? 6 : k == 1 ? 8 : k == 2 ? 17 : k == 3 ? 2 : 1; }
+__host__ __device__ constexpr int env_P(int k) { return k == CADM_ENV_SPEC ? CADM_SPEC_P : k == 0 ? 18 : k == 1 ? 27 : k == 2 ? 45 : k == 3 ? 4 : 3; }
 
 // RNG stream tags (oracle/philox.py)
 #define CADM_STREAM_EPS 1u
@@ -160,6 +170,11 @@ struct cadm_ctx {
     // second packed copy of the planner weights for the wave-tile kernel (rollout_wt.h): ONE consumption order for every wave
     XdlGeo xg1;
     unsigned short* xw1 = nullptr;  // [E][member_frags of xg1] fragments of 2 KB
+    // CADM_ENV_SPEC (cadm_set_env_spec): the declared tables, and per preprocessed feature f its source obs dim | op << 8 (op 0 id,
+    // 1 sin, 2 cos) on the device -- what the training / prediction input assembly reads (train.hip)
+    cadm_env_spec spec{};
+    bool spec_set = false;
+    int* spec_feat = nullptr;
 };
 
 // Entry points launch on the ctx's device whatever device the caller's thread has current (two engines on different GPUs in

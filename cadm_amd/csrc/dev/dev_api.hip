@@ -40,6 +40,7 @@ static int rollout_f32(cadm_ctx* ctx, const RolloutArgs& a0, int rpm, hipStream_
         case CADM_ENV_CARTPOLE: return cadm_rollout_f32_env_cartpole(ctx, a, rpm, s);
         case CADM_ENV_PENDULUM: return cadm_rollout_f32_env_pendulum(ctx, a, rpm, s);
     }
+    cadm_set_error("fp32 comparison rollout: env kind %d not compiled in (built-in kinds only)", ctx->cfg.env_kind);
     return CADM_EINVAL;
 }
 

@@ -53,16 +53,20 @@ int cadm_launch_rollout(cadm_ctx* ctx, const float* obs, const float* obs_rows, 
         case CADM_ENV_SLIM_HUMANOID: return cadm_rollout_env_slim_humanoid(ctx, a, rpm, s);
         case CADM_ENV_CARTPOLE: return cadm_rollout_env_cartpole(ctx, a, rpm, s);
         case CADM_ENV_PENDULUM: return cadm_rollout_env_pendulum(ctx, a, rpm, s);
+        case CADM_ENV_SPEC:
+            cadm_set_error("rollout: a user-declared env (CADM_ENV_SPEC) has no kernel in the library; cadm_amd.jit builds one for its spec "
+                           "(cadm_register_rollout)");
+            return CADM_ENOTBUILT;
     }
     cadm_set_error("rollout: unknown env kind %d", ctx->cfg.env_kind);
     return CADM_EINVAL;
 }
 
-// 1 if the library carries a kernel for the ctx's geometry (rollout_dispatch.h: HIDS x CTXS, 4 hidden layers, swish)
+// 1 if the library carries a kernel for the ctx's geometry (rollout_dispatch.h: HIDS x CTXS, 4 hidden layers, swish; never for a spec env)
 int cadm_rollout_builtin_env(cadm_ctx* ctx) {
     static const int hids[] = {CADM_HID_LIST};
     static const int ctxs[] = {CADM_CTX_LIST};
-    if (ctx->NH != 4 || ctx->cfg.hidden_act != CADM_ACT_SWISH) return 0;
+    if (ctx->cfg.env_kind == CADM_ENV_SPEC || ctx->NH != 4 || ctx->cfg.hidden_act != CADM_ACT_SWISH) return 0;
     bool h = false, c = false;
     for (int v : hids) h = h || v == ctx->xg.HID;      // the kernel's width (narrow nets run zero-padded on 128: xdl_geo.h)
     for (int v : ctxs) c = c || v == ctx->C;

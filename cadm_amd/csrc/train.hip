@@ -131,6 +131,7 @@ struct ChainAsm {         // raw batch -> normalised network inputs
     const float *act, *cp_obs, *cp_act;
     const float *obs_mean, *obs_std, *act_mean, *act_std, *cp_obs_mean, *cp_obs_std, *cp_act_mean, *cp_act_std;
     int D, A, P, ncpo, ncpa, env;
+    const int* spec_feat;     // CADM_ENV_SPEC: per feature, source obs dim | op << 8 (cadm_set_env_spec); else null
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -655,6 +656,7 @@ struct ChainInSrc {
     gcptr x0, a0, b0;
     int hc;                   // half-cheetah obs_preproc (columns 0..2 <- o[1], sin o[2], cos o[2])
     int shift;                // ant obs_preproc: column f <- o[f + 1]
+    const int* sf;            // env spec: column f <- op(o[sf[f] & 255]), op = sf[f] >> 8 (0 id, 1 sin, 2 cos)
     bool rok, two;
     long grow;
 };
@@ -665,7 +667,7 @@ __device__ __forceinline__ ChainInSrc chain_input_src(const ChainLoad& d, const 
     r.grow = (long)e * B + (r.rok ? row : 0);
     long srow = r.grow, swin = r.grow;
     if (d.mode) map_row(ap.map, r.grow, srow, swin);
-    r.hc = 0; r.shift = 0; r.two = false;
+    r.hc = 0; r.shift = 0; r.sf = nullptr; r.two = false;
     if (d.mode == 0) {
         r.x0 = as_global(d.g0) + r.grow * d.ld_in;
         r.two = d.g1 != nullptr;
@@ -675,6 +677,7 @@ __device__ __forceinline__ ChainInSrc chain_input_src(const ChainLoad& d, const 
         r.x0 = as_global(d.g0) + srow * ap.D; r.a0 = as_global(ap.obs_mean); r.b0 = as_global(ap.obs_std);
         r.hc = ap.env == CADM_ENV_HALFCHEETAH;
         r.shift = ap.env == CADM_ENV_ANT;
+        r.sf = ap.spec_feat;
     } else if (d.mode == 2) {          // action columns
         r.x0 = as_global(ap.act) + srow * ap.A; r.a0 = as_global(ap.act_mean); r.b0 = as_global(ap.act_std);
     } else if (d.mode == 3) {          // context encoder: observation history
@@ -691,7 +694,7 @@ __device__ __forceinline__ void chain_input_fetch(const ChainLoad& d, const Chai
         const int idx = base + u * NT + tid;
         const int k = (idx >> 8) * 16 + (idx & 15);
         const int j = k < d.K ? k : 0;
-        const int jx = r.hc ? (j == 0 ? 1 : j <= 2 ? 2 : j) : j + r.shift;     // preproc_at's source column
+        const int jx = r.sf ? (r.sf[j] & 255) : r.hc ? (j == 0 ? 1 : j <= 2 ? 2 : j) : j + r.shift;     // preproc_at's source column
         q.x[u] = r.x0[jx];
         q.a[u] = r.a0[j];
     }
@@ -723,6 +726,11 @@ __device__ __forceinline__ void chain_input_commit(const ChainLoad& d, const Cha
             if (u == 0 && r.hc && base == 0) {              // (columns 1 and 2 only exist in a thread's first element; hc: mode 1)
                 if (k == 1) t = sinf(t);
                 else if (k == 2) t = cosf(t);
+            }
+            if (r.sf) {                                     // env spec (mode 1): the same sinf / cosf as the half-cheetah path
+                const int op = r.sf[k < d.K ? k : 0] >> 8;
+                if (op == 1) t = sinf(t);
+                else if (op == 2) t = cosf(t);
             }
             x = (t - q.a[u]) / (sd[u] + 1e-10f);
         }
@@ -1984,6 +1992,11 @@ int forward_nets(cadm_ctx* ctx, const RowMap& map, const float* obs, const float
     ap.D = D; ap.A = ctx->A; ap.P = ctx->P;
     ap.ncpo = D * ctx->cfg.history_length; ap.ncpa = ctx->A * ctx->cfg.history_length;
     ap.env = ctx->cfg.env_kind;
+    if (ap.env == CADM_ENV_SPEC && !ctx->spec_set) {
+        cadm_set_error("training / prediction on a CADM_ENV_SPEC ctx needs its tables first (cadm_set_env_spec)");
+        return CADM_ESTATE;
+    }
+    ap.spec_feat = ap.env == CADM_ENV_SPEC ? ctx->spec_feat : nullptr;
     for (int i = 0; i < t->npre[PROG_FWD_FF]; ++i) if (t->pre[PROG_FWD_FF][i].mode == 1) t->pre[PROG_FWD_FF][i].g0 = obs;
     for (int i = 0; i < t->npre[PROG_FWD_BK]; ++i) if (t->pre[PROG_FWD_BK][i].mode == 1) t->pre[PROG_FWD_BK][i].g0 = obs_next;
     for (int i = 0; i < t->npre[PROG_FWD_BK_NOCP]; ++i) if (t->pre[PROG_FWD_BK_NOCP][i].mode == 1) t->pre[PROG_FWD_BK_NOCP][i].g0 = obs_next;

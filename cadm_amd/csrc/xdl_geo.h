@@ -115,7 +115,7 @@ __host__ __device__ constexpr int xdl_frag_index(int ntw, int nchl, int ti, int 
 // A wave-tile round that is NOT full is cheaper than a full one -- its workgroups run 5, 6 or 7 waves instead of 8 (wt_launch gives a
 // partly filled round the member's whole CU share): wt8p[k - 5] = cost of a round that covers k = 5, 6, 7 units (halfcheetah 735.6 /
 // 741.8 / 794.0 us: 4.48 / 4.52 / 4.84; at 6 units one partial round beats three two-tile launches, 741.8 against 776.9 us).
-// Geometries nobody measured use halfcheetah's.
+// Geometries nobody measured use halfcheetah's, user-declared envs (CADM_ENV_SPEC) included.
 struct XdlCosts { float c[4]; float wt8p[3]; };
 __host__ __device__ constexpr XdlCosts xdl_costs(int env_kind, int hid) {
     return env_kind == 2 /* CADM_ENV_SLIM_HUMANOID */ ? XdlCosts{{1.0f, 1.62f, 3.62f, 5.5f}, {4.78f, 4.80f, 5.15f}}

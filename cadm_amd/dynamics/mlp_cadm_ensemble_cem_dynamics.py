@@ -10,7 +10,8 @@ handling (dataset growth, float64 statistics, bootstrap indices, early stopping)
 
 Differences a caller can see (all opt-in except the first):
   * `env` may be a reference env object, a NormalizedEnv wrapper or a cadm_amd.envs.EnvSpec;
-    its class selects the compiled-in closures (cadm_amd/envs.py);
+    its class selects the compiled-in closures (cadm_amd/envs.py) -- or any env that declares its closures as a
+    cadm_amd.env_spec.EnvDecl in a `cadm_env_spec` attribute (the rollout kernel is then built for that spec);
   * extra kwargs: `reference_quirks` (default True: reproduce the context-layout quirks Q1/Q2
     of core/utils.py:434-435), `seed` (device Philox key; the reference never seeds TF),
     `device`, `process_group` (OPT-IN: shard candidates over the ranks of that torch.distributed group; every

@@ -73,6 +73,14 @@ class HipEngine:
         if self._padded and hidden_nonlinearity == "sigmoid":
             raise NotImplementedError("unequal hidden_sizes %r with hidden_nonlinearity='sigmoid': zero-padded units would train "
                                       "(sigmoid(0) != 0); use equal widths or swish / relu / tanh / None" % (hs,))
+        # env_kind: a built-in kind name, or a user-declared env (env_spec.EnvDecl) whose closures the rollout module is built from
+        from .env_spec import EnvDecl
+        self.spec = env_kind if isinstance(env_kind, EnvDecl) else None
+        if self.spec is not None and (D, A, P) != (self.spec.obs_dim, self.spec.act_dim, self.spec.proc_obs_dim):
+            raise ValueError("env spec dims (D=%d, A=%d, P=%d) differ from the model's (D=%d, A=%d, P=%d)"
+                             % (self.spec.obs_dim, self.spec.act_dim, self.spec.proc_obs_dim, D, A, P))
+        if self.spec is not None and discrete:
+            raise ValueError("env specs declare continuous actions only")
         self.env_kind, self.E, self.p, self.D, self.A, self.P, self.C = env_kind, E, p, D, A, P, C
         self.H, self.NH, self.HID = H, len(hs), max(hs)
         self.Hh = history_length
@@ -86,7 +94,11 @@ class HipEngine:
         self._rollout_ready = set()
         cfg = Config()
         cfg.abi_version = _lib.ABI_VERSION
-        cfg.env_kind = _lib.ENV_KINDS[env_kind]
+        if self.spec is not None:
+            cfg.env_kind = _lib.ENV_SPEC
+            cfg.reserved[0], cfg.reserved[1] = self.spec.hash_words
+        else:
+            cfg.env_kind = _lib.ENV_KINDS[env_kind]
         cfg.ensemble_size, cfg.n_particles = E, p
         cfg.obs_dim, cfg.act_dim, cfg.proc_obs_dim, cfg.context_dim = D, A, P, C
         cfg.n_hidden, cfg.hidden, cfg.horizon = self.NH, self.HID, H
@@ -105,6 +117,9 @@ class HipEngine:
         self._ctx = C_void_p()
         with torch.cuda.device(self.device):
             self._check(self.lib.cadm_ctx_create(ct.byref(cfg), ct.byref(self._ctx)), "cadm_ctx_create")
+            if self.spec is not None:
+                self._spec_c = self.spec.to_c()
+                self._check(self.lib.cadm_set_env_spec(self._ctx, ct.byref(self._spec_c)), "cadm_set_env_spec")
         self.nets = OrderedDict()   # net name -> OrderedDict(param name -> tensor)
         self._ws = None
         self._ws_key = None

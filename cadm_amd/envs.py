@@ -5,7 +5,8 @@ The reference model object only touches a handful of env attributes
 ``observation_space.shape[0]``, ``proc_observation_space_dims``, ``action_space.{shape,n}``,
 ``obs_preproc``, ``obs_postproc``, ``targ_proc``, ``tf_reward_fn()``.  A TF closure cannot
 be traced here, so the env CLASS NAME selects a compiled-in env kind (SURVEY.md
-Appendix B); unknown envs are rejected.
+Appendix B); any other env declares its closures (env_spec.EnvDecl, found through an explicit
+``cadm_env_spec`` attribute) or is rejected.
 
 ``EnvSpec`` objects are simulator-free stand-ins with the same duck type, used for
 synthetic workloads and by ``fit`` for its host-side (numpy, float64) target
@@ -82,10 +83,18 @@ def make_env_spec(kind):
 
 
 def resolve_env_kind(env):
-    """Map an env object (reference env, NormalizedEnv wrapper, or EnvSpec) to a kind name."""
+    """Map an env object (reference env, NormalizedEnv wrapper, or EnvSpec) to a kind name -- or, for a user-declared env, to its
+    ``EnvDecl`` (env_spec.py): the env or a wrapper in its ``wrapped_env`` chain carries it as an explicit ``cadm_env_spec``
+    attribute (never inferred from the duck type)."""
+    from .env_spec import EnvDecl
     seen = 0
     e = env
     while e is not None and seen < 8:
+        spec = getattr(e, "cadm_env_spec", None)
+        if spec is not None:
+            if not isinstance(spec, EnvDecl):
+                raise TypeError("%s.cadm_env_spec must be a cadm_amd.env_spec.EnvDecl, got %r" % (type(e).__name__, type(spec).__name__))
+            return spec
         kind = getattr(e, "cadm_env_kind", None)
         if isinstance(kind, str):
             return kind
@@ -101,5 +110,6 @@ def resolve_env_kind(env):
         e = nxt
         seen += 1
     raise ValueError(
-        "cannot map env %r to a compiled-in env kind; supported reference env classes: %s"
+        "cannot map env %r to a compiled-in env kind; supported reference env classes: %s (any other env declares its closures "
+        "with a cadm_amd.env_spec.EnvDecl in a `cadm_env_spec` attribute)"
         % (type(env).__name__, sorted(CLASS_TO_KIND)))

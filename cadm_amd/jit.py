@@ -6,7 +6,8 @@ units, swish, context_out_dim 0 / 10).  For any other `--hidden_size` / `--conte
 or nonlinearity (dynamics.py:17-24) this module compiles csrc/rollout_jit.hip with hipcc -- one small shared object per noise
 mode, cached (cache_dir(): the package's jit_cache/ when writable, else the user's cache directory) under a key made of the
 geometry, a hash of the kernel sources and the compiler's version -- and registers it on the engine's ctx
-(`cadm_register_rollout`).  hipcc is the only requirement ($HIPCC / $ROCM_PATH / /opt/rocm / PATH); there is no fallback
+(`cadm_register_rollout`).  A user-declared env (env_spec.EnvDecl) always takes this path: its closures are compiled in from the
+spec's generated header (-DCADM_JIT_SPEC), and its spec hash is part of the module's name and of what the ctx checks.  hipcc is the only requirement ($HIPCC / $ROCM_PATH / /opt/rocm / PATH); there is no fallback
 kernel.  Hidden widths below 113 need no build: they run zero-padded on the 128-wide kernel (xdl_geo.h).
 """
 import ctypes as C
@@ -85,17 +86,34 @@ def _build_key():
     return _memo["key"]
 
 
-def module_path(env_kind, C_, hid, nh, act, noise):
-    return os.path.join(cache_dir(), "rollout_e%d_c%d_h%d_n%d_a%d_z%d_%s.so" % (env_kind, C_, hid, nh, act, noise, _build_key()))
+def module_path(env_kind, C_, hid, nh, act, noise, spec=None):
+    tag = "e%d" % env_kind if spec is None else "e%d_s%s" % (env_kind, spec.hash[:16])      # a user-declared env: its spec hash
+    return os.path.join(cache_dir(), "rollout_%s_c%d_h%d_n%d_a%d_z%d_%s.so" % (tag, C_, hid, nh, act, noise, _build_key()))
 
 
-def build(env_kind, C_, hid, nh, act, noise, verbose=False):
+def spec_header_dir(spec):
+    """Write a spec's generated cadm_spec_tables.h (env_spec.EnvDecl.header: data tables only) into the cache; returns its directory."""
+    d = os.path.join(cache_dir(), "spec_%s" % spec.hash[:16])
+    os.makedirs(d, exist_ok=True)
+    path, text = os.path.join(d, "cadm_spec_tables.h"), spec.header()
+    if not os.path.exists(path) or open(path).read() != text:
+        tmp = path + ".tmp%d" % os.getpid()
+        with open(tmp, "w") as f:
+            f.write(text)
+        os.replace(tmp, path)
+    return d
+
+
+def build(env_kind, C_, hid, nh, act, noise, verbose=False, spec=None):
     """Compile one instantiation (if it is not cached) and return the path of its shared object.  `hid` is the KERNEL's width
-    (kernel_hid(model width)).  Processes that want the same module at the same time -- the ranks of a multi-GPU job each
-    construct the same model -- serialise on a lock file next to it: the first one compiles (~6-30 s), the others wait and load."""
+    (kernel_hid(model width)); `spec` the env_spec.EnvDecl of a user-declared env (env_kind = _lib.ENV_SPEC).  Processes that want
+    the same module at the same time -- the ranks of a multi-GPU job each construct the same model -- serialise on a lock file next
+    to it: the first one compiles (~6-30 s), the others wait and load."""
     if hid < MIN_HID:
         raise _lib.CadmError("rollout kernel width %d: widths below %d are served by the %d-wide kernel (jit.kernel_hid)" % (hid, MIN_HID, NARROW_HID))
-    path = module_path(env_kind, C_, hid, nh, act, noise)
+    if (spec is not None) != (env_kind == _lib.ENV_SPEC):
+        raise _lib.CadmError("a rollout module for env kind %d %s" % (env_kind, "takes no spec" if spec is not None else "needs its env spec"))
+    path = module_path(env_kind, C_, hid, nh, act, noise, spec)
     if os.path.exists(path):
         return path
     cc = hipcc()
@@ -109,8 +127,10 @@ def build(env_kind, C_, hid, nh, act, noise, verbose=False):
         tmp = path + ".tmp%d" % os.getpid()
         cmd = [cc, "--offload-arch=" + ARCH, "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
                "-Wno-unused-function", "-DCADM_JIT_MODULE", "-DCADM_JIT_ENV=%d" % env_kind, "-DCADM_JIT_C=%d" % C_, "-DCADM_JIT_HID=%d" % hid,
-               "-DCADM_JIT_NH=%d" % nh, "-DCADM_JIT_ACT=%d" % act, "-DCADM_JIT_NOISE=%d" % noise,
-               os.path.join(_lib.CSRC, "rollout_jit.hip"), "-o", tmp]
+               "-DCADM_JIT_NH=%d" % nh, "-DCADM_JIT_ACT=%d" % act, "-DCADM_JIT_NOISE=%d" % noise]
+        if spec is not None:
+            cmd += ["-DCADM_JIT_SPEC", "-I" + spec_header_dir(spec)]
+        cmd += [os.path.join(_lib.CSRC, "rollout_jit.hip"), "-o", tmp]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if verbose or r.returncode != 0:
             print(r.stdout)
@@ -155,15 +175,16 @@ def ensure(engine, noise):
     lib = engine.lib
     if lib.cadm_rollout_builtin(engine._ctx):
         return False
-    key = (_lib.ENV_KINDS[engine.env_kind], engine.C, kernel_hid(engine.HID), engine.NH, engine.hidden_act, noise)
-    path = build(*key)
+    spec = getattr(engine, "spec", None)
+    kind = _lib.ENV_SPEC if spec is not None else _lib.ENV_KINDS[engine.env_kind]
+    path = build(kind, engine.C, kernel_hid(engine.HID), engine.NH, engine.hidden_act, noise, spec=spec)
     if path not in _loaded:
         mod = C.CDLL(path)
         mod.cadm_jit_describe.argtypes = [C.POINTER(C.c_int)]
         mod.cadm_jit_describe.restype = None
         _loaded[path] = mod
     mod = _loaded[path]
-    desc = (C.c_int * 8)()
+    desc = (C.c_int * 10)()
     mod.cadm_jit_describe(desc)
     engine._check(lib.cadm_register_rollout(engine._ctx, noise, C.cast(mod.cadm_jit_rollout, C.c_void_p), desc), "cadm_register_rollout")
     return True

@@ -94,8 +94,13 @@ def make_problem(env="halfcheetah", context=True, E=5, m=1, hidden_sizes=(200,) 
                  with_back=False, **_unused):
     """Weights + stats + planner inputs for one synthetic planning problem.
     ``trained_like`` rescales the heads so the per-step delta is of unit order and
-    gives the biases small random values (the reference init leaves them at 0)."""
-    D, A, P, discrete = ENV_SHAPES[env]
+    gives the biases small random values (the reference init leaves them at 0).
+    ``env``: a built-in kind name or a user-declared env (env_spec.EnvDecl); a spec with a built-in kind's
+    shapes draws exactly that kind's problem for the same seed."""
+    if isinstance(env, str):
+        D, A, P, discrete = ENV_SHAPES[env]
+    else:
+        D, A, P, discrete = env.obs_dim, env.act_dim, env.proc_obs_dim, False
     rng = np.random.default_rng(seed)
     Cc = C if context else 0
     K0 = P + A + Cc

@@ -50,6 +50,7 @@ extern "C" {
 #define CADM_ENV_SLIM_HUMANOID 2 /* slim_humanoid_env.py:39-46,95-111 */
 #define CADM_ENV_CARTPOLE 3      /* classic_control.py:94-101,154-166 */
 #define CADM_ENV_PENDULUM 4      /* classic_control.py:209-218,284-291 */
+#define CADM_ENV_SPEC 5          /* a user-declared env (cadm_env_spec below): rollouts come from a module built for the spec (cadm_amd/jit.py) */
 
 #define CADM_NET_FF 0    /* variable scope 'ff_model'        (dynamics.py:159) */
 #define CADM_NET_BACK 1  /* variable scope 'backward_model'  (dynamics.py:213) */
@@ -86,8 +87,46 @@ typedef struct cadm_config {
     float upper_bound;         /* +1  (core/utils.py:396) */
     int32_t back_model;        /* 1: backward model present (back_coeff > 0, dynamics.py:212) */
     int32_t hidden_act;        /* CADM_ACT_*: hidden_nonlinearity of both dynamics nets (dynamics.py:104; 0 = swish) */
-    int32_t reserved[6];
+    int32_t reserved[6];       /* CADM_ENV_SPEC: [0], [1] = low / high word of the spec's 64-bit hash (cadm_env_spec.hash); else 0 */
 } cadm_config;
+
+/* A user-declared env (env_kind CADM_ENV_SPEC, cadm_amd/env_spec.py): the closures obs_preproc / obs_postproc / targ_proc / reward
+ * as tables.  Continuous actions only.  Envelope (checked by cadm_ctx_create before any HIP call):
+ * 1 <= D <= CADM_SPEC_MAX_D, 1 <= A <= CADM_SPEC_MAX_A, 1 <= P <= CADM_SPEC_MAX_P, discrete == 0.
+ *   preproc[d]   CADM_SPEC_PRE_*: the features of obs dim d, in dim order (sincos: sin then cos); P = their count
+ *   postproc[d]  CADM_SPEC_POST_*: next[d] = obs[d] + delta[d] (add) or delta[d] (replace); targ_proc follows
+ *   terms        reward = sum over terms of w * f(x), x = obs[dim] (when OBS: the pre-step state) or next_obs[dim] (NEXT_OBS);
+ *                f = x, x^2, |x|, [lo < x < hi] or [x > hi] + [x < lo]; then - ctrl_cost * sum(a^2) + bonus */
+#define CADM_SPEC_MAX_D 48
+#define CADM_SPEC_MAX_A 24
+#define CADM_SPEC_MAX_P 64
+#define CADM_SPEC_MAX_TERMS 32
+#define CADM_SPEC_PRE_ID 0
+#define CADM_SPEC_PRE_DROP 1
+#define CADM_SPEC_PRE_SINCOS 2
+#define CADM_SPEC_POST_ADD 0
+#define CADM_SPEC_POST_REPLACE 1
+#define CADM_SPEC_TERM_LINEAR 0
+#define CADM_SPEC_TERM_SQUARE 1
+#define CADM_SPEC_TERM_ABS 2
+#define CADM_SPEC_TERM_INSIDE 3
+#define CADM_SPEC_TERM_OUTSIDE 4
+#define CADM_SPEC_WHEN_OBS 0
+#define CADM_SPEC_WHEN_NEXT_OBS 1
+typedef struct cadm_env_spec {
+    int32_t obs_dim, act_dim, proc_obs_dim;
+    int32_t preproc[CADM_SPEC_MAX_D];
+    int32_t postproc[CADM_SPEC_MAX_D];
+    int32_t n_terms;
+    int32_t term_kind[CADM_SPEC_MAX_TERMS];
+    int32_t term_dim[CADM_SPEC_MAX_TERMS];
+    int32_t term_when[CADM_SPEC_MAX_TERMS];
+    float term_w[CADM_SPEC_MAX_TERMS];
+    float term_lo[CADM_SPEC_MAX_TERMS];
+    float term_hi[CADM_SPEC_MAX_TERMS];
+    float ctrl_cost, bonus;
+    uint32_t hash_lo, hash_hi;   /* hash of the spec's canonical serialisation: must equal the ctx config's reserved[0..1] */
+} cadm_env_spec;
 
 const char* cadm_last_error(void);
 int cadm_abi_version(void);
@@ -98,6 +137,10 @@ const char* cadm_build_id(void);
 /* Build / free the per-model device state (replaces graph construction, dynamics.py:107-342). */
 int cadm_ctx_create(const cadm_config* cfg, cadm_ctx** out);
 int cadm_ctx_destroy(cadm_ctx* ctx);
+/* CADM_ENV_SPEC only, right after cadm_ctx_create: validate the spec's tables against the ctx (dims, feature count P, hash),
+ * keep them and upload the per-feature (source dim, op) table the training / prediction input assembly reads.  Training and
+ * prediction on a spec ctx fail with CADM_ESTATE until it is set.  Synchronous. */
+int cadm_set_env_spec(cadm_ctx* ctx, const cadm_env_spec* spec);
 
 /* Register one dense layer's master weights (raw TF layout W [E,in,out], b [E,1,out];
  * create_dense_layer, core/utils.py:635-641).  The pointers stay owned by the caller and must
@@ -171,11 +214,12 @@ int cadm_rollout_returns(cadm_ctx* ctx, const float* obs, const float* obs_rows,
  * (`--hidden_size`, `--context_out_dim`, run_cadm_pets.py:122-135) the caller builds cadm_amd/csrc/rollout_jit.hip with hipcc
  * (cadm_amd/jit.py does) and registers the module's entry point for a noise mode (0 device Philox, 1 injected eps, 2 deterministic).
  *   cadm_rollout_builtin   1 if the ctx's geometry is compiled in, else 0
- *   cadm_register_rollout  fn = the module's `cadm_jit_rollout`; describe = its `cadm_jit_describe` output (checked against the ctx)
+ *   cadm_register_rollout  fn = the module's `cadm_jit_rollout`; describe = its `cadm_jit_describe` output (checked against the ctx;
+ *                          CADM_ENV_SPEC: describe[8], describe[9] = the spec hash the module was built for, refused unless it is the ctx's)
  *   cadm_rollout_check     validates that a rollout of m x n_local candidates can be launched (kernel present, LDS fits the
  *                          horizon) WITHOUT launching -- construction-time instead of first-get_action failure */
 int cadm_rollout_builtin(cadm_ctx* ctx);
-int cadm_register_rollout(cadm_ctx* ctx, int noise_mode, void* fn, const int describe[8]);
+int cadm_register_rollout(cadm_ctx* ctx, int noise_mode, void* fn, const int describe[10]);
 int cadm_rollout_check(cadm_ctx* ctx, int noise_mode, int m, int n_local);
 
 /* Mean over particles (core/utils.py:474): returns_rows [m,n_local,p] -> cand_returns [m,n_local]. */
