@@ -18,6 +18,7 @@ import os
 import shutil
 import subprocess
 import tempfile
+import threading
 import warnings
 
 from . import _lib, isa_check
@@ -97,7 +98,7 @@ def spec_header_dir(spec):
     os.makedirs(d, exist_ok=True)
     path, text = os.path.join(d, "cadm_spec_tables.h"), spec.header()
     if not os.path.exists(path) or open(path).read() != text:
-        tmp = path + ".tmp%d" % os.getpid()
+        tmp = path + ".tmp%d_%d" % (os.getpid(), threading.get_ident())      # (threads of one process build modules of one spec too)
         with open(tmp, "w") as f:
             f.write(text)
         os.replace(tmp, path)

@@ -73,3 +73,259 @@ def f16_split_saturating(x):
     with np.errstate(invalid="ignore"):
         lo = sat((x - hi).astype(np.float32))
     return (hi + lo).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# user-declared envs (cadm_amd/env_spec.py EnvDecl): what tests/test_gpu_env_spec.py and tests/test_gpu_env_spec_envelope.py share
+# ------------------------------------------------------------------------------------------------------------------------------
+SPEC_WD = (0.000025, 0.00005, 0.000075, 0.000075, 0.0001)
+SPEC_CWD = (0.000025, 0.00005, 0.000075)
+FLAVOURS = ("1", "2", "3", "4")      # cooperative kernel with one / two row tiles, wave-tile kernel with 8 / 4 tiles per workgroup
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def spec_oracle(prob, spec, dt=np.float32):
+    """A synth problem of a spec env as oracle inputs (the oracle is duck-typed on env objects: the spec is its env)."""
+    o = dict(env=spec, ff=onets.cast_params(prob["ff"], dt), cp=None if prob["cp"] is None else onets.cast_params(prob["cp"], dt),
+             st=onets.cast_stats(prob["stats"], dt))
+    for k in ("obs", "cp_obs", "cp_act", "init_mean", "init_var"):
+        o[k] = prob[k].astype(dt)
+    return o
+
+
+class flavour:
+    """`with flavour(eng, "3"):` forces one rollout flavour on a developer-library engine, and hands back the launch plan after."""
+
+    def __init__(self, eng, fl):
+        self.eng, self.fl = eng, fl
+
+    def __enter__(self):
+        self.eng.dev_set_rollout("xdl", row_tiles=int(self.fl))
+        return self.eng
+
+    def __exit__(self, *exc):
+        self.eng.dev_set_rollout("xdl", row_tiles=0)
+
+
+def run_flavour(eng, fl, obs, ctx, acts, **kw):
+    """(returns [m,n,p], trajectory [H,m,n,p,D]) of one rollout call in flavour `fl`, as numpy."""
+    import torch
+    with flavour(eng, fl):
+        rows, traj = eng.rollout_returns(obs, ctx, acts, want_traj=True, **kw)
+        torch.cuda.synchronize()
+        return _np(rows), _np(traj)
+
+
+def threshold_jump(spec, H, p):
+    """Largest change of a candidate's return from indicator terms (inside / outside) taking the other side of a threshold once per
+    step: their weights summed, over H steps, averaged over p particles."""
+    return sum(abs(t[3]) for t in spec.terms if t[0] in ("inside", "outside")) * H / p
+
+
+def close_but_jumps(got, want, jump, what):
+    """Candidate returns against the oracle's.  An indicator term (inside / outside) jumps by its weight where a state sits on its
+    threshold: a particle whose state lands within rounding of it may take the other side in the oracle.  Such a candidate is off by
+    a multiple of w / p -- allowed for at most 1 % of the candidates, everything else at the usual 1e-4 bar."""
+    bad = np.abs(got - want) > 1e-4 * np.maximum(np.abs(want), np.sqrt(np.mean(want ** 2)))
+    assert bad.sum() <= 0.01 * bad.size, "%s: %d/%d candidates off" % (what, bad.sum(), bad.size)
+    assert (np.abs(got - want)[bad] <= jump + 1e-3).all(), "%s: off by more than one threshold flip" % what
+
+
+def check_spec_training_step(spec, prob, E, det, what, B=48, predict=False):
+    """One training step of a spec env against oracle/train: the three losses at rtol 5e-5, and every gradient (linearised Adam:
+    g = w_before - w_after) within 2e-3 of its tensor's max against fp64 autograd.  `predict`: also predict_heads against the oracle's
+    one-step forward pass (float64).  The oracle's obs_preproc is picked by env name, so it is handed the spec's preprocessed
+    observations under an identity-preproc name: the same network inputs."""
+    import torch
+    from cadm_amd import synth
+    from oracle import train as otrain
+    context = prob["cp"] is not None
+    batch = synth.make_train_batch(prob, B=B, seed=2)
+    cfg = dict(deterministic=det, back_coeff=0.5, weight_decay_coeff=1.0, weight_decays=SPEC_WD, context_weight_decays=SPEC_CWD,
+               n_hidden=len(prob["hidden_sizes"]), n_cp_hidden=len(prob["cp_hidden_sizes"]))
+    keys = ["obs", "act", "delta", "obs_next", "back_delta"] + (["cp_obs", "cp_act"] if context else [])
+    tb = {k: torch.tensor(v, dtype=torch.float64) for k, v in batch.items()}
+    tb["obs"] = torch.tensor(spec.obs_preproc(batch["obs"]), dtype=torch.float64)
+    tb["obs_next"] = torch.tensor(spec.obs_preproc(batch["obs_next"]), dtype=torch.float64)
+
+    def oracle_nets(rg):
+        return (otrain.to_torch(prob["ff"], torch.float64, rg), otrain.to_torch(prob["back"], torch.float64, rg),
+                otrain.to_torch(prob["cp"], torch.float64, rg) if context else None, otrain.to_torch(prob["stats"], torch.float64))
+    eng = make_engine(prob, p=E, deterministic=det)
+    eng.train_configure(1e-3, SPEC_WD, SPEC_CWD, 1.0, 0.5, max_batch=B)
+    got = _np(eng.train_step({k: eng._t(batch[k]) for k in keys}, train=False))
+    ff, back, cp, st = oracle_nets(False)
+    ref = otrain.train_losses("slim_humanoid", ff, back, cp, st, tb, cfg)       # (identity obs_preproc)
+    np.testing.assert_allclose(got, [float(ref["mse"]), float(ref["back_mse"]), float(ref["recon"])], rtol=5e-5, atol=5e-5)
+    if predict:
+        mu, lv = eng.predict_heads(batch["obs"], batch["act"], batch["cp_obs"] if context else None, batch["cp_act"] if context else None)
+        o = {k: onets.cast_params(prob[k], np.float64) for k in ("ff",) + (("cp",) if context else ())}
+        s = onets.cast_stats(prob["stats"], np.float64)
+        feats = [onets.normalize(spec.obs_preproc(batch["obs"]), s["obs_mean"], s["obs_std"]),
+                 onets.normalize(batch["act"], s["act_mean"], s["act_std"])]
+        if context:
+            feats.append(onets.context_forward_bs(o["cp"], batch["cp_obs"], batch["cp_act"], s))
+        _, mu_ref, lv_ref = onets.dynamics_forward(o["ff"], np.concatenate(feats, -1), s["delta_mean"], s["delta_std"],
+                                                   np.zeros((E, B, prob["D"])), det)
+        assert_close(_np(mu), mu_ref, 2e-5, "%s predict mu" % what)
+        if not det:
+            assert_close(_np(lv), lv_ref, 2e-5, "%s predict logvar" % what)
+    eng.close()
+    eng = make_engine(prob, p=E, deterministic=det)
+    eng.train_configure(1e6, SPEC_WD, SPEC_CWD, 1.0, 0.5, max_batch=B, beta1=0.0, beta2=0.0, epsilon=1e6)    # linearised Adam
+    before = {nn: {k: v.clone() for k, v in eng.nets[nn].items()} for nn in eng.net_names()}
+    eng.train_step({k: eng._t(batch[k]) for k in keys}, train=True)
+    ff, back, cp, st = oracle_nets(True)
+    out = otrain.train_losses("slim_humanoid", ff, back, cp, st, tb, cfg)
+    grads = otrain.grads_of(out["loss"], {"ff_model": ff, "backward_model": back, "context_model": cp})
+    for net in eng.net_names():
+        for pname, w0 in before[net].items():
+            g_ref = grads[net][pname]
+            g_hip = (w0 - eng.nets[net][pname]).cpu().numpy().astype(np.float64)
+            if g_ref is None:
+                assert np.abs(g_hip).max() == 0.0
+                continue
+            g_ref = g_ref.numpy()
+            err = np.abs(g_hip - g_ref).max() / max(np.abs(g_ref).max(), 1e-12)
+            assert err < 2e-3, "%s %s/%s gradient off: %.3e" % (what, net, pname, err)
+    eng.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the corners of the kernels' envelope (include/cadm_hip.h CADM_SPEC_MAX_*: D <= 48, A <= 24, P <= 64, 32 reward terms), as plain
+# declarations: tests/test_env_spec.py restates the closures from these lists, tests/test_gpu_env_spec_envelope.py runs them
+# ------------------------------------------------------------------------------------------------------------------------------
+_WIDEST_SINCOS = (1, 4, 6, 11, 15, 20, 26, 30, 32, 34, 37, 39, 42, 43, 45, 46, 47)      # 17 dims on both sides of dim 32
+_WIDEST_REPLACE = (0, 13, 33, 40, 47)
+CORNER_DECLS = {
+    # D = 48, A = 24, P = 30 id + 17 sincos x 2 = 64 (dim 40 dropped).  32 terms: every kind on both states, several terms on dims 35
+    # and 47 and on pair 17, terms on pairs 16..23 (return slots shared with pairs 0..7).  The first term reads dim 35 (pair 17): the
+    # ctrl cost and bonus ride on slot 1, which pair 1's own terms (dims 2, 3) share.
+    "widest": dict(
+        obs_dim=48, act_dim=24,
+        preproc=["drop" if d == 40 else "sincos" if d in _WIDEST_SINCOS else "id" for d in range(48)],
+        postproc=["replace" if d in _WIDEST_REPLACE else "add" for d in range(48)],
+        reward=[dict(kind="linear", dim=35, w=0.8),
+                dict(kind="square", dim=34, w=-0.3),
+                dict(kind="abs", dim=35, w=0.2, when="next_obs"),
+                dict(kind="inside", dim=47, w=0.5, lo=-0.4, hi=0.6),
+                dict(kind="outside", dim=47, w=-0.7, lo=-1.2, hi=1.1, when="next_obs"),
+                dict(kind="linear", dim=46, w=0.4, when="next_obs"),
+                dict(kind="square", dim=3, w=-0.05),
+                dict(kind="abs", dim=2, w=-0.15, when="next_obs"),
+                dict(kind="linear", dim=0, w=1.0),
+                dict(kind="inside", dim=1, w=0.3, lo=-0.5, hi=0.5, when="next_obs"),
+                dict(kind="outside", dim=5, w=-0.25, lo=-1.5, hi=1.5),
+                dict(kind="square", dim=32, w=-0.1, when="next_obs"),
+                dict(kind="linear", dim=33, w=-0.6),
+                dict(kind="abs", dim=40, w=0.35),
+                dict(kind="linear", dim=40, w=0.12, when="next_obs"),
+                dict(kind="square", dim=41, w=-0.08),
+                dict(kind="inside", dim=44, w=0.9, lo=0.0, hi=2.0),
+                dict(kind="outside", dim=38, w=-0.45, lo=-0.8, hi=0.9, when="next_obs"),
+                dict(kind="linear", dim=20, w=0.22),
+                dict(kind="abs", dim=21, w=-0.33),
+                dict(kind="square", dim=30, w=0.07, when="next_obs"),
+                dict(kind="linear", dim=31, w=-0.18, when="next_obs"),
+                dict(kind="inside", dim=12, w=0.6, lo=-1.0, hi=0.2, when="next_obs"),
+                dict(kind="outside", dim=18, w=-0.2, lo=-0.3, hi=0.3),
+                dict(kind="abs", dim=47, w=0.11),
+                dict(kind="linear", dim=47, w=0.27, when="next_obs"),
+                dict(kind="square", dim=36, w=-0.04),
+                dict(kind="linear", dim=39, w=0.5, when="next_obs"),
+                dict(kind="abs", dim=43, w=-0.09, when="next_obs"),
+                dict(kind="square", dim=45, w=-0.06),
+                dict(kind="linear", dim=35, w=-0.2),
+                dict(kind="outside", dim=26, w=-0.3, lo=-2.0, hi=2.0, when="next_obs")],
+        ctrl_cost=0.02, bonus=0.5),
+    # the smallest env: one dim, one action, one feature, no reward terms (ctrl cost only, on pair 0)
+    "tiny": dict(obs_dim=1, act_dim=1, preproc=["id"], reward=[], ctrl_cost=0.1),
+    # two dims, the first dropped, the second sin / cos: P = 2 from one dim
+    "tiny_sincos": dict(obs_dim=2, act_dim=2, preproc=["drop", "sincos"], postproc=["add", "replace"],
+                        reward=[dict(kind="square", dim=1, w=-0.5)], ctrl_cost=0.03, bonus=0.25),
+    # odd D = 47: the last pair (23, return slot 7, Philox group 11) holds dim 46 alone, which is sin / cos, replaced, and read by a
+    # pre-step and a next-obs term.  P = 1 drop, 4 sincos, 42 id = 50.
+    "odd_tail": dict(
+        obs_dim=47, act_dim=13,
+        preproc=["drop" if d == 0 else "sincos" if d in (3, 20, 35, 46) else "id" for d in range(47)],
+        postproc=["replace" if d in (5, 46) else "add" for d in range(47)],
+        reward=[dict(kind="linear", dim=2, w=1.0), dict(kind="square", dim=46, w=-0.2, when="next_obs"),
+                dict(kind="abs", dim=46, w=0.3), dict(kind="inside", dim=45, w=0.4, lo=-0.5, hi=0.5, when="next_obs"),
+                dict(kind="linear", dim=33, w=-0.1)],
+        ctrl_cost=0.01, bonus=0.2),
+    # the first term reads the next state: the ctrl cost and bonus ride on its pair (6), which has no pre-step term of its own
+    "first_next": dict(
+        obs_dim=20, act_dim=5,
+        preproc=["drop" if d == 0 else "sincos" if d in (7, 13) else "id" for d in range(20)],
+        postproc=["replace" if d == 13 else "add" for d in range(20)],
+        reward=[dict(kind="linear", dim=13, w=0.5, when="next_obs"), dict(kind="square", dim=4, w=-0.1),
+                dict(kind="inside", dim=19, w=0.3, lo=-0.5, hi=1.0), dict(kind="abs", dim=12, w=-0.2, when="next_obs")],
+        ctrl_cost=0.05, bonus=1.5),
+}
+
+
+def corner_spec(name):
+    from cadm_amd.env_spec import EnvDecl
+    return EnvDecl(**CORNER_DECLS[name])
+
+
+def check_class_api_on_spec(spec, tmp_path, epochs):
+    """The class API on a user's simulator that declares its closures by a spec (wrapped the way the reference's NormalizedEnv wraps
+    an env): fit, plan through MPCController (finite, inside [-1, 1]), warm-started replan, predict, context, and save / load / replan
+    bit for bit."""
+    from cadm_amd.caller import DevicePlannerState
+    from cadm_amd.dynamics.mlp_cadm_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel
+    from cadm_amd.policies.mpc_controller import MPCController
+    from cadm_amd.samplers.model_sample_processor import ModelSampleProcessor
+
+    class UserSim:                                       # a user's simulator: declares its closures, is no built-in class
+        cadm_env_spec = spec
+        observation_space, action_space, proc_observation_space_dims = spec.observation_space, spec.action_space, spec.proc_obs_dim
+        obs_preproc, obs_postproc, targ_proc, reward = spec.obs_preproc, spec.obs_postproc, spec.targ_proc, spec.reward
+
+    class Normalized:                                    # the reference's NormalizedEnv wrapper shape
+        def __init__(self, e):
+            self.wrapped_env = e
+            for k in ("observation_space", "action_space", "proc_observation_space_dims", "obs_preproc", "obs_postproc", "targ_proc", "reward"):
+                setattr(self, k, getattr(e, k))
+    env = Normalized(UserSim())
+    D, A, Hh, F, H = spec.obs_dim, spec.act_dim, 10, 10, 6
+    kw = dict(hidden_nonlinearity="swish", context_out_dim=10, n_forwards=H, n_candidates=64, ensemble_size=5, n_particles=10, use_cem=True,
+              batch_size=32, state_diff=1, normalize_input=True, back_coeff=0.5, weight_decays=SPEC_WD, weight_decay_coeff=1.0,
+              context_weight_decays=SPEC_CWD + (0.0001,), history_length=Hh, future_length=F)
+    model = MLPEnsembleCEMDynamicsModel("dyn", env, **kw)
+    assert model.engine.spec == spec
+    rng = np.random.default_rng(0)
+    paths = []
+    for L in (30, 45, 12):
+        obs = rng.standard_normal((L, D)).astype(np.float32)
+        paths.append(dict(observations=obs, actions=rng.uniform(-1, 1, (L, A)).astype(np.float32), rewards=rng.standard_normal(L),
+                          cp_obs=0.1 * rng.standard_normal((L, D * Hh)).astype(np.float32),
+                          cp_act=rng.uniform(-1, 1, (L, A * Hh)).astype(np.float32)))
+    d = ModelSampleProcessor(context=True, future_length=F).process_samples(paths)
+    model.fit(d["concat_obs"], d["concat_act"], d["concat_next_obs"], d["cp_observations"], d["cp_actions"], d["concat_bool"], epochs=epochs)
+    policy = MPCController("mpc", env, model, use_cem=True, n_candidates=64, horizon=H, num_rollouts=2, context=True)
+    o, cpo, cpa = rng.standard_normal((2, D)), 0.1 * rng.standard_normal((2, D * Hh)), rng.uniform(-1, 1, (2, A * Hh))
+    mean, var = np.zeros((2, H, A)), np.full((2, H, A), 0.25)
+    plan, _ = policy.get_actions(o, cpo, cpa, mean, var)
+    assert plan.shape == (2, H, A) and np.isfinite(plan).all() and np.abs(plan).max() <= 1.0
+    warm = np.concatenate([plan[:, 1:], np.zeros((2, 1, A))], axis=1)          # the samplers' CEM warm start
+    plan2, _ = policy.get_actions(o, cpo, cpa, warm, var)
+    assert np.isfinite(plan2).all()
+    assert DevicePlannerState(model, 2).eng.spec == spec          # the device-resident caller state builds on the same engine
+    mu, sd = model.predict(o, plan[:, 0], cpo, cpa, return_std=True)
+    assert np.isfinite(mu).all() and np.isfinite(sd).all() and (sd > 0).all()
+    cp = model.get_context_pred(cpo, cpa)
+    assert np.isfinite(np.asarray(cp)).all()
+    path = str(tmp_path / "params")
+    model.save(path)
+    model2 = MLPEnsembleCEMDynamicsModel("dyn", env, **kw)
+    model2.load(path)
+    model._call = model2._call = 7
+    a1 = model.get_action(o, cpo, cpa, warm, var)
+    a2 = model2.get_action(o, cpo, cpa, warm, var)
+    assert np.isfinite(a1).all() and np.abs(a1).max() <= 1.0
+    np.testing.assert_array_equal(a1, a2)

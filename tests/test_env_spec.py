@@ -2,13 +2,15 @@
 the generated header and its hash, a cross-compiled spec rollout module, and the library's envelope check of a spec-kind config."""
 import ctypes
 import os
+import re
 
 import numpy as np
 import pytest
 
 from cadm_amd import _lib
-from cadm_amd.env_spec import EnvDecl, restate
+from cadm_amd.env_spec import TERMS, WHEN, EnvDecl, restate
 from cadm_amd.envs import resolve_env_kind, make_env_spec
+from helpers import CORNER_DECLS, corner_spec
 from oracle.envs import make_env
 
 KINDS = ("halfcheetah", "ant", "slim_humanoid")
@@ -206,3 +208,152 @@ def test_spec_struct_layout_matches_header():
     # 3 + 48 + 48 + 1 + 3 * 32 int32, 3 * 32 + 2 float, 2 uint32
     assert ctypes.sizeof(_lib.EnvSpecC) == (3 + 48 + 48 + 1 + 96 + 96 + 2 + 2) * 4
     assert ctypes.sizeof(_lib.Config) == 37 * 4
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the corners of the envelope (tests/helpers.py CORNER_DECLS; run on the GPU by tests/test_gpu_env_spec_envelope.py)
+# ------------------------------------------------------------------------------------------------------------------------------
+def _restated(decl):
+    """The closures of a declaration, restated from its plain lists in float64 (independent of EnvDecl's tables)."""
+    D = decl["obs_dim"]
+    pre = decl.get("preproc", "id")
+    post = decl.get("postproc", "add")
+    pre = [pre] * D if isinstance(pre, str) else list(pre)
+    post = [post] * D if isinstance(post, str) else list(post)
+
+    def preproc(obs):
+        cols = []
+        for d in range(D):
+            if pre[d] == "id":
+                cols.append(obs[..., d])
+            elif pre[d] == "sincos":
+                cols += [np.sin(obs[..., d]), np.cos(obs[..., d])]
+        return np.stack(cols, -1)
+
+    def postproc(obs, pred):
+        return np.stack([pred[..., d] if post[d] == "replace" else obs[..., d] + pred[..., d] for d in range(D)], -1)
+
+    def targ(obs, nxt):
+        return np.stack([nxt[..., d] if post[d] == "replace" else nxt[..., d] - obs[..., d] for d in range(D)], -1)
+
+    def term(t, obs, nxt):
+        x = (nxt if t.get("when", "obs") == "next_obs" else obs)[..., t["dim"]]
+        w = t.get("w", 1.0)
+        if t["kind"] == "linear":
+            return w * x
+        if t["kind"] == "square":
+            return w * x * x
+        if t["kind"] == "abs":
+            return w * np.abs(x)
+        if t["kind"] == "inside":
+            return w * ((x > t["lo"]) & (x < t["hi"]))
+        return w * ((x > t["hi"]).astype(float) + (x < t["lo"]))
+
+    def reward(obs, act, nxt):
+        r = sum((term(t, obs, nxt) for t in decl["reward"]), np.zeros(obs.shape[:-1]))
+        return r - decl.get("ctrl_cost", 0.0) * np.sum(act * act, -1) + decl.get("bonus", 0.0)
+    return preproc, postproc, targ, reward
+
+
+# the first term's pair, and the pre-step terms on it that the kernels sum first (before the ctrl cost and the bonus)
+FIRST_PAIR_GROUP = {"widest": [0, 1, 30], "tiny": [], "tiny_sincos": [0], "odd_tail": [0], "first_next": []}
+
+
+@pytest.mark.parametrize("corner", sorted(CORNER_DECLS))
+def test_corner_closures_match_a_float64_restatement(corner):
+    decl, spec = CORNER_DECLS[corner], corner_spec(corner)
+    D, A = decl["obs_dim"], decl["act_dim"]
+    preproc, postproc, targ, reward = _restated(decl)
+    rng = np.random.default_rng(5)
+    obs, nxt, pred = (1.5 * rng.standard_normal((6, 9, D)) for _ in range(3))
+    act = rng.uniform(-1, 1, (6, 9, A))
+    assert spec.proc_obs_dim == preproc(obs).shape[-1]
+    assert np.array_equal(spec.obs_preproc(obs), preproc(obs))
+    assert np.array_equal(spec.obs_postproc(obs, pred), postproc(obs, pred))
+    assert np.array_equal(spec.targ_proc(obs, nxt), targ(obs, nxt))
+    assert np.array_equal(spec.obs_postproc(obs, spec.targ_proc(obs, nxt)), postproc(obs, targ(obs, nxt)))
+    np.testing.assert_allclose(spec.reward(obs, act, nxt), reward(obs, act, nxt), rtol=1e-12, atol=1e-12)
+    # float32: the kernels' grouping, term by term -- ((first pair's pre-step terms) - c ctrl) + bonus, then the rest in order
+    o32, n32, a32 = obs.astype(np.float32), nxt.astype(np.float32), act.astype(np.float32)
+    terms = decl["reward"]
+    head = FIRST_PAIR_GROUP[corner]
+    assert head == [k for k, t in enumerate(terms) if t["dim"] >> 1 == terms[0]["dim"] >> 1 and t.get("when", "obs") == "obs"]
+    f32 = np.float32
+
+    def t32(t):
+        x = (n32 if t.get("when", "obs") == "next_obs" else o32)[..., t["dim"]]
+        w = f32(t.get("w", 1.0))
+        if t["kind"] == "linear":
+            return w * x
+        if t["kind"] == "square":
+            return w * (x * x)
+        if t["kind"] == "abs":
+            return w * np.abs(x)
+        if t["kind"] == "inside":
+            return np.where((x > f32(t["lo"])) & (x < f32(t["hi"])), w, f32(0))
+        return w * ((x > f32(t["hi"])).astype(f32) + (x < f32(t["lo"])).astype(f32))
+    r = np.zeros(o32.shape[:-1], f32)
+    for i, k in enumerate(head):
+        r = t32(terms[k]) if i == 0 else r + t32(terms[k])
+    if decl.get("ctrl_cost", 0.0):
+        r = r - f32(decl["ctrl_cost"]) * np.sum(np.square(a32), -1)
+    if decl.get("bonus", 0.0):
+        r = r + f32(decl["bonus"])
+    for k, t in enumerate(terms):
+        if k not in head:
+            r = r + t32(t)
+    got = spec.reward(o32, a32, n32)
+    assert got.dtype == np.float32 and np.array_equal(got, r)
+
+
+def test_widest_header_masks_and_terms():
+    decl, spec = CORNER_DECLS["widest"], corner_spec("widest")
+    h = spec.header()
+    for k, v in (("D", 48), ("A", 24), ("P", 64), ("NTERMS", 32)):
+        assert "#define CADM_SPEC_%s %d\n" % (k, v) in h
+    masks = {k: int(re.search(r"#define CADM_SPEC_%s_MASK 0x([0-9a-f]{16})ull" % k, h).group(1), 16) for k in ("DROP", "SINCOS", "REPLACE")}
+    for name, field, value in (("DROP", "preproc", "drop"), ("SINCOS", "preproc", "sincos"), ("REPLACE", "postproc", "replace")):
+        want = {d for d in range(48) if decl[field][d] == value}
+        assert {d for d in range(64) if (masks[name] >> d) & 1} == want, name
+    assert {d for d in range(32, 48) if (masks["SINCOS"] >> d) & 1} == {32, 34, 37, 39, 42, 43, 45, 46, 47}
+    assert {d for d in range(32, 48) if (masks["DROP"] >> d) & 1} == {40}
+    assert {d for d in range(32, 48) if (masks["REPLACE"] >> d) & 1} == {33, 40, 47}
+    table = re.search(r"#define CADM_SPEC_TERMS (.*)\n", h).group(1)
+    got = [tuple(int(x) for x in e.split(",")[:3]) for e in re.findall(r"\{([^}]*)\}", table)]
+    assert got == [(TERMS[t["kind"]], t["dim"], WHEN[t.get("when", "obs")]) for t in decl["reward"]]
+    c = spec.to_c()
+    assert c.n_terms == 32 and list(c.term_dim)[:32] == [t["dim"] for t in decl["reward"]]
+    with pytest.raises(ValueError, match="33 reward terms, at most 32"):
+        EnvDecl(**dict(decl, reward=decl["reward"] + [dict(kind="linear", dim=0)]))
+
+
+# the widest spec in both noise modes that draw or read noise, every other corner in one mode (about 17 s of hipcc each)
+CORNER_MODULES = [("widest", 10, _lib.NOISE_PHILOX), ("widest", 10, _lib.NOISE_INJECT), ("widest", 0, _lib.NOISE_NONE),
+                  ("tiny", 10, _lib.NOISE_INJECT), ("odd_tail", 10, _lib.NOISE_PHILOX), ("first_next", 10, _lib.NOISE_NONE)]
+
+
+def test_jit_cross_compiles_the_corner_modules(tmp_path, monkeypatch):
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+    from cadm_amd import isa_check, jit
+    if not jit.hipcc() or not isa_check.find_objdump():
+        pytest.skip("hipcc / llvm-objdump not available")
+    monkeypatch.setenv("CADM_JIT_CACHE", str(tmp_path))
+    monkeypatch.setattr(jit, "_memo", {})
+    jit.cache_dir(), jit._build_key()
+
+    def build(job):
+        corner, C, noise = job
+        return jit.build(_lib.ENV_SPEC, C, 200, 4, _lib.ACT_KINDS["swish"], noise, spec=corner_spec(corner))
+    with ThreadPoolExecutor(max_workers=max(1, min(len(CORNER_MODULES), os.cpu_count() or 1))) as ex:
+        paths = list(ex.map(build, CORNER_MODULES))
+    for (corner, C, noise), path in zip(CORNER_MODULES, paths):
+        spec = corner_spec(corner)
+        rep = json.load(open(path + ".isa.json"))
+        assert rep["checked"] and rep["problems"] == 0 and rep["kernels"] >= 3, rep
+        # scratch use is a performance defect, not asserted: printed so that a change which moves the spills shows up
+        print("%s C=%d noise=%d: scratch %s" % (corner, C, noise, rep["scratch"] or "none"))
+        mod = ctypes.CDLL(path)
+        desc = (ctypes.c_int * 10)()
+        mod.cadm_jit_describe(desc)
+        assert desc[1] == _lib.ENV_SPEC and tuple(desc[8:10]) == spec.hash_words

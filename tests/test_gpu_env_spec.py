@@ -10,24 +10,20 @@ import ctypes
 
 import numpy as np
 import pytest
-import torch
 
 from cadm_amd import _lib, jit, synth
 from cadm_amd import planner as hplanner
-from cadm_amd.dynamics.mlp_cadm_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel
 from cadm_amd.env_spec import EnvDecl, restate
-from cadm_amd.policies.mpc_controller import MPCController
-from cadm_amd.samplers.model_sample_processor import ModelSampleProcessor
-from helpers import assert_close, make_engine, trunc_z
+from helpers import (FLAVOURS, _np, assert_close, check_class_api_on_spec, check_spec_training_step, close_but_jumps, make_engine,
+                     threshold_jump, trunc_z)
+from helpers import SPEC_CWD as CWD
+from helpers import SPEC_WD as WD
+from helpers import run_flavour as _run
+from helpers import spec_oracle as _oracle
 from oracle import nets as onets
 from oracle import planner as oplanner
-from oracle import train as otrain
 
 pytestmark = pytest.mark.gpu
-
-WD = (0.000025, 0.00005, 0.000075, 0.000075, 0.0001)
-CWD = (0.000025, 0.00005, 0.000075)
-FLAVOURS = ("1", "2", "3", "4")      # cooperative kernel with one / two row tiles, wave-tile kernel with 8 / 4 tiles per workgroup
 
 
 def hopper_like():
@@ -46,28 +42,6 @@ def small_vanilla():
     return EnvDecl(7, 1, preproc=["id", "id", "sincos", "id", "drop", "id", "id"],
                    reward=[dict(kind="linear", dim=0, when="next_obs"), dict(kind="square", dim=2, w=-0.1, when="next_obs"),
                            dict(kind="outside", dim=1, w=-1.0, lo=-1.5, hi=1.5, when="next_obs")], ctrl_cost=0.01)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _oracle(prob, spec, dt=np.float32):
-    o = dict(env=spec, ff=onets.cast_params(prob["ff"], dt), cp=None if prob["cp"] is None else onets.cast_params(prob["cp"], dt),
-             st=onets.cast_stats(prob["stats"], dt))
-    for k in ("obs", "cp_obs", "cp_act", "init_mean", "init_var"):
-        o[k] = prob[k].astype(dt)
-    return o
-
-
-def _run(eng, flavour, obs, ctx, acts, **kw):
-    eng.dev_set_rollout("xdl", row_tiles=int(flavour))
-    try:
-        rows, traj = eng.rollout_returns(obs, ctx, acts, want_traj=True, **kw)
-        torch.cuda.synchronize()
-        return _np(rows), _np(traj)
-    finally:
-        eng.dev_set_rollout("xdl", row_tiles=0)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -178,127 +152,33 @@ def test_new_env_planners_match_oracle(gpu, name, make, context, E, p, det):
     o = _oracle(prob, spec)
     ref, rinfo, _ = oplanner.cem_plan(spec, o["ff"], o["cp"], o["st"], o["obs"], o["cp_obs"], o["cp_act"], o["init_mean"], o["init_var"],
                                       z, eps, E, p, deterministic=det, return_info=True)
-    # An indicator term (inside / outside) jumps by its weight where a state sits on its threshold: a particle whose state lands
-    # within rounding of it may take the other side in the oracle.  Such a candidate is off by a multiple of w / p -- allowed for at
-    # most 1 % of the candidates, everything else at the usual bar (and the elite sets exactly).
-    jump = sum(abs(t[3]) for t in spec.terms if t[0] in ("inside", "outside")) * H / p
-
-    def close_but_jumps(got, want, what):
-        bad = np.abs(got - want) > 1e-4 * np.maximum(np.abs(want), np.sqrt(np.mean(want ** 2)))
-        assert bad.sum() <= 0.01 * bad.size, "%s: %d/%d candidates off" % (what, bad.sum(), bad.size)
-        assert (np.abs(got - want)[bad] <= jump + 1e-3).all(), "%s: off by more than one threshold flip" % what
+    jump = threshold_jump(spec, H, p)
     for it in range(5):
         np.testing.assert_array_equal(np.sort(_np(info[it]["elites"]), axis=1), np.sort(rinfo[it]["elites"], axis=1),
                                       err_msg="%s: elite set differs at CEM iteration %d" % (name, it))
-        close_but_jumps(_np(info[it]["cand"])[0], rinfo[it]["cand_returns"], "candidate returns it=%d" % it)
+        close_but_jumps(_np(info[it]["cand"])[0], rinfo[it]["cand_returns"], jump, "candidate returns it=%d" % it)
     assert_close(_np(plan), oplanner.get_action_clip(ref), 1e-4, "%s final CEM plan" % name)
     acts = rng.uniform(-1, 1, (m, n, H, A)).astype(np.float32)
     first, cand = hplanner.rs_plan(eng, prob["obs"], prob["cp_obs"], prob["cp_act"], n, actions=acts, eps=None if det else eng._t(eps[0]))
     rfirst, rcand = oplanner.rs_plan(spec, o["ff"], o["cp"], o["st"], o["obs"], o["cp_obs"], o["cp_act"], acts, eps[0], E, p, deterministic=det)
-    close_but_jumps(_np(cand)[0], rcand, "%s RS candidate returns" % name)
+    close_but_jumps(_np(cand)[0], rcand, jump, "%s RS candidate returns" % name)
     np.testing.assert_array_equal(_np(first), np.clip(rfirst, -1, 1))
     eng.close()
 
 
 @pytest.mark.parametrize("name,make,context,E,p,det", NEW)
 def test_new_env_training_step_matches_oracle(gpu, name, make, context, E, p, det):
-    """Losses and gradients against oracle/train.  The oracle's obs_preproc is picked by env name, so it is handed the spec's
-    preprocessed observations under an identity-preproc name: the same network inputs."""
+    """Losses and gradients against oracle/train (helpers.check_spec_training_step)."""
     spec = make()
-    B = 48
     prob = synth.make_problem(env=spec, context=context, E=E, trained_like=True, with_back=True, seed=61)
-    batch = synth.make_train_batch(prob, B=B, seed=2)
-    cfg = dict(deterministic=det, back_coeff=0.5, weight_decay_coeff=1.0, weight_decays=WD, context_weight_decays=CWD,
-               n_hidden=len(prob["hidden_sizes"]), n_cp_hidden=len(prob["cp_hidden_sizes"]))
-    keys = ["obs", "act", "delta", "obs_next", "back_delta"] + (["cp_obs", "cp_act"] if context else [])
-    tb = {k: torch.tensor(v, dtype=torch.float64) for k, v in batch.items()}
-    tb["obs"] = torch.tensor(spec.obs_preproc(batch["obs"]), dtype=torch.float64)
-    tb["obs_next"] = torch.tensor(spec.obs_preproc(batch["obs_next"]), dtype=torch.float64)
-
-    def oracle_nets(rg):
-        return (otrain.to_torch(prob["ff"], torch.float64, rg), otrain.to_torch(prob["back"], torch.float64, rg),
-                otrain.to_torch(prob["cp"], torch.float64, rg) if context else None, otrain.to_torch(prob["stats"], torch.float64))
-    eng = make_engine(prob, p=E, deterministic=det)
-    eng.train_configure(1e-3, WD, CWD, 1.0, 0.5, max_batch=B)
-    got = _np(eng.train_step({k: eng._t(batch[k]) for k in keys}, train=False))
-    ff, back, cp, st = oracle_nets(False)
-    ref = otrain.train_losses("slim_humanoid", ff, back, cp, st, tb, cfg)       # (identity obs_preproc)
-    np.testing.assert_allclose(got, [float(ref["mse"]), float(ref["back_mse"]), float(ref["recon"])], rtol=5e-5, atol=5e-5)
-    eng.close()
-    eng = make_engine(prob, p=E, deterministic=det)
-    eng.train_configure(1e6, WD, CWD, 1.0, 0.5, max_batch=B, beta1=0.0, beta2=0.0, epsilon=1e6)    # linearised Adam: g = w_before - w_after
-    before = {nn: {k: v.clone() for k, v in eng.nets[nn].items()} for nn in eng.net_names()}
-    eng.train_step({k: eng._t(batch[k]) for k in keys}, train=True)
-    ff, back, cp, st = oracle_nets(True)
-    out = otrain.train_losses("slim_humanoid", ff, back, cp, st, tb, cfg)
-    grads = otrain.grads_of(out["loss"], {"ff_model": ff, "backward_model": back, "context_model": cp})
-    for net in eng.net_names():
-        for pname, w0 in before[net].items():
-            g_ref = grads[net][pname]
-            g_hip = (w0 - eng.nets[net][pname]).cpu().numpy().astype(np.float64)
-            if g_ref is None:
-                assert np.abs(g_hip).max() == 0.0
-                continue
-            g_ref = g_ref.numpy()
-            err = np.abs(g_hip - g_ref).max() / max(np.abs(g_ref).max(), 1e-12)
-            assert err < 2e-3, "%s %s/%s gradient off: %.3e" % (name, net, pname, err)
-    eng.close()
+    check_spec_training_step(spec, prob, E, det, name)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # the class API on a spec env
 # ------------------------------------------------------------------------------------------------------------------------------
 def test_class_api_on_a_spec_env(gpu, tmp_path):
-    spec = hopper_like()
-
-    class HopperSim:                                     # a user's simulator: declares its closures, is no built-in class
-        cadm_env_spec = spec
-        observation_space, action_space, proc_observation_space_dims = spec.observation_space, spec.action_space, spec.proc_obs_dim
-        obs_preproc, obs_postproc, targ_proc, reward = spec.obs_preproc, spec.obs_postproc, spec.targ_proc, spec.reward
-
-    class Normalized:                                    # the reference's NormalizedEnv wrapper shape
-        def __init__(self, e):
-            self.wrapped_env = e
-            for k in ("observation_space", "action_space", "proc_observation_space_dims", "obs_preproc", "obs_postproc", "targ_proc", "reward"):
-                setattr(self, k, getattr(e, k))
-    env = Normalized(HopperSim())
-    D, A, Hh, F, H = 11, 3, 10, 10, 6
-    kw = dict(hidden_nonlinearity="swish", context_out_dim=10, n_forwards=H, n_candidates=64, ensemble_size=5, n_particles=10, use_cem=True,
-              batch_size=32, state_diff=1, normalize_input=True, back_coeff=0.5, weight_decays=WD, weight_decay_coeff=1.0,
-              context_weight_decays=CWD + (0.0001,), history_length=Hh, future_length=F)
-    model = MLPEnsembleCEMDynamicsModel("dyn", env, **kw)
-    assert model.engine.spec == spec
-    rng = np.random.default_rng(0)
-    paths = []
-    for L in (30, 45, 12):
-        obs = rng.standard_normal((L, D)).astype(np.float32)
-        paths.append(dict(observations=obs, actions=rng.uniform(-1, 1, (L, A)).astype(np.float32), rewards=rng.standard_normal(L),
-                          cp_obs=0.1 * rng.standard_normal((L, D * Hh)).astype(np.float32),
-                          cp_act=rng.uniform(-1, 1, (L, A * Hh)).astype(np.float32)))
-    d = ModelSampleProcessor(context=True, future_length=F).process_samples(paths)
-    model.fit(d["concat_obs"], d["concat_act"], d["concat_next_obs"], d["cp_observations"], d["cp_actions"], d["concat_bool"], epochs=3)
-    policy = MPCController("mpc", env, model, use_cem=True, n_candidates=64, horizon=H, num_rollouts=2, context=True)
-    o, cpo, cpa = rng.standard_normal((2, D)), 0.1 * rng.standard_normal((2, D * Hh)), rng.uniform(-1, 1, (2, A * Hh))
-    mean, var = np.zeros((2, H, A)), np.full((2, H, A), 0.25)
-    plan, _ = policy.get_actions(o, cpo, cpa, mean, var)
-    assert plan.shape == (2, H, A) and np.isfinite(plan).all() and np.abs(plan).max() <= 1.0
-    warm = np.concatenate([plan[:, 1:], np.zeros((2, 1, A))], axis=1)          # the samplers' CEM warm start
-    plan2, _ = policy.get_actions(o, cpo, cpa, warm, var)
-    assert np.isfinite(plan2).all()
-    from cadm_amd.caller import DevicePlannerState
-    assert DevicePlannerState(model, 2).eng.spec == spec          # the device-resident caller state builds on the same engine
-    mu, sd = model.predict(o, plan[:, 0], cpo, cpa, return_std=True)
-    assert np.isfinite(mu).all() and np.isfinite(sd).all() and (sd > 0).all()
-    cp = model.get_context_pred(cpo, cpa)
-    assert np.isfinite(np.asarray(cp)).all()
-    path = str(tmp_path / "params")
-    model.save(path)
-    model2 = MLPEnsembleCEMDynamicsModel("dyn", env, **kw)
-    model2.load(path)
-    model._call = model2._call = 7
-    a1 = model.get_action(o, cpo, cpa, warm, var)
-    a2 = model2.get_action(o, cpo, cpa, warm, var)
-    np.testing.assert_array_equal(a1, a2)
+    check_class_api_on_spec(hopper_like(), tmp_path, epochs=3)
 
 
 def test_vanilla_class_on_a_spec_env(gpu):
