@@ -49,19 +49,10 @@ void cadm_set_error(const char* fmt, ...);
 // ---------------------------------------------------------------------------------------------
 // env tables
 // ---------------------------------------------------------------------------------------------
-// CADM_ENV_SPEC: a side module built for one user-declared env carries its dims as compile-time constants (the generated
-// cadm_spec_tables.h, cadm_amd/jit.py); the library takes them from the ctx config (cadm_ctx_create) and never instantiates a kernel
-// for the spec kind.
-#ifdef CADM_JIT_SPEC
-#include "cadm_spec_tables.h"
-#else
-#define CADM_SPEC_D 0
-#define CADM_SPEC_A 0
-#define CADM_SPEC_P 0
-#endif
-__host__ __device__ constexpr int env_D(int k) { return k == CADM_ENV_SPEC ? CADM_SPEC_D : k == 0 ? 18 : k == 1 ? 28 : k == 2 ? 45 : k == 3 ? 4 : 3; }
-__host__ __device__ constexpr int env_A(int k) { return k == CADM_ENV_SPEC ? CADM_SPEC_A : k == 0 ? 6 : k == 1 ? 8 : k == 2 ? 17 : k == 3 ? 2 : 1; }
-__host__ __device__ constexpr int env_P(int k) { return k == CADM_ENV_SPEC ? CADM_SPEC_P : k == 0 ? 18 : k == 1 ? 27 : k == 2 ? 45 : k == 3 ? 4 : 3; }
+// env_D / env_A / env_P and the per-kind EnvTable.  A side module built for one user-declared env carries its dims as compile-time
+// constants (the generated cadm_spec_tables.h, cadm_amd/jit.py); the library takes them from the ctx config (cadm_ctx_create) and
+// never instantiates a kernel for the spec kind.
+#include "env_tables.h"
 
 // RNG stream tags (oracle/philox.py)
 #define CADM_STREAM_EPS 1u

@@ -415,14 +415,15 @@ __global__ __launch_bounds__(256) void rollout_kernel(const RolloutArgs a) {
                     }
                     if constexpr (ENV == CADM_ENV_CARTPOLE) {
                         if (t > 0) ret += reward_part<ENV>(dp, po[mt][pi][0], po[mt][pi][1], 0.0f);   // reads NEXT obs
-                    } else {
+                    } else {                                                                          // pre-step, then post-step terms
                         if (t < H) ret += reward_part<ENV>(dp, po[mt][pi][0], po[mt][pi][1], ctrl_s[(mt * 16 + arow) * H + t]);
+                        if constexpr (has_next<ENV>()) { if (t > 0) ret += spec_reward_next<ENV>(dp, po[mt][pi][0], po[mt][pi][1]); }
                     }
                     if (t < H) {
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
                             float sn = 0.0f, cs = 0.0f;
-                            if constexpr (ENV == CADM_ENV_HALFCHEETAH) {                 // the one trig pair (obs dim 2)
+                            if constexpr (has_sincos<ENV>()) {                           // halfcheetah's obs dim 2, a table's sincos dims
                                 if (fx_op[pi][h][0] != 0) sincos_cw(po[mt][pi][h], &sn, &cs);
                             }
 #pragma unroll

@@ -57,37 +57,23 @@ constexpr int rup(int a, int b) { return (a + b - 1) / b * b; }
 // env closures, compile-time per env kind.
 // The rollout state is tracked per DIM PAIR (2dp, 2dp+1): these tables say which input features
 // a dim feeds and which part of the reward a pair contributes.
+// A TABLE kind (env_tables.h EnvTable<ENV>: a user-declared env in the side module built for its spec, cadm_amd/jit.py) has its
+// closures evaluated from its table; everything below folds to constants of that table.  The five built-in kinds are hand-written.
 // ---------------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------------
-// CADM_ENV_SPEC: a user-declared env (include/cadm_hip.h cadm_env_spec, cadm_amd/env_spec.py).  A side module built for one spec
-// (cadm_amd/jit.py, -DCADM_JIT_SPEC) includes the data tables generated from it (cadm_spec_tables.h: macros only); everything below
-// folds to constants of that spec, as the built-in kinds' closures do.  Elsewhere the spec kind is never instantiated.
-// ---------------------------------------------------------------------------------------------
-struct SpecTerm { int kind, dim, when; float w, lo, hi; };
-#ifdef CADM_JIT_SPEC
-constexpr unsigned long long kSpecDrop = CADM_SPEC_DROP_MASK;        // bit d: obs dim d feeds no feature
-constexpr unsigned long long kSpecSincos = CADM_SPEC_SINCOS_MASK;    // bit d: obs dim d feeds sin, cos
-constexpr unsigned long long kSpecReplace = CADM_SPEC_REPLACE_MASK;  // bit d: next[d] = delta[d] (else obs[d] + delta[d])
-constexpr int kSpecNTerms = CADM_SPEC_NTERMS;
-constexpr SpecTerm kSpecTerms[CADM_SPEC_NTERMS + 1] = {CADM_SPEC_TERMS {0, 0, 0, 0.0f, 0.0f, 0.0f}};
-constexpr float kSpecCtrl = CADM_SPEC_CTRL, kSpecBonus = CADM_SPEC_BONUS;
-#else
-constexpr unsigned long long kSpecDrop = 0, kSpecSincos = 0, kSpecReplace = 0;
-constexpr int kSpecNTerms = 0;
-constexpr SpecTerm kSpecTerms[1] = {{0, 0, 0, 0.0f, 0.0f, 0.0f}};
-constexpr float kSpecCtrl = 0.0f, kSpecBonus = 0.0f;
-#endif
-constexpr bool spec_has_sincos() { return kSpecSincos != 0; }
-constexpr bool spec_has_next() {
-    for (int k = 0; k < kSpecNTerms; ++k) if (kSpecTerms[k].when == CADM_SPEC_WHEN_NEXT_OBS) return true;
+// obs dims feed sin / cos features: halfcheetah's dim 2, a table's sincos dims
+template <int ENV> constexpr bool has_sincos() { return ENV == CADM_ENV_HALFCHEETAH || EnvTable<ENV>::sincos != 0; }
+// a reward term reads the NEXT state
+template <int ENV> constexpr bool has_next() {
+    for (int k = 0; k < EnvTable<ENV>::nterms; ++k) if (EnvTable<ENV>::terms[k].when == CADM_SPEC_WHEN_NEXT_OBS) return true;
     return false;
 }
 // ctrl_cost and bonus ride on the pair of the first reward term (pair 0 without terms), in its pre-step part
-constexpr int spec_ctrl_pair() { return kSpecNTerms > 0 ? kSpecTerms[0].dim >> 1 : 0; }
+template <int ENV> constexpr int spec_ctrl_pair() { return EnvTable<ENV>::nterms > 0 ? EnvTable<ENV>::terms[0].dim >> 1 : 0; }
 // term k is the first of its (pair, when) group: the group's sum starts from it instead of from 0 (no 0 + x: bit-exact restatements)
-constexpr bool spec_first_in_group(int k) {
+template <int ENV> constexpr bool spec_first_in_group(int k) {
+    using T = EnvTable<ENV>;
     for (int j = 0; j < k; ++j)
-        if ((kSpecTerms[j].dim >> 1) == (kSpecTerms[k].dim >> 1) && kSpecTerms[j].when == kSpecTerms[k].when) return false;
+        if ((T::terms[j].dim >> 1) == (T::terms[k].dim >> 1) && T::terms[j].when == T::terms[k].when) return false;
     return true;
 }
 template <int KIND> __device__ __forceinline__ float spec_term_value(float x, float w, float lo, float hi) {
@@ -98,15 +84,15 @@ template <int KIND> __device__ __forceinline__ float spec_term_value(float x, fl
     else return w * ((x > hi ? 1.0f : 0.0f) + (x < lo ? 1.0f : 0.0f));
 }
 // sum of the terms of one `when` that read dim pair dp = (o0, o1), in declaration order
-template <int WHEN> __device__ __forceinline__ float spec_terms_sum(int dp, float o0, float o1) {
+template <int ENV, int WHEN> __device__ __forceinline__ float spec_terms_sum(int dp, float o0, float o1) {
     float s = 0.0f;
-    static_for(std::make_integer_sequence<int, kSpecNTerms>{}, [&](auto kc) {
+    static_for(std::make_integer_sequence<int, EnvTable<ENV>::nterms>{}, [&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        constexpr SpecTerm T = kSpecTerms[k];
+        constexpr EnvTerm T = EnvTable<ENV>::terms[k];
         if constexpr (T.when == WHEN) {
             if (dp == (T.dim >> 1)) {
                 const float v = spec_term_value<T.kind>((T.dim & 1) ? o1 : o0, T.w, T.lo, T.hi);
-                s = spec_first_in_group(k) ? v : s + v;
+                s = spec_first_in_group<ENV>(k) ? v : s + v;
             }
         }
     });
@@ -114,17 +100,20 @@ template <int WHEN> __device__ __forceinline__ float spec_terms_sum(int dp, floa
 }
 // the part of the step reward read from the NEXT state (terms with when = next_obs): added at loop step t > 0, whose state is step
 // t - 1's post-step state
-__device__ __forceinline__ float spec_reward_next(int dp, float o0, float o1) { return spec_terms_sum<CADM_SPEC_WHEN_NEXT_OBS>(dp, o0, o1); }
+template <int ENV> __device__ __forceinline__ float spec_reward_next(int dp, float o0, float o1) {
+    return spec_terms_sum<ENV, CADM_SPEC_WHEN_NEXT_OBS>(dp, o0, o1);
+}
 
 // features computed from obs dim d: index f[] in the preprocessed vector and op[] (0 id, 1 sin, 2 cos)
 template <int ENV> __device__ __forceinline__ int dim_feats(int d, int (&f)[2], int (&op)[2]) {
+    using T = EnvTable<ENV>;
     f[0] = f[1] = 0; op[0] = op[1] = 0;
-    if constexpr (ENV == CADM_ENV_SPEC) {             // features in dim order: drop 0, id 1, sincos 2 (sin, cos)
+    if constexpr (T::is_table) {                      // features in dim order: drop 0, id 1, sincos 2 (sin, cos)
         const unsigned long long below = (1ull << d) - 1ull;
-        const int f0 = __builtin_popcountll(~kSpecDrop & below) + __builtin_popcountll(kSpecSincos & below);
-        if ((kSpecDrop >> d) & 1ull) return 0;
+        const int f0 = __builtin_popcountll(~T::drop & below) + __builtin_popcountll(T::sincos & below);
+        if ((T::drop >> d) & 1ull) return 0;
         f[0] = f0;
-        if ((kSpecSincos >> d) & 1ull) { op[0] = 1; f[1] = f0 + 1; op[1] = 2; return 2; }
+        if ((T::sincos >> d) & 1ull) { op[0] = 1; f[1] = f0 + 1; op[1] = 2; return 2; }
         return 1;
     } else if constexpr (ENV == CADM_ENV_HALFCHEETAH) {      // half_cheetah_env.py:46-50: [o1, sin o2, cos o2, o3:]
         if (d == 0) return 0;
@@ -139,10 +128,10 @@ template <int ENV> __device__ __forceinline__ int dim_feats(int d, int (&f)[2], 
     }
 }
 
-// obs_postproc (half_cheetah_env.py:52-56, ant_env.py:55-59: [pred0, obs1: + pred1:]; others obs + pred)
+// obs_postproc (half_cheetah_env.py:52-56, ant_env.py:55-59: [pred0, obs1: + pred1:]; a table's replace dims; others obs + pred)
 template <int ENV> __device__ __forceinline__ float postproc(int d, float o, float delta) {
     if constexpr (ENV == CADM_ENV_HALFCHEETAH || ENV == CADM_ENV_ANT) return d == 0 ? delta : o + delta;
-    else if constexpr (ENV == CADM_ENV_SPEC) return ((kSpecReplace >> d) & 1ull) ? delta : o + delta;
+    else if constexpr (EnvTable<ENV>::replace != 0) return ((EnvTable<ENV>::replace >> d) & 1ull) ? delta : o + delta;
     else return o + delta;
 }
 
@@ -163,16 +152,17 @@ template <int ENV> __device__ __forceinline__ float ctrl_term(const float* a, in
 // Contribution of dim pair dp = (o0, o1) to the step reward; a row's reward is the sum over its pairs
 // (one non-zero contributor for halfcheetah / ant, so their summation order equals the reference's).
 // Obs are the PRE-step state, except cartpole whose reward reads the NEXT state.
-// CADM_ENV_SPEC: the pre-step part, ((terms) - c * ctrl) + bonus on the first term's pair (spec_reward_next adds the rest).
+// A table kind: the pre-step part, ((terms) - c * ctrl) + bonus on the first term's pair (spec_reward_next adds the rest).
 template <int ENV> __device__ __forceinline__ float reward_part(int dp, float o0, float o1, float ctrl) {
-    if constexpr (ENV == CADM_ENV_SPEC) {
-        float s = spec_terms_sum<CADM_SPEC_WHEN_OBS>(dp, o0, o1);
-        if (dp == spec_ctrl_pair()) {
-            if constexpr (kSpecCtrl != 0.0f) s = s - kSpecCtrl * ctrl;
-            if constexpr (kSpecBonus != 0.0f) s = s + kSpecBonus;
+    using T = EnvTable<ENV>;
+    if constexpr (T::is_table) {
+        float s = spec_terms_sum<ENV, CADM_SPEC_WHEN_OBS>(dp, o0, o1);
+        if (dp == spec_ctrl_pair<ENV>()) {
+            if constexpr (T::ctrl != 0.0f) s = s - T::ctrl * ctrl;
+            if constexpr (T::bonus != 0.0f) s = s + T::bonus;
         }
         return s;
-    } else if constexpr (ENV == CADM_ENV_HALFCHEETAH) {          // half_cheetah_env.py:82-88
+    } else if constexpr (ENV == CADM_ENV_HALFCHEETAH) {   // half_cheetah_env.py:82-88
         return dp == 0 ? o0 - 0.1f * ctrl : 0.0f;
     } else if constexpr (ENV == CADM_ENV_ANT) {           // ant_env.py:89-98
         return dp == 0 ? ((o0 + (-0.005f * ctrl)) + 0.0f) + 0.05f : 0.0f;

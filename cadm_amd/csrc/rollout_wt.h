@@ -343,20 +343,16 @@ __global__ __launch_bounds__(WT<G>::NTHR) void rollout_wt_kernel(const RolloutAr
                         // a row's return is summed over 16 pair slots (pair dp and dp + 16 share slot dp mod 16), in slot order: rollout_xdl.h
                         if constexpr (ENV == CADM_ENV_CARTPOLE) {
                             if (t > 0) retq[jj & 3] += reward_part<ENV>(dp, po[jj][0], po[jj][1], 0.0f);   // reads NEXT obs
-                        } else if constexpr (ENV == CADM_ENV_SPEC) {                                      // pre-step, then post-step terms
+                        } else {                                                                          // pre-step, then post-step terms
                             if (t < H) retq[jj & 3] += reward_part<ENV>(dp, po[jj][0], po[jj][1], ctrl_s[r * H + t]);
-                            if constexpr (spec_has_next()) { if (t > 0) retq[jj & 3] += spec_reward_next(dp, po[jj][0], po[jj][1]); }
-                        } else {
-                            if (t < H) retq[jj & 3] += reward_part<ENV>(dp, po[jj][0], po[jj][1], ctrl_s[r * H + t]);
+                            if constexpr (has_next<ENV>()) { if (t > 0) retq[jj & 3] += spec_reward_next<ENV>(dp, po[jj][0], po[jj][1]); }
                         }
                         if (t < H) {
 #pragma unroll
                             for (int h = 0; h < 2; ++h) {
                                 float sn = 0.0f, cs = 0.0f;
-                                if constexpr (ENV == CADM_ENV_HALFCHEETAH) {                 // the one trig pair (obs dim 2)
+                                if constexpr (has_sincos<ENV>()) {                           // halfcheetah's obs dim 2, a table's sincos dims
                                     if (ti_(22 + 2 * h) == 1) sincos_cw(po[jj][h], &sn, &cs);
-                                } else if constexpr (ENV == CADM_ENV_SPEC) {                 // the spec's sincos dims (rollout_env.h)
-                                    if constexpr (spec_has_sincos()) { if (ti_(22 + 2 * h) == 1) sincos_cw(po[jj][h], &sn, &cs); }
                                 }
 #pragma unroll
                                 for (int i = 0; i < 2; ++i) {

@@ -848,10 +848,8 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
                     }
                     if (t < H) {
                         float sn = 0.0f, cs = 0.0f;
-                        if constexpr (ENV == CADM_ENV_HALFCHEETAH) {                             // the one trig pair (obs dim 2)
+                        if constexpr (has_sincos<ENV>()) {                                       // halfcheetah's obs dim 2, a table's sincos dims
                             if (ti_(11) == 1) sincos_cw(po[0][0], &sn, &cs);
-                        } else if constexpr (ENV == CADM_ENV_SPEC) {                             // the spec's sincos dims (rollout_env.h)
-                            if constexpr (spec_has_sincos()) { if (ti_(11) == 1) sincos_cw(po[0][0], &sn, &cs); }
                         }
 #pragma unroll
                         for (int i = 0; i < 2; ++i) {
@@ -875,11 +873,9 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
                 if (feat && hh == 0) {
                     if constexpr (ENV == CADM_ENV_CARTPOLE) {
                         if (t > 0) ret += reward_part<ENV>(dp, po[0][0], o1, 0.0f);              // reads NEXT obs
-                    } else if constexpr (ENV == CADM_ENV_SPEC) {                                 // pre-step terms, then post-step terms (rollout_env.h)
+                    } else {                                                                     // pre-step terms, then post-step terms (rollout_env.h)
                         if (t < H) ret += reward_part<ENV>(dp, po[0][0], o1, ctrl_s[arow * H + t]);
-                        if constexpr (spec_has_next()) { if (t > 0) ret += spec_reward_next(dp, po[0][0], o1); }
-                    } else {
-                        if (t < H) ret += reward_part<ENV>(dp, po[0][0], o1, ctrl_s[arow * H + t]);
+                        if constexpr (has_next<ENV>()) { if (t > 0) ret += spec_reward_next<ENV>(dp, po[0][0], o1); }
                     }
                 }
             } else if (feat) {
@@ -915,20 +911,16 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
                     }
                     if constexpr (ENV == CADM_ENV_CARTPOLE) {
                         if (t > 0) ret += reward_part<ENV>(dp, po[pi][0], po[pi][1], 0.0f);   // reads NEXT obs
-                    } else if constexpr (ENV == CADM_ENV_SPEC) {                              // pre-step terms, then post-step terms (rollout_env.h)
+                    } else {                                                                  // pre-step terms, then post-step terms (rollout_env.h)
                         if (t < H) ret += reward_part<ENV>(dp, po[pi][0], po[pi][1], ctrl_s[arow * H + t]);
-                        if constexpr (spec_has_next()) { if (t > 0) ret += spec_reward_next(dp, po[pi][0], po[pi][1]); }
-                    } else {
-                        if (t < H) ret += reward_part<ENV>(dp, po[pi][0], po[pi][1], ctrl_s[arow * H + t]);
+                        if constexpr (has_next<ENV>()) { if (t > 0) ret += spec_reward_next<ENV>(dp, po[pi][0], po[pi][1]); }
                     }
                     if (t < H) {
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
                             float sn = 0.0f, cs = 0.0f;
-                            if constexpr (ENV == CADM_ENV_HALFCHEETAH) {                 // the one trig pair (obs dim 2)
+                            if constexpr (has_sincos<ENV>()) {                           // halfcheetah's obs dim 2, a table's sincos dims
                                 if (ti_(22 + 2 * h) == 1) sincos_cw(po[pi][h], &sn, &cs);
-                            } else if constexpr (ENV == CADM_ENV_SPEC) {                 // the spec's sincos dims (rollout_env.h)
-                                if constexpr (spec_has_sincos()) { if (ti_(22 + 2 * h) == 1) sincos_cw(po[pi][h], &sn, &cs); }
                             }
 #pragma unroll
                             for (int i = 0; i < 2; ++i) {

@@ -4,7 +4,7 @@ The reference's model class takes any env object that provides ``obs_preproc``, 
 ``tf_reward_fn()`` (cadm/dynamics/mlp_cadm_ensemble_cem_dynamics.py:95-102,185-187).  The HIP kernels cannot
 trace a Python closure, so an env that is not one of the compiled-in kinds (envs.CLASS_TO_KIND) describes its closures with an
 ``EnvDecl``; the library compiles them into a rollout module of its own (cadm_amd/jit.py: the generated ``cadm_spec_tables.h``
-feeds csrc/rollout_env.h) and uploads the preprocessing table the training kernels read (``cadm_set_env_spec``).
+feeds csrc/env_tables.h) and uploads the preprocessing table the training kernels read (``cadm_set_env_spec``).
 
 What a spec expresses (continuous actions only):
   * ``preproc``: per obs dim ``"id"``, ``"drop"`` or ``"sincos"`` (sin then cos); the features appear in dim order, P is their count;
@@ -155,7 +155,7 @@ class EnvDecl:
 
     # ------------------------------------------------------------------ what the library compiles
     def header(self):
-        """The generated cadm_spec_tables.h of a rollout module (cadm_amd/jit.py): data tables only, read by csrc/rollout_env.h."""
+        """The generated cadm_spec_tables.h of a rollout module (cadm_amd/jit.py): data tables only, read by csrc/env_tables.h."""
         def fl(x):
             return float(np.float32(x)).hex() + "f"
 
@@ -245,7 +245,8 @@ class EnvDecl:
 
 
 def restate(kind):
-    """The built-in kinds halfcheetah, ant and slim humanoid as specs (tests, tools; the library keeps their compiled-in kernels)."""
+    """The built-in kinds halfcheetah, ant and slim humanoid as specs: tests, tools, and the closures of envs.EnvSpec.  The library
+    keeps their hand-written kernels (profiles/env_tables_ab.md)."""
     if kind in ("halfcheetah", "cripple_halfcheetah"):      # half_cheetah_env.py:46-59,82-88
         return EnvDecl(18, 6, preproc=["drop", "id", "sincos"] + ["id"] * 15, postproc=["replace"] + ["add"] * 17,
                        reward=[dict(kind="linear", dim=0)], ctrl_cost=0.1)

@@ -12,9 +12,8 @@ Appendix B); any other env declares its closures (env_spec.EnvDecl, found throug
 synthetic workloads and by ``fit`` for its host-side (numpy, float64) target
 computation -- exactly what the reference does on the host (dynamics.py:399-407).
 """
-import numpy as np
-
 from ._lib import ENV_KINDS
+from .env_spec import EnvDecl, _Box, restate
 
 # reference env class name -> kind name (cadm/envs/*.py class definitions)
 CLASS_TO_KIND = {
@@ -29,13 +28,6 @@ CLASS_TO_KIND = {
 }
 
 
-class _Box:
-    def __init__(self, dim):
-        self.shape = (dim,)
-        self.low = -np.ones(dim)
-        self.high = np.ones(dim)
-
-
 class _Discrete:
     def __init__(self, n):
         self.shape = ()
@@ -43,39 +35,35 @@ class _Discrete:
 
 
 class EnvSpec:
-    """Simulator-free env stand-in: spaces + the four closures (numpy)."""
+    """Simulator-free env stand-in: spaces + the closures (numpy).  Halfcheetah, ant and slim humanoid take theirs from
+    env_spec.restate(kind), held privately: they expose no ``cadm_env_spec`` and keep resolving to their kind name, i.e. to the
+    kernels compiled into the library."""
 
     def __init__(self, kind):
         if kind not in ENV_KINDS:
             raise ValueError("unknown env kind %r (supported: %s)" % (kind, sorted(ENV_KINDS)))
         self.kind = kind
-        D, A, P, discrete = {
-            "halfcheetah": (18, 6, 18, False), "cripple_halfcheetah": (18, 6, 18, False),
-            "ant": (28, 8, 27, False), "slim_humanoid": (45, 17, 45, False),
-            "cartpole": (4, 2, 4, True), "pendulum": (3, 1, 3, False)}[kind]
-        self.observation_space = _Box(D)
-        self.action_space = _Discrete(A) if discrete else _Box(A)
-        self.proc_observation_space_dims = P
         self.cadm_env_kind = kind
+        if kind in ("cartpole", "pendulum"):            # outside what a spec expresses: identity preproc, next = obs + pred
+            D, A = (4, 2) if kind == "cartpole" else (3, 1)
+            self._decl = None
+            self.observation_space = _Box(D)
+            self.action_space = _Discrete(A) if kind == "cartpole" else _Box(A)
+            self.proc_observation_space_dims = D
+        else:
+            self._decl = restate(kind)
+            self.observation_space, self.action_space = self._decl.observation_space, self._decl.action_space
+            self.proc_observation_space_dims = self._decl.proc_obs_dim
 
     # --- closures (numpy, host side) ---
     def obs_preproc(self, obs):
-        if self.kind in ("halfcheetah", "cripple_halfcheetah"):
-            return np.concatenate([obs[..., 1:2], np.sin(obs[..., 2:3]), np.cos(obs[..., 2:3]),
-                                   obs[..., 3:]], axis=-1)
-        if self.kind == "ant":
-            return obs[..., 1:]
-        return obs
+        return self._decl.obs_preproc(obs) if self._decl else obs
 
     def obs_postproc(self, obs, pred):
-        if self.kind in ("halfcheetah", "cripple_halfcheetah", "ant"):
-            return np.concatenate([pred[..., :1], obs[..., 1:] + pred[..., 1:]], axis=-1)
-        return obs + pred
+        return self._decl.obs_postproc(obs, pred) if self._decl else obs + pred
 
     def targ_proc(self, obs, next_obs):
-        if self.kind in ("halfcheetah", "cripple_halfcheetah", "ant"):
-            return np.concatenate([next_obs[..., :1], next_obs[..., 1:] - obs[..., 1:]], axis=-1)
-        return next_obs - obs
+        return self._decl.targ_proc(obs, next_obs) if self._decl else next_obs - obs
 
 
 def make_env_spec(kind):
@@ -86,7 +74,6 @@ def resolve_env_kind(env):
     """Map an env object (reference env, NormalizedEnv wrapper, or EnvSpec) to a kind name -- or, for a user-declared env, to its
     ``EnvDecl`` (env_spec.py): the env or a wrapper in its ``wrapped_env`` chain carries it as an explicit ``cadm_env_spec``
     attribute (never inferred from the duck type)."""
-    from .env_spec import EnvDecl
     seen = 0
     e = env
     while e is not None and seen < 8:

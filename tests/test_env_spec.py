@@ -149,6 +149,30 @@ def test_header_and_hash():
     assert (lo & 0xFFFFFFFF) | ((hi & 0xFFFFFFFF) << 32) == a.hash64
 
 
+def test_env_spec_of_a_restated_kind_is_its_restated_spec():
+    """envs.EnvSpec of halfcheetah / ant / slim humanoid: dims and numpy closures of restate(kind) (bit for bit, float32 and float64),
+    but it resolves to its NAME (the kernels compiled into the library, no JIT build).  Cartpole and pendulum: identity closures."""
+    rng = np.random.default_rng(4)
+    for kind in KINDS + ("cripple_halfcheetah",):
+        env, spec = make_env_spec(kind), restate(kind)
+        assert not hasattr(env, "cadm_env_spec") and env.cadm_env_kind == env.kind == kind and resolve_env_kind(env) == kind
+        assert (env.observation_space.shape, env.action_space.shape, env.proc_observation_space_dims) == ((spec.obs_dim,), (spec.act_dim,), spec.proc_obs_dim)
+        ref = make_env(kind)
+        for dtype in (np.float32, np.float64):
+            obs, pred, nxt = (rng.standard_normal((3, 5, spec.obs_dim)).astype(dtype) for _ in range(3))
+            for mine, decl, theirs in ((env.obs_preproc(obs), spec.obs_preproc(obs), ref.obs_preproc(obs)),
+                                       (env.obs_postproc(obs, pred), spec.obs_postproc(obs, pred), ref.obs_postproc(obs, pred)),
+                                       (env.targ_proc(obs, nxt), spec.targ_proc(obs, nxt), ref.targ_proc(obs, nxt))):
+                assert mine.dtype == dtype and mine.shape == theirs.shape
+                assert np.array_equal(mine, decl) and np.array_equal(mine.view(np.uint8), theirs.view(np.uint8))
+    for kind, dims in (("cartpole", (4, 2, 4)), ("pendulum", (3, 1, 3))):
+        env = make_env_spec(kind)
+        A = env.action_space.n if kind == "cartpole" else env.action_space.shape[0]
+        assert (env.observation_space.shape[0], A, env.proc_observation_space_dims) == dims and resolve_env_kind(env) == kind
+        o, q = np.arange(dims[0], dtype=np.float64), np.ones(dims[0])
+        assert np.array_equal(env.obs_preproc(o), o) and np.array_equal(env.obs_postproc(o, q), o + q) and np.array_equal(env.targ_proc(o, q), q - o)
+
+
 def test_jit_cross_compiles_a_spec_module(tmp_path, monkeypatch):
     import json
     from cadm_amd import isa_check, jit
