@@ -221,7 +221,8 @@ int cadm_launch_plan_head(cadm_ctx* ctx, const float* host_block, int nfloats, c
                           uint32_t seed, uint32_t call, float* ctx_out, float* actions_out, hipStream_t s);
 void cadm_train_free(cadm_ctx* ctx);
 // (developer library: dev/dev_api.hip) Adam moment buffers of one trained tensor; layer as in cadm_set_weights, is_bias 0 / 1;
-// layer == -1 / -2: max_logvar / min_logvar of the forward net.  Returns null pointers before cadm_train_configure.
+// layer == -1 / -2: max_logvar / min_logvar of the forward net.  Returns null pointers before cadm_train_configure, and CADM_EINVAL
+// for a net id that is not one of CADM_NET_FF / BACK / CTX or a layer the net does not have.
 int cadm_train_adam_slot(cadm_ctx* ctx, int net, int layer, int is_bias, float** m, float** v, size_t* n);
 int cadm_dist_allgather(cadm_ctx* ctx, const float* send, float* recv, size_t count, hipStream_t s);
 

@@ -16,7 +16,7 @@ int cadm_dev_set_rollout(cadm_ctx* ctx, int kind, int row_tiles);
 int cadm_dev_set_timing_buffer(cadm_ctx* ctx, void* dev_u64_buf);
 /* Copy one Adam moment buffer (second == 0: first moment m, 1: second moment v) of a trained tensor into dst (device, n_floats =
  * the tensor's element count [E, in, out] / [E, out] / [D]).  layer as in cadm_set_weights; layer -1 / -2 = max / min_logvar
- * (CADM_NET_FF).  With beta1 = 0 the first moment after a step IS that step's gradient (m = 0 m + 1 g, exact): the tests read
+ * (CADM_NET_FF); any other net id or layer is refused.  With beta1 = 0 the first moment after a step IS that step's gradient (m = 0 m + 1 g, exact): the tests read
  * dL/dW and dL/db element by element this way (tests/test_gpu_train.py) instead of differencing weights. */
 /* The launcher's plan for a member of `units` CU shares of row tiles (csrc/xdl_geo.h: xdl_plan_units): count_out[4] = launches
  * (rounds) of {cooperative one tile, cooperative two tiles, wave-tile 4, wave-tile 8}.  Host logic only: no ctx, no device. */

@@ -260,7 +260,7 @@ def check_rollout_wt(sym, raw):
 # chain_kernel (training)
 # ---------------------------------------------------------------------------------------------------------------------------------
 def check_chain(sym, raw):
-    """The training chains' operand ring is a[0:63], named literally in inline asm (csrc/train.hip).  From the first ring load on, a0-a63
+    """The training chains' operand ring is a[0:63], named literally in inline asm (csrc/train_chain.h).  From the first ring load on, a0-a63
     hold operand blocks between one asm statement (the load) and another (the MFMAs): a value hipcc parks there would overwrite them.  In
     front of it -- the kernel prologue -- the ring is empty and hipcc may use the registers as it likes.  "From .. on" is decided by CONTROL
     FLOW: a block placed earlier in the image but executed after the ring prologue (a loop tail) counts."""

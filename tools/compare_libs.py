@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Bitwise comparison of two builds of the library on the same inputs (developer tool; needs a GPU):
    python tools/compare_libs.py libA.so libB.so      -- rollouts (returns + trajectories) and whole CEM plans over a set of
-problem shapes.  A schedule-only change of the rollout kernel must print 'identical' everywhere."""
+problem shapes, then the training step: the losses of three steps, every weight tensor afterwards, the prediction heads and one
+evaluation step.  A schedule-only change of a kernel, or a host-only change, must print 'identical' everywhere."""
 import os
 import sys
 
@@ -11,6 +12,7 @@ import numpy as np
 import torch
 
 from cadm_amd import _lib, synth
+from cadm_amd.env_spec import EnvDecl
 
 CASES = [  # env, context, hid, E, p, m, n, H, det
     ("halfcheetah", True, 200, 5, 20, 1, 200, 30, False),
@@ -24,6 +26,38 @@ CASES = [  # env, context, hid, E, p, m, n, H, det
     ("cartpole", True, 256, 2, 4, 1, 33, 9, False),
     ("halfcheetah", True, 512, 5, 5, 1, 40, 4, False),
 ]
+
+WD = (0.000025, 0.00005, 0.000075, 0.000075, 0.0001)
+CWD = (0.000025, 0.00005, 0.000075)
+SPEC = dict(obs_dim=11, act_dim=3, preproc=["drop", "sincos", "id", "id", "sincos"] + ["id"] * 6, postproc=["add"] * 5 + ["replace"] + ["add"] * 5,
+            reward=[dict(kind="linear", dim=5), dict(kind="square", dim=3, w=-0.5, when="next_obs")], ctrl_cost=0.001)     # a user-declared env
+TRAIN_CASES = [  # env, context + backward model, hidden sizes, E, B, det
+    ("halfcheetah", True, (200,) * 4, 5, 256, False),
+    ("halfcheetah", True, (200,) * 4, 5, 1856, False),            # the first batch size on the large-batch path at five members
+    ("halfcheetah", True, (200,) * 4, 5, 96, True),
+    ("ant", False, (200,) * 4, 5, 256, False),                    # vanilla: no context encoder, no backward model
+    ("spec", True, (200,) * 4, 5, 37, False),
+    ("slim_humanoid", True, (128, 200, 96, 200), 3, 100, False),  # unequal hidden widths, ragged row tile
+]
+
+
+def train_case(lib, env, full, hids, E, B, det):
+    """losses of three training steps, every weight tensor afterwards, the prediction heads, one evaluation step"""
+    prob = synth.make_problem(env=EnvDecl(**SPEC) if env == "spec" else env, context=full, E=E, hidden_sizes=hids, trained_like=True,
+                              with_back=full, seed=9)
+    batch = synth.make_train_batch(prob, B=B, seed=2)
+    keys = ["obs", "act", "delta"] + (["obs_next", "back_delta", "cp_obs", "cp_act"] if full else [])
+    eng = synth.make_engine(prob, p=E, deterministic=det, lib=lib)
+    eng.train_configure(1e-3, WD, CWD, 1.0, 0.5 if full else 0.0, max_batch=B)
+    dev = {k: eng._t(batch[k]) for k in keys}
+    res = [eng.train_step(dev, train=True).cpu().numpy() for _ in range(3)]
+    res += [v.cpu().numpy() for n in eng.net_names() for _, v in sorted(eng.nets[n].items())]
+    res += [x.cpu().numpy() for x in eng.predict_heads(batch["obs"], batch["act"], batch["cp_obs"] if full else None,
+                                                        batch["cp_act"] if full else None) if x is not None]
+    res.append(eng.train_step(dev, train=False).cpu().numpy())
+    torch.cuda.synchronize()
+    eng.close()
+    return res
 
 
 def main():
@@ -56,6 +90,12 @@ def main():
         bad += 0 if (same and finite) else 1
         print("%-14s ctx=%d hid=%d E=%d p=%d m=%d n=%d H=%d det=%d: %s%s" % (env, context, hid, E, p, m, n, H, det,
               "identical" if same else "DIFFERENT", "" if finite else " (non-finite!)"))
+    for case in TRAIN_CASES:
+        outs = [train_case(lib, *case) for lib in libs]
+        same = len(outs[0]) == len(outs[1]) and all(np.array_equal(x, y, equal_nan=True) for x, y in zip(*outs))
+        finite = all(np.isfinite(x).all() for x in outs[1])
+        bad += 0 if (same and finite) else 1
+        print("train %-14s ctx+back=%d hid=%s E=%d B=%d det=%d: %s%s" % (case + ("identical" if same else "DIFFERENT", "" if finite else " (non-finite!)")))
     sys.exit(1 if bad else 0)
 
 
