@@ -106,6 +106,9 @@ SIGNATURES = {
     "cadm_warm_start_shift": (_i, [_P, _P, _i, _P, _P, _P]),
     "cadm_history_update": (_i, [_P, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P, _P]),
     "cadm_build_windows": (_i, [_P, _P, _P, _P, _i, _i, _i, _i, _i, _P, _P, _P, _i, _i, _P, _P, _P, _P, _P, _P, _P]),
+    "cadm_horizon_error": (_i, [_P, _P, C.c_longlong, _P, _i, _i, _i, _i, _i, C.c_longlong, _P, C.c_longlong, _P, _P, _P, _P, _P, _i, _P]),
+    "cadm_eval_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
+    "cadm_eval_horizon": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _u32, _u32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cadm_dist_unique_id": (_i, [C.c_char_p]),
     "cadm_dist_init": (_i, [_P, C.c_char_p, _i, _i]),
     "cadm_dist_destroy": (_i, [_P]),

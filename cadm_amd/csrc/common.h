@@ -188,7 +188,8 @@ int cadm_pack_xdl(cadm_ctx* ctx, hipStream_t s);
 int cadm_launch_rollout(cadm_ctx* ctx, const float* obs, const float* obs_rows, const float* ctx_vec,
                         const float* actions, const float* eps, int norm_actions, uint32_t seed,
                         uint32_t call, int it, int cand_offset, int n_global, int m, int n_local,
-                        float* returns_rows, float* traj_out, hipStream_t s, int dry_run = 0, int force_deterministic = -1);
+                        float* returns_rows, float* traj_out, hipStream_t s, int dry_run = 0, int force_deterministic = -1,
+                        int horizon = 0);      // horizon > 0 (cadm_eval_horizon only): that many steps, actions [m,n_global,horizon,A]; 0: cfg.horizon
 // Sharded planner (capi.hip: cem_plan_impl): what the refit needs to REGENERATE the elites' action sequences by global
 // candidate id instead of reading them (a rank draws only its own shard), and to check the input checksums at the end of every rank's
 // all-gather payload.
@@ -204,8 +205,10 @@ struct RefitRegen {
 inline bool cadm_sharded(const cadm_ctx* c) { return c->comm != nullptr || c->ext_allgather != nullptr; }
 int cadm_launch_input_checksum(cadm_ctx* ctx, const float* obs, const float* cp_obs, const float* cp_act, const float* mean, const float* var,
                                int m, unsigned* out, hipStream_t s);
+// force_batched: take the GEMM-shaped encoder whatever m is (the per-row kernel of small calls sums in another order): a row's
+// context is then the same bits however the caller cuts its histories into calls (cadm_eval_horizon)
 int cadm_launch_context(cadm_ctx* ctx, const float* cp_obs, const float* cp_act, int m, int bs,
-                        float* out, hipStream_t s);
+                        float* out, hipStream_t s, int force_batched = 0);
 // Per-call inputs of a small planner call travel as KERNEL ARGUMENTS (cadm_cem_plan_staged, capi.hip): up to CADM_INGEST_MAX floats.
 #define CADM_INGEST_MAX 960
 struct IngestBlock { float v[CADM_INGEST_MAX]; };

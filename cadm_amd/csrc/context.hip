@@ -425,7 +425,7 @@ int cadm_launch_plan_head(cadm_ctx* ctx, const float* host_block, int nfloats, c
 }
 
 int cadm_launch_context(cadm_ctx* ctx, const float* cp_obs, const float* cp_act, int m, int bs, float* out,
-                        hipStream_t s) {
+                        hipStream_t s, int force_batched) {
     CpArgs a{};
     {
         const int rc = context_args(ctx, a);
@@ -433,7 +433,7 @@ int cadm_launch_context(cadm_ctx* ctx, const float* cp_obs, const float* cp_act,
     }
     a.cp_obs = cp_obs; a.cp_act = cp_act;
     a.m = m; a.bs = bs; a.out = out;
-    if (m >= CADM_CONTEXT_BATCHED_MIN_ROWS) {       // many histories per member: the GEMM-shaped path (weights reused across rows)
+    if (m >= CADM_CONTEXT_BATCHED_MIN_ROWS || force_batched) {       // many histories per member: the GEMM-shaped path (weights reused across rows)
         bool launched = false;
         const int rc = launch_context_batched(ctx, a, m, s, &launched);
         if (rc || launched) return rc;

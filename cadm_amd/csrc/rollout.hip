@@ -11,7 +11,7 @@ int cadm_rollout_env_pendulum(cadm_ctx*, const RolloutArgs&, int, hipStream_t);
 int cadm_launch_rollout(cadm_ctx* ctx, const float* obs, const float* obs_rows, const float* ctx_vec,
                         const float* actions, const float* eps, int norm_actions, uint32_t seed,
                         uint32_t call, int it, int cand_offset, int n_global, int m, int n_local,
-                        float* returns_rows, float* traj_out, hipStream_t s, int dry_run, int force_deterministic) {
+                        float* returns_rows, float* traj_out, hipStream_t s, int dry_run, int force_deterministic, int horizon) {
     RolloutArgs a{};
     const size_t xbytes = (size_t)ctx->xg.member_frags() * CADM_XDL_FRAG_BYTES * ctx->E;
     if (xbytes >= (1ull << 31)) {
@@ -33,12 +33,12 @@ int cadm_launch_rollout(cadm_ctx* ctx, const float* obs, const float* obs_rows, 
     a.maxlv = ctx->ff_maxlv; a.minlv = ctx->ff_minlv;
     a.returns_rows = returns_rows; a.traj = traj_out;
     a.m = m; a.n_local = n_local; a.n_global = n_global; a.cand_offset = cand_offset;
-    a.E = ctx->E; a.p = ctx->p; a.PE = ctx->p / ctx->E; a.H = ctx->H; a.NH = ctx->NH;
+    a.E = ctx->E; a.p = ctx->p; a.PE = ctx->p / ctx->E; a.H = horizon > 0 ? horizon : ctx->H; a.NH = ctx->NH;
     a.it = it; a.quirks = ctx->cfg.reference_quirks; a.deterministic = force_deterministic >= 0 ? force_deterministic : ctx->cfg.deterministic;   // (>= 0: cadm_rollout_check asks about a mode)
     a.norm_actions = norm_actions; a.seed = seed; a.call = call;
     a.tbuf = ctx->tbuf;
     const long long rows_total = (long long)m * n_global * ctx->p;
-    if (rows_total * ctx->H * ctx->A >= (1ll << 31) || rows_total * ctx->D * ctx->H >= (1ll << 31)) {
+    if (rows_total * a.H * ctx->A >= (1ll << 31) || rows_total * ctx->D * a.H >= (1ll << 31)) {
         cadm_set_error("rollout: problem too large for 32-bit row indexing (m*n*p = %lld)", rows_total);
         return CADM_EINVAL;
     }

@@ -201,6 +201,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
         self._call = 0
+        self._eval_call = 0             # evaluate_horizon's own noise counter: evaluations never shift get_action's draws
         self._checked_sig = None        # shape set of the last get_action whose inputs were checked
         self._group = process_group
         self._shard1 = None
@@ -446,6 +447,49 @@ class MLPEnsembleCEMDynamicsModel(object):
         valid_rows = self._row_index(ds["future_bool"], perm[:n_valid]) if n_valid > 0 else None
         return self._fit_loop(dev, train_rows, valid_rows, epochs, rolling_average_persitency, verbose, log_tabular, index_stream,
                               device_shuffle=not injected, keep_trace=keep_trace)
+
+    def evaluate_horizon(self, obs, act, obs_next, cp_obs, cp_act, future_bool, seed=None, chunk=4096):
+        """Open-loop prediction error along the horizon on held-out windows (no reference twin).  Takes the arrays `fit` takes
+        (future windows of F = future_length steps, F <= n_forwards).  Every window is rolled out from its first observation
+        through its recorded actions, F steps without correction, with the rows the planner scores (n_particles particles over
+        the ensemble, planning-time context layout and noise) -- all on the device; the trajectories never reach the host.
+        Step h of a window counts while future_bool[:, :h + 1] is all set.  Returns numpy arrays (NaN where count == 0):
+            mse [F,D]         squared error of the particle mean, averaged over the counted windows
+            member_mse [E,F,D]   the same for each member's own particles
+            spread [F,D]      mean biased variance over the particles (what the ensemble BELIEVES its error is)
+            rmse [F]          sqrt(mean over dims of mse)
+            count, diverged [F]   windows counted / left out because their trajectory was not finite
+        Uses the current normalisation statistics (RuntimeError when unset); leaves the dataset, weights, optimiser state and
+        get_action's noise sequence alone.  `seed`: Philox key of the noise (default: the model's, with a call counter of its own)."""
+        D, A, F, Hh = self.obs_space_dims, self.action_space_dims, self.future_length, self.history_length
+        assert obs.ndim == 2 and obs.shape[1] == D * F
+        assert obs_next.ndim == 2 and obs_next.shape[1] == D * F
+        assert act.ndim == 2 and act.shape[1] == A * F
+        assert cp_obs.ndim == 2 and cp_obs.shape[1] == D * Hh
+        assert cp_act.ndim == 2 and cp_act.shape[1] == A * Hh
+        assert future_bool.ndim == 2 and future_bool.shape[1] == F
+        if F > self.n_forwards:
+            raise ValueError("evaluate_horizon: future_length %d exceeds the planning horizon n_forwards %d" % (F, self.n_forwards))
+        N = obs.shape[0]
+        if N == 0:
+            raise ValueError("evaluate_horizon: no windows")
+        self._stats12()                 # (raises RuntimeError when no statistics are set)
+        self._push_stats()
+        eng = self.engine
+        dev = {k: eng._t(v) for k, v in (("obs", obs), ("act", act), ("obs_next", obs_next), ("cp_obs", cp_obs), ("cp_act", cp_act))}
+        dev["future_bool"] = eng._t(np.asarray(future_bool) > 0)
+        self._eval_call += 1
+        out = eng.eval_horizon(dev, N, F, chunk=int(chunk), seed=(self.seed if seed is None else int(seed)) & 0xFFFFFFFF,
+                               call=self._eval_call & 0xFFFFFFFF)
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        count = out["count"].astype(np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            n = np.where(count > 0, count, np.nan)[:, None]
+            mse = out["se"].astype(np.float64) / n
+            res = dict(mse=mse, member_mse=out["se_member"].astype(np.float64) / n[None], spread=out["spread"].astype(np.float64) / n,
+                       count=count, diverged=out["diverged"].astype(np.int64))
+            res["rmse"] = np.sqrt(mse.mean(axis=1))
+        return res
 
     _BATCH_KEYS = ("obs", "act", "delta", "obs_next", "back_delta", "cp_obs", "cp_act")
 

@@ -57,6 +57,16 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """reference :353-373: (obs_mean, obs_std, act_mean, act_std, delta_mean, delta_std)."""
         return self._stats12()[:6]
 
+    def evaluate_horizon(self, obs, act, obs_next, seed=None, chunk=4096):
+        """Prediction error on held-out samples with the planner's particles (see the CaDM class; a vanilla model's windows hold
+        one step, so F = 1)."""
+        N = obs.shape[0]
+        D, A = self.obs_space_dims, self.action_space_dims
+        assert obs.ndim == 2 and obs.shape[1] == D
+        assert obs_next.ndim == 2 and obs_next.shape[1] == D
+        assert act.ndim == 2 and act.shape[1] == A
+        return super().evaluate_horizon(obs, act, obs_next, np.zeros((N, 0)), np.zeros((N, 0)), np.ones((N, 1)), seed=seed, chunk=chunk)
+
     def fit(self, obs, act, obs_next, epochs=1000, compute_normalization=True, valid_split_ratio=None,
             rolling_average_persitency=None, verbose=False, log_tabular=False, max_logging=5000, rng=None, index_stream=None):
         """reference :209-323 (single-step samples, no history window)."""

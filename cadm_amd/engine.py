@@ -499,6 +499,55 @@ class HipEngine:
                                     ptr(raw), self.stream), "cadm_rs_plan")
         return raw if self.discrete else out
 
+    # ------------------------------------------------------------------ open-loop prediction error along the horizon
+    def _horizon_outputs(self, F, D):
+        z = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        return dict(se=z((F, D), torch.float32), spread=z((F, D), torch.float32), se_member=z((self.E, F, D), torch.float32),
+                    count=z((F,), torch.int32), diverged=z((F,), torch.int32))
+
+    def horizon_error(self, traj, truth, mask, calls=None):
+        """`cadm_horizon_error` on device tensors: traj [F,m,1,p,D] (or [F,m,p,D]), truth [m,F,D], mask [m,F] -> dict of device
+        tensors se / spread [F,D], se_member [E,F,D] (SUMS over the valid, finite windows) and count / diverged [F] int32.
+        `calls`: window counts (multiples of 64 but the last) to cut the windows into several stage-1 launches -- the result is the
+        same bits (tests, tools)."""
+        traj, truth, mask = self._t(traj), self._t(truth), self._t(mask)
+        F, m, p, D = traj.shape[0], traj.shape[1], traj.shape[-2], traj.shape[-1]
+        if tuple(truth.shape) != (m, F, D) or tuple(mask.shape) != (m, F) or traj.numel() != F * m * p * D:
+            raise ValueError("horizon_error: traj %r, truth %r, mask %r do not agree" % (tuple(traj.shape), tuple(truth.shape), tuple(mask.shape)))
+        blocks = (m + 63) // 64
+        partials = torch.empty((blocks * F * ((2 + self.E) * D + 2),), dtype=torch.float32, device=self.device)
+        out = self._horizon_outputs(F, D)
+        w0 = 0
+        for n in (calls or [m]):
+            # a launch reads its windows' [F, n, p, D] slice as one tensor
+            part = traj if n == m else traj.reshape(F, m, p, D)[:, w0:w0 + n].contiguous()
+            self._check(self.lib.cadm_horizon_error(ptr(part), ptr(truth[w0:]), F * D, ptr(mask[w0:]), n, F, p, self.E, D, w0, ptr(partials),
+                                                    blocks, ptr(out["se"]), ptr(out["spread"]), ptr(out["se_member"]), ptr(out["count"]),
+                                                    ptr(out["diverged"]), int(w0 + n >= m), self.stream), "cadm_horizon_error")
+            w0 += n
+        if w0 != m:
+            raise ValueError("horizon_error: calls %r do not add up to %d windows" % (calls, m))
+        return out
+
+    def eval_horizon(self, dev, N, F, chunk=4096, seed=0, call=0, eps=None):
+        """`cadm_eval_horizon` on the device-resident windowed dataset `dev` (what `fit` uploads: obs / obs_next [N,F*D], act
+        [N,F*A], cp_obs / cp_act [N,.], plus future_bool [N,F] float32) -> the dict of `horizon_error`.  eps: injected noise
+        [F,N,1,p,D] (parity tests)."""
+        if chunk <= 0 or chunk % 64:
+            raise ValueError("eval_horizon: chunk must be a positive multiple of 64, got %r" % (chunk,))
+        eps = None if eps is None else self._t(eps)
+        mc = min(int(chunk), (N + 63) // 64 * 64)
+        self.ensure_rollout(_lib.NOISE_NONE if self.deterministic else _lib.NOISE_INJECT if eps is not None else _lib.NOISE_PHILOX, min(mc, N), 1)
+        nbytes = self.lib.cadm_eval_workspace_bytes(self._ctx, int(N), int(F), int(chunk))
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
+        out = self._horizon_outputs(F, self.D)
+        g = lambda k: ptr(dev.get(k))
+        self._check(self.lib.cadm_eval_horizon(self._ctx, g("obs"), g("act"), g("obs_next"), g("cp_obs") if self.C > 0 else None,
+                                               g("cp_act") if self.C > 0 else None, g("future_bool"), int(N), int(F), int(chunk), seed, call,
+                                               ptr(eps), ptr(ws), ptr(out["se"]), ptr(out["spread"]), ptr(out["se_member"]), ptr(out["count"]),
+                                               ptr(out["diverged"]), self.stream), "cadm_eval_horizon")
+        return out
+
     # ------------------------------------------------------------------ training
     def train_configure(self, learning_rate, weight_decays, context_weight_decays, weight_decay_coeff, back_coeff,
                         max_batch, beta1=0.9, beta2=0.999, epsilon=1e-8):

@@ -329,6 +329,50 @@ int cadm_build_windows(const void* obs, const void* act, const void* cp_obs, con
                        void* concat_obs, void* concat_act, void* concat_next_obs, void* concat_bool, void* cp_obs_out,
                        void* cp_act_out, void* stream);
 
+/* Open-loop prediction error along the horizon: how far along the planner's rollouts the ensemble's trajectories still resemble
+ * held-out data (the planner scores candidates on n_forwards-step rollouts; training and validation see one step).
+ *
+ * cadm_horizon_error: the statistics of trajectories against truth, on the device.  Needs no ctx; asynchronous on `stream`.
+ *   traj   [F,m,1,p,D]  the layout of cadm_rollout_returns' traj_out (m windows, one candidate each)
+ *   truth  [m,F,D] read in place, `truth_row_stride` floats between windows (a slice of the dataset's obs_next: F * D)
+ *   mask   [m,F]   future_bool as float32 (non-zero = recorded step)
+ *   E              p % E == 0; particle j belongs to member j / (p / E), as in the rollout
+ * Step h of window i is VALID iff mask[i, 0..h] are all non-zero (a hole invalidates everything behind it).  A valid (window, step)
+ * with a non-finite value among its p * D trajectory values is left out of every sum and counted in diverged[h] instead.  Over the
+ * rest, fp32 SUMS (the caller divides by count):
+ *   se_out [F,D]           sum of (mean over the p particles - truth)^2
+ *   spread_out [F,D]       sum of the biased variance over the p particles
+ *   se_member_out [E,F,D]  sum of (mean over member e's p / E particles - truth)^2
+ *   count_out, diverged_out [F] int32
+ * Reduction contract: no floating-point atomics.  Stage 1 (every call) writes one partial per block of 64 consecutive windows and
+ * step into `partials` -- block b = windows [64 b, 64 b + 64) of the GLOBAL index window0 + i, window0 % 64 == 0 -- with a summation
+ * order inside the block that depends on (p, E, D) only.  Stage 2 (`finalize` != 0) adds the partials of blocks 0 .. (window0 + m
+ * + 63) / 64 - 1, i.e. all blocks written so far, in block order into the outputs.  Results are bit-identical run to run and do not
+ * depend on how the windows were cut into calls.  `partials`: partials_blocks * F * ((2 + E) * D + 2) 4-byte words.
+ * All argument checks run before any HIP call: null pointers, F, m, p, D >= 1, p % E == 0, window0 % 64 == 0, D <= 64,
+ * D * (p + E + 2) * 4 bytes within one LDS tile (48 KiB), the blocks within partials_blocks. */
+int cadm_horizon_error(const float* traj, const float* truth, long long truth_row_stride, const float* mask, int m, int F, int p,
+                       int E, int D, long long window0, float* partials, long long partials_blocks, float* se_out,
+                       float* spread_out, float* se_member_out, int32_t* count_out, int32_t* diverged_out, int finalize,
+                       void* stream);
+/* The same statistics for the ctx's model on a windowed dataset that is resident on the device (what `fit` uploads): ds_obs /
+ * ds_obs_next [N,F,D], ds_act [N,F,A], ds_cp_obs [N,D*Hh], ds_cp_act [N,A*Hh] (NULL when C == 0), future_bool [N,F] float32.
+ * Per chunk of `chunk` windows (a multiple of 64): the start states ds_obs[:,0,:] are gathered, the context encoder runs on the
+ * chunk's histories, ONE rollout of F steps replays the recorded actions (every window is an env with one candidate; F <=
+ * cfg.horizon, else CADM_EINVAL; the rollout runs F steps, not cfg.horizon), and stage 1 of cadm_horizon_error reduces its
+ * trajectories; stage 2 runs after the last chunk.  Everything is enqueued on `stream`; nothing is copied to the host.
+ * The rows are the rows the PLANNER scores: actions normalised as in planning and training, context laid out per the ctx's
+ * reference_quirks as at CEM iteration 0 (particle j of member j / (p / E) reads encoder j % E with quirks on), noise per the
+ * ctx's `deterministic` flag.  eps: injected N(0,1) [F,N,1,p,D], or NULL to draw from Philox keyed (seed, call); drawn noise is
+ * keyed by a row's position inside its chunk and the chunk's index, so with drawn noise the result depends on `chunk` (and on
+ * nothing else); with injected noise or a deterministic model it does not.  CADM_ENV_SPEC ctxs need their rollout module registered.
+ * workspace: device scratch of cadm_eval_workspace_bytes(ctx, N, F, chunk) bytes (0 for bad arguments). */
+size_t cadm_eval_workspace_bytes(cadm_ctx* ctx, int N, int F, int chunk);
+int cadm_eval_horizon(cadm_ctx* ctx, const float* ds_obs, const float* ds_act, const float* ds_obs_next, const float* ds_cp_obs,
+                      const float* ds_cp_act, const float* future_bool, int N, int F, int chunk, uint32_t seed, uint32_t call,
+                      const float* eps, void* workspace, float* se_out, float* spread_out, float* se_member_out,
+                      int32_t* count_out, int32_t* diverged_out, void* stream);
+
 /* Multi-GPU planning: candidates shard contiguously over the ranks of an RCCL communicator owned by the
  * ctx (one process per GPU).  The reference is single-device (cadm/trainers/mb_trainer.py:103-107); this
  * adds exactly one collective per CEM iteration -- ncclAllGather of the per-candidate returns
