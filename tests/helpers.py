@@ -76,6 +76,69 @@ def f16_split_saturating(x):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# the fused training step against the oracle: what tests/test_gpu_train.py and tests/test_gpu_train_state.py share
+# ------------------------------------------------------------------------------------------------------------------------------
+WD = (0.000025, 0.00005, 0.000075, 0.000075, 0.0001)      # run_cadm_pets.py:223
+CWD = (0.000025, 0.00005, 0.000075)                        # run_cadm_pets.py:232
+
+
+def _cfg(prob, det, back_coeff):
+    return dict(deterministic=det, back_coeff=back_coeff, weight_decay_coeff=1.0, weight_decays=WD,
+                context_weight_decays=CWD, n_hidden=len(prob["hidden_sizes"]), n_cp_hidden=len(prob["cp_hidden_sizes"]))
+
+
+def _oracle_nets(prob, dtype, requires_grad=True):
+    from oracle import train as otrain
+    ff = otrain.to_torch(prob["ff"], dtype, requires_grad)
+    back = otrain.to_torch(prob["back"], dtype, requires_grad) if prob.get("back") is not None else None
+    cp = otrain.to_torch(prob["cp"], dtype, requires_grad) if prob["cp"] is not None else None
+    st = otrain.to_torch(prob["stats"], dtype)
+    return ff, back, cp, st
+
+
+def _dev_batch(eng, batch, context, with_back):
+    keys = ["obs", "act", "delta"] + (["obs_next", "back_delta"] if with_back else []) + (["cp_obs", "cp_act"] if context else [])
+    return {k: eng._t(batch[k]) for k in keys}
+
+
+def _dev_engine(prob, p, **kw):
+    """An engine on the DEVELOPER library: the product's objects plus the hook that reads Adam's moment buffers."""
+    from cadm_amd import _lib
+    return make_engine(prob, p=p, lib=_lib.load_dev(), **kw)
+
+
+def _grad_report(g_hip, g_ref):
+    """(max |d| / max |ref|,  max elementwise |d| / |ref| over |ref| >= 0.25 rms(ref))"""
+    scale = max(np.abs(g_ref).max(), 1e-300)
+    d = np.abs(g_hip - g_ref)
+    big = np.abs(g_ref) >= 0.25 * np.sqrt(np.mean(g_ref ** 2))
+    return d.max() / scale, (d[big] / np.abs(g_ref[big])).max() if big.any() else 0.0
+
+
+def _check_gradients(eng, grads, what):
+    """Every gradient tensor the fused step produced, read back DIRECTLY (Adam's first moment after one step with beta1 = 0 is
+    the gradient, exactly: m = 0 m + 1 g) and compared element by element with torch.autograd on the fp64 oracle:
+    <= 1e-5 of the tensor's max, and <= 1e-4 PURE relative on every element with |g| >= 0.25 rms (fp32 forward / backward over a
+    256-row batch: roundoff-scale bars; a sign or scale error in any slice of any tensor fails them)."""
+    checked, worst = 0, (0.0, 0.0, "")
+    for net in eng.net_names():
+        for name in eng.nets[net]:
+            g_ref = grads[net][name]
+            if g_ref is None:      # TF skips variables without a gradient (backward model's logvar head, dynamics.py:213-240)
+                continue
+            g_hip = eng.dev_read_adam_moment(net, name).cpu().numpy().astype(np.float64)
+            assert np.isfinite(g_hip).all()
+            to_max, pure = _grad_report(g_hip, g_ref.numpy())
+            assert to_max <= 1e-5, "%s %s/%s gradient: max err %.2e of the tensor's max" % (what, net, name, to_max)
+            assert pure <= 1e-4, "%s %s/%s gradient: pure relative err %.2e on |g| >= 0.25 rms" % (what, net, name, pure)
+            if to_max > worst[0]:
+                worst = (to_max, pure, "%s/%s" % (net, name))
+            checked += 1
+    print("%s: %d gradient tensors, worst %.2e of max (pure-relative %.2e) at %s" % ((what, checked) + worst))
+    return checked
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # user-declared envs (cadm_amd/env_spec.py EnvDecl): what tests/test_gpu_env_spec.py and tests/test_gpu_env_spec_envelope.py share
 # ------------------------------------------------------------------------------------------------------------------------------
 SPEC_WD = (0.000025, 0.00005, 0.000075, 0.000075, 0.0001)

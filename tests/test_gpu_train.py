@@ -5,32 +5,11 @@ import pytest
 import torch
 
 from cadm_amd import synth
-from helpers import assert_close, make_engine, rel_err
+from helpers import (CWD, WD, _cfg, _check_gradients, _dev_batch, _dev_engine, _oracle_nets, assert_close, make_engine,
+                     rel_err)
 from oracle import train as otrain
 
 pytestmark = pytest.mark.gpu
-
-WD = (0.000025, 0.00005, 0.000075, 0.000075, 0.0001)      # run_cadm_pets.py:223
-CWD = (0.000025, 0.00005, 0.000075)                        # run_cadm_pets.py:232
-
-
-def _cfg(prob, det, back_coeff):
-    return dict(deterministic=det, back_coeff=back_coeff, weight_decay_coeff=1.0, weight_decays=WD,
-                context_weight_decays=CWD, n_hidden=len(prob["hidden_sizes"]), n_cp_hidden=len(prob["cp_hidden_sizes"]))
-
-
-def _oracle_nets(prob, dtype, requires_grad=True):
-    ff = otrain.to_torch(prob["ff"], dtype, requires_grad)
-    back = otrain.to_torch(prob["back"], dtype, requires_grad) if prob.get("back") is not None else None
-    cp = otrain.to_torch(prob["cp"], dtype, requires_grad) if prob["cp"] is not None else None
-    st = otrain.to_torch(prob["stats"], dtype)
-    return ff, back, cp, st
-
-
-def _dev_batch(eng, batch, context, with_back):
-    keys = ["obs", "act", "delta"] + (["obs_next", "back_delta"] if with_back else []) + (["cp_obs", "cp_act"] if context else [])
-    return {k: eng._t(batch[k]) for k in keys}
-
 
 CASES = [  # env, context, with_back, det, E, B
     ("halfcheetah", True, True, False, 5, 256),
@@ -56,43 +35,6 @@ def test_losses_match_oracle(gpu, env, context, with_back, det, E, B):
         ref = otrain.train_losses(env, ff, back, cp, st, tb, _cfg(prob, det, bc))
         want = np.array([float(ref["mse"]), float(ref["back_mse"]), float(ref["recon"])])
         np.testing.assert_allclose(got, want, rtol=tol, atol=tol, err_msg="losses vs %s oracle" % dt)
-
-
-def _dev_engine(prob, p, **kw):
-    """An engine on the DEVELOPER library: the product's objects plus the hook that reads Adam's moment buffers."""
-    from cadm_amd import _lib
-    return make_engine(prob, p=p, lib=_lib.load_dev(), **kw)
-
-
-def _grad_report(g_hip, g_ref):
-    """(max |d| / max |ref|,  max elementwise |d| / |ref| over |ref| >= 0.25 rms(ref))"""
-    scale = max(np.abs(g_ref).max(), 1e-300)
-    d = np.abs(g_hip - g_ref)
-    big = np.abs(g_ref) >= 0.25 * np.sqrt(np.mean(g_ref ** 2))
-    return d.max() / scale, (d[big] / np.abs(g_ref[big])).max() if big.any() else 0.0
-
-
-def _check_gradients(eng, grads, what):
-    """Every gradient tensor the fused step produced, read back DIRECTLY (Adam's first moment after one step with beta1 = 0 is
-    the gradient, exactly: m = 0 m + 1 g) and compared element by element with torch.autograd on the fp64 oracle:
-    <= 1e-5 of the tensor's max, and <= 1e-4 PURE relative on every element with |g| >= 0.25 rms (fp32 forward / backward over a
-    256-row batch: roundoff-scale bars; a sign or scale error in any slice of any tensor fails them)."""
-    checked, worst = 0, (0.0, 0.0, "")
-    for net in eng.net_names():
-        for name in eng.nets[net]:
-            g_ref = grads[net][name]
-            if g_ref is None:      # TF skips variables without a gradient (backward model's logvar head, dynamics.py:213-240)
-                continue
-            g_hip = eng.dev_read_adam_moment(net, name).cpu().numpy().astype(np.float64)
-            assert np.isfinite(g_hip).all()
-            to_max, pure = _grad_report(g_hip, g_ref.numpy())
-            assert to_max <= 1e-5, "%s %s/%s gradient: max err %.2e of the tensor's max" % (what, net, name, to_max)
-            assert pure <= 1e-4, "%s %s/%s gradient: pure relative err %.2e on |g| >= 0.25 rms" % (what, net, name, pure)
-            if to_max > worst[0]:
-                worst = (to_max, pure, "%s/%s" % (net, name))
-            checked += 1
-    print("%s: %d gradient tensors, worst %.2e of max (pure-relative %.2e) at %s" % ((what, checked) + worst))
-    return checked
 
 
 # chain kernel: 8 waves x 1 workgroup per CU (latency) / 4 waves x 3 per CU (throughput); + 16 + 64: the whole large-batch path forced at these
