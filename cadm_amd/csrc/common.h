@@ -287,9 +287,11 @@ __device__ __forceinline__ float sample_action(float mu, float var, const float*
 }
 
 
-// (return desc, index asc) as one ascending 64-bit key: reproduces tf.nn.top_k's order, ties -> lower index (core/utils.py:475)
+// (return desc, index asc) as one ascending 64-bit key: reproduces tf.nn.top_k's order, ties -> lower index (core/utils.py:475).
+// top_k compares by VALUE: -0.0 and +0.0 are a tie, so both take +0.0's key (no key of a non-zero return changes)
 __device__ __forceinline__ uint64_t make_key(float v, uint32_t idx) {
     uint32_t u = __float_as_uint(v);
+    if ((u & 0x7FFFFFFFu) == 0u) u = 0u;
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // ascending-orderable
     return ((uint64_t)(~u) << 32) | idx;               // ascending key == descending value, ties -> lower idx
 }

@@ -118,7 +118,7 @@ def cem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, seed=0, call=0
         elites = engine.cem_refit(cand, actions, mean, var, want_elites=return_info)
         if return_info:
             info.append(dict(actions=actions, rows=rows, cand=cand, elites=elites, mean=mean.clone(), var=var.clone()))
-    plan = mean if engine.discrete else mean.clamp(-1.0, 1.0)   # dynamics.py:365-366
+    plan = mean if engine.discrete else mean.clamp(float(engine.cfg.lower_bound), float(engine.cfg.upper_bound))   # dynamics.py:365-366
     return (plan, info, ctx_vec) if return_info else plan
 
 
@@ -136,4 +136,4 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
     if engine.discrete:
         raw = engine._t(raw, dtype=torch.int32)
         return raw[torch.arange(m, device=raw.device), best.long(), 0], cand
-    return first.clamp(-1.0, 1.0), cand
+    return first.clamp(float(engine.cfg.lower_bound), float(engine.cfg.upper_bound)), cand

@@ -185,15 +185,15 @@ def rollout_indexed(env, dyn, st, obs, T, actions, eps, E, p, deterministic, nor
 # ----------------------------------------------------------------------------
 # CEM pieces
 # ----------------------------------------------------------------------------
-def constrained_var(mean, var):  # utils.py:425-426
+def constrained_var(mean, var, lower=LOWER, upper=UPPER):  # utils.py:425-426
     dt = mean.dtype.type
-    lb_dist, ub_dist = mean - dt(LOWER), dt(UPPER) - mean
+    lb_dist, ub_dist = mean - dt(lower), dt(upper) - mean
     return np.minimum(np.minimum(np.square(lb_dist / dt(2)), np.square(ub_dist / dt(2))), var)
 
 
-def sample_actions(mean, var, z):  # utils.py:427-429
+def sample_actions(mean, var, z, lower=LOWER, upper=UPPER):  # utils.py:427-429
     """actions [m,n,H,A] = mean + sqrt(constrained_var) * z, z truncated standard normal."""
-    cvar = constrained_var(mean, var)
+    cvar = constrained_var(mean, var, lower, upper)
     return mean[:, None] + np.sqrt(cvar)[:, None] * z
 
 
@@ -220,8 +220,9 @@ def elite_refit(mean, var, actions, cand_returns, num_elites=NUM_ELITES, alpha=A
 
 def cem_plan(env, dyn, cp, st, obs, cp_obs, cp_act, init_mean, init_var, z, eps, E, p,
              deterministic=False, formulation="indexed", quirks=True, n_iters=NUM_CEM_ITERS,
-             num_elites=NUM_ELITES, return_info=False):
-    """Full CEM block (utils.py:398-488).  cp=None -> vanilla model (no context)."""
+             num_elites=NUM_ELITES, return_info=False, alpha=ALPHA, lower=LOWER, upper=UPPER):
+    """Full CEM block (utils.py:398-488).  cp=None -> vanilla model (no context).  n_iters / num_elites / alpha / lower / upper:
+    the block's constants (:391-396), read with other values."""
     m = obs.shape[0]
     ctx = None
     if cp is not None:
@@ -230,7 +231,7 @@ def cem_plan(env, dyn, cp, st, obs, cp_obs, cp_act, init_mean, init_var, z, eps,
     mean, var = init_mean, init_var
     info = []
     for it in range(n_iters):
-        actions = sample_actions(mean, var, z[it])
+        actions = sample_actions(mean, var, z[it], lower, upper)
         T = None
         ctx_rows = None
         if ctx is not None:
@@ -247,7 +248,7 @@ def cem_plan(env, dyn, cp, st, obs, cp_obs, cp_act, init_mean, init_var, z, eps,
             rets = rollout_indexed(env, dyn, st, obs, T, actions, eps[it], E, p, deterministic,
                                    ctx_rows=ctx_rows)
         cand = particle_mean(rets)
-        mean, var, idx = elite_refit(mean, var, actions, cand, num_elites)
+        mean, var, idx = elite_refit(mean, var, actions, cand, num_elites, alpha)
         if return_info:
             info.append(dict(actions=actions, returns=rets, cand_returns=cand, elites=idx,
                              mean=mean.copy(), var=var.copy()))
@@ -286,12 +287,12 @@ def rs_plan(env, dyn, cp, st, obs, cp_obs, cp_act, actions, eps, E, p, determini
     return actions[np.arange(m), best, 0], cand
 
 
-def get_action_clip(action, discrete=False):
-    """mlp_cadm_ensemble_cem_dynamics.py:365-366."""
+def get_action_clip(action, discrete=False, lower=LOWER, upper=UPPER):
+    """mlp_cadm_ensemble_cem_dynamics.py:365-366 (the literals -1.0 / 1.0 there are the CEM block's bounds)."""
     if discrete:
         return action
     dt = action.dtype.type
-    return np.minimum(np.maximum(action, dt(-1.0)), dt(1.0))
+    return np.minimum(np.maximum(action, dt(lower)), dt(upper))
 
 
 def warm_start_shift(prev_sol, sol):

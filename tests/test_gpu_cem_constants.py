@@ -1,0 +1,413 @@
+"""GPU: the CEM planner away from the reference's constants (K = 50, 5 iterations, alpha = 0.1, bounds +-1) and the staged call
+(`cadm_cem_plan_staged`) on each of its three input routes.
+
+Three kinds of check:
+  * the bookkeeping kernels of csrc/cem.hip (sampling, elite refit, clip) against the float64 oracle at the (HA, K, n) where they
+    change path: the fused kernel's K <= 64 limit, the grouped / sequential elite statistics, the counting / radix-select ranking;
+  * `eng.cem_plan` (one C call, fused refit + sample kernel where it applies) against the stepwise composition of the same primitives
+    (`cadm_amd.planner.cem_plan`), bit for bit;
+  * `eng.cem_plan_host` (the staged call) against `eng.cem_plan` on the same inputs, bit for bit.
+
+What these tests CANNOT see is which kernel ran: `profile_read` counts launches of the rollout kernel, and every path launches it
+once per CEM iteration.  The path of a case is therefore derived from the library's dispatch rules, restated here (`_fuses`, `_route`)
+and asserted on the case's shape; what is measured is that the result is right whichever path that is.
+"""
+import numpy as np
+import pytest
+
+from cadm_amd import _lib
+from cadm_amd import planner as hplanner
+from cadm_amd import synth
+from helpers import assert_close, make_engine, oracle_problem, trunc_z
+from oracle import planner as oplanner
+
+pytestmark = pytest.mark.gpu
+
+HID = (128,) * 4      # compiled into the library (no on-demand kernel build); the smallest of the built-in widths
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _bar(got, want):
+    """The smallest rtol `assert_close(got, want, rtol)` passes with."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    scale = max(float(np.sqrt(np.mean(want * want))), 1e-30)
+    return float((np.abs(got - want) / np.maximum(np.abs(want), scale)).max())
+
+
+def _fuses(K, n):
+    """csrc/cem.hip cadm_refit_sample_ok: a single-rank plan takes cem_refit_sample_kernel between its iterations."""
+    return n <= 256 and n >= K and K <= 64
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# refit and sampling against the float64 oracle
+# ------------------------------------------------------------------------------------------------------------------------------
+def _refit_inputs(env, H, n, seed, lower=-1.0, upper=1.0, m=2):
+    """float32 mean / var / candidate actions / returns of one refit, with exact ties among the returns (lower index first)."""
+    A = synth.ENV_SHAPES[env][1]
+    rng = np.random.default_rng(seed)
+    span = upper - lower
+    mean = rng.uniform(lower + 0.05 * span, upper - 0.05 * span, (m, H, A)).astype(np.float32)
+    var = rng.uniform(0.01, 0.3, (m, H, A)).astype(np.float32)
+    z = trunc_z(rng, (m, n, H, A)).astype(np.float32)
+    acts = oplanner.sample_actions(mean, var, z, lower, upper).astype(np.float32)
+    cand = rng.standard_normal((m, n)).astype(np.float32)
+    cand[0, 17] = cand[0, 3]
+    cand[1, 50] = cand[1, 20] = cand[1, 59]
+    return mean, var, z, acts, cand
+
+
+def _refit_engine(env, H, K, m=2, **kw):
+    prob = synth.make_problem(env=env, m=m, H=H, seed=6, hidden_sizes=HID)
+    return make_engine(prob, p=5, num_elites=K, **kw)
+
+
+def _run_refit(eng, mean, var, acts, cand, **kw):
+    mt, vt = eng._t(mean).clone(), eng._t(var).clone()
+    el = eng.cem_refit(eng._t(cand), eng._t(acts), mt, vt, want_elites=True, **kw)
+    return _np(el), _np(mt), _np(vt)
+
+
+def _oracle_refit(mean, var, acts, cand, K, alpha, dt=np.float64):
+    return oplanner.elite_refit(mean.astype(dt), var.astype(dt), acts.astype(dt), cand, num_elites=K, alpha=dt(alpha))
+
+
+REFIT_ROWS = [      # env, H, K, n, what it reaches
+    ("halfcheetah", 30, 80, 200, "grouped-all-16-slots"),      # HA = 180: KG = 5 groups x 16 register slots = 80 elites
+    ("halfcheetah", 30, 81, 200, "first-sequential-K"),        # KG * 16 < K
+    ("halfcheetah", 30, 1, 64, "K1-var-exact"),
+    ("halfcheetah", 30, 64, 64, "K-equals-n"),
+    ("halfcheetah", 4, 7, 300, "KG-equals-K-select"),          # HA = 24: 1024 / HA = 42 > K; n > 256: radix select
+    ("halfcheetah", 180, 16, 64, "HA1080-K16"),                # HA > 1024: one group; the fused kernel calls that `par`, this one does not
+    ("halfcheetah", 180, 50, 300, "HA1080-K50-select"),
+    ("pendulum", 30, 50, 100, "HA30-not-multiple-of-4"),
+]
+
+
+@pytest.mark.parametrize("env,H,K,n,what", REFIT_ROWS, ids=["%s-HA%d-K%d-n%d-%s" % (r[0], r[1] * synth.ENV_SHAPES[r[0]][1], r[2], r[3], r[4])
+                                                           for r in REFIT_ROWS])
+def test_refit_rows(gpu, env, H, K, n, what):
+    """`cem_refit` at the (HA, K, n) where cem_refit_kernel changes path, against the float64 oracle on the same float32 inputs:
+    elites exact and in order; mean within 1e-6 and var within 1e-5 of max(|ref|, rms(ref)) -- the bars of test_sample_and_refit.
+    No row needs a wider bar.  Measured on an MI355X, in assert_close's metric (mean / var): K = 80 1.7e-7 / 1.5e-7, K = 81
+    3.5e-7 / 3.5e-7, largest over the eight rows 3.6e-7 / 3.5e-7.  For scale, the float32 oracle's own error against float64 on the
+    same inputs (numpy's summation order) is 3.5e-7 / 3.9e-7 at K = 80, 3.5e-7 / 3.5e-7 at K = 81, at most 3.6e-7 / 3.9e-7 over
+    the rows: the rows on the sequential path reproduce it to the digit (same order of summation), the grouped ones sit below it."""
+    alpha = 0.1
+    mean, var, _, acts, cand = _refit_inputs(env, H, n, seed=1000 + 7 * K + n)
+    eng = _refit_engine(env, H, K)
+    el, gm, gv = _run_refit(eng, mean, var, acts, cand)
+    rm, rv, ridx = _oracle_refit(mean, var, acts, cand, K, alpha)
+    print("\n[%s] refit vs float64: mean %.2e, var %.2e" % (what, _bar(gm, rm), _bar(gv, rv)))
+    np.testing.assert_array_equal(el, ridx)
+    assert_close(gm, rm, 1e-6, "refit mean")
+    assert_close(gv, rv, 1e-5, "refit var")
+    if K == 1:      # the only elite is the mean: variance exactly 0, so var = alpha * var_in in ONE rounding
+        np.testing.assert_array_equal(gv, var * np.float32(alpha))
+    if K == n:      # every candidate is an elite
+        np.testing.assert_array_equal(np.sort(el, axis=1), np.tile(np.arange(n), (2, 1)))
+
+
+@pytest.mark.parametrize("alpha", [0.0, 1.0, 0.5])
+def test_refit_alpha(gpu, alpha):
+    """alpha = 1 keeps mean / var bit for bit (x * 1 + 0 * y); alpha = 0 returns the elites' statistics whatever the old mean /
+    var were; 0.5 is exact in float32, so only the statistics round."""
+    H, K, n = 30, 50, 200
+    mean, var, _, acts, cand = _refit_inputs("halfcheetah", H, n, seed=77)
+    eng = _refit_engine("halfcheetah", H, K, alpha=alpha)
+    el, gm, gv = _run_refit(eng, mean, var, acts, cand)
+    rm, rv, ridx = _oracle_refit(mean, var, acts, cand, K, alpha)
+    np.testing.assert_array_equal(el, ridx)
+    print("\n[alpha=%g] refit vs float64: mean %.2e, var %.2e" % (alpha, _bar(gm, rm), _bar(gv, rv)))
+    assert_close(gm, rm, 1e-6, "refit mean")
+    assert_close(gv, rv, 1e-5, "refit var")
+    if alpha == 1.0:
+        np.testing.assert_array_equal(gm, mean)
+        np.testing.assert_array_equal(gv, var)
+    if alpha == 0.0:
+        elites = np.take_along_axis(acts.astype(np.float64), ridx[:, :, None, None], axis=1)
+        assert_close(gm, elites.mean(1).reshape(gm.shape), 1e-6, "alpha = 0: the elites' mean")
+        assert_close(gv, elites.var(1).reshape(gv.shape), 1e-5, "alpha = 0: the elites' biased variance")
+        _, gm2, gv2 = _run_refit(eng, -mean, 3.0 * var, acts, cand)
+        np.testing.assert_array_equal(gm2, gm)
+        np.testing.assert_array_equal(gv2, gv)
+
+
+@pytest.mark.parametrize("n", [200, 300], ids=["n200-counting", "n300-select"])
+@pytest.mark.parametrize("K", [1, 50])
+def test_refit_signed_zero_is_a_tie(gpu, K, n):
+    """-0.0 at candidate 3 and +0.0 at candidate 40 of env 0 sit on the elite boundary: K - 1 returns are positive, every other one is
+    negative, so exactly one of the two zeros is an elite.  tf.nn.top_k and the oracle compare values -- a tie, the lower index
+    wins: candidate 3.  (A key made of the raw bit pattern sorts +0.0 strictly above -0.0 and picks 40.)  Env 1 has the signs
+    the other way round and a third zero that must stay out."""
+    H = 4
+    mean, var, _, acts, cand = _refit_inputs("halfcheetah", H, n, seed=5 + n)
+    cand = -np.abs(cand) - np.float32(0.01)
+    pos = [i for i in range(60, 60 + 2 * K, 2)][:K - 1]
+    cand[:, pos] = np.float32(1.0) + np.arange(K - 1, dtype=np.float32)[::-1] * np.float32(0.5)
+    cand[0, 3], cand[0, 40] = -0.0, 0.0
+    cand[1, 5], cand[1, 41], cand[1, 58] = 0.0, -0.0, -0.0
+    assert np.signbit(cand[0, 3]) and not np.signbit(cand[0, 40])
+    eng = _refit_engine("halfcheetah", H, K)
+    el, gm, gv = _run_refit(eng, mean, var, acts, cand)
+    rm, rv, ridx = _oracle_refit(mean, var, acts, cand, K, 0.1)
+    assert ridx[0, K - 1] == 3 and ridx[1, K - 1] == 5
+    np.testing.assert_array_equal(el, ridx)
+    assert_close(gm, rm, 1e-6, "refit mean")
+    assert_close(gv, rv, 1e-5, "refit var")
+
+
+BOUNDS = [(-0.5, 2.0), (0.25, 0.75)]
+
+
+@pytest.mark.parametrize("lower,upper", BOUNDS)
+def test_sampling_and_regen_with_bounds(gpu, lower, upper):
+    """`sample_action`'s constrained variance and the regenerating refit read the ctx's bounds: injected z against the oracle with the same
+    bounds at 1e-6, means ON a bound (constrained variance 0: the action is the mean) and 5e-4 inside one; device-drawn samples stay
+    inside the bounds; a refit that draws its elites again equals the refit that reads them, bit for bit."""
+    H, K, n = 30, 50, 100
+    mean, var, z, _, cand = _refit_inputs("halfcheetah", H, n, seed=31, lower=lower, upper=upper)
+    lo32, hi32 = np.float32(lower), np.float32(upper)
+    mean[0, 0, 0], mean[0, 0, 1], mean[1, 29, 5], mean[1, 29, 4] = lo32, hi32, lo32, hi32
+    mean[0, 1, 0], mean[0, 1, 1], mean[1, 2, 3], mean[1, 2, 4] = lo32 + np.float32(5e-4), hi32 - np.float32(5e-4), lo32 + np.float32(1e-4), hi32 - np.float32(9e-4)
+    eng = _refit_engine("halfcheetah", H, K, lower_bound=lower, upper_bound=upper)
+    got = _np(eng.sample_actions(mean, var, n, z=z))
+    ref = oplanner.sample_actions(mean.astype(np.float64), var.astype(np.float64), z.astype(np.float64), lower, upper)
+    print("\n[bounds %g %g] sample_actions vs float64: %.2e" % (lower, upper, _bar(got, ref)))
+    assert_close(got, ref, 1e-6, "sample_actions with bounds")
+    for (mi, t, a) in ((0, 0, 0), (0, 0, 1), (1, 29, 5), (1, 29, 4)):
+        np.testing.assert_array_equal(got[mi, :, t, a], np.full(n, mean[mi, t, a]))
+    # the bounds bite: with +-1 these means would give other actions
+    assert not np.allclose(got, oplanner.sample_actions(mean.astype(np.float64), var.astype(np.float64), z.astype(np.float64)), atol=1e-3)
+    drawn = eng.sample_actions(mean, var, n, seed=11, call=3, it=2)
+    d = _np(drawn)
+    assert d.min() >= lo32 and d.max() <= hi32, "device-drawn candidates leave [%g, %g]: %r .. %r" % (lower, upper, d.min(), d.max())
+    assert np.unique(d[0, :, 5, 2]).size > n // 2
+    m1, v1 = eng._t(mean).clone(), eng._t(var).clone()
+    e1 = eng.cem_refit(eng._t(cand), drawn, m1, v1, want_elites=True)
+    m2, v2 = eng._t(mean).clone(), eng._t(var).clone()
+    e2 = eng.cem_refit(eng._t(cand), drawn, m2, v2, want_elites=True, regen=(11, 3, 2))
+    np.testing.assert_array_equal(_np(e1), _np(e2))
+    np.testing.assert_array_equal(_np(m1), _np(m2))
+    np.testing.assert_array_equal(_np(v1), _np(v2))
+    rm, rv, ridx = _oracle_refit(mean, var, d, cand, K, 0.1)
+    np.testing.assert_array_equal(_np(e1), ridx)
+    assert_close(_np(m1), rm, 1e-6, "refit mean")
+    assert_close(_np(v1), rv, 1e-5, "refit var")
+
+
+def test_refusals_leave_the_engine_usable(gpu):
+    """num_elites = 0 is refused at construction; n < num_elites by cem_refit, cem_plan and cem_plan_host (tf.nn.top_k would fail);
+    the valid call after each refusal returns what an engine that never saw one returns."""
+    prob = synth.make_problem(env="halfcheetah", m=2, H=6, seed=21, hidden_sizes=HID)
+    with pytest.raises(_lib.CadmError, match="bad CEM constants"):
+        make_engine(prob, p=10, num_elites=0)
+    eng, twin = make_engine(prob, p=10), make_engine(prob, p=10)
+    args = (prob["obs"], prob["cp_obs"], prob["cp_act"], prob["init_mean"], prob["init_var"])
+    msg = "n_candidates 40 < num_elites 50"
+    rng = np.random.default_rng(0)
+    with pytest.raises(_lib.CadmError, match=msg):
+        eng.cem_refit(eng._t(rng.standard_normal((2, 40))), eng._t(rng.uniform(-1, 1, (2, 40, 6, 6))), eng._t(prob["init_mean"]).clone(),
+                      eng._t(prob["init_var"]).clone())
+    with pytest.raises(_lib.CadmError, match=msg):
+        eng.cem_plan(*args, 40, seed=2, call=5)
+    np.testing.assert_array_equal(_np(eng.cem_plan(*args, 64, seed=2, call=5)), _np(twin.cem_plan(*args, 64, seed=2, call=5)))
+    with pytest.raises(_lib.CadmError, match=msg):
+        eng.cem_plan_host(args, 40, seed=2, call=6)
+    a, b = eng.cem_plan_host(args, 64, seed=2, call=6), twin.cem_plan_host(args, 64, seed=2, call=6)
+    assert np.isfinite(a).all()
+    np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(a, _np(twin.cem_plan(*args, 64, seed=2, call=6)))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# one call == the stepwise composition, at non-default constants
+# ------------------------------------------------------------------------------------------------------------------------------
+PLAN_CASES = {      # id -> dict(env, E, p, H, n, engine constants); m = 2
+    "K1-n128": dict(n=128, num_elites=1),
+    "K16-n128": dict(n=128, num_elites=16),
+    "K64-n128-last-fused-K": dict(n=128, num_elites=64),
+    "K65-n128-first-unfused-K": dict(n=128, num_elites=65),
+    "K64-n64-every-candidate-an-elite": dict(n=64, num_elites=64),
+    "K50-n256-last-fused-n": dict(n=256),
+    "K50-n257-first-unfused-n": dict(n=257),
+    "iters1-no-fused-step": dict(n=100, num_cem_iters=1),
+    "iters2-one-fused-step": dict(n=100, num_cem_iters=2),
+    "p32-E4-eight-float4": dict(n=100, E=4, p=32),
+    "p40-E5-scalar-sum": dict(n=100, E=5, p=40),
+    "pendulum-HA7-last-workgroup-owns-3": dict(n=100, env="pendulum", H=7),
+    "HA1080-K16-n64": dict(n=64, H=180, num_elites=16),
+    "bounds-0.5-2": dict(n=100, lower_bound=-0.5, upper_bound=2.0),
+}
+
+
+@pytest.mark.parametrize("case", sorted(PLAN_CASES))
+def test_plan_equals_stepwise(gpu, case):
+    """`cadm_cem_plan` == sample / rollout / particle mean / refit one iteration at a time, bit for bit.  Which of the two forms the
+    one call took (cem_refit_sample_kernel between iterations, or sample + refit) is decided by `_fuses`; `profile_read` cannot
+    tell them apart (the rollout kernel is launched once per iteration in both), so the launch count is asserted only as that."""
+    c = dict(PLAN_CASES[case])
+    env, E, p, H, n = c.pop("env", "halfcheetah"), c.pop("E", 5), c.pop("p", 10), c.pop("H", 10), c.pop("n")
+    prob = synth.make_problem(env=env, E=E, m=2, H=H, seed=5, hidden_sizes=HID)
+    eng = make_engine(prob, p=p, **c)
+    K, iters = c.get("num_elites", 50), c.get("num_cem_iters", 5)
+    assert _fuses(K, n) == (case.find("unfused") < 0)
+    args = (prob["obs"], prob["cp_obs"], prob["cp_act"], prob["init_mean"], prob["init_var"])
+    eng.profile_enable(True)
+    a = _np(eng.cem_plan(*args, n, seed=9, call=4))
+    assert eng.profile_read()[1] == iters
+    eng.profile_enable(False)
+    b = _np(hplanner.cem_plan(eng, *args, n, seed=9, call=4))
+    assert np.isfinite(a).all() and np.abs(a).max() > 0
+    np.testing.assert_array_equal(a, b)
+    lo, hi = c.get("lower_bound", -1.0), c.get("upper_bound", 1.0)
+    assert a.min() >= lo and a.max() <= hi
+    if "lower_bound" in c:      # the bounds are read: the same call with +-1 plans something else
+        ref = _np(make_engine(prob, p=p).cem_plan(*args, n, seed=9, call=4))
+        assert not np.array_equal(a, ref)
+
+
+@pytest.mark.parametrize("case,kw", [("K16-iters2", dict(num_elites=16, num_cem_iters=2)), ("bounds-0.5-2", dict(lower_bound=-0.5, upper_bound=2.0))],
+                         ids=["K16-iters2", "bounds-0.5-2"])
+def test_plan_injected_against_oracle(gpu, case, kw):
+    """test_cem_plan_injected at other constants: injected z / eps, against the float32 oracle with the same constants -- elite sets
+    identical per iteration, candidate returns and the final (clipped) plan within that test's 1e-4."""
+    E, p, m, n, H = 5, 10, 2, 64, 8
+    prob = synth.make_problem(env="halfcheetah", E=E, m=m, H=H, seed=8, hidden_sizes=HID)
+    eng = make_engine(prob, p=p, **kw)
+    iters, K = kw.get("num_cem_iters", 5), kw.get("num_elites", 50)
+    lo, hi = kw.get("lower_bound", -1.0), kw.get("upper_bound", 1.0)
+    rng = np.random.default_rng(12)
+    z = trunc_z(rng, (iters, m, n, H, 6)).astype(np.float32)
+    eps = rng.standard_normal((iters, H, m, n, p, 18)).astype(np.float32)
+    init_mean = rng.uniform(lo + 0.2 * (hi - lo), hi - 0.2 * (hi - lo), (m, H, 6)).astype(np.float32)
+    plan, info, ctx = hplanner.cem_plan(eng, prob["obs"], prob["cp_obs"], prob["cp_act"], init_mean, prob["init_var"], n,
+                                        z=eng._t(z), eps=eng._t(eps), return_info=True)
+    o = oracle_problem(prob, np.float32)
+    ref, rinfo, rctx = oplanner.cem_plan(o["env"], o["ff"], o["cp"], o["st"], o["obs"], o["cp_obs"], o["cp_act"], init_mean, o["init_var"],
+                                         z, eps, E, p, formulation="literal", return_info=True, n_iters=iters, num_elites=K,
+                                         alpha=0.1, lower=lo, upper=hi)
+    assert len(info) == iters == len(rinfo)
+    for it in range(iters):
+        assert _np(info[it]["elites"]).shape == (m, K)
+        np.testing.assert_array_equal(np.sort(_np(info[it]["elites"]), axis=1), np.sort(rinfo[it]["elites"], axis=1),
+                                      err_msg="elite set differs at CEM iteration %d" % it)
+        assert_close(_np(info[it]["cand"])[0], rinfo[it]["cand_returns"], 1e-4, "candidate returns it=%d" % it)
+    want = oplanner.get_action_clip(ref, lower=lo, upper=hi)
+    print("\n[%s] final plan vs float32 oracle: %.2e" % (case, _bar(_np(plan), want)))
+    assert_close(_np(plan), want, 1e-4, "final CEM plan")
+    assert _np(plan).min() >= lo and _np(plan).max() <= hi
+
+
+def test_random_shooting_with_bounds(gpu):
+    """The random-shooting clip reads the ctx's bounds: the best candidate's first action equals the oracle's clipped to (-0.5, 2.0)."""
+    E, p, m, n, H = 5, 5, 2, 40, 6
+    lo, hi = -0.5, 2.0
+    prob = synth.make_problem(env="halfcheetah", E=E, m=m, H=H, seed=13, hidden_sizes=HID)
+    eng = make_engine(prob, p=p, lower_bound=lo, upper_bound=hi)
+    rng = np.random.default_rng(2)
+    acts = rng.uniform(-1.0, 2.5, (m, n, H, 6)).astype(np.float32)      # first actions on both sides of both bounds
+    eps = rng.standard_normal((H, m, n, p, 18)).astype(np.float32)
+    first, cand = hplanner.rs_plan(eng, prob["obs"], prob["cp_obs"], prob["cp_act"], n, actions=acts, eps=eng._t(eps))
+    o = oracle_problem(prob, np.float32)
+    rfirst, rcand = oplanner.rs_plan(o["env"], o["ff"], o["cp"], o["st"], o["obs"], o["cp_obs"], o["cp_act"], acts, eps, E, p)
+    assert_close(_np(cand)[0], rcand, 1e-4, "RS candidate returns")
+    want = oplanner.get_action_clip(rfirst, lower=lo, upper=hi)
+    np.testing.assert_array_equal(_np(first), want)
+    assert (rfirst < lo).any() or (rfirst > hi).any(), "the clip was not exercised: pick another seed"
+    # the library's own one-call form: U(-1, 1) draws, clipped by clip_kernel to the same bounds
+    a1 = _np(eng.rs_plan(prob["obs"], prob["cp_obs"], prob["cp_act"], n, seed=1, call=1))
+    unclipped = _np(make_engine(prob, p=p).rs_plan(prob["obs"], prob["cp_obs"], prob["cp_act"], n, seed=1, call=1))
+    np.testing.assert_array_equal(a1, np.clip(unclipped, np.float32(lo), np.float32(hi)))
+    assert (unclipped < lo).any()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the staged call on each input route
+# ------------------------------------------------------------------------------------------------------------------------------
+HEAD_MAX, INGEST_MAX, BATCHED_MIN_ROWS = 896, 960, 48      # csrc/common.h CADM_HEAD_INGEST_MAX, CADM_INGEST_MAX, CADM_CONTEXT_BATCHED_MIN_ROWS
+
+
+def _route(nfloats, m):
+    """capi.hip cadm_cem_plan_staged: how a block of `nfloats` floats for m envs reaches the device."""
+    if nfloats <= HEAD_MAX and m < BATCHED_MIN_ROWS:
+        return "head"
+    return "ingest" if nfloats <= INGEST_MAX else "copy"
+
+
+def _nfloats(prob):
+    m, D, A, H, C, Hh = prob["m"], prob["D"], prob["A"], prob["H"], prob["C"], prob["Hh"]
+    return m * (D + (Hh * (D + A) if C > 0 else 0) + 2 * H * A)
+
+
+def _staged_inputs(prob, seed):
+    """The five per-call arrays, none of them trivial (a warm-started mean, a non-constant variance)."""
+    rng = np.random.default_rng(seed)
+    m, H, A = prob["m"], prob["H"], prob["A"]
+    ctx = prob["C"] > 0
+    arrays = (rng.standard_normal((m, prob["D"])).astype(np.float32),
+              (0.1 * rng.standard_normal(prob["cp_obs"].shape)).astype(np.float32) if ctx else None,
+              rng.uniform(-1, 1, prob["cp_act"].shape).astype(np.float32) if ctx else None,
+              rng.uniform(-0.5, 0.5, (m, H, A)).astype(np.float32), rng.uniform(0.05, 0.3, (m, H, A)).astype(np.float32))
+    assert sum(a.size for a in arrays if a is not None) == _nfloats(prob)
+    return arrays
+
+
+STAGED = [      # env, context, m, H, Hh, nfloats, route
+    ("halfcheetah", True, 1, 53, 10, 894, "head"),
+    ("halfcheetah", True, 1, 54, 10, 906, "ingest"),
+    ("halfcheetah", True, 1, 58, 10, 954, "ingest"),
+    ("halfcheetah", True, 1, 59, 10, 966, "copy"),
+    ("halfcheetah", False, 2, 8, 10, 228, "head"),        # vanilla: the head runs no encoder blocks
+    ("halfcheetah", False, 2, 36, 10, 900, "ingest"),
+    ("ant", True, 1, 52, 1, 896, "head"),                 # exactly CADM_HEAD_INGEST_MAX: 28 + (28 + 8) + 2 * 52 * 8
+    ("ant", True, 1, 56, 1, 960, "ingest"),               # exactly CADM_INGEST_MAX
+    ("pendulum", True, 47, 5, 1, 799, "head"),            # the last m on the per-row encoder
+    ("pendulum", True, 48, 5, 1, 816, "ingest"),          # small enough for the head, but m = 48 takes the batched encoder: not fused
+]
+
+
+@pytest.mark.parametrize("env,context,m,H,Hh,nfloats,route", STAGED,
+                         ids=["%s-%s-m%d-H%d-nfloats%d-%s" % (r[0], "ctx" if r[1] else "vanilla", r[2], r[3], r[5], r[6]) for r in STAGED])
+def test_staged_call_routes(gpu, env, context, m, H, Hh, nfloats, route):
+    """`cem_plan_host` == `cem_plan` on the same inputs, bit for bit, with the block on each side of the two size thresholds and of the
+    m = 48 encoder switch.  The route is derived from (nfloats, m) by the library's rule restated in `_route`: the test cannot observe
+    which launch carried the block, only that the plan is the unfused call's whichever it was."""
+    prob = synth.make_problem(env=env, context=context, m=m, H=H, Hh=Hh, seed=40 + H, hidden_sizes=HID)
+    assert _nfloats(prob) == nfloats and _route(nfloats, m) == route
+    eng = make_engine(prob, p=5)
+    arrays = _staged_inputs(prob, seed=H)
+    a = eng.cem_plan_host(arrays, 64, seed=3, call=9)
+    b = _np(eng.cem_plan(*arrays, 64, seed=3, call=9))
+    assert a.shape == (m, H, prob["A"]) and np.isfinite(a).all() and np.abs(a).max() <= 1.0
+    np.testing.assert_array_equal(a, b)
+    # and against an engine that only ever made the unfused call (the staged call shares this engine's workspace)
+    np.testing.assert_array_equal(a, _np(make_engine(prob, p=5).cem_plan(*arrays, 64, seed=3, call=9)))
+
+
+def test_staged_call_changes_route_on_one_engine(gpu):
+    """head -> copy -> ingest -> head on ONE engine (halfcheetah, H = 4: 306 floats per env, m = 2 / 4 / 3 / 2): the workspace and the
+    pinned blocks are rebuilt per shape set, and every call equals a fresh engine's for that shape.  Then the same shape and the SAME
+    call id twice with other inputs: the completion flags the first call left behind carry the value the second waits for, and must
+    not satisfy it (the plan buffer would still hold the first call's plan)."""
+    H = 4
+    probs = {m: synth.make_problem(env="halfcheetah", m=m, H=H, seed=60, hidden_sizes=HID) for m in (2, 3, 4)}
+    assert [_route(_nfloats(probs[m]), m) for m in (2, 4, 3)] == ["head", "copy", "ingest"]
+    eng = make_engine(probs[2], p=5)
+
+    def fresh(m, arrays, call):
+        return make_engine(probs[m], p=5).cem_plan_host(arrays, 64, seed=7, call=call)
+    steps = [(2, 1, 100), (4, 2, 101), (3, 3, 102), (2, 3, 103), (2, 3, 104), (2, 3, 103)]      # m, call id, input seed
+    plans = []
+    for m, call, seed in steps:
+        arrays = _staged_inputs(probs[m], seed)
+        got = eng.cem_plan_host(arrays, 64, seed=7, call=call)
+        assert np.isfinite(got).all()
+        np.testing.assert_array_equal(got, fresh(m, arrays, call), err_msg="step m=%d call=%d inputs=%d" % (m, call, seed))
+        plans.append(got)
+    assert not np.array_equal(plans[3], plans[4])       # same shape, same call id, other inputs: another plan
+    np.testing.assert_array_equal(plans[3], plans[5])   # and the first inputs again: the first plan again
+    assert not np.array_equal(plans[0], plans[3])       # same shape, other call id: other draws

@@ -145,3 +145,86 @@ def test_fp32_oracle_tracks_fp64():
         res[dt] = op.rollout_indexed(o["env"], o["ff"], o["st"], o["obs"], T, acts.astype(dt), eps.astype(dt), E, p, False)
         assert res[dt].dtype == dt
     assert np.abs(res[np.float32] - res[np.float64]).max() / np.abs(res[np.float64]).max() < 1e-4
+
+
+def test_bound_keywords_default_to_the_reference_constants():
+    """The lower / upper / alpha keywords at their defaults: bit for bit what the functions computed with the literals -1.0 / 1.0 / 0.1
+    (utils.py:393-396, 425-429; dynamics.py:365-366), restated here."""
+    rng = np.random.default_rng(7)
+    for dt in (np.float32, np.float64):
+        mean = rng.uniform(-1.2, 1.2, (2, 5, 3)).astype(dt)
+        mean[0, 0, 0], mean[1, 4, 2] = -1.0, 1.0
+        var = rng.uniform(0.0, 0.5, (2, 5, 3)).astype(dt)
+        z = trunc_z(rng, (2, 9, 5, 3)).astype(dt)
+        cv_old = np.minimum(np.minimum(np.square((mean - dt(-1.0)) / dt(2)), np.square((dt(1.0) - mean) / dt(2))), var)
+        np.testing.assert_array_equal(op.constrained_var(mean, var), cv_old)
+        np.testing.assert_array_equal(op.constrained_var(mean, var, lower=-1.0, upper=1.0), cv_old)
+        acts_old = mean[:, None] + np.sqrt(cv_old)[:, None] * z
+        np.testing.assert_array_equal(op.sample_actions(mean, var, z), acts_old)
+        assert op.sample_actions(mean, var, z).dtype == dt
+        a = (3.0 * rng.standard_normal((4, 6))).astype(dt)
+        np.testing.assert_array_equal(op.get_action_clip(a), np.minimum(np.maximum(a, dt(-1.0)), dt(1.0)))
+        np.testing.assert_array_equal(op.get_action_clip(a, discrete=True), a)
+    E, p, m, n, H = 5, 5, 2, 60, 3
+    prob = synth.make_problem(env="halfcheetah", E=E, m=m, H=H, trained_like=True, seed=4)
+    o = oracle_problem(prob, np.float64)
+    z = trunc_z(rng, (5, m, n, H, 6))
+    eps = rng.standard_normal((5, H, m, n, p, 18))
+    args = (o["env"], o["ff"], o["cp"], o["st"], o["obs"], o["cp_obs"], o["cp_act"], o["init_mean"], o["init_var"], z, eps, E, p)
+    a = op.cem_plan(*args)
+    b = op.cem_plan(*args, n_iters=5, num_elites=50, alpha=0.1, lower=-1.0, upper=1.0)
+    np.testing.assert_array_equal(a, b)
+    # the loop restated from the pieces, with the constants as literals
+    mean, var = o["init_mean"], o["init_var"]
+    ctx = onets.context_forward(o["cp"], o["cp_obs"], o["cp_act"], o["st"])
+    for it in range(5):
+        acts = op.sample_actions(mean, var, z[it])
+        cand = op.particle_mean(op.rollout_indexed(o["env"], o["ff"], o["st"], o["obs"], op.context_table_indexed(ctx, it), acts,
+                                                   eps[it], E, p, False))
+        mean, var, _ = op.elite_refit(mean, var, acts, cand, 50, 0.1)
+    np.testing.assert_array_equal(a, mean)
+    # and the keywords reach the loop: other constants give another plan, inside the other bounds' reach
+    c = op.cem_plan(*args, n_iters=2, num_elites=7, alpha=0.5, lower=-0.5, upper=2.0)
+    assert not np.array_equal(a, c)
+
+
+def test_constrained_var_and_clip_with_other_bounds():
+    """Bounds (-0.5, 2.0) by hand: cv = min(((mean + 0.5) / 2)^2, ((2 - mean) / 2)^2, var) (utils.py:425-426 with lower_bound = -0.5,
+    upper_bound = 2.0) and the clip to the same bounds (dynamics.py:365-366)."""
+    mean = np.array([[-0.5, 0.0, 1.9], [2.0, 0.75, -0.3]])
+    var = np.array([[0.25, 0.25, 0.25], [0.1, 0.01, 1.0]])
+    want = np.array([[0.0,        # on the lower bound: (0 / 2)^2
+                      0.0625,     # (0.5 / 2)^2 = 0.0625 < (2 / 2)^2 = 1 and < 0.25
+                      0.0025],    # (0.1 / 2)^2 = 0.0025 < (2.4 / 2)^2 = 1.44 and < 0.25
+                     [0.0,        # on the upper bound
+                      0.01,       # var = 0.01 < (1.25 / 2)^2 = 0.390625 on both sides
+                      0.01]])     # (0.2 / 2)^2 = 0.01 < (2.3 / 2)^2 = 1.3225 and < 1.0
+    cv = op.constrained_var(mean, var, lower=-0.5, upper=2.0)
+    np.testing.assert_allclose(cv, want, rtol=1e-12, atol=1e-15)
+    assert cv[0, 0] == 0.0 and cv[1, 0] == 0.0 and cv[0, 1] == 0.0625 and cv[1, 1] == 0.01
+    z = np.full((2, 1, 3), 1.5)                                      # [m, n = 1, H * A]
+    acts = op.sample_actions(mean, var, z, lower=-0.5, upper=2.0)
+    np.testing.assert_allclose(acts[:, 0], mean + 1.5 * np.sqrt(want), rtol=1e-12)
+    assert acts[0, 0, 0] == -0.5 and acts[1, 0, 0] == 2.0           # constrained variance 0: the action is the mean
+    a = np.array([[-0.6, -0.5, 0.3], [1.99, 2.0, 2.5]])
+    np.testing.assert_array_equal(op.get_action_clip(a, lower=-0.5, upper=2.0), [[-0.5, -0.5, 0.3], [1.99, 2.0, 2.0]])
+    np.testing.assert_array_equal(op.get_action_clip(a, discrete=True, lower=-0.5, upper=2.0), a)
+    a32 = a.astype(np.float32)
+    assert op.get_action_clip(a32, lower=-0.5, upper=2.0).dtype == np.float32
+
+
+def test_top_k_signed_zeros_tie_lower_index_first():
+    """tf.nn.top_k compares values: -0.0 == +0.0 is a tie and the lower index comes first, whichever sign it carries."""
+    for dt in (np.float32, np.float64):
+        ret = np.full((2, 8), -1.0, dt)
+        ret[0, 2], ret[0, 5] = -0.0, 0.0          # -0.0 at the lower index
+        ret[1, 1], ret[1, 6] = 0.0, -0.0          # +0.0 at the lower index
+        ret[:, 7] = 3.0
+        np.testing.assert_array_equal(op.top_k_indices(ret, 2), [[7, 2], [7, 1]])
+        np.testing.assert_array_equal(op.top_k_indices(ret, 3), [[7, 2, 5], [7, 1, 6]])
+        np.testing.assert_array_equal(op.top_k_indices(ret, 4)[:, 3], [0, 0])
+    acts = np.arange(16, dtype=np.float64).reshape(1, 8, 2, 1)
+    ret = np.full((1, 8), -1.0); ret[0, 2], ret[0, 5] = -0.0, 0.0
+    nm, _, idx = op.elite_refit(np.zeros((1, 2, 1)), np.ones((1, 2, 1)), acts, ret, num_elites=1, alpha=0.0)
+    np.testing.assert_array_equal(idx, [[2]])
+    np.testing.assert_array_equal(nm[0], acts[0, 2])
