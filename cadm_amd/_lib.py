@@ -55,6 +55,11 @@ class EnvSpecC(C.Structure):          # include/cadm_hip.h cadm_env_spec
     ]
 
 
+class IcemParams(C.Structure):          # include/cadm_hip.h cadm_icem_params
+    _fields_ = [("noise_beta", C.c_float), ("keep_elites", C.c_int32), ("decay", C.c_float), ("return_best", C.c_int32),
+                ("add_mean_last", C.c_int32)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -94,6 +99,12 @@ SIGNATURES = {
     "cadm_plan_workspace_bytes": (C.c_size_t, [_P, _i, _i]),
     "cadm_cem_plan": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P]),
     "cadm_cem_plan_staged": (_i, [_P, _P, _P, C.POINTER(C.c_int32), _i, _i, _i, _u32, _u32, _P, _P, _i, _P]),
+    "cadm_sample_actions_colored": (_i, [_P, _P, _P, _P, C.c_float, _u32, _u32, _i, _i, _i, _P, _P]),
+    "cadm_icem_keep": (_i, [_P, _P, _P, _i, _i, _i, _P, _P]),
+    "cadm_icem_inject": (_i, [_P, _P, _P, _i, _i, _i, _i, _P, _P]),
+    "cadm_icem_track_best": (_i, [_P, _P, _P, _P, _i, _i, _P, _P, _P]),
+    "cadm_icem_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
+    "cadm_icem_plan": (_i, [_P, C.POINTER(IcemParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

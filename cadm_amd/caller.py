@@ -34,8 +34,16 @@ class DevicePlannerState:
         model, eng = self.model, self.eng
         model._push_stats()
         obs = eng._t(obs)
-        plan = eng.cem_plan(obs, self.hist_obs if self.context else None, self.hist_act if self.context else None,
-                            self.prev_sol, self.init_var, model.n_candidates, seed=model.seed, call=model._next_call())
+        hist = (self.hist_obs, self.hist_act) if self.context else (None, None)
+        if getattr(model, "_icem", None) is not None:      # the opt-in iCEM planner: its carried elites live on the model
+            K = model._icem["keep_elites"]
+            if K > 0 and (model._plan_carry is None or model._plan_carry.shape[0] != self.m):
+                model._plan_carry = torch.zeros((self.m, K, eng.H, eng.A), dtype=torch.float32, device=eng.device)
+                model._plan_carry_valid = torch.zeros((self.m,), dtype=torch.int32, device=eng.device)
+            plan = eng.icem_plan(model._icem_params, obs, hist[0], hist[1], self.prev_sol, self.init_var, model.n_candidates,
+                                 carry=model._plan_carry, carry_valid=model._plan_carry_valid, seed=model.seed, call=model._next_call())
+        else:
+            plan = eng.cem_plan(obs, hist[0], hist[1], self.prev_sol, self.init_var, model.n_candidates, seed=model.seed, call=model._next_call())
         eng._check(eng.lib.cadm_warm_start_shift(eng._ctx, ptr(plan), self.m, ptr(self.prev_sol), ptr(self.action), eng.stream),
               "cadm_warm_start_shift")
         return self.action
@@ -43,6 +51,8 @@ class DevicePlannerState:
     def observe(self, obs, action, next_obs, done=None):
         """History update after the env step (sampler.py:165-178) and per-env reset on done (:193-200)."""
         eng = self.eng
+        if done is not None and hasattr(self.model, "reset_plan_carry"):      # finished episodes: the iCEM planner forgets their elites
+            self.model.reset_plan_carry(done)
         if not self.context:
             return
         obs, action, next_obs = eng._t(obs), eng._t(action), eng._t(next_obs)
@@ -55,3 +65,5 @@ class DevicePlannerState:
     def reset(self):
         for t in (self.prev_sol, self.hist_obs, self.hist_act, self.counts):
             t.zero_()
+        if hasattr(self.model, "reset_plan_carry"):
+            self.model.reset_plan_carry()

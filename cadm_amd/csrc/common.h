@@ -58,6 +58,7 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_STREAM_EPS 1u
 #define CADM_STREAM_ACT 2u
 #define CADM_STREAM_UNI 3u
+#define CADM_STREAM_ICEM 4u   // spectral draws of the coloured-noise sampler (icem.hip)
 
 // ---------------------------------------------------------------------------------------------
 // planner weight-stream geometry (see DESIGN.md "weight streams")

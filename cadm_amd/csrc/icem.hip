@@ -1,0 +1,337 @@
+// iCEM planner (Pinneri et al. 2020, "Sample-efficient Cross-Entropy Method for Real-time Planning"): an OPT-IN second planner loop
+// beside cem_plan_impl (capi.hip).  No reference twin: the reference's CEM block (core/utils.py:398-488) draws white truncated-normal
+// noise and keeps nothing between iterations or calls.  New here:
+//   * temporally correlated ("coloured") candidate noise, synthesised per sequence from H spectral draws (icem_colored_kernel);
+//   * elite carry-over inside a call and, shifted by one step, between calls (icem_keep_kernel / icem_inject_kernel);
+//   * the best sequence seen in a call as the plan (icem_track_best_kernel);
+//   * a decaying candidate count.
+// The rollout, the context encoder, the truncated-normal sampler and the elite refit are the reference path's, called unchanged.
+#include <math.h>
+
+#include "common.h"
+
+int cadm_launch_clip(const float* in, float* out, int total, float lo, float hi, int do_clip, hipStream_t s);
+int cadm_launch_refit(cadm_ctx* ctx, const float* cand_returns, const float* rows, int G, int n_local, const float* actions,
+                      int m, const float* mean_in, const float* var_in, float* mean_out, float* var_out, int32_t* elites_out,
+                      float* plan_out, hipStream_t stream, const RefitRegen* regen);
+
+// ---------------------------------------------------------------------------------------------
+// coloured-noise candidates
+// ---------------------------------------------------------------------------------------------
+// One noise sequence z_0 .. z_{H-1} per (env mi, candidate c, action dim a), from spectral draws x_k, y_k ~ N(0,1):
+//   z_t = c_b [ x_0 / sqrt2 + sum_{1 <= k < H/2} k^(-b/2) (x_k cos th_kt - y_k sin th_kt) + [H even] (H/2)^(-b/2) x_{H/2} (-1)^t / sqrt2 ]
+//   th_kt = 2 pi ((k t) mod H) / H,    c_b = (1/2 + sum_{1 <= k < H/2} k^(-b) + [H even] (H/2)^(-b) / 2)^(-1/2)
+// Var z_t = 1 for every t and b; b = 0 is an orthonormal transform of H iid normals (white); b > 0 weights the low frequencies.
+// action = clip(mean + sd z_t, lb, ub), sd as in sample_action (common.h); no rejection (it would break the correlation).
+//
+// One thread owns one sequence: its H spectral numbers sit in LDS (slot-major: lanes read consecutive words), the H outputs are
+// formed by direct synthesis (~H^2 / 2 multiply-adds).  The angle is reduced in integers, (k t) mod H, and looked up in a table of
+// the H-th roots of unity built once per workgroup in double precision: accuracy does not depend on H.
+// Spectral slots: 0 = x_0, then (x_k, y_k) at (2k - 1, 2k) for 1 <= k < H/2, and x_{H/2} at H - 1 when H is even: H numbers.
+constexpr int ICEM_BLOCK = 64;
+
+static size_t icem_colored_lds(int H) { return ((size_t)2 * H + (size_t)(H / 2 + 1) + (size_t)H * ICEM_BLOCK) * sizeof(float); }
+
+__global__ __launch_bounds__(ICEM_BLOCK) void icem_colored_kernel(const float* __restrict__ mean, const float* __restrict__ var,
+                                                                  const float* __restrict__ xi, float beta, double cbeta, uint32_t seed,
+                                                                  uint32_t call, int it, int m, int n, int H, int A, float lb, float ub,
+                                                                  float* __restrict__ out) {
+    extern __shared__ float icem_sm[];
+    float* ct = icem_sm;                    // [H] cos(2 pi j / H)
+    float* st = ct + H;                     // [H] sin(2 pi j / H)
+    float* wt = st + H;                     // [H/2 + 1] c_b k^(-b/2); [0] = c_b / sqrt2; [H/2] (H even) = c_b (H/2)^(-b/2) / sqrt2
+    float* sp = wt + (H / 2 + 1);           // [H][ICEM_BLOCK] spectral numbers of this workgroup's sequences
+    const int tid = threadIdx.x;
+    const int nyq = (H & 1) ? -1 : H / 2;   // the Nyquist term exists for even H only
+    for (int j = tid; j < H; j += ICEM_BLOCK) {
+        double s, c;
+        sincospi(2.0 * (double)j / (double)H, &s, &c);
+        ct[j] = (float)c;
+        st[j] = (float)s;
+    }
+    for (int k = tid; k <= H / 2; k += ICEM_BLOCK) {
+        double w = k == 0 ? 0.70710678118654752440 : pow((double)k, -0.5 * (double)beta);
+        if (k > 0 && k == nyq) w *= 0.70710678118654752440;
+        wt[k] = (float)(cbeta * w);
+    }
+    const size_t total = (size_t)m * n * A;
+    const size_t q = (size_t)blockIdx.x * ICEM_BLOCK + tid;      // global sequence index (mi * n + c) * A + a
+    const bool live = q < total;
+    if (live) {
+        if (xi) {
+            for (int s = 0; s < H; ++s) sp[s * ICEM_BLOCK + tid] = xi[q * H + s];
+        } else {
+            for (int k = 0; 2 * k <= H; ++k) {
+                uint32_t r[4];
+                philox4x32_10((uint32_t)(q & 0xFFFFFFFFull), (uint32_t)k, (uint32_t)(q >> 32), CADM_STREAM_ICEM | ((uint32_t)it << 8), seed, call, r);
+                // Box-Muller with the library's accurate logf / sincosf: the spectral draws are summed, so their errors add up
+                const float rad = sqrtf(-2.0f * logf(u01(r[0])));
+                float sn, cs;
+                sincosf(6.28318530717958647692f * u01(r[1]), &sn, &cs);
+                if (k == 0) sp[tid] = rad * cs;
+                else if (2 * k < H) { sp[(2 * k - 1) * ICEM_BLOCK + tid] = rad * cs; sp[(2 * k) * ICEM_BLOCK + tid] = rad * sn; }
+                else sp[(H - 1) * ICEM_BLOCK + tid] = rad * cs;
+            }
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const int a = (int)(q % A);
+    const size_t mc = q / A;                                     // mi * n + c
+    const int mi = (int)(mc / n);
+    const float* mu_m = mean + (size_t)mi * H * A + a;
+    const float* var_m = var + (size_t)mi * H * A + a;
+    float* o = out + mc * H * A + a;
+    const float x0 = sp[tid];
+    const float xn = nyq > 0 ? sp[(H - 1) * ICEM_BLOCK + tid] : 0.0f;
+    for (int t = 0; t < H; ++t) {
+        float z = wt[0] * x0;
+        for (int k = 1; 2 * k < H; ++k) {
+            const int j = (k * t) % H;
+            const float xk = sp[(2 * k - 1) * ICEM_BLOCK + tid], yk = sp[(2 * k) * ICEM_BLOCK + tid];
+            z += wt[k] * (xk * ct[j] - yk * st[j]);
+        }
+        if (nyq > 0) z += (t & 1) ? -(wt[nyq] * xn) : wt[nyq] * xn;
+        const float mu = mu_m[(size_t)t * A];
+        const float a1 = (mu - lb) / 2.0f, a2 = (ub - mu) / 2.0f;
+        const float cv = fminf(fminf(a1 * a1, a2 * a2), var_m[(size_t)t * A]);
+        o[(size_t)t * A] = fminf(fmaxf(mu + sqrtf(cv) * z, lb), ub);
+    }
+}
+
+static double icem_cbeta(int H, double beta) {
+    double s = 0.5;
+    for (int k = 1; 2 * k < H; ++k) s += pow((double)k, -beta);
+    if (H % 2 == 0) s += 0.5 * pow((double)(H / 2), -beta);
+    return 1.0 / sqrt(s);
+}
+
+extern "C" int cadm_sample_actions_colored(cadm_ctx* ctx, const float* mean, const float* var, const float* xi, float beta,
+                                           uint32_t seed, uint32_t call, int it, int m, int n, float* actions_out, void* stream) {
+    CADM_REQUIRE(ctx && mean && var && actions_out && m > 0 && n > 0, "cadm_sample_actions_colored: bad arguments");
+    CADM_REQUIRE(beta >= 0.0f && beta <= 16.0f, "cadm_sample_actions_colored: noise_beta %g outside [0, 16]", (double)beta);
+    CADM_REQUIRE(it >= 0 && it < (1 << 24), "cadm_sample_actions_colored: iteration %d outside [0, 2^24)", it);
+    CADM_REQUIRE(!ctx->cfg.discrete, "cadm_sample_actions_colored: continuous actions only");
+    const size_t lds = icem_colored_lds(ctx->H);
+    CADM_REQUIRE(lds <= 64 * 1024, "cadm_sample_actions_colored: horizon %d needs %zu bytes of LDS (limit 65536)", ctx->H, lds);
+    const size_t total = (size_t)m * n * ctx->A, blocks = (total + ICEM_BLOCK - 1) / ICEM_BLOCK;
+    CADM_REQUIRE(blocks <= 0x7FFFFFFFull, "cadm_sample_actions_colored: %zu sequences are too many for one launch", total);
+    CADM_ON_DEVICE(ctx);
+    hipLaunchKernelGGL(icem_colored_kernel, dim3((unsigned)blocks), dim3(ICEM_BLOCK), lds, (hipStream_t)stream, mean, var, xi, beta,
+                       icem_cbeta(ctx->H, (double)beta), seed, call, it, m, n, ctx->H, ctx->A, ctx->cfg.lower_bound, ctx->cfg.upper_bound,
+                       actions_out);
+    CADM_CHECK_HIP(hipGetLastError());
+    return CADM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// elite carry-over and the best plan of a call
+// ---------------------------------------------------------------------------------------------
+// kept[mi, j] = actions[mi, elites[mi, j]] for j < K (elites [m, KE]: the refit's order, return descending, ties to the lower index);
+// valid_out (optional): valid_out[mi] = 1
+__global__ void icem_keep_kernel(const float* __restrict__ actions, const int32_t* __restrict__ elites, int m, int n, int K, int KE, int HA,
+                                 float* __restrict__ kept, int32_t* __restrict__ valid_out) {
+    const size_t total = (size_t)m * K * HA;
+    for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
+        const int e = (int)(q % HA);
+        const size_t mj = q / HA;
+        const int j = (int)(mj % K), mi = (int)(mj / K);
+        const int32_t c = elites[(size_t)mi * KE + j];
+        if ((uint32_t)c < (uint32_t)n) kept[q] = actions[((size_t)mi * n + c) * HA + e];
+        if (valid_out && j == 0 && e == 0) valid_out[mi] = 1;
+    }
+}
+
+// candidate slots [0, K) of every env (with valid[mi] != 0, when valid is given) take the kept sequences: whole (shift = 0), or moved one
+// step towards the present (shift = 1: steps [0, H - 1) take kept steps [1, H); step H - 1 keeps what the sampler drew)
+__global__ void icem_inject_kernel(const float* __restrict__ kept, const int32_t* __restrict__ valid, int m, int n, int K, int H, int A,
+                                   int shift, float* __restrict__ actions) {
+    const int HA = H * A;
+    const size_t total = (size_t)m * K * HA;
+    for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
+        const int e = (int)(q % HA);
+        const size_t mj = q / HA;
+        const int j = (int)(mj % K), mi = (int)(mj / K);
+        if (valid && valid[mi] == 0) continue;
+        if (shift && e >= HA - A) continue;
+        actions[((size_t)mi * n + j) * HA + e] = kept[q + (shift ? A : 0)];
+    }
+}
+
+// the iteration's top candidate (elites[mi, 0]) against the best of this call so far: replaced where its return is STRICTLY greater
+// (a tie, -0.0 against +0.0 included, keeps the earlier sequence; a NaN return never replaces).  One workgroup per env; every thread
+// reads the stored return before any thread writes it.
+__global__ void icem_track_best_kernel(const float* __restrict__ cand, const int32_t* __restrict__ elites, const float* __restrict__ actions,
+                                       int n, int KE, int HA, float* __restrict__ best_ret, float* __restrict__ best_seq) {
+    const int mi = blockIdx.x;
+    const int32_t c = elites[(size_t)mi * KE];
+    const float old = best_ret[mi];
+    const float r = (uint32_t)c < (uint32_t)n ? cand[(size_t)mi * n + c] : old;
+    __syncthreads();
+    if (!(r > old)) return;
+    for (int e = threadIdx.x; e < HA; e += blockDim.x) best_seq[(size_t)mi * HA + e] = actions[((size_t)mi * n + c) * HA + e];
+    if (threadIdx.x == 0) best_ret[mi] = r;
+}
+
+__global__ void icem_best_init_kernel(int m, int HA, float* __restrict__ best_ret, float* __restrict__ best_seq) {
+    const size_t total = (size_t)m * HA;
+    for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
+        best_seq[q] = __uint_as_float(0x7fc00000u);      // (a call whose returns are all NaN plans NaN, as the mean would)
+        if (q < (size_t)m) best_ret[q] = -INFINITY;
+    }
+}
+
+static int icem_grid(size_t total) {
+    const size_t g = (total + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+static int launch_keep(cadm_ctx* ctx, const float* actions, const int32_t* elites, int m, int n, int K, float* kept, int32_t* valid_out,
+                       hipStream_t s) {
+    const int HA = ctx->H * ctx->A;
+    hipLaunchKernelGGL(icem_keep_kernel, dim3(icem_grid((size_t)m * K * HA)), dim3(256), 0, s, actions, elites, m, n, K, ctx->cfg.num_elites,
+                       HA, kept, valid_out);
+    CADM_CHECK_HIP(hipGetLastError());
+    return CADM_OK;
+}
+
+static int launch_inject(cadm_ctx* ctx, const float* kept, const int32_t* valid, int m, int n, int K, int shift, float* actions, hipStream_t s) {
+    hipLaunchKernelGGL(icem_inject_kernel, dim3(icem_grid((size_t)m * K * ctx->H * ctx->A)), dim3(256), 0, s, kept, valid, m, n, K, ctx->H,
+                       ctx->A, shift, actions);
+    CADM_CHECK_HIP(hipGetLastError());
+    return CADM_OK;
+}
+
+static int launch_track_best(cadm_ctx* ctx, const float* cand, const int32_t* elites, const float* actions, int m, int n, float* best_ret,
+                             float* best_seq, hipStream_t s) {
+    hipLaunchKernelGGL(icem_track_best_kernel, dim3(m), dim3(256), 0, s, cand, elites, actions, n, ctx->cfg.num_elites, ctx->H * ctx->A,
+                       best_ret, best_seq);
+    CADM_CHECK_HIP(hipGetLastError());
+    return CADM_OK;
+}
+
+extern "C" int cadm_icem_keep(cadm_ctx* ctx, const float* actions, const int32_t* elites, int m, int n, int K, float* kept_out, void* stream) {
+    CADM_REQUIRE(ctx && actions && elites && kept_out && m > 0 && n > 0, "cadm_icem_keep: bad arguments");
+    CADM_REQUIRE(K >= 0 && K <= ctx->cfg.num_elites && K <= n, "cadm_icem_keep: keep_elites %d outside [0, min(num_elites %d, n %d)]", K,
+                 ctx->cfg.num_elites, n);
+    if (K == 0) return CADM_OK;
+    CADM_ON_DEVICE(ctx);
+    return launch_keep(ctx, actions, elites, m, n, K, kept_out, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int cadm_icem_inject(cadm_ctx* ctx, const float* kept, const int32_t* valid, int m, int n, int K, int shift, float* actions_io,
+                                void* stream) {
+    CADM_REQUIRE(ctx && kept && actions_io && m > 0 && n > 0, "cadm_icem_inject: bad arguments");
+    CADM_REQUIRE(K >= 0 && K <= n, "cadm_icem_inject: keep_elites %d outside [0, n %d]", K, n);
+    CADM_REQUIRE(shift == 0 || shift == 1, "cadm_icem_inject: shift %d is not 0 or 1", shift);
+    if (K == 0) return CADM_OK;
+    CADM_ON_DEVICE(ctx);
+    return launch_inject(ctx, kept, valid, m, n, K, shift, actions_io, (hipStream_t)stream);
+}
+
+extern "C" int cadm_icem_track_best(cadm_ctx* ctx, const float* cand_returns, const int32_t* elites, const float* actions, int m, int n,
+                                    float* best_ret_io, float* best_seq_io, void* stream) {
+    CADM_REQUIRE(ctx && cand_returns && elites && actions && best_ret_io && best_seq_io && m > 0 && n > 0, "cadm_icem_track_best: bad arguments");
+    CADM_ON_DEVICE(ctx);
+    return launch_track_best(ctx, cand_returns, elites, actions, m, n, best_ret_io, best_seq_io, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the planner loop
+// ---------------------------------------------------------------------------------------------
+struct IcemWs {
+    float *ctxv, *actions, *rows, *cand, *mean, *var, *meanclip, *kept, *best_ret, *best_seq;
+    int32_t* elites;
+};
+
+static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, char* base, IcemWs* w) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    const size_t HA = (size_t)ctx->H * ctx->A;
+    IcemWs t;
+    t.ctxv = (float*)take((size_t)ctx->E * m * (ctx->C > 0 ? ctx->C : 1) * 4);
+    t.actions = (float*)take((size_t)m * n * HA * 4);
+    t.rows = (float*)take((size_t)m * n * ctx->p * 4);
+    t.cand = (float*)take((size_t)m * n * 4);
+    t.mean = (float*)take((size_t)m * HA * 4);
+    t.var = (float*)take((size_t)m * HA * 4);
+    t.meanclip = (float*)take((size_t)m * HA * 4);
+    t.kept = (float*)take((size_t)m * (K > 0 ? K : 1) * HA * 4);
+    t.best_ret = (float*)take((size_t)m * 4);
+    t.best_seq = (float*)take((size_t)m * HA * 4);
+    t.elites = (int32_t*)take((size_t)m * ctx->cfg.num_elites * 4);
+    if (w) *w = t;
+    return off;
+}
+
+extern "C" size_t cadm_icem_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
+    return icem_carve(ctx, m, n, K, nullptr, nullptr);
+}
+
+// candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
+static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
+    double v = floor((double)n / pow(decay, (double)it));
+    int ni = v >= (double)n ? n : (int)v;
+    if (ni < 2 * num_elites) ni = 2 * num_elites;
+    if (ni < K + 1) ni = K + 1;
+    return ni < n ? ni : n;
+}
+
+extern "C" int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
+                              const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                              uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+    CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "cadm_icem_plan: bad arguments");
+    CADM_REQUIRE(!cadm_sharded(ctx), "cadm_icem_plan: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)");
+    CADM_REQUIRE(!ctx->cfg.discrete, "cadm_icem_plan: continuous actions only");
+    const int K = prm->keep_elites, KE = ctx->cfg.num_elites, iters = ctx->cfg.num_cem_iters;
+    CADM_REQUIRE(K >= 0 && K <= KE, "cadm_icem_plan: keep_elites %d outside [0, num_elites %d]", K, KE);
+    CADM_REQUIRE(prm->decay >= 1.0f && prm->decay <= 1e6f, "cadm_icem_plan: decay %g must be >= 1", (double)prm->decay);
+    CADM_REQUIRE(prm->noise_beta >= 0.0f && prm->noise_beta <= 16.0f, "cadm_icem_plan: noise_beta %g outside [0, 16]", (double)prm->noise_beta);
+    CADM_REQUIRE(n >= KE, "cadm_icem_plan: n_candidates %d < num_elites %d", n, KE);
+    CADM_REQUIRE(!prm->add_mean_last || n >= K + 1, "cadm_icem_plan: n_candidates %d leaves no slot for the mean candidate behind %d kept elites", n, K);
+    CADM_REQUIRE(K == 0 || (carry_io && carry_valid_io), "cadm_icem_plan: carry / carry_valid required with keep_elites > 0");
+    CADM_REQUIRE(ctx->C == 0 || (cp_obs && cp_act), "cadm_icem_plan: cp_obs/cp_act required for a context model");
+    CADM_REQUIRE(prm->noise_beta == 0.0f || icem_colored_lds(ctx->H) <= 64 * 1024, "cadm_icem_plan: horizon %d is too long for the coloured sampler", ctx->H);
+    CADM_ON_DEVICE(ctx);
+    hipStream_t s = (hipStream_t)stream;
+    IcemWs w;
+    icem_carve(ctx, m, n, K, (char*)workspace, &w);
+    const int HA = ctx->H * ctx->A;
+    const bool track = prm->return_best != 0 || best_return_out != nullptr;
+    int rc;
+    if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
+    if (track) {
+        hipLaunchKernelGGL(icem_best_init_kernel, dim3(icem_grid((size_t)m * HA)), dim3(256), 0, s, m, HA, w.best_ret, w.best_seq);
+        CADM_CHECK_HIP(hipGetLastError());
+    }
+    for (int it = 0; it < iters; ++it) {
+        const bool first = it == 0, last = it + 1 == iters;
+        const int ni = icem_n_it(n, (double)prm->decay, it, KE, K);
+        const float* mean_in = first ? init_mean : w.mean;
+        const float* var_in = first ? init_var : w.var;
+        // candidates [m, ni, H, A]: white truncated-normal noise (the reference path's sampler) or coloured noise
+        if (prm->noise_beta > 0.0f) rc = cadm_sample_actions_colored(ctx, mean_in, var_in, nullptr, prm->noise_beta, seed, call, it, m, ni, w.actions, stream);
+        else rc = cadm_sample_actions(ctx, mean_in, var_in, nullptr, seed, call, it, m, ni, w.actions, stream);
+        if (rc) return rc;
+        // slots [0, K): the previous call's elites moved one step on (iteration 0, envs that have some), or the previous iteration's
+        if (K > 0 && (rc = first ? launch_inject(ctx, carry_io, carry_valid_io, m, ni, K, 1, w.actions, s)
+                                 : launch_inject(ctx, w.kept, nullptr, m, ni, K, 0, w.actions, s))) return rc;
+        // slot K of the last iteration: the current mean itself
+        if (last && prm->add_mean_last) {
+            if ((rc = cadm_launch_clip(mean_in, w.meanclip, m * HA, ctx->cfg.lower_bound, ctx->cfg.upper_bound, 1, s))) return rc;
+            if ((rc = launch_inject(ctx, w.meanclip, nullptr, m, ni, 1, 0, w.actions + (size_t)K * HA, s))) return rc;
+        }
+        if ((rc = cadm_rollout_returns(ctx, obs, nullptr, ctx->C > 0 ? w.ctxv : nullptr, w.actions, nullptr, 1, seed, call, it, 0, ni, m, ni,
+                                       w.rows, nullptr, stream))) return rc;
+        if ((rc = cadm_particle_mean(ctx, w.rows, m, ni, w.cand, stream))) return rc;
+        float* plan = (last && !prm->return_best) ? plan_out : nullptr;      // the refitted mean, clipped (dynamics.py:365-366)
+        if ((rc = cadm_launch_refit(ctx, w.cand, nullptr, 1, ni, w.actions, m, mean_in, var_in, w.mean, w.var, w.elites, plan, s, nullptr))) return rc;
+        if (track && (rc = launch_track_best(ctx, w.cand, w.elites, w.actions, m, ni, w.best_ret, w.best_seq, s))) return rc;
+        if (K > 0 && (rc = last ? launch_keep(ctx, w.actions, w.elites, m, ni, K, carry_io, carry_valid_io, s)
+                                : launch_keep(ctx, w.actions, w.elites, m, ni, K, w.kept, nullptr, s))) return rc;
+    }
+    if (prm->return_best && (rc = cadm_launch_clip(w.best_seq, plan_out, m * HA, 0.0f, 0.0f, 0, s))) return rc;
+    if (best_return_out && (rc = cadm_launch_clip(w.best_ret, best_return_out, m, 0.0f, 0.0f, 0, s))) return rc;
+    return CADM_OK;
+}

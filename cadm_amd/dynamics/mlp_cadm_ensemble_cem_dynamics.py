@@ -20,6 +20,10 @@ Differences a caller can see (all opt-in except the first):
     `check_replicated_calls` (2) sharded calls AND every `check_replicated_every`-th (256th) one after them compare a checksum
     of the inputs with one extra all-reduce and raise on a mismatch; all other calls run only the path's own collectives.
     `check_replicated_every=0` switches the periodic check OFF -- then nothing detects divergence after the first calls);
+  * `cem_noise_beta`, `cem_keep_elites`, `cem_decay`, `cem_return`, `cem_add_mean`: the iCEM planner (Pinneri et al. 2020; INTEGRATION.md
+    "iCEM planner").  At their defaults (0.0, 0, 1.0, "mean", False) `get_action` is the reference's CEM, unchanged; any other value
+    plans with `cadm_icem_plan` -- coloured action noise, elites kept between CEM iterations and (moved one step on) between
+    consecutive calls, `reset_plan_carry` to forget them at an episode boundary;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
     prediction of every ensemble member (the reference has no public predict).
 """
@@ -143,6 +147,11 @@ class MLPEnsembleCEMDynamicsModel(object):
                  process_group=None,
                  check_replicated_calls=2,
                  check_replicated_every=256,
+                 cem_noise_beta=0.0,
+                 cem_keep_elites=0,
+                 cem_decay=1.0,
+                 cem_return="mean",
+                 cem_add_mean=False,
                  engine_lib=None,
                  ):
         self.env = env
@@ -198,6 +207,31 @@ class MLPEnsembleCEMDynamicsModel(object):
         if n_particles % ensemble_size != 0:
             raise ValueError("n_particles must be a multiple of ensemble_size (core/utils.py:447 int(p/E))")
 
+        # the iCEM planner's switches: all at their defaults = the reference's CEM (`_icem` stays None and get_action never looks further)
+        self._icem = None
+        if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean)) != (0.0, 0, 1.0, "mean", False):
+            if not use_cem:
+                raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean configure the CEM planner: "
+                                 "they need use_cem=True")
+            if cem_return not in ("mean", "best"):
+                raise ValueError("cem_return must be 'mean' or 'best', got %r" % (cem_return,))
+            if not 0.0 <= float(cem_noise_beta) <= 16.0:
+                raise ValueError("cem_noise_beta must lie in [0, 16], got %r" % (cem_noise_beta,))
+            if not float(cem_decay) >= 1.0:
+                raise ValueError("cem_decay must be >= 1, got %r" % (cem_decay,))
+            if int(cem_keep_elites) < 0:
+                raise ValueError("cem_keep_elites must be >= 0, got %r" % (cem_keep_elites,))
+            if self.discrete:
+                raise NotImplementedError("the iCEM planner (cem_* kwargs) plans continuous actions only; this env's action space is discrete")
+            if process_group is not None:
+                import torch.distributed as dist
+                if dist.get_world_size(process_group) > 1:
+                    raise NotImplementedError("the iCEM planner (cem_* kwargs) does not shard candidates over a process group of more than "
+                                              "one rank: carried elites cannot be regenerated by id")
+            self._icem = dict(noise_beta=float(cem_noise_beta), keep_elites=int(cem_keep_elites), decay=float(cem_decay),
+                              return_best=cem_return == "best", add_mean_last=bool(cem_add_mean))
+        self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (iCEM, keep_elites > 0)
+
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
         self._call = 0
@@ -224,6 +258,10 @@ class MLPEnsembleCEMDynamicsModel(object):
         # (`--hidden_size`, `--context_out_dim`, depth, nonlinearity) is built now (cadm_amd.jit, ~30 s once, then cached),
         # and a launch that cannot fit the hardware (LDS for this horizon) raises here -- not at the first get_action.
         self.engine.ensure_rollout(None, 1, max(1, n_candidates))
+        if self._icem is not None:
+            if self._icem["keep_elites"] > self.engine.num_elites:
+                raise ValueError("cem_keep_elites=%d exceeds the planner's %d elites" % (self._icem["keep_elites"], self.engine.num_elites))
+            self._icem_params = HipEngine.icem_params(**self._icem)
 
     # ------------------------------------------------------------------ planning
     def _push_stats(self):
@@ -302,6 +340,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         (ints [m] for discrete envs).  Continuous outputs are clipped to [-1,1]."""
         if self._stats_dirty:
             self._push_stats()
+        if getattr(self, "_icem", None) is not None and cem_init_mean is not None:      # the opt-in iCEM planner; None: today's route
+            return self._get_action_icem(obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
         nd = np.ndarray
         counted = False
         if (type(obs) is nd and type(cem_init_mean) is nd and type(cem_init_var) is nd and (cp_obs is None or type(cp_obs) is nd)
@@ -359,6 +399,44 @@ class MLPEnsembleCEMDynamicsModel(object):
             action = np.minimum(np.maximum(action, -1.0), 1.0)
         return action
 
+    def _get_action_icem(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
+        """The opt-in iCEM route of get_action: one `cadm_icem_plan` call; the elites it keeps for the next call stay on the device."""
+        m = int(np.shape(obs)[0])
+        if m == 0:
+            return np.zeros((0, self.n_forwards, self.action_space_dims), np.float32)
+        sig = tuple(None if x is None else tuple(np.shape(x)) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
+        if sig != self._checked_sig:
+            self._check_planner_inputs(obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
+            self._checked_sig = sig
+        eng, K = self.engine, self._icem["keep_elites"]
+        if K > 0 and (self._plan_carry is None or self._plan_carry.shape[0] != m):      # first call, or another number of envs: nothing carried
+            self._plan_carry = torch.zeros((m, K, self.n_forwards, self.action_space_dims), dtype=torch.float32, device=eng.device)
+            self._plan_carry_valid = torch.zeros((m,), dtype=torch.int32, device=eng.device)
+        call = self._next_call()
+        if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
+            obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
+        if self.context_out_dim == 0:
+            cp_obs = cp_act = None
+        host = eng.host_out((m, self.n_forwards, self.action_space_dims))
+        eng.icem_plan(self._icem_params, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
+                      carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=host)
+        torch.cuda.current_stream(eng.device).synchronize()
+        return host.numpy().copy()
+
+    def reset_plan_carry(self, mask=None):
+        """Forget the elites the iCEM planner carries from one get_action to the next (`cem_keep_elites` > 0): for every env, or for
+        those where `mask` [m] is set -- at an episode boundary, so that a new episode never starts from the previous one's plans.
+        A no-op for a model that carries nothing."""
+        if getattr(self, "_plan_carry_valid", None) is None:
+            return
+        if mask is None:
+            self._plan_carry_valid.zero_()
+            return
+        mk = self.engine._t(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.bool).reshape(-1)
+        if mk.shape[0] != self._plan_carry_valid.shape[0]:
+            raise ValueError("reset_plan_carry: mask has %d entries, the planner carries elites for %d envs" % (mk.shape[0], self._plan_carry_valid.shape[0]))
+        self._plan_carry_valid.masked_fill_(mk, 0)
+
     def get_context_pred(self, cp_obs, cp_act):
         """reference :369-380 -> [E,m,C]."""
         self._push_stats()
@@ -409,6 +487,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         if rolling_average_persitency is None:
             rolling_average_persitency = self.rolling_average_persitency
         assert 1 > valid_split_ratio >= 0
+        if getattr(self, "_plan_carry_valid", None) is not None:      # elites planned under the old weights
+            self._plan_carry_valid.zero_()
         injected = index_stream is not None
         if index_stream is None:
             index_stream = FitIndexStream(rng if rng is not None else np.random.default_rng(self.seed + 7919 * (self._call + 1)))
@@ -609,6 +689,7 @@ class MLPEnsembleCEMDynamicsModel(object):
     def load(self, load_path):
         """reference :579-588 (positional assignment)."""
         self.engine.load_params_list(joblib.load(load_path))
+        self.reset_plan_carry()
         if self.normalize_input:
             self.normalization = joblib.load(load_path + "_norm_stats")
             self._stats_dirty = True

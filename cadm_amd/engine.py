@@ -499,6 +499,81 @@ class HipEngine:
                                     ptr(raw), self.stream), "cadm_rs_plan")
         return raw if self.discrete else out
 
+    # ------------------------------------------------------------------ iCEM planner (opt-in; csrc/icem.hip)
+    def sample_actions_colored(self, mean, var, n, beta, xi=None, seed=0, call=0, it=0):
+        """Candidates [m,n,H,A] with temporally correlated noise (`cadm_sample_actions_colored`).  xi [m,n,A,H]: injected spectral
+        draws (slot 0 = x_0, then (x_k, y_k) in k order), or None to draw them on the device."""
+        mean, var = self._t(mean), self._t(var)
+        m = mean.shape[0]
+        xi = None if xi is None else self._t(xi)
+        if xi is not None and tuple(xi.shape) != (m, n, self.A, self.H):
+            raise ValueError("sample_actions_colored: xi has shape %r, expected %r" % (tuple(xi.shape), (m, n, self.A, self.H)))
+        out = torch.empty((m, n, self.H, self.A), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_sample_actions_colored(self._ctx, ptr(mean), ptr(var), ptr(xi), float(beta), seed, call, it, m, n,
+                                                         ptr(out), self.stream), "cadm_sample_actions_colored")
+        return out
+
+    def icem_keep(self, actions, elites, K):
+        """actions [m,n,H,A], elites [m,num_elites] int32 (the refit's) -> the first K elites' sequences [m,K,H,A]."""
+        m, n = actions.shape[0], actions.shape[1]
+        out = torch.empty((m, K, self.H, self.A), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_icem_keep(self._ctx, ptr(actions), ptr(elites), m, n, int(K), ptr(out), self.stream), "cadm_icem_keep")
+        return out
+
+    def icem_inject(self, actions, kept, valid=None, shift=0, slot0=0):
+        """Write kept [m,K,H,A] into candidate slots [slot0, slot0 + K) of actions [m,n,H,A] IN PLACE (shift = 1: one step on,
+        step H - 1 untouched; valid [m] int32: only envs with a non-zero flag)."""
+        m, n, K = actions.shape[0], actions.shape[1], kept.shape[1]
+        if not actions.is_contiguous() or not kept.is_contiguous() or slot0 < 0 or slot0 + K > n or kept.shape[0] != m:
+            raise ValueError("icem_inject: slots [%d, %d) of %d candidates, kept %r" % (slot0, slot0 + K, n, tuple(kept.shape)))
+        dst = ct.c_void_p(actions.data_ptr() + 4 * slot0 * self.H * self.A)
+        self._check(self.lib.cadm_icem_inject(self._ctx, ptr(kept), ptr(valid), m, n, K, int(shift), dst, self.stream), "cadm_icem_inject")
+        return actions
+
+    def icem_track_best(self, cand, elites, actions, best_ret, best_seq):
+        """best_ret [m] / best_seq [m,H,A] updated IN PLACE where this iteration's top candidate is strictly better."""
+        m, n = actions.shape[0], actions.shape[1]
+        self._check(self.lib.cadm_icem_track_best(self._ctx, ptr(cand), ptr(elites), ptr(actions), m, n, ptr(best_ret), ptr(best_seq),
+                                                  self.stream), "cadm_icem_track_best")
+
+    @staticmethod
+    def icem_params(noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False, add_mean_last=False):
+        prm = _lib.IcemParams()
+        prm.noise_beta, prm.keep_elites, prm.decay = float(noise_beta), int(keep_elites), float(decay)
+        prm.return_best, prm.add_mean_last = int(bool(return_best)), int(bool(add_mean_last))
+        return prm
+
+    def icem_candidates(self, n, decay, it, keep_elites=0):
+        """Candidates of CEM iteration `it`: min(n, max(floor(n / decay^it), 2 num_elites, K + 1)), decay rounded to float32 as the
+        library receives it (csrc/icem.hip icem_n_it)."""
+        v = int(np.floor(float(n) / float(np.float32(decay)) ** it))
+        return min(n, max(v, 2 * self.num_elites, keep_elites + 1))
+
+    def icem_plan(self, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
+                  want_best_return=False):
+        """`cadm_icem_plan`.  carry [m,K,H,A] float32 / carry_valid [m] int32: caller-owned device tensors, read at iteration 0 and
+        rewritten after the last refit (required when params.keep_elites > 0).  `out` as in `cem_plan`."""
+        obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
+        cp_obs = None if cp_obs is None else self._t(cp_obs)
+        cp_act = None if cp_act is None else self._t(cp_act)
+        m, K = obs.shape[0], int(params.keep_elites)
+        if K > 0 and (carry is None or carry_valid is None or tuple(carry.shape) != (m, K, self.H, self.A) or carry.dtype != torch.float32
+                      or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
+            raise ValueError("icem_plan: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (K, m, K, self.H, self.A, m))
+        self.ensure_rollout(None, m, n)
+        key = ("icem", m, n, K)
+        if getattr(self, "_icem_ws_key", None) != key:
+            nbytes = self.lib.cadm_icem_workspace_bytes(self._ctx, m, n, K)
+            self._icem_ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
+            self._icem_ws_key = key
+        if out is None:
+            out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
+        best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
+        self._check(self.lib.cadm_icem_plan(self._ctx, ct.byref(params), ptr(obs), ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var),
+                                            ptr(carry), ptr(carry_valid), m, n, seed, call, ptr(self._icem_ws), ptr(out), ptr(best),
+                                            self.stream), "cadm_icem_plan")
+        return (out, best) if want_best_return else out
+
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D):
         z = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)

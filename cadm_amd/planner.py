@@ -11,6 +11,7 @@ checks -- an all-gather this module supplies over any torch.distributed backend 
 What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
+  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
@@ -137,3 +138,46 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
         raw = engine._t(raw, dtype=torch.int32)
         return raw[torch.arange(m, device=raw.device), best.long(), 0], cand
     return first.clamp(float(engine.cfg.lower_bound), float(engine.cfg.upper_bound)), cand
+
+
+def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
+              add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False):
+    """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
+    tests with injected draws and for diagnostics.  z / xi / eps: optional per-iteration lists of injected truncated-normal draws
+    [m,n_it,H,A] (noise_beta == 0), spectral draws [m,n_it,A,H] (noise_beta > 0) and head noise [H,m,n_it,p,D].  carry [m,K,H,A] /
+    carry_valid [m] int32 are read at iteration 0 and rewritten IN PLACE after the last refit, as the library does."""
+    obs = engine._t(obs)
+    mean, var = engine._t(init_mean).clone(), engine._t(init_var).clone()
+    m, K, iters = obs.shape[0], int(keep_elites), engine.num_cem_iters
+    lo, hi = float(engine.cfg.lower_bound), float(engine.cfg.upper_bound)
+    ctx_vec = engine.context_forward(cp_obs, cp_act) if engine.C > 0 else None
+    best_ret = torch.full((m,), float("-inf"), dtype=torch.float32, device=engine.device)
+    best_seq = torch.full((m, engine.H, engine.A), float("nan"), dtype=torch.float32, device=engine.device)
+    kept, info = None, []
+    for it in range(iters):
+        last = it + 1 == iters
+        ni = engine.icem_candidates(n, decay, it, K)
+        if noise_beta > 0:
+            actions = engine.sample_actions_colored(mean, var, ni, noise_beta, xi=None if xi is None else xi[it], seed=seed, call=call, it=it)
+        else:
+            actions = engine.sample_actions(mean, var, ni, z=None if z is None else z[it], seed=seed, call=call, it=it)
+        if K > 0 and it == 0:
+            engine.icem_inject(actions, carry, valid=carry_valid, shift=1)
+        elif K > 0:
+            engine.icem_inject(actions, kept)
+        if last and add_mean_last:
+            engine.icem_inject(actions, mean.clamp(lo, hi).unsqueeze(1).contiguous(), slot0=K)
+        rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
+        cand = engine.particle_mean(rows)
+        elites = engine.cem_refit(cand.unsqueeze(0), actions, mean, var, want_elites=True)
+        engine.icem_track_best(cand, elites, actions, best_ret, best_seq)
+        if K > 0:
+            kept = engine.icem_keep(actions, elites, K)
+            if last:
+                carry.copy_(kept)
+                carry_valid.fill_(1)
+        if return_info:
+            info.append(dict(actions=actions, rows=rows, cand=cand, elites=elites, kept=kept, mean=mean.clone(), var=var.clone()))
+    plan_mean = mean.clamp(lo, hi)
+    plan = best_seq if return_best else plan_mean
+    return (plan, info, dict(best_ret=best_ret, best_seq=best_seq, plan_mean=plan_mean)) if return_info else plan

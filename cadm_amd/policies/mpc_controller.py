@@ -52,12 +52,17 @@ class MPCController(object):
 class CEMWarmStart(object):
     """prev_sol / init_var bookkeeping of the samplers (sampler.py:50-57,118-120; samplers/utils.py:70-78)."""
 
-    def __init__(self, num_rollouts, horizon, act_dim):
+    def __init__(self, num_rollouts, horizon, act_dim, model=None):
+        self.model = model      # optional: a dynamics model whose iCEM planner carries elites between calls (reset with the warm start)
         self.prev_sol = np.tile(0., [num_rollouts, horizon, act_dim])
         self.init_var = np.tile(np.square(2) / 16, [num_rollouts, horizon, act_dim])   # = 0.25
 
     def reset(self, idx):                      # sampler.py:55-57
         self.prev_sol[idx] = 0.
+        if self.model is not None and hasattr(self.model, "reset_plan_carry"):      # a new episode never starts from the last one's elites
+            mask = np.zeros(self.prev_sol.shape[0], dtype=bool)
+            mask[idx] = True
+            self.model.reset_plan_carry(mask)
 
     def step(self, cem_solutions):             # sampler.py:118-120
         """Shift the plan left by one step, zero the tail, return the action to execute."""

@@ -269,6 +269,52 @@ int cadm_rs_plan(cadm_ctx* ctx, const float* obs, const float* cp_obs, const flo
                  int m, int n, uint32_t seed, uint32_t call, void* workspace,
                  float* action_out, int32_t* raw_best_out, void* stream);
 
+/* iCEM planner (Pinneri et al. 2020; no reference twin, OPT-IN beside cadm_cem_plan, which is untouched): temporally correlated
+ * candidate noise, elites carried over between CEM iterations and -- moved one step on -- between consecutive calls, optionally the
+ * best sequence seen as the plan, and a decaying candidate count.  Single rank, continuous actions.
+ *
+ * cadm_sample_actions_colored: one noise sequence z_0 .. z_{H-1} per (env mi, candidate c, action dim a) from spectral draws
+ * x_k, y_k ~ N(0,1):
+ *   z_t = c_b [ x_0 / sqrt2 + sum_{1 <= k < H/2} k^(-b/2) (x_k cos th_kt - y_k sin th_kt) + [H even] (H/2)^(-b/2) x_{H/2} (-1)^t / sqrt2 ],
+ *   th_kt = 2 pi ((k t) mod H) / H,   c_b = (1/2 + sum_{1 <= k < H/2} k^(-b) + [H even] (H/2)^(-b) / 2)^(-1/2)
+ * (Var z_t = 1 for every t, b; b = 0: an orthonormal transform of iid normals, white; b > 0: low frequencies weigh more), and
+ *   actions[mi,c,t,a] = clip(mean + sd z_t, lb, ub),  sd = sqrt(min(min(((mean-lb)/2)^2, ((ub-mean)/2)^2), var))  as cadm_sample_actions;
+ * no rejection step.  The spectral draws are injected -- xi [m,n,A,H]: slot 0 = x_0, then (x_k, y_k) in k order, x_{H/2} last when H
+ * is even: H numbers per sequence -- or, xi NULL, drawn from Philox4x32-10 keyed (seed, call) with counters (global sequence index
+ * (mi n + c) A + a, k, STREAM_ICEM | it<<8) and Box-Muller on the first two words (x_k = r cos, y_k = r sin).  0 <= beta <= 16;
+ * the horizon must fit the kernel's LDS (H <= 246). */
+typedef struct cadm_icem_params {
+    float noise_beta;       /* 0: the truncated-normal sampler of cadm_sample_actions, unchanged; > 0: coloured noise */
+    int32_t keep_elites;    /* K, 0 <= K <= num_elites */
+    float decay;            /* >= 1: iteration it uses min(n, max(floor(n / decay^it), 2 num_elites, K + 1)) candidates */
+    int32_t return_best;    /* 1: the plan is the best sequence of this call; 0: the refitted mean, clipped */
+    int32_t add_mean_last;  /* 1: candidate slot K of the last iteration is the current mean, clipped */
+} cadm_icem_params;
+int cadm_sample_actions_colored(cadm_ctx* ctx, const float* mean, const float* var, const float* xi, float beta,
+                                uint32_t seed, uint32_t call, int it, int m, int n, float* actions_out, void* stream);
+/* gather: kept_out[mi,j] = actions[mi, elites[mi,j]] for j < K; actions [m,n,H,A], elites [m,num_elites] as cadm_cem_refit's
+ * elites_out (return descending, ties to the lower index), kept_out [m,K,H,A] */
+int cadm_icem_keep(cadm_ctx* ctx, const float* actions, const int32_t* elites, int m, int n, int K, float* kept_out, void* stream);
+/* scatter: candidate slots [0,K) of actions_io [m,n,H,A] take kept [m,K,H,A]; shift = 1 (across calls): steps [0,H-1) take kept
+ * steps [1,H) and step H-1 keeps its value; valid [m] int32 (or NULL = all): envs with valid[mi] == 0 are left untouched */
+int cadm_icem_inject(cadm_ctx* ctx, const float* kept, const int32_t* valid, int m, int n, int K, int shift, float* actions_io,
+                     void* stream);
+/* per env: where cand_returns[mi, elites[mi,0]] is STRICTLY greater than best_ret_io[mi] (a tie, -0.0 against +0.0 included, and
+ * a NaN are not), that return and that candidate's sequence replace best_ret_io [m] / best_seq_io [m,H,A] */
+int cadm_icem_track_best(cadm_ctx* ctx, const float* cand_returns, const int32_t* elites, const float* actions, int m, int n,
+                         float* best_ret_io, float* best_seq_io, void* stream);
+/* The loop: context encoder once, then per iteration `it` with n_it candidates: sample (white or coloured), write the kept sequences
+ * into slots [0,K) -- iteration 0: carry_io [m,K,H,A] of envs with carry_valid_io[mi] != 0, moved one step on; later: the K best of
+ * the previous iteration -- and (last iteration, add_mean_last) the clipped mean into slot K; rollout; particle mean; refit; track the
+ * best; gather the K best (after the last refit into carry_io, setting carry_valid_io[mi] = 1).  plan_out [m,H,A]; best_return_out
+ * [m] optional: the best candidate return of the call.  carry_io / carry_valid_io are caller-owned and may be NULL when K == 0.
+ * CADM_EINVAL (before any HIP call) for a sharded ctx, discrete actions, K > num_elites, decay < 1, n < num_elites.
+ * workspace: cadm_icem_workspace_bytes(ctx, m, n, K) bytes (0 for bad arguments).  Everything is enqueued on `stream`. */
+size_t cadm_icem_workspace_bytes(cadm_ctx* ctx, int m, int n, int K);
+int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* params, const float* obs, const float* cp_obs, const float* cp_act,
+                   const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                   uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
+
 /* One training step = sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the

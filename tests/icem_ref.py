@@ -1,0 +1,175 @@
+"""numpy restatement of the iCEM planner's maths (csrc/icem.hip, include/cadm_hip.h "iCEM planner"): the coloured-noise synthesis,
+its Philox draws, the candidate schedule and the whole loop over the oracle's rollout and top-k.  Test infrastructure only."""
+import numpy as np
+
+from oracle import nets as onets
+from oracle import philox
+from oracle import planner as oplanner
+
+STREAM_ICEM = 4      # csrc/common.h CADM_STREAM_ICEM
+
+
+def cbeta(H, beta):
+    s = 0.5 + sum(float(k) ** -beta for k in range(1, H) if 2 * k < H)
+    if H % 2 == 0:
+        s += 0.5 * float(H // 2) ** -beta
+    return s ** -0.5
+
+
+def synthesis_matrix(H, beta):
+    """S [H, H] float64 with z = S @ xi: rows are time steps, columns the spectral slots (0 = x_0, then (x_k, y_k) at (2k - 1, 2k)
+    for 1 <= k < H / 2, x_{H/2} last when H is even)."""
+    S = np.zeros((H, H))
+    t = np.arange(H)
+    S[:, 0] = 1.0 / np.sqrt(2.0)
+    for k in range(1, H):
+        if 2 * k >= H:
+            break
+        th = 2.0 * np.pi * ((k * t) % H) / H
+        w = float(k) ** (-beta / 2.0)
+        S[:, 2 * k - 1] = w * np.cos(th)
+        S[:, 2 * k] = -w * np.sin(th)
+    if H % 2 == 0:
+        S[:, H - 1] = float(H // 2) ** (-beta / 2.0) * np.where(t % 2 == 0, 1.0, -1.0) / np.sqrt(2.0)
+    return cbeta(H, beta) * S
+
+
+def rho1(H, beta):
+    """Closed-form lag-1 autocorrelation of z."""
+    s = 0.5 + sum(float(k) ** -beta * np.cos(2.0 * np.pi * k / H) for k in range(1, H) if 2 * k < H)
+    if H % 2 == 0:
+        s -= 0.5 * float(H // 2) ** -beta
+    return cbeta(H, beta) ** 2 * s
+
+
+def colored_noise(xi, beta):
+    """xi [..., H] spectral draws -> z [..., H] (float64)."""
+    H = xi.shape[-1]
+    return np.asarray(xi, np.float64) @ synthesis_matrix(H, beta).T
+
+
+def colored_actions(mean, var, xi, beta, lower=-1.0, upper=1.0):
+    """mean / var [m,H,A], xi [m,n,A,H] -> actions [m,n,H,A] = clip(mean + sd z, lb, ub), float64."""
+    mean, var = np.asarray(mean, np.float64), np.asarray(var, np.float64)
+    z = np.transpose(colored_noise(xi, beta), (0, 1, 3, 2))      # [m,n,H,A]
+    sd = np.sqrt(oplanner.constrained_var(mean, var, lower, upper))
+    return np.clip(mean[:, None] + sd[:, None] * z, lower, upper)
+
+
+def spectral_draws(seed, call, it, m, n, A, H):
+    """The device's spectral draws [m,n,A,H] float32: Philox4x32-10 keyed (seed, call), counters (sequence (mi n + c) A + a, k,
+    STREAM_ICEM | it << 8), Box-Muller on the first two words: x_k = r cos, y_k = r sin."""
+    q = np.arange(m * n * A, dtype=np.uint64)
+    lo, hi = (q & np.uint64(0xFFFFFFFF)).astype(np.uint32), (q >> np.uint64(32)).astype(np.uint32)
+    out = np.zeros((m * n * A, H), np.float32)
+    for k in range(H // 2 + 1):
+        r = philox.philox4x32_10(philox._ctr(lo, np.uint32(k), hi, np.uint32(STREAM_ICEM | (it << 8))), philox._key(seed, call, q.shape))
+        x, y = philox.box_muller(philox.u01(r[..., 0]), philox.u01(r[..., 1]))
+        if k == 0:
+            out[:, 0] = x
+        elif 2 * k < H:
+            out[:, 2 * k - 1], out[:, 2 * k] = x, y
+        else:
+            out[:, H - 1] = x
+    return out.reshape(m, n, A, H)
+
+
+def n_candidates(n, decay, it, num_elites, K):
+    v = int(np.floor(float(n) / float(np.float32(decay)) ** it))
+    return min(n, max(v, 2 * num_elites, K + 1))
+
+
+def icem_loop(o, E, p, n, iters, num_elites, noise_beta=0.0, K=0, decay=1.0, return_best=False, add_mean_last=False, z=None, xi=None,
+              carry=None, carry_valid=None, alpha=0.1, lower=-1.0, upper=1.0, deterministic=True):
+    """The loop of section 2 of the issue over the oracle's rollout (deterministic model) and top-k.  o: helpers.oracle_problem(...)
+    of some dtype; z / xi: per-iteration lists of injected draws.  Returns (plan, info, carry, carry_valid)."""
+    dt = o["obs"].dtype.type
+    mean, var = o["init_mean"].copy(), o["init_var"].copy()
+    m, H, A = mean.shape
+    D = o["obs"].shape[1]
+    ctx = None if o["cp"] is None else onets.context_forward(o["cp"], o["cp_obs"], o["cp_act"], o["st"])
+    best_ret, best_seq = np.full(m, -np.inf, dt), np.full((m, H, A), np.nan, dt)
+    kept, info = None, []
+    for it in range(iters):
+        last = it + 1 == iters
+        ni = n_candidates(n, decay, it, num_elites, K)
+        if noise_beta > 0:
+            actions = colored_actions(mean, var, xi[it], noise_beta, lower, upper).astype(dt)
+        else:
+            actions = oplanner.sample_actions(mean, var, z[it].astype(dt), lower, upper).astype(dt)
+        assert actions.shape == (m, ni, H, A)
+        if K > 0 and it == 0 and carry is not None:
+            for mi in range(m):
+                if carry_valid[mi]:
+                    actions[mi, :K, :H - 1] = carry[mi, :, 1:]
+        elif K > 0 and it > 0:
+            actions[:, :K] = kept
+        if last and add_mean_last:
+            actions[:, K] = np.clip(mean, dt(lower), dt(upper))
+        T = None if ctx is None else oplanner.context_table_indexed(ctx, it)
+        rets = oplanner.rollout_indexed(o["env"], o["ff"], o["st"], o["obs"], T, actions, np.zeros((H, m, ni, p, D), dt), E, p, deterministic)
+        cand = oplanner.particle_mean(rets)
+        mean, var, idx = oplanner.elite_refit(mean, var, actions, cand, num_elites, dt(alpha))
+        top = cand[np.arange(m), idx[:, 0]]
+        for mi in range(m):
+            if top[mi] > best_ret[mi]:
+                best_ret[mi], best_seq[mi] = top[mi], actions[mi, idx[mi, 0]]
+        if K > 0:
+            kept = np.take_along_axis(actions, idx[:, :K, None, None], axis=1)
+        info.append(dict(actions=actions, cand=cand, elites=idx, kept=kept, mean=mean.copy(), var=var.copy()))
+    if K > 0:
+        carry, carry_valid = kept.copy(), np.ones(m, np.int32)
+    plan = best_seq if return_best else np.clip(mean, dt(lower), dt(upper))
+    return plan, info, carry, carry_valid
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the whole-loop cases shared by tests/test_icem_ref.py (CPU: the condition on the seeds) and tests/test_gpu_icem.py
+# ------------------------------------------------------------------------------------------------------------------------------
+LOOP = dict(E=5, p=5, m=2, n=64, num_elites=8, K=3, iters=3, hidden_sizes=(32,) * 4)
+LOOP_CASES = [(H, context, beta, decay) for H in (5, 6) for context in (False, True) for beta in (0.0, 1.0) for decay in (1.0, 1.5)]
+# problem / draw seed per case: the first at which the float32 and the float64 oracle pick the same elites, in the same order, in
+# every iteration, with every gap among the 9 best returns above LOOP_MIN_GAP of their scale (a result within the 1e-5 bar of
+# the float64 returns then ranks them the same way) -- tests/test_icem_ref.py checks that they still do
+LOOP_SEEDS = {(5, False, 0.0, 1.0): 4, (5, False, 0.0, 1.5): 0, (5, False, 1.0, 1.0): 1, (5, False, 1.0, 1.5): 0, (5, True, 0.0, 1.0): 3,
+              (5, True, 0.0, 1.5): 3, (5, True, 1.0, 1.0): 21, (5, True, 1.0, 1.5): 10, (6, False, 0.0, 1.0): 5, (6, False, 0.0, 1.5): 2,
+              (6, False, 1.0, 1.0): 25, (6, False, 1.0, 1.5): 4, (6, True, 0.0, 1.0): 19, (6, True, 0.0, 1.5): 16, (6, True, 1.0, 1.0): 0,
+              (6, True, 1.0, 1.5): 0}
+LOOP_MIN_GAP = 2e-4      # smallest gap between neighbouring returns among the 9 best, over the largest |return|: 20 x the 1e-5 bar
+
+
+def loop_case(H, context, beta, decay, seed=None):
+    """(problem, per-iteration z or None, per-iteration xi or None, carry [m,K,H,A] float32, carry_valid [m]) of one loop case: a warm
+    start away from zero, env 1 carrying elites from an earlier call and env 0 not."""
+    from cadm_amd import synth
+    from helpers import trunc_z
+    c = LOOP
+    seed = LOOP_SEEDS.get((H, context, beta, decay), 0) if seed is None else seed
+    prob = synth.make_problem(env="halfcheetah", context=context, E=c["E"], m=c["m"], H=H, seed=100 + seed, hidden_sizes=c["hidden_sizes"],
+                              trained_like=True)
+    rng = np.random.default_rng(1000 + seed)
+    A = prob["A"]
+    prob["init_mean"] = rng.uniform(-0.6, 0.6, (c["m"], H, A)).astype(np.float32).astype(np.float64)
+    prob["init_var"] = rng.uniform(0.05, 0.3, (c["m"], H, A)).astype(np.float32).astype(np.float64)
+    for k in ("obs", "cp_obs", "cp_act"):
+        prob[k] = prob[k].astype(np.float32).astype(np.float64)
+    for k in ("ff", "cp", "stats"):      # float32-representable weights and statistics: the float64 oracle evaluates the device's model
+        if prob[k] is not None:
+            prob[k] = type(prob[k])((name, np.asarray(v).astype(np.float32).astype(np.float64)) for name, v in prob[k].items())
+    ns = [n_candidates(c["n"], decay, it, c["num_elites"], c["K"]) for it in range(c["iters"])]
+    z = xi = None
+    if beta > 0:
+        xi = [rng.standard_normal((c["m"], ni, A, H)).astype(np.float32) for ni in ns]
+    else:
+        z = [trunc_z(rng, (c["m"], ni, H, A)).astype(np.float32) for ni in ns]
+    carry = rng.uniform(-1.0, 1.0, (c["m"], c["K"], H, A)).astype(np.float32)
+    return prob, z, xi, carry, np.array([0, 1], np.int32)
+
+
+def loop_reference(H, context, beta, decay, dtype, seed=None):
+    from helpers import oracle_problem
+    prob, z, xi, carry, valid = loop_case(H, context, beta, decay, seed)
+    c = LOOP
+    o = oracle_problem(prob, dtype)
+    return icem_loop(o, c["E"], c["p"], c["n"], c["iters"], c["num_elites"], noise_beta=beta, K=c["K"], decay=decay, add_mean_last=True,
+                     z=z, xi=xi, carry=carry.astype(dtype), carry_valid=valid)
