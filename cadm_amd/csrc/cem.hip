@@ -1,6 +1,6 @@
 // CEM / random-shooting bookkeeping kernels: action sampling (core/utils.py:425-429, 498-503),
 // particle mean (:474), elite refit (:475-486), RS argmax (:554-561), final clip (dynamics.py:365-366).
-#include "common.h"
+#include "planner.h"
 
 // ---------------------------------------------------------------------------------------------
 // action sampling
@@ -594,7 +594,7 @@ int cadm_launch_particle_mean_tail(cadm_ctx* ctx, const float* returns_rows, int
 
 int cadm_launch_refit(cadm_ctx* ctx, const float* cand_returns, const float* rows, int G, int n_local, const float* actions,
                       int m, const float* mean_in, const float* var_in, float* mean_out, float* var_out, int32_t* elites_out,
-                      float* plan_out, hipStream_t stream, const RefitRegen* regen) {
+                      float* plan_out, hipStream_t stream, const RefitRegen* regen, PlanDone done) {
     RefitRegen rg{};
     if (regen) rg = *regen;
     rg.lb = ctx->cfg.lower_bound; rg.ub = ctx->cfg.upper_bound;
@@ -623,7 +623,7 @@ int cadm_launch_refit(cadm_ctx* ctx, const float* cand_returns, const float* row
     hipLaunchKernelGGL(cem_refit_kernel, dim3(m), dim3(1024), lds, stream, cand_returns, rows, ctx->p, G, n_local, actions,
                        m, ctx->H, ctx->A, ctx->cfg.num_elites, ctx->cfg.alpha, npow2, mean_in, var_in, mean_out, var_out,
                        elites_out, plan_out, ctx->cfg.lower_bound, ctx->cfg.upper_bound, ctx->cfg.discrete ? 0 : 1, (int)lds_keys,
-                       plan_out ? ctx->plan_done : nullptr, ctx->plan_done_val, rg);
+                       plan_out ? done.flags : nullptr, done.val, rg);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;
 }
@@ -634,7 +634,7 @@ extern "C" int cadm_cem_refit(cadm_ctx* ctx, const float* cand_returns, int G, i
                  "cadm_cem_refit: bad arguments");
     CADM_ON_DEVICE(ctx);
     return cadm_launch_refit(ctx, cand_returns, nullptr, G, n_local, actions, m, mean_io, var_io, mean_io, var_io, elites_out,
-                             nullptr, (hipStream_t)stream, nullptr);
+                             nullptr, (hipStream_t)stream);
 }
 
 extern "C" int cadm_cem_refit_regen(cadm_ctx* ctx, const float* cand_returns, int G, int n_local, int m, float* mean_io, float* var_io,

@@ -27,7 +27,7 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_HID_LIST 200              // the reference default --hidden_size (run_cadm_pets.py:129)
 #endif
 // bumped whenever cadm_ctx / RolloutArgs change: a side module built against another layout is refused
-#define CADM_CTX_LAYOUT_TAG 3005
+#define CADM_CTX_LAYOUT_TAG 3006
 
 #define CADM_CHECK_HIP(expr)                                                                   \
     do {                                                                                       \
@@ -149,9 +149,6 @@ struct cadm_ctx {
     std::vector<hipEvent_t> prof_ag;   // start/stop pairs around the per-iteration ncclAllGather (sharded planner)
     size_t prof_ag_used = 0;
     unsigned long long* tbuf = nullptr;   // cadm_dev_set_timing_buffer (developer library only)
-    // completion flags of a staged planner call (cadm_cem_plan_staged): [m] words in pinned host memory, released by the last refit
-    unsigned* plan_done = nullptr;
-    unsigned plan_done_val = 0;
     // candidate-sharded planning (dist.hip): the RCCL communicator the ctx owns, OR an all-gather supplied by the host
     // (cadm_dist_init_external: torch.distributed over any backend) -- the planner loop is the same, only the collective differs
     void* comm = nullptr;
@@ -191,38 +188,11 @@ int cadm_launch_rollout(cadm_ctx* ctx, const float* obs, const float* obs_rows, 
                         uint32_t call, int it, int cand_offset, int n_global, int m, int n_local,
                         float* returns_rows, float* traj_out, hipStream_t s, int dry_run = 0, int force_deterministic = -1,
                         int horizon = 0);      // horizon > 0 (cadm_eval_horizon only): that many steps, actions [m,n_global,horizon,A]; 0: cfg.horizon
-// Sharded planner (capi.hip: cem_plan_impl): what the refit needs to REGENERATE the elites' action sequences by global
-// candidate id instead of reading them (a rank draws only its own shard), and to check the input checksums at the end of every rank's
-// all-gather payload.
-struct RefitRegen {
-    int on;                    // 1: elite actions are drawn again from (seed, call, it); the actions pointer may be null
-    uint32_t seed, call; int it;
-    float lb, ub;
-    int gstride;               // floats per rank in the gathered buffer (0: m * n_local); m * n_local + 1 with the trailing checksum
-    int my_rank;               // >= 0: compare every rank's checksum with this rank's; mismatch -> NaN plan
-    unsigned* mismatch;        // device word raised on a checksum mismatch (ctx->dist_flag), may be null
-    unsigned* mismatch_host;   // pinned host words [m] behind the completion flags of a staged call, may be null
-};
 inline bool cadm_sharded(const cadm_ctx* c) { return c->comm != nullptr || c->ext_allgather != nullptr; }
-int cadm_launch_input_checksum(cadm_ctx* ctx, const float* obs, const float* cp_obs, const float* cp_act, const float* mean, const float* var,
-                               int m, unsigned* out, hipStream_t s);
 // force_batched: take the GEMM-shaped encoder whatever m is (the per-row kernel of small calls sums in another order): a row's
 // context is then the same bits however the caller cuts its histories into calls (cadm_eval_horizon)
 int cadm_launch_context(cadm_ctx* ctx, const float* cp_obs, const float* cp_act, int m, int bs,
                         float* out, hipStream_t s, int force_batched = 0);
-// Per-call inputs of a small planner call travel as KERNEL ARGUMENTS (cadm_cem_plan_staged, capi.hip): up to CADM_INGEST_MAX floats.
-#define CADM_INGEST_MAX 960
-struct IngestBlock { float v[CADM_INGEST_MAX]; };
-// the fused head's copy of the block shares the 4 KB kernel-argument segment with the encoder's and the sampler's arguments: a smaller cap
-// (blocks between the two caps take the plain ingest kernel + the unfused head)
-#define CADM_HEAD_INGEST_MAX 896
-struct HeadBlock { float v[CADM_HEAD_INGEST_MAX]; };
-#define CADM_CONTEXT_BATCHED_MIN_ROWS 48    // histories per member from which the context encoder runs as a GEMM chain (context.hip)
-// The head of a staged planner call as ONE launch (context.hip: plan_head_kernel): unpack the ingest block into the device block, the
-// context encoder on the block's history (C > 0), and the candidates of CEM iteration 0.  off[5] = float offsets of obs, cp_obs,
-// cp_act, init_mean, init_var inside the block (-1: absent).
-int cadm_launch_plan_head(cadm_ctx* ctx, const float* host_block, int nfloats, const int32_t off[5], float* dev_block, int m, int n,
-                          uint32_t seed, uint32_t call, float* ctx_out, float* actions_out, hipStream_t s);
 void cadm_train_free(cadm_ctx* ctx);
 // (developer library: dev/dev_api.hip) Adam moment buffers of one trained tensor; layer as in cadm_set_weights, is_bias 0 / 1;
 // layer == -1 / -2: max_logvar / min_logvar of the forward net.  Returns null pointers before cadm_train_configure, and CADM_EINVAL

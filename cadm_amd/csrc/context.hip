@@ -5,10 +5,10 @@
 // many histories per call (get_context_pred from the PPO consumer, SURVEY 8f-3: a GEMM chain on the fp32 matrix pipe).
 #include <string.h>
 
-#include "common.h"
+#include "planner.h"
 
 #define CP_MAX_WIDTH 1024
-// (CADM_CONTEXT_BATCHED_MIN_ROWS, common.h: below it, one latency-tuned workgroup per row -- the planner's m = 1..10)
+// (CADM_CONTEXT_BATCHED_MIN_ROWS, planner.h: below it, one latency-tuned workgroup per row -- the planner's m = 1..10)
 
 struct CpArgs {
     const float* W[CADM_MAX_CP_LAYERS + 1];

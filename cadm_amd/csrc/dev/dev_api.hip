@@ -4,6 +4,7 @@
 //   * a forced row-tile flavour of the production kernel (tests/test_gpu_rowtiles.py),
 //   * the phase-timing buffer of the CADM_PHASE_TIMING build (tools/phase_timing.py).
 // Selection is per ctx and explicit (these calls); nothing reads the environment.
+#include "../planner.h"
 #include "../rollout_args.h"
 #include "dev_api.h"
 
@@ -98,10 +99,6 @@ extern "C" int cadm_dev_read_adam_moment(cadm_ctx* ctx, int net, int layer, int 
     CADM_CHECK_HIP(hipMemcpyAsync(dst, second ? v : m, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return CADM_OK;
 }
-
-int cadm_launch_refit(cadm_ctx* ctx, const float* cand_returns, const float* rows, int G, int n_local, const float* actions,
-                      int m, const float* mean_in, const float* var_in, float* mean_out, float* var_out, int32_t* elites_out,
-                      float* plan_out, hipStream_t stream, const RefitRegen* regen);
 
 extern "C" int cadm_dev_refit_sharded(cadm_ctx* ctx, const float* payload, int G, int n_local, int m, int my_rank, float* mean_io, float* var_io,
                                       uint32_t seed, uint32_t call, int it, float* plan_out, void* stream) {

@@ -1,6 +1,6 @@
 // Open-loop prediction error of the ensemble along the horizon: trajectories of a rollout (`traj_out` of the rollout kernel,
 // [F, m, 1, p, D]) against held-out next observations, reduced on the device to per-step sums (cadm_horizon_error;
-// cadm_eval_horizon in capi.hip strings encoder, rollout and this kernel together chunk by chunk).
+// cadm_eval_horizon, at the end of this file, strings encoder, rollout and this kernel together chunk by chunk).
 //
 // Per (window i, step h) that is VALID -- future_bool[i, 0..h] all non-zero: a hole invalidates everything behind it -- and whose
 // p * D trajectory values are all finite (else the pair only counts in diverged[h]):
@@ -21,7 +21,7 @@
 // Traffic: `traj` is read exactly once -- a (block, step)'s windows are one contiguous span of 64 * p * D floats, loaded lane-linear
 // with 16-byte loads into LDS (scalar loads where the span is not 16-byte aligned), 16 windows at a time; means and variances are
 // formed from LDS in two passes (mean first: a one-pass sum of squares cancels).  Truth (1 / p of the traffic) and mask are read in place.
-#include "common.h"
+#include "planner.h"
 
 namespace {
 
@@ -192,6 +192,94 @@ extern "C" int cadm_horizon_error(const float* traj, const float* truth, long lo
         hipLaunchKernelGGL(horizon_finalize_kernel, dim3((total + HE_THREADS - 1) / HE_THREADS), dim3(HE_THREADS), 0, s, partials, block0 + nblk, F,
                            E, D, se_out, spread_out, se_member_out, count_out, diverged_out);
         CADM_CHECK_HIP(hipGetLastError());
+    }
+    return CADM_OK;
+}
+
+// cadm_eval_horizon: encoder, rollout and the statistics kernel above, strung together chunk by chunk of held-out windows
+// rows of `width` floats, `src_ld` floats apart -> contiguous rows
+__global__ void strided_rows_kernel(const float* __restrict__ src, size_t src_ld, float* __restrict__ dst, size_t width, size_t total) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / width, c = i - r * width;
+        dst[i] = src[r * src_ld + c];
+    }
+}
+
+static int launch_strided_rows(const float* src, size_t src_ld, float* dst, size_t width, size_t rows, hipStream_t s) {
+    const size_t total = width * rows, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(strided_rows_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, src, src_ld, dst, width, total);
+    CADM_CHECK_HIP(hipGetLastError());
+    return CADM_OK;
+}
+
+struct EvalWs {
+    float *obs0, *ctxv, *rows, *traj, *eps, *partials;
+    long long blocks;
+};
+
+// windows per launch: the caller's chunk, no larger than the dataset rounded up to whole blocks of 64
+static int eval_chunk(int N, int chunk) {
+    const long long n64 = ((long long)N + 63) / 64 * 64;
+    return (int)(chunk < n64 ? chunk : n64);
+}
+
+static size_t eval_carve(cadm_ctx* ctx, int N, int F, int chunk, char* base, EvalWs* w) {
+    Carver c{base};
+    const size_t mc = (size_t)eval_chunk(N, chunk), blocks = ((size_t)N + 63) / 64;
+    EvalWs t;
+    t.obs0 = c.take<float>(mc * ctx->D);
+    t.ctxv = c.take<float>((size_t)ctx->E * mc * (ctx->C > 0 ? ctx->C : 1));
+    t.rows = c.take<float>(mc * ctx->p);
+    t.traj = c.take<float>((size_t)F * mc * ctx->p * ctx->D);
+    t.eps = c.take<float>((size_t)F * mc * ctx->p * ctx->D);      // a chunk of injected noise, made contiguous
+    t.partials = c.take<float>(blocks * F * ((size_t)(2 + ctx->E) * ctx->D + 2));
+    t.blocks = (long long)blocks;
+    if (w) *w = t;
+    return c.off;
+}
+
+extern "C" size_t cadm_eval_workspace_bytes(cadm_ctx* ctx, int N, int F, int chunk) {
+    if (!ctx || N <= 0 || F <= 0 || chunk <= 0 || chunk % 64) return 0;
+    return eval_carve(ctx, N, F, chunk, nullptr, nullptr);
+}
+
+extern "C" int cadm_eval_horizon(cadm_ctx* ctx, const float* ds_obs, const float* ds_act, const float* ds_obs_next, const float* ds_cp_obs,
+                                 const float* ds_cp_act, const float* future_bool, int N, int F, int chunk, uint32_t seed, uint32_t call,
+                                 const float* eps, void* workspace, float* se_out, float* spread_out, float* se_member_out,
+                                 int32_t* count_out, int32_t* diverged_out, void* stream) {
+    CADM_REQUIRE(ctx && ds_obs && ds_act && ds_obs_next && future_bool && workspace && se_out && spread_out && se_member_out && count_out &&
+                     diverged_out, "cadm_eval_horizon: null argument");
+    CADM_REQUIRE(N >= 1 && F >= 1, "cadm_eval_horizon: N (%d) and F (%d) must be >= 1", N, F);
+    CADM_REQUIRE(chunk >= 64 && chunk % 64 == 0, "cadm_eval_horizon: chunk (%d) must be a positive multiple of 64", chunk);
+    CADM_REQUIRE(F <= ctx->H, "cadm_eval_horizon: F (%d) exceeds the model's planning horizon n_forwards (%d)", F, ctx->H);
+    CADM_REQUIRE(ctx->C == 0 || (ds_cp_obs && ds_cp_act), "cadm_eval_horizon: ds_cp_obs / ds_cp_act required for a context model");
+    CADM_ON_DEVICE(ctx);
+    int rc = cadm_require_ready(ctx, "cadm_eval_horizon");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (!ctx->packed && (rc = cadm_pack_streams(ctx, s))) return rc;
+    EvalWs w;
+    eval_carve(ctx, N, F, chunk, (char*)workspace, &w);
+    const int D = ctx->D, A = ctx->A, p = ctx->p, Hh = ctx->cfg.history_length, mc_max = eval_chunk(N, chunk);
+    const bool inject = eps && !ctx->cfg.deterministic;
+    CADM_REQUIRE(((long long)N + mc_max - 1) / mc_max < (1 << 23), "cadm_eval_horizon: N (%d) needs too many chunks of %d windows", N, mc_max);
+    for (int w0 = 0; w0 < N; w0 += mc_max) {
+        const int mc = N - w0 < mc_max ? N - w0 : mc_max;
+        // start state of every window: ds_obs[w, 0, :]
+        if ((rc = launch_strided_rows(ds_obs + (size_t)w0 * F * D, (size_t)F * D, w.obs0, D, mc, s))) return rc;
+        if (ctx->C > 0 && (rc = cadm_launch_context(ctx, ds_cp_obs + (size_t)w0 * D * Hh, ds_cp_act + (size_t)w0 * A * Hh, mc, 0, w.ctxv, s,
+                                                    /*force_batched=*/1))) return rc;
+        // eps [F, N, 1, p, D] -> this chunk's [F, mc, 1, p, D]
+        if (inject && (rc = launch_strided_rows(eps + (size_t)w0 * p * D, (size_t)N * p * D, w.eps, (size_t)mc * p * D, F, s))) return rc;
+        // one rollout of F steps: every window is an env with ONE candidate, its recorded actions ([N, F * A] is [m, 1, F, A]).  The
+        // iteration word is 2 * (chunk index): even, so the context layout is iteration 0's, and device-drawn noise (keyed by the row
+        // INSIDE the launch and the iteration word) is not repeated from chunk to chunk
+        if ((rc = cadm_launch_rollout(ctx, w.obs0, nullptr, ctx->C > 0 ? w.ctxv : nullptr, ds_act + (size_t)w0 * F * A, inject ? w.eps : nullptr,
+                                      /*norm_actions=*/1, seed, call, /*it=*/2 * (w0 / mc_max), 0, 1, mc, 1, w.rows, w.traj, s, 0, -1, /*horizon=*/F))) return rc;
+        const bool last = w0 + mc >= N;
+        if ((rc = cadm_horizon_error(w.traj, ds_obs_next + (size_t)w0 * F * D, (long long)F * D, future_bool + (size_t)w0 * F, mc, F, p, ctx->E, D,
+                                     w0, w.partials, w.blocks, se_out, spread_out, se_member_out, count_out, diverged_out, last ? 1 : 0, stream)))
+            return rc;
     }
     return CADM_OK;
 }

@@ -1,5 +1,5 @@
 // iCEM planner (Pinneri et al. 2020, "Sample-efficient Cross-Entropy Method for Real-time Planning"): an OPT-IN second planner loop
-// beside cem_plan_impl (capi.hip).  No reference twin: the reference's CEM block (core/utils.py:398-488) draws white truncated-normal
+// beside cem_plan_impl (plan.hip).  No reference twin: the reference's CEM block (core/utils.py:398-488) draws white truncated-normal
 // noise and keeps nothing between iterations or calls.  New here:
 //   * temporally correlated ("coloured") candidate noise, synthesised per sequence from H spectral draws (icem_colored_kernel);
 //   * elite carry-over inside a call and, shifted by one step, between calls (icem_keep_kernel / icem_inject_kernel);
@@ -8,12 +8,7 @@
 // The rollout, the context encoder, the truncated-normal sampler and the elite refit are the reference path's, called unchanged.
 #include <math.h>
 
-#include "common.h"
-
-int cadm_launch_clip(const float* in, float* out, int total, float lo, float hi, int do_clip, hipStream_t s);
-int cadm_launch_refit(cadm_ctx* ctx, const float* cand_returns, const float* rows, int G, int n_local, const float* actions,
-                      int m, const float* mean_in, const float* var_in, float* mean_out, float* var_out, int32_t* elites_out,
-                      float* plan_out, hipStream_t stream, const RefitRegen* regen);
+#include "planner.h"
 
 // ---------------------------------------------------------------------------------------------
 // coloured-noise candidates
@@ -245,23 +240,22 @@ struct IcemWs {
 };
 
 static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, char* base, IcemWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
     IcemWs t;
-    t.ctxv = (float*)take((size_t)ctx->E * m * (ctx->C > 0 ? ctx->C : 1) * 4);
-    t.actions = (float*)take((size_t)m * n * HA * 4);
-    t.rows = (float*)take((size_t)m * n * ctx->p * 4);
-    t.cand = (float*)take((size_t)m * n * 4);
-    t.mean = (float*)take((size_t)m * HA * 4);
-    t.var = (float*)take((size_t)m * HA * 4);
-    t.meanclip = (float*)take((size_t)m * HA * 4);
-    t.kept = (float*)take((size_t)m * (K > 0 ? K : 1) * HA * 4);
-    t.best_ret = (float*)take((size_t)m * 4);
-    t.best_seq = (float*)take((size_t)m * HA * 4);
-    t.elites = (int32_t*)take((size_t)m * ctx->cfg.num_elites * 4);
+    t.ctxv = c.take<float>((size_t)ctx->E * m * (ctx->C > 0 ? ctx->C : 1));
+    t.actions = c.take<float>((size_t)m * n * HA);
+    t.rows = c.take<float>((size_t)m * n * ctx->p);
+    t.cand = c.take<float>((size_t)m * n);
+    t.mean = c.take<float>((size_t)m * HA);
+    t.var = c.take<float>((size_t)m * HA);
+    t.meanclip = c.take<float>((size_t)m * HA);
+    t.kept = c.take<float>((size_t)m * (K > 0 ? K : 1) * HA);
+    t.best_ret = c.take<float>((size_t)m);
+    t.best_seq = c.take<float>((size_t)m * HA);
+    t.elites = c.take<int32_t>((size_t)m * ctx->cfg.num_elites);
     if (w) *w = t;
-    return off;
+    return c.off;
 }
 
 extern "C" size_t cadm_icem_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) {
@@ -326,7 +320,7 @@ extern "C" int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* prm, const 
                                        w.rows, nullptr, stream))) return rc;
         if ((rc = cadm_particle_mean(ctx, w.rows, m, ni, w.cand, stream))) return rc;
         float* plan = (last && !prm->return_best) ? plan_out : nullptr;      // the refitted mean, clipped (dynamics.py:365-366)
-        if ((rc = cadm_launch_refit(ctx, w.cand, nullptr, 1, ni, w.actions, m, mean_in, var_in, w.mean, w.var, w.elites, plan, s, nullptr))) return rc;
+        if ((rc = cadm_launch_refit(ctx, w.cand, nullptr, 1, ni, w.actions, m, mean_in, var_in, w.mean, w.var, w.elites, plan, s))) return rc;
         if (track && (rc = launch_track_best(ctx, w.cand, w.elites, w.actions, m, ni, w.best_ret, w.best_seq, s))) return rc;
         if (K > 0 && (rc = last ? launch_keep(ctx, w.actions, w.elites, m, ni, K, carry_io, carry_valid_io, s)
                                 : launch_keep(ctx, w.actions, w.elites, m, ni, K, w.kept, nullptr, s))) return rc;

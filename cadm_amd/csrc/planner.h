@@ -1,0 +1,79 @@
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, context.hip, horizon.hip): the loops' types, ONE declaration
+// of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
+#pragma once
+#include "common.h"
+
+// Sharded planner (plan.hip: cem_plan_impl): what the refit needs to REGENERATE the elites' action sequences by global
+// candidate id instead of reading them (a rank draws only its own shard), and to check the input checksums at the end of every rank's
+// all-gather payload.
+struct RefitRegen {
+    int on;                    // 1: elite actions are drawn again from (seed, call, it); the actions pointer may be null
+    uint32_t seed, call; int it;
+    float lb, ub;
+    int gstride;               // floats per rank in the gathered buffer (0: m * n_local); m * n_local + 1 with the trailing checksum
+    int my_rank;               // >= 0: compare every rank's checksum with this rank's; mismatch -> NaN plan
+    unsigned* mismatch;        // device word raised on a checksum mismatch (ctx->dist_flag), may be null
+    unsigned* mismatch_host;   // pinned host words [m] behind the completion flags of a staged call, may be null
+};
+// completion flags of a staged planner call: [m] words in pinned host memory, set to `val` by the refit that writes the plan (null: none)
+struct PlanDone { unsigned* flags = nullptr; unsigned val = 0; };
+// Per-call inputs of a small planner call travel as KERNEL ARGUMENTS (cadm_cem_plan_staged, plan.hip): up to CADM_INGEST_MAX floats.
+#define CADM_INGEST_MAX 960
+struct IngestBlock { float v[CADM_INGEST_MAX]; };
+// the fused head's copy of the block shares the 4 KB kernel-argument segment with the encoder's and the sampler's arguments: a smaller cap
+// (blocks between the two caps take the plain ingest kernel + the unfused head)
+#define CADM_HEAD_INGEST_MAX 896
+struct HeadBlock { float v[CADM_HEAD_INGEST_MAX]; };
+#define CADM_CONTEXT_BATCHED_MIN_ROWS 48    // histories per member from which the context encoder runs as a GEMM chain (context.hip)
+
+// Views of a caller's workspace, taken in order, each start rounded up to 256 bytes.  base == null: only the running total is wanted.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    template <class T> T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
+// cem.hip
+int cadm_launch_clip(const float* in, float* out, int total, float lo, float hi, int do_clip, hipStream_t s);
+int cadm_launch_refit(cadm_ctx* ctx, const float* cand_returns, const float* rows, int G, int n_local, const float* actions,
+                      int m, const float* mean_in, const float* var_in, float* mean_out, float* var_out, int32_t* elites_out,
+                      float* plan_out, hipStream_t stream, const RefitRegen* regen = nullptr, PlanDone done = {});
+int cadm_launch_refit_sample(cadm_ctx* ctx, const float* cand_returns, const float* rows, int G, int n_local, float* actions, int m,
+                             const float* mean_in, const float* var_in, float* mean_out, float* var_out, uint32_t seed, uint32_t call,
+                             int next_it, hipStream_t stream);
+bool cadm_refit_sample_ok(const cadm_ctx* ctx, int n);
+int cadm_launch_particle_mean_tail(cadm_ctx* ctx, const float* returns_rows, int m, int n_local, float* cand_returns, const unsigned* tail,
+                                   hipStream_t stream);
+int cadm_launch_input_checksum(cadm_ctx* ctx, const float* obs, const float* cp_obs, const float* cp_act, const float* mean, const float* var,
+                               int m, unsigned* out, hipStream_t s);
+// The head of a staged planner call as ONE launch (context.hip: plan_head_kernel): unpack the ingest block into the device block, the
+// context encoder on the block's history (C > 0), and the candidates of CEM iteration 0.  off[5] = float offsets of obs, cp_obs,
+// cp_act, init_mean, init_var inside the block (-1: absent).
+int cadm_launch_plan_head(cadm_ctx* ctx, const float* host_block, int nfloats, const int32_t off[5], float* dev_block, int m, int n,
+                          uint32_t seed, uint32_t call, float* ctx_out, float* actions_out, hipStream_t s);
+int cadm_rollout_builtin_env(cadm_ctx* ctx);     // rollout.hip
+
+// next start/stop event pair of a profiling list (grown on demand)
+inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {
+    if (used + 2 > ev.size()) {
+        hipEvent_t a, b;
+        CADM_CHECK_HIP(hipEventCreate(&a));
+        CADM_CHECK_HIP(hipEventCreate(&b));
+        ev.push_back(a);
+        ev.push_back(b);
+    }
+    *e0 = ev[used];
+    *e1 = ev[used + 1];
+    used += 2;
+    return CADM_OK;
+}
+
+inline int cadm_require_ready(cadm_ctx* ctx, const char* who) {
+    if (!ctx->st.set) { cadm_set_error("%s: normalisation stats not set (call cadm_set_norm_stats)", who); return CADM_ESTATE; }
+    if (!ctx->ff_maxlv || !ctx->ff_minlv) { cadm_set_error("%s: logvar bounds not set", who); return CADM_ESTATE; }
+    return CADM_OK;
+}

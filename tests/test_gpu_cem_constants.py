@@ -328,11 +328,11 @@ def test_random_shooting_with_bounds(gpu):
 # ------------------------------------------------------------------------------------------------------------------------------
 # the staged call on each input route
 # ------------------------------------------------------------------------------------------------------------------------------
-HEAD_MAX, INGEST_MAX, BATCHED_MIN_ROWS = 896, 960, 48      # csrc/common.h CADM_HEAD_INGEST_MAX, CADM_INGEST_MAX, CADM_CONTEXT_BATCHED_MIN_ROWS
+HEAD_MAX, INGEST_MAX, BATCHED_MIN_ROWS = 896, 960, 48      # csrc/planner.h CADM_HEAD_INGEST_MAX, CADM_INGEST_MAX, CADM_CONTEXT_BATCHED_MIN_ROWS
 
 
 def _route(nfloats, m):
-    """capi.hip cadm_cem_plan_staged: how a block of `nfloats` floats for m envs reaches the device."""
+    """plan.hip cadm_cem_plan_staged: how a block of `nfloats` floats for m envs reaches the device."""
     if nfloats <= HEAD_MAX and m < BATCHED_MIN_ROWS:
         return "head"
     return "ingest" if nfloats <= INGEST_MAX else "copy"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Bitwise comparison of two builds of the library on the same inputs (developer tool; needs a GPU):
-   python tools/compare_libs.py libA.so libB.so      -- rollouts (returns + trajectories) and whole CEM plans over a set of
-problem shapes, then the training step: the losses of three steps, every weight tensor afterwards, the prediction heads and one
+   python tools/compare_libs.py libA.so libB.so      -- rollouts (returns + trajectories) and every planner route (CEM plan from device
+and from host arrays, random shooting, two iCEM calls that share a carry) over a set of problem shapes, the open-loop horizon error, then the training step: the losses of three steps, every weight tensor afterwards, the prediction heads and one
 evaluation step.  A schedule-only change of a kernel, or a host-only change, must print 'identical' everywhere."""
 import os
 import sys
@@ -39,6 +39,30 @@ TRAIN_CASES = [  # env, context + backward model, hidden sizes, E, B, det
     ("spec", True, (200,) * 4, 5, 37, False),
     ("slim_humanoid", True, (128, 200, 96, 200), 3, 100, False),  # unequal hidden widths, ragged row tile
 ]
+EVAL_CASES = [  # env, context, windows N (no multiple of the chunk), steps F, chunk, det
+    ("halfcheetah", True, 70, 3, 64, False),
+    ("ant", False, 150, 4, 64, True),
+]
+
+
+def eval_case(lib, env, context, N, F, chunk, det):
+    """open-loop horizon error of a small synthetic windowed set: device-drawn noise, then injected noise"""
+    prob = synth.make_problem(env=env, context=context, E=5, m=N, H=6, trained_like=True, seed=7)
+    rng = np.random.default_rng(3)
+    D, A = prob["D"], prob["A"]
+    obs = rng.standard_normal((N, F, D))
+    obs[:, 0] = prob["obs"]
+    mask = (rng.uniform(size=(N, F)) > 0.1).astype(np.float32)
+    ds = dict(obs=obs.reshape(N, -1), act=rng.uniform(-1, 1, (N, F * A)), obs_next=obs.reshape(N, -1) + 0.1 * rng.standard_normal((N, F * D)),
+              cp_obs=prob["cp_obs"], cp_act=prob["cp_act"], future_bool=mask)
+    eng = synth.make_engine(prob, p=5, deterministic=det, lib=lib)
+    dev = {k: eng._t(v) for k, v in ds.items() if v is not None}
+    res = []
+    for kw in (dict(seed=7, call=3), dict(eps=rng.standard_normal((F, N, 1, 5, D)).astype(np.float32))):
+        res += [v.cpu().numpy() for _, v in sorted(eng.eval_horizon(dev, N, F, chunk=chunk, **kw).items())]
+    torch.cuda.synchronize()
+    eng.close()
+    return res
 
 
 def train_case(lib, env, full, hids, E, B, det):
@@ -80,8 +104,17 @@ def main():
                 rows, traj = eng.rollout_returns(prob["obs"], ctx, acts, want_traj=True, norm_actions=not prob["discrete"], **kw)
                 res += [rows.cpu().numpy(), traj.cpu().numpy()]
             if not prob["discrete"] and n >= 50:
-                res.append(eng.cem_plan(prob["obs"], prob["cp_obs"] if context else None, prob["cp_act"] if context else None,
-                                        prob["init_mean"], prob["init_var"], n, seed=1, call=2).cpu().numpy())
+                cp = (prob["cp_obs"], prob["cp_act"]) if context else (None, None)
+                res.append(eng.cem_plan(prob["obs"], *cp, prob["init_mean"], prob["init_var"], n, seed=1, call=2).cpu().numpy())
+                res.append(eng.cem_plan_host((prob["obs"], *cp, prob["init_mean"], prob["init_var"]), n, seed=1, call=3))
+                res.append(eng.rs_plan(prob["obs"], *cp, n, seed=1, call=4).cpu().numpy())
+                prm = eng.icem_params(noise_beta=1.0, keep_elites=3, decay=1.25, add_mean_last=True)
+                carry = torch.zeros((m, 3, H, prob["A"]), dtype=torch.float32, device=eng.device)
+                valid = torch.zeros((m,), dtype=torch.int32, device=eng.device)
+                for call in (5, 6):      # the second call starts from the elites the first one left in the carry
+                    res += [x.cpu().numpy() for x in eng.icem_plan(prm, prob["obs"], *cp, prob["init_mean"], prob["init_var"], n, carry=carry,
+                                                                   carry_valid=valid, seed=1, call=call, want_best_return=True)]
+                res += [carry.cpu().numpy(), valid.cpu().numpy()]
             torch.cuda.synchronize()
             outs.append(res)
             eng.close()
@@ -90,6 +123,12 @@ def main():
         bad += 0 if (same and finite) else 1
         print("%-14s ctx=%d hid=%d E=%d p=%d m=%d n=%d H=%d det=%d: %s%s" % (env, context, hid, E, p, m, n, H, det,
               "identical" if same else "DIFFERENT", "" if finite else " (non-finite!)"))
+    for case in EVAL_CASES:
+        outs = [eval_case(lib, *case) for lib in libs]
+        same = all(np.array_equal(x, y, equal_nan=True) for x, y in zip(*outs))
+        finite = all(np.isfinite(x).all() for x in outs[1])
+        bad += 0 if (same and finite) else 1
+        print("eval_horizon %-14s ctx=%d N=%d F=%d chunk=%d det=%d: %s%s" % (case + ("identical" if same else "DIFFERENT", "" if finite else " (non-finite!)")))
     for case in TRAIN_CASES:
         outs = [train_case(lib, *case) for lib in libs]
         same = len(outs[0]) == len(outs[1]) and all(np.array_equal(x, y, equal_nan=True) for x, y in zip(*outs))
