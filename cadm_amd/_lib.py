@@ -60,6 +60,10 @@ class IcemParams(C.Structure):          # include/cadm_hip.h cadm_icem_params
                 ("add_mean_last", C.c_int32)]
 
 
+class MppiParams(C.Structure):          # include/cadm_hip.h cadm_mppi_params
+    _fields_ = [("icem", IcemParams), ("temperature", C.c_float), ("relative", C.c_int32)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -105,6 +109,9 @@ SIGNATURES = {
     "cadm_icem_track_best": (_i, [_P, _P, _P, _P, _i, _i, _P, _P, _P]),
     "cadm_icem_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
     "cadm_icem_plan": (_i, [_P, C.POINTER(IcemParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_mppi_refit": (_i, [_P, _P, _P, _i, _i, C.c_float, _i, _P, _P, _P, _P]),
+    "cadm_mppi_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
+    "cadm_mppi_plan": (_i, [_P, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

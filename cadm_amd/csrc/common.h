@@ -164,6 +164,9 @@ struct cadm_ctx {
     cadm_env_spec spec{};
     bool spec_set = false;
     int* spec_feat = nullptr;
+    // weights and group partials of a stand-alone cadm_mppi_refit (mppi.hip), grown on demand; the planner loop carves its own
+    float* mppi_scratch = nullptr;
+    size_t mppi_scratch_floats = 0;
 };
 
 // Entry points launch on the ctx's device whatever device the caller's thread has current (two engines on different GPUs in

@@ -6,6 +6,7 @@
 //   * the best sequence seen in a call as the plan (icem_track_best_kernel);
 //   * a decaying candidate count.
 // The rollout, the context encoder, the truncated-normal sampler and the elite refit are the reference path's, called unchanged.
+// The loop takes its update as a parameter: cadm_icem_plan runs it with the elite refit, cadm_mppi_plan with the MPPI refit (mppi.hip).
 #include <math.h>
 
 #include "planner.h"
@@ -234,15 +235,25 @@ extern "C" int cadm_icem_track_best(cadm_ctx* ctx, const float* cand_returns, co
 // ---------------------------------------------------------------------------------------------
 // the planner loop
 // ---------------------------------------------------------------------------------------------
+// the update that turns an iteration's scored candidates into the next distribution: the elite refit (cem.hip), or the softmax-weighted
+// refit over all candidates (mppi.hip).  The rest of the loop is one body.
+struct PlanUpdate {
+    const char* who;           // the entry point's name, for its messages
+    int mppi;                  // 0: cadm_launch_refit; 1: cadm_launch_mppi_refit
+    float temperature;
+    int relative;
+};
+
 struct IcemWs {
     float *ctxv, *actions, *rows, *cand, *mean, *var, *meanclip, *kept, *best_ret, *best_seq;
     int32_t* elites;
+    float *emean, *evar, *mppi;      // MPPI only: where the elite selection's own refit goes (discarded), the update's weights and partials
 };
 
-static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, char* base, IcemWs* w) {
+static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w) {
     Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
-    IcemWs t;
+    IcemWs t{};
     t.ctxv = c.take<float>((size_t)ctx->E * m * (ctx->C > 0 ? ctx->C : 1));
     t.actions = c.take<float>((size_t)m * n * HA);
     t.rows = c.take<float>((size_t)m * n * ctx->p);
@@ -254,13 +265,23 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, char* base, I
     t.best_ret = c.take<float>((size_t)m);
     t.best_seq = c.take<float>((size_t)m * HA);
     t.elites = c.take<int32_t>((size_t)m * ctx->cfg.num_elites);
+    if (mppi) {
+        t.emean = c.take<float>((size_t)m * HA);
+        t.evar = c.take<float>((size_t)m * HA);
+        t.mppi = c.take<float>(cadm_mppi_scratch_floats(ctx, m, n));
+    }
     if (w) *w = t;
     return c.off;
 }
 
 extern "C" size_t cadm_icem_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) {
     if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, nullptr, nullptr);
+    return icem_carve(ctx, m, n, K, 0, nullptr, nullptr);
+}
+
+extern "C" size_t cadm_mppi_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
+    return icem_carve(ctx, m, n, K, 1, nullptr, nullptr);
 }
 
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
@@ -272,28 +293,30 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     return ni < n ? ni : n;
 }
 
-extern "C" int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
-                              const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
-                              uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
-    CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "cadm_icem_plan: bad arguments");
-    CADM_REQUIRE(!cadm_sharded(ctx), "cadm_icem_plan: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)");
-    CADM_REQUIRE(!ctx->cfg.discrete, "cadm_icem_plan: continuous actions only");
+static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_icem_params* prm, const float* obs, const float* cp_obs,
+                     const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                     uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+    const char* who = upd.who;
+    CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
+    CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
+    CADM_REQUIRE(!ctx->cfg.discrete, "%s: continuous actions only", who);
     const int K = prm->keep_elites, KE = ctx->cfg.num_elites, iters = ctx->cfg.num_cem_iters;
-    CADM_REQUIRE(K >= 0 && K <= KE, "cadm_icem_plan: keep_elites %d outside [0, num_elites %d]", K, KE);
-    CADM_REQUIRE(prm->decay >= 1.0f && prm->decay <= 1e6f, "cadm_icem_plan: decay %g must be >= 1", (double)prm->decay);
-    CADM_REQUIRE(prm->noise_beta >= 0.0f && prm->noise_beta <= 16.0f, "cadm_icem_plan: noise_beta %g outside [0, 16]", (double)prm->noise_beta);
-    CADM_REQUIRE(n >= KE, "cadm_icem_plan: n_candidates %d < num_elites %d", n, KE);
-    CADM_REQUIRE(!prm->add_mean_last || n >= K + 1, "cadm_icem_plan: n_candidates %d leaves no slot for the mean candidate behind %d kept elites", n, K);
-    CADM_REQUIRE(K == 0 || (carry_io && carry_valid_io), "cadm_icem_plan: carry / carry_valid required with keep_elites > 0");
-    CADM_REQUIRE(ctx->C == 0 || (cp_obs && cp_act), "cadm_icem_plan: cp_obs/cp_act required for a context model");
-    CADM_REQUIRE(prm->noise_beta == 0.0f || icem_colored_lds(ctx->H) <= 64 * 1024, "cadm_icem_plan: horizon %d is too long for the coloured sampler", ctx->H);
+    CADM_REQUIRE(K >= 0 && K <= KE, "%s: keep_elites %d outside [0, num_elites %d]", who, K, KE);
+    CADM_REQUIRE(prm->decay >= 1.0f && prm->decay <= 1e6f, "%s: decay %g must be >= 1", who, (double)prm->decay);
+    CADM_REQUIRE(prm->noise_beta >= 0.0f && prm->noise_beta <= 16.0f, "%s: noise_beta %g outside [0, 16]", who, (double)prm->noise_beta);
+    CADM_REQUIRE(n >= KE, "%s: n_candidates %d < num_elites %d", who, n, KE);
+    CADM_REQUIRE(!prm->add_mean_last || n >= K + 1, "%s: n_candidates %d leaves no slot for the mean candidate behind %d kept elites", who, n, K);
+    CADM_REQUIRE(K == 0 || (carry_io && carry_valid_io), "%s: carry / carry_valid required with keep_elites > 0", who);
+    CADM_REQUIRE(ctx->C == 0 || (cp_obs && cp_act), "%s: cp_obs/cp_act required for a context model", who);
+    CADM_REQUIRE(prm->noise_beta == 0.0f || icem_colored_lds(ctx->H) <= 64 * 1024, "%s: horizon %d is too long for the coloured sampler", who, ctx->H);
+    int rc;
+    if (upd.mppi && (rc = cadm_mppi_check(ctx, m, upd.temperature, who))) return rc;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    icem_carve(ctx, m, n, K, (char*)workspace, &w);
+    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w);
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
-    int rc;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
     if (track) {
         hipLaunchKernelGGL(icem_best_init_kernel, dim3(icem_grid((size_t)m * HA)), dim3(256), 0, s, m, HA, w.best_ret, w.best_seq);
@@ -320,7 +343,16 @@ extern "C" int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* prm, const 
                                        w.rows, nullptr, stream))) return rc;
         if ((rc = cadm_particle_mean(ctx, w.rows, m, ni, w.cand, stream))) return rc;
         float* plan = (last && !prm->return_best) ? plan_out : nullptr;      // the refitted mean, clipped (dynamics.py:365-366)
-        if ((rc = cadm_launch_refit(ctx, w.cand, nullptr, 1, ni, w.actions, m, mean_in, var_in, w.mean, w.var, w.elites, plan, s))) return rc;
+        if (!upd.mppi) {
+            if ((rc = cadm_launch_refit(ctx, w.cand, nullptr, 1, ni, w.actions, m, mean_in, var_in, w.mean, w.var, w.elites, plan, s))) return rc;
+        } else {
+            // the elite ids that keep / track-best read are the elite selection's (top num_elites by return, descending, ties to the lower
+            // index): its own refit goes to scratch.  Only when somebody reads them.
+            if ((K > 0 || track) &&
+                (rc = cadm_launch_refit(ctx, w.cand, nullptr, 1, ni, w.actions, m, mean_in, var_in, w.emean, w.evar, w.elites, nullptr, s))) return rc;
+            if ((rc = cadm_launch_mppi_refit(ctx, w.cand, w.actions, m, ni, upd.temperature, upd.relative, mean_in, var_in, w.mean, w.var, plan,
+                                             w.mppi, s))) return rc;
+        }
         if (track && (rc = launch_track_best(ctx, w.cand, w.elites, w.actions, m, ni, w.best_ret, w.best_seq, s))) return rc;
         if (K > 0 && (rc = last ? launch_keep(ctx, w.actions, w.elites, m, ni, K, carry_io, carry_valid_io, s)
                                 : launch_keep(ctx, w.actions, w.elites, m, ni, K, w.kept, nullptr, s))) return rc;
@@ -328,4 +360,22 @@ extern "C" int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* prm, const 
     if (prm->return_best && (rc = cadm_launch_clip(w.best_seq, plan_out, m * HA, 0.0f, 0.0f, 0, s))) return rc;
     if (best_return_out && (rc = cadm_launch_clip(w.best_ret, best_return_out, m, 0.0f, 0.0f, 0, s))) return rc;
     return CADM_OK;
+}
+
+extern "C" int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
+                              const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                              uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+    const PlanUpdate upd{"cadm_icem_plan", 0, 0.0f, 0};
+    return icem_loop(ctx, upd, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call, workspace, plan_out,
+                     best_return_out, stream);
+}
+
+// the same loop with the MPPI update (mppi.hip) in place of the elite refit
+extern "C" int cadm_mppi_plan(cadm_ctx* ctx, const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
+                              const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                              uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_mppi_plan: bad arguments");
+    const PlanUpdate upd{"cadm_mppi_plan", 1, prm->temperature, prm->relative};
+    return icem_loop(ctx, upd, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call, workspace,
+                     plan_out, best_return_out, stream);
 }

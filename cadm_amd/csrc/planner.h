@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, context.hip, horizon.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, context.hip, horizon.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -56,6 +56,13 @@ int cadm_launch_input_checksum(cadm_ctx* ctx, const float* obs, const float* cp_
 int cadm_launch_plan_head(cadm_ctx* ctx, const float* host_block, int nfloats, const int32_t off[5], float* dev_block, int m, int n,
                           uint32_t seed, uint32_t call, float* ctx_out, float* actions_out, hipStream_t s);
 int cadm_rollout_builtin_env(cadm_ctx* ctx);     // rollout.hip
+// mppi.hip: the softmax-weighted refit.  scratch: cadm_mppi_scratch_floats(ctx, m, n) floats, 16-byte aligned; mean_in / var_in may
+// alias mean_out / var_out.  cadm_mppi_check: the refusals of the update (temperature, discrete, sharded), before any HIP call.
+size_t cadm_mppi_scratch_floats(const cadm_ctx* ctx, int m, int n);
+int cadm_mppi_check(const cadm_ctx* ctx, int m, float temperature, const char* who);
+int cadm_launch_mppi_refit(cadm_ctx* ctx, const float* cand_returns, const float* actions, int m, int n, float temperature, int relative,
+                           const float* mean_in, const float* var_in, float* mean_out, float* var_out, float* plan_out, float* scratch,
+                           hipStream_t s);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

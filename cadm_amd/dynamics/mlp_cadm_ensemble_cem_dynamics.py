@@ -24,6 +24,9 @@ Differences a caller can see (all opt-in except the first):
     "iCEM planner").  At their defaults (0.0, 0, 1.0, "mean", False) `get_action` is the reference's CEM, unchanged; any other value
     plans with `cadm_icem_plan` -- coloured action noise, elites kept between CEM iterations and (moved one step on) between
     consecutive calls, `reset_plan_carry` to forget them at an episode boundary;
+  * `cem_update="mppi"`, `cem_temperature`, `cem_temperature_relative`: the MPPI update (INTEGRATION.md "MPPI update") in that loop --
+    every candidate refits the mean and variance with weight exp(return / temperature) instead of the top `num_elites` alone;
+    `cem_update="mppi"` alone takes the opt-in route, the default "cem" leaves everything as it is;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
     prediction of every ensemble member (the reference has no public predict).
 """
@@ -152,6 +155,9 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_decay=1.0,
                  cem_return="mean",
                  cem_add_mean=False,
+                 cem_update="cem",
+                 cem_temperature=1.0,
+                 cem_temperature_relative=False,
                  engine_lib=None,
                  ):
         self.env = env
@@ -209,10 +215,18 @@ class MLPEnsembleCEMDynamicsModel(object):
 
         # the iCEM planner's switches: all at their defaults = the reference's CEM (`_icem` stays None and get_action never looks further)
         self._icem = None
-        if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean)) != (0.0, 0, 1.0, "mean", False):
+        self._icem_update = "cem"
+        if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
+                bool(cem_temperature_relative)) != (0.0, 0, 1.0, "mean", False, "cem", 1.0, False):
             if not use_cem:
-                raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean configure the CEM planner: "
-                                 "they need use_cem=True")
+                raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature "
+                                 "configure the CEM planner: they need use_cem=True")
+            if cem_update not in ("cem", "mppi"):
+                raise ValueError("cem_update must be 'cem' or 'mppi', got %r" % (cem_update,))
+            if not (np.isfinite(float(cem_temperature)) and float(cem_temperature) > 0.0):
+                raise ValueError("cem_temperature must be finite and > 0, got %r" % (cem_temperature,))
+            if cem_update == "cem" and (float(cem_temperature) != 1.0 or bool(cem_temperature_relative)):
+                raise ValueError("cem_temperature / cem_temperature_relative configure the MPPI update: they need cem_update='mppi'")
             if cem_return not in ("mean", "best"):
                 raise ValueError("cem_return must be 'mean' or 'best', got %r" % (cem_return,))
             if not 0.0 <= float(cem_noise_beta) <= 16.0:
@@ -230,6 +244,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                                               "one rank: carried elites cannot be regenerated by id")
             self._icem = dict(noise_beta=float(cem_noise_beta), keep_elites=int(cem_keep_elites), decay=float(cem_decay),
                               return_best=cem_return == "best", add_mean_last=bool(cem_add_mean))
+            self._icem_update = cem_update
+            self._mppi = dict(temperature=float(cem_temperature), relative=bool(cem_temperature_relative))
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (iCEM, keep_elites > 0)
 
         self.env_kind = resolve_env_kind(env)
@@ -261,7 +277,10 @@ class MLPEnsembleCEMDynamicsModel(object):
         if self._icem is not None:
             if self._icem["keep_elites"] > self.engine.num_elites:
                 raise ValueError("cem_keep_elites=%d exceeds the planner's %d elites" % (self._icem["keep_elites"], self.engine.num_elites))
-            self._icem_params = HipEngine.icem_params(**self._icem)
+            if self._icem_update == "mppi":
+                self._icem_params = HipEngine.mppi_params(**self._mppi, **self._icem)
+            else:
+                self._icem_params = HipEngine.icem_params(**self._icem)
 
     # ------------------------------------------------------------------ planning
     def _push_stats(self):
@@ -400,7 +419,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         return action
 
     def _get_action_icem(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
-        """The opt-in iCEM route of get_action: one `cadm_icem_plan` call; the elites it keeps for the next call stay on the device."""
+        """The opt-in iCEM route of get_action: one `cadm_icem_plan` call (`cadm_mppi_plan` with cem_update="mppi"); the elites it keeps
+        for the next call stay on the device."""
         m = int(np.shape(obs)[0])
         if m == 0:
             return np.zeros((0, self.n_forwards, self.action_space_dims), np.float32)
@@ -418,8 +438,9 @@ class MLPEnsembleCEMDynamicsModel(object):
         if self.context_out_dim == 0:
             cp_obs = cp_act = None
         host = eng.host_out((m, self.n_forwards, self.action_space_dims))
-        eng.icem_plan(self._icem_params, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
-                      carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=host)
+        run = eng.mppi_plan if self._icem_update == "mppi" else eng.icem_plan
+        run(self._icem_params, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
+            carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=host)
         torch.cuda.current_stream(eng.device).synchronize()
         return host.numpy().copy()
 

@@ -574,6 +574,52 @@ class HipEngine:
                                             self.stream), "cadm_icem_plan")
         return (out, best) if want_best_return else out
 
+    # ------------------------------------------------------------------ MPPI update (opt-in; csrc/mppi.hip)
+    def mppi_refit(self, cand, actions, mean, var, temperature=1.0, relative=False, want_plan=False):
+        """`cadm_mppi_refit`: cand [m,n], actions [m,n,H,A]; mean / var [m,H,A] updated IN PLACE with the softmax-weighted statistics of
+        ALL candidates (weights exp((R - max R) / lambda); `relative`: lambda is a fraction of the env's return range).  want_plan:
+        also returns clip(new mean) [m,H,A]."""
+        m, n = actions.shape[0], actions.shape[1]
+        if tuple(cand.shape) != (m, n) or tuple(mean.shape) != (m, self.H, self.A) or tuple(var.shape) != (m, self.H, self.A):
+            raise ValueError("mppi_refit: cand %r, actions %r, mean %r, var %r do not agree" % (tuple(cand.shape), tuple(actions.shape),
+                                                                                           tuple(mean.shape), tuple(var.shape)))
+        plan = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device) if want_plan else None
+        self._check(self.lib.cadm_mppi_refit(self._ctx, ptr(cand), ptr(actions), m, n, float(temperature), int(bool(relative)), ptr(mean),
+                                             ptr(var), ptr(plan), self.stream), "cadm_mppi_refit")
+        return plan
+
+    @staticmethod
+    def mppi_params(temperature=1.0, relative=False, **icem):
+        """`cadm_mppi_params`: the switches of `icem_params` plus the temperature and its relative flag."""
+        prm = _lib.MppiParams()
+        prm.icem = HipEngine.icem_params(**icem)
+        prm.temperature, prm.relative = float(temperature), int(bool(relative))
+        return prm
+
+    def mppi_plan(self, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
+                  want_best_return=False):
+        """`cadm_mppi_plan`: the loop of `icem_plan` with the MPPI update in place of the elite refit.  Arguments as `icem_plan`."""
+        obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
+        cp_obs = None if cp_obs is None else self._t(cp_obs)
+        cp_act = None if cp_act is None else self._t(cp_act)
+        m, K = obs.shape[0], int(params.icem.keep_elites)
+        if K > 0 and (carry is None or carry_valid is None or tuple(carry.shape) != (m, K, self.H, self.A) or carry.dtype != torch.float32
+                      or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
+            raise ValueError("mppi_plan: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (K, m, K, self.H, self.A, m))
+        self.ensure_rollout(None, m, n)
+        key = ("mppi", m, n, K)
+        if getattr(self, "_mppi_ws_key", None) != key:
+            nbytes = self.lib.cadm_mppi_workspace_bytes(self._ctx, m, n, K)
+            self._mppi_ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
+            self._mppi_ws_key = key
+        if out is None:
+            out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
+        best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
+        self._check(self.lib.cadm_mppi_plan(self._ctx, ct.byref(params), ptr(obs), ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var),
+                                            ptr(carry), ptr(carry_valid), m, n, seed, call, ptr(self._mppi_ws), ptr(out), ptr(best),
+                                            self.stream), "cadm_mppi_plan")
+        return (out, best) if want_best_return else out
+
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D):
         z = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)

@@ -315,6 +315,33 @@ int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* params, const float* o
                    const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                    uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
 
+/* MPPI update (Williams et al. 2017; no reference twin, OPT-IN): a softmax-weighted refit over ALL candidates in place of the top-k
+ * elite refit.  Per env, with F = the candidates whose return is finite (NaN, +inf and -inf get weight 0):
+ *   R* = max_F R,   lambda_eff = temperature (relative == 0)   or   temperature (R* - min_F R) (relative != 0);
+ *   w_c = exp((R_c - R*) / lambda_eff)   (relative and lambda_eff == 0, all finite returns equal: w_c = 1),   W = sum_c w_c >= 1,
+ *   mu = sum_c w_c a_c / W,   v = sum_c w_c (a_c - mu)^2 / W   (the mean first, then the variance around it),
+ *   mean <- alpha mean + (1 - alpha) mu,   var <- alpha var + (1 - alpha) v   (the ctx's alpha, the blend of cadm_cem_refit),
+ *   plan_out [m,H,A] (optional; device or pinned host memory) = clip(new mean, lower_bound, upper_bound).
+ * An env without any finite return keeps mean_io / var_io bit for bit, and its plan is clip(mean).  The action sequences must be
+ * finite.  Sums are taken in a fixed order (csrc/mppi.hip, "Reduction contract"): the same bits run to run, and per env whatever m.
+ *   cand_returns [m,n], actions [m,n,H,A], mean_io / var_io [m,H,A] updated in place
+ * CADM_EINVAL (before any HIP call) for a temperature that is not finite and > 0, discrete actions, a sharded ctx. */
+int cadm_mppi_refit(cadm_ctx* ctx, const float* cand_returns, const float* actions, int m, int n, float temperature, int relative,
+                    float* mean_io, float* var_io, float* plan_out, void* stream);
+/* The loop of cadm_icem_plan with this update in place of the elite refit; everything else composes unchanged: white or coloured
+ * sampling, kept elites across iterations and calls, the candidate-count decay, add_mean_last, return_best, best_return_out.  The
+ * elites that are kept and tracked are still the top num_elites by return (descending, ties to the lower index).  Refusals: those of
+ * cadm_icem_plan, and the temperature check.  workspace: cadm_mppi_workspace_bytes(ctx, m, n, K) bytes (0 for bad arguments). */
+typedef struct cadm_mppi_params {
+    cadm_icem_params icem;
+    float temperature;      /* lambda > 0 */
+    int32_t relative;       /* != 0: lambda is a fraction of the env's return range R* - min_F R */
+} cadm_mppi_params;
+size_t cadm_mppi_workspace_bytes(cadm_ctx* ctx, int m, int n, int K);
+int cadm_mppi_plan(cadm_ctx* ctx, const cadm_mppi_params* params, const float* obs, const float* cp_obs, const float* cp_act,
+                   const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                   uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
+
 /* One training step = sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the

@@ -1,0 +1,432 @@
+"""GPU: the opt-in MPPI update (csrc/mppi.hip: `cadm_mppi_refit`) and the planner loop that uses it (`cadm_mppi_plan`, csrc/icem.hip).
+
+Geometry as tests/test_gpu_icem.py: halfcheetah, vanilla and CaDM, hidden (32,) * 4, ensemble 5, particles 5, m = 2, num_elites = 8, 3 CEM
+iterations, H = 5 (H A = 30: scalar loads) and H = 6 (H A = 36: 16-byte loads).  Numpy restatement: tests/mppi_ref.py, used at float64.
+
+The bars against float64 are the project's: the mean within 1e-5 absolute, the variance within 1e-5 of its largest element.  The kernel's
+header states a rounding chain of 2 (15 + ceil(n / 64)) + 4 = 68 roundings at n = 1030; 68 x 2^-24 + 30 x 2^-23 = 7.6e-6 < 1e-5."""
+import ctypes as ct
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import mppi_ref
+from cadm_amd import _lib
+from cadm_amd import planner as hplanner
+from cadm_amd import synth
+from cadm_amd.engine import HipEngine
+from helpers import make_engine
+
+pytestmark = pytest.mark.gpu
+
+HID = (32,) * 4
+M, N, KE, K, ITERS, A = 2, 64, 8, 3, 3, 6
+BAR = 1e-5
+assert (2 * (15 + (1030 + 63) // 64) + 4) * 2.0 ** -24 + 30 * 2.0 ** -23 < BAR      # the chain of csrc/mppi.hip's header at n = 1030
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def _engine(H, context=False, env="halfcheetah"):
+    prob = synth.make_problem(env=env, context=context, E=5, m=M, H=H, seed=3, hidden_sizes=HID, trained_like=env == "halfcheetah")
+    return prob, make_engine(prob, p=5, num_elites=KE, num_cem_iters=ITERS)
+
+
+def _refit_data(H, n, seed):
+    """Actions in [-1, 1]; returns in [-3, 3] with both ends present, so that a temperature fixes the largest exponent argument."""
+    rng = np.random.default_rng(seed)
+    mean = rng.uniform(-0.7, 0.7, (M, H, A)).astype(np.float32)
+    var = rng.uniform(0.02, 0.3, (M, H, A)).astype(np.float32)
+    actions = rng.uniform(-1.0, 1.0, (M, n, H, A)).astype(np.float32)
+    cand = rng.uniform(-3.0, 3.0, (M, n)).astype(np.float32)
+    cand[:, 3], cand[:, n - 2] = -3.0, 3.0
+    return mean, var, actions, cand
+
+
+def _temperature(relative, spread):
+    """(R* - R_c) / lambda_eff <= 24 (narrow) or <= 300 (wide: the far tail underflows to weight 0) on a return range of 6."""
+    arg = 24.0 if spread == "narrow" else 300.0
+    return float(np.float32(1.0 / arg if relative else 6.0 / arg))
+
+
+def _reference(mean, var, actions, cand, temperature, relative, alpha=0.1):
+    return mppi_ref.mppi_update(*(np.asarray(x, np.float64) for x in (mean, var, actions, cand)), temperature, relative, alpha=alpha)
+
+
+def _check_against_float64(got_mean, got_var, got_plan, ref, what):
+    rm, rv, rp = ref
+    em, ev = np.abs(got_mean - rm).max(), np.abs(got_var - rv).max() / np.abs(rv).max()
+    print("\n[%s] mean: max abs %.2e; var: %.2e of its largest element" % (what, em, ev), end="")
+    assert em <= BAR, what
+    assert ev <= BAR, what
+    if got_plan is not None:
+        assert np.abs(got_plan - rp).max() <= BAR and np.abs(got_plan).max() <= 1.0, what
+    return em, ev
+
+
+def _refit(eng, mean, var, actions, cand, temperature, relative, want_plan=True):
+    tm, tv = eng._t(mean).clone(), eng._t(var).clone()
+    plan = eng.mppi_refit(eng._t(cand), eng._t(actions), tm, tv, temperature=temperature, relative=relative, want_plan=want_plan)
+    return _np(tm), _np(tv), None if plan is None else _np(plan)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- 1
+@pytest.mark.parametrize("spread", ["narrow", "wide"])
+@pytest.mark.parametrize("relative", [False, True], ids=["absolute", "relative"])
+@pytest.mark.parametrize("n", [64, 130, 1030])
+@pytest.mark.parametrize("H", [5, 6])
+def test_refit_against_float64(gpu, H, n, relative, spread):
+    """`cadm_mppi_refit` on injected returns and actions against the float64 restatement: one group (n = 64), a ragged last group (130),
+    many groups (1030); scalar (H = 5) and 16-byte (H = 6) loads; exponent arguments up to 24, and up to 300.
+    Measured on an MI355X, worst over the 24 cases: mean 1.1e-07 absolute; var 2.0e-07 of its largest element."""
+    prob, eng = _engine(H)
+    mean, var, actions, cand = _refit_data(H, n, 100 * H + n)
+    lam = _temperature(relative, spread)
+    got = _refit(eng, mean, var, actions, cand, lam, relative)
+    ref = _reference(mean, var, actions, cand, lam, relative, alpha=float(np.float32(eng.cfg.alpha)))
+    _check_against_float64(*got, ref, "H=%d n=%d %s %s" % (H, n, "relative" if relative else "absolute", spread))
+    # the update moved the distribution, and towards the best candidates: not the plain candidate mean
+    assert np.abs(got[0] - mean).max() > 0.05
+    flat = _reference(mean, var, actions, np.zeros_like(cand), lam, relative, alpha=float(np.float32(eng.cfg.alpha)))
+    assert np.abs(got[0] - flat[0]).max() > 0.05
+
+
+def test_refit_on_more_than_one_element_tile(gpu):
+    """H A = 1032 > 1024: two element tiles per group, the second 8 elements wide.  Measured: mean 7.6e-08, var 1.8e-07."""
+    H, n = 172, 130
+    prob, eng = _engine(H)
+    mean, var, actions, cand = _refit_data(H, n, 7)
+    got = _refit(eng, mean, var, actions, cand, 0.25, False)
+    _check_against_float64(*got, _reference(mean, var, actions, cand, 0.25, False, alpha=float(np.float32(eng.cfg.alpha))), "H=172 n=130")
+
+
+def test_equal_returns_and_a_far_best_candidate(gpu):
+    """Known answers on the device: equal returns (relative: lambda_eff == 0) give the candidates' plain mean and biased variance;
+    a best candidate 200 lambda above the rest is the new mean exactly (alpha blends it with the old mean: one rounding each)."""
+    H, n = 6, 130
+    prob, eng = _engine(H)
+    alpha = np.float64(np.float32(eng.cfg.alpha))
+    mean, var, actions, cand = _refit_data(H, n, 11)
+    for relative in (False, True):
+        gm, gv, _ = _refit(eng, mean, var, actions, np.full_like(cand, 1.75), 0.5, relative)
+        a64 = actions.astype(np.float64)
+        assert np.abs(gm - (alpha * mean + (1 - alpha) * a64.mean(axis=1))).max() <= BAR
+        assert np.abs(gv - (alpha * var + (1 - alpha) * a64.var(axis=1))).max() <= BAR
+    far = np.minimum(cand, 0.0) - np.float32(200 * 0.05)
+    far[0, 5], far[1, 77] = 0.0, 0.0
+    gm, gv, _ = _refit(eng, mean, var, actions, far, 0.05, False)
+    best = actions[np.arange(M), [5, 77]]
+    np.testing.assert_array_equal(gm, mean * np.float32(eng.cfg.alpha) + (np.float32(1.0) - np.float32(eng.cfg.alpha)) * best)
+    np.testing.assert_array_equal(gv, var * np.float32(eng.cfg.alpha))
+
+
+# ---------------------------------------------------------------------------------------------------------------------- 2
+@pytest.mark.parametrize("H", [5, 6])
+def test_non_finite_returns_bit_for_bit(gpu, H):
+    """NaN / +inf / -inf returns weigh nothing: the result equals, bit for bit, the one with those candidates' returns replaced by a
+    finite value whose weight underflows to 0, and is within the bars of the float64 reference that drops them (measured: mean
+    5.2e-08, var 2.3e-07).  An env whose
+    returns are all NaN keeps mean / var bit for bit and plans clip(mean); the other env's result is the one it has alone."""
+    n = 130
+    prob, eng = _engine(H)
+    mean, var, actions, cand = _refit_data(H, n, 20 + H)
+    mean[1, 0, 0], mean[1, H - 1, 5] = 1.5, -2.0                      # (clip(mean) is not mean)
+    bad = cand.copy()
+    bad[0, [1, 64, 129]] = [np.nan, np.inf, -np.inf]
+    bad[1, [0, 70]] = [-np.inf, np.nan]
+    for relative in (False, True):
+        got = _refit(eng, mean, var, actions, bad, 0.5, relative)
+        assert all(np.isfinite(g).all() for g in got)
+        ref = _reference(mean, var, actions, bad, 0.5, relative, alpha=float(np.float32(eng.cfg.alpha)))
+        _check_against_float64(got[0], got[1], None, ref, "H=%d non-finite %s" % (H, "relative" if relative else "absolute"))
+    low = np.where(np.isfinite(bad), bad, np.float32(-1e6))           # exp(-1e6 / 0.5) = 0: the same weights, absolute form
+    np.testing.assert_array_equal(_refit(eng, mean, var, actions, bad, 0.5, False)[0], _refit(eng, mean, var, actions, low, 0.5, False)[0])
+    dead = cand.copy()
+    dead[1] = np.nan
+    gm, gv, gp = _refit(eng, mean, var, actions, dead, 0.5, False)
+    np.testing.assert_array_equal(gm[1].view(np.uint32), mean[1].view(np.uint32))
+    np.testing.assert_array_equal(gv[1].view(np.uint32), var[1].view(np.uint32))
+    np.testing.assert_array_equal(gp[1], np.clip(mean[1], -1.0, 1.0))
+    alone = _refit(eng, mean[:1], var[:1], actions[:1], cand[:1], 0.5, False)
+    for g, a in zip((gm, gv, gp), alone):
+        np.testing.assert_array_equal(g[0], a[0])
+
+
+@pytest.mark.parametrize("H,n", [(5, 130), (6, 1030)])
+def test_deterministic_and_independent_per_env(gpu, H, n):
+    """Two runs: the same bits.  m = 2 in one call and as two m = 1 calls: the same bits per env.  16-byte loads and scalar loads
+    (the same buffer moved one float off its alignment): the same bits."""
+    prob, eng = _engine(H)
+    mean, var, actions, cand = _refit_data(H, n, 30 + H)
+    for relative in (False, True):
+        a = _refit(eng, mean, var, actions, cand, 0.3, relative)
+        b = _refit(eng, mean, var, actions, cand, 0.3, relative)
+        for x, y in zip(a, b):
+            np.testing.assert_array_equal(x, y)
+        for mi in range(M):
+            one = _refit(eng, mean[mi:mi + 1], var[mi:mi + 1], actions[mi:mi + 1], cand[mi:mi + 1], 0.3, relative)
+            for x, y in zip(a, one):
+                np.testing.assert_array_equal(x[mi], y[0], err_msg="env %d" % mi)
+        flat = torch.empty(actions.size + 1, dtype=torch.float32, device=eng.device)
+        off = flat[1:].view(actions.shape)
+        off.copy_(eng._t(actions))
+        assert off.data_ptr() % 16 == 4
+        tm, tv = eng._t(mean).clone(), eng._t(var).clone()
+        eng.mppi_refit(eng._t(cand), off, tm, tv, temperature=0.3, relative=relative)
+        np.testing.assert_array_equal(_np(tm), a[0])
+        np.testing.assert_array_equal(_np(tv), a[1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------- 3
+LOOP = [      # H, context, beta, decay, K, return_best, add_mean_last, n, relative, temperature, want the best return
+    (5, False, 0.0, 1.0, 0, False, False, 64, False, 0.5, False),      # nobody reads the elites: the selection is skipped
+    (6, True, 1.0, 1.5, 3, True, False, 64, True, 0.1, True),
+    (5, True, 1.0, 1.0, 3, False, True, 130, False, 0.5, True),
+    (6, False, 0.0, 1.5, 0, False, False, 1030, True, 0.1, True),      # n > 256: the elite selection's radix path
+    (6, True, 0.0, 1.5, 3, False, False, 1030, False, 0.5, False),
+]
+
+
+@pytest.mark.parametrize("H,context,beta,decay,keep,best,addmean,n,relative,lam,want_ret", LOOP,
+                         ids=["H%d-%s-beta%g-decay%g-K%d-%s%s-n%d-%s" % (r[0], "cadm" if r[1] else "vanilla", r[2], r[3], r[4], "best" if r[5] else "mean",
+                                                                        "-addmean" if r[6] else "", r[7], "relative" if r[8] else "absolute") for r in LOOP])
+def test_fused_equals_stepwise(gpu, H, context, beta, decay, keep, best, addmean, n, relative, lam, want_ret):
+    """`cadm_mppi_plan` with device RNG == the same loop one launch at a time over the engine's primitives (sample / sample_colored,
+    icem_inject, rollout, particle mean, mppi_refit, icem_track_best, icem_keep), bit for bit: the plan, the best return and the carried
+    elites of two consecutive calls.  Every stepwise refit is held to the float64 reference on the device's own returns and actions.
+    Measured on an MI355X, worst over the 30 refits of the 5 cases: mean 1.6e-07 absolute; var 2.1e-07 of its largest element."""
+    prob, eng = _engine(H, context)
+    prm = HipEngine.mppi_params(temperature=lam, relative=relative, noise_beta=beta, keep_elites=keep, decay=decay, return_best=best,
+                                add_mean_last=addmean)
+    args = (prob["obs"], prob["cp_obs"], prob["cp_act"])
+
+    def zero_carry():
+        if keep == 0:
+            return None, None
+        return (torch.zeros((M, keep, H, A), dtype=torch.float32, device=eng.device), torch.zeros((M,), dtype=torch.int32, device=eng.device))
+    (ca, va), (cb, vb) = zero_carry(), zero_carry()
+    mean, var = prob["init_mean"], prob["init_var"]
+    alpha = float(np.float32(eng.cfg.alpha))
+    for call in (1, 2):
+        a = eng.mppi_plan(prm, *args, mean, var, n, carry=ca, carry_valid=va, seed=4, call=call, want_best_return=want_ret)
+        a, ra = a if want_ret else (a, None)
+        b, info, extra = hplanner.icem_plan(eng, *args, mean, var, n, noise_beta=beta, keep_elites=keep, decay=decay, return_best=best,
+                                            add_mean_last=addmean, carry=cb, carry_valid=vb, seed=4, call=call, return_info=True,
+                                            update="mppi", temperature=lam, relative=relative)
+        a = _np(a)
+        assert a.shape == (M, H, A) and np.isfinite(a).all() and 0 < np.abs(a).max() <= 1.0
+        np.testing.assert_array_equal(a, _np(b), err_msg="plan of call %d" % call)
+        if want_ret:
+            np.testing.assert_array_equal(_np(ra), _np(extra["best_ret"]))
+        if keep:
+            np.testing.assert_array_equal(_np(ca), _np(cb), err_msg="carry after call %d" % call)
+            np.testing.assert_array_equal(_np(va), [1, 1])
+        pm, pv = np.asarray(mean, np.float64), np.asarray(var, np.float64)
+        assert [x["actions"].shape[1] for x in info] == [eng.icem_candidates(n, decay, it, keep) for it in range(ITERS)]
+        for it, x in enumerate(info):
+            cand = _np(x["cand"])
+            assert np.isfinite(cand).all()
+            ref = _reference(pm.astype(np.float32), pv.astype(np.float32), _np(x["actions"]), cand, float(np.float32(lam)), relative, alpha=alpha)
+            _check_against_float64(_np(x["mean"]), _np(x["var"]), None, ref, "call %d iteration %d" % (call, it))
+            np.testing.assert_array_equal(_np(x["elites"]), mppi_ref.top_elites(cand, KE))
+            pm, pv = _np(x["mean"]).astype(np.float64), _np(x["var"]).astype(np.float64)
+        if not best:
+            np.testing.assert_array_equal(a, np.clip(_np(info[-1]["mean"]), -1.0, 1.0))
+        mean = np.concatenate([a[:, 1:], np.zeros((M, 1, A), np.float32)], axis=1)      # the samplers' warm start
+    if keep and not best:      # the carry is consumed: the same call without it refits another mean
+        cc, vc = zero_carry()
+        c = _np(eng.mppi_plan(prm, *args, mean, var, n, carry=cc, carry_valid=vc, seed=4, call=3))
+        d = _np(eng.mppi_plan(prm, *args, mean, var, n, carry=ca.clone(), carry_valid=va.clone(), seed=4, call=3))
+        assert not np.array_equal(c, d)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- 4
+def _model(context, H, **kw):
+    from cadm_amd.dynamics.mlp_cadm_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as CaDMModel
+    from cadm_amd.dynamics.mlp_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as VanillaModel
+    from cadm_amd.envs import make_env_spec
+    env = kw.pop("env", None) or make_env_spec("halfcheetah")
+    base = dict(name="dyn", env=env, hidden_sizes=HID, hidden_nonlinearity="swish", n_forwards=H, n_candidates=N, ensemble_size=5,
+                n_particles=5, use_cem=True, normalize_input=True, seed=7)
+    base.update(kw)
+    prob = synth.make_problem(env="halfcheetah", context=context, E=5, m=M, H=H, seed=9, hidden_sizes=HID, trained_like=True)
+    st = prob["stats"]
+    if context:
+        model = CaDMModel(**base)
+        model.engine.set_net("context_model", prob["cp"])
+    else:
+        model = VanillaModel(**base)
+    model.engine.set_net("ff_model", prob["ff"])
+    nz = {"obs": (st["obs_mean"], st["obs_std"]), "delta": (st["delta_mean"], st["delta_std"]), "act": (st["act_mean"], st["act_std"])}
+    if context:
+        nz.update({"cp_obs": (st["cp_obs_mean"], st["cp_obs_std"]), "cp_act": (st["cp_act_mean"], st["cp_act_std"]),
+                   "back_delta": (st["back_delta_mean"], st["back_delta_std"])})
+    model.set_normalization(nz)
+    return model, prob
+
+
+def _act(model, prob, context, mean, var):
+    if context:
+        return model.get_action(prob["obs"], prob["cp_obs"], prob["cp_act"], mean, var)
+    return model.get_action(prob["obs"], mean, var)
+
+
+@pytest.mark.parametrize("context", [False, True], ids=["vanilla", "cadm"])
+def test_default_kwargs_take_the_untouched_route(gpu, context):
+    """A model built without the new kwargs and one with them spelled out at their defaults: bit-identical get_action results over
+    three calls, equal to the engine's one-call CEM planner on the same (seed, call); neither holds any iCEM / MPPI state."""
+    H = 5
+    a, prob = _model(context, H)
+    b, _ = _model(context, H, cem_update="cem", cem_temperature=1.0, cem_temperature_relative=False)
+    assert a._icem is None and b._icem is None and a._icem_update == b._icem_update == "cem"
+    mean, var = np.zeros((M, H, A)), np.full((M, H, A), 0.25)
+    for _ in range(3):
+        pa, pb = _act(a, prob, context, mean, var), _act(b, prob, context, mean, var)
+        assert np.isfinite(pa).all()
+        np.testing.assert_array_equal(pa, pb)
+        ref = _np(a.engine.cem_plan(prob["obs"], prob["cp_obs"] if context else None, prob["cp_act"] if context else None, mean, var, N,
+                                    seed=a.seed, call=a._call))
+        np.testing.assert_array_equal(pa, ref)
+        mean = np.concatenate([pa[:, 1:], np.zeros((M, 1, A))], axis=1)
+    assert a._plan_carry is None and b._plan_carry is None
+    a.reset_plan_carry()
+
+
+@pytest.mark.parametrize("context", [False, True], ids=["vanilla", "cadm"])
+def test_get_action_with_the_mppi_update(gpu, context):
+    """cem_update="mppi" alone takes the opt-in route: the plan is [m,H,A] inside the bounds, equals the stepwise MPPI loop on the
+    model's engine bit for bit, and differs from the CEM plan of the same (seed, call).  With cem_keep_elites the model carries elites:
+    the second call equals the stepwise loop started from that carry and differs from the same call without one; reset_plan_carry
+    makes the next plan a fresh model's."""
+    H = 6
+    model, prob = _model(context, H, cem_update="mppi")
+    assert model._icem is not None and model._icem_update == "mppi" and model._plan_carry is None
+    eng = model.engine
+    cp = (prob["cp_obs"], prob["cp_act"]) if context else (None, None)
+    mean, var = np.zeros((M, H, A)), np.full((M, H, A), 0.25)
+    p1 = _act(model, prob, context, mean, var)
+    assert p1.shape == (M, H, A) and np.isfinite(p1).all() and 0 < np.abs(p1).max() <= 1.0
+    q1 = hplanner.icem_plan(eng, prob["obs"], cp[0], cp[1], mean, var, N, seed=model.seed, call=1, update="mppi")
+    np.testing.assert_array_equal(p1, _np(q1))
+    cem = _np(eng.cem_plan(prob["obs"], cp[0], cp[1], mean, var, N, seed=model.seed, call=1))
+    assert np.abs(p1 - cem).max() > 1e-3
+    # elites carried across calls
+    kw = dict(cem_update="mppi", cem_temperature=0.2, cem_temperature_relative=True, cem_keep_elites=K, cem_noise_beta=1.0)
+    model, _ = _model(context, H, **kw)
+    eng = model.engine
+    p1 = _act(model, prob, context, mean, var)
+    carry1 = model._plan_carry.clone()
+    np.testing.assert_array_equal(_np(model._plan_carry_valid), [1, 1])
+    assert tuple(carry1.shape) == (M, K, H, A) and np.abs(_np(carry1)).max() > 0
+    mean2 = np.concatenate([p1[:, 1:], np.zeros((M, 1, A))], axis=1)
+    p2 = _act(model, prob, context, mean2, var)
+    step = dict(noise_beta=1.0, keep_elites=K, seed=model.seed, call=2, update="mppi", temperature=0.2, relative=True)
+    c2, v2 = carry1.clone(), torch.ones((M,), dtype=torch.int32, device=eng.device)
+    q2, info, _ = hplanner.icem_plan(eng, prob["obs"], cp[0], cp[1], mean2, var, N, carry=c2, carry_valid=v2, return_info=True, **step)
+    np.testing.assert_array_equal(_np(info[0]["actions"])[:, :K, :H - 1], _np(carry1)[:, :, 1:])
+    np.testing.assert_array_equal(p2, _np(q2))
+    np.testing.assert_array_equal(_np(model._plan_carry), _np(c2))
+    c0, v0 = torch.zeros_like(carry1), torch.zeros((M,), dtype=torch.int32, device=eng.device)
+    q0 = hplanner.icem_plan(eng, prob["obs"], cp[0], cp[1], mean2, var, N, carry=c0, carry_valid=v0, **step)
+    assert not np.array_equal(p2, _np(q0))
+    fresh, _ = _model(context, H, **kw)
+    fresh._call = model._call
+    model.reset_plan_carry()
+    np.testing.assert_array_equal(_np(model._plan_carry_valid), [0, 0])
+    np.testing.assert_array_equal(_act(model, prob, context, mean2, var), _act(fresh, prob, context, mean2, var))
+    model.reset_plan_carry(np.array([False, True]))
+    np.testing.assert_array_equal(_np(model._plan_carry_valid), [1, 0])
+
+
+def test_device_planner_state_takes_the_mppi_route(gpu):
+    from cadm_amd.caller import DevicePlannerState
+    H = 5
+    model, prob = _model(True, H, cem_update="mppi", cem_keep_elites=K)
+    state = DevicePlannerState(model, M)
+    a = state.act(prob["obs"])
+    assert tuple(a.shape) == (M, A) and np.isfinite(_np(a)).all() and np.abs(_np(a)).max() <= 1.0
+    np.testing.assert_array_equal(_np(model._plan_carry_valid), [1, 1])
+    zero = torch.zeros((M, H, A), dtype=torch.float32, device=model.engine.device)
+    want = model.engine.mppi_plan(model._icem_params, prob["obs"], torch.zeros_like(state.hist_obs), torch.zeros_like(state.hist_act), zero, state.init_var,
+                                  N, carry=torch.zeros_like(model._plan_carry), carry_valid=torch.zeros((M,), dtype=torch.int32, device=zero.device),
+                                  seed=model.seed, call=1)
+    np.testing.assert_array_equal(_np(a), _np(want)[:, 0])
+    state.observe(prob["obs"], a, prob["obs"], done=np.array([1, 0]))
+    np.testing.assert_array_equal(_np(model._plan_carry_valid), [0, 1])
+
+
+def test_refusals_at_construction(gpu, monkeypatch):
+    from cadm_amd.envs import make_env_spec
+    for bad, msg in ((dict(cem_update="softmax"), "cem_update must be"), (dict(cem_update="mppi", cem_temperature=0.0), "cem_temperature"),
+                     (dict(cem_update="mppi", cem_temperature=-1.0), "cem_temperature"), (dict(cem_update="mppi", cem_temperature=float("nan")), "cem_temperature"),
+                     (dict(cem_update="mppi", cem_temperature=float("inf")), "cem_temperature"), (dict(cem_temperature=0.5), "need cem_update='mppi'"),
+                     (dict(cem_temperature_relative=True), "need cem_update='mppi'"), (dict(cem_keep_elites=2, cem_temperature=2.0), "need cem_update='mppi'"),
+                     (dict(use_cem=False, cem_update="mppi"), "need use_cem=True"), (dict(use_cem=False, cem_temperature=0.5), "need use_cem=True"),
+                     (dict(cem_update="mppi", cem_keep_elites=51), "exceeds the planner's 50 elites")):
+        for context in (False, True):
+            with pytest.raises(ValueError, match=msg):
+                _model(context, 5, **bad)
+    with pytest.raises(NotImplementedError, match="continuous actions only"):
+        _model(True, 5, env=make_env_spec("cartpole"), cem_update="mppi")
+    import torch.distributed as dist
+    monkeypatch.setattr(dist, "get_world_size", lambda group=None: 2)
+    with pytest.raises(NotImplementedError, match="more than one rank"):
+        _model(True, 5, process_group=object(), cem_update="mppi")
+
+
+def test_argument_checks_return_einval(gpu):
+    """The new exports refuse bad arguments with CADM_EINVAL and a message naming themselves; the checks run before any HIP call, so
+    the stream and the null pointers next to the bad argument are never touched; the engine plans normally afterwards."""
+    prob, eng = _engine(5, True)
+    lib, ctx = eng.lib, eng._ctx
+    buf = torch.zeros(8192, dtype=torch.float32, device=eng.device)
+    ibuf = torch.zeros(64, dtype=torch.int32, device=eng.device)
+    P, I = ct.c_void_p(buf.data_ptr()), ct.c_void_p(ibuf.data_ptr())
+
+    def einval(rc, name, frag):
+        msg = lib.cadm_last_error().decode()
+        assert rc == -1, "%s: expected CADM_EINVAL, got %d (%s)" % (name, rc, msg)
+        assert msg.startswith(name + ":") and frag in msg, msg
+
+    def refit(c=ctx, lam=1.0, cand=P, m=M, n=N):
+        return lib.cadm_mppi_refit(c, cand, None if cand is None else P, m, n, lam, 0, None if cand is None else P, None if cand is None else P, None, None)
+
+    def plan(prm, c=ctx, n=N, carry=P, valid=I, cp=P):
+        return lib.cadm_mppi_plan(c, ct.byref(prm), P, cp, cp, P, P, carry, valid, M, n, 0, 1, P, P, None, None)
+    for lam in (0.0, -1.0, float("nan"), float("inf")):
+        einval(lib.cadm_mppi_refit(ctx, P, None, M, N, lam, 0, None, None, None, None), "cadm_mppi_refit", "bad arguments")
+        einval(lib.cadm_mppi_refit(ctx, P, P, M, N, lam, 0, P, P, None, None), "cadm_mppi_refit", "temperature")
+        einval(plan(HipEngine.mppi_params(temperature=lam)), "cadm_mppi_plan", "temperature")
+    einval(refit(cand=None), "cadm_mppi_refit", "bad arguments")
+    einval(refit(m=0), "cadm_mppi_refit", "bad arguments")
+    einval(refit(n=0), "cadm_mppi_refit", "bad arguments")
+    einval(plan(HipEngine.mppi_params(keep_elites=KE + 1)), "cadm_mppi_plan", "keep_elites")
+    einval(plan(HipEngine.mppi_params(decay=0.9)), "cadm_mppi_plan", "decay")
+    einval(plan(HipEngine.mppi_params(noise_beta=-1.0)), "cadm_mppi_plan", "noise_beta")
+    einval(plan(HipEngine.mppi_params(keep_elites=K), carry=None), "cadm_mppi_plan", "carry")
+    einval(plan(HipEngine.mppi_params(), n=KE - 1), "cadm_mppi_plan", "num_elites")
+    einval(plan(HipEngine.mppi_params(), cp=None), "cadm_mppi_plan", "cp_obs/cp_act")
+    einval(lib.cadm_mppi_plan(ctx, None, P, P, P, P, P, P, I, M, N, 0, 1, P, P, None, None), "cadm_mppi_plan", "bad arguments")
+    assert lib.cadm_mppi_workspace_bytes(ctx, 0, N, K) == 0 and lib.cadm_mppi_workspace_bytes(ctx, M, N, -1) == 0
+    assert lib.cadm_mppi_workspace_bytes(ctx, M, N, K) > lib.cadm_icem_workspace_bytes(ctx, M, N, K) > 0
+    # discrete actions
+    dprob, deng = _engine(5, True, env="cartpole")
+    einval(plan(HipEngine.mppi_params(), c=deng._ctx), "cadm_mppi_plan", "continuous actions only")
+    einval(refit(c=deng._ctx), "cadm_mppi_refit", "continuous actions only")
+    # a candidate-sharded ctx (a host-supplied all-gather registered for two ranks; it is never called)
+    sprob = synth.make_problem(env="halfcheetah", context=True, E=5, m=M, H=5, seed=3, hidden_sizes=HID, trained_like=True)
+    seng = make_engine(sprob, p=5, num_elites=KE, num_cem_iters=ITERS)
+    fn = _lib.ALLGATHER_FN(lambda *a: 1)
+    assert lib.cadm_dist_init_external(seng._ctx, 2, 0, ct.cast(fn, ct.c_void_p), None) == 0
+    einval(plan(HipEngine.mppi_params(), c=seng._ctx), "cadm_mppi_plan", "sharded")
+    einval(refit(c=seng._ctx), "cadm_mppi_refit", "sharded")
+    assert lib.cadm_dist_destroy(seng._ctx) == 0
+    # the engine is usable afterwards
+    out = _np(eng.mppi_plan(HipEngine.mppi_params(temperature=0.5, noise_beta=1.0), prob["obs"], prob["cp_obs"], prob["cp_act"], prob["init_mean"],
+                            prob["init_var"], N, seed=1, call=1))
+    assert np.isfinite(out).all() and np.abs(out).max() <= 1.0
