@@ -154,26 +154,65 @@ __global__ void icem_inject_kernel(const float* __restrict__ kept, const int32_t
     }
 }
 
-// the iteration's top candidate (elites[mi, 0]) against the best of this call so far: replaced where its return is STRICTLY greater
-// (a tie, -0.0 against +0.0 included, keeps the earlier sequence; a NaN return never replaces).  One workgroup per env; every thread
-// reads the stored return before any thread writes it.
-__global__ void icem_track_best_kernel(const float* __restrict__ cand, const int32_t* __restrict__ elites, const float* __restrict__ actions,
-                                       int n, int KE, int HA, float* __restrict__ best_ret, float* __restrict__ best_seq) {
-    const int mi = blockIdx.x;
-    const int32_t c = elites[(size_t)mi * KE];
+// The iteration's best candidate against the best of this call so far.  Non-finite returns: the iteration's best is the candidate
+// with the GREATEST NON-NaN return (+inf and -inf are returns like any other), ties -- -0.0 against +0.0 included -- to the lower
+// index.  make_key (common.h) ranks a positive NaN above +inf, so an iteration's NaN returns come FIRST among its elites: the kernel
+// walks elites[mi, 0 .. KE) (the refit's order) to the first whose return is not NaN, and when all KE are NaN takes the arg-max over
+// the env's candidates itself.  An elite id outside [0, n) ends the walk: that env is left as it is.  The stored best is replaced
+// where it holds nothing yet (best_ret NaN: icem_best_init_kernel) or the new return is STRICTLY greater (a tie keeps the earlier
+// sequence): over a call the plan is the sequence with the greatest non-NaN return, ties to the earliest iteration, then to the
+// lowest index, and NaN only if every return of the call is NaN.  One workgroup of TB_THREADS per env; every thread reads the
+// stored return before any thread writes it.
+constexpr int TB_THREADS = 256;
+
+__global__ __launch_bounds__(TB_THREADS) void icem_track_best_kernel(const float* __restrict__ cand, const int32_t* __restrict__ elites,
+                                                                     const float* __restrict__ actions, int n, int KE, int HA,
+                                                                     float* __restrict__ best_ret, float* __restrict__ best_seq) {
+    __shared__ float sv[TB_THREADS];
+    __shared__ int si[TB_THREADS];
+    const int mi = blockIdx.x, tid = threadIdx.x;
+    const float* r_m = cand + (size_t)mi * n;
     const float old = best_ret[mi];
-    const float r = (uint32_t)c < (uint32_t)n ? cand[(size_t)mi * n + c] : old;
+    int c = -1, j = 0;
+    float r = 0.0f;
+    for (; j < KE; ++j) {                                // (the same walk in every thread: what follows is uniform over the workgroup)
+        const int32_t cj = elites[(size_t)mi * KE + j];
+        if ((uint32_t)cj >= (uint32_t)n) break;
+        const float rj = r_m[cj];
+        if (rj == rj) { c = cj; r = rj; break; }
+    }
+    if (j == KE) {                                       // every elite's return is NaN
+        int bi = -1;
+        float bv = 0.0f;
+        for (int i = tid; i < n; i += TB_THREADS) {      // (ascending i: a strict > keeps the lower index)
+            const float v = r_m[i];
+            if (v == v && (bi < 0 || v > bv)) { bv = v; bi = i; }
+        }
+        sv[tid] = bv;
+        si[tid] = bi;
+        __syncthreads();
+        for (int d = TB_THREADS / 2; d > 0; d >>= 1) {
+            if (tid < d) {
+                const int oi = si[tid + d];
+                const float ov = sv[tid + d];
+                if (oi >= 0 && (si[tid] < 0 || ov > sv[tid] || (ov == sv[tid] && oi < si[tid]))) { sv[tid] = ov; si[tid] = oi; }
+            }
+            __syncthreads();
+        }
+        c = si[0];
+        r = sv[0];
+    }
     __syncthreads();
-    if (!(r > old)) return;
-    for (int e = threadIdx.x; e < HA; e += blockDim.x) best_seq[(size_t)mi * HA + e] = actions[((size_t)mi * n + c) * HA + e];
-    if (threadIdx.x == 0) best_ret[mi] = r;
+    if (c < 0 || r <= old) return;                       // (old NaN: nothing stored yet, r <= old is false)
+    for (int e = tid; e < HA; e += TB_THREADS) best_seq[(size_t)mi * HA + e] = actions[((size_t)mi * n + c) * HA + e];
+    if (tid == 0) best_ret[mi] = r;
 }
 
 __global__ void icem_best_init_kernel(int m, int HA, float* __restrict__ best_ret, float* __restrict__ best_seq) {
     const size_t total = (size_t)m * HA;
     for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
-        best_seq[q] = __uint_as_float(0x7fc00000u);      // (a call whose returns are all NaN plans NaN, as the mean would)
-        if (q < (size_t)m) best_ret[q] = -INFINITY;
+        best_seq[q] = __uint_as_float(0x7fc00000u);      // (a call whose returns are ALL NaN plans NaN, as the mean would,
+        if (q < (size_t)m) best_ret[q] = __uint_as_float(0x7fc00000u);      //  and reports a NaN best return: nothing was scored)
     }
 }
 
@@ -200,7 +239,7 @@ static int launch_inject(cadm_ctx* ctx, const float* kept, const int32_t* valid,
 
 static int launch_track_best(cadm_ctx* ctx, const float* cand, const int32_t* elites, const float* actions, int m, int n, float* best_ret,
                              float* best_seq, hipStream_t s) {
-    hipLaunchKernelGGL(icem_track_best_kernel, dim3(m), dim3(256), 0, s, cand, elites, actions, n, ctx->cfg.num_elites, ctx->H * ctx->A,
+    hipLaunchKernelGGL(icem_track_best_kernel, dim3(m), dim3(TB_THREADS), 0, s, cand, elites, actions, n, ctx->cfg.num_elites, ctx->H * ctx->A,
                        best_ret, best_seq);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;

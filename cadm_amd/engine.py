@@ -531,7 +531,8 @@ class HipEngine:
         return actions
 
     def icem_track_best(self, cand, elites, actions, best_ret, best_seq):
-        """best_ret [m] / best_seq [m,H,A] updated IN PLACE where this iteration's top candidate is strictly better."""
+        """best_ret [m] / best_seq [m,H,A] updated IN PLACE where this iteration's best candidate -- the greatest non-NaN return: the
+        first elite whose return is not NaN, the arg-max over cand when all are NaN -- is strictly better, or best_ret is NaN."""
         m, n = actions.shape[0], actions.shape[1]
         self._check(self.lib.cadm_icem_track_best(self._ctx, ptr(cand), ptr(elites), ptr(actions), m, n, ptr(best_ret), ptr(best_seq),
                                                   self.stream), "cadm_icem_track_best")

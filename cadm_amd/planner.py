@@ -153,7 +153,7 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     m, K, iters = obs.shape[0], int(keep_elites), engine.num_cem_iters
     lo, hi = float(engine.cfg.lower_bound), float(engine.cfg.upper_bound)
     ctx_vec = engine.context_forward(cp_obs, cp_act) if engine.C > 0 else None
-    best_ret = torch.full((m,), float("-inf"), dtype=torch.float32, device=engine.device)
+    best_ret = torch.full((m,), float("nan"), dtype=torch.float32, device=engine.device)      # NaN: nothing scored yet (icem_best_init_kernel)
     best_seq = torch.full((m, engine.H, engine.A), float("nan"), dtype=torch.float32, device=engine.device)
     kept, info = None, []
     for it in range(iters):

@@ -299,8 +299,14 @@ int cadm_icem_keep(cadm_ctx* ctx, const float* actions, const int32_t* elites, i
  * steps [1,H) and step H-1 keeps its value; valid [m] int32 (or NULL = all): envs with valid[mi] == 0 are left untouched */
 int cadm_icem_inject(cadm_ctx* ctx, const float* kept, const int32_t* valid, int m, int n, int K, int shift, float* actions_io,
                      void* stream);
-/* per env: where cand_returns[mi, elites[mi,0]] is STRICTLY greater than best_ret_io[mi] (a tie, -0.0 against +0.0 included, and
- * a NaN are not), that return and that candidate's sequence replace best_ret_io [m] / best_seq_io [m,H,A] */
+/* per env: the iteration's best candidate is the one with the greatest NON-NaN return (+inf and -inf count), ties (-0.0 against
+ * +0.0 included) to the lower index: the first of elites[mi, 0 .. num_elites) whose return is not NaN (cadm_cem_refit's elites_out
+ * ranks a NaN return above +inf, so NaN returns come first), or, when all of them are NaN, the arg-max over cand_returns[mi, :].
+ * An elite id outside [0, n) ends the walk and leaves the env as it is.  Where best_ret_io[mi] is NaN (nothing stored yet) or that
+ * return is STRICTLY greater than it (a tie is not), the return and the candidate's sequence replace best_ret_io [m] /
+ * best_seq_io [m,H,A].  Over a cadm_icem_plan call: the plan under return_best is the sequence with the greatest non-NaN return
+ * scored in the call, ties to the earliest iteration, then the lowest index; it (and best_return_out) is NaN only if every return
+ * of the call is NaN. */
 int cadm_icem_track_best(cadm_ctx* ctx, const float* cand_returns, const int32_t* elites, const float* actions, int m, int n,
                          float* best_ret_io, float* best_seq_io, void* stream);
 /* The loop: context encoder once, then per iteration `it` with n_it candidates: sample (white or coloured), write the kept sequences

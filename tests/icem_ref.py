@@ -79,6 +79,50 @@ def n_candidates(n, decay, it, num_elites, K):
     return min(n, max(v, 2 * num_elites, K + 1))
 
 
+def key_order(cand, k=None):
+    """cand [n] -> candidate ids in the order of cadm_cem_refit's `elites_out` (csrc/common.h make_key): return descending by the
+    float's bit pattern, so a POSITIVE NaN ranks above +inf (a negative NaN below -inf); -0.0 ties with +0.0; ties to the lower index."""
+    u = np.asarray(cand, np.float32).view(np.uint32).astype(np.int64)
+    u = np.where((u & 0x7FFFFFFF) == 0, 0, u)
+    asc = np.where(u & 0x80000000, (~u) & 0xFFFFFFFF, u | 0x80000000)
+    order = np.argsort(-asc, kind="stable")
+    return order if k is None else order[:k]
+
+
+def best_candidate(cand):
+    """cand [n] -> the id of the greatest non-NaN return (+inf / -inf count; ties, -0.0 against +0.0 included, to the lower index),
+    or -1 when every return is NaN: the rule of icem_track_best_kernel."""
+    ok = ~np.isnan(cand)
+    if not ok.any():
+        return -1
+    return int(np.flatnonzero(ok & (cand == cand[ok].max()))[0])
+
+
+def track_best(cand, actions, best_ret, best_seq):
+    """best_ret [m] (NaN: nothing yet) / best_seq [m,H,A] updated IN PLACE with the iteration's best candidate where nothing is
+    stored yet or its return is strictly greater."""
+    for mi in range(cand.shape[0]):
+        c = best_candidate(cand[mi])
+        if c >= 0 and not cand[mi, c] <= best_ret[mi]:
+            best_ret[mi], best_seq[mi] = cand[mi, c], actions[mi, c]
+
+
+# decay = 1.1 is not a float32 number: the library receives float32(1.1) = 1.10000002384 and floor(66 / that) = 59, where float64 1.1
+# gives floor(66 / 1.1) = 60 (tests/test_icem_ref.py checks that the two disagree at this n)
+DECAY_11_N = 77
+
+
+def colored_actions_f32(mean, var, xi, beta, lower=-1.0, upper=1.0):
+    """`colored_actions` evaluated in float32 throughout (tables, products and sums rounded to float32; numpy's summation order):
+    how far a float32 evaluation of the synthesis lies from the float64 one."""
+    f = np.float32
+    mean, var, xi = np.asarray(mean, f), np.asarray(var, f), np.asarray(xi, f)
+    z = np.transpose(xi @ synthesis_matrix(xi.shape[-1], beta).astype(f).T, (0, 1, 3, 2))
+    a1, a2 = (mean - f(lower)) / f(2), (f(upper) - mean) / f(2)
+    sd = np.sqrt(np.minimum(np.minimum(a1 * a1, a2 * a2), var))
+    return np.clip(mean[:, None] + sd[:, None] * z, f(lower), f(upper))
+
+
 def icem_loop(o, E, p, n, iters, num_elites, noise_beta=0.0, K=0, decay=1.0, return_best=False, add_mean_last=False, z=None, xi=None,
               carry=None, carry_valid=None, alpha=0.1, lower=-1.0, upper=1.0, deterministic=True):
     """The loop of section 2 of the issue over the oracle's rollout (deterministic model) and top-k.  o: helpers.oracle_problem(...)
@@ -88,7 +132,7 @@ def icem_loop(o, E, p, n, iters, num_elites, noise_beta=0.0, K=0, decay=1.0, ret
     m, H, A = mean.shape
     D = o["obs"].shape[1]
     ctx = None if o["cp"] is None else onets.context_forward(o["cp"], o["cp_obs"], o["cp_act"], o["st"])
-    best_ret, best_seq = np.full(m, -np.inf, dt), np.full((m, H, A), np.nan, dt)
+    best_ret, best_seq = np.full(m, np.nan, dt), np.full((m, H, A), np.nan, dt)
     kept, info = None, []
     for it in range(iters):
         last = it + 1 == iters
@@ -110,13 +154,10 @@ def icem_loop(o, E, p, n, iters, num_elites, noise_beta=0.0, K=0, decay=1.0, ret
         rets = oplanner.rollout_indexed(o["env"], o["ff"], o["st"], o["obs"], T, actions, np.zeros((H, m, ni, p, D), dt), E, p, deterministic)
         cand = oplanner.particle_mean(rets)
         mean, var, idx = oplanner.elite_refit(mean, var, actions, cand, num_elites, dt(alpha))
-        top = cand[np.arange(m), idx[:, 0]]
-        for mi in range(m):
-            if top[mi] > best_ret[mi]:
-                best_ret[mi], best_seq[mi] = top[mi], actions[mi, idx[mi, 0]]
+        track_best(cand, actions, best_ret, best_seq)
         if K > 0:
             kept = np.take_along_axis(actions, idx[:, :K, None, None], axis=1)
-        info.append(dict(actions=actions, cand=cand, elites=idx, kept=kept, mean=mean.copy(), var=var.copy()))
+        info.append(dict(actions=actions, cand=cand, elites=idx, kept=kept, mean=mean.copy(), var=var.copy(), best_ret=best_ret.copy()))
     if K > 0:
         carry, carry_valid = kept.copy(), np.ones(m, np.int32)
     plan = best_seq if return_best else np.clip(mean, dt(lower), dt(upper))
@@ -127,7 +168,9 @@ def icem_loop(o, E, p, n, iters, num_elites, noise_beta=0.0, K=0, decay=1.0, ret
 # the whole-loop cases shared by tests/test_icem_ref.py (CPU: the condition on the seeds) and tests/test_gpu_icem.py
 # ------------------------------------------------------------------------------------------------------------------------------
 LOOP = dict(E=5, p=5, m=2, n=64, num_elites=8, K=3, iters=3, hidden_sizes=(32,) * 4)
+# a case: (H, context, beta, decay) on halfcheetah with bounds (-1, 1), or (H, context, beta, decay, env, (lower, upper))
 LOOP_CASES = [(H, context, beta, decay) for H in (5, 6) for context in (False, True) for beta in (0.0, 1.0) for decay in (1.0, 1.5)]
+LOOP_CASES += [(5, False, 0.0, 1.5, "ant", (-1.0, 1.0)), (6, True, 1.0, 1.0, "halfcheetah", (-0.5, 2.0))]
 # problem / draw seed per case: the first at which the float32 and the float64 oracle pick the same elites, in the same order, in
 # every iteration, with every gap among the 9 best returns above LOOP_MIN_GAP of their scale (a result within the 1e-5 bar of
 # the float64 returns then ranks them the same way) -- tests/test_icem_ref.py checks that they still do
@@ -135,17 +178,29 @@ LOOP_SEEDS = {(5, False, 0.0, 1.0): 4, (5, False, 0.0, 1.5): 0, (5, False, 1.0, 
               (5, True, 0.0, 1.5): 3, (5, True, 1.0, 1.0): 21, (5, True, 1.0, 1.5): 10, (6, False, 0.0, 1.0): 5, (6, False, 0.0, 1.5): 2,
               (6, False, 1.0, 1.0): 25, (6, False, 1.0, 1.5): 4, (6, True, 0.0, 1.0): 19, (6, True, 0.0, 1.5): 16, (6, True, 1.0, 1.0): 0,
               (6, True, 1.0, 1.5): 0}
+LOOP_SEEDS.update({LOOP_CASES[-2]: 26, LOOP_CASES[-1]: 3})
 LOOP_MIN_GAP = 2e-4      # smallest gap between neighbouring returns among the 9 best, over the largest |return|: 20 x the 1e-5 bar
 
 
-def loop_case(H, context, beta, decay, seed=None):
+def case_env_bounds(case):
+    return (case[4], tuple(case[5])) if len(case) > 4 else ("halfcheetah", (-1.0, 1.0))
+
+
+def case_id(case):
+    env, (lo, hi) = case_env_bounds(case)
+    return "H%d-%s-beta%g-decay%g" % (case[0], "cadm" if case[1] else "vanilla", case[2], case[3]) + ("" if len(case) == 4 else "-%s-%g_%g" % (env, lo, hi))
+
+
+def loop_case(case, seed=None):
     """(problem, per-iteration z or None, per-iteration xi or None, carry [m,K,H,A] float32, carry_valid [m]) of one loop case: a warm
     start away from zero, env 1 carrying elites from an earlier call and env 0 not."""
     from cadm_amd import synth
     from helpers import trunc_z
     c = LOOP
-    seed = LOOP_SEEDS.get((H, context, beta, decay), 0) if seed is None else seed
-    prob = synth.make_problem(env="halfcheetah", context=context, E=c["E"], m=c["m"], H=H, seed=100 + seed, hidden_sizes=c["hidden_sizes"],
+    H, context, beta, decay = case[:4]
+    env, (lower, upper) = case_env_bounds(case)
+    seed = LOOP_SEEDS.get(case, 0) if seed is None else seed
+    prob = synth.make_problem(env=env, context=context, E=c["E"], m=c["m"], H=H, seed=100 + seed, hidden_sizes=c["hidden_sizes"],
                               trained_like=True)
     rng = np.random.default_rng(1000 + seed)
     A = prob["A"]
@@ -162,14 +217,15 @@ def loop_case(H, context, beta, decay, seed=None):
         xi = [rng.standard_normal((c["m"], ni, A, H)).astype(np.float32) for ni in ns]
     else:
         z = [trunc_z(rng, (c["m"], ni, H, A)).astype(np.float32) for ni in ns]
-    carry = rng.uniform(-1.0, 1.0, (c["m"], c["K"], H, A)).astype(np.float32)
+    carry = rng.uniform(lower, upper, (c["m"], c["K"], H, A)).astype(np.float32)      # (an earlier call's elites: inside the bounds)
     return prob, z, xi, carry, np.array([0, 1], np.int32)
 
 
-def loop_reference(H, context, beta, decay, dtype, seed=None):
+def loop_reference(case, dtype, seed=None, return_best=False):
     from helpers import oracle_problem
-    prob, z, xi, carry, valid = loop_case(H, context, beta, decay, seed)
+    prob, z, xi, carry, valid = loop_case(case, seed)
     c = LOOP
+    lower, upper = case_env_bounds(case)[1]
     o = oracle_problem(prob, dtype)
-    return icem_loop(o, c["E"], c["p"], c["n"], c["iters"], c["num_elites"], noise_beta=beta, K=c["K"], decay=decay, add_mean_last=True,
-                     z=z, xi=xi, carry=carry.astype(dtype), carry_valid=valid)
+    return icem_loop(o, c["E"], c["p"], c["n"], c["iters"], c["num_elites"], noise_beta=case[2], K=c["K"], decay=case[3], add_mean_last=True,
+                     return_best=return_best, z=z, xi=xi, carry=carry.astype(dtype), carry_valid=valid, lower=lower, upper=upper)

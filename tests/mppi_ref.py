@@ -56,7 +56,7 @@ def mppi_loop(o, E, p, n, iters, num_elites, temperature=1.0, relative=False, no
     m, H, A = mean.shape
     D = o["obs"].shape[1]
     ctx = None if o["cp"] is None else onets.context_forward(o["cp"], o["cp_obs"], o["cp_act"], o["st"])
-    best_ret, best_seq = np.full(m, -np.inf, dt), np.full((m, H, A), np.nan, dt)
+    best_ret, best_seq = np.full(m, np.nan, dt), np.full((m, H, A), np.nan, dt)
     kept, info = None, []
     for it in range(iters):
         last = it + 1 == iters
@@ -79,10 +79,7 @@ def mppi_loop(o, E, p, n, iters, num_elites, temperature=1.0, relative=False, no
         cand = oplanner.particle_mean(rets)
         idx = top_elites(cand, num_elites)
         mean, var, _ = mppi_update(mean, var, actions, cand, temperature, relative, alpha, lower, upper)
-        top = cand[np.arange(m), idx[:, 0]]
-        for mi in range(m):
-            if top[mi] > best_ret[mi]:
-                best_ret[mi], best_seq[mi] = top[mi], actions[mi, idx[mi, 0]]
+        icem_ref.track_best(cand, actions, best_ret, best_seq)
         if K > 0:
             kept = np.take_along_axis(actions, idx[:, :K, None, None], axis=1)
         info.append(dict(actions=actions, cand=cand, elites=idx, kept=kept, mean=mean.copy(), var=var.copy()))

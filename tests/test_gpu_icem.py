@@ -156,6 +156,7 @@ def test_keep_inject_track_best_exact(gpu, H):
     want[:, K] = one[:, 0]
     np.testing.assert_array_equal(got, want)
     # track-best: strictly greater replaces; a tie keeps the earlier sequence, -0.0 against +0.0 included; NaN never replaces
+    # (non-finite returns at length: tests/test_gpu_icem_envelope.py)
     cand = rng.standard_normal((M, n)).astype(np.float32)
     best_ret = eng._t(np.array([-np.inf, -np.inf], np.float32))
     best_seq = eng._t(np.full((M, H, A), np.nan, np.float32))
@@ -180,13 +181,27 @@ def test_keep_inject_track_best_exact(gpu, H):
     eng.icem_track_best(eng._t(cand3), eng._t(el2, dtype=torch.int32), ta, zr, zs)
     np.testing.assert_array_equal(_np(zs), first_seq)
     assert np.signbit(_np(zr)[0]) and not np.signbit(_np(zr)[1])
+    # a NaN return never replaces: where every return is NaN nothing changes ...
+    eng.icem_track_best(eng._t(np.full_like(cand3, np.nan)), eng._t(el2, dtype=torch.int32), ta, zr, zs)
+    np.testing.assert_array_equal(_np(zs), first_seq)
+    assert np.signbit(_np(zr)[0]) and not np.signbit(_np(zr)[1])
+    # ... and where the first elites' returns are NaN, the first elite whose return is not NaN stands for the iteration (the NaN
+    # returns rank first among the refit's elites; before, elite 0 alone was read and the iteration counted for nothing)
     cand3[:, el2[:, 0]] = np.nan
     eng.icem_track_best(eng._t(cand3), eng._t(el2, dtype=torch.int32), ta, zr, zs)
-    np.testing.assert_array_equal(_np(zs), first_seq)
+    want_seq, want_ret = first_seq.copy(), np.array([-0.0, 0.0], np.float32)
+    for mi in range(M):
+        c = next(int(c) for c in el2[mi] if not np.isnan(cand3[mi, c]))
+        assert c == el2[mi, 2]                                       # (elites 0 and 1 are the same, NaN, candidate)
+        if cand3[mi, c] > want_ret[mi]:
+            want_seq[mi], want_ret[mi] = acts[mi, c], cand3[mi, c]
+    np.testing.assert_array_equal(_np(zs), want_seq)
+    np.testing.assert_array_equal(_np(zr), want_ret)
+    assert not np.array_equal(want_seq, first_seq)                   # (at these seeds env 1's next elite beats the stored 0.0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 4
-@pytest.mark.parametrize("case", icem_ref.LOOP_CASES, ids=["H%d-%s-beta%g-decay%g" % (c[0], "cadm" if c[1] else "vanilla", c[2], c[3]) for c in icem_ref.LOOP_CASES])
+@pytest.mark.parametrize("case", icem_ref.LOOP_CASES, ids=[icem_ref.case_id(c) for c in icem_ref.LOOP_CASES])
 def test_whole_loop_stepwise_against_numpy(gpu, case):
     """The loop through the stepwise exports (cadm_amd.planner.icem_plan) against the numpy loop of tests/icem_ref.py in float64, on the
     deterministic model with injected draws (truncated-normal z for beta = 0, spectral xi for beta = 1), K = 3 with env 1 starting from
@@ -194,16 +209,17 @@ def test_whole_loop_stepwise_against_numpy(gpu, case):
     of max(|ref|, rms(ref))), elites identical and in order, kept sequences bit-equal to the candidates they came from; the final plan
     within 1e-5 absolute for cem_return 'mean' and 'best'.  Condition, checked on the CPU (tests/test_icem_ref.py): at these seeds the
     float32 and float64 oracles rank the elites the same way, with no two of the 9 best returns closer than 2e-4 of their scale."""
-    H, context, beta, decay = case
+    H, context, beta, decay = case[:4]
+    lower, upper = icem_ref.case_env_bounds(case)[1]      # (the two last cases: ant; bounds (-0.5, 2))
     c = icem_ref.LOOP
-    prob, z, xi, carry, valid = icem_ref.loop_case(*case)
-    eng = make_engine(prob, p=c["p"], deterministic=True, num_elites=c["num_elites"], num_cem_iters=c["iters"])
+    prob, z, xi, carry, valid = icem_ref.loop_case(case)
+    eng = make_engine(prob, p=c["p"], deterministic=True, num_elites=c["num_elites"], num_cem_iters=c["iters"], lower_bound=lower, upper_bound=upper)
     tcarry, tvalid = eng._t(carry), eng._t(valid, dtype=torch.int32)
     plan, info, best = hplanner.icem_plan(eng, prob["obs"], prob["cp_obs"], prob["cp_act"], prob["init_mean"], prob["init_var"], c["n"],
                                           noise_beta=beta, keep_elites=c["K"], decay=decay, add_mean_last=True, carry=tcarry, carry_valid=tvalid,
                                           z=None if z is None else [eng._t(x) for x in z], xi=None if xi is None else [eng._t(x) for x in xi],
                                           return_info=True)
-    rplan, rinfo, rcarry, rvalid = icem_ref.loop_reference(*case, np.float64)
+    rplan, rinfo, rcarry, rvalid = icem_ref.loop_reference(case, np.float64)
     assert len(info) == len(rinfo) == c["iters"]
     for it in range(c["iters"]):
         acts = _np(info[it]["actions"])
@@ -227,12 +243,7 @@ def test_whole_loop_stepwise_against_numpy(gpu, case):
 
 
 def _best_plan(case):
-    c = icem_ref.LOOP
-    from helpers import oracle_problem
-    prob, z, xi, carry, valid = icem_ref.loop_case(*case)
-    o = oracle_problem(prob, np.float64)
-    return icem_ref.icem_loop(o, c["E"], c["p"], c["n"], c["iters"], c["num_elites"], noise_beta=case[2], K=c["K"], decay=case[3],
-                              return_best=True, add_mean_last=True, z=z, xi=xi, carry=carry.astype(np.float64), carry_valid=valid)[0]
+    return icem_ref.loop_reference(case, np.float64, return_best=True)[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 5

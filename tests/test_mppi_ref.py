@@ -118,7 +118,7 @@ def test_loop_runs_on_the_icem_cases():
     from helpers import oracle_problem
     case = (6, True, 1.0, 1.5)
     c = icem_ref.LOOP
-    prob, z, xi, carry, valid = icem_ref.loop_case(*case)
+    prob, z, xi, carry, valid = icem_ref.loop_case(case)
     o = oracle_problem(prob, np.float64)
     kw = dict(noise_beta=case[2], K=c["K"], decay=case[3], add_mean_last=True, z=z, xi=xi, carry=carry.astype(np.float64), carry_valid=valid)
     plan, info, ncarry, nvalid = mppi_ref.mppi_loop(o, c["E"], c["p"], c["n"], c["iters"], c["num_elites"], temperature=0.5, relative=True, **kw)
