@@ -64,6 +64,13 @@ class MppiParams(C.Structure):          # include/cadm_hip.h cadm_mppi_params
     _fields_ = [("icem", IcemParams), ("temperature", C.c_float), ("relative", C.c_int32)]
 
 
+class ScoreParams(C.Structure):         # include/cadm_hip.h cadm_score_params
+    _fields_ = [("mode", C.c_int32), ("kappa", C.c_float), ("k", C.c_int32)]
+
+
+SCORE_MODES = {"mean": 0, "mean_std": 1, "member_std": 2, "cvar": 3}      # CADM_SCORE_*
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -112,6 +119,8 @@ SIGNATURES = {
     "cadm_mppi_refit": (_i, [_P, _P, _P, _i, _i, C.c_float, _i, _P, _P, _P, _P]),
     "cadm_mppi_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
     "cadm_mppi_plan": (_i, [_P, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_particle_score": (_i, [_P, _P, _i, _i, C.POINTER(ScoreParams), _P, _P]),
+    "cadm_scored_plan": (_i, [_P, C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

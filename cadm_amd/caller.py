@@ -40,9 +40,8 @@ class DevicePlannerState:
             if K > 0 and (model._plan_carry is None or model._plan_carry.shape[0] != self.m):
                 model._plan_carry = torch.zeros((self.m, K, eng.H, eng.A), dtype=torch.float32, device=eng.device)
                 model._plan_carry_valid = torch.zeros((self.m,), dtype=torch.int32, device=eng.device)
-            run = eng.mppi_plan if model._icem_update == "mppi" else eng.icem_plan
-            plan = run(model._icem_params, obs, hist[0], hist[1], self.prev_sol, self.init_var, model.n_candidates,
-                       carry=model._plan_carry, carry_valid=model._plan_carry_valid, seed=model.seed, call=model._next_call())
+            plan = model._plan_opt_in(obs, hist[0], hist[1], self.prev_sol, self.init_var, model.n_candidates,
+                                      carry=model._plan_carry, carry_valid=model._plan_carry_valid, seed=model.seed, call=model._next_call())
         else:
             plan = eng.cem_plan(obs, hist[0], hist[1], self.prev_sol, self.init_var, model.n_candidates, seed=model.seed, call=model._next_call())
         eng._check(eng.lib.cadm_warm_start_shift(eng._ctx, ptr(plan), self.m, ptr(self.prev_sol), ptr(self.action), eng.stream),

@@ -6,7 +6,8 @@
 //   * the best sequence seen in a call as the plan (icem_track_best_kernel);
 //   * a decaying candidate count.
 // The rollout, the context encoder, the truncated-normal sampler and the elite refit are the reference path's, called unchanged.
-// The loop takes its update as a parameter: cadm_icem_plan runs it with the elite refit, cadm_mppi_plan with the MPPI refit (mppi.hip).
+// The loop takes its update and its candidate score as parameters: cadm_icem_plan runs it with the elite refit, cadm_mppi_plan with the
+// MPPI refit (mppi.hip), both on the particle mean; cadm_scored_plan chooses the update and the score (score.hip).
 #include <math.h>
 
 #include "planner.h"
@@ -332,9 +333,11 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     return ni < n ? ni : n;
 }
 
-static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_icem_params* prm, const float* obs, const float* cp_obs,
-                     const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
-                     uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+// score: what a candidate's particle returns become before the update sees them (score.hip); null = the particle mean
+static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
+                     const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                     int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                     float* best_return_out, void* stream) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -350,6 +353,7 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_icem_param
     CADM_REQUIRE(prm->noise_beta == 0.0f || icem_colored_lds(ctx->H) <= 64 * 1024, "%s: horizon %d is too long for the coloured sampler", who, ctx->H);
     int rc;
     if (upd.mppi && (rc = cadm_mppi_check(ctx, m, upd.temperature, who))) return rc;
+    if ((rc = cadm_score_check(ctx, score, who))) return rc;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
@@ -380,7 +384,7 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_icem_param
         }
         if ((rc = cadm_rollout_returns(ctx, obs, nullptr, ctx->C > 0 ? w.ctxv : nullptr, w.actions, nullptr, 1, seed, call, it, 0, ni, m, ni,
                                        w.rows, nullptr, stream))) return rc;
-        if ((rc = cadm_particle_mean(ctx, w.rows, m, ni, w.cand, stream))) return rc;
+        if ((rc = cadm_particle_score(ctx, w.rows, m, ni, score, w.cand, stream))) return rc;      // (the mean: cadm_particle_mean itself)
         float* plan = (last && !prm->return_best) ? plan_out : nullptr;      // the refitted mean, clipped (dynamics.py:365-366)
         if (!upd.mppi) {
             if ((rc = cadm_launch_refit(ctx, w.cand, nullptr, 1, ni, w.actions, m, mean_in, var_in, w.mean, w.var, w.elites, plan, s))) return rc;
@@ -405,8 +409,8 @@ extern "C" int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* prm, const 
                               const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                               uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
     const PlanUpdate upd{"cadm_icem_plan", 0, 0.0f, 0};
-    return icem_loop(ctx, upd, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call, workspace, plan_out,
-                     best_return_out, stream);
+    return icem_loop(ctx, upd, nullptr, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call, workspace,
+                     plan_out, best_return_out, stream);
 }
 
 // the same loop with the MPPI update (mppi.hip) in place of the elite refit
@@ -415,6 +419,18 @@ extern "C" int cadm_mppi_plan(cadm_ctx* ctx, const cadm_mppi_params* prm, const 
                               uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
     CADM_REQUIRE(prm, "cadm_mppi_plan: bad arguments");
     const PlanUpdate upd{"cadm_mppi_plan", 1, prm->temperature, prm->relative};
-    return icem_loop(ctx, upd, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call, workspace,
-                     plan_out, best_return_out, stream);
+    return icem_loop(ctx, upd, nullptr, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream);
+}
+
+// the same loop with the update and the candidate score chosen by the caller (score.hip); score null or MEAN: the launches of the two above
+extern "C" int cadm_scored_plan(cadm_ctx* ctx, const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs,
+                                const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                                int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                                float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_scored_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_scored_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_scored_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream);
 }

@@ -27,6 +27,9 @@ Differences a caller can see (all opt-in except the first):
   * `cem_update="mppi"`, `cem_temperature`, `cem_temperature_relative`: the MPPI update (INTEGRATION.md "MPPI update") in that loop --
     every candidate refits the mean and variance with weight exp(return / temperature) instead of the top `num_elites` alone;
     `cem_update="mppi"` alone takes the opt-in route, the default "cem" leaves everything as it is;
+  * `cem_score="mean_std" | "member_std" | "cvar"`, `cem_risk`: risk-aware candidate scores in that loop (INTEGRATION.md "Risk-aware
+    scoring") -- a candidate's particle returns become mean - cem_risk * std, mean - cem_risk * (std of the ensemble members' means), or
+    the mean of the worst cem_risk fraction of them, instead of their plain mean; a non-default `cem_score` alone takes the opt-in route;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
     prediction of every ensemble member (the reference has no public predict).
 """
@@ -158,6 +161,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_update="cem",
                  cem_temperature=1.0,
                  cem_temperature_relative=False,
+                 cem_score="mean",
+                 cem_risk=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -216,11 +221,26 @@ class MLPEnsembleCEMDynamicsModel(object):
         # the iCEM planner's switches: all at their defaults = the reference's CEM (`_icem` stays None and get_action never looks further)
         self._icem = None
         self._icem_update = "cem"
+        self._score = None              # (mode name, kappa, k) of a risk-aware score; None: the particle mean
         if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
-                bool(cem_temperature_relative)) != (0.0, 0, 1.0, "mean", False, "cem", 1.0, False):
+                bool(cem_temperature_relative), cem_score, cem_risk) != (0.0, 0, 1.0, "mean", False, "cem", 1.0, False, "mean", None):
             if not use_cem:
-                raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature "
-                                 "configure the CEM planner: they need use_cem=True")
+                raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
+                                 "cem_score / cem_risk configure the CEM planner: they need use_cem=True")
+            if cem_score not in ("mean", "mean_std", "member_std", "cvar"):
+                raise ValueError("cem_score must be 'mean', 'mean_std', 'member_std' or 'cvar', got %r" % (cem_score,))
+            if cem_score == "mean":
+                if cem_risk is not None:
+                    raise ValueError("cem_risk configures a risk-aware score: it needs cem_score='mean_std', 'member_std' or 'cvar'")
+            else:
+                if cem_risk is None or not np.isfinite(float(cem_risk)):
+                    raise ValueError("cem_score=%r needs a finite cem_risk, got %r" % (cem_score, cem_risk))
+                if cem_score == "cvar":
+                    if not 0.0 < float(cem_risk) <= 1.0:
+                        raise ValueError("cem_score='cvar': cem_risk is the tail fraction, in (0, 1]; got %r" % (cem_risk,))
+                    self._score = ("cvar", 0.0, HipEngine.cvar_k(cem_risk, n_particles))
+                else:
+                    self._score = (cem_score, float(cem_risk), None)
             if cem_update not in ("cem", "mppi"):
                 raise ValueError("cem_update must be 'cem' or 'mppi', got %r" % (cem_update,))
             if not (np.isfinite(float(cem_temperature)) and float(cem_temperature) > 0.0):
@@ -281,6 +301,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                 self._icem_params = HipEngine.mppi_params(**self._mppi, **self._icem)
             else:
                 self._icem_params = HipEngine.icem_params(**self._icem)
+            self._score_params = None if self._score is None else HipEngine.score_params(*self._score)
 
     # ------------------------------------------------------------------ planning
     def _push_stats(self):
@@ -418,9 +439,17 @@ class MLPEnsembleCEMDynamicsModel(object):
             action = np.minimum(np.maximum(action, -1.0), 1.0)
         return action
 
+    def _plan_opt_in(self, *args, **kw):
+        """The opt-in loop's entry point for this model's switches: `cadm_icem_plan`, `cadm_mppi_plan` (cem_update="mppi"), or
+        `cadm_scored_plan` with either update (a non-default cem_score).  Arguments as `HipEngine.icem_plan` behind its params."""
+        eng = self.engine
+        if getattr(self, "_score_params", None) is not None:
+            return eng.scored_plan(self._score_params, self._icem_params, *args, **kw)
+        return (eng.mppi_plan if self._icem_update == "mppi" else eng.icem_plan)(self._icem_params, *args, **kw)
+
     def _get_action_icem(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
-        """The opt-in iCEM route of get_action: one `cadm_icem_plan` call (`cadm_mppi_plan` with cem_update="mppi"); the elites it keeps
-        for the next call stay on the device."""
+        """The opt-in iCEM route of get_action: one `cadm_icem_plan` call (`cadm_mppi_plan` with cem_update="mppi", `cadm_scored_plan` with
+        a non-default cem_score); the elites it keeps for the next call stay on the device."""
         m = int(np.shape(obs)[0])
         if m == 0:
             return np.zeros((0, self.n_forwards, self.action_space_dims), np.float32)
@@ -438,9 +467,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         if self.context_out_dim == 0:
             cp_obs = cp_act = None
         host = eng.host_out((m, self.n_forwards, self.action_space_dims))
-        run = eng.mppi_plan if self._icem_update == "mppi" else eng.icem_plan
-        run(self._icem_params, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
-            carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=host)
+        self._plan_opt_in(obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
+                          carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=host)
         torch.cuda.current_stream(eng.device).synchronize()
         return host.numpy().copy()
 

@@ -20,7 +20,8 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
                  weight_decays=(0., 0., 0., 0., 0.), weight_decay_coeff=0.0,
                  reference_quirks=True, seed=0, device=None, process_group=None, check_replicated_calls=2,
                  check_replicated_every=256, cem_noise_beta=0.0, cem_keep_elites=0, cem_decay=1.0, cem_return="mean",
-                 cem_add_mean=False, cem_update="cem", cem_temperature=1.0, cem_temperature_relative=False, engine_lib=None):
+                 cem_add_mean=False, cem_update="cem", cem_temperature=1.0, cem_temperature_relative=False, cem_score="mean",
+                 cem_risk=None, engine_lib=None):
         super().__init__(name, env, hidden_sizes=hidden_sizes, hidden_nonlinearity=hidden_nonlinearity,
                          output_nonlinearity=output_nonlinearity, batch_size=batch_size, learning_rate=learning_rate,
                          normalize_input=normalize_input, optimizer=optimizer, valid_split_ratio=valid_split_ratio,
@@ -33,7 +34,7 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
                          check_replicated_calls=check_replicated_calls, check_replicated_every=check_replicated_every,
                          cem_noise_beta=cem_noise_beta, cem_keep_elites=cem_keep_elites, cem_decay=cem_decay, cem_return=cem_return,
                          cem_add_mean=cem_add_mean, cem_update=cem_update, cem_temperature=cem_temperature,
-                         cem_temperature_relative=cem_temperature_relative, engine_lib=engine_lib)
+                         cem_temperature_relative=cem_temperature_relative, cem_score=cem_score, cem_risk=cem_risk, engine_lib=engine_lib)
 
     def get_action(self, obs, cem_init_mean=None, cem_init_var=None):
         return super().get_action(obs, None, None, cem_init_mean, cem_init_var)

@@ -6,6 +6,7 @@ kernels behind the C ABI.  No host fallback exists: without a GPU or without the
 built library the constructor raises.
 """
 import ctypes as ct
+import math
 from collections import OrderedDict
 
 import numpy as np
@@ -562,18 +563,24 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("icem_plan: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        key = ("icem", m, n, K)
-        if getattr(self, "_icem_ws_key", None) != key:
-            nbytes = self.lib.cadm_icem_workspace_bytes(self._ctx, m, n, K)
-            self._icem_ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
-            self._icem_ws_key = key
+        ws = self._loop_workspace(False, m, n, K)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
         self._check(self.lib.cadm_icem_plan(self._ctx, ct.byref(params), ptr(obs), ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var),
-                                            ptr(carry), ptr(carry_valid), m, n, seed, call, ptr(self._icem_ws), ptr(out), ptr(best),
+                                            ptr(carry), ptr(carry_valid), m, n, seed, call, ptr(ws), ptr(out), ptr(best),
                                             self.stream), "cadm_icem_plan")
         return (out, best) if want_best_return else out
+
+    def _loop_workspace(self, mppi, m, n, K):
+        """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update."""
+        name = "_mppi_ws" if mppi else "_icem_ws"
+        key = ("mppi" if mppi else "icem", m, n, K)
+        if getattr(self, name + "_key", None) != key:
+            nbytes = (self.lib.cadm_mppi_workspace_bytes if mppi else self.lib.cadm_icem_workspace_bytes)(self._ctx, m, n, K)
+            setattr(self, name, torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device))
+            setattr(self, name + "_key", key)
+        return getattr(self, name)
 
     # ------------------------------------------------------------------ MPPI update (opt-in; csrc/mppi.hip)
     def mppi_refit(self, cand, actions, mean, var, temperature=1.0, relative=False, want_plan=False):
@@ -608,17 +615,68 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("mppi_plan: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        key = ("mppi", m, n, K)
-        if getattr(self, "_mppi_ws_key", None) != key:
-            nbytes = self.lib.cadm_mppi_workspace_bytes(self._ctx, m, n, K)
-            self._mppi_ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
-            self._mppi_ws_key = key
+        ws = self._loop_workspace(True, m, n, K)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
         self._check(self.lib.cadm_mppi_plan(self._ctx, ct.byref(params), ptr(obs), ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var),
-                                            ptr(carry), ptr(carry_valid), m, n, seed, call, ptr(self._mppi_ws), ptr(out), ptr(best),
+                                            ptr(carry), ptr(carry_valid), m, n, seed, call, ptr(ws), ptr(out), ptr(best),
                                             self.stream), "cadm_mppi_plan")
+        return (out, best) if want_best_return else out
+
+    # ------------------------------------------------------------------ risk-aware candidate scores (opt-in; csrc/score.hip)
+    @staticmethod
+    def score_params(mode="mean", kappa=0.0, k=None):
+        """`cadm_score_params`.  mode: "mean" | "mean_std" | "member_std" | "cvar" (or its CADM_SCORE_* number); kappa: the weight of the
+        standard deviation (the std modes); k: how many of the lowest particle returns are averaged (cvar)."""
+        prm = _lib.ScoreParams()
+        prm.mode = _lib.SCORE_MODES[mode] if isinstance(mode, str) else int(mode)
+        prm.kappa, prm.k = float(kappa), 0 if k is None else int(k)
+        return prm
+
+    @staticmethod
+    def cvar_k(alpha, p):
+        """The tail fraction alpha in (0, 1] of p particles as a count: min(p, max(1, ceil(alpha p))), alpha p rounded to 6 decimals first
+        (0.1 * 20 is 2.0000000000000004 in binary: 2 particles, not 3)."""
+        return int(min(p, max(1, math.ceil(round(float(alpha) * p, 6)))))
+
+    def particle_score(self, rows, mode, kappa=0.0, k=None):
+        """`cadm_particle_score`: rows [m,n_local,p] -> the candidates' scores [m,n_local] (mode "mean": `particle_mean`'s bits).
+        mode: a name or number as in `score_params`, or a `score_params` result."""
+        rows = self._t(rows)
+        if rows.dim() != 3 or rows.shape[2] != self.p or not rows.is_contiguous():
+            raise ValueError("particle_score: rows %r, expected [m, n_local, %d] contiguous" % (tuple(rows.shape), self.p))
+        m, n_local = rows.shape[0], rows.shape[1]
+        prm = mode if isinstance(mode, _lib.ScoreParams) else self.score_params(mode, kappa, k)
+        out = torch.empty((m, n_local), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_particle_score(self._ctx, ptr(rows), m, n_local, ct.byref(prm), ptr(out), self.stream), "cadm_particle_score")
+        return out
+
+    def scored_plan(self, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
+                    want_best_return=False):
+        """`cadm_scored_plan`: the loop of `icem_plan` (params from `icem_params`) or of `mppi_plan` (params from `mppi_params`) with
+        `score` (`score_params`; None = the mean) in place of the particle mean.  The best return is then the best score.  Arguments as
+        `icem_plan`; the workspaces are the ones those two cache."""
+        mppi = isinstance(params, _lib.MppiParams)
+        if not mppi:
+            full = _lib.MppiParams()
+            full.icem, full.temperature = params, 1.0
+            params = full
+        obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
+        cp_obs = None if cp_obs is None else self._t(cp_obs)
+        cp_act = None if cp_act is None else self._t(cp_act)
+        m, K = obs.shape[0], int(params.icem.keep_elites)
+        if K > 0 and (carry is None or carry_valid is None or tuple(carry.shape) != (m, K, self.H, self.A) or carry.dtype != torch.float32
+                      or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
+            raise ValueError("scored_plan: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (K, m, K, self.H, self.A, m))
+        self.ensure_rollout(None, m, n)
+        ws = self._loop_workspace(mppi, m, n, K)
+        if out is None:
+            out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
+        best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
+        self._check(self.lib.cadm_scored_plan(self._ctx, None if score is None else ct.byref(score), int(mppi), ct.byref(params), ptr(obs),
+                                              ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var), ptr(carry), ptr(carry_valid), m, n,
+                                              seed, call, ptr(ws), ptr(out), ptr(best), self.stream), "cadm_scored_plan")
         return (out, best) if want_best_return else out
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon

@@ -11,7 +11,7 @@ checks -- an all-gather this module supplies over any torch.distributed backend 
 What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
-  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`) one launch at a time, for the same purposes;
+  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
@@ -142,10 +142,11 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
 
 def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
               add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False,
-              update="cem", temperature=1.0, relative=False):
+              update="cem", temperature=1.0, relative=False, score=None):
     """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
     tests with injected draws and for diagnostics.  update="mppi": the loop of `cadm_mppi_plan` -- the elite ids come from an elite
-    refit into copies of mean / var, the distribution from `mppi_refit`.  z / xi / eps: optional per-iteration lists of injected truncated-normal draws
+    refit into copies of mean / var, the distribution from `mppi_refit`.  score: a `HipEngine.score_params` (`cadm_scored_plan`; None: the
+    particle mean) -- `cand`, the elites and the best return are then by score.  z / xi / eps: optional per-iteration lists of injected truncated-normal draws
     [m,n_it,H,A] (noise_beta == 0), spectral draws [m,n_it,A,H] (noise_beta > 0) and head noise [H,m,n_it,p,D].  carry [m,K,H,A] /
     carry_valid [m] int32 are read at iteration 0 and rewritten IN PLACE after the last refit, as the library does."""
     obs = engine._t(obs)
@@ -170,7 +171,7 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
         if last and add_mean_last:
             engine.icem_inject(actions, mean.clamp(lo, hi).unsqueeze(1).contiguous(), slot0=K)
         rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
-        cand = engine.particle_mean(rows)
+        cand = engine.particle_mean(rows) if score is None else engine.particle_score(rows, score)
         if update == "mppi":
             elites = engine.cem_refit(cand.unsqueeze(0), actions, mean.clone(), var.clone(), want_elites=True)
             engine.mppi_refit(cand, actions, mean, var, temperature=temperature, relative=relative)

@@ -348,6 +348,44 @@ int cadm_mppi_plan(cadm_ctx* ctx, const cadm_mppi_params* params, const float* o
                    const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                    uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
 
+/* Risk-aware candidate scores (no reference twin, OPT-IN): what a candidate's p particle returns become before the update of the
+ * opt-in loop ranks or weighs it.  The rollout writes every particle's return (returns_rows [m,n_local,p]) -- a probabilistic ensemble
+ * with trajectory sampling computes them to expose model uncertainty -- and the plain mean averages that uncertainty away.  Per
+ * candidate, with mu = the mean exactly as cadm_particle_mean computes it (one fp32 chain over j = 0 .. p-1, then / p):
+ *   CADM_SCORE_MEAN        mu: cadm_particle_mean itself is enqueued (the same kernel, grid and bits)
+ *   CADM_SCORE_MEAN_STD    mu - kappa sigma,    sigma   = sqrt(sum_j (r_j - mu)^2 / p)        (mu first, then the deviations from it)
+ *   CADM_SCORE_MEMBER_STD  mu - kappa sigma_E,  sigma_E = sqrt(sum_e (mu_e - mu)^2 / E),  mu_e = the mean of member e's q = p / E
+ *                          particles (particle j belongs to member j / q, as in the rollout): what the MEMBERS disagree about
+ *   CADM_SCORE_CVAR        the mean of the k lowest returns, 1 <= k <= p: particle j counts iff rank_j < k,
+ *                          rank_j = #{i : r_i < r_j or (r_i == r_j and i < j)}; the counted r_j are added in particle order, then / k
+ * kappa: any finite float (> 0 pessimistic, < 0 optimistic, 0: mu's bits).  k = p: the mean up to rounding; k = 1: the minimum.
+ * Every sum is one chain in index order: the same bits run to run, whatever m, n_local and the candidate's position.
+ * A candidate with a NaN or +-inf particle return scores, in every mode, exactly what cadm_particle_mean gives it: a diverged row
+ * meets the elite ranking, cadm_icem_track_best and MPPI's zero weight as it does under the mean.
+ * cadm_particle_score is rank-local (it works on a sharded ctx, like cadm_particle_mean) and needs no workspace.
+ * CADM_EINVAL (before any HIP call) for an unknown mode, a kappa that is not finite (the std modes), k outside [1, p] (CVAR).
+ * score NULL = CADM_SCORE_MEAN. */
+#define CADM_SCORE_MEAN 0
+#define CADM_SCORE_MEAN_STD 1
+#define CADM_SCORE_MEMBER_STD 2
+#define CADM_SCORE_CVAR 3
+typedef struct cadm_score_params {
+    int32_t mode;           /* CADM_SCORE_* */
+    float kappa;            /* MEAN_STD, MEMBER_STD: the weight of the standard deviation */
+    int32_t k;              /* CVAR: the number of lowest particle returns averaged */
+} cadm_score_params;
+int cadm_particle_score(cadm_ctx* ctx, const float* returns_rows, int m, int n_local, const cadm_score_params* score,
+                        float* cand_returns, void* stream);
+/* The loop of cadm_icem_plan (update == 0: the elite refit; only params->icem is read) or of cadm_mppi_plan (update == 1) with this
+ * score in place of the particle mean; everything else composes unchanged.  The elites, the tracked best plan and best_return_out
+ * are by SCORE (best_return_out is the best score, not the best mean).  score NULL or CADM_SCORE_MEAN: exactly the launches of
+ * cadm_icem_plan / cadm_mppi_plan.  Refusals: those of the loop with that update, the score's, and an update that is not 0 or 1.
+ * workspace: cadm_icem_workspace_bytes (update 0) / cadm_mppi_workspace_bytes (update 1); scoring needs none of its own. */
+int cadm_scored_plan(cadm_ctx* ctx, const cadm_score_params* score, int update, const cadm_mppi_params* params, const float* obs,
+                     const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                     int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                     float* best_return_out, void* stream);
+
 /* One training step = sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
