@@ -68,6 +68,11 @@ class ScoreParams(C.Structure):         # include/cadm_hip.h cadm_score_params
     _fields_ = [("mode", C.c_int32), ("kappa", C.c_float), ("k", C.c_int32)]
 
 
+class ForecastOut(C.Structure):         # include/cadm_hip.h cadm_forecast_out: device pointers
+    _fields_ = [(k, C.c_void_p) for k in ("mean", "member_mean", "var_total", "var_epistemic", "var_aleatoric", "lo", "hi", "reward_mean",
+                                          "reward_var", "reward_member", "returns", "diverged_step", "rollout_returns")]
+
+
 SCORE_MODES = {"mean": 0, "mean_std": 1, "member_std": 2, "cvar": 3}      # CADM_SCORE_*
 
 
@@ -136,6 +141,9 @@ SIGNATURES = {
     "cadm_horizon_error": (_i, [_P, _P, C.c_longlong, _P, _i, _i, _i, _i, _i, C.c_longlong, _P, C.c_longlong, _P, _P, _P, _P, _P, _i, _P]),
     "cadm_eval_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
     "cadm_eval_horizon": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _u32, _u32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cadm_forecast_stats": (_i, [_P, _P, _P, _P, _i, _i, _i, _i, _i, _i, C.POINTER(ForecastOut), _P]),
+    "cadm_forecast_workspace_bytes": (C.c_size_t, [_P, _i, _i]),
+    "cadm_plan_forecast": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _i, _u32, _u32, _P, C.POINTER(ForecastOut), _P]),
     "cadm_dist_unique_id": (_i, [C.c_char_p]),
     "cadm_dist_init": (_i, [_P, C.c_char_p, _i, _i]),
     "cadm_dist_destroy": (_i, [_P]),

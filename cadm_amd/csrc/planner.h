@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, forecast.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -36,6 +36,11 @@ struct Carver {
         return p;
     }
 };
+
+// forecast.hip: the rollout of cadm_plan_forecast runs under this iteration word (include/cadm_hip.h).  Even: the context layout is
+// iteration 0's.  The planner loops count 0 .. num_cem_iters - 1 (cadm_plan_forecast refuses a ctx whose loop could get here), so a
+// forecast never repeats the noise a planner call drew for the same (seed, call).  (The word takes 24 bits of a Philox counter.)
+#define CADM_FORECAST_IT 0xFC0000
 
 // cem.hip
 int cadm_launch_clip(const float* in, float* out, int total, float lo, float hi, int do_clip, hipStream_t s);

@@ -30,6 +30,8 @@ Differences a caller can see (all opt-in except the first):
   * `cem_score="mean_std" | "member_std" | "cvar"`, `cem_risk`: risk-aware candidate scores in that loop (INTEGRATION.md "Risk-aware
     scoring") -- a candidate's particle returns become mean - cem_risk * std, mean - cem_risk * (std of the ensemble members' means), or
     the mean of the worst cem_risk fraction of them, instead of their plain mean; a non-default `cem_score` alone takes the opt-in route;
+  * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
+    their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
     prediction of every ensemble member (the reference has no public predict).
 """
@@ -375,9 +377,13 @@ class MLPEnsembleCEMDynamicsModel(object):
             return True
         return self._check_replicated_every > 0 and self._sharded_calls % self._check_replicated_every == 0
 
-    def get_action(self, obs, cp_obs, cp_act, cem_init_mean=None, cem_init_var=None):
+    def get_action(self, obs, cp_obs, cp_act, cem_init_mean=None, cem_init_var=None, return_forecast=False):
         """reference :344-367.  CEM: returns the whole plan [m,H,A]; RS: the first action [m,A]
-        (ints [m] for discrete envs).  Continuous outputs are clipped to [-1,1]."""
+        (ints [m] for discrete envs).  Continuous outputs are clipped to [-1,1].
+        return_forecast=True (an extension; CEM routes only): returns (plan, forecast) -- `forecast` of the returned plan, drawn with
+        this call's own (seed, call)."""
+        if return_forecast:
+            return self._get_action_with_forecast(obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
         if self._stats_dirty:
             self._push_stats()
         if getattr(self, "_icem", None) is not None and cem_init_mean is not None:      # the opt-in iCEM planner; None: today's route
@@ -471,6 +477,65 @@ class MLPEnsembleCEMDynamicsModel(object):
                           carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=host)
         torch.cuda.current_stream(eng.device).synchronize()
         return host.numpy().copy()
+
+    # ------------------------------------------------------------------ forecast of a plan (INTEGRATION.md "Forecasting a plan")
+    def _forecast_refuse(self, what):
+        if self.discrete:
+            raise ValueError("%s: discrete actions are not forecast (random shooting returns no plan)" % what)
+
+    def _get_action_with_forecast(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
+        """get_action on today's route, whichever it is, then the forecast of the plan it returned under the same (seed, call)."""
+        self._forecast_refuse("get_action(return_forecast=True)")
+        if cem_init_mean is None:
+            raise ValueError("get_action(return_forecast=True): the random-shooting route returns one action, not a plan to forecast")
+        plan = MLPEnsembleCEMDynamicsModel.get_action(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var)      # (not a subclass's signature)
+        return plan, self._forecast(obs, plan, cp_obs, cp_act, 1, self.seed, self._call & 0xFFFFFFFF)
+
+    def _forecast(self, obs, actions, cp_obs, cp_act, band_k, seed, call):
+        self._push_stats()
+        D, A, H = self.obs_space_dims, self.action_space_dims, self.n_forwards
+        shp = tuple(int(v) for v in np.shape(actions))
+        m = int(np.shape(obs)[0])
+        if tuple(np.shape(obs)) != (m, D) or m == 0 or len(shp) not in (3, 4) or shp[0] != m or shp[-2:] != (H, A):
+            raise ValueError("forecast: obs %r, actions %r: expected [m,%d] with m >= 1 and [m,%d,%d] or [m,n,%d,%d]"
+                             % (tuple(np.shape(obs)), shp, D, H, A, H, A))
+        if self.context_out_dim > 0:
+            if cp_obs is None or cp_act is None:
+                raise ValueError("forecast: cp_obs and cp_act are required for a context model")
+            Hh = self.history_length
+            if tuple(np.shape(cp_obs)) != (m, D * Hh) or tuple(np.shape(cp_act)) != (m, A * Hh):
+                raise ValueError("forecast: cp_obs %r / cp_act %r, expected %r / %r" % (tuple(np.shape(cp_obs)), tuple(np.shape(cp_act)),
+                                                                                       (m, D * Hh), (m, A * Hh)))
+        else:
+            cp_obs = cp_act = None
+        eng = self.engine
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        out = eng.plan_forecast(obs, cp_obs, cp_act, acts[:, None] if squeeze else acts, band_k=band_k, seed=int(seed) & 0xFFFFFFFF, call=call)
+        r = {k: v.cpu().numpy() for k, v in out.items()}
+        res = dict(mean=r["mean"], member_mean=r["member_mean"], std_total=np.sqrt(r["var_total"]), std_epistemic=np.sqrt(r["var_epistemic"]),
+                   std_aleatoric=np.sqrt(r["var_aleatoric"]), lo=r["lo"], hi=r["hi"], reward_mean=r["reward_mean"],
+                   reward_std=np.sqrt(r["reward_var"]), reward_member=r["reward_member"], returns=r["returns"],
+                   return_mean=r["returns"].mean(axis=-1), rollout_returns=r["rollout_returns"], diverged_step=r["diverged_step"])
+        if squeeze:
+            res = {k: v[:, :, 0] if k in ("member_mean", "reward_member") else v[:, 0] for k, v in res.items()}
+        return res
+
+    def forecast(self, obs, actions, cp_obs=None, cp_act=None, band_k=1, seed=None):
+        """What the model predicts under `actions` ([m,H,A], or [m,n,H,A]: n sequences per env; numpy or tensor), step by step, as
+        numpy arrays (for [m,H,A] input the n axis is dropped):
+          mean, std_total, std_epistemic, std_aleatoric, lo, hi [m,n,H,D]; member_mean [E,m,n,H,D]   predicted states: particle mean,
+              spread over the particles, its part from member disagreement / from noise inside a member (total^2 = epistemic^2 +
+              aleatoric^2), and the band_k-th smallest / largest particle value
+          reward_mean, reward_std [m,n,H]; reward_member [E,m,n,H]   the step reward
+          returns, rollout_returns [m,n,p]; return_mean [m,n]        per-particle returns (the forecast's own sum of step rewards, and
+              the rollout kernel's), and the particle mean of `returns`
+          diverged_step [m,n]   the first step with a non-finite predicted value (H: none); from it on the statistics are NaN
+        The noise is the device generator's under (seed, call) -- seed: the model's by default, call: the last get_action's -- with an
+        iteration word no planner loop uses.  The planner's call counter does not move: planning is the same with or without forecasts
+        in between, and `forecast` of the plan `get_action` just returned reproduces `get_action(..., return_forecast=True)`'s."""
+        self._forecast_refuse("forecast")
+        return self._forecast(obs, actions, cp_obs, cp_act, band_k, self.seed if seed is None else seed, self._call & 0xFFFFFFFF)
 
     def reset_plan_carry(self, mask=None):
         """Forget the elites the iCEM planner carries from one get_action to the next (`cem_keep_elites` > 0): for every env, or for

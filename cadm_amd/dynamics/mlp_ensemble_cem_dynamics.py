@@ -36,8 +36,14 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
                          cem_add_mean=cem_add_mean, cem_update=cem_update, cem_temperature=cem_temperature,
                          cem_temperature_relative=cem_temperature_relative, cem_score=cem_score, cem_risk=cem_risk, engine_lib=engine_lib)
 
-    def get_action(self, obs, cem_init_mean=None, cem_init_var=None):
+    def get_action(self, obs, cem_init_mean=None, cem_init_var=None, return_forecast=False):
+        if return_forecast:
+            return super().get_action(obs, None, None, cem_init_mean, cem_init_var, return_forecast=True)
         return super().get_action(obs, None, None, cem_init_mean, cem_init_var)
+
+    def forecast(self, obs, actions, band_k=1, seed=None):
+        """The model's per-step prediction under `actions` (see the CaDM class; a vanilla model has no history)."""
+        return super().forecast(obs, actions, None, None, band_k=band_k, seed=seed)
 
     def predict(self, obs, act, return_std=False):
         return super().predict(obs, act, None, None, return_std=return_std)

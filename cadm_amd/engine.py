@@ -728,6 +728,67 @@ class HipEngine:
                                                ptr(out["diverged"]), self.stream), "cadm_eval_horizon")
         return out
 
+    # ------------------------------------------------------------------ forecast of a plan (opt-in; csrc/forecast.hip)
+    def _forecast_outputs(self, m, n, H, p, E, rollout_returns=False):
+        D = self.D
+        z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        out = dict(mean=z(m, n, H, D), member_mean=z(E, m, n, H, D), var_total=z(m, n, H, D), var_epistemic=z(m, n, H, D),
+                   var_aleatoric=z(m, n, H, D), lo=z(m, n, H, D), hi=z(m, n, H, D), reward_mean=z(m, n, H), reward_var=z(m, n, H),
+                   reward_member=z(E, m, n, H), returns=z(m, n, p),
+                   diverged_step=torch.empty((m, n), dtype=torch.int32, device=self.device))
+        if rollout_returns:
+            out["rollout_returns"] = z(m, n, p)
+        c = _lib.ForecastOut()
+        for k, v in out.items():
+            setattr(c, k, v.data_ptr())
+        return out, c
+
+    def forecast_stats(self, traj, obs, actions, band_k=1, E=None):
+        """`cadm_forecast_stats` on device tensors: traj [H,m,n,p,D] (a rollout's `traj_out`; H may be below the engine's horizon, p
+        need not be the engine's), obs [m,D], actions [m,n,H,A] raw -> dict of device tensors: mean / var_total / var_epistemic /
+        var_aleatoric / lo / hi [m,n,H,D], member_mean [E,m,n,H,D], reward_mean / reward_var [m,n,H], reward_member [E,m,n,H], returns
+        [m,n,p], diverged_step [m,n] int32.  VARIANCES; lo / hi are the band_k-th smallest / largest particle value.  E: the number
+        of members the p particles split into (default: the engine's)."""
+        traj, obs, actions = self._t(traj), self._t(obs), self._t(actions)
+        E = self.E if E is None else int(E)
+        if traj.dim() != 5 or actions.dim() != 4 or obs.dim() != 2:
+            raise ValueError("forecast_stats: traj %r, obs %r, actions %r: expected [H,m,n,p,D], [m,D], [m,n,H,A]"
+                             % (tuple(traj.shape), tuple(obs.shape), tuple(actions.shape)))
+        H, m, n, p, D = traj.shape
+        if D != self.D or tuple(obs.shape) != (m, D) or tuple(actions.shape) != (m, n, H, self.A):
+            raise ValueError("forecast_stats: traj %r, obs %r, actions %r do not agree (D=%d, A=%d)"
+                             % (tuple(traj.shape), tuple(obs.shape), tuple(actions.shape), self.D, self.A))
+        out, c = self._forecast_outputs(m, n, H, p, max(E, 1))
+        self._check(self.lib.cadm_forecast_stats(self._ctx, ptr(traj), ptr(obs), ptr(actions), m, n, H, p, E, int(band_k), ct.byref(c),
+                                                 self.stream), "cadm_forecast_stats")
+        return out
+
+    def plan_forecast(self, obs, cp_obs, cp_act, actions, band_k=1, eps=None, seed=0, call=0):
+        """`cadm_plan_forecast`: the context encoder, one rollout of the n given action sequences per env (actions [m,n,H,A], raw;
+        eps [H,m,n,p,D] injected noise, else device Philox keyed (seed, call) under the forecast's own iteration word) and the
+        statistics of its trajectories -> the dict of `forecast_stats` plus rollout_returns [m,n,p], the rollout's own returns."""
+        obs, actions = self._t(obs), self._t(actions)
+        cp_obs = None if cp_obs is None or self.C == 0 else self._t(cp_obs)
+        cp_act = None if cp_act is None or self.C == 0 else self._t(cp_act)
+        eps = None if eps is None else self._t(eps)
+        if actions.dim() != 4 or obs.dim() != 2 or tuple(actions.shape) != (obs.shape[0], actions.shape[1], self.H, self.A) or obs.shape[1] != self.D:
+            raise ValueError("plan_forecast: obs %r, actions %r: expected [m,%d] and [m,n,%d,%d]" % (tuple(obs.shape), tuple(actions.shape), self.D,
+                                                                                                   self.H, self.A))
+        m, n = actions.shape[0], actions.shape[1]
+        if eps is not None and tuple(eps.shape) != (self.H, m, n, self.p, self.D):
+            raise ValueError("plan_forecast: eps has shape %r, expected %r" % (tuple(eps.shape), (self.H, m, n, self.p, self.D)))
+        if not self.discrete:      # (a discrete engine is refused by the library, with its message)
+            self.ensure_rollout(_lib.NOISE_NONE if self.deterministic else _lib.NOISE_INJECT if eps is not None else _lib.NOISE_PHILOX, m, n)
+        key = (m, n)
+        if getattr(self, "_forecast_ws_key", None) != key:
+            nbytes = self.lib.cadm_forecast_workspace_bytes(self._ctx, m, n)
+            self._forecast_ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
+            self._forecast_ws_key = key
+        out, c = self._forecast_outputs(m, n, self.H, self.p, self.E, rollout_returns=True)
+        self._check(self.lib.cadm_plan_forecast(self._ctx, ptr(obs), ptr(cp_obs), ptr(cp_act), ptr(actions), ptr(eps), m, n, int(band_k),
+                                                seed, call, ptr(self._forecast_ws), ct.byref(c), self.stream), "cadm_plan_forecast")
+        return out
+
     # ------------------------------------------------------------------ training
     def train_configure(self, learning_rate, weight_decays, context_weight_decays, weight_decay_coeff, back_coeff,
                         max_batch, beta1=0.9, beta2=0.999, epsilon=1e-8):

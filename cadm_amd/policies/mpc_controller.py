@@ -6,7 +6,7 @@ import numpy as np
 
 class MPCController(object):
     def __init__(self, name, env, dynamics_model, reward_model=None, discount=1, use_cem=False,
-                 n_candidates=1024, horizon=10, num_rollouts=10, context=False):
+                 n_candidates=1024, horizon=10, num_rollouts=10, context=False, forecast=False):
         self.name = name
         self.env = env
         self.dynamics_model = dynamics_model
@@ -17,6 +17,9 @@ class MPCController(object):
         self.use_cem = use_cem
         self.context = context
         self.num_rollouts = num_rollouts
+        # forecast=True (an extension; CEM only): every plan comes with the model's forecast of it, kept as `last_forecast`
+        self.forecast = bool(forecast)
+        self.last_forecast = None
 
     @property
     def vectorized(self):
@@ -30,6 +33,9 @@ class MPCController(object):
             args += list(cp if cp is not None else (None, None))
         if self.use_cem:
             args += list(init if init is not None else (None, None))
+        if self.forecast:
+            plan, self.last_forecast = self.dynamics_model.get_action(*args, return_forecast=True)
+            return plan
         return self.dynamics_model.get_action(*args)
 
     # ---- the reference's entry points (mpc_controller.py:43-90), all thin views of _plan ----

@@ -490,6 +490,62 @@ int cadm_eval_horizon(cadm_ctx* ctx, const float* ds_obs, const float* ds_act, c
                       const float* eps, void* workspace, float* se_out, float* spread_out, float* se_member_out,
                       int32_t* count_out, int32_t* diverged_out, void* stream);
 
+/* Forecast of a plan (no reference twin, OPT-IN): what the ensemble predicts under given action sequences, step by step, and how
+ * sure it is -- the trajectories of one rollout reduced on the device.  The rollout kernels and the planner loops are untouched.
+ *
+ * cadm_forecast_stats: the statistics of recorded trajectories.  The ctx supplies D, A and the reward closure; nothing of its model.
+ *   traj     [H,m,n,p,D]  post-step states: the layout of cadm_rollout_returns' traj_out; H >= 1 may be below the ctx's horizon
+ *   obs      [m,D]        start state
+ *   actions  [m,n,H,A]    raw, as the rollout takes them (the same H)
+ *   p, E                  p % E == 0; particle j belongs to member j / (p / E), as in the rollout
+ *   band_k                1 .. p
+ * Outputs (cadm_forecast_out; every pointer but rollout_returns is required), per sequence (mi, ni) and step t:
+ *   mean [m,n,H,D]           over the p particles
+ *   member_mean [E,m,n,H,D]  over a member's p / E particles
+ *   var_total [m,n,H,D]      biased variance over the particles
+ *   var_epistemic [m,n,H,D]  biased variance of the E member means: what the members disagree about
+ *   var_aleatoric [m,n,H,D]  mean over the members of the biased variance inside a member; total = epistemic + aleatoric
+ *   lo, hi [m,n,H,D]         the band_k-th smallest / band_k-th largest particle value (order statistics, no interpolation; 1: min, max)
+ *   reward_mean, reward_var [m,n,H], reward_member [E,m,n,H]   the same mean / biased variance / member means of the step reward
+ *   returns [m,n,p]          per particle, its step rewards added in step order
+ *   diverged_step [m,n]      int32: the first t at which any of the sequence's p * D values is non-finite, H if there is none
+ * VARIANCES, not standard deviations.  Means and variances are formed relative to particle 0: particles that agree give exactly their
+ * value as every mean and exactly 0 as every variance.  The step reward of particle j at step t reads the pre-step state (obs at
+ * t = 0, else traj[t-1]), the post-step state traj[t] and the raw action: for the built-in continuous kinds the pair parts the
+ * rollout adds, summed in ascending dim-pair order; for CADM_ENV_SPEC the ctx's cadm_env_spec evaluated at run time as
+ * ((pre-step terms of the first term's dim pair, in order) - ctrl_cost sum(a^2)) + bonus, then the other terms in declaration order.
+ * Divergence: every statistic of a sequence at t >= its diverged_step is NaN, and so are its returns; other sequences are unaffected.
+ * It is read off `traj` alone: a non-finite `obs` leaves diverged_step as it is and shows as non-finite step-0 rewards and returns.
+ * A member of one particle (p == E) has that particle's value, bit for bit, as its member_mean / reward_member.
+ * Every sum is one thread's chain in a fixed order (csrc/forecast.hip, "Reduction contract"); no floating-point atomics: the same
+ * bits run to run, and per sequence whatever m and n.
+ * Refusals, before any HIP call: CADM_EINVAL for a null pointer, a discrete ctx (cartpole; the RS planner returns no plan), m, n, H,
+ * p < 1, p % E != 0, band_k outside 1 .. p, and a p * D whose two LDS tiles and accumulators (8 p D + 8 p + 40 bytes at most) exceed
+ * 48 KiB; CADM_ESTATE for a CADM_ENV_SPEC ctx before cadm_set_env_spec. */
+typedef struct cadm_forecast_out {
+    float *mean, *member_mean, *var_total, *var_epistemic, *var_aleatoric, *lo, *hi;
+    float *reward_mean, *reward_var, *reward_member, *returns;
+    int32_t* diverged_step;
+    float* rollout_returns;   /* cadm_plan_forecast only: [m,n,p], the rollout's own returns_rows */
+} cadm_forecast_out;
+int cadm_forecast_stats(cadm_ctx* ctx, const float* traj, const float* obs, const float* actions, int m, int n, int H, int p, int E,
+                        int band_k, const cadm_forecast_out* out, void* stream);
+/* The forecast of the ctx's model for n given action sequences per env: the context encoder as cadm_cem_plan runs it (C > 0), ONE
+ * rollout of m envs x n sequences over the ctx's full horizon that records its trajectories (n_local = n_global = n, cand_offset 0),
+ * and cadm_forecast_stats with the ctx's p and E.  obs [m,D], cp_obs / cp_act as cadm_cem_plan, actions [m,n,H,A] raw.
+ * Noise: eps [H,m,n,p,D] injected N(0,1), or NULL to draw from Philox keyed (seed, call) (a deterministic ctx reads neither).  The
+ * rollout's iteration word is the constant 0xFC0000 (16515072): even, so the context layout is iteration 0's, and beyond every
+ * planner loop's iterations 0 .. num_cem_iters - 1 (a ctx whose num_cem_iters exceeds it is refused): a forecast never repeats the
+ * noise the planner drew for the same (seed, call).  out->rollout_returns receives the rollout's own returns_rows: the forecast's
+ * returns account for the return the planner scores, up to the order of the additions.
+ * A sharded ctx runs it unsharded on every rank; there is no collective.  Refusals: those of cadm_forecast_stats and of
+ * cadm_rollout_returns.  workspace: cadm_forecast_workspace_bytes(ctx, m, n) bytes (0 for bad arguments).  Everything is enqueued
+ * on `stream`. */
+size_t cadm_forecast_workspace_bytes(cadm_ctx* ctx, int m, int n);
+int cadm_plan_forecast(cadm_ctx* ctx, const float* obs, const float* cp_obs, const float* cp_act, const float* actions, const float* eps,
+                       int m, int n, int band_k, uint32_t seed, uint32_t call, void* workspace, const cadm_forecast_out* out,
+                       void* stream);
+
 /* Multi-GPU planning: candidates shard contiguously over the ranks of an RCCL communicator owned by the
  * ctx (one process per GPU).  The reference is single-device (cadm/trainers/mb_trainer.py:103-107); this
  * adds exactly one collective per CEM iteration -- ncclAllGather of the per-candidate returns
