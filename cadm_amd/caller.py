@@ -35,13 +35,8 @@ class DevicePlannerState:
         model._push_stats()
         obs = eng._t(obs)
         hist = (self.hist_obs, self.hist_act) if self.context else (None, None)
-        if getattr(model, "_icem", None) is not None:      # the opt-in iCEM planner: its carried elites live on the model
-            K = model._icem["keep_elites"]
-            if K > 0 and (model._plan_carry is None or model._plan_carry.shape[0] != self.m):
-                model._plan_carry = torch.zeros((self.m, K, eng.H, eng.A), dtype=torch.float32, device=eng.device)
-                model._plan_carry_valid = torch.zeros((self.m,), dtype=torch.int32, device=eng.device)
-            plan = model._plan_opt_in(obs, hist[0], hist[1], self.prev_sol, self.init_var, model.n_candidates,
-                                      carry=model._plan_carry, carry_valid=model._plan_carry_valid, seed=model.seed, call=model._next_call())
+        if model._opt is not None:      # the opt-in planner: the model owns its carried elites and the call
+            plan = model._plan_opt_in(obs, hist[0], hist[1], self.prev_sol, self.init_var)
         else:
             plan = eng.cem_plan(obs, hist[0], hist[1], self.prev_sol, self.init_var, model.n_candidates, seed=model.seed, call=model._next_call())
         eng._check(eng.lib.cadm_warm_start_shift(eng._ctx, ptr(plan), self.m, ptr(self.prev_sol), ptr(self.action), eng.stream),

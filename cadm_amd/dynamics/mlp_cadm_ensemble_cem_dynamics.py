@@ -27,6 +27,7 @@ Differences a caller can see (all opt-in except the first):
   * `cem_update="mppi"`, `cem_temperature`, `cem_temperature_relative`: the MPPI update (INTEGRATION.md "MPPI update") in that loop --
     every candidate refits the mean and variance with weight exp(return / temperature) instead of the top `num_elites` alone;
     `cem_update="mppi"` alone takes the opt-in route, the default "cem" leaves everything as it is;
+    (what the ten `cem_*` kwargs mean is held in ONE attribute, `_opt`: None at the defaults, else a cadm_amd.planner.PlanOptions)
   * `cem_score="mean_std" | "member_std" | "cvar"`, `cem_risk`: risk-aware candidate scores in that loop (INTEGRATION.md "Risk-aware
     scoring") -- a candidate's particle returns become mean - cem_risk * std, mean - cem_risk * (std of the ensemble members' means), or
     the mean of the worst cem_risk fraction of them, instead of their plain mean; a non-default `cem_score` alone takes the opt-in route;
@@ -115,6 +116,16 @@ class ReplayIndexStream(object):
 
     def epoch_order(self, E, n_train):
         return self._next("epoch_order", (E, n_train))
+
+
+def _checked_shapes(model, *inputs):
+    """The shape set of get_action's (obs, cp_obs, cp_act, cem_init_mean, cem_init_var), checked once per set (the reference would raise a
+    TF shape error; raw device pointers would not).  A function of the model: the CPU tests of get_action run it on a stand-in object."""
+    sig = tuple(None if x is None else tuple(np.shape(x)) for x in inputs)
+    if sig != model._checked_sig:
+        model._check_planner_inputs(*inputs)
+        model._checked_sig = sig
+    return sig
 
 
 class MLPEnsembleCEMDynamicsModel(object):
@@ -220,55 +231,12 @@ class MLPEnsembleCEMDynamicsModel(object):
         if n_particles % ensemble_size != 0:
             raise ValueError("n_particles must be a multiple of ensemble_size (core/utils.py:447 int(p/E))")
 
-        # the iCEM planner's switches: all at their defaults = the reference's CEM (`_icem` stays None and get_action never looks further)
-        self._icem = None
-        self._icem_update = "cem"
-        self._score = None              # (mode name, kappa, k) of a risk-aware score; None: the particle mean
-        if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
-                bool(cem_temperature_relative), cem_score, cem_risk) != (0.0, 0, 1.0, "mean", False, "cem", 1.0, False, "mean", None):
-            if not use_cem:
-                raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
-                                 "cem_score / cem_risk configure the CEM planner: they need use_cem=True")
-            if cem_score not in ("mean", "mean_std", "member_std", "cvar"):
-                raise ValueError("cem_score must be 'mean', 'mean_std', 'member_std' or 'cvar', got %r" % (cem_score,))
-            if cem_score == "mean":
-                if cem_risk is not None:
-                    raise ValueError("cem_risk configures a risk-aware score: it needs cem_score='mean_std', 'member_std' or 'cvar'")
-            else:
-                if cem_risk is None or not np.isfinite(float(cem_risk)):
-                    raise ValueError("cem_score=%r needs a finite cem_risk, got %r" % (cem_score, cem_risk))
-                if cem_score == "cvar":
-                    if not 0.0 < float(cem_risk) <= 1.0:
-                        raise ValueError("cem_score='cvar': cem_risk is the tail fraction, in (0, 1]; got %r" % (cem_risk,))
-                    self._score = ("cvar", 0.0, HipEngine.cvar_k(cem_risk, n_particles))
-                else:
-                    self._score = (cem_score, float(cem_risk), None)
-            if cem_update not in ("cem", "mppi"):
-                raise ValueError("cem_update must be 'cem' or 'mppi', got %r" % (cem_update,))
-            if not (np.isfinite(float(cem_temperature)) and float(cem_temperature) > 0.0):
-                raise ValueError("cem_temperature must be finite and > 0, got %r" % (cem_temperature,))
-            if cem_update == "cem" and (float(cem_temperature) != 1.0 or bool(cem_temperature_relative)):
-                raise ValueError("cem_temperature / cem_temperature_relative configure the MPPI update: they need cem_update='mppi'")
-            if cem_return not in ("mean", "best"):
-                raise ValueError("cem_return must be 'mean' or 'best', got %r" % (cem_return,))
-            if not 0.0 <= float(cem_noise_beta) <= 16.0:
-                raise ValueError("cem_noise_beta must lie in [0, 16], got %r" % (cem_noise_beta,))
-            if not float(cem_decay) >= 1.0:
-                raise ValueError("cem_decay must be >= 1, got %r" % (cem_decay,))
-            if int(cem_keep_elites) < 0:
-                raise ValueError("cem_keep_elites must be >= 0, got %r" % (cem_keep_elites,))
-            if self.discrete:
-                raise NotImplementedError("the iCEM planner (cem_* kwargs) plans continuous actions only; this env's action space is discrete")
-            if process_group is not None:
-                import torch.distributed as dist
-                if dist.get_world_size(process_group) > 1:
-                    raise NotImplementedError("the iCEM planner (cem_* kwargs) does not shard candidates over a process group of more than "
-                                              "one rank: carried elites cannot be regenerated by id")
-            self._icem = dict(noise_beta=float(cem_noise_beta), keep_elites=int(cem_keep_elites), decay=float(cem_decay),
-                              return_best=cem_return == "best", add_mean_last=bool(cem_add_mean))
-            self._icem_update = cem_update
-            self._mppi = dict(temperature=float(cem_temperature), relative=bool(cem_temperature_relative))
-        self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (iCEM, keep_elites > 0)
+        # the opt-in planner's switches (planner.PlanOptions), checked before the engine is built; None, every cem_* kwarg at its default:
+        # the reference's CEM, and get_action never looks further
+        self._opt = _planner.PlanOptions.from_kwargs(cem_noise_beta, cem_keep_elites, cem_decay, cem_return, cem_add_mean, cem_update,
+                                                     cem_temperature, cem_temperature_relative, cem_score, cem_risk, use_cem=use_cem,
+                                                     discrete=self.discrete, process_group=process_group, n_particles=n_particles)
+        self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
 
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
@@ -296,14 +264,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         # (`--hidden_size`, `--context_out_dim`, depth, nonlinearity) is built now (cadm_amd.jit, ~30 s once, then cached),
         # and a launch that cannot fit the hardware (LDS for this horizon) raises here -- not at the first get_action.
         self.engine.ensure_rollout(None, 1, max(1, n_candidates))
-        if self._icem is not None:
-            if self._icem["keep_elites"] > self.engine.num_elites:
-                raise ValueError("cem_keep_elites=%d exceeds the planner's %d elites" % (self._icem["keep_elites"], self.engine.num_elites))
-            if self._icem_update == "mppi":
-                self._icem_params = HipEngine.mppi_params(**self._mppi, **self._icem)
-            else:
-                self._icem_params = HipEngine.icem_params(**self._icem)
-            self._score_params = None if self._score is None else HipEngine.score_params(*self._score)
+        if self._opt is not None and self._opt.keep_elites > self.engine.num_elites:
+            raise ValueError("cem_keep_elites=%d exceeds the planner's %d elites" % (self._opt.keep_elites, self.engine.num_elites))
 
     # ------------------------------------------------------------------ planning
     def _push_stats(self):
@@ -386,8 +348,8 @@ class MLPEnsembleCEMDynamicsModel(object):
             return self._get_action_with_forecast(obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
         if self._stats_dirty:
             self._push_stats()
-        if getattr(self, "_icem", None) is not None and cem_init_mean is not None:      # the opt-in iCEM planner; None: today's route
-            return self._get_action_icem(obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
+        if getattr(self, "_opt", None) is not None and cem_init_mean is not None:      # the opt-in planner; None (or a CPU test's stand-in object): today's route
+            return self._get_action_opt_in(obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
         nd = np.ndarray
         counted = False
         if (type(obs) is nd and type(cem_init_mean) is nd and type(cem_init_var) is nd and (cp_obs is None or type(cp_obs) is nd)
@@ -411,11 +373,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                 return np.zeros((0, self.n_forwards, self.action_space_dims), np.float32)
             return np.zeros((0,), np.int32) if self.discrete else np.zeros((0, self.action_space_dims), np.float32)
         host_in = not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
-        # shape checks once per shape set (the reference would raise a TF shape error; raw device pointers would not)
-        sig = tuple(None if x is None else tuple(np.shape(x)) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
-        if sig != self._checked_sig:
-            self._check_planner_inputs(obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
-            self._checked_sig = sig
+        sig = _checked_shapes(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
         call = self._next_call()
         shard, fused = self._sharding()
         check_due = shard.world > 1 and self._replication_check_due(peek=counted)
@@ -445,25 +403,11 @@ class MLPEnsembleCEMDynamicsModel(object):
             action = np.minimum(np.maximum(action, -1.0), 1.0)
         return action
 
-    def _plan_opt_in(self, *args, **kw):
-        """The opt-in loop's entry point for this model's switches: `cadm_icem_plan`, `cadm_mppi_plan` (cem_update="mppi"), or
-        `cadm_scored_plan` with either update (a non-default cem_score).  Arguments as `HipEngine.icem_plan` behind its params."""
-        eng = self.engine
-        if getattr(self, "_score_params", None) is not None:
-            return eng.scored_plan(self._score_params, self._icem_params, *args, **kw)
-        return (eng.mppi_plan if self._icem_update == "mppi" else eng.icem_plan)(self._icem_params, *args, **kw)
-
-    def _get_action_icem(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
-        """The opt-in iCEM route of get_action: one `cadm_icem_plan` call (`cadm_mppi_plan` with cem_update="mppi", `cadm_scored_plan` with
-        a non-default cem_score); the elites it keeps for the next call stay on the device."""
-        m = int(np.shape(obs)[0])
-        if m == 0:
-            return np.zeros((0, self.n_forwards, self.action_space_dims), np.float32)
-        sig = tuple(None if x is None else tuple(np.shape(x)) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
-        if sig != self._checked_sig:
-            self._check_planner_inputs(obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
-            self._checked_sig = sig
-        eng, K = self.engine, self._icem["keep_elites"]
+    def _plan_opt_in(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, out=None):
+        """One planned call of the opt-in loop under this model's switches (`HipEngine.opt_in_plan`: `cadm_icem_plan`, `cadm_mppi_plan` with
+        cem_update="mppi", `cadm_scored_plan` with a non-default cem_score), for get_action and caller.DevicePlannerState alike: the elites
+        it keeps for the next call stay on the device, here; it draws the call number."""
+        eng, K, m = self.engine, self._opt.keep_elites, int(np.shape(obs)[0])
         if K > 0 and (self._plan_carry is None or self._plan_carry.shape[0] != m):      # first call, or another number of envs: nothing carried
             self._plan_carry = torch.zeros((m, K, self.n_forwards, self.action_space_dims), dtype=torch.float32, device=eng.device)
             self._plan_carry_valid = torch.zeros((m,), dtype=torch.int32, device=eng.device)
@@ -472,10 +416,18 @@ class MLPEnsembleCEMDynamicsModel(object):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
         if self.context_out_dim == 0:
             cp_obs = cp_act = None
-        host = eng.host_out((m, self.n_forwards, self.action_space_dims))
-        self._plan_opt_in(obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
-                          carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=host)
-        torch.cuda.current_stream(eng.device).synchronize()
+        return eng.opt_in_plan(self._opt, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
+                               carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=out)
+
+    def _get_action_opt_in(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
+        """The opt-in route of get_action: `_plan_opt_in` into the pinned host buffer."""
+        m = int(np.shape(obs)[0])
+        if m == 0:
+            return np.zeros((0, self.n_forwards, self.action_space_dims), np.float32)
+        _checked_shapes(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var)
+        host = self.engine.host_out((m, self.n_forwards, self.action_space_dims))
+        self._plan_opt_in(obs, cp_obs, cp_act, cem_init_mean, cem_init_var, out=host)
+        torch.cuda.current_stream(self.engine.device).synchronize()
         return host.numpy().copy()
 
     # ------------------------------------------------------------------ forecast of a plan (INTEGRATION.md "Forecasting a plan")
@@ -541,7 +493,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         """Forget the elites the iCEM planner carries from one get_action to the next (`cem_keep_elites` > 0): for every env, or for
         those where `mask` [m] is set -- at an episode boundary, so that a new episode never starts from the previous one's plans.
         A no-op for a model that carries nothing."""
-        if getattr(self, "_plan_carry_valid", None) is None:
+        if self._plan_carry_valid is None:
             return
         if mask is None:
             self._plan_carry_valid.zero_()
@@ -601,7 +553,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         if rolling_average_persitency is None:
             rolling_average_persitency = self.rolling_average_persitency
         assert 1 > valid_split_ratio >= 0
-        if getattr(self, "_plan_carry_valid", None) is not None:      # elites planned under the old weights
+        if getattr(self, "_plan_carry_valid", None) is not None:      # elites planned under the old weights (getattr: the CPU tests' fit on a bare object)
             self._plan_carry_valid.zero_()
         injected = index_stream is not None
         if index_stream is None:

@@ -17,11 +17,12 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
                  output_nonlinearity=None, batch_size=128, learning_rate=0.001, normalize_input=True,
                  optimizer=None, valid_split_ratio=0.2, rolling_average_persitency=0.99, n_forwards=30,
                  n_candidates=2500, ensemble_size=5, n_particles=20, use_cem=False, deterministic=False,
-                 weight_decays=(0., 0., 0., 0., 0.), weight_decay_coeff=0.0,
-                 reference_quirks=True, seed=0, device=None, process_group=None, check_replicated_calls=2,
-                 check_replicated_every=256, cem_noise_beta=0.0, cem_keep_elites=0, cem_decay=1.0, cem_return="mean",
-                 cem_add_mean=False, cem_update="cem", cem_temperature=1.0, cem_temperature_relative=False, cem_score="mean",
-                 cem_risk=None, engine_lib=None):
+                 weight_decays=(0., 0., 0., 0., 0.), weight_decay_coeff=0.0, **extensions):
+        """The reference's own kwargs (:25-45); `extensions`: the CaDM class's, checked by its signature -- but its context kwargs."""
+        for kw in ("cp_hidden_sizes", "context_weight_decays", "context_out_dim", "context_hidden_nonlinearity", "history_length",
+                   "future_length", "state_diff", "back_coeff"):
+            if kw in extensions:
+                raise TypeError("__init__() got an unexpected keyword argument %r" % kw)
         super().__init__(name, env, hidden_sizes=hidden_sizes, hidden_nonlinearity=hidden_nonlinearity,
                          output_nonlinearity=output_nonlinearity, batch_size=batch_size, learning_rate=learning_rate,
                          normalize_input=normalize_input, optimizer=optimizer, valid_split_ratio=valid_split_ratio,
@@ -29,12 +30,7 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
                          n_candidates=n_candidates, ensemble_size=ensemble_size, n_particles=n_particles,
                          use_cem=use_cem, deterministic=deterministic, weight_decays=weight_decays,
                          weight_decay_coeff=weight_decay_coeff, cp_hidden_sizes=(), context_weight_decays=(),
-                         context_out_dim=0, history_length=0, future_length=1, state_diff=False, back_coeff=0.0,
-                         reference_quirks=reference_quirks, seed=seed, device=device, process_group=process_group,
-                         check_replicated_calls=check_replicated_calls, check_replicated_every=check_replicated_every,
-                         cem_noise_beta=cem_noise_beta, cem_keep_elites=cem_keep_elites, cem_decay=cem_decay, cem_return=cem_return,
-                         cem_add_mean=cem_add_mean, cem_update=cem_update, cem_temperature=cem_temperature,
-                         cem_temperature_relative=cem_temperature_relative, cem_score=cem_score, cem_risk=cem_risk, engine_lib=engine_lib)
+                         context_out_dim=0, history_length=0, future_length=1, state_diff=False, back_coeff=0.0, **extensions)
 
     def get_action(self, obs, cem_init_mean=None, cem_init_var=None, return_forecast=False):
         if return_forecast:

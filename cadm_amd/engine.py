@@ -125,6 +125,7 @@ class HipEngine:
         self._ws = None
         self._ws_key = None
         self._host_plan = None
+        self._loop_ws = {}          # the opt-in loop's workspaces: mppi (bool) -> ((m, n, K), tensor)
         self._train_B = 0
         self.dist_world, self.dist_rank = 1, 0
 
@@ -555,32 +556,44 @@ class HipEngine:
                   want_best_return=False):
         """`cadm_icem_plan`.  carry [m,K,H,A] float32 / carry_valid [m] int32: caller-owned device tensors, read at iteration 0 and
         rewritten after the last refit (required when params.keep_elites > 0).  `out` as in `cem_plan`."""
+        return self._loop_plan("icem_plan", self.lib.cadm_icem_plan, (ct.byref(params),), False, params.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
+
+    def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
+                   want_best_return):
+        """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
+        `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
-        m, K = obs.shape[0], int(params.keep_elites)
+        m, K = obs.shape[0], int(K)
         if K > 0 and (carry is None or carry_valid is None or tuple(carry.shape) != (m, K, self.H, self.A) or carry.dtype != torch.float32
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
-            raise ValueError("icem_plan: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (K, m, K, self.H, self.A, m))
+            raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(False, m, n, K)
+        ws = self._loop_workspace(mppi, m, n, K)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
-        self._check(self.lib.cadm_icem_plan(self._ctx, ct.byref(params), ptr(obs), ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var),
-                                            ptr(carry), ptr(carry_valid), m, n, seed, call, ptr(ws), ptr(out), ptr(best),
-                                            self.stream), "cadm_icem_plan")
+        self._check(export(self._ctx, *head, ptr(obs), ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var), ptr(carry), ptr(carry_valid),
+                           m, n, seed, call, ptr(ws), ptr(out), ptr(best), self.stream), "cadm_" + who)
         return (out, best) if want_best_return else out
+
+    def opt_in_plan(self, opt, *args, **kw):
+        """The opt-in loop under a `planner.PlanOptions`: `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
+        Arguments as `icem_plan` behind its params."""
+        if opt.score_params is not None:
+            return self.scored_plan(opt.score_params, opt.params, *args, **kw)
+        return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
     def _loop_workspace(self, mppi, m, n, K):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update."""
-        name = "_mppi_ws" if mppi else "_icem_ws"
-        key = ("mppi" if mppi else "icem", m, n, K)
-        if getattr(self, name + "_key", None) != key:
+        key, ws = self._loop_ws.get(bool(mppi), (None, None))
+        if key != (m, n, K):
             nbytes = (self.lib.cadm_mppi_workspace_bytes if mppi else self.lib.cadm_icem_workspace_bytes)(self._ctx, m, n, K)
-            setattr(self, name, torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device))
-            setattr(self, name + "_key", key)
-        return getattr(self, name)
+            ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
+            self._loop_ws[bool(mppi)] = ((m, n, K), ws)
+        return ws
 
     # ------------------------------------------------------------------ MPPI update (opt-in; csrc/mppi.hip)
     def mppi_refit(self, cand, actions, mean, var, temperature=1.0, relative=False, want_plan=False):
@@ -607,22 +620,8 @@ class HipEngine:
     def mppi_plan(self, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
                   want_best_return=False):
         """`cadm_mppi_plan`: the loop of `icem_plan` with the MPPI update in place of the elite refit.  Arguments as `icem_plan`."""
-        obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
-        cp_obs = None if cp_obs is None else self._t(cp_obs)
-        cp_act = None if cp_act is None else self._t(cp_act)
-        m, K = obs.shape[0], int(params.icem.keep_elites)
-        if K > 0 and (carry is None or carry_valid is None or tuple(carry.shape) != (m, K, self.H, self.A) or carry.dtype != torch.float32
-                      or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
-            raise ValueError("mppi_plan: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (K, m, K, self.H, self.A, m))
-        self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(True, m, n, K)
-        if out is None:
-            out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
-        best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
-        self._check(self.lib.cadm_mppi_plan(self._ctx, ct.byref(params), ptr(obs), ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var),
-                                            ptr(carry), ptr(carry_valid), m, n, seed, call, ptr(ws), ptr(out), ptr(best),
-                                            self.stream), "cadm_mppi_plan")
-        return (out, best) if want_best_return else out
+        return self._loop_plan("mppi_plan", self.lib.cadm_mppi_plan, (ct.byref(params),), True, params.icem.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ risk-aware candidate scores (opt-in; csrc/score.hip)
     @staticmethod
@@ -662,22 +661,9 @@ class HipEngine:
             full = _lib.MppiParams()
             full.icem, full.temperature = params, 1.0
             params = full
-        obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
-        cp_obs = None if cp_obs is None else self._t(cp_obs)
-        cp_act = None if cp_act is None else self._t(cp_act)
-        m, K = obs.shape[0], int(params.icem.keep_elites)
-        if K > 0 and (carry is None or carry_valid is None or tuple(carry.shape) != (m, K, self.H, self.A) or carry.dtype != torch.float32
-                      or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
-            raise ValueError("scored_plan: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (K, m, K, self.H, self.A, m))
-        self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K)
-        if out is None:
-            out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
-        best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
-        self._check(self.lib.cadm_scored_plan(self._ctx, None if score is None else ct.byref(score), int(mppi), ct.byref(params), ptr(obs),
-                                              ptr(cp_obs), ptr(cp_act), ptr(init_mean), ptr(init_var), ptr(carry), ptr(carry_valid), m, n,
-                                              seed, call, ptr(ws), ptr(out), ptr(best), self.stream), "cadm_scored_plan")
-        return (out, best) if want_best_return else out
+        head = (None if score is None else ct.byref(score), int(mppi), ct.byref(params))
+        return self._loop_plan("scored_plan", self.lib.cadm_scored_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D):

@@ -11,12 +11,81 @@ checks -- an all-gather this module supplies over any torch.distributed backend 
 What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
+  * `PlanOptions`: what a model's `cem_*` kwargs mean -- their checks, the switches, and the ctypes structs `HipEngine.opt_in_plan` hands to the library;
   * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
 """
+import collections
+
+import numpy as np
 import torch
+
+from .engine import HipEngine
+
+
+class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
+                                                       "params score_params")):
+    """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
+    `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
+    `score`: None, or (mode name, kappa, k)."""
+    __slots__ = ()
+
+    @staticmethod
+    def from_kwargs(cem_noise_beta=0.0, cem_keep_elites=0, cem_decay=1.0, cem_return="mean", cem_add_mean=False, cem_update="cem",
+                    cem_temperature=1.0, cem_temperature_relative=False, cem_score="mean", cem_risk=None, use_cem=False, discrete=False,
+                    process_group=None, n_particles=20):
+        """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
+        everything that needs no engine -- and folded into a `PlanOptions`."""
+        if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
+                bool(cem_temperature_relative), cem_score, cem_risk) == (0.0, 0, 1.0, "mean", False, "cem", 1.0, False, "mean", None):
+            return None
+        if not use_cem:
+            raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
+                             "cem_score / cem_risk configure the CEM planner: they need use_cem=True")
+        score = None
+        if cem_score not in ("mean", "mean_std", "member_std", "cvar"):
+            raise ValueError("cem_score must be 'mean', 'mean_std', 'member_std' or 'cvar', got %r" % (cem_score,))
+        if cem_score == "mean":
+            if cem_risk is not None:
+                raise ValueError("cem_risk configures a risk-aware score: it needs cem_score='mean_std', 'member_std' or 'cvar'")
+        else:
+            if cem_risk is None or not np.isfinite(float(cem_risk)):
+                raise ValueError("cem_score=%r needs a finite cem_risk, got %r" % (cem_score, cem_risk))
+            if cem_score == "cvar":
+                if not 0.0 < float(cem_risk) <= 1.0:
+                    raise ValueError("cem_score='cvar': cem_risk is the tail fraction, in (0, 1]; got %r" % (cem_risk,))
+                score = ("cvar", 0.0, HipEngine.cvar_k(cem_risk, n_particles))
+            else:
+                score = (cem_score, float(cem_risk), None)
+        if cem_update not in ("cem", "mppi"):
+            raise ValueError("cem_update must be 'cem' or 'mppi', got %r" % (cem_update,))
+        if not (np.isfinite(float(cem_temperature)) and float(cem_temperature) > 0.0):
+            raise ValueError("cem_temperature must be finite and > 0, got %r" % (cem_temperature,))
+        if cem_update == "cem" and (float(cem_temperature) != 1.0 or bool(cem_temperature_relative)):
+            raise ValueError("cem_temperature / cem_temperature_relative configure the MPPI update: they need cem_update='mppi'")
+        if cem_return not in ("mean", "best"):
+            raise ValueError("cem_return must be 'mean' or 'best', got %r" % (cem_return,))
+        if not 0.0 <= float(cem_noise_beta) <= 16.0:
+            raise ValueError("cem_noise_beta must lie in [0, 16], got %r" % (cem_noise_beta,))
+        if not float(cem_decay) >= 1.0:
+            raise ValueError("cem_decay must be >= 1, got %r" % (cem_decay,))
+        if int(cem_keep_elites) < 0:
+            raise ValueError("cem_keep_elites must be >= 0, got %r" % (cem_keep_elites,))
+        if discrete:
+            raise NotImplementedError("the iCEM planner (cem_* kwargs) plans continuous actions only; this env's action space is discrete")
+        if process_group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(process_group) > 1:
+                raise NotImplementedError("the iCEM planner (cem_* kwargs) does not shard candidates over a process group of more than "
+                                          "one rank: carried elites cannot be regenerated by id")
+        icem = dict(noise_beta=float(cem_noise_beta), keep_elites=int(cem_keep_elites), decay=float(cem_decay), return_best=cem_return == "best",
+                    add_mean_last=bool(cem_add_mean))
+        mppi = dict(temperature=float(cem_temperature), relative=bool(cem_temperature_relative))
+        params = HipEngine.mppi_params(**mppi, **icem) if cem_update == "mppi" else HipEngine.icem_params(**icem)
+        return PlanOptions(update=cem_update, score=score, params=params, score_params=None if score is None else HipEngine.score_params(*score),
+                           **mppi, **icem)
 
 
 class Shard:

@@ -1,4 +1,6 @@
 """Shared helpers for the test-suite (tests may import both the product and the oracle)."""
+import functools
+
 import numpy as np
 
 from cadm_amd import synth
@@ -148,6 +150,53 @@ FLAVOURS = ("1", "2", "3", "4")      # cooperative kernel with one / two row til
 
 def _np(t):
     return t.detach().cpu().numpy()
+
+
+# the opt-in planner: what tests/test_gpu_icem.py, tests/test_gpu_mppi.py and tests/test_gpu_risk.py share
+@functools.lru_cache(maxsize=None)
+def planner_engine(H, context=False, p=5, env="halfcheetah"):
+    """(problem, engine), cached: hidden (32,) * 4, ensemble 5, m = 2, num_elites = 8, 3 CEM iterations."""
+    prob = synth.make_problem(env=env, context=context, E=5, m=2, H=H, seed=3, hidden_sizes=(32,) * 4, trained_like=env == "halfcheetah")
+    return prob, make_engine(prob, p=p, num_elites=8, num_cem_iters=3)
+
+
+def plan_model(context, H, hidden=(32,) * 4, n_candidates=64, n_particles=5, m=2, **kw):
+    """(model, problem): a CaDM (context) or vanilla model with a synthetic halfcheetah problem's weights and statistics; kw: more kwargs."""
+    from cadm_amd.dynamics.mlp_cadm_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as CaDMModel
+    from cadm_amd.dynamics.mlp_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as VanillaModel
+    from cadm_amd.envs import make_env_spec
+    env = kw.pop("env", None) or make_env_spec("halfcheetah")
+    base = dict(name="dyn", env=env, hidden_sizes=hidden, hidden_nonlinearity="swish", n_forwards=H, n_candidates=n_candidates, ensemble_size=5,
+                n_particles=n_particles, use_cem=True, normalize_input=True, seed=7)
+    base.update(kw)
+    prob = synth.make_problem(env="halfcheetah", context=context, E=5, m=m, H=H, seed=9, hidden_sizes=hidden, trained_like=True)
+    st = prob["stats"]
+    if context:
+        model = CaDMModel(**base)
+        model.engine.set_net("context_model", prob["cp"])
+    else:
+        model = VanillaModel(**base)
+    model.engine.set_net("ff_model", prob["ff"])
+    nz = {"obs": (st["obs_mean"], st["obs_std"]), "delta": (st["delta_mean"], st["delta_std"]), "act": (st["act_mean"], st["act_std"])}
+    if context:
+        nz.update({"cp_obs": (st["cp_obs_mean"], st["cp_obs_std"]), "cp_act": (st["cp_act_mean"], st["cp_act_std"]),
+                   "back_delta": (st["back_delta_mean"], st["back_delta_std"])})
+    model.set_normalization(nz)
+    return model, prob
+
+
+def plan_act(model, prob, context, mean, var):
+    if context:
+        return model.get_action(prob["obs"], prob["cp_obs"], prob["cp_act"], mean, var)
+    return model.get_action(prob["obs"], mean, var)
+
+
+def zero_carry(eng, m, K, H):
+    """(carry [m,K,H,A] float32, carry_valid [m] int32) of a planner that has carried nothing yet; (None, None) for K = 0."""
+    import torch
+    if K == 0:
+        return None, None
+    return torch.zeros((m, K, H, eng.A), dtype=torch.float32, device=eng.device), torch.zeros((m,), dtype=torch.int32, device=eng.device)
 
 
 def spec_oracle(prob, spec, dt=np.float32):

@@ -14,16 +14,14 @@ from cadm_amd import _lib
 from cadm_amd import planner as hplanner
 from cadm_amd import synth
 from cadm_amd.engine import HipEngine
-from helpers import assert_close, make_engine
+from helpers import _np, assert_close, make_engine, zero_carry
+from helpers import plan_act as _act
+from helpers import plan_model as _model
 
 pytestmark = pytest.mark.gpu
 
 HID = (32,) * 4
 M, N, KE, K, ITERS, A = 2, 64, 8, 3, 3, 6
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def _engine(H, context=True, seed=3, **kw):
@@ -263,7 +261,7 @@ def test_fused_equals_stepwise(gpu, H, context, beta, decay, best, addmean):
     prob, eng = _engine(H, context=context)
     prm = HipEngine.icem_params(noise_beta=beta, keep_elites=K, decay=decay, return_best=best, add_mean_last=addmean)
     args = (prob["obs"], prob["cp_obs"], prob["cp_act"])
-    z = lambda: (torch.zeros((M, K, H, A), dtype=torch.float32, device=eng.device), torch.zeros((M,), dtype=torch.int32, device=eng.device))
+    z = lambda: zero_carry(eng, M, K, H)
     (ca, va), (cb, vb) = z(), z()
     mean, var = prob["init_mean"], prob["init_var"]
     plans = []
@@ -288,36 +286,6 @@ def test_fused_equals_stepwise(gpu, H, context, beta, decay, best, addmean):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 6
-def _model(context, H, **kw):
-    from cadm_amd.dynamics.mlp_cadm_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as CaDMModel
-    from cadm_amd.dynamics.mlp_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as VanillaModel
-    from cadm_amd.envs import make_env_spec
-    env = kw.pop("env", None) or make_env_spec("halfcheetah")
-    base = dict(name="dyn", env=env, hidden_sizes=HID, hidden_nonlinearity="swish", n_forwards=H, n_candidates=N, ensemble_size=5,
-                n_particles=5, use_cem=True, normalize_input=True, seed=7)
-    base.update(kw)
-    prob = synth.make_problem(env="halfcheetah", context=context, E=5, m=M, H=H, seed=9, hidden_sizes=HID, trained_like=True)
-    st = prob["stats"]
-    if context:
-        model = CaDMModel(**base)
-        model.engine.set_net("context_model", prob["cp"])
-    else:
-        model = VanillaModel(**base)
-    model.engine.set_net("ff_model", prob["ff"])
-    nz = {"obs": (st["obs_mean"], st["obs_std"]), "delta": (st["delta_mean"], st["delta_std"]), "act": (st["act_mean"], st["act_std"])}
-    if context:
-        nz.update({"cp_obs": (st["cp_obs_mean"], st["cp_obs_std"]), "cp_act": (st["cp_act_mean"], st["cp_act_std"]),
-                   "back_delta": (st["back_delta_mean"], st["back_delta_std"])})
-    model.set_normalization(nz)
-    return model, prob
-
-
-def _act(model, prob, context, mean, var):
-    if context:
-        return model.get_action(prob["obs"], prob["cp_obs"], prob["cp_act"], mean, var)
-    return model.get_action(prob["obs"], mean, var)
-
-
 @pytest.mark.parametrize("context", [False, True], ids=["vanilla", "cadm"])
 def test_default_kwargs_take_the_untouched_route(gpu, context):
     """All-default kwargs and the same kwargs spelled out at their defaults: bit-identical get_action results over three calls, and
@@ -325,7 +293,7 @@ def test_default_kwargs_take_the_untouched_route(gpu, context):
     H = 5
     a, prob = _model(context, H)
     b, _ = _model(context, H, cem_noise_beta=0.0, cem_keep_elites=0, cem_decay=1.0, cem_return="mean", cem_add_mean=False)
-    assert a._icem is None and b._icem is None
+    assert a._opt is None and b._opt is None
     mean, var = np.zeros((M, H, A)), np.full((M, H, A), 0.25)
     for _ in range(3):
         pa, pb = _act(a, prob, context, mean, var), _act(b, prob, context, mean, var)
@@ -429,6 +397,31 @@ def test_warm_start_resets_reach_the_carry(gpu):
     np.testing.assert_array_equal(_np(model._plan_carry_valid), [0, 1])
     state.reset()
     np.testing.assert_array_equal(_np(model._plan_carry_valid), [0, 0])
+
+
+def test_device_planner_state_on_another_number_of_envs(gpu):
+    """get_action with m = 2, then DevicePlannerState(model, 3).act: the model's carry is reallocated for 3 envs, all invalid when the plan
+    starts -- the action is the first step of `icem_plan` from a zero carry under call 2 -- and the two calls moved the counter by 2."""
+    from cadm_amd.caller import DevicePlannerState
+    H = 5
+    model, prob = _model(True, H, cem_keep_elites=K)
+    eng = model.engine
+    _act(model, prob, True, np.zeros((M, H, A)), np.full((M, H, A), 0.25))
+    assert model._call == 1 and tuple(model._plan_carry.shape) == (M, K, H, A) and _np(model._plan_carry_valid).tolist() == [1, 1]
+    state, seen, real = DevicePlannerState(model, 3), {}, eng.opt_in_plan
+
+    def spy(opt, *a, **kw):
+        seen.update(shape=tuple(kw["carry"].shape), valid=_np(kw["carry_valid"]).copy(), call=kw["call"])
+        return real(opt, *a, **kw)
+    eng.opt_in_plan = spy
+    obs = np.concatenate([prob["obs"], prob["obs"][:1] + np.float32(0.1)])
+    a = state.act(obs)
+    assert seen["shape"] == (3, K, H, A) and seen["valid"].tolist() == [0, 0, 0] and seen["call"] == 2 and model._call == 2
+    np.testing.assert_array_equal(_np(model._plan_carry_valid), [1, 1, 1])
+    zero = torch.zeros((3, H, A), dtype=torch.float32, device=eng.device)
+    want = eng.icem_plan(model._opt.params, obs, torch.zeros_like(state.hist_obs), torch.zeros_like(state.hist_act), zero, state.init_var, N,
+                         *zero_carry(eng, 3, K, H), seed=model.seed, call=2)
+    np.testing.assert_array_equal(_np(a), _np(want)[:, 0])
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 7

@@ -6,7 +6,6 @@ iterations, H = 5 (H A = 30: scalar loads) and H = 6 (H A = 36: 16-byte loads). 
 The bars against float64 are the project's: the mean within 1e-5 absolute, the variance within 1e-5 of its largest element.  The kernel's
 header states a rounding chain of 2 (15 + ceil(n / 64)) + 4 = 68 roundings at n = 1030; 68 x 2^-24 + 30 x 2^-23 = 7.6e-6 < 1e-5."""
 import ctypes as ct
-import functools
 
 import numpy as np
 import pytest
@@ -17,7 +16,10 @@ from cadm_amd import _lib
 from cadm_amd import planner as hplanner
 from cadm_amd import synth
 from cadm_amd.engine import HipEngine
-from helpers import make_engine
+from helpers import _np, make_engine, zero_carry
+from helpers import plan_act as _act
+from helpers import plan_model as _model
+from helpers import planner_engine as _engine
 
 pytestmark = pytest.mark.gpu
 
@@ -25,16 +27,6 @@ HID = (32,) * 4
 M, N, KE, K, ITERS, A = 2, 64, 8, 3, 3, 6
 BAR = 1e-5
 assert (2 * (15 + (1030 + 63) // 64) + 4) * 2.0 ** -24 + 30 * 2.0 ** -23 < BAR      # the chain of csrc/mppi.hip's header at n = 1030
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-@functools.lru_cache(maxsize=None)
-def _engine(H, context=False, env="halfcheetah"):
-    prob = synth.make_problem(env=env, context=context, E=5, m=M, H=H, seed=3, hidden_sizes=HID, trained_like=env == "halfcheetah")
-    return prob, make_engine(prob, p=5, num_elites=KE, num_cem_iters=ITERS)
 
 
 def _refit_data(H, n, seed):
@@ -204,12 +196,7 @@ def test_fused_equals_stepwise(gpu, H, context, beta, decay, keep, best, addmean
     prm = HipEngine.mppi_params(temperature=lam, relative=relative, noise_beta=beta, keep_elites=keep, decay=decay, return_best=best,
                                 add_mean_last=addmean)
     args = (prob["obs"], prob["cp_obs"], prob["cp_act"])
-
-    def zero_carry():
-        if keep == 0:
-            return None, None
-        return (torch.zeros((M, keep, H, A), dtype=torch.float32, device=eng.device), torch.zeros((M,), dtype=torch.int32, device=eng.device))
-    (ca, va), (cb, vb) = zero_carry(), zero_carry()
+    (ca, va), (cb, vb) = zero_carry(eng, M, keep, H), zero_carry(eng, M, keep, H)
     mean, var = prob["init_mean"], prob["init_var"]
     alpha = float(np.float32(eng.cfg.alpha))
     for call in (1, 2):
@@ -239,43 +226,13 @@ def test_fused_equals_stepwise(gpu, H, context, beta, decay, keep, best, addmean
             np.testing.assert_array_equal(a, np.clip(_np(info[-1]["mean"]), -1.0, 1.0))
         mean = np.concatenate([a[:, 1:], np.zeros((M, 1, A), np.float32)], axis=1)      # the samplers' warm start
     if keep and not best:      # the carry is consumed: the same call without it refits another mean
-        cc, vc = zero_carry()
+        cc, vc = zero_carry(eng, M, keep, H)
         c = _np(eng.mppi_plan(prm, *args, mean, var, n, carry=cc, carry_valid=vc, seed=4, call=3))
         d = _np(eng.mppi_plan(prm, *args, mean, var, n, carry=ca.clone(), carry_valid=va.clone(), seed=4, call=3))
         assert not np.array_equal(c, d)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 4
-def _model(context, H, **kw):
-    from cadm_amd.dynamics.mlp_cadm_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as CaDMModel
-    from cadm_amd.dynamics.mlp_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as VanillaModel
-    from cadm_amd.envs import make_env_spec
-    env = kw.pop("env", None) or make_env_spec("halfcheetah")
-    base = dict(name="dyn", env=env, hidden_sizes=HID, hidden_nonlinearity="swish", n_forwards=H, n_candidates=N, ensemble_size=5,
-                n_particles=5, use_cem=True, normalize_input=True, seed=7)
-    base.update(kw)
-    prob = synth.make_problem(env="halfcheetah", context=context, E=5, m=M, H=H, seed=9, hidden_sizes=HID, trained_like=True)
-    st = prob["stats"]
-    if context:
-        model = CaDMModel(**base)
-        model.engine.set_net("context_model", prob["cp"])
-    else:
-        model = VanillaModel(**base)
-    model.engine.set_net("ff_model", prob["ff"])
-    nz = {"obs": (st["obs_mean"], st["obs_std"]), "delta": (st["delta_mean"], st["delta_std"]), "act": (st["act_mean"], st["act_std"])}
-    if context:
-        nz.update({"cp_obs": (st["cp_obs_mean"], st["cp_obs_std"]), "cp_act": (st["cp_act_mean"], st["cp_act_std"]),
-                   "back_delta": (st["back_delta_mean"], st["back_delta_std"])})
-    model.set_normalization(nz)
-    return model, prob
-
-
-def _act(model, prob, context, mean, var):
-    if context:
-        return model.get_action(prob["obs"], prob["cp_obs"], prob["cp_act"], mean, var)
-    return model.get_action(prob["obs"], mean, var)
-
-
 @pytest.mark.parametrize("context", [False, True], ids=["vanilla", "cadm"])
 def test_default_kwargs_take_the_untouched_route(gpu, context):
     """A model built without the new kwargs and one with them spelled out at their defaults: bit-identical get_action results over
@@ -283,7 +240,7 @@ def test_default_kwargs_take_the_untouched_route(gpu, context):
     H = 5
     a, prob = _model(context, H)
     b, _ = _model(context, H, cem_update="cem", cem_temperature=1.0, cem_temperature_relative=False)
-    assert a._icem is None and b._icem is None and a._icem_update == b._icem_update == "cem"
+    assert a._opt is None and b._opt is None
     mean, var = np.zeros((M, H, A)), np.full((M, H, A), 0.25)
     for _ in range(3):
         pa, pb = _act(a, prob, context, mean, var), _act(b, prob, context, mean, var)
@@ -305,7 +262,7 @@ def test_get_action_with_the_mppi_update(gpu, context):
     makes the next plan a fresh model's."""
     H = 6
     model, prob = _model(context, H, cem_update="mppi")
-    assert model._icem is not None and model._icem_update == "mppi" and model._plan_carry is None
+    assert model._opt is not None and model._opt.update == "mppi" and model._plan_carry is None
     eng = model.engine
     cp = (prob["cp_obs"], prob["cp_act"]) if context else (None, None)
     mean, var = np.zeros((M, H, A)), np.full((M, H, A), 0.25)
@@ -352,7 +309,7 @@ def test_device_planner_state_takes_the_mppi_route(gpu):
     assert tuple(a.shape) == (M, A) and np.isfinite(_np(a)).all() and np.abs(_np(a)).max() <= 1.0
     np.testing.assert_array_equal(_np(model._plan_carry_valid), [1, 1])
     zero = torch.zeros((M, H, A), dtype=torch.float32, device=model.engine.device)
-    want = model.engine.mppi_plan(model._icem_params, prob["obs"], torch.zeros_like(state.hist_obs), torch.zeros_like(state.hist_act), zero, state.init_var,
+    want = model.engine.mppi_plan(model._opt.params, prob["obs"], torch.zeros_like(state.hist_obs), torch.zeros_like(state.hist_act), zero, state.init_var,
                                   N, carry=torch.zeros_like(model._plan_carry), carry_valid=torch.zeros((M,), dtype=torch.int32, device=zero.device),
                                   seed=model.seed, call=1)
     np.testing.assert_array_equal(_np(a), _np(want)[:, 0])

@@ -20,7 +20,9 @@ from cadm_amd import _lib
 from cadm_amd import planner as hplanner
 from cadm_amd import synth
 from cadm_amd.engine import HipEngine
-from helpers import make_engine
+from helpers import _np, make_engine, plan_model, zero_carry
+from helpers import plan_act as _act
+from helpers import planner_engine as _engine
 
 pytestmark = pytest.mark.gpu
 
@@ -28,20 +30,11 @@ HID = (32,) * 4
 M, N, KE, K, ITERS, A, E = 2, 64, 8, 3, 3, 6, 5
 BAR = 1e-5
 EPS = 2.0 ** -24
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
+_model = functools.partial(plan_model, n_particles=10)
 
 
 def _bits(x):
     return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
-@functools.lru_cache(maxsize=None)
-def _engine(H, context=False, p=10, env="halfcheetah"):
-    prob = synth.make_problem(env=env, context=context, E=E, m=M, H=H, seed=3, hidden_sizes=HID, trained_like=env == "halfcheetah")
-    return prob, make_engine(prob, p=p, num_elites=KE, num_cem_iters=ITERS)
 
 
 def _rows(p, n, seed):
@@ -183,12 +176,7 @@ def test_fused_equals_stepwise(gpu, mode, kappa, k, update, context, H, beta, de
     icem = dict(noise_beta=beta, keep_elites=keep, decay=decay, return_best=best, add_mean_last=addmean)
     prm = _params(update, **icem)
     args = (prob["obs"], prob["cp_obs"], prob["cp_act"])
-
-    def zero_carry():
-        if keep == 0:
-            return None, None
-        return (torch.zeros((M, keep, H, A), dtype=torch.float32, device=eng.device), torch.zeros((M,), dtype=torch.int32, device=eng.device))
-    (ca, va), (cb, vb) = zero_carry(), zero_carry()
+    (ca, va), (cb, vb) = zero_carry(eng, M, keep, H), zero_carry(eng, M, keep, H)
     mean, var = prob["init_mean"], prob["init_var"]
     for call in (1, 2):
         a, ra = eng.scored_plan(score, prm, *args, mean, var, N, carry=ca, carry_valid=va, seed=4, call=call, want_best_return=True)
@@ -226,7 +214,7 @@ def test_mean_score_is_the_existing_entry(gpu, update):
     prm = _params(update, noise_beta=1.0, keep_elites=K, decay=1.25, return_best=True, add_mean_last=True)
     args = (prob["obs"], prob["cp_obs"], prob["cp_act"])
     existing = eng.mppi_plan if update == "mppi" else eng.icem_plan
-    carries = [(torch.zeros((M, K, H, A), dtype=torch.float32, device=eng.device), torch.zeros((M,), dtype=torch.int32, device=eng.device)) for _ in range(3)]
+    carries = [zero_carry(eng, M, K, H) for _ in range(3)]
     mean, var = prob["init_mean"], prob["init_var"]
     for call in (1, 2):
         want, wr = existing(prm, *args, mean, var, N, carry=carries[0][0], carry_valid=carries[0][1], seed=9, call=call, want_best_return=True)
@@ -239,36 +227,6 @@ def test_mean_score_is_the_existing_entry(gpu, update):
         mean = np.concatenate([_np(want)[:, 1:], np.zeros((M, 1, A), np.float32)], axis=1)
 
 
-def _model(context, H, n_particles=10, **kw):
-    from cadm_amd.dynamics.mlp_cadm_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as CaDMModel
-    from cadm_amd.dynamics.mlp_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel as VanillaModel
-    from cadm_amd.envs import make_env_spec
-    env = kw.pop("env", None) or make_env_spec("halfcheetah")
-    base = dict(name="dyn", env=env, hidden_sizes=HID, hidden_nonlinearity="swish", n_forwards=H, n_candidates=N, ensemble_size=E,
-                n_particles=n_particles, use_cem=True, normalize_input=True, seed=7)
-    base.update(kw)
-    prob = synth.make_problem(env="halfcheetah", context=context, E=E, m=M, H=H, seed=9, hidden_sizes=HID, trained_like=True)
-    st = prob["stats"]
-    if context:
-        model = CaDMModel(**base)
-        model.engine.set_net("context_model", prob["cp"])
-    else:
-        model = VanillaModel(**base)
-    model.engine.set_net("ff_model", prob["ff"])
-    nz = {"obs": (st["obs_mean"], st["obs_std"]), "delta": (st["delta_mean"], st["delta_std"]), "act": (st["act_mean"], st["act_std"])}
-    if context:
-        nz.update({"cp_obs": (st["cp_obs_mean"], st["cp_obs_std"]), "cp_act": (st["cp_act_mean"], st["cp_act_std"]),
-                   "back_delta": (st["back_delta_mean"], st["back_delta_std"])})
-    model.set_normalization(nz)
-    return model, prob
-
-
-def _act(model, prob, context, mean, var):
-    if context:
-        return model.get_action(prob["obs"], prob["cp_obs"], prob["cp_act"], mean, var)
-    return model.get_action(prob["obs"], mean, var)
-
-
 @pytest.mark.parametrize("context", [False, True], ids=["vanilla", "cadm"])
 def test_get_action_with_kappa_zero_is_get_action_with_the_mean(gpu, context):
     """cem_score="mean_std", cem_risk=0.0 plans through `cadm_scored_plan`, cem_score="mean" with the same other kwargs through
@@ -276,11 +234,11 @@ def test_get_action_with_kappa_zero_is_get_action_with_the_mean(gpu, context):
     at their defaults holds no opt-in state at all."""
     H = 5
     plain, prob = _model(context, H, cem_score="mean", cem_risk=None)
-    assert plain._icem is None and plain._score is None
+    assert plain._opt is None
     for other in (dict(cem_keep_elites=K, cem_noise_beta=1.0), dict(cem_update="mppi", cem_temperature=0.3, cem_keep_elites=K)):
         a, _ = _model(context, H, cem_score="mean", **other)
         b, _ = _model(context, H, cem_score="mean_std", cem_risk=0.0, **other)
-        assert a._score_params is None and b._score_params is not None and b._score_params.mode == 1
+        assert a._opt.score_params is None and b._opt.score_params is not None and b._opt.score_params.mode == 1
         mean, var = np.zeros((M, H, A)), np.full((M, H, A), 0.25)
         for _ in range(2):
             pa, pb = _act(a, prob, context, mean, var), _act(b, prob, context, mean, var)
@@ -421,10 +379,10 @@ def test_class_route_under_cvar(gpu, context):
     kw = dict(cem_score="cvar", cem_risk=0.1, cem_keep_elites=K, cem_noise_beta=1.0)
     model, prob = _model(context, H, n_particles=p, **kw)
     eng = model.engine
-    assert model._icem is not None and model._score == ("cvar", 0.0, 2) and model._score_params.k == 2 and model._score_params.mode == 3
+    assert model._opt is not None and model._opt.score == ("cvar", 0.0, 2) and model._opt.score_params.k == 2 and model._opt.score_params.mode == 3
     cp = (prob["cp_obs"], prob["cp_act"]) if context else (None, None)
     score, prm = HipEngine.score_params("cvar", k=2), HipEngine.icem_params(noise_beta=1.0, keep_elites=K)
-    carry, valid = torch.zeros((M, K, H, A), dtype=torch.float32, device=eng.device), torch.zeros((M,), dtype=torch.int32, device=eng.device)
+    carry, valid = zero_carry(eng, M, K, H)
     mean, var = np.zeros((M, H, A)), np.full((M, H, A), 0.25)
     plans = []
     for call in (1, 2):
@@ -459,3 +417,47 @@ def test_class_route_under_cvar(gpu, context):
     np.testing.assert_array_equal(_np(model._plan_carry), _np(c2))
     state.observe(prob["obs"], act, prob["obs"], done=np.array([1, 0]))
     np.testing.assert_array_equal(_np(model._plan_carry_valid), [0, 1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------- 9
+def test_the_dispatcher_calls_the_public_method(gpu):
+    """`HipEngine.opt_in_plan` under a `PlanOptions` for each update, with and without a score == the public method those options stand
+    for, given structs built by hand, on the same (seed, call) and a valid carry: plan, best return and the carry it leaves, bit for bit."""
+    from cadm_amd.planner import PlanOptions
+    H, p = 5, 10
+    prob, eng = _engine(H, True, p)
+    icem, mppi = dict(noise_beta=1.0, keep_elites=K), dict(cem_update="mppi", cem_temperature=0.5, cem_temperature_relative=True)
+    lam, cvar = HipEngine.mppi_params(temperature=0.5, relative=True, **icem), HipEngine.score_params("cvar", k=2)
+    routes = [(dict(), eng.icem_plan, (HipEngine.icem_params(**icem),)), (mppi, eng.mppi_plan, (lam,)),
+              (dict(cem_score="cvar", cem_risk=0.2), eng.scored_plan, (cvar, HipEngine.icem_params(**icem))),
+              (dict(mppi, cem_score="cvar", cem_risk=0.2), eng.scored_plan, (cvar, lam))]
+    args = (prob["obs"], prob["cp_obs"], prob["cp_act"], prob["init_mean"], prob["init_var"], N)
+    carry = eng._t(np.random.default_rng(1).uniform(-1, 1, (M, K, H, A)).astype(np.float32))
+    plans = []
+    for kw, method, head in routes:
+        opt = PlanOptions.from_kwargs(cem_noise_beta=1.0, cem_keep_elites=K, use_cem=True, n_particles=p, **kw)
+        (ca, va), (cb, vb) = [(carry.clone(), torch.ones((M,), dtype=torch.int32, device=eng.device)) for _ in range(2)]
+        got, gr = eng.opt_in_plan(opt, *args, carry=ca, carry_valid=va, seed=6, call=3, want_best_return=True)
+        want, wr = method(*head, *args, carry=cb, carry_valid=vb, seed=6, call=3, want_best_return=True)
+        assert np.isfinite(_np(got)).all() and 0 < np.abs(_np(got)).max() <= 1.0
+        np.testing.assert_array_equal(_bits(_np(got)), _bits(_np(want)))
+        np.testing.assert_array_equal(_bits(_np(gr)), _bits(_np(wr)))
+        np.testing.assert_array_equal(_np(ca), _np(cb))
+        assert not np.array_equal(_np(ca), _np(carry))
+        plans.append(_np(got))
+    assert not any(np.array_equal(plans[i], plans[j]) for i in range(4) for j in range(i))      # four routes, four plans
+
+
+def test_each_update_keeps_its_workspace(gpu):
+    """icem_plan, mppi_plan, icem_plan on one engine: neither workspace is reallocated (the tensors are held here, so a new allocation
+    could not land on an old address)."""
+    prob, eng = _engine(5, True, 10)
+    args = (prob["obs"], prob["cp_obs"], prob["cp_act"], prob["init_mean"], prob["init_var"], N)
+    eng.icem_plan(HipEngine.icem_params(), *args, seed=1, call=1)
+    wi = eng._loop_workspace(False, M, N, 0)
+    eng.mppi_plan(HipEngine.mppi_params(), *args, seed=1, call=1)
+    wm = eng._loop_workspace(True, M, N, 0)
+    ptrs = wi.data_ptr(), wm.data_ptr()
+    assert ptrs[0] != ptrs[1] and wm.numel() > wi.numel()
+    eng.icem_plan(HipEngine.icem_params(), *args, seed=1, call=2)
+    assert (eng._loop_workspace(False, M, N, 0).data_ptr(), eng._loop_workspace(True, M, N, 0).data_ptr()) == ptrs
