@@ -250,6 +250,9 @@ __global__ __launch_bounds__(256) void rollout_kernel(const RolloutArgs a) {
     const int e = blockIdx.x / a.wgs_per_member;
     const int grp = blockIdx.x % a.wgs_per_member;
     const int H = a.H;
+    // state H is read only by a trajectory output or a reward term on the NEXT observation: without either the loop leaves one step early (rollout_xdl.h)
+    const bool need_last = a.traj != nullptr || ENV == CADM_ENV_CARTPOLE || has_next<ENV>();      // (workgroup-uniform)
+    const int t_end = need_last ? H : H - 1;
 
     float* x_in = smem + G::X_IN;
     float* ctrl_s = smem + G::CTRL_S;
@@ -450,7 +453,7 @@ __global__ __launch_bounds__(256) void rollout_kernel(const RolloutArgs a) {
                 }
             }
         }
-        if (t == H) break;
+        if (t >= t_end) break;
         TS(0)
         __syncthreads();
         TS(1)

@@ -162,6 +162,9 @@ __global__ __launch_bounds__(WT<G>::NTHR) void rollout_wt_kernel(const RolloutAr
     const int item = rollout_item();
     const int e = item / a.wgs_per_member, grp = item % a.wgs_per_member;
     const int H = a.H;
+    // state H is read only by a trajectory output or a reward term on the NEXT observation: without either the loop leaves one step early (rollout_xdl.h)
+    const bool need_last = a.traj != nullptr || ENV == CADM_ENV_CARTPOLE || has_next<ENV>();      // (workgroup-uniform)
+    const int t_end = need_last ? H : H - 1;
     const int wbytes = W::wave_bytes(H);
     unsigned char* xw = sm + W::WAVE0 + wave * wbytes;           // this wave's x_in image: [2 parts][NC0][64 lanes] x 16 B
     float* ctrl_s = reinterpret_cast<float*>(xw + W::XW_BYTES);  // [16 rows][H]
@@ -393,7 +396,7 @@ __global__ __launch_bounds__(WT<G>::NTHR) void rollout_wt_kernel(const RolloutAr
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the next step's writes must not overtake these reads in program order)
                 }
             }
-            if (t == H) break;
+            if (t >= t_end) break;      // (before the step's first block boundary: the weight ring stands where a step starts)
 
             // ================= dense layers: activations stay in registers =================
             f16x8 Y1[NCH], Y2[NCH];

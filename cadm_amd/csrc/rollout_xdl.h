@@ -515,6 +515,10 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
     const int e = item / a.wgs_per_member;
     const int grp = item % a.wgs_per_member;
     const int H = a.H;
+    // The state after the last step is read only by a trajectory output and by a reward term that reads the NEXT observation; without
+    // either, the step loop leaves behind step H-1's state phase (which has added the last reward) and never evaluates the model for it.
+    const bool need_last = a.traj != nullptr || ENV == CADM_ENV_CARTPOLE || has_next<ENV>();      // (workgroup-uniform)
+    const int t_end = need_last ? H : H - 1;
     const int arow = tid & 15, fg = (tid >> 4) & 15;
     // feature threads (rollout state, input assembly): MT = 1: waves 0-3, their twins in waves 4-7 make the noise;
     // MT = 2: everybody -- waves 0-3 hold row tile 0, waves 4-7 row tile 1, and make their own noise
@@ -950,7 +954,9 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
                 }
             }
             }
-            if (t == H) break;
+            // (t_end: H, or H-1 when nothing reads state H.  The exit is at the loop's own entry state -- the ring holds next_streamed(XNH)'s
+            //  first fragments, x_in / zb / ofull are read by nobody until the barriers behind the loop -- so the next row tile finds what it expects)
+            if (t >= t_end) break;
             // Gaussian-head noise of THIS step (consumed by the next state phase, through the double-buffered zb).
             // One row tile: made here by the twin thread in waves 4-7, which have nothing else to do while waves 0-3 update
             // the state.  Two row tiles: every thread owns state and makes its own noise, but not here, where it would

@@ -202,7 +202,10 @@ int cadm_sample_uniform(cadm_ctx* ctx, uint32_t seed, uint32_t call, int m, int 
  *                                 STREAM_EPS | it<<8) -- independent of the candidate sharding
  *   it           CEM iteration (selects the context layout of quirk Q2, :434)
  *   returns_rows [m,n_local,p]    out: per-row returns before the particle mean (:471)
- *   traj_out     [H,m,n_local,p,D] optional out: next observation after every step, else NULL */
+ *   traj_out     [H,m,n_local,p,D] optional out: next observation after every step, else NULL
+ * The state after the LAST step is computed only when something reads it: with traj_out, or for an env whose reward reads the next
+ * observation (cartpole; a CADM_ENV_SPEC env with a CADM_SPEC_WHEN_NEXT_OBS term).  Otherwise the launch evaluates the model H - 1
+ * times per row (not at all at H = 1) and never reads eps[H-1]; returns_rows are bit-identical either way. */
 int cadm_rollout_returns(cadm_ctx* ctx, const float* obs, const float* obs_rows, const float* ctx_vec,
                          const float* actions, const float* eps, int norm_actions,
                          uint32_t seed, uint32_t call, int it,

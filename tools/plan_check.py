@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Is the launcher's plan (flavour 0) as fast as the best single rollout flavour on shapes the cost table was NOT measured on?
-   python tools/plan_check.py      -> one line per shape: us per rollout for the plan and for forced flavours 1 / 2 / 3"""
+   python tools/plan_check.py [LIB]   -> one line per shape: us per rollout for the plan and for forced flavours 1 / 2 / 3
+   (LIB: another build of the developer library, for an A/B on one box)"""
 import os
 import sys
 
@@ -22,11 +23,12 @@ SHAPES = [      # env, context, E, p, n, m, hidden, deterministic
     ("cartpole", True, 5, 5, 4000, 4, 200, False),
     ("halfcheetah", True, 2, 4, 10000, 1, 200, False),       # E = 2: 128 CUs per member
 ]
+LIBP = sys.argv[1] if len(sys.argv) > 1 else None
 for env, context, E, p, n, m, hid, det in SHAPES:
     prob = synth.make_problem(env=env, context=context, E=E, m=m, H=10, hidden_sizes=(hid,) * 4, seed=0)
     row = []
     for fl in (0, 1, 2, 3):
-        eng = synth.make_engine(prob, p=p, deterministic=det, lib=_lib.load_dev())
+        eng = synth.make_engine(prob, p=p, deterministic=det, lib=_lib.load_dev(LIBP))
         eng.dev_set_rollout("xdl", row_tiles=fl)
         args = [eng._t(prob[k]) if prob.get(k) is not None else None for k in ("obs", "cp_obs", "cp_act", "init_mean", "init_var")]
         try:
