@@ -74,6 +74,13 @@ class ForecastOut(C.Structure):         # include/cadm_hip.h cadm_forecast_out: 
 
 
 SCORE_MODES = {"mean": 0, "mean_std": 1, "member_std": 2, "cvar": 3}      # CADM_SCORE_*
+MAX_CONSTRAINTS = 16                                                       # CADM_MAX_CONSTRAINTS
+CONSTRAIN_MODES = {"penalty": 0, "terminate": 1}                           # CADM_CONSTRAIN_*
+
+
+class ConstraintParams(C.Structure):    # include/cadm_hip.h cadm_constraint_params
+    _fields_ = [("n", C.c_int32), ("mode", C.c_int32), ("weight", C.c_float), ("dim", C.c_int32 * MAX_CONSTRAINTS),
+                ("lo", C.c_float * MAX_CONSTRAINTS), ("hi", C.c_float * MAX_CONSTRAINTS)]
 
 
 class TrainHParams(C.Structure):
@@ -126,6 +133,10 @@ SIGNATURES = {
     "cadm_mppi_plan": (_i, [_P, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_particle_score": (_i, [_P, _P, _i, _i, C.POINTER(ScoreParams), _P, _P]),
     "cadm_scored_plan": (_i, [_P, C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_constrain_returns": (_i, [_P, C.POINTER(ConstraintParams), _P, _P, _P, _P, _i, _i, _P, _P, _P, _P]),
+    "cadm_constrained_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i]),
+    "cadm_constrained_plan": (_i, [_P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P,
+                                   _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

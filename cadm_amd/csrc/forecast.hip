@@ -32,21 +32,12 @@
 // Traffic: `traj` is read exactly once -- a (sequence, step)'s p * D values are one contiguous span, loaded lane-linear with 16-byte
 // loads into one of two LDS tiles (scalar loads where the span is not 16-byte aligned); the other tile still holds the previous
 // step: the pre-step state of the rewards.
-#include "planner.h"
-#include "rollout_env.h"
+#include "step_reward.h"
 
 namespace {
 
 constexpr int FC_THREADS = 256;
 constexpr int FC_LDS_BUDGET = 48 * 1024;     // two tiles + per-particle rewards and returns, below the 64 KiB a kernel gets without an attribute
-
-// a CADM_ENV_SPEC ctx's reward tables (cadm_env_spec), evaluated at run time: the library holds no compile-time table for them
-struct ForecastSpec {
-    int n_terms;
-    int kind[CADM_SPEC_MAX_TERMS], dim[CADM_SPEC_MAX_TERMS], when[CADM_SPEC_MAX_TERMS];
-    float w[CADM_SPEC_MAX_TERMS], lo[CADM_SPEC_MAX_TERMS], hi[CADM_SPEC_MAX_TERMS];
-    float ctrl, bonus;
-};
 
 struct ForecastArgs {
     const float *traj, *obs, *actions;
@@ -56,53 +47,6 @@ struct ForecastArgs {
 };
 
 __device__ __forceinline__ bool fc_non_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
-__device__ __forceinline__ float fc_term(int kind, float x, float w, float lo, float hi) {
-    switch (kind) {
-        case CADM_SPEC_TERM_LINEAR: return spec_term_value<CADM_SPEC_TERM_LINEAR>(x, w, lo, hi);
-        case CADM_SPEC_TERM_SQUARE: return spec_term_value<CADM_SPEC_TERM_SQUARE>(x, w, lo, hi);
-        case CADM_SPEC_TERM_ABS: return spec_term_value<CADM_SPEC_TERM_ABS>(x, w, lo, hi);
-        case CADM_SPEC_TERM_INSIDE: return spec_term_value<CADM_SPEC_TERM_INSIDE>(x, w, lo, hi);
-        default: return spec_term_value<CADM_SPEC_TERM_OUTSIDE>(x, w, lo, hi);
-    }
-}
-
-// Step reward of one particle: pre / post = its D pre- and post-step values, act = the step's raw action.
-// Built-in kinds: the pair parts of rollout_env.h (the terms the rollout adds), summed in ascending pair order.
-// CADM_ENV_SPEC: the grouping of env_spec.py EnvDecl.reward -- ((pre-step terms of the first term's dim pair) - c ctrl) + bonus,
-// then the other terms in declaration order.
-template <int ENV>
-__device__ __forceinline__ float step_reward(const ForecastArgs& a, const float* pre, const float* post, const float* act) {
-    const float ctrl = ctrl_term<ENV>(act, a.A);
-    if constexpr (ENV == CADM_ENV_SPEC) {
-        const ForecastSpec& sp = a.spec;
-        const int first_pair = sp.n_terms > 0 ? sp.dim[0] >> 1 : 0;
-        float r = 0.0f;
-        bool any = false;
-        for (int k = 0; k < sp.n_terms; ++k) {
-            if ((sp.dim[k] >> 1) != first_pair || sp.when[k] != CADM_SPEC_WHEN_OBS) continue;
-            const float v = fc_term(sp.kind[k], pre[sp.dim[k]], sp.w[k], sp.lo[k], sp.hi[k]);
-            r = any ? r + v : v;
-            any = true;
-        }
-        if (sp.ctrl != 0.0f) r = r - sp.ctrl * ctrl;
-        if (sp.bonus != 0.0f) r = r + sp.bonus;
-        for (int k = 0; k < sp.n_terms; ++k) {
-            const bool next = sp.when[k] != CADM_SPEC_WHEN_OBS;
-            if ((sp.dim[k] >> 1) == first_pair && !next) continue;
-            r = r + fc_term(sp.kind[k], (next ? post : pre)[sp.dim[k]], sp.w[k], sp.lo[k], sp.hi[k]);
-        }
-        return r;
-    } else {
-        float r = 0.0f;
-        const int pairs = (a.D + 1) >> 1;
-        for (int dp = 0; dp < pairs; ++dp) {
-            const float part = reward_part<ENV>(dp, pre[2 * dp], 2 * dp + 1 < a.D ? pre[2 * dp + 1] : 0.0f, ctrl);
-            r = dp == 0 ? part : r + part;
-        }
-        return r;
-    }
-}
 
 template <int ENV>
 __global__ __launch_bounds__(FC_THREADS) void forecast_stats_kernel(const ForecastArgs a) {
@@ -192,7 +136,7 @@ __global__ __launch_bounds__(FC_THREADS) void forecast_stats_kernel(const Foreca
         // step rewards: one thread per particle
         const float* act = a.actions + row * a.A;
         for (int j = tid; j < p; j += FC_THREADS) {
-            const float r = step_reward<ENV>(a, pre + j * D, cur + j * D, act);
+            const float r = step_reward<ENV>(a.spec, D, a.A, pre + j * D, cur + j * D, act);
             rew[j] = r;
             ret[j] = ret[j] + r;
         }
@@ -284,15 +228,7 @@ extern "C" int cadm_forecast_stats(cadm_ctx* ctx, const float* traj, const float
     a.traj = traj; a.obs = obs; a.actions = actions;
     a.m = m; a.n = n; a.H = H; a.p = p; a.E = E; a.D = ctx->D; a.A = ctx->A; a.PE = p / E; a.band_k = band_k;
     a.out = *out;
-    if (ctx->cfg.env_kind == CADM_ENV_SPEC) {
-        const cadm_env_spec& sp = ctx->spec;
-        a.spec.n_terms = sp.n_terms;
-        for (int k = 0; k < sp.n_terms; ++k) {
-            a.spec.kind[k] = sp.term_kind[k]; a.spec.dim[k] = sp.term_dim[k]; a.spec.when[k] = sp.term_when[k];
-            a.spec.w[k] = sp.term_w[k]; a.spec.lo[k] = sp.term_lo[k]; a.spec.hi[k] = sp.term_hi[k];
-        }
-        a.spec.ctrl = sp.ctrl_cost; a.spec.bonus = sp.bonus;
-    }
+    forecast_spec_fill(ctx, &a.spec);
     const size_t lds = forecast_lds_bytes(p, ctx->D);
     hipStream_t s = (hipStream_t)stream;
     switch (ctx->cfg.env_kind) {

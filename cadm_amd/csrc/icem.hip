@@ -7,7 +7,8 @@
 //   * a decaying candidate count.
 // The rollout, the context encoder, the truncated-normal sampler and the elite refit are the reference path's, called unchanged.
 // The loop takes its update and its candidate score as parameters: cadm_icem_plan runs it with the elite refit, cadm_mppi_plan with the
-// MPPI refit (mppi.hip), both on the particle mean; cadm_scored_plan chooses the update and the score (score.hip).
+// MPPI refit (mppi.hip), both on the particle mean; cadm_scored_plan chooses the update and the score (score.hip); cadm_constrained_plan
+// also rewrites the particle returns under state constraints (constrain.hip) before the score sees them.
 #include <math.h>
 
 #include "planner.h"
@@ -288,9 +289,10 @@ struct IcemWs {
     float *ctxv, *actions, *rows, *cand, *mean, *var, *meanclip, *kept, *best_ret, *best_seq;
     int32_t* elites;
     float *emean, *evar, *mppi;      // MPPI only: where the elite selection's own refit goes (discarded), the update's weights and partials
+    float* traj;                     // constrained only: the rollout's trajectories [H, m, n, p, D], the LAST view (the sums before it stay)
 };
 
-static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w) {
+static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0) {
     Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
     IcemWs t{};
@@ -310,6 +312,7 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
         t.evar = c.take<float>((size_t)m * HA);
         t.mppi = c.take<float>(cadm_mppi_scratch_floats(ctx, m, n));
     }
+    if (traj) t.traj = c.take<float>((size_t)ctx->H * m * n * ctx->p * ctx->D);
     if (w) *w = t;
     return c.off;
 }
@@ -324,6 +327,11 @@ extern "C" size_t cadm_mppi_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) 
     return icem_carve(ctx, m, n, K, 1, nullptr, nullptr);
 }
 
+extern "C" size_t cadm_constrained_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1);
+}
+
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
 static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     double v = floor((double)n / pow(decay, (double)it));
@@ -334,10 +342,11 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 }
 
 // score: what a candidate's particle returns become before the update sees them (score.hip); null = the particle mean
+// constraints: state constraints that rewrite the particle returns before the score (constrain.hip); null = none, and today's launches
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
-                     float* best_return_out, void* stream) {
+                     float* best_return_out, void* stream, const cadm_constraint_params* constraints = nullptr) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -354,10 +363,11 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     int rc;
     if (upd.mppi && (rc = cadm_mppi_check(ctx, m, upd.temperature, who))) return rc;
     if ((rc = cadm_score_check(ctx, score, who))) return rc;
+    if (constraints && (rc = cadm_constraint_check(ctx, constraints, who))) return rc;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w);
+    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr);      // (w.traj: null without constraints)
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
@@ -383,7 +393,10 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
             if ((rc = launch_inject(ctx, w.meanclip, nullptr, m, ni, 1, 0, w.actions + (size_t)K * HA, s))) return rc;
         }
         if ((rc = cadm_rollout_returns(ctx, obs, nullptr, ctx->C > 0 ? w.ctxv : nullptr, w.actions, nullptr, 1, seed, call, it, 0, ni, m, ni,
-                                       w.rows, nullptr, stream))) return rc;
+                                       w.rows, w.traj, stream))) return rc;
+        // the trajectories are [H, m, ni, p, D] of this iteration's ni candidates; the returns are rewritten in place
+        if (constraints && (rc = cadm_constrain_returns(ctx, constraints, w.traj, obs, w.actions, w.rows, m, ni, w.rows, nullptr, nullptr,
+                                                        stream))) return rc;
         if ((rc = cadm_particle_score(ctx, w.rows, m, ni, score, w.cand, stream))) return rc;      // (the mean: cadm_particle_mean itself)
         float* plan = (last && !prm->return_best) ? plan_out : nullptr;      // the refitted mean, clipped (dynamics.py:365-366)
         if (!upd.mppi) {
@@ -433,4 +446,16 @@ extern "C" int cadm_scored_plan(cadm_ctx* ctx, const cadm_score_params* score, i
     const PlanUpdate upd{"cadm_scored_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream);
+}
+
+// the same loop once more, with state constraints (constrain.hip) between the rollout and the score; constraints null: cadm_scored_plan's launches
+extern "C" int cadm_constrained_plan(cadm_ctx* ctx, const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
+                                     const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
+                                     const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                                     uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_constrained_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_constrained_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_constrained_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints);
 }

@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, forecast.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, forecast.hip, constrain.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -70,6 +70,9 @@ int cadm_launch_mppi_refit(cadm_ctx* ctx, const float* cand_returns, const float
                            hipStream_t s);
 // score.hip: the refusals of a candidate score (unknown mode, kappa not finite, cvar k outside [1, p]), before any HIP call; null = the mean
 int cadm_score_check(const cadm_ctx* ctx, const cadm_score_params* score, const char* who);
+// constrain.hip: the refusals of a constraint set (count, dims, bounds, mode, weight, a discrete / sharded ctx, a spec ctx without its spec in
+// terminate mode, a D whose tiles exceed the kernel's LDS), before any HIP call
+int cadm_constraint_check(const cadm_ctx* ctx, const cadm_constraint_params* c, const char* who);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

@@ -31,6 +31,11 @@ Differences a caller can see (all opt-in except the first):
   * `cem_score="mean_std" | "member_std" | "cvar"`, `cem_risk`: risk-aware candidate scores in that loop (INTEGRATION.md "Risk-aware
     scoring") -- a candidate's particle returns become mean - cem_risk * std, mean - cem_risk * (std of the ensemble members' means), or
     the mean of the worst cem_risk fraction of them, instead of their plain mean; a non-default `cem_score` alone takes the opt-in route;
+  * `cem_constraints=[dict(dim=d, lo=..., hi=...), ...]`, `cem_constraint_mode="penalty" | "terminate"`, `cem_constraint_weight`: state
+    constraints in that loop (INTEGRATION.md "State constraints and termination") -- a predicted state is healthy while lo < obs[d] < hi
+    for every entry; "penalty" takes cem_constraint_weight off a particle's return per violating step, "terminate" ends its return at
+    the first one (that step still pays) and takes the weight off once; `cem_constraints` alone takes the opt-in route, and a constraint
+    that never binds leaves every plan as it is.  `constraint_check(obs, actions, ...)`: which particles of given plans violate, and when;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -176,6 +181,9 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_temperature_relative=False,
                  cem_score="mean",
                  cem_risk=None,
+                 cem_constraints=None,
+                 cem_constraint_mode="penalty",
+                 cem_constraint_weight=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -235,7 +243,13 @@ class MLPEnsembleCEMDynamicsModel(object):
         # the reference's CEM, and get_action never looks further
         self._opt = _planner.PlanOptions.from_kwargs(cem_noise_beta, cem_keep_elites, cem_decay, cem_return, cem_add_mean, cem_update,
                                                      cem_temperature, cem_temperature_relative, cem_score, cem_risk, use_cem=use_cem,
-                                                     discrete=self.discrete, process_group=process_group, n_particles=n_particles)
+                                                     discrete=self.discrete, process_group=process_group, n_particles=n_particles,
+                                                     cem_constraints=cem_constraints, cem_constraint_mode=cem_constraint_mode,
+                                                     cem_constraint_weight=cem_constraint_weight)
+        if self._opt is not None and self._opt.constraint_params is not None:
+            cp = self._opt.constraint_params
+            if max(cp.dim[:cp.n]) >= obs_space_dims:
+                raise ValueError("cem_constraints read observation dim %d, this env has %d" % (max(cp.dim[:cp.n]), obs_space_dims))
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
 
         self.env_kind = resolve_env_kind(env)
@@ -443,23 +457,27 @@ class MLPEnsembleCEMDynamicsModel(object):
         plan = MLPEnsembleCEMDynamicsModel.get_action(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var)      # (not a subclass's signature)
         return plan, self._forecast(obs, plan, cp_obs, cp_act, 1, self.seed, self._call & 0xFFFFFFFF)
 
-    def _forecast(self, obs, actions, cp_obs, cp_act, band_k, seed, call):
-        self._push_stats()
+    def _rollout_inputs(self, who, obs, actions, cp_obs, cp_act):
+        """The input checks `forecast` and `constraint_check` share -> (cp_obs, cp_act), None for a model without context."""
         D, A, H = self.obs_space_dims, self.action_space_dims, self.n_forwards
         shp = tuple(int(v) for v in np.shape(actions))
         m = int(np.shape(obs)[0])
         if tuple(np.shape(obs)) != (m, D) or m == 0 or len(shp) not in (3, 4) or shp[0] != m or shp[-2:] != (H, A):
-            raise ValueError("forecast: obs %r, actions %r: expected [m,%d] with m >= 1 and [m,%d,%d] or [m,n,%d,%d]"
-                             % (tuple(np.shape(obs)), shp, D, H, A, H, A))
-        if self.context_out_dim > 0:
-            if cp_obs is None or cp_act is None:
-                raise ValueError("forecast: cp_obs and cp_act are required for a context model")
-            Hh = self.history_length
-            if tuple(np.shape(cp_obs)) != (m, D * Hh) or tuple(np.shape(cp_act)) != (m, A * Hh):
-                raise ValueError("forecast: cp_obs %r / cp_act %r, expected %r / %r" % (tuple(np.shape(cp_obs)), tuple(np.shape(cp_act)),
-                                                                                       (m, D * Hh), (m, A * Hh)))
-        else:
-            cp_obs = cp_act = None
+            raise ValueError("%s: obs %r, actions %r: expected [m,%d] with m >= 1 and [m,%d,%d] or [m,n,%d,%d]"
+                             % (who, tuple(np.shape(obs)), shp, D, H, A, H, A))
+        if self.context_out_dim == 0:
+            return None, None
+        if cp_obs is None or cp_act is None:
+            raise ValueError("%s: cp_obs and cp_act are required for a context model" % who)
+        Hh = self.history_length
+        if tuple(np.shape(cp_obs)) != (m, D * Hh) or tuple(np.shape(cp_act)) != (m, A * Hh):
+            raise ValueError("%s: cp_obs %r / cp_act %r, expected %r / %r" % (who, tuple(np.shape(cp_obs)), tuple(np.shape(cp_act)),
+                                                                             (m, D * Hh), (m, A * Hh)))
+        return cp_obs, cp_act
+
+    def _forecast(self, obs, actions, cp_obs, cp_act, band_k, seed, call):
+        self._push_stats()
+        cp_obs, cp_act = self._rollout_inputs("forecast", obs, actions, cp_obs, cp_act)
         eng = self.engine
         acts = eng._t(actions)
         squeeze = acts.dim() == 3
@@ -488,6 +506,34 @@ class MLPEnsembleCEMDynamicsModel(object):
         in between, and `forecast` of the plan `get_action` just returned reproduces `get_action(..., return_forecast=True)`'s."""
         self._forecast_refuse("forecast")
         return self._forecast(obs, actions, cp_obs, cp_act, band_k, self.seed if seed is None else seed, self._call & 0xFFFFFFFF)
+
+    def constraint_check(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
+        """Which particles of `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) leave the region this model's `cem_constraints` declare
+        healthy, and when -- the companion of `forecast`: the context encoder, one rollout that records its trajectories, and the
+        constraint kernel under the model's mode and weight, as numpy arrays (for [m,H,A] input the n axis is dropped):
+          first_violation, violations [m,n,p]   the first violating step (H: none) and the number of violating steps, per particle
+          violation_fraction [m,n]              the share of a sequence's particles with any violation
+          returns [m,n,p]                       the constrained particle returns, as the planner would score them
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; the planner's
+        call counter does not move."""
+        if self._opt is None or self._opt.constraint_params is None:
+            raise ValueError("constraint_check: this model has no cem_constraints")
+        self._push_stats()
+        cp_obs, cp_act = self._rollout_inputs("constraint_check", obs, actions, cp_obs, cp_act)
+        eng = self.engine
+        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        acts = (acts[:, None] if squeeze else acts).contiguous()
+        obs = eng._t(obs)
+        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        rows, first, viol = eng.constrain_returns(traj, rows, self._opt.constraint_params, obs=obs, actions=acts)
+        res = dict(first_violation=first.cpu().numpy(), violations=viol.cpu().numpy(), returns=rows.cpu().numpy())
+        res["violation_fraction"] = (res["violations"] > 0).mean(axis=-1)
+        if squeeze:
+            res = {k: v[:, 0] for k, v in res.items()}
+        return res
 
     def reset_plan_carry(self, mask=None):
         """Forget the elites the iCEM planner carries from one get_action to the next (`cem_keep_elites` > 0): for every env, or for

@@ -41,6 +41,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """The model's per-step prediction under `actions` (see the CaDM class; a vanilla model has no history)."""
         return super().forecast(obs, actions, None, None, band_k=band_k, seed=seed)
 
+    def constraint_check(self, obs, actions, seed=None):
+        """Which particles of `actions` violate this model's `cem_constraints`, and when (see the CaDM class; a vanilla model has no history)."""
+        return super().constraint_check(obs, actions, None, None, seed=seed)
+
     def predict(self, obs, act, return_std=False):
         return super().predict(obs, act, None, None, return_std=return_std)
 

@@ -125,7 +125,7 @@ class HipEngine:
         self._ws = None
         self._ws_key = None
         self._host_plan = None
-        self._loop_ws = {}          # the opt-in loop's workspaces: mppi (bool) -> ((m, n, K), tensor)
+        self._loop_ws = {}          # the opt-in loop's workspaces: (mppi, with trajectory view) -> ((m, n, K), tensor)
         self._train_B = 0
         self.dist_world, self.dist_rank = 1, 0
 
@@ -560,9 +560,10 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return):
+                   want_best_return, traj=False):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
-        `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites."""
+        `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
+        workspace with the trajectory view behind it (a constrained loop)."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -571,7 +572,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -580,19 +581,27 @@ class HipEngine:
         return (out, best) if want_best_return else out
 
     def opt_in_plan(self, opt, *args, **kw):
-        """The opt-in loop under a `planner.PlanOptions`: `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
+        """The opt-in loop under a `planner.PlanOptions`: `constrained_plan` when it holds constraints, `scored_plan` when it holds a score,
+        else `mppi_plan` or `icem_plan` by its update.
         Arguments as `icem_plan` behind its params."""
+        if opt.constraint_params is not None:
+            return self.constrained_plan(opt.constraint_params, opt.score_params, opt.params, *args, **kw)
         if opt.score_params is not None:
             return self.scored_plan(opt.score_params, opt.params, *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
-    def _loop_workspace(self, mppi, m, n, K):
-        """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update."""
-        key, ws = self._loop_ws.get(bool(mppi), (None, None))
+    def _loop_workspace(self, mppi, m, n, K, traj=False):
+        """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
+        constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that)."""
+        slot = (bool(mppi), bool(traj))
+        key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            nbytes = (self.lib.cadm_mppi_workspace_bytes if mppi else self.lib.cadm_icem_workspace_bytes)(self._ctx, m, n, K)
+            if traj:
+                nbytes = self.lib.cadm_constrained_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)))
+            else:
+                nbytes = (self.lib.cadm_mppi_workspace_bytes if mppi else self.lib.cadm_icem_workspace_bytes)(self._ctx, m, n, K)
             ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
-            self._loop_ws[bool(mppi)] = ((m, n, K), ws)
+            self._loop_ws[slot] = ((m, n, K), ws)
         return ws
 
     # ------------------------------------------------------------------ MPPI update (opt-in; csrc/mppi.hip)
@@ -664,6 +673,92 @@ class HipEngine:
         head = (None if score is None else ct.byref(score), int(mppi), ct.byref(params))
         return self._loop_plan("scored_plan", self.lib.cadm_scored_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
+
+    # ------------------------------------------------------------------ state constraints and termination (opt-in; csrc/constrain.hip)
+    @staticmethod
+    def constraint_params(constraints, mode="penalty", weight=None):
+        """`cadm_constraint_params` from a list of dict(dim=d, lo=..., hi=...): a state is healthy iff lo < x[d] < hi for every entry (a
+        missing side: -inf / +inf; at least one is given, and lo < hi).  mode: "penalty" | "terminate" (or its CADM_CONSTRAIN_* number);
+        weight: finite, >= 0 -- per violating step (penalty), or once at the first one (terminate).  Everything that needs no engine is
+        checked here; a dim beyond the engine's D is refused by the library."""
+        if isinstance(constraints, dict):
+            constraints = [constraints]
+        try:
+            cons = list(constraints)
+        except TypeError:
+            raise ValueError("constraints must be a list of dict(dim=, lo=, hi=), got %r" % (constraints,)) from None
+        if not 1 <= len(cons) <= _lib.MAX_CONSTRAINTS:
+            raise ValueError("constraints: %d entries, expected 1 .. %d" % (len(cons), _lib.MAX_CONSTRAINTS))
+        if isinstance(mode, str):
+            if mode not in _lib.CONSTRAIN_MODES:
+                raise ValueError("constraint mode must be 'penalty' or 'terminate', got %r" % (mode,))
+            mode = _lib.CONSTRAIN_MODES[mode]
+        elif int(mode) not in _lib.CONSTRAIN_MODES.values():
+            raise ValueError("constraint mode must be 'penalty' or 'terminate', got %r" % (mode,))
+        if weight is None or not math.isfinite(float(weight)) or float(weight) < 0.0:
+            raise ValueError("constraints need a weight that is finite and >= 0, got %r" % (weight,))
+        prm = _lib.ConstraintParams()
+        prm.n, prm.mode, prm.weight = len(cons), int(mode), float(weight)
+        for k, c in enumerate(cons):
+            if not isinstance(c, dict) or "dim" not in c or set(c) - {"dim", "lo", "hi"}:
+                raise ValueError("constraint %d: expected dict(dim=, lo=, hi=), got %r" % (k, c))
+            lo, hi = c.get("lo"), c.get("hi")
+            if lo is None and hi is None:
+                raise ValueError("constraint %d: at least one of lo and hi is needed" % k)
+            if isinstance(c["dim"], bool) or not isinstance(c["dim"], (int, np.integer)) or int(c["dim"]) < 0:
+                raise ValueError("constraint %d: dim must be an observation index >= 0, got %r" % (k, c["dim"]))
+            lo = -math.inf if lo is None else float(np.float32(lo))      # (the bounds as the kernel compares them)
+            hi = math.inf if hi is None else float(np.float32(hi))
+            if math.isnan(lo) or math.isnan(hi):
+                raise ValueError("constraint %d: a bound is NaN" % k)
+            if not lo < hi:
+                raise ValueError("constraint %d: lo %r must be below hi %r (in float32)" % (k, lo, hi))
+            if math.isinf(lo) and math.isinf(hi):
+                raise ValueError("constraint %d: both sides are infinite: it constrains nothing" % k)
+            prm.dim[k], prm.lo[k], prm.hi[k] = int(c["dim"]), lo, hi
+        return prm
+
+    def constrain_returns(self, traj, rows, constraints, mode="penalty", weight=None, obs=None, actions=None, out=None):
+        """`cadm_constrain_returns` on device tensors: traj [H,m,n,p,D] (a rollout's `traj_out`), rows [m,n,p] (its returns) ->
+        (rows' [m,n,p], first_violation [m,n,p] int32, violations [m,n,p] int32).  constraints: a `constraint_params` result, or the
+        list it takes (then with mode and weight).  obs [m,D] / actions [m,n,H,A] raw: needed in terminate mode.  out: where rows' go
+        (may be `rows` itself)."""
+        prm = constraints if isinstance(constraints, _lib.ConstraintParams) else self.constraint_params(constraints, mode, weight)
+        traj, rows = self._t(traj), self._t(rows)
+        obs = None if obs is None else self._t(obs)
+        actions = None if actions is None else self._t(actions)
+        if traj.dim() != 5 or rows.dim() != 3 or not traj.is_contiguous() or not rows.is_contiguous():
+            raise ValueError("constrain_returns: traj %r, rows %r: expected contiguous [H,m,n,p,D] and [m,n,p]" % (tuple(traj.shape), tuple(rows.shape)))
+        H, m, n, p, D = traj.shape
+        if (H, p, D) != (self.H, self.p, self.D) or tuple(rows.shape) != (m, n, p):
+            raise ValueError("constrain_returns: traj %r, rows %r do not agree with the engine (H=%d, p=%d, D=%d)"
+                             % (tuple(traj.shape), tuple(rows.shape), self.H, self.p, self.D))
+        if obs is not None and tuple(obs.shape) != (m, D) or actions is not None and tuple(actions.shape) != (m, n, H, self.A):
+            raise ValueError("constrain_returns: obs %r, actions %r: expected [%d,%d] and [%d,%d,%d,%d]"
+                             % (None if obs is None else tuple(obs.shape), None if actions is None else tuple(actions.shape), m, D, m, n, H, self.A))
+        if out is None:
+            out = torch.empty_like(rows)
+        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("constrain_returns: out %r, expected contiguous float32 %r" % (tuple(out.shape), (m, n, p)))
+        first = torch.empty((m, n, p), dtype=torch.int32, device=self.device)
+        viol = torch.empty((m, n, p), dtype=torch.int32, device=self.device)
+        self._check(self.lib.cadm_constrain_returns(self._ctx, ct.byref(prm), ptr(traj), ptr(obs), ptr(actions), ptr(rows), m, n, ptr(out),
+                                                    ptr(first), ptr(viol), self.stream), "cadm_constrain_returns")
+        return out, first, viol
+
+    def constrained_plan(self, constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0,
+                         call=0, out=None, want_best_return=False):
+        """`cadm_constrained_plan`: the loop of `scored_plan` with `constraints` (`constraint_params`; None = none, and `scored_plan`'s
+        launches) rewriting every iteration's particle returns before the score.  Arguments behind `constraints` as `scored_plan`; with
+        constraints the workspace carries the trajectory view (`cadm_constrained_workspace_bytes`), cached apart from the plain ones."""
+        mppi = isinstance(params, _lib.MppiParams)
+        if not mppi:
+            full = _lib.MppiParams()
+            full.icem, full.temperature = params, 1.0
+            params = full
+        head = (None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi), ct.byref(params))
+        return self._loop_plan("constrained_plan", self.lib.cadm_constrained_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None)
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D):

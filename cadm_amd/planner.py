@@ -12,7 +12,7 @@ What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
   * `PlanOptions`: what a model's `cem_*` kwargs mean -- their checks, the switches, and the ctypes structs `HipEngine.opt_in_plan` hands to the library;
-  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`) one launch at a time, for the same purposes;
+  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
@@ -25,25 +25,40 @@ import torch
 from .engine import HipEngine
 
 
+FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/planner.h CADM_FORECAST_IT (tests/test_constraint_ref.py pairs the two)
+
+
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
-                                                       "params score_params")):
+                                                       "params score_params constraints constraint_params")):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
-    `score`: None, or (mode name, kappa, k)."""
+    `score`: None, or (mode name, kappa, k).  `constraints`: None, or (the list of dict(dim=, lo=, hi=), mode name, weight), with
+    `constraint_params` the `ConstraintParams` built from it (None: no state constraints, and the loop records no trajectory)."""
     __slots__ = ()
 
     @staticmethod
     def from_kwargs(cem_noise_beta=0.0, cem_keep_elites=0, cem_decay=1.0, cem_return="mean", cem_add_mean=False, cem_update="cem",
                     cem_temperature=1.0, cem_temperature_relative=False, cem_score="mean", cem_risk=None, use_cem=False, discrete=False,
-                    process_group=None, n_particles=20):
+                    process_group=None, n_particles=20, cem_constraints=None, cem_constraint_mode="penalty", cem_constraint_weight=None):
         """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
         everything that needs no engine -- and folded into a `PlanOptions`."""
         if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
-                bool(cem_temperature_relative), cem_score, cem_risk) == (0.0, 0, 1.0, "mean", False, "cem", 1.0, False, "mean", None):
+                bool(cem_temperature_relative), cem_score, cem_risk, cem_constraints, cem_constraint_mode,
+                cem_constraint_weight) == (0.0, 0, 1.0, "mean", False, "cem", 1.0, False, "mean", None, None, "penalty", None):
             return None
         if not use_cem:
             raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
-                             "cem_score / cem_risk configure the CEM planner: they need use_cem=True")
+                             "cem_score / cem_risk / cem_constraints configure the CEM planner: they need use_cem=True")
+        constraints = cparams = None
+        if cem_constraints is None:
+            if cem_constraint_mode != "penalty" or cem_constraint_weight is not None:
+                raise ValueError("cem_constraint_mode / cem_constraint_weight configure state constraints: they need cem_constraints")
+        else:
+            if cem_constraint_weight is None:
+                raise ValueError("cem_constraints need a cem_constraint_weight (finite, >= 0): the penalty per violating step, or at termination")
+            cparams = HipEngine.constraint_params(cem_constraints, cem_constraint_mode, cem_constraint_weight)
+            cons = [cem_constraints] if isinstance(cem_constraints, dict) else list(cem_constraints)
+            constraints = (tuple(dict(c) for c in cons), cem_constraint_mode, float(cem_constraint_weight))
         score = None
         if cem_score not in ("mean", "mean_std", "member_std", "cvar"):
             raise ValueError("cem_score must be 'mean', 'mean_std', 'member_std' or 'cvar', got %r" % (cem_score,))
@@ -85,7 +100,7 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
         mppi = dict(temperature=float(cem_temperature), relative=bool(cem_temperature_relative))
         params = HipEngine.mppi_params(**mppi, **icem) if cem_update == "mppi" else HipEngine.icem_params(**icem)
         return PlanOptions(update=cem_update, score=score, params=params, score_params=None if score is None else HipEngine.score_params(*score),
-                           **mppi, **icem)
+                           constraints=constraints, constraint_params=cparams, **mppi, **icem)
 
 
 class Shard:
@@ -211,11 +226,13 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
 
 def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
               add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False,
-              update="cem", temperature=1.0, relative=False, score=None):
+              update="cem", temperature=1.0, relative=False, score=None, constraints=None):
     """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
     tests with injected draws and for diagnostics.  update="mppi": the loop of `cadm_mppi_plan` -- the elite ids come from an elite
     refit into copies of mean / var, the distribution from `mppi_refit`.  score: a `HipEngine.score_params` (`cadm_scored_plan`; None: the
-    particle mean) -- `cand`, the elites and the best return are then by score.  z / xi / eps: optional per-iteration lists of injected truncated-normal draws
+    particle mean) -- `cand`, the elites and the best return are then by score.  constraints: a `HipEngine.constraint_params`
+    (`cadm_constrained_plan`; None: none) -- every rollout then records its trajectories and `constrain_returns` rewrites `rows` before the
+    score; `return_info` carries `traj`, `first_violation`, `violations` and the rollout's own `rows_raw`.  z / xi / eps: optional per-iteration lists of injected truncated-normal draws
     [m,n_it,H,A] (noise_beta == 0), spectral draws [m,n_it,A,H] (noise_beta > 0) and head noise [H,m,n_it,p,D].  carry [m,K,H,A] /
     carry_valid [m] int32 are read at iteration 0 and rewritten IN PLACE after the last refit, as the library does."""
     obs = engine._t(obs)
@@ -239,7 +256,14 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
             engine.icem_inject(actions, kept)
         if last and add_mean_last:
             engine.icem_inject(actions, mean.clamp(lo, hi).unsqueeze(1).contiguous(), slot0=K)
-        rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
+        extra = {}
+        if constraints is None:
+            rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
+        else:
+            raw, traj = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it,
+                                               want_traj=True)
+            rows, first, viol = engine.constrain_returns(traj, raw, constraints, obs=obs, actions=actions)
+            extra = dict(traj=traj, first_violation=first, violations=viol, rows_raw=raw)
         cand = engine.particle_mean(rows) if score is None else engine.particle_score(rows, score)
         if update == "mppi":
             elites = engine.cem_refit(cand.unsqueeze(0), actions, mean.clone(), var.clone(), want_elites=True)
@@ -253,7 +277,7 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
                 carry.copy_(kept)
                 carry_valid.fill_(1)
         if return_info:
-            info.append(dict(actions=actions, rows=rows, cand=cand, elites=elites, kept=kept, mean=mean.clone(), var=var.clone()))
+            info.append(dict(actions=actions, rows=rows, cand=cand, elites=elites, kept=kept, mean=mean.clone(), var=var.clone(), **extra))
     plan_mean = mean.clamp(lo, hi)
     plan = best_seq if return_best else plan_mean
     return (plan, info, dict(best_ret=best_ret, best_seq=best_seq, plan_mean=plan_mean)) if return_info else plan

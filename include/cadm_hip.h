@@ -389,6 +389,52 @@ int cadm_scored_plan(cadm_ctx* ctx, const cadm_score_params* score, int update, 
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                      float* best_return_out, void* stream);
 
+/* State constraints and early termination (no reference twin, OPT-IN): tell the opt-in loop "do not go there".  A constraint reads ONE
+ * observation dim: a state is healthy iff x[dim[k]] > lo[k] && x[dim[k]] < hi[k] for every k < n, compared in float32 (a missing side
+ * is -inf / +inf).  A value equal to a bound violates; NaN or +-inf in a constrained dim violates; a non-finite value in any other dim
+ * is not looked at.  Checked is the POST-step state of every step t = 0 .. H-1 of a recorded trajectory (traj [H,m,n,p,D], the layout
+ * of cadm_rollout_returns' traj_out, H and p the ctx's); the observation a call starts from is never checked.  Per particle row:
+ *   violations [m,n,p]       int32: the number of steps whose post-step state violates
+ *   first_violation [m,n,p]  int32: the first such step, H if there is none
+ *   CADM_CONSTRAIN_PENALTY    rows_out = rows_in - weight * (float)violations     (one fp32 multiply and one subtract)
+ *   CADM_CONSTRAIN_TERMINATE  rows_out = (r_0 + ... + r_tau) - weight, tau = first_violation < H: r_t the particle's step reward as
+ *                             cadm_forecast_stats evaluates it (pre-step state: obs at t = 0, else traj[t-1]; post-step state
+ *                             traj[t]; the raw action), added in step order from r_0.  The step that leaves the region still pays;
+ *                             whatever traj holds after tau, a blow-up included, does not reach the return.
+ * A row without a violation keeps rows_in's bits in both modes: a constraint that never binds changes no plan.
+ * cadm_constrain_returns: rows_in / rows_out [m,n,p] (rows_out may alias rows_in); first_violation_out / violations_out may each be
+ * NULL; obs [m,D] and actions [m,n,H,A] (raw) are read in TERMINATE mode only and may be NULL in PENALTY mode.  traj is read at most
+ * once; a row's counters and partial sum are one thread's chain in step order (csrc/constrain.hip), no floating-point atomics: the
+ * same bits run to run, whatever m, n and the row's position.  Needs no workspace.
+ * Refusals, before any HIP call: CADM_EINVAL for n outside 1 .. CADM_MAX_CONSTRAINTS, a dim outside 0 .. D-1, lo >= hi, a NaN bound,
+ * both sides infinite, an unknown mode, a weight that is negative or not finite, a discrete ctx (cartpole), a sharded ctx, a D whose
+ * LDS tiles (2 x 64 x D floats) exceed 48 KiB; CADM_ESTATE for a CADM_ENV_SPEC ctx before cadm_set_env_spec in TERMINATE mode. */
+#define CADM_MAX_CONSTRAINTS 16
+#define CADM_CONSTRAIN_PENALTY 0
+#define CADM_CONSTRAIN_TERMINATE 1
+typedef struct cadm_constraint_params {
+    int32_t n;              /* 1 .. CADM_MAX_CONSTRAINTS */
+    int32_t mode;           /* CADM_CONSTRAIN_* */
+    float weight;           /* finite, >= 0 */
+    int32_t dim[CADM_MAX_CONSTRAINTS];
+    float lo[CADM_MAX_CONSTRAINTS];
+    float hi[CADM_MAX_CONSTRAINTS];
+} cadm_constraint_params;
+int cadm_constrain_returns(cadm_ctx* ctx, const cadm_constraint_params* params, const float* traj, const float* obs,
+                           const float* actions, const float* rows_in, int m, int n, float* rows_out, int32_t* first_violation_out,
+                           int32_t* violations_out, void* stream);
+/* The loop of cadm_scored_plan under constraints: every iteration's rollout records its trajectories into a view of the workspace,
+ * and cadm_constrain_returns rewrites the particle returns in place before cadm_particle_score sees them; everything else composes
+ * unchanged (the elites, the best plan and best_return_out are by the constrained score).  constraints NULL: exactly the launches of
+ * cadm_scored_plan.  Refusals: those of cadm_scored_plan and of cadm_constrain_returns.
+ * workspace: cadm_constrained_workspace_bytes(ctx, m, n, K, mppi) bytes -- cadm_icem_workspace_bytes (mppi == 0) or
+ * cadm_mppi_workspace_bytes (mppi != 0) plus one view of H m n p D floats at the end (0 for bad arguments). */
+size_t cadm_constrained_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi);
+int cadm_constrained_plan(cadm_ctx* ctx, const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
+                          const cadm_mppi_params* params, const float* obs, const float* cp_obs, const float* cp_act,
+                          const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                          uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
+
 /* One training step = sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
