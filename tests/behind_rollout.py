@@ -1,0 +1,58 @@
+"""Inputs for the kernels behind the rollout (csrc/forecast.hip, csrc/constrain.hip) on the built-in kinds other than halfcheetah --
+test infrastructure shared by tests/test_forecast_ref.py (CPU) and tests/test_gpu_behind_rollout_envs.py.
+
+kind           engine p, H   synthetic m, n   rows                      seed   constrained dims, band
+ant            10, 5         3, 7             210: 64, 64, 64, 18       21     (0, 27), mean +- 1.8 std
+slim_humanoid  15, 3         2, 5             150: 64, 64, 22           22     (1, 44), mean +- 1.5 std
+pendulum       5, 5          3, 9             135: 64, 64, 7            23     (2, 0),  mean +- 1.8 std
+
+ant: p * D = 280 > 256, step spans always 16-byte aligned.  slim_humanoid: an odd D, spans aligned at even steps only, the largest
+terminate-mode tiles of any built-in kind.  pendulum: D = 3, spans of mixed alignment."""
+import numpy as np
+
+KINDS = {      # kind: (D, A, engine p, H, m, n, seed, constrained dims, band width in std)
+    "ant": (28, 8, 10, 5, 3, 7, 21, (0, 27), 1.8),
+    "slim_humanoid": (45, 17, 15, 3, 2, 5, 22, (1, 44), 1.5),
+    "pendulum": (3, 1, 5, 5, 3, 9, 23, (2, 0), 1.8),
+}
+HALFCHEETAH_B = (2, 8, 2, 1, 20, 18, 6)      # tests/test_gpu_forecast.py's shape (b): synth_traj's arguments
+
+
+def synth_traj(seed, H, m, n, p, D, A):
+    """(traj [H,m,n,p,D], obs [m,D], actions [m,n,H,A]) float32: per-dim scales 0.5 .. 3 and offsets of order 1."""
+    rng = np.random.default_rng(seed)
+    traj = (rng.standard_normal((H, m, n, p, D)) * rng.uniform(0.5, 3.0, D) + rng.standard_normal(D)).astype(np.float32)
+    return traj, rng.standard_normal((m, D)).astype(np.float32), rng.uniform(-1, 1, (m, n, H, A)).astype(np.float32)
+
+
+def band(traj, d, k, lower_only=False):
+    """dim d inside mean +- k std of that dim over the array (lower_only: above mean - k std)"""
+    mu, sd = float(traj[..., d].mean()), float(traj[..., d].std())
+    return dict(dim=d, lo=mu - k * sd) if lower_only else dict(dim=d, lo=mu - k * sd, hi=mu + k * sd)
+
+
+def alive_share(traj, obs):
+    """slim_humanoid: the share of PRE-step states (obs at step 0, traj[t - 1] after) whose dim 1 lies inside (1, 2)"""
+    H, m, n, p, _ = traj.shape
+    pre1 = np.concatenate([np.broadcast_to(obs[None, :, None, None, 1], (1, m, n, p)), traj[:-1, ..., 1]], axis=0)
+    return float(((pre1 > np.float32(1.0)) & (pre1 < np.float32(2.0))).mean())
+
+
+def kind_inputs(kind):
+    """(traj, obs, actions, constraints) of one kind, with the adjustments that make its reward terms bite:
+    slim_humanoid -- dim 1 redrawn around the alive bonus's interval (1, 2), two observations inside / outside it;
+    pendulum -- actions scaled by 3 (a third of them beyond the torque clip at +-2), pre-step states planted exactly on atan2's
+    branch cut, (x, y) = (-1, +0.0) and (-1, -0.0), and at its origin (0, 0)."""
+    D, A, p, H, m, n, seed, dims, k = KINDS[kind]
+    traj, obs, acts = synth_traj(seed, H, m, n, p, D, A)
+    if kind == "slim_humanoid":
+        traj[..., 1] = (1.5 + 0.5 * np.random.default_rng(99).standard_normal(traj.shape[:-1])).astype(np.float32)
+        obs[:2, 1] = [1.2, 2.3]
+        assert 0.2 <= alive_share(traj, obs) <= 0.8, "slim_humanoid: alive share %.2f" % alive_share(traj, obs)
+    if kind == "pendulum":
+        acts = (acts * np.float32(3.0)).astype(np.float32)
+        assert (np.abs(acts) > 2.0).mean() > 0.1, "pendulum: %.2f of the actions are clipped" % (np.abs(acts) > 2.0).mean()
+        obs[0, :2] = [-1.0, 0.0]                 # step 0's pre-step state of env 0: theta = +pi
+        traj[0, 1, 0, 0, :2] = [-1.0, -0.0]      # step 1's pre-step state of row (1, 0, 0): theta = -pi
+        traj[1, 2, 0, 1, :2] = [0.0, 0.0]        # step 2's pre-step state of row (2, 0, 1): atan2(0, 0) = 0
+    return traj, obs, acts, [band(traj, d, k) for d in dims]

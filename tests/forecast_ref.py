@@ -2,7 +2,7 @@
 
 States are reduced in float64.  Step rewards come from the env's own closure (`EnvDecl.reward`, or the oracle env's `reward`) on
 FLOAT32 arrays: threshold terms (inside / outside) then compare the same float32 numbers the kernel compares; their statistics are
-taken in float64."""
+taken in float64.  `reward_bound` says how far a float32 evaluation of a step reward may lie from its float64 value, per env kind."""
 import numpy as np
 
 from cadm_amd.env_spec import EnvDecl, restate
@@ -42,6 +42,30 @@ def reward_terms(env, traj, obs, actions):
         S += np.abs(spec.bonus)
         T += 1
     return T, S
+
+
+def pendulum_angle(pre):
+    """float64 normalised angle of pre-step states [..., 3]: ((atan2(y, x) + pi) floormod 2 pi) - pi, in [-pi, pi)."""
+    x = np.asarray(pre, np.float64)
+    return np.mod(np.arctan2(x[..., 1], x[..., 0]) + np.pi, 2.0 * np.pi) - np.pi
+
+
+def reward_bound(env, traj, obs, actions):
+    """b [m,n,H,p]: how far a float32 evaluation of the step reward may lie from its float64 value, for any continuous kind.
+    halfcheetah, ant, slim_humanoid and an EnvDecl: (T + 3) 2^-23 S of `reward_terms`.
+    pendulum: 6 2^-23 S + 4 |tn| 2^-20 with S = tn^2 + 0.1 thetadot^2 + 0.001 clip(a, +-2)^2 and tn the float64 normalised angle of
+    the pre-step state.  The second term is the angle's own rounding, which enters through tn^2 (d tn^2 = 2 |tn| d tn, on both of two
+    compared sides): atan2f within 2 ulp at |theta| <= pi (2^-21), the addition of pi (2^-22), the final subtraction (2^-23), below
+    2^-20 together.  The float32 pi cancels between the addition and the subtraction; the branch cut does not matter, the cost reads
+    tn^2, which is continuous across it."""
+    if env != "pendulum":
+        T, S = reward_terms(env, traj, obs, actions)
+        return (T + 3) * 2.0 ** -23 * S
+    pre, _ = pre_post(traj, obs)
+    tn = pendulum_angle(pre)
+    tq = np.clip(actions.astype(np.float64)[..., 0], -2.0, 2.0)[:, :, :, None]
+    S = tn ** 2 + 0.1 * pre[..., 2].astype(np.float64) ** 2 + 0.001 * tq ** 2
+    return 6 * 2.0 ** -23 * S + 4 * np.abs(tn) * 2.0 ** -20
 
 
 def diverged_step(traj):

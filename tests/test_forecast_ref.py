@@ -1,10 +1,14 @@
 """CPU: the float64 restatement of the plan forecast (tests/forecast_ref.py) against a brute-force loop, the variance identity
-total = epistemic + aleatoric, and the divergence rule."""
+total = epistemic + aleatoric, the divergence rule, and the step-reward bound (`reward_bound`) of every built-in continuous kind."""
+import math
+
 import numpy as np
 import pytest
 
 from cadm_amd.env_spec import restate
-from forecast_ref import brute_force, diverged_step, forecast_ref, reward_terms, step_rewards
+import behind_rollout as br
+import constraint_ref as cref
+from forecast_ref import brute_force, diverged_step, forecast_ref, pendulum_angle, pre_post, reward_bound, reward_terms, step_rewards
 from oracle import envs as oenvs
 
 STATE_KEYS = ("mean", "member_mean", "var_total", "var_epistemic", "var_aleatoric", "lo", "hi")
@@ -76,3 +80,80 @@ def test_rewards_use_pre_and_post_step_states():
     T, S = reward_terms("halfcheetah", traj, obs, acts)
     assert T == 2 and S.shape == (m, n, H, p) and (S >= np.abs(r) - 1e-6).all()
     np.testing.assert_array_equal(step_rewards(restate("halfcheetah"), traj, obs, acts), r)
+
+
+def _inputs(kind):
+    if kind == "halfcheetah":
+        return br.synth_traj(*br.HALFCHEETAH_B) + (None,)
+    return br.kind_inputs(kind)
+
+
+@pytest.mark.parametrize("kind", ["halfcheetah", "ant", "slim_humanoid", "pendulum"])
+def test_reward_bound_holds_float32_to_float64(kind):
+    """On the inputs the GPU tests use, the env's closure on float32 arrays lies within `reward_bound` of the same closure on float64
+    arrays (thresholds compare the same numbers in both: the float64 arrays are the float32 values).  Worst |err| / bound with
+    numpy's float32: halfcheetah 0.21, ant 0.14, slim_humanoid 0.16, pendulum 0.16."""
+    traj, obs, acts, cons = _inputs(kind)
+    env = oenvs.make_env(kind)
+    pre, post = pre_post(traj, obs)
+    m, n, H, p, _ = pre.shape
+    act = np.broadcast_to(acts.astype(np.float64)[:, :, :, None, :], (m, n, H, p, acts.shape[-1]))
+    r64 = env.reward(pre.astype(np.float64), act, post.astype(np.float64))
+    assert r64.dtype == np.float64 and r64.shape == (m, n, H, p)
+    b = reward_bound(kind, traj, obs, acts)
+    assert b.shape == (m, n, H, p) and (b > 0).all() and np.isfinite(b).all()
+    err = np.abs(step_rewards(env, traj, obs, acts).astype(np.float64) - r64)
+    print("%s: float32 closure vs float64 closure, worst |err| / bound %.3f" % (kind, (err / b).max()))
+    assert (err <= b).all(), "%s: worst |err| / bound %.3f" % (kind, (err / b).max())
+    if kind != "pendulum":
+        T, S = reward_terms(kind, traj, obs, acts)
+        np.testing.assert_array_equal(b, (T + 3) * 2.0 ** -23 * S)          # the bound the other kinds have always had
+        assert T == {"halfcheetah": 2, "ant": 3, "slim_humanoid": 3}[kind]
+
+
+def test_reward_bound_of_a_declared_env_is_unchanged():
+    spec = restate("ant")
+    traj, obs, acts, _ = br.kind_inputs("ant")
+    T, S = reward_terms(spec, traj, obs, acts)
+    np.testing.assert_array_equal(reward_bound(spec, traj, obs, acts), (T + 3) * 2.0 ** -23 * S)
+    np.testing.assert_array_equal(reward_bound(spec, traj, obs, acts), reward_bound("ant", traj, obs, acts))
+
+
+def test_pendulum_bound_by_hand_and_on_the_cut():
+    """The planted pre-step states: (-1, +0.0) and (-1, -0.0) both normalise to -pi (the floormod folds +pi onto -pi), (0, 0) to 0,
+    where the bound has no angle term left.  One entry of the bound by plain arithmetic."""
+    traj, obs, acts, _ = br.kind_inputs("pendulum")
+    pre, _ = pre_post(traj, obs)
+    tn = pendulum_angle(pre)
+    assert tn.min() >= -np.pi and tn.max() < np.pi
+    assert np.signbit(pre[1, 0, 1, 0, 1]) and not np.signbit(pre[0, 0, 0, 0, 1])
+    np.testing.assert_array_equal(tn[0, :, 0, :], -np.pi)                     # env 0, step 0: the observation (-1, +0.0)
+    assert tn[1, 0, 1, 0] == -np.pi and tn[2, 0, 2, 1] == 0.0
+    b = reward_bound("pendulum", traj, obs, acts)
+    th, a = float(pre[2, 0, 2, 1, 2]), float(np.clip(acts[2, 0, 2, 0], -2, 2))
+    assert b[2, 0, 2, 1] == 6 * 2.0 ** -23 * (0.1 * th * th + 0.001 * a * a)
+    x, y, th, a = [float(v) for v in pre[1, 3, 2, 4]] + [float(acts[1, 3, 2, 0])]
+    t = (math.atan2(y, x) + math.pi) % (2 * math.pi) - math.pi
+    want = 6 * 2.0 ** -23 * (t * t + 0.1 * th * th + 0.001 * min(max(a, -2.0), 2.0) ** 2) + 4 * abs(t) * 2.0 ** -20
+    assert abs(b[1, 3, 2, 4] - want) <= 1e-12 * want
+    # the float32 closure on the cut: both signs of zero give the same cost, pi^2 to float32 rounding
+    r = step_rewards(oenvs.make_env("pendulum"), traj, obs, acts)
+    assert abs(float(r[0, 0, 0, 0]) + np.pi ** 2 + 0.1 * float(obs[0, 2]) ** 2 + 0.001 * min(abs(float(acts[0, 0, 0, 0])), 2.0) ** 2) <= b[0, 0, 0, 0]
+
+
+@pytest.mark.parametrize("kind", sorted(br.KINDS))
+def test_inputs_meet_the_coverage_condition(kind):
+    """What the GPU tests assert again on their own counters, here on the numpy restatement alone: 20 % .. 80 % of the rows violate,
+    one first at step 0, one first at step H - 1; the rows fill several workgroups of 64 and leave a partial one."""
+    traj, obs, acts, cons = br.kind_inputs(kind)
+    H, m, n, p, D = traj.shape
+    first, viol = cref.counters(traj, cons)
+    share = float((first < H).mean())
+    print("%s: %.2f of %d rows violate" % (kind, share, first.size))
+    assert 0.2 <= share <= 0.8 and (first == 0).any() and (first == H - 1).any()
+    assert first.size > 128 and first.size % 64 != 0
+    assert [c["dim"] for c in cons] == list(br.KINDS[kind][7])
+    if kind == "slim_humanoid":
+        assert 0.2 <= br.alive_share(traj, obs) <= 0.8
+    if kind == "pendulum":
+        assert (np.abs(acts) > 2.0).mean() > 0.1

@@ -3,7 +3,8 @@ synthetic trajectories and at its edges, the fused loop (`cadm_constrained_plan`
 binds and one that does, the class route with `constraint_check`, and the refusals.
 
 Geometries: the compiled-in halfcheetah 200 x 4 kernel and tests/test_gpu_horizon.py's hopper_like declaration (the JIT module that
-file and tests/test_gpu_forecast.py build).  Numpy restatement: tests/constraint_ref.py.
+file and tests/test_gpu_forecast.py build); the fused loop in terminate mode also on ant, slim_humanoid and pendulum (the isolated
+kernel on those: tests/test_gpu_behind_rollout_envs.py).  Numpy restatement: tests/constraint_ref.py.
 
 Bounds.  Counters and `penalty` rows (w = 4: a power of two, the product is exact) are compared bit for bit.  A `terminate` row that
 first violates at tau is a chain of tau + 1 step rewards; each is held to b_t = (T + 3) 2^-23 S_t of the env's closure (the bound
@@ -26,13 +27,13 @@ from cadm_amd import synth
 from cadm_amd._lib import ptr
 from cadm_amd.engine import HipEngine
 from cadm_amd.env_spec import EnvDecl
-from forecast_ref import reward_terms
+from behind_rollout import band, synth_traj
+from forecast_ref import reward_bound
 from helpers import _np, make_engine, plan_model, zero_carry
 from oracle import envs as oenvs
 
 pytestmark = pytest.mark.gpu
 
-U23 = 2.0 ** -23
 M, N, KE, ITERS = 2, 24, 8, 3
 NEVER = [dict(dim=0, lo=-3e38, hi=3e38), dict(dim=5, lo=-3e38, hi=3e38)]
 
@@ -49,20 +50,8 @@ def hopper_like():          # tests/test_gpu_horizon.py's declaration (same geom
                    ctrl_cost=0.001, bonus=1.0)
 
 
-def synth_traj(seed, H, m, n, p, D, A):          # tests/test_gpu_forecast.py's recipe
-    rng = np.random.default_rng(seed)
-    traj = (rng.standard_normal((H, m, n, p, D)) * rng.uniform(0.5, 3.0, D) + rng.standard_normal(D)).astype(np.float32)
-    return traj, rng.standard_normal((m, D)).astype(np.float32), rng.uniform(-1, 1, (m, n, H, A)).astype(np.float32)
-
-
 def _bits(x):
     return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
-def band(traj, d, k, lower_only=False):
-    """dim d inside mean +- k std of that dim over the array (lower_only: above mean - k std)"""
-    mu, sd = float(traj[..., d].mean()), float(traj[..., d].std())
-    return dict(dim=d, lo=mu - k * sd) if lower_only else dict(dim=d, lo=mu - k * sd, hi=mu + k * sd)
 
 
 def coverage(first, H, what):
@@ -117,6 +106,25 @@ def hc5(gpu):
         eng.close()
 
 
+OTHER_KINDS = dict(ant=(5, (0, 27)), slim_humanoid=(3, (1, 44)), pendulum=(5, (2, 0)))      # kind: (H, constrained dims)
+
+
+@pytest.fixture(scope="module")
+def others(gpu):
+    """ant, slim_humanoid and pendulum as hc5[True]: context, trained-like, p = 5, 8 elites, 3 CEM iterations, H = 5, 3, 5.
+    kind -> (problem, engine), built when first asked for."""
+    built = {}
+
+    def get(kind):
+        if kind not in built:
+            prob = synth.make_problem(env=kind, context=True, E=5, m=M, H=OTHER_KINDS[kind][0], seed=3, trained_like=True)
+            built[kind] = (prob, make_engine(prob, p=5, num_elites=KE, num_cem_iters=ITERS))
+        return built[kind]
+    yield get
+    for _, eng in built.values():
+        eng.close()
+
+
 def run(eng, traj, rows, cons, mode, w, obs, acts, out=None):
     r, f, v = eng.constrain_returns(traj, rows, cons, mode, w, obs=obs, actions=acts, out=out)
     torch.cuda.synchronize()
@@ -124,12 +132,12 @@ def run(eng, traj, rows, cons, mode, w, obs, acts, out=None):
 
 
 def terminate_bound(terms_env, traj, obs, acts, first, ref=None):
-    """(tau + 1) max_{t <= tau} b_t per row [m,n,p], b = (T + 3) 2^-23 S; 0 where nothing violates.  ref: the float64 reference, to add
+    """(tau + 1) max_{t <= tau} b_t per row [m,n,p], b = `reward_bound` ((T + 3) 2^-23 S; pendulum: plus its angle's rounding); 0 where
+    nothing violates.  ref: the float64 reference, to add
     the rounding of the final subtraction of w, 2^-24 |ref| (see the module docstring)"""
     H = traj.shape[0]
     with np.errstate(all="ignore"):
-        T, S = reward_terms(terms_env, traj, obs, acts)
-    b = np.moveaxis((T + 3) * U23 * S, 2, 0)                                         # [H,m,n,p]
+        b = np.moveaxis(reward_bound(terms_env, traj, obs, acts), 2, 0)              # [H,m,n,p]
     tau = np.minimum(first, H - 1)
     upto = np.where(np.arange(H)[:, None, None, None] <= tau[None], b, 0.0)          # steps after tau are not read: their b may be NaN
     return (tau + 1) * upto.max(axis=0) + (0.0 if ref is None else 2.0 ** -24 * np.abs(ref))
@@ -324,19 +332,28 @@ def iteration0_traj(eng, prob, beta, seed, call):
 
 LOOP = [      # mode, env, context
     ("penalty", "hopper", True), ("penalty", "halfcheetah", False), ("terminate", "halfcheetah", True), ("terminate", "halfcheetah", False),
-    ("terminate", "hopper", True),
+    ("terminate", "hopper", True), ("terminate", "ant", True), ("terminate", "slim_humanoid", True), ("terminate", "pendulum", True),
 ]
 
 
 @pytest.mark.parametrize("mode,env,context", LOOP, ids=["%s-%s-%s" % (r[0], r[1], "cadm" if r[2] else "vanilla") for r in LOOP])
-def test_fused_equals_stepwise(hop, hc5, mode, env, context):
+def test_fused_equals_stepwise(hop, hc5, others, mode, env, context):
     """`cadm_constrained_plan` with device RNG == the same loop one launch at a time (`planner.icem_plan(..., constraints=...)`), bit for
     bit over three consecutive calls: plan, best return, carry, carry-valid.  penalty: the elite refit, the mean, white noise, K = 0;
     terminate: MPPI, cvar, coloured noise, two kept elites, decay 1.25, the best plan.  Every stepwise iteration is held to the numpy
-    restatement on its own recorded trajectory."""
+    restatement on its own recorded trajectory.  terminate: a row that first violates at the LAST step has paid every step, so its
+    partial sum is the rollout's own return -- rows + w is held to rows_raw within the row's bound plus the rounding of the rollout's
+    sum, 2^-24 |raw|: the step reward of step_reward.h against the rollout kernels', for every env kind.
+
+    Measured on an MI355X, worst |err| / bound over the iterations of call 1 -- terminated rows: halfcheetah cadm 0.569, vanilla 0.148,
+    hopper 0.023, ant 0.413, slim_humanoid 0.056, pendulum 0.104; rows + w against rows_raw: halfcheetah cadm 0.087, vanilla 0.021,
+    hopper 0.047, ant 0.000 (the same bits), slim_humanoid 0.019, pendulum 0.048."""
     if env == "hopper":
         spec, prob, eng = hop
         closure, H, dims = spec, 3, (0, 3)
+    elif env in OTHER_KINDS:
+        prob, eng = others(env)
+        closure, spec, (H, dims) = oenvs.make_env(env), env, OTHER_KINDS[env]
     else:
         prob, eng = hc5[context]
         closure, spec, H, dims = oenvs.make_env("halfcheetah"), "halfcheetah", 5, (1, 7)
@@ -387,6 +404,17 @@ def test_fused_equals_stepwise(hop, hc5, mode, env, context):
                     print("%s iteration %d: terminated rows, worst |err| / bound %.3f over %d rows" % (what, it, (err / lim[~alive]).max(), err.size))
                 assert (err <= lim[~alive]).all(), "%s: terminated rows of call %d iteration %d, worst |err| / bound %.3f" % (
                     what, call, it, (err / lim[~alive]).max())
+                last = first == H - 1                                                  # a full-length partial sum: the rollout's return
+                if call == 1 and it == 0:
+                    assert last.any()
+                if last.any():
+                    full = np.abs(rows.astype(np.float64) + float(np.float32(4.0)) - raw)[last]
+                    lim_full = (lim + 2.0 ** -24 * np.abs(raw))[last]
+                    if call == 1:
+                        print("%s iteration %d: rows + w vs rows_raw where the first violation is at step H - 1, worst |err| / bound %.3f over "
+                              "%d rows" % (what, it, (full / lim_full).max(), full.size))
+                    assert (full <= lim_full).all(), "%s: rows + w vs rows_raw of call %d iteration %d, worst |err| / bound %.3f" % (
+                        what, call, it, (full / lim_full).max())
                 want = rows
                 # the score step against the float64 reference: cvar is 1-Lipschitz in the largest row error, plus its own k + 1 roundings
                 ref_rows = np.where(alive, raw.astype(np.float64), ref)

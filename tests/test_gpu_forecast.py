@@ -5,6 +5,9 @@ Shapes: (a) hopper_like D = 11, p = 5, E = 5, H = 3, m = 3, n = 2 -- one particl
 16-byte alignment; (b) halfcheetah D = 18, p = 20, E = 5, H = 8, m = 2, n = 1; (c) E = 1, p = 4; (d) p = 1.  The composite runs
 halfcheetah with context at E = 5, p = 10, H = 8, m = 3, n = 2 (the compiled-in 200 x 4 kernel) and hopper_like, both with injected
 noise.
+At the kernel's size limits (section 6): the last p its LDS carve accepts and the first it refuses, for halfcheetah (p = 323 / 324: the
+per-particle loops take a second stride of the 256 threads) and slim_humanoid (p = 133 / 134); particles that agree, wholly and
+inside a member; order statistics full of ties.  Ant, slim_humanoid and pendulum: tests/test_gpu_behind_rollout_envs.py.
 
 Bounds of the isolated kernel, from its particle-0 form (every deviation x_j - x_0 - mean carries at most p + 2 roundings of size
 2^-24 R, R = max_j |x_j - x_0|): means within (p + 4) 2^-24 max_j |x_j| of float64, variances within 4 (p + 4) 2^-24 R^2."""
@@ -17,7 +20,8 @@ import torch
 from cadm_amd import _lib, synth
 from cadm_amd._lib import ptr
 from cadm_amd.env_spec import EnvDecl
-from forecast_ref import forecast_ref, reward_terms, step_rewards
+from behind_rollout import synth_traj
+from forecast_ref import forecast_ref, reward_bound, step_rewards
 from helpers import make_engine, oracle_problem, spec_oracle
 from oracle import envs as oenvs
 from oracle import nets as onets
@@ -25,7 +29,7 @@ from oracle import planner as oplanner
 
 pytestmark = pytest.mark.gpu
 
-U24, U23 = 2.0 ** -24, 2.0 ** -23
+U24 = 2.0 ** -24
 VARS = ("var_total", "var_epistemic", "var_aleatoric")
 STATE = ("mean", "member_mean") + VARS + ("lo", "hi")
 REWARD = ("reward_mean", "reward_var", "reward_member", "returns")
@@ -51,12 +55,6 @@ def _np(out):
 
 def _bits(a):
     return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def synth_traj(seed, H, m, n, p, D, A):
-    rng = np.random.default_rng(seed)
-    traj = (rng.standard_normal((H, m, n, p, D)) * rng.uniform(0.5, 3.0, D) + rng.standard_normal(D)).astype(np.float32)
-    return traj, rng.standard_normal((m, D)).astype(np.float32), rng.uniform(-1, 1, (m, n, H, A)).astype(np.float32)
 
 
 @pytest.fixture(scope="module")
@@ -175,15 +173,15 @@ def test_divergence(hop):
 
 # ---------------------------------------------------------------------------------------------------------------------- 3
 def check_rewards(eng, env, terms_env, traj, obs, acts, E, what):
-    """Per-particle step rewards r_j: the env's closure on float32 arrays; b_j = (T + 3) 2^-23 sum |terms| bounds each of them.
+    """Per-particle step rewards r_j: the env's closure on float32 arrays; b_j = `reward_bound` ((T + 3) 2^-23 sum |terms|; pendulum:
+    plus its angle's rounding) bounds each of them.
     The kernel's own step rewards are read with E = p: a member of one particle reports that particle's reward bit for bit
     (reward_member), and is held to b_j with nothing added.  With the engine's E, a mean of rewards (reward_mean, reward_member) is
     held to the mean of its particles' b_j, a return to H times the largest b_j of its steps; a variance moves by at most
     mean_j (2 |r_j - rbar| 2 b + (2 b)^2), b = max_j b_j, plus its own rounding 4 (p + 4) 2^-24 R^2 (as for the states)."""
     H, m, n, p, D = traj.shape
     r32 = step_rewards(env, traj, obs, acts)
-    T, S = reward_terms(terms_env, traj, obs, acts)
-    b = (T + 3) * U23 * S                                                            # [m,n,H,p]
+    b = reward_bound(terms_env, traj, obs, acts)                                     # [m,n,H,p]
     r = r32.astype(np.float64)
     each = _np(eng.forecast_stats(traj, obs, acts, E=p))
     err = np.abs(np.moveaxis(each["reward_member"], 0, 3) - r)
@@ -239,8 +237,7 @@ def check_composite(eng, prob, o, env, terms_env, seed, what):
         assert (err <= lim[k]).all(), "%s %s: %d entries outside the trajectory bar, worst |err| / bound %.3f" % (
             what, k, (err > lim[k]).sum(), (err / lim[k]).max())
     # the forecast's rewards account for the return the planner scored
-    Tn, S = reward_terms(terms_env, t_ref, o["obs"], acts)
-    lim_ret = H * ((Tn + 3) * U23 * S).max(2)
+    lim_ret = H * reward_bound(terms_env, t_ref, o["obs"], acts).max(2)
     err = np.abs(got["returns"].astype(np.float64) - got["rollout_returns"])
     print("%s returns vs rollout_returns: worst |err| / bound %.3f" % (what, (err / lim_ret).max()))
     assert (err <= lim_ret).all(), "%s: returns vs rollout_returns, worst |err| / bound %.3f" % (what, (err / lim_ret).max())
@@ -286,8 +283,8 @@ def test_composite_deterministic_engine(hc):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 5
-def raw_stats(eng, ctx, traj, obs, acts, p, E, band_k):
-    """cadm_forecast_stats called directly, every output pre-filled: (return code, message, whether an output was written)."""
+def raw_outputs(eng, ctx, traj, obs, acts, p, E, band_k):
+    """cadm_forecast_stats called directly, every output pre-filled with 7: (return code, message, the outputs on the device)."""
     H, m, n = traj.shape[0], traj.shape[1], traj.shape[2]
     out, c = eng._forecast_outputs(m, n, H, max(p, 1), max(E, 1))
     for v in out.values():
@@ -296,6 +293,12 @@ def raw_stats(eng, ctx, traj, obs, acts, p, E, band_k):
     rc = eng.lib.cadm_forecast_stats(ctx, ptr(t), ptr(o), ptr(a), m, n, H, p, E, band_k, ct.byref(c), eng.stream)
     msg = eng.lib.cadm_last_error().decode()
     torch.cuda.synchronize()
+    return rc, msg, out
+
+
+def raw_stats(eng, ctx, traj, obs, acts, p, E, band_k):
+    """(return code, message, whether an output was written)"""
+    rc, msg, out = raw_outputs(eng, ctx, traj, obs, acts, p, E, band_k)
     return rc, msg, any(bool((v != 7).any()) for v in out.values())
 
 
@@ -333,6 +336,122 @@ def test_refusals(hc, hop):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 6
+# The kernel's LDS carve (forecast.hip: forecast_stats_kernel) against the bytes the host asks for (forecast_lds_bytes), with
+# ts = p * D rounded up to a multiple of 4 floats: two tiles, 2 * ts floats; ret and rew, 2 * p floats; the `bad` word, 4 bytes of the
+# 16 the host adds.  The budget is 49152 bytes.
+#     halfcheetah   p = 323, D = 18: ts = 5816, (2 * 5816 + 2 * 323) * 4 + 16 = 49128 bytes -- accepted; the kernel's last word, `bad`,
+#                   sits at byte 49112
+#                   p = 324:         ts = 5832, (2 * 5832 + 2 * 324) * 4 + 16 = 49264 bytes -- refused
+#     slim_humanoid p = 133, D = 45: ts = 5988, (2 * 5988 + 2 * 133) * 4 + 16 = 48984 bytes -- accepted
+#                   p = 134:         ts = 6032, (2 * 6032 + 2 * 134) * 4 + 16 = 49344 bytes -- refused
+# Without the 2 * p term the host would ask for 46544 bytes at p = 323 while the kernel's carve reaches byte 49116, and would accept
+# every p up to 341: a change of either side has to keep these figures in step.
+@pytest.fixture(scope="module")
+def hum(gpu):
+    """slim_humanoid (D = 45, A = 17) with a small network: the statistics kernel never reads the model"""
+    prob = synth.make_problem(env="slim_humanoid", context=True, E=5, m=1, H=2, seed=55, hidden_sizes=(32,) * 4)
+    eng = make_engine(prob, p=5)
+    yield prob, eng
+    eng.close()
+
+
+def check_at_the_last_accepted_p(eng, env, kind, traj, obs, acts, E, what):
+    H, m, n, p, D = traj.shape
+    got = _np(eng.forecast_stats(traj, obs, acts, E=E))
+    check_state_stats(got, traj, E, what)
+    check_order_stats(eng, traj, obs, acts, E, what)
+    check_rewards(eng, env, kind, traj, obs, acts, E, what)
+    # one particle more: refused on the host before any launch, nothing written
+    E1 = next(e for e in range(2, p + 2) if (p + 1) % e == 0)
+    big = np.zeros((1, 1, 1, p + 1, D), np.float32)
+    rc, msg, wrote = raw_stats(eng, eng._ctx, big, obs[:1], acts[:1, :1, :1], p + 1, E1, 1)
+    assert rc == -1 and "LDS" in msg and "49152" in msg and not wrote, (rc, msg, wrote)
+    return msg
+
+
+def test_last_accepted_p_halfcheetah(hc):
+    """p = 323 = 17 * 19 particles of D = 18 dims, E = 17: 49128 of the 49152 bytes, and the per-particle loops (ret, rew, the reward
+    threads, the returns) take a second stride of the 256-thread workgroup.  p = 324 is refused.
+    Measured on an MI355X: worst |err| / bound -- mean 0.003, member_mean 0.006, variances 0.001; every one of the 1292 step rewards
+    bit-equal to the float32 closure; reward_mean 0.055, reward_member 0.124, returns 0.087."""
+    prob, eng = hc
+    traj, obs, acts = synth_traj(31, 2, 1, 2, 323, 18, 6)
+    msg = check_at_the_last_accepted_p(eng, oenvs.make_env("halfcheetah"), "halfcheetah", traj, obs, acts, 17, "halfcheetah p=323 E=17")
+    assert "49264" in msg, msg
+    # the returns of the particles behind the first stride: r_0 + r_1 of the float32 closure, within the two steps' bounds
+    got = _np(eng.forecast_stats(traj, obs, acts, E=17))
+    r = step_rewards(oenvs.make_env("halfcheetah"), traj, obs, acts).astype(np.float64)
+    b = reward_bound("halfcheetah", traj, obs, acts)
+    assert (np.abs(got["returns"] - r.sum(2))[..., 256:] <= 2 * b.max(2)[..., 256:]).all()
+
+
+def test_last_accepted_p_slim_humanoid(hum):
+    """p = 133 = 7 * 19 particles of D = 45 dims, E = 7: 48984 bytes; spans of 5985 floats, unaligned for three sequence-steps of four.
+    p = 134 is refused.  Dim 1 is redrawn around the alive bonus's interval.
+    Measured on an MI355X: worst |err| / bound -- mean 0.010, member_mean 0.017, variances 0.003; every one of the 532 step rewards
+    bit-equal to the float32 closure; reward_mean 0.011, reward_member 0.096, returns 0.052."""
+    prob, eng = hum
+    traj, obs, acts = synth_traj(32, 2, 1, 2, 133, 45, 17)
+    traj[..., 1] = (1.5 + 0.5 * np.random.default_rng(98).standard_normal(traj.shape[:-1])).astype(np.float32)
+    obs[0, 1] = 1.2
+    msg = check_at_the_last_accepted_p(eng, oenvs.make_env("slim_humanoid"), "slim_humanoid", traj, obs, acts, 7, "slim_humanoid p=133 E=7")
+    assert "49344" in msg, msg
+
+
+def test_particles_that_agree(hc):
+    """forecast.hip's header: particles that agree give exactly their value as every mean and exactly 0 as every variance.
+    (1) all p = 20 particles of a sequence equal; (2) equal inside each of the 5 members (4 particles each: c + c + c + c is exact
+    in float32), the members differing."""
+    prob, eng = hc
+    H, m, n, p, E, D = 8, 2, 2, 20, 5, 18
+    one, obs, acts = synth_traj(33, H, m, n, 1, D, 6)
+    traj = np.ascontiguousarray(np.broadcast_to(one, (H, m, n, p, D)))
+    got = _np(eng.forecast_stats(traj, obs, acts, E=E))
+    x = np.transpose(one, (1, 2, 0, 3, 4))[:, :, :, 0]                               # [m,n,H,D]
+    assert (got["diverged_step"] == H).all()
+    for k in ("mean", "lo", "hi"):
+        assert np.array_equal(_bits(got[k]), _bits(x)), "(1) %s differs from the particles' bits" % k
+    for e in range(E):
+        assert np.array_equal(_bits(got["member_mean"][e]), _bits(x)), "(1) member_mean[%d]" % e
+        assert np.array_equal(_bits(got["reward_member"][e]), _bits(got["reward_mean"])), "(1) reward_member[%d]" % e
+    for k in VARS + ("reward_var",):
+        assert (got[k] == 0).all(), "(1) %s is not exactly 0" % k
+    r1 = step_rewards(oenvs.make_env("halfcheetah"), one, obs, acts)[..., 0]       # [m,n,H]
+    assert (np.abs(got["reward_mean"] - r1) <= reward_bound("halfcheetah", one, obs, acts)[..., 0]).all()
+    for j in range(p):
+        assert np.array_equal(_bits(got["returns"][..., j]), _bits(got["returns"][..., 0])), "(1) returns of particle %d" % j
+    mem, obs, acts = synth_traj(34, H, m, n, E, D, 6)
+    traj = np.ascontiguousarray(np.repeat(mem, p // E, axis=3))                     # particle j holds member j // 4's values
+    got = _np(eng.forecast_stats(traj, obs, acts, E=E))
+    assert (got["var_aleatoric"] == 0).all(), "(2) identical particles of a member must give exactly 0"
+    assert (got["var_epistemic"] > 0).all()
+    check_state_stats(got, traj, E, "(2) particles equal inside a member")
+
+
+def test_order_statistics_with_ties(hc):
+    """A trajectory of the four values -1, -0.0, +0.0, 1: every dim of every step is full of ties, and the two zeros compare equal.
+    lo / hi equal np.sort's by value; every entry is written (each rank 0 .. p - 1 is taken by exactly one particle)."""
+    prob, eng = hc
+    H, m, n, p, D = 3, 2, 2, 20, 18
+    rng = np.random.default_rng(35)
+    traj = np.array([-1.0, -0.0, 0.0, 1.0], np.float32)[rng.integers(0, 4, (H, m, n, p, D))]
+    traj[0, 0, 0, :, 0] = 0.0
+    traj[0, 0, 0, ::2, 0] = -0.0                  # only zeros, of both signs
+    traj[0, 0, 0, :, 1] = 1.0                     # only one value
+    assert np.signbit(traj[traj == 0]).any() and not np.signbit(traj[traj == 0]).all()
+    _, obs, acts = synth_traj(36, H, m, n, 1, D, 6)
+    srt = np.sort(np.transpose(traj, (1, 2, 0, 3, 4)), axis=3)
+    for k in (1, 2, p):
+        rc, msg, out = raw_outputs(eng, eng._ctx, traj, obs, acts, p, 5, k)
+        assert rc == 0, msg
+        got = _np(out)
+        for name in ALL:
+            assert (got[name] != 7).all(), "band_k = %d: an entry of %s was not written" % (k, name)
+        assert np.array_equal(got["lo"], srt[:, :, :, k - 1]), "lo, band_k = %d" % k
+        assert np.array_equal(got["hi"], srt[:, :, :, p - k]), "hi, band_k = %d" % k
+
+
+# ---------------------------------------------------------------------------------------------------------------------- 7
 FORECAST_SHAPES = dict(mean="mHD", std_total="mHD", std_epistemic="mHD", std_aleatoric="mHD", lo="mHD", hi="mHD", member_mean="EmHD",
                        reward_mean="mH", reward_std="mH", reward_member="EmH", returns="mp", rollout_returns="mp", return_mean="m",
                        diverged_step="m")
