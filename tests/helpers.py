@@ -49,6 +49,13 @@ def assert_close(a, b, rtol=1e-5, what=""):
         what, int(bad.sum()), bad.size, float(np.abs(a - b).max()), float(bound.flat[np.abs(a - b).argmax()]), rel_err(a, b))
 
 
+def floored_rel(a, b):
+    """The smallest rtol `assert_close(a, b, rtol)` passes with: max |a-b| / max(|b|, rms(b))."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    scale = max(float(np.sqrt(np.mean(b * b))), 1e-30)
+    return float((np.abs(a - b) / np.maximum(np.abs(b), scale)).max())
+
+
 def floor_reliance(a, b, rtol=1e-5):
     """How much of `assert_close`'s verdict leans on its rms floor: (elements that violate the PURE relative bound
     |a-b| <= rtol*|b|, total elements, largest |b|/rms among those).  Elements far below the tensor's rms are sums that
@@ -138,6 +145,86 @@ def _check_gradients(eng, grads, what):
             checked += 1
     print("%s: %d gradient tensors, worst %.2e of max (pure-relative %.2e) at %s" % ((what, checked) + worst))
     return checked
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the context encoder under non-identity history statistics (state_diff = False: the history holds raw observations): what
+# tests/test_context_stats_inputs.py, tests/test_gpu_context_stats.py and tests/test_gpu_context.py share
+# ------------------------------------------------------------------------------------------------------------------------------
+RAW_GEOMETRIES = [  # env, E, Hh, cp_sizes, C
+    ("halfcheetah", 5, 10, (256, 128, 64), 10),       # the reference's encoder
+    ("pendulum", 5, 1, (8, 6), 3),                    # input width 4, layers narrower than one 64-unit group, odd widths
+    ("halfcheetah", 3, 3, (320, 100, 30), 10),        # a layer wider than 256; widths not multiples of 4 / 64
+    ("ant", 7, 2, (64,), 7),                          # one hidden layer, odd output width, E = 7
+    ("slim_humanoid", 2, 10, (256, 128, 64), 10),     # input width 620
+    ("halfcheetah", 5, 10, (1024, 512), 16),          # two row tiles do not fit in LDS: the launcher falls back to ONE at every m
+    ("halfcheetah", 5, 3, (70, 50, 30), 10),          # no width a multiple of 4 behind the input, fewer than four 64-unit groups per layer
+]
+
+
+def raw_history_problem(env, E, Hh, cp_sizes, C, m, seed, zero_std_cols=(), **kw):
+    """(prob, cp_obs [m, D Hh], cp_act [m, A Hh]): a trained-like synth problem whose statistics are those of a model built with
+    state_diff = False -- every history column has its own mean (5 N(0,1)) and spread (U(0.5, 2)) -- and histories at that scale,
+    cp_obs = mean + std N(0,1).  A column of `zero_std_cols` has std 0 and sits exactly on its mean: what np.std of a constant
+    column gives `fit`.  Statistics and histories are float32 values (held in float64 arrays): the float64 oracle then sees the
+    numbers the device sees, and a zero-std column normalises to exactly 0 in every precision instead of to a rounding error
+    divided by 1e-10.  `kw` goes to synth.make_problem (trained_like=False: the reference's initialiser); prob["cp_obs"] / prob["cp_act"] are the returned histories."""
+    prob = synth.make_problem(env=env, E=E, m=m, Hh=Hh, cp_hidden_sizes=cp_sizes, C=C, seed=seed, **dict(dict(trained_like=True), **kw))
+    rng = np.random.default_rng(seed + 1000)
+    st = synth.norm_stats(rng, prob["D"], prob["A"], prob["P"], Hh, state_diff=False, discrete=prob["discrete"])
+    st["cp_obs_mean"] = 5.0 * st["cp_obs_mean"]
+    st["cp_obs_std"][list(zero_std_cols)] = 0.0
+    for k in st:
+        st[k] = st[k].astype(np.float32).astype(np.float64)
+    prob["stats"] = st
+    cp_obs, _ = raw_histories(prob, (m,), rng)
+    cp_act = rng.uniform(-1, 1, (m, prob["A"] * Hh)).astype(np.float32).astype(np.float64)
+    prob["cp_obs"], prob["cp_act"] = cp_obs, cp_act
+    return prob, cp_obs, cp_act
+
+
+def raw_histories(prob, lead, rng):
+    """(cp_obs [*lead, D Hh] at the scale of prob's cp_obs statistics, cp_act [*lead, A Hh] ~ U(-1, 1)) as float32 values."""
+    st = prob["stats"]
+    cp_obs = st["cp_obs_mean"] + st["cp_obs_std"] * rng.standard_normal(tuple(lead) + (prob["D"] * prob["Hh"],))
+    cp_act = rng.uniform(-1, 1, tuple(lead) + (prob["A"] * prob["Hh"],))
+    return cp_obs.astype(np.float32).astype(np.float64), cp_act.astype(np.float32).astype(np.float64)
+
+
+def raw_train_batch(prob, B, seed):
+    """synth.make_train_batch with the history's cp_obs redrawn at raw scale from prob's own statistics."""
+    batch = synth.make_train_batch(prob, B=B, seed=seed)
+    batch["cp_obs"], _ = raw_histories(prob, (prob["E"], B), np.random.default_rng(seed + 2000))
+    return batch
+
+
+def rolled_stats(stats, key):
+    """The statistics with one vector moved by one column: what a kernel that reads the neighbouring column computes with."""
+    out = dict(stats)
+    out[key] = np.roll(stats[key], 1)
+    return out
+
+
+def identity_history_stats(stats):
+    out = dict(stats)
+    out["cp_obs_mean"], out["cp_obs_std"] = np.zeros_like(stats["cp_obs_mean"]), np.ones_like(stats["cp_obs_std"])
+    return out
+
+
+def context_row_tiles(E, m, n_cus):
+    """csrc/context.hip launch_context_batched: the row tiles per workgroup (16 rows each) the launcher tries FIRST for m >= 48 rows
+    per member.  (Layers too wide for two tiles in LDS fall back to one: RAW_GEOMETRIES' (1024, 512).)"""
+    wg2 = E * ((m + 31) // 32)
+    return 1 if (n_cus < wg2 < 2 * n_cus + n_cus // 2) or wg2 <= n_cus // 4 else 2
+
+
+def two_tile_m(E, n_cus):
+    """The smallest m = 1 (mod 32) whose batched call takes two row tiles: its last 32-row tile holds ONE row, the second half empty."""
+    m = 33
+    while context_row_tiles(E, m, n_cus) != 2:
+        m += 32
+        assert m < 1 << 16, "no two-tile m for E = %d on %d CUs" % (E, n_cus)
+    return m
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

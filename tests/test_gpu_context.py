@@ -5,11 +5,12 @@ at PPO scale (m = 2048), at ragged row counts around the tile and dispatch bound
 of 4 / 16 / 64, for both input layouts, and agreement with the planner's per-row kernel on the same rows."""
 import numpy as np
 import pytest
+import torch
 
 from cadm_amd import synth
 from cadm_amd.dynamics.mlp_cadm_ensemble_cem_dynamics import MLPEnsembleCEMDynamicsModel
 from cadm_amd.envs import make_env_spec
-from helpers import assert_close, make_engine, oracle_problem
+from helpers import assert_close, context_row_tiles, make_engine, oracle_problem, two_tile_m
 from oracle import nets as onets
 
 pytestmark = pytest.mark.gpu
@@ -71,8 +72,19 @@ def test_context_across_the_kernel_dispatch_threshold(gpu):
     ("ant", 7, 2, (64,), 7, 513),                      # one hidden layer, odd output width, E = 7
     ("slim_humanoid", 2, 10, (256, 128, 64), 10, 300),  # input width 620: the widest LDS input tile of the reference envs
     ("halfcheetah", 5, 10, (1024, 512), 16, 64),       # too wide for two row tiles in LDS: the one-tile flavour
+    ("halfcheetah", 5, 3, (70, 50, 30), 10, 77),       # no width a multiple of 4 behind the input; fewer than four 64-unit groups per layer
+    # m = 0: the smallest m = 1 (mod 32) at which the launcher takes TWO row tiles per workgroup on this device (helpers.two_tile_m: 385 /
+    # 673 on 256 CUs; of the cases above only ant's m = 513 takes two): odd widths through the XOR-swizzled [unit][row] tiles,
+    # row tiles of one group on different waves, a K that is no multiple of 4 behind zero-padded units, a last tile holding one row
+    ("pendulum", 5, 1, (8, 6), 3, 0),
+    ("halfcheetah", 3, 3, (320, 100, 30), 10, 0),
+    ("halfcheetah", 5, 3, (70, 50, 30), 10, 0),
 ])
 def test_batched_context_shapes(gpu, env, E, Hh, cp_sizes, C, m):
+    n_cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    if m == 0:
+        m = two_tile_m(E, n_cus)
+        assert context_row_tiles(E, m, n_cus) == 2 and m % 32 == 1
     prob = synth.make_problem(env=env, E=E, trained_like=True, seed=5, Hh=Hh, cp_hidden_sizes=cp_sizes, C=C)
     eng = make_engine(prob, p=E)
     cp_obs, cp_act = _histories(prob, m, 9)
