@@ -17,6 +17,9 @@ class DevicePlannerState:
     def __init__(self, model, num_envs):
         self.model = model
         eng = self.eng = model.engine
+        if eng.discrete:      # sampler.py:145-146 one-hot encodes a discrete action before it enters the history; this class keeps raw actions
+            raise NotImplementedError("DevicePlannerState: discrete actions are not supported (the samplers' history holds one-hot "
+                                      "actions, sampler.py:145-146); drive a discrete env through get_action and the host-side bookkeeping")
         self.m = int(num_envs)
         H, A, D, Hh = eng.H, eng.A, eng.D, eng.Hh
         dev = eng.device
@@ -29,12 +32,17 @@ class DevicePlannerState:
         self.context = eng.C > 0
 
     def act(self, obs):
-        """One MPC step: CEM plan from the warm start, then shift the plan (sampler.py:109-120).
+        """One MPC step: CEM plan from the warm start, then shift the plan (sampler.py:109-120) -- or, for a model built with
+        use_cem=False, random shooting's first action clipped to [-1, 1], the warm start left alone (sampler.py:121-127).
         obs [m,D] (numpy or device tensor) -> device tensor [m,A] (the action to execute)."""
         model, eng = self.model, self.eng
         model._push_stats()
         obs = eng._t(obs)
         hist = (self.hist_obs, self.hist_act) if self.context else (None, None)
+        if not model.use_cem:
+            first = eng.rs_plan(obs, hist[0], hist[1], model.n_candidates, seed=model.seed, call=model._next_call())
+            torch.clamp(first, -1.0, 1.0, out=self.action)
+            return self.action
         if model._opt is not None:      # the opt-in planner: the model owns its carried elites and the call
             plan = model._plan_opt_in(obs, hist[0], hist[1], self.prev_sol, self.init_var)
         else:
@@ -49,6 +57,11 @@ class DevicePlannerState:
         if done is not None and hasattr(self.model, "reset_plan_carry"):      # finished episodes: the iCEM planner forgets their elites
             self.model.reset_plan_carry(done)
         if not self.context:
+            if done is not None:      # reset_cem with or without a context (sampler.py:193-195); a context model resets in the kernel below
+                mask = eng._t(np.asarray(done) if not isinstance(done, torch.Tensor) else done, dtype=torch.bool).reshape(-1)
+                if mask.shape[0] != self.m:
+                    raise ValueError("observe: done has %d entries for %d envs" % (mask.shape[0], self.m))
+                self.prev_sol.masked_fill_(mask[:, None, None], 0.0)
             return
         obs, action, next_obs = eng._t(obs), eng._t(action), eng._t(next_obs)
         d = None if done is None else eng._t(np.asarray(done, dtype=np.int32) if not isinstance(done, torch.Tensor) else done,

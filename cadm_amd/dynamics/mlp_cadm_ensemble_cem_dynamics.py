@@ -588,6 +588,11 @@ class MLPEnsembleCEMDynamicsModel(object):
         the per-epoch validation losses and, with `keep_trace` (default: only when an index stream is injected), one
         [steps, 3] array of training losses [mse, back_mse, recon] per epoch."""
         D, A, F, Hh = self.obs_space_dims, self.action_space_dims, self.future_length, self.history_length
+        # torch tensors (ModelSampleProcessor.process_samples(as_device=True)) come to the host here, as float64 -- the dtype of the
+        # processor's own numpy output: the dataset is kept on the host (it grows by np.concatenate) and uploaded again below
+        obs, act, obs_next, cp_obs, cp_act, future_bool = (
+            x.detach().cpu().numpy().astype(np.float64, copy=False) if isinstance(x, torch.Tensor) else x
+            for x in (obs, act, obs_next, cp_obs, cp_act, future_bool))
         assert obs.ndim == 2 and obs.shape[1] == D * F
         assert obs_next.ndim == 2 and obs_next.shape[1] == D * F
         assert act.ndim == 2 and act.shape[1] == A * F

@@ -4,8 +4,9 @@
 Same constructor kwargs and the same `process_samples(paths, log, log_prefix, itr)` -> samples_data dict.  The heavy part
 of the `context` branch -- exploding every path into future windows (concat_obs / concat_act / concat_next_obs /
 concat_bool, :58-97) -- runs on the device (`cadm_build_windows`, cadm_amd/csrc/windows.hip): one H2D of the concatenated
-paths, one kernel, and either one D2H (numpy out, the reference's contract) or none (`as_device=True`: torch tensors that
-`fit` can take as they are).  The small per-path bookkeeping (discounted returns, the plain transition arrays) stays numpy.
+paths, one kernel, and either one D2H (numpy out, the reference's contract) or none (`as_device=True`: torch tensors in the
+paths' dtype, for device-side consumers; `fit` accepts them too, but keeps its dataset on the host: it copies them down at its
+entry, as float64 like the numpy output, so handing them to `fit` saves no transfer).  The small per-path bookkeeping (discounted returns, the plain transition arrays) stays numpy.
 Logging (`log != False`) goes to the injected logger (cadm_amd.utils.log)."""
 import ctypes as ct
 
