@@ -761,28 +761,34 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None)
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
-    def _horizon_outputs(self, F, D):
+    def _horizon_outputs(self, F, D, E=None):
         z = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
-        return dict(se=z((F, D), torch.float32), spread=z((F, D), torch.float32), se_member=z((self.E, F, D), torch.float32),
+        E = self.E if E is None else E
+        return dict(se=z((F, D), torch.float32), spread=z((F, D), torch.float32), se_member=z((E, F, D), torch.float32),
                     count=z((F,), torch.int32), diverged=z((F,), torch.int32))
 
-    def horizon_error(self, traj, truth, mask, calls=None):
+    def horizon_error(self, traj, truth, mask, calls=None, E=None, truth_ld=None):
         """`cadm_horizon_error` on device tensors: traj [F,m,1,p,D] (or [F,m,p,D]), truth [m,F,D], mask [m,F] -> dict of device
         tensors se / spread [F,D], se_member [E,F,D] (SUMS over the valid, finite windows) and count / diverged [F] int32.
         `calls`: window counts (multiples of 64 but the last) to cut the windows into several stage-1 launches -- the result is the
-        same bits (tests, tools)."""
+        same bits (tests, tools).  `E`: the number of members the p particles split into (default: the engine's; the kernel reads no
+        model).  `truth_ld`: floats between the truth rows of consecutive windows (default F * D); truth is then [m, truth_ld],
+        a window's F * D values first."""
         traj, truth, mask = self._t(traj), self._t(truth), self._t(mask)
         F, m, p, D = traj.shape[0], traj.shape[1], traj.shape[-2], traj.shape[-1]
-        if tuple(truth.shape) != (m, F, D) or tuple(mask.shape) != (m, F) or traj.numel() != F * m * p * D:
+        E = self.E if E is None else int(E)
+        ld = F * D if truth_ld is None else int(truth_ld)
+        if (tuple(truth.shape) != ((m, F, D) if truth_ld is None else (m, ld)) or tuple(mask.shape) != (m, F) or traj.numel() != F * m * p * D
+                or E < 1):
             raise ValueError("horizon_error: traj %r, truth %r, mask %r do not agree" % (tuple(traj.shape), tuple(truth.shape), tuple(mask.shape)))
         blocks = (m + 63) // 64
-        partials = torch.empty((blocks * F * ((2 + self.E) * D + 2),), dtype=torch.float32, device=self.device)
-        out = self._horizon_outputs(F, D)
+        partials = torch.empty((blocks * F * ((2 + E) * D + 2),), dtype=torch.float32, device=self.device)
+        out = self._horizon_outputs(F, D, E)
         w0 = 0
         for n in (calls or [m]):
             # a launch reads its windows' [F, n, p, D] slice as one tensor
             part = traj if n == m else traj.reshape(F, m, p, D)[:, w0:w0 + n].contiguous()
-            self._check(self.lib.cadm_horizon_error(ptr(part), ptr(truth[w0:]), F * D, ptr(mask[w0:]), n, F, p, self.E, D, w0, ptr(partials),
+            self._check(self.lib.cadm_horizon_error(ptr(part), ptr(truth[w0:]), ld, ptr(mask[w0:]), n, F, p, E, D, w0, ptr(partials),
                                                     blocks, ptr(out["se"]), ptr(out["spread"]), ptr(out["se_member"]), ptr(out["count"]),
                                                     ptr(out["diverged"]), int(w0 + n >= m), self.stream), "cadm_horizon_error")
             w0 += n

@@ -23,6 +23,7 @@ from cadm_amd.envs import make_env_spec
 from helpers import (CWD, RAW_GEOMETRIES, WD, _cfg, _check_gradients, _dev_batch, _dev_engine, _oracle_nets, assert_close,
                      context_row_tiles, floored_rel, make_engine, oracle_problem, raw_histories, raw_history_problem, raw_train_batch,
                      rolled_stats, two_tile_m)
+from horizon_ref import check_against_oracle, make_mask
 from oracle import nets as onets
 from oracle import planner as oplanner
 from oracle import train as otrain
@@ -199,7 +200,7 @@ def test_losses_under_raw_statistics(gpu, env, with_back, E, B):
 # ---------------------------------------------------------------------------------------------------------------------- e
 def test_evaluate_horizon_under_raw_statistics(gpu):
     """`cadm_eval_horizon` forces the batched encoder at any row count: N = 20 windows (fewer than 48) with raw statistics, the composite
-    against the oracle trajectory's statistics within tests/test_gpu_horizon.py's propagated bound (its stats64 / check_against_oracle).
+    against the oracle trajectory's statistics within tests/horizon_ref.py's propagated bound (its stats64 / check_against_oracle).
     Measured on an MI355X: worst |diff| / bound 0.011 (se), 0.002 (spread), 0.014 (se_member)."""
     th = horizon_tests
     N = 20
@@ -209,7 +210,7 @@ def test_evaluate_horizon_under_raw_statistics(gpu):
     rng = np.random.default_rng(141)
     acts = rng.uniform(-1, 1, (N, 1, th.F, A)).astype(np.float32)
     eps = rng.standard_normal((th.F, N, 1, th.P_, D)).astype(np.float32)
-    c.mask = th.make_mask(N, th.F)
+    c.mask = make_mask(N, th.F)
     assert (c.mask[5] == 0).all() and tuple(c.mask[9]) == (1, 1, 0, 1)
     o = oracle_problem(prob, np.float32)
     T = oplanner.context_table_indexed(onets.context_forward(o["cp"], o["cp_obs"], o["cp_act"], o["st"]), 0)
@@ -223,7 +224,7 @@ def test_evaluate_horizon_under_raw_statistics(gpu):
               cp_obs=prob["cp_obs"], cp_act=prob["cp_act"], future_bool=c.mask)
     eng = make_engine(prob, p=th.P_)
     comp = th._np(eng.eval_horizon({k: eng._t(v) for k, v in ds.items()}, N, th.F, eps=eps.copy()))
-    th.check_against_oracle(c, comp, "halfcheetah, raw statistics, 20 windows")
+    check_against_oracle(c, comp, "halfcheetah, raw statistics, 20 windows")
     eng.close()
 
 

@@ -12,13 +12,13 @@ import torch
 from cadm_amd import _lib, synth
 from cadm_amd.env_spec import EnvDecl
 from helpers import make_engine, oracle_problem, spec_oracle
+from horizon_ref import RTOL, check_against_oracle, make_mask, stats64
 from oracle import nets as onets
 from oracle import planner as oplanner
 
 pytestmark = pytest.mark.gpu
 
 E, P_, H_ENG, F, N = 5, 10, 8, 4, 150
-RTOL = 4e-6      # a statistic is a chain of fewer than 64 fp32 roundings of non-negative terms: 64 * 2^-24
 KEYS = ("se", "spread", "se_member", "count", "diverged")
 
 
@@ -38,31 +38,6 @@ def small_vanilla():        # the shape of tests/test_gpu_env_spec.py's vanilla 
     return EnvDecl(7, 1, preproc=["id", "id", "sincos", "id", "drop", "id", "id"],
                    reward=[dict(kind="linear", dim=0, when="next_obs"), dict(kind="square", dim=2, w=-0.1, when="next_obs"),
                            dict(kind="outside", dim=1, w=-1.0, lo=-1.5, hi=1.5, when="next_obs")], ctrl_cost=0.01)
-
-
-def make_mask(n, f):
-    """All-valid windows, prefixes of every length, window 5 all-invalid, window 9 with a hole."""
-    mask = np.ones((n, f), np.float32)
-    for i in range(20, n, 3):
-        mask[i, (i // 3) % f + 1:] = 0.0
-    mask[5] = 0.0
-    mask[9] = (1, 1, 0, 1)[:f] if f == 4 else mask[9]
-    return mask
-
-
-def stats64(traj, truth, mask, e):
-    """The statistics restated in float64: traj [F,m,p,D], truth [m,F,D], mask [m,F] -> sums and counts."""
-    f, m, p, d = traj.shape
-    valid = (np.cumprod(mask != 0, axis=1) > 0).T                                  # [F,m] prefix rule
-    finite = np.isfinite(traj).all(axis=(2, 3))
-    use = valid & finite
-    x = np.where(np.isfinite(traj), traj, 0.0).astype(np.float64)
-    y = np.transpose(truth.astype(np.float64), (1, 0, 2))                          # [F,m,D]
-    mem = x.reshape(f, m, e, p // e, d).mean(3)                                    # [F,m,E,D]
-    u = use[:, :, None]
-    return dict(se=(u * (x.mean(2) - y) ** 2).sum(1), spread=(u * x.var(2)).sum(1),
-                se_member=np.transpose((u[..., None] * (mem - y[:, :, None, :]) ** 2).sum(1), (1, 0, 2)),
-                count=use.sum(1), diverged=(valid & ~finite).sum(1))
 
 
 def _np(out):
@@ -149,40 +124,6 @@ def test_statistics_kernel_odd_dim(hc):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 2
-def oracle_bound(t_ref, truth, mask, e):
-    """The project's trajectory bar (helpers.assert_close: every value within delta = 1e-5 * max(|x_ref|, rms(x_ref[h]))) propagated
-    through the statistics, per entry, from the oracle's values: a mean of values moves by at most the mean of their deltas, so
-        |d se| <= sum_i 2 |xbar_i - y_i| dbar_i + dbar_i^2          (likewise per member)
-        |d var_i| <= 1/p sum_j 2 |x_ij - xbar_i| (d_ij + dbar_i) + (d_ij + dbar_i)^2
-    plus the kernel's own rounding (RTOL of the statistic, test 1)."""
-    f, m, p, d = t_ref.shape
-    x = t_ref.astype(np.float64)
-    rms = np.sqrt((x ** 2).mean(axis=(1, 2, 3), keepdims=True))
-    dl = 1e-5 * np.maximum(np.abs(x), rms)
-    y = np.transpose(truth.astype(np.float64), (1, 0, 2))
-    u = ((np.cumprod(mask != 0, axis=1) > 0).T)[:, :, None]
-    xb, db = x.mean(2), dl.mean(2)
-    se = (u * (2 * np.abs(xb - y) * db + db ** 2)).sum(1)
-    dj = dl + db[:, :, None, :]
-    spread = (u * (2 * np.abs(x - xb[:, :, None, :]) * dj + dj ** 2).mean(2)).sum(1)
-    xm, dm = x.reshape(f, m, e, p // e, d).mean(3), dl.reshape(f, m, e, p // e, d).mean(3)
-    sem = np.transpose((u[..., None] * (2 * np.abs(xm - y[:, :, None, :]) * dm + dm ** 2)).sum(1), (1, 0, 2))
-    return dict(se=se, spread=spread, se_member=sem)
-
-
-def check_against_oracle(case, comp, what):
-    ref = stats64(case.t_ref, case.truth, case.mask, E)
-    bound = oracle_bound(case.t_ref, case.truth, case.mask, E)
-    np.testing.assert_array_equal(comp["count"], ref["count"])
-    assert comp["diverged"].sum() == 0
-    for k in ("se", "spread", "se_member"):
-        lim = bound[k] + RTOL * np.abs(ref[k])
-        diff = np.abs(comp[k] - ref[k])
-        print("%s %s: worst |diff| / bound %.3f (worst relative %.2e)" % (what, k, (diff / lim).max(), (diff / np.abs(ref[k])).max()))
-        assert (diff <= lim).all(), "%s %s: %d entries outside the propagated trajectory bar, worst |diff| / bound %.3f" % (
-            what, k, (diff > lim).sum(), (diff / lim).max())
-
-
 def test_composite_matches_oracle_and_the_isolated_kernel(hc):
     check_against_oracle(hc, hc.comp, "halfcheetah")
     # 4 steps of the 8-step engine == the composite's 4-step launch, row for row
