@@ -73,6 +73,10 @@ class ForecastOut(C.Structure):         # include/cadm_hip.h cadm_forecast_out: 
                                           "reward_var", "reward_member", "returns", "diverged_step", "rollout_returns")]
 
 
+class CalibrationOut(C.Structure):     # include/cadm_hip.h cadm_calibration_out: device pointers
+    _fields_ = [(k, C.c_void_p) for k in ("rank_hist", "rank_hist_member", "ties", "degenerate", "crps", "z2", "nll", "count", "diverged")]
+
+
 SCORE_MODES = {"mean": 0, "mean_std": 1, "member_std": 2, "cvar": 3}      # CADM_SCORE_*
 MAX_CONSTRAINTS = 16                                                       # CADM_MAX_CONSTRAINTS
 CONSTRAIN_MODES = {"penalty": 0, "terminate": 1}                           # CADM_CONSTRAIN_*
@@ -152,6 +156,9 @@ SIGNATURES = {
     "cadm_horizon_error": (_i, [_P, _P, C.c_longlong, _P, _i, _i, _i, _i, _i, C.c_longlong, _P, C.c_longlong, _P, _P, _P, _P, _P, _i, _P]),
     "cadm_eval_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
     "cadm_eval_horizon": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _u32, _u32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cadm_calibration_stats": (_i, [_P, _P, C.c_longlong, _P, _i, _i, _i, _i, _i, C.c_longlong, _P, C.c_longlong, C.POINTER(CalibrationOut), _i, _P]),
+    "cadm_eval_calibration_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
+    "cadm_eval_calibration": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _u32, _u32, _P, _P, C.POINTER(CalibrationOut), _P]),
     "cadm_forecast_stats": (_i, [_P, _P, _P, _P, _i, _i, _i, _i, _i, _i, C.POINTER(ForecastOut), _P]),
     "cadm_forecast_workspace_bytes": (C.c_size_t, [_P, _i, _i]),
     "cadm_plan_forecast": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _i, _u32, _u32, _P, C.POINTER(ForecastOut), _P]),

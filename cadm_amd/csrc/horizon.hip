@@ -196,7 +196,8 @@ extern "C" int cadm_horizon_error(const float* traj, const float* truth, long lo
     return CADM_OK;
 }
 
-// cadm_eval_horizon: encoder, rollout and the statistics kernel above, strung together chunk by chunk of held-out windows
+// cadm_eval_horizon and cadm_eval_calibration: encoder, rollout and a statistics kernel (the one above; calibration.hip's), strung
+// together chunk by chunk of held-out windows by ONE loop, eval_chunks
 // rows of `width` floats, `src_ld` floats apart -> contiguous rows
 __global__ void strided_rows_kernel(const float* __restrict__ src, size_t src_ld, float* __restrict__ dst, size_t width, size_t total) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -223,7 +224,8 @@ static int eval_chunk(int N, int chunk) {
     return (int)(chunk < n64 ? chunk : n64);
 }
 
-static size_t eval_carve(cadm_ctx* ctx, int N, int F, int chunk, char* base, EvalWs* w) {
+// partial_words: 4-byte words of one (block, step) partial of the statistics kernel that reduces the trajectories
+static size_t eval_carve(cadm_ctx* ctx, int N, int F, int chunk, size_t partial_words, char* base, EvalWs* w) {
     Carver c{base};
     const size_t mc = (size_t)eval_chunk(N, chunk), blocks = ((size_t)N + 63) / 64;
     EvalWs t;
@@ -232,37 +234,45 @@ static size_t eval_carve(cadm_ctx* ctx, int N, int F, int chunk, char* base, Eva
     t.rows = c.take<float>(mc * ctx->p);
     t.traj = c.take<float>((size_t)F * mc * ctx->p * ctx->D);
     t.eps = c.take<float>((size_t)F * mc * ctx->p * ctx->D);      // a chunk of injected noise, made contiguous
-    t.partials = c.take<float>(blocks * F * ((size_t)(2 + ctx->E) * ctx->D + 2));
+    t.partials = c.take<float>(blocks * F * partial_words);
     t.blocks = (long long)blocks;
     if (w) *w = t;
     return c.off;
 }
 
+static size_t horizon_partial_words(const cadm_ctx* ctx) { return (size_t)(2 + ctx->E) * ctx->D + 2; }
+static size_t calibration_partial_words(const cadm_ctx* ctx) { return 3 * (size_t)ctx->D; }
+
 extern "C" size_t cadm_eval_workspace_bytes(cadm_ctx* ctx, int N, int F, int chunk) {
     if (!ctx || N <= 0 || F <= 0 || chunk <= 0 || chunk % 64) return 0;
-    return eval_carve(ctx, N, F, chunk, nullptr, nullptr);
+    return eval_carve(ctx, N, F, chunk, horizon_partial_words(ctx), nullptr, nullptr);
 }
 
-extern "C" int cadm_eval_horizon(cadm_ctx* ctx, const float* ds_obs, const float* ds_act, const float* ds_obs_next, const float* ds_cp_obs,
-                                 const float* ds_cp_act, const float* future_bool, int N, int F, int chunk, uint32_t seed, uint32_t call,
-                                 const float* eps, void* workspace, float* se_out, float* spread_out, float* se_member_out,
-                                 int32_t* count_out, int32_t* diverged_out, void* stream) {
-    CADM_REQUIRE(ctx && ds_obs && ds_act && ds_obs_next && future_bool && workspace && se_out && spread_out && se_member_out && count_out &&
-                     diverged_out, "cadm_eval_horizon: null argument");
-    CADM_REQUIRE(N >= 1 && F >= 1, "cadm_eval_horizon: N (%d) and F (%d) must be >= 1", N, F);
-    CADM_REQUIRE(chunk >= 64 && chunk % 64 == 0, "cadm_eval_horizon: chunk (%d) must be a positive multiple of 64", chunk);
-    CADM_REQUIRE(F <= ctx->H, "cadm_eval_horizon: F (%d) exceeds the model's planning horizon n_forwards (%d)", F, ctx->H);
-    CADM_REQUIRE(ctx->C == 0 || (ds_cp_obs && ds_cp_act), "cadm_eval_horizon: ds_cp_obs / ds_cp_act required for a context model");
+extern "C" size_t cadm_eval_calibration_workspace_bytes(cadm_ctx* ctx, int N, int F, int chunk) {
+    if (!ctx || N <= 0 || F <= 0 || chunk <= 0 || chunk % 64) return 0;
+    return eval_carve(ctx, N, F, chunk, calibration_partial_words(ctx), nullptr, nullptr);
+}
+
+// The chunk loop of cadm_eval_horizon and cadm_eval_calibration (`who`): per chunk of windows the start states, the context encoder and
+// ONE rollout of F steps, then stats(w, w0, mc, last) on the chunk's trajectories w.traj [F, mc, 1, p, D] -- windows [w0, w0 + mc) of the
+// dataset; `last`: no chunk follows.  The callers have checked their own pointers.
+template <class Stats>
+static int eval_chunks(cadm_ctx* ctx, const char* who, const float* ds_obs, const float* ds_act, const float* ds_cp_obs, const float* ds_cp_act,
+                       int N, int F, int chunk, uint32_t seed, uint32_t call, const float* eps, void* workspace, size_t partial_words,
+                       hipStream_t s, Stats stats) {
+    CADM_REQUIRE(N >= 1 && F >= 1, "%s: N (%d) and F (%d) must be >= 1", who, N, F);
+    CADM_REQUIRE(chunk >= 64 && chunk % 64 == 0, "%s: chunk (%d) must be a positive multiple of 64", who, chunk);
+    CADM_REQUIRE(F <= ctx->H, "%s: F (%d) exceeds the model's planning horizon n_forwards (%d)", who, F, ctx->H);
+    CADM_REQUIRE(ctx->C == 0 || (ds_cp_obs && ds_cp_act), "%s: ds_cp_obs / ds_cp_act required for a context model", who);
     CADM_ON_DEVICE(ctx);
-    int rc = cadm_require_ready(ctx, "cadm_eval_horizon");
+    int rc = cadm_require_ready(ctx, who);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
     if (!ctx->packed && (rc = cadm_pack_streams(ctx, s))) return rc;
     EvalWs w;
-    eval_carve(ctx, N, F, chunk, (char*)workspace, &w);
+    eval_carve(ctx, N, F, chunk, partial_words, (char*)workspace, &w);
     const int D = ctx->D, A = ctx->A, p = ctx->p, Hh = ctx->cfg.history_length, mc_max = eval_chunk(N, chunk);
     const bool inject = eps && !ctx->cfg.deterministic;
-    CADM_REQUIRE(((long long)N + mc_max - 1) / mc_max < (1 << 23), "cadm_eval_horizon: N (%d) needs too many chunks of %d windows", N, mc_max);
+    CADM_REQUIRE(((long long)N + mc_max - 1) / mc_max < (1 << 23), "%s: N (%d) needs too many chunks of %d windows", who, N, mc_max);
     for (int w0 = 0; w0 < N; w0 += mc_max) {
         const int mc = N - w0 < mc_max ? N - w0 : mc_max;
         // start state of every window: ds_obs[w, 0, :]
@@ -276,10 +286,36 @@ extern "C" int cadm_eval_horizon(cadm_ctx* ctx, const float* ds_obs, const float
         // INSIDE the launch and the iteration word) is not repeated from chunk to chunk
         if ((rc = cadm_launch_rollout(ctx, w.obs0, nullptr, ctx->C > 0 ? w.ctxv : nullptr, ds_act + (size_t)w0 * F * A, inject ? w.eps : nullptr,
                                       /*norm_actions=*/1, seed, call, /*it=*/2 * (w0 / mc_max), 0, 1, mc, 1, w.rows, w.traj, s, 0, -1, /*horizon=*/F))) return rc;
-        const bool last = w0 + mc >= N;
-        if ((rc = cadm_horizon_error(w.traj, ds_obs_next + (size_t)w0 * F * D, (long long)F * D, future_bool + (size_t)w0 * F, mc, F, p, ctx->E, D,
-                                     w0, w.partials, w.blocks, se_out, spread_out, se_member_out, count_out, diverged_out, last ? 1 : 0, stream)))
-            return rc;
+        if ((rc = stats(w, w0, mc, w0 + mc >= N))) return rc;
     }
     return CADM_OK;
+}
+
+extern "C" int cadm_eval_horizon(cadm_ctx* ctx, const float* ds_obs, const float* ds_act, const float* ds_obs_next, const float* ds_cp_obs,
+                                 const float* ds_cp_act, const float* future_bool, int N, int F, int chunk, uint32_t seed, uint32_t call,
+                                 const float* eps, void* workspace, float* se_out, float* spread_out, float* se_member_out,
+                                 int32_t* count_out, int32_t* diverged_out, void* stream) {
+    CADM_REQUIRE(ctx && ds_obs && ds_act && ds_obs_next && future_bool && workspace && se_out && spread_out && se_member_out && count_out &&
+                     diverged_out, "cadm_eval_horizon: null argument");
+    return eval_chunks(ctx, "cadm_eval_horizon", ds_obs, ds_act, ds_cp_obs, ds_cp_act, N, F, chunk, seed, call, eps, workspace,
+                       horizon_partial_words(ctx), (hipStream_t)stream, [&](const EvalWs& w, int w0, int mc, bool last) {
+                           return cadm_horizon_error(w.traj, ds_obs_next + (size_t)w0 * F * ctx->D, (long long)F * ctx->D,
+                                                     future_bool + (size_t)w0 * F, mc, F, ctx->p, ctx->E, ctx->D, w0, w.partials, w.blocks, se_out,
+                                                     spread_out, se_member_out, count_out, diverged_out, last ? 1 : 0, stream);
+                       });
+}
+
+// (the statistics kernel: calibration.hip)
+extern "C" int cadm_eval_calibration(cadm_ctx* ctx, const float* ds_obs, const float* ds_act, const float* ds_obs_next, const float* ds_cp_obs,
+                                     const float* ds_cp_act, const float* future_bool, int N, int F, int chunk, uint32_t seed, uint32_t call,
+                                     const float* eps, void* workspace, const cadm_calibration_out* out, void* stream) {
+    CADM_REQUIRE(ctx && ds_obs && ds_act && ds_obs_next && future_bool && workspace && out, "cadm_eval_calibration: null argument");
+    CADM_REQUIRE(out->rank_hist && out->rank_hist_member && out->ties && out->degenerate && out->crps && out->z2 && out->nll && out->count &&
+                     out->diverged, "cadm_eval_calibration: a pointer of out is null");
+    return eval_chunks(ctx, "cadm_eval_calibration", ds_obs, ds_act, ds_cp_obs, ds_cp_act, N, F, chunk, seed, call, eps, workspace,
+                       calibration_partial_words(ctx), (hipStream_t)stream, [&](const EvalWs& w, int w0, int mc, bool last) {
+                           return cadm_calibration_stats(w.traj, ds_obs_next + (size_t)w0 * F * ctx->D, (long long)F * ctx->D,
+                                                         future_bool + (size_t)w0 * F, mc, F, ctx->p, ctx->E, ctx->D, w0, w.partials, w.blocks, out,
+                                                         last ? 1 : 0, stream);
+                       });
 }

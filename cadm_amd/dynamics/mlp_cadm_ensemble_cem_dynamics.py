@@ -133,6 +133,29 @@ def _checked_shapes(model, *inputs):
     return sig
 
 
+def calibration_summary(out):
+    """The sums and counts of `cadm_calibration_stats` (numpy arrays) -> what `evaluate_calibration` returns (see there): the means,
+    and coverage / nominal / calibration_error derived from rank_hist.  NaN where the divisor is 0."""
+    res = {k: out[k].astype(np.int64) for k in ("rank_hist", "rank_hist_member", "ties", "degenerate", "count", "diverged")}
+    hist, count = res["rank_hist"], res["count"]
+    p = hist.shape[-1] - 1
+    with np.errstate(invalid="ignore", divide="ignore"):
+        n = np.where(count > 0, count, np.nan)[:, None]
+        res["crps"] = out["crps"].astype(np.float64) / n
+        used = count[:, None] - res["degenerate"]
+        nd = np.where(used > 0, used, np.nan)
+        res["z2"] = out["z2"].astype(np.float64) / nd
+        res["nll"] = out["nll"].astype(np.float64) / nd
+        res["z2_ideal"] = (p + 1.0) / (p - 3.0) if p > 3 else float("nan")
+        ks = np.arange(p // 2)
+        res["nominal"] = (p - 1.0 - 2.0 * ks) / (p + 1.0)
+        csum = np.concatenate([np.zeros(hist.shape[:-1] + (1,), np.int64), np.cumsum(hist, axis=-1)], axis=-1)      # [.., r]: ranks below r
+        res["coverage"] = (csum[..., p - ks] - csum[..., ks + 1]) / n[:, :, None]          # ranks k + 1 .. p - 1 - k
+        cdf = csum[..., 1:] / n[:, :, None]
+        res["calibration_error"] = np.abs(cdf - np.arange(1, p + 2) / (p + 1.0)).max(axis=-1).mean(axis=-1)
+    return res
+
+
 class MLPEnsembleCEMDynamicsModel(object):
     """Probabilistic-ensemble MLP dynamics model with a context encoder and a CEM / RS planner."""
 
@@ -645,6 +668,29 @@ class MLPEnsembleCEMDynamicsModel(object):
         return self._fit_loop(dev, train_rows, valid_rows, epochs, rolling_average_persitency, verbose, log_tabular, index_stream,
                               device_shuffle=not injected, keep_trace=keep_trace)
 
+    def _eval_windows(self, who, obs, act, obs_next, cp_obs, cp_act, future_bool, seed):
+        """What evaluate_horizon and evaluate_calibration share: the asserts, the F <= n_forwards check, the statistics push, the upload
+        and the evaluations' own call counter -> (engine, device dataset, N, F, dict(seed=, call=))."""
+        D, A, F, Hh = self.obs_space_dims, self.action_space_dims, self.future_length, self.history_length
+        assert obs.ndim == 2 and obs.shape[1] == D * F
+        assert obs_next.ndim == 2 and obs_next.shape[1] == D * F
+        assert act.ndim == 2 and act.shape[1] == A * F
+        assert cp_obs.ndim == 2 and cp_obs.shape[1] == D * Hh
+        assert cp_act.ndim == 2 and cp_act.shape[1] == A * Hh
+        assert future_bool.ndim == 2 and future_bool.shape[1] == F
+        if F > self.n_forwards:
+            raise ValueError("%s: future_length %d exceeds the planning horizon n_forwards %d" % (who, F, self.n_forwards))
+        N = obs.shape[0]
+        if N == 0:
+            raise ValueError("%s: no windows" % who)
+        self._stats12()                 # (raises RuntimeError when no statistics are set)
+        self._push_stats()
+        eng = self.engine
+        dev = {k: eng._t(v) for k, v in (("obs", obs), ("act", act), ("obs_next", obs_next), ("cp_obs", cp_obs), ("cp_act", cp_act))}
+        dev["future_bool"] = eng._t(np.asarray(future_bool) > 0)
+        self._eval_call += 1
+        return eng, dev, N, F, dict(seed=(self.seed if seed is None else int(seed)) & 0xFFFFFFFF, call=self._eval_call & 0xFFFFFFFF)
+
     def evaluate_horizon(self, obs, act, obs_next, cp_obs, cp_act, future_bool, seed=None, chunk=4096):
         """Open-loop prediction error along the horizon on held-out windows (no reference twin).  Takes the arrays `fit` takes
         (future windows of F = future_length steps, F <= n_forwards).  Every window is rolled out from its first observation
@@ -658,26 +704,8 @@ class MLPEnsembleCEMDynamicsModel(object):
             count, diverged [F]   windows counted / left out because their trajectory was not finite
         Uses the current normalisation statistics (RuntimeError when unset); leaves the dataset, weights, optimiser state and
         get_action's noise sequence alone.  `seed`: Philox key of the noise (default: the model's, with a call counter of its own)."""
-        D, A, F, Hh = self.obs_space_dims, self.action_space_dims, self.future_length, self.history_length
-        assert obs.ndim == 2 and obs.shape[1] == D * F
-        assert obs_next.ndim == 2 and obs_next.shape[1] == D * F
-        assert act.ndim == 2 and act.shape[1] == A * F
-        assert cp_obs.ndim == 2 and cp_obs.shape[1] == D * Hh
-        assert cp_act.ndim == 2 and cp_act.shape[1] == A * Hh
-        assert future_bool.ndim == 2 and future_bool.shape[1] == F
-        if F > self.n_forwards:
-            raise ValueError("evaluate_horizon: future_length %d exceeds the planning horizon n_forwards %d" % (F, self.n_forwards))
-        N = obs.shape[0]
-        if N == 0:
-            raise ValueError("evaluate_horizon: no windows")
-        self._stats12()                 # (raises RuntimeError when no statistics are set)
-        self._push_stats()
-        eng = self.engine
-        dev = {k: eng._t(v) for k, v in (("obs", obs), ("act", act), ("obs_next", obs_next), ("cp_obs", cp_obs), ("cp_act", cp_act))}
-        dev["future_bool"] = eng._t(np.asarray(future_bool) > 0)
-        self._eval_call += 1
-        out = eng.eval_horizon(dev, N, F, chunk=int(chunk), seed=(self.seed if seed is None else int(seed)) & 0xFFFFFFFF,
-                               call=self._eval_call & 0xFFFFFFFF)
+        eng, dev, N, F, kw = self._eval_windows("evaluate_horizon", obs, act, obs_next, cp_obs, cp_act, future_bool, seed)
+        out = eng.eval_horizon(dev, N, F, chunk=int(chunk), **kw)
         out = {k: v.cpu().numpy() for k, v in out.items()}
         count = out["count"].astype(np.int64)
         with np.errstate(invalid="ignore", divide="ignore"):
@@ -687,6 +715,30 @@ class MLPEnsembleCEMDynamicsModel(object):
                        count=count, diverged=out["diverged"].astype(np.int64))
             res["rmse"] = np.sqrt(mse.mean(axis=1))
         return res
+
+    def evaluate_calibration(self, obs, act, obs_next, cp_obs, cp_act, future_bool, seed=None, chunk=4096):
+        """Is the ensemble's predictive distribution calibrated?  Takes what `evaluate_horizon` takes and rolls the same particles out
+        the same way (same statistics push, same call counter, same noise keys), then asks, per counted (window, step) and dim,
+        where the recorded next observation y falls among the p = n_particles particles x_j -- on the device.  Returns numpy arrays,
+        NaN where the divisor is 0:
+            rank_hist [F,D,p+1]            int64: windows whose y exceeds exactly r particles (Talagrand histogram; flat when calibrated,
+                                           U-shaped when over-confident, dome-shaped when under-confident, skewed when biased)
+            rank_hist_member [E,F,D,p/E+1] int64: the same against each member's own particles
+            ties, degenerate [F,D]         int64: windows where y equals a particle / where the biased particle variance is exactly 0
+            count, diverged [F]            int64: as evaluate_horizon's
+            crps [F,D]                     mean of (1/p) sum |x_j - y| - (1/(2 p^2)) sum |x_j - x_k|: in the units of the state, lower is better
+            z2 [F,D]                       mean of (xbar - y)^2 / v over the non-degenerate windows, v the biased particle variance
+            nll [F,D]                      mean of 0.5 (log 2 pi + log v + (xbar - y)^2 / v) over the same
+            z2_ideal                       (p + 1) / (p - 3), NaN for p <= 3: for a Gaussian predictive distribution of which the p particles and
+                                           the truth are independent draws, E[(xbar - y)^2 / v_biased] = (1 + 1/p) p / (p - 3) -- 21/17 at p = 20.
+                                           z2 above it: over-confident; below it: under-confident
+            coverage [F,D,K], nominal [K]  K = p // 2: the share of windows whose y lies between order statistics k and p - 1 - k of the
+                                           particles (k + 1 <= rank <= p - 1 - k), and that interval's nominal level (p - 1 - 2 k) / (p + 1)
+            calibration_error [F]          mean over dims of max_r |empirical CDF of the rank at r - (r + 1) / (p + 1)|
+        Leaves the dataset, weights, optimiser state and get_action's noise sequence alone."""
+        eng, dev, N, F, kw = self._eval_windows("evaluate_calibration", obs, act, obs_next, cp_obs, cp_act, future_bool, seed)
+        out = eng.eval_calibration(dev, N, F, chunk=int(chunk), **kw)
+        return calibration_summary({k: v.cpu().numpy() for k, v in out.items()})
 
     _BATCH_KEYS = ("obs", "act", "delta", "obs_next", "back_delta", "cp_obs", "cp_act")
 

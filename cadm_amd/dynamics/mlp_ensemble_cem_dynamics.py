@@ -77,6 +77,16 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         assert act.ndim == 2 and act.shape[1] == A
         return super().evaluate_horizon(obs, act, obs_next, np.zeros((N, 0)), np.zeros((N, 0)), np.ones((N, 1)), seed=seed, chunk=chunk)
 
+    def evaluate_calibration(self, obs, act, obs_next, seed=None, chunk=4096):
+        """Calibration of the predictive distribution on held-out samples (see the CaDM class; a vanilla model's windows hold one
+        step, so F = 1)."""
+        N = obs.shape[0]
+        D, A = self.obs_space_dims, self.action_space_dims
+        assert obs.ndim == 2 and obs.shape[1] == D
+        assert obs_next.ndim == 2 and obs_next.shape[1] == D
+        assert act.ndim == 2 and act.shape[1] == A
+        return super().evaluate_calibration(obs, act, obs_next, np.zeros((N, 0)), np.zeros((N, 0)), np.ones((N, 1)), seed=seed, chunk=chunk)
+
     def fit(self, obs, act, obs_next, epochs=1000, compute_normalization=True, valid_split_ratio=None,
             rolling_average_persitency=None, verbose=False, log_tabular=False, max_logging=5000, rng=None, index_stream=None):
         """reference :209-323 (single-step samples, no history window)."""

@@ -815,6 +815,60 @@ class HipEngine:
                                                ptr(out["diverged"]), self.stream), "cadm_eval_horizon")
         return out
 
+    # ------------------------------------------------------------------ calibration of the predictive distribution (csrc/calibration.hip)
+    def _calibration_outputs(self, F, D, p, E):
+        i = lambda *shape: torch.empty(shape, dtype=torch.int32, device=self.device)
+        z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        out = dict(rank_hist=i(F, D, p + 1), rank_hist_member=i(E, F, D, p // E + 1), ties=i(F, D), degenerate=i(F, D), crps=z(F, D), z2=z(F, D),
+                   nll=z(F, D), count=i(F), diverged=i(F))
+        c = _lib.CalibrationOut()
+        for k, v in out.items():
+            setattr(c, k, v.data_ptr())
+        return out, c
+
+    def calibration_stats(self, traj, truth, mask, calls=None, E=None, truth_ld=None):
+        """`cadm_calibration_stats` on device tensors: the arguments of `horizon_error` -> dict of device tensors rank_hist [F,D,p+1],
+        rank_hist_member [E,F,D,p/E+1], ties / degenerate [F,D], count / diverged [F] (int32 counts) and crps / z2 / nll [F,D] (float32
+        SUMS over the counted windows; z2 and nll leave the degenerate ones out)."""
+        traj, truth, mask = self._t(traj), self._t(truth), self._t(mask)
+        F, m, p, D = traj.shape[0], traj.shape[1], traj.shape[-2], traj.shape[-1]
+        E = self.E if E is None else int(E)
+        ld = F * D if truth_ld is None else int(truth_ld)
+        if (tuple(truth.shape) != ((m, F, D) if truth_ld is None else (m, ld)) or tuple(mask.shape) != (m, F) or traj.numel() != F * m * p * D
+                or E < 1 or p % E):
+            raise ValueError("calibration_stats: traj %r, truth %r, mask %r, E %d do not agree"
+                             % (tuple(traj.shape), tuple(truth.shape), tuple(mask.shape), E))
+        blocks = (m + 63) // 64
+        partials = torch.empty((blocks * F * 3 * D,), dtype=torch.float32, device=self.device)
+        out, c = self._calibration_outputs(F, D, p, E)
+        w0 = 0
+        for n in (calls or [m]):
+            # a launch reads its windows' [F, n, p, D] slice as one tensor
+            part = traj if n == m else traj.reshape(F, m, p, D)[:, w0:w0 + n].contiguous()
+            self._check(self.lib.cadm_calibration_stats(ptr(part), ptr(truth[w0:]), ld, ptr(mask[w0:]), n, F, p, E, D, w0, ptr(partials), blocks,
+                                                        ct.byref(c), int(w0 + n >= m), self.stream), "cadm_calibration_stats")
+            w0 += n
+        if w0 != m:
+            raise ValueError("calibration_stats: calls %r do not add up to %d windows" % (calls, m))
+        return out
+
+    def eval_calibration(self, dev, N, F, chunk=4096, seed=0, call=0, eps=None):
+        """`cadm_eval_calibration` on the device-resident windowed dataset `dev` (see `eval_horizon`: the same arguments, rollouts
+        and noise keys) -> the dict of `calibration_stats`."""
+        if chunk <= 0 or chunk % 64:
+            raise ValueError("eval_calibration: chunk must be a positive multiple of 64, got %r" % (chunk,))
+        eps = None if eps is None else self._t(eps)
+        mc = min(int(chunk), (N + 63) // 64 * 64)
+        self.ensure_rollout(_lib.NOISE_NONE if self.deterministic else _lib.NOISE_INJECT if eps is not None else _lib.NOISE_PHILOX, min(mc, N), 1)
+        nbytes = self.lib.cadm_eval_calibration_workspace_bytes(self._ctx, int(N), int(F), int(chunk))
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
+        out, c = self._calibration_outputs(F, self.D, self.p, self.E)
+        g = lambda k: ptr(dev.get(k))
+        self._check(self.lib.cadm_eval_calibration(self._ctx, g("obs"), g("act"), g("obs_next"), g("cp_obs") if self.C > 0 else None,
+                                                   g("cp_act") if self.C > 0 else None, g("future_bool"), int(N), int(F), int(chunk), seed, call,
+                                                   ptr(eps), ptr(ws), ct.byref(c), self.stream), "cadm_eval_calibration")
+        return out
+
     # ------------------------------------------------------------------ forecast of a plan (opt-in; csrc/forecast.hip)
     def _forecast_outputs(self, m, n, H, p, E, rollout_returns=False):
         D = self.D

@@ -539,6 +539,43 @@ int cadm_eval_horizon(cadm_ctx* ctx, const float* ds_obs, const float* ds_act, c
                       const float* eps, void* workspace, float* se_out, float* spread_out, float* se_member_out,
                       int32_t* count_out, int32_t* diverged_out, void* stream);
 
+/* Calibration of the predictive distribution (no reference twin): are the particles the planner scores a calibrated sample of where
+ * the system went?  The inputs of cadm_horizon_error -- traj [F,m,1,p,D], truth with a row stride, mask [m,F], p % E == 0 -- and its
+ * rule for which (window, step) pairs count; count_out / diverged_out equal cadm_horizon_error's on the same inputs.  Per counted
+ * pair and dim d, with particles x_0 .. x_{p-1}, truth y, every comparison in float32 (cadm_calibration_out, device pointers):
+ *   rank_hist [F,D,p+1] int32           += 1 at r = #{j : x_j < y}
+ *   rank_hist_member [E,F,D,p/E+1] int32   the same over each member's own p / E particles
+ *   ties [F,D] int32                    += 1 where some x_j == y
+ *   degenerate [F,D] int32              += 1 where the biased particle variance v is exactly 0; left out of z2 and nll
+ *   crps [F,D] fp32 sum                 (1/p) sum_j |x_j - y| - (1/(2 p^2)) sum_j sum_k |x_j - x_k|, formed per window, then summed
+ *   z2 [F,D] fp32 sum                   (xbar - y)^2 / v
+ *   nll [F,D] fp32 sum                  0.5 (log 2 pi + log v + (xbar - y)^2 / v)
+ *   count, diverged [F] int32           as cadm_horizon_error
+ * xbar and v are formed as cadm_horizon_error forms them: v is the per-window term of its spread_out.  Sums and counts; the caller divides.
+ * Reduction contract: the float sums follow cadm_horizon_error's (stage 1 per block of 64 windows of the GLOBAL index window0 + i,
+ * window0 % 64 == 0; stage 2 when `finalize` != 0 over all blocks written so far; no floating-point atomics; the same bits run to
+ * run and however the windows are cut into calls).  `partials`: partials_blocks * F * 3 * D floats.  The integers are exact in any
+ * order: every call ADDS to them (integer atomics), and the call with window0 == 0 clears them first -- so every pointer of `out` is
+ * required in every call, and the calls of one evaluation share one `out`.
+ * All argument checks run before any HIP call: null pointers, F, m, p, D >= 1, p % E == 0, window0 % 64 == 0, D <= 64, F <= 65535,
+ * one window's tile, float slots and the histograms (4 D (p + 3) + D (2 p + E + 9) + 40 bytes) within 48 KiB, the blocks within
+ * partials_blocks. */
+typedef struct cadm_calibration_out {
+    int32_t *rank_hist, *rank_hist_member, *ties, *degenerate;
+    float *crps, *z2, *nll;
+    int32_t *count, *diverged;
+} cadm_calibration_out;
+int cadm_calibration_stats(const float* traj, const float* truth, long long truth_row_stride, const float* mask, int m, int F, int p,
+                           int E, int D, long long window0, float* partials, long long partials_blocks,
+                           const cadm_calibration_out* out, int finalize, void* stream);
+/* The same statistics for the ctx's model on a device-resident windowed dataset: cadm_eval_horizon's arguments, chunk loop, rollout
+ * rows and noise keys (with the same (seed, call) the two see the same trajectories), with cadm_calibration_stats as the reduction.
+ * workspace: cadm_eval_calibration_workspace_bytes(ctx, N, F, chunk) bytes (0 for bad arguments). */
+size_t cadm_eval_calibration_workspace_bytes(cadm_ctx* ctx, int N, int F, int chunk);
+int cadm_eval_calibration(cadm_ctx* ctx, const float* ds_obs, const float* ds_act, const float* ds_obs_next, const float* ds_cp_obs,
+                          const float* ds_cp_act, const float* future_bool, int N, int F, int chunk, uint32_t seed, uint32_t call,
+                          const float* eps, void* workspace, const cadm_calibration_out* out, void* stream);
+
 /* Forecast of a plan (no reference twin, OPT-IN): what the ensemble predicts under given action sequences, step by step, and how
  * sure it is -- the trajectories of one rollout reduced on the device.  The rollout kernels and the planner loops are untouched.
  *
