@@ -49,13 +49,13 @@ __global__ void pack_xdl_kernel(const XdlPackArgs a) {
         }
         const int grp = lane >> 4, m = lane & 15;
         int tile, c;
-        if (invf) { tile = g.tstart(w) + fj; c = g.NC0 - 1; }      // the invariant chunk: one fragment per tile, in tile order
+        if (invf) { tile = g.tile_of(w, fj); c = g.NC0 - 1; }      // the invariant chunk: one fragment per tile, in the wave's tile order
         else if (layer < g.NH) {              // hidden-type outputs: tiles in groups of xdl_group(), chunk-major inside a group
             const int gsz = xdl_group();
             const int gi = fj / (gsz * nchl), jj = fj - gsz * gi * nchl;
             const int gs = (ntw - gsz * gi) < gsz ? (ntw - gsz * gi) : gsz;
             c = jj / gs;
-            tile = g.tstart(w) + gsz * gi + jj % gs;
+            tile = g.tile_of(w, gsz * gi + jj % gs);
         } else {                              // head: valid slots in order, chunk-major per slot
             int sv = fj / g.NCH;
             c = fj % g.NCH;
@@ -69,11 +69,13 @@ __global__ void pack_xdl_kernel(const XdlPackArgs a) {
         if (layer == 0) { kin = 32 * c + 8 * grp + i; if (kin >= g.K0) kin = -1; }
         else { kin = (2 * c + (i >> 2)) * 16 + 4 * grp + (i & 3); if (kin >= g.HIDR) kin = -1; }
         const int K = layer == 0 ? g.K0 : g.HIDR;     // (master weights: the MODEL's width; units HIDR .. HID - 1 are zero padding)
+        // the half tile (xdl_geo.h): rows 0-7 hold w1 in both parts, rows 8-15 the SAME units' w2 in part 0 and zeros in part 1
+        const bool half = g.HALF && layer < g.NH && tile == g.NT - 1;
         float v = 0.0f;
         if (kin >= 0 && tile >= 0) {
             if (layer < g.NH) {
-                const int u = 16 * tile + m;
-                if (u < g.HIDR) v = a.W[layer][((size_t)e * K + kin) * g.HIDR + u];
+                const int u = 16 * tile + (half ? (m & 7) : m);
+                if (u < g.HIDR && !(half && part == 1 && m >= 8)) v = a.W[layer][((size_t)e * K + kin) * g.HIDR + u];
             } else {
                 const int q = m >> 2, r = m & 3;
                 const int d = 8 * tile + 2 * q + (r & 1);
@@ -86,7 +88,7 @@ __global__ void pack_xdl_kernel(const XdlPackArgs a) {
         if (!(fabsf(v) <= 65000.0f)) { *a.overflow = 1; v = 0.0f; }
         const _Float16 v1 = (_Float16)v;
         const _Float16 v2 = (_Float16)((v - (float)v1) * 2048.0f);
-        a.dst[idx] = f16_bits(part == 0 ? v1 : v2);
+        a.dst[idx] = f16_bits(half ? (m < 8 ? v1 : v2) : part == 0 ? v1 : v2);
     }
 }
 

@@ -17,7 +17,8 @@
 //     streamed from L2 in consumption order through a register ring), the 16 rows of a tile are the B / D columns.  A
 //     lane's D fragments of tiles (2c, 2c+1) are its B fragment of chunk c of the next layer: activations cross layers
 //     through LDS with lane-linear accesses;
-//   * wave w owns BASE + (w < EXTRA) hidden tiles and computes them two at a time (xdl_geo.h: xdl_group) over the whole K (the
+//   * wave w owns BASE + (w < EXTRA) hidden tiles (xdl_geo.h: xdl_tile_of; a last tile with at most 8 real units is a HALF tile -- two
+//     MFMAs per chunk into one accumulator -- owned by a wave of the busiest SIMD) and computes them two at a time (xdl_group) over the whole K (the
 //     B operand is read chunk by chunk from LDS, ahead of its use); the last group's epilogue (swish, f16 split, LDS store)
 //     overlaps with the SIMD's other wave, earlier groups' with the next group's MFMAs;
 //   * MT = 1: the rollout state lives in registers of the 256 "feature threads" (waves 0-3), their twins in waves 4-7
@@ -59,6 +60,11 @@ struct XC {
     static constexpr int NTO = (D + 7) / 8;               // head tiles (8 dims: mu | lv)
     static constexpr int NW = CADM_XDL_WAVES, NTHR = NW * 64;
     static constexpr int BASE = NT / NW, EXTRA = NT % NW;
+    // half last hidden tile (xdl_geo.h): two MFMAs per chunk into one accumulator, on wave HALFW (its last local tile), which runs a body of
+    // its own; MOVED: that wave is not the tile's contiguous owner, and the full tiles are dealt around it (xdl_tile_of)
+    static constexpr bool HALF = xdl_half(HID, NW), MOVED = xdl_half_moved(HID, NW);
+    static constexpr int HALFW = xdl_half_wave(HID, NW);
+    static_assert(xdl_owners_ok(HID, NW), "hidden tile ownership: every tile exactly one owner");
     static constexpr int NTOW = (NTO + NW - 1) / NW;      // head tile slots per wave
     static_assert(NTOW == 1, "one head tile per wave at most (obs dim <= 64)");
     static constexpr int R = 4;                           // ring depth (fragments)
@@ -200,6 +206,24 @@ __device__ __forceinline__ void xdl_operand_nops(floatx4& a, floatx4& b, floatx4
     if constexpr (LL) asm volatile("s_nop 4" : "+v"(a), "+v"(b), "+v"(c));
     else asm volatile("s_nop 4" : "+v"(a), "+v"(b));
 }
+// (a half tile has ONE accumulator, xdl_geo.h: naming a second one would keep 4 dead registers alive through the sweep)
+__device__ __forceinline__ void xdl_result_nops1(floatx4& a) { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" : "+v"(a)); }
+__device__ __forceinline__ void xdl_operand_nops1(floatx4& a) { asm volatile("s_nop 4" : "+v"(a)); }
+// Half tile: the accumulator's lanes 32-63 hold LO of the units whose HI is in lanes 0-31 (D layout: row 4g + r in lane group g, so lane
+// L + 32 holds LO of the unit whose HI is in lane L).  v_permlane32_swap a, b exchanges lanes 32-63 of a with lanes 0-31 of b: on registers
+// (r, r + 1) of the accumulator it leaves  a = HI of unit r in lanes 0-31 | HI of unit r + 1 in lanes 32-63,  b = LO of the same.  Two swaps
+// turn the four registers into ONE (HI, LO) pair of two values per lane, all 64 lanes busy: lanes 0-31 finish units 4g + 0 and 4g + 2, lanes
+// 32-63 units 4g + 1 and 4g + 3 of the same (g, row) -- half the epilogue arithmetic of a full tile, and nobody computes the units that do not exist.
+__device__ __forceinline__ void xdl_half_pairs(const floatx4& acc, floatx2& hp, floatx2& lp) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float fa = acc[2 * k], fb = acc[2 * k + 1];      // (through scalars: bit_cast of an ext-vector element is miscompiled by hipcc 7.2)
+        const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(fa), __float_as_uint(fb), false, false);
+        const unsigned ua = s[0], ub = s[1];
+        hp[k] = __uint_as_float(ua);
+        lp[k] = __uint_as_float(ub);
+    }
+}
 
 // split an ACTIVATION for the f16 pipe: hi = f16(v), lo = f16(v - hi), UNSCALED (xdl_geo.h: the products w1 * lo accumulate next to
 // w1 * hi; a low part below the f16 normal range is a subnormal with 2^-24 absolute spacing: an absolute error of 3e-8 on an
@@ -221,7 +245,8 @@ __device__ __forceinline__ void xsplit(float v, _Float16& hi, _Float16& lo) {
 // the wave-tile kernel's waves drift apart inside a block, an epilogue meets the partner's MFMAs: scalar, cfg3 -1.8 %; the cooperative
 // kernel's waves run the same phase between the same barriers, the shorter epilogue wins: packed, cfg2 -0.5..1.5 % (same-box A/B,
 // profiles/r5_wave_tile_experiments.md).  The rollout translation units are compiled with -fno-slp-vectorize so hipcc does not re-pack scalars.
-template <class G, bool PACKED = true>      // (packed in the cooperative kernel, scalar in the wave-tile kernel)
+// HT: local index of the wave's half tile (xdl_geo.h; the wave's LAST tile, global tile NT - 1 whoever owns it), -1: none.
+template <class G, bool PACKED = true, int HT = -1>      // (packed in the cooperative kernel, scalar in the wave-tile kernel)
 struct XHiddenEpi {
     static constexpr int NSTAGE = 6;
     struct StateP { floatx2 v[2], s[2]; f16x4 h1, h2; };
@@ -232,31 +257,39 @@ struct XHiddenEpi {
     int bias_off;
     int layer, out, tstart, lane;
     const unsigned char* inv = nullptr;      // layer 0 of a geometry with an invariant last chunk (xdl_geo.h): (HI, LO) of "bias + that chunk" per (row tile, tile)
+    __device__ __forceinline__ int gtile(int ti) const { return (HT >= 0 && ti == HT) ? G::NT - 1 : tstart + ti; }      // global tile of local tile ti (xdl_tile_of)
     __device__ __forceinline__ floatx4 init(int ti, int hh) const {       // accumulator HI: bias tile (fp32, D layout) of local tile ti, or the tile's invariant start
-        if (inv) return *reinterpret_cast<const floatx4*>(inv + ((hh * G::NT + tstart + ti) * 2 + 0) * 1024 + lane * 16);
-        const int tile = layer * G::NT + tstart + ti;
+        if (inv) return *reinterpret_cast<const floatx4*>(inv + ((hh * G::NT + gtile(ti)) * 2 + 0) * 1024 + lane * 16);
+        const int tile = layer * G::NT + gtile(ti);
         const int bt = tile * 64 + lane;
         // (a select between an LDS and a global POINTER would become a flat load with a full vmcnt/lgkmcnt drain)
         if constexpr (G::BIAS_LDS) return *reinterpret_cast<const floatx4*>(xsmem + bias_off + tile * G::BIAS_TILE_B + (lane >> 4) * 16);
         else return *reinterpret_cast<const floatx4*>(xb + bt * 4);
     }
     __device__ __forceinline__ floatx4 init_lo(int ti, int hh) const {    // accumulator LO: zero, or the tile's invariant start
-        if (inv) return *reinterpret_cast<const floatx4*>(inv + ((hh * G::NT + tstart + ti) * 2 + 1) * 1024 + lane * 16);
+        if (inv) return *reinterpret_cast<const floatx4*>(inv + ((hh * G::NT + gtile(ti)) * 2 + 1) * 1024 + lane * 16);
         return floatx4{0.f, 0.f, 0.f, 0.f};
     }
     static __device__ __forceinline__ floatx2 lo2(const floatx4& x) { return __builtin_shufflevector(x, x, 0, 1); }
     static __device__ __forceinline__ floatx2 hi2(const floatx4& x) { return __builtin_shufflevector(x, x, 2, 3); }
     template <int S>
-    __device__ __forceinline__ void stage(int ti, int hh, const floatx4& hi, const floatx4& lo, const floatx4& ll, State& st) const {
+    __device__ __forceinline__ void stage(int ti, int hh, const floatx4& hi, const floatx4& lo_, const floatx4& ll, State& st) const {
+        // half tile: ONE accumulator, hi -- LO is its upper half wave (lo_ is not read)
+        const floatx4& lo = lo_;
+        const bool half = HT >= 0 && ti == HT;      // ONE accumulator, hi; the stages work on one pair of values per lane (xdl_half_pairs)
+        const int nq = half ? 1 : 2;
         constexpr float KE = G::ACT == CADM_ACT_TANH ? -2.0f * 1.4426950408889634f : -1.4426950408889634f;
         constexpr bool SIG = G::ACT != CADM_ACT_RELU && G::ACT != CADM_ACT_NONE;       // nonlinearities built on sigmoid
         if constexpr (PACKED) {
         if constexpr (S == 0) {            // pre-activation (hi + 2^-11 lo), exp2 argument
             const floatx2 c11 = {4.8828125e-4f, 4.8828125e-4f};
             const floatx2 ke = {KE, KE};
+            floatx2 hp = lo2(hi), lp = lo2(lo);
+            if (half) xdl_half_pairs(hi, hp, lp);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const floatx2 pre = __builtin_elementwise_fma(q ? hi2(lo) : lo2(lo), c11, q ? hi2(hi) : lo2(hi));
+                if (q >= nq) continue;
+                const floatx2 pre = __builtin_elementwise_fma(q ? hi2(lo) : lp, c11, q ? hi2(hi) : hp);
                 st.v[q] = pre;                 // (no f16-range clamp: the conversions below saturate, fp16_saturate_on)
                 // swish: the packed weights carry log2(e) (xdl_geo.h), pre IS the exp2 argument up to its sign
                 if constexpr (G::ACT == CADM_ACT_SWISH) st.s[q] = -pre;
@@ -265,13 +298,14 @@ struct XHiddenEpi {
         } else if constexpr (S == 1) {
             if constexpr (SIG) {
 #pragma unroll
-                for (int q = 0; q < 2; ++q) { st.s[q][0] = __builtin_amdgcn_exp2f(st.s[q][0]); st.s[q][1] = __builtin_amdgcn_exp2f(st.s[q][1]); }
+                for (int q = 0; q < 2; ++q) { if (q >= nq) continue; st.s[q][0] = __builtin_amdgcn_exp2f(st.s[q][0]); st.s[q][1] = __builtin_amdgcn_exp2f(st.s[q][1]); }
             }
         } else if constexpr (S == 2) {
             if constexpr (SIG) {
                 const floatx2 one = {1.0f, 1.0f};
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
+                    if (q >= nq) continue;
                     st.s[q] = st.s[q] + one;
                     st.s[q][0] = __builtin_amdgcn_rcpf(st.s[q][0]);
                     st.s[q][1] = __builtin_amdgcn_rcpf(st.s[q][1]);
@@ -280,6 +314,7 @@ struct XHiddenEpi {
         } else if constexpr (S == 3) {     // the nonlinearity (dynamics.py:17-24) and the high f16 part
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
+                if (q >= nq) continue;
                 if constexpr (G::ACT == CADM_ACT_SWISH) st.v[q] = st.v[q] * st.s[q];                 // x * sigmoid(x), :23
                 else if constexpr (G::ACT == CADM_ACT_SIGMOID) st.v[q] = st.s[q];                    // 1 / (1 + e^-x)
                 else if constexpr (G::ACT == CADM_ACT_TANH) {      // 2 sigmoid(2x) - 1 (s was built from 2x); odd series near 0, where that cancels
@@ -296,6 +331,7 @@ struct XHiddenEpi {
         } else if constexpr (S == 4) {     // low part: h - hi = fma(hi, -1, h), exact in fp32, rounded once to f16 (unscaled: xsplit)
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
+                if (q >= nq) continue;
                 const floatx2 t = st.v[q];
                 const f16x2 hp = {st.h1[2 * q], st.h1[2 * q + 1]};
                 f16x2 lp;
@@ -348,10 +384,20 @@ struct XHiddenEpi {
         }
         }
         if constexpr (S == 5) {
-            const int Tg = tstart + ti;
+            const int Tg = gtile(ti);
             unsigned char* dst = xsmem + out + hh * G::ACT_T + ((Tg >> 1) * 64 + lane) * 16 + (Tg & 1) * 8;
-            *reinterpret_cast<f16x4*>(dst) = st.h1;
-            *reinterpret_cast<f16x4*>(dst + G::NCH * 1024) = st.h2;
+            if (half) {
+                // lanes 0-31 hold units 4g + 0, 4g + 2 of (g, row) = lane & 31, lanes 32-63 units 4g + 1, 4g + 3 of the same: four 2-byte stores.
+                // Nobody writes the tile's other eight unit slots (units that do not exist): they keep the zeros of the workgroup's LDS fill.
+                unsigned char* d2 = xsmem + out + hh * G::ACT_T + ((Tg >> 1) * 64 + (lane & 31)) * 16 + (Tg & 1) * 8 + (lane >> 5) * 2;
+                *reinterpret_cast<_Float16*>(d2) = st.h1[0];
+                *reinterpret_cast<_Float16*>(d2 + 4) = st.h1[1];
+                *reinterpret_cast<_Float16*>(d2 + G::NCH * 1024) = st.h2[0];
+                *reinterpret_cast<_Float16*>(d2 + G::NCH * 1024 + 4) = st.h2[1];
+            } else {
+                *reinterpret_cast<f16x4*>(dst) = st.h1;
+                *reinterpret_cast<f16x4*>(dst + G::NCH * 1024) = st.h2;
+            }
         }
     }
 };
@@ -391,7 +437,9 @@ struct XHeadEpi {
 //   VALU work of the same wave); the last group's epilogue overlaps with the SIMD's other wave.
 //   NLDS: the LAST NLDS fragments of the layer (consumption order) are LDS-resident (lq: this wave's copy, made once per workgroup):
 //   they go through the ring like streamed ones, from LDS instead of L2.  The first R ring fragments stay streamed.
-template <class G, int NTW, int NCHL, int NRES, int GS, bool SIDE, int NLDS, int NCB = NCHL, class Epi>
+//   HT: local index of this wave's half tile (xdl_geo.h), -1: none.  That tile has ONE accumulator (hi): product 0 takes part 0 of its
+//   fragment, product 1 is not issued, product 2 takes part 1.  Fragment order, ring slots and residency are a full tile's.
+template <class G, int NTW, int NCHL, int NRES, int GS, bool SIDE, int NLDS, int NCB = NCHL, int HT = -1, class Epi>
 __device__ __forceinline__ void xdl_sweep(XRing<G>& ring, const uintx4 (*res)[2], __amdgpu_buffer_rsrc_t rsrc, unsigned wcur,
                                           unsigned wnext, int nx_nf, const unsigned char* lds_in, int lane, const Epi& epi,
                                           const unsigned char* lq TS_PARAMS) {
@@ -423,6 +471,7 @@ __device__ __forceinline__ void xdl_sweep(XRing<G>& ring, const uintx4 (*res)[2]
         }
     };
     constexpr int NG = (NTW + GS - 1) / GS, NST = Epi::NSTAGE;
+    static_assert(HT < 0 || (HT == NTW - 1 && G::NPROD == 3 && G::ASM_MFMA), "the half tile is the wave's last tile; three products per block");
     constexpr int NPR = G::NPROD;
     floatx4 hi[2][GS][MT], lo[2][GS][MT], ll[2][GS][MT];   // [group parity][tile of the group][row tile]: the previous group is
     typename Epi::State pst[GS][MT];                       // finished as side work while this group accumulates (no register moves)
@@ -445,7 +494,10 @@ __device__ __forceinline__ void xdl_sweep(XRing<G>& ring, const uintx4 (*res)[2]
 #pragma unroll
         for (int k = 0; k < gs; ++k)
 #pragma unroll
-            for (int h = 0; h < MT; ++h) xdl_operand_nops<false>(hi[gp][k][h], lo[gp][k][h], ll[gp][k][h]);      // VALU-zeroed accumulators -> MFMA srcC
+            for (int h = 0; h < MT; ++h) {      // VALU-zeroed accumulators -> MFMA srcC
+                if (HT >= 0 && GS * g + k == HT) xdl_operand_nops1(hi[gp][k][h]);
+                else xdl_operand_nops<false>(hi[gp][k][h], lo[gp][k][h], ll[gp][k][h]);
+            }
         static_for(std::make_integer_sequence<int, NCHL>{}, [&](auto cc) {
             constexpr int c = decltype(cc)::value;
             constexpr int j0 = GS * g * NCHL + c * gs;
@@ -454,10 +506,12 @@ __device__ __forceinline__ void xdl_sweep(XRing<G>& ring, const uintx4 (*res)[2]
             static_for(std::make_integer_sequence<int, NPR * gs * MT>{}, [&](auto mc) {      // hi(k,h).. lo(k,h).. lo'(k,h).. [ll(k,h)..]
                 constexpr int h = decltype(mc)::value % MT, k = (decltype(mc)::value / MT) % gs, prod = decltype(mc)::value / (MT * gs);
                 constexpr int j = j0 + k;
+                constexpr bool half = HT >= 0 && GS * g + k == HT;      // [w1; w2] x1, [w1; 0] x2 into hi
                 floatx4& acc = (prod == 0 || prod == 2) ? hi[gp][k][h] : lo[gp][k][h];      // w1 x1, w1 x2 | w2 x1 [, w2 x2] (x2 unscaled: xdl_geo.h)
                 const f16x8& x = prod >= 2 ? X2[c % XD][h] : X1[c % XD][h];
-                constexpr int part = (prod == 1 || prod == 3) ? 1 : 0;
-                if constexpr (j < NRES) xmfma_res(acc, res[j][part], x);
+                constexpr int part = half ? (prod == 2 ? 1 : 0) : (prod == 1 || prod == 3) ? 1 : 0;
+                if constexpr (half && prod == 1) {}
+                else if constexpr (j < NRES) xmfma_res(acc, res[j][part], x);
                 else xmfma_ring<G::ASM_MFMA>(acc, ring.w[(j - NRES) % R][part], x);
             });
             static_for(std::make_integer_sequence<int, gs>{}, [&](auto kc) {
@@ -484,7 +538,10 @@ __device__ __forceinline__ void xdl_sweep(XRing<G>& ring, const uintx4 (*res)[2]
 #pragma unroll
             for (int k = 0; k < gs; ++k)
 #pragma unroll
-                for (int h = 0; h < MT; ++h) xdl_result_nops<false>(hi[gp][k][h], lo[gp][k][h], ll[gp][k][h]);
+                for (int h = 0; h < MT; ++h) {
+                    if (HT >= 0 && GS * g + k == HT) xdl_result_nops1(hi[gp][k][h]);
+                    else xdl_result_nops<false>(hi[gp][k][h], lo[gp][k][h], ll[gp][k][h]);
+                }
             static_for(std::make_integer_sequence<int, NST>{}, [&](auto sc) {
 #pragma unroll
                 for (int k = 0; k < gs; ++k)
@@ -502,8 +559,11 @@ __device__ __forceinline__ void xdl_sweep(XRing<G>& ring, const uintx4 (*res)[2]
     });
 }
 
-template <class G, int NOISE, int NTW>
+// HALFB: the body of the wave that owns the half tile (XC::HALFW; its last local tile: xdl_geo.h)
+template <class G, int NOISE, int NTW, bool HALFB = false>
 __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsmem) {
+    constexpr int HT = HALFB ? NTW - 1 : -1;
+    using HEpi = XHiddenEpi<G, true, HT>;
     constexpr int D = G::D, A = G::A, P = G::P, C = G::C, K0 = G::K0, NC0 = G::NC0, NCH = G::NCH, NTO = G::NTO;
     constexpr int NP = G::NP, NPI = G::NPI, NAI = G::NAI, ENV = G::ENV, R = G::R;
     constexpr int MT = G::MT;
@@ -635,7 +695,8 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
     const unsigned wbase = e * a.xw_member_b + a.xw_wave_b[wave];
     const float* xb = a.xb + (size_t)e * a.xb_member;
     const int my_ntw = G::BASE + (wave < G::EXTRA ? 1 : 0);
-    const int tstart = wave * G::BASE + (wave < G::EXTRA ? wave : G::EXTRA);
+    // first global tile of this wave's contiguous tiles (xdl_tile_of; a half tile that changed owner is not one of them: HEpi::gtile)
+    const int tstart = G::MOVED ? wave * G::BASE + (wave < G::EXTRA - 1 ? wave : G::EXTRA - 1) : wave * G::BASE + (wave < G::EXTRA ? wave : G::EXTRA);
     const int ht = G::NW - 1 - wave;                       // this wave's head tile (if < NTO)
     const int nhead = ht < NTO ? 1 : 0;
     const int l0_nf = my_ntw * G::NC0S, lh_nf = my_ntw * NCH, hd_nf = nhead * NCH;      // (NC0S: without layer 0's invariant chunk, xdl_geo.h)
@@ -803,7 +864,7 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
             // this kernel does so here, once per row tile -- bias -> HI += w1 x1, LO += w2 x1, HI += w1 x2, the instructions a sweep would issue --
             // and leaves (HI, LO) per tile in LDS: the step loop's layer-0 accumulators start from them.  A wave reads back only its own tiles.
             floatx4 ll0 = floatx4{0.f, 0.f, 0.f, 0.f};
-            const XHiddenEpi<G> epib{xsmem, xb, bias_off, 0, 0, tstart, lane};
+            const HEpi epib{xsmem, xb, bias_off, 0, 0, tstart, lane};
             static_for(std::make_integer_sequence<int, NTW>{}, [&](auto tc) {
                 constexpr int ti = decltype(tc)::value;
                 const uintx4 w0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, w_inv + ti * CADM_XDL_FRAG_BYTES, 0);
@@ -814,14 +875,22 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
                     const f16x8 x1 = *reinterpret_cast<const f16x8*>(xin + ((0 * NC0 + NC0 - 1) * 64 + lane) * 16);
                     const f16x8 x2 = *reinterpret_cast<const f16x8*>(xin + ((1 * NC0 + NC0 - 1) * 64 + lane) * 16);
                     floatx4 hi = epib.init(ti, h), lo = floatx4{0.f, 0.f, 0.f, 0.f};
-                    xdl_operand_nops<false>(hi, lo, ll0);
-                    xmfma_ring<G::ASM_MFMA>(hi, w0, x1);
-                    xmfma_ring<G::ASM_MFMA>(lo, w1, x1);
-                    xmfma_ring<G::ASM_MFMA>(hi, w0, x2);
-                    xdl_result_nops<false>(hi, lo, ll0);
-                    unsigned char* dst = xsmem + inv_off + ((h * G::NT + tstart + ti) * 2) * 1024 + lane * 16;
-                    *reinterpret_cast<floatx4*>(dst) = hi;
-                    *reinterpret_cast<floatx4*>(dst + 1024) = lo;
+                    unsigned char* dst = xsmem + inv_off + ((h * G::NT + epib.gtile(ti)) * 2) * 1024 + lane * 16;
+                    if constexpr (ti == HT) {      // half tile: [w1; w2] x1, [w1; 0] x2 into the one accumulator the step loop starts from
+                        xdl_operand_nops1(hi);
+                        xmfma_ring<G::ASM_MFMA>(hi, w0, x1);
+                        xmfma_ring<G::ASM_MFMA>(hi, w1, x2);
+                        xdl_result_nops1(hi);
+                        *reinterpret_cast<floatx4*>(dst) = hi;
+                    } else {
+                        xdl_operand_nops<false>(hi, lo, ll0);
+                        xmfma_ring<G::ASM_MFMA>(hi, w0, x1);
+                        xmfma_ring<G::ASM_MFMA>(lo, w1, x1);
+                        xmfma_ring<G::ASM_MFMA>(hi, w0, x2);
+                        xdl_result_nops<false>(hi, lo, ll0);
+                        *reinterpret_cast<floatx4*>(dst) = hi;
+                        *reinterpret_cast<floatx4*>(dst + 1024) = lo;
+                    }
                 }
             });
         }
@@ -972,13 +1041,13 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
             {
                 int act_out = G::ACTA, act_in = G::XIN;      // LDS byte offsets (not pointers: keeps every access a ds_ op)
                 // hidden epilogue: bias, swish, f16 split, store as the next layer's B operand
-                auto hidden_epi = [&](int layer, int out) { return XHiddenEpi<G>{xsmem, xb, bias_off, layer, out, tstart, lane}; };
+                auto hidden_epi = [&](int layer, int out) { return HEpi{xsmem, xb, bias_off, layer, out, tstart, lane}; };
                 // layer 0
                 {
                     const int nx = next_streamed(0);
-                    XHiddenEpi<G> epi0 = hidden_epi(0, act_out);
+                    HEpi epi0 = hidden_epi(0, act_out);
                     if constexpr (G::INV) epi0.inv = xsmem + inv_off;      // accumulators start from "bias + invariant chunk" (made once per row tile, below the tile prologue)
-                    xdl_sweep<G, NTW, G::NC0S, 0, GSZ, true, 0, NC0>(ring, nullptr, rsrc, w_l0, lay_off(nx), lay_nf(nx), xsmem + act_in, lane,
+                    xdl_sweep<G, NTW, G::NC0S, 0, GSZ, true, 0, NC0, HT>(ring, nullptr, rsrc, w_l0, lay_off(nx), lay_nf(nx), xsmem + act_in, lane,
                                               epi0, nullptr TS_ARGS);
                 }
                 TS(2)
@@ -996,7 +1065,7 @@ __device__ __forceinline__ void xdl_run(const RolloutArgs& a, unsigned char* xsm
                     // (layers 1..3: distinct instantiations with their LDS-resident tail; deeper layers stream everything)
                     constexpr int NL = decltype(lq_c)::value ? LQ : 0;
                     TR_ON(t == 10 && l == 2, wave)      // (CADM_PHASE_TIMING builds: raw stamps of this one sweep, tools/sweep_trace.py)
-                    xdl_sweep<G, NTW, NCH, NRES, GSZ, true, NL>(ring, resH + RBASE, rsrc, lay_off(l), lay_off(nx), lay_nf(nx), xsmem + act_in, lane,
+                    xdl_sweep<G, NTW, NCH, NRES, GSZ, true, NL, NCH, HT>(ring, resH + RBASE, rsrc, lay_off(l), lay_off(nx), lay_nf(nx), xsmem + act_in, lane,
                                                  hidden_epi(l, act_out), xsmem + lq_off + (l - 1) * LQ * CADM_XDL_FRAG_BYTES TS_ARGS);
                     // two row tiles: the waves that have a head tile (and one hidden tile less than the others: they would
                     // wait at this barrier anyway) make their noise now
@@ -1079,11 +1148,20 @@ __global__ __launch_bounds__(G::NTHR) void rollout_xdl_kernel(const RolloutArgs 
         if (wave >= G::NW / 2) __builtin_amdgcn_s_setprio(1);
     }
     // waves [0, EXTRA) own one hidden tile more than the others: two specialisations of the whole body, chosen per wave
-    // (a scalar branch; every wave executes the same number of barriers)
+    // (a scalar branch; every wave executes the same number of barriers); the owner of a half tile (xdl_geo.h) runs a third
+    // (the branch the half tile's owner is not in stays the two-way choice it was: its code and register allocation are unchanged)
     if (wave < G::EXTRA) {
-        if constexpr (G::EXTRA > 0) xdl_run<G, NOISE, G::BASE + 1>(a, xsmem_raw);
+        if constexpr (G::EXTRA > 0) {
+            if constexpr (G::HALF && G::HALFW < G::EXTRA) {
+                if (wave == G::HALFW) xdl_run<G, NOISE, G::BASE + 1, true>(a, xsmem_raw);
+                else if constexpr (G::EXTRA > 1) xdl_run<G, NOISE, G::BASE + 1>(a, xsmem_raw);
+            } else xdl_run<G, NOISE, G::BASE + 1>(a, xsmem_raw);
+        }
     } else {
-        xdl_run<G, NOISE, G::BASE>(a, xsmem_raw);
+        if constexpr (G::HALF && G::HALFW >= G::EXTRA) {
+            if (wave == G::HALFW) xdl_run<G, NOISE, G::BASE, true>(a, xsmem_raw);
+            else xdl_run<G, NOISE, G::BASE>(a, xsmem_raw);
+        } else xdl_run<G, NOISE, G::BASE>(a, xsmem_raw);
     }
 }
 

@@ -16,7 +16,8 @@
 //     32 = one PAIR of producer tiles, so a lane's D fragments (units 4g..4g+3 of tiles 2c, 2c+1) ARE its B fragment
 //     for chunk c: activations cross layers through LDS without any cross-lane movement.
 //   * Hidden tiles are distributed over the CADM_XDL_WAVES waves of a workgroup contiguously (wave w: BASE + (w < EXTRA)
-//     tiles); head tiles (8 obs dims: mu0 mu1 lv0 lv1 per lane) go to the waves with the fewest hidden tiles first.
+//     tiles; XdlGeo::tile_of maps a wave's local tile to the global one -- a HALF tile, below, may change owner); head tiles
+//     (8 obs dims: mu0 mu1 lv0 lv1 per lane) go to the waves with the fewest hidden tiles first.
 //   * A "fragment" = one (tile, chunk) of weights = 2 split parts x 64 lanes x 16 B = 2 KB.  Per (member, wave) the
 //     stream stores the fragments in EXACTLY the order that wave consumes them during one rollout step:
 //     [layer 0][hidden 1 .. NH-1][head]; inside a layer tiles go in groups of xdl_group(), chunk-major inside a group
@@ -35,6 +36,62 @@
 #define CADM_XDL_NARROW_HID 128
 __host__ __device__ constexpr int xdl_kernel_hid(int hid) { return hid < CADM_XDL_MIN_HID ? CADM_XDL_NARROW_HID : hid; }
 
+// HALF LAST HIDDEN TILE.  When the last hidden tile holds at most 8 real units (HID % 16 in 1..8; HID = 200: units 192..199 of tile 12) half
+// of its A operand is zero rows, and with three products per block the w2 rows fit there.  The cooperative stream packs that tile's fragments as
+//     part 0 = [ w1(u0..u7) ; w2(u0..u7) ]      acc += part0 * x1     rows 0-7: HI += w1 x1    rows 8-15: LO += w2 x1
+//     part 1 = [ w1(u0..u7) ;     0      ]      acc += part1 * x2     rows 0-7: HI += w1 x2    rows 8-15: += 0
+// (A-operand lane (grp, m) holds row m: m < 8 is unit 16 tile + m, m >= 8 is the low part of unit 16 tile + m - 8 in part 0, zero in part 1)
+// in every layer that OUTPUTS hidden units, layer 0's invariant-chunk fragment included: TWO MFMAs per (tile, chunk) into ONE accumulator
+// instead of three into two.  Every real output element sees the same dot products over the same k positions added in the same order as in the
+// three-MFMA form -- HI: w1 x1 then w1 x2, chunk by chunk; LO: w2 x1, chunk by chunk -- so the result is that form's bit for bit, with two
+// caveats nobody can observe: the zero rows of part 1 add +-0 to LO, which can only change the sign of a LO that is exactly zero (and then
+// fma(LO, 2^-11, HI) is HI either way unless HI is a zero too, whose sign swish / the f16 split pass on to a product with a finite weight), and a
+// NaN activation makes both forms NaN.  In the D fragment HI of units 4g..4g+3 sits in lane groups g = 0, 1, LO of the same units in groups
+// 2, 3: the epilogue exchanges half waves between register pairs (rollout_xdl.h: xdl_half_pairs), after which every lane holds (HI, LO) of
+// TWO real units -- half a full tile's epilogue arithmetic -- and stores them as 2-byte pieces; the slots of the units that do not exist are
+// written by nobody and keep the zeros of the workgroup's LDS fill.  (A first form -- LO brought down to lanes 0-31, lanes 32-63 idle and
+// storing zeros -- lengthened the owner's exposed epilogue by what the MFMAs saved: no gain, profiles/half_tile_ab.md.)  The bias tile needs
+// nothing: its lanes 32-63 are zero already, LO's initial value.  Fragment size, stream order and wave_frags are those of a full tile.  The wave-tile stream (NW = 1) keeps the three-MFMA form: it is what this one is tested against.
+// Units are NOT permuted among k positions (an MFMA's summation order depends on them).
+__host__ __device__ constexpr bool xdl_half(int hid_kernel, int nw) {
+    return nw == CADM_XDL_WAVES && hid_kernel <= 256 && hid_kernel % 16 >= 1 && hid_kernel % 16 <= 8;
+}
+// TILE OWNERSHIP.  Wave w runs on SIMD w mod 4, and a hidden layer ends when the busiest SIMD is done.  Where ONE SIMD carries more tiles
+// than every other (EXTRA mod 4 == 1: HID 200 is 13 tiles, 4 / 3 / 3 / 3) the half tile's saving counts only there, so it becomes the
+// LAST local tile of the last wave with an extra tile (wave EXTRA - 1, on that SIMD) and the full tiles are dealt contiguously around it:
+// HID 200: waves 0-3 {0,1} {2,3} {4,5} {6,7}, wave 4 {8, 12}, waves 5-7 {9} {10} {11} -- per hidden layer 2 x 21 + 21 + 14 = 77 MFMAs on
+// SIMD 0 against 63 on the others (84 before).  Everywhere else no placement lowers the busiest SIMD's count (no extra tiles, or two SIMDs
+// tied with full tiles only), and the last tile stays the last wave's.  xdl_half_wave: the owner, or -1 without a half tile.
+__host__ __device__ constexpr bool xdl_half_moved(int hid_kernel, int nw) {
+    return xdl_half(hid_kernel, nw) && (((hid_kernel + 15) / 16) % nw) % 4 == 1;
+}
+__host__ __device__ constexpr int xdl_half_wave(int hid_kernel, int nw) {
+    return !xdl_half(hid_kernel, nw) ? -1 : xdl_half_moved(hid_kernel, nw) ? ((hid_kernel + 15) / 16) % nw - 1 : nw - 1;
+}
+// global tile of local tile ti of wave w (nt tiles over nw waves)
+__host__ __device__ constexpr int xdl_tile_of(int nt, int nw, bool moved, int w, int ti) {
+    const int base = nt / nw, extra = nt % nw;
+    if (!moved) return w * base + (w < extra ? w : extra) + ti;
+    if (w == extra - 1 && ti == base) return nt - 1;
+    return w * base + (w < extra - 1 ? w : extra - 1) + ti;
+}
+__host__ __device__ constexpr bool xdl_owners_ok(int hid_kernel, int nw) {       // every tile has exactly one owner
+    const int nt = (hid_kernel + 15) / 16, base = nt / nw, extra = nt % nw;
+    for (int t = 0; t < nt; ++t) {
+        int n = 0;
+        for (int w = 0; w < nw; ++w)
+            for (int ti = 0; ti < base + (w < extra ? 1 : 0); ++ti) n += xdl_tile_of(nt, nw, xdl_half_moved(hid_kernel, nw), w, ti) == t ? 1 : 0;
+        if (n != 1) return false;
+    }
+    const int hw = xdl_half_wave(hid_kernel, nw);      // the half tile is its owner's LAST local tile
+    return hw < 0 || xdl_tile_of(nt, nw, xdl_half_moved(hid_kernel, nw), hw, base + (hw < extra ? 1 : 0) - 1) == nt - 1;
+}
+static_assert(xdl_owners_ok(128, CADM_XDL_WAVES) && xdl_owners_ok(200, CADM_XDL_WAVES) && xdl_owners_ok(256, CADM_XDL_WAVES) &&
+              xdl_owners_ok(512, CADM_XDL_WAVES) && xdl_owners_ok(200, 1), "hidden tile ownership: every tile exactly one owner");
+static_assert(!xdl_half(128, CADM_XDL_WAVES) && xdl_half(200, CADM_XDL_WAVES) && !xdl_half(256, CADM_XDL_WAVES) && !xdl_half(512, CADM_XDL_WAVES) &&
+              xdl_half_wave(200, CADM_XDL_WAVES) == 4 && xdl_tile_of(13, CADM_XDL_WAVES, true, 4, 1) == 12 && xdl_tile_of(13, CADM_XDL_WAVES, true, 7, 0) == 11 &&
+              xdl_half_wave(120, CADM_XDL_WAVES) == 7 && xdl_half_wave(196, CADM_XDL_WAVES) == 4, "half tile: of the compiled-in widths only 200");
+
 // INVARIANT LAST CHUNK OF LAYER 0 (round 6).  Layer 0's inputs are [obs features | action | context]; the context vector does not change
 // over a rollout, so a layer-0 chunk that holds ONLY context features (halfcheetah CaDM: K0 = 18 + 6 + 10 = 34, chunk 1 = context features
 // 8 and 9; slim humanoid: chunk 2 of 3) contributes the same products in all H steps.  Where that holds (xdl_inv0) EVERY flavour accumulates
@@ -52,8 +109,10 @@ struct XdlGeo {
     int INV;     // 1: the cooperative kernels' stream keeps layer 0's invariant chunk apart (above); the wave-tile stream (NW = 1) never does
     int NC0, NT, NCH, NTO, BASE, EXTRA, NTOW;
     int NW;      // waves the tiles are dealt to: CADM_XDL_WAVES (cooperative kernel), 1 (wave-tile kernel, rollout_wt.h: every wave owns ALL tiles)
+    int HALF;    // 1: the last hidden tile is packed as a half tile (above); HALFW its owner (-1: none)
+    int HALFW;
     __host__ __device__ int ntw(int w) const { return BASE + (w < EXTRA ? 1 : 0); }
-    __host__ __device__ int tstart(int w) const { return w * BASE + (w < EXTRA ? w : EXTRA); }
+    __host__ __device__ int tile_of(int w, int ti) const { return xdl_tile_of(NT, NW, HALF && xdl_half_moved(HID, NW), w, ti); }
     __host__ __device__ int head_tile(int w, int s) const { return (NW - 1 - w) + NW * s; }          // slot s of wave w (valid if < NTO)
     __host__ __device__ int nhead(int w) const {
         int n = 0;
@@ -82,6 +141,8 @@ inline XdlGeo make_xdl_geo(int K0, int hid_model, int D, int NH, int nw = CADM_X
     g.BASE = g.NT / nw;
     g.EXTRA = g.NT % nw;
     g.NTOW = (g.NTO + nw - 1) / nw;
+    g.HALF = xdl_half(HID, nw) ? 1 : 0;
+    g.HALFW = xdl_half_wave(HID, nw);
     return g;
 }
 
