@@ -87,6 +87,13 @@ class ConstraintParams(C.Structure):    # include/cadm_hip.h cadm_constraint_par
                 ("lo", C.c_float * MAX_CONSTRAINTS), ("hi", C.c_float * MAX_CONSTRAINTS)]
 
 
+KNOT_INTERPS = {"hold": 0, "linear": 1}                                    # CADM_KNOT_*
+
+
+class KnotParams(C.Structure):          # include/cadm_hip.h cadm_knot_params
+    _fields_ = [("spacing", C.c_int32), ("interp", C.c_int32)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -141,6 +148,9 @@ SIGNATURES = {
     "cadm_constrained_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i]),
     "cadm_constrained_plan": (_i, [_P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P,
                                    _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_shape_actions": (_i, [_P, C.POINTER(KnotParams), _P, _i, _i, _P, _P]),
+    "cadm_knot_plan": (_i, [_P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P,
+                            _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

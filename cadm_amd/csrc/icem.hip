@@ -8,7 +8,8 @@
 // The rollout, the context encoder, the truncated-normal sampler and the elite refit are the reference path's, called unchanged.
 // The loop takes its update and its candidate score as parameters: cadm_icem_plan runs it with the elite refit, cadm_mppi_plan with the
 // MPPI refit (mppi.hip), both on the particle mean; cadm_scored_plan chooses the update and the score (score.hip); cadm_constrained_plan
-// also rewrites the particle returns under state constraints (constrain.hip) before the score sees them.
+// also rewrites the particle returns under state constraints (constrain.hip) before the score sees them; cadm_knot_plan also shapes every
+// iteration's candidates onto a grid of knot steps (knots.hip) before the rollout sees them.
 #include <math.h>
 
 #include "planner.h"
@@ -343,10 +344,13 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 
 // score: what a candidate's particle returns become before the update sees them (score.hip); null = the particle mean
 // constraints: state constraints that rewrite the particle returns before the score (constrain.hip); null = none, and today's launches
+// knots: the grid every candidate is shaped onto before its rollout (knots.hip), phase [m] int32 on the device or null = 0; knots null or
+// spacing 1 = none, and today's launches.  With a grid, iteration 0's mean is the caller's shaped, in the workspace (init_mean is not written).
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
-                     float* best_return_out, void* stream, const cadm_constraint_params* constraints = nullptr) {
+                     float* best_return_out, void* stream, const cadm_constraint_params* constraints = nullptr,
+                     const cadm_knot_params* knots = nullptr, const int32_t* phase = nullptr) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -364,6 +368,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     if (upd.mppi && (rc = cadm_mppi_check(ctx, m, upd.temperature, who))) return rc;
     if ((rc = cadm_score_check(ctx, score, who))) return rc;
     if (constraints && (rc = cadm_constraint_check(ctx, constraints, who))) return rc;
+    if (knots && (rc = cadm_knot_check(knots, who))) return rc;
+    const bool shape = knots && knots->spacing > 1;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
@@ -375,10 +381,14 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         hipLaunchKernelGGL(icem_best_init_kernel, dim3(icem_grid((size_t)m * HA)), dim3(256), 0, s, m, HA, w.best_ret, w.best_seq);
         CADM_CHECK_HIP(hipGetLastError());
     }
+    if (shape) {      // iteration 0 samples around the caller's mean on the grid: a shaped copy (the refit runs with mean_in == mean_out anyway)
+        if ((rc = cadm_launch_clip(init_mean, w.mean, m * HA, 0.0f, 0.0f, 0, s))) return rc;
+        if ((rc = cadm_launch_shape_actions(ctx, knots, phase, m, 1, w.mean, s))) return rc;
+    }
     for (int it = 0; it < iters; ++it) {
         const bool first = it == 0, last = it + 1 == iters;
         const int ni = icem_n_it(n, (double)prm->decay, it, KE, K);
-        const float* mean_in = first ? init_mean : w.mean;
+        const float* mean_in = (first && !shape) ? init_mean : w.mean;
         const float* var_in = first ? init_var : w.var;
         // candidates [m, ni, H, A]: white truncated-normal noise (the reference path's sampler) or coloured noise
         if (prm->noise_beta > 0.0f) rc = cadm_sample_actions_colored(ctx, mean_in, var_in, nullptr, prm->noise_beta, seed, call, it, m, ni, w.actions, stream);
@@ -392,6 +402,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
             if ((rc = cadm_launch_clip(mean_in, w.meanclip, m * HA, ctx->cfg.lower_bound, ctx->cfg.upper_bound, 1, s))) return rc;
             if ((rc = launch_inject(ctx, w.meanclip, nullptr, m, ni, 1, 0, w.actions + (size_t)K * HA, s))) return rc;
         }
+        // every candidate onto the grid, the injected slots included: ni, the packed count of this iteration, not the workspace's n
+        if (shape && (rc = cadm_launch_shape_actions(ctx, knots, phase, m, ni, w.actions, s))) return rc;
         if ((rc = cadm_rollout_returns(ctx, obs, nullptr, ctx->C > 0 ? w.ctxv : nullptr, w.actions, nullptr, 1, seed, call, it, 0, ni, m, ni,
                                        w.rows, w.traj, stream))) return rc;
         // the trajectories are [H, m, ni, p, D] of this iteration's ni candidates; the returns are rewritten in place
@@ -458,4 +470,18 @@ extern "C" int cadm_constrained_plan(cadm_ctx* ctx, const cadm_constraint_params
     const PlanUpdate upd{"cadm_constrained_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream, constraints);
+}
+
+// and once more, with every candidate shaped onto a grid of knot steps (knots.hip) between the injections and the rollout; knots null or
+// spacing 1: cadm_constrained_plan's launches
+extern "C" int cadm_knot_plan(cadm_ctx* ctx, const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                              const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs, const float* cp_obs,
+                              const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io,
+                              int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out,
+                              void* stream) {
+    CADM_REQUIRE(prm, "cadm_knot_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_knot_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_knot_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints, knots, phase);
 }

@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -73,6 +73,10 @@ int cadm_score_check(const cadm_ctx* ctx, const cadm_score_params* score, const 
 // constrain.hip: the refusals of a constraint set (count, dims, bounds, mode, weight, a discrete / sharded ctx, a spec ctx without its spec in
 // terminate mode, a D whose tiles exceed the kernel's LDS), before any HIP call
 int cadm_constraint_check(const cadm_ctx* ctx, const cadm_constraint_params* c, const char* who);
+// knots.hip: the refusals of a knot grid (spacing < 1, an unknown interp), before any HIP call; and the in-place shaping of seqs [m, n, H, A]
+// onto the grid (phase [m] int32 on the device, or null = 0), n the PACKED candidate count of the buffer
+int cadm_knot_check(const cadm_knot_params* knots, const char* who);
+int cadm_launch_shape_actions(cadm_ctx* ctx, const cadm_knot_params* knots, const int32_t* phase, int m, int n, float* seqs, hipStream_t s);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

@@ -36,6 +36,11 @@ Differences a caller can see (all opt-in except the first):
     for every entry; "penalty" takes cem_constraint_weight off a particle's return per violating step, "terminate" ends its return at
     the first one (that step still pays) and takes the weight off once; `cem_constraints` alone takes the opt-in route, and a constraint
     that never binds leaves every plan as it is.  `constraint_check(obs, actions, ...)`: which particles of given plans violate, and when;
+  * `cem_knots=r`, `cem_knot_interp="hold" | "linear"`, `cem_knot_anchor="call" | "episode"`: plans on knots in that loop (INTEGRATION.md
+    "Plans on knots") -- every candidate is piecewise constant ("hold": action repeat r) or piecewise linear on knot steps r apart, so the
+    search runs over H / r decisions per action dim instead of H; "call" hangs the grid on every call's first step, "episode" keeps
+    the breakpoints fixed in episode time (the model advances a per-env phase by one per call, `reset_plan_carry` puts it back to 0);
+    `cem_knots` > 1 alone takes the opt-in route, the default 1 leaves everything as it is;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -207,6 +212,9 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_constraints=None,
                  cem_constraint_mode="penalty",
                  cem_constraint_weight=None,
+                 cem_knots=1,
+                 cem_knot_interp="hold",
+                 cem_knot_anchor="call",
                  engine_lib=None,
                  ):
         self.env = env
@@ -268,12 +276,14 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      cem_temperature, cem_temperature_relative, cem_score, cem_risk, use_cem=use_cem,
                                                      discrete=self.discrete, process_group=process_group, n_particles=n_particles,
                                                      cem_constraints=cem_constraints, cem_constraint_mode=cem_constraint_mode,
-                                                     cem_constraint_weight=cem_constraint_weight)
+                                                     cem_constraint_weight=cem_constraint_weight, cem_knots=cem_knots,
+                                                     cem_knot_interp=cem_knot_interp, cem_knot_anchor=cem_knot_anchor)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
                 raise ValueError("cem_constraints read observation dim %d, this env has %d" % (max(cp.dim[:cp.n]), obs_space_dims))
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
+        self._plan_phase = None                               # device tensor [m] int32: the knot grid's phase (cem_knot_anchor="episode")
 
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
@@ -448,13 +458,20 @@ class MLPEnsembleCEMDynamicsModel(object):
         if K > 0 and (self._plan_carry is None or self._plan_carry.shape[0] != m):      # first call, or another number of envs: nothing carried
             self._plan_carry = torch.zeros((m, K, self.n_forwards, self.action_space_dims), dtype=torch.float32, device=eng.device)
             self._plan_carry_valid = torch.zeros((m,), dtype=torch.int32, device=eng.device)
+        episode = self._opt.knots is not None and self._opt.knots[2] == "episode"
+        if episode and (self._plan_phase is None or self._plan_phase.shape[0] != m):      # likewise: the grid hangs on this call's first step
+            self._plan_phase = torch.zeros((m,), dtype=torch.int32, device=eng.device)
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
         if self.context_out_dim == 0:
             cp_obs = cp_act = None
-        return eng.opt_in_plan(self._opt, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
-                               carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=out)
+        plan = eng.opt_in_plan(self._opt, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
+                               carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=out,
+                               **(dict(phase=self._plan_phase) if episode else {}))
+        if episode:      # the horizon recedes by one step per call, the breakpoints stay where they are in episode time (torch ops on the
+            self._plan_phase.add_(1).remainder_(self._opt.knots[0])      # engine's stream, behind the plan: no host synchronisation)
+        return plan
 
     def _get_action_opt_in(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
         """The opt-in route of get_action: `_plan_opt_in` into the pinned host buffer."""
@@ -560,17 +577,20 @@ class MLPEnsembleCEMDynamicsModel(object):
 
     def reset_plan_carry(self, mask=None):
         """Forget the elites the iCEM planner carries from one get_action to the next (`cem_keep_elites` > 0): for every env, or for
-        those where `mask` [m] is set -- at an episode boundary, so that a new episode never starts from the previous one's plans.
-        A no-op for a model that carries nothing."""
-        if self._plan_carry_valid is None:
+        those where `mask` [m] is set -- at an episode boundary, so that a new episode never starts from the previous one's plans --
+        and put their knot grids back on the call's first step (`cem_knot_anchor="episode"`).  A no-op for a model that carries nothing."""
+        held = [t for t in (self._plan_carry_valid, getattr(self, "_plan_phase", None)) if t is not None]
+        if not held:
             return
         if mask is None:
-            self._plan_carry_valid.zero_()
+            for t in held:
+                t.zero_()
             return
         mk = self.engine._t(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.bool).reshape(-1)
-        if mk.shape[0] != self._plan_carry_valid.shape[0]:
-            raise ValueError("reset_plan_carry: mask has %d entries, the planner carries elites for %d envs" % (mk.shape[0], self._plan_carry_valid.shape[0]))
-        self._plan_carry_valid.masked_fill_(mk, 0)
+        if mk.shape[0] != held[0].shape[0]:
+            raise ValueError("reset_plan_carry: mask has %d entries, the planner carries elites for %d envs" % (mk.shape[0], held[0].shape[0]))
+        for t in held:
+            t.masked_fill_(mk, 0)
 
     def get_context_pred(self, cp_obs, cp_act):
         """reference :369-380 -> [E,m,C]."""

@@ -580,10 +580,12 @@ class HipEngine:
                            m, n, seed, call, ptr(ws), ptr(out), ptr(best), self.stream), "cadm_" + who)
         return (out, best) if want_best_return else out
 
-    def opt_in_plan(self, opt, *args, **kw):
-        """The opt-in loop under a `planner.PlanOptions`: `constrained_plan` when it holds constraints, `scored_plan` when it holds a score,
-        else `mppi_plan` or `icem_plan` by its update.
+    def opt_in_plan(self, opt, *args, phase=None, **kw):
+        """The opt-in loop under a `planner.PlanOptions`: `knot_plan` when it holds knots (phase: the envs' grid phases [m] int32, None = 0),
+        `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
         Arguments as `icem_plan` behind its params."""
+        if opt.knot_params is not None:
+            return self.knot_plan(opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params, *args, **kw)
         if opt.constraint_params is not None:
             return self.constrained_plan(opt.constraint_params, opt.score_params, opt.params, *args, **kw)
         if opt.score_params is not None:
@@ -660,16 +662,21 @@ class HipEngine:
         self._check(self.lib.cadm_particle_score(self._ctx, ptr(rows), m, n_local, ct.byref(prm), ptr(out), self.stream), "cadm_particle_score")
         return out
 
+    @staticmethod
+    def _as_mppi_params(params):
+        """(is it an MPPI loop, the `cadm_mppi_params` the scored / constrained / knot exports take): an `icem_params` result is wrapped."""
+        if isinstance(params, _lib.MppiParams):
+            return True, params
+        full = _lib.MppiParams()
+        full.icem, full.temperature = params, 1.0
+        return False, full
+
     def scored_plan(self, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
                     want_best_return=False):
         """`cadm_scored_plan`: the loop of `icem_plan` (params from `icem_params`) or of `mppi_plan` (params from `mppi_params`) with
         `score` (`score_params`; None = the mean) in place of the particle mean.  The best return is then the best score.  Arguments as
         `icem_plan`; the workspaces are the ones those two cache."""
-        mppi = isinstance(params, _lib.MppiParams)
-        if not mppi:
-            full = _lib.MppiParams()
-            full.icem, full.temperature = params, 1.0
-            params = full
+        mppi, params = self._as_mppi_params(params)
         head = (None if score is None else ct.byref(score), int(mppi), ct.byref(params))
         return self._loop_plan("scored_plan", self.lib.cadm_scored_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
@@ -751,13 +758,58 @@ class HipEngine:
         """`cadm_constrained_plan`: the loop of `scored_plan` with `constraints` (`constraint_params`; None = none, and `scored_plan`'s
         launches) rewriting every iteration's particle returns before the score.  Arguments behind `constraints` as `scored_plan`; with
         constraints the workspace carries the trajectory view (`cadm_constrained_workspace_bytes`), cached apart from the plain ones."""
-        mppi = isinstance(params, _lib.MppiParams)
-        if not mppi:
-            full = _lib.MppiParams()
-            full.icem, full.temperature = params, 1.0
-            params = full
+        mppi, params = self._as_mppi_params(params)
         head = (None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi), ct.byref(params))
         return self._loop_plan("constrained_plan", self.lib.cadm_constrained_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None)
+
+    # ------------------------------------------------------------------ plans on knots (opt-in; csrc/knots.hip)
+    @staticmethod
+    def knot_params(spacing, interp="hold"):
+        """`cadm_knot_params`: knot steps `spacing` >= 1 apart (1: every step is a knot); interp: "hold" | "linear" (or its CADM_KNOT_*
+        number) -- action repeat, or linear interpolation between knots."""
+        if isinstance(spacing, bool) or not isinstance(spacing, (int, np.integer)) or int(spacing) < 1:
+            raise ValueError("knot spacing must be an integer >= 1, got %r" % (spacing,))
+        if isinstance(interp, str):
+            if interp not in _lib.KNOT_INTERPS:
+                raise ValueError("knot interp must be 'hold' or 'linear', got %r" % (interp,))
+            interp = _lib.KNOT_INTERPS[interp]
+        elif int(interp) not in _lib.KNOT_INTERPS.values():
+            raise ValueError("knot interp must be 'hold' or 'linear', got %r" % (interp,))
+        prm = _lib.KnotParams()
+        prm.spacing, prm.interp = int(spacing), int(interp)
+        return prm
+
+    def _phase(self, phase, m, who):
+        """phase [m] int32 on the device (None stays None: phase 0 for every env)"""
+        if phase is None:
+            return None
+        phase = self._t(phase, dtype=torch.int32)
+        if tuple(phase.shape) != (m,) or not phase.is_contiguous():
+            raise ValueError("%s: phase %r, expected [%d] int32" % (who, tuple(phase.shape), m))
+        return phase
+
+    def shape_actions(self, seqs, knots, phase=None):
+        """`cadm_shape_actions`: seqs [m,n,H,A] or [m,H,A] (a contiguous float32 device tensor) shaped onto the grid of `knots`
+        (`knot_params`) IN PLACE; phase [m] int32 (None: 0 for every env).  Returns seqs."""
+        if not isinstance(seqs, torch.Tensor) or seqs.dtype != torch.float32 or not seqs.is_contiguous() or seqs.dim() not in (3, 4) \
+                or tuple(seqs.shape[-2:]) != (self.H, self.A) or seqs.shape[0] == 0 or not seqs.is_cuda:
+            raise ValueError("shape_actions: expected a contiguous float32 device tensor [m,n,%d,%d] or [m,%d,%d]" % (self.H, self.A, self.H, self.A))
+        m, n = seqs.shape[0], seqs.shape[1] if seqs.dim() == 4 else 1
+        phase = self._phase(phase, m, "shape_actions")
+        self._check(self.lib.cadm_shape_actions(self._ctx, ct.byref(knots), ptr(phase), m, n, ptr(seqs), self.stream), "cadm_shape_actions")
+        return seqs
+
+    def knot_plan(self, knots, phase, constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None,
+                  seed=0, call=0, out=None, want_best_return=False):
+        """`cadm_knot_plan`: the loop of `constrained_plan` with every iteration's candidates shaped onto the grid of `knots`
+        (`knot_params`; None = none, and `constrained_plan`'s launches) before the rollout; phase [m] int32 (None: 0 for every env).
+        Arguments behind `phase` as `constrained_plan`, and its workspaces."""
+        mppi, params = self._as_mppi_params(params)
+        phase = self._phase(phase, int(np.shape(obs)[0]), "knot_plan")
+        head = (None if knots is None else ct.byref(knots), ptr(phase), None if constraints is None else ct.byref(constraints),
+                None if score is None else ct.byref(score), int(mppi), ct.byref(params))
+        return self._loop_plan("knot_plan", self.lib.cadm_knot_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None)
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon

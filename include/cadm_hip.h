@@ -435,6 +435,45 @@ int cadm_constrained_plan(cadm_ctx* ctx, const cadm_constraint_params* constrain
                           const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                           uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
 
+/* Plans on knots (no reference twin, OPT-IN): the opt-in loop searches over fewer decisions than the horizon has steps -- action repeat
+ * (HOLD) or linear interpolation (LINEAR) between knot steps `spacing` = r >= 1 apart.  Per env a phase phi, taken modulo r with a
+ * non-negative result (a negative or >= r phase is legal), moves the grid; H is the ctx's horizon.
+ *   step t belongs to segment j = (t + phi) div r;  the segment's knot step is k_j = max(0, j r - phi);  the next knot is
+ *   k_{j+1} = (j+1) r - phi.  The knot steps are k_0 = 0 < k_1 < ..., J = (H - 1 + phi) div r + 1 of them, all inside [0, H).
+ *   H = 7, r = 3: phi = 0 -> {0, 3, 6}; phi = 1 -> {0, 2, 5}; phi = 2 -> {0, 1, 4}.   H = 5, r = 8, phi = 5 -> {0, 3}.
+ * Shaping a sequence a[0 .. H), per action dim:
+ *   a knot step keeps its bits;
+ *   any other step t under CADM_KNOT_HOLD takes a[k_j] (a copy: the same bits);
+ *   any other step t under CADM_KNOT_LINEAR with k_{j+1} <= H - 1 takes fmaf(w, a[k_{j+1}] - a[k_j], a[k_j]),
+ *       w = (float)(t - k_j) / (float)(k_{j+1} - k_j) in fp32 (one rounded difference, one rounded quotient, one fused multiply-add);
+ *   any other step t under CADM_KNOT_LINEAR in a last segment without a next knot inside the horizon holds a[k_j].
+ * Shaping is idempotent; shaped values of a sequence inside [lb, ub] stay inside [lb, ub]; r = 1 is the identity (nothing is enqueued);
+ * a HOLD-shaped sequence moved one step on (cadm_icem_inject, shift = 1) lies on the grid of phase phi + 1 -- carried elites and a
+ * phase that advances by one per call fit together.  Reads come from knot steps only, writes go to the other steps only.
+ * cadm_shape_actions: seqs_io [m,n,H,A] shaped IN PLACE, n the packed candidate count of the buffer (n = 1: means [m,1,H,A]); phase [m]
+ * int32 on the device, or NULL = 0 for every env.  One thread per element, no atomics, no workspace.
+ * CADM_EINVAL (before any HIP call) for spacing < 1, an unknown interp.  spacing >= H is legal: one knot (a constant plan), or two with
+ * a non-zero phase. */
+#define CADM_KNOT_HOLD 0
+#define CADM_KNOT_LINEAR 1
+typedef struct cadm_knot_params {
+    int32_t spacing;        /* r >= 1: knot steps are r apart; 1: every step is a knot */
+    int32_t interp;         /* CADM_KNOT_* */
+} cadm_knot_params;
+int cadm_shape_actions(cadm_ctx* ctx, const cadm_knot_params* knots, const int32_t* phase, int m, int n, float* seqs_io, void* stream);
+/* The loop of cadm_constrained_plan on a grid of knots.  Before iteration 0, init_mean is copied into the workspace and shaped (n = 1):
+ * that copy is iteration 0's mean; the caller's init_mean is not written, init_var is used as it is.  In every iteration, behind the
+ * sampler, the kept-elite injection and the add_mean_last injection and before the rollout, the iteration's n_it candidates are shaped
+ * in place: the rollout, the constraints, the score, either refit, the tracked best, the kept elites and the carry written after the
+ * last refit see sequences on the grid, and their per-step statistics at the knot steps are those of a CEM run in knot space.  The draws
+ * are those of the loop without knots.  knots NULL or spacing == 1: exactly the launches of cadm_constrained_plan.  Refusals: those of
+ * cadm_constrained_plan and of cadm_shape_actions.  workspace: that of the loop underneath -- cadm_constrained_workspace_bytes with
+ * constraints, else cadm_icem_workspace_bytes (update 0) / cadm_mppi_workspace_bytes (update 1). */
+int cadm_knot_plan(cadm_ctx* ctx, const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                   const cadm_score_params* score, int update, const cadm_mppi_params* params, const float* obs, const float* cp_obs,
+                   const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m,
+                   int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
+
 /* One training step = sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
