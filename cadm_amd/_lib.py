@@ -94,6 +94,15 @@ class KnotParams(C.Structure):          # include/cadm_hip.h cadm_knot_params
     _fields_ = [("spacing", C.c_int32), ("interp", C.c_int32)]
 
 
+MAX_TRACK_TERMS = 16                                                       # CADM_MAX_TRACK_TERMS
+TRACK_KINDS = {"square": 0, "abs": 1, "huber": 2}                          # CADM_TRACK_*
+
+
+class TrackParams(C.Structure):         # include/cadm_hip.h cadm_track_params
+    _fields_ = [("n", C.c_int32), ("dim", C.c_int32 * MAX_TRACK_TERMS), ("kind", C.c_int32 * MAX_TRACK_TERMS),
+                ("w", C.c_float * MAX_TRACK_TERMS), ("delta", C.c_float * MAX_TRACK_TERMS)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -151,6 +160,10 @@ SIGNATURES = {
     "cadm_shape_actions": (_i, [_P, C.POINTER(KnotParams), _P, _i, _i, _P, _P]),
     "cadm_knot_plan": (_i, [_P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P,
                             _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_tracking_returns": (_i, [_P, C.POINTER(TrackParams), _P, _P, _i, _P, _P, _P, _i, _i, _P, _P, _P]),
+    "cadm_tracking_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i]),
+    "cadm_tracking_plan": (_i, [_P, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams),
+                                C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

@@ -9,7 +9,8 @@
 // The loop takes its update and its candidate score as parameters: cadm_icem_plan runs it with the elite refit, cadm_mppi_plan with the
 // MPPI refit (mppi.hip), both on the particle mean; cadm_scored_plan chooses the update and the score (score.hip); cadm_constrained_plan
 // also rewrites the particle returns under state constraints (constrain.hip) before the score sees them; cadm_knot_plan also shapes every
-// iteration's candidates onto a grid of knot steps (knots.hip) before the rollout sees them.
+// iteration's candidates onto a grid of knot steps (knots.hip) before the rollout sees them; cadm_tracking_plan also takes the cost of
+// run-time tracking targets (tracking.hip) off the particle returns, behind the constraints and before the score.
 #include <math.h>
 
 #include "planner.h"
@@ -290,10 +291,11 @@ struct IcemWs {
     float *ctxv, *actions, *rows, *cand, *mean, *var, *meanclip, *kept, *best_ret, *best_seq;
     int32_t* elites;
     float *emean, *evar, *mppi;      // MPPI only: where the elite selection's own refit goes (discarded), the update's weights and partials
-    float* traj;                     // constrained only: the rollout's trajectories [H, m, n, p, D], the LAST view (the sums before it stay)
+    int32_t* first;                  // tracked under TERMINATE constraints only: the constraint kernel's first_violation [m, n, p], in front of traj
+    float* traj;                     // constrained or tracked only: the rollout's trajectories [H, m, n, p, D], the LAST view (the sums before it stay)
 };
 
-static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0) {
+static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0, int first = 0) {
     Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
     IcemWs t{};
@@ -313,6 +315,7 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
         t.evar = c.take<float>((size_t)m * HA);
         t.mppi = c.take<float>(cadm_mppi_scratch_floats(ctx, m, n));
     }
+    if (first) t.first = c.take<int32_t>((size_t)m * n * ctx->p);
     if (traj) t.traj = c.take<float>((size_t)ctx->H * m * n * ctx->p * ctx->D);
     if (w) *w = t;
     return c.off;
@@ -333,6 +336,11 @@ extern "C" size_t cadm_constrained_workspace_bytes(cadm_ctx* ctx, int m, int n, 
     return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1);
 }
 
+extern "C" size_t cadm_tracking_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0);
+}
+
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
 static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     double v = floor((double)n / pow(decay, (double)it));
@@ -346,11 +354,15 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 // constraints: state constraints that rewrite the particle returns before the score (constrain.hip); null = none, and today's launches
 // knots: the grid every candidate is shaped onto before its rollout (knots.hip), phase [m] int32 on the device or null = 0; knots null or
 // spacing 1 = none, and today's launches.  With a grid, iteration 0's mean is the caller's shaped, in the workspace (init_mean is not written).
+// terms: tracking terms whose cost against targets [m, T, K] (offset [m] int32 on the device or null = 0) comes off the particle returns
+// behind the constraints and before the score (tracking.hip); null = none, and today's launches.  With terms every rollout records its
+// trajectories, and TERMINATE constraints hand their first violations on: what a terminated trajectory holds behind them is not tracked.
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                      float* best_return_out, void* stream, const cadm_constraint_params* constraints = nullptr,
-                     const cadm_knot_params* knots = nullptr, const int32_t* phase = nullptr) {
+                     const cadm_knot_params* knots = nullptr, const int32_t* phase = nullptr, const cadm_track_params* terms = nullptr,
+                     const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -369,11 +381,14 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     if ((rc = cadm_score_check(ctx, score, who))) return rc;
     if (constraints && (rc = cadm_constraint_check(ctx, constraints, who))) return rc;
     if (knots && (rc = cadm_knot_check(knots, who))) return rc;
+    if (terms && (rc = cadm_track_check(ctx, terms, targets, T, who))) return rc;
     const bool shape = knots && knots->spacing > 1;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr);      // (w.traj: null without constraints)
+    // (w.traj: null without constraints and terms; w.first: null unless terms follow TERMINATE constraints)
+    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || terms != nullptr,
+               terms != nullptr && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE);
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
@@ -407,8 +422,9 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if ((rc = cadm_rollout_returns(ctx, obs, nullptr, ctx->C > 0 ? w.ctxv : nullptr, w.actions, nullptr, 1, seed, call, it, 0, ni, m, ni,
                                        w.rows, w.traj, stream))) return rc;
         // the trajectories are [H, m, ni, p, D] of this iteration's ni candidates; the returns are rewritten in place
-        if (constraints && (rc = cadm_constrain_returns(ctx, constraints, w.traj, obs, w.actions, w.rows, m, ni, w.rows, nullptr, nullptr,
+        if (constraints && (rc = cadm_constrain_returns(ctx, constraints, w.traj, obs, w.actions, w.rows, m, ni, w.rows, w.first, nullptr,
                                                         stream))) return rc;
+        if (terms && (rc = cadm_tracking_returns(ctx, terms, w.traj, targets, T, offset, w.first, w.rows, m, ni, w.rows, nullptr, stream))) return rc;
         if ((rc = cadm_particle_score(ctx, w.rows, m, ni, score, w.cand, stream))) return rc;      // (the mean: cadm_particle_mean itself)
         float* plan = (last && !prm->return_best) ? plan_out : nullptr;      // the refitted mean, clipped (dynamics.py:365-366)
         if (!upd.mppi) {
@@ -484,4 +500,19 @@ extern "C" int cadm_knot_plan(cadm_ctx* ctx, const cadm_knot_params* knots, cons
     const PlanUpdate upd{"cadm_knot_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream, constraints, knots, phase);
+}
+
+// the outermost of the nest: with the cost of run-time tracking targets (tracking.hip) taken off the particle returns between the
+// constraints and the score; track null: cadm_knot_plan's launches
+extern "C" int cadm_tracking_plan(cadm_ctx* ctx, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                                  const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                                  const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs,
+                                  const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                                  int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                                  float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_tracking_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_tracking_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_tracking_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset);
 }

@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -77,6 +77,9 @@ int cadm_constraint_check(const cadm_ctx* ctx, const cadm_constraint_params* c, 
 // onto the grid (phase [m] int32 on the device, or null = 0), n the PACKED candidate count of the buffer
 int cadm_knot_check(const cadm_knot_params* knots, const char* who);
 int cadm_launch_shape_actions(cadm_ctx* ctx, const cadm_knot_params* knots, const int32_t* phase, int m, int n, float* seqs, hipStream_t s);
+// tracking.hip: the refusals of a set of tracking terms and its targets (count, dims, kinds, weights, Huber deltas, T < 1, null targets, a
+// discrete / sharded ctx, a D whose tile exceeds the kernel's LDS), before any HIP call
+int cadm_track_check(const cadm_ctx* ctx, const cadm_track_params* track, const float* targets, int T, const char* who);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

@@ -41,6 +41,12 @@ Differences a caller can see (all opt-in except the first):
     search runs over H / r decisions per action dim instead of H; "call" hangs the grid on every call's first step, "episode" keeps
     the breakpoints fixed in episode time (the model advances a per-env phase by one per call, `reset_plan_carry` puts it back to 0);
     `cem_knots` > 1 alone takes the opt-in route, the default 1 leaves everything as it is;
+  * `cem_tracking=[dict(dim=d, kind="square" | "abs" | "huber", w=..., delta=...), ...]`, `cem_target_advance`: targets set at run time in
+    that loop (INTEGRATION.md "Tracking targets at run time") -- `set_targets(targets, offset=None)` gives every env a goal [m,K] or a
+    reference [m,T,K] for the K terms, and every candidate's particle returns lose sum_t sum_k w_k c(x_t[d_k] - target) before they are
+    scored; NaN in the targets: no target there; the model moves every env's place in its reference on by one per planned call
+    (`cem_target_advance=False`: the caller does), `reset_plan_carry` puts it back to 0; `clear_targets()`; `tracking_cost(obs, actions,
+    ...)`: what the terms cost given plans.  `cem_tracking` alone takes the opt-in route; targets that are all NaN change no plan;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -215,6 +221,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_knots=1,
                  cem_knot_interp="hold",
                  cem_knot_anchor="call",
+                 cem_tracking=None,
+                 cem_target_advance=True,
                  engine_lib=None,
                  ):
         self.env = env
@@ -277,13 +285,19 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      discrete=self.discrete, process_group=process_group, n_particles=n_particles,
                                                      cem_constraints=cem_constraints, cem_constraint_mode=cem_constraint_mode,
                                                      cem_constraint_weight=cem_constraint_weight, cem_knots=cem_knots,
-                                                     cem_knot_interp=cem_knot_interp, cem_knot_anchor=cem_knot_anchor)
+                                                     cem_knot_interp=cem_knot_interp, cem_knot_anchor=cem_knot_anchor,
+                                                     cem_tracking=cem_tracking, cem_target_advance=cem_target_advance)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
                 raise ValueError("cem_constraints read observation dim %d, this env has %d" % (max(cp.dim[:cp.n]), obs_space_dims))
+        if self._opt is not None and self._opt.track_params is not None:
+            tp = self._opt.track_params
+            if max(tp.dim[:tp.n]) >= obs_space_dims:
+                raise ValueError("cem_tracking reads observation dim %d, this env has %d" % (max(tp.dim[:tp.n]), obs_space_dims))
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
         self._plan_phase = None                               # device tensor [m] int32: the knot grid's phase (cem_knot_anchor="episode")
+        self._targets = self._target_offset = None            # device tensors [m,T,K] float32 / [m] int32 (cem_tracking): `set_targets`
 
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
@@ -461,17 +475,83 @@ class MLPEnsembleCEMDynamicsModel(object):
         episode = self._opt.knots is not None and self._opt.knots[2] == "episode"
         if episode and (self._plan_phase is None or self._plan_phase.shape[0] != m):      # likewise: the grid hangs on this call's first step
             self._plan_phase = torch.zeros((m,), dtype=torch.int32, device=eng.device)
+        extra = dict(phase=self._plan_phase) if episode else {}
+        tracked = self._opt.track_params is not None
+        if tracked:
+            if self._targets is None:
+                raise RuntimeError("get_action: this model plans under cem_tracking and has no targets (call set_targets first)")
+            if self._targets.shape[0] != m or self._targets.shape[2] != self._opt.track_params.n:
+                raise ValueError("get_action: the targets are %r, this call has %d envs and cem_tracking %d terms: expected [%d,T,%d]"
+                                 % (tuple(self._targets.shape), m, self._opt.track_params.n, m, self._opt.track_params.n))
+            extra.update(targets=self._targets, target_offset=self._target_offset)
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
         if self.context_out_dim == 0:
             cp_obs = cp_act = None
         plan = eng.opt_in_plan(self._opt, obs, cp_obs, cp_act, cem_init_mean, cem_init_var, self.n_candidates, carry=self._plan_carry,
-                               carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=out,
-                               **(dict(phase=self._plan_phase) if episode else {}))
+                               carry_valid=self._plan_carry_valid, seed=self.seed, call=call, out=out, **extra)
         if episode:      # the horizon recedes by one step per call, the breakpoints stay where they are in episode time (torch ops on the
             self._plan_phase.add_(1).remainder_(self._opt.knots[0])      # engine's stream, behind the plan: no host synchronisation)
+        if tracked and self._opt.target_advance:      # likewise: the next call's step 0 is this call's step 1 of the reference
+            self._target_offset.add_(1)
         return plan
+
+    # ------------------------------------------------------------------ tracking targets (INTEGRATION.md "Tracking targets at run time")
+    def set_targets(self, targets, offset=None):
+        """The targets `cem_tracking`'s terms are held against from the next get_action on: [m,K] (a constant goal per env) or [m,T,K] (a
+        reference of T rows per env; K: the number of terms, in their order), numpy or tensor, kept on the device.  NaN: no target for
+        that term at that row.  Step t of a plan is compared with row clamp(offset + t, 0, T - 1) of its env; offset [m] ints (None:
+        zeros) -- with `cem_target_advance=True` the model moves every env's on by one per planned call, `reset_plan_carry(mask)` puts
+        the masked envs' back to 0."""
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.track_params is None:
+            raise ValueError("set_targets: this model has no cem_tracking")
+        K = opt.track_params.n
+        shp = tuple(int(v) for v in np.shape(targets))
+        if len(shp) not in (2, 3) or shp[0] < 1 or shp[-1] != K or (len(shp) == 3 and shp[1] < 1):
+            raise ValueError("set_targets: targets %r, expected [m,%d] or [m,T,%d] with m, T >= 1 (one column per cem_tracking term)" % (shp, K, K))
+        if offset is not None and tuple(int(v) for v in np.shape(offset)) != (shp[0],):
+            raise ValueError("set_targets: offset %r, expected [%d]" % (tuple(np.shape(offset)), shp[0]))
+        eng = self.engine
+        t = eng._t(targets)
+        self._targets = (t[:, None] if t.dim() == 2 else t).contiguous().clone()      # (the model's own copy: a later edit of the caller's tensor changes no plan)
+        if offset is None:
+            self._target_offset = torch.zeros((shp[0],), dtype=torch.int32, device=eng.device)
+        else:
+            self._target_offset = eng._t(offset, dtype=torch.int32).clone()
+
+    def clear_targets(self):
+        """Forget the targets and their offsets: get_action on a model with `cem_tracking` then raises until `set_targets` is called."""
+        self._targets = self._target_offset = None
+
+    def tracking_cost(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
+        """What this model's `cem_tracking` terms cost `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) against the current targets and
+        offsets -- the companion of `constraint_check`: the context encoder, one rollout that records its trajectories and the tracking
+        kernel, as numpy arrays (for [m,H,A] input the n axis is dropped):
+          cost [m,n,p]               the tracking cost per particle
+          returns [m,n,p]            the tracked particle returns (returns_untracked - cost), as the planner scores them without constraints
+          returns_untracked [m,n,p]  the rollout's own returns: what `w` has to be weighed against
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; the planner's
+        call counter and the offsets do not move."""
+        if self._opt is None or self._opt.track_params is None:
+            raise ValueError("tracking_cost: this model has no cem_tracking")
+        if self._targets is None:
+            raise RuntimeError("tracking_cost: this model has no targets (call set_targets first)")
+        self._push_stats()
+        cp_obs, cp_act = self._rollout_inputs("tracking_cost", obs, actions, cp_obs, cp_act)
+        eng = self.engine
+        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        acts = (acts[:, None] if squeeze else acts).contiguous()
+        raw, traj = eng.rollout_returns(eng._t(obs), ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                        call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        rows, cost = eng.tracking_returns(traj, raw, self._opt.track_params, self._targets, offset=self._target_offset, want_cost=True)
+        res = dict(cost=cost.cpu().numpy(), returns=rows.cpu().numpy(), returns_untracked=raw.cpu().numpy())
+        if squeeze:
+            res = {k: v[:, 0] for k, v in res.items()}
+        return res
 
     def _get_action_opt_in(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
         """The opt-in route of get_action: `_plan_opt_in` into the pinned host buffer."""
@@ -578,8 +658,9 @@ class MLPEnsembleCEMDynamicsModel(object):
     def reset_plan_carry(self, mask=None):
         """Forget the elites the iCEM planner carries from one get_action to the next (`cem_keep_elites` > 0): for every env, or for
         those where `mask` [m] is set -- at an episode boundary, so that a new episode never starts from the previous one's plans --
-        and put their knot grids back on the call's first step (`cem_knot_anchor="episode"`).  A no-op for a model that carries nothing."""
-        held = [t for t in (self._plan_carry_valid, getattr(self, "_plan_phase", None)) if t is not None]
+        and put their knot grids back on the call's first step (`cem_knot_anchor="episode"`) and their tracking references back on row 0
+        (`cem_tracking`: the target offsets; the targets themselves stay).  A no-op for a model that carries nothing."""
+        held = [t for t in (self._plan_carry_valid, getattr(self, "_plan_phase", None), getattr(self, "_target_offset", None)) if t is not None]
         if not held:
             return
         if mask is None:
@@ -587,8 +668,9 @@ class MLPEnsembleCEMDynamicsModel(object):
                 t.zero_()
             return
         mk = self.engine._t(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.bool).reshape(-1)
-        if mk.shape[0] != held[0].shape[0]:
-            raise ValueError("reset_plan_carry: mask has %d entries, the planner carries elites for %d envs" % (mk.shape[0], held[0].shape[0]))
+        for t in held:
+            if mk.shape[0] != t.shape[0]:
+                raise ValueError("reset_plan_carry: mask has %d entries, the planner carries elites for %d envs" % (mk.shape[0], t.shape[0]))
         for t in held:
             t.masked_fill_(mk, 0)
 

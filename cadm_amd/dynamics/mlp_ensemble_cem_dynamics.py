@@ -45,6 +45,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """Which particles of `actions` violate this model's `cem_constraints`, and when (see the CaDM class; a vanilla model has no history)."""
         return super().constraint_check(obs, actions, None, None, seed=seed)
 
+    def tracking_cost(self, obs, actions, seed=None):
+        """What this model's `cem_tracking` terms cost `actions` against the current targets (see the CaDM class; a vanilla model has no history)."""
+        return super().tracking_cost(obs, actions, None, None, seed=seed)
+
     def predict(self, obs, act, return_std=False):
         return super().predict(obs, act, None, None, return_std=return_std)
 

@@ -560,10 +560,10 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return, traj=False):
+                   want_best_return, traj=False, track=None):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
         `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
-        workspace with the trajectory view behind it (a constrained loop)."""
+        workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop)."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -572,7 +572,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K, traj=traj)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -580,10 +580,14 @@ class HipEngine:
                            m, n, seed, call, ptr(ws), ptr(out), ptr(best), self.stream), "cadm_" + who)
         return (out, best) if want_best_return else out
 
-    def opt_in_plan(self, opt, *args, phase=None, **kw):
-        """The opt-in loop under a `planner.PlanOptions`: `knot_plan` when it holds knots (phase: the envs' grid phases [m] int32, None = 0),
+    def opt_in_plan(self, opt, *args, phase=None, targets=None, target_offset=None, **kw):
+        """The opt-in loop under a `planner.PlanOptions`: `tracking_plan` when it holds tracking terms (targets [m,T,K] or [m,K],
+        target_offset [m] int32 or None = 0), `knot_plan` when it holds knots (phase: the envs' grid phases [m] int32, None = 0),
         `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
         Arguments as `icem_plan` behind its params."""
+        if opt.track_params is not None:
+            return self.tracking_plan(opt.track_params, targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params,
+                                      opt.params, *args, **kw)
         if opt.knot_params is not None:
             return self.knot_plan(opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params, *args, **kw)
         if opt.constraint_params is not None:
@@ -592,13 +596,17 @@ class HipEngine:
             return self.scored_plan(opt.score_params, opt.params, *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
-    def _loop_workspace(self, mppi, m, n, K, traj=False):
+    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
-        constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that)."""
-        slot = (bool(mppi), bool(traj))
+        constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that).  track: None,
+        or whether a tracked loop runs under TERMINATE constraints -- the tracking slot (`cadm_tracking_workspace_bytes`: the trajectory
+        view, and the first-violation view in front of it under TERMINATE)."""
+        slot = (bool(mppi), bool(traj)) if track is None else (bool(mppi), "track", bool(track))
         key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            if traj:
+            if track is not None:
+                nbytes = self.lib.cadm_tracking_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(track)))
+            elif traj:
                 nbytes = self.lib.cadm_constrained_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)))
             else:
                 nbytes = (self.lib.cadm_mppi_workspace_bytes if mppi else self.lib.cadm_icem_workspace_bytes)(self._ctx, m, n, K)
@@ -811,6 +819,111 @@ class HipEngine:
                 None if score is None else ct.byref(score), int(mppi), ct.byref(params))
         return self._loop_plan("knot_plan", self.lib.cadm_knot_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None)
+
+    # ------------------------------------------------------------------ tracking targets at run time (opt-in; csrc/tracking.hip)
+    @staticmethod
+    def track_params(terms):
+        """`cadm_track_params` from a list of dict(dim=d, kind="square" | "abs" | "huber", w=..., delta=...): term k costs w * c(x[d] - target k),
+        c = e^2, |e|, or the Huber function with threshold delta (kind: a name or its CADM_TRACK_* number; default "square"; w: finite,
+        >= 0, default 1; delta: finite, > 0, for "huber" only and required there).  Everything that needs no engine is checked here; a dim
+        beyond the engine's D is refused by the library."""
+        if isinstance(terms, dict):
+            terms = [terms]
+        try:
+            terms = list(terms)
+        except TypeError:
+            raise ValueError("tracking terms must be a list of dict(dim=, kind=, w=, delta=), got %r" % (terms,)) from None
+        if not 1 <= len(terms) <= _lib.MAX_TRACK_TERMS:
+            raise ValueError("tracking: %d terms, expected 1 .. %d" % (len(terms), _lib.MAX_TRACK_TERMS))
+        prm = _lib.TrackParams()
+        prm.n = len(terms)
+        for k, c in enumerate(terms):
+            if not isinstance(c, dict) or "dim" not in c or set(c) - {"dim", "kind", "w", "delta"}:
+                raise ValueError("tracking term %d: expected dict(dim=, kind=, w=, delta=), got %r" % (k, c))
+            if isinstance(c["dim"], bool) or not isinstance(c["dim"], (int, np.integer)) or int(c["dim"]) < 0:
+                raise ValueError("tracking term %d: dim must be an observation index >= 0, got %r" % (k, c["dim"]))
+            kind = c.get("kind", "square")
+            if isinstance(kind, str):
+                if kind not in _lib.TRACK_KINDS:
+                    raise ValueError("tracking term %d: kind must be 'square', 'abs' or 'huber', got %r" % (k, kind))
+                kind = _lib.TRACK_KINDS[kind]
+            elif isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or int(kind) not in _lib.TRACK_KINDS.values():
+                raise ValueError("tracking term %d: kind must be 'square', 'abs' or 'huber', got %r" % (k, kind))
+            w = float(np.float32(c.get("w", 1.0)))      # (the weight as the kernel multiplies by it)
+            if not math.isfinite(w) or w < 0.0:
+                raise ValueError("tracking term %d: w must be finite and >= 0, got %r" % (k, c.get("w")))
+            delta = c.get("delta")
+            if int(kind) == _lib.TRACK_KINDS["huber"]:
+                if delta is None or not math.isfinite(float(np.float32(delta))) or float(np.float32(delta)) <= 0.0:
+                    raise ValueError("tracking term %d: kind 'huber' needs a delta that is finite and > 0, got %r" % (k, delta))
+            elif delta is not None:
+                raise ValueError("tracking term %d: delta configures kind 'huber' only" % k)
+            prm.dim[k], prm.kind[k], prm.w[k], prm.delta[k] = int(c["dim"]), int(kind), w, 0.0 if delta is None else float(np.float32(delta))
+        return prm
+
+    def _targets(self, targets, offset, m, K, who):
+        """(targets [m,T,K] float32 contiguous on the device -- [m,K] is T = 1 --, T, offset [m] int32 on the device or None)"""
+        if targets is None:
+            raise ValueError("%s: tracking terms need targets" % who)
+        targets = self._t(targets)
+        if targets.dim() == 2:
+            targets = targets[:, None]
+        if targets.dim() != 3 or targets.shape[0] != m or targets.shape[1] < 1 or targets.shape[2] != K:
+            raise ValueError("%s: targets %r, expected [%d,T,%d] with T >= 1 or [%d,%d]" % (who, tuple(targets.shape), m, K, m, K))
+        targets = targets.contiguous()
+        if offset is not None:
+            offset = self._t(offset, dtype=torch.int32)
+            if tuple(offset.shape) != (m,) or not offset.is_contiguous():
+                raise ValueError("%s: offset %r, expected [%d] int32" % (who, tuple(offset.shape), m))
+        return targets, int(targets.shape[1]), offset
+
+    def tracking_returns(self, traj, rows, track, targets, offset=None, first=None, out=None, want_cost=False):
+        """`cadm_tracking_returns` on device tensors: traj [H,m,n,p,D] (a rollout's `traj_out`), rows [m,n,p] (its returns, or what
+        `constrain_returns` made of them) -> rows' [m,n,p] = rows - cost (with want_cost: (rows', cost [m,n,p])).  track: a `track_params`
+        result, or the list it takes.  targets [m,T,K] or [m,K]; offset [m] int32 (None: 0); first [m,n,p] int32 (None: every step
+        counts): `constrain_returns`' first_violation -- steps behind it are not counted.  out: where rows' go (may be `rows` itself)."""
+        prm = track if isinstance(track, _lib.TrackParams) else self.track_params(track)
+        traj, rows = self._t(traj), self._t(rows)
+        if traj.dim() != 5 or rows.dim() != 3 or not traj.is_contiguous() or not rows.is_contiguous():
+            raise ValueError("tracking_returns: traj %r, rows %r: expected contiguous [H,m,n,p,D] and [m,n,p]" % (tuple(traj.shape), tuple(rows.shape)))
+        H, m, n, p, D = traj.shape
+        if (H, p, D) != (self.H, self.p, self.D) or tuple(rows.shape) != (m, n, p):
+            raise ValueError("tracking_returns: traj %r, rows %r do not agree with the engine (H=%d, p=%d, D=%d)"
+                             % (tuple(traj.shape), tuple(rows.shape), self.H, self.p, self.D))
+        targets, T, offset = self._targets(targets, offset, m, prm.n, "tracking_returns")
+        if first is not None:
+            first = self._t(first, dtype=torch.int32)
+            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
+                raise ValueError("tracking_returns: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
+        if out is None:
+            out = torch.empty_like(rows)
+        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("tracking_returns: out %r, expected contiguous float32 %r" % (tuple(out.shape), (m, n, p)))
+        cost = torch.empty((m, n, p), dtype=torch.float32, device=self.device) if want_cost else None
+        self._check(self.lib.cadm_tracking_returns(self._ctx, ct.byref(prm), ptr(traj), ptr(targets), T, ptr(offset), ptr(first), ptr(rows), m, n,
+                                                   ptr(out), ptr(cost), self.stream), "cadm_tracking_returns")
+        return (out, cost) if want_cost else out
+
+    def tracking_plan(self, track, targets, offset, knots, phase, constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n,
+                      carry=None, carry_valid=None, seed=0, call=0, out=None, want_best_return=False):
+        """`cadm_tracking_plan`: the loop of `knot_plan` with the cost of `track` (`track_params`; None = none, and `knot_plan`'s launches)
+        against targets [m,T,K] or [m,K] at offset [m] int32 (None: 0 for every env) taken off every iteration's particle returns, behind
+        the constraints and before the score.  Arguments behind `offset` as `knot_plan`; with terms the workspace is the tracking slot
+        (`cadm_tracking_workspace_bytes`), cached apart from the others."""
+        mppi, params = self._as_mppi_params(params)
+        m = int(np.shape(obs)[0])
+        phase = self._phase(phase, m, "tracking_plan")
+        T = 0
+        if track is None:      # the library's own route to the loop underneath, with that loop's workspace
+            targets = offset = None
+        else:
+            targets, T, offset = self._targets(targets, offset, m, track.n, "tracking_plan")
+        head = (None if track is None else ct.byref(track), ptr(targets), T, ptr(offset), None if knots is None else ct.byref(knots), ptr(phase),
+                None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi), ct.byref(params))
+        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
+        return self._loop_plan("tracking_plan", self.lib.cadm_tracking_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None,
+                               track=None if track is None else terminate)
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

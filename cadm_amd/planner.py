@@ -12,7 +12,7 @@ What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
   * `PlanOptions`: what a model's `cem_*` kwargs mean -- their checks, the switches, and the ctypes structs `HipEngine.opt_in_plan` hands to the library;
-  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`) one launch at a time, for the same purposes;
+  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
@@ -22,6 +22,7 @@ import collections
 import numpy as np
 import torch
 
+from . import _lib
 from .engine import HipEngine
 
 
@@ -29,31 +30,42 @@ FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/p
 
 
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
-                                                       "params score_params constraints constraint_params knots knot_params",
-                                                       defaults=(None, None))):
+                                                       "params score_params constraints constraint_params knots knot_params tracking track_params "
+                                                       "target_advance", defaults=(None, None, None, None, True))):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
     `score`: None, or (mode name, kappa, k).  `constraints`: None, or (the list of dict(dim=, lo=, hi=), mode name, weight), with
     `constraint_params` the `ConstraintParams` built from it (None: no state constraints, and the loop records no trajectory).
-    `knots`: None, or (spacing, interp name, anchor name), with `knot_params` the `KnotParams` built from it (None: every step is a decision)."""
+    `knots`: None, or (spacing, interp name, anchor name), with `knot_params` the `KnotParams` built from it (None: every step is a decision).
+    `tracking`: None, or the tuple of dict(dim=, kind=, w=, delta=), with `track_params` the `TrackParams` built from it (None: no run-time
+    targets); `target_advance`: whether a model moves its per-env target offsets on by one after every plan."""
     __slots__ = ()
 
     @staticmethod
     def from_kwargs(cem_noise_beta=0.0, cem_keep_elites=0, cem_decay=1.0, cem_return="mean", cem_add_mean=False, cem_update="cem",
                     cem_temperature=1.0, cem_temperature_relative=False, cem_score="mean", cem_risk=None, use_cem=False, discrete=False,
                     process_group=None, n_particles=20, cem_constraints=None, cem_constraint_mode="penalty", cem_constraint_weight=None, *,
-                    cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call"):
+                    cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call", cem_tracking=None, cem_target_advance=True):
         """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
         everything that needs no engine -- and folded into a `PlanOptions`."""
         if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
                 bool(cem_temperature_relative), cem_score, cem_risk, cem_constraints, cem_constraint_mode,
                 cem_constraint_weight) == (0.0, 0, 1.0, "mean", False, "cem", 1.0, False, "mean", None, None, "penalty", None) \
                 and (cem_knot_interp, cem_knot_anchor) == ("hold", "call") and isinstance(cem_knots, (int, np.integer)) \
-                and not isinstance(cem_knots, bool) and int(cem_knots) == 1:
+                and not isinstance(cem_knots, bool) and int(cem_knots) == 1 and cem_tracking is None and cem_target_advance is True:
             return None
         if not use_cem:
             raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
-                             "cem_score / cem_risk / cem_constraints / cem_knots configure the CEM planner: they need use_cem=True")
+                             "cem_score / cem_risk / cem_constraints / cem_knots / cem_tracking configure the CEM planner: they need use_cem=True")
+        if not isinstance(cem_target_advance, (bool, np.bool_)):
+            raise ValueError("cem_target_advance must be True or False, got %r" % (cem_target_advance,))
+        tracking = tparams = None
+        if cem_tracking is None:
+            if not cem_target_advance:
+                raise ValueError("cem_target_advance configures tracking targets: it needs cem_tracking")
+        else:
+            tparams = HipEngine.track_params(cem_tracking)
+            tracking = tuple(dict(c) for c in ([cem_tracking] if isinstance(cem_tracking, dict) else cem_tracking))
         if isinstance(cem_knots, bool) or not isinstance(cem_knots, (int, np.integer)) or int(cem_knots) < 1:
             raise ValueError("cem_knots must be an integer >= 1 (the spacing of the knot steps), got %r" % (cem_knots,))
         if cem_knot_interp not in ("hold", "linear"):
@@ -115,7 +127,8 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
         params = HipEngine.mppi_params(**mppi, **icem) if cem_update == "mppi" else HipEngine.icem_params(**icem)
         return PlanOptions(update=cem_update, score=score, params=params, score_params=None if score is None else HipEngine.score_params(*score),
                            constraints=constraints, constraint_params=cparams, knots=knots,
-                           knot_params=None if knots is None else HipEngine.knot_params(knots[0], knots[1]), **mppi, **icem)
+                           knot_params=None if knots is None else HipEngine.knot_params(knots[0], knots[1]), tracking=tracking,
+                           track_params=tparams, target_advance=bool(cem_target_advance), **mppi, **icem)
 
 
 class Shard:
@@ -241,7 +254,7 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
 
 def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
               add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False,
-              update="cem", temperature=1.0, relative=False, score=None, constraints=None, knots=None, phase=None):
+              update="cem", temperature=1.0, relative=False, score=None, constraints=None, knots=None, phase=None, tracking=None):
     """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
     tests with injected draws and for diagnostics.  update="mppi": the loop of `cadm_mppi_plan` -- the elite ids come from an elite
     refit into copies of mean / var, the distribution from `mppi_refit`.  score: a `HipEngine.score_params` (`cadm_scored_plan`; None: the
@@ -251,7 +264,10 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     [m,n_it,H,A] (noise_beta == 0), spectral draws [m,n_it,A,H] (noise_beta > 0) and head noise [H,m,n_it,p,D].  carry [m,K,H,A] /
     carry_valid [m] int32 are read at iteration 0 and rewritten IN PLACE after the last refit, as the library does.  knots: a
     `HipEngine.knot_params` (`cadm_knot_plan`; None or spacing 1: none) with phase [m] int32 (None: 0) -- the copy of init_mean and every
-    iteration's candidates, behind the injections, are shaped onto the grid (`shape_actions`); `return_info` carries the shaped `actions`."""
+    iteration's candidates, behind the injections, are shaped onto the grid (`shape_actions`); `return_info` carries the shaped `actions`.
+    tracking: (a `HipEngine.track_params`, targets [m,T,K] or [m,K], offset [m] int32 or None) (`cadm_tracking_plan`; None: none) -- every
+    rollout then records its trajectories and `tracking_returns` takes the cost off `rows` behind `constrain_returns` (whose first
+    violations it reads in terminate mode) and before the score; `return_info` carries `track_cost` and `rows_untracked`."""
     obs = engine._t(obs)
     mean, var = engine._t(init_mean).clone(), engine._t(init_var).clone()
     if knots is not None and knots.spacing == 1:
@@ -280,13 +296,22 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
         if knots is not None:
             engine.shape_actions(actions, knots, phase)
         extra = {}
-        if constraints is None:
+        if constraints is None and tracking is None:
             rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
         else:
-            raw, traj = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it,
-                                               want_traj=True)
-            rows, first, viol = engine.constrain_returns(traj, raw, constraints, obs=obs, actions=actions)
-            extra = dict(traj=traj, first_violation=first, violations=viol, rows_raw=raw)
+            rows, traj = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it,
+                                                want_traj=True)
+            first = None
+            if constraints is not None:
+                raw = rows
+                rows, first, viol = engine.constrain_returns(traj, raw, constraints, obs=obs, actions=actions)
+                extra = dict(traj=traj, first_violation=first, violations=viol, rows_raw=raw)
+                if constraints.mode != _lib.CONSTRAIN_MODES["terminate"]:
+                    first = None
+            if tracking is not None:
+                untracked = rows
+                rows, cost = engine.tracking_returns(traj, untracked, tracking[0], tracking[1], offset=tracking[2], first=first, want_cost=True)
+                extra.update(traj=traj, track_cost=cost, rows_untracked=untracked)
         cand = engine.particle_mean(rows) if score is None else engine.particle_score(rows, score)
         if update == "mppi":
             elites = engine.cem_refit(cand.unsqueeze(0), actions, mean.clone(), var.clone(), want_elites=True)

@@ -474,6 +474,60 @@ int cadm_knot_plan(cadm_ctx* ctx, const cadm_knot_params* knots, const int32_t* 
                    const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m,
                    int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
 
+/* Tracking targets at run time (no reference twin, OPT-IN): tell the opt-in loop "go there" -- a cost on the predicted states that the
+ * caller sets per env and per step when it calls, with no new env spec and no rebuild.  A term k < n reads ONE observation dim of the
+ * POST-step state of every step t = 0 .. H-1 of a recorded trajectory (traj [H,m,n,p,D], the layout of cadm_rollout_returns' traj_out, H
+ * and p the ctx's); the observation a call starts from is never read.  targets [m,T,K] float32 on the device, K = n terms, T >= 1 rows
+ * per env; offset [m] int32 on the device, or NULL = 0.  Step t of env mi is compared with
+ *   g = targets[mi, clamp(offset[mi] + t, 0, T-1), k]
+ * -- T = 1 is a constant goal, a reference shorter than the horizon holds its last row, a negative offset holds the first.  A NaN g
+ * means "no target for this term at this step": the (step, term) is skipped (a terminal cost, sparse waypoints).  Per particle row, one
+ * chain over t = 0 .. H-1 in step order, k ascending inside a step, every operation rounded to float32 (nothing is fused):
+ *   e = x[dim[k]] - g;   c = e*e (CADM_TRACK_SQUARE), |e| (CADM_TRACK_ABS), or |e| <= delta[k] ? 0.5 e*e : delta[k] (|e| - 0.5 delta[k])
+ *   (CADM_TRACK_HUBER);   cost += w[k] * c;   rows_out = rows_in - cost
+ * A row whose every (step, term) was skipped keeps rows_in's bits: targets that are all NaN change no plan.  A non-finite value in a
+ * tracked dim at a counted step makes the row's return non-finite (it then meets the score, the elite ranking and MPPI's zero weight as
+ * a diverged rollout's row does); other dims are not looked at.  Not done: wrapping an angle's e, targets on actions, a discount.
+ * cadm_tracking_returns: rows_in / rows_out [m,n,p] (rows_out may alias rows_in).  first [m,n,p] int32, or NULL: cadm_constrain_returns'
+ * first_violation_out -- steps t > first[row] are not counted: the step that leaves the region still pays, as it does for the reward in
+ * TERMINATE mode, and nothing traj holds after it reaches the return.  cost_out [m,n,p], or NULL: the cost alone (0 for a row with
+ * nothing counted).  traj is read at most once; a row's cost is one thread's chain (csrc/tracking.hip), no floating-point atomics: the
+ * same bits run to run, whatever m, n and the row's position.  Needs no workspace.
+ * Refusals, before any HIP call: CADM_EINVAL for n outside 1 .. CADM_MAX_TRACK_TERMS, a dim outside 0 .. D-1, an unknown kind, a w that
+ * is negative or not finite, a Huber delta that is not finite or <= 0, T < 1, NULL targets, a discrete ctx (cartpole), a sharded ctx, a
+ * D whose LDS tile (64 x D floats, plus 4.5 KiB of targets, offsets and terms) exceeds 48 KiB. */
+#define CADM_MAX_TRACK_TERMS 16
+#define CADM_TRACK_SQUARE 0
+#define CADM_TRACK_ABS 1
+#define CADM_TRACK_HUBER 2
+typedef struct cadm_track_params {
+    int32_t n;              /* 1 .. CADM_MAX_TRACK_TERMS */
+    int32_t dim[CADM_MAX_TRACK_TERMS];
+    int32_t kind[CADM_MAX_TRACK_TERMS];     /* CADM_TRACK_* */
+    float w[CADM_MAX_TRACK_TERMS];          /* finite, >= 0 */
+    float delta[CADM_MAX_TRACK_TERMS];      /* CADM_TRACK_HUBER only: finite, > 0 */
+} cadm_track_params;
+int cadm_tracking_returns(cadm_ctx* ctx, const cadm_track_params* track, const float* traj, const float* targets, int T,
+                          const int32_t* offset, const int32_t* first, const float* rows_in, int m, int n, float* rows_out,
+                          float* cost_out, void* stream);
+/* The loop of cadm_knot_plan under tracking targets.  With track set, every iteration's rollout records its trajectories into the
+ * workspace whether or not there are constraints, and the order is rollout -> cadm_constrain_returns (if any) -> cadm_tracking_returns
+ * -> cadm_particle_score, the particle returns rewritten in place.  Under TERMINATE constraints the constraint kernel also writes its
+ * first_violation into an [m,n,p] int32 view of the workspace and the tracking kernel reads it as `first`; under PENALTY constraints or
+ * none, first is NULL.  The elites, the tracked best plan, best_return_out, the kept elites and the carry are by the tracked score.
+ * targets [m,T,K] / offset [m] (or NULL) are read, never written: advancing the offsets between calls is the caller's.
+ * track NULL: exactly the launches of cadm_knot_plan (targets, T and offset are not looked at).  Refusals: those of cadm_knot_plan and
+ * of cadm_tracking_returns.
+ * workspace: cadm_tracking_workspace_bytes(ctx, m, n, K, mppi, terminate) bytes with track set -- cadm_constrained_workspace_bytes(ctx,
+ * m, n, K, mppi) plus, for terminate != 0 (TERMINATE constraints), the first_violation view (0 for bad arguments); with track NULL that
+ * of cadm_knot_plan. */
+size_t cadm_tracking_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate);
+int cadm_tracking_plan(cadm_ctx* ctx, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                       const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                       const cadm_score_params* score, int update, const cadm_mppi_params* params, const float* obs, const float* cp_obs,
+                       const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m,
+                       int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
+
 /* One training step = sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
