@@ -103,6 +103,13 @@ class TrackParams(C.Structure):         # include/cadm_hip.h cadm_track_params
                 ("w", C.c_float * MAX_TRACK_TERMS), ("delta", C.c_float * MAX_TRACK_TERMS)]
 
 
+MAX_ACT_DIMS = 32                                                          # CADM_MAX_ACT_DIMS
+
+
+class ActuatorParams(C.Structure):      # include/cadm_hip.h cadm_actuator_params
+    _fields_ = [("delay", C.c_int32), ("n_dims", C.c_int32), ("rate_limit", C.c_float * MAX_ACT_DIMS), ("rate_w", C.c_float * MAX_ACT_DIMS)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -164,6 +171,11 @@ SIGNATURES = {
     "cadm_tracking_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i]),
     "cadm_tracking_plan": (_i, [_P, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams),
                                 C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_actuate_actions": (_i, [_P, C.POINTER(ActuatorParams), _P, _P, _i, _i, _P, _P, _P]),
+    "cadm_actuated_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i]),
+    "cadm_actuated_plan": (_i, [_P, C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P,
+                                C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i,
+                                _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

@@ -10,7 +10,8 @@
 // MPPI refit (mppi.hip), both on the particle mean; cadm_scored_plan chooses the update and the score (score.hip); cadm_constrained_plan
 // also rewrites the particle returns under state constraints (constrain.hip) before the score sees them; cadm_knot_plan also shapes every
 // iteration's candidates onto a grid of knot steps (knots.hip) before the rollout sees them; cadm_tracking_plan also takes the cost of
-// run-time tracking targets (tracking.hip) off the particle returns, behind the constraints and before the score.
+// run-time tracking targets (tracking.hip) off the particle returns, behind the constraints and before the score; cadm_actuated_plan also
+// passes every iteration's candidates, and the plan, through an actuator model (actuator.hip: action delay, rate limits, rate cost).
 #include <math.h>
 
 #include "planner.h"
@@ -292,10 +293,12 @@ struct IcemWs {
     int32_t* elites;
     float *emean, *evar, *mppi;      // MPPI only: where the elite selection's own refit goes (discarded), the update's weights and partials
     int32_t* first;                  // tracked under TERMINATE constraints only: the constraint kernel's first_violation [m, n, p], in front of traj
-    float* traj;                     // constrained or tracked only: the rollout's trajectories [H, m, n, p, D], the LAST view (the sums before it stay)
+    float* traj;                     // constrained or tracked only: the rollout's trajectories [H, m, n, p, D], the last view of every loop before the
+                                     // actuated one (the sums before it stay)
+    float *acost, *aplan;            // actuated only, behind traj: the candidates' rate cost [m, n]; the plan [m, H, A] before its last actuate pass
 };
 
-static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0, int first = 0) {
+static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0, int first = 0, int act = 0) {
     Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
     IcemWs t{};
@@ -317,6 +320,10 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
     }
     if (first) t.first = c.take<int32_t>((size_t)m * n * ctx->p);
     if (traj) t.traj = c.take<float>((size_t)ctx->H * m * n * ctx->p * ctx->D);
+    if (act) {
+        t.acost = c.take<float>((size_t)m * n);
+        t.aplan = c.take<float>((size_t)m * HA);
+    }
     if (w) *w = t;
     return c.off;
 }
@@ -341,6 +348,11 @@ extern "C" size_t cadm_tracking_workspace_bytes(cadm_ctx* ctx, int m, int n, int
     return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0);
 }
 
+extern "C" size_t cadm_actuated_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int traj, int terminate) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, traj != 0, traj != 0 && terminate != 0, 1);
+}
+
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
 static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     double v = floor((double)n / pow(decay, (double)it));
@@ -357,12 +369,17 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 // terms: tracking terms whose cost against targets [m, T, K] (offset [m] int32 on the device or null = 0) comes off the particle returns
 // behind the constraints and before the score (tracking.hip); null = none, and today's launches.  With terms every rollout records its
 // trajectories, and TERMINATE constraints hand their first violations on: what a terminated trajectory holds behind them is not tracked.
+// act: an actuator model (actuator.hip) with the envs' last applied action prev [m, A] and committed steps prefix [m, delay, A] on the
+// device; null = none, and today's launches.  With it every iteration's candidates are actuated in place behind the knot shaping, their
+// rate cost comes off the candidate score behind cadm_particle_score, and the plan is actuated once more (n = 1) on a device copy before
+// it is written to plan_out; advance: then prev <- plan[:, 0], prefix[:, j] <- plan[:, 1 + j].
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                      float* best_return_out, void* stream, const cadm_constraint_params* constraints = nullptr,
                      const cadm_knot_params* knots = nullptr, const int32_t* phase = nullptr, const cadm_track_params* terms = nullptr,
-                     const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr) {
+                     const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr, const cadm_actuator_params* act = nullptr,
+                     float* prev_io = nullptr, float* prefix_io = nullptr, int advance = 0) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -382,13 +399,17 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     if (constraints && (rc = cadm_constraint_check(ctx, constraints, who))) return rc;
     if (knots && (rc = cadm_knot_check(knots, who))) return rc;
     if (terms && (rc = cadm_track_check(ctx, terms, targets, T, who))) return rc;
+    if (act) {
+        if ((rc = cadm_actuator_check(ctx, act, who))) return rc;
+        CADM_REQUIRE(prev_io && (act->delay == 0 || prefix_io), "%s: the actuator model needs prev [m, A], and prefix [m, delay, A] with a delay", who);
+    }
     const bool shape = knots && knots->spacing > 1;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
     // (w.traj: null without constraints and terms; w.first: null unless terms follow TERMINATE constraints)
     icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || terms != nullptr,
-               terms != nullptr && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE);
+               terms != nullptr && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr);
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
@@ -419,6 +440,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         }
         // every candidate onto the grid, the injected slots included: ni, the packed count of this iteration, not the workspace's n
         if (shape && (rc = cadm_launch_shape_actions(ctx, knots, phase, m, ni, w.actions, s))) return rc;
+        // and through the actuator: pins, rate limits, and what the moves cost
+        if (act && (rc = cadm_launch_actuate(ctx, act, prev_io, prefix_io, m, ni, w.actions, w.acost, s))) return rc;
         if ((rc = cadm_rollout_returns(ctx, obs, nullptr, ctx->C > 0 ? w.ctxv : nullptr, w.actions, nullptr, 1, seed, call, it, 0, ni, m, ni,
                                        w.rows, w.traj, stream))) return rc;
         // the trajectories are [H, m, ni, p, D] of this iteration's ni candidates; the returns are rewritten in place
@@ -426,7 +449,10 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
                                                         stream))) return rc;
         if (terms && (rc = cadm_tracking_returns(ctx, terms, w.traj, targets, T, offset, w.first, w.rows, m, ni, w.rows, nullptr, stream))) return rc;
         if ((rc = cadm_particle_score(ctx, w.rows, m, ni, score, w.cand, stream))) return rc;      // (the mean: cadm_particle_mean itself)
-        float* plan = (last && !prm->return_best) ? plan_out : nullptr;      // the refitted mean, clipped (dynamics.py:365-366)
+        // the cost is deterministic per candidate: it comes off the candidate score, not off the particle rows
+        if (act && (rc = cadm_launch_actuator_sub(w.cand, w.acost, (size_t)m * ni, s))) return rc;
+        // the refitted mean, clipped (dynamics.py:365-366); actuated: into the workspace, for its last pass
+        float* plan = (last && !prm->return_best) ? (act ? w.aplan : plan_out) : nullptr;
         if (!upd.mppi) {
             if ((rc = cadm_launch_refit(ctx, w.cand, nullptr, 1, ni, w.actions, m, mean_in, var_in, w.mean, w.var, w.elites, plan, s))) return rc;
         } else {
@@ -441,7 +467,14 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if (K > 0 && (rc = last ? launch_keep(ctx, w.actions, w.elites, m, ni, K, carry_io, carry_valid_io, s)
                                 : launch_keep(ctx, w.actions, w.elites, m, ni, K, w.kept, nullptr, s))) return rc;
     }
-    if (prm->return_best && (rc = cadm_launch_clip(w.best_seq, plan_out, m * HA, 0.0f, 0.0f, 0, s))) return rc;
+    if (act) {
+        // a mean of feasible sequences is feasible only up to rounding: one more pass with n = 1 on a device copy (plan_out may be pinned
+        // host memory), for the best sequence a bitwise no-op; then the plan leaves, and episode time moves on by one step
+        float* fin = prm->return_best ? w.best_seq : w.aplan;
+        if ((rc = cadm_launch_actuate(ctx, act, prev_io, prefix_io, m, 1, fin, nullptr, s))) return rc;
+        if ((rc = cadm_launch_clip(fin, plan_out, m * HA, 0.0f, 0.0f, 0, s))) return rc;
+        if (advance && (rc = cadm_launch_actuator_advance(ctx, act, fin, prev_io, prefix_io, m, s))) return rc;
+    } else if (prm->return_best && (rc = cadm_launch_clip(w.best_seq, plan_out, m * HA, 0.0f, 0.0f, 0, s))) return rc;
     if (best_return_out && (rc = cadm_launch_clip(w.best_ret, best_return_out, m, 0.0f, 0.0f, 0, s))) return rc;
     return CADM_OK;
 }
@@ -515,4 +548,21 @@ extern "C" int cadm_tracking_plan(cadm_ctx* ctx, const cadm_track_params* track,
     const PlanUpdate upd{"cadm_tracking_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset);
+}
+
+// the outermost of the nest: with an actuator model (actuator.hip) between the knot shaping and the rollout, its rate cost behind the score
+// and its last pass over the plan; act null: cadm_tracking_plan's launches
+extern "C" int cadm_actuated_plan(cadm_ctx* ctx, const cadm_actuator_params* act, float* prev_io, float* prefix_io, int advance,
+                                  const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                                  const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                                  const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs,
+                                  const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                                  int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                                  float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_actuated_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_actuated_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_actuated_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
+                     advance);
 }

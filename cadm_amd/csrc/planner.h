@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -80,6 +80,16 @@ int cadm_launch_shape_actions(cadm_ctx* ctx, const cadm_knot_params* knots, cons
 // tracking.hip: the refusals of a set of tracking terms and its targets (count, dims, kinds, weights, Huber deltas, T < 1, null targets, a
 // discrete / sharded ctx, a D whose tile exceeds the kernel's LDS), before any HIP call
 int cadm_track_check(const cadm_ctx* ctx, const cadm_track_params* track, const float* targets, int T, const char* who);
+// actuator.hip: the refusals of an actuator model (delay outside [0, H), a limit <= 0 or NaN, a cost negative or not finite, arrays built
+// for another A, A beyond their capacity, a discrete / sharded ctx), before any HIP call; the in-place pass over seqs [m, n, H, A] (n the
+// PACKED candidate count; prev [m, A] / prefix [m, delay, A] on the device or null = NaN; cost_out [m, n] or null); cand -= cost; and the
+// step of episode time behind a plan [m, H, A]: prev <- plan[:, 0], prefix[:, j] <- plan[:, 1 + j]
+int cadm_actuator_check(const cadm_ctx* ctx, const cadm_actuator_params* act, const char* who);
+int cadm_launch_actuate(cadm_ctx* ctx, const cadm_actuator_params* act, const float* prev, const float* prefix, int m, int n, float* seqs,
+                        float* cost_out, hipStream_t s);
+int cadm_launch_actuator_sub(float* cand, const float* cost, size_t total, hipStream_t s);
+int cadm_launch_actuator_advance(cadm_ctx* ctx, const cadm_actuator_params* act, const float* plan, float* prev, float* prefix, int m,
+                                 hipStream_t s);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

@@ -47,6 +47,13 @@ Differences a caller can see (all opt-in except the first):
     scored; NaN in the targets: no target there; the model moves every env's place in its reference on by one per planned call
     (`cem_target_advance=False`: the caller does), `reset_plan_carry` puts it back to 0; `clear_targets()`; `tracking_cost(obs, actions,
     ...)`: what the terms cost given plans.  `cem_tracking` alone takes the opt-in route; targets that are all NaN change no plan;
+  * `cem_action_delay=d`, `cem_action_rate_limit`, `cem_action_rate_cost`, `cem_action_advance`: an actuator model in that loop
+    (INTEGRATION.md "Actuator model") -- the plan's first d steps are the ones earlier calls committed, every other step stays within
+    `cem_action_rate_limit` (a scalar or [A]) of the step before it, step 0 of the action applied last, and sum_t sum_a w_a (u_t - u_{t-1})^2
+    (`cem_action_rate_cost`, a scalar or [A]) comes off every candidate's score; the model keeps the applied action and the committed
+    steps per env on the device and moves them on after every planned call (`cem_action_advance=False`: the caller does, with
+    `set_applied_actions`), `reset_plan_carry` forgets them; `actuator_state()`; `action_cost(actions)`: what the model makes of given
+    plans.  Any of the three alone takes the opt-in route;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -223,6 +230,10 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_knot_anchor="call",
                  cem_tracking=None,
                  cem_target_advance=True,
+                 cem_action_delay=0,
+                 cem_action_rate_limit=None,
+                 cem_action_rate_cost=None,
+                 cem_action_advance=True,
                  engine_lib=None,
                  ):
         self.env = env
@@ -286,7 +297,10 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      cem_constraints=cem_constraints, cem_constraint_mode=cem_constraint_mode,
                                                      cem_constraint_weight=cem_constraint_weight, cem_knots=cem_knots,
                                                      cem_knot_interp=cem_knot_interp, cem_knot_anchor=cem_knot_anchor,
-                                                     cem_tracking=cem_tracking, cem_target_advance=cem_target_advance)
+                                                     cem_tracking=cem_tracking, cem_target_advance=cem_target_advance,
+                                                     cem_action_delay=cem_action_delay, cem_action_rate_limit=cem_action_rate_limit,
+                                                     cem_action_rate_cost=cem_action_rate_cost, cem_action_advance=cem_action_advance,
+                                                     n_forwards=n_forwards, action_dim=None if self.discrete else self.action_space_dims)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
@@ -298,6 +312,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
         self._plan_phase = None                               # device tensor [m] int32: the knot grid's phase (cem_knot_anchor="episode")
         self._targets = self._target_offset = None            # device tensors [m,T,K] float32 / [m] int32 (cem_tracking): `set_targets`
+        self._act_prev = self._act_prefix = None              # device tensors [m,A] / [m,delay,A] float32, NaN = unknown (the actuator model)
 
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
@@ -484,6 +499,9 @@ class MLPEnsembleCEMDynamicsModel(object):
                 raise ValueError("get_action: the targets are %r, this call has %d envs and cem_tracking %d terms: expected [%d,T,%d]"
                                  % (tuple(self._targets.shape), m, self._opt.track_params.n, m, self._opt.track_params.n))
             extra.update(targets=self._targets, target_offset=self._target_offset)
+        if self._opt.actuator_params is not None:      # first call, or another number of envs: nothing applied, nothing committed; the
+            self._actuator_tensors(m)                  # library moves both on behind the plan, on the engine's stream (cem_action_advance)
+            extra.update(act_prev=self._act_prev, act_prefix=self._act_prefix)
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
@@ -496,6 +514,78 @@ class MLPEnsembleCEMDynamicsModel(object):
         if tracked and self._opt.target_advance:      # likewise: the next call's step 0 is this call's step 1 of the reference
             self._target_offset.add_(1)
         return plan
+
+    # ------------------------------------------------------------------ actuator model (INTEGRATION.md "Actuator model")
+    def _actuator_tensors(self, m):
+        """The actuator state for m envs, allocated on first use and again -- all NaN -- for another number of envs."""
+        if self._act_prev is None or self._act_prev.shape[0] != m:
+            nan = float("nan")
+            self._act_prev = torch.full((m, self.action_space_dims), nan, dtype=torch.float32, device=self.engine.device)
+            self._act_prefix = torch.full((m, self._opt.actuator_params.delay, self.action_space_dims), nan, dtype=torch.float32,
+                                          device=self.engine.device)
+
+    def _require_actuator(self, who):
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.actuator_params is None:
+            raise ValueError("%s: this model has no actuator model (cem_action_delay / cem_action_rate_limit / cem_action_rate_cost)" % who)
+        return opt.actuator_params
+
+    def set_applied_actions(self, prev=None, committed=None, mask=None):
+        """Tell the actuator model what the device was really told: prev [m,A], the action applied immediately before the next plan's
+        step 0, and / or committed [m,delay,A], the actions already decided for its steps 0 .. delay-1 -- for a caller whose executed
+        action differs from the plan, who starts an episode with a known command, or who advances the state themselves
+        (`cem_action_advance=False`).  NaN: unknown / that step is free.  None leaves that part as it is; mask [m]: only the envs where
+        it is set are written."""
+        prm = self._require_actuator("set_applied_actions")
+        given = [np.shape(x)[0] for x in (prev, committed) if x is not None]
+        if not given:
+            return
+        m, A, d = int(given[0]), self.action_space_dims, prm.delay
+        for name, x, shp in (("prev", prev, (m, A)), ("committed", committed, (m, d, A))):
+            if x is not None and tuple(int(v) for v in np.shape(x)) != shp:
+                raise ValueError("set_applied_actions: %s %r, expected %r" % (name, tuple(np.shape(x)), shp))
+        eng = self.engine
+        self._actuator_tensors(m)
+        mk = None
+        if mask is not None:
+            mk = eng._t(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.bool).reshape(-1)
+            if mk.shape[0] != m:
+                raise ValueError("set_applied_actions: mask has %d entries, expected %d" % (mk.shape[0], m))
+        for x, dst in ((prev, self._act_prev), (committed, self._act_prefix)):
+            if x is None:
+                continue
+            src = eng._t(x)
+            if mk is None:
+                dst.copy_(src)
+            else:
+                dst.copy_(torch.where(mk.reshape((m,) + (1,) * (dst.dim() - 1)), src, dst))
+
+    def actuator_state(self):
+        """dict(prev [m,A], committed [m,delay,A]) as numpy copies (NaN: unknown / free), or None before the first planned call."""
+        self._require_actuator("actuator_state")
+        if self._act_prev is None:
+            return None
+        return dict(prev=self._act_prev.cpu().numpy(), committed=self._act_prefix.cpu().numpy())
+
+    def action_cost(self, actions):
+        """What the actuator model makes of `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) under the current state and parameters, and
+        what that costs -- the companion of `tracking_cost`: dict(cost [m,n], actions [m,n,H,A]) as numpy arrays (for [m,H,A] input the n
+        axis is dropped).  Moves no counter and no state; the caller's array is not written."""
+        prm = self._require_actuator("action_cost")
+        eng = self.engine
+        acts = eng._t(actions)
+        if acts.dim() not in (3, 4) or tuple(acts.shape[-2:]) != (self.n_forwards, self.action_space_dims):
+            raise ValueError("action_cost: actions %r, expected [m,%d,%d] or [m,n,%d,%d]"
+                             % (tuple(acts.shape), self.n_forwards, self.action_space_dims, self.n_forwards, self.action_space_dims))
+        acts = acts.contiguous().clone()
+        m = acts.shape[0]
+        prev = prefix = None
+        if self._act_prev is not None:
+            if self._act_prev.shape[0] != m:
+                raise ValueError("action_cost: actions for %d envs, the actuator state holds %d" % (m, self._act_prev.shape[0]))
+            prev, prefix = self._act_prev, self._act_prefix
+        acts, cost = eng.actuate_actions(acts, prm, prev=prev, prefix=prefix, want_cost=True)
+        return dict(cost=cost.cpu().numpy(), actions=acts.cpu().numpy())
 
     # ------------------------------------------------------------------ tracking targets (INTEGRATION.md "Tracking targets at run time")
     def set_targets(self, targets, offset=None):
@@ -659,20 +749,27 @@ class MLPEnsembleCEMDynamicsModel(object):
         """Forget the elites the iCEM planner carries from one get_action to the next (`cem_keep_elites` > 0): for every env, or for
         those where `mask` [m] is set -- at an episode boundary, so that a new episode never starts from the previous one's plans --
         and put their knot grids back on the call's first step (`cem_knot_anchor="episode"`) and their tracking references back on row 0
-        (`cem_tracking`: the target offsets; the targets themselves stay).  A no-op for a model that carries nothing."""
+        (`cem_tracking`: the target offsets; the targets themselves stay); the actuator model's applied action and committed steps become
+        unknown (NaN, not zero: a new episode's first step is not limited against the last episode's command).  A no-op for a model
+        that carries nothing."""
         held = [t for t in (self._plan_carry_valid, getattr(self, "_plan_phase", None), getattr(self, "_target_offset", None)) if t is not None]
-        if not held:
+        unknown = [t for t in (getattr(self, "_act_prev", None), getattr(self, "_act_prefix", None)) if t is not None]
+        if not held and not unknown:
             return
         if mask is None:
             for t in held:
                 t.zero_()
+            for t in unknown:
+                t.fill_(float("nan"))
             return
         mk = self.engine._t(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.bool).reshape(-1)
-        for t in held:
+        for t in held + unknown:
             if mk.shape[0] != t.shape[0]:
                 raise ValueError("reset_plan_carry: mask has %d entries, the planner carries elites for %d envs" % (mk.shape[0], t.shape[0]))
         for t in held:
             t.masked_fill_(mk, 0)
+        for t in unknown:
+            t.masked_fill_(mk.reshape((-1,) + (1,) * (t.dim() - 1)), float("nan"))
 
     def get_context_pred(self, cp_obs, cp_act):
         """reference :369-380 -> [E,m,C]."""

@@ -560,10 +560,10 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return, traj=False, track=None):
+                   want_best_return, traj=False, track=None, act=False):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
         `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
-        workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop)."""
+        workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop); act: the workspace of an actuated loop."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -572,7 +572,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -580,11 +580,15 @@ class HipEngine:
                            m, n, seed, call, ptr(ws), ptr(out), ptr(best), self.stream), "cadm_" + who)
         return (out, best) if want_best_return else out
 
-    def opt_in_plan(self, opt, *args, phase=None, targets=None, target_offset=None, **kw):
-        """The opt-in loop under a `planner.PlanOptions`: `tracking_plan` when it holds tracking terms (targets [m,T,K] or [m,K],
+    def opt_in_plan(self, opt, *args, phase=None, targets=None, target_offset=None, act_prev=None, act_prefix=None, **kw):
+        """The opt-in loop under a `planner.PlanOptions`: `actuated_plan` when it holds an actuator model (act_prev [m,A] / act_prefix
+        [m,delay,A]: the envs' actuator state, moved on in place when the options say so), `tracking_plan` when it holds tracking terms (targets [m,T,K] or [m,K],
         target_offset [m] int32 or None = 0), `knot_plan` when it holds knots (phase: the envs' grid phases [m] int32, None = 0),
         `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
         Arguments as `icem_plan` behind its params."""
+        if opt.actuator_params is not None:
+            return self.actuated_plan(opt.actuator_params, act_prev, act_prefix, opt.action_advance, opt.track_params, targets, target_offset,
+                                      opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params, *args, **kw)
         if opt.track_params is not None:
             return self.tracking_plan(opt.track_params, targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params,
                                       opt.params, *args, **kw)
@@ -596,15 +600,21 @@ class HipEngine:
             return self.scored_plan(opt.score_params, opt.params, *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
-    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None):
+    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
         constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that).  track: None,
         or whether a tracked loop runs under TERMINATE constraints -- the tracking slot (`cadm_tracking_workspace_bytes`: the trajectory
-        view, and the first-violation view in front of it under TERMINATE)."""
+        view, and the first-violation view in front of it under TERMINATE).  act: an actuated loop's slot (`cadm_actuated_workspace_bytes`:
+        the loop underneath's views, and behind them the candidates' rate cost and the plan's device copy)."""
         slot = (bool(mppi), bool(traj)) if track is None else (bool(mppi), "track", bool(track))
+        if act:
+            slot = slot + ("act",)
         key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            if track is not None:
+            if act:
+                nbytes = self.lib.cadm_actuated_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(traj) or track is not None),
+                                                                int(bool(track)))
+            elif track is not None:
                 nbytes = self.lib.cadm_tracking_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(track)))
             elif traj:
                 nbytes = self.lib.cadm_constrained_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)))
@@ -924,6 +934,104 @@ class HipEngine:
         return self._loop_plan("tracking_plan", self.lib.cadm_tracking_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None,
                                track=None if track is None else terminate)
+
+    # ------------------------------------------------------------------ actuator model (opt-in; csrc/actuator.hip)
+    @staticmethod
+    def actuator_params(delay=0, rate_limit=None, rate_cost=None, action_dim=None, horizon=None):
+        """`cadm_actuator_params`: delay -- an integer >= 0, the number of leading plan steps earlier calls have committed (below
+        `horizon` when that is given); rate_limit -- None (none), a scalar or [A]: how far an action dim may move per step, > 0, inf = no
+        limit for that dim; rate_cost -- None (0), a scalar or [A]: the weight of (u_t - u_{t-1})^2 per dim, finite and >= 0.  Arrays
+        must have `action_dim` entries when that is given, at most `_lib.MAX_ACT_DIMS` anyway, and agree with one another; the library
+        checks them, and the delay, against the engine's A and H.  Needs no GPU."""
+        if isinstance(delay, bool) or not isinstance(delay, (int, np.integer)) or int(delay) < 0 \
+                or (horizon is not None and int(delay) >= int(horizon)):
+            raise ValueError("action delay must be an integer in [0, n_forwards%s), got %r" % ("" if horizon is None else " = %d" % horizon, delay))
+        if action_dim is not None and not 1 <= int(action_dim) <= _lib.MAX_ACT_DIMS:
+            raise ValueError("the actuator model holds up to %d action dims, got %r" % (_lib.MAX_ACT_DIMS, action_dim))
+        prm = _lib.ActuatorParams()
+        prm.delay, n_dims = int(delay), 0
+        for name, val, default, field in (("rate_limit", rate_limit, math.inf, prm.rate_limit), ("rate_cost", rate_cost, 0.0, prm.rate_w)):
+            try:
+                arr = np.asarray(default if val is None else val, dtype=np.float32)
+            except (TypeError, ValueError):
+                raise ValueError("action %s must be a number or a list of them, got %r" % (name, val)) from None
+            if arr.ndim > 1 or (arr.ndim == 1 and not 1 <= arr.shape[0] <= _lib.MAX_ACT_DIMS):
+                raise ValueError("action %s must be a scalar or [A] with A <= %d, got shape %r" % (name, _lib.MAX_ACT_DIMS, arr.shape))
+            if arr.ndim == 1:
+                if (action_dim is not None and arr.shape[0] != int(action_dim)) or (n_dims and arr.shape[0] != n_dims):
+                    raise ValueError("action %s has %d entries, expected %d (one per action dim)"
+                                     % (name, arr.shape[0], n_dims if action_dim is None else int(action_dim)))
+                n_dims = int(arr.shape[0])
+            if name == "rate_limit" and not bool(np.all(arr > 0.0)):
+                raise ValueError("action rate_limit must be > 0 (inf: no limit), got %r" % (val,))
+            if name == "rate_cost" and not bool(np.all(np.isfinite(arr) & (arr >= 0.0))):
+                raise ValueError("action rate_cost must be finite and >= 0, got %r" % (val,))
+            full = np.full((_lib.MAX_ACT_DIMS,), arr if arr.ndim == 0 else default, dtype=np.float32)
+            if arr.ndim == 1:
+                full[:arr.shape[0]] = arr
+            for k in range(_lib.MAX_ACT_DIMS):
+                field[k] = float(full[k])
+        prm.n_dims = n_dims
+        return prm
+
+    def _actuator_state(self, prev, prefix, m, d, who):
+        """(prev [m,A], prefix [m,d,A]) float32 contiguous on the device, None staying None (unknown / nothing committed)"""
+        if prev is not None:
+            prev = self._t(prev)
+            if tuple(prev.shape) != (m, self.A) or not prev.is_contiguous():
+                raise ValueError("%s: prev %r, expected contiguous [%d,%d]" % (who, tuple(prev.shape), m, self.A))
+        if prefix is not None:
+            prefix = self._t(prefix)
+            if tuple(prefix.shape) != (m, d, self.A) or not prefix.is_contiguous():
+                raise ValueError("%s: prefix %r, expected contiguous [%d,%d,%d] (m, delay, A)" % (who, tuple(prefix.shape), m, d, self.A))
+        return prev, prefix
+
+    def actuate_actions(self, seqs, params, prev=None, prefix=None, want_cost=False):
+        """`cadm_actuate_actions`: seqs [m,n,H,A] or [m,H,A] (a contiguous float32 device tensor) passed through the actuator model
+        `params` (`actuator_params`) IN PLACE -- the committed steps of prefix [m,delay,A] pinned, every other step within the rate limits
+        of the step before (step 0: of prev [m,A]) and the action box; NaN in prev / prefix, or None: unknown / not committed.  Returns
+        seqs, with want_cost (seqs, cost [m,n] or [m]): sum_a sum_t w_a (u_t - u_{t-1})^2 of the actuated sequences."""
+        if not isinstance(seqs, torch.Tensor) or seqs.dtype != torch.float32 or not seqs.is_contiguous() or seqs.dim() not in (3, 4) \
+                or tuple(seqs.shape[-2:]) != (self.H, self.A) or seqs.shape[0] == 0 or not seqs.is_cuda:
+            raise ValueError("actuate_actions: expected a contiguous float32 device tensor [m,n,%d,%d] or [m,%d,%d]" % (self.H, self.A, self.H, self.A))
+        m, n = seqs.shape[0], seqs.shape[1] if seqs.dim() == 4 else 1
+        prev, prefix = self._actuator_state(prev, prefix, m, params.delay, "actuate_actions")
+        cost = torch.empty(tuple(seqs.shape[:-2]), dtype=torch.float32, device=self.device) if want_cost else None
+        self._check(self.lib.cadm_actuate_actions(self._ctx, ct.byref(params), ptr(prev), ptr(prefix), m, n, ptr(seqs), ptr(cost), self.stream),
+                    "cadm_actuate_actions")
+        return (seqs, cost) if want_cost else seqs
+
+    def actuated_plan(self, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score, params, obs, cp_obs,
+                      cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None, want_best_return=False):
+        """`cadm_actuated_plan`: the loop of `tracking_plan` under the actuator model `actuator` (`actuator_params`; None = none, and
+        `tracking_plan`'s launches): every iteration's candidates actuated behind the knot shaping, their rate cost taken off the candidate
+        score, the plan actuated once more before it is written.  prev [m,A] / prefix [m,delay,A] (prefix may be None with delay 0): the
+        envs' actuator state on the device, device tensors that `advance` moves on IN PLACE by one step behind the plan.  Arguments
+        behind `advance` as `tracking_plan`; the workspace is the actuated slot (`cadm_actuated_workspace_bytes`)."""
+        if actuator is None:
+            return self.tracking_plan(track, targets, offset, knots, phase, constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var,
+                                      n, carry=carry, carry_valid=carry_valid, seed=seed, call=call, out=out, want_best_return=want_best_return)
+        mppi, params = self._as_mppi_params(params)
+        m = int(np.shape(obs)[0])
+        for name, t in (("prev", prev), ("prefix", prefix)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+                raise ValueError("actuated_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
+        if prev is None or (prefix is None and actuator.delay > 0):
+            raise ValueError("actuated_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
+        prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "actuated_plan")
+        phase = self._phase(phase, m, "actuated_plan")
+        T = 0
+        if track is None:
+            targets = offset = None
+        else:
+            targets, T, offset = self._targets(targets, offset, m, track.n, "actuated_plan")
+        head = (ct.byref(actuator), ptr(prev), ptr(prefix), int(bool(advance)), None if track is None else ct.byref(track), ptr(targets), T,
+                ptr(offset), None if knots is None else ct.byref(knots), ptr(phase), None if constraints is None else ct.byref(constraints),
+                None if score is None else ct.byref(score), int(mppi), ct.byref(params))
+        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
+        return self._loop_plan("actuated_plan", self.lib.cadm_actuated_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None,
+                               track=None if track is None else terminate, act=True)
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

@@ -30,33 +30,57 @@ FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/p
 
 
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
-                                                       "params score_params constraints constraint_params knots knot_params tracking track_params "
-                                                       "target_advance", defaults=(None, None, None, None, True))):
+                                                       "params score_params constraints constraint_params knots knot_params actuator actuator_params "
+                                                       "action_advance tracking track_params target_advance",
+                                                       defaults=(None, None, None, None, True, None, None, True))):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
     `score`: None, or (mode name, kappa, k).  `constraints`: None, or (the list of dict(dim=, lo=, hi=), mode name, weight), with
     `constraint_params` the `ConstraintParams` built from it (None: no state constraints, and the loop records no trajectory).
     `knots`: None, or (spacing, interp name, anchor name), with `knot_params` the `KnotParams` built from it (None: every step is a decision).
     `tracking`: None, or the tuple of dict(dim=, kind=, w=, delta=), with `track_params` the `TrackParams` built from it (None: no run-time
-    targets); `target_advance`: whether a model moves its per-env target offsets on by one after every plan."""
+    targets); `target_advance`: whether a model moves its per-env target offsets on by one after every plan.
+    `actuator`: None, or (delay, the rate limits, the rate costs) -- each of the two a tuple of A floats or one float -- with
+    `actuator_params` the `ActuatorParams` built from it (None: no actuator model); `action_advance`: whether a planned call ends with the
+    actuator state moved on by one step (prev <- plan[:,0], the committed prefix <- plan[:,1 .. delay])."""
     __slots__ = ()
 
     @staticmethod
     def from_kwargs(cem_noise_beta=0.0, cem_keep_elites=0, cem_decay=1.0, cem_return="mean", cem_add_mean=False, cem_update="cem",
                     cem_temperature=1.0, cem_temperature_relative=False, cem_score="mean", cem_risk=None, use_cem=False, discrete=False,
                     process_group=None, n_particles=20, cem_constraints=None, cem_constraint_mode="penalty", cem_constraint_weight=None, *,
-                    cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call", cem_tracking=None, cem_target_advance=True):
+                    cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call", cem_tracking=None, cem_target_advance=True,
+                    cem_action_delay=0, cem_action_rate_limit=None, cem_action_rate_cost=None, cem_action_advance=True, n_forwards=None,
+                    action_dim=None):
         """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
-        everything that needs no engine -- and folded into a `PlanOptions`."""
+        everything that needs no engine -- and folded into a `PlanOptions`.  n_forwards / action_dim: the model's horizon and action
+        dims, what `cem_action_delay` and the lengths of `cem_action_rate_limit` / `cem_action_rate_cost` are checked against (None: the
+        library checks them against the engine's)."""
+        act_off = (cem_action_rate_limit is None and cem_action_rate_cost is None and isinstance(cem_action_delay, (int, np.integer))
+                   and not isinstance(cem_action_delay, bool) and int(cem_action_delay) == 0)
         if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
                 bool(cem_temperature_relative), cem_score, cem_risk, cem_constraints, cem_constraint_mode,
                 cem_constraint_weight) == (0.0, 0, 1.0, "mean", False, "cem", 1.0, False, "mean", None, None, "penalty", None) \
                 and (cem_knot_interp, cem_knot_anchor) == ("hold", "call") and isinstance(cem_knots, (int, np.integer)) \
-                and not isinstance(cem_knots, bool) and int(cem_knots) == 1 and cem_tracking is None and cem_target_advance is True:
+                and not isinstance(cem_knots, bool) and int(cem_knots) == 1 and cem_tracking is None and cem_target_advance is True \
+                and act_off and cem_action_advance is True:
             return None
         if not use_cem:
             raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
-                             "cem_score / cem_risk / cem_constraints / cem_knots / cem_tracking configure the CEM planner: they need use_cem=True")
+                             "cem_score / cem_risk / cem_constraints / cem_knots / cem_tracking / cem_action_delay / cem_action_rate_limit / "
+                             "cem_action_rate_cost configure the CEM planner: they need use_cem=True")
+        if not isinstance(cem_action_advance, (bool, np.bool_)):
+            raise ValueError("cem_action_advance must be True or False, got %r" % (cem_action_advance,))
+        actuator = aparams = None
+        if act_off:
+            if not cem_action_advance:
+                raise ValueError("cem_action_advance configures the actuator model: it needs cem_action_delay, cem_action_rate_limit or "
+                                 "cem_action_rate_cost")
+        else:
+            aparams = HipEngine.actuator_params(cem_action_delay, cem_action_rate_limit, cem_action_rate_cost, action_dim=action_dim,
+                                                horizon=n_forwards)
+            as_key = lambda v: None if v is None else (float(v) if np.ndim(v) == 0 else tuple(float(x) for x in np.asarray(v).reshape(-1)))
+            actuator = (int(cem_action_delay), as_key(cem_action_rate_limit), as_key(cem_action_rate_cost))
         if not isinstance(cem_target_advance, (bool, np.bool_)):
             raise ValueError("cem_target_advance must be True or False, got %r" % (cem_target_advance,))
         tracking = tparams = None
@@ -128,7 +152,8 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
         return PlanOptions(update=cem_update, score=score, params=params, score_params=None if score is None else HipEngine.score_params(*score),
                            constraints=constraints, constraint_params=cparams, knots=knots,
                            knot_params=None if knots is None else HipEngine.knot_params(knots[0], knots[1]), tracking=tracking,
-                           track_params=tparams, target_advance=bool(cem_target_advance), **mppi, **icem)
+                           track_params=tparams, target_advance=bool(cem_target_advance), actuator=actuator, actuator_params=aparams,
+                           action_advance=bool(cem_action_advance), **mppi, **icem)
 
 
 class Shard:
@@ -254,7 +279,8 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
 
 def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
               add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False,
-              update="cem", temperature=1.0, relative=False, score=None, constraints=None, knots=None, phase=None, tracking=None):
+              update="cem", temperature=1.0, relative=False, score=None, constraints=None, knots=None, phase=None, tracking=None, actuator=None,
+              action_advance=False):
     """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
     tests with injected draws and for diagnostics.  update="mppi": the loop of `cadm_mppi_plan` -- the elite ids come from an elite
     refit into copies of mean / var, the distribution from `mppi_refit`.  score: a `HipEngine.score_params` (`cadm_scored_plan`; None: the
@@ -267,7 +293,11 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     iteration's candidates, behind the injections, are shaped onto the grid (`shape_actions`); `return_info` carries the shaped `actions`.
     tracking: (a `HipEngine.track_params`, targets [m,T,K] or [m,K], offset [m] int32 or None) (`cadm_tracking_plan`; None: none) -- every
     rollout then records its trajectories and `tracking_returns` takes the cost off `rows` behind `constrain_returns` (whose first
-    violations it reads in terminate mode) and before the score; `return_info` carries `track_cost` and `rows_untracked`."""
+    violations it reads in terminate mode) and before the score; `return_info` carries `track_cost` and `rows_untracked`.
+    actuator: (a `HipEngine.actuator_params`, prev [m,A], prefix [m,delay,A] or None) (`cadm_actuated_plan`; None: none) -- every
+    iteration's candidates pass `actuate_actions` behind the knot shaping, their cost comes off `cand` behind the score, and the plan takes
+    one more pass with n = 1; `return_info` carries the actuated `actions`, `action_cost` [m,n_it] and `score`, the candidates' score
+    before the subtraction.  action_advance: then prev and prefix are moved on by one step IN PLACE, as the library does."""
     obs = engine._t(obs)
     mean, var = engine._t(init_mean).clone(), engine._t(init_var).clone()
     if knots is not None and knots.spacing == 1:
@@ -295,6 +325,9 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
             engine.icem_inject(actions, mean.clamp(lo, hi).unsqueeze(1).contiguous(), slot0=K)
         if knots is not None:
             engine.shape_actions(actions, knots, phase)
+        action_cost = None
+        if actuator is not None:
+            _, action_cost = engine.actuate_actions(actions, actuator[0], prev=actuator[1], prefix=actuator[2], want_cost=True)
         extra = {}
         if constraints is None and tracking is None:
             rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
@@ -313,6 +346,9 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
                 rows, cost = engine.tracking_returns(traj, untracked, tracking[0], tracking[1], offset=tracking[2], first=first, want_cost=True)
                 extra.update(traj=traj, track_cost=cost, rows_untracked=untracked)
         cand = engine.particle_mean(rows) if score is None else engine.particle_score(rows, score)
+        if actuator is not None:
+            extra.update(action_cost=action_cost, score=cand)
+            cand = cand - action_cost
         if update == "mppi":
             elites = engine.cem_refit(cand.unsqueeze(0), actions, mean.clone(), var.clone(), want_elites=True)
             engine.mppi_refit(cand, actions, mean, var, temperature=temperature, relative=relative)
@@ -328,4 +364,11 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
             info.append(dict(actions=actions, rows=rows, cand=cand, elites=elites, kept=kept, mean=mean.clone(), var=var.clone(), **extra))
     plan_mean = mean.clamp(lo, hi)
     plan = best_seq if return_best else plan_mean
+    if actuator is not None:
+        plan = engine.actuate_actions(plan.clone(), actuator[0], prev=actuator[1], prefix=actuator[2])
+        if action_advance:
+            d = actuator[0].delay
+            actuator[1].copy_(plan[:, 0])
+            if d > 0:
+                actuator[2].copy_(plan[:, 1:1 + d])
     return (plan, info, dict(best_ret=best_ret, best_seq=best_seq, plan_mean=plan_mean)) if return_info else plan

@@ -528,6 +528,66 @@ int cadm_tracking_plan(cadm_ctx* ctx, const cadm_track_params* track, const floa
                        const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m,
                        int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
 
+/* Actuator model (no reference twin, OPT-IN): what the device that executes a plan can do with it -- an action delay (a committed
+ * prefix), per-dim rate limits, and a per-dim cost on the change of the action.  It acts on action sequences [m,n,H,A] (H, A and the box
+ * [lb, ub] the ctx's), never on trajectories.
+ * Parameters: delay d, 0 <= d < H;  per action dim a a rate limit delta_a > 0 (+inf: none) and a rate-cost weight w_a, finite, >= 0.
+ * Device state, per env mi (float32, NaN = absent, as in cadm_tracking_returns' targets):
+ *   prev[mi, a]       the action applied immediately before the plan's step 0; NaN: unknown.            [m,A], or NULL: all NaN
+ *   prefix[mi, j, a]  j < d: the action already committed for the plan's step j; NaN: that step is free.  [m,d,A], or NULL: all NaN
+ * Any per-env pattern can be pinned by writing values and NaNs into prefix (a latch for the rest of a knot segment, say).
+ * Actuate, IN PLACE, an independent chain per (env, candidate, action dim), steps ascending, every operation rounded to float32:
+ *   last = prev[mi,a]
+ *   for t in 0 .. H-1:
+ *       x = u[t]
+ *       if t < d and prefix[mi,t,a] is not NaN:     y = prefix[mi,t,a]                      (a fact: neither limited nor clipped)
+ *       elif delta_a is finite and last is not NaN:  y = clip(clip(x, last - delta_a, last + delta_a), lb, ub)
+ *       else:                                        y = x
+ *       if last is not NaN:                          c_a += w_a * (y - last)^2              (pinned steps count too)
+ *       u[t] = y;  last = y
+ *   cost[mi,c] = ((c_0 + c_1) + c_2) + ...   (ascending a)
+ * clip(x, lo, hi) = min(max(x, lo), hi) by comparisons: v = x < lo ? lo : x;  v > hi ? hi : v -- a NaN x stays NaN.  last - delta_a and
+ * last + delta_a are one rounding each; the difference, the square, the product and each add of the cost are one rounding each (nothing
+ * is fused): the new sequences are reproducible bit for bit in numpy float32.  With last inside the box both bounds hold; with last
+ * outside it (a prev the caller reports from outside) the box wins.  Actuate is idempotent bit for bit.  With d = 0, every delta = +inf
+ * and every w = 0 it copies its input and the cost is 0.  A chain is one thread's and a candidate's dims are added by one thread
+ * (csrc/actuator.hip), no floating-point atomics: nothing depends on the grid, on m or n, or on the row's position.
+ * cadm_actuate_actions: seqs_io [m,n,H,A], n the packed candidate count of the buffer; cost_out [m,n], or NULL.  No workspace.
+ * n_dims: the number of action dims the arrays were filled for, or 0 when every entry holds the same broadcast value.
+ * Refusals, before any HIP call: CADM_EINVAL for a delay outside [0, H), a limit that is <= 0 or NaN, a cost that is negative or not
+ * finite, n_dims that is neither 0 nor A, A > CADM_MAX_ACT_DIMS, a discrete ctx (cartpole), a candidate-sharded ctx. */
+#define CADM_MAX_ACT_DIMS 32
+typedef struct cadm_actuator_params {
+    int32_t delay;                          /* d: 0 .. H-1 */
+    int32_t n_dims;                         /* 0, or the ctx's A */
+    float rate_limit[CADM_MAX_ACT_DIMS];    /* > 0; +inf: none */
+    float rate_w[CADM_MAX_ACT_DIMS];        /* finite, >= 0 */
+} cadm_actuator_params;
+int cadm_actuate_actions(cadm_ctx* ctx, const cadm_actuator_params* params, const float* prev, const float* prefix, int m, int n,
+                         float* seqs_io, float* cost_out, void* stream);
+/* The loop of cadm_tracking_plan under an actuator model.  Per iteration: sampler -> kept-elite injection -> add_mean_last injection ->
+ * knot shaping -> ACTUATE (the iteration's n_it candidates in place, their cost into the workspace) -> rollout -> constraints ->
+ * tracking -> score -> cand[mi,c] = cand[mi,c] - cost[mi,c] -> the refit (elite or MPPI), track-best, keep.  Everything behind actuate
+ * sees feasible sequences: the rollout, the elites, the tracked best, the kept elites and the carry.  The cost is deterministic per
+ * candidate, so it comes off the candidate score and not off the particle rows: a risk score of the returns is unaffected by it; a
+ * non-finite score stays non-finite.  A mean of feasible sequences (the elite mean, the MPPI weighted mean) is feasible only up to
+ * rounding, so the plan is written to the workspace, takes one more actuate pass with n = 1 there, and is then written to plan_out
+ * (which may be pinned host memory): the returned plan obeys pins and limits exactly as defined above.  For return_best that pass is a
+ * bitwise no-op.  advance != 0: behind the plan, on the same stream, prev_io <- plan[:,0] and prefix_io[:,j] <- plan[:,1+j] for j < d.
+ * prev_io [m,A] is required, prefix_io [m,d,A] with d > 0.
+ * params NULL: exactly the launches of cadm_tracking_plan (prev_io, prefix_io and advance are not looked at).  Refusals: those of
+ * cadm_tracking_plan and of cadm_actuate_actions.
+ * workspace: cadm_actuated_workspace_bytes(ctx, m, n, K, mppi, traj, terminate) with params set -- traj != 0: with constraints or
+ * tracking terms (the trajectory view); terminate != 0: tracking terms under TERMINATE constraints -- that is the loop underneath's plus
+ * the cost [m,n] and the plan copy [m,H,A] (0 for bad arguments); with params NULL that of cadm_tracking_plan. */
+size_t cadm_actuated_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int traj, int terminate);
+int cadm_actuated_plan(cadm_ctx* ctx, const cadm_actuator_params* params, float* prev_io, float* prefix_io, int advance,
+                       const cadm_track_params* track, const float* targets, int T, const int32_t* offset, const cadm_knot_params* knots,
+                       const int32_t* phase, const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
+                       const cadm_mppi_params* mppi_params, const float* obs, const float* cp_obs, const float* cp_act,
+                       const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                       uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
+
 /* One training step = sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
