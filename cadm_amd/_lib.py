@@ -110,6 +110,16 @@ class ActuatorParams(C.Structure):      # include/cadm_hip.h cadm_actuator_param
     _fields_ = [("delay", C.c_int32), ("n_dims", C.c_int32), ("rate_limit", C.c_float * MAX_ACT_DIMS), ("rate_w", C.c_float * MAX_ACT_DIMS)]
 
 
+MAX_UNC_DIMS = 128                                                         # CADM_MAX_UNC_DIMS
+UNC_KINDS = {"epistemic": 0, "total": 1}                                   # CADM_UNC_EPISTEMIC / CADM_UNC_TOTAL
+UNC_FORMS = {"var": 0, "std": 1}                                           # CADM_UNC_VAR / CADM_UNC_STD
+
+
+class UncertaintyParams(C.Structure):   # include/cadm_hip.h cadm_uncertainty_params
+    _fields_ = [("kind", C.c_int32), ("form", C.c_int32), ("weight", C.c_float), ("cap", C.c_float), ("n_dims", C.c_int32),
+                ("w", C.c_float * MAX_UNC_DIMS)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -176,6 +186,11 @@ SIGNATURES = {
     "cadm_actuated_plan": (_i, [_P, C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P,
                                 C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i,
                                 _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_uncertainty_cost": (_i, [_P, C.POINTER(UncertaintyParams), _P, _P, _i, _i, _P, _P, _P]),
+    "cadm_uncertain_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i]),
+    "cadm_uncertain_plan": (_i, [_P, C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P,
+                                 C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P,
+                                 _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

@@ -11,7 +11,8 @@
 // also rewrites the particle returns under state constraints (constrain.hip) before the score sees them; cadm_knot_plan also shapes every
 // iteration's candidates onto a grid of knot steps (knots.hip) before the rollout sees them; cadm_tracking_plan also takes the cost of
 // run-time tracking targets (tracking.hip) off the particle returns, behind the constraints and before the score; cadm_actuated_plan also
-// passes every iteration's candidates, and the plan, through an actuator model (actuator.hip: action delay, rate limits, rate cost).
+// passes every iteration's candidates, and the plan, through an actuator model (actuator.hip: action delay, rate limits, rate cost);
+// cadm_uncertain_plan also prices the ensemble's disagreement about the states a candidate visits (uncertainty.hip), off the candidate score.
 #include <math.h>
 
 #include "planner.h"
@@ -296,9 +297,11 @@ struct IcemWs {
     float* traj;                     // constrained or tracked only: the rollout's trajectories [H, m, n, p, D], the last view of every loop before the
                                      // actuated one (the sums before it stay)
     float *acost, *aplan;            // actuated only, behind traj: the candidates' rate cost [m, n]; the plan [m, H, A] before its last actuate pass
+    float *ustep, *ucost;            // uncertainty term only, behind everything else: the step costs u [m, n, H]; the candidates' cost [m, n]
 };
 
-static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0, int first = 0, int act = 0) {
+static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0, int first = 0, int act = 0,
+                         int unc = 0) {
     Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
     IcemWs t{};
@@ -323,6 +326,10 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
     if (act) {
         t.acost = c.take<float>((size_t)m * n);
         t.aplan = c.take<float>((size_t)m * HA);
+    }
+    if (unc) {
+        t.ustep = c.take<float>((size_t)m * n * ctx->H);
+        t.ucost = c.take<float>((size_t)m * n);
     }
     if (w) *w = t;
     return c.off;
@@ -353,6 +360,11 @@ extern "C" size_t cadm_actuated_workspace_bytes(cadm_ctx* ctx, int m, int n, int
     return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, traj != 0, traj != 0 && terminate != 0, 1);
 }
 
+extern "C" size_t cadm_uncertain_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, 1);
+}
+
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
 static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     double v = floor((double)n / pow(decay, (double)it));
@@ -373,13 +385,17 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 // device; null = none, and today's launches.  With it every iteration's candidates are actuated in place behind the knot shaping, their
 // rate cost comes off the candidate score behind cadm_particle_score, and the plan is actuated once more (n = 1) on a device copy before
 // it is written to plan_out; advance: then prev <- plan[:, 0], prefix[:, j] <- plan[:, 1 + j].
+// unc: an uncertainty term (uncertainty.hip); null = none, and today's launches.  With it every rollout records its trajectories, TERMINATE
+// constraints hand their first violations on (with or without terms), and lambda times the cost of the counted steps comes off the
+// candidate score behind the actuator's: a statistic OVER the particles, so not off the particle rows.
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                      float* best_return_out, void* stream, const cadm_constraint_params* constraints = nullptr,
                      const cadm_knot_params* knots = nullptr, const int32_t* phase = nullptr, const cadm_track_params* terms = nullptr,
                      const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr, const cadm_actuator_params* act = nullptr,
-                     float* prev_io = nullptr, float* prefix_io = nullptr, int advance = 0) {
+                     float* prev_io = nullptr, float* prefix_io = nullptr, int advance = 0,
+                     const cadm_uncertainty_params* unc = nullptr) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -403,13 +419,16 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if ((rc = cadm_actuator_check(ctx, act, who))) return rc;
         CADM_REQUIRE(prev_io && (act->delay == 0 || prefix_io), "%s: the actuator model needs prev [m, A], and prefix [m, delay, A] with a delay", who);
     }
+    if (unc && (rc = cadm_uncertainty_check(ctx, unc, who))) return rc;
     const bool shape = knots && knots->spacing > 1;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    // (w.traj: null without constraints and terms; w.first: null unless terms follow TERMINATE constraints)
-    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || terms != nullptr,
-               terms != nullptr && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr);
+    // (w.traj: null without constraints, terms and an uncertainty term; w.first: null unless terms or an uncertainty term follow TERMINATE
+    // constraints)
+    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || terms != nullptr || unc != nullptr,
+               (terms != nullptr || unc != nullptr) && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr,
+               unc != nullptr);
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
@@ -451,6 +470,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if ((rc = cadm_particle_score(ctx, w.rows, m, ni, score, w.cand, stream))) return rc;      // (the mean: cadm_particle_mean itself)
         // the cost is deterministic per candidate: it comes off the candidate score, not off the particle rows
         if (act && (rc = cadm_launch_actuator_sub(w.cand, w.acost, (size_t)m * ni, s))) return rc;
+        // so is the ensemble's disagreement about the states: cand -= lambda * ucost, of this iteration's ni packed candidates
+        if (unc && (rc = cadm_launch_uncertainty(ctx, unc, w.traj, w.first, m, ni, w.ustep, w.ucost, w.cand, s))) return rc;
         // the refitted mean, clipped (dynamics.py:365-366); actuated: into the workspace, for its last pass
         float* plan = (last && !prm->return_best) ? (act ? w.aplan : plan_out) : nullptr;
         if (!upd.mppi) {
@@ -565,4 +586,21 @@ extern "C" int cadm_actuated_plan(cadm_ctx* ctx, const cadm_actuator_params* act
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
                      advance);
+}
+
+// the outermost of the nest: with the ensemble's disagreement about the states a candidate visits (uncertainty.hip) priced off the candidate
+// score, behind the actuator's cost and before the refit; unc null: cadm_actuated_plan's launches
+extern "C" int cadm_uncertain_plan(cadm_ctx* ctx, const cadm_uncertainty_params* unc, const cadm_actuator_params* act, float* prev_io,
+                                   float* prefix_io, int advance, const cadm_track_params* track, const float* targets, int T,
+                                   const int32_t* offset, const cadm_knot_params* knots, const int32_t* phase,
+                                   const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
+                                   const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
+                                   const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                                   uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_uncertain_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_uncertain_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_uncertain_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
+                     advance, unc);
 }

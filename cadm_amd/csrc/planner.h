@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -90,6 +90,13 @@ int cadm_launch_actuate(cadm_ctx* ctx, const cadm_actuator_params* act, const fl
 int cadm_launch_actuator_sub(float* cand, const float* cost, size_t total, hipStream_t s);
 int cadm_launch_actuator_advance(cadm_ctx* ctx, const cadm_actuator_params* act, const float* plan, float* prev, float* prefix, int m,
                                  hipStream_t s);
+// uncertainty.hip: the refusals of an uncertainty term (an unknown kind or form, a lambda that is not finite, a cap <= 0 or NaN, a weight
+// negative or not finite, every weight 0, weights built for another D, D beyond their capacity, a discrete / sharded ctx, a p * D tile beyond
+// the kernel's LDS), before any HIP call; and the two launches behind a rollout's traj [H, m, n, p, D] (n the PACKED candidate count; first
+// [m, n, p] or null): u into step [m, n, H], the cost of the counted steps into cost [m, n], and with cand [m, n]: cand -= lambda * cost
+int cadm_uncertainty_check(const cadm_ctx* ctx, const cadm_uncertainty_params* unc, const char* who);
+int cadm_launch_uncertainty(cadm_ctx* ctx, const cadm_uncertainty_params* unc, const float* traj, const int32_t* first, int m, int n,
+                            float* step, float* cost, float* cand, hipStream_t s);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

@@ -54,6 +54,11 @@ Differences a caller can see (all opt-in except the first):
     steps per env on the device and moves them on after every planned call (`cem_action_advance=False`: the caller does, with
     `set_applied_actions`), `reset_plan_carry` forgets them; `actuator_state()`; `action_cost(actions)`: what the model makes of given
     plans.  Any of the three alone takes the opt-in route;
+  * `cem_uncertainty=dict(kind="epistemic" | "total", weight=lambda, w=None | float | [D] | "delta_std", form="var" | "std", cap=None)`:
+    the ensemble's disagreement about the states a candidate visits, per step, as a cost (lambda > 0) or a bonus (lambda < 0) in that
+    loop's candidate score (INTEGRATION.md "Pricing model uncertainty"); `w="delta_std"` weighs every dim by 1 / sigma_delta^2 of the
+    current normalisation statistics (picked up again after every `fit`), `set_uncertainty_weights(w)` replaces the weights at run time,
+    `uncertainty_cost(obs, actions, ...)`: what the term makes of given plans.  It alone takes the opt-in route;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -234,6 +239,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_action_rate_limit=None,
                  cem_action_rate_cost=None,
                  cem_action_advance=True,
+                 cem_uncertainty=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -300,7 +306,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      cem_tracking=cem_tracking, cem_target_advance=cem_target_advance,
                                                      cem_action_delay=cem_action_delay, cem_action_rate_limit=cem_action_rate_limit,
                                                      cem_action_rate_cost=cem_action_rate_cost, cem_action_advance=cem_action_advance,
-                                                     n_forwards=n_forwards, action_dim=None if self.discrete else self.action_space_dims)
+                                                     n_forwards=n_forwards, action_dim=None if self.discrete else self.action_space_dims,
+                                                     cem_uncertainty=cem_uncertainty, obs_dim=obs_space_dims)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
@@ -348,8 +355,66 @@ class MLPEnsembleCEMDynamicsModel(object):
         if self._stats_dirty:
             keys = ("obs_mean", "obs_std", "act_mean", "act_std", "delta_mean", "delta_std", "cp_obs_mean",
                     "cp_obs_std", "cp_act_mean", "cp_act_std", "back_delta_mean", "back_delta_std")
-            self.engine.set_stats(dict(zip(keys, self._stats12())))
+            stats = self._stats12()
+            self.engine.set_stats(dict(zip(keys, stats)))
             self._stats_dirty = False
+            opt = getattr(self, "_opt", None)
+            if opt is not None and opt.uncertainty is not None and opt.uncertainty[2] == "delta_std":
+                # the spread in units of the model's own one-step target scale: w_d = 1 / (sigma_delta_d + 1e-10)^2 of THESE statistics
+                sd = np.asarray(stats[5], dtype=np.float64).reshape(-1) + 1e-10
+                self._set_uncertainty_w((1.0 / (sd * sd)).astype(np.float32))
+
+    def _set_uncertainty_w(self, w):
+        kind, lam, _, form, cap = self._opt.uncertainty
+        self._opt = self._opt._replace(uncertainty_params=self.engine.uncertainty_params(kind, lam, w, form, cap, obs_dim=self.obs_space_dims))
+
+    def _require_uncertainty(self, who):
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.uncertainty_params is None:
+            raise ValueError("%s: this model has no cem_uncertainty" % who)
+        return opt
+
+    def set_uncertainty_weights(self, w):
+        """Replace the per-dim weights of `cem_uncertainty` from the next call on: None (1 for every dim), a number, or [D] (finite, >= 0, at
+        least one > 0; dims with 0 are never read).  A model built with w="delta_std" stops following its statistics: the weights are
+        then the caller's."""
+        opt = self._require_uncertainty("set_uncertainty_weights")
+        if isinstance(w, str):
+            raise ValueError("set_uncertainty_weights: w must be None, a number or [D] numbers, got %r" % (w,))
+        kind, lam, _, form, cap = opt.uncertainty
+        key = None if w is None else (float(w) if np.ndim(w) == 0 else tuple(float(x) for x in np.asarray(w).reshape(-1)))
+        self._opt = opt._replace(uncertainty=(kind, lam, key, form, cap))
+        self._set_uncertainty_w(w)
+
+    def uncertainty_cost(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
+        """What this model's `cem_uncertainty` term makes of `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) -- the companion of
+        `tracking_cost` / `constraint_check`: the context encoder, one rollout that records its trajectories and the uncertainty kernels,
+        as numpy arrays (for [m,H,A] input the n axis is dropped):
+          step [m,n,H]      the step cost u_t (weighted variance or its square root, capped) of every step
+          cost [m,n]        their sum over the counted steps: what the planner multiplies by lambda and takes off the candidate score
+          returns [m,n,p]   the rollout's particle returns: what lambda has to be weighed against
+        If the model has `cem_constraints` in terminate mode their first violations cut the sum, as in the loop.  The noise is drawn as
+        `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        self._require_uncertainty("uncertainty_cost")
+        self._push_stats()
+        opt = self._opt
+        cp_obs, cp_act = self._rollout_inputs("uncertainty_cost", obs, actions, cp_obs, cp_act)
+        eng = self.engine
+        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        acts = (acts[:, None] if squeeze else acts).contiguous()
+        obs = eng._t(obs)
+        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        first = None
+        if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
+            _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
+        step, cost = eng.uncertainty_cost(traj, opt.uncertainty_params, first=first, want_steps=True)
+        res = dict(step=step.cpu().numpy(), cost=cost.cpu().numpy(), returns=rows.cpu().numpy())
+        if squeeze:
+            res = {k: v[:, 0] for k, v in res.items()}
+        return res
 
     def _next_call(self):
         self._call += 1

@@ -49,6 +49,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """What this model's `cem_tracking` terms cost `actions` against the current targets (see the CaDM class; a vanilla model has no history)."""
         return super().tracking_cost(obs, actions, None, None, seed=seed)
 
+    def uncertainty_cost(self, obs, actions, seed=None):
+        """What this model's `cem_uncertainty` term makes of `actions` (see the CaDM class; a vanilla model has no history)."""
+        return super().uncertainty_cost(obs, actions, None, None, seed=seed)
+
     def predict(self, obs, act, return_std=False):
         return super().predict(obs, act, None, None, return_std=return_std)
 

@@ -560,10 +560,11 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return, traj=False, track=None, act=False):
+                   want_best_return, traj=False, track=None, act=False, unc=None):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
         `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
-        workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop); act: the workspace of an actuated loop."""
+        workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop); act: the workspace of an actuated loop;
+        unc: None, or the (terminate, actuator) of a loop with an uncertainty term, whose slot it is."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -572,7 +573,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -585,7 +586,11 @@ class HipEngine:
         [m,delay,A]: the envs' actuator state, moved on in place when the options say so), `tracking_plan` when it holds tracking terms (targets [m,T,K] or [m,K],
         target_offset [m] int32 or None = 0), `knot_plan` when it holds knots (phase: the envs' grid phases [m] int32, None = 0),
         `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
-        Arguments as `icem_plan` behind its params."""
+        Arguments as `icem_plan` behind its params.  First of all `uncertain_plan`, when it holds an uncertainty term."""
+        if getattr(opt, "uncertainty_params", None) is not None:
+            return self.uncertain_plan(opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix, opt.action_advance, opt.track_params,
+                                       targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params,
+                                       *args, **kw)
         if opt.actuator_params is not None:
             return self.actuated_plan(opt.actuator_params, act_prev, act_prefix, opt.action_advance, opt.track_params, targets, target_offset,
                                       opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params, *args, **kw)
@@ -600,18 +605,24 @@ class HipEngine:
             return self.scored_plan(opt.score_params, opt.params, *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
-    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False):
+    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
         constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that).  track: None,
         or whether a tracked loop runs under TERMINATE constraints -- the tracking slot (`cadm_tracking_workspace_bytes`: the trajectory
         view, and the first-violation view in front of it under TERMINATE).  act: an actuated loop's slot (`cadm_actuated_workspace_bytes`:
-        the loop underneath's views, and behind them the candidates' rate cost and the plan's device copy)."""
+        the loop underneath's views, and behind them the candidates' rate cost and the plan's device copy).  unc: None, or (terminate,
+        actuator) -- the slot of a loop with an uncertainty term (`cadm_uncertain_workspace_bytes`: always with the trajectory view, the
+        first-violation view under TERMINATE constraints, the actuator's views, and behind everything the step costs and the cost)."""
         slot = (bool(mppi), bool(traj)) if track is None else (bool(mppi), "track", bool(track))
         if act:
             slot = slot + ("act",)
+        if unc is not None:
+            slot = (bool(mppi), "unc", bool(unc[0]), bool(unc[1]))
         key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            if act:
+            if unc is not None:
+                nbytes = self.lib.cadm_uncertain_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(unc[0])), int(bool(unc[1])))
+            elif act:
                 nbytes = self.lib.cadm_actuated_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(traj) or track is not None),
                                                                 int(bool(track)))
             elif track is not None:
@@ -1032,6 +1043,112 @@ class HipEngine:
         return self._loop_plan("actuated_plan", self.lib.cadm_actuated_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None,
                                track=None if track is None else terminate, act=True)
+
+    # ------------------------------------------------------------------ pricing model uncertainty (opt-in; csrc/uncertainty.hip)
+    @staticmethod
+    def uncertainty_params(kind, weight, w=None, form="var", cap=None, obs_dim=None):
+        """`cadm_uncertainty_params`: kind -- "epistemic" (the biased variance of the member means) or "total" (of the particles), a name
+        or its CADM_UNC_* number; weight -- lambda, finite, any sign (> 0: a penalty on disagreement, < 0: a bonus); w -- None (1 for every
+        dim), a scalar or [D]: the weight of each observation dim's variance, finite and >= 0 with at least one > 0 (dims with 0 are never
+        read); form -- "var" (the weighted variance per step) or "std" (its square root); cap -- None (none) or a bound > 0 on the step
+        cost.  An array must have `obs_dim` entries when that is given, at most `_lib.MAX_UNC_DIMS` anyway; the library checks it against
+        the engine's D.  Needs no GPU."""
+        def pick(val, table, what):
+            if isinstance(val, str) and val in table:
+                return table[val]
+            if not isinstance(val, (bool, str)) and isinstance(val, (int, np.integer)) and int(val) in table.values():
+                return int(val)
+            raise ValueError("uncertainty %s must be %s, got %r" % (what, " or ".join(repr(k) for k in table), val))
+        prm = _lib.UncertaintyParams()
+        prm.kind, prm.form = pick(kind, _lib.UNC_KINDS, "kind"), pick(form, _lib.UNC_FORMS, "form")
+        try:
+            lam = float(np.float32(weight))
+        except (TypeError, ValueError):
+            raise ValueError("uncertainty weight must be a finite number, got %r" % (weight,)) from None
+        if isinstance(weight, bool) or not math.isfinite(lam):
+            raise ValueError("uncertainty weight must be a finite number, got %r" % (weight,))
+        try:
+            cp = math.inf if cap is None else float(np.float32(cap))
+        except (TypeError, ValueError):
+            raise ValueError("uncertainty cap must be None or a number > 0, got %r" % (cap,)) from None
+        if not cp > 0.0:
+            raise ValueError("uncertainty cap must be None or a number > 0, got %r" % (cap,))
+        if obs_dim is not None and not 1 <= int(obs_dim) <= _lib.MAX_UNC_DIMS:
+            raise ValueError("the uncertainty term holds up to %d observation dims, got %r" % (_lib.MAX_UNC_DIMS, obs_dim))
+        try:
+            arr = np.asarray(1.0 if w is None else w, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("uncertainty w must be None, a number or a list of them, got %r" % (w,)) from None
+        if arr.ndim > 1 or (arr.ndim == 1 and not 1 <= arr.shape[0] <= _lib.MAX_UNC_DIMS):
+            raise ValueError("uncertainty w must be a scalar or [D] with D <= %d, got shape %r" % (_lib.MAX_UNC_DIMS, arr.shape))
+        if arr.ndim == 1 and obs_dim is not None and arr.shape[0] != int(obs_dim):
+            raise ValueError("uncertainty w has %d entries, expected %d (one per observation dim)" % (arr.shape[0], int(obs_dim)))
+        if not bool(np.all(np.isfinite(arr) & (arr >= 0.0))):
+            raise ValueError("uncertainty w must be finite and >= 0, got %r" % (w,))
+        if not bool(np.any(arr > 0.0)):
+            raise ValueError("uncertainty w must be > 0 for at least one observation dim, got %r" % (w,))
+        prm.weight, prm.cap, prm.n_dims = lam, cp, 0 if arr.ndim == 0 else int(arr.shape[0])
+        full = np.zeros((_lib.MAX_UNC_DIMS,), np.float32)
+        full[:max(1, prm.n_dims)] = arr
+        for k in range(_lib.MAX_UNC_DIMS):
+            prm.w[k] = float(full[k])
+        return prm
+
+    def uncertainty_cost(self, traj, params, first=None, want_steps=False):
+        """`cadm_uncertainty_cost` on device tensors: traj [H,m,n,p,D] (a rollout's `traj_out`) -> cost [m,n], the step costs of
+        `params` (`uncertainty_params`) added over the counted steps; with want_steps (step [m,n,H], cost): u_t of every step, counted
+        or not.  first [m,n,p] int32 (None: every step counts): `constrain_returns`' first_violation -- steps behind the smallest one of a
+        candidate's particles are not counted.  lambda is not applied."""
+        traj = self._t(traj)
+        if traj.dim() != 5 or not traj.is_contiguous():
+            raise ValueError("uncertainty_cost: traj %r: expected contiguous [H,m,n,p,D]" % (tuple(traj.shape),))
+        H, m, n, p, D = traj.shape
+        if (H, p, D) != (self.H, self.p, self.D):
+            raise ValueError("uncertainty_cost: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (tuple(traj.shape), self.H, self.p, self.D))
+        if first is not None:
+            first = self._t(first, dtype=torch.int32)
+            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
+                raise ValueError("uncertainty_cost: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
+        step = torch.empty((m, n, H), dtype=torch.float32, device=self.device) if want_steps else None
+        cost = torch.empty((m, n), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_uncertainty_cost(self._ctx, ct.byref(params), ptr(traj), ptr(first), m, n, ptr(step), ptr(cost), self.stream),
+                    "cadm_uncertainty_cost")
+        return (step, cost) if want_steps else cost
+
+    def uncertain_plan(self, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score, params, obs,
+                       cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None, want_best_return=False):
+        """`cadm_uncertain_plan`: the loop of `actuated_plan` with lambda times the uncertainty cost of `uncertainty`
+        (`uncertainty_params`; None = none, and `actuated_plan`'s launches) taken off every iteration's candidate scores, behind the
+        actuator's cost and before the refit.  Arguments behind `uncertainty` as `actuated_plan`; the workspace is the slot of
+        `cadm_uncertain_workspace_bytes`, cached apart from the others."""
+        if uncertainty is None:
+            return self.actuated_plan(actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score, params, obs,
+                                      cp_obs, cp_act, init_mean, init_var, n, carry=carry, carry_valid=carry_valid, seed=seed, call=call, out=out,
+                                      want_best_return=want_best_return)
+        mppi, params = self._as_mppi_params(params)
+        m = int(np.shape(obs)[0])
+        if actuator is None:
+            prev = prefix = None
+        else:
+            for name, t in (("prev", prev), ("prefix", prefix)):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+                    raise ValueError("uncertain_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
+            if prev is None or (prefix is None and actuator.delay > 0):
+                raise ValueError("uncertain_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
+            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "uncertain_plan")
+        phase = self._phase(phase, m, "uncertain_plan")
+        T = 0
+        if track is None:
+            targets = offset = None
+        else:
+            targets, T, offset = self._targets(targets, offset, m, track.n, "uncertain_plan")
+        head = (ct.byref(uncertainty), None if actuator is None else ct.byref(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
+                None if track is None else ct.byref(track), ptr(targets), T, ptr(offset), None if knots is None else ct.byref(knots), ptr(phase),
+                None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi), ct.byref(params))
+        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
+        return self._loop_plan("uncertain_plan", self.lib.cadm_uncertain_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return,
+                               unc=(terminate, actuator is not None))
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

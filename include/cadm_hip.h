@@ -588,7 +588,72 @@ int cadm_actuated_plan(cadm_ctx* ctx, const cadm_actuator_params* params, float*
                        const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                        uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
 
-/* One training step = sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
+/* Pricing model uncertainty (no reference twin, OPT-IN): a cost, or with a negative weight a bonus, on the ensemble's disagreement about
+ * the STATES a candidate's plan visits, per step -- cadm_forecast_stats' var_epistemic / var_total as a term of the candidate score.
+ * (cadm_score_params' MEMBER_STD is not this: it measures disagreement about the summed reward, is blind to every observation dim the
+ * reward does not read, and sees nothing of a disagreement that cancels over the horizon.)
+ * For a candidate (env mi, candidate c), a step t and an observation dim d with weight w_d > 0, over x_j = traj[t,mi,c,j,d] (traj
+ * [H,m,n,p,D]: a rollout's traj_out; particle j belongs to member j / q, q = p / E; H, p, E, D the ctx's), the variance is formed by
+ * the chain of cadm_forecast_stats, every operation rounded to float32 and nothing fused:
+ *   x0  = x_0
+ *   s_e = sum_{j<q} (x_{e q + j} - x0)        j ascending, from 0.0f        (e = 0 .. E-1)
+ *   tot = sum_e s_e                           e ascending, from 0.0f
+ *   md  = tot / (float)p
+ *   CADM_UNC_TOTAL:      var = sum_j ((x_j - x0) - md)^2   j ascending;   v = var / (float)p
+ *   CADM_UNC_EPISTEMIC:  de = s_e / (float)q - md;  epi = sum_e de*de   e ascending;   v = epi / (float)E
+ * so a one-hot w reproduces cadm_forecast_stats' var_total / var_epistemic bit for bit.  The step cost is
+ *   u_t = sum_d w_d * v[t,d]   over the dims with w_d > 0, ascending d, from the first such term (one product and one add per dim);
+ *   form CADM_UNC_STD: u_t = sqrtf(u_t);     then  u_t = u_t > cap ? cap : u_t   (a comparison, not fminf: NaN stays NaN; +inf: no cap)
+ * and the candidate's cost is  cost[mi,c] = sum_t u_t  over the COUNTED steps, in step order, from 0.0f: every step 0 .. H-1, or with
+ * first [m,n,p] (cadm_constrain_returns' first_violation, TERMINATE mode) the steps t <= min_j first[mi,c,j] -- the step at which the
+ * first particle leaves still counts, as it does for the reward and for tracking; behind it the particles are a mix of dead and live
+ * ones, and whatever traj holds there never reaches the cost.  Dims with w_d == 0 are never read.  A non-finite value in a weighted dim
+ * at a counted step makes u_t and the cost non-finite by the arithmetic above; an overflowed, infinite u_t is a value like any other.
+ * A planner with weight < 0 (a bonus) should set a cap: an unbounded bonus rewards a diverging rollout.
+ * Every v, every u_t and every cost is one thread's chain (csrc/uncertainty.hip), no floating-point atomics: nothing depends on the
+ * grid, on m or n, or on the candidate's position; the same bits run to run and inside any batch.
+ * cadm_uncertainty_cost: n the packed candidate count of traj; step_out [m,n,H] (u_t of EVERY step, counted or not) or NULL -- the same
+ * cost_out bits either way; cost_out [m,n].  No workspace.  Rank-local arithmetic, but refused on a candidate-sharded ctx, like
+ * cadm_tracking_returns.  `weight` (lambda) is not applied here: it is what cadm_uncertain_plan multiplies the cost by.
+ * Refusals, before any HIP call: CADM_EINVAL for an unknown kind or form, a weight that is not finite, a cap that is NaN or <= 0, a w
+ * that is negative, NaN or infinite, all w zero, n_dims that is neither 0 nor D, D > CADM_MAX_UNC_DIMS, a discrete ctx (cartpole), a
+ * candidate-sharded ctx, a p * D tile beyond the kernel's LDS budget (p * D + 2 D floats, each count rounded up to 4, above 48 KiB). */
+#define CADM_MAX_UNC_DIMS 128
+#define CADM_UNC_EPISTEMIC 0
+#define CADM_UNC_TOTAL 1
+#define CADM_UNC_VAR 0
+#define CADM_UNC_STD 1
+typedef struct cadm_uncertainty_params {
+    int32_t kind, form;              /* CADM_UNC_EPISTEMIC | CADM_UNC_TOTAL;  CADM_UNC_VAR | CADM_UNC_STD */
+    float weight;                    /* lambda: finite, any sign (> 0: a penalty, < 0: a bonus) */
+    float cap;                       /* > 0; +inf: none */
+    int32_t n_dims;                  /* 0: w[0] for every dim; else the ctx's D */
+    float w[CADM_MAX_UNC_DIMS];      /* finite, >= 0, at least one > 0 */
+} cadm_uncertainty_params;
+int cadm_uncertainty_cost(cadm_ctx* ctx, const cadm_uncertainty_params* params, const float* traj, const int32_t* first, int m, int n,
+                          float* step_out, float* cost_out, void* stream);
+/* The loop of cadm_actuated_plan with that cost in the candidate score.  Every iteration's rollout records its trajectories, as it does
+ * for constraints and tracking terms; TERMINATE constraints write their first violations into the workspace with or without tracking
+ * terms.  Per iteration: rollout -> constraints -> tracking -> cadm_particle_score -> the actuator's cand -= cost ->
+ * cand[mi,c] = cand[mi,c] - weight * cost[mi,c] (one multiply, one subtract; n_it, the iteration's packed candidate count) -> the
+ * refit (elite or MPPI) -> track-best -> keep.  The cost is a statistic over the particles, so it comes off the candidate score, not off
+ * the particle rows: a risk score of the returns is unaffected by it.  The elites, the tracked best, best_return_out, the kept elites
+ * and the carry are by the final score; a candidate whose cost is not finite meets them as a diverged rollout's does.
+ * params NULL: exactly the launches of cadm_actuated_plan.  Refusals: those of cadm_actuated_plan and of cadm_uncertainty_cost.
+ * workspace: cadm_uncertain_workspace_bytes(ctx, m, n, K, mppi, terminate, actuator) with params set -- terminate != 0: TERMINATE
+ * constraints; actuator != 0: an actuator model -- that is the loop underneath's WITH the trajectory view (and under TERMINATE the
+ * first-violation view), and behind everything else u [m,n,H] and the cost [m,n] (0 for bad arguments); with params NULL that of
+ * cadm_actuated_plan. */
+size_t cadm_uncertain_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator);
+int cadm_uncertain_plan(cadm_ctx* ctx, const cadm_uncertainty_params* params, const cadm_actuator_params* actuator, float* prev_io,
+                        float* prefix_io, int advance, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                        const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                        const cadm_score_params* score, int update, const cadm_mppi_params* mppi_params, const float* obs,
+                        const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                        int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                        float* best_return_out, void* stream);
+
+/* One training step =sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
  * registered master weights.  train != 0 applies the update; train == 0 only evaluates the losses
