@@ -120,6 +120,14 @@ class UncertaintyParams(C.Structure):   # include/cadm_hip.h cadm_uncertainty_pa
                 ("w", C.c_float * MAX_UNC_DIMS)]
 
 
+MAX_VALUE_LAYERS, MAX_VALUE_WIDTH, MAX_VALUE_DIMS = 4, 512, 128            # CADM_MAX_VALUE_LAYERS / _WIDTH / _DIMS
+VALUE_ACTS = {"relu": 0, "tanh": 1, "swish": 2}                            # CADM_VALUE_RELU / _TANH / _SWISH
+
+
+class ValueParams(C.Structure):         # include/cadm_hip.h cadm_value_params
+    _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_VALUE_LAYERS), ("activation", C.c_int32), ("weight", C.c_float)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -191,6 +199,13 @@ SIGNATURES = {
     "cadm_uncertain_plan": (_i, [_P, C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P,
                                  C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P,
                                  _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_set_value_net": (_i, [_P, C.POINTER(ValueParams), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
+    "cadm_value_eval": (_i, [_P, _P, _i, _P, _P]),
+    "cadm_value_returns": (_i, [_P, C.POINTER(ValueParams), _P, _P, _i, _i, _P, _P, _P, _P]),
+    "cadm_valued_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i]),
+    "cadm_valued_plan": (_i, [_P, C.POINTER(ValueParams), C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i,
+                              C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams),
+                              _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

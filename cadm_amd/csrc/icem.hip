@@ -12,7 +12,8 @@
 // iteration's candidates onto a grid of knot steps (knots.hip) before the rollout sees them; cadm_tracking_plan also takes the cost of
 // run-time tracking targets (tracking.hip) off the particle returns, behind the constraints and before the score; cadm_actuated_plan also
 // passes every iteration's candidates, and the plan, through an actuator model (actuator.hip: action delay, rate limits, rate cost);
-// cadm_uncertain_plan also prices the ensemble's disagreement about the states a candidate visits (uncertainty.hip), off the candidate score.
+// cadm_uncertain_plan also prices the ensemble's disagreement about the states a candidate visits (uncertainty.hip), off the candidate score;
+// cadm_valued_plan also adds a caller-supplied value net's V of every particle's last state (value.hip) to the particle returns.
 #include <math.h>
 
 #include "planner.h"
@@ -365,6 +366,11 @@ extern "C" size_t cadm_uncertain_workspace_bytes(cadm_ctx* ctx, int m, int n, in
     return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, 1);
 }
 
+extern "C" size_t cadm_valued_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0);
+}
+
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
 static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     double v = floor((double)n / pow(decay, (double)it));
@@ -388,6 +394,9 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 // unc: an uncertainty term (uncertainty.hip); null = none, and today's launches.  With it every rollout records its trajectories, TERMINATE
 // constraints hand their first violations on (with or without terms), and lambda times the cost of the counted steps comes off the
 // candidate score behind the actuator's: a statistic OVER the particles, so not off the particle rows.
+// value: a terminal value (value.hip) of the net registered with cadm_set_value_net; null = none, and today's launches.  With it every
+// rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * V(traj[H - 1]) is added to the
+// particle rows behind the constraints and the tracking terms and before the score: a risk-aware score sees return + value per particle.
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
@@ -395,7 +404,7 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
                      const cadm_knot_params* knots = nullptr, const int32_t* phase = nullptr, const cadm_track_params* terms = nullptr,
                      const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr, const cadm_actuator_params* act = nullptr,
                      float* prev_io = nullptr, float* prefix_io = nullptr, int advance = 0,
-                     const cadm_uncertainty_params* unc = nullptr) {
+                     const cadm_uncertainty_params* unc = nullptr, const cadm_value_params* value = nullptr) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -420,15 +429,17 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         CADM_REQUIRE(prev_io && (act->delay == 0 || prefix_io), "%s: the actuator model needs prev [m, A], and prefix [m, delay, A] with a delay", who);
     }
     if (unc && (rc = cadm_uncertainty_check(ctx, unc, who))) return rc;
+    if (value && (rc = cadm_value_plan_check(ctx, value, who))) return rc;
     const bool shape = knots && knots->spacing > 1;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    // (w.traj: null without constraints, terms and an uncertainty term; w.first: null unless terms or an uncertainty term follow TERMINATE
-    // constraints)
-    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || terms != nullptr || unc != nullptr,
-               (terms != nullptr || unc != nullptr) && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr,
-               unc != nullptr);
+    // (w.traj: null without constraints, terms, an uncertainty term and a value; w.first: null unless terms, an uncertainty term or a value
+    // follow TERMINATE constraints)
+    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || terms != nullptr || unc != nullptr || value != nullptr,
+               (terms != nullptr || unc != nullptr || value != nullptr) && constraints != nullptr &&
+                   constraints->mode == CADM_CONSTRAIN_TERMINATE,
+               act != nullptr, unc != nullptr);
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
@@ -467,6 +478,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if (constraints && (rc = cadm_constrain_returns(ctx, constraints, w.traj, obs, w.actions, w.rows, m, ni, w.rows, w.first, nullptr,
                                                         stream))) return rc;
         if (terms && (rc = cadm_tracking_returns(ctx, terms, w.traj, targets, T, offset, w.first, w.rows, m, ni, w.rows, nullptr, stream))) return rc;
+        // what lies behind the horizon: rows += weight * V(last state), of this iteration's ni packed candidates
+        if (value && (rc = cadm_launch_value(ctx, value, w.traj, w.first, m, ni, w.rows, s))) return rc;
         if ((rc = cadm_particle_score(ctx, w.rows, m, ni, score, w.cand, stream))) return rc;      // (the mean: cadm_particle_mean itself)
         // the cost is deterministic per candidate: it comes off the candidate score, not off the particle rows
         if (act && (rc = cadm_launch_actuator_sub(w.cand, w.acost, (size_t)m * ni, s))) return rc;
@@ -603,4 +616,22 @@ extern "C" int cadm_uncertain_plan(cadm_ctx* ctx, const cadm_uncertainty_params*
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
                      advance, unc);
+}
+
+// the outermost of the nest: with weight * V of every particle's last state (value.hip, the net of cadm_set_value_net) added to the
+// particle returns, behind the constraints and the tracking terms and before the score; value null: cadm_uncertain_plan's launches
+extern "C" int cadm_valued_plan(cadm_ctx* ctx, const cadm_value_params* value, const cadm_uncertainty_params* unc,
+                                const cadm_actuator_params* act, float* prev_io, float* prefix_io, int advance,
+                                const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                                const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                                const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs, const float* cp_obs,
+                                const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io,
+                                int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out,
+                                void* stream) {
+    CADM_REQUIRE(prm, "cadm_valued_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_valued_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_valued_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
+                     advance, unc, value);
 }

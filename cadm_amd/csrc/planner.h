@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -97,6 +97,13 @@ int cadm_launch_actuator_advance(cadm_ctx* ctx, const cadm_actuator_params* act,
 int cadm_uncertainty_check(const cadm_ctx* ctx, const cadm_uncertainty_params* unc, const char* who);
 int cadm_launch_uncertainty(cadm_ctx* ctx, const cadm_uncertainty_params* unc, const float* traj, const int32_t* first, int m, int n,
                             float* step, float* cost, float* cand, hipStream_t s);
+// value.hip: the refusals of a terminal value (null parameters, a layer count outside 0 .. 4, a width outside 1 .. 512, an unknown
+// activation, a weight that is not finite, D beyond the net's input dims, a discrete / sharded ctx, activation tiles beyond the LDS; no
+// registered net: CADM_ESTATE; parameters that do not describe the registered net), before any HIP call; and the launch behind a rollout's
+// traj [H, m, n, p, D] (n the PACKED candidate count; first [m, n, p] or null): rows[q] += weight * V(traj[H - 1, q]) in place
+int cadm_value_plan_check(const cadm_ctx* ctx, const cadm_value_params* value, const char* who);
+int cadm_launch_value(cadm_ctx* ctx, const cadm_value_params* value, const float* traj, const int32_t* first, int m, int n, float* rows,
+                      hipStream_t s);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

@@ -59,6 +59,12 @@ Differences a caller can see (all opt-in except the first):
     loop's candidate score (INTEGRATION.md "Pricing model uncertainty"); `w="delta_std"` weighs every dim by 1 / sigma_delta^2 of the
     current normalisation statistics (picked up again after every `fit`), `set_uncertainty_weights(w)` replaces the weights at run time,
     `uncertainty_cost(obs, actions, ...)`: what the term makes of given plans.  It alone takes the opt-in route;
+  * `cem_terminal_value=dict(hidden_sizes=(256, 256), activation="relu" | "tanh" | "swish", weight=1.0)`: a value net V on the last
+    state of every particle in that loop, so that a candidate is scored by return + weight * V(s_H) (INTEGRATION.md "Terminal value").
+    The kwarg declares the net's shape; `set_terminal_value(weights, obs_mean=None, obs_std=None)` hands over a critic at run time (a
+    list of (W [in,out], b [out]) or a torch.nn.Sequential), as often as it is retrained and with nothing rebuilt,
+    `clear_terminal_value()` removes it, `terminal_value(states)` evaluates V through the planner's kernel,
+    `plan_terminal_value(obs, actions, ...)`: what the term adds for given plans.  It alone takes the opt-in route;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -240,6 +246,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_action_rate_cost=None,
                  cem_action_advance=True,
                  cem_uncertainty=None,
+                 cem_terminal_value=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -307,7 +314,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      cem_action_delay=cem_action_delay, cem_action_rate_limit=cem_action_rate_limit,
                                                      cem_action_rate_cost=cem_action_rate_cost, cem_action_advance=cem_action_advance,
                                                      n_forwards=n_forwards, action_dim=None if self.discrete else self.action_space_dims,
-                                                     cem_uncertainty=cem_uncertainty, obs_dim=obs_space_dims)
+                                                     cem_uncertainty=cem_uncertainty, obs_dim=obs_space_dims,
+                                                     cem_terminal_value=cem_terminal_value)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
@@ -320,6 +328,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         self._plan_phase = None                               # device tensor [m] int32: the knot grid's phase (cem_knot_anchor="episode")
         self._targets = self._target_offset = None            # device tensors [m,T,K] float32 / [m] int32 (cem_tracking): `set_targets`
         self._act_prev = self._act_prefix = None              # device tensors [m,A] / [m,delay,A] float32, NaN = unknown (the actuator model)
+        self._value_set = False                               # whether the engine holds a value net (cem_terminal_value): `set_terminal_value`
 
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
@@ -567,6 +576,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         if self._opt.actuator_params is not None:      # first call, or another number of envs: nothing applied, nothing committed; the
             self._actuator_tensors(m)                  # library moves both on behind the plan, on the engine's stream (cem_action_advance)
             extra.update(act_prev=self._act_prev, act_prefix=self._act_prefix)
+        if self._opt.value_params is not None and not self._value_set:
+            raise RuntimeError("get_action: this model plans under cem_terminal_value and has no value net (call set_terminal_value first)")
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
@@ -706,6 +717,65 @@ class MLPEnsembleCEMDynamicsModel(object):
         res = dict(cost=cost.cpu().numpy(), returns=rows.cpu().numpy(), returns_untracked=raw.cpu().numpy())
         if squeeze:
             res = {k: v[:, 0] for k, v in res.items()}
+        return res
+
+    # ------------------------------------------------------------------ terminal value (INTEGRATION.md "Terminal value")
+    def _require_value(self, who, need_net=False):
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.value_params is None:
+            raise ValueError("%s: this model has no cem_terminal_value" % who)
+        if need_net and not self._value_set:
+            raise RuntimeError("%s: this model has no value net (call set_terminal_value first)" % who)
+        return opt
+
+    def set_terminal_value(self, weights, obs_mean=None, obs_std=None):
+        """The value net of `cem_terminal_value` from the next call on: `weights` a list of (W [in,out], b [out]) per layer, numpy or
+        torch, or a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules (Linear.weight is transposed on import) -- of the
+        declared layer sizes and activation, else it is refused; obs_mean / obs_std [D] (None: 0 / 1, std finite and > 0): the net reads
+        (obs - obs_mean) / obs_std of the raw observation.  Everything is copied: a later edit of the caller's tensors changes no plan.
+        Replacing the net rebuilds nothing."""
+        opt = self._require_value("set_terminal_value")
+        self.engine.set_value_net(opt.value_params, weights, obs_mean=obs_mean, obs_std=obs_std)
+        self._value_set = True
+
+    def clear_terminal_value(self):
+        """Remove the value net: get_action on a model with `cem_terminal_value` then raises until `set_terminal_value` is called."""
+        self._require_value("clear_terminal_value")
+        self.engine.set_value_net(None)
+        self._value_set = False
+
+    def terminal_value(self, states):
+        """V of raw observations `states` [..., D] (numpy or tensor) through the planner's kernel -> numpy [...]; NaN for a state with a
+        non-finite value."""
+        self._require_value("terminal_value", need_net=True)
+        return self.engine.value_eval(states).cpu().numpy()
+
+    def plan_terminal_value(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
+        """What this model's terminal value adds for `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) -- the companion of
+        `tracking_cost`: the context encoder, one rollout that records its trajectories and the value kernel, as numpy arrays (for [m,H,A]
+        input the n axis is dropped):
+          value [m,n,p]     V of every particle's last state (NaN: a diverged particle, or one the constraints ended before the horizon);
+                            the planner adds weight * value to the particle's return
+          first [m,n,p]     with `cem_constraints` in terminate mode their first violations (a particle with first < H gets no value), else None
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        opt = self._require_value("plan_terminal_value", need_net=True)
+        self._push_stats()
+        cp_obs, cp_act = self._rollout_inputs("plan_terminal_value", obs, actions, cp_obs, cp_act)
+        eng = self.engine
+        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        acts = (acts[:, None] if squeeze else acts).contiguous()
+        obs = eng._t(obs)
+        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        first = None
+        if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
+            _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
+        _, v = eng.value_returns(traj, rows, opt.value_params, first=first, want_v=True)
+        res = dict(value=v.cpu().numpy(), first=None if first is None else first.cpu().numpy())
+        if squeeze:
+            res = {k: None if x is None else x[:, 0] for k, x in res.items()}
         return res
 
     def _get_action_opt_in(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):

@@ -53,6 +53,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """What this model's `cem_uncertainty` term makes of `actions` (see the CaDM class; a vanilla model has no history)."""
         return super().uncertainty_cost(obs, actions, None, None, seed=seed)
 
+    def plan_terminal_value(self, obs, actions, seed=None):
+        """What this model's `cem_terminal_value` adds for `actions` (see the CaDM class; a vanilla model has no history)."""
+        return super().plan_terminal_value(obs, actions, None, None, seed=seed)
+
     def predict(self, obs, act, return_std=False):
         return super().predict(obs, act, None, None, return_std=return_std)
 

@@ -560,11 +560,12 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return, traj=False, track=None, act=False, unc=None):
+                   want_best_return, traj=False, track=None, act=False, unc=None, val=None):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
         `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
         workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop); act: the workspace of an actuated loop;
-        unc: None, or the (terminate, actuator) of a loop with an uncertainty term, whose slot it is."""
+        unc: None, or the (terminate, actuator) of a loop with an uncertainty term, whose slot it is; val: None, or the (terminate, actuator,
+        uncertainty) of a loop with a terminal value, whose slot it is."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -573,7 +574,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -586,7 +587,12 @@ class HipEngine:
         [m,delay,A]: the envs' actuator state, moved on in place when the options say so), `tracking_plan` when it holds tracking terms (targets [m,T,K] or [m,K],
         target_offset [m] int32 or None = 0), `knot_plan` when it holds knots (phase: the envs' grid phases [m] int32, None = 0),
         `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
-        Arguments as `icem_plan` behind its params.  First of all `uncertain_plan`, when it holds an uncertainty term."""
+        Arguments as `icem_plan` behind its params.  First of all `valued_plan`, when it holds a terminal value, then `uncertain_plan`, when
+        it holds an uncertainty term."""
+        if getattr(opt, "value_params", None) is not None:
+            return self.valued_plan(opt.value_params, opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix, opt.action_advance,
+                                    opt.track_params, targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params,
+                                    opt.params, *args, **kw)
         if getattr(opt, "uncertainty_params", None) is not None:
             return self.uncertain_plan(opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix, opt.action_advance, opt.track_params,
                                        targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params,
@@ -605,22 +611,28 @@ class HipEngine:
             return self.scored_plan(opt.score_params, opt.params, *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
-    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None):
+    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
         constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that).  track: None,
         or whether a tracked loop runs under TERMINATE constraints -- the tracking slot (`cadm_tracking_workspace_bytes`: the trajectory
         view, and the first-violation view in front of it under TERMINATE).  act: an actuated loop's slot (`cadm_actuated_workspace_bytes`:
         the loop underneath's views, and behind them the candidates' rate cost and the plan's device copy).  unc: None, or (terminate,
         actuator) -- the slot of a loop with an uncertainty term (`cadm_uncertain_workspace_bytes`: always with the trajectory view, the
-        first-violation view under TERMINATE constraints, the actuator's views, and behind everything the step costs and the cost)."""
+        first-violation view under TERMINATE constraints, the actuator's views, and behind everything the step costs and the cost).  val:
+        None, or (terminate, actuator, uncertainty) -- the slot of a loop with a terminal value (`cadm_valued_workspace_bytes`)."""
         slot = (bool(mppi), bool(traj)) if track is None else (bool(mppi), "track", bool(track))
         if act:
             slot = slot + ("act",)
         if unc is not None:
             slot = (bool(mppi), "unc", bool(unc[0]), bool(unc[1]))
+        if val is not None:
+            slot = (bool(mppi), "val", bool(val[0]), bool(val[1]), bool(val[2]))
         key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            if unc is not None:
+            if val is not None:
+                nbytes = self.lib.cadm_valued_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(val[0])), int(bool(val[1])),
+                                                              int(bool(val[2])))
+            elif unc is not None:
                 nbytes = self.lib.cadm_uncertain_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(unc[0])), int(bool(unc[1])))
             elif act:
                 nbytes = self.lib.cadm_actuated_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(traj) or track is not None),
@@ -1149,6 +1161,192 @@ class HipEngine:
         return self._loop_plan("uncertain_plan", self.lib.cadm_uncertain_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return,
                                unc=(terminate, actuator is not None))
+
+    # ------------------------------------------------------------------ terminal value (opt-in; csrc/value.hip)
+    @staticmethod
+    def value_params(hidden_sizes=(), activation="relu", weight=1.0):
+        """`cadm_value_params`: hidden_sizes -- the widths h_1 .. h_L of the value net D -> h_1 -> .. -> h_L -> 1, L in 0 ..
+        `_lib.MAX_VALUE_LAYERS` (() is a linear V), each in 1 .. `_lib.MAX_VALUE_WIDTH`; activation -- "relu", "tanh" or "swish" (or its
+        CADM_VALUE_* number), one for the net; weight -- what V is multiplied by before it is added to a return, finite (it carries a
+        discount gamma^H).  Needs no GPU."""
+        try:
+            hs = [hidden_sizes] if isinstance(hidden_sizes, (int, np.integer)) and not isinstance(hidden_sizes, bool) else list(hidden_sizes)
+        except TypeError:
+            raise ValueError("value hidden_sizes must be a sequence of ints, got %r" % (hidden_sizes,)) from None
+        if len(hs) > _lib.MAX_VALUE_LAYERS:
+            raise ValueError("a value net has at most %d hidden layers, got %d" % (_lib.MAX_VALUE_LAYERS, len(hs)))
+        for h in hs:
+            if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or not 1 <= int(h) <= _lib.MAX_VALUE_WIDTH:
+                raise ValueError("a value net's hidden widths must be ints in 1 .. %d, got %r" % (_lib.MAX_VALUE_WIDTH, h))
+        if isinstance(activation, str) and activation in _lib.VALUE_ACTS:
+            act = _lib.VALUE_ACTS[activation]
+        elif not isinstance(activation, (bool, str)) and isinstance(activation, (int, np.integer)) and int(activation) in _lib.VALUE_ACTS.values():
+            act = int(activation)
+        else:
+            raise ValueError("value activation must be %s, got %r" % (" or ".join(repr(k) for k in _lib.VALUE_ACTS), activation))
+        try:
+            w = float(np.float32(weight))
+        except (TypeError, ValueError):
+            raise ValueError("value weight must be a finite number, got %r" % (weight,)) from None
+        if isinstance(weight, bool) or not math.isfinite(w):
+            raise ValueError("value weight must be a finite number, got %r" % (weight,))
+        prm = _lib.ValueParams()
+        prm.n_hidden, prm.activation, prm.weight = len(hs), act, w
+        for l, h in enumerate(hs):
+            prm.hidden[l] = int(h)
+        return prm
+
+    @staticmethod
+    def value_weights(weights):
+        """A value net's layers on the host: `weights` is a list of (W [in,out], b [out]) in numpy or torch, or a `torch.nn.Sequential` of
+        `Linear` modules with `ReLU` / `Tanh` / `SiLU` between them (`Linear.weight` is [out,in]: transposed here).  Returns (the list of
+        (W, b) as contiguous float32 numpy arrays, the activation's name or None when the input does not say).  Needs no GPU."""
+        act = None
+        if isinstance(weights, torch.nn.Module):
+            if not isinstance(weights, torch.nn.Sequential):
+                raise ValueError("a value net module must be a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules, got %r" % (type(weights).__name__,))
+            names = {torch.nn.ReLU: "relu", torch.nn.Tanh: "tanh", torch.nn.SiLU: "swish"}
+            mods, pairs = list(weights), []
+            if not mods or len(mods) % 2 == 0:
+                raise ValueError("a value net Sequential alternates Linear and activation modules and ends with a Linear (got %d modules)" % len(mods))
+            for j, mod in enumerate(mods):
+                if j % 2 == 0:
+                    if not isinstance(mod, torch.nn.Linear) or mod.bias is None:
+                        raise ValueError("value net Sequential: module %d must be a Linear with a bias, got %r" % (j, type(mod).__name__))
+                    pairs.append((mod.weight.detach().t(), mod.bias.detach()))
+                else:
+                    if type(mod) not in names:
+                        raise ValueError("value net Sequential: module %d must be ReLU, Tanh or SiLU, got %r" % (j, type(mod).__name__))
+                    if act is not None and names[type(mod)] != act:
+                        raise ValueError("value net Sequential: one activation for the whole net, got %r and %r" % (act, names[type(mod)]))
+                    act = names[type(mod)]
+            weights = pairs
+        try:
+            items = [(w, b) for w, b in weights]
+        except (TypeError, ValueError):
+            raise ValueError("value net weights must be a list of (W [in,out], b [out]) pairs or a torch.nn.Sequential") from None
+        out = []
+        for l, (w, b) in enumerate(items):
+            w = w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else np.asarray(w)
+            b = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
+            w, b = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+            if w.ndim != 2 or b.ndim != 1 or b.shape[0] != w.shape[1]:
+                raise ValueError("value net layer %d: W %r and b %r, expected [in,out] and [out]" % (l, w.shape, b.shape))
+            if not (np.all(np.isfinite(w)) and np.all(np.isfinite(b))):
+                raise ValueError("value net layer %d holds a weight or a bias that is not finite" % l)
+            out.append((w, b))
+        return out, act
+
+    def set_value_net(self, params, weights=None, obs_mean=None, obs_std=None):
+        """`cadm_set_value_net`: registers the value net that `params` (`value_params`) describes -- `weights` as `value_weights` takes
+        them, the input statistics obs_mean / obs_std [D] (None: 0 / 1; std finite and > 0; 1 / std is formed in float64 and rounded once
+        to float32).  Shapes and finiteness are checked here; the library packs a copy of its own, so a second call replaces the net
+        without touching anything else.  params None: the net is cleared."""
+        if params is None:
+            self._check(self.lib.cadm_set_value_net(self._ctx, None, None, None, None, None, self.stream), "cadm_set_value_net")
+            self._value_src = None
+            return
+        layers, act = self.value_weights(weights)
+        dims = [self.D] + [int(params.hidden[l]) for l in range(params.n_hidden)] + [1]
+        if len(layers) != len(dims) - 1:
+            raise ValueError("set_value_net: %d layers given, the declared net %r has %d" % (len(layers), dims, len(dims) - 1))
+        for l, (w, b) in enumerate(layers):
+            if w.shape != (dims[l], dims[l + 1]):
+                raise ValueError("set_value_net: layer %d is %r, the declared net %r needs %r" % (l, w.shape, dims, (dims[l], dims[l + 1])))
+        if act is not None and _lib.VALUE_ACTS[act] != params.activation:
+            raise ValueError("set_value_net: the module's activation %r is not the declared one" % (act,))
+        mean = np.zeros((self.D,), np.float64) if obs_mean is None else np.asarray(self._host(obs_mean), dtype=np.float64).reshape(-1)
+        std = np.ones((self.D,), np.float64) if obs_std is None else np.asarray(self._host(obs_std), dtype=np.float64).reshape(-1)
+        if mean.shape != (self.D,) or std.shape != (self.D,):
+            raise ValueError("set_value_net: obs_mean %r / obs_std %r, expected [%d]" % (mean.shape, std.shape, self.D))
+        if not np.all(np.isfinite(mean)):
+            raise ValueError("set_value_net: obs_mean must be finite")
+        if not np.all(np.isfinite(std) & (std > 0.0)):
+            raise ValueError("set_value_net: obs_std must be finite and > 0")
+        dev = [(self._t(w), self._t(b)) for w, b in layers]
+        mean_d, inv_d = self._t(mean.astype(np.float32)), self._t((1.0 / std).astype(np.float32))
+        nl = len(dev)
+        Wp, bp = (ct.c_void_p * nl)(*[w.data_ptr() for w, _ in dev]), (ct.c_void_p * nl)(*[b.data_ptr() for _, b in dev])
+        self._check(self.lib.cadm_set_value_net(self._ctx, ct.byref(params), Wp, bp, ptr(mean_d), ptr(inv_d), self.stream), "cadm_set_value_net")
+        self._value_src = (dev, mean_d, inv_d)      # (kept until the next net: the copy is enqueued, not done)
+
+    @staticmethod
+    def _host(x):
+        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
+
+    def value_eval(self, states):
+        """`cadm_value_eval`: V of states [..., D] -> [...] (device tensors), through the planner's kernel."""
+        states = self._t(states)
+        if states.dim() < 1 or states.shape[-1] != self.D:
+            raise ValueError("value_eval: states %r, expected [..., %d]" % (tuple(states.shape), self.D))
+        flat = states.reshape(-1, self.D).contiguous()
+        if flat.shape[0] < 1:
+            raise ValueError("value_eval: no states")
+        v = torch.empty((flat.shape[0],), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_value_eval(self._ctx, ptr(flat), int(flat.shape[0]), ptr(v), self.stream), "cadm_value_eval")
+        return v.reshape(states.shape[:-1])
+
+    def value_returns(self, traj, rows, params, first=None, want_v=False, out=None):
+        """`cadm_value_returns` on device tensors: traj [H,m,n,p,D] (a rollout's `traj_out`), rows [m,n,p] -> rows + weight * V(traj[H-1])
+        per row under `params` (`value_params`, describing the registered net).  first [m,n,p] int32 (None: every row):
+        `constrain_returns`' first_violation -- a row with first < H keeps its bits.  want_v: (rows_out, v [m,n,p]), v NaN where skipped.
+        out: where the new rows go (may be `rows` itself)."""
+        traj, rows = self._t(traj), self._t(rows)
+        if traj.dim() != 5 or not traj.is_contiguous():
+            raise ValueError("value_returns: traj %r: expected contiguous [H,m,n,p,D]" % (tuple(traj.shape),))
+        H, m, n, p, D = traj.shape
+        if (H, p, D) != (self.H, self.p, self.D):
+            raise ValueError("value_returns: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (tuple(traj.shape), self.H, self.p, self.D))
+        if tuple(rows.shape) != (m, n, p) or not rows.is_contiguous():
+            raise ValueError("value_returns: rows %r, expected contiguous %r" % (tuple(rows.shape), (m, n, p)))
+        if first is not None:
+            first = self._t(first, dtype=torch.int32)
+            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
+                raise ValueError("value_returns: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
+        if out is None:
+            out = torch.empty_like(rows)
+        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rows.device:
+            raise ValueError("value_returns: out must be a contiguous float32 device tensor %r" % ((m, n, p),))
+        v = torch.empty((m, n, p), dtype=torch.float32, device=self.device) if want_v else None
+        self._check(self.lib.cadm_value_returns(self._ctx, ct.byref(params), ptr(traj), ptr(first), m, n, ptr(rows), ptr(out), ptr(v),
+                                                self.stream), "cadm_value_returns")
+        return (out, v) if want_v else out
+
+    def valued_plan(self, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score, params,
+                    obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None, want_best_return=False):
+        """`cadm_valued_plan`: the loop of `uncertain_plan` with `value.weight` times the registered value net's V of every particle's last
+        state added to the particle returns, behind the constraints and the tracking terms and before the score (`value`: a
+        `value_params` describing the net of `set_value_net`; None = none, and `uncertain_plan`'s launches).  Arguments behind `value` as
+        `uncertain_plan`; the workspace is the slot of `cadm_valued_workspace_bytes`, cached apart from the others."""
+        if value is None:
+            return self.uncertain_plan(uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score,
+                                       params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=carry, carry_valid=carry_valid, seed=seed,
+                                       call=call, out=out, want_best_return=want_best_return)
+        mppi, params = self._as_mppi_params(params)
+        m = int(np.shape(obs)[0])
+        if actuator is None:
+            prev = prefix = None
+        else:
+            for name, t in (("prev", prev), ("prefix", prefix)):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+                    raise ValueError("valued_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
+            if prev is None or (prefix is None and actuator.delay > 0):
+                raise ValueError("valued_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
+            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "valued_plan")
+        phase = self._phase(phase, m, "valued_plan")
+        T = 0
+        if track is None:
+            targets = offset = None
+        else:
+            targets, T, offset = self._targets(targets, offset, m, track.n, "valued_plan")
+        head = (ct.byref(value), None if uncertainty is None else ct.byref(uncertainty), None if actuator is None else ct.byref(actuator),
+                ptr(prev), ptr(prefix), int(bool(advance)), None if track is None else ct.byref(track), ptr(targets), T, ptr(offset),
+                None if knots is None else ct.byref(knots), ptr(phase), None if constraints is None else ct.byref(constraints),
+                None if score is None else ct.byref(score), int(mppi), ct.byref(params))
+        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
+        return self._loop_plan("valued_plan", self.lib.cadm_valued_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act, init_mean,
+                               init_var, n, carry, carry_valid, seed, call, out, want_best_return,
+                               val=(terminate, actuator is not None, uncertainty is not None))
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

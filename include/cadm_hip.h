@@ -653,6 +653,64 @@ int cadm_uncertain_plan(cadm_ctx* ctx, const cadm_uncertainty_params* params, co
                         int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                         float* best_return_out, void* stream);
 
+/* Terminal value (no reference twin, OPT-IN): a caller-supplied value net V on the LAST state of every particle's trajectory, so that a
+ * plan is scored by  return + weight * V(s_H)  and sees beyond its H steps (POLO, LOOP, TD-MPC).  `weight` carries a discount gamma^H.
+ * V is an MLP  D -> h_1 -> .. -> h_L -> 1,  L = n_hidden in 0 .. CADM_MAX_VALUE_LAYERS (0: a linear V), every width in
+ * 1 .. CADM_MAX_VALUE_WIDTH, one hidden activation for the net, a linear output, D <= CADM_MAX_VALUE_DIMS.  For a state s [D], all in
+ * float32 (csrc/value.hip):
+ *   x_k = (s_k - mean_k) * std_inv_k                                        one subtract, one multiply
+ *   layer with K inputs, unit u:  acc = b[u];  for k = 0 .. K4-1 ascending:  acc = fmaf(W[k][u], x_k, acc)
+ *       (K4: K rounded up to 4; W and x are exact zeros for K <= k < K4; the bias seeds the accumulator)
+ *   hidden:  CADM_VALUE_RELU max(z, 0) | CADM_VALUE_TANH tanhf(z) | CADM_VALUE_SWISH z / (1 + expf(-z));   output: the sum itself.
+ * A state with any non-finite value has V = NaN, set explicitly.  V of a state is one chain in ascending k, no floating-point
+ * atomics: the same bits run to run, in any batch, at any row position, for any m or n, from cadm_value_eval as from the planner.
+ * cadm_set_value_net: W[l] [in,out] row-major and b[l] [out] (l = 0 .. n_hidden), mean [D] and std_inv [D] are DEVICE pointers; they are
+ * copied and packed into memory the ctx owns, on `stream` -- the caller may free its tensors afterwards.  A second call replaces the
+ * net; params NULL clears it.  params->weight is not kept: every call below brings its own.
+ * cadm_value_eval: v_out[r] = V(states[r]) for states [R,D].
+ * cadm_value_returns: for row q of rows [m,n,p] with the terminal state traj[H-1,q,:] (traj [H,m,n,p,D]: a rollout's traj_out, n its
+ * packed candidate count):  rows_out[q] = rows_in[q] + weight * V  (one multiply, then one add, no fma; a NaN V gives a NaN return, as a
+ * diverged rollout's is).  With first [m,n,p] (cadm_constrain_returns' first_violation, TERMINATE mode) a row with first[q] < H keeps its
+ * input bits and its terminal state is not read: an ended episode has no future.  rows_out may alias rows_in.  v_out [m,n,p] or NULL:
+ * V of every row, NaN for the rows `first` skipped.  params must describe the registered net (layer count, widths, activation), else
+ * CADM_EINVAL; no registered net: CADM_ESTATE.
+ * Refusals, before any HIP call: CADM_EINVAL for null pointers, n_hidden outside 0 .. 4, a width outside 1 .. 512, an unknown
+ * activation, a weight that is not finite, D > CADM_MAX_VALUE_DIMS, a discrete ctx (cartpole), a candidate-sharded ctx, activation
+ * tiles (two regions of 16 rows x the widest layers, each width rounded up to 4) beyond the 160 KiB of LDS. */
+#define CADM_MAX_VALUE_LAYERS 4
+#define CADM_MAX_VALUE_WIDTH 512
+#define CADM_MAX_VALUE_DIMS 128
+#define CADM_VALUE_RELU 0
+#define CADM_VALUE_TANH 1
+#define CADM_VALUE_SWISH 2
+typedef struct cadm_value_params {
+    int32_t n_hidden;                          /* L: 0 .. CADM_MAX_VALUE_LAYERS */
+    int32_t hidden[CADM_MAX_VALUE_LAYERS];     /* h_1 .. h_L, each 1 .. CADM_MAX_VALUE_WIDTH */
+    int32_t activation;                        /* CADM_VALUE_RELU | CADM_VALUE_TANH | CADM_VALUE_SWISH */
+    float weight;                              /* finite */
+} cadm_value_params;
+int cadm_set_value_net(cadm_ctx* ctx, const cadm_value_params* params, const float* const* W, const float* const* b, const float* mean,
+                       const float* std_inv, void* stream);
+int cadm_value_eval(cadm_ctx* ctx, const float* states, int R, float* v_out, void* stream);
+int cadm_value_returns(cadm_ctx* ctx, const cadm_value_params* params, const float* traj, const int32_t* first, int m, int n,
+                       const float* rows_in, float* rows_out, float* v_out, void* stream);
+/* The loop of cadm_uncertain_plan with that term in the particle returns.  Every iteration's rollout records its trajectories;
+ * TERMINATE constraints write their first violations into the workspace.  Per iteration: rollout -> constraints -> tracking ->
+ * rows[q] += weight * V(traj[H-1,q]) on the particle rows [m,n_it,p] -> cadm_particle_score (a risk-aware score sees return + value per
+ * particle) -> the actuator's and the uncertainty term's costs off the candidate score, unchanged -> the refit.  PENALTY constraints do
+ * not gate the value.  params NULL: exactly the launches of cadm_uncertain_plan.  Refusals: those of cadm_uncertain_plan and of
+ * cadm_value_returns.  workspace: cadm_valued_workspace_bytes(ctx, m, n, K, mppi, terminate, actuator, uncertainty) with params set --
+ * the loop underneath's WITH the trajectory view, and under TERMINATE constraints the first-violation view (0 for bad arguments); with
+ * params NULL that of cadm_uncertain_plan. */
+size_t cadm_valued_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty);
+int cadm_valued_plan(cadm_ctx* ctx, const cadm_value_params* params, const cadm_uncertainty_params* uncertainty,
+                     const cadm_actuator_params* actuator, float* prev_io, float* prefix_io, int advance, const cadm_track_params* track,
+                     const float* targets, int T, const int32_t* offset, const cadm_knot_params* knots, const int32_t* phase,
+                     const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
+                     const cadm_mppi_params* mppi_params, const float* obs, const float* cp_obs, const float* cp_act,
+                     const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n, uint32_t seed,
+                     uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
+
 /* One training step =sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
