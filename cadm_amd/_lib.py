@@ -128,6 +128,15 @@ class ValueParams(C.Structure):         # include/cadm_hip.h cadm_value_params
     _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_VALUE_LAYERS), ("activation", C.c_int32), ("weight", C.c_float)]
 
 
+MAX_REWARD_DIMS = 256                                                      # CADM_MAX_REWARD_DIMS
+REWARD_INPUTS = {"next_obs": 0, "obs_act": 1, "obs_act_next_obs": 2}       # CADM_REWARD_NEXT_OBS / _OBS_ACT / _OBS_ACT_NEXT_OBS
+
+
+class RewardParams(C.Structure):        # include/cadm_hip.h cadm_reward_params (the layer conventions are the value net's)
+    _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_VALUE_LAYERS), ("activation", C.c_int32), ("inputs", C.c_int32),
+                ("weight", C.c_float)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -206,6 +215,15 @@ SIGNATURES = {
     "cadm_valued_plan": (_i, [_P, C.POINTER(ValueParams), C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i,
                               C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams),
                               _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_set_reward_net": (_i, [_P, C.POINTER(RewardParams), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
+    "cadm_reward_eval": (_i, [_P, _P, _i, _P, _P]),
+    "cadm_reward_workspace_bytes": (C.c_size_t, [_P, _i, _i]),
+    "cadm_reward_returns": (_i, [_P, C.POINTER(RewardParams), _P, _P, _P, _P, _i, _i, _P, _P, _P, _P, _P, _P]),
+    "cadm_rewarded_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i]),
+    "cadm_rewarded_plan": (_i, [_P, C.POINTER(RewardParams), C.POINTER(ValueParams), C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams),
+                                _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams),
+                                C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P,
+                                _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

@@ -27,7 +27,7 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_HID_LIST 200              // the reference default --hidden_size (run_cadm_pets.py:129)
 #endif
 // bumped whenever cadm_ctx / RolloutArgs change: a side module built against another layout is refused
-#define CADM_CTX_LAYOUT_TAG 3007
+#define CADM_CTX_LAYOUT_TAG 3008
 
 #define CADM_CHECK_HIP(expr)                                                                   \
     do {                                                                                       \
@@ -102,6 +102,7 @@ struct NormStats {  // device copies of the 12 stat vectors + derived
 struct TrainState;  // train.hip
 struct RolloutArgs;  // rollout_args.h
 struct ValueNet;  // value.hip
+struct RewardNet;  // reward.hip
 
 struct cadm_ctx {
     cadm_config cfg;
@@ -170,6 +171,8 @@ struct cadm_ctx {
     size_t mppi_scratch_floats = 0;
     // the registered terminal value net (cadm_set_value_net, value.hip): a packed copy the ctx owns; null before the first one
     ValueNet* value = nullptr;
+    // the registered reward net (cadm_set_reward_net, reward.hip): likewise
+    RewardNet* reward = nullptr;
 };
 
 // Entry points launch on the ctx's device whatever device the caller's thread has current (two engines on different GPUs in
@@ -201,6 +204,7 @@ int cadm_launch_context(cadm_ctx* ctx, const float* cp_obs, const float* cp_act,
                         float* out, hipStream_t s, int force_batched = 0);
 void cadm_train_free(cadm_ctx* ctx);
 void cadm_value_free(cadm_ctx* ctx);      // value.hip
+void cadm_reward_free(cadm_ctx* ctx);     // reward.hip
 // (developer library: dev/dev_api.hip) Adam moment buffers of one trained tensor; layer as in cadm_set_weights, is_bias 0 / 1;
 // layer == -1 / -2: max_logvar / min_logvar of the forward net.  Returns null pointers before cadm_train_configure, and CADM_EINVAL
 // for a net id that is not one of CADM_NET_FF / BACK / CTX or a layer the net does not have.

@@ -13,7 +13,8 @@
 // run-time tracking targets (tracking.hip) off the particle returns, behind the constraints and before the score; cadm_actuated_plan also
 // passes every iteration's candidates, and the plan, through an actuator model (actuator.hip: action delay, rate limits, rate cost);
 // cadm_uncertain_plan also prices the ensemble's disagreement about the states a candidate visits (uncertainty.hip), off the candidate score;
-// cadm_valued_plan also adds a caller-supplied value net's V of every particle's last state (value.hip) to the particle returns.
+// cadm_valued_plan also adds a caller-supplied value net's V of every particle's last state (value.hip) to the particle returns;
+// cadm_rewarded_plan also adds a caller-supplied reward net's R of every step of every particle (reward.hip) to the particle returns.
 #include <math.h>
 
 #include "planner.h"
@@ -298,11 +299,12 @@ struct IcemWs {
     float* traj;                     // constrained or tracked only: the rollout's trajectories [H, m, n, p, D], the last view of every loop before the
                                      // actuated one (the sums before it stay)
     float *acost, *aplan;            // actuated only, behind traj: the candidates' rate cost [m, n]; the plan [m, H, A] before its last actuate pass
-    float *ustep, *ucost;            // uncertainty term only, behind everything else: the step costs u [m, n, H]; the candidates' cost [m, n]
+    float *ustep, *ucost;            // uncertainty term only, behind everything before: the step costs u [m, n, H]; the candidates' cost [m, n]
+    float* rstep;                    // learned reward only, behind everything else: the step rewards [H, m, n, p]
 };
 
 static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0, int first = 0, int act = 0,
-                         int unc = 0) {
+                         int unc = 0, int rew = 0) {
     Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
     IcemWs t{};
@@ -332,6 +334,7 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
         t.ustep = c.take<float>((size_t)m * n * ctx->H);
         t.ucost = c.take<float>((size_t)m * n);
     }
+    if (rew) t.rstep = c.take<float>((size_t)ctx->H * m * n * ctx->p);
     if (w) *w = t;
     return c.off;
 }
@@ -371,6 +374,11 @@ extern "C" size_t cadm_valued_workspace_bytes(cadm_ctx* ctx, int m, int n, int K
     return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0);
 }
 
+extern "C" size_t cadm_rewarded_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0, 1);
+}
+
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
 static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     double v = floor((double)n / pow(decay, (double)it));
@@ -397,6 +405,9 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 // value: a terminal value (value.hip) of the net registered with cadm_set_value_net; null = none, and today's launches.  With it every
 // rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * V(traj[H - 1]) is added to the
 // particle rows behind the constraints and the tracking terms and before the score: a risk-aware score sees return + value per particle.
+// reward: a learned step reward (reward.hip) of the net registered with cadm_set_reward_net; null = none, and today's launches.  With it
+// every rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * (the sum of R over the
+// counted steps) is added to the particle rows behind the constraints and the tracking terms and IN FRONT OF the terminal value.
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
@@ -404,7 +415,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
                      const cadm_knot_params* knots = nullptr, const int32_t* phase = nullptr, const cadm_track_params* terms = nullptr,
                      const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr, const cadm_actuator_params* act = nullptr,
                      float* prev_io = nullptr, float* prefix_io = nullptr, int advance = 0,
-                     const cadm_uncertainty_params* unc = nullptr, const cadm_value_params* value = nullptr) {
+                     const cadm_uncertainty_params* unc = nullptr, const cadm_value_params* value = nullptr,
+                     const cadm_reward_params* reward = nullptr) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -430,16 +442,17 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     }
     if (unc && (rc = cadm_uncertainty_check(ctx, unc, who))) return rc;
     if (value && (rc = cadm_value_plan_check(ctx, value, who))) return rc;
+    if (reward && (rc = cadm_reward_plan_check(ctx, reward, who))) return rc;
     const bool shape = knots && knots->spacing > 1;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    // (w.traj: null without constraints, terms, an uncertainty term and a value; w.first: null unless terms, an uncertainty term or a value
-    // follow TERMINATE constraints)
-    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || terms != nullptr || unc != nullptr || value != nullptr,
-               (terms != nullptr || unc != nullptr || value != nullptr) && constraints != nullptr &&
-                   constraints->mode == CADM_CONSTRAIN_TERMINATE,
-               act != nullptr, unc != nullptr);
+    // (w.traj: null without constraints, terms, an uncertainty term, a value and a reward; w.first: null unless terms, an uncertainty term,
+    // a value or a reward follow TERMINATE constraints)
+    const bool reads_traj = terms != nullptr || unc != nullptr || value != nullptr || reward != nullptr;
+    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || reads_traj,
+               reads_traj && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr, unc != nullptr,
+               reward != nullptr);
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
@@ -478,6 +491,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if (constraints && (rc = cadm_constrain_returns(ctx, constraints, w.traj, obs, w.actions, w.rows, m, ni, w.rows, w.first, nullptr,
                                                         stream))) return rc;
         if (terms && (rc = cadm_tracking_returns(ctx, terms, w.traj, targets, T, offset, w.first, w.rows, m, ni, w.rows, nullptr, stream))) return rc;
+        // what the env's own reward does not say: rows += weight * (the sum of R over the counted steps), of this iteration's ni packed candidates
+        if (reward && (rc = cadm_launch_reward(ctx, reward, w.traj, obs, w.actions, w.first, m, ni, w.rows, w.rstep, s))) return rc;
         // what lies behind the horizon: rows += weight * V(last state), of this iteration's ni packed candidates
         if (value && (rc = cadm_launch_value(ctx, value, w.traj, w.first, m, ni, w.rows, s))) return rc;
         if ((rc = cadm_particle_score(ctx, w.rows, m, ni, score, w.cand, stream))) return rc;      // (the mean: cadm_particle_mean itself)
@@ -634,4 +649,22 @@ extern "C" int cadm_valued_plan(cadm_ctx* ctx, const cadm_value_params* value, c
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
                      advance, unc, value);
+}
+
+// the outermost of the nest: with weight * (the sum over the counted steps of R, reward.hip, the net of cadm_set_reward_net) added to the
+// particle returns, behind the constraints and the tracking terms and in front of the terminal value; reward null: cadm_valued_plan's launches
+extern "C" int cadm_rewarded_plan(cadm_ctx* ctx, const cadm_reward_params* reward, const cadm_value_params* value,
+                                  const cadm_uncertainty_params* unc, const cadm_actuator_params* act, float* prev_io, float* prefix_io,
+                                  int advance, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                                  const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                                  const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs,
+                                  const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                                  int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                                  float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_rewarded_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_rewarded_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_rewarded_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
+                     advance, unc, value, reward);
 }

@@ -1,0 +1,214 @@
+// What the caller-supplied nets of the opt-in planner share (value.hip: the terminal value; reward.hip: the learned step reward): an MLP
+// K -> h_1 -> .. -> h_L -> 1 evaluated transposed on the fp32 matrix pipe -- activations resident in LDS as [unit][row], rows as the B / D
+// columns of v_mfma_f32_16x16x4_f32, weights from a ctx-owned packed copy through a register ring -- and the packed copy itself.  Each of
+// the two files is its own translation unit: everything here but MlpNet has internal linkage.
+//
+// Arithmetic of one row through one layer with K inputs (all fp32, nothing fused but the MFMA's own multiply-add):
+//   acc = b_u;  for k = 0 .. K4-1 ascending: acc = fma(W[k][u], x_k, acc)      K4 = K rounded up to 4
+//   (the MFMA adds its 4 products in ascending k onto the accumulator, as context.hip relies on; the bias SEEDS the accumulator; for
+//   K <= k < K4 both W and x are exact zeros)
+//   hidden: relu max(z, 0), tanhf(z), or swish z / (1 + expf(-z));  output: linear.
+// A workgroup of 4 waves owns 16 * RT consecutive rows (RT = 1 or 2) and takes them through every layer.  A layer's 64-unit groups go
+// to the waves (all row tiles each, so a weight fragment is used RT times); with fewer groups than waves the (group, row tile) pairs do.
+// (Four row tiles were built and measured for reward.hip and lost to one and two at every width: see its header.)
+// Packed weights: per layer [group of 64 units][k-step][lane][4], so that the A operands of FOUR 16-unit tiles (tile t = units {64 g + 4 i + t}) are one 16-byte load per lane and a wave's k-step is
+// 1 KiB contiguous; K is zero-padded to 4 and the units to 64 there, the biases to 64.  Activation units behind N up to the next multiple
+// of 4 are written as exact zeros.  With two row tiles the rows of odd k are stored with bit 4 flipped, so that the two k of a
+// half-wave's B read fall into different banks.  A row's result is one column's chain in ascending k, the same instruction sequence
+// wherever the row sits and whichever wave takes it: nothing depends on RT or on the grid.
+#pragma once
+#include <math.h>
+
+#include "planner.h"
+
+constexpr int MLP_THREADS = 256;
+constexpr int MLP_WAVES = 4;
+constexpr int MLP_PF = 6;                    // k-steps of weight fragments in flight per wave
+constexpr int MLP_LDS_MAX = 160 * 1024;      // the CU's LDS; above 64 KiB a kernel's dynamic-LDS attribute is raised
+constexpr int MLP_NL = CADM_MAX_VALUE_LAYERS + 1;
+
+// a ctx-owned packed copy of a registered net
+struct MlpNet {
+    bool set = false;
+    float* buf = nullptr;          // one allocation: mean, inv_std, then per layer the packed weights and the padded biases
+    size_t cap = 0;                // floats allocated
+    float *mean = nullptr, *istd = nullptr;
+    float* W[MLP_NL] = {};
+    float* b[MLP_NL] = {};
+};
+
+namespace {
+
+// where row `row` of input k sits inside its [k] line of 16 * RT rows
+template <int RT>
+__device__ __forceinline__ int mlp_swz(int row, int k) { return row ^ (RT == 2 ? 16 * (k & 1) : 0); }
+
+__device__ __forceinline__ float mlp_act(float z, int act) {
+    if (act == CADM_VALUE_RELU) return fmaxf(z, 0.0f);
+    if (act == CADM_VALUE_TANH) return tanhf(z);
+    return z / (1.0f + expf(-z));
+}
+
+// One work item of a layer: NT tiles of 16 units of group g x NRT row tiles, the whole K.  The k loop is straight-line code: one ring
+// slot consumed, one refilled, NRT LDS reads, NT * NRT MFMAs; everything it could branch on is a template parameter.
+template <int RT, int NRT, int NT>
+__device__ __forceinline__ void mlp_item(const float* __restrict__ Wg, const float* __restrict__ bias, int nsteps, int N, int act, bool last,
+                                         const float* xin, float* xout, float* vres, int g, int rt0, int lane) {
+    constexpr int R = 16 * RT;
+    const int i = lane & 15, q = lane >> 4;
+    floatx4 acc[NT][NRT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        floatx4 b4;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) b4[rr] = bias[g * 64 + 4 * (4 * q + rr) + t];
+#pragma unroll
+        for (int r = 0; r < NRT; ++r) acc[t][r] = b4;
+    }
+    // A operand of k-step s: row k = 4 s + q of W, units 64 g + 4 i + (0 .. 3)
+    const floatx4* wp = reinterpret_cast<const floatx4*>(Wg) + lane;
+    auto fetch = [&](int s) -> floatx4 { return wp[(size_t)s * 64]; };
+    // B operand of k-step s for row tile r: X[k = 4 s + q][row = 16 (rt0 + r) + i]
+    int boff[NRT];
+#pragma unroll
+    for (int r = 0; r < NRT; ++r) boff[r] = q * R + mlp_swz<RT>(16 * (rt0 + r) + i, q);      // (k & 1 == q & 1)
+    constexpr int bstep = 4 * R;
+    auto bread = [&](float (&bv)[NRT], int s) {
+#pragma unroll
+        for (int r = 0; r < NRT; ++r) bv[r] = xin[boff[r] + s * bstep];
+    };
+    auto mfmas = [&](const floatx4& av, const float (&bv)[NRT]) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < NRT; ++r) acc[t][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], bv[r], acc[t][r], 0, 0, 0);
+    };
+    floatx4 ring[MLP_PF];
+#pragma unroll
+    for (int u = 0; u < MLP_PF; ++u) ring[u] = fetch(u < nsteps ? u : nsteps - 1);
+    int s0 = 0;
+    for (; s0 + MLP_PF <= nsteps; s0 += MLP_PF) {
+        float bv[MLP_PF][NRT];
+#pragma unroll
+        for (int u = 0; u < MLP_PF; ++u) bread(bv[u], s0 + u);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < MLP_PF; ++u) {
+            mfmas(ring[u], bv[u]);
+            const int sn = s0 + u + MLP_PF;
+            ring[u] = fetch(sn < nsteps ? sn : nsteps - 1);      // (past the end: a re-read of the last step, never consumed)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < MLP_PF - 1; ++u)                         // the last nsteps % PF steps are already in the ring
+        if (s0 + u < nsteps) { float bv[NRT]; bread(bv, s0 + u); mfmas(ring[u], bv); }
+    // D layout: lane (i -> data row, q), register rr -> unit 64 g + 4 (4 q + rr) + t
+    const int N4 = (N + 3) & ~3;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int unit = g * 64 + 4 * (4 * q + rr) + t;
+#pragma unroll
+            for (int r = 0; r < NRT; ++r) {
+                const float z = acc[t][r][rr];
+                const int row = 16 * (rt0 + r) + i;
+                if (last) { if (unit == 0) vres[row] = z; }
+                else if (unit < N4) xout[unit * R + mlp_swz<RT>(row, unit)] = unit < N ? mlp_act(z, act) : 0.0f;
+            }
+        }
+}
+
+template <int RT>
+__device__ __forceinline__ void mlp_layer(const float* __restrict__ W, const float* __restrict__ bias, int K, int N, int act, bool last,
+                                          const float* xin, float* xout, float* vres, int wave, int lane) {
+    const int NG = (N + 63) >> 6, nsteps = (K + 3) >> 2;
+    const size_t gfl = (size_t)nsteps * 256;                     // packed floats of one group
+    if (last) {                                                  // one unit: the first tile of group 0, a row tile per wave
+        for (int rt0 = wave; rt0 < RT; rt0 += MLP_WAVES) mlp_item<RT, 1, 1>(W, bias, nsteps, N, act, true, xin, xout, vres, 0, rt0, lane);
+    } else if (RT == 1 || NG >= MLP_WAVES) {                     // a wave takes whole groups, all row tiles
+        for (int g = wave; g < NG; g += MLP_WAVES) mlp_item<RT, RT, 4>(W + g * gfl, bias, nsteps, N, act, false, xin, xout, vres, g, 0, lane);
+    } else {                                                     // few groups: the row tiles of a group go to different waves
+        for (int item = wave; item < NG * RT; item += MLP_WAVES) {
+            const int g = item % NG, rt0 = item / NG;
+            mlp_item<RT, 1, 4>(W + g * gfl, bias, nsteps, N, act, false, xin, xout, vres, g, rt0, lane);
+        }
+    }
+}
+
+// dst [NG][nsteps][64 lanes][4]: lane (i = lane & 15, q = lane >> 4), t -> W[k = 4 s + q][unit = 64 g + 4 i + t], 0 outside [K, N);
+// bdst [NG * 64]: the biases, 0 behind N
+__global__ void mlp_pack_kernel(const float* __restrict__ W, const float* __restrict__ b, int K, int N, float* __restrict__ dst,
+                                float* __restrict__ bdst) {
+    const int nsteps = (K + 3) >> 2, NG = (N + 63) >> 6;
+    const size_t total = (size_t)NG * nsteps * 256;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int t = (int)(e & 3), lane = (int)((e >> 2) & 63);
+        const size_t gs = e >> 8;
+        const int s = (int)(gs % nsteps), g = (int)(gs / nsteps);
+        const int k = 4 * s + (lane >> 4), unit = 64 * g + 4 * (lane & 15) + t;
+        dst[e] = (k < K && unit < N) ? W[(size_t)k * N + unit] : 0.0f;
+        if (e < (size_t)NG * 64) bdst[e] = e < (size_t)N ? b[e] : 0.0f;
+    }
+}
+
+__global__ void mlp_copy_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ da, float* __restrict__ db) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { da[i] = a[i]; db[i] = b[i]; }
+}
+
+size_t mlp_w_floats(int K, int N) { return (size_t)((N + 63) >> 6) * ((K + 3) >> 2) * 256; }
+size_t mlp_b_floats(int N) { return (size_t)((N + 63) >> 6) * 64; }
+
+// LDS floats of a workgroup's two activation regions with RT row tiles: region 0 (the input tile, later the outputs of the odd layers)
+// and region 1 (the outputs of the even layers); returns their sum
+size_t mlp_region_floats(const int* dims, int nlayers, int RT, int* region0, int* region1) {
+    const size_t R = 16 * (size_t)RT;
+    size_t r0 = R * (size_t)((dims[0] + 3) & ~3), r1 = 0;
+    for (int l = 0; l + 1 < nlayers; ++l) {
+        const size_t need = R * (size_t)((dims[l + 1] + 3) & ~3);
+        if (l & 1) r0 = need > r0 ? need : r0; else r1 = need > r1 ? need : r1;
+    }
+    if (region0) *region0 = (int)r0;
+    if (region1) *region1 = (int)r1;
+    return r0 + r1;
+}
+
+void mlp_net_release(MlpNet* net) {
+    if (net && net->buf) (void)hipFree(net->buf);
+}
+
+// packs the net dims[0] -> .. -> dims[nl] (W[l] [in,out] row-major, b[l] [out], mean / std_inv [dims[0]]: device pointers) into memory
+// `net` owns, on `s`; a net that fits the allocation it has allocates nothing
+int mlp_net_upload(MlpNet& net, const int* dims, int nl, const float* const* W, const float* const* b, const float* mean, const float* std_inv,
+                   hipStream_t s, const char* who) {
+    const size_t K64 = (size_t)((dims[0] + 63) & ~63);
+    size_t need = 2 * K64;
+    for (int l = 0; l < nl; ++l) need += mlp_w_floats(dims[l], dims[l + 1]) + mlp_b_floats(dims[l + 1]);
+    net.set = false;
+    if (need > net.cap) {
+        if (net.buf) CADM_CHECK_HIP(hipFree(net.buf));      // (waits for every launch that still reads the old copy)
+        net.buf = nullptr; net.cap = 0;
+        if (hipMalloc(&net.buf, need * sizeof(float)) != hipSuccess) { cadm_set_error("%s: hipMalloc failed", who); return CADM_ENOMEM; }
+        net.cap = need;
+    }
+    float* q = net.buf;
+    net.mean = q; q += K64;
+    net.istd = q; q += K64;
+    hipLaunchKernelGGL(mlp_copy_kernel, dim3((dims[0] + 127) / 128), dim3(128), 0, s, mean, std_inv, dims[0], net.mean, net.istd);
+    CADM_CHECK_HIP(hipGetLastError());
+    for (int l = 0; l < nl; ++l) {
+        const size_t wf = mlp_w_floats(dims[l], dims[l + 1]);
+        net.W[l] = q; q += wf;
+        net.b[l] = q; q += mlp_b_floats(dims[l + 1]);
+        const size_t g = (wf + 255) / 256;
+        hipLaunchKernelGGL(mlp_pack_kernel, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, W[l], b[l], dims[l], dims[l + 1], net.W[l],
+                           net.b[l]);
+        CADM_CHECK_HIP(hipGetLastError());
+    }
+    net.set = true;
+    return CADM_OK;
+}
+
+}  // namespace

@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -104,6 +104,14 @@ int cadm_launch_uncertainty(cadm_ctx* ctx, const cadm_uncertainty_params* unc, c
 int cadm_value_plan_check(const cadm_ctx* ctx, const cadm_value_params* value, const char* who);
 int cadm_launch_value(cadm_ctx* ctx, const cadm_value_params* value, const float* traj, const int32_t* first, int m, int n, float* rows,
                       hipStream_t s);
+// reward.hip: the refusals of a learned reward (null parameters, a layer count outside 0 .. 4, a width outside 1 .. 512, an unknown
+// activation or inputs, a weight that is not finite, K beyond CADM_MAX_REWARD_DIMS, a discrete / sharded ctx, activation tiles beyond the
+// LDS; no registered net: CADM_ESTATE; parameters that do not describe the registered net), before any HIP call; and the two launches
+// behind a rollout's traj [H, m, n, p, D] (n the PACKED candidate count; first [m, n, p] or null): r_step [H, m, n, p] = R of every
+// (step, row), NaN where not counted, then rows[q] += weight * (the sum of the counted steps in ascending t) in place
+int cadm_reward_plan_check(const cadm_ctx* ctx, const cadm_reward_params* reward, const char* who);
+int cadm_launch_reward(cadm_ctx* ctx, const cadm_reward_params* reward, const float* traj, const float* obs, const float* actions,
+                       const int32_t* first, int m, int n, float* rows, float* r_step, hipStream_t s);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

@@ -18,7 +18,7 @@
 //
 // Mapping: a workgroup of 4 waves owns 16 * RT consecutive rows (RT = 1 or 2) and takes them through every layer.  A layer's 64-unit
 // groups go to the waves (all row tiles each, so a weight fragment is used RT times); with fewer groups than waves the (group, row tile)
-// pairs do.  The weights are a ctx-owned packed copy (value_pack_kernel): per layer [group of 64 units][k-step][lane][4], so that the A
+// pairs do (mlp_chain.h, shared with reward.hip).  The weights are a ctx-owned packed copy (mlp_pack_kernel): per layer [group of 64 units][k-step][lane][4], so that the A
 // operands of FOUR 16-unit tiles (tile t = units {64 g + 4 i + t}) are one 16-byte load per lane and a wave's k-step is 1 KiB contiguous;
 // K is zero-padded to 4 and the units to 64 there, the biases to 64.  Activation units behind N up to the next multiple of 4 are
 // written as exact zeros, rows behind the batch compute on zeros and store nothing.  Rows are the B / D columns of the MFMAs: a value
@@ -26,22 +26,14 @@
 // Reduction contract: a row's V is one column's chain in ascending k, the same instruction sequence wherever the row sits; no
 // floating-point atomics; nothing depends on the grid, on RT, on m or n: the same bits run to run, inside any batch, and from
 // cadm_value_eval as from the planner stage.
-#include <math.h>
-
-#include "planner.h"
+#include "mlp_chain.h"
 
 namespace {
 
-constexpr int VAL_THREADS = 256;
-constexpr int VAL_WAVES = 4;
-constexpr int VAL_PF = 6;                    // k-steps of weight fragments in flight per wave
-constexpr int VAL_LDS_MAX = 160 * 1024;      // the CU's LDS; above 64 KiB the kernel's dynamic-LDS attribute is raised
-constexpr int VAL_NL = CADM_MAX_VALUE_LAYERS + 1;
-
 struct ValueArgs {
-    const float* W[VAL_NL];        // packed, per layer
-    const float* b[VAL_NL];        // padded to 64 units
-    int dims[VAL_NL + 1];          // D, h_1 .. h_L, 1
+    const float* W[MLP_NL];        // packed, per layer
+    const float* b[MLP_NL];        // padded to 64 units
+    int dims[MLP_NL + 1];          // D, h_1 .. h_L, 1
     int nlayers;                   // dense layers including the output
     int act;
     const float *mean, *istd;      // [D]
@@ -55,102 +47,8 @@ struct ValueArgs {
     int region0, region1;          // LDS floats of the two activation regions
 };
 
-__device__ __forceinline__ float value_act(float z, int act) {
-    if (act == CADM_VALUE_RELU) return fmaxf(z, 0.0f);
-    if (act == CADM_VALUE_TANH) return tanhf(z);
-    return z / (1.0f + expf(-z));
-}
-
-// One work item of a layer: NT tiles of 16 units of group g x NRT row tiles, the whole K.  The k loop is straight-line code: one ring
-// slot consumed, one refilled, NRT LDS reads, NT * NRT MFMAs; everything it could branch on is a template parameter.
-template <int RT, int NRT, int NT>
-__device__ __forceinline__ void value_item(const float* __restrict__ Wg, const float* __restrict__ bias, int nsteps, int N, int act, bool last,
-                                           const float* xin, float* xout, float* vres, int g, int rt0, int lane) {
-    constexpr int R = 16 * RT;
-    const int i = lane & 15, q = lane >> 4;
-    floatx4 acc[NT][NRT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        floatx4 b4;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) b4[rr] = bias[g * 64 + 4 * (4 * q + rr) + t];
-#pragma unroll
-        for (int r = 0; r < NRT; ++r) acc[t][r] = b4;
-    }
-    // A operand of k-step s: row k = 4 s + q of W, units 64 g + 4 i + (0 .. 3)
-    const floatx4* wp = reinterpret_cast<const floatx4*>(Wg) + lane;
-    auto fetch = [&](int s) -> floatx4 { return wp[(size_t)s * 64]; };
-    // B operand of k-step s for row tile r: X[k = 4 s + q][row = 16 (rt0 + r) + i]
-    int boff[NRT];
-#pragma unroll
-    for (int r = 0; r < NRT; ++r) boff[r] = q * R + ((16 * (rt0 + r) + i) ^ (RT == 2 ? 16 * (q & 1) : 0));      // (k & 1 == q & 1)
-    constexpr int bstep = 4 * R;
-    auto bread = [&](float (&bv)[NRT], int s) {
-#pragma unroll
-        for (int r = 0; r < NRT; ++r) bv[r] = xin[boff[r] + s * bstep];
-    };
-    auto mfmas = [&](const floatx4& av, const float (&bv)[NRT]) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < NRT; ++r) acc[t][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], bv[r], acc[t][r], 0, 0, 0);
-    };
-    floatx4 ring[VAL_PF];
-#pragma unroll
-    for (int u = 0; u < VAL_PF; ++u) ring[u] = fetch(u < nsteps ? u : nsteps - 1);
-    int s0 = 0;
-    for (; s0 + VAL_PF <= nsteps; s0 += VAL_PF) {
-        float bv[VAL_PF][NRT];
-#pragma unroll
-        for (int u = 0; u < VAL_PF; ++u) bread(bv[u], s0 + u);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < VAL_PF; ++u) {
-            mfmas(ring[u], bv[u]);
-            const int sn = s0 + u + VAL_PF;
-            ring[u] = fetch(sn < nsteps ? sn : nsteps - 1);      // (past the end: a re-read of the last step, never consumed)
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < VAL_PF - 1; ++u)                         // the last nsteps % PF steps are already in the ring
-        if (s0 + u < nsteps) { float bv[NRT]; bread(bv, s0 + u); mfmas(ring[u], bv); }
-    // D layout: lane (i -> data row, q), register rr -> unit 64 g + 4 (4 q + rr) + t
-    const int N4 = (N + 3) & ~3;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int unit = g * 64 + 4 * (4 * q + rr) + t;
-#pragma unroll
-            for (int r = 0; r < NRT; ++r) {
-                const float z = acc[t][r][rr];
-                const int row = 16 * (rt0 + r) + i;
-                if (last) { if (unit == 0) vres[row] = z; }
-                else if (unit < N4) xout[unit * R + (row ^ (RT == 2 ? 16 * (unit & 1) : 0))] = unit < N ? value_act(z, act) : 0.0f;
-            }
-        }
-}
-
 template <int RT>
-__device__ __forceinline__ void value_layer(const float* __restrict__ W, const float* __restrict__ bias, int K, int N, int act, bool last,
-                                            const float* xin, float* xout, float* vres, int wave, int lane) {
-    const int NG = (N + 63) >> 6, nsteps = (K + 3) >> 2;
-    const size_t gfl = (size_t)nsteps * 256;                     // packed floats of one group
-    if (last) {                                                  // one unit: the first tile of group 0, a row tile per wave
-        for (int rt0 = wave; rt0 < RT; rt0 += VAL_WAVES) value_item<RT, 1, 1>(W, bias, nsteps, N, act, true, xin, xout, vres, 0, rt0, lane);
-    } else if (RT == 1 || NG >= VAL_WAVES) {                     // a wave takes whole groups, all row tiles
-        for (int g = wave; g < NG; g += VAL_WAVES) value_item<RT, RT, 4>(W + g * gfl, bias, nsteps, N, act, false, xin, xout, vres, g, 0, lane);
-    } else {                                                     // few groups: the row tiles of a group go to different waves
-        for (int item = wave; item < NG * RT; item += VAL_WAVES) {
-            const int g = item % NG, rt0 = item / NG;
-            value_item<RT, 1, 4>(W + g * gfl, bias, nsteps, N, act, false, xin, xout, vres, g, rt0, lane);
-        }
-    }
-}
-
-template <int RT>
-__global__ __launch_bounds__(VAL_THREADS) void value_kernel(const ValueArgs a) {
+__global__ __launch_bounds__(MLP_THREADS) void value_kernel(const ValueArgs a) {
     extern __shared__ __attribute__((aligned(16))) float val_smem[];
     constexpr int R = 16 * RT;
     float* reg0 = val_smem;
@@ -168,7 +66,7 @@ __global__ __launch_bounds__(VAL_THREADS) void value_kernel(const ValueArgs a) {
     __syncthreads();
     // the input tile [k][row], normalised on the way in; rows that are not evaluated and the k behind D are zeros
     const int D = a.dims[0], D4 = (D + 3) & ~3;
-    for (int idx = tid; idx < R * D4; idx += VAL_THREADS) {
+    for (int idx = tid; idx < R * D4; idx += MLP_THREADS) {
         const int row = idx / D4, k = idx - row * D4;
         float x = 0.0f;
         if (k < D && flag[row] == 0) {
@@ -176,13 +74,13 @@ __global__ __launch_bounds__(VAL_THREADS) void value_kernel(const ValueArgs a) {
             if ((__float_as_uint(v) & 0x7f800000u) == 0x7f800000u) bad[row] = 1;      // (every writer stores the same 1)
             x = (v - a.mean[k]) * a.istd[k];
         }
-        reg0[k * R + (row ^ (RT == 2 ? 16 * (k & 1) : 0))] = x;
+        reg0[k * R + mlp_swz<RT>(row, k)] = x;
     }
     __syncthreads();
     const float* xin = reg0;
     for (int l = 0; l < a.nlayers; ++l) {
         float* xout = (l & 1) ? reg0 : reg1;
-        value_layer<RT>(a.W[l], a.b[l], a.dims[l], a.dims[l + 1], a.act, l + 1 == a.nlayers, xin, xout, vres, wave, lane);
+        mlp_layer<RT>(a.W[l], a.b[l], a.dims[l], a.dims[l + 1], a.act, l + 1 == a.nlayers, xin, xout, vres, wave, lane);
         __syncthreads();
         xin = xout;
     }
@@ -199,42 +97,10 @@ __global__ __launch_bounds__(VAL_THREADS) void value_kernel(const ValueArgs a) {
     }
 }
 
-// dst [NG][nsteps][64 lanes][4]: lane (i = lane & 15, q = lane >> 4), t -> W[k = 4 s + q][unit = 64 g + 4 i + t], 0 outside [K, N);
-// bdst [NG * 64]: the biases, 0 behind N
-__global__ void value_pack_kernel(const float* __restrict__ W, const float* __restrict__ b, int K, int N, float* __restrict__ dst,
-                                  float* __restrict__ bdst) {
-    const int nsteps = (K + 3) >> 2, NG = (N + 63) >> 6;
-    const size_t total = (size_t)NG * nsteps * 256;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int t = (int)(e & 3), lane = (int)((e >> 2) & 63);
-        const size_t gs = e >> 8;
-        const int s = (int)(gs % nsteps), g = (int)(gs / nsteps);
-        const int k = 4 * s + (lane >> 4), unit = 64 * g + 4 * (lane & 15) + t;
-        dst[e] = (k < K && unit < N) ? W[(size_t)k * N + unit] : 0.0f;
-        if (e < (size_t)NG * 64) bdst[e] = e < (size_t)N ? b[e] : 0.0f;
-    }
-}
-
-__global__ void value_copy_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ da, float* __restrict__ db) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { da[i] = a[i]; db[i] = b[i]; }
-}
-
-size_t value_w_floats(int K, int N) { return (size_t)((N + 63) >> 6) * ((K + 3) >> 2) * 256; }
-size_t value_b_floats(int N) { return (size_t)((N + 63) >> 6) * 64; }
-
 // LDS of a workgroup with RT row tiles: region 0 (the input tile, later the outputs of the odd layers), region 1 (the outputs of the even
 // layers), the output sums and the two flag arrays
 size_t value_lds_bytes(const int* dims, int nlayers, int RT, int* region0, int* region1) {
-    const size_t R = 16 * (size_t)RT;
-    size_t r0 = R * (size_t)((dims[0] + 3) & ~3), r1 = 0;
-    for (int l = 0; l + 1 < nlayers; ++l) {
-        const size_t need = R * (size_t)((dims[l + 1] + 3) & ~3);
-        if (l & 1) r0 = need > r0 ? need : r0; else r1 = need > r1 ? need : r1;
-    }
-    if (region0) *region0 = (int)r0;
-    if (region1) *region1 = (int)r1;
-    return (r0 + r1 + 3 * R) * sizeof(float);
+    return (mlp_region_floats(dims, nlayers, RT, region0, region1) + 3 * 16 * (size_t)RT) * sizeof(float);
 }
 
 void value_dims(const cadm_ctx* ctx, const cadm_value_params* p, int* dims) {
@@ -246,19 +112,13 @@ void value_dims(const cadm_ctx* ctx, const cadm_value_params* p, int* dims) {
 }  // namespace
 
 // the ctx-owned packed copy of the registered net
-struct ValueNet {
-    bool set = false;
+struct ValueNet : MlpNet {
     cadm_value_params prm{};       // what was registered (its weight is not used: every call brings its own)
-    float* buf = nullptr;          // one allocation: mean, inv_std, then per layer the packed weights and the padded biases
-    size_t cap = 0;                // floats allocated
-    float *mean = nullptr, *istd = nullptr;
-    float* W[VAL_NL] = {};
-    float* b[VAL_NL] = {};
 };
 
 void cadm_value_free(cadm_ctx* ctx) {
     if (!ctx->value) return;
-    if (ctx->value->buf) (void)hipFree(ctx->value->buf);
+    mlp_net_release(ctx->value);
     delete ctx->value;
     ctx->value = nullptr;
 }
@@ -278,11 +138,11 @@ int cadm_value_check(const cadm_ctx* ctx, const cadm_value_params* p, const char
     CADM_REQUIRE(!ctx->cfg.discrete && ctx->cfg.env_kind != CADM_ENV_CARTPOLE, "%s: a terminal value needs a continuous-action ctx (discrete "
                  "actions are planned by random shooting)", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: a terminal value is not supported on a candidate-sharded ctx", who);
-    int dims[VAL_NL + 1];
+    int dims[MLP_NL + 1];
     value_dims(ctx, p, dims);
     const size_t lds = value_lds_bytes(dims, p->n_hidden + 1, 1, nullptr, nullptr);
-    CADM_REQUIRE(lds <= (size_t)VAL_LDS_MAX, "%s: the value net's activation tiles need %zu bytes of LDS at one row tile, the bound is %d", who,
-                 lds, VAL_LDS_MAX);
+    CADM_REQUIRE(lds <= (size_t)MLP_LDS_MAX, "%s: the value net's activation tiles need %zu bytes of LDS at one row tile, the bound is %d", who,
+                 lds, MLP_LDS_MAX);
     return CADM_OK;
 }
 
@@ -316,16 +176,16 @@ static int value_launch(cadm_ctx* ctx, float weight, const float* x, const int32
     // two row tiles halve the weight stream per row; one tile keeps every CU busy while the rows are few
     int RT = (total + 15) / 16 > 2 * (size_t)ctx->n_cus ? 2 : 1;
     size_t lds = value_lds_bytes(a.dims, a.nlayers, RT, &a.region0, &a.region1);
-    if (lds > (size_t)VAL_LDS_MAX) { RT = 1; lds = value_lds_bytes(a.dims, a.nlayers, RT, &a.region0, &a.region1); }
+    if (lds > (size_t)MLP_LDS_MAX) { RT = 1; lds = value_lds_bytes(a.dims, a.nlayers, RT, &a.region0, &a.region1); }
     const size_t R = 16 * (size_t)RT, blocks = (total + R - 1) / R;
     CADM_REQUIRE(blocks <= 0x7fffffffull, "%s: %zu rows are too many for one launch", who, total);
     const void* fn = RT == 2 ? reinterpret_cast<const void*>(&value_kernel<2>) : reinterpret_cast<const void*>(&value_kernel<1>);
     if (lds > 64 * 1024 && !ctx->attr_done.count(fn)) {
-        CADM_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, VAL_LDS_MAX));
+        CADM_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_MAX));
         ctx->attr_done.insert(fn);
     }
-    if (RT == 2) hipLaunchKernelGGL(value_kernel<2>, dim3((unsigned)blocks), dim3(VAL_THREADS), lds, s, a);
-    else hipLaunchKernelGGL(value_kernel<1>, dim3((unsigned)blocks), dim3(VAL_THREADS), lds, s, a);
+    if (RT == 2) hipLaunchKernelGGL(value_kernel<2>, dim3((unsigned)blocks), dim3(MLP_THREADS), lds, s, a);
+    else hipLaunchKernelGGL(value_kernel<1>, dim3((unsigned)blocks), dim3(MLP_THREADS), lds, s, a);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;
 }
@@ -349,40 +209,16 @@ extern "C" int cadm_set_value_net(cadm_ctx* ctx, const cadm_value_params* params
     CADM_REQUIRE(W && b && mean && std_inv, "cadm_set_value_net: W / b / mean / std_inv is null");
     const int nl = params->n_hidden + 1;
     for (int l = 0; l < nl; ++l) CADM_REQUIRE(W[l] && b[l], "cadm_set_value_net: the weights or the biases of layer %d are null", l);
-    int dims[VAL_NL + 1];
+    int dims[MLP_NL + 1];
     value_dims(ctx, params, dims);
-    size_t need = 2 * (size_t)((ctx->D + 63) & ~63);
-    for (int l = 0; l < nl; ++l) need += value_w_floats(dims[l], dims[l + 1]) + value_b_floats(dims[l + 1]);
     CADM_ON_DEVICE(ctx);
     if (!ctx->value) {
         ctx->value = new (std::nothrow) ValueNet();
         if (!ctx->value) { cadm_set_error("cadm_set_value_net: out of host memory"); return CADM_ENOMEM; }
     }
     ValueNet& net = *ctx->value;
-    net.set = false;
-    if (need > net.cap) {
-        if (net.buf) CADM_CHECK_HIP(hipFree(net.buf));      // (waits for every launch that still reads the old copy)
-        net.buf = nullptr; net.cap = 0;
-        if (hipMalloc(&net.buf, need * sizeof(float)) != hipSuccess) { cadm_set_error("cadm_set_value_net: hipMalloc failed"); return CADM_ENOMEM; }
-        net.cap = need;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    float* q = net.buf;
-    net.mean = q; q += (ctx->D + 63) & ~63;
-    net.istd = q; q += (ctx->D + 63) & ~63;
-    hipLaunchKernelGGL(value_copy_kernel, dim3((ctx->D + 127) / 128), dim3(128), 0, s, mean, std_inv, ctx->D, net.mean, net.istd);
-    CADM_CHECK_HIP(hipGetLastError());
-    for (int l = 0; l < nl; ++l) {
-        const size_t wf = value_w_floats(dims[l], dims[l + 1]);
-        net.W[l] = q; q += wf;
-        net.b[l] = q; q += value_b_floats(dims[l + 1]);
-        const size_t g = (wf + 255) / 256;
-        hipLaunchKernelGGL(value_pack_kernel, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, W[l], b[l], dims[l], dims[l + 1], net.W[l],
-                           net.b[l]);
-        CADM_CHECK_HIP(hipGetLastError());
-    }
+    if ((rc = mlp_net_upload(net, dims, nl, W, b, mean, std_inv, (hipStream_t)stream, "cadm_set_value_net"))) return rc;
     net.prm = *params;
-    net.set = true;
     return CADM_OK;
 }
 

@@ -65,6 +65,12 @@ Differences a caller can see (all opt-in except the first):
     list of (W [in,out], b [out]) or a torch.nn.Sequential), as often as it is retrained and with nothing rebuilt,
     `clear_terminal_value()` removes it, `terminal_value(states)` evaluates V through the planner's kernel,
     `plan_terminal_value(obs, actions, ...)`: what the term adds for given plans.  It alone takes the opt-in route;
+  * `cem_reward_net=dict(inputs="next_obs" | "obs_act" | "obs_act_next_obs", hidden_sizes=(128, 128), activation=, weight=1.0)`: a
+    learned reward net R on every step of every particle in that loop, so that a candidate is scored by return + weight * sum_t R_t
+    (INTEGRATION.md "Learned reward").  The kwarg declares the net's shape; `set_reward_net(weights, in_mean=None, in_std=None)` hands
+    over the net at run time (a list of (W [in,out], b [out]) or a torch.nn.Sequential) with nothing rebuilt, `clear_reward_net()`
+    removes it, `reward_net(obs, act, next_obs)` evaluates R through the planner's kernel, `plan_rewards(obs, actions, ...)`: the step
+    rewards of given plans.  It alone takes the opt-in route;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -247,6 +253,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_action_advance=True,
                  cem_uncertainty=None,
                  cem_terminal_value=None,
+                 cem_reward_net=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -315,7 +322,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      cem_action_rate_cost=cem_action_rate_cost, cem_action_advance=cem_action_advance,
                                                      n_forwards=n_forwards, action_dim=None if self.discrete else self.action_space_dims,
                                                      cem_uncertainty=cem_uncertainty, obs_dim=obs_space_dims,
-                                                     cem_terminal_value=cem_terminal_value)
+                                                     cem_terminal_value=cem_terminal_value, cem_reward_net=cem_reward_net)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
@@ -329,6 +336,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         self._targets = self._target_offset = None            # device tensors [m,T,K] float32 / [m] int32 (cem_tracking): `set_targets`
         self._act_prev = self._act_prefix = None              # device tensors [m,A] / [m,delay,A] float32, NaN = unknown (the actuator model)
         self._value_set = False                               # whether the engine holds a value net (cem_terminal_value): `set_terminal_value`
+        self._reward_set = False                              # whether the engine holds a reward net (cem_reward_net): `set_reward_net`
 
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
@@ -578,6 +586,8 @@ class MLPEnsembleCEMDynamicsModel(object):
             extra.update(act_prev=self._act_prev, act_prefix=self._act_prefix)
         if self._opt.value_params is not None and not self._value_set:
             raise RuntimeError("get_action: this model plans under cem_terminal_value and has no value net (call set_terminal_value first)")
+        if self._opt.reward_params is not None and not self._reward_set:
+            raise RuntimeError("get_action: this model plans under cem_reward_net and has no reward net (call set_reward_net first)")
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
@@ -774,6 +784,76 @@ class MLPEnsembleCEMDynamicsModel(object):
             _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
         _, v = eng.value_returns(traj, rows, opt.value_params, first=first, want_v=True)
         res = dict(value=v.cpu().numpy(), first=None if first is None else first.cpu().numpy())
+        if squeeze:
+            res = {k: None if x is None else x[:, 0] for k, x in res.items()}
+        return res
+
+    # ------------------------------------------------------------------ learned reward (INTEGRATION.md "Learned reward")
+    def _require_reward(self, who, need_net=False):
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.reward_params is None:
+            raise ValueError("%s: this model has no cem_reward_net" % who)
+        if need_net and not self._reward_set:
+            raise RuntimeError("%s: this model has no reward net (call set_reward_net first)" % who)
+        return opt
+
+    def set_reward_net(self, weights, in_mean=None, in_std=None):
+        """The reward net of `cem_reward_net` from the next call on: `weights` as `set_terminal_value` takes them (a list of (W [in,out],
+        b [out]) per layer, or a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules) -- of the declared input, layer sizes and
+        activation, else it is refused; in_mean / in_std [K] over the concatenated input (None: 0 / 1, std finite and > 0): the net reads
+        (input - in_mean) / in_std of the raw observations and actions.  Everything is copied; replacing the net rebuilds nothing."""
+        opt = self._require_reward("set_reward_net")
+        self.engine.set_reward_net(opt.reward_params, weights, in_mean=in_mean, in_std=in_std)
+        self._reward_set = True
+
+    def clear_reward_net(self):
+        """Remove the reward net: get_action on a model with `cem_reward_net` then raises until `set_reward_net` is called."""
+        self._require_reward("clear_reward_net")
+        self.engine.set_reward_net(None)
+        self._reward_set = False
+
+    def reward_net(self, obs=None, act=None, next_obs=None):
+        """R of raw transitions through the planner's kernel -> numpy [...]: obs [..., D], act [..., A], next_obs [..., D] (numpy or
+        tensor), of which the declared `inputs` says which are read and concatenated (the others may be None); NaN for an input with a
+        non-finite value."""
+        opt = self._require_reward("reward_net", need_net=True)
+        eng = self.engine
+        need = {"next_obs": (("next_obs", next_obs, eng.D),), "obs_act": (("obs", obs, eng.D), ("act", act, eng.A)),
+                "obs_act_next_obs": (("obs", obs, eng.D), ("act", act, eng.A), ("next_obs", next_obs, eng.D))}[opt.reward[0]]
+        parts = []
+        for name, x, dim in need:
+            if x is None or np.ndim(x) < 1 or np.shape(x)[-1] != dim:
+                raise ValueError("reward_net: inputs %r need %s [..., %d], got %r" % (opt.reward[0], name, dim, None if x is None else tuple(np.shape(x))))
+            parts.append(eng._t(x))
+        if any(t.shape[:-1] != parts[0].shape[:-1] for t in parts):
+            raise ValueError("reward_net: the leading shapes %r do not agree" % ([tuple(t.shape) for t in parts],))
+        return eng.reward_eval(torch.cat(parts, dim=-1)).cpu().numpy()
+
+    def plan_rewards(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
+        """The learned step rewards of `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) -- the companion of `plan_terminal_value`: the
+        context encoder, one rollout that records its trajectories and the reward kernels, as numpy arrays (for [m,H,A] input the n axis
+        is dropped):
+          reward [m,n,p,H]  R of every step of every particle (NaN: a step with a non-finite input, or one behind a particle's first violation)
+          total [m,n,p]     the sum over the counted steps in ascending t; the planner adds weight * total to the particle's return
+          first [m,n,p]     with `cem_constraints` in terminate mode their first violations (steps t <= first count), else None
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        opt = self._require_reward("plan_rewards", need_net=True)
+        self._push_stats()
+        cp_obs, cp_act = self._rollout_inputs("plan_rewards", obs, actions, cp_obs, cp_act)
+        eng = self.engine
+        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        acts = (acts[:, None] if squeeze else acts).contiguous()
+        obs = eng._t(obs)
+        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        first = None
+        if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
+            _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
+        _, steps, total = eng.reward_returns(traj, obs, acts, rows, opt.reward_params, first=first, want_steps=True)
+        res = dict(reward=steps.permute(1, 2, 3, 0).cpu().numpy(), total=total.cpu().numpy(),
+                   first=None if first is None else first.cpu().numpy())
         if squeeze:
             res = {k: None if x is None else x[:, 0] for k, x in res.items()}
         return res

@@ -57,6 +57,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """What this model's `cem_terminal_value` adds for `actions` (see the CaDM class; a vanilla model has no history)."""
         return super().plan_terminal_value(obs, actions, None, None, seed=seed)
 
+    def plan_rewards(self, obs, actions, seed=None):
+        """The learned step rewards of `actions` under this model's `cem_reward_net` (see the CaDM class; a vanilla model has no history)."""
+        return super().plan_rewards(obs, actions, None, None, seed=seed)
+
     def predict(self, obs, act, return_std=False):
         return super().predict(obs, act, None, None, return_std=return_std)
 

@@ -560,12 +560,12 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return, traj=False, track=None, act=False, unc=None, val=None):
+                   want_best_return, traj=False, track=None, act=False, unc=None, val=None, rew=None):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
         `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
         workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop); act: the workspace of an actuated loop;
         unc: None, or the (terminate, actuator) of a loop with an uncertainty term, whose slot it is; val: None, or the (terminate, actuator,
-        uncertainty) of a loop with a terminal value, whose slot it is."""
+        uncertainty) of a loop with a terminal value, whose slot it is; rew: likewise for a loop with a learned reward."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -574,7 +574,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val, rew=rew)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -587,8 +587,12 @@ class HipEngine:
         [m,delay,A]: the envs' actuator state, moved on in place when the options say so), `tracking_plan` when it holds tracking terms (targets [m,T,K] or [m,K],
         target_offset [m] int32 or None = 0), `knot_plan` when it holds knots (phase: the envs' grid phases [m] int32, None = 0),
         `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
-        Arguments as `icem_plan` behind its params.  First of all `valued_plan`, when it holds a terminal value, then `uncertain_plan`, when
-        it holds an uncertainty term."""
+        Arguments as `icem_plan` behind its params.  First of all `rewarded_plan`, when it holds a learned reward, then `valued_plan`, when
+        it holds a terminal value, then `uncertain_plan`, when it holds an uncertainty term."""
+        if getattr(opt, "reward_params", None) is not None:
+            return self.rewarded_plan(opt.reward_params, opt.value_params, opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix,
+                                      opt.action_advance, opt.track_params, targets, target_offset, opt.knot_params, phase,
+                                      opt.constraint_params, opt.score_params, opt.params, *args, **kw)
         if getattr(opt, "value_params", None) is not None:
             return self.valued_plan(opt.value_params, opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix, opt.action_advance,
                                     opt.track_params, targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params,
@@ -611,7 +615,7 @@ class HipEngine:
             return self.scored_plan(opt.score_params, opt.params, *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
-    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None):
+    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None, rew=None):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
         constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that).  track: None,
         or whether a tracked loop runs under TERMINATE constraints -- the tracking slot (`cadm_tracking_workspace_bytes`: the trajectory
@@ -619,7 +623,9 @@ class HipEngine:
         the loop underneath's views, and behind them the candidates' rate cost and the plan's device copy).  unc: None, or (terminate,
         actuator) -- the slot of a loop with an uncertainty term (`cadm_uncertain_workspace_bytes`: always with the trajectory view, the
         first-violation view under TERMINATE constraints, the actuator's views, and behind everything the step costs and the cost).  val:
-        None, or (terminate, actuator, uncertainty) -- the slot of a loop with a terminal value (`cadm_valued_workspace_bytes`)."""
+        None, or (terminate, actuator, uncertainty) -- the slot of a loop with a terminal value (`cadm_valued_workspace_bytes`).  rew:
+        None, or (terminate, actuator, uncertainty) -- the slot of a loop with a learned reward (`cadm_rewarded_workspace_bytes`: the
+        valued loop's, and behind everything the step rewards)."""
         slot = (bool(mppi), bool(traj)) if track is None else (bool(mppi), "track", bool(track))
         if act:
             slot = slot + ("act",)
@@ -627,9 +633,14 @@ class HipEngine:
             slot = (bool(mppi), "unc", bool(unc[0]), bool(unc[1]))
         if val is not None:
             slot = (bool(mppi), "val", bool(val[0]), bool(val[1]), bool(val[2]))
+        if rew is not None:
+            slot = (bool(mppi), "rew", bool(rew[0]), bool(rew[1]), bool(rew[2]))
         key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            if val is not None:
+            if rew is not None:
+                nbytes = self.lib.cadm_rewarded_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(rew[0])), int(bool(rew[1])),
+                                                                int(bool(rew[2])))
+            elif val is not None:
                 nbytes = self.lib.cadm_valued_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(val[0])), int(bool(val[1])),
                                                               int(bool(val[2])))
             elif unc is not None:
@@ -1169,32 +1180,38 @@ class HipEngine:
         `_lib.MAX_VALUE_LAYERS` (() is a linear V), each in 1 .. `_lib.MAX_VALUE_WIDTH`; activation -- "relu", "tanh" or "swish" (or its
         CADM_VALUE_* number), one for the net; weight -- what V is multiplied by before it is added to a return, finite (it carries a
         discount gamma^H).  Needs no GPU."""
+        prm = _lib.ValueParams()
+        HipEngine._net_params(prm, "value", hidden_sizes, activation, weight)
+        return prm
+
+    @staticmethod
+    def _net_params(prm, what, hidden_sizes, activation, weight):
+        """What `value_params` and `reward_params` share: the checks of a caller-supplied net's layers, activation and weight, and the
+        fields of `prm` (a `ValueParams` or a `RewardParams`) they fill."""
         try:
             hs = [hidden_sizes] if isinstance(hidden_sizes, (int, np.integer)) and not isinstance(hidden_sizes, bool) else list(hidden_sizes)
         except TypeError:
-            raise ValueError("value hidden_sizes must be a sequence of ints, got %r" % (hidden_sizes,)) from None
+            raise ValueError("%s hidden_sizes must be a sequence of ints, got %r" % (what, hidden_sizes)) from None
         if len(hs) > _lib.MAX_VALUE_LAYERS:
-            raise ValueError("a value net has at most %d hidden layers, got %d" % (_lib.MAX_VALUE_LAYERS, len(hs)))
+            raise ValueError("a %s net has at most %d hidden layers, got %d" % (what, _lib.MAX_VALUE_LAYERS, len(hs)))
         for h in hs:
             if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or not 1 <= int(h) <= _lib.MAX_VALUE_WIDTH:
-                raise ValueError("a value net's hidden widths must be ints in 1 .. %d, got %r" % (_lib.MAX_VALUE_WIDTH, h))
+                raise ValueError("a %s net's hidden widths must be ints in 1 .. %d, got %r" % (what, _lib.MAX_VALUE_WIDTH, h))
         if isinstance(activation, str) and activation in _lib.VALUE_ACTS:
             act = _lib.VALUE_ACTS[activation]
         elif not isinstance(activation, (bool, str)) and isinstance(activation, (int, np.integer)) and int(activation) in _lib.VALUE_ACTS.values():
             act = int(activation)
         else:
-            raise ValueError("value activation must be %s, got %r" % (" or ".join(repr(k) for k in _lib.VALUE_ACTS), activation))
+            raise ValueError("%s activation must be %s, got %r" % (what, " or ".join(repr(k) for k in _lib.VALUE_ACTS), activation))
         try:
             w = float(np.float32(weight))
         except (TypeError, ValueError):
-            raise ValueError("value weight must be a finite number, got %r" % (weight,)) from None
+            raise ValueError("%s weight must be a finite number, got %r" % (what, weight)) from None
         if isinstance(weight, bool) or not math.isfinite(w):
-            raise ValueError("value weight must be a finite number, got %r" % (weight,))
-        prm = _lib.ValueParams()
+            raise ValueError("%s weight must be a finite number, got %r" % (what, weight))
         prm.n_hidden, prm.activation, prm.weight = len(hs), act, w
         for l, h in enumerate(hs):
             prm.hidden[l] = int(h)
-        return prm
 
     @staticmethod
     def value_weights(weights):
@@ -1242,33 +1259,39 @@ class HipEngine:
         them, the input statistics obs_mean / obs_std [D] (None: 0 / 1; std finite and > 0; 1 / std is formed in float64 and rounded once
         to float32).  Shapes and finiteness are checked here; the library packs a copy of its own, so a second call replaces the net
         without touching anything else.  params None: the net is cleared."""
+        self._value_src = HipEngine._set_net(self, "set_value_net", params, self.D, weights, obs_mean, obs_std, "obs_mean", "obs_std")
+
+    def _set_net(self, who, params, K, weights, mean, std, mean_name, std_name):
+        """What `set_value_net` and `set_reward_net` share: the checks of a caller-supplied net K -> hidden -> 1 against its declared
+        `params` and of its input statistics [K] -- all of them before the library is looked at --, the staging, and the call of
+        cadm_<who>.  Returns what must stay alive until the next net (the copy is enqueued, not done); params None: the net is cleared,
+        and None."""
         if params is None:
-            self._check(self.lib.cadm_set_value_net(self._ctx, None, None, None, None, None, self.stream), "cadm_set_value_net")
-            self._value_src = None
-            return
+            self._check(getattr(self.lib, "cadm_" + who)(self._ctx, None, None, None, None, None, self.stream), "cadm_" + who)
+            return None
         layers, act = self.value_weights(weights)
-        dims = [self.D] + [int(params.hidden[l]) for l in range(params.n_hidden)] + [1]
+        dims = [K] + [int(params.hidden[l]) for l in range(params.n_hidden)] + [1]
         if len(layers) != len(dims) - 1:
-            raise ValueError("set_value_net: %d layers given, the declared net %r has %d" % (len(layers), dims, len(dims) - 1))
+            raise ValueError("%s: %d layers given, the declared net %r has %d" % (who, len(layers), dims, len(dims) - 1))
         for l, (w, b) in enumerate(layers):
             if w.shape != (dims[l], dims[l + 1]):
-                raise ValueError("set_value_net: layer %d is %r, the declared net %r needs %r" % (l, w.shape, dims, (dims[l], dims[l + 1])))
+                raise ValueError("%s: layer %d is %r, the declared net %r needs %r" % (who, l, w.shape, dims, (dims[l], dims[l + 1])))
         if act is not None and _lib.VALUE_ACTS[act] != params.activation:
-            raise ValueError("set_value_net: the module's activation %r is not the declared one" % (act,))
-        mean = np.zeros((self.D,), np.float64) if obs_mean is None else np.asarray(self._host(obs_mean), dtype=np.float64).reshape(-1)
-        std = np.ones((self.D,), np.float64) if obs_std is None else np.asarray(self._host(obs_std), dtype=np.float64).reshape(-1)
-        if mean.shape != (self.D,) or std.shape != (self.D,):
-            raise ValueError("set_value_net: obs_mean %r / obs_std %r, expected [%d]" % (mean.shape, std.shape, self.D))
+            raise ValueError("%s: the module's activation %r is not the declared one" % (who, act))
+        mean = np.zeros((K,), np.float64) if mean is None else np.asarray(self._host(mean), dtype=np.float64).reshape(-1)
+        std = np.ones((K,), np.float64) if std is None else np.asarray(self._host(std), dtype=np.float64).reshape(-1)
+        if mean.shape != (K,) or std.shape != (K,):
+            raise ValueError("%s: %s %r / %s %r, expected [%d]" % (who, mean_name, mean.shape, std_name, std.shape, K))
         if not np.all(np.isfinite(mean)):
-            raise ValueError("set_value_net: obs_mean must be finite")
+            raise ValueError("%s: %s must be finite" % (who, mean_name))
         if not np.all(np.isfinite(std) & (std > 0.0)):
-            raise ValueError("set_value_net: obs_std must be finite and > 0")
+            raise ValueError("%s: %s must be finite and > 0" % (who, std_name))
         dev = [(self._t(w), self._t(b)) for w, b in layers]
         mean_d, inv_d = self._t(mean.astype(np.float32)), self._t((1.0 / std).astype(np.float32))
         nl = len(dev)
         Wp, bp = (ct.c_void_p * nl)(*[w.data_ptr() for w, _ in dev]), (ct.c_void_p * nl)(*[b.data_ptr() for _, b in dev])
-        self._check(self.lib.cadm_set_value_net(self._ctx, ct.byref(params), Wp, bp, ptr(mean_d), ptr(inv_d), self.stream), "cadm_set_value_net")
-        self._value_src = (dev, mean_d, inv_d)      # (kept until the next net: the copy is enqueued, not done)
+        self._check(getattr(self.lib, "cadm_" + who)(self._ctx, ct.byref(params), Wp, bp, ptr(mean_d), ptr(inv_d), self.stream), "cadm_" + who)
+        return (dev, mean_d, inv_d)
 
     @staticmethod
     def _host(x):
@@ -1347,6 +1370,131 @@ class HipEngine:
         return self._loop_plan("valued_plan", self.lib.cadm_valued_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act, init_mean,
                                init_var, n, carry, carry_valid, seed, call, out, want_best_return,
                                val=(terminate, actuator is not None, uncertainty is not None))
+
+    # ------------------------------------------------------------------ learned reward (opt-in; csrc/reward.hip)
+    @staticmethod
+    def reward_params(inputs="obs_act_next_obs", hidden_sizes=(), activation="relu", weight=1.0):
+        """`cadm_reward_params`: inputs -- what the reward net reads per step: "next_obs" (s_{t+1}; K = D), "obs_act" (s_t, a_t; K = D + A)
+        or "obs_act_next_obs" (s_t, a_t, s_{t+1}; K = 2 D + A), or its CADM_REWARD_* number; hidden_sizes / activation / weight -- as
+        `value_params` (the net is K -> h_1 -> .. -> h_L -> 1; weight is what the step sum is multiplied by before it is added to a
+        return).  Needs no GPU."""
+        if isinstance(inputs, str) and inputs in _lib.REWARD_INPUTS:
+            inp = _lib.REWARD_INPUTS[inputs]
+        elif not isinstance(inputs, (bool, str)) and isinstance(inputs, (int, np.integer)) and int(inputs) in _lib.REWARD_INPUTS.values():
+            inp = int(inputs)
+        else:
+            raise ValueError("reward inputs must be %s, got %r" % (" or ".join(repr(k) for k in _lib.REWARD_INPUTS), inputs))
+        prm = _lib.RewardParams()
+        HipEngine._net_params(prm, "reward", hidden_sizes, activation, weight)
+        prm.inputs = inp
+        return prm
+
+    @staticmethod
+    def reward_input_dims(inputs, D, A):
+        """K of a reward net on D observation and A action dims; inputs: a name or a CADM_REWARD_* number."""
+        inp = _lib.REWARD_INPUTS[inputs] if isinstance(inputs, str) else int(inputs)
+        return (D, D + A, 2 * D + A)[inp]
+
+    def set_reward_net(self, params, weights=None, in_mean=None, in_std=None):
+        """`cadm_set_reward_net`: registers the reward net that `params` (`reward_params`) describes -- `weights` as `value_weights` takes
+        them, the input statistics in_mean / in_std [K] over the concatenated input (None: 0 / 1; std finite and > 0; 1 / std is formed
+        in float64 and rounded once to float32).  Shapes and finiteness are checked here; the library packs a copy of its own, so a second
+        call replaces the net without touching anything else.  params None: the net is cleared."""
+        K = None if params is None else HipEngine.reward_input_dims(params.inputs, self.D, self.A)
+        self._reward_src = HipEngine._set_net(self, "set_reward_net", params, K, weights, in_mean, in_std, "in_mean", "in_std")
+        self._reward_K = K
+
+    def reward_eval(self, x):
+        """`cadm_reward_eval`: R of already concatenated inputs x [..., K] -> [...] (device tensors), through the planner's kernel."""
+        x = self._t(x)
+        K = getattr(self, "_reward_K", None)
+        if K is None:
+            raise _lib.CadmError("reward_eval: no reward net is registered (call set_reward_net)")
+        if x.dim() < 1 or x.shape[-1] != K:
+            raise ValueError("reward_eval: x %r, expected [..., %d]" % (tuple(x.shape), K))
+        flat = x.reshape(-1, K).contiguous()
+        if flat.shape[0] < 1:
+            raise ValueError("reward_eval: no inputs")
+        r = torch.empty((flat.shape[0],), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_reward_eval(self._ctx, ptr(flat), int(flat.shape[0]), ptr(r), self.stream), "cadm_reward_eval")
+        return r.reshape(x.shape[:-1])
+
+    def reward_returns(self, traj, obs, actions, rows, params, first=None, want_steps=False, out=None):
+        """`cadm_reward_returns` on device tensors: traj [H,m,n,p,D] (a rollout's `traj_out`), obs [m,D], actions [m,n,H,A] (what the
+        rollout read), rows [m,n,p] -> rows + weight * S per row under `params` (`reward_params`, describing the registered net), S the
+        sum of R over the counted steps in ascending t.  first [m,n,p] int32 (None: every step counts): `constrain_returns`'
+        first_violation -- the steps t <= first count.  want_steps: (rows_out, steps [H,m,n,p], S [m,n,p]), steps NaN where not counted;
+        else the step rewards go to a cached workspace.  out: where the new rows go (may be `rows` itself)."""
+        traj, rows, obs, actions = self._t(traj), self._t(rows), self._t(obs), self._t(actions)
+        if traj.dim() != 5 or not traj.is_contiguous():
+            raise ValueError("reward_returns: traj %r: expected contiguous [H,m,n,p,D]" % (tuple(traj.shape),))
+        H, m, n, p, D = traj.shape
+        if (H, p, D) != (self.H, self.p, self.D):
+            raise ValueError("reward_returns: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (tuple(traj.shape), self.H, self.p, self.D))
+        if tuple(rows.shape) != (m, n, p) or not rows.is_contiguous():
+            raise ValueError("reward_returns: rows %r, expected contiguous %r" % (tuple(rows.shape), (m, n, p)))
+        if tuple(obs.shape) != (m, D) or not obs.is_contiguous():
+            raise ValueError("reward_returns: obs %r, expected contiguous %r" % (tuple(obs.shape), (m, D)))
+        if tuple(actions.shape) != (m, n, H, self.A) or not actions.is_contiguous():
+            raise ValueError("reward_returns: actions %r, expected contiguous %r" % (tuple(actions.shape), (m, n, H, self.A)))
+        if first is not None:
+            first = self._t(first, dtype=torch.int32)
+            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
+                raise ValueError("reward_returns: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
+        if out is None:
+            out = torch.empty_like(rows)
+        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rows.device:
+            raise ValueError("reward_returns: out must be a contiguous float32 device tensor %r" % ((m, n, p),))
+        steps = S = ws = None
+        if want_steps:
+            steps = torch.empty((H, m, n, p), dtype=torch.float32, device=self.device)
+            S = torch.empty((m, n, p), dtype=torch.float32, device=self.device)
+        else:
+            need = self.lib.cadm_reward_workspace_bytes(self._ctx, m, n)
+            ws = getattr(self, "_reward_ws", None)
+            if ws is None or ws.numel() < need:
+                ws = self._reward_ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.cadm_reward_returns(self._ctx, ct.byref(params), ptr(traj), ptr(obs), ptr(actions), ptr(first), m, n, ptr(rows),
+                                                 ptr(out), ptr(steps), ptr(S), ptr(ws), self.stream), "cadm_reward_returns")
+        return (out, steps, S) if want_steps else out
+
+    def rewarded_plan(self, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints,
+                      score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
+                      want_best_return=False):
+        """`cadm_rewarded_plan`: the loop of `valued_plan` with `reward.weight` times the registered reward net's step sum added to the
+        particle returns, behind the constraints and the tracking terms and in front of the terminal value (`reward`: a `reward_params`
+        describing the net of `set_reward_net`; None = none, and `valued_plan`'s launches).  Arguments behind `reward` as `valued_plan`;
+        the workspace is the slot of `cadm_rewarded_workspace_bytes`, cached apart from the others."""
+        if reward is None:
+            return self.valued_plan(value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints,
+                                    score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=carry, carry_valid=carry_valid,
+                                    seed=seed, call=call, out=out, want_best_return=want_best_return)
+        mppi, params = self._as_mppi_params(params)
+        m = int(np.shape(obs)[0])
+        if actuator is None:
+            prev = prefix = None
+        else:
+            for name, t in (("prev", prev), ("prefix", prefix)):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+                    raise ValueError("rewarded_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
+            if prev is None or (prefix is None and actuator.delay > 0):
+                raise ValueError("rewarded_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
+            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "rewarded_plan")
+        phase = self._phase(phase, m, "rewarded_plan")
+        T = 0
+        if track is None:
+            targets = offset = None
+        else:
+            targets, T, offset = self._targets(targets, offset, m, track.n, "rewarded_plan")
+        head = (ct.byref(reward), None if value is None else ct.byref(value), None if uncertainty is None else ct.byref(uncertainty),
+                None if actuator is None else ct.byref(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
+                None if track is None else ct.byref(track), ptr(targets), T, ptr(offset), None if knots is None else ct.byref(knots),
+                ptr(phase), None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi),
+                ct.byref(params))
+        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
+        return self._loop_plan("rewarded_plan", self.lib.cadm_rewarded_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return,
+                               rew=(terminate, actuator is not None, uncertainty is not None))
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

@@ -12,7 +12,7 @@ What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
   * `PlanOptions`: what a model's `cem_*` kwargs mean -- their checks, the switches, and the ctypes structs `HipEngine.opt_in_plan` hands to the library;
-  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`; `actuator=`: `cadm_actuated_plan`; `uncertainty=`: `cadm_uncertain_plan`; `value=`: `cadm_valued_plan`) one launch at a time, for the same purposes;
+  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`; `actuator=`: `cadm_actuated_plan`; `uncertainty=`: `cadm_uncertain_plan`; `value=`: `cadm_valued_plan`; `reward=`: `cadm_rewarded_plan`) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
@@ -31,8 +31,9 @@ FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/p
 
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
                                                        "params score_params constraints constraint_params knots knot_params actuator actuator_params "
-                                                       "action_advance value value_params uncertainty uncertainty_params tracking track_params target_advance",
-                                                       defaults=(None, None, None, None, True, None, None, None, None, None, None, True))):
+                                                       "action_advance reward reward_params value value_params uncertainty uncertainty_params tracking track_params "
+                                                       "target_advance",
+                                                       defaults=(None, None, None, None, True, None, None, None, None, None, None, None, None, True))):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
     `score`: None, or (mode name, kappa, k).  `constraints`: None, or (the list of dict(dim=, lo=, hi=), mode name, weight), with
@@ -47,7 +48,9 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
     `uncertainty_params` the `UncertaintyParams` built from it (None: no uncertainty term; for w="delta_std" a placeholder with w = 1
     that the model replaces whenever it pushes its normalisation statistics).
     `value`: None, or (the tuple of hidden widths, activation name, weight), with `value_params` the `ValueParams` built from it (None: no
-    terminal value).  The net itself is not an option: a model registers it at run time (`set_terminal_value`)."""
+    terminal value).  The net itself is not an option: a model registers it at run time (`set_terminal_value`).
+    `reward`: None, or (inputs name, the tuple of hidden widths, activation name, weight), with `reward_params` the `RewardParams` built
+    from it (None: no learned reward); the net is registered at run time too (`set_reward_net`)."""
     __slots__ = ()
 
     @staticmethod
@@ -56,14 +59,16 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                     process_group=None, n_particles=20, cem_constraints=None, cem_constraint_mode="penalty", cem_constraint_weight=None, *,
                     cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call", cem_tracking=None, cem_target_advance=True,
                     cem_action_delay=0, cem_action_rate_limit=None, cem_action_rate_cost=None, cem_action_advance=True, n_forwards=None,
-                    action_dim=None, cem_uncertainty=None, obs_dim=None, cem_terminal_value=None):
+                    action_dim=None, cem_uncertainty=None, obs_dim=None, cem_terminal_value=None, cem_reward_net=None):
         """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
         everything that needs no engine -- and folded into a `PlanOptions`.  n_forwards / action_dim: the model's horizon and action
         dims, what `cem_action_delay` and the lengths of `cem_action_rate_limit` / `cem_action_rate_cost` are checked against (None: the
         library checks them against the engine's).  cem_uncertainty: None, or dict(kind="epistemic" | "total", weight=lambda, w=None |
         float | [D] | "delta_std", form="var" | "std", cap=None) (`HipEngine.uncertainty_params`); obs_dim: the model's observation dims,
         what a list `w` is checked against.  cem_terminal_value: None, or dict(hidden_sizes=(..), activation="relu" | "tanh" | "swish",
-        weight=1.0) (`HipEngine.value_params`): the shape of the value net a model is given at run time."""
+        weight=1.0) (`HipEngine.value_params`): the shape of the value net a model is given at run time.  cem_reward_net: None, or
+        dict(inputs="next_obs" | "obs_act" | "obs_act_next_obs", hidden_sizes=(..), activation=, weight=1.0) (`HipEngine.reward_params`):
+        the shape of the reward net a model is given at run time; obs_dim / action_dim: what its input dims are checked against."""
         act_off = (cem_action_rate_limit is None and cem_action_rate_cost is None and isinstance(cem_action_delay, (int, np.integer))
                    and not isinstance(cem_action_delay, bool) and int(cem_action_delay) == 0)
         if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
@@ -71,12 +76,14 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                 cem_constraint_weight) == (0.0, 0, 1.0, "mean", False, "cem", 1.0, False, "mean", None, None, "penalty", None) \
                 and (cem_knot_interp, cem_knot_anchor) == ("hold", "call") and isinstance(cem_knots, (int, np.integer)) \
                 and not isinstance(cem_knots, bool) and int(cem_knots) == 1 and cem_tracking is None and cem_target_advance is True \
-                and act_off and cem_action_advance is True and cem_uncertainty is None and cem_terminal_value is None:
+                and act_off and cem_action_advance is True and cem_uncertainty is None and cem_terminal_value is None \
+                and cem_reward_net is None:
             return None
         if not use_cem:
             raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
                              "cem_score / cem_risk / cem_constraints / cem_knots / cem_tracking / cem_action_delay / cem_action_rate_limit / "
-                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value configure the CEM planner: they need use_cem=True")
+                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net configure the CEM planner: they need "
+                             "use_cem=True")
         value = vparams = None
         if cem_terminal_value is not None:
             if not isinstance(cem_terminal_value, dict) or set(cem_terminal_value) - {"hidden_sizes", "activation", "weight"}:
@@ -88,6 +95,21 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
             vparams = HipEngine.value_params(v["hidden_sizes"], v["activation"], v["weight"])
             value = (tuple(int(vparams.hidden[l]) for l in range(vparams.n_hidden)),
                      [k for k, x in _lib.VALUE_ACTS.items() if x == vparams.activation][0], float(vparams.weight))
+        reward = rparams = None
+        if cem_reward_net is not None:
+            if not isinstance(cem_reward_net, dict) or set(cem_reward_net) - {"inputs", "hidden_sizes", "activation", "weight"}:
+                raise ValueError("cem_reward_net must be dict(inputs=, hidden_sizes=, activation=, weight=), got %r" % (cem_reward_net,))
+            r = dict(inputs="obs_act_next_obs", hidden_sizes=(), activation="relu", weight=1.0)
+            r.update(cem_reward_net)
+            rparams = HipEngine.reward_params(r["inputs"], r["hidden_sizes"], r["activation"], r["weight"])
+            if obs_dim is not None and action_dim is not None:
+                K = HipEngine.reward_input_dims(rparams.inputs, int(obs_dim), int(action_dim))
+                if not 1 <= K <= _lib.MAX_REWARD_DIMS:
+                    raise ValueError("a reward net reads up to %d input dims, %r on %r observation and %r action dims are %d"
+                                     % (_lib.MAX_REWARD_DIMS, r["inputs"], obs_dim, action_dim, K))
+            reward = ([k for k, x in _lib.REWARD_INPUTS.items() if x == rparams.inputs][0],
+                      tuple(int(rparams.hidden[l]) for l in range(rparams.n_hidden)),
+                      [k for k, x in _lib.VALUE_ACTS.items() if x == rparams.activation][0], float(rparams.weight))
         uncertainty = uparams = None
         if cem_uncertainty is not None:
             if not isinstance(cem_uncertainty, dict) or not {"kind", "weight"} <= set(cem_uncertainty) \
@@ -188,8 +210,8 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                            constraints=constraints, constraint_params=cparams, knots=knots,
                            knot_params=None if knots is None else HipEngine.knot_params(knots[0], knots[1]), tracking=tracking,
                            track_params=tparams, target_advance=bool(cem_target_advance), actuator=actuator, actuator_params=aparams,
-                           action_advance=bool(cem_action_advance), uncertainty=uncertainty, uncertainty_params=uparams, value=value, value_params=vparams, **mppi,
-                           **icem)
+                           action_advance=bool(cem_action_advance), uncertainty=uncertainty, uncertainty_params=uparams, value=value, value_params=vparams, reward=reward,
+                           reward_params=rparams, **mppi, **icem)
 
 
 class Shard:
@@ -316,7 +338,7 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
 def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
               add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False,
               update="cem", temperature=1.0, relative=False, score=None, constraints=None, knots=None, phase=None, tracking=None, actuator=None,
-              action_advance=False, uncertainty=None, value=None):
+              action_advance=False, uncertainty=None, value=None, reward=None):
     """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
     tests with injected draws and for diagnostics.  update="mppi": the loop of `cadm_mppi_plan` -- the elite ids come from an elite
     refit into copies of mean / var, the distribution from `mppi_refit`.  score: a `HipEngine.score_params` (`cadm_scored_plan`; None: the
@@ -341,7 +363,11 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     value: a `HipEngine.value_params` describing the engine's registered value net (`cadm_valued_plan`; None: none) -- every rollout then
     records its trajectories and `value_returns` adds weight * V(last state) to the particle rows behind the constraints (under TERMINATE
     with their first violations) and the tracking terms, before the score; `return_info` carries `value` [m,n_it,p], V of every row (NaN
-    where skipped), and `value_rows`, the rows before the addition."""
+    where skipped), and `value_rows`, the rows before the addition.
+    reward: a `HipEngine.reward_params` describing the engine's registered reward net (`cadm_rewarded_plan`; None: none) -- every rollout
+    then records its trajectories and `reward_returns` adds weight * (the sum of R over the counted steps) to the particle rows behind the
+    constraints (under TERMINATE with their first violations) and the tracking terms, in front of the terminal value; `return_info`
+    carries `reward_steps` [H,m,n_it,p] (NaN where not counted), `reward_sum` [m,n_it,p] and `reward_rows`, the rows before the addition."""
     obs = engine._t(obs)
     mean, var = engine._t(init_mean).clone(), engine._t(init_var).clone()
     if knots is not None and knots.spacing == 1:
@@ -373,7 +399,7 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
         if actuator is not None:
             _, action_cost = engine.actuate_actions(actions, actuator[0], prev=actuator[1], prefix=actuator[2], want_cost=True)
         extra = {}
-        if constraints is None and tracking is None and uncertainty is None and value is None:
+        if constraints is None and tracking is None and uncertainty is None and value is None and reward is None:
             rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
         else:
             rows, traj = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it,
@@ -389,6 +415,10 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
                 untracked = rows
                 rows, cost = engine.tracking_returns(traj, untracked, tracking[0], tracking[1], offset=tracking[2], first=first, want_cost=True)
                 extra.update(traj=traj, track_cost=cost, rows_untracked=untracked)
+            if reward is not None:
+                unrewarded = rows
+                rows, steps, rsum = engine.reward_returns(traj, obs, actions, unrewarded, reward, first=first, want_steps=True)
+                extra.update(traj=traj, reward_steps=steps, reward_sum=rsum, reward_rows=unrewarded)
             if value is not None:
                 unvalued = rows
                 rows, v = engine.value_returns(traj, unvalued, value, first=first, want_v=True)

@@ -711,6 +711,80 @@ int cadm_valued_plan(cadm_ctx* ctx, const cadm_value_params* params, const cadm_
                      const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n, uint32_t seed,
                      uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
 
+/* Learned reward (no reference twin, OPT-IN): a caller-supplied reward net R on EVERY step of every particle's trajectory, so that a
+ * plan is scored by  return + weight * sum_t R_t  (+ the terminal value) and a reward that is no sum of one-dim terms -- a product of two
+ * dims, a distance in a plane, a contact or success signal, a reward known only from logged (s, a, s', r) -- can be planned against
+ * (MBPO, PlaNet, Dreamer, TD-MPC).  The term is ADDED to the env's own return; an env whose reward is entirely learned is declared with
+ * no reward terms.
+ * R is an MLP  K -> h_1 -> .. -> h_L -> 1  under the value net's conventions: L = n_hidden in 0 .. CADM_MAX_VALUE_LAYERS, every width in
+ * 1 .. CADM_MAX_VALUE_WIDTH, one hidden activation CADM_VALUE_RELU | _TANH | _SWISH, a linear output.  Its input for step t of particle
+ * row q = (env mi, candidate ni, particle j) is the concatenation that `inputs` selects:
+ *   CADM_REWARD_NEXT_OBS          s_{t+1}                 K = D
+ *   CADM_REWARD_OBS_ACT           s_t, a_t                K = D + A
+ *   CADM_REWARD_OBS_ACT_NEXT_OBS  s_t, a_t, s_{t+1}       K = 2 D + A
+ * with  s_0 = obs[mi],  s_t = traj[t-1,q] (t >= 1),  s_{t+1} = traj[t,q],  a_t = actions[mi,ni,t,:] -- the candidate buffer exactly as
+ * the rollout reads it (behind the injections, the knot shaping and the actuator pass), raw, not normalised.  K <= CADM_MAX_REWARD_DIMS.
+ * For one (t, q), all in float32 (csrc/reward.hip, csrc/mlp_chain.h):
+ *   x_k = (in_k - mean_k) * std_inv_k   over the K concatenated dims              one subtract, one multiply
+ *   layer with K inputs, unit u:  acc = b[u];  for k = 0 .. K4-1 ascending:  acc = fmaf(W[k][u], x_k, acc)
+ *       (K4: K rounded up to 4; W and x are exact zeros for K <= k < K4; the bias seeds the accumulator) -- the chain of the value net
+ *   hidden: the activation;   output: the sum itself.
+ * The step sum:  S[q] = ((0 + R_0) + R_1) + ..,  plain float32 adds in ascending t over the COUNTED steps: every step without `first`;
+ * with first [m,n,p] (cadm_constrain_returns' first_violation, TERMINATE mode) the steps t <= first[q] -- the step that violates still
+ * pays, later steps are not counted and their states are not read.   rows_out[q] = rows_in[q] + weight * S[q]:  one multiply, then one
+ * add, no fma.  A counted step whose input holds a non-finite value has R = NaN, set explicitly, so S and the row are NaN (a diverged
+ * rollout's row already is).
+ * Determinism: R(t, q) is one chain in ascending k, the step sum is sequential in t, no floating-point atomics: the same bits run to run,
+ * in any batch, at any row position, for any m, n or p, from cadm_reward_eval as from the planner.
+ * cadm_set_reward_net: W[l] [in,out] row-major and b[l] [out] (l = 0 .. n_hidden), mean [K] and std_inv [K] are DEVICE pointers; they are
+ * copied and packed into memory the ctx owns, on `stream`.  A second call replaces the net (one of the same shape allocates nothing);
+ * params NULL clears it.  params->weight is not kept: every call below brings its own.
+ * cadm_reward_eval: r_out[r] = R(x[r]) for ALREADY CONCATENATED inputs x [R,K], through the same per-row chain.
+ * cadm_reward_returns: traj [H,m,n,p,D] (a rollout's traj_out, n its packed candidate count), obs [m,D], actions [m,n,H,A], first
+ * [m,n,p] or NULL.  step_out [H,m,n,p] or NULL: R of every (step, row), NaN for the steps that are not counted; sum_out [m,n,p] or NULL:
+ * S.  rows_out may alias rows_in.  workspace: cadm_reward_workspace_bytes(ctx, m, n) bytes (H m n p floats, where the step rewards go
+ * when step_out is NULL; may be NULL with step_out).  params must describe the registered net (inputs, layer count, widths, activation),
+ * else CADM_EINVAL; no registered net: CADM_ESTATE.
+ * Refusals, before any HIP call: CADM_EINVAL for null pointers, n_hidden outside 0 .. 4, a width outside 1 .. 512, an unknown
+ * activation, unknown inputs, a weight that is not finite, K > CADM_MAX_REWARD_DIMS, a discrete ctx (cartpole), a candidate-sharded ctx,
+ * activation tiles (two regions of 16 rows x the widest layers, each width rounded up to 4) beyond the 160 KiB of LDS. */
+#define CADM_MAX_REWARD_DIMS 256
+#define CADM_REWARD_NEXT_OBS 0
+#define CADM_REWARD_OBS_ACT 1
+#define CADM_REWARD_OBS_ACT_NEXT_OBS 2
+typedef struct cadm_reward_params {
+    int32_t n_hidden;                          /* L: 0 .. CADM_MAX_VALUE_LAYERS */
+    int32_t hidden[CADM_MAX_VALUE_LAYERS];     /* h_1 .. h_L, each 1 .. CADM_MAX_VALUE_WIDTH */
+    int32_t activation;                        /* CADM_VALUE_RELU | CADM_VALUE_TANH | CADM_VALUE_SWISH */
+    int32_t inputs;                            /* CADM_REWARD_NEXT_OBS | CADM_REWARD_OBS_ACT | CADM_REWARD_OBS_ACT_NEXT_OBS */
+    float weight;                              /* finite */
+} cadm_reward_params;
+int cadm_set_reward_net(cadm_ctx* ctx, const cadm_reward_params* params, const float* const* W, const float* const* b, const float* mean,
+                        const float* std_inv, void* stream);
+int cadm_reward_eval(cadm_ctx* ctx, const float* x, int R, float* r_out, void* stream);
+size_t cadm_reward_workspace_bytes(cadm_ctx* ctx, int m, int n);
+int cadm_reward_returns(cadm_ctx* ctx, const cadm_reward_params* params, const float* traj, const float* obs, const float* actions,
+                        const int32_t* first, int m, int n, const float* rows_in, float* rows_out, float* step_out, float* sum_out,
+                        void* workspace, void* stream);
+/* The loop of cadm_valued_plan with that term in the particle returns: the outermost entry of the nest.  Every iteration's rollout
+ * records its trajectories; TERMINATE constraints write their first violations into the workspace.  Per iteration: rollout ->
+ * constraints -> tracking -> rows[q] += weight * S[q] on the particle rows [m,n_it,p] -> the terminal value -> cadm_particle_score (a
+ * risk-aware score sees return + learned reward (+ value) per particle) -> the actuator's and the uncertainty term's costs off the
+ * candidate score, unchanged -> the refit.  PENALTY constraints do not gate the reward.  params NULL: exactly the launches of
+ * cadm_valued_plan.  Refusals: those of cadm_valued_plan and of cadm_reward_returns.  workspace:
+ * cadm_rewarded_workspace_bytes(ctx, m, n, K, mppi, terminate, actuator, uncertainty) with params set -- the loop underneath's WITH the
+ * trajectory view, under TERMINATE constraints the first-violation view, and behind everything the step rewards [H,m,n,p] (0 for bad
+ * arguments); with params NULL that of cadm_valued_plan. */
+size_t cadm_rewarded_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty);
+int cadm_rewarded_plan(cadm_ctx* ctx, const cadm_reward_params* params, const cadm_value_params* value,
+                       const cadm_uncertainty_params* uncertainty, const cadm_actuator_params* actuator, float* prev_io, float* prefix_io,
+                       int advance, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                       const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                       const cadm_score_params* score, int update, const cadm_mppi_params* mppi_params, const float* obs,
+                       const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                       int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                       float* best_return_out, void* stream);
+
 /* One training step =sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
