@@ -17,6 +17,25 @@ KINDS = {      # kind: (D, A, engine p, H, m, n, seed, constrained dims, band wi
 }
 HALFCHEETAH_B = (2, 8, 2, 1, 20, 18, 6)      # tests/test_gpu_forecast.py's shape (b): synth_traj's arguments
 
+# The engines of tests/test_gpu_terms_envelope.py -- the planner terms behind the rollout (uncertainty, tracking, actuator, knots, value
+# and reward nets) off the geometries their own files run on; the CPU tests of the restatements read the shapes from here.
+TERM_ENGINES = {      # name: (env, D, A, E, p, H); "widest" is helpers.corner_spec's declaration, the others are built-in kinds
+    "pend": ("pendulum", 3, 1, 5, 5, 5),
+    "ant": ("ant", 28, 8, 5, 10, 5),
+    "slim": ("slim_humanoid", 45, 17, 5, 15, 3),
+    "slim35": ("slim_humanoid", 45, 17, 5, 35, 3),
+    "wide": ("widest", 48, 24, 5, 10, 3),
+    "long": ("halfcheetah", 18, 6, 5, 5, 40),
+    "one": ("halfcheetah", 18, 6, 5, 5, 1),
+    "p1": ("halfcheetah", 18, 6, 1, 1, 5),
+}
+
+
+def term_traj(name, m, n, seed):
+    """`synth_traj` at the shape of one of TERM_ENGINES"""
+    _, D, A, _, p, H = TERM_ENGINES[name]
+    return synth_traj(seed, H, m, n, p, D, A)
+
 
 def synth_traj(seed, H, m, n, p, D, A):
     """(traj [H,m,n,p,D], obs [m,D], actions [m,n,H,A]) float32: per-dim scales 0.5 .. 3 and offsets of order 1."""

@@ -50,10 +50,16 @@ def test_kernel_against_restatement(engines, name, m, n):
     candidates each at A = 6), 3 x 100 candidates span workgroups and envs inside one, n = 1 is the plan's own pass.  A second pass
     changes no bit; inert parameters copy their input and cost 0; the [m,H,A] form is the n = 1 form."""
     _, eng = engines(name)
+    check_kernel(eng, name, m, n)
+
+
+def check_kernel(eng, name, m, n, make_case=aref.make_case):
+    """The body of `test_kernel_against_restatement` on any engine; `make_case`: `actuator_ref.make_case`, or a function of its
+    arguments (where its weights would all be zero).  Returns the worst |err| / bound of the cost."""
     H, A = eng.H, eng.A
     worst = 0.0
     for d in (0, 1, H - 1):
-        seqs, dl, w, prev, prefix = aref.make_case(m, n, H, A, d, seed=10 * m + n + d, nan_env=m - 1, outside=True)
+        seqs, dl, w, prev, prefix = make_case(m, n, H, A, d, seed=10 * m + n + d, nan_env=m - 1, outside=True)
         ref, cost_ref, S = aref.actuate(seqs, d, dl, w, prev, prefix, eng.cfg.lower_bound, eng.cfg.upper_bound)
         prm = _params(eng, d, dl, w)
         dev = eng._t(seqs).clone()
@@ -86,6 +92,7 @@ def test_kernel_against_restatement(engines, name, m, n):
         flat, c1 = eng.actuate_actions(eng._t(seqs[:, 0]).clone(), prm, prev=prev, prefix=prefix, want_cost=True)
         assert tuple(flat.shape) == (m, H, A) and tuple(c1.shape) == (m,)
         np.testing.assert_array_equal(_bits(_np(flat)), _bits(ref[:, 0]))
+    return worst
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 2: the loop
@@ -98,6 +105,18 @@ def _state(eng, d, seed):
     if d:
         prefix[0, 0, 1] = np.nan
     return eng._t(prev).clone(), eng._t(prefix).clone()
+
+
+def _check_iterations(eng, info, d, dl, w, before):
+    """every stepwise iteration: the score behind the actuator's subtraction (`cand`, or `unc_score` where an uncertainty term follows)
+    is float32(score - cost) bit for bit, the candidates are feasible against the state `before` = (prev, prefix) the call started
+    from (a second pass changes nothing), and the cost is the restatement's within the bound"""
+    for x in info:
+        acts, cost, score, cand = _np(x["actions"]), _np(x["action_cost"]), _np(x["score"]), _np(x["unc_score" if "unc_score" in x else "cand"])
+        np.testing.assert_array_equal(_bits(cand), _bits((score - cost).astype(F)))
+        ref, cost_ref, S = aref.actuate(acts, d, dl, w, before[0], before[1], eng.cfg.lower_bound, eng.cfg.upper_bound)
+        np.testing.assert_array_equal(_bits(ref), _bits(acts), err_msg="an iteration's candidates are not feasible")
+        assert (np.abs(cost - cost_ref) <= aref.bound(S, eng.H, eng.A)).all() and (cost_ref[0] > 0).all()
 
 
 LOOP = [("hc5-vanilla", "cem", False, 0, 1, 1), ("hc5", "cem", True, 2, 1, 2), ("hc5", "mppi", False, 2, 2, 4), ("hc5-vanilla", "mppi", True, 0, 1, 0),
@@ -149,12 +168,7 @@ def test_fused_equals_stepwise(engines, name, update, best, K, r, d):
         assert aref.window_ok(a, dl, before[0], eng.cfg.lower_bound, eng.cfg.upper_bound, free=~pinned).all(), "windows of call %d" % call
         if best:      # the last pass over the best sequence is a bitwise no-op
             np.testing.assert_array_equal(_bits(a), _bits(_np(extra["best_seq"])))
-        for x in info:
-            acts, cost, score, cand = _np(x["actions"]), _np(x["action_cost"]), _np(x["score"]), _np(x["cand"])
-            np.testing.assert_array_equal(_bits(cand), _bits((score - cost).astype(F)))
-            ref, cost_ref, S = aref.actuate(acts, d, dl, w, before[0], before[1], eng.cfg.lower_bound, eng.cfg.upper_bound)
-            np.testing.assert_array_equal(_bits(ref), _bits(acts), err_msg="an iteration's candidates are not feasible")
-            assert (np.abs(cost - cost_ref) <= aref.bound(S, H, A)).all() and (cost_ref[0] > 0).all()
+        _check_iterations(eng, info, d, dl, w, before)
         mean = np.concatenate([a[:, 1:], np.zeros((M, 1, A), F)], axis=1)      # the samplers' warm start
     # the model matters: without it, another plan
     other = _np(eng.tracking_plan(None, None, None, knots, phase, None, None, prm, *args, mean, var, N, *zero_carry(eng, M, K, H), seed=4, call=2))

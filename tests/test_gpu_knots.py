@@ -61,13 +61,19 @@ def test_shape_actions_against_numpy(gpu, H, r, interp):
     at the knot steps and in held tails, elsewhere within 2^-22 absolute (the reference rounds the float64 expression once; the kernel
     rounds the difference, the weight and the fused multiply-add: 2^-24 + 2^-25 + 2^-25 on values in [-1, 1], plus the reference's 2^-25);
     nothing leaves [-1, 1]; the floats behind the m n sequences are untouched."""
-    m = 3
-    _, eng = _engine(H, False, m)
+    _, eng = _engine(H, False, 3)
+    check_shape_actions(eng, r, interp)
+
+
+def check_shape_actions(eng, r, interp, ns=(1, 37, 64)):
+    """The body of `test_shape_actions_against_numpy` on any engine (its H and A), for n in `ns`.  Returns the largest error of an
+    interpolated step against float64."""
+    m, H, A = 3, eng.H, eng.A
     knots, code = HipEngine.knot_params(r, interp), _lib.KNOT_INTERPS[interp]
     rng = np.random.default_rng(100 * H + r)
     worst = 0.0
     for phases in ((0, 1, r - 1), (-1, r, 2 * r + 1), None):
-        for n in (1, 37, 64):
+        for n in ns:
             used = m * n * H * A
             host = rng.uniform(-1, 1, (used + 5 * H * A + 3,)).astype(np.float32)
             host[rng.integers(0, host.size, 40)] = 1.0
@@ -99,6 +105,7 @@ def test_shape_actions_against_numpy(gpu, H, r, interp):
     np.testing.assert_array_equal(_bits(_np(a)), _bits(_np(b)[:, 0]))
     # spacing 1: the identity
     np.testing.assert_array_equal(_bits(_np(eng.shape_actions(x.clone(), HipEngine.knot_params(1, interp), ph))), _bits(_np(x)))
+    return worst
 
 
 def test_argument_checks_return_einval(gpu):

@@ -71,18 +71,27 @@ def test_kernel_against_restatement(engines, act):
             prm, layers = _set(eng, inputs, hidden, act, seed=10 + gi, weight=0.5)
             for m, n in ((3, 11), (3, 1)):
                 traj, obs, actions = _case(eng, m, n, 30 + gi + 7 * ii)
-                x = rref.gather_inputs(traj, obs, actions, inputs)
-                ref = rref.reward64(x, layers, act)
                 rows = np.random.default_rng(gi).standard_normal((m, n, eng.p)).astype(F)
-                out, steps, S = (_np(t) for t in eng.reward_returns(traj, obs, actions, rows, prm, want_steps=True))
                 what = "%s %s %r m=%d n=%d" % (act, inputs, hidden, m, n)
-                assert steps.shape == (eng.H, m, n, eng.p) and np.isfinite(steps).all(), what
-                worst = max(worst, floored_rel(steps, ref) / 1e-5)
-                assert_close(steps, ref, what=what)
-                np.testing.assert_array_equal(_bits(_np(eng.reward_eval(x))), _bits(steps), err_msg=what + ": cadm_reward_eval against step_out")
-                np.testing.assert_array_equal(_bits(S), _bits(rref.step_sum(steps)), err_msg=what)
-                np.testing.assert_array_equal(_bits(out), _bits(rref.update(rows, S, 0.5)), err_msg=what)
+                worst = max(worst, check_kernel_case(eng, prm, layers, act, inputs, traj, obs, actions, rows, 0.5, what)[0])
     print("\n[%s] worst |err| / (1e-5 of scale): %.3f" % (act, worst))
+
+
+def check_kernel_case(eng, prm, layers, act, inputs, traj, obs, actions, rows, weight, what, mean=None, std=None):
+    """`cadm_reward_returns`' step_out against the float64 restatement at 1e-5 of scale; `cadm_reward_eval` on the concatenated inputs
+    gives step_out's bits; the sum and the rows are the restatement's from those bits.  Returns (|err| / (1e-5 of scale), step_out,
+    the restatement's step rewards)."""
+    m, n = traj.shape[1:3]
+    x = rref.gather_inputs(traj, obs, actions, inputs)
+    ref = rref.reward64(x, layers, act, mean, std)
+    out, steps, S = (_np(t) for t in eng.reward_returns(traj, obs, actions, rows, prm, want_steps=True))
+    assert steps.shape == (eng.H, m, n, eng.p) and np.isfinite(steps).all(), what
+    ratio = floored_rel(steps, ref) / 1e-5
+    assert_close(steps, ref, what=what)
+    np.testing.assert_array_equal(_bits(_np(eng.reward_eval(x))), _bits(steps), err_msg=what + ": cadm_reward_eval against step_out")
+    np.testing.assert_array_equal(_bits(S), _bits(rref.step_sum(steps)), err_msg=what)
+    np.testing.assert_array_equal(_bits(out), _bits(rref.update(rows, S, weight)), err_msg=what)
+    return ratio, steps, ref
 
 
 def test_kernel_at_the_widest_net(engines):

@@ -61,8 +61,38 @@ ENGINE_OF = {"hopper-240": "hopper", "hopper-45": "hopper", "halfcheetah-320": "
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 1: the kernel
+def check_kernel_case(eng, H, K, case, what, all_nan_env=None):
+    """One (traj, rows, terms, targets, offset) case of `cadm_tracking_returns` against tests/tracking_ref.py within the derived bound: the
+    rows and `cost_out`, `rows_in` left alone, rows with nothing counted bit for bit, `rows_out` aliasing `rows_in`.  Returns (worst
+    |err| / bound of the rows, of the cost, the number of rows with nothing counted, the kernel's rows)."""
+    traj, rows, terms, targets, offset = case
+    ref, cost_ref, S, counted = tref.tracking(traj, rows, terms, targets, offset)
+    t_dev, r_dev = eng._t(traj), eng._t(rows)
+    out, cost = eng.tracking_returns(t_dev, r_dev, terms, targets, offset=offset, want_cost=True)
+    out, cost = _np(out), _np(cost)
+    np.testing.assert_array_equal(_bits(_np(r_dev)), _bits(rows), err_msg=what + ": rows_in was written")
+    none = counted == 0
+    np.testing.assert_array_equal(_bits(out[none]), _bits(rows[none]), err_msg=what + ": rows with nothing counted")
+    assert (cost[none] == 0).all()
+    lim, lim_cost = tref.bound(S, ref, H, K), tref.bound(S, None, H, K)
+    err, err_cost = np.abs(out - ref), np.abs(cost - cost_ref)
+    assert np.isfinite(out).all()
+    assert (err[~none] <= lim[~none]).all(), "%s: rows, worst |err| / bound %.3f" % (what, (err[~none] / lim[~none]).max())
+    assert (err_cost[~none] <= lim_cost[~none]).all(), "%s: cost, worst |err| / bound %.3f" % (what, (err_cost[~none] / lim_cost[~none]).max())
+    worst = worst_cost = 0.0
+    if (~none).any():
+        worst = float((err[~none] / lim[~none]).max())
+        worst_cost = float((err_cost[~none] / np.maximum(lim_cost[~none], 1e-300)).max())
+    if all_nan_env is not None:
+        assert none[all_nan_env].all()
+    alias = r_dev.clone()
+    assert eng.tracking_returns(t_dev, alias, terms, targets, offset=offset, out=alias) is alias
+    np.testing.assert_array_equal(_bits(_np(alias)), _bits(out), err_msg=what + ": rows_out aliasing rows_in")
+    return worst, worst_cost, int(none.sum()), out
+
+
 @pytest.mark.parametrize("K", [1, 16])
-@pytest.mark.parametrize("shape", list(tref.SHAPES))
+@pytest.mark.parametrize("shape", list(ENGINE_OF))
 def test_kernel_against_restatement(engines, shape, K):
     """`cadm_tracking_returns` on `synth_traj` against tests/tracking_ref.py within the derived bound, for T in {1, H, H - 1, H + 3} --
     K = 1: each kind alone; K = 16: the three kinds in turn -- with offsets that are negative, in range and beyond T, a fifth of every
@@ -78,30 +108,10 @@ def test_kernel_against_restatement(engines, shape, K):
     skipped_rows = 0
     for T in (1, H, H - 1, H + 3):
         for kinds in ([(k,) for k in tref.KINDS] if K == 1 else [tref.KINDS]):
-            traj, rows, terms, targets, offset = tref.make_case(shape, K, T, kinds=kinds, seed=len(kinds[0]))
-            ref, cost_ref, S, counted = tref.tracking(traj, rows, terms, targets, offset)
-            t_dev, r_dev = eng._t(traj), eng._t(rows)
-            out, cost = eng.tracking_returns(t_dev, r_dev, terms, targets, offset=offset, want_cost=True)
-            out, cost = _np(out), _np(cost)
+            case = tref.make_case(shape, K, T, kinds=kinds, seed=len(kinds[0]))
             what = "%s K=%d T=%d %s" % (shape, K, T, "/".join(kinds))
-            np.testing.assert_array_equal(_bits(_np(r_dev)), _bits(rows), err_msg=what + ": rows_in was written")
-            none = counted == 0
-            skipped_rows += int(none.sum())
-            np.testing.assert_array_equal(_bits(out[none]), _bits(rows[none]), err_msg=what + ": rows with nothing counted")
-            assert (cost[none] == 0).all()
-            lim, lim_cost = tref.bound(S, ref, H, K), tref.bound(S, None, H, K)
-            err, err_cost = np.abs(out - ref), np.abs(cost - cost_ref)
-            assert np.isfinite(out).all()
-            assert (err[~none] <= lim[~none]).all(), "%s: rows, worst |err| / bound %.3f" % (what, (err[~none] / lim[~none]).max())
-            assert (err_cost[~none] <= lim_cost[~none]).all(), "%s: cost, worst |err| / bound %.3f" % (what, (err_cost[~none] / lim_cost[~none]).max())
-            if (~none).any():
-                worst = max(worst, float((err[~none] / lim[~none]).max()))
-                worst_cost = max(worst_cost, float((err_cost[~none] / np.maximum(lim_cost[~none], 1e-300)).max()))
-            if m == 4:
-                assert none[tref.ALL_NAN_ENV].all()
-            alias = r_dev.clone()
-            assert eng.tracking_returns(t_dev, alias, terms, targets, offset=offset, out=alias) is alias
-            np.testing.assert_array_equal(_bits(_np(alias)), _bits(out), err_msg=what + ": rows_out aliasing rows_in")
+            r, rc, skipped, _ = check_kernel_case(eng, H, K, case, what, tref.ALL_NAN_ENV if m == 4 else None)
+            worst, worst_cost, skipped_rows = max(worst, r), max(worst_cost, rc), skipped_rows + skipped
     assert m != 4 or skipped_rows > 0
     print("\n[%s K=%d] worst |err| / bound: rows %.3f, cost %.3f" % (shape, K, worst, worst_cost))
 

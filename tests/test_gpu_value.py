@@ -63,18 +63,25 @@ def test_kernel_against_restatement(engines, act):
         prm, layers = _set(eng, hidden, act, seed=10 + gi, weight=0.5)
         for m, n in ((3, 11), (3, 1)):
             traj = _traj(eng, m, n, 30 + gi)
-            states = traj[-1].reshape(-1, eng.D)
-            ref = vref.value(states, layers, act)
-            got = _np(eng.value_eval(states))
-            what = "%s %r %d rows" % (act, hidden, states.shape[0])
-            assert got.shape == (m * n * eng.p,) and np.isfinite(got).all(), what
-            worst = max(worst, floored_rel(got, ref) / 1e-5)
-            assert_close(got, ref, what=what)
             rows = np.random.default_rng(gi).standard_normal((m, n, eng.p)).astype(F)
-            out, v = eng.value_returns(traj, rows, prm, want_v=True)
-            np.testing.assert_array_equal(_bits(_np(v)).reshape(-1), _bits(got), err_msg=what + ": v_out against cadm_value_eval")
-            np.testing.assert_array_equal(_bits(_np(out)), _bits(vref.update(rows, _np(v), 0.5)), err_msg=what)
+            worst = max(worst, check_kernel_case(eng, prm, layers, act, traj, rows, 0.5, "%s %r %d rows" % (act, hidden, m * n * eng.p))[0])
     print("\n[%s] worst |err| / (1e-5 of scale): %.3f" % (act, worst))
+
+
+def check_kernel_case(eng, prm, layers, act, traj, rows, weight, what, mean=None, std=None):
+    """`cadm_value_eval` of traj's last states against the float64 restatement at 1e-5 of scale; `cadm_value_returns`' v_out has its bits,
+    and the rows are the row update from them.  Returns (|err| / (1e-5 of scale), V float32, the restatement's V)."""
+    m, n = traj.shape[1:3]
+    states = traj[-1].reshape(-1, eng.D)
+    ref = vref.value(states, layers, act, mean, std)
+    got = _np(eng.value_eval(states))
+    assert got.shape == (m * n * eng.p,) and np.isfinite(got).all(), what
+    ratio = floored_rel(got, ref) / 1e-5
+    assert_close(got, ref, what=what)
+    out, v = eng.value_returns(traj, rows, prm, want_v=True)
+    np.testing.assert_array_equal(_bits(_np(v)).reshape(-1), _bits(got), err_msg=what + ": v_out against cadm_value_eval")
+    np.testing.assert_array_equal(_bits(_np(out)), _bits(vref.update(rows, _np(v), weight)), err_msg=what)
+    return ratio, got, ref
 
 
 def test_kernel_at_the_widest_net(engines):

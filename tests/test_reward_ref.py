@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import reward_ref as rref
+import value_ref as vref
 from behind_rollout import synth_traj
 from cadm_amd import _lib
 from cadm_amd.engine import HipEngine
@@ -48,6 +49,29 @@ def test_float32_chain_against_float64(inputs, hidden, act):
     assert emu.dtype == F and emu.shape == (H, m, n, p) and np.isfinite(ref).all()
     assert_close(emu, ref, what="%s %r %s" % (inputs, hidden, act))
     print("\n[%s %r %s] float32 chain against float64: %.2e of scale" % (inputs, hidden, act, floored_rel(emu, ref)))
+
+
+ENVELOPE = [(e, i, h, a) for e in ("pend", "slim", "wide") for i in rref.INPUTS for h in vref.ENVELOPE_NETS for a in vref.ACTS] + \
+    [("ant", i, (130, 66), a) for i in rref.INPUTS for a in vref.ACTS]
+
+
+@pytest.mark.parametrize("name,inputs,hidden,act", ENVELOPE, ids=["%s-%s-%s-%s" % (e, i, "x".join(map(str, h)), a) for e, i, h, a in ENVELOPE])
+def test_float32_chain_at_the_envelope_shapes(name, inputs, hidden, act):
+    """The nets tests/test_gpu_terms_envelope.py registers (widths off the multiples of 4 and 64, four hidden layers) on its inputs
+    (K = 3, 4, 7 on pendulum; 45, 62, 107 on slim_humanoid; 48, 72, 120 at the envelope's corner; 28, 36, 64 on ant with (130, 66); 3 x 11 candidates): the
+    float32 chain stays within the GPU test's bar of the float64 restatement, and the nets meet that file's liveness condition."""
+    import behind_rollout as br
+    _, D, A = br.TERM_ENGINES[name][:3]
+    x = rref.gather_inputs(*br.term_traj(name, 3, 11, 91), inputs)
+    K = rref.input_dims(inputs, D, A)
+    layers = vref.envelope_net(K, hidden)
+    share, spread = vref.liveness(x, layers, act)
+    assert share >= 0.5 and spread > 1e-3, "%s %s %r %s: live share %.2f, output spread %.2e" % (name, inputs, hidden, act, share, spread)
+    ref = rref.reward64(x, layers, act)
+    emu = rref.emulate32(x, layers, act)
+    assert emu.dtype == F and np.isfinite(ref).all()
+    assert_close(emu, ref, what="%s %s %r %s" % (name, inputs, hidden, act))
+    print("\n[%s %s %r %s] float32 chain against float64: %.2e of scale, live share %.2f" % (name, inputs, hidden, act, floored_rel(emu, ref), share))
 
 
 @pytest.mark.parametrize("inputs", rref.INPUTS)

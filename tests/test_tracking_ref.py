@@ -21,7 +21,7 @@ CASES = [(s, K, T) for s in tref.SHAPES for K in (1, 16) for T in (1, tref.SHAPE
 def _first(shape, seed):
     H, m, n, p = tref.SHAPES[shape][:4]
     first = np.random.default_rng(seed).integers(0, H + 1, (m, n, p)).astype(np.int32)
-    first[0, 0, 0], first[0, 0, 1] = 0, H
+    first.reshape(-1)[:2] = 0, H      # (rows (0, 0, 0) and (0, 0, 1) where p > 1)
     return first
 
 

@@ -41,6 +41,28 @@ def test_float32_chain_against_float64(hidden, act):
     print("\n[%r %s] float32 chain against float64: %.2e of scale" % (hidden, act, floored_rel(emu, ref)))
 
 
+ENVELOPE = [(e, h, a) for e in ("pend", "slim", "wide") for h in vref.ENVELOPE_NETS for a in vref.ACTS] + [("ant", (130, 66), a) for a in vref.ACTS]
+
+
+@pytest.mark.parametrize("name,hidden,act", ENVELOPE, ids=["%s-%s-%s" % (e, "x".join(map(str, h)), a) for e, h, a in ENVELOPE])
+def test_float32_chain_at_the_envelope_shapes(name, hidden, act):
+    """The nets tests/test_gpu_terms_envelope.py registers (widths off the multiples of 4 and 64, four hidden layers) on its inputs
+    (D = 3, 45, 48, and 28 with (130, 66); 3 x 11 candidates): the float32 chain stays within the GPU test's bar of the float64 restatement, and the nets meet
+    that file's liveness condition -- every hidden layer has a row with at least half of its units non-zero, and the output's standard
+    deviation over the rows is above 1e-3 of its largest magnitude."""
+    import behind_rollout as br
+    D = br.TERM_ENGINES[name][1]
+    states = br.term_traj(name, 3, 11, 91)[0][-1].reshape(-1, D)
+    layers = vref.envelope_net(D, hidden)
+    share, spread = vref.liveness(states, layers, act)
+    assert share >= 0.5 and spread > 1e-3, "%s %r %s: live share %.2f, output spread %.2e" % (name, hidden, act, share, spread)
+    ref = vref.value(states, layers, act)
+    emu = vref.emulate32(states, layers, act)
+    assert emu.dtype == F and np.isfinite(ref).all()
+    assert_close(emu, ref, what="%s %r %s" % (name, hidden, act))
+    print("\n[%s %r %s] float32 chain against float64: %.2e of scale, live share %.2f" % (name, hidden, act, floored_rel(emu, ref), share))
+
+
 def test_non_finite_states_and_the_update():
     """A non-finite value anywhere in a state makes V NaN in both statements, relu or not, and nothing else; the row update is one float32
     multiply and one float32 add, and a row with first < H keeps its bits."""

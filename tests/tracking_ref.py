@@ -133,21 +133,33 @@ SHAPES = {      # name: (H, m, n, p, D, A, offsets) -- the geometries of tests/t
     "hopper-240": (3, 4, 12, 5, 11, 3, (-2, 1, 0, None)),      # 240 rows = 3 full workgroups + 48; 60 rows per env: workgroups span envs
     "hopper-45": (3, 1, 9, 5, 11, 3, (1,)),                    # fewer rows than a workgroup; 495 floats per step: odd steps are not 16-byte aligned
     "halfcheetah-320": (8, 4, 4, 20, 18, 6, (None, 3, 0, -1)),
+    # off the geometries above (tests/test_gpu_terms_envelope.py's engines)
+    "slim-150": (3, 2, 5, 15, 45, 17, (-2, 1)),               # 64 + 64 + 22 rows, tiles of 64 x 45 floats: an odd D, spans aligned at even steps only
+    "wide-100": (3, 2, 5, 10, 48, 24, (1, None)),             # the declared envelope's corner: tiles of 64 x 48 floats
+    "pend-135": (5, 3, 9, 5, 3, 1, (-1, 2, None)),            # D = 3: a tile of 192 floats, fewer than the workgroup has threads
+    # n p = 1: one env per row, so workgroup 0 holds 64 envs, each with its own offset and target rows, and workgroup 1 holds 6
+    "p1-70": (5, 70, 1, 1, 18, 6, tuple((7 * i) % 13 - 4 for i in range(70))),
+    # n p = 3: 90 rows, three per env; the first workgroup ends inside env 21
+    "p1-90": (5, 30, 3, 1, 18, 6, tuple((5 * i) % 13 - 4 for i in range(30))),
+    "long-130": (40, 2, 13, 5, 18, 6, (-3, 5)),               # H = 40: 64 + 64 + 2 rows
 }
 ALL_NAN_ENV = 2      # of the shapes with m = 4: every target NaN
 
 
-def make_case(shape, K, T, kinds=KINDS, seed=0):
+def make_case(shape, K, T, kinds=KINDS, seed=0, dims=None):
     """(traj, rows, terms, targets [m,T,K], offset [m] int32) on `behind_rollout.synth_traj`: K terms on random dims with the given kinds
     in turn, w in [0.1, 2], Huber deltas in [0.5, 2] (both sides of delta occur: the errors are of order 1 to 3); targets of the dims' own
     scale; an offset None stands for T + 1 (beyond the reference); a fifth of every env's T K targets NaN, and -- shapes with m = 4 --
-    every target of env ALL_NAN_ENV."""
+    every target of env ALL_NAN_ENV.  `dims`: the dims of the first terms, in place of the drawn ones (the draws stay what they are)."""
     from behind_rollout import synth_traj
     H, m, n, p, D, A, offs = SHAPES[shape]
     rng = np.random.default_rng([seed, K, T, len(shape)])
     traj, _, _ = synth_traj(int(rng.integers(1 << 30)), H, m, n, p, D, A)
     rows = (10.0 * rng.standard_normal((m, n, p))).astype(np.float32)
-    dims = rng.integers(0, D, K)
+    dims_drawn = rng.integers(0, D, K)
+    if dims is not None:
+        dims_drawn[:min(K, len(dims))] = list(dims)[:K]
+    dims = dims_drawn
     terms = []
     for k in range(K):
         c = dict(dim=int(dims[k]), kind=kinds[k % len(kinds)], w=float(np.float32(rng.uniform(0.1, 2.0))))

@@ -100,6 +100,33 @@ def he_net(D, hidden, seed=0, out_scale=1.0):
     return layers
 
 
+# Hidden widths off the multiples of 4 and 64 (tests/test_gpu_terms_envelope.py): widths 1, 2, 3; units N .. N4 - 1 written as zeros
+# (5, 7, 65, 66, 130, 50, 30, 70, 18, 37); a last 64-unit group of 1 or 2 units (65, 130); four hidden layers.
+ENVELOPE_NETS = [(1,), (2,), (3,), (5, 7), (65,), (130, 66), (50, 30, 70, 18), (37, 37, 37, 37)]
+
+
+def envelope_net(K, hidden):
+    """the He-initialised net of ENVELOPE_NETS at input width K that the CPU and the GPU tests share"""
+    return he_net(K, hidden, seed=100 + ENVELOPE_NETS.index(tuple(hidden)))
+
+
+def liveness(x, layers, act, mean=None, std=None):
+    """(the smallest, over the hidden layers, of the largest share of non-zero units any row has; the standard deviation of the float64
+    output over the rows as a fraction of its largest magnitude) -- a net whose units are dead, or whose output is constant, checks
+    nothing"""
+    x = np.asarray(x, F).astype(np.float64).reshape(-1, np.shape(x)[-1])
+    mu = 0.0 if mean is None else np.asarray(mean, F).astype(np.float64)
+    si = 1.0 if std is None else inv_std(std).astype(np.float64)
+    h, share = (x - mu) * si, 1.0
+    for l, (W, b) in enumerate(layers):
+        h = h @ np.asarray(W, F).astype(np.float64) + np.asarray(b, F).astype(np.float64)
+        if l + 1 < len(layers):
+            h = act64(h, act)
+            share = min(share, float((h != 0).mean(axis=1).max()))
+    out = h[:, 0]
+    return share, float(out.std() / max(np.abs(out).max(), 1e-300))
+
+
 def sequential(layers, act):
     """the same net as a torch.nn.Sequential (Linear.weight is [out,in])"""
     import torch
