@@ -137,6 +137,16 @@ class RewardParams(C.Structure):        # include/cadm_hip.h cadm_reward_params 
                 ("weight", C.c_float)]
 
 
+MAX_POLICY_ACTIONS = 64                                                    # CADM_MAX_POLICY_ACTIONS
+POLICY_SQUASH = {"none": 0, "tanh": 1}                                     # CADM_POLICY_NONE / _TANH
+POLICY_IT = 0xFA0000                                                       # csrc/planner.h CADM_POLICY_IT: the roll's one-step rollouts run under POLICY_IT + 2 t
+
+
+class PolicyParams(C.Structure):        # include/cadm_hip.h cadm_policy_params (the layer conventions are the value net's)
+    _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_VALUE_LAYERS), ("activation", C.c_int32), ("squash", C.c_int32),
+                ("n_samples", C.c_int32), ("noise_std", C.c_float)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -224,6 +234,15 @@ SIGNATURES = {
                                 _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams),
                                 C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P,
                                 _P]),
+    "cadm_set_policy_net": (_i, [_P, C.POINTER(PolicyParams), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
+    "cadm_policy_eval": (_i, [_P, _P, _i, _P, _P]),
+    "cadm_policy_workspace_bytes": (C.c_size_t, [_P, _i, _i]),
+    "cadm_policy_propose": (_i, [_P, C.POINTER(PolicyParams), _P, _P, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_guided_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "cadm_guided_plan": (_i, [_P, C.POINTER(PolicyParams), C.POINTER(RewardParams), C.POINTER(ValueParams), C.POINTER(UncertaintyParams),
+                              C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P,
+                              C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i,
+                              _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

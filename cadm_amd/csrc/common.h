@@ -27,7 +27,7 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_HID_LIST 200              // the reference default --hidden_size (run_cadm_pets.py:129)
 #endif
 // bumped whenever cadm_ctx / RolloutArgs change: a side module built against another layout is refused
-#define CADM_CTX_LAYOUT_TAG 3008
+#define CADM_CTX_LAYOUT_TAG 3009
 
 #define CADM_CHECK_HIP(expr)                                                                   \
     do {                                                                                       \
@@ -59,6 +59,7 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_STREAM_ACT 2u
 #define CADM_STREAM_UNI 3u
 #define CADM_STREAM_ICEM 4u   // spectral draws of the coloured-noise sampler (icem.hip)
+#define CADM_STREAM_POLICY 5u // exploration noise of the policy prior's proposals (policy.hip)
 
 // ---------------------------------------------------------------------------------------------
 // planner weight-stream geometry (see DESIGN.md "weight streams")
@@ -103,6 +104,7 @@ struct TrainState;  // train.hip
 struct RolloutArgs;  // rollout_args.h
 struct ValueNet;  // value.hip
 struct RewardNet;  // reward.hip
+struct PolicyNet;  // policy.hip
 
 struct cadm_ctx {
     cadm_config cfg;
@@ -173,6 +175,8 @@ struct cadm_ctx {
     ValueNet* value = nullptr;
     // the registered reward net (cadm_set_reward_net, reward.hip): likewise
     RewardNet* reward = nullptr;
+    // the registered policy net (cadm_set_policy_net, policy.hip): likewise
+    PolicyNet* policy = nullptr;
 };
 
 // Entry points launch on the ctx's device whatever device the caller's thread has current (two engines on different GPUs in
@@ -205,6 +209,7 @@ int cadm_launch_context(cadm_ctx* ctx, const float* cp_obs, const float* cp_act,
 void cadm_train_free(cadm_ctx* ctx);
 void cadm_value_free(cadm_ctx* ctx);      // value.hip
 void cadm_reward_free(cadm_ctx* ctx);     // reward.hip
+void cadm_policy_free(cadm_ctx* ctx);     // policy.hip
 // (developer library: dev/dev_api.hip) Adam moment buffers of one trained tensor; layer as in cadm_set_weights, is_bias 0 / 1;
 // layer == -1 / -2: max_logvar / min_logvar of the forward net.  Returns null pointers before cadm_train_configure, and CADM_EINVAL
 // for a net id that is not one of CADM_NET_FF / BACK / CTX or a layer the net does not have.

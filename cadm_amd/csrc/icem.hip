@@ -14,7 +14,9 @@
 // passes every iteration's candidates, and the plan, through an actuator model (actuator.hip: action delay, rate limits, rate cost);
 // cadm_uncertain_plan also prices the ensemble's disagreement about the states a candidate visits (uncertainty.hip), off the candidate score;
 // cadm_valued_plan also adds a caller-supplied value net's V of every particle's last state (value.hip) to the particle returns;
-// cadm_rewarded_plan also adds a caller-supplied reward net's R of every step of every particle (reward.hip) to the particle returns.
+// cadm_rewarded_plan also adds a caller-supplied reward net's R of every step of every particle (reward.hip) to the particle returns;
+// cadm_guided_plan also rolls a caller-supplied policy net through the model once per call (policy.hip) and places its proposal
+// sequences among every iteration's candidates.
 #include <math.h>
 
 #include "planner.h"
@@ -300,11 +302,12 @@ struct IcemWs {
                                      // actuated one (the sums before it stay)
     float *acost, *aplan;            // actuated only, behind traj: the candidates' rate cost [m, n]; the plan [m, H, A] before its last actuate pass
     float *ustep, *ucost;            // uncertainty term only, behind everything before: the step costs u [m, n, H]; the candidates' cost [m, n]
-    float* rstep;                    // learned reward only, behind everything else: the step rewards [H, m, n, p]
+    float* rstep;                    // learned reward only, behind everything before: the step rewards [H, m, n, p]
+    float* pseqs; char* pws;         // policy prior only, behind everything else: the proposals [m, P, H, A]; the roll's workspace
 };
 
 static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0, int first = 0, int act = 0,
-                         int unc = 0, int rew = 0) {
+                         int unc = 0, int rew = 0, int pol = 0) {
     Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
     IcemWs t{};
@@ -335,6 +338,10 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
         t.ucost = c.take<float>((size_t)m * n);
     }
     if (rew) t.rstep = c.take<float>((size_t)ctx->H * m * n * ctx->p);
+    if (pol > 0) {
+        t.pseqs = c.take<float>((size_t)m * pol * HA);
+        t.pws = c.take<char>(cadm_policy_workspace_bytes(const_cast<cadm_ctx*>(ctx), m, pol));
+    }
     if (w) *w = t;
     return c.off;
 }
@@ -379,6 +386,13 @@ extern "C" size_t cadm_rewarded_workspace_bytes(cadm_ctx* ctx, int m, int n, int
     return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0, 1);
 }
 
+// enough for every combination of terms: the rewarded loop's views, and with P > 0 behind them the proposals and the roll's workspace
+// (a loop with fewer terms takes fewer views in front of the policy's: it fits)
+extern "C" size_t cadm_guided_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0 || P < 0) return 0;
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0, 1, P);
+}
+
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
 static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     double v = floor((double)n / pow(decay, (double)it));
@@ -408,6 +422,9 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 // reward: a learned step reward (reward.hip) of the net registered with cadm_set_reward_net; null = none, and today's launches.  With it
 // every rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * (the sum of R over the
 // counted steps) is added to the particle rows behind the constraints and the tracking terms and IN FRONT OF the terminal value.
+// policy: a policy prior (policy.hip) of the net registered with cadm_set_policy_net; null = none, and today's launches.  With it ONE
+// proposal roll behind the context encoder, and in every iteration its P sequences take the slots behind the kept elites and the mean
+// candidate, in front of the knot shaping and the actuator pass.
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
@@ -416,7 +433,7 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
                      const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr, const cadm_actuator_params* act = nullptr,
                      float* prev_io = nullptr, float* prefix_io = nullptr, int advance = 0,
                      const cadm_uncertainty_params* unc = nullptr, const cadm_value_params* value = nullptr,
-                     const cadm_reward_params* reward = nullptr) {
+                     const cadm_reward_params* reward = nullptr, const cadm_policy_params* policy = nullptr) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -443,6 +460,14 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     if (unc && (rc = cadm_uncertainty_check(ctx, unc, who))) return rc;
     if (value && (rc = cadm_value_plan_check(ctx, value, who))) return rc;
     if (reward && (rc = cadm_reward_plan_check(ctx, reward, who))) return rc;
+    const int P = policy ? policy->n_samples : 0;
+    if (policy) {
+        if ((rc = cadm_policy_plan_check(ctx, policy, who))) return rc;
+        const int n_min = icem_n_it(n, (double)prm->decay, iters - 1, KE, K);      // (the count never grows with the iteration)
+        CADM_REQUIRE((long long)K + 1 + P <= n_min, "%s: %d kept elites, the mean candidate and %d policy proposals do not fit the %d "
+                     "candidates of the smallest iteration", who, K, P, n_min);
+        if ((rc = cadm_require_ready(ctx, who))) return rc;
+    }
     const bool shape = knots && knots->spacing > 1;
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
@@ -452,10 +477,13 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     const bool reads_traj = terms != nullptr || unc != nullptr || value != nullptr || reward != nullptr;
     icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || reads_traj,
                reads_traj && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr, unc != nullptr,
-               reward != nullptr);
+               reward != nullptr, P);
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
+    // the policy's proposals: one roll per call, injected into every iteration's candidates below
+    if (policy && (rc = cadm_launch_policy_propose(ctx, policy, obs, ctx->C > 0 ? w.ctxv : nullptr, m, seed, call, w.pseqs, nullptr, w.pws, s,
+                                                   who))) return rc;
     if (track) {
         hipLaunchKernelGGL(icem_best_init_kernel, dim3(icem_grid((size_t)m * HA)), dim3(256), 0, s, m, HA, w.best_ret, w.best_seq);
         CADM_CHECK_HIP(hipGetLastError());
@@ -481,6 +509,9 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
             if ((rc = cadm_launch_clip(mean_in, w.meanclip, m * HA, ctx->cfg.lower_bound, ctx->cfg.upper_bound, 1, s))) return rc;
             if ((rc = launch_inject(ctx, w.meanclip, nullptr, m, ni, 1, 0, w.actions + (size_t)K * HA, s))) return rc;
         }
+        // behind them: the policy's proposals
+        if (policy && (rc = launch_inject(ctx, w.pseqs, nullptr, m, ni, P, 0,
+                                          w.actions + (size_t)(K + (last && prm->add_mean_last ? 1 : 0)) * HA, s))) return rc;
         // every candidate onto the grid, the injected slots included: ni, the packed count of this iteration, not the workspace's n
         if (shape && (rc = cadm_launch_shape_actions(ctx, knots, phase, m, ni, w.actions, s))) return rc;
         // and through the actuator: pins, rate limits, and what the moves cost
@@ -667,4 +698,22 @@ extern "C" int cadm_rewarded_plan(cadm_ctx* ctx, const cadm_reward_params* rewar
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
                      advance, unc, value, reward);
+}
+
+// the outermost of the nest: with the proposals of a caller-supplied policy net (policy.hip, the net of cadm_set_policy_net), rolled through
+// the model once per call, among every iteration's candidates; policy null: cadm_rewarded_plan's launches
+extern "C" int cadm_guided_plan(cadm_ctx* ctx, const cadm_policy_params* policy, const cadm_reward_params* reward,
+                                const cadm_value_params* value, const cadm_uncertainty_params* unc, const cadm_actuator_params* act,
+                                float* prev_io, float* prefix_io, int advance, const cadm_track_params* track, const float* targets, int T,
+                                const int32_t* offset, const cadm_knot_params* knots, const int32_t* phase,
+                                const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
+                                const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
+                                const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                                uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_guided_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_guided_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_guided_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
+                     advance, unc, value, reward, policy);
 }

@@ -8,6 +8,8 @@
 //   (the MFMA adds its 4 products in ascending k onto the accumulator, as context.hip relies on; the bias SEEDS the accumulator; for
 //   K <= k < K4 both W and x are exact zeros)
 //   hidden: relu max(z, 0), tanhf(z), or swish z / (1 + expf(-z));  output: linear.
+// An output layer of N > 1 units (policy.hip: the A action dims) runs as one more hidden-type layer whose activation is the identity
+// MLP_ACT_NONE: its sums land in LDS as [unit][row] like any layer's outputs.  The N = 1 `last` path of the two nets above is as it was.
 // A workgroup of 4 waves owns 16 * RT consecutive rows (RT = 1 or 2) and takes them through every layer.  A layer's 64-unit groups go
 // to the waves (all row tiles each, so a weight fragment is used RT times); with fewer groups than waves the (group, row tile) pairs do.
 // (Four row tiles were built and measured for reward.hip and lost to one and two at every width: see its header.)
@@ -26,6 +28,7 @@ constexpr int MLP_WAVES = 4;
 constexpr int MLP_PF = 6;                    // k-steps of weight fragments in flight per wave
 constexpr int MLP_LDS_MAX = 160 * 1024;      // the CU's LDS; above 64 KiB a kernel's dynamic-LDS attribute is raised
 constexpr int MLP_NL = CADM_MAX_VALUE_LAYERS + 1;
+constexpr int MLP_ACT_NONE = 3;              // the identity: a linear output layer written to LDS (behind CADM_VALUE_RELU / _TANH / _SWISH)
 
 // a ctx-owned packed copy of a registered net
 struct MlpNet {
@@ -46,6 +49,7 @@ __device__ __forceinline__ int mlp_swz(int row, int k) { return row ^ (RT == 2 ?
 __device__ __forceinline__ float mlp_act(float z, int act) {
     if (act == CADM_VALUE_RELU) return fmaxf(z, 0.0f);
     if (act == CADM_VALUE_TANH) return tanhf(z);
+    if (act == MLP_ACT_NONE) return z;
     return z / (1.0f + expf(-z));
 }
 

@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -41,6 +41,10 @@ struct Carver {
 // iteration 0's.  The planner loops count 0 .. num_cem_iters - 1 (cadm_plan_forecast refuses a ctx whose loop could get here), so a
 // forecast never repeats the noise a planner call drew for the same (seed, call).  (The word takes 24 bits of a Philox counter.)
 #define CADM_FORECAST_IT 0xFC0000
+// policy.hip: the one-step rollouts of cadm_policy_propose run under CADM_POLICY_IT + 2 t, t = 0 .. H - 2.  Even: the context layout is
+// iteration 0's.  The range lies above every planner iteration and below the forecast's word (cadm_policy_propose refuses a ctx whose
+// num_cem_iters or horizon could break that), so a roll never repeats the noise of a planner call or a forecast of the same (seed, call).
+#define CADM_POLICY_IT 0xFA0000
 
 // cem.hip
 int cadm_launch_clip(const float* in, float* out, int total, float lo, float hi, int do_clip, hipStream_t s);
@@ -112,6 +116,14 @@ int cadm_launch_value(cadm_ctx* ctx, const cadm_value_params* value, const float
 int cadm_reward_plan_check(const cadm_ctx* ctx, const cadm_reward_params* reward, const char* who);
 int cadm_launch_reward(cadm_ctx* ctx, const cadm_reward_params* reward, const float* traj, const float* obs, const float* actions,
                        const int32_t* first, int m, int n, float* rows, float* r_step, hipStream_t s);
+// policy.hip: the refusals of a policy prior (null parameters, a layer count outside 0 .. 4, a width outside 1 .. 512, an unknown
+// activation or squash, n_samples < 1, a noise_std negative or not finite, D or A beyond the net's dims, a discrete / sharded ctx,
+// activation tiles beyond the LDS, a num_cem_iters or horizon that reaches the roll's iteration words; no registered net: CADM_ESTATE;
+// parameters that do not describe the registered net), before any HIP call; and the roll itself: seqs_out [m, P, H, A], states_out
+// [H, m, P, p, D] or null, workspace of cadm_policy_workspace_bytes(ctx, m, P)
+int cadm_policy_plan_check(const cadm_ctx* ctx, const cadm_policy_params* policy, const char* who);
+int cadm_launch_policy_propose(cadm_ctx* ctx, const cadm_policy_params* policy, const float* obs, const float* ctx_vec, int m, uint32_t seed,
+                               uint32_t call, float* seqs_out, float* states_out, void* workspace, hipStream_t s, const char* who);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

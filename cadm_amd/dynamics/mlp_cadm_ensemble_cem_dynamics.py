@@ -71,6 +71,13 @@ Differences a caller can see (all opt-in except the first):
     over the net at run time (a list of (W [in,out], b [out]) or a torch.nn.Sequential) with nothing rebuilt, `clear_reward_net()`
     removes it, `reward_net(obs, act, next_obs)` evaluates R through the planner's kernel, `plan_rewards(obs, actions, ...)`: the step
     rewards of given plans.  It alone takes the opt-in route;
+  * `cem_policy_prior=dict(hidden_sizes=(256, 256), activation="relu", squash="tanh" | "none", n_samples=24, noise_std=0.0)`: the
+    learner's actor as a prior in that loop (INTEGRATION.md "Policy prior") -- once per call the policy is rolled through the model
+    on `n_samples` sequences per env (sequence 0 without noise), and every iteration's candidates hold those sequences behind the kept
+    elites and the mean candidate.  The kwarg declares the net's shape; `set_policy(weights, obs_mean=None, obs_std=None)` hands over
+    an actor at run time (a list of (W [in,out], b [out]) or a torch.nn.Sequential) with nothing rebuilt, `clear_policy()` removes it,
+    `policy_action(states)` evaluates it through the planner's kernel, `policy_proposals(obs, ...)`: the sequences a call would
+    inject.  It alone takes the opt-in route; `fit` does not touch the policy;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -254,6 +261,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_uncertainty=None,
                  cem_terminal_value=None,
                  cem_reward_net=None,
+                 cem_policy_prior=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -322,7 +330,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      cem_action_rate_cost=cem_action_rate_cost, cem_action_advance=cem_action_advance,
                                                      n_forwards=n_forwards, action_dim=None if self.discrete else self.action_space_dims,
                                                      cem_uncertainty=cem_uncertainty, obs_dim=obs_space_dims,
-                                                     cem_terminal_value=cem_terminal_value, cem_reward_net=cem_reward_net)
+                                                     cem_terminal_value=cem_terminal_value, cem_reward_net=cem_reward_net,
+                                                     cem_policy_prior=cem_policy_prior)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
@@ -337,6 +346,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         self._act_prev = self._act_prefix = None              # device tensors [m,A] / [m,delay,A] float32, NaN = unknown (the actuator model)
         self._value_set = False                               # whether the engine holds a value net (cem_terminal_value): `set_terminal_value`
         self._reward_set = False                              # whether the engine holds a reward net (cem_reward_net): `set_reward_net`
+        self._policy_set = False                              # whether the engine holds a policy net (cem_policy_prior): `set_policy`
 
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
@@ -366,6 +376,12 @@ class MLPEnsembleCEMDynamicsModel(object):
         self.engine.ensure_rollout(None, 1, max(1, n_candidates))
         if self._opt is not None and self._opt.keep_elites > self.engine.num_elites:
             raise ValueError("cem_keep_elites=%d exceeds the planner's %d elites" % (self._opt.keep_elites, self.engine.num_elites))
+        if self._opt is not None and self._opt.policy_params is not None:
+            K, P = self._opt.keep_elites, self._opt.policy_params.n_samples
+            least = _planner.policy_min_candidates(n_candidates, self._opt.decay, self.engine.num_elites, K, self.engine.num_cem_iters)
+            if K + 1 + P > least:
+                raise ValueError("cem_policy_prior: %d kept elites, the mean candidate and %d proposals need %d candidate slots, the smallest "
+                                 "iteration has %d" % (K, P, K + 1 + P, least))
 
     # ------------------------------------------------------------------ planning
     def _push_stats(self):
@@ -588,6 +604,8 @@ class MLPEnsembleCEMDynamicsModel(object):
             raise RuntimeError("get_action: this model plans under cem_terminal_value and has no value net (call set_terminal_value first)")
         if self._opt.reward_params is not None and not self._reward_set:
             raise RuntimeError("get_action: this model plans under cem_reward_net and has no reward net (call set_reward_net first)")
+        if self._opt.policy_params is not None and not self._policy_set:
+            raise RuntimeError("get_action: this model plans under cem_policy_prior and has no policy net (call set_policy first)")
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
@@ -787,6 +805,55 @@ class MLPEnsembleCEMDynamicsModel(object):
         if squeeze:
             res = {k: None if x is None else x[:, 0] for k, x in res.items()}
         return res
+
+    # ------------------------------------------------------------------ policy prior (INTEGRATION.md "Policy prior")
+    def _require_policy(self, who, need_net=False):
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.policy_params is None:
+            raise ValueError("%s: this model has no cem_policy_prior" % who)
+        if need_net and not self._policy_set:
+            raise RuntimeError("%s: this model has no policy net (call set_policy first)" % who)
+        return opt
+
+    def set_policy(self, weights, obs_mean=None, obs_std=None):
+        """The policy net of `cem_policy_prior` from the next call on: `weights` as `set_terminal_value` takes them (a list of (W [in,out],
+        b [out]) per layer or a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules, the last Linear with A outputs) -- of the
+        declared layer sizes and activation, else it is refused; obs_mean / obs_std [D] (None: 0 / 1): the net reads (obs - obs_mean) /
+        obs_std of the raw observation.  Everything is copied; replacing the net rebuilds nothing."""
+        opt = self._require_policy("set_policy")
+        self.engine.set_policy_net(opt.policy_params, weights, obs_mean=obs_mean, obs_std=obs_std)
+        self._policy_set = True
+
+    def clear_policy(self):
+        """Remove the policy net: get_action on a model with `cem_policy_prior` then raises until `set_policy` is called."""
+        self._require_policy("clear_policy")
+        self.engine.set_policy_net(None)
+        self._policy_set = False
+
+    def policy_action(self, states):
+        """The policy's action of raw observations `states` [..., D] (numpy or tensor) through the planner's kernel -> numpy [..., A]:
+        squashed and clipped to the action bounds, no noise; clip(0, lb, ub) for a state with a non-finite value."""
+        self._require_policy("policy_action", need_net=True)
+        return self.engine.policy_eval(states).cpu().numpy()
+
+    def policy_proposals(self, obs, cp_obs=None, cp_act=None, seed=None, return_states=False):
+        """The sequences the policy prior would inject for `obs` [m,D] (with a context model its history cp_obs / cp_act) -> numpy
+        [m,n_samples,H,A]: the context encoder and the proposal roll, drawn under (seed, the last get_action's call); no counter moves.
+        return_states: (proposals, states [H,m,n_samples,p,D]), the particle states every step's actions were computed from."""
+        opt = self._require_policy("policy_proposals", need_net=True)
+        self._push_stats()
+        D, m = self.obs_space_dims, int(np.shape(obs)[0])
+        if tuple(np.shape(obs)) != (m, D) or m == 0:
+            raise ValueError("policy_proposals: obs %r, expected [m,%d] with m >= 1" % (tuple(np.shape(obs)), D))
+        ctx_vec = None
+        eng = self.engine
+        if self.context_out_dim > 0:
+            if cp_obs is None or cp_act is None:
+                raise ValueError("policy_proposals: cp_obs and cp_act are required for a context model")
+            ctx_vec = eng.context_forward(cp_obs, cp_act)
+        out = eng.policy_propose(opt.policy_params, eng._t(obs).contiguous(), ctx_vec, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                 call=self._call & 0xFFFFFFFF, want_states=return_states)
+        return (out[0].cpu().numpy(), out[1].cpu().numpy()) if return_states else out.cpu().numpy()
 
     # ------------------------------------------------------------------ learned reward (INTEGRATION.md "Learned reward")
     def _require_reward(self, who, need_net=False):

@@ -61,6 +61,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """The learned step rewards of `actions` under this model's `cem_reward_net` (see the CaDM class; a vanilla model has no history)."""
         return super().plan_rewards(obs, actions, None, None, seed=seed)
 
+    def policy_proposals(self, obs, seed=None, return_states=False):
+        """The sequences this model's `cem_policy_prior` would inject for `obs` (see the CaDM class; a vanilla model has no history)."""
+        return super().policy_proposals(obs, None, None, seed=seed, return_states=return_states)
+
     def predict(self, obs, act, return_std=False):
         return super().predict(obs, act, None, None, return_std=return_std)
 

@@ -560,12 +560,13 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return, traj=False, track=None, act=False, unc=None, val=None, rew=None):
+                   want_best_return, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
         `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
         workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop); act: the workspace of an actuated loop;
         unc: None, or the (terminate, actuator) of a loop with an uncertainty term, whose slot it is; val: None, or the (terminate, actuator,
-        uncertainty) of a loop with a terminal value, whose slot it is; rew: likewise for a loop with a learned reward."""
+        uncertainty) of a loop with a terminal value, whose slot it is; rew: likewise for a loop with a learned reward; pol: None, or the
+        (terminate, actuator, uncertainty, P) of a loop with a policy prior, whose slot it is."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -574,7 +575,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val, rew=rew)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val, rew=rew, pol=pol)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -588,7 +589,12 @@ class HipEngine:
         target_offset [m] int32 or None = 0), `knot_plan` when it holds knots (phase: the envs' grid phases [m] int32, None = 0),
         `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
         Arguments as `icem_plan` behind its params.  First of all `rewarded_plan`, when it holds a learned reward, then `valued_plan`, when
-        it holds a terminal value, then `uncertain_plan`, when it holds an uncertainty term."""
+        it holds a terminal value, then `uncertain_plan`, when it holds an uncertainty term.  Before all of them `guided_plan`, when it
+        holds a policy prior."""
+        if getattr(opt, "policy_params", None) is not None:
+            return self.guided_plan(opt.policy_params, opt.reward_params, opt.value_params, opt.uncertainty_params, opt.actuator_params,
+                                    act_prev, act_prefix, opt.action_advance, opt.track_params, targets, target_offset, opt.knot_params, phase,
+                                    opt.constraint_params, opt.score_params, opt.params, *args, **kw)
         if getattr(opt, "reward_params", None) is not None:
             return self.rewarded_plan(opt.reward_params, opt.value_params, opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix,
                                       opt.action_advance, opt.track_params, targets, target_offset, opt.knot_params, phase,
@@ -615,7 +621,7 @@ class HipEngine:
             return self.scored_plan(opt.score_params, opt.params, *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
-    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None, rew=None):
+    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
         constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that).  track: None,
         or whether a tracked loop runs under TERMINATE constraints -- the tracking slot (`cadm_tracking_workspace_bytes`: the trajectory
@@ -625,7 +631,9 @@ class HipEngine:
         first-violation view under TERMINATE constraints, the actuator's views, and behind everything the step costs and the cost).  val:
         None, or (terminate, actuator, uncertainty) -- the slot of a loop with a terminal value (`cadm_valued_workspace_bytes`).  rew:
         None, or (terminate, actuator, uncertainty) -- the slot of a loop with a learned reward (`cadm_rewarded_workspace_bytes`: the
-        valued loop's, and behind everything the step rewards)."""
+        valued loop's, and behind everything the step rewards).  pol: None, or (terminate, actuator, uncertainty, P) -- the slot of a loop
+        with a policy prior (`cadm_guided_workspace_bytes`: the rewarded loop's, and behind everything the proposals and the roll's
+        workspace)."""
         slot = (bool(mppi), bool(traj)) if track is None else (bool(mppi), "track", bool(track))
         if act:
             slot = slot + ("act",)
@@ -635,9 +643,14 @@ class HipEngine:
             slot = (bool(mppi), "val", bool(val[0]), bool(val[1]), bool(val[2]))
         if rew is not None:
             slot = (bool(mppi), "rew", bool(rew[0]), bool(rew[1]), bool(rew[2]))
+        if pol is not None:
+            slot = (bool(mppi), "pol", bool(pol[0]), bool(pol[1]), bool(pol[2]), int(pol[3]))
         key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            if rew is not None:
+            if pol is not None:
+                nbytes = self.lib.cadm_guided_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(pol[0])), int(bool(pol[1])),
+                                                              int(bool(pol[2])), int(pol[3]))
+            elif rew is not None:
                 nbytes = self.lib.cadm_rewarded_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(rew[0])), int(bool(rew[1])),
                                                                 int(bool(rew[2])))
             elif val is not None:
@@ -1186,8 +1199,8 @@ class HipEngine:
 
     @staticmethod
     def _net_params(prm, what, hidden_sizes, activation, weight):
-        """What `value_params` and `reward_params` share: the checks of a caller-supplied net's layers, activation and weight, and the
-        fields of `prm` (a `ValueParams` or a `RewardParams`) they fill."""
+        """What `value_params`, `reward_params` and `policy_params` share: the checks of a caller-supplied net's layers, activation and
+        weight, and the fields of `prm` (a `ValueParams`, a `RewardParams` or a `PolicyParams`) they fill."""
         try:
             hs = [hidden_sizes] if isinstance(hidden_sizes, (int, np.integer)) and not isinstance(hidden_sizes, bool) else list(hidden_sizes)
         except TypeError:
@@ -1203,13 +1216,15 @@ class HipEngine:
             act = int(activation)
         else:
             raise ValueError("%s activation must be %s, got %r" % (what, " or ".join(repr(k) for k in _lib.VALUE_ACTS), activation))
-        try:
-            w = float(np.float32(weight))
-        except (TypeError, ValueError):
-            raise ValueError("%s weight must be a finite number, got %r" % (what, weight)) from None
-        if isinstance(weight, bool) or not math.isfinite(w):
-            raise ValueError("%s weight must be a finite number, got %r" % (what, weight))
-        prm.n_hidden, prm.activation, prm.weight = len(hs), act, w
+        if weight is not None:      # (None: a net that is not added to a return -- the policy)
+            try:
+                w = float(np.float32(weight))
+            except (TypeError, ValueError):
+                raise ValueError("%s weight must be a finite number, got %r" % (what, weight)) from None
+            if isinstance(weight, bool) or not math.isfinite(w):
+                raise ValueError("%s weight must be a finite number, got %r" % (what, weight))
+            prm.weight = w
+        prm.n_hidden, prm.activation = len(hs), act
         for l, h in enumerate(hs):
             prm.hidden[l] = int(h)
 
@@ -1261,8 +1276,8 @@ class HipEngine:
         without touching anything else.  params None: the net is cleared."""
         self._value_src = HipEngine._set_net(self, "set_value_net", params, self.D, weights, obs_mean, obs_std, "obs_mean", "obs_std")
 
-    def _set_net(self, who, params, K, weights, mean, std, mean_name, std_name):
-        """What `set_value_net` and `set_reward_net` share: the checks of a caller-supplied net K -> hidden -> 1 against its declared
+    def _set_net(self, who, params, K, weights, mean, std, mean_name, std_name, N=1):
+        """What `set_value_net`, `set_reward_net` and `set_policy_net` share: the checks of a caller-supplied net K -> hidden -> N against its declared
         `params` and of its input statistics [K] -- all of them before the library is looked at --, the staging, and the call of
         cadm_<who>.  Returns what must stay alive until the next net (the copy is enqueued, not done); params None: the net is cleared,
         and None."""
@@ -1270,7 +1285,7 @@ class HipEngine:
             self._check(getattr(self.lib, "cadm_" + who)(self._ctx, None, None, None, None, None, self.stream), "cadm_" + who)
             return None
         layers, act = self.value_weights(weights)
-        dims = [K] + [int(params.hidden[l]) for l in range(params.n_hidden)] + [1]
+        dims = [K] + [int(params.hidden[l]) for l in range(params.n_hidden)] + [N]
         if len(layers) != len(dims) - 1:
             raise ValueError("%s: %d layers given, the declared net %r has %d" % (who, len(layers), dims, len(dims) - 1))
         for l, (w, b) in enumerate(layers):
@@ -1495,6 +1510,109 @@ class HipEngine:
         return self._loop_plan("rewarded_plan", self.lib.cadm_rewarded_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return,
                                rew=(terminate, actuator is not None, uncertainty is not None))
+
+    # ------------------------------------------------------------------ policy prior (opt-in; csrc/policy.hip)
+    @staticmethod
+    def policy_params(hidden_sizes=(), activation="relu", squash="tanh", n_samples=1, noise_std=0.0):
+        """`cadm_policy_params`: hidden_sizes / activation -- as `value_params` (the net is D -> h_1 -> .. -> h_L -> A); squash -- "tanh"
+        (a = mid + half * tanh(z), onto the action bounds) or "none" (a = z), or its CADM_POLICY_* number; n_samples -- P >= 1, the
+        proposal sequences per env; noise_std -- finite, >= 0, the exploration noise of sequences 1 .. P - 1 (sequence 0 is the policy's
+        own trajectory).  Needs no GPU."""
+        if isinstance(squash, str) and squash in _lib.POLICY_SQUASH:
+            sq = _lib.POLICY_SQUASH[squash]
+        elif not isinstance(squash, (bool, str)) and isinstance(squash, (int, np.integer)) and int(squash) in _lib.POLICY_SQUASH.values():
+            sq = int(squash)
+        else:
+            raise ValueError("policy squash must be %s, got %r" % (" or ".join(repr(k) for k in _lib.POLICY_SQUASH), squash))
+        if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or int(n_samples) < 1:
+            raise ValueError("policy n_samples must be an int >= 1, got %r" % (n_samples,))
+        try:
+            std = float(np.float32(noise_std))
+        except (TypeError, ValueError):
+            raise ValueError("policy noise_std must be a finite number >= 0, got %r" % (noise_std,)) from None
+        if isinstance(noise_std, bool) or not math.isfinite(std) or std < 0.0:
+            raise ValueError("policy noise_std must be a finite number >= 0, got %r" % (noise_std,))
+        prm = _lib.PolicyParams()
+        HipEngine._net_params(prm, "policy", hidden_sizes, activation, None)
+        prm.squash, prm.n_samples, prm.noise_std = sq, int(n_samples), std
+        return prm
+
+    def set_policy_net(self, params, weights=None, obs_mean=None, obs_std=None):
+        """`cadm_set_policy_net`: registers the policy net that `params` (`policy_params`) describes -- `weights` as `value_weights` takes
+        them (the last layer has A outputs), the input statistics obs_mean / obs_std [D] as `set_value_net` takes them.  The library
+        packs a copy of its own, so a second call replaces the net without touching anything else.  params None: the net is cleared."""
+        self._policy_src = HipEngine._set_net(self, "set_policy_net", params, self.D, weights, obs_mean, obs_std, "obs_mean", "obs_std", N=self.A)
+
+    def policy_eval(self, states):
+        """`cadm_policy_eval`: the registered policy's action of states [..., D] -> [..., A] (device tensors): squash and clip, no
+        noise, through the chain of the proposal roll."""
+        states = self._t(states)
+        if states.dim() < 1 or states.shape[-1] != self.D:
+            raise ValueError("policy_eval: states %r, expected [..., %d]" % (tuple(states.shape), self.D))
+        flat = states.reshape(-1, self.D).contiguous()
+        if flat.shape[0] < 1:
+            raise ValueError("policy_eval: no states")
+        a = torch.empty((flat.shape[0], self.A), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_policy_eval(self._ctx, ptr(flat), int(flat.shape[0]), ptr(a), self.stream), "cadm_policy_eval")
+        return a.reshape(tuple(states.shape[:-1]) + (self.A,))
+
+    def policy_propose(self, params, obs, ctx_vec=None, seed=0, call=0, want_states=False):
+        """`cadm_policy_propose`: obs [m,D], ctx_vec the context encoder's output (`context_forward`; None for a model without one) ->
+        the P = params.n_samples proposal sequences per env [m,P,H,A]: the registered policy rolled through the model on the particle
+        mean of every sequence, sequence 0 without noise.  want_states: (seqs, states [H,m,P,p,D]), the particle states every step
+        read."""
+        obs = self._t(obs)
+        if obs.dim() != 2 or obs.shape[1] != self.D or not obs.is_contiguous():
+            raise ValueError("policy_propose: obs %r, expected contiguous [m, %d]" % (tuple(obs.shape), self.D))
+        m, P = int(obs.shape[0]), int(params.n_samples)
+        ctx_vec = None if ctx_vec is None else self._t(ctx_vec)
+        if P >= 1:
+            self.ensure_rollout(None, m, P)
+        seqs = torch.empty((m, max(P, 1), self.H, self.A), dtype=torch.float32, device=self.device)
+        states = torch.empty((self.H, m, max(P, 1), self.p, self.D), dtype=torch.float32, device=self.device) if want_states else None
+        need = self.lib.cadm_policy_workspace_bytes(self._ctx, m, max(P, 1))
+        ws = getattr(self, "_policy_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._policy_ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.cadm_policy_propose(self._ctx, ct.byref(params), ptr(obs), ptr(ctx_vec), m, seed, call, ptr(seqs), ptr(states),
+                                                 ptr(ws), self.stream), "cadm_policy_propose")
+        return (seqs, states) if want_states else seqs
+
+    def guided_plan(self, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints,
+                    score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
+                    want_best_return=False):
+        """`cadm_guided_plan`: the loop of `rewarded_plan` with the registered policy net's proposals (`policy`: a `policy_params`
+        describing the net of `set_policy_net`; None = none, and `rewarded_plan`'s launches) rolled through the model once and placed
+        among every iteration's candidates, behind the kept elites and the mean candidate.  Arguments behind `policy` as
+        `rewarded_plan`; the workspace is the slot of `cadm_guided_workspace_bytes`, cached apart from the others."""
+        if policy is None:
+            return self.rewarded_plan(reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase,
+                                      constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=carry,
+                                      carry_valid=carry_valid, seed=seed, call=call, out=out, want_best_return=want_best_return)
+        mppi, params = self._as_mppi_params(params)
+        m = int(np.shape(obs)[0])
+        if actuator is None:
+            prev = prefix = None
+        else:
+            for name, t in (("prev", prev), ("prefix", prefix)):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+                    raise ValueError("guided_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
+            if prev is None or (prefix is None and actuator.delay > 0):
+                raise ValueError("guided_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
+            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "guided_plan")
+        phase = self._phase(phase, m, "guided_plan")
+        T = 0
+        if track is None:
+            targets = offset = None
+        else:
+            targets, T, offset = self._targets(targets, offset, m, track.n, "guided_plan")
+        by = lambda x: None if x is None else ct.byref(x)
+        head = (ct.byref(policy), by(reward), by(value), by(uncertainty), by(actuator), ptr(prev), ptr(prefix), int(bool(advance)), by(track),
+                ptr(targets), T, ptr(offset), by(knots), ptr(phase), by(constraints), by(score), int(mppi), ct.byref(params))
+        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
+        return self._loop_plan("guided_plan", self.lib.cadm_guided_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act, init_mean,
+                               init_var, n, carry, carry_valid, seed, call, out, want_best_return,
+                               pol=(terminate, actuator is not None, uncertainty is not None, max(int(policy.n_samples), 0)))
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

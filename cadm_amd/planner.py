@@ -12,7 +12,7 @@ What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
   * `PlanOptions`: what a model's `cem_*` kwargs mean -- their checks, the switches, and the ctypes structs `HipEngine.opt_in_plan` hands to the library;
-  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`; `actuator=`: `cadm_actuated_plan`; `uncertainty=`: `cadm_uncertain_plan`; `value=`: `cadm_valued_plan`; `reward=`: `cadm_rewarded_plan`) one launch at a time, for the same purposes;
+  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`; `actuator=`: `cadm_actuated_plan`; `uncertainty=`: `cadm_uncertain_plan`; `value=`: `cadm_valued_plan`; `reward=`: `cadm_rewarded_plan`; `policy=`: `cadm_guided_plan`) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
@@ -26,14 +26,16 @@ from . import _lib
 from .engine import HipEngine
 
 
+POLICY_IT = _lib.POLICY_IT  # the iteration word of the proposal roll's first one-step rollout: csrc/planner.h CADM_POLICY_IT (tests/test_policy_ref.py pairs the two)
 FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/planner.h CADM_FORECAST_IT (tests/test_constraint_ref.py pairs the two)
 
 
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
                                                        "params score_params constraints constraint_params knots knot_params actuator actuator_params "
-                                                       "action_advance reward reward_params value value_params uncertainty uncertainty_params tracking track_params "
-                                                       "target_advance",
-                                                       defaults=(None, None, None, None, True, None, None, None, None, None, None, None, None, True))):
+                                                       "action_advance policy policy_params reward reward_params value value_params uncertainty uncertainty_params tracking "
+                                                       "track_params target_advance",
+                                                       defaults=(None, None, None, None, True, None, None, None, None, None, None, None, None, None, None,
+                                                                 True))):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
     `score`: None, or (mode name, kappa, k).  `constraints`: None, or (the list of dict(dim=, lo=, hi=), mode name, weight), with
@@ -50,7 +52,9 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
     `value`: None, or (the tuple of hidden widths, activation name, weight), with `value_params` the `ValueParams` built from it (None: no
     terminal value).  The net itself is not an option: a model registers it at run time (`set_terminal_value`).
     `reward`: None, or (inputs name, the tuple of hidden widths, activation name, weight), with `reward_params` the `RewardParams` built
-    from it (None: no learned reward); the net is registered at run time too (`set_reward_net`)."""
+    from it (None: no learned reward); the net is registered at run time too (`set_reward_net`).
+    `policy`: None, or (the tuple of hidden widths, activation name, squash name, n_samples, noise_std), with `policy_params` the
+    `PolicyParams` built from it (None: no policy prior); the net is registered at run time too (`set_policy`)."""
     __slots__ = ()
 
     @staticmethod
@@ -59,7 +63,8 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                     process_group=None, n_particles=20, cem_constraints=None, cem_constraint_mode="penalty", cem_constraint_weight=None, *,
                     cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call", cem_tracking=None, cem_target_advance=True,
                     cem_action_delay=0, cem_action_rate_limit=None, cem_action_rate_cost=None, cem_action_advance=True, n_forwards=None,
-                    action_dim=None, cem_uncertainty=None, obs_dim=None, cem_terminal_value=None, cem_reward_net=None):
+                    action_dim=None, cem_uncertainty=None, obs_dim=None, cem_terminal_value=None, cem_reward_net=None,
+                    cem_policy_prior=None):
         """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
         everything that needs no engine -- and folded into a `PlanOptions`.  n_forwards / action_dim: the model's horizon and action
         dims, what `cem_action_delay` and the lengths of `cem_action_rate_limit` / `cem_action_rate_cost` are checked against (None: the
@@ -68,7 +73,10 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
         what a list `w` is checked against.  cem_terminal_value: None, or dict(hidden_sizes=(..), activation="relu" | "tanh" | "swish",
         weight=1.0) (`HipEngine.value_params`): the shape of the value net a model is given at run time.  cem_reward_net: None, or
         dict(inputs="next_obs" | "obs_act" | "obs_act_next_obs", hidden_sizes=(..), activation=, weight=1.0) (`HipEngine.reward_params`):
-        the shape of the reward net a model is given at run time; obs_dim / action_dim: what its input dims are checked against."""
+        the shape of the reward net a model is given at run time; obs_dim / action_dim: what its input dims are checked against.
+        cem_policy_prior: None, or dict(hidden_sizes=(..), activation=, squash="tanh" | "none", n_samples=24, noise_std=0.0)
+        (`HipEngine.policy_params`): the shape of the policy net a model is given at run time and how many proposals it makes (whether
+        they fit the smallest iteration's candidates is the model's check, once it knows its engine's elites: `policy_min_candidates`)."""
         act_off = (cem_action_rate_limit is None and cem_action_rate_cost is None and isinstance(cem_action_delay, (int, np.integer))
                    and not isinstance(cem_action_delay, bool) and int(cem_action_delay) == 0)
         if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
@@ -77,12 +85,12 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                 and (cem_knot_interp, cem_knot_anchor) == ("hold", "call") and isinstance(cem_knots, (int, np.integer)) \
                 and not isinstance(cem_knots, bool) and int(cem_knots) == 1 and cem_tracking is None and cem_target_advance is True \
                 and act_off and cem_action_advance is True and cem_uncertainty is None and cem_terminal_value is None \
-                and cem_reward_net is None:
+                and cem_reward_net is None and cem_policy_prior is None:
             return None
         if not use_cem:
             raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
                              "cem_score / cem_risk / cem_constraints / cem_knots / cem_tracking / cem_action_delay / cem_action_rate_limit / "
-                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net configure the CEM planner: they need "
+                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net / cem_policy_prior configure the CEM planner: they need "
                              "use_cem=True")
         value = vparams = None
         if cem_terminal_value is not None:
@@ -95,6 +103,21 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
             vparams = HipEngine.value_params(v["hidden_sizes"], v["activation"], v["weight"])
             value = (tuple(int(vparams.hidden[l]) for l in range(vparams.n_hidden)),
                      [k for k, x in _lib.VALUE_ACTS.items() if x == vparams.activation][0], float(vparams.weight))
+        policy = pparams = None
+        if cem_policy_prior is not None:
+            if not isinstance(cem_policy_prior, dict) or set(cem_policy_prior) - {"hidden_sizes", "activation", "squash", "n_samples", "noise_std"}:
+                raise ValueError("cem_policy_prior must be dict(hidden_sizes=, activation=, squash=, n_samples=, noise_std=), got %r"
+                                 % (cem_policy_prior,))
+            if obs_dim is not None and not 1 <= int(obs_dim) <= _lib.MAX_VALUE_DIMS:
+                raise ValueError("a policy net reads up to %d observation dims, got %r" % (_lib.MAX_VALUE_DIMS, obs_dim))
+            if action_dim is not None and not 1 <= int(action_dim) <= _lib.MAX_POLICY_ACTIONS:
+                raise ValueError("a policy net writes up to %d action dims, got %r" % (_lib.MAX_POLICY_ACTIONS, action_dim))
+            q = dict(hidden_sizes=(256, 256), activation="relu", squash="tanh", n_samples=24, noise_std=0.0)
+            q.update(cem_policy_prior)
+            pparams = HipEngine.policy_params(q["hidden_sizes"], q["activation"], q["squash"], q["n_samples"], q["noise_std"])
+            policy = (tuple(int(pparams.hidden[l]) for l in range(pparams.n_hidden)),
+                      [k for k, x in _lib.VALUE_ACTS.items() if x == pparams.activation][0],
+                      [k for k, x in _lib.POLICY_SQUASH.items() if x == pparams.squash][0], int(pparams.n_samples), float(pparams.noise_std))
         reward = rparams = None
         if cem_reward_net is not None:
             if not isinstance(cem_reward_net, dict) or set(cem_reward_net) - {"inputs", "hidden_sizes", "activation", "weight"}:
@@ -211,7 +234,21 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                            knot_params=None if knots is None else HipEngine.knot_params(knots[0], knots[1]), tracking=tracking,
                            track_params=tparams, target_advance=bool(cem_target_advance), actuator=actuator, actuator_params=aparams,
                            action_advance=bool(cem_action_advance), uncertainty=uncertainty, uncertainty_params=uparams, value=value, value_params=vparams, reward=reward,
-                           reward_params=rparams, **mppi, **icem)
+                           reward_params=rparams, policy=policy, policy_params=pparams, **mppi, **icem)
+
+
+def policy_slot(keep_elites, last, add_mean_last):
+    """The first candidate slot of the policy prior's proposals in an iteration: behind the kept elites and, in the last iteration of a
+    loop with add_mean_last, the mean candidate (csrc/icem.hip)."""
+    return int(keep_elites) + (1 if last and add_mean_last else 0)
+
+
+def policy_min_candidates(n, decay, num_elites, keep_elites, iters=5):
+    """The candidate count of the smallest iteration of a loop of `iters` iterations, min over it of min(n, max(floor(n / decay^it),
+    2 num_elites, keep_elites + 1)) (csrc/icem.hip icem_n_it; decay rounded to float32 as the library receives it): what keep_elites + 1
+    + n_samples of a policy prior must fit."""
+    d = float(np.float32(decay))
+    return min(min(int(n), max(int(np.floor(float(n) / d ** it)), 2 * int(num_elites), int(keep_elites) + 1)) for it in range(int(iters)))
 
 
 class Shard:
@@ -338,7 +375,7 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
 def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
               add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False,
               update="cem", temperature=1.0, relative=False, score=None, constraints=None, knots=None, phase=None, tracking=None, actuator=None,
-              action_advance=False, uncertainty=None, value=None, reward=None):
+              action_advance=False, uncertainty=None, value=None, reward=None, policy=None):
     """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
     tests with injected draws and for diagnostics.  update="mppi": the loop of `cadm_mppi_plan` -- the elite ids come from an elite
     refit into copies of mean / var, the distribution from `mppi_refit`.  score: a `HipEngine.score_params` (`cadm_scored_plan`; None: the
@@ -367,7 +404,10 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     reward: a `HipEngine.reward_params` describing the engine's registered reward net (`cadm_rewarded_plan`; None: none) -- every rollout
     then records its trajectories and `reward_returns` adds weight * (the sum of R over the counted steps) to the particle rows behind the
     constraints (under TERMINATE with their first violations) and the tracking terms, in front of the terminal value; `return_info`
-    carries `reward_steps` [H,m,n_it,p] (NaN where not counted), `reward_sum` [m,n_it,p] and `reward_rows`, the rows before the addition."""
+    carries `reward_steps` [H,m,n_it,p] (NaN where not counted), `reward_sum` [m,n_it,p] and `reward_rows`, the rows before the addition.
+    policy: a `HipEngine.policy_params` describing the engine's registered policy net (`cadm_guided_plan`; None: none) -- one
+    `policy_propose` behind the context encoder, and in every iteration its sequences are injected at `policy_slot`, in front of the knot
+    shaping and the actuator pass; the third return value of `return_info` carries `proposals` [m,P,H,A]."""
     obs = engine._t(obs)
     mean, var = engine._t(init_mean).clone(), engine._t(init_var).clone()
     if knots is not None and knots.spacing == 1:
@@ -377,6 +417,7 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     m, K, iters = obs.shape[0], int(keep_elites), engine.num_cem_iters
     lo, hi = float(engine.cfg.lower_bound), float(engine.cfg.upper_bound)
     ctx_vec = engine.context_forward(cp_obs, cp_act) if engine.C > 0 else None
+    proposals = None if policy is None else engine.policy_propose(policy, obs, ctx_vec, seed=seed, call=call)
     best_ret = torch.full((m,), float("nan"), dtype=torch.float32, device=engine.device)      # NaN: nothing scored yet (icem_best_init_kernel)
     best_seq = torch.full((m, engine.H, engine.A), float("nan"), dtype=torch.float32, device=engine.device)
     kept, info = None, []
@@ -393,6 +434,8 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
             engine.icem_inject(actions, kept)
         if last and add_mean_last:
             engine.icem_inject(actions, mean.clamp(lo, hi).unsqueeze(1).contiguous(), slot0=K)
+        if proposals is not None:
+            engine.icem_inject(actions, proposals, slot0=policy_slot(K, last, add_mean_last))
         if knots is not None:
             engine.shape_actions(actions, knots, phase)
         action_cost = None
@@ -453,4 +496,4 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
             actuator[1].copy_(plan[:, 0])
             if d > 0:
                 actuator[2].copy_(plan[:, 1:1 + d])
-    return (plan, info, dict(best_ret=best_ret, best_seq=best_seq, plan_mean=plan_mean)) if return_info else plan
+    return (plan, info, dict(best_ret=best_ret, best_seq=best_seq, plan_mean=plan_mean, proposals=proposals)) if return_info else plan

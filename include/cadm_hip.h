@@ -785,6 +785,75 @@ int cadm_rewarded_plan(cadm_ctx* ctx, const cadm_reward_params* params, const ca
                        int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                        float* best_return_out, void* stream);
 
+/* Policy prior (no reference twin, OPT-IN): a caller-supplied actor pi rolled through the ensemble, its trajectories placed among the
+ * candidates of every iteration of the opt-in loop (LOOP, TD-MPC): with few candidates and a short horizon the planner then starts from
+ * what the learner already knows instead of from draws around a mean.
+ * pi is an MLP  D -> h_1 -> .. -> h_L -> A  under the value net's conventions: L = n_hidden in 0 .. CADM_MAX_VALUE_LAYERS, every width in
+ * 1 .. CADM_MAX_VALUE_WIDTH, one hidden activation CADM_VALUE_RELU | _TANH | _SWISH, a linear output of A <= CADM_MAX_POLICY_ACTIONS
+ * units, D <= CADM_MAX_VALUE_DIMS.  For a state s [D], all in float32 (csrc/policy.hip, csrc/mlp_chain.h):
+ *   x_k = (s_k - mean_k) * std_inv_k                                        one subtract, one multiply
+ *   layer with K inputs, unit u:  acc = b[u];  for k = 0 .. K4-1 ascending:  acc = fmaf(W[k][u], x_k, acc)     (the value net's chain)
+ *   hidden: the activation;   output z_d: the sum itself
+ *   CADM_POLICY_TANH: a_d = mid + half * tanhf(z_d),  mid = 0.5f * (ub + lb), half = 0.5f * (ub - lb)  (one multiply, then one add, no
+ *   fma; lb / ub: the ctx's lower_bound / upper_bound);   CADM_POLICY_NONE: a_d = z_d
+ *   with noise:  a_d = a_d + noise_std * xi_d  (one multiply, one add);   always last:  a_d = fminf(fmaxf(a_d, lb), ub).
+ * cadm_set_policy_net: as cadm_set_value_net (device pointers, a packed copy the ctx owns, a second call replaces the net, params NULL
+ * clears it).  n_samples and noise_std of the registered params are not kept: every call below brings its own.
+ * cadm_policy_eval: act_out[r,:] = the action of states[r,:] for states [R,D]: squash and clip, no noise -- the chain of the roll below.
+ * cadm_policy_propose: P = n_samples proposal sequences per env, seqs_out [m,P,H,A].  Sequence (mi, j) acts at step t on its STATE
+ * ESTIMATE, the mean over its p particles: obs[mi] at t = 0; at t >= 1 sequential float32 adds over the particles in ascending order,
+ * starting from particle 0's value, then one IEEE division by (float)p.  A sequence with a non-finite value in any particle takes the
+ * fallback clip(0, lb, ub) in every dim.  Its action then moves its particles one step through the model (a one-step rollout under the
+ * iteration word CADM_POLICY_IT + 2 t = 0xFA0000 + 2 t; particles keep their member; a deterministic ctx rolls the mean head): H policy
+ * steps and H - 1 one-step rollouts, nothing behind the last action.  Sequence 0 never gets noise; for j >= 1 xi is drawn with
+ * Philox4x32-10 keyed (seed, call), counter (mi * P + j, t, g, 5): one call serves dims 4 g .. 4 g + 3, words (0, 1) through Box-Muller to
+ * dims 4 g and 4 g + 1, words (2, 3) to 4 g + 2 and 4 g + 3; noise_std == 0 draws nothing.  ctx_vec: the context encoder's output
+ * (cadm_context_forward), NULL for a model without one.  states_out [H,m,P,p,D] or NULL: the particle states every step read (step 0:
+ * obs[mi] in every particle).  workspace: cadm_policy_workspace_bytes(ctx, m, P) bytes.  The roll follows its own actions: an actuator
+ * model's delay is not honoured inside it.
+ * Determinism: an action is one chain in ascending k behind a sequential particle sum, no floating-point atomics: the same bits run to
+ * run, at any row position, for any m or P, from cadm_policy_eval as from the roll.
+ * Refusals, before any HIP call: CADM_EINVAL for null pointers, n_hidden outside 0 .. 4, a width outside 1 .. 512, an unknown activation
+ * or squash, n_samples < 1, a noise_std negative or not finite, D > CADM_MAX_VALUE_DIMS, A > CADM_MAX_POLICY_ACTIONS, a discrete ctx
+ * (cartpole), a candidate-sharded ctx, activation tiles beyond the 160 KiB of LDS, a ctx whose num_cem_iters or horizon reaches the
+ * roll's iteration words; params that do not describe the registered net (layers, widths, activation, squash): CADM_EINVAL; no
+ * registered net: CADM_ESTATE. */
+#define CADM_MAX_POLICY_ACTIONS 64
+#define CADM_POLICY_NONE 0
+#define CADM_POLICY_TANH 1
+typedef struct cadm_policy_params {
+    int32_t n_hidden;                          /* L: 0 .. CADM_MAX_VALUE_LAYERS */
+    int32_t hidden[CADM_MAX_VALUE_LAYERS];     /* h_1 .. h_L, each 1 .. CADM_MAX_VALUE_WIDTH */
+    int32_t activation;                        /* CADM_VALUE_RELU | CADM_VALUE_TANH | CADM_VALUE_SWISH */
+    int32_t squash;                            /* CADM_POLICY_NONE | CADM_POLICY_TANH */
+    int32_t n_samples;                         /* P >= 1: proposal sequences per env */
+    float noise_std;                           /* finite, >= 0: exploration noise of sequences 1 .. P - 1 */
+} cadm_policy_params;
+int cadm_set_policy_net(cadm_ctx* ctx, const cadm_policy_params* params, const float* const* W, const float* const* b, const float* mean,
+                        const float* std_inv, void* stream);
+int cadm_policy_eval(cadm_ctx* ctx, const float* states, int R, float* act_out, void* stream);
+size_t cadm_policy_workspace_bytes(cadm_ctx* ctx, int m, int P);
+int cadm_policy_propose(cadm_ctx* ctx, const cadm_policy_params* params, const float* obs, const float* ctx_vec, int m, uint32_t seed,
+                        uint32_t call, float* seqs_out, float* states_out, void* workspace, void* stream);
+/* The loop of cadm_rewarded_plan with the policy's proposals among its candidates: the outermost entry of the nest.  Behind the context
+ * encoder ONE cadm_policy_propose; every iteration then writes the P sequences into the candidate slots [K + (last iteration &&
+ * add_mean_last ? 1 : 0), .. + P) -- behind the kept elites and the mean candidate, in front of the knot shaping and the actuator pass,
+ * so proposals are shaped and pinned like any other candidate.  policy NULL: exactly the launches of cadm_rewarded_plan.  Refusals: those
+ * of cadm_rewarded_plan and of cadm_policy_propose, and keep_elites + 1 + n_samples beyond the smallest per-iteration candidate count
+ * max(floor(n / decay^it), 2 num_elites, keep_elites + 1) capped at n.  workspace: cadm_guided_workspace_bytes(ctx, m, n, K, mppi,
+ * terminate, actuator, uncertainty, P), enough for every combination of terms: cadm_rewarded_workspace_bytes' with a reward set, and
+ * with P = n_samples > 0 behind it the proposals [m,P,H,A] and the roll's workspace (0 for bad arguments) -- a loop with fewer terms
+ * takes fewer views in front of the policy's and fits; with policy NULL the workspace of cadm_rewarded_plan will do. */
+size_t cadm_guided_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P);
+int cadm_guided_plan(cadm_ctx* ctx, const cadm_policy_params* policy, const cadm_reward_params* params, const cadm_value_params* value,
+                     const cadm_uncertainty_params* uncertainty, const cadm_actuator_params* actuator, float* prev_io, float* prefix_io,
+                     int advance, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                     const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                     const cadm_score_params* score, int update, const cadm_mppi_params* mppi_params, const float* obs,
+                     const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                     int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                     float* best_return_out, void* stream);
+
 /* One training step =sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
