@@ -30,6 +30,76 @@ TERM_ENGINES = {      # name: (env, D, A, E, p, H); "widest" is helpers.corner_s
     "p1": ("halfcheetah", 18, 6, 1, 1, 5),
 }
 
+# The engines of tests/test_gpu_policy_envelope.py -- the policy prior's roll and the guided loop off halfcheetah at p in {5, 20}, H <= 5;
+# tests/test_policy_ref.py reads the shapes, the nets and the noise levels from here and shows on the CPU that the restatement alone
+# meets the conditions the GPU tests put on their inputs.  Every built-in kind at hidden 200 x 4 and swish (nothing is built on demand),
+# the problems as TERM_ENGINES' (m = 2, seed 3, `trained_like`; "wide": seed 8), widened to more envs by `with_rows`.
+POLICY_ENGINES = {      # name: (env, D, A, E, p, H) + (context, (lower_bound, upper_bound) or None)
+    "pend": TERM_ENGINES["pend"] + (True, None),                       # A = 1, D4 = 4
+    "ant": ("ant", 28, 8, 5, 10, 3, True, None),                       # two full noise groups, p = 10
+    "slim": TERM_ENGINES["slim"] + (True, None),                       # odd D, groups 0 .. 4 with one dim in the last, p = 15
+    "long": TERM_ENGINES["long"] + (False, None),                      # H = 40: the CPU roll of tests/test_policy_ref.py stays finite over all 40
+    "big": ("halfcheetah", 18, 6, 5, 5, 2, False, None),               # "long"'s weights: the roll with two row tiles per workgroup
+    "bnd": ("halfcheetah", 18, 6, 5, 5, 3, True, (-0.5, 2.0)),         # bounds that are not -1, 1
+    "wide": ("widest", 48, 24, 5, 10, 1, True, None),                  # noise at A = 24; H = 1: no rollout, no module built on demand
+    "fit": ("halfcheetah", 18, 6, 5, 5, 5, False, None),               # tests/test_gpu_policy.py's "hc5-vanilla": the exact fit of the slots
+}
+POLICY_NET = ((50, 30, 70, 18), "swish", "tanh")      # tests/test_gpu_policy.py's net of the roll: `policy_ref.envelope_policy`
+POLICY_BIG_NET = ((64, 48, 200), "swish", "tanh", 21)      # hidden, act, squash, `policy_ref.he_policy`'s seed (out_scale 0.5)
+POLICY_BND_NET = ((37,) * 4, "tanh", 5, 1.0)      # hidden, act, `he_policy`'s seed and out_scale: with squash "none" both bounds are reached
+POLICY_LOOP_NET = ((50, 30), "tanh", "tanh", 40)      # the guided loop's: hidden, act, squash, `he_policy`'s seed (out_scale 0.5)
+POLICY_LONG_IN_SCALE = 2.0 ** -7      # "long": what the first layer of POLICY_NET is scaled by (`policy_layers`)
+POLICY_SEED, POLICY_CALL = 5, 9
+POLICY_ROLLS = {      # name: (noise_std, [(m, P)]) of `check_roll`
+    "pend": (0.3, [(3, 6), (1, 17)]), "ant": (0.3, [(3, 6), (1, 17)]), "slim": (0.3, [(3, 6), (1, 17)]),
+    "long": (0.2, [(2, 6)]), "big": (0.3, [(65, 127)]), "bnd": (0.5, [(3, 6)]), "wide": (0.25, [(3, 17)]),
+}
+
+
+def with_rows(prob, m, seed=77):
+    """a copy of a synth problem with obs, cp_obs and cp_act grown to m envs: the problem's own rows first, then rows drawn as
+    `synth.make_problem` draws them"""
+    have = prob["obs"].shape[0]
+    if m <= have:
+        return dict(prob, obs=prob["obs"][:m], cp_obs=prob["cp_obs"][:m], cp_act=prob["cp_act"][:m], m=m)
+    rng = np.random.default_rng(seed)
+    D, A, Hh = prob["D"], prob["A"], prob["Hh"]
+    more = m - have
+    return dict(prob, m=m, obs=np.concatenate([prob["obs"], rng.standard_normal((more, D))]),
+                cp_obs=np.concatenate([prob["cp_obs"], 0.1 * rng.standard_normal((more, D * Hh))]),
+                cp_act=np.concatenate([prob["cp_act"], rng.uniform(-1.0, 1.0, (more, A * Hh))]))
+
+
+def policy_problem(name, env=None):
+    """the synth problem of one of POLICY_ENGINES (m = 2); env: the declaration behind "widest" (helpers.corner_spec), which this
+    module does not import"""
+    from cadm_amd import synth
+    kind, D, A, E, p, H, context, _ = POLICY_ENGINES[name]
+    if name == "wide":
+        return synth.make_problem(env=env, context=True, E=E, m=2, H=H, seed=8)
+    return synth.make_problem(env=kind, context=context, E=E, m=2, H=H, seed=3, trained_like=True)
+
+
+def policy_layers(name, squash="tanh"):
+    """(layers, act, squash) of the net tests/test_gpu_policy_envelope.py rolls on engine `name`.  "long": the synthetic model's states
+    double every five steps (tests/test_policy_ref.py), so the first layer is scaled by 2^-7 -- an exact scaling -- and the tanh squash
+    stays open over all 40; "wide": tests/test_gpu_policy.py's bias-only net of the noise test."""
+    import policy_ref as pref
+    _, D, A = POLICY_ENGINES[name][:3]
+    if name == "wide":
+        return [(np.zeros((D, A), np.float32), np.linspace(-0.3, 0.3, A).astype(np.float32))], "relu", "none"
+    if name == "big":
+        hidden, act, squash, seed = POLICY_BIG_NET
+        return pref.he_policy(D, hidden, A, seed, 0.5), act, squash
+    if name == "bnd":
+        hidden, act, seed, scale = POLICY_BND_NET
+        return pref.he_policy(D, hidden, A, seed, scale), act, squash
+    hidden, act, squash = POLICY_NET
+    layers = pref.envelope_policy(D, hidden, A)
+    if name == "long":
+        layers[0] = ((layers[0][0] * np.float32(POLICY_LONG_IN_SCALE)).astype(np.float32), layers[0][1])
+    return layers, act, squash
+
 
 def term_traj(name, m, n, seed):
     """`synth_traj` at the shape of one of TERM_ENGINES"""

@@ -177,6 +177,57 @@ def test_propose_step_at_one_particle_is_policy_eval(gpu):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 3: the roll, one step at a time
+def check_roll(eng, twin, prob, prm, layers, act, squash, m, seed, call, noise, lb, ub):
+    """The body of `test_one_step_at_a_time` on the first m envs of `prob`: `eng` has the net `layers` registered as `prm` describes it
+    (P = prm.n_samples) and the action bounds lb, ub; `twin` is an engine with n_forwards = 1, the same weights and the same bounds.
+    -> (seqs, states, worst action error / (1e-5 of the range), worst noise error / bound)."""
+    H, P, rng_ = eng.H, int(prm.n_samples), float(ub) - float(lb)
+    context = eng.C > 0
+    obs = np.asarray(prob["obs"], F)[:m]
+    ctx_vec = eng.context_forward(prob["cp_obs"][:m], prob["cp_act"][:m]) if context else None
+    seqs, states = eng.policy_propose(prm, obs, ctx_vec, seed=seed, call=call, want_states=True)
+    again = eng.policy_propose(prm, obs, ctx_vec, seed=seed, call=call)
+    np.testing.assert_array_equal(_bits(_np(again)), _bits(_np(seqs)), err_msg="run to run, with and without states_out")
+    seqs, states = _np(seqs), _np(states)
+    assert seqs.shape == (m, P, H, eng.A) and states.shape == (H, m, P, eng.p, eng.D) and np.isfinite(seqs).all() and np.isfinite(states).all()
+    np.testing.assert_array_equal(_bits(states[0]), _bits(np.broadcast_to(obs[:, None, None, :], states[0].shape)), err_msg="step 0 reads obs[mi]")
+    worst_a = worst_z = 0.0
+    for t in range(H):
+        est = pref.particle_mean32(states[t])
+        z = pref.xi(seed, call, m, P, t, eng.A)
+        z[:, 0] = 0.0
+        want, raw = pref.emulate32(est, layers, act, squash, lb, ub, xi=z, noise_std=noise, want_raw=True)
+        a = seqs[:, :, t]
+        err = np.abs(a.astype(np.float64) - want.astype(np.float64)).max()
+        assert err <= 1e-5 * rng_, "step %d: the action is off by %.3e" % (t, err)
+        worst_a = max(worst_a, err / (1e-5 * rng_))
+        # sequence 0 is the policy's own action: no noise (the raw action lies inside the bounds under the tanh squash; without it, clipped)
+        assert np.abs(a[:, 0].astype(np.float64) - np.clip(raw[:, 0], F(lb), F(ub))).max() <= 1e-5 * rng_
+        if P > 1:
+            free = (a[:, 1:] > F(lb)) & (a[:, 1:] < F(ub))
+            rec = (a[:, 1:].astype(np.float64) - raw[:, 1:].astype(np.float64)) / float(F(noise))
+            bound = 1e-5 * rng_ / noise + 4e-6 * np.maximum(1.0, pref.xi_radius(seed, call, m, P, t, eng.A)[:, 1:] / 2.0)
+            dz = np.abs(rec - z[:, 1:])
+            assert free.mean() > 0.5 and (dz[free] <= bound[free]).all(), "step %d: the noise is off by %.3e" % (t, (dz[free] / bound[free]).max())
+            worst_z = max(worst_z, float((dz[free] / bound[free]).max()))
+        if t + 1 < H:
+            tv = twin.context_forward(prob["cp_obs"][:m], prob["cp_act"][:m]) if context else None
+            _, nxt = twin.rollout_returns(obs, tv, np.ascontiguousarray(a[:, :, None, :]), obs_rows=states[t].reshape(-1, eng.D), seed=seed,
+                                          call=call, it=hplanner.POLICY_IT + 2 * t, want_traj=True)
+            nxt = _np(nxt)
+            assert nxt.shape == (1, m, P, eng.p, eng.D)
+            np.testing.assert_array_equal(_bits(states[t + 1]), _bits(nxt[0]), err_msg="the states step %d read against the one-step rollout" % (t + 1))
+            assert not np.array_equal(states[t + 1], states[t])
+            if not eng.deterministic and eng.p > eng.E:      # two particles of one member differ by their head noise
+                assert not np.array_equal(states[t + 1][:, :, 0], states[t + 1][:, :, eng.E])
+    # the rows of env 0 do not depend on m, nor a sequence's on P: the same bits wherever the row sits (row ids, hence the noise, agree)
+    if m > 1:
+        alone = _np(eng.policy_propose(prm, obs[:1], None if ctx_vec is None else eng.context_forward(prob["cp_obs"][:1], prob["cp_act"][:1]),
+                                       seed=seed, call=call))
+        np.testing.assert_array_equal(_bits(alone[0, :, 0]), _bits(seqs[0, :, 0]), err_msg="env 0 alone, step 0")
+    return seqs, states, worst_a, worst_z
+
+
 ROLLS = [("v-p5", 2, 1, 1), ("v-p5", 2, 1, 17), ("c-p20", 3, 3, 6), ("cd-p5", 2, 3, 6), ("v-p5", 1, 3, 6), ("c-p20", 2, 1, 17)]
 
 
@@ -193,51 +244,10 @@ def test_one_step_at_a_time(engines, fam, H, m, P):
     draw's radius sqrt(-2 ln u1) beyond 2: the error of the unit-circle factor is multiplied by it."""
     prob, eng = engines("%s-h%d" % (fam, H))
     _, twin = engines("%s-h1" % fam)
-    context, noise, seed, call = not fam.startswith("v-"), 0.3, 5, 9
+    noise, seed, call = 0.3, 5, 9
     prm, layers = _set(eng, (50, 30, 70, 18), "swish", "tanh", P=P, noise=noise)
-    obs = np.asarray(prob["obs"], F)[:m]
-    ctx_vec = eng.context_forward(prob["cp_obs"][:m], prob["cp_act"][:m]) if context else None
-    seqs, states = eng.policy_propose(prm, obs, ctx_vec, seed=seed, call=call, want_states=True)
-    again = eng.policy_propose(prm, obs, ctx_vec, seed=seed, call=call)
-    np.testing.assert_array_equal(_bits(_np(again)), _bits(_np(seqs)), err_msg="run to run, with and without states_out")
-    seqs, states = _np(seqs), _np(states)
-    assert seqs.shape == (m, P, H, eng.A) and states.shape == (H, m, P, eng.p, eng.D) and np.isfinite(seqs).all() and np.isfinite(states).all()
-    np.testing.assert_array_equal(_bits(states[0]), _bits(np.broadcast_to(obs[:, None, None, :], states[0].shape)), err_msg="step 0 reads obs[mi]")
-    worst_a = worst_z = 0.0
-    for t in range(H):
-        est = pref.particle_mean32(states[t])
-        z = pref.xi(seed, call, m, P, t, eng.A)
-        z[:, 0] = 0.0
-        want, raw = pref.emulate32(est, layers, "swish", "tanh", -1.0, 1.0, xi=z, noise_std=noise, want_raw=True)
-        a = seqs[:, :, t]
-        err = np.abs(a.astype(np.float64) - want.astype(np.float64)).max()
-        assert err <= 1e-5 * 2.0, "step %d: the action is off by %.3e" % (t, err)
-        worst_a = max(worst_a, err / 2e-5)
-        # sequence 0 is the policy's own action: no noise
-        assert np.abs(a[:, 0].astype(np.float64) - raw[:, 0]).max() <= 1e-5 * 2.0
-        if P > 1:
-            free = (np.abs(a[:, 1:]) < 1.0)
-            rec = (a[:, 1:].astype(np.float64) - raw[:, 1:].astype(np.float64)) / float(F(noise))
-            bound = 1e-5 * 2.0 / noise + 4e-6 * np.maximum(1.0, pref.xi_radius(seed, call, m, P, t, eng.A)[:, 1:] / 2.0)
-            dz = np.abs(rec - z[:, 1:])
-            assert free.mean() > 0.5 and (dz[free] <= bound[free]).all(), "step %d: the noise is off by %.3e" % (t, (dz[free] / bound[free]).max())
-            worst_z = max(worst_z, float((dz[free] / bound[free]).max()))
-        if t + 1 < H:
-            tv = twin.context_forward(prob["cp_obs"][:m], prob["cp_act"][:m]) if context else None
-            _, nxt = twin.rollout_returns(obs, tv, np.ascontiguousarray(a[:, :, None, :]), obs_rows=states[t].reshape(-1, eng.D), seed=seed,
-                                          call=call, it=hplanner.POLICY_IT + 2 * t, want_traj=True)
-            nxt = _np(nxt)
-            assert nxt.shape == (1, m, P, eng.p, eng.D)
-            np.testing.assert_array_equal(_bits(states[t + 1]), _bits(nxt[0]), err_msg="the states step %d read against the one-step rollout" % (t + 1))
-            assert not np.array_equal(states[t + 1], states[t])
-            if not fam.startswith("cd-") and eng.p > eng.E:      # two particles of one member differ by their head noise
-                assert not np.array_equal(states[t + 1][:, :, 0], states[t + 1][:, :, eng.E])
+    _, _, worst_a, worst_z = check_roll(eng, twin, prob, prm, layers, "swish", "tanh", m, seed, call, noise, -1.0, 1.0)
     print("\n[%s H=%d m=%d P=%d] worst action err / (1e-5 of range) %.3f, worst noise err / bound %.3f" % (fam, H, m, P, worst_a, worst_z))
-    # the rows of env 0 do not depend on m, nor a sequence's on P: the same bits wherever the row sits (row ids, hence the noise, agree)
-    if m > 1:
-        alone = _np(eng.policy_propose(prm, obs[:1], None if ctx_vec is None else eng.context_forward(prob["cp_obs"][:1], prob["cp_act"][:1]),
-                                       seed=seed, call=call))
-        np.testing.assert_array_equal(_bits(alone[0, :, 0]), _bits(seqs[0, :, 0]), err_msg="env 0 alone, step 0")
 
 
 def test_noise_against_philox(engines):

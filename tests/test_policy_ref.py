@@ -1,6 +1,8 @@
 """CPU: the policy prior of the opt-in planner -- the float32 emulation of the kernel's chain against the float64 restatement
 (tests/policy_ref.py), the noise, the fallback, the slot arithmetic, the struct and the signatures against the header, the options and
-the host-side refusals.  The kernels themselves: tests/test_gpu_policy.py."""
+the host-side refusals; and, for the geometries of tests/test_gpu_policy_envelope.py (behind_rollout.py POLICY_ENGINES), that the
+restatement alone meets what those tests ask of their inputs: the nets hold the bar and are live, more than half of the draws stay
+unclipped, the 40-step roll stays finite.  The kernels themselves: tests/test_gpu_policy.py and tests/test_gpu_policy_envelope.py."""
 import ctypes
 import os
 import re
@@ -9,13 +11,16 @@ import types
 import numpy as np
 import pytest
 
+import behind_rollout as br
 import policy_ref as pref
 import value_ref as vref
 from cadm_amd import _lib
 from cadm_amd import planner as hplanner
 from cadm_amd.engine import HipEngine
 from cadm_amd.planner import PlanOptions
-from helpers import assert_close, floored_rel
+from helpers import assert_close, corner_spec, floored_rel, oracle_problem
+from oracle import philox
+from oracle import planner as oplanner
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -151,6 +156,139 @@ def test_slot_arithmetic_against_the_candidate_rule():
             assert hplanner.policy_slot(K, True, True) + P <= least
     src = open(os.path.join(ROOT, "cadm_amd", "csrc", "icem.hip")).read()
     assert "K + (last && prm->add_mean_last ? 1 : 0)" in src and "(long long)K + 1 + P <= n_min" in src
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the envelope's inputs
+# What tests/test_gpu_policy_envelope.py asks of its inputs, shown for the restatement alone: the engines, nets, seeds and noise levels
+# are behind_rollout.py's POLICY_* tables, which both files read.
+def envelope_problem(name):
+    return br.policy_problem(name, corner_spec("widest") if name == "wide" else None)
+
+
+envelope_layers = br.policy_layers
+
+
+def test_nets_hold_the_bar_on_the_envelope_inputs():
+    """The nets the envelope rolls, on D = 3, 28, 45 and 48 (and the halfcheetah nets that are new there): the float32 chain within 1e-5
+    of the action range of the float64 restatement, and live -- on `states_for`'s rows and on the start states the roll reads."""
+    worst = 0.0
+    loop = br.POLICY_LOOP_NET
+    cases = [(n, envelope_layers(n) + ((-1.0, 1.0),)) for n in ("pend", "ant", "slim", "big", "long")]
+    cases += [("wide", (pref.envelope_policy(48, br.POLICY_NET[0], 24),) + br.POLICY_NET[1:] + ((-1.0, 1.0),))]
+    cases += [("bnd", envelope_layers("bnd", sq) + ((-0.5, 2.0),)) for sq in pref.SQUASH]
+    cases += [(n, (pref.he_policy(br.POLICY_ENGINES[n][1], loop[0], br.POLICY_ENGINES[n][2], loop[3], 0.5), loop[1], loop[2], (-1.0, 1.0)))
+              for n in ("pend", "slim")]
+    assert sorted({br.POLICY_ENGINES[n][1] for n, _ in cases}) == [3, 18, 28, 45, 48]
+    for name, (layers, act, squash, (lb, ub)) in cases:
+        D = br.POLICY_ENGINES[name][1]
+        start = np.asarray(br.with_rows(envelope_problem(name), 3)["obs"], F)
+        for x in (states_for(D), start):
+            share, spread, open_ = pref.liveness(x, layers, act)
+            assert share >= 0.5 and spread > 1e-3 and open_ >= 0.5, "%s %s: %.2f %.2e %.2f" % (name, squash, share, spread, open_)
+            ref = pref.action64(x, layers, act, squash, lb, ub)
+            emu = pref.emulate32(x, layers, act, squash, lb, ub)
+            err = np.abs(emu.astype(np.float64) - ref).max()
+            assert err <= 1e-5 * (ub - lb), (name, squash, err)
+            assert emu.min() >= F(lb) and emu.max() <= F(ub)
+            worst = max(worst, err / (1e-5 * (ub - lb)))
+    print("\n[envelope nets] float32 chain against float64: %.3f of (1e-5 of the range)" % worst)
+
+
+def test_noise_prefixes_and_counters_of_the_wide_groups():
+    """An action dim's draw depends on (row, t, g = d >> 2) and its place in the group, never on A: the draws of a narrower env are the
+    leading dims of a wider one's -- A = 1 uses z0 of words (0, 1) of group 0, A = 17 one dim of group 4, A = 24 six full groups -- and
+    another group, step or row is another draw."""
+    seed, call, m, P = br.POLICY_SEED, br.POLICY_CALL, 3, 17
+    wide = pref.xi(seed, call, m, P, 1, 24)
+    assert wide.shape == (m, P, 24) and len(np.unique(wide)) == wide.size
+    for A in (1, 6, 8, 17):
+        np.testing.assert_array_equal(pref.xi(seed, call, m, P, 1, A).view(np.uint32), wide[..., :A].view(np.uint32), err_msg="A = %d" % A)
+    np.testing.assert_array_equal(pref.xi(seed, call, m, P, 1, 8)[..., :1], pref.xi(seed, call, m, P, 1, 1))
+    # group g of one row is group 0 of no other counter: every (g, word pair) of a row differs, as do the steps and the rows
+    for g in range(1, 6):
+        assert not np.array_equal(wide[..., 4 * g:4 * g + 4], wide[..., :4]), "group %d repeats group 0" % g
+    for t in (0, 2, 39):
+        other = pref.xi(seed, call, m, P, t, 24)
+        assert not (other == wide).any(), "step %d repeats step 1" % t
+    assert not (np.roll(wide.reshape(m * P, 24), 1, axis=0) == wide.reshape(m * P, 24)).any()
+    # the row id is mi * P + j: env 1 of (3, 17) is rows 17 .. 33 of one env with 51 sequences
+    np.testing.assert_array_equal(pref.xi(seed, call, 1, m * P, 1, 17).reshape(m, P, 17), wide[..., :17])
+    r = pref.xi_radius(seed, call, m, P, 1, 17)
+    assert r.shape == (m, P, 17) and (r[..., 16] >= np.abs(wide[..., 16]) - 1e-6).all()
+
+
+def test_share_of_unclipped_draws_at_step_zero():
+    """The GPU tests recover the noise from the dims the clip left alone and ask that these are more than half (0.98 with the bias-only
+    net of the A = 24 test): the restatement's own share at step 0 of every geometry, with the seeds, nets and noise levels of the
+    GPU tests.  With bounds -0.5, 2 and squash "none", step 0 alone already has elements on either bound."""
+    seed, call = br.POLICY_SEED, br.POLICY_CALL
+    for name, (noise, shapes) in br.POLICY_ROLLS.items():
+        _, D, A, _, _, _, _, bounds = br.POLICY_ENGINES[name]
+        lb, ub = bounds or (-1.0, 1.0)
+        prob = envelope_problem(name)
+        for squash in (pref.SQUASH if name == "bnd" else ("tanh",)):
+            layers, act, squash = envelope_layers(name, squash)
+            for m, P in shapes:
+                obs = np.asarray(br.with_rows(prob, m)["obs"], F)
+                z = pref.xi(77 if name == "wide" else seed, 4 if name == "wide" else call, m, P, 0, A)      # (wide: test_noise_against_philox's)
+                z[:, 0] = 0.0
+                a = pref.emulate32(np.broadcast_to(obs[:, None], (m, P, D)), layers, act, squash, lb, ub, xi=z, noise_std=noise)
+                free = ((a > F(lb)) & (a < F(ub)))[:, 1:]
+                assert free.mean() > (0.98 if name == "wide" else 0.5), "%s %s m=%d P=%d: %.3f of the draws are unclipped" % (name, squash, m, P, free.mean())
+                if name == "slim":
+                    assert free[..., 16].any(), "no unclipped draw of group 4"
+                if name == "bnd" and squash == "none":
+                    assert (a == F(lb)).any() and (a == F(ub)).any()
+                print("[%s %s m=%d P=%d noise %.2f] unclipped at step 0: %.3f" % (name, squash, m, P, noise, free.mean()))
+
+
+def cpu_roll(prob, layers, act, squash, m, P, p, H, noise, seed, call):
+    """the proposal roll of a vanilla problem restated on the CPU: `emulate32` on the particle mean, the oracle's one-step rollout from
+    obs_rows under the Philox head noise of the iteration word POLICY_IT + 2 t -> (seqs [m,P,H,A], states [H,m,P,p,D])"""
+    o = oracle_problem(br.with_rows(prob, m), F)
+    E, D, A = prob["E"], prob["D"], prob["A"]
+    states = np.broadcast_to(o["obs"][:, None, None, :], (m, P, p, D)).copy()
+    seqs, read = np.empty((m, P, H, A), F), []
+    for t in range(H):
+        read.append(states)
+        z = pref.xi(seed, call, m, P, t, A)
+        z[:, 0] = 0.0
+        a = pref.emulate32(pref.particle_mean32(states), layers, act, squash, xi=z, noise_std=noise)
+        seqs[:, :, t] = a
+        eps = philox.eps_normals(seed, call, hplanner.POLICY_IT + 2 * t, m, P, p, 1, D)
+        _, traj = oplanner.rollout_indexed(o["env"], o["ff"], o["st"], o["obs"], None, np.ascontiguousarray(a[:, :, None, :]), eps, E, p, False,
+                                           return_traj=True, obs_rows=states)
+        states = traj[0].astype(F)
+    return seqs, np.stack(read)
+
+
+def test_the_long_roll_stays_finite():
+    """Engine "long": the restated policy rolled through the oracle model for the H of POLICY_ENGINES -- every sequence, the noiseless
+    one among them -- reads finite states below 1e4 in magnitude at every step, the last two steps' actions differ, and more than half
+    of the draws stay unclipped at every step: the GPU test's checks along the 40 steps compare numbers, not NaN."""
+    _, D, A, E, p, H = br.POLICY_ENGINES["long"][:6]
+    noise, ((m, P),) = br.POLICY_ROLLS["long"]
+    layers, act, squash = envelope_layers("long")
+    seqs, states = cpu_roll(envelope_problem("long"), layers, act, squash, m, P, p, H, noise, br.POLICY_SEED, br.POLICY_CALL)
+    assert H == 40 and states.shape == (H, m, P, p, D)
+    assert np.isfinite(states).all() and np.abs(states).max() < 1e4, "the synthetic model leaves 1e4 within %d steps" % H
+    assert np.isfinite(seqs).all() and not np.array_equal(seqs[:, :, H - 2], seqs[:, :, H - 1])
+    free = np.abs(seqs[:, 1:]) < 1.0
+    assert (free.mean(axis=(0, 1, 3)) > 0.5).all(), free.mean(axis=(0, 1, 3)).min()
+    moved = np.abs(np.diff(states, axis=0)).max(axis=(1, 2, 3, 4))
+    assert (moved > 0).all()
+    print("\n[long roll on the CPU] largest |state| %.3g over %d steps, smallest unclipped share %.3f" % (np.abs(states).max(), H, free.mean(axis=(0, 1, 3)).min()))
+
+
+def test_slot_arithmetic_of_the_exact_fit():
+    """The GPU test of the exact fit: 24 candidates, 8 elites, 3 iterations, decay 2 -- 24, 16, 16 candidates --, 2 kept elites, the mean
+    added last and 13 proposals: K + 1 + P = 16 = the smallest iteration, the proposals in slots 2 .. 14 and, last, 3 .. 15."""
+    n, KE, iters, decay, K, P = 24, 8, 3, 2.0, 2, 13
+    assert [pref.n_it(n, decay, it, KE, K) for it in range(iters)] == [24, 16, 16]
+    assert hplanner.policy_min_candidates(n, decay, KE, K, iters) == 16 == K + 1 + P
+    assert hplanner.policy_slot(K, False, True) == 2 and hplanner.policy_slot(K, True, True) == 3
+    assert hplanner.policy_slot(K, True, True) + P == 16 and hplanner.policy_slot(K, False, True) + P == 15
+    assert K + 1 + (P + 1) > hplanner.policy_min_candidates(n, decay, KE, K, iters)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- the header
