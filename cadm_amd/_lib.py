@@ -147,6 +147,15 @@ class PolicyParams(C.Structure):        # include/cadm_hip.h cadm_policy_params 
                 ("n_samples", C.c_int32), ("noise_std", C.c_float)]
 
 
+MAX_CRITICS = 5                                                            # CADM_MAX_CRITICS
+CRITIC_REDUCES = {"min": 0, "mean": 1}                                     # CADM_CRITIC_MIN / _MEAN
+
+
+class CriticParams(C.Structure):        # include/cadm_hip.h cadm_critic_params (the layer conventions are the value net's)
+    _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_VALUE_LAYERS), ("activation", C.c_int32), ("n_critics", C.c_int32),
+                ("reduce", C.c_int32), ("weight", C.c_float)]
+
+
 class TrainHParams(C.Structure):
     _fields_ = [
         ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
@@ -243,6 +252,14 @@ SIGNATURES = {
                               C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P,
                               C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i,
                               _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_set_critic_nets": (_i, [_P, C.POINTER(CriticParams), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
+    "cadm_critic_eval": (_i, [_P, _P, _P, _i, _P, _P, _P, _P]),
+    "cadm_critic_returns": (_i, [_P, C.POINTER(CriticParams), _P, _P, _i, _i, _P, _P, _P, _P]),
+    "cadm_critic_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "cadm_critic_plan": (_i, [_P, C.POINTER(CriticParams), C.POINTER(PolicyParams), C.POINTER(RewardParams), C.POINTER(ValueParams),
+                              C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P,
+                              C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P,
+                              _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

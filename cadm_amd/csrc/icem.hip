@@ -16,7 +16,9 @@
 // cadm_valued_plan also adds a caller-supplied value net's V of every particle's last state (value.hip) to the particle returns;
 // cadm_rewarded_plan also adds a caller-supplied reward net's R of every step of every particle (reward.hip) to the particle returns;
 // cadm_guided_plan also rolls a caller-supplied policy net through the model once per call (policy.hip) and places its proposal
-// sequences among every iteration's candidates.
+// sequences among every iteration's candidates;
+// cadm_critic_plan also adds weight * reduce_c Q_c(s_H, pi(s_H)) of caller-supplied critics at the registered actor's action (critic.hip) to
+// the particle returns, in the place of the terminal value.
 #include <math.h>
 
 #include "planner.h"
@@ -386,6 +388,11 @@ extern "C" size_t cadm_rewarded_workspace_bytes(cadm_ctx* ctx, int m, int n, int
     return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0, 1);
 }
 
+// the guided loop's: a terminal Q reads the trajectory view and the first violations the other terms read, and takes no view of its own
+extern "C" size_t cadm_critic_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P) {
+    return cadm_guided_workspace_bytes(ctx, m, n, K, mppi, terminate, actuator, uncertainty, P);
+}
+
 // enough for every combination of terms: the rewarded loop's views, and with P > 0 behind them the proposals and the roll's workspace
 // (a loop with fewer terms takes fewer views in front of the policy's: it fits)
 extern "C" size_t cadm_guided_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P) {
@@ -425,6 +432,10 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 // policy: a policy prior (policy.hip) of the net registered with cadm_set_policy_net; null = none, and today's launches.  With it ONE
 // proposal roll behind the context encoder, and in every iteration its P sequences take the slots behind the kept elites and the mean
 // candidate, in front of the knot shaping and the actuator pass.
+// critic: a terminal Q (critic.hip) of the critics registered with cadm_set_critic_nets at the action of the registered policy net; null =
+// none, and today's launches.  It stands where the terminal value stands and excludes it: weight * reduce_c Q_c(s, pi(s)), s = traj[H - 1],
+// is added to the particle rows behind the constraints, the tracking terms and the learned reward, before the score.  `policy` may be
+// null with it: the critic needs the registered net, not the proposals.
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
@@ -433,7 +444,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
                      const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr, const cadm_actuator_params* act = nullptr,
                      float* prev_io = nullptr, float* prefix_io = nullptr, int advance = 0,
                      const cadm_uncertainty_params* unc = nullptr, const cadm_value_params* value = nullptr,
-                     const cadm_reward_params* reward = nullptr, const cadm_policy_params* policy = nullptr) {
+                     const cadm_reward_params* reward = nullptr, const cadm_policy_params* policy = nullptr,
+                     const cadm_critic_params* critic = nullptr) {
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -460,6 +472,10 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     if (unc && (rc = cadm_uncertainty_check(ctx, unc, who))) return rc;
     if (value && (rc = cadm_value_plan_check(ctx, value, who))) return rc;
     if (reward && (rc = cadm_reward_plan_check(ctx, reward, who))) return rc;
+    if (critic) {
+        CADM_REQUIRE(!value, "%s: a terminal Q and a terminal value are both given: a plan has one terminal term", who);
+        if ((rc = cadm_critic_plan_check(ctx, critic, who))) return rc;
+    }
     const int P = policy ? policy->n_samples : 0;
     if (policy) {
         if ((rc = cadm_policy_plan_check(ctx, policy, who))) return rc;
@@ -472,9 +488,9 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    // (w.traj: null without constraints, terms, an uncertainty term, a value and a reward; w.first: null unless terms, an uncertainty term,
-    // a value or a reward follow TERMINATE constraints)
-    const bool reads_traj = terms != nullptr || unc != nullptr || value != nullptr || reward != nullptr;
+    // (w.traj: null without constraints, terms, an uncertainty term, a value, a reward and a critic; w.first: null unless terms, an
+    // uncertainty term, a value, a reward or a critic follow TERMINATE constraints)
+    const bool reads_traj = terms != nullptr || unc != nullptr || value != nullptr || reward != nullptr || critic != nullptr;
     icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || reads_traj,
                reads_traj && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr, unc != nullptr,
                reward != nullptr, P);
@@ -526,6 +542,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if (reward && (rc = cadm_launch_reward(ctx, reward, w.traj, obs, w.actions, w.first, m, ni, w.rows, w.rstep, s))) return rc;
         // what lies behind the horizon: rows += weight * V(last state), of this iteration's ni packed candidates
         if (value && (rc = cadm_launch_value(ctx, value, w.traj, w.first, m, ni, w.rows, s))) return rc;
+        // or, from a learner without a V: rows += weight * reduce_c Q_c(last state, pi(last state)), one launch
+        if (critic && (rc = cadm_launch_critic(ctx, critic, w.traj, w.first, m, ni, w.rows, s))) return rc;
         if ((rc = cadm_particle_score(ctx, w.rows, m, ni, score, w.cand, stream))) return rc;      // (the mean: cadm_particle_mean itself)
         // the cost is deterministic per candidate: it comes off the candidate score, not off the particle rows
         if (act && (rc = cadm_launch_actuator_sub(w.cand, w.acost, (size_t)m * ni, s))) return rc;
@@ -716,4 +734,23 @@ extern "C" int cadm_guided_plan(cadm_ctx* ctx, const cadm_policy_params* policy,
     return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
                      workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
                      advance, unc, value, reward, policy);
+}
+
+// the outermost of the nest: with weight * reduce_c Q_c(s_H, pi(s_H)) of every particle's last state (critic.hip, the critics of
+// cadm_set_critic_nets at the action of the net of cadm_set_policy_net) added to the particle returns where the terminal value would be;
+// critic null: cadm_guided_plan's launches
+extern "C" int cadm_critic_plan(cadm_ctx* ctx, const cadm_critic_params* critic, const cadm_policy_params* policy,
+                                const cadm_reward_params* reward, const cadm_value_params* value, const cadm_uncertainty_params* unc,
+                                const cadm_actuator_params* act, float* prev_io, float* prefix_io, int advance, const cadm_track_params* track,
+                                const float* targets, int T, const int32_t* offset, const cadm_knot_params* knots, const int32_t* phase,
+                                const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
+                                const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
+                                const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
+                                uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "cadm_critic_plan: bad arguments");
+    CADM_REQUIRE(update == 0 || update == 1, "cadm_critic_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
+    const PlanUpdate upd{"cadm_critic_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
+                     advance, unc, value, reward, policy, critic);
 }

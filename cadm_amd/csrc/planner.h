@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, critic.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -124,6 +124,19 @@ int cadm_launch_reward(cadm_ctx* ctx, const cadm_reward_params* reward, const fl
 int cadm_policy_plan_check(const cadm_ctx* ctx, const cadm_policy_params* policy, const char* who);
 int cadm_launch_policy_propose(cadm_ctx* ctx, const cadm_policy_params* policy, const float* obs, const float* ctx_vec, int m, uint32_t seed,
                                uint32_t call, float* seqs_out, float* states_out, void* workspace, hipStream_t s, const char* who);
+// policy.hip, for critic.hip: the packed copy (mlp_chain.h) and the description of the registered policy net, null while none is
+// registered; and the net's dims D, h_1 .. h_L, A
+struct MlpNet;
+const MlpNet* cadm_policy_registered(const cadm_ctx* ctx, const cadm_policy_params** prm);
+void cadm_policy_net_dims(const cadm_ctx* ctx, const cadm_policy_params* policy, int* dims);
+// critic.hip: the refusals of a terminal Q (null parameters, a layer count outside 0 .. 4, a width outside 1 .. 512, an unknown
+// activation or reduce, a critic count outside 1 .. 5, a weight that is not finite, D or A beyond the nets' dims, a discrete / sharded
+// ctx, the input tile and the activation tiles beyond the LDS; no registered critics or no registered policy net: CADM_ESTATE;
+// parameters that do not describe the registered critics), before any HIP call; and the launch behind a rollout's traj [H, m, n, p, D]
+// (n the PACKED candidate count; first [m, n, p] or null): rows[q] += weight * reduce_c Q_c(s, pi(s)), s = traj[H - 1, q], in place
+int cadm_critic_plan_check(const cadm_ctx* ctx, const cadm_critic_params* critic, const char* who);
+int cadm_launch_critic(cadm_ctx* ctx, const cadm_critic_params* critic, const float* traj, const int32_t* first, int m, int n, float* rows,
+                       hipStream_t s);
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

@@ -163,6 +163,15 @@ void cadm_policy_free(cadm_ctx* ctx) {
     ctx->policy = nullptr;
 }
 
+// what critic.hip reads of the registered net: its packed copy and its description, null while none is registered; and its dims
+const MlpNet* cadm_policy_registered(const cadm_ctx* ctx, const cadm_policy_params** prm) {
+    if (!ctx->policy || !ctx->policy->set) return nullptr;
+    if (prm) *prm = &ctx->policy->prm;
+    return ctx->policy;
+}
+
+void cadm_policy_net_dims(const cadm_ctx* ctx, const cadm_policy_params* p, int* dims) { policy_dims(ctx, p, dims); }
+
 // the refusals of a policy net's description, before any HIP call
 int cadm_policy_check(const cadm_ctx* ctx, const cadm_policy_params* p, const char* who) {
     CADM_REQUIRE(p, "%s: the policy parameters are null", who);

@@ -78,6 +78,13 @@ Differences a caller can see (all opt-in except the first):
     an actor at run time (a list of (W [in,out], b [out]) or a torch.nn.Sequential) with nothing rebuilt, `clear_policy()` removes it,
     `policy_action(states)` evaluates it through the planner's kernel, `policy_proposals(obs, ...)`: the sequences a call would
     inject.  It alone takes the opt-in route; `fit` does not touch the policy;
+  * `cem_terminal_q=dict(hidden_sizes=(256, 256), activation="relu", n_critics=2, reduce="min" | "mean", weight=1.0,
+    policy=dict(hidden_sizes=, activation=, squash=))`: the terminal value of a learner that has an actor and Q critics but no V
+    (INTEGRATION.md "Terminal value from Q critics") -- weight * reduce_c Q_c(s_H, pi(s_H)) on the last state of every particle, one
+    fused launch per iteration.  The kwarg declares the shapes (`policy` may be left out with a `cem_policy_prior`: the actor is then
+    that net); `set_critics(nets, in_mean=None, in_std=None)` hands over the C critics (each as `set_terminal_value` takes a net, with
+    D + A inputs) and `set_policy(...)` the actor, at run time and with nothing rebuilt; `clear_critics()`, `q_value(states,
+    actions=None)`, `plan_terminal_q(obs, actions, ...)`.  Not together with `cem_terminal_value`.  It alone takes the opt-in route;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -262,6 +269,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_terminal_value=None,
                  cem_reward_net=None,
                  cem_policy_prior=None,
+                 cem_terminal_q=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -331,7 +339,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      n_forwards=n_forwards, action_dim=None if self.discrete else self.action_space_dims,
                                                      cem_uncertainty=cem_uncertainty, obs_dim=obs_space_dims,
                                                      cem_terminal_value=cem_terminal_value, cem_reward_net=cem_reward_net,
-                                                     cem_policy_prior=cem_policy_prior)
+                                                     cem_policy_prior=cem_policy_prior, cem_terminal_q=cem_terminal_q)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
@@ -346,7 +354,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         self._act_prev = self._act_prefix = None              # device tensors [m,A] / [m,delay,A] float32, NaN = unknown (the actuator model)
         self._value_set = False                               # whether the engine holds a value net (cem_terminal_value): `set_terminal_value`
         self._reward_set = False                              # whether the engine holds a reward net (cem_reward_net): `set_reward_net`
-        self._policy_set = False                              # whether the engine holds a policy net (cem_policy_prior): `set_policy`
+        self._policy_set = False                              # whether the engine holds a policy net (cem_policy_prior, cem_terminal_q): `set_policy`
+        self._critics_set = False                             # whether the engine holds Q critics (cem_terminal_q): `set_critics`
 
         self.env_kind = resolve_env_kind(env)
         self.seed = int(seed)
@@ -606,6 +615,10 @@ class MLPEnsembleCEMDynamicsModel(object):
             raise RuntimeError("get_action: this model plans under cem_reward_net and has no reward net (call set_reward_net first)")
         if self._opt.policy_params is not None and not self._policy_set:
             raise RuntimeError("get_action: this model plans under cem_policy_prior and has no policy net (call set_policy first)")
+        if self._opt.critic_params is not None and not self._critics_set:
+            raise RuntimeError("get_action: this model plans under cem_terminal_q and has no critics (call set_critics first)")
+        if self._opt.critic_params is not None and not self._policy_set:
+            raise RuntimeError("get_action: this model plans under cem_terminal_q and has no policy net (call set_policy first)")
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
@@ -806,11 +819,73 @@ class MLPEnsembleCEMDynamicsModel(object):
             res = {k: None if x is None else x[:, 0] for k, x in res.items()}
         return res
 
-    # ------------------------------------------------------------------ policy prior (INTEGRATION.md "Policy prior")
-    def _require_policy(self, who, need_net=False):
+    # ------------------------------------------------------------------ terminal value from Q critics (INTEGRATION.md "Terminal value from Q critics")
+    def _require_critics(self, who, need_nets=False, need_actor=False):
         opt = getattr(self, "_opt", None)
-        if opt is None or opt.policy_params is None:
-            raise ValueError("%s: this model has no cem_policy_prior" % who)
+        if opt is None or opt.critic_params is None:
+            raise ValueError("%s: this model has no cem_terminal_q" % who)
+        if need_nets and not self._critics_set:
+            raise RuntimeError("%s: this model has no critics (call set_critics first)" % who)
+        if need_actor and not self._policy_set:
+            raise RuntimeError("%s: this model has no policy net (call set_policy first)" % who)
+        return opt
+
+    def set_critics(self, nets, in_mean=None, in_std=None):
+        """The Q critics of `cem_terminal_q` from the next call on: `nets` a list of n_critics nets, each what `set_terminal_value` takes
+        (a list of (W [in,out], b [out]) per layer or a torch.nn.Sequential) with D + A inputs -- of the declared layer sizes and
+        activation, else it is refused; in_mean / in_std [D + A] (None: 0 / 1): every critic reads ([obs ; act] - in_mean) / in_std of
+        the raw observation and the actor's clipped action.  Everything is copied; replacing the critics rebuilds nothing."""
+        opt = self._require_critics("set_critics")
+        self.engine.set_critic_nets(opt.critic_params, nets, in_mean=in_mean, in_std=in_std)
+        self._critics_set = True
+
+    def clear_critics(self):
+        """Remove the critics: get_action on a model with `cem_terminal_q` then raises until `set_critics` is called."""
+        self._require_critics("clear_critics")
+        self.engine.set_critic_nets(None)
+        self._critics_set = False
+
+    def q_value(self, states, actions=None, return_each=False):
+        """The reduced Q of raw observations `states` [..., D] (numpy or tensor) through the planner's kernel -> numpy [...]: at the
+        policy net's action (actions None; `set_policy` first), or at `actions` [..., A].  NaN for a state (or action) with a non-finite
+        value.  return_each: (q, each [n_critics, ...]), every critic's own value."""
+        self._require_critics("q_value", need_nets=True, need_actor=actions is None)
+        out = self.engine.critic_eval(states, actions, want_each=return_each)
+        return (out[0].cpu().numpy(), out[1].cpu().numpy()) if return_each else out.cpu().numpy()
+
+    def plan_terminal_q(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
+        """What this model's terminal Q adds for `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) -- the companion of
+        `plan_terminal_value`: the context encoder, one rollout that records its trajectories and the fused actor / critics kernel, as
+        numpy arrays (for [m,H,A] input the n axis is dropped):
+          q [m,n,p]         reduce_c Q_c(s_H, pi(s_H)) of every particle's last state (NaN: a diverged particle, or one the constraints
+                            ended before the horizon); the planner adds weight * q to the particle's return
+          first [m,n,p]     with `cem_constraints` in terminate mode their first violations (a particle with first < H gets no q), else None
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        opt = self._require_critics("plan_terminal_q", need_nets=True, need_actor=True)
+        self._push_stats()
+        cp_obs, cp_act = self._rollout_inputs("plan_terminal_q", obs, actions, cp_obs, cp_act)
+        eng = self.engine
+        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        acts = (acts[:, None] if squeeze else acts).contiguous()
+        obs = eng._t(obs)
+        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        first = None
+        if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
+            _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
+        _, q = eng.critic_returns(traj, rows, opt.critic_params, first=first, want_q=True)
+        res = dict(q=q.cpu().numpy(), first=None if first is None else first.cpu().numpy())
+        if squeeze:
+            res = {k: None if x is None else x[:, 0] for k, x in res.items()}
+        return res
+
+    # ------------------------------------------------------------------ policy prior (INTEGRATION.md "Policy prior")
+    def _require_policy(self, who, need_net=False, prior_or_q=False):
+        opt = getattr(self, "_opt", None)
+        if opt is None or (opt.policy_params is None and not (prior_or_q and opt.critic_params is not None)):
+            raise ValueError("%s: this model has no cem_policy_prior%s" % (who, " and no cem_terminal_q" if prior_or_q else ""))
         if need_net and not self._policy_set:
             raise RuntimeError("%s: this model has no policy net (call set_policy first)" % who)
         return opt
@@ -820,20 +895,20 @@ class MLPEnsembleCEMDynamicsModel(object):
         b [out]) per layer or a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules, the last Linear with A outputs) -- of the
         declared layer sizes and activation, else it is refused; obs_mean / obs_std [D] (None: 0 / 1): the net reads (obs - obs_mean) /
         obs_std of the raw observation.  Everything is copied; replacing the net rebuilds nothing."""
-        opt = self._require_policy("set_policy")
-        self.engine.set_policy_net(opt.policy_params, weights, obs_mean=obs_mean, obs_std=obs_std)
+        opt = self._require_policy("set_policy", prior_or_q=True)      # (the actor of cem_terminal_q alone: registered with n_samples = 1)
+        self.engine.set_policy_net(opt.actor_params(), weights, obs_mean=obs_mean, obs_std=obs_std)
         self._policy_set = True
 
     def clear_policy(self):
         """Remove the policy net: get_action on a model with `cem_policy_prior` then raises until `set_policy` is called."""
-        self._require_policy("clear_policy")
+        self._require_policy("clear_policy", prior_or_q=True)
         self.engine.set_policy_net(None)
         self._policy_set = False
 
     def policy_action(self, states):
         """The policy's action of raw observations `states` [..., D] (numpy or tensor) through the planner's kernel -> numpy [..., A]:
         squashed and clipped to the action bounds, no noise; clip(0, lb, ub) for a state with a non-finite value."""
-        self._require_policy("policy_action", need_net=True)
+        self._require_policy("policy_action", need_net=True, prior_or_q=True)
         return self.engine.policy_eval(states).cpu().numpy()
 
     def policy_proposals(self, obs, cp_obs=None, cp_act=None, seed=None, return_states=False):

@@ -61,6 +61,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """The learned step rewards of `actions` under this model's `cem_reward_net` (see the CaDM class; a vanilla model has no history)."""
         return super().plan_rewards(obs, actions, None, None, seed=seed)
 
+    def plan_terminal_q(self, obs, actions, seed=None):
+        """What this model's `cem_terminal_q` adds for `actions` (see the CaDM class; a vanilla model has no history)."""
+        return super().plan_terminal_q(obs, actions, None, None, seed=seed)
+
     def policy_proposals(self, obs, seed=None, return_states=False):
         """The sequences this model's `cem_policy_prior` would inject for `obs` (see the CaDM class; a vanilla model has no history)."""
         return super().policy_proposals(obs, None, None, seed=seed, return_states=return_states)

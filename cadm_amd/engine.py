@@ -560,13 +560,13 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None):
+                   want_best_return, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None, crt=None):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
         `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
         workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop); act: the workspace of an actuated loop;
         unc: None, or the (terminate, actuator) of a loop with an uncertainty term, whose slot it is; val: None, or the (terminate, actuator,
         uncertainty) of a loop with a terminal value, whose slot it is; rew: likewise for a loop with a learned reward; pol: None, or the
-        (terminate, actuator, uncertainty, P) of a loop with a policy prior, whose slot it is."""
+        (terminate, actuator, uncertainty, P) of a loop with a policy prior, whose slot it is; crt: likewise for a loop with a terminal Q."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -575,7 +575,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val, rew=rew, pol=pol)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val, rew=rew, pol=pol, crt=crt)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -590,7 +590,11 @@ class HipEngine:
         `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
         Arguments as `icem_plan` behind its params.  First of all `rewarded_plan`, when it holds a learned reward, then `valued_plan`, when
         it holds a terminal value, then `uncertain_plan`, when it holds an uncertainty term.  Before all of them `guided_plan`, when it
-        holds a policy prior."""
+        holds a policy prior; and before that `critic_plan`, when it holds a terminal Q."""
+        if getattr(opt, "critic_params", None) is not None:
+            return self.critic_plan(opt.critic_params, opt.policy_params, opt.reward_params, opt.value_params, opt.uncertainty_params,
+                                    opt.actuator_params, act_prev, act_prefix, opt.action_advance, opt.track_params, targets, target_offset,
+                                    opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params, *args, **kw)
         if getattr(opt, "policy_params", None) is not None:
             return self.guided_plan(opt.policy_params, opt.reward_params, opt.value_params, opt.uncertainty_params, opt.actuator_params,
                                     act_prev, act_prefix, opt.action_advance, opt.track_params, targets, target_offset, opt.knot_params, phase,
@@ -621,7 +625,7 @@ class HipEngine:
             return self.scored_plan(opt.score_params, opt.params, *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
-    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None):
+    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None, crt=None):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
         constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that).  track: None,
         or whether a tracked loop runs under TERMINATE constraints -- the tracking slot (`cadm_tracking_workspace_bytes`: the trajectory
@@ -633,7 +637,8 @@ class HipEngine:
         None, or (terminate, actuator, uncertainty) -- the slot of a loop with a learned reward (`cadm_rewarded_workspace_bytes`: the
         valued loop's, and behind everything the step rewards).  pol: None, or (terminate, actuator, uncertainty, P) -- the slot of a loop
         with a policy prior (`cadm_guided_workspace_bytes`: the rewarded loop's, and behind everything the proposals and the roll's
-        workspace)."""
+        workspace).  crt: None, or (terminate, actuator, uncertainty, P) -- the slot of a loop with a terminal Q
+        (`cadm_critic_workspace_bytes`: the guided loop's; P = 0 without a policy prior in the same call)."""
         slot = (bool(mppi), bool(traj)) if track is None else (bool(mppi), "track", bool(track))
         if act:
             slot = slot + ("act",)
@@ -645,9 +650,14 @@ class HipEngine:
             slot = (bool(mppi), "rew", bool(rew[0]), bool(rew[1]), bool(rew[2]))
         if pol is not None:
             slot = (bool(mppi), "pol", bool(pol[0]), bool(pol[1]), bool(pol[2]), int(pol[3]))
+        if crt is not None:
+            slot = (bool(mppi), "crt", bool(crt[0]), bool(crt[1]), bool(crt[2]), int(crt[3]))
         key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            if pol is not None:
+            if crt is not None:
+                nbytes = self.lib.cadm_critic_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(crt[0])), int(bool(crt[1])),
+                                                              int(bool(crt[2])), int(crt[3]))
+            elif pol is not None:
                 nbytes = self.lib.cadm_guided_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(pol[0])), int(bool(pol[1])),
                                                               int(bool(pol[2])), int(pol[3]))
             elif rew is not None:
@@ -1613,6 +1623,161 @@ class HipEngine:
         return self._loop_plan("guided_plan", self.lib.cadm_guided_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act, init_mean,
                                init_var, n, carry, carry_valid, seed, call, out, want_best_return,
                                pol=(terminate, actuator is not None, uncertainty is not None, max(int(policy.n_samples), 0)))
+
+    # ------------------------------------------------------------------ terminal value from Q critics (opt-in; csrc/critic.hip)
+    @staticmethod
+    def critic_params(hidden_sizes=(), activation="relu", n_critics=2, reduce="min", weight=1.0):
+        """`cadm_critic_params`: hidden_sizes / activation -- as `value_params` (every critic is D + A -> h_1 -> .. -> h_L -> 1); n_critics
+        -- C in 1 .. `_lib.MAX_CRITICS`; reduce -- "min" or "mean" over the critics (or its CADM_CRITIC_* number); weight -- what the
+        reduced Q is multiplied by before it is added to a return, finite (it carries a discount gamma^H).  Needs no GPU."""
+        if isinstance(n_critics, bool) or not isinstance(n_critics, (int, np.integer)) or not 1 <= int(n_critics) <= _lib.MAX_CRITICS:
+            raise ValueError("critic n_critics must be an int in 1 .. %d, got %r" % (_lib.MAX_CRITICS, n_critics))
+        if isinstance(reduce, str) and reduce in _lib.CRITIC_REDUCES:
+            red = _lib.CRITIC_REDUCES[reduce]
+        elif not isinstance(reduce, (bool, str)) and isinstance(reduce, (int, np.integer)) and int(reduce) in _lib.CRITIC_REDUCES.values():
+            red = int(reduce)
+        else:
+            raise ValueError("critic reduce must be %s, got %r" % (" or ".join(repr(k) for k in _lib.CRITIC_REDUCES), reduce))
+        prm = _lib.CriticParams()
+        HipEngine._net_params(prm, "critic", hidden_sizes, activation, weight)
+        prm.n_critics, prm.reduce = int(n_critics), red
+        return prm
+
+    def set_critic_nets(self, params, nets=None, in_mean=None, in_std=None):
+        """`cadm_set_critic_nets`: registers the C = params.n_critics critics that `params` (`critic_params`) describes -- `nets` a list
+        of C nets, each as `value_weights` takes them with D + A inputs, the shared input statistics in_mean / in_std [D + A] over
+        [state ; action] as `set_value_net` takes them.  The library packs copies of its own, so a second call replaces the critics
+        without touching anything else.  params None: the critics are cleared."""
+        who, K = "set_critic_nets", self.D + self.A
+        if params is None:
+            self._check(self.lib.cadm_set_critic_nets(self._ctx, None, None, None, None, None, self.stream), "cadm_" + who)
+            self._critic_src, self._critic_n = None, 0
+            return
+        if isinstance(nets, torch.nn.Sequential) or nets is None:
+            raise ValueError("%s: nets must be a list of %d nets" % (who, params.n_critics))
+        nets = list(nets)
+        if len(nets) != params.n_critics:
+            raise ValueError("%s: %d nets given, %d critics declared" % (who, len(nets), params.n_critics))
+        dims = [K] + [int(params.hidden[l]) for l in range(params.n_hidden)] + [1]
+        dev = []
+        for c, net in enumerate(nets):
+            layers, act = self.value_weights(net)
+            if len(layers) != len(dims) - 1:
+                raise ValueError("%s: critic %d has %d layers, the declared net %r has %d" % (who, c, len(layers), dims, len(dims) - 1))
+            for l, (w, b) in enumerate(layers):
+                if w.shape != (dims[l], dims[l + 1]):
+                    raise ValueError("%s: layer %d of critic %d is %r, the declared net %r needs %r" % (who, l, c, w.shape, dims, (dims[l], dims[l + 1])))
+            if act is not None and _lib.VALUE_ACTS[act] != params.activation:
+                raise ValueError("%s: the activation %r of critic %d's module is not the declared one" % (who, act, c))
+            dev.extend((self._t(w), self._t(b)) for w, b in layers)
+        mean = np.zeros((K,), np.float64) if in_mean is None else np.asarray(self._host(in_mean), dtype=np.float64).reshape(-1)
+        std = np.ones((K,), np.float64) if in_std is None else np.asarray(self._host(in_std), dtype=np.float64).reshape(-1)
+        if mean.shape != (K,) or std.shape != (K,):
+            raise ValueError("%s: in_mean %r / in_std %r, expected [%d]" % (who, mean.shape, std.shape, K))
+        if not np.all(np.isfinite(mean)):
+            raise ValueError("%s: in_mean must be finite" % who)
+        if not np.all(np.isfinite(std) & (std > 0.0)):
+            raise ValueError("%s: in_std must be finite and > 0" % who)
+        mean_d, inv_d = self._t(mean.astype(np.float32)), self._t((1.0 / std).astype(np.float32))
+        nl = len(dev)
+        Wp, bp = (ct.c_void_p * nl)(*[w.data_ptr() for w, _ in dev]), (ct.c_void_p * nl)(*[b.data_ptr() for _, b in dev])
+        self._check(self.lib.cadm_set_critic_nets(self._ctx, ct.byref(params), Wp, bp, ptr(mean_d), ptr(inv_d), self.stream), "cadm_" + who)
+        self._critic_n = int(params.n_critics)
+        self._critic_src = (dev, mean_d, inv_d)      # alive until the next critics: the copy is enqueued, not done
+
+    def critic_eval(self, states, actions=None, want_each=False, want_actions=False):
+        """`cadm_critic_eval`: the reduced Q of states [..., D] -> [...] (device tensors) through the planner's kernel, at the registered
+        policy net's action (actions None) or at actions [..., A].  want_each: also every critic's q [C, ...]; want_actions: also the
+        action that was used [..., A].  Returns q, or the tuple (q[, each][, actions])."""
+        states = self._t(states)
+        if states.dim() < 1 or states.shape[-1] != self.D:
+            raise ValueError("critic_eval: states %r, expected [..., %d]" % (tuple(states.shape), self.D))
+        flat = states.reshape(-1, self.D).contiguous()
+        R = int(flat.shape[0])
+        if R < 1:
+            raise ValueError("critic_eval: no states")
+        aflat = None
+        if actions is not None:
+            actions = self._t(actions)
+            if tuple(actions.shape) != tuple(states.shape[:-1]) + (self.A,):
+                raise ValueError("critic_eval: actions %r, expected %r" % (tuple(actions.shape), tuple(states.shape[:-1]) + (self.A,)))
+            aflat = actions.reshape(-1, self.A).contiguous()
+        q = torch.empty((R,), dtype=torch.float32, device=self.device)
+        C = getattr(self, "_critic_n", 0) if want_each else 0      # (0: no critics registered, and the library says so)
+        each = torch.empty((C, R), dtype=torch.float32, device=self.device) if want_each else None
+        act = torch.empty((R, self.A), dtype=torch.float32, device=self.device) if want_actions else None
+        self._check(self.lib.cadm_critic_eval(self._ctx, ptr(flat), ptr(aflat), R, ptr(q), ptr(each), ptr(act), self.stream), "cadm_critic_eval")
+        lead = tuple(states.shape[:-1])
+        res = (q.reshape(lead),)
+        if want_each:
+            res += (each.reshape((C,) + lead),)
+        if want_actions:
+            res += (act.reshape(lead + (self.A,)),)
+        return res[0] if len(res) == 1 else res
+
+    def critic_returns(self, traj, rows, params, first=None, want_q=False, out=None):
+        """`cadm_critic_returns` on device tensors: traj [H,m,n,p,D] (a rollout's `traj_out`), rows [m,n,p] -> rows + weight * reduce_c
+        Q_c(s, pi(s)), s = traj[H-1], per row under `params` (`critic_params`, describing the registered critics).  first [m,n,p] int32
+        (None: every row): `constrain_returns`' first_violation -- a row with first < H keeps its bits.  want_q: (rows_out, q [m,n,p]),
+        q NaN where skipped.  out: where the new rows go (may be `rows` itself)."""
+        traj, rows = self._t(traj), self._t(rows)
+        if traj.dim() != 5 or not traj.is_contiguous():
+            raise ValueError("critic_returns: traj %r: expected contiguous [H,m,n,p,D]" % (tuple(traj.shape),))
+        H, m, n, p, D = traj.shape
+        if (H, p, D) != (self.H, self.p, self.D):
+            raise ValueError("critic_returns: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (tuple(traj.shape), self.H, self.p, self.D))
+        if tuple(rows.shape) != (m, n, p) or not rows.is_contiguous():
+            raise ValueError("critic_returns: rows %r, expected contiguous %r" % (tuple(rows.shape), (m, n, p)))
+        if first is not None:
+            first = self._t(first, dtype=torch.int32)
+            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
+                raise ValueError("critic_returns: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
+        if out is None:
+            out = torch.empty_like(rows)
+        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rows.device:
+            raise ValueError("critic_returns: out must be a contiguous float32 device tensor %r" % ((m, n, p),))
+        q = torch.empty((m, n, p), dtype=torch.float32, device=self.device) if want_q else None
+        self._check(self.lib.cadm_critic_returns(self._ctx, ct.byref(params), ptr(traj), ptr(first), m, n, ptr(rows), ptr(out), ptr(q),
+                                                 self.stream), "cadm_critic_returns")
+        return (out, q) if want_q else out
+
+    def critic_plan(self, critic, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase,
+                    constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0,
+                    out=None, want_best_return=False):
+        """`cadm_critic_plan`: the loop of `guided_plan` with `critic.weight` times the registered critics' reduced Q of every particle's
+        last state, at the registered policy net's action, added to the particle returns where the terminal value would be (`critic`: a
+        `critic_params` describing the critics of `set_critic_nets`; None = none, and `guided_plan`'s launches).  `policy` may be None
+        while a policy net is registered.  Arguments behind `critic` as `guided_plan`; the workspace is the slot of
+        `cadm_critic_workspace_bytes`, cached apart from the others."""
+        if critic is None:
+            return self.guided_plan(policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase,
+                                    constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=carry,
+                                    carry_valid=carry_valid, seed=seed, call=call, out=out, want_best_return=want_best_return)
+        mppi, params = self._as_mppi_params(params)
+        m = int(np.shape(obs)[0])
+        if actuator is None:
+            prev = prefix = None
+        else:
+            for name, t in (("prev", prev), ("prefix", prefix)):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+                    raise ValueError("critic_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
+            if prev is None or (prefix is None and actuator.delay > 0):
+                raise ValueError("critic_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
+            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "critic_plan")
+        phase = self._phase(phase, m, "critic_plan")
+        T = 0
+        if track is None:
+            targets = offset = None
+        else:
+            targets, T, offset = self._targets(targets, offset, m, track.n, "critic_plan")
+        by = lambda x: None if x is None else ct.byref(x)
+        head = (ct.byref(critic), by(policy), by(reward), by(value), by(uncertainty), by(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
+                by(track), ptr(targets), T, ptr(offset), by(knots), ptr(phase), by(constraints), by(score), int(mppi), ct.byref(params))
+        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
+        P = 0 if policy is None else max(int(policy.n_samples), 0)
+        return self._loop_plan("critic_plan", self.lib.cadm_critic_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act, init_mean,
+                               init_var, n, carry, carry_valid, seed, call, out, want_best_return,
+                               crt=(terminate, actuator is not None, uncertainty is not None, P))
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

@@ -12,7 +12,7 @@ What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
   * `PlanOptions`: what a model's `cem_*` kwargs mean -- their checks, the switches, and the ctypes structs `HipEngine.opt_in_plan` hands to the library;
-  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`; `actuator=`: `cadm_actuated_plan`; `uncertainty=`: `cadm_uncertain_plan`; `value=`: `cadm_valued_plan`; `reward=`: `cadm_rewarded_plan`; `policy=`: `cadm_guided_plan`) one launch at a time, for the same purposes;
+  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`; `actuator=`: `cadm_actuated_plan`; `uncertainty=`: `cadm_uncertain_plan`; `value=`: `cadm_valued_plan`; `reward=`: `cadm_rewarded_plan`; `policy=`: `cadm_guided_plan`; `critic=`: `cadm_critic_plan`) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
@@ -32,10 +32,10 @@ FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/p
 
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
                                                        "params score_params constraints constraint_params knots knot_params actuator actuator_params "
-                                                       "action_advance policy policy_params reward reward_params value value_params uncertainty uncertainty_params tracking "
-                                                       "track_params target_advance",
+                                                       "action_advance critic critic_params policy policy_params reward reward_params value value_params uncertainty "
+                                                       "uncertainty_params tracking track_params target_advance",
                                                        defaults=(None, None, None, None, True, None, None, None, None, None, None, None, None, None, None,
-                                                                 True))):
+                                                                 None, None, True))):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
     `score`: None, or (mode name, kappa, k).  `constraints`: None, or (the list of dict(dim=, lo=, hi=), mode name, weight), with
@@ -54,8 +54,22 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
     `reward`: None, or (inputs name, the tuple of hidden widths, activation name, weight), with `reward_params` the `RewardParams` built
     from it (None: no learned reward); the net is registered at run time too (`set_reward_net`).
     `policy`: None, or (the tuple of hidden widths, activation name, squash name, n_samples, noise_std), with `policy_params` the
-    `PolicyParams` built from it (None: no policy prior); the net is registered at run time too (`set_policy`)."""
+    `PolicyParams` built from it (None: no policy prior); the net is registered at run time too (`set_policy`).
+    `critic`: None, or (the tuple of hidden widths, activation name, n_critics, reduce name, weight, actor), with `critic_params` the
+    `CriticParams` built from it (None: no terminal Q); actor = (the tuple of hidden widths, activation name, squash name) of the policy
+    net the critics are evaluated at -- the policy prior's when one is declared (`actor_params` builds its `PolicyParams`); critics
+    and actor are registered at run time (`set_critics`, `set_policy`)."""
     __slots__ = ()
+
+    def actor_params(self):
+        """The `PolicyParams` a model registers its actor under: the policy prior's, or -- for a model whose only actor declaration is
+        `cem_terminal_q`'s `policy` -- one built from it with n_samples = 1 (the value is not used); None without either."""
+        if self.policy_params is not None:
+            return self.policy_params
+        if self.critic is None:
+            return None
+        hs, act, squash = self.critic[5]
+        return HipEngine.policy_params(hs, act, squash, 1, 0.0)
 
     @staticmethod
     def from_kwargs(cem_noise_beta=0.0, cem_keep_elites=0, cem_decay=1.0, cem_return="mean", cem_add_mean=False, cem_update="cem",
@@ -64,7 +78,7 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                     cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call", cem_tracking=None, cem_target_advance=True,
                     cem_action_delay=0, cem_action_rate_limit=None, cem_action_rate_cost=None, cem_action_advance=True, n_forwards=None,
                     action_dim=None, cem_uncertainty=None, obs_dim=None, cem_terminal_value=None, cem_reward_net=None,
-                    cem_policy_prior=None):
+                    cem_policy_prior=None, cem_terminal_q=None):
         """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
         everything that needs no engine -- and folded into a `PlanOptions`.  n_forwards / action_dim: the model's horizon and action
         dims, what `cem_action_delay` and the lengths of `cem_action_rate_limit` / `cem_action_rate_cost` are checked against (None: the
@@ -76,7 +90,11 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
         the shape of the reward net a model is given at run time; obs_dim / action_dim: what its input dims are checked against.
         cem_policy_prior: None, or dict(hidden_sizes=(..), activation=, squash="tanh" | "none", n_samples=24, noise_std=0.0)
         (`HipEngine.policy_params`): the shape of the policy net a model is given at run time and how many proposals it makes (whether
-        they fit the smallest iteration's candidates is the model's check, once it knows its engine's elites: `policy_min_candidates`)."""
+        they fit the smallest iteration's candidates is the model's check, once it knows its engine's elites: `policy_min_candidates`).
+        cem_terminal_q: None, or dict(hidden_sizes=(256, 256), activation="relu", n_critics=2, reduce="min" | "mean", weight=1.0,
+        policy=dict(hidden_sizes=, activation=, squash=)) (`HipEngine.critic_params`): the shape of the Q critics and of the actor they
+        are evaluated at; `policy` may be left out when cem_policy_prior is declared (the actor is then that net; given both, they must
+        agree); not together with cem_terminal_value: a plan has one terminal term."""
         act_off = (cem_action_rate_limit is None and cem_action_rate_cost is None and isinstance(cem_action_delay, (int, np.integer))
                    and not isinstance(cem_action_delay, bool) and int(cem_action_delay) == 0)
         if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
@@ -85,12 +103,12 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                 and (cem_knot_interp, cem_knot_anchor) == ("hold", "call") and isinstance(cem_knots, (int, np.integer)) \
                 and not isinstance(cem_knots, bool) and int(cem_knots) == 1 and cem_tracking is None and cem_target_advance is True \
                 and act_off and cem_action_advance is True and cem_uncertainty is None and cem_terminal_value is None \
-                and cem_reward_net is None and cem_policy_prior is None:
+                and cem_reward_net is None and cem_policy_prior is None and cem_terminal_q is None:
             return None
         if not use_cem:
             raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
                              "cem_score / cem_risk / cem_constraints / cem_knots / cem_tracking / cem_action_delay / cem_action_rate_limit / "
-                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net / cem_policy_prior configure the CEM planner: they need "
+                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net / cem_policy_prior / cem_terminal_q configure the CEM planner: they need "
                              "use_cem=True")
         value = vparams = None
         if cem_terminal_value is not None:
@@ -118,6 +136,40 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
             policy = (tuple(int(pparams.hidden[l]) for l in range(pparams.n_hidden)),
                       [k for k, x in _lib.VALUE_ACTS.items() if x == pparams.activation][0],
                       [k for k, x in _lib.POLICY_SQUASH.items() if x == pparams.squash][0], int(pparams.n_samples), float(pparams.noise_std))
+        critic = qparams = None
+        if cem_terminal_q is not None:
+            if not isinstance(cem_terminal_q, dict) or set(cem_terminal_q) - {"hidden_sizes", "activation", "n_critics", "reduce", "weight", "policy"}:
+                raise ValueError("cem_terminal_q must be dict(hidden_sizes=, activation=, n_critics=, reduce=, weight=, policy=), got %r"
+                                 % (cem_terminal_q,))
+            if cem_terminal_value is not None:
+                raise ValueError("cem_terminal_q and cem_terminal_value are both given: a plan has one terminal term")
+            if obs_dim is not None and not 1 <= int(obs_dim) <= _lib.MAX_VALUE_DIMS:
+                raise ValueError("Q critics read up to %d observation dims, got %r" % (_lib.MAX_VALUE_DIMS, obs_dim))
+            if action_dim is not None and not 1 <= int(action_dim) <= _lib.MAX_POLICY_ACTIONS:
+                raise ValueError("Q critics read up to %d action dims, got %r" % (_lib.MAX_POLICY_ACTIONS, action_dim))
+            c = dict(hidden_sizes=(256, 256), activation="relu", n_critics=2, reduce="min", weight=1.0, policy=None)
+            c.update(cem_terminal_q)
+            qparams = HipEngine.critic_params(c["hidden_sizes"], c["activation"], c["n_critics"], c["reduce"], c["weight"])
+            actor = None
+            if c["policy"] is not None:
+                if not isinstance(c["policy"], dict) or set(c["policy"]) - {"hidden_sizes", "activation", "squash"}:
+                    raise ValueError("cem_terminal_q: policy must be dict(hidden_sizes=, activation=, squash=), got %r" % (c["policy"],))
+                a = dict(hidden_sizes=(256, 256), activation="relu", squash="tanh")
+                a.update(c["policy"])
+                ap = HipEngine.policy_params(a["hidden_sizes"], a["activation"], a["squash"], 1, 0.0)
+                actor = (tuple(int(ap.hidden[l]) for l in range(ap.n_hidden)), [k for k, x in _lib.VALUE_ACTS.items() if x == ap.activation][0],
+                         [k for k, x in _lib.POLICY_SQUASH.items() if x == ap.squash][0])
+            if policy is not None:
+                if actor is not None and actor != policy[:3]:
+                    raise ValueError("cem_terminal_q: policy %r does not agree with cem_policy_prior's net %r (one actor: hidden_sizes, "
+                                     "activation and squash must be the same)" % (actor, policy[:3]))
+                actor = policy[:3]
+            if actor is None:
+                raise ValueError("cem_terminal_q needs policy=dict(hidden_sizes=, activation=, squash=), the actor the critics are evaluated at "
+                                 "(or a cem_policy_prior, whose net it then is)")
+            critic = (tuple(int(qparams.hidden[l]) for l in range(qparams.n_hidden)),
+                      [k for k, x in _lib.VALUE_ACTS.items() if x == qparams.activation][0], int(qparams.n_critics),
+                      [k for k, x in _lib.CRITIC_REDUCES.items() if x == qparams.reduce][0], float(qparams.weight), actor)
         reward = rparams = None
         if cem_reward_net is not None:
             if not isinstance(cem_reward_net, dict) or set(cem_reward_net) - {"inputs", "hidden_sizes", "activation", "weight"}:
@@ -234,7 +286,7 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                            knot_params=None if knots is None else HipEngine.knot_params(knots[0], knots[1]), tracking=tracking,
                            track_params=tparams, target_advance=bool(cem_target_advance), actuator=actuator, actuator_params=aparams,
                            action_advance=bool(cem_action_advance), uncertainty=uncertainty, uncertainty_params=uparams, value=value, value_params=vparams, reward=reward,
-                           reward_params=rparams, policy=policy, policy_params=pparams, **mppi, **icem)
+                           reward_params=rparams, policy=policy, policy_params=pparams, critic=critic, critic_params=qparams, **mppi, **icem)
 
 
 def policy_slot(keep_elites, last, add_mean_last):
@@ -375,7 +427,7 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
 def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
               add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False,
               update="cem", temperature=1.0, relative=False, score=None, constraints=None, knots=None, phase=None, tracking=None, actuator=None,
-              action_advance=False, uncertainty=None, value=None, reward=None, policy=None):
+              action_advance=False, uncertainty=None, value=None, reward=None, policy=None, critic=None):
     """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
     tests with injected draws and for diagnostics.  update="mppi": the loop of `cadm_mppi_plan` -- the elite ids come from an elite
     refit into copies of mean / var, the distribution from `mppi_refit`.  score: a `HipEngine.score_params` (`cadm_scored_plan`; None: the
@@ -407,7 +459,13 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     carries `reward_steps` [H,m,n_it,p] (NaN where not counted), `reward_sum` [m,n_it,p] and `reward_rows`, the rows before the addition.
     policy: a `HipEngine.policy_params` describing the engine's registered policy net (`cadm_guided_plan`; None: none) -- one
     `policy_propose` behind the context encoder, and in every iteration its sequences are injected at `policy_slot`, in front of the knot
-    shaping and the actuator pass; the third return value of `return_info` carries `proposals` [m,P,H,A]."""
+    shaping and the actuator pass; the third return value of `return_info` carries `proposals` [m,P,H,A].
+    critic: a `HipEngine.critic_params` describing the engine's registered critics (`cadm_critic_plan`; None: none; not with `value`) --
+    every rollout then records its trajectories and `critic_returns` adds weight * reduce_c Q_c(s, pi(s)) of the last state to the
+    particle rows behind the reward stage, before the score; `return_info` carries `q` [m,n_it,p] (NaN where skipped) and `q_rows`, the
+    rows before the addition."""
+    if critic is not None and value is not None:
+        raise ValueError("icem_plan: critic and value are both given: a plan has one terminal term")
     obs = engine._t(obs)
     mean, var = engine._t(init_mean).clone(), engine._t(init_var).clone()
     if knots is not None and knots.spacing == 1:
@@ -442,7 +500,7 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
         if actuator is not None:
             _, action_cost = engine.actuate_actions(actions, actuator[0], prev=actuator[1], prefix=actuator[2], want_cost=True)
         extra = {}
-        if constraints is None and tracking is None and uncertainty is None and value is None and reward is None:
+        if constraints is None and tracking is None and uncertainty is None and value is None and reward is None and critic is None:
             rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
         else:
             rows, traj = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it,
@@ -466,6 +524,10 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
                 unvalued = rows
                 rows, v = engine.value_returns(traj, unvalued, value, first=first, want_v=True)
                 extra.update(traj=traj, value=v, value_rows=unvalued)
+            if critic is not None:
+                q_rows = rows
+                rows, q = engine.critic_returns(traj, q_rows, critic, first=first, want_q=True)
+                extra.update(traj=traj, q=q, q_rows=q_rows)
         cand = engine.particle_mean(rows) if score is None else engine.particle_score(rows, score)
         if actuator is not None:
             extra.update(action_cost=action_cost, score=cand)

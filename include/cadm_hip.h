@@ -854,6 +854,74 @@ int cadm_guided_plan(cadm_ctx* ctx, const cadm_policy_params* policy, const cadm
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                      float* best_return_out, void* stream);
 
+/* Terminal value from Q critics (no reference twin, OPT-IN): for a learner that has an actor pi and critics Q_c(s, a) but no state-value
+ * net (LOOP on SAC / TD3: twin critics; TD-MPC: Q(z_H, pi(z_H)) behind every imagined trajectory), the terminal term
+ *   rows_out[q] = rows_in[q] + weight * reduce_c Q_c(s, pi(s)),   s = traj[H-1,q]
+ * on the LAST state of every particle, in ONE launch: actor, then critics, then the reduction.  It stands where cadm_value_returns'
+ * term stands and excludes it.  pi is the net of cadm_set_policy_net.  Each of the C = n_critics critics is an MLP
+ * D + A -> h_1 -> .. -> h_L -> 1 under the value net's conventions; all share one layer count, one set of widths, one activation and
+ * the input statistics, weights are per critic.  For one row, all in float32 (csrc/critic.hip, csrc/mlp_chain.h):
+ *   actor: exactly cadm_policy_eval of s -- x_k = (s_k - pmean_k) * pistd_k, the chain, the squash, no noise, the clip to [lb, ub]
+ *   critic input u = [s ; a], K = D + A:  x_k = (u_k - mean_k) * std_inv_k                      one subtract, one multiply
+ *   critic c, unit u of a layer:  acc = b[u];  for k = 0 .. K4-1 ascending:  acc = fmaf(W_c[k][u], x_k, acc)   (the value net's chain)
+ *   hidden: the activation;   output q_c: the sum itself
+ *   CADM_CRITIC_MIN:   r = q_0;  r = fminf(r, q_c) in ascending c
+ *   CADM_CRITIC_MEAN:  r = q_0;  r = r + q_c in ascending c;  for C > 1 then r = r / (float)C  (IEEE division)
+ *   rows_out = rows_in + weight * r:  one multiply, then one add, no fma.   weight carries a discount gamma^H.
+ * A row whose terminal state holds a non-finite value has r = NaN, set explicitly, and so a NaN return: the actor's fallback action is
+ * not what a Q is computed from.  With first [m,n,p] (cadm_constrain_returns' first_violation, TERMINATE mode) a row with first[q] < H
+ * keeps the bits of rows_in, its q_out is NaN, and its terminal state is not read.
+ * Determinism: a row's result is one column's chains in ascending k, behind one another in a fixed order, no floating-point atomics:
+ * the same bits run to run, in any batch, at any row position, for any m or n, from cadm_critic_eval as from the planner.
+ * cadm_set_critic_nets: W and b hold C * (L + 1) DEVICE pointers, critic-major (W[c * (L + 1) + l] [in,out] row-major, b[..] [out]);
+ * mean [D + A] and std_inv [D + A] are device pointers; everything is copied and packed into memory the ctx owns, on `stream`.  A second
+ * call replaces the critics (the same shapes allocate nothing); params NULL clears them; cadm_ctx_destroy frees them.  params->weight is
+ * not kept: every planner call brings its own weight and reduce; params->reduce is what cadm_critic_eval reduces with.
+ * cadm_critic_eval: states [R,D].  actions NULL: the registered policy net acts (required: CADM_ESTATE without one); actions [R,A]: the
+ * actor is skipped and the critics are evaluated at these (a non-finite action: NaN).  q_out [R]; q_each_out [C,R] or NULL: every
+ * critic's q_c; act_out [R,A] or NULL: the action that was used.
+ * cadm_critic_returns: traj [H,m,n,p,D] (a rollout's traj_out, n its packed candidate count), first [m,n,p] or NULL; q_out [m,n,p] or
+ * NULL: r of every row, NaN where cut or non-finite.  rows_out may alias rows_in.
+ * Refusals, before any HIP call: CADM_EINVAL for null pointers, n_hidden outside 0 .. 4, a width outside 1 .. 512, an unknown
+ * activation, n_critics outside 1 .. CADM_MAX_CRITICS, an unknown reduce, a weight that is not finite, D > CADM_MAX_VALUE_DIMS,
+ * A > CADM_MAX_POLICY_ACTIONS, a discrete ctx (cartpole), a candidate-sharded ctx, LDS at one row tile (the critics' input tile of 16
+ * rows x (D + A rounded up to 4), two regions of 16 rows x the widest layers of actor and critics, the output sums and the flags) beyond
+ * 160 KiB; no registered critics, or on the actor path no registered policy net: CADM_ESTATE; params that do not describe the
+ * registered critics (count, layers, widths, activation): CADM_EINVAL. */
+#define CADM_MAX_CRITICS 5
+#define CADM_CRITIC_MIN 0
+#define CADM_CRITIC_MEAN 1
+typedef struct cadm_critic_params {
+    int32_t n_hidden;                          /* L: 0 .. CADM_MAX_VALUE_LAYERS */
+    int32_t hidden[CADM_MAX_VALUE_LAYERS];     /* h_1 .. h_L, each 1 .. CADM_MAX_VALUE_WIDTH */
+    int32_t activation;                        /* CADM_VALUE_RELU | CADM_VALUE_TANH | CADM_VALUE_SWISH */
+    int32_t n_critics;                         /* C: 1 .. CADM_MAX_CRITICS */
+    int32_t reduce;                            /* CADM_CRITIC_MIN | CADM_CRITIC_MEAN */
+    float weight;                              /* finite */
+} cadm_critic_params;
+int cadm_set_critic_nets(cadm_ctx* ctx, const cadm_critic_params* params, const float* const* W, const float* const* b, const float* mean,
+                         const float* std_inv, void* stream);
+int cadm_critic_eval(cadm_ctx* ctx, const float* states, const float* actions, int R, float* q_out, float* q_each_out, float* act_out,
+                     void* stream);
+int cadm_critic_returns(cadm_ctx* ctx, const cadm_critic_params* params, const float* traj, const int32_t* first, int m, int n,
+                        const float* rows_in, float* rows_out, float* q_out, void* stream);
+/* The loop of cadm_guided_plan with that term in the particle returns: the outermost entry of the nest.  Per iteration the stage runs
+ * where the terminal value's runs: rollout -> constraints -> tracking -> the learned reward -> rows[q] += weight * r[q] on the particle
+ * rows [m,n_it,p] -> cadm_particle_score -> the costs off the candidate score -> the refit.  critic NULL: exactly the launches of
+ * cadm_guided_plan.  policy may be NULL while a policy net is registered: the term needs the registered net, not the proposals.
+ * Refusals: those of cadm_guided_plan and of cadm_critic_returns, and critic and value both non-NULL (CADM_EINVAL: a plan has one
+ * terminal term).  workspace: cadm_critic_workspace_bytes(ctx, m, n, K, mppi, terminate, actuator, uncertainty, P) -- that of
+ * cadm_guided_workspace_bytes: the term reads the trajectory view and takes none of its own. */
+size_t cadm_critic_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P);
+int cadm_critic_plan(cadm_ctx* ctx, const cadm_critic_params* critic, const cadm_policy_params* policy, const cadm_reward_params* params,
+                     const cadm_value_params* value, const cadm_uncertainty_params* uncertainty, const cadm_actuator_params* actuator,
+                     float* prev_io, float* prefix_io, int advance, const cadm_track_params* track, const float* targets, int T,
+                     const int32_t* offset, const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                     const cadm_score_params* score, int update, const cadm_mppi_params* mppi_params, const float* obs,
+                     const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                     int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                     float* best_return_out, void* stream);
+
 /* One training step =sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
