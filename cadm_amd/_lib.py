@@ -260,6 +260,9 @@ SIGNATURES = {
                               C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P,
                               C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P,
                               _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_set_discount": (_i, [_P, C.c_float, _P]),
+    "cadm_discount_weights": (_i, [_P, C.POINTER(C.c_float), C.POINTER(_i)]),
+    "cadm_discount_returns": (_i, [_P, _P, _P, _P, _i, _i, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

@@ -1,7 +1,8 @@
 // Actuator model of the opt-in planner loop (icem.hip; no reference twin, OPT-IN): what the device that executes a plan can do with it.
 //   * action delay: the plan's steps 0 .. d-1 were decided by earlier calls (a committed prefix, per env) and are facts;
 //   * rate limits: a step moves an action dim by at most delta_a from the step before, step 0 from the action applied last (prev, per env);
-//   * rate cost: sum_t w_a (u_t - u_{t-1})^2 comes off a candidate's score.
+//   * rate cost: sum_t w_a (u_t - u_{t-1})^2 comes off a candidate's score; on a ctx with a discount over the horizon (cadm_set_discount,
+//     discount.hip) sum_t disc[t] (w_a (u_t - u_{t-1})^2).
 // All three act on the candidate action sequences [m, n, H, A], not on trajectories: ONE kernel between the sampler (and the injections
 // and the knot shaping) and the rollout, and one subtraction behind the score.  The rollout kernels are not touched.  The semantics are
 // restated in include/cadm_hip.h (cadm_actuate_actions).
@@ -24,6 +25,7 @@ struct ActArgs {
     const float* prev;         // [m, A], or null: unknown (NaN) everywhere
     const float* prefix;       // [m, d, A], or null: nothing committed
     float* cost;               // [m, n], or null
+    const float* disc;         // [H + 1] the ctx's discount table (DISC kernel only)
     size_t cands;              // m * n
     int n, H, A, cpb;          // cpb: candidates per workgroup
     float lb, ub;
@@ -36,6 +38,8 @@ __device__ __forceinline__ float act_clip(float x, float lo, float hi) {
     return v > hi ? hi : v;
 }
 
+// DISC: the ctx's discount over the horizon (discount.hip): c_a = c_a + disc[t] * (w_a (y - last)^2).  false: the kernel as it was
+template <bool DISC>
 __global__ __launch_bounds__(ACT_THREADS) void actuate_kernel(const ActArgs a) {
     __shared__ float sc[ACT_THREADS];
     const int tid = threadIdx.x, A = a.A;
@@ -66,7 +70,7 @@ __global__ __launch_bounds__(ACT_THREADS) void actuate_kernel(const ActArgs a) {
             if (known) {
                 const float e = y - last;
                 const float sq = e * e;
-                cost = cost + w * sq;
+                cost = DISC ? __fadd_rn(cost, __fmul_rn(a.disc[t], __fmul_rn(w, sq))) : cost + w * sq;
             }
             u[(size_t)t * A] = y;
             last = y;
@@ -128,7 +132,9 @@ int cadm_launch_actuate(cadm_ctx* ctx, const cadm_actuator_params* prm, const fl
     a.c = *prm;
     const size_t blocks = (a.cands + a.cpb - 1) / a.cpb;
     CADM_REQUIRE(blocks <= 0x7fffffffull, "actuate: %zu candidates are too many for one launch", a.cands);
-    hipLaunchKernelGGL(actuate_kernel, dim3((unsigned)blocks), dim3(ACT_THREADS), 0, s, a);
+    a.disc = cost_out ? ctx->disc : nullptr;      // (without a cost the discount has nothing to weigh: pins, limits and sequences are untouched)
+    if (a.disc) hipLaunchKernelGGL(actuate_kernel<true>, dim3((unsigned)blocks), dim3(ACT_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(actuate_kernel<false>, dim3((unsigned)blocks), dim3(ACT_THREADS), 0, s, a);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;
 }

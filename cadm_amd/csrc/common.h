@@ -27,7 +27,7 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_HID_LIST 200              // the reference default --hidden_size (run_cadm_pets.py:129)
 #endif
 // bumped whenever cadm_ctx / RolloutArgs change: a side module built against another layout is refused
-#define CADM_CTX_LAYOUT_TAG 3010
+#define CADM_CTX_LAYOUT_TAG 3011
 
 #define CADM_CHECK_HIP(expr)                                                                   \
     do {                                                                                       \
@@ -180,6 +180,11 @@ struct cadm_ctx {
     PolicyNet* policy = nullptr;
     // the registered Q critics (cadm_set_critic_nets, critic.hip): likewise
     CriticNets* critic = nullptr;
+    // the discount over the horizon (cadm_set_discount, discount.hip): disc[0 .. H] on the device, null = none (gamma == 1); the host
+    // copy holds the same floats; disc_buf is the allocation, kept while the discount is cleared
+    float* disc = nullptr;
+    float* disc_buf = nullptr;
+    std::vector<float> disc_host;
 };
 
 // Entry points launch on the ctx's device whatever device the caller's thread has current (two engines on different GPUs in
@@ -214,6 +219,7 @@ void cadm_value_free(cadm_ctx* ctx);      // value.hip
 void cadm_reward_free(cadm_ctx* ctx);     // reward.hip
 void cadm_policy_free(cadm_ctx* ctx);     // policy.hip
 void cadm_critic_free(cadm_ctx* ctx);     // critic.hip
+void cadm_discount_free(cadm_ctx* ctx);   // discount.hip
 // (developer library: dev/dev_api.hip) Adam moment buffers of one trained tensor; layer as in cadm_set_weights, is_bias 0 / 1;
 // layer == -1 / -2: max_logvar / min_logvar of the forward net.  Returns null pointers before cadm_train_configure, and CADM_EINVAL
 // for a net id that is not one of CADM_NET_FF / BACK / CTX or a layer the net does not have.

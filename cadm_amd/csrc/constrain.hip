@@ -15,6 +15,9 @@
 //                      (pre-step state, post-step state, raw action), added in step order from r_0; the step that leaves still pays;
 //                      nothing the trajectory holds after tau reaches the return
 // A row without a violation keeps its input bits in both modes.
+// On a ctx with a discount over the horizon (cadm_set_discount, discount.hip; disc[t] its table):
+//     PENALTY          pen = pen + disc[t] on the violating steps, ascending t from 0.0f;  rows' = rows - w * pen; the counters are unchanged
+//     TERMINATE        sum = disc[0] r_0, sum = sum + disc[t] r_t up to tau;  rows' = sum - w * disc[tau]: the penalty is paid at the step that leaves
 //
 // Mapping and traffic: a workgroup owns CN_ROWS consecutive rows, one thread per row; its CN_THREADS threads (four waves) all load.
 // For a fixed step those rows' D values are ONE contiguous span of `traj`, loaded lane-linear into an LDS tile (16-byte loads where the
@@ -37,6 +40,7 @@ constexpr int CN_LDS_BUDGET = 48 * 1024;     // two tiles of CN_ROWS * D floats,
 
 struct ConstrainArgs {
     const float *traj, *obs, *actions, *rows_in;
+    const float* disc;         // [H + 1] the ctx's discount table (DISC kernels only)
     float* rows_out;
     int32_t *first, *viol;
     size_t total;              // m * n * p rows
@@ -46,7 +50,8 @@ struct ConstrainArgs {
     ForecastSpec spec;
 };
 
-template <int ENV>
+// DISC: the ctx's discount over the horizon (discount.hip).  false: the undiscounted kernel, instruction for instruction what it was
+template <int ENV, bool DISC>
 __global__ __launch_bounds__(CN_THREADS) void constrain_returns_kernel(const ConstrainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float cn_smem[];
     const int D = a.D, H = a.H, ts = (CN_ROWS * D + 3) & ~3, tid = threadIdx.x;
@@ -64,7 +69,7 @@ __global__ __launch_bounds__(CN_THREADS) void constrain_returns_kernel(const Con
     }
     const float* act = a.term && mine ? a.actions + (q / (size_t)a.p) * H * a.A : nullptr;      // the row's sequence: [H, A]
     int count = 0, first = H;
-    float sum = 0.0f;
+    float sum = 0.0f, pen = 0.0f, dfirst = 0.0f;      // (DISC: the discounted count; disc[first])
     for (int t = 0; t < H; ++t) {
         float* cur = cn_smem + (a.term ? (t & 1) * ts : 0);
         const float* pre = cn_smem + ((t & 1) ^ 1) * ts;
@@ -82,10 +87,19 @@ __global__ __launch_bounds__(CN_THREADS) void constrain_returns_kernel(const Con
             }
             if (a.term && first == H) {          // still alive before this step: it pays, also when it leaves
                 const float r = step_reward<ENV>(a.spec, D, a.A, pre + tid * D, x, act + (size_t)t * a.A);
-                sum = t == 0 ? r : sum + r;
+                if constexpr (DISC) {
+                    const float dr = __fmul_rn(a.disc[t], r);    // (one product, then one add: never an fma)
+                    sum = t == 0 ? dr : __fadd_rn(sum, dr);
+                } else {
+                    sum = t == 0 ? r : sum + r;
+                }
             }
             if (bad) {
                 ++count;
+                if constexpr (DISC) {
+                    pen = __fadd_rn(pen, a.disc[t]);
+                    if (first == H) dfirst = a.disc[t];
+                }
                 if (first == H) first = t;
             }
         }
@@ -100,9 +114,14 @@ __global__ __launch_bounds__(CN_THREADS) void constrain_returns_kernel(const Con
     const float r_in = a.rows_in[q];
     float r_out = r_in;
     if (a.term) {
-        if (first < H) r_out = sum - a.c.weight;
+        if constexpr (DISC) {
+            if (first < H) r_out = __fsub_rn(sum, __fmul_rn(a.c.weight, dfirst));      // the penalty is paid at the step that leaves
+        } else {
+            if (first < H) r_out = sum - a.c.weight;
+        }
     } else if (count > 0) {
-        r_out = r_in - a.c.weight * (float)count;
+        if constexpr (DISC) r_out = __fsub_rn(r_in, __fmul_rn(a.c.weight, pen));
+        else r_out = r_in - a.c.weight * (float)count;
     }
     a.rows_out[q] = r_out;
     if (a.first) a.first[q] = first;
@@ -113,7 +132,8 @@ size_t constrain_lds_bytes(int D, int term) { return (size_t)(term ? 2 : 1) * ((
 
 template <int ENV>
 int constrain_launch(const ConstrainArgs& a, size_t blocks, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL(constrain_returns_kernel<ENV>, dim3((unsigned)blocks), dim3(CN_THREADS), lds, s, a);
+    if (a.disc) hipLaunchKernelGGL((constrain_returns_kernel<ENV, true>), dim3((unsigned)blocks), dim3(CN_THREADS), lds, s, a);
+    else hipLaunchKernelGGL((constrain_returns_kernel<ENV, false>), dim3((unsigned)blocks), dim3(CN_THREADS), lds, s, a);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;
 }
@@ -160,7 +180,7 @@ extern "C" int cadm_constrain_returns(cadm_ctx* ctx, const cadm_constraint_param
     CADM_ON_DEVICE(ctx);
     ConstrainArgs a{};
     a.traj = traj; a.obs = obs; a.actions = actions; a.rows_in = rows_in; a.rows_out = rows_out;
-    a.first = first_violation_out; a.viol = violations_out;
+    a.first = first_violation_out; a.viol = violations_out; a.disc = ctx->disc;
     a.total = total; a.np = n * ctx->p; a.H = ctx->H; a.p = ctx->p; a.D = ctx->D; a.A = ctx->A; a.term = term;
     a.c = *prm;
     if (term) forecast_spec_fill(ctx, &a.spec);

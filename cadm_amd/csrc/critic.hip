@@ -12,7 +12,8 @@
 //     swish;  a linear output q_c
 //   CADM_CRITIC_MIN:  r = q_0;  r = fminf(r, q_c) in ascending c
 //   CADM_CRITIC_MEAN: r = q_0;  r = r + q_c in ascending c;  for C > 1 then r = r / (float)C (IEEE)
-//   rows' = rows + weight * r: one multiply, then one add.
+//   rows' = rows + weight * r: one multiply, then one add.  On a ctx with a discount over the horizon (cadm_set_discount, discount.hip)
+//   the launcher passes weight * disc[H], one fp32 product on the host; the kernel is the same.
 // A row whose terminal state (or, with given actions, whose action) holds a non-finite value gets r = NaN explicitly and so a NaN return:
 // the actor's fallback action clip(0, lb, ub) is what act_out reads for it, never what a Q is computed from.  With `first` (the
 // constraint kernel's first_violation) a row with first < H keeps its input bits, reads NaN in the outputs, and its state is not loaded.
@@ -303,7 +304,7 @@ static int critic_launch(cadm_ctx* ctx, int reduce, float weight, const float* x
 int cadm_launch_critic(cadm_ctx* ctx, const cadm_critic_params* p, const float* traj, const int32_t* first, int m, int n, float* rows,
                        hipStream_t s) {
     const size_t total = (size_t)m * n * ctx->p;
-    return critic_launch(ctx, p->reduce, p->weight, traj + (size_t)(ctx->H - 1) * total * ctx->D, nullptr, first, total, rows, rows, nullptr,
+    return critic_launch(ctx, p->reduce, cadm_discounted_weight(ctx, p->weight), traj + (size_t)(ctx->H - 1) * total * ctx->D, nullptr, first, total, rows, rows, nullptr,
                          nullptr, nullptr, s, "cadm_critic_plan");
 }
 
@@ -356,6 +357,6 @@ extern "C" int cadm_critic_returns(cadm_ctx* ctx, const cadm_critic_params* para
     CADM_REQUIRE(m >= 1 && n >= 1, "cadm_critic_returns: m, n must be >= 1 (got m=%d n=%d)", m, n);
     CADM_ON_DEVICE(ctx);
     const size_t total = (size_t)m * n * ctx->p;
-    return critic_launch(ctx, params->reduce, params->weight, traj + (size_t)(ctx->H - 1) * total * ctx->D, nullptr, first, total, rows_in,
+    return critic_launch(ctx, params->reduce, cadm_discounted_weight(ctx, params->weight), traj + (size_t)(ctx->H - 1) * total * ctx->D, nullptr, first, total, rows_in,
                          rows_out, q_out, nullptr, nullptr, (hipStream_t)stream, "cadm_critic_returns");
 }

@@ -348,14 +348,18 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
     return c.off;
 }
 
+// On a ctx with a discount over the horizon (cadm_set_discount, discount.hip) the loop always records trajectories: every size below is
+// then the one with the trajectory view.  The discount is set BEFORE the workspace is sized.
+static int icem_discounted(const cadm_ctx* ctx) { return ctx->disc != nullptr; }
+
 extern "C" size_t cadm_icem_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) {
     if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, 0, nullptr, nullptr);
+    return icem_carve(ctx, m, n, K, 0, nullptr, nullptr, icem_discounted(ctx));
 }
 
 extern "C" size_t cadm_mppi_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) {
     if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, 1, nullptr, nullptr);
+    return icem_carve(ctx, m, n, K, 1, nullptr, nullptr, icem_discounted(ctx));
 }
 
 extern "C" size_t cadm_constrained_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi) {
@@ -370,7 +374,7 @@ extern "C" size_t cadm_tracking_workspace_bytes(cadm_ctx* ctx, int m, int n, int
 
 extern "C" size_t cadm_actuated_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int traj, int terminate) {
     if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, traj != 0, traj != 0 && terminate != 0, 1);
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, traj != 0 || icem_discounted(ctx), traj != 0 && terminate != 0, 1);
 }
 
 extern "C" size_t cadm_uncertain_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator) {
@@ -429,6 +433,9 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
 // reward: a learned step reward (reward.hip) of the net registered with cadm_set_reward_net; null = none, and today's launches.  With it
 // every rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * (the sum of R over the
 // counted steps) is added to the particle rows behind the constraints and the tracking terms and IN FRONT OF the terminal value.
+// The ctx's discount over the horizon (cadm_set_discount, discount.hip) is not a parameter: with a table set every rollout records its
+// trajectories, the env's own return is rewritten as sum_t disc[t] r_t directly behind the rollout (cadm_launch_discount), and every stage
+// below weighs its steps by the same table; a terminal term's weight is multiplied by disc[H].  No table: today's launches.
 // policy: a policy prior (policy.hip) of the net registered with cadm_set_policy_net; null = none, and today's launches.  With it ONE
 // proposal roll behind the context encoder, and in every iteration its P sequences take the slots behind the kept elites and the mean
 // candidate, in front of the knot shaping and the actuator pass.
@@ -476,6 +483,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         CADM_REQUIRE(!value, "%s: a terminal Q and a terminal value are both given: a plan has one terminal term", who);
         if ((rc = cadm_critic_plan_check(ctx, critic, who))) return rc;
     }
+    const bool disc = ctx->disc != nullptr;
+    if (disc && (rc = cadm_discount_check(ctx, who))) return rc;
     const int P = policy ? policy->n_samples : 0;
     if (policy) {
         if ((rc = cadm_policy_plan_check(ctx, policy, who))) return rc;
@@ -488,10 +497,10 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    // (w.traj: null without constraints, terms, an uncertainty term, a value, a reward and a critic; w.first: null unless terms, an
+    // (w.traj: null without constraints, terms, an uncertainty term, a value, a reward, a critic and a discount; w.first: null unless terms, an
     // uncertainty term, a value, a reward or a critic follow TERMINATE constraints)
     const bool reads_traj = terms != nullptr || unc != nullptr || value != nullptr || reward != nullptr || critic != nullptr;
-    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || reads_traj,
+    icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || reads_traj || disc,
                reads_traj && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr, unc != nullptr,
                reward != nullptr, P);
     const int HA = ctx->H * ctx->A;
@@ -534,6 +543,9 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if (act && (rc = cadm_launch_actuate(ctx, act, prev_io, prefix_io, m, ni, w.actions, w.acost, s))) return rc;
         if ((rc = cadm_rollout_returns(ctx, obs, nullptr, ctx->C > 0 ? w.ctxv : nullptr, w.actions, nullptr, 1, seed, call, it, 0, ni, m, ni,
                                        w.rows, w.traj, stream))) return rc;
+        // a discount over the horizon: the rollout's undiscounted sums are replaced by sum_t disc[t] r_t from the trajectories, in front of
+        // everything that rewrites the rows; the stages below read the ctx's table themselves
+        if (disc && (rc = cadm_launch_discount(ctx, w.traj, obs, w.actions, m, ni, w.rows, w.rows, nullptr, s))) return rc;
         // the trajectories are [H, m, ni, p, D] of this iteration's ni candidates; the returns are rewritten in place
         if (constraints && (rc = cadm_constrain_returns(ctx, constraints, w.traj, obs, w.actions, w.rows, m, ni, w.rows, w.first, nullptr,
                                                         stream))) return rc;

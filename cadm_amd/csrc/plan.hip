@@ -61,6 +61,7 @@ static int cem_plan_impl(cadm_ctx* ctx, const float* obs, const float* cp_obs, c
                          uint32_t call, void* workspace, float* plan_out, void* stream, bool head_done, PlanDone done) {
     CADM_REQUIRE(ctx && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0,
                  "cadm_cem_plan: bad arguments");
+    if (int rd = cadm_refuse_discounted(ctx, "cadm_cem_plan")) return rd;
     CADM_ON_DEVICE(ctx);
     int rc = cem_plan_refuse(ctx, cp_obs && cp_act, n, "cadm_rollout_returns");      // (the call that has always reported an unready engine)
     if (rc) return rc;
@@ -149,6 +150,7 @@ extern "C" int cadm_cem_plan_staged(cadm_ctx* ctx, const float* host_block, floa
                                     void* stream) {
     CADM_REQUIRE(ctx && host_block && dev_block && off && nfloats > 0 && plan_out_host && workspace && m > 0 && n > 0,
                  "cadm_cem_plan_staged: bad arguments");
+    if (int rd = cadm_refuse_discounted(ctx, "cadm_cem_plan_staged")) return rd;
     CADM_ON_DEVICE(ctx);
     // refused before the fused head is enqueued (it carves the workspace and writes into it)
     CADM_REQUIRE(off[0] >= 0 && off[3] >= 0 && off[4] >= 0, "cadm_cem_plan_staged: obs / init_mean / init_var missing from the block");
@@ -210,6 +212,7 @@ extern "C" int cadm_rs_plan(cadm_ctx* ctx, const float* obs, const float* cp_obs
                             uint32_t seed, uint32_t call, void* workspace, float* action_out, int32_t* raw_best_out,
                             void* stream) {
     CADM_REQUIRE(ctx && obs && workspace && action_out && m > 0 && n > 0, "cadm_rs_plan: bad arguments");
+    if (int rd = cadm_refuse_discounted(ctx, "cadm_rs_plan")) return rd;
     CADM_ON_DEVICE(ctx);
     CADM_REQUIRE(ctx->C == 0 || (cp_obs && cp_act), "cadm_rs_plan: cp_obs/cp_act required for a context model");
     CADM_REQUIRE(!ctx->cfg.discrete || raw_best_out, "cadm_rs_plan: raw_best_out required for discrete actions");

@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, critic.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, critic.hip, discount.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -137,6 +137,22 @@ void cadm_policy_net_dims(const cadm_ctx* ctx, const cadm_policy_params* policy,
 int cadm_critic_plan_check(const cadm_ctx* ctx, const cadm_critic_params* critic, const char* who);
 int cadm_launch_critic(cadm_ctx* ctx, const cadm_critic_params* critic, const float* traj, const int32_t* first, int m, int n, float* rows,
                        hipStream_t s);
+// discount.hip: the refusals of a discount over the horizon (a discrete / sharded ctx, a D whose two tiles exceed the kernel's LDS, a spec
+// ctx without its spec: CADM_ESTATE), before any HIP call; and the launch behind a rollout's traj [H, m, n, p, D] (n the PACKED candidate
+// count) on a ctx whose table is set: rows_out[q] = sum_t disc[t] * r_t in ascending t (a NaN rows_in[q] stays), step_out [H, m, n, p] or
+// null takes the undiscounted r_t.  The other stages read ctx->disc themselves: null = their undiscounted launch.
+int cadm_discount_check(const cadm_ctx* ctx, const char* who);
+int cadm_launch_discount(cadm_ctx* ctx, const float* traj, const float* obs, const float* actions, int m, int n, const float* rows_in,
+                         float* rows_out, float* step_out, hipStream_t s);
+// what the reference-path loops (plan.hip) answer on a discounted ctx: they sum the step rewards inside the rollout kernel
+inline int cadm_refuse_discounted(const cadm_ctx* ctx, const char* who) {
+    if (!ctx->disc) return CADM_OK;
+    cadm_set_error("%s: a discount over the horizon is set (cadm_set_discount): this loop plans the undiscounted sum of the rollout kernel; "
+                   "use the opt-in loop, or clear the discount", who);
+    return CADM_ESTATE;
+}
+// value.hip, critic.hip: the weight of a terminal term on this ctx: weight * disc[H], one fp32 product on the host; without a discount the weight
+inline float cadm_discounted_weight(const cadm_ctx* ctx, float weight) { return ctx->disc ? weight * ctx->disc_host[(size_t)ctx->H] : weight; }
 
 // next start/stop event pair of a profiling list (grown on demand)
 inline int cadm_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, hipEvent_t* e0, hipEvent_t* e1) {

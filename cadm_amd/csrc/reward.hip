@@ -9,7 +9,7 @@
 // Arithmetic of one (t, q) (all fp32): x_k = (in_k - mean_k) * inv_std_k over the K concatenated dims, then the chain of mlp_chain.h --
 // the one value.hip runs.  A counted step whose input holds a non-finite value gets R = NaN explicitly.  With `first` (the constraint
 // kernel's first_violation) the counted steps are t <= first[q]; the others read NaN in r_step, are not summed, and their inputs are not
-// loaded.
+// loaded.  On a ctx with a discount over the horizon (cadm_set_discount, discount.hip): S = S + disc[t] * R_t; r_step stays undiscounted.
 //
 // Mapping.  reward_kernel: the (t, q) pairs are one flat row space e = t * (m n p) + q, the order of traj itself, and of r_step
 // [H, m, n, p].  A workgroup of 4 waves owns 16 * RT consecutive e (RT = 1 or 2), gathers their input tile [k][row] from the three
@@ -125,8 +125,10 @@ __global__ __launch_bounds__(MLP_THREADS) void reward_kernel(const RewardArgs a)
 }
 
 // S[q] = ((0 + r[0, q]) + r[1, q]) + .. over the counted steps t <= first[q] (all H without `first`), rows_out = rows_in + weight * S
+// DISC: the ctx's discount over the horizon (discount.hip): S = S + disc[t] * r[t, q].  false: the undiscounted kernel as it was
+template <bool DISC>
 __global__ void reward_sum_kernel(const float* __restrict__ r_step, const int32_t* __restrict__ first, int H, size_t total, float weight,
-                                  const float* rows_in, float* rows_out, float* __restrict__ sum_out) {
+                                  const float* rows_in, float* rows_out, float* __restrict__ sum_out, const float* __restrict__ disc) {
     const size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (q >= total) return;
     int last = H - 1;
@@ -138,7 +140,7 @@ __global__ void reward_sum_kernel(const float* __restrict__ r_step, const int32_
         for (int u = 0; u < 32; ++u) r[u] = t0 + u <= last ? r_step[(size_t)(t0 + u) * total + q] : 0.0f;
 #pragma unroll
         for (int u = 0; u < 32; ++u)
-            if (t0 + u <= last) S = __fadd_rn(S, r[u]);
+            if (t0 + u <= last) S = DISC ? __fadd_rn(S, __fmul_rn(disc[t0 + u], r[u])) : __fadd_rn(S, r[u]);
     }
     if (sum_out) sum_out[q] = S;
     rows_out[q] = __fadd_rn(rows_in[q], __fmul_rn(weight, S));   // (one multiply, then one add: never an fma)
@@ -252,8 +254,10 @@ static int reward_stage(cadm_ctx* ctx, float weight, const float* traj, const fl
     a.r_out = r_step;
     int rc;
     if ((rc = reward_launch(ctx, a, s, who))) return rc;
-    hipLaunchKernelGGL(reward_sum_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, s, r_step, first, ctx->H, a.total, weight, rows_in,
-                       rows_out, sum_out);
+    if (ctx->disc) hipLaunchKernelGGL(reward_sum_kernel<true>, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, s, r_step, first, ctx->H,
+                                      a.total, weight, rows_in, rows_out, sum_out, ctx->disc);
+    else hipLaunchKernelGGL(reward_sum_kernel<false>, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, s, r_step, first, ctx->H, a.total,
+                            weight, rows_in, rows_out, sum_out, nullptr);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;
 }

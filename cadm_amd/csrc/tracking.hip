@@ -10,6 +10,7 @@
 // A NaN target skips its (step, term); a row whose every (step, term) was skipped keeps its input bits.  With `first` (the constraint
 // kernel's first_violation) steps t > first[row] are not counted: the step that leaves the region still pays, nothing behind it does.
 // A non-finite value in a tracked dim at a counted step makes the row's return non-finite; other dims are not looked at.
+// On a ctx with a discount over the horizon (cadm_set_discount, discount.hip): cost += disc[t] * (w_k c), the same order, the same skips.
 //
 // Mapping and traffic: constrain.hip's PENALTY mapping.  A workgroup owns TR_ROWS consecutive rows, one thread per row; its TR_THREADS
 // threads (four waves) all load.  For a fixed step those rows' D values are ONE contiguous span of `traj`, loaded lane-linear into an
@@ -32,6 +33,7 @@ constexpr int TR_TARGET_FLOATS = TR_ROWS * CADM_MAX_TRACK_TERMS;      // up to T
 
 struct TrackArgs {
     const float *traj, *targets, *rows_in;
+    const float* disc;         // [H + 1] the ctx's discount table (DISC kernel only)
     const int32_t *offset, *first;
     float *rows_out, *cost_out;
     size_t total;              // m * n * p rows
@@ -40,6 +42,8 @@ struct TrackArgs {
     cadm_track_params c;
 };
 
+// DISC: the ctx's discount over the horizon (discount.hip): cost = cost + disc[t] * (w_k c).  false: the undiscounted kernel as it was
+template <bool DISC>
 __global__ __launch_bounds__(TR_THREADS) void tracking_returns_kernel(const TrackArgs a) {
     extern __shared__ __attribute__((aligned(16))) float tr_smem[];
     const int D = a.D, H = a.H, K = a.c.n, ts = (TR_ROWS * D + 3) & ~3, tid = threadIdx.x;
@@ -84,6 +88,7 @@ __global__ __launch_bounds__(TR_THREADS) void tracking_returns_kernel(const Trac
         __syncthreads();
         if (mine && t <= cut) {
             const float* x = tr_smem + tid * D;
+            const float dt = DISC ? a.disc[t] : 1.0f;
             // No branch on the data and nothing read under one: a term's parameters, its target and its value (all LDS reads) depend on
             // nothing the term before it computed, so the reads of several terms are in flight together.  With a branch per term and the
             // parameters read from the kernel arguments every term waited for five dependent loads in turn (measured: 106 us against
@@ -95,7 +100,7 @@ __global__ __launch_bounds__(TR_THREADS) void tracking_returns_kernel(const Trac
                 const float e = x[sdim[k]] - gk, ae = fabsf(e);
                 const float sq = e * e, hub = ae <= dl ? 0.5f * e * e : dl * (ae - 0.5f * dl);
                 const float c = kind == CADM_TRACK_SQUARE ? sq : kind == CADM_TRACK_ABS ? ae : hub;
-                const float next = cost + w * c;
+                const float next = DISC ? __fadd_rn(cost, __fmul_rn(dt, __fmul_rn(w, c))) : cost + w * c;
                 const bool use = gk == gk;               // NaN: no target for this term at this step
                 cost = use ? next : cost;
                 any = any || use;
@@ -158,7 +163,9 @@ extern "C" int cadm_tracking_returns(cadm_ctx* ctx, const cadm_track_params* tra
     a.traj = traj; a.targets = targets; a.rows_in = rows_in; a.offset = offset; a.first = first; a.rows_out = rows_out; a.cost_out = cost_out;
     a.total = total; a.np = n * ctx->p; a.H = ctx->H; a.D = ctx->D; a.T = T;
     a.c = *track;
-    hipLaunchKernelGGL(tracking_returns_kernel, dim3((unsigned)blocks), dim3(TR_THREADS), tracking_lds_bytes(ctx->D), (hipStream_t)stream, a);
+    a.disc = ctx->disc;
+    if (a.disc) hipLaunchKernelGGL(tracking_returns_kernel<true>, dim3((unsigned)blocks), dim3(TR_THREADS), tracking_lds_bytes(ctx->D), (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(tracking_returns_kernel<false>, dim3((unsigned)blocks), dim3(TR_THREADS), tracking_lds_bytes(ctx->D), (hipStream_t)stream, a);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;
 }

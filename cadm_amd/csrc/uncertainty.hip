@@ -8,7 +8,8 @@
 // Per candidate (mi, c), step t and dim d with w_d > 0, over x_j = traj[t, mi, c, j, d] (particle j belongs to member j / (p / E)):
 // the variance v by forecast_stats_kernel's chain, relative to particle 0;  u_t = sum_d w_d v[t, d] (ascending d, from the first
 // term), sqrtf of it (STD), the cap by a comparison;  cost = sum of u_t over the counted steps (all, or t <= min_j first[mi, c, j]) in
-// step order from 0;  in the loop cand' = cand - lambda cost.
+// step order from 0;  in the loop cand' = cand - lambda cost.  On a ctx with a discount over the horizon (cadm_set_discount, discount.hip)
+// cost = cost + disc[t] u_t, u_t taken behind the form and the cap, in both kernels that add; u [m, n, H] stays undiscounted.
 //
 // Mapping: the forecast kernel's (one workgroup per sequence, D busy threads, an H-long chain of loads) is the wrong one for every
 // candidate of an iteration.  Here a work item is (a group of G consecutive candidates, ONE step): the grid is ceil(m n / G) x H, and no
@@ -41,6 +42,7 @@ struct UncArgs {
     int H, p, E, PE, D, G;
     int kind, form;
     float cap;
+    const float* disc;         // [H + 1] the ctx's discount table, or null (the walking kernel only)
     float w[CADM_MAX_UNC_DIMS];      // [D], broadcast already
 };
 
@@ -60,7 +62,8 @@ __device__ __forceinline__ int unc_cut(const int32_t* first, size_t q, int p, in
 
 // WALK = false: blockIdx.y is the step, u goes to a.step.  WALK = true: the workgroup walks the steps, the candidate's thread adds the
 // counted ones and writes a.cost (a.step may be null).
-template <bool WALK>
+// DISC (with WALK only): the ctx's discount over the horizon (discount.hip): cost = cost + disc[t] * u_t.  false: the kernel as it was
+template <bool WALK, bool DISC = false>
 __global__ __launch_bounds__(UNC_THREADS) void uncertainty_steps_kernel(const UncArgs a) {
     extern __shared__ __attribute__((aligned(16))) float unc_smem[];
     const int D = a.D, p = a.p, E = a.E, PE = a.PE, H = a.H, pD = p * D, tid = threadIdx.x;
@@ -129,19 +132,20 @@ __global__ __launch_bounds__(UNC_THREADS) void uncertainty_steps_kernel(const Un
             if (a.form == CADM_UNC_STD) u = sqrtf(u);
             u = u > a.cap ? a.cap : u;      // (a comparison, not fminf: a NaN stays NaN)
             if (a.step) a.step[(c0 + tid) * H + t] = u;
-            if (WALK && t <= cut) cost = cost + u;
+            if (WALK && t <= cut) cost = DISC ? __fadd_rn(cost, __fmul_rn(a.disc[t], u)) : cost + u;
         }
     }
     if (WALK && mine) a.cost[c0 + tid] = cost;
 }
 
 // cost[q] = the counted steps of step[q, :] added in order from 0; cand (or null): cand[q] = cand[q] - lambda * cost[q]
+template <bool DISC>
 __global__ void uncertainty_apply_kernel(const float* __restrict__ step, const int32_t* __restrict__ first, size_t cands, int H, int p,
-                                         float lambda, float* __restrict__ cost_out, float* __restrict__ cand) {
+                                         float lambda, float* __restrict__ cost_out, float* __restrict__ cand, const float* __restrict__ disc) {
     for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < cands; q += (size_t)gridDim.x * blockDim.x) {
         const int cut = unc_cut(first, q, p, H);
         float cost = 0.0f;
-        for (int t = 0; t < H && t <= cut; ++t) cost = cost + step[q * H + t];
+        for (int t = 0; t < H && t <= cut; ++t) cost = DISC ? __fadd_rn(cost, __fmul_rn(disc[t], step[q * H + t])) : cost + step[q * H + t];
         cost_out[q] = cost;
         if (cand) {
             const float pen = lambda * cost;
@@ -208,8 +212,10 @@ int cadm_launch_uncertainty(cadm_ctx* ctx, const cadm_uncertainty_params* prm, c
                        unc_lds_bytes(a.G, ctx->p, ctx->D), s, a);
     CADM_CHECK_HIP(hipGetLastError());
     const size_t g = (a.cands + 255) / 256;
-    hipLaunchKernelGGL(uncertainty_apply_kernel, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, step, first, a.cands, ctx->H, ctx->p,
-                       prm->weight, cost, cand);
+    if (ctx->disc) hipLaunchKernelGGL(uncertainty_apply_kernel<true>, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, step, first, a.cands,
+                                      ctx->H, ctx->p, prm->weight, cost, cand, ctx->disc);
+    else hipLaunchKernelGGL(uncertainty_apply_kernel<false>, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, step, first, a.cands, ctx->H,
+                            ctx->p, prm->weight, cost, cand, nullptr);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;
 }
@@ -226,8 +232,11 @@ extern "C" int cadm_uncertainty_cost(cadm_ctx* ctx, const cadm_uncertainty_param
     unc_fill(ctx, params, traj, first, m, n, nullptr, cost_out, &a);
     const size_t blocks = (a.cands + a.G - 1) / a.G;
     CADM_REQUIRE(blocks <= 0x7fffffffull, "cadm_uncertainty_cost: %zu candidates are too many for one launch", a.cands);
-    hipLaunchKernelGGL(uncertainty_steps_kernel<true>, dim3((unsigned)blocks), dim3(UNC_THREADS), unc_lds_bytes(a.G, ctx->p, ctx->D),
-                       (hipStream_t)stream, a);
+    a.disc = ctx->disc;
+    if (a.disc) hipLaunchKernelGGL((uncertainty_steps_kernel<true, true>), dim3((unsigned)blocks), dim3(UNC_THREADS), unc_lds_bytes(a.G, ctx->p, ctx->D),
+                                   (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((uncertainty_steps_kernel<true, false>), dim3((unsigned)blocks), dim3(UNC_THREADS), unc_lds_bytes(a.G, ctx->p, ctx->D),
+                            (hipStream_t)stream, a);
     CADM_CHECK_HIP(hipGetLastError());
     return CADM_OK;
 }

@@ -11,7 +11,8 @@
 //   (v_mfma_f32_16x16x4_f32 adds its 4 products in ascending k onto the accumulator, as context.hip relies on; the bias SEEDS the
 //   accumulator; for K <= k < K4 both W and x are exact zeros)
 //   hidden: relu max(z, 0), tanhf(z), or swish z / (1 + expf(-z));  output: linear.
-//   rows' = rows + weight * V: one multiply, then one add.
+//   rows' = rows + weight * V: one multiply, then one add.  On a ctx with a discount over the horizon (cadm_set_discount, discount.hip)
+//   the launcher passes weight * disc[H], one fp32 product on the host; the kernel is the same.
 // A row whose terminal state holds a non-finite value gets V = NaN explicitly (relu would otherwise hide it) and so a NaN return.  With
 // `first` (the constraint kernel's first_violation) a row with first < H keeps its input bits, its V reads NaN, and its terminal
 // state is not loaded.
@@ -194,7 +195,7 @@ static int value_launch(cadm_ctx* ctx, float weight, const float* x, const int32
 int cadm_launch_value(cadm_ctx* ctx, const cadm_value_params* p, const float* traj, const int32_t* first, int m, int n, float* rows,
                       hipStream_t s) {
     const size_t total = (size_t)m * n * ctx->p;
-    return value_launch(ctx, p->weight, traj + (size_t)(ctx->H - 1) * total * ctx->D, first, total, rows, rows, nullptr, s, "cadm_valued_plan");
+    return value_launch(ctx, cadm_discounted_weight(ctx, p->weight), traj + (size_t)(ctx->H - 1) * total * ctx->D, first, total, rows, rows, nullptr, s, "cadm_valued_plan");
 }
 
 extern "C" int cadm_set_value_net(cadm_ctx* ctx, const cadm_value_params* params, const float* const* W, const float* const* b,
@@ -238,6 +239,6 @@ extern "C" int cadm_value_returns(cadm_ctx* ctx, const cadm_value_params* params
     CADM_REQUIRE(m >= 1 && n >= 1, "cadm_value_returns: m, n must be >= 1 (got m=%d n=%d)", m, n);
     CADM_ON_DEVICE(ctx);
     const size_t total = (size_t)m * n * ctx->p;
-    return value_launch(ctx, params->weight, traj + (size_t)(ctx->H - 1) * total * ctx->D, first, total, rows_in, rows_out, v_out,
+    return value_launch(ctx, cadm_discounted_weight(ctx, params->weight), traj + (size_t)(ctx->H - 1) * total * ctx->D, first, total, rows_in, rows_out, v_out,
                         (hipStream_t)stream, "cadm_value_returns");
 }

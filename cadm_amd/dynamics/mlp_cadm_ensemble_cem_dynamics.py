@@ -85,6 +85,11 @@ Differences a caller can see (all opt-in except the first):
     that net); `set_critics(nets, in_mean=None, in_std=None)` hands over the C critics (each as `set_terminal_value` takes a net, with
     D + A inputs) and `set_policy(...)` the actor, at run time and with nothing rebuilt; `clear_critics()`, `q_value(states,
     actions=None)`, `plan_terminal_q(obs, actions, ...)`.  Not together with `cem_terminal_value`.  It alone takes the opt-in route;
+  * `cem_discount=gamma` in (0, 1]: a discount over the horizon in that loop (INTEGRATION.md "Discount over the horizon") -- every
+    quantity that enters a candidate's score is weighted by gamma^t at step t: the env's own step rewards, the constraint penalty, the
+    tracking, uncertainty and rate costs and the learned reward, and a terminal value or Q by gamma^H on top of its `weight` (which
+    then no longer carries gamma ** n_forwards).  `plan_returns(obs, actions, ...)`: the discounted returns of given plans; the other
+    diagnostics report discounted figures too; `forecast` does not.  Any value other than 1.0 takes the opt-in route;
   * `forecast(obs, actions, ...)` and `get_action(..., return_forecast=True)`: the model's per-step predicted states, rewards and
     their spread under a plan (INTEGRATION.md "Forecasting a plan"); the default `return_forecast=False` is today's path, unchanged;
   * `predict(obs, act, cp_obs, cp_act)` -- thin alias the north-star asks for: one-step mean
@@ -270,6 +275,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_reward_net=None,
                  cem_policy_prior=None,
                  cem_terminal_q=None,
+                 cem_discount=1.0,
                  engine_lib=None,
                  ):
         self.env = env
@@ -339,7 +345,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      n_forwards=n_forwards, action_dim=None if self.discrete else self.action_space_dims,
                                                      cem_uncertainty=cem_uncertainty, obs_dim=obs_space_dims,
                                                      cem_terminal_value=cem_terminal_value, cem_reward_net=cem_reward_net,
-                                                     cem_policy_prior=cem_policy_prior, cem_terminal_q=cem_terminal_q)
+                                                     cem_policy_prior=cem_policy_prior, cem_terminal_q=cem_terminal_q,
+                                                     cem_discount=cem_discount)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
@@ -376,6 +383,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                                 lib=engine_lib)      # engine_lib: developer builds only (tools/ab.sh); None = the product library
         # tf.global_variables_initializer() equivalent (mb_trainer.py:164)
         self.engine.init_weights(np.random.default_rng(self.seed))
+        if self._opt is not None and self._opt.discount != 1.0:
+            self.engine.set_discount(self._opt.discount)      # state of the engine, set once: every stage and diagnostic reads it there
         self._train_ready = False
         self._stats_dirty = True
         self._dist_failed = False
@@ -436,7 +445,8 @@ class MLPEnsembleCEMDynamicsModel(object):
           cost [m,n]        their sum over the counted steps: what the planner multiplies by lambda and takes off the candidate score
           returns [m,n,p]   the rollout's particle returns: what lambda has to be weighed against
         If the model has `cem_constraints` in terminate mode their first violations cut the sum, as in the loop.  The noise is drawn as
-        `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.  On a model with
+        `cem_discount` the cost and the returns are the discounted ones; step stays undiscounted."""
         self._require_uncertainty("uncertainty_cost")
         self._push_stats()
         opt = self._opt
@@ -453,7 +463,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
             _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
         step, cost = eng.uncertainty_cost(traj, opt.uncertainty_params, first=first, want_steps=True)
-        res = dict(step=step.cpu().numpy(), cost=cost.cpu().numpy(), returns=rows.cpu().numpy())
+        res = dict(step=step.cpu().numpy(), cost=cost.cpu().numpy(), returns=self._env_rows(traj, obs, acts, rows).cpu().numpy())
         if squeeze:
             res = {k: v[:, 0] for k, v in res.items()}
         return res
@@ -687,7 +697,8 @@ class MLPEnsembleCEMDynamicsModel(object):
     def action_cost(self, actions):
         """What the actuator model makes of `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) under the current state and parameters, and
         what that costs -- the companion of `tracking_cost`: dict(cost [m,n], actions [m,n,H,A]) as numpy arrays (for [m,H,A] input the n
-        axis is dropped).  Moves no counter and no state; the caller's array is not written."""
+        axis is dropped).  Moves no counter and no state; the caller's array is not written.  On a model with `cem_discount` the cost is
+        the discounted one."""
         prm = self._require_actuator("action_cost")
         eng = self.engine
         acts = eng._t(actions)
@@ -740,7 +751,7 @@ class MLPEnsembleCEMDynamicsModel(object):
           returns [m,n,p]            the tracked particle returns (returns_untracked - cost), as the planner scores them without constraints
           returns_untracked [m,n,p]  the rollout's own returns: what `w` has to be weighed against
         The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; the planner's
-        call counter and the offsets do not move."""
+        call counter and the offsets do not move.  On a model with `cem_discount` the cost and both returns are the discounted ones."""
         if self._opt is None or self._opt.track_params is None:
             raise ValueError("tracking_cost: this model has no cem_tracking")
         if self._targets is None:
@@ -752,8 +763,10 @@ class MLPEnsembleCEMDynamicsModel(object):
         acts = eng._t(actions)
         squeeze = acts.dim() == 3
         acts = (acts[:, None] if squeeze else acts).contiguous()
-        raw, traj = eng.rollout_returns(eng._t(obs), ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+        obs = eng._t(obs)
+        raw, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        raw = self._env_rows(traj, obs, acts, raw)
         rows, cost = eng.tracking_returns(traj, raw, self._opt.track_params, self._targets, offset=self._target_offset, want_cost=True)
         res = dict(cost=cost.cpu().numpy(), returns=rows.cpu().numpy(), returns_untracked=raw.cpu().numpy())
         if squeeze:
@@ -798,7 +811,8 @@ class MLPEnsembleCEMDynamicsModel(object):
           value [m,n,p]     V of every particle's last state (NaN: a diverged particle, or one the constraints ended before the horizon);
                             the planner adds weight * value to the particle's return
           first [m,n,p]     with `cem_constraints` in terminate mode their first violations (a particle with first < H gets no value), else None
-        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.
+        On a model with `cem_discount` the planner adds weight * gamma^H * value (`plan_returns`' weights[H]); value itself is V."""
         opt = self._require_value("plan_terminal_value", need_net=True)
         self._push_stats()
         cp_obs, cp_act = self._rollout_inputs("plan_terminal_value", obs, actions, cp_obs, cp_act)
@@ -860,7 +874,8 @@ class MLPEnsembleCEMDynamicsModel(object):
           q [m,n,p]         reduce_c Q_c(s_H, pi(s_H)) of every particle's last state (NaN: a diverged particle, or one the constraints
                             ended before the horizon); the planner adds weight * q to the particle's return
           first [m,n,p]     with `cem_constraints` in terminate mode their first violations (a particle with first < H gets no q), else None
-        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.
+        On a model with `cem_discount` the planner adds weight * gamma^H * q (`plan_returns`' weights[H]); q itself is the reduced Q."""
         opt = self._require_critics("plan_terminal_q", need_nets=True, need_actor=True)
         self._push_stats()
         cp_obs, cp_act = self._rollout_inputs("plan_terminal_q", obs, actions, cp_obs, cp_act)
@@ -978,7 +993,8 @@ class MLPEnsembleCEMDynamicsModel(object):
           reward [m,n,p,H]  R of every step of every particle (NaN: a step with a non-finite input, or one behind a particle's first violation)
           total [m,n,p]     the sum over the counted steps in ascending t; the planner adds weight * total to the particle's return
           first [m,n,p]     with `cem_constraints` in terminate mode their first violations (steps t <= first count), else None
-        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.
+        On a model with `cem_discount` total is the discounted sum (gamma^t * R_t); reward stays undiscounted."""
         opt = self._require_reward("plan_rewards", need_net=True)
         self._push_stats()
         cp_obs, cp_act = self._rollout_inputs("plan_rewards", obs, actions, cp_obs, cp_act)
@@ -1010,6 +1026,44 @@ class MLPEnsembleCEMDynamicsModel(object):
         self._plan_opt_in(obs, cp_obs, cp_act, cem_init_mean, cem_init_var, out=host)
         torch.cuda.current_stream(self.engine.device).synchronize()
         return host.numpy().copy()
+
+    # ------------------------------------------------------------------ discount over the horizon (INTEGRATION.md "Discount over the horizon")
+    def _env_rows(self, traj, obs, acts, rows):
+        """The env's own particle returns as the planner scores them: on a model with `cem_discount` the rollout's undiscounted sums
+        are replaced by the discounted ones (`HipEngine.discount_returns`), as the loop does directly behind its rollout."""
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.discount == 1.0:
+            return rows
+        return self.engine.discount_returns(traj, obs, acts, rows)
+
+    def plan_returns(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
+        """The discounted env returns of `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) under this model's `cem_discount` -- the
+        companion of `plan_rewards` and `tracking_cost`: the context encoder, one rollout that records its trajectories and the discount
+        kernel, as numpy arrays (for [m,H,A] input the n axis is dropped):
+          returns [m,n,p]         sum_t weights[t] * step_rewards[..., t] in ascending t: what the planner scores in the place of the
+                                  rollout's undiscounted sum
+          step_rewards [m,n,H,p]  the undiscounted step rewards, from the recorded states
+          weights [H+1]           gamma^t, the floats the kernels read (weights[H]: what a terminal value or Q is multiplied by)
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves."""
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.discount == 1.0:
+            raise ValueError("plan_returns: this model has no cem_discount")
+        self._push_stats()
+        cp_obs, cp_act = self._rollout_inputs("plan_returns", obs, actions, cp_obs, cp_act)
+        eng = self.engine
+        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        acts = (acts[:, None] if squeeze else acts).contiguous()
+        obs = eng._t(obs)
+        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        out, steps = eng.discount_returns(traj, obs, acts, rows, want_steps=True)
+        res = dict(returns=out.cpu().numpy(), step_rewards=steps.permute(1, 2, 0, 3).cpu().numpy())
+        if squeeze:
+            res = {k: v[:, 0] for k, v in res.items()}
+        res["weights"] = eng.discount_weights()
+        return res
 
     # ------------------------------------------------------------------ forecast of a plan (INTEGRATION.md "Forecasting a plan")
     def _forecast_refuse(self, what):
@@ -1082,7 +1136,7 @@ class MLPEnsembleCEMDynamicsModel(object):
           violation_fraction [m,n]              the share of a sequence's particles with any violation
           returns [m,n,p]                       the constrained particle returns, as the planner would score them
         The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; the planner's
-        call counter does not move."""
+        call counter does not move.  On a model with `cem_discount` the returns and the penalty are the discounted ones."""
         if self._opt is None or self._opt.constraint_params is None:
             raise ValueError("constraint_check: this model has no cem_constraints")
         self._push_stats()
@@ -1095,7 +1149,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         obs = eng._t(obs)
         rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
                                          call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
-        rows, first, viol = eng.constrain_returns(traj, rows, self._opt.constraint_params, obs=obs, actions=acts)
+        rows, first, viol = eng.constrain_returns(traj, self._env_rows(traj, obs, acts, rows), self._opt.constraint_params, obs=obs, actions=acts)
         res = dict(first_violation=first.cpu().numpy(), violations=viol.cpu().numpy(), returns=rows.cpu().numpy())
         res["violation_fraction"] = (res["violations"] > 0).mean(axis=-1)
         if squeeze:

@@ -65,6 +65,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """What this model's `cem_terminal_q` adds for `actions` (see the CaDM class; a vanilla model has no history)."""
         return super().plan_terminal_q(obs, actions, None, None, seed=seed)
 
+    def plan_returns(self, obs, actions, seed=None):
+        """The discounted env returns of `actions` under this model's `cem_discount` (see the CaDM class; a vanilla model has no history)."""
+        return super().plan_returns(obs, actions, None, None, seed=seed)
+
     def policy_proposals(self, obs, seed=None, return_states=False):
         """The sequences this model's `cem_policy_prior` would inject for `obs` (see the CaDM class; a vanilla model has no history)."""
         return super().policy_proposals(obs, None, None, seed=seed, return_states=return_states)

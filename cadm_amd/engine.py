@@ -838,6 +838,49 @@ class HipEngine:
         return self._loop_plan("constrained_plan", self.lib.cadm_constrained_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None)
 
+    # ------------------------------------------------------------------ discount over the horizon (opt-in; csrc/discount.hip)
+    def set_discount(self, gamma):
+        """`cadm_set_discount`: gamma in (0, 1]; 1.0 clears the discount.  State of the engine, as the horizon is: from here on the opt-in
+        loop and every stand-alone stage call weigh step t by gamma^t (`discount_weights`), and `cem_plan` / `rs_plan` refuse.  The
+        loop records trajectories under a discount, so every cached loop workspace is dropped and sized again at the next plan."""
+        gamma = float(gamma)
+        if not (0.0 < gamma <= 1.0):      # (NaN: false)
+            raise ValueError("set_discount: the discount %r is not in (0, 1]" % (gamma,))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cadm_set_discount(self._ctx, gamma, self.stream), "cadm_set_discount")
+        self._loop_ws = {}
+
+    def discount_weights(self):
+        """`cadm_discount_weights`: the floats the kernels read, float32 [H + 1] (gamma^t, t = 0 .. H), or None while no discount is set."""
+        out = np.empty((self.H + 1,), np.float32)
+        is_set = ct.c_int(0)
+        self._check(self.lib.cadm_discount_weights(self._ctx, out.ctypes.data_as(ct.POINTER(ct.c_float)), ct.byref(is_set)),
+                    "cadm_discount_weights")
+        return out if is_set.value else None
+
+    def discount_returns(self, traj, obs, actions, rows, want_steps=False, out=None):
+        """`cadm_discount_returns` on device tensors: traj [H,m,n,p,D] (a rollout's `traj_out`), obs [m,D], actions [m,n,H,A] raw, rows
+        [m,n,p] (its returns: a NaN stays) -> the discounted env returns [m,n,p]; want_steps: also the undiscounted step rewards
+        [H,m,n,p].  out: where the returns go (may be `rows` itself).  Needs a discount (`set_discount`)."""
+        traj, obs, actions, rows = self._t(traj), self._t(obs), self._t(actions), self._t(rows)
+        if traj.dim() != 5 or rows.dim() != 3:
+            raise ValueError("discount_returns: traj %r, rows %r: expected [H,m,n,p,D] and [m,n,p]" % (tuple(traj.shape), tuple(rows.shape)))
+        H, m, n, p, D = traj.shape
+        if (H, p, D) != (self.H, self.p, self.D) or tuple(rows.shape) != (m, n, p):
+            raise ValueError("discount_returns: traj %r, rows %r do not agree with the engine (H=%d, p=%d, D=%d)"
+                             % (tuple(traj.shape), tuple(rows.shape), self.H, self.p, self.D))
+        if tuple(obs.shape) != (m, D) or tuple(actions.shape) != (m, n, H, self.A):
+            raise ValueError("discount_returns: obs %r, actions %r: expected [%d,%d] and [%d,%d,%d,%d]"
+                             % (tuple(obs.shape), tuple(actions.shape), m, D, m, n, H, self.A))
+        if out is None:
+            out = torch.empty_like(rows)
+        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("discount_returns: out %r, expected contiguous float32 %r" % (tuple(out.shape), (m, n, p)))
+        steps = torch.empty((H, m, n, p), dtype=torch.float32, device=self.device) if want_steps else None
+        self._check(self.lib.cadm_discount_returns(self._ctx, ptr(traj), ptr(obs), ptr(actions), m, n, ptr(rows), ptr(out), ptr(steps),
+                                                   self.stream), "cadm_discount_returns")
+        return (out, steps) if want_steps else out
+
     # ------------------------------------------------------------------ plans on knots (opt-in; csrc/knots.hip)
     @staticmethod
     def knot_params(spacing, interp="hold"):
@@ -1202,7 +1245,8 @@ class HipEngine:
         """`cadm_value_params`: hidden_sizes -- the widths h_1 .. h_L of the value net D -> h_1 -> .. -> h_L -> 1, L in 0 ..
         `_lib.MAX_VALUE_LAYERS` (() is a linear V), each in 1 .. `_lib.MAX_VALUE_WIDTH`; activation -- "relu", "tanh" or "swish" (or its
         CADM_VALUE_* number), one for the net; weight -- what V is multiplied by before it is added to a return, finite (it carries a
-        discount gamma^H).  Needs no GPU."""
+        discount gamma^H -- not on an
+        engine with `set_discount`: the library then multiplies gamma^H in).  Needs no GPU."""
         prm = _lib.ValueParams()
         HipEngine._net_params(prm, "value", hidden_sizes, activation, weight)
         return prm
@@ -1629,7 +1673,8 @@ class HipEngine:
     def critic_params(hidden_sizes=(), activation="relu", n_critics=2, reduce="min", weight=1.0):
         """`cadm_critic_params`: hidden_sizes / activation -- as `value_params` (every critic is D + A -> h_1 -> .. -> h_L -> 1); n_critics
         -- C in 1 .. `_lib.MAX_CRITICS`; reduce -- "min" or "mean" over the critics (or its CADM_CRITIC_* number); weight -- what the
-        reduced Q is multiplied by before it is added to a return, finite (it carries a discount gamma^H).  Needs no GPU."""
+        reduced Q is multiplied by before it is added to a return, finite (it carries a discount gamma^H -- not on an
+        engine with `set_discount`: the library then multiplies gamma^H in).  Needs no GPU."""
         if isinstance(n_critics, bool) or not isinstance(n_critics, (int, np.integer)) or not 1 <= int(n_critics) <= _lib.MAX_CRITICS:
             raise ValueError("critic n_critics must be an int in 1 .. %d, got %r" % (_lib.MAX_CRITICS, n_critics))
         if isinstance(reduce, str) and reduce in _lib.CRITIC_REDUCES:

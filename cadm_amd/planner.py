@@ -32,9 +32,9 @@ FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/p
 
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
                                                        "params score_params constraints constraint_params knots knot_params actuator actuator_params "
-                                                       "action_advance critic critic_params policy policy_params reward reward_params value value_params uncertainty "
+                                                       "action_advance discount critic critic_params policy policy_params reward reward_params value value_params uncertainty "
                                                        "uncertainty_params tracking track_params target_advance",
-                                                       defaults=(None, None, None, None, True, None, None, None, None, None, None, None, None, None, None,
+                                                       defaults=(None, None, None, None, True, 1.0, None, None, None, None, None, None, None, None, None, None,
                                                                  None, None, True))):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
@@ -58,7 +58,9 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
     `critic`: None, or (the tuple of hidden widths, activation name, n_critics, reduce name, weight, actor), with `critic_params` the
     `CriticParams` built from it (None: no terminal Q); actor = (the tuple of hidden widths, activation name, squash name) of the policy
     net the critics are evaluated at -- the policy prior's when one is declared (`actor_params` builds its `PolicyParams`); critics
-    and actor are registered at run time (`set_critics`, `set_policy`)."""
+    and actor are registered at run time (`set_critics`, `set_policy`).
+    `discount`: gamma in (0, 1], the discount over the horizon every term of a candidate's score is weighted by per step (1.0: none); a
+    model hands it to its engine once (`HipEngine.set_discount`), it is not a parameter of a plan call."""
     __slots__ = ()
 
     def actor_params(self):
@@ -78,7 +80,7 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                     cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call", cem_tracking=None, cem_target_advance=True,
                     cem_action_delay=0, cem_action_rate_limit=None, cem_action_rate_cost=None, cem_action_advance=True, n_forwards=None,
                     action_dim=None, cem_uncertainty=None, obs_dim=None, cem_terminal_value=None, cem_reward_net=None,
-                    cem_policy_prior=None, cem_terminal_q=None):
+                    cem_policy_prior=None, cem_terminal_q=None, cem_discount=1.0):
         """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
         everything that needs no engine -- and folded into a `PlanOptions`.  n_forwards / action_dim: the model's horizon and action
         dims, what `cem_action_delay` and the lengths of `cem_action_rate_limit` / `cem_action_rate_cost` are checked against (None: the
@@ -94,7 +96,15 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
         cem_terminal_q: None, or dict(hidden_sizes=(256, 256), activation="relu", n_critics=2, reduce="min" | "mean", weight=1.0,
         policy=dict(hidden_sizes=, activation=, squash=)) (`HipEngine.critic_params`): the shape of the Q critics and of the actor they
         are evaluated at; `policy` may be left out when cem_policy_prior is declared (the actor is then that net; given both, they must
-        agree); not together with cem_terminal_value: a plan has one terminal term."""
+        agree); not together with cem_terminal_value: a plan has one terminal term.  cem_discount: gamma in (0, 1], the discount over
+        the horizon (`HipEngine.set_discount`); 1.0: none.  With it the `weight` of cem_terminal_value / cem_terminal_q no longer carries
+        gamma ** n_forwards: the library multiplies it in."""
+        if isinstance(cem_discount, (bool, np.bool_)) or not isinstance(cem_discount, (int, float, np.integer, np.floating)) \
+                or not 0.0 < float(cem_discount) <= 1.0:      # (NaN: false)
+            raise ValueError("cem_discount must be a number in (0, 1] (1.0: no discount over the horizon), got %r" % (cem_discount,))
+        discount = float(np.float32(cem_discount))      # what the library is handed
+        if not 0.0 < discount <= 1.0:
+            raise ValueError("cem_discount must be a number in (0, 1] in float32, got %r" % (cem_discount,))
         act_off = (cem_action_rate_limit is None and cem_action_rate_cost is None and isinstance(cem_action_delay, (int, np.integer))
                    and not isinstance(cem_action_delay, bool) and int(cem_action_delay) == 0)
         if (float(cem_noise_beta), int(cem_keep_elites), float(cem_decay), cem_return, bool(cem_add_mean), cem_update, float(cem_temperature),
@@ -103,13 +113,22 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                 and (cem_knot_interp, cem_knot_anchor) == ("hold", "call") and isinstance(cem_knots, (int, np.integer)) \
                 and not isinstance(cem_knots, bool) and int(cem_knots) == 1 and cem_tracking is None and cem_target_advance is True \
                 and act_off and cem_action_advance is True and cem_uncertainty is None and cem_terminal_value is None \
-                and cem_reward_net is None and cem_policy_prior is None and cem_terminal_q is None:
+                and cem_reward_net is None and cem_policy_prior is None and cem_terminal_q is None and float(cem_discount) == 1.0:
             return None
         if not use_cem:
             raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
                              "cem_score / cem_risk / cem_constraints / cem_knots / cem_tracking / cem_action_delay / cem_action_rate_limit / "
-                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net / cem_policy_prior / cem_terminal_q configure the CEM planner: they need "
+                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net / cem_policy_prior / cem_terminal_q / cem_discount configure the CEM planner: they need "
                              "use_cem=True")
+        if float(cem_discount) != 1.0:
+            if discrete:
+                raise ValueError("cem_discount needs continuous actions: this env's action space is discrete (discrete actions are planned "
+                                 "by random shooting, which sums the step rewards undiscounted)")
+            if process_group is not None:
+                import torch.distributed as dist
+                if dist.get_world_size(process_group) > 1:
+                    raise ValueError("cem_discount is not supported on a process group of more than one rank: the candidate-sharded planner "
+                                     "sums the step rewards undiscounted")
         value = vparams = None
         if cem_terminal_value is not None:
             if not isinstance(cem_terminal_value, dict) or set(cem_terminal_value) - {"hidden_sizes", "activation", "weight"}:
@@ -286,7 +305,7 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                            knot_params=None if knots is None else HipEngine.knot_params(knots[0], knots[1]), tracking=tracking,
                            track_params=tparams, target_advance=bool(cem_target_advance), actuator=actuator, actuator_params=aparams,
                            action_advance=bool(cem_action_advance), uncertainty=uncertainty, uncertainty_params=uparams, value=value, value_params=vparams, reward=reward,
-                           reward_params=rparams, policy=policy, policy_params=pparams, critic=critic, critic_params=qparams, **mppi, **icem)
+                           reward_params=rparams, policy=policy, policy_params=pparams, critic=critic, critic_params=qparams, discount=discount, **mppi, **icem)
 
 
 def policy_slot(keep_elites, last, add_mean_last):
@@ -463,7 +482,11 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     critic: a `HipEngine.critic_params` describing the engine's registered critics (`cadm_critic_plan`; None: none; not with `value`) --
     every rollout then records its trajectories and `critic_returns` adds weight * reduce_c Q_c(s, pi(s)) of the last state to the
     particle rows behind the reward stage, before the score; `return_info` carries `q` [m,n_it,p] (NaN where skipped) and `q_rows`, the
-    rows before the addition."""
+    rows before the addition.
+    On an engine with a discount over the horizon (`HipEngine.set_discount`) every rollout records its trajectories and
+    `discount_returns` rewrites `rows` directly behind it, in front of the constraints; the stage calls above pick the engine's table up
+    themselves; `return_info` carries `rows_undiscounted`, the rollout's own sums, and `rows_discounted` (`rows_raw` is then the
+    discounted rows the constraints read)."""
     if critic is not None and value is not None:
         raise ValueError("icem_plan: critic and value are both given: a plan has one terminal term")
     obs = engine._t(obs)
@@ -479,6 +502,7 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     best_ret = torch.full((m,), float("nan"), dtype=torch.float32, device=engine.device)      # NaN: nothing scored yet (icem_best_init_kernel)
     best_seq = torch.full((m, engine.H, engine.A), float("nan"), dtype=torch.float32, device=engine.device)
     kept, info = None, []
+    discounted = engine.discount_weights() is not None
     for it in range(iters):
         last = it + 1 == iters
         ni = engine.icem_candidates(n, decay, it, K)
@@ -500,16 +524,21 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
         if actuator is not None:
             _, action_cost = engine.actuate_actions(actions, actuator[0], prev=actuator[1], prefix=actuator[2], want_cost=True)
         extra = {}
-        if constraints is None and tracking is None and uncertainty is None and value is None and reward is None and critic is None:
+        if constraints is None and tracking is None and uncertainty is None and value is None and reward is None and critic is None \
+                and not discounted:
             rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
         else:
             rows, traj = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it,
                                                 want_traj=True)
             first = None
+            if discounted:
+                undiscounted = rows
+                rows = engine.discount_returns(traj, obs, actions, undiscounted)
+                extra = dict(traj=traj, rows_undiscounted=undiscounted, rows_discounted=rows)
             if constraints is not None:
                 raw = rows
                 rows, first, viol = engine.constrain_returns(traj, raw, constraints, obs=obs, actions=actions)
-                extra = dict(traj=traj, first_violation=first, violations=viol, rows_raw=raw)
+                extra.update(traj=traj, first_violation=first, violations=viol, rows_raw=raw)
                 if constraints.mode != _lib.CONSTRAIN_MODES["terminate"]:
                     first = None
             if tracking is not None:

@@ -487,7 +487,8 @@ int cadm_knot_plan(cadm_ctx* ctx, const cadm_knot_params* knots, const int32_t* 
  *   (CADM_TRACK_HUBER);   cost += w[k] * c;   rows_out = rows_in - cost
  * A row whose every (step, term) was skipped keeps rows_in's bits: targets that are all NaN change no plan.  A non-finite value in a
  * tracked dim at a counted step makes the row's return non-finite (it then meets the score, the elite ranking and MPPI's zero weight as
- * a diverged rollout's row does); other dims are not looked at.  Not done: wrapping an angle's e, targets on actions, a discount.
+ * a diverged rollout's row does); other dims are not looked at.  Not done: wrapping an angle's e, targets on actions.  On a ctx with a discount
+ * over the horizon (cadm_set_discount): cost += disc[t] * (w_k * c).
  * cadm_tracking_returns: rows_in / rows_out [m,n,p] (rows_out may alias rows_in).  first [m,n,p] int32, or NULL: cadm_constrain_returns'
  * first_violation_out -- steps t > first[row] are not counted: the step that leaves the region still pays, as it does for the reward in
  * TERMINATE mode, and nothing traj holds after it reaches the return.  cost_out [m,n,p], or NULL: the cost alone (0 for a row with
@@ -654,7 +655,8 @@ int cadm_uncertain_plan(cadm_ctx* ctx, const cadm_uncertainty_params* params, co
                         float* best_return_out, void* stream);
 
 /* Terminal value (no reference twin, OPT-IN): a caller-supplied value net V on the LAST state of every particle's trajectory, so that a
- * plan is scored by  return + weight * V(s_H)  and sees beyond its H steps (POLO, LOOP, TD-MPC).  `weight` carries a discount gamma^H.
+ * plan is scored by  return + weight * V(s_H)  and sees beyond its H steps (POLO, LOOP, TD-MPC).  `weight` carries a discount gamma^H -- unless the ctx has a discount
+ * over the horizon (cadm_set_discount): the library then multiplies disc[H] in, and `weight` no longer carries it.
  * V is an MLP  D -> h_1 -> .. -> h_L -> 1,  L = n_hidden in 0 .. CADM_MAX_VALUE_LAYERS (0: a linear V), every width in
  * 1 .. CADM_MAX_VALUE_WIDTH, one hidden activation for the net, a linear output, D <= CADM_MAX_VALUE_DIMS.  For a state s [D], all in
  * float32 (csrc/value.hip):
@@ -867,7 +869,8 @@ int cadm_guided_plan(cadm_ctx* ctx, const cadm_policy_params* policy, const cadm
  *   hidden: the activation;   output q_c: the sum itself
  *   CADM_CRITIC_MIN:   r = q_0;  r = fminf(r, q_c) in ascending c
  *   CADM_CRITIC_MEAN:  r = q_0;  r = r + q_c in ascending c;  for C > 1 then r = r / (float)C  (IEEE division)
- *   rows_out = rows_in + weight * r:  one multiply, then one add, no fma.   weight carries a discount gamma^H.
+ *   rows_out = rows_in + weight * r:  one multiply, then one add, no fma.   weight carries a discount gamma^H, unless the
+ *   ctx has a discount over the horizon (cadm_set_discount): the library then multiplies disc[H] in.
  * A row whose terminal state holds a non-finite value has r = NaN, set explicitly, and so a NaN return: the actor's fallback action is
  * not what a Q is computed from.  With first [m,n,p] (cadm_constrain_returns' first_violation, TERMINATE mode) a row with first[q] < H
  * keeps the bits of rows_in, its q_out is NaN, and its terminal state is not read.
@@ -921,6 +924,44 @@ int cadm_critic_plan(cadm_ctx* ctx, const cadm_critic_params* critic, const cadm
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                      float* best_return_out, void* stream);
+
+/* A discount over the horizon of the opt-in planner (csrc/discount.hip; no reference twin, OPT-IN).  It is state of the ctx, as the
+ * horizon is, not an argument of the plan entry points: every quantity that enters a candidate's score is weighted per step by ONE
+ * table, so that a learner's critic behind the plan and the step rewards in front of it obey one Bellman equation.
+ * cadm_set_discount: gamma in (0, 1]; NaN, gamma <= 0 and gamma > 1 are CADM_EINVAL before any HIP call.  gamma == 1 clears the
+ * discount: the table is then null and every launch of the library is the undiscounted one.  Otherwise the ctx owns a device table
+ *   disc[t] = (float)pow((double)gamma, (double)t),  t = 0 .. H,  disc[0] = 1 exactly,
+ * built on the host and copied on `stream`.  Set the discount BEFORE a workspace is sized: with a discount the loop always records
+ * trajectories, and every cadm_*_workspace_bytes(ctx, ..) of the nest from cadm_icem_workspace_bytes to cadm_critic_workspace_bytes
+ * returns the size with the trajectory view.  Refusals of a gamma < 1: a discrete ctx (cartpole), a candidate-sharded ctx, a D whose two
+ * tiles of 64 x D floats and the table exceed 48 KiB of LDS (CADM_EINVAL); a CADM_ENV_SPEC ctx whose spec is not set (CADM_ESTATE).
+ * cadm_discount_weights: *set_out = 1 and host_out[0 .. H] = the same floats the kernels read (host_out may be NULL), or *set_out = 0.
+ * What a table does, with disc[t] the weight of step t (every product and every add one fp32 rounding, nothing fused):
+ *   the env's own return      the loop launches cadm_discount_returns directly behind the rollout:  sum = disc[0] * r_0;  for t = 1 ..
+ *                             H - 1: sum = sum + disc[t] * r_t;  rows_out[q] = isnan(rows_in[q]) ? rows_in[q] : sum.  r_t is the step
+ *                             reward from the recorded states (pre-step state obs at t = 0, else traj[t - 1]; post-step state traj[t];
+ *                             the raw action), as cadm_constrain_returns' TERMINATE mode takes it
+ *   cadm_constrain_returns    PENALTY: pen = pen + disc[t] on the violating steps, ascending t from 0.0f;  rows - w * pen (a row without
+ *                             a violation keeps its bits; the counters are unchanged).  TERMINATE: sum as above up to tau, then
+ *                             sum - w * disc[tau]: the penalty is paid at the step that leaves
+ *   cadm_tracking_returns     cost = cost + disc[t] * (w_k * c), the order (t, k) ascending and the NaN-target skip unchanged
+ *   cadm_reward_returns       S = S + disc[t] * R_t; step_out stays undiscounted
+ *   cadm_uncertainty_cost     cost = cost + disc[t] * u_t, u_t behind form and cap; step [m,n,H] stays undiscounted
+ *   cadm_actuate_actions      c_a = c_a + disc[t] * (w_a * (y - last)^2); pins, limits and the sequences are untouched
+ *   cadm_value_returns,       rows + weight_eff * V with weight_eff = weight * disc[H], one fp32 product on the host: with a discount
+ *   cadm_critic_returns       set, `weight` no longer carries gamma^H, the library multiplies it in
+ * The `first` cuts of these calls are unchanged.  The stand-alone calls read the table as the loop's stages do: a diagnostic reports what
+ * the planner scored.  cadm_cem_plan, cadm_cem_plan_staged and cadm_rs_plan sum the step rewards inside the rollout kernel: on a ctx with
+ * a discount they return CADM_ESTATE and launch nothing.  cadm_plan_forecast, cadm_policy_propose, cadm_eval_horizon and
+ * cadm_eval_calibration do not score a plan and ignore the table: a forecast's returns stay the undiscounted sums.
+ * cadm_discount_returns: traj [H,m,n,p,D] (a rollout's traj_out, n its packed candidate count), obs [m,D], actions [m,n,H,A] (raw, as the
+ * rollout read them), rows_in / rows_out [m,n,p] (rows_out may alias rows_in), step_out [H,m,n,p] or NULL: the undiscounted r_t.  With no
+ * discount set: CADM_ESTATE.  Determinism: a row's sum is one thread's chain in ascending t, no floating-point atomics, nothing depends
+ * on the grid, on m or n, or on the row's position: the same bits run to run and inside any batch. */
+int cadm_set_discount(cadm_ctx* ctx, float gamma, void* stream);
+int cadm_discount_weights(cadm_ctx* ctx, float* host_out, int* set_out);
+int cadm_discount_returns(cadm_ctx* ctx, const float* traj, const float* obs, const float* actions, int m, int n, const float* rows_in,
+                          float* rows_out, float* step_out, void* stream);
 
 /* One training step =sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
