@@ -139,6 +139,9 @@ class RewardParams(C.Structure):        # include/cadm_hip.h cadm_reward_params 
 
 MAX_POLICY_ACTIONS = 64                                                    # CADM_MAX_POLICY_ACTIONS
 POLICY_SQUASH = {"none": 0, "tanh": 1}                                     # CADM_POLICY_NONE / _TANH
+IMAGINE_IT = 0xF00000                                                      # csrc/planner.h CADM_IMAGINE_IT: imagine's one-step rollouts run under IMAGINE_IT + 2 t, below POLICY_IT
+IMAGINE_VIEWS = 9                                                          # include/cadm_hip.h CADM_IMAGINE_VIEWS: the outputs cadm_imagine_workspace_bytes reports offsets of
+STREAM_IMAGINE, STREAM_IMAGINE_ACT = 6, 7                                  # csrc/common.h: the Philox stream words of imagine's particle draw and action noise
 POLICY_IT = 0xFA0000                                                       # csrc/planner.h CADM_POLICY_IT: the roll's one-step rollouts run under POLICY_IT + 2 t
 
 
@@ -263,6 +266,10 @@ SIGNATURES = {
     "cadm_set_discount": (_i, [_P, C.c_float, _P]),
     "cadm_discount_weights": (_i, [_P, C.POINTER(C.c_float), C.POINTER(_i)]),
     "cadm_discount_returns": (_i, [_P, _P, _P, _P, _i, _i, _P, _P, _P, _P]),
+    "cadm_imagine_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, C.POINTER(C.c_uint64)]),
+    "cadm_imagine": (_i, [_P, _P, _P, _P, _i, _i, _i, C.c_float, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P]),
+    "cadm_imagine_select": (_i, [_P, _P, _P, _P, _P, _i, _i, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P, _P,
+                                 _P, _P, _P, _P, _P, _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

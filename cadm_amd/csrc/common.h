@@ -60,6 +60,8 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_STREAM_UNI 3u
 #define CADM_STREAM_ICEM 4u   // spectral draws of the coloured-noise sampler (icem.hip)
 #define CADM_STREAM_POLICY 5u // exploration noise of the policy prior's proposals (policy.hip)
+#define CADM_STREAM_IMAGINE 6u      // the particle draw of an imagined transition (imagine.hip)
+#define CADM_STREAM_IMAGINE_ACT 7u  // exploration noise of an imagined rollout's actions (imagine.hip, through policy.hip's step)
 
 // ---------------------------------------------------------------------------------------------
 // planner weight-stream geometry (see DESIGN.md "weight streams")

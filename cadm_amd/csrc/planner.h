@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, critic.hip, discount.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, critic.hip, discount.hip, imagine.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -45,6 +45,10 @@ struct Carver {
 // iteration 0's.  The range lies above every planner iteration and below the forecast's word (cadm_policy_propose refuses a ctx whose
 // num_cem_iters or horizon could break that), so a roll never repeats the noise of a planner call or a forecast of the same (seed, call).
 #define CADM_POLICY_IT 0xFA0000
+// imagine.hip: the one-step rollouts of cadm_imagine run under CADM_IMAGINE_IT + 2 t, t = 0 .. k - 1.  Even: the context layout is
+// iteration 0's.  The range lies above every planner iteration and below the proposal roll's words (cadm_imagine refuses a ctx whose
+// num_cem_iters, or a k whose last word, would leave it), so imagined rollouts never repeat the noise of a plan, a roll or a forecast.
+#define CADM_IMAGINE_IT 0xF00000
 
 // cem.hip
 int cadm_launch_clip(const float* in, float* out, int total, float lo, float hi, int do_clip, hipStream_t s);
@@ -124,6 +128,11 @@ int cadm_launch_reward(cadm_ctx* ctx, const cadm_reward_params* reward, const fl
 int cadm_policy_plan_check(const cadm_ctx* ctx, const cadm_policy_params* policy, const char* who);
 int cadm_launch_policy_propose(cadm_ctx* ctx, const cadm_policy_params* policy, const float* obs, const float* ctx_vec, int m, uint32_t seed,
                                uint32_t call, float* seqs_out, float* states_out, void* workspace, hipStream_t s, const char* who);
+// policy.hip, for imagine.hip: ONE policy step of the registered net (CADM_ESTATE without one) on states x [total, D], one state per row:
+// a1 [total, A] = the squashed action, with noise_std > 0 perturbed on EVERY row by noise_std * xi under the given stream word
+// (counter (row, t, g, stream)), clipped.  noise_std == 0: the launch of cadm_policy_eval.
+int cadm_launch_policy_step(cadm_ctx* ctx, const float* x, size_t total, int t, float noise_std, uint32_t seed, uint32_t call,
+                            uint32_t stream_word, float* a1, hipStream_t s, const char* who);
 // policy.hip, for critic.hip: the packed copy (mlp_chain.h) and the description of the registered policy net, null while none is
 // registered; and the net's dims D, h_1 .. h_L, A
 struct MlpNet;
@@ -144,6 +153,15 @@ int cadm_launch_critic(cadm_ctx* ctx, const cadm_critic_params* critic, const fl
 int cadm_discount_check(const cadm_ctx* ctx, const char* who);
 int cadm_launch_discount(cadm_ctx* ctx, const float* traj, const float* obs, const float* actions, int m, int n, const float* rows_in,
                          float* rows_out, float* step_out, hipStream_t s);
+// imagine.hip: branched one-step rollouts recorded as transitions (include/cadm_hip.h, "Imagined rollouts").  The refusals of the chain
+// (k or branches < 1, a discrete / sharded ctx, a p * D tile beyond the select kernel's LDS, m * n * p rows beyond one rollout launch, a
+// num_cem_iters or k that leaves the chain's iteration words, constraints that constrain.hip or weights that uncertainty.hip refuses),
+// before any HIP call; and the chain itself over the buffer of cadm_imagine_workspace_bytes(ctx, m, n, k)
+int cadm_imagine_check(const cadm_ctx* ctx, int m, int n, int k, const cadm_constraint_params* constraints,
+                       const cadm_uncertainty_params* disagreement, const char* who);
+int cadm_launch_imagine(cadm_ctx* ctx, const float* obs, const float* ctx_vec, const float* actions, int m, int n, int k, float noise_std,
+                        const cadm_constraint_params* constraints, const cadm_uncertainty_params* disagreement, uint32_t seed, uint32_t call,
+                        void* buffer, hipStream_t s, const char* who);
 // what the reference-path loops (plan.hip) answer on a discounted ctx: they sum the step rewards inside the rollout kernel
 inline int cadm_refuse_discounted(const cadm_ctx* ctx, const char* who) {
     if (!ctx->disc) return CADM_OK;

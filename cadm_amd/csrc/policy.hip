@@ -13,6 +13,7 @@
 //   hidden: relu, tanhf or swish;  output z_d: linear, A units
 //   CADM_POLICY_TANH: a_d = mid + half * tanhf(z_d)  (one multiply, one add);  CADM_POLICY_NONE: a_d = z_d
 //   j >= 1 and noise_std > 0: a_d = a_d + noise_std * xi_d  (one multiply, one add);   a_d = fminf(fmaxf(a_d, lb), ub)
+//   (PolicyArgs::all_rows, imagine.hip's steps only: j == 0 is perturbed too, and xi's stream word is PolicyArgs::stream)
 // xi: Philox4x32-10 keyed (seed, call), counter (mi * P + j, t, g, CADM_STREAM_POLICY); one call serves dims 4 g .. 4 g + 3, words
 // (0, 1) through Box-Muller to dims 4 g and 4 g + 1, words (2, 3) to 4 g + 2 and 4 g + 3 (u01 / box_muller of common.h, the Gaussian
 // head's).  Sequence 0 never gets noise: the policy's own trajectory is always among the proposals.
@@ -44,6 +45,8 @@ struct PolicyArgs {
     float* states;                 // [total, p, D] or null: the particle states that were read
     size_t total;
     int region0, region1;          // LDS floats of the two activation regions
+    int all_rows;                  // 1: row j == 0 is perturbed like the others (imagine.hip); 0: sequence 0 never gets noise
+    uint32_t stream;               // the stream word of xi: CADM_STREAM_POLICY for the proposals
 };
 
 __device__ __forceinline__ bool policy_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
@@ -110,9 +113,9 @@ __global__ __launch_bounds__(MLP_THREADS) void policy_step_kernel(const PolicyAr
         } else {
             v = xin[d * R + mlp_swz<RT>(row, d)];
             if (a.squash == CADM_POLICY_TANH) v = __fadd_rn(a.mid, __fmul_rn(a.half, tanhf(v)));      // (one multiply, then one add: never an fma)
-            if (a.noise_std > 0.0f && q % a.P != 0) {
+            if (a.noise_std > 0.0f && (a.all_rows || q % a.P != 0)) {
                 uint32_t r[4];
-                philox4x32_10((uint32_t)q, (uint32_t)a.t, (uint32_t)(d >> 2), CADM_STREAM_POLICY, a.seed, a.call, r);
+                philox4x32_10((uint32_t)q, (uint32_t)a.t, (uint32_t)(d >> 2), a.stream, a.seed, a.call, r);
                 float z0, z1;
                 const int w = d & 2;
                 box_muller(u01(r[w]), u01(r[w + 1]), z0, z1);
@@ -221,7 +224,8 @@ int cadm_policy_plan_check(const cadm_ctx* ctx, const cadm_policy_params* p, con
 
 // one policy step over `total` rows: obs [m, D] (t == 0) or x [total, p, D]; seqs [total, H, A] or null; a1 [total, A]; states or null
 static int policy_launch(cadm_ctx* ctx, const float* obs, const float* x, int P, int p, int t, float noise_std, uint32_t seed, uint32_t call,
-                         float* seqs, float* a1, float* states, size_t total, hipStream_t s, const char* who) {
+                         float* seqs, float* a1, float* states, size_t total, hipStream_t s, const char* who, int all_rows = 0,
+                         uint32_t stream_word = CADM_STREAM_POLICY) {
     const PolicyNet& net = *ctx->policy;
     PolicyArgs a{};
     policy_dims(ctx, &net.prm, a.dims);
@@ -234,6 +238,7 @@ static int policy_launch(cadm_ctx* ctx, const float* obs, const float* x, int P,
     a.lb = ctx->cfg.lower_bound; a.ub = ctx->cfg.upper_bound;
     a.mid = 0.5f * (a.ub + a.lb); a.half = 0.5f * (a.ub - a.lb);
     a.noise_std = noise_std; a.seed = seed; a.call = call;
+    a.all_rows = all_rows; a.stream = stream_word;
     a.seqs = seqs; a.a1 = a1; a.states = states; a.total = total;
     // two row tiles halve the weight stream per row; one tile keeps every CU busy while the rows are few
     int RT = (total + 15) / 16 > 2 * (size_t)ctx->n_cus ? 2 : 1;
@@ -274,6 +279,13 @@ int cadm_launch_policy_propose(cadm_ctx* ctx, const cadm_policy_params* prm, con
         }
     }
     return CADM_OK;
+}
+
+// imagine.hip's step: the registered net on one state per row (cadm_policy_eval's launch), every row perturbed under `stream_word`
+int cadm_launch_policy_step(cadm_ctx* ctx, const float* x, size_t total, int t, float noise_std, uint32_t seed, uint32_t call,
+                            uint32_t stream_word, float* a1, hipStream_t s, const char* who) {
+    if (!ctx->policy || !ctx->policy->set) { cadm_set_error("%s: no policy net is registered (call cadm_set_policy_net)", who); return CADM_ESTATE; }
+    return policy_launch(ctx, nullptr, x, 1, 1, t, noise_std, seed, call, nullptr, a1, nullptr, total, s, who, 1, stream_word);
 }
 
 extern "C" int cadm_set_policy_net(cadm_ctx* ctx, const cadm_policy_params* params, const float* const* W, const float* const* b,

@@ -276,6 +276,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_policy_prior=None,
                  cem_terminal_q=None,
                  cem_discount=1.0,
+                 imagine_policy=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -355,6 +356,10 @@ class MLPEnsembleCEMDynamicsModel(object):
             tp = self._opt.track_params
             if max(tp.dim[:tp.n]) >= obs_space_dims:
                 raise ValueError("cem_tracking reads observation dim %d, this env has %d" % (max(tp.dim[:tp.n]), obs_space_dims))
+        # the actor of `imagine` on a model whose planner declares none (planner.imagine_policy_params): never part of `_opt`, so
+        # get_action of such a model stays on the route its cem_* kwargs select
+        self._imagine_policy = _planner.imagine_policy_params(imagine_policy, self._opt, obs_dim=obs_space_dims,
+                                                              action_dim=self.action_space_dims, discrete=self.discrete)
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
         self._plan_phase = None                               # device tensor [m] int32: the knot grid's phase (cem_knot_anchor="episode")
         self._targets = self._target_offset = None            # device tensors [m,T,K] float32 / [m] int32 (cem_tracking): `set_targets`
@@ -368,6 +373,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         self.seed = int(seed)
         self._call = 0
         self._eval_call = 0             # evaluate_horizon's own noise counter: evaluations never shift get_action's draws
+        self._imagine_call = 0          # imagine's own noise counter, likewise: the key of a call is (seed, _imagine_call), then it moves on
         self._checked_sig = None        # shape set of the last get_action whose inputs were checked
         self._group = process_group
         self._shard1 = None
@@ -899,19 +905,29 @@ class MLPEnsembleCEMDynamicsModel(object):
     # ------------------------------------------------------------------ policy prior (INTEGRATION.md "Policy prior")
     def _require_policy(self, who, need_net=False, prior_or_q=False):
         opt = getattr(self, "_opt", None)
+        if prior_or_q and getattr(self, "_imagine_policy", None) is not None:      # (the actor of `imagine` alone: no planner option)
+            if need_net and not self._policy_set:
+                raise RuntimeError("%s: this model has no policy net (call set_policy first)" % who)
+            return opt
         if opt is None or (opt.policy_params is None and not (prior_or_q and opt.critic_params is not None)):
-            raise ValueError("%s: this model has no cem_policy_prior%s" % (who, " and no cem_terminal_q" if prior_or_q else ""))
+            raise ValueError("%s: this model has no cem_policy_prior%s" % (who, " and no cem_terminal_q (and no imagine_policy)" if prior_or_q else ""))
         if need_net and not self._policy_set:
             raise RuntimeError("%s: this model has no policy net (call set_policy first)" % who)
         return opt
 
+    def _actor_params(self):
+        """the `PolicyParams` this model's actor is registered under: the planner's declaration, else `imagine_policy`'s; None without one"""
+        opt = getattr(self, "_opt", None)
+        prm = None if opt is None else opt.actor_params()
+        return prm if prm is not None else getattr(self, "_imagine_policy", None)
+
     def set_policy(self, weights, obs_mean=None, obs_std=None):
-        """The policy net of `cem_policy_prior` from the next call on: `weights` as `set_terminal_value` takes them (a list of (W [in,out],
+        """The policy net of `cem_policy_prior` (or the actor of `cem_terminal_q` / `imagine_policy`) from the next call on: `weights` as `set_terminal_value` takes them (a list of (W [in,out],
         b [out]) per layer or a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules, the last Linear with A outputs) -- of the
         declared layer sizes and activation, else it is refused; obs_mean / obs_std [D] (None: 0 / 1): the net reads (obs - obs_mean) /
         obs_std of the raw observation.  Everything is copied; replacing the net rebuilds nothing."""
-        opt = self._require_policy("set_policy", prior_or_q=True)      # (the actor of cem_terminal_q alone: registered with n_samples = 1)
-        self.engine.set_policy_net(opt.actor_params(), weights, obs_mean=obs_mean, obs_std=obs_std)
+        self._require_policy("set_policy", prior_or_q=True)      # (the actor of cem_terminal_q or imagine_policy alone: registered with n_samples = 1)
+        self.engine.set_policy_net(self._actor_params(), weights, obs_mean=obs_mean, obs_std=obs_std)
         self._policy_set = True
 
     def clear_policy(self):
@@ -944,6 +960,60 @@ class MLPEnsembleCEMDynamicsModel(object):
         out = eng.policy_propose(opt.policy_params, eng._t(obs).contiguous(), ctx_vec, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
                                  call=self._call & 0xFFFFFFFF, want_states=return_states)
         return (out[0].cpu().numpy(), out[1].cpu().numpy()) if return_states else out.cpu().numpy()
+
+    # ------------------------------------------------------------------ imagined rollouts (INTEGRATION.md "Imagined rollouts for a learner")
+    def imagine(self, obs, cp_obs=None, cp_act=None, horizon=1, branches=1, actions=None, noise_std=0.0, disagreement_w=None, seed=None,
+                numpy=False):
+        """Model-generated experience for a learner (MBPO / Dyna): `branches` independent rollouts of `horizon` steps from each start state
+        obs [m,D] (with a context model each state's own history cp_obs / cp_act, as `policy_proposals` takes them), as transitions.
+        Actions: the registered actor (`set_policy`) on every row's own state, perturbed by noise_std * xi and clipped on EVERY row; or
+        `actions` [m,branches,horizon,A], raw and clipped to the bounds, with no policy registered -- one source per call.  Every step is a
+        one-step rollout of the planner's kernels, so horizon is independent of n_forwards; of the n_particles predictions of a row
+        (every member n_particles / E times) ONE is kept, drawn uniformly (MBPO's scheme).  Returns a dict of device tensors (numpy=True:
+        numpy copies) of static shape, k = horizon, n = branches:
+          states [k+1,m,n,D]   with the views obs = states[:-1] and next_obs = states[1:]
+          act [k,m,n,A]; rew [k,m,n]   the action taken; the rollout's own step reward of the kept particle -- what the planner scores by
+          done, valid [k,m,n] uint8    valid: a transition to train on; done: it ended the row (the state left `cem_constraints`)
+          member [k,m,n] int32         the ensemble member that predicted it (-1: the row was dead)
+          disagreement [k,m,n]         sum_d w_d * (epistemic variance of dim d over the row's particles) as `cem_uncertainty` computes it
+                                       (kind="epistemic", form="var", no cap); w: disagreement_w -- None (1), [D], or "delta_std"; +inf if not finite
+          length [m,n] int32; n_valid  the valid transitions of a row; of the call (a 0-dim tensor; numpy=True: an int)
+        A row whose kept particle is not finite stops without a valid transition; a row behind its end is frozen at its last state with
+        valid = 0, rew = 0, member = -1, disagreement = 0.  Nothing is compacted: out["obs"][out["valid"].bool()] is the flat batch.
+        `cem_constraints` (either mode) define termination; `cem_reward_net` with a registered net adds weight * R(s, a, s') to rew, and the
+        dict then also holds rew_env and rew_net (0 where not valid).  The other planner options -- knots, tracking, the actuator model,
+        uncertainty pricing, the discount, the terminal value or Q -- change nothing here.  A deterministic model draws no head noise and
+        still draws the kept particle.  The noise is keyed (seed, a counter of imagine's own): get_action's draws never move."""
+        import torch.distributed as dist
+        world = dist.get_world_size(self._group) if self._group is not None else 1
+        a = _planner.imagine_args(obs, cp_obs, cp_act, horizon, branches, actions, noise_std, disagreement_w, obs_dim=self.obs_space_dims,
+                                  action_dim=self.action_space_dims, n_particles=self.n_particles, context=self.context_out_dim > 0,
+                                  history_length=self.history_length, discrete=self.discrete, world=world,
+                                  policy_registered=self._policy_set)
+        self._push_stats()
+        eng, opt = self.engine, getattr(self, "_opt", None)
+        w = a.w
+        if isinstance(w, str):      # the spread in units of the model's own one-step target scale, as cem_uncertainty's "delta_std"
+            sd = np.asarray(self._stats12()[5], dtype=np.float64).reshape(-1) + 1e-10
+            w = (1.0 / (sd * sd)).astype(np.float32)
+        ctx_vec = eng.context_forward(cp_obs, cp_act) if self.context_out_dim > 0 else None
+        call = self._imagine_call & 0xFFFFFFFF
+        self._imagine_call += 1
+        out = eng.imagine(eng._t(obs).contiguous(), ctx_vec, a.k, a.n, actions, a.noise_std,
+                          None if opt is None else opt.constraint_params, w, int(self.seed if seed is None else seed) & 0xFFFFFFFF, call)
+        out.pop("alive")
+        out["obs"], out["next_obs"] = out["states"][:-1], out["states"][1:]
+        out["n_valid"] = out["valid"].sum()
+        if opt is not None and opt.reward_params is not None and self._reward_set:
+            parts = {"next_obs": (out["next_obs"],), "obs_act": (out["obs"], out["act"]),
+                     "obs_act_next_obs": (out["obs"], out["act"], out["next_obs"])}[opt.reward[0]]
+            r = eng.reward_eval(torch.cat(parts, dim=-1))
+            out["rew_env"] = out["rew"]
+            out["rew_net"] = torch.where(out["valid"].bool(), r, torch.zeros_like(r))
+            out["rew"] = out["rew_env"] + out["rew_net"] * float(np.float32(opt.reward_params.weight))      # (one multiply, then one add: two launches)
+        if numpy:
+            out = {k: (int(v) if k == "n_valid" else v.cpu().numpy()) for k, v in out.items()}
+        return out
 
     # ------------------------------------------------------------------ learned reward (INTEGRATION.md "Learned reward")
     def _require_reward(self, who, need_net=False):

@@ -1632,6 +1632,74 @@ class HipEngine:
                                                  ptr(ws), self.stream), "cadm_policy_propose")
         return (seqs, states) if want_states else seqs
 
+    def _imagine_w(self, w):
+        """the disagreement weights of `imagine` / `imagine_select` as the library takes them: None (w = 1), or an `UncertaintyParams`
+        holding [D] weights (only n_dims and w are read)"""
+        if w is None or isinstance(w, _lib.UncertaintyParams):
+            return w
+        return HipEngine.uncertainty_params("epistemic", 1.0, w, "var", None, obs_dim=self.D)
+
+    def imagine(self, obs, ctx_vec=None, horizon=1, branches=1, actions=None, noise_std=0.0, constraints=None, w=None, seed=0, call=0):
+        """`cadm_imagine`: n = branches rollouts of k = horizon one-step rollouts from each of obs [m,D] (ctx_vec: the context encoder's
+        output for them, None without one), under actions [m,n,k,A] (raw, clipped) or, with None, the registered policy net perturbed by
+        noise_std * xi on every row -> a dict of device tensors, views of ONE buffer the call allocates: states [k+1,m,n,D], act
+        [k,m,n,A], rew [k,m,n], done / valid [k,m,n] uint8, member [k,m,n] int32, disagreement [k,m,n], length [m,n] int32, alive [m,n]
+        uint8.  constraints: a `ConstraintParams` (a violated one ends the row) or None; w: None, [D] weights or an
+        `UncertaintyParams` of the disagreement.  (seed, call): the Philox key of the head noise, the particle draws and the action noise."""
+        obs = self._t(obs)
+        if obs.dim() != 2 or obs.shape[1] != self.D or not obs.is_contiguous():
+            raise ValueError("imagine: obs %r, expected contiguous [m, %d]" % (tuple(obs.shape), self.D))
+        m, n, k = int(obs.shape[0]), int(branches), int(horizon)
+        if actions is not None:
+            actions = self._t(actions)
+            if tuple(actions.shape) != (m, n, k, self.A):
+                raise ValueError("imagine: actions %r, expected %r" % (tuple(actions.shape), (m, n, k, self.A)))
+        ctx_vec = None if ctx_vec is None else self._t(ctx_vec)
+        w = self._imagine_w(w)
+        if m >= 1 and n >= 1:
+            self.ensure_rollout(None, m, n)
+        off = (ct.c_uint64 * _lib.IMAGINE_VIEWS)()
+        need = self.lib.cadm_imagine_workspace_bytes(self._ctx, m, n, k, off)
+        buf = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.cadm_imagine(self._ctx, ptr(obs), ptr(ctx_vec), ptr(actions), m, n, k, float(noise_std),
+                                          None if constraints is None else ct.byref(constraints), None if w is None else ct.byref(w),
+                                          seed, call, ptr(buf), self.stream), "cadm_imagine")
+        views = (("states", torch.float32, (k + 1, m, n, self.D)), ("act", torch.float32, (k, m, n, self.A)), ("rew", torch.float32, (k, m, n)),
+                 ("done", torch.uint8, (k, m, n)), ("valid", torch.uint8, (k, m, n)), ("member", torch.int32, (k, m, n)),
+                 ("disagreement", torch.float32, (k, m, n)), ("length", torch.int32, (m, n)), ("alive", torch.uint8, (m, n)))
+        out = {}
+        for (name, dtype, shape), o in zip(views, off):
+            nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+            out[name] = buf[int(o):int(o) + nbytes].view(dtype).view(shape)
+        return out
+
+    def imagine_select(self, nxt, rows1, state, alive, t=0, sel=None, constraints=None, w=None, seed=0, call=0, length=None, want_bcast=True):
+        """`cadm_imagine_select`, the stage between two of `imagine`'s rollouts alone: nxt [R,p,D] and rows1 [R,p] (a one-step rollout's
+        states and returns), state [R,D] (states[t]), alive [R] uint8 -> dict(state, rew, done, valid, member, disagreement, alive, length,
+        bcast): the outputs of step t for the R rows; `alive` and `length` (None: zeros) are copied, not changed.  sel [R] int32: the
+        particle of every row in the place of the draw under (seed, call, row, t)."""
+        nxt, rows1, state = self._t(nxt), self._t(rows1), self._t(state)
+        R = int(state.shape[0]) if state.dim() == 2 else -1
+        if tuple(nxt.shape) != (R, self.p, self.D) or tuple(rows1.shape) != (R, self.p) or tuple(state.shape) != (R, self.D) or R < 1:
+            raise ValueError("imagine_select: next %r, rows1 %r, state %r: expected [R,%d,%d], [R,%d], [R,%d]"
+                             % (tuple(nxt.shape), tuple(rows1.shape), tuple(state.shape), self.p, self.D, self.p, self.D))
+        alive = self._t(alive, dtype=torch.uint8).clone()
+        length = torch.zeros((R,), dtype=torch.int32, device=self.device) if length is None else self._t(length, dtype=torch.int32).clone()
+        sel = None if sel is None else self._t(sel, dtype=torch.int32)
+        if tuple(alive.shape) != (R,) or tuple(length.shape) != (R,) or (sel is not None and tuple(sel.shape) != (R,)):
+            raise ValueError("imagine_select: alive / length / sel must be [%d]" % R)
+        w = self._imagine_w(w)
+        new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=self.device)
+        out = dict(state=new((R, self.D)), rew=new((R,)), done=new((R,), torch.uint8), valid=new((R,), torch.uint8),
+                   member=new((R,), torch.int32), disagreement=new((R,)), alive=alive, length=length,
+                   bcast=new((R, self.p, self.D)) if want_bcast else None)
+        self._check(self.lib.cadm_imagine_select(self._ctx, ptr(nxt), ptr(rows1), ptr(state), ptr(sel), R, int(t),
+                                                 None if constraints is None else ct.byref(constraints), None if w is None else ct.byref(w),
+                                                 seed, call, ptr(alive), ptr(out["state"]), ptr(out["rew"]), ptr(out["done"]), ptr(out["valid"]),
+                                                 ptr(out["member"]), ptr(out["disagreement"]), ptr(length), ptr(out["bcast"]), self.stream),
+                    "cadm_imagine_select")
+        return out
+
     def guided_plan(self, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints,
                     score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
                     want_best_return=False):

@@ -322,6 +322,93 @@ def policy_min_candidates(n, decay, num_elites, keep_elites, iters=5):
     return min(min(int(n), max(int(np.floor(float(n) / d ** it)), 2 * int(num_elites), int(keep_elites) + 1)) for it in range(int(iters)))
 
 
+def imagine_policy_params(imagine_policy, opt=None, obs_dim=None, action_dim=None, discrete=False):
+    """What a model's `imagine_policy` kwarg means -> the `PolicyParams` its actor is registered under (`set_policy`), or None for None.
+    imagine_policy: dict(hidden_sizes=, activation=, squash=), the shape of the actor `imagine` rolls out on a model that PLANS without
+    one; `opt`: the model's `PlanOptions` (None: the reference planner) -- a planner-declared actor (`cem_policy_prior`, or
+    `cem_terminal_q`'s policy) is the one actor of a model, so giving both is refused.  Touches no planner option.  Needs no GPU."""
+    if imagine_policy is None:
+        return None
+    if not isinstance(imagine_policy, dict) or set(imagine_policy) - {"hidden_sizes", "activation", "squash"}:
+        raise ValueError("imagine_policy must be dict(hidden_sizes=, activation=, squash=), got %r" % (imagine_policy,))
+    if opt is not None and opt.actor_params() is not None:
+        raise ValueError("imagine_policy is given together with a planner-declared actor (cem_policy_prior / cem_terminal_q): a model has one "
+                         "actor, and imagine() rolls that one out")
+    if discrete:
+        raise NotImplementedError("imagine_policy declares a continuous actor: this env's action space is discrete")
+    if obs_dim is not None and not 1 <= int(obs_dim) <= _lib.MAX_VALUE_DIMS:
+        raise ValueError("a policy net reads up to %d observation dims, got %r" % (_lib.MAX_VALUE_DIMS, obs_dim))
+    if action_dim is not None and not 1 <= int(action_dim) <= _lib.MAX_POLICY_ACTIONS:
+        raise ValueError("a policy net writes up to %d action dims, got %r" % (_lib.MAX_POLICY_ACTIONS, action_dim))
+    q = dict(hidden_sizes=(256, 256), activation="relu", squash="tanh")
+    q.update(imagine_policy)
+    return HipEngine.policy_params(q["hidden_sizes"], q["activation"], q["squash"], 1, 0.0)
+
+
+IMAGINE_IT = _lib.IMAGINE_IT      # the iteration word of imagine's first one-step rollout: csrc/planner.h CADM_IMAGINE_IT
+IMAGINE_MAX_STEPS = (POLICY_IT - IMAGINE_IT) // 2      # steps whose even words IMAGINE_IT + 2 t stay below the proposal roll's
+ImagineArgs = collections.namedtuple("ImagineArgs", "m n k noise_std w")
+
+
+def imagine_args(obs, cp_obs=None, cp_act=None, horizon=1, branches=1, actions=None, noise_std=0.0, disagreement_w=None, *, obs_dim, action_dim,
+                 n_particles, context=False, history_length=0, discrete=False, world=1, policy_registered=False):
+    """The parsing and the refusals of `model.imagine`'s arguments, before anything is launched -> ImagineArgs(m, n, k, noise_std, w): m start
+    states, n branches, k steps, the noise as the float32 the library is handed, and w -- None (1 for every dim), "delta_std", or the
+    float32 [D] weights of the disagreement.  Arrays may be numpy or torch.  ValueError for horizon / branches < 1, neither a registered
+    policy nor actions or both, wrong shapes, non-finite obs, a missing history on a context model, m * n * p rows beyond one rollout
+    launch, k beyond the iteration words; NotImplementedError for a discrete action space or more than one rank.  Needs no GPU."""
+    D, A, p = int(obs_dim), int(action_dim), int(n_particles)
+    if discrete:
+        raise NotImplementedError("imagine: discrete actions are not rolled out (the actor and the open-loop actions are continuous)")
+    if int(world) > 1:
+        raise NotImplementedError("imagine is not sharded over a process group of more than one rank")
+    for name, v in (("horizon", horizon), ("branches", branches)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise ValueError("imagine: %s must be an int >= 1, got %r" % (name, v))
+    k, n = int(horizon), int(branches)
+    if k > IMAGINE_MAX_STEPS:
+        raise ValueError("imagine: horizon %d is beyond the %d steps the rollouts' iteration words hold" % (k, IMAGINE_MAX_STEPS))
+    shp = tuple(int(v) for v in np.shape(obs))
+    if len(shp) != 2 or shp[1] != D or shp[0] < 1:
+        raise ValueError("imagine: obs %r, expected [m,%d] with m >= 1" % (shp, D))
+    m = shp[0]
+    if m * n * p * max(D, A) >= 1 << 31:
+        raise ValueError("imagine: m * branches * n_particles = %d rows are more than one rollout launch takes" % (m * n * p))
+    finite = bool(torch.isfinite(obs).all()) if isinstance(obs, torch.Tensor) else bool(np.isfinite(np.asarray(obs, dtype=np.float64)).all())
+    if not finite:
+        raise ValueError("imagine: obs holds a non-finite value (a rollout cannot start from it)")
+    if (actions is None) == (not policy_registered):
+        raise ValueError("imagine: %s" % ("neither a registered policy (set_policy) nor actions" if actions is None else
+                                          "actions are given and a policy is registered: clear_policy() first, one source of actions per call"))
+    if actions is not None and tuple(int(v) for v in np.shape(actions)) != (m, n, k, A):
+        raise ValueError("imagine: actions %r, expected [m,branches,horizon,A] = %r" % (tuple(np.shape(actions)), (m, n, k, A)))
+    if context:
+        if cp_obs is None or cp_act is None:
+            raise ValueError("imagine: cp_obs and cp_act are required for a context model (each start state's own history)")
+        want = ((m, D * int(history_length)), (m, A * int(history_length)))
+        if (tuple(np.shape(cp_obs)), tuple(np.shape(cp_act))) != want:
+            raise ValueError("imagine: cp_obs %r / cp_act %r, expected %r / %r" % ((tuple(np.shape(cp_obs)), tuple(np.shape(cp_act))) + want))
+    elif cp_obs is not None or cp_act is not None:
+        raise ValueError("imagine: this model has no context encoder, cp_obs / cp_act must be None")
+    try:
+        std = float(np.float32(noise_std))
+    except (TypeError, ValueError):
+        raise ValueError("imagine: noise_std must be a finite number >= 0, got %r" % (noise_std,)) from None
+    if isinstance(noise_std, bool) or not np.isfinite(std) or std < 0.0:
+        raise ValueError("imagine: noise_std must be a finite number >= 0, got %r" % (noise_std,))
+    if actions is not None and std != 0.0:
+        raise ValueError("imagine: noise_std perturbs the policy's actions; open-loop actions are taken as given")
+    w = disagreement_w
+    if isinstance(w, str):
+        if w != "delta_std":
+            raise ValueError("imagine: disagreement_w must be None, [D] numbers or 'delta_std', got %r" % (w,))
+    elif w is not None:
+        w = np.asarray(w, dtype=np.float32)
+        if w.shape != (D,) or not bool(np.all(np.isfinite(w) & (w >= 0.0))) or not bool(np.any(w > 0.0)):
+            raise ValueError("imagine: disagreement_w must be [%d] finite numbers >= 0 with at least one > 0" % D)
+    return ImagineArgs(m, n, k, std, w)
+
+
 class Shard:
     """Contiguous candidate shard of one rank."""
 

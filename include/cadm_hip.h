@@ -963,6 +963,51 @@ int cadm_discount_weights(cadm_ctx* ctx, float* host_out, int* set_out);
 int cadm_discount_returns(cadm_ctx* ctx, const float* traj, const float* obs, const float* actions, int m, int n, const float* rows_in,
                           float* rows_out, float* step_out, void* stream);
 
+/* Imagined rollouts for a learner (csrc/imagine.hip; no reference twin): n = branches independent model rollouts of k steps from each of
+ * m start states, recorded as transitions -- what MBPO / Dyna train an actor and critics on, with the per-transition ensemble
+ * disagreement MOPO / M2AC penalise or mask by.  Every step is ONE one-step rollout of the unchanged rollout kernels over [m,n,p] particle
+ * rows (k is independent of the ctx's horizon) under the even iteration word CADM_IMAGINE_IT + 2 t = 0xF00000 + 2 t -- above every planner
+ * iteration, below the proposal roll's 0xFA0000 --, so the head noise never repeats that of a plan, a roll or a forecast of the same
+ * (seed, call).  A row is (start state mi, branch j), row = mi * n + j; all of its p particles start step t from states[t,row] (step 0:
+ * obs[mi]), so every member predicts p / E times and one particle is kept (MBPO's scheme).  Per row and step t, in this order:
+ *   a_t   actions NULL: the registered policy net (cadm_set_policy_net) on states[t,row], exactly cadm_policy_eval's chain, then with
+ *         noise_std > 0  a_d = a_d + noise_std * xi_d  (one multiply, one add) on EVERY row, xi drawn as cadm_policy_propose draws it but
+ *         under counter (row, t, g, 7), then the clip;  actions [m,n,k,A]: a_t = fminf(fmaxf(actions[mi,j,t,:], lb), ub), no net is evaluated
+ *   sel   = (uint64(w0) * p) >> 32,  w0 = word 0 of Philox4x32-10 keyed (seed, call), counter (row, t, 0, 6);  member = sel / (p / E)
+ *   s'    = next[row,sel,:], the kept particle's post-step state;   r = rows1[row,sel], the rollout's own one-step return of that particle
+ *   u     = sum_d w_d v_d in ascending d from the first term, v_d the epistemic variance over the row's p particles exactly as
+ *         cadm_uncertainty_cost computes it (kind epistemic, form var, no cap; dims with w_d == 0 are not read); a non-finite u is +inf
+ *   alive, s' finite, healthy:      valid 1, done 0, states[t+1] = s'
+ *   alive, s' finite, not healthy:  valid 1, done 1, states[t+1] = s', the row is dead afterwards
+ *   alive, a value of s' NaN / inf: valid 0, done 0, rew 0, states[t+1] = states[t], the row is dead afterwards (member and u are recorded)
+ *   dead:                           valid 0, done 0, rew 0, member -1, u 0, states[t+1] = states[t]
+ *   healthy: s'[dim] > lo && s'[dim] < hi in float32 for every constraint (cadm_constrain_returns' test; only n, dim, lo, hi are read:
+ *   either mode defines termination here);  length[row] = the number of valid transitions.  A dead row's rollout still runs (static
+ *   shapes) from its frozen, finite state and is ignored.  A deterministic ctx draws no head noise and still draws sel.
+ * cadm_imagine_workspace_bytes: the bytes of `buffer`; offsets_out [CADM_IMAGINE_VIEWS] or NULL takes the byte offsets of the outputs in
+ * it, in this order: states [k+1,m,n,D] float, act [k,m,n,A] float, rew [k,m,n] float, done [k,m,n] uint8, valid [k,m,n] uint8, member
+ * [k,m,n] int32, disagreement [k,m,n] float, length [m,n] int32, alive [m,n] uint8 (the state machine's flag behind the last step); the
+ * chain's own views lie behind them.  Nothing is compacted: shapes are static.  0 for bad arguments.
+ * cadm_imagine: obs [m,D]; ctx_vec the context encoder's output for the m start states, NULL without one; disagreement NULL: w = 1 (only
+ * n_dims and w are read).  cadm_imagine_select: the stage between two rollouts alone, on the caller's next [rows,p,D], rows1 [rows,p],
+ * state [rows,D] (states[t]) and alive_io [rows]; sel_in [rows] or NULL replaces the draw (clamped to 0 .. p - 1); length_io [rows] or
+ * NULL is incremented by valid; bcast_out [rows,p,D] or NULL takes states[t+1] in every particle slot (it must not alias next).
+ * Determinism: every output is one thread's chain in the order above, no floating-point atomics, nothing depends on the grid or the
+ * group size: the same bits run to run, and at any row position for the same sel.
+ * Refusals, before any HIP call: CADM_EINVAL for null pointers, m, n or k < 1, a noise_std negative or not finite, a discrete ctx
+ * (cartpole), a candidate-sharded ctx, D > CADM_MAX_UNC_DIMS, a p * D tile beyond the stage's 48 KiB LDS budget, m * n * p rows beyond
+ * one rollout launch's 32-bit indexing, a num_cem_iters or a k whose last word leaves 0xF00000 .. 0xF9FFFE, what cadm_constrain_returns
+ * / cadm_uncertainty_cost refuse of their parameters; neither actions nor a registered policy net: CADM_ESTATE. */
+#define CADM_IMAGINE_VIEWS 9
+size_t cadm_imagine_workspace_bytes(cadm_ctx* ctx, int m, int n, int k, uint64_t* offsets_out);
+int cadm_imagine(cadm_ctx* ctx, const float* obs, const float* ctx_vec, const float* actions, int m, int n, int k, float noise_std,
+                 const cadm_constraint_params* constraints, const cadm_uncertainty_params* disagreement, uint32_t seed, uint32_t call,
+                 void* buffer, void* stream);
+int cadm_imagine_select(cadm_ctx* ctx, const float* next, const float* rows1, const float* state, const int32_t* sel_in, int rows, int t,
+                        const cadm_constraint_params* constraints, const cadm_uncertainty_params* disagreement, uint32_t seed,
+                        uint32_t call, uint8_t* alive_io, float* state_out, float* rew_out, uint8_t* done_out, uint8_t* valid_out,
+                        int32_t* member_out, float* disagreement_out, int32_t* length_io, float* bcast_out, void* stream);
+
 /* One training step =sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
