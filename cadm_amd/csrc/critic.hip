@@ -27,10 +27,14 @@
 // Reduction contract: a row's result is one column's chains in ascending k, behind one another in a fixed order: the same instruction
 // sequence wherever the row sits; no floating-point atomics; nothing depends on the grid, on RT, on m or n: the same bits run to run,
 // inside any batch, and from cadm_critic_eval as from the planner stage.
+// The host path around the kernel (description checks, registration, row tiles, launch) is mlp_chain.h's; what stands below is what
+// this net has of its own.
 #include "mlp_chain.h"
 
 namespace {
 
+// (Not built from MlpDev: with the actor's and the critics' halves embedded the fields move, and the launch of few rows, whose time is one
+// workgroup's latency, measured slower than with this order: profiles/mlp_host_refactor.md.)
 struct CriticArgs {
     const float* pW[MLP_NL];                       // the actor: packed, per layer
     const float* pb[MLP_NL];
@@ -56,8 +60,6 @@ struct CriticArgs {
     size_t total;
     int inp, region0, region1;                     // LDS floats of the critics' input tile and of the two activation regions
 };
-
-__device__ __forceinline__ bool critic_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
 template <int RT>
 __global__ __launch_bounds__(MLP_THREADS) void critic_kernel(const CriticArgs a) {
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(MLP_THREADS) void critic_kernel(const CriticArgs a)
         float xa = 0.0f, xc = 0.0f;
         if (k < D && flag[row] == 0) {
             const float v = a.x[(q0 + row) * D + k];
-            if (critic_nonfinite(v)) bad[row] = 1;               // (every writer stores the same 1)
+            if (mlp_nonfinite(v)) bad[row] = 1;               // (every writer stores the same 1)
             xc = (v - a.cmean[k]) * a.cistd[k];
             if (actor) xa = (v - a.pmean[k]) * a.pistd[k];
         }
@@ -95,6 +97,7 @@ __global__ __launch_bounds__(MLP_THREADS) void critic_kernel(const CriticArgs a)
     }
     __syncthreads();
     const float* xin = reg0;
+    // (both chains stand here and do not go through mlp_forward: this kernel's registers and branches came out differently with it)
     if (actor)
         for (int l = 0; l < a.pnl; ++l) {
             float* xout = (l & 1) ? reg0 : reg1;
@@ -111,14 +114,11 @@ __global__ __launch_bounds__(MLP_THREADS) void critic_kernel(const CriticArgs a)
             const size_t q = q0 + row;
             float v = 0.0f;
             if (actor) {
-                if (!bad[row]) {
-                    v = xin[d * R + mlp_swz<RT>(row, d)];
-                    if (a.squash == CADM_POLICY_TANH) v = __fadd_rn(a.mid, __fmul_rn(a.half, tanhf(v)));      // (one multiply, then one add: never an fma)
-                }
+                if (!bad[row]) v = mlp_squash(xin[d * R + mlp_swz<RT>(row, d)], a.squash, a.mid, a.half);
                 v = fminf(fmaxf(v, a.lb), a.ub);
             } else if (flag[row] == 0) {
                 v = a.actions[q * A + d];
-                if (critic_nonfinite(v)) bad[row] = 1;
+                if (mlp_nonfinite(v)) bad[row] = 1;
             }
             if (a.act_out) a.act_out[q * A + d] = v;
             if (flag[row] == 0) x = (v - a.cmean[k]) * a.cistd[k];
@@ -156,11 +156,7 @@ __global__ __launch_bounds__(MLP_THREADS) void critic_kernel(const CriticArgs a)
     }
 }
 
-void critic_dims(const cadm_ctx* ctx, const cadm_critic_params* p, int* dims) {
-    dims[0] = ctx->D + ctx->A;
-    for (int l = 0; l < p->n_hidden; ++l) dims[1 + l] = p->hidden[l];
-    dims[1 + p->n_hidden] = 1;
-}
+void critic_dims(const cadm_ctx* ctx, const cadm_critic_params* p, int* dims) { mlp_dims(mlp_shape(p), ctx->D + ctx->A, 1, dims); }
 
 // LDS of a workgroup with RT row tiles: the critics' input tile, two regions sized for the wider of the actor (pdims: its input tile and
 // every layer's outputs, the A sums of the output layer among them; null: no actor in the launch) and a critic (its hidden layers'
@@ -186,45 +182,27 @@ size_t critic_lds_bytes(const int* pdims, int pnl, const int* cdims, int cnl, in
 
 }  // namespace
 
-// the ctx-owned packed copies of the registered critics (every one carries the shared input statistics; critic 0's are read)
-struct CriticNets {
-    bool set = false;
-    MlpNet net[CADM_MAX_CRITICS];
-    cadm_critic_params prm{};      // what was registered (its weight is not used; its reduce is cadm_critic_eval's: a planner call brings both)
-};
+// the ctx-owned packed copies of the registered critics (every one carries the shared input statistics; critic 0's are read).  The
+// weight of its prm is not used; its reduce is cadm_critic_eval's: a planner call brings both
+struct CriticNets : MlpOwned<cadm_critic_params, CADM_MAX_CRITICS> {};
 
-void cadm_critic_free(cadm_ctx* ctx) {
-    if (!ctx->critic) return;
-    for (int c = 0; c < CADM_MAX_CRITICS; ++c) mlp_net_release(&ctx->critic->net[c]);
-    delete ctx->critic;
-    ctx->critic = nullptr;
-}
+void cadm_critic_free(cadm_ctx* ctx) { mlp_free(ctx->critic); }
 
 // the refusals of a description of critics, before any HIP call
 int cadm_critic_check(const cadm_ctx* ctx, const cadm_critic_params* p, const char* who) {
-    CADM_REQUIRE(p, "%s: the critic parameters are null", who);
-    CADM_REQUIRE(p->n_hidden >= 0 && p->n_hidden <= CADM_MAX_VALUE_LAYERS, "%s: %d hidden layers, outside 0 .. %d", who, p->n_hidden,
-                 CADM_MAX_VALUE_LAYERS);
-    for (int l = 0; l < p->n_hidden; ++l)
-        CADM_REQUIRE(p->hidden[l] >= 1 && p->hidden[l] <= CADM_MAX_VALUE_WIDTH, "%s: hidden layer %d has width %d, outside 1 .. %d", who, l,
-                     p->hidden[l], CADM_MAX_VALUE_WIDTH);
-    CADM_REQUIRE(p->activation == CADM_VALUE_RELU || p->activation == CADM_VALUE_TANH || p->activation == CADM_VALUE_SWISH,
-                 "%s: unknown critic activation %d", who, p->activation);
+    int rc;
+    if ((rc = mlp_shape_check(mlp_shape(p), "critic", who))) return rc;
     CADM_REQUIRE(p->n_critics >= 1 && p->n_critics <= CADM_MAX_CRITICS, "%s: %d critics, outside 1 .. %d", who, p->n_critics, CADM_MAX_CRITICS);
     CADM_REQUIRE(p->reduce == CADM_CRITIC_MIN || p->reduce == CADM_CRITIC_MEAN, "%s: unknown critic reduce %d", who, p->reduce);
     CADM_REQUIRE(isfinite(p->weight), "%s: the critic weight %g is not finite", who, (double)p->weight);
     CADM_REQUIRE(ctx->D <= CADM_MAX_VALUE_DIMS, "%s: D (%d) is beyond the critics' %d state dims", who, ctx->D, CADM_MAX_VALUE_DIMS);
     CADM_REQUIRE(ctx->A <= CADM_MAX_POLICY_ACTIONS, "%s: A (%d) is beyond the critics' %d action dims", who, ctx->A, CADM_MAX_POLICY_ACTIONS);
-    CADM_REQUIRE(!ctx->cfg.discrete && ctx->cfg.env_kind != CADM_ENV_CARTPOLE, "%s: a terminal Q needs a continuous-action ctx (discrete "
-                 "actions are planned by random shooting)", who);
-    CADM_REQUIRE(!cadm_sharded(ctx), "%s: a terminal Q is not supported on a candidate-sharded ctx", who);
-    int cdims[MLP_NL + 1], pdims[MLP_NL + 1];
+    if ((rc = mlp_ctx_check(ctx, "a terminal Q", who))) return rc;
+    int cdims[MLP_NL + 1];
     critic_dims(ctx, p, cdims);
-    const cadm_policy_params* pp = nullptr;
-    const bool actor = cadm_policy_registered(ctx, &pp) != nullptr;
-    if (actor) cadm_policy_net_dims(ctx, pp, pdims);
-    const size_t lds = critic_lds_bytes(actor ? pdims : nullptr, actor ? pp->n_hidden + 1 : 0, cdims, p->n_hidden + 1, p->n_critics, 1, nullptr,
-                                        nullptr, nullptr);
+    MlpDev pd{};
+    const bool actor = cadm_policy_dev(ctx, &pd, nullptr);
+    const size_t lds = critic_lds_bytes(actor ? pd.dims : nullptr, pd.nlayers, cdims, p->n_hidden + 1, p->n_critics, 1, nullptr, nullptr, nullptr);
     CADM_REQUIRE(lds <= (size_t)MLP_LDS_MAX, "%s: the critics' input tile and the activation tiles of actor and critics need %zu bytes of LDS "
                  "at one row tile, the bound is %d", who, lds, MLP_LDS_MAX);
     return CADM_OK;
@@ -232,16 +210,14 @@ int cadm_critic_check(const cadm_ctx* ctx, const cadm_critic_params* p, const ch
 
 // `p` must describe the registered critics; need_actor: and a policy net must be registered
 static int critic_match(const cadm_ctx* ctx, const cadm_critic_params* p, bool need_actor, const char* who) {
-    if (!ctx->critic || !ctx->critic->set) { cadm_set_error("%s: no critics are registered (call cadm_set_critic_nets)", who); return CADM_ESTATE; }
-    if (need_actor && !cadm_policy_registered(ctx, nullptr)) {
+    if (!mlp_registered(ctx->critic)) { cadm_set_error("%s: no critics are registered (call cadm_set_critic_nets)", who); return CADM_ESTATE; }
+    if (need_actor && !cadm_policy_dev(ctx, nullptr, nullptr)) {
         cadm_set_error("%s: no policy net is registered (call cadm_set_policy_net): the critics are evaluated at its action", who);
         return CADM_ESTATE;
     }
     if (!p) return CADM_OK;
     const cadm_critic_params& r = ctx->critic->prm;
-    bool same = p->n_hidden == r.n_hidden && p->activation == r.activation && p->n_critics == r.n_critics;
-    for (int l = 0; same && l < p->n_hidden; ++l) same = p->hidden[l] == r.hidden[l];
-    CADM_REQUIRE(same, "%s: the critic parameters do not describe the registered critics (count, layers, widths or activation differ)", who);
+    CADM_REQUIRE(p->n_critics == r.n_critics && mlp_shape_same(mlp_shape(p), mlp_shape(&r)), "%s: the critic parameters do not describe the registered critics (count, layers, widths or activation differ)", who);
     return CADM_OK;
 }
 
@@ -260,44 +236,33 @@ static int critic_launch(cadm_ctx* ctx, int reduce, float weight, const float* x
     critic_dims(ctx, &nets.prm, a.cdims);
     a.cnl = nets.prm.n_hidden + 1;
     a.cact = nets.prm.activation;
+    a.cmean = nets.net[0].mean; a.cistd = nets.net[0].istd;
     a.C = nets.prm.n_critics;
     a.reduce = reduce;
     for (int c = 0; c < a.C; ++c)
         for (int l = 0; l < a.cnl; ++l) { a.cW[c][l] = nets.net[c].W[l]; a.cb[c][l] = nets.net[c].b[l]; }
-    a.cmean = nets.net[0].mean; a.cistd = nets.net[0].istd;
     const bool actor = actions == nullptr;
-    a.pdims[0] = ctx->D; a.pdims[1] = ctx->A; a.pnl = 1;         // (the kernel reads D and A from the two sets of dims)
+    a.pdims[0] = ctx->D; a.pdims[1] = ctx->A; a.pnl = 1; // (the kernel reads D and A from the two sets of dims)
     if (actor) {
-        const cadm_policy_params* pp = nullptr;
-        const MlpNet* pn = cadm_policy_registered(ctx, &pp);
-        cadm_policy_net_dims(ctx, pp, a.pdims);
-        a.pnl = pp->n_hidden + 1;
-        a.pact = pp->activation;
-        a.squash = pp->squash;
-        for (int l = 0; l < a.pnl; ++l) { a.pW[l] = pn->W[l]; a.pb[l] = pn->b[l]; }
-        a.pmean = pn->mean; a.pistd = pn->istd;
+        MlpDev pd{};
+        cadm_policy_dev(ctx, &pd, &a.squash);                    // (registered: critic_match has asked)
+        for (int l = 0; l < pd.nlayers; ++l) { a.pW[l] = pd.W[l]; a.pb[l] = pd.b[l]; a.pdims[l + 1] = pd.dims[l + 1]; }
+        a.pnl = pd.nlayers; a.pact = pd.act; a.pmean = pd.mean; a.pistd = pd.istd;
     }
     a.lb = ctx->cfg.lower_bound; a.ub = ctx->cfg.upper_bound;
     a.mid = 0.5f * (a.ub + a.lb); a.half = 0.5f * (a.ub - a.lb);
     a.x = x; a.actions = actions; a.first = first; a.H = ctx->H; a.rows_in = rows_in; a.rows_out = rows_out; a.q_out = q_out; a.q_each = q_each;
     a.act_out = act_out; a.weight = weight; a.total = total;
-    // two row tiles halve the weight stream per row; one tile keeps every CU busy while the rows are few
-    int RT = (total + 15) / 16 > 2 * (size_t)ctx->n_cus ? 2 : 1;
+    // two row tiles where the rows are many (mlp_many_tiles) and their LDS fits; else one
+    int RT = mlp_many_tiles(ctx, total) ? 2 : 1;
     size_t lds = critic_lds_bytes(actor ? a.pdims : nullptr, a.pnl, a.cdims, a.cnl, a.C, RT, &a.inp, &a.region0, &a.region1);
-    if (lds > (size_t)MLP_LDS_MAX) { RT = 1; lds = critic_lds_bytes(actor ? a.pdims : nullptr, a.pnl, a.cdims, a.cnl, a.C, RT, &a.inp, &a.region0, &a.region1); }
+    if (lds > (size_t)MLP_LDS_MAX) {
+        RT = 1;
+        lds = critic_lds_bytes(actor ? a.pdims : nullptr, a.pnl, a.cdims, a.cnl, a.C, RT, &a.inp, &a.region0, &a.region1);
+    }
     CADM_REQUIRE(lds <= (size_t)MLP_LDS_MAX, "%s: the critics' input tile and the activation tiles of actor and critics need %zu bytes of LDS "
                  "at one row tile, the bound is %d", who, lds, MLP_LDS_MAX);
-    const size_t R = 16 * (size_t)RT, blocks = (total + R - 1) / R;
-    CADM_REQUIRE(blocks <= 0x7fffffffull, "%s: %zu rows are too many for one launch", who, total);
-    const void* fn = RT == 2 ? reinterpret_cast<const void*>(&critic_kernel<2>) : reinterpret_cast<const void*>(&critic_kernel<1>);
-    if (lds > 64 * 1024 && !ctx->attr_done.count(fn)) {
-        CADM_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_MAX));
-        ctx->attr_done.insert(fn);
-    }
-    if (RT == 2) hipLaunchKernelGGL(critic_kernel<2>, dim3((unsigned)blocks), dim3(MLP_THREADS), lds, s, a);
-    else hipLaunchKernelGGL(critic_kernel<1>, dim3((unsigned)blocks), dim3(MLP_THREADS), lds, s, a);
-    CADM_CHECK_HIP(hipGetLastError());
-    return CADM_OK;
+    return mlp_launch(ctx, critic_kernel<1>, critic_kernel<2>, RT, lds, total, a, s, who);
 }
 
 // the planner's stage: rows [m, n, p] in place, behind a rollout's traj [H, m, n, p, D] (n the PACKED candidate count)
@@ -310,31 +275,15 @@ int cadm_launch_critic(cadm_ctx* ctx, const cadm_critic_params* p, const float* 
 
 extern "C" int cadm_set_critic_nets(cadm_ctx* ctx, const cadm_critic_params* params, const float* const* W, const float* const* b,
                                     const float* mean, const float* std_inv, void* stream) {
-    CADM_REQUIRE(ctx, "cadm_set_critic_nets: ctx is null");
-    if (!params) {
-        if (ctx->critic) ctx->critic->set = false;
-        return CADM_OK;
-    }
+    const char* who = "cadm_set_critic_nets";
+    CADM_REQUIRE(ctx, "%s: ctx is null", who);
+    if (!params) { mlp_clear(ctx->critic); return CADM_OK; }
     int rc;
-    if ((rc = cadm_critic_check(ctx, params, "cadm_set_critic_nets"))) return rc;
-    CADM_REQUIRE(W && b && mean && std_inv, "cadm_set_critic_nets: W / b / mean / std_inv is null");
-    const int nl = params->n_hidden + 1, C = params->n_critics;
-    for (int i = 0; i < C * nl; ++i)
-        CADM_REQUIRE(W[i] && b[i], "cadm_set_critic_nets: the weights or the biases of layer %d of critic %d are null", i % nl, i / nl);
+    if ((rc = cadm_critic_check(ctx, params, who))) return rc;
     int dims[MLP_NL + 1];
     critic_dims(ctx, params, dims);
-    CADM_ON_DEVICE(ctx);
-    if (!ctx->critic) {
-        ctx->critic = new (std::nothrow) CriticNets();
-        if (!ctx->critic) { cadm_set_error("cadm_set_critic_nets: out of host memory"); return CADM_ENOMEM; }
-    }
-    CriticNets& nets = *ctx->critic;
-    nets.set = false;
-    for (int c = 0; c < C; ++c)
-        if ((rc = mlp_net_upload(nets.net[c], dims, nl, W + (size_t)c * nl, b + (size_t)c * nl, mean, std_inv, (hipStream_t)stream,
-                                 "cadm_set_critic_nets"))) return rc;
-    nets.prm = *params;
-    nets.set = true;
+    if ((rc = mlp_register(ctx, ctx->critic, params->n_critics, "critic", dims, params->n_hidden + 1, W, b, mean, std_inv, stream, who))) return rc;
+    ctx->critic->prm = *params;
     return CADM_OK;
 }
 

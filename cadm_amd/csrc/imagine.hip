@@ -343,7 +343,7 @@ extern "C" int cadm_imagine(cadm_ctx* ctx, const float* obs, const float* ctx_ve
     if ((rc = cadm_imagine_check(ctx, m, n, k, constraints, disagreement, who))) return rc;
     CADM_REQUIRE(isfinite(noise_std) && noise_std >= 0.0f, "%s: noise_std %g is negative or not finite", who, (double)noise_std);
     CADM_REQUIRE(ctx->C == 0 || ctx_vec, "%s: ctx_vec required for a context model", who);
-    if (!actions && !cadm_policy_registered(ctx, nullptr)) {
+    if (!actions && !cadm_policy_dev(ctx, nullptr, nullptr)) {
         cadm_set_error("%s: neither actions nor a registered policy net (call cadm_set_policy_net)", who);
         return CADM_ESTATE;
     }

@@ -133,11 +133,10 @@ int cadm_launch_policy_propose(cadm_ctx* ctx, const cadm_policy_params* policy, 
 // (counter (row, t, g, stream)), clipped.  noise_std == 0: the launch of cadm_policy_eval.
 int cadm_launch_policy_step(cadm_ctx* ctx, const float* x, size_t total, int t, float noise_std, uint32_t seed, uint32_t call,
                             uint32_t stream_word, float* a1, hipStream_t s, const char* who);
-// policy.hip, for critic.hip: the packed copy (mlp_chain.h) and the description of the registered policy net, null while none is
-// registered; and the net's dims D, h_1 .. h_L, A
-struct MlpNet;
-const MlpNet* cadm_policy_registered(const cadm_ctx* ctx, const cadm_policy_params** prm);
-void cadm_policy_net_dims(const cadm_ctx* ctx, const cadm_policy_params* policy, int* dims);
+// policy.hip, for critic.hip and imagine.hip: false while no policy net is registered; else `d` (or null) receives the net's half of a
+// kernel's arguments (mlp_chain.h) and `squash` (or null) its squash
+struct MlpDev;
+bool cadm_policy_dev(const cadm_ctx* ctx, MlpDev* d, int* squash);
 // critic.hip: the refusals of a terminal Q (null parameters, a layer count outside 0 .. 4, a width outside 1 .. 512, an unknown
 // activation or reduce, a critic count outside 1 .. 5, a weight that is not finite, D or A beyond the nets' dims, a discrete / sharded
 // ctx, the input tile and the activation tiles beyond the LDS; no registered critics or no registered policy net: CADM_ESTATE;

@@ -24,20 +24,17 @@
 // A <= 64 sums in LDS, from where the epilogue squashes, perturbs, clips and stores.
 // Reduction contract: a row's action is one column's chain in ascending k behind a sequential particle sum; no floating-point atomics;
 // nothing depends on the grid, on RT, on m or P: the same bits run to run, wherever the row sits, from cadm_policy_eval as from the roll.
+// The host path around the kernel (description checks, registration, row tiles, launch) is mlp_chain.h's; what stands below is what
+// this net has of its own.
 #include "mlp_chain.h"
 
 namespace {
 
 struct PolicyArgs {
-    const float* W[MLP_NL];        // packed, per layer
-    const float* b[MLP_NL];        // padded to 64 units
-    int dims[MLP_NL + 1];          // D, h_1 .. h_L, A
-    int nlayers;                   // dense layers including the output
-    int act, squash;
-    const float *mean, *istd;      // [D]
+    MlpDev net;                    // D -> h_1 .. h_L -> A
     const float* obs;              // [m, D]: the state of every row of env mi (t == 0), or null
     const float* x;                // [total, p, D]: the particle states of the rows (t >= 1; cadm_policy_eval: p = 1), or null
-    int P, p, t, H;
+    int squash, P, p, t, H;        // (squash behind the pointers: mean, istd, obs and x stay adjacent, one scalar load)
     float lb, ub, mid, half, noise_std;
     uint32_t seed, call;
     float* seqs;                   // [total, H, A] or null: a_t goes to [q, t, :]
@@ -48,8 +45,6 @@ struct PolicyArgs {
     int all_rows;                  // 1: row j == 0 is perturbed like the others (imagine.hip); 0: sequence 0 never gets noise
     uint32_t stream;               // the stream word of xi: CADM_STREAM_POLICY for the proposals
 };
-
-__device__ __forceinline__ bool policy_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
 template <int RT>
 __global__ __launch_bounds__(MLP_THREADS) void policy_step_kernel(const PolicyArgs a) {
@@ -64,7 +59,7 @@ __global__ __launch_bounds__(MLP_THREADS) void policy_step_kernel(const PolicyAr
     if (tid < R) bad[tid] = 0;
     __syncthreads();
     // the input tile [k][row]: the state estimate, normalised on the way in; rows behind the batch and the k behind D are zeros
-    const int D = a.dims[0], D4 = (D + 3) & ~3;
+    const int D = a.net.dims[0], D4 = (D + 3) & ~3;
     for (int idx = tid; idx < R * D4; idx += MLP_THREADS) {
         const int row = idx / D4, k = idx - row * D4;
         float x = 0.0f;
@@ -74,36 +69,30 @@ __global__ __launch_bounds__(MLP_THREADS) void policy_step_kernel(const PolicyAr
             bool nf;
             if (a.obs) {
                 est = a.obs[(q / a.P) * D + k];
-                nf = policy_nonfinite(est);
+                nf = mlp_nonfinite(est);
                 if (a.states)
                     for (int j = 0; j < a.p; ++j) a.states[(q * a.p + j) * D + k] = est;
             } else {
                 const float* xp = a.x + q * a.p * D + k;
                 float s = xp[0];
-                nf = policy_nonfinite(s);
+                nf = mlp_nonfinite(s);
                 if (a.states) a.states[q * a.p * D + k] = s;
                 for (int j = 1; j < a.p; ++j) {
                     const float v = xp[(size_t)j * D];
-                    nf = nf || policy_nonfinite(v);
+                    nf = nf || mlp_nonfinite(v);
                     if (a.states) a.states[(q * a.p + j) * D + k] = v;
                     s = __fadd_rn(s, v);
                 }
                 est = a.p > 1 ? __fdiv_rn(s, (float)a.p) : s;
             }
             if (nf) bad[row] = 1;                                // (every writer stores the same 1)
-            x = (est - a.mean[k]) * a.istd[k];
+            x = (est - a.net.mean[k]) * a.net.istd[k];
         }
         reg0[k * R + mlp_swz<RT>(row, k)] = x;
     }
     __syncthreads();
-    const float* xin = reg0;
-    for (int l = 0; l < a.nlayers; ++l) {
-        float* xout = (l & 1) ? reg0 : reg1;
-        mlp_layer<RT>(a.W[l], a.b[l], a.dims[l], a.dims[l + 1], l + 1 == a.nlayers ? MLP_ACT_NONE : a.act, false, xin, xout, nullptr, wave, lane);
-        __syncthreads();
-        xin = xout;
-    }
-    const int A = a.dims[a.nlayers];
+    const float* xin = mlp_forward<RT>(a.net, false, reg0, reg1, reg0, nullptr, wave, lane);
+    const int A = a.net.dims[a.net.nlayers];
     for (int idx = tid; idx < rows * A; idx += MLP_THREADS) {
         const int row = idx / A, d = idx - row * A;
         const size_t q = q0 + row;
@@ -111,8 +100,7 @@ __global__ __launch_bounds__(MLP_THREADS) void policy_step_kernel(const PolicyAr
         if (bad[row]) {
             v = 0.0f;
         } else {
-            v = xin[d * R + mlp_swz<RT>(row, d)];
-            if (a.squash == CADM_POLICY_TANH) v = __fadd_rn(a.mid, __fmul_rn(a.half, tanhf(v)));      // (one multiply, then one add: never an fma)
+            v = mlp_squash(xin[d * R + mlp_swz<RT>(row, d)], a.squash, a.mid, a.half);
             if (a.noise_std > 0.0f && (a.all_rows || q % a.P != 0)) {
                 uint32_t r[4];
                 philox4x32_10((uint32_t)q, (uint32_t)a.t, (uint32_t)(d >> 2), a.stream, a.seed, a.call, r);
@@ -133,11 +121,7 @@ size_t policy_lds_bytes(const int* dims, int nlayers, int RT, int* region0, int*
     return (mlp_region_floats(dims, nlayers + 1, RT, region0, region1) + 16 * (size_t)RT) * sizeof(float);
 }
 
-void policy_dims(const cadm_ctx* ctx, const cadm_policy_params* p, int* dims) {
-    dims[0] = ctx->D;
-    for (int l = 0; l < p->n_hidden; ++l) dims[1 + l] = p->hidden[l];
-    dims[1 + p->n_hidden] = ctx->A;
-}
+void policy_dims(const cadm_ctx* ctx, const cadm_policy_params* p, int* dims) { mlp_dims(mlp_shape(p), ctx->D, ctx->A, dims); }
 
 struct PolicyWs { float *a1, *rows1, *cur, *next; };
 
@@ -154,37 +138,24 @@ size_t policy_carve(const cadm_ctx* ctx, int m, int P, char* base, PolicyWs* w) 
 
 }  // namespace
 
-// the ctx-owned packed copy of the registered net
-struct PolicyNet : MlpNet {
-    cadm_policy_params prm{};      // what was registered (n_samples and noise_std are not used: every call brings its own)
-};
+// the ctx-owned packed copy of the registered net (n_samples and noise_std of its prm are not used: every call brings its own)
+struct PolicyNet : MlpOwned<cadm_policy_params> {};
 
-void cadm_policy_free(cadm_ctx* ctx) {
-    if (!ctx->policy) return;
-    mlp_net_release(ctx->policy);
-    delete ctx->policy;
-    ctx->policy = nullptr;
+void cadm_policy_free(cadm_ctx* ctx) { mlp_free(ctx->policy); }
+
+// false while no net is registered; else the registered net D -> h_1 .. h_L -> A as its half of a kernel's arguments and its squash,
+// where asked for (critic.hip's actor reads both)
+bool cadm_policy_dev(const cadm_ctx* ctx, MlpDev* d, int* squash) {
+    if (!mlp_registered(ctx->policy)) return false;
+    if (d) mlp_dev(*d, ctx->policy->net[0], mlp_shape(&ctx->policy->prm), ctx->D, ctx->A);
+    if (squash) *squash = ctx->policy->prm.squash;
+    return true;
 }
-
-// what critic.hip reads of the registered net: its packed copy and its description, null while none is registered; and its dims
-const MlpNet* cadm_policy_registered(const cadm_ctx* ctx, const cadm_policy_params** prm) {
-    if (!ctx->policy || !ctx->policy->set) return nullptr;
-    if (prm) *prm = &ctx->policy->prm;
-    return ctx->policy;
-}
-
-void cadm_policy_net_dims(const cadm_ctx* ctx, const cadm_policy_params* p, int* dims) { policy_dims(ctx, p, dims); }
 
 // the refusals of a policy net's description, before any HIP call
 int cadm_policy_check(const cadm_ctx* ctx, const cadm_policy_params* p, const char* who) {
-    CADM_REQUIRE(p, "%s: the policy parameters are null", who);
-    CADM_REQUIRE(p->n_hidden >= 0 && p->n_hidden <= CADM_MAX_VALUE_LAYERS, "%s: %d hidden layers, outside 0 .. %d", who, p->n_hidden,
-                 CADM_MAX_VALUE_LAYERS);
-    for (int l = 0; l < p->n_hidden; ++l)
-        CADM_REQUIRE(p->hidden[l] >= 1 && p->hidden[l] <= CADM_MAX_VALUE_WIDTH, "%s: hidden layer %d has width %d, outside 1 .. %d", who, l,
-                     p->hidden[l], CADM_MAX_VALUE_WIDTH);
-    CADM_REQUIRE(p->activation == CADM_VALUE_RELU || p->activation == CADM_VALUE_TANH || p->activation == CADM_VALUE_SWISH,
-                 "%s: unknown policy activation %d", who, p->activation);
+    int rc;
+    if ((rc = mlp_shape_check(mlp_shape(p), "policy", who))) return rc;
     CADM_REQUIRE(p->squash == CADM_POLICY_NONE || p->squash == CADM_POLICY_TANH, "%s: unknown policy squash %d", who, p->squash);
     CADM_REQUIRE(p->n_samples >= 1, "%s: n_samples must be >= 1 (got %d)", who, p->n_samples);
     CADM_REQUIRE(isfinite(p->noise_std) && p->noise_std >= 0.0f, "%s: the policy noise_std %g is negative or not finite", who,
@@ -192,9 +163,7 @@ int cadm_policy_check(const cadm_ctx* ctx, const cadm_policy_params* p, const ch
     CADM_REQUIRE(ctx->D <= CADM_MAX_VALUE_DIMS, "%s: D (%d) is beyond the policy net's %d input dims", who, ctx->D, CADM_MAX_VALUE_DIMS);
     CADM_REQUIRE(ctx->A <= CADM_MAX_POLICY_ACTIONS, "%s: A (%d) is beyond the policy net's %d action dims", who, ctx->A,
                  CADM_MAX_POLICY_ACTIONS);
-    CADM_REQUIRE(!ctx->cfg.discrete && ctx->cfg.env_kind != CADM_ENV_CARTPOLE, "%s: a policy prior needs a continuous-action ctx (discrete "
-                 "actions are planned by random shooting)", who);
-    CADM_REQUIRE(!cadm_sharded(ctx), "%s: a policy prior is not supported on a candidate-sharded ctx", who);
+    if ((rc = mlp_ctx_check(ctx, "a policy prior", who))) return rc;
     int dims[MLP_NL + 1];
     policy_dims(ctx, p, dims);
     const size_t lds = policy_lds_bytes(dims, p->n_hidden + 1, 1, nullptr, nullptr);
@@ -205,11 +174,9 @@ int cadm_policy_check(const cadm_ctx* ctx, const cadm_policy_params* p, const ch
 
 // `p` must describe the registered net
 static int policy_match(const cadm_ctx* ctx, const cadm_policy_params* p, const char* who) {
-    if (!ctx->policy || !ctx->policy->set) { cadm_set_error("%s: no policy net is registered (call cadm_set_policy_net)", who); return CADM_ESTATE; }
+    if (!mlp_registered(ctx->policy)) { cadm_set_error("%s: no policy net is registered (call cadm_set_policy_net)", who); return CADM_ESTATE; }
     const cadm_policy_params& r = ctx->policy->prm;
-    bool same = p->n_hidden == r.n_hidden && p->activation == r.activation && p->squash == r.squash;
-    for (int l = 0; same && l < p->n_hidden; ++l) same = p->hidden[l] == r.hidden[l];
-    CADM_REQUIRE(same, "%s: the policy parameters do not describe the registered net (layers, widths, activation or squash differ)", who);
+    CADM_REQUIRE(p->squash == r.squash && mlp_shape_same(mlp_shape(p), mlp_shape(&r)), "%s: the policy parameters do not describe the registered net (layers, widths, activation or squash differ)", who);
     return CADM_OK;
 }
 
@@ -226,35 +193,20 @@ int cadm_policy_plan_check(const cadm_ctx* ctx, const cadm_policy_params* p, con
 static int policy_launch(cadm_ctx* ctx, const float* obs, const float* x, int P, int p, int t, float noise_std, uint32_t seed, uint32_t call,
                          float* seqs, float* a1, float* states, size_t total, hipStream_t s, const char* who, int all_rows = 0,
                          uint32_t stream_word = CADM_STREAM_POLICY) {
-    const PolicyNet& net = *ctx->policy;
     PolicyArgs a{};
-    policy_dims(ctx, &net.prm, a.dims);
-    a.nlayers = net.prm.n_hidden + 1;
-    a.act = net.prm.activation;
-    a.squash = net.prm.squash;
-    for (int l = 0; l < a.nlayers; ++l) { a.W[l] = net.W[l]; a.b[l] = net.b[l]; }
-    a.mean = net.mean; a.istd = net.istd;
+    cadm_policy_dev(ctx, &a.net, &a.squash);
     a.obs = obs; a.x = x; a.P = P; a.p = p; a.t = t; a.H = ctx->H;
     a.lb = ctx->cfg.lower_bound; a.ub = ctx->cfg.upper_bound;
     a.mid = 0.5f * (a.ub + a.lb); a.half = 0.5f * (a.ub - a.lb);
     a.noise_std = noise_std; a.seed = seed; a.call = call;
     a.all_rows = all_rows; a.stream = stream_word;
     a.seqs = seqs; a.a1 = a1; a.states = states; a.total = total;
-    // two row tiles halve the weight stream per row; one tile keeps every CU busy while the rows are few
-    int RT = (total + 15) / 16 > 2 * (size_t)ctx->n_cus ? 2 : 1;
-    size_t lds = policy_lds_bytes(a.dims, a.nlayers, RT, &a.region0, &a.region1);
-    if (lds > (size_t)MLP_LDS_MAX) { RT = 1; lds = policy_lds_bytes(a.dims, a.nlayers, RT, &a.region0, &a.region1); }
-    const size_t R = 16 * (size_t)RT, blocks = (total + R - 1) / R;
-    CADM_REQUIRE(blocks <= 0x7fffffffull && total <= 0xffffffffull, "%s: %zu rows are too many for one launch", who, total);
-    const void* fn = RT == 2 ? reinterpret_cast<const void*>(&policy_step_kernel<2>) : reinterpret_cast<const void*>(&policy_step_kernel<1>);
-    if (lds > 64 * 1024 && !ctx->attr_done.count(fn)) {
-        CADM_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_MAX));
-        ctx->attr_done.insert(fn);
-    }
-    if (RT == 2) hipLaunchKernelGGL(policy_step_kernel<2>, dim3((unsigned)blocks), dim3(MLP_THREADS), lds, s, a);
-    else hipLaunchKernelGGL(policy_step_kernel<1>, dim3((unsigned)blocks), dim3(MLP_THREADS), lds, s, a);
-    CADM_CHECK_HIP(hipGetLastError());
-    return CADM_OK;
+    // two row tiles where the rows are many (mlp_many_tiles) and their LDS fits; else one
+    int RT = mlp_many_tiles(ctx, total) ? 2 : 1;
+    size_t lds = policy_lds_bytes(a.net.dims, a.net.nlayers, RT, &a.region0, &a.region1);
+    if (lds > (size_t)MLP_LDS_MAX) { RT = 1; lds = policy_lds_bytes(a.net.dims, a.net.nlayers, RT, &a.region0, &a.region1); }
+    CADM_REQUIRE(total <= 0xffffffffull, "%s: %zu rows are too many for one launch", who, total);      // (xi's Philox counter takes the row)
+    return mlp_launch(ctx, policy_step_kernel<1>, policy_step_kernel<2>, RT, lds, total, a, s, who);
 }
 
 // the roll: H policy steps and H - 1 one-step rollouts; nothing is evaluated behind the last action.  Every one-step rollout runs under
@@ -284,39 +236,28 @@ int cadm_launch_policy_propose(cadm_ctx* ctx, const cadm_policy_params* prm, con
 // imagine.hip's step: the registered net on one state per row (cadm_policy_eval's launch), every row perturbed under `stream_word`
 int cadm_launch_policy_step(cadm_ctx* ctx, const float* x, size_t total, int t, float noise_std, uint32_t seed, uint32_t call,
                             uint32_t stream_word, float* a1, hipStream_t s, const char* who) {
-    if (!ctx->policy || !ctx->policy->set) { cadm_set_error("%s: no policy net is registered (call cadm_set_policy_net)", who); return CADM_ESTATE; }
+    if (!mlp_registered(ctx->policy)) { cadm_set_error("%s: no policy net is registered (call cadm_set_policy_net)", who); return CADM_ESTATE; }
     return policy_launch(ctx, nullptr, x, 1, 1, t, noise_std, seed, call, nullptr, a1, nullptr, total, s, who, 1, stream_word);
 }
 
 extern "C" int cadm_set_policy_net(cadm_ctx* ctx, const cadm_policy_params* params, const float* const* W, const float* const* b,
                                    const float* mean, const float* std_inv, void* stream) {
-    CADM_REQUIRE(ctx, "cadm_set_policy_net: ctx is null");
-    if (!params) {
-        if (ctx->policy) ctx->policy->set = false;
-        return CADM_OK;
-    }
+    const char* who = "cadm_set_policy_net";
+    CADM_REQUIRE(ctx, "%s: ctx is null", who);
+    if (!params) { mlp_clear(ctx->policy); return CADM_OK; }
     int rc;
-    if ((rc = cadm_policy_check(ctx, params, "cadm_set_policy_net"))) return rc;
-    CADM_REQUIRE(W && b && mean && std_inv, "cadm_set_policy_net: W / b / mean / std_inv is null");
-    const int nl = params->n_hidden + 1;
-    for (int l = 0; l < nl; ++l) CADM_REQUIRE(W[l] && b[l], "cadm_set_policy_net: the weights or the biases of layer %d are null", l);
+    if ((rc = cadm_policy_check(ctx, params, who))) return rc;
     int dims[MLP_NL + 1];
     policy_dims(ctx, params, dims);
-    CADM_ON_DEVICE(ctx);
-    if (!ctx->policy) {
-        ctx->policy = new (std::nothrow) PolicyNet();
-        if (!ctx->policy) { cadm_set_error("cadm_set_policy_net: out of host memory"); return CADM_ENOMEM; }
-    }
-    PolicyNet& net = *ctx->policy;
-    if ((rc = mlp_net_upload(net, dims, nl, W, b, mean, std_inv, (hipStream_t)stream, "cadm_set_policy_net"))) return rc;
-    net.prm = *params;
+    if ((rc = mlp_register(ctx, ctx->policy, 1, nullptr, dims, params->n_hidden + 1, W, b, mean, std_inv, stream, who))) return rc;
+    ctx->policy->prm = *params;
     return CADM_OK;
 }
 
 extern "C" int cadm_policy_eval(cadm_ctx* ctx, const float* states, int R, float* act_out, void* stream) {
     CADM_REQUIRE(ctx && states && act_out, "cadm_policy_eval: ctx / states / act_out is null");
     CADM_REQUIRE(R >= 1, "cadm_policy_eval: R must be >= 1 (got %d)", R);
-    if (!ctx->policy || !ctx->policy->set) { cadm_set_error("cadm_policy_eval: no policy net is registered (call cadm_set_policy_net)"); return CADM_ESTATE; }
+    if (!mlp_registered(ctx->policy)) { cadm_set_error("cadm_policy_eval: no policy net is registered (call cadm_set_policy_net)"); return CADM_ESTATE; }
     CADM_ON_DEVICE(ctx);
     return policy_launch(ctx, nullptr, states, 1, 1, 0, 0.0f, 0, 0, nullptr, act_out, nullptr, (size_t)R, (hipStream_t)stream, "cadm_policy_eval");
 }

@@ -39,17 +39,14 @@
 // Reduction contract: R(t, q) is one column's chain in ascending k, the same instruction sequence wherever the row sits; the step sum is
 // sequential in t per row; no floating-point atomics; nothing depends on the grid, on RT, on m, n or p: the same bits run to run, inside
 // any batch, and from cadm_reward_eval as from the planner stage.
+// The host path around the kernel (description checks, registration, row tiles, launch) is mlp_chain.h's; what stands below is what
+// this net has of its own.
 #include "mlp_chain.h"
 
 namespace {
 
 struct RewardArgs {
-    const float* W[MLP_NL];        // packed, per layer
-    const float* b[MLP_NL];        // padded to 64 units
-    int dims[MLP_NL + 1];          // K, h_1 .. h_L, 1
-    int nlayers;                   // dense layers including the output
-    int act;
-    const float *mean, *istd;      // [K]
+    MlpDev net;                    // K -> h_1 .. h_L -> 1
     const float* x;                // cadm_reward_eval: [rows, K] concatenated inputs; else null
     const float *traj, *obs, *actions;      // [H, m, n, p, D], [m, D], [m, n, H, A]
     const int32_t* first;          // [m, n, p] or null
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(MLP_THREADS) void reward_kernel(const RewardArgs a)
     }
     __syncthreads();
     // the input tile [k][row], gathered and normalised on the way in; rows that are not evaluated and the k behind K are zeros
-    const int K = a.dims[0], K4 = (K + 3) & ~3, D = a.D, DA = a.D + a.A;
+    const int K = a.net.dims[0], K4 = (K + 3) & ~3, D = a.D, DA = a.D + a.A;
     for (int idx = tid; idx < R * K4; idx += MLP_THREADS) {
         const int row = idx / K4, k = idx - row * K4;
         float x = 0.0f;
@@ -107,19 +104,13 @@ __global__ __launch_bounds__(MLP_THREADS) void reward_kernel(const RewardArgs a)
             else if (k < D) v = sp[row][k];
             else if (k < DA) v = ap[row][k - D];
             else v = a.traj[(e0 + row) * D + (k - DA)];
-            if ((__float_as_uint(v) & 0x7f800000u) == 0x7f800000u) bad[row] = 1;      // (every writer stores the same 1)
-            x = (v - a.mean[k]) * a.istd[k];
+            if (mlp_nonfinite(v)) bad[row] = 1;                  // (every writer stores the same 1)
+            x = (v - a.net.mean[k]) * a.net.istd[k];
         }
         reg0[k * R + mlp_swz<RT>(row, k)] = x;
     }
     __syncthreads();
-    const float* xin = reg0;
-    for (int l = 0; l < a.nlayers; ++l) {
-        float* xout = (l & 1) ? reg0 : reg1;
-        mlp_layer<RT>(a.W[l], a.b[l], a.dims[l], a.dims[l + 1], a.act, l + 1 == a.nlayers, xin, xout, vres, wave, lane);
-        __syncthreads();
-        xin = xout;
-    }
+    mlp_forward<RT>(a.net, true, reg0, reg1, reg0, vres, wave, lane);
     if (tid >= rows) return;
     a.r_out[e0 + tid] = (flag[tid] == 1 || bad[tid]) ? __uint_as_float(0x7fc00000u) : vres[tid];
 }
@@ -155,46 +146,25 @@ int reward_K(const cadm_ctx* ctx, int inputs) {
     return inputs == CADM_REWARD_NEXT_OBS ? ctx->D : inputs == CADM_REWARD_OBS_ACT ? ctx->D + ctx->A : 2 * ctx->D + ctx->A;
 }
 
-void reward_dims(const cadm_ctx* ctx, const cadm_reward_params* p, int* dims) {
-    dims[0] = reward_K(ctx, p->inputs);
-    for (int l = 0; l < p->n_hidden; ++l) dims[1 + l] = p->hidden[l];
-    dims[1 + p->n_hidden] = 1;
-}
-
 }  // namespace
 
-// the ctx-owned packed copy of the registered net
-struct RewardNet : MlpNet {
-    cadm_reward_params prm{};      // what was registered (its weight is not used: every call brings its own)
-};
+// the ctx-owned packed copy of the registered net (the weight of its prm is not used: every call brings its own)
+struct RewardNet : MlpOwned<cadm_reward_params> {};
 
-void cadm_reward_free(cadm_ctx* ctx) {
-    if (!ctx->reward) return;
-    mlp_net_release(ctx->reward);
-    delete ctx->reward;
-    ctx->reward = nullptr;
-}
+void cadm_reward_free(cadm_ctx* ctx) { mlp_free(ctx->reward); }
 
 // the refusals of a reward net's description, before any HIP call
 static int reward_check(const cadm_ctx* ctx, const cadm_reward_params* p, const char* who) {
-    CADM_REQUIRE(p, "%s: the reward parameters are null", who);
-    CADM_REQUIRE(p->n_hidden >= 0 && p->n_hidden <= CADM_MAX_VALUE_LAYERS, "%s: %d hidden layers, outside 0 .. %d", who, p->n_hidden,
-                 CADM_MAX_VALUE_LAYERS);
-    for (int l = 0; l < p->n_hidden; ++l)
-        CADM_REQUIRE(p->hidden[l] >= 1 && p->hidden[l] <= CADM_MAX_VALUE_WIDTH, "%s: hidden layer %d has width %d, outside 1 .. %d", who, l,
-                     p->hidden[l], CADM_MAX_VALUE_WIDTH);
-    CADM_REQUIRE(p->activation == CADM_VALUE_RELU || p->activation == CADM_VALUE_TANH || p->activation == CADM_VALUE_SWISH,
-                 "%s: unknown reward activation %d", who, p->activation);
+    int rc;
+    if ((rc = mlp_shape_check(mlp_shape(p), "reward", who))) return rc;
     CADM_REQUIRE(p->inputs == CADM_REWARD_NEXT_OBS || p->inputs == CADM_REWARD_OBS_ACT || p->inputs == CADM_REWARD_OBS_ACT_NEXT_OBS,
                  "%s: unknown reward inputs %d", who, p->inputs);
     CADM_REQUIRE(isfinite(p->weight), "%s: the reward weight %g is not finite", who, (double)p->weight);
-    CADM_REQUIRE(!ctx->cfg.discrete && ctx->cfg.env_kind != CADM_ENV_CARTPOLE, "%s: a learned reward needs a continuous-action ctx (discrete "
-                 "actions are planned by random shooting)", who);
-    CADM_REQUIRE(!cadm_sharded(ctx), "%s: a learned reward is not supported on a candidate-sharded ctx", who);
+    if ((rc = mlp_ctx_check(ctx, "a learned reward", who))) return rc;
     const int K = reward_K(ctx, p->inputs);
     CADM_REQUIRE(K <= CADM_MAX_REWARD_DIMS, "%s: the reward net's input has %d dims, beyond %d", who, K, CADM_MAX_REWARD_DIMS);
     int dims[MLP_NL + 1];
-    reward_dims(ctx, p, dims);
+    mlp_dims(mlp_shape(p), K, 1, dims);
     const size_t lds = reward_lds_bytes(dims, p->n_hidden + 1, 1, nullptr, nullptr);
     CADM_REQUIRE(lds <= (size_t)MLP_LDS_MAX, "%s: the reward net's activation tiles need %zu bytes of LDS at one row tile, the bound is %d", who,
                  lds, MLP_LDS_MAX);
@@ -203,11 +173,9 @@ static int reward_check(const cadm_ctx* ctx, const cadm_reward_params* p, const 
 
 // `p` must describe the registered net
 static int reward_match(const cadm_ctx* ctx, const cadm_reward_params* p, const char* who) {
-    if (!ctx->reward || !ctx->reward->set) { cadm_set_error("%s: no reward net is registered (call cadm_set_reward_net)", who); return CADM_ESTATE; }
+    if (!mlp_registered(ctx->reward)) { cadm_set_error("%s: no reward net is registered (call cadm_set_reward_net)", who); return CADM_ESTATE; }
     const cadm_reward_params& r = ctx->reward->prm;
-    bool same = p->n_hidden == r.n_hidden && p->activation == r.activation && p->inputs == r.inputs;
-    for (int l = 0; same && l < p->n_hidden; ++l) same = p->hidden[l] == r.hidden[l];
-    CADM_REQUIRE(same, "%s: the reward parameters do not describe the registered net (inputs, layers, widths or activation differ)", who);
+    CADM_REQUIRE(p->inputs == r.inputs && mlp_shape_same(mlp_shape(p), mlp_shape(&r)), "%s: the reward parameters do not describe the registered net (inputs, layers, widths or activation differ)", who);
     return CADM_OK;
 }
 
@@ -220,28 +188,13 @@ int cadm_reward_plan_check(const cadm_ctx* ctx, const cadm_reward_params* p, con
 // the GEMM launch over a.rows rows: the net's half of `a` is filled here
 static int reward_launch(cadm_ctx* ctx, RewardArgs& a, hipStream_t s, const char* who) {
     const RewardNet& net = *ctx->reward;
-    reward_dims(ctx, &net.prm, a.dims);
-    a.nlayers = net.prm.n_hidden + 1;
-    a.act = net.prm.activation;
+    mlp_dev(a.net, net.net[0], mlp_shape(&net.prm), reward_K(ctx, net.prm.inputs), 1);
     a.inputs = net.prm.inputs;
-    for (int l = 0; l < a.nlayers; ++l) { a.W[l] = net.W[l]; a.b[l] = net.b[l]; }
-    a.mean = net.mean; a.istd = net.istd;
     a.D = ctx->D; a.A = ctx->A; a.H = ctx->H; a.p = ctx->p;
     // two row tiles where four workgroups of them still fit a CU and the rows fill the CUs twice over; else one (see the header)
-    const size_t tiles = (a.rows + 15) / 16;
-    const int RT = tiles > 2 * (size_t)ctx->n_cus && reward_lds_bytes(a.dims, a.nlayers, 2, nullptr, nullptr) <= (size_t)MLP_LDS_MAX / 4 ? 2 : 1;
-    const size_t lds = reward_lds_bytes(a.dims, a.nlayers, RT, &a.region0, &a.region1);
-    const size_t R = 16 * (size_t)RT, blocks = (a.rows + R - 1) / R;
-    CADM_REQUIRE(blocks <= 0x7fffffffull, "%s: %zu rows are too many for one launch", who, a.rows);
-    const void* fn = RT == 2 ? reinterpret_cast<const void*>(&reward_kernel<2>) : reinterpret_cast<const void*>(&reward_kernel<1>);
-    if (lds > 64 * 1024 && !ctx->attr_done.count(fn)) {
-        CADM_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS_MAX));
-        ctx->attr_done.insert(fn);
-    }
-    if (RT == 2) hipLaunchKernelGGL(reward_kernel<2>, dim3((unsigned)blocks), dim3(MLP_THREADS), lds, s, a);
-    else hipLaunchKernelGGL(reward_kernel<1>, dim3((unsigned)blocks), dim3(MLP_THREADS), lds, s, a);
-    CADM_CHECK_HIP(hipGetLastError());
-    return CADM_OK;
+    const int RT = mlp_many_tiles(ctx, a.rows) && reward_lds_bytes(a.net.dims, a.net.nlayers, 2, nullptr, nullptr) <= (size_t)MLP_LDS_MAX / 4 ? 2 : 1;
+    const size_t lds = reward_lds_bytes(a.net.dims, a.net.nlayers, RT, &a.region0, &a.region1);
+    return mlp_launch(ctx, reward_kernel<1>, reward_kernel<2>, RT, lds, a.rows, a, s, who);
 }
 
 // both launches behind a rollout's traj [H, m, n, p, D] (n the PACKED candidate count): r_step [H, m, n, p], then the step sum
@@ -270,33 +223,22 @@ int cadm_launch_reward(cadm_ctx* ctx, const cadm_reward_params* p, const float* 
 
 extern "C" int cadm_set_reward_net(cadm_ctx* ctx, const cadm_reward_params* params, const float* const* W, const float* const* b,
                                    const float* mean, const float* std_inv, void* stream) {
-    CADM_REQUIRE(ctx, "cadm_set_reward_net: ctx is null");
-    if (!params) {
-        if (ctx->reward) ctx->reward->set = false;
-        return CADM_OK;
-    }
+    const char* who = "cadm_set_reward_net";
+    CADM_REQUIRE(ctx, "%s: ctx is null", who);
+    if (!params) { mlp_clear(ctx->reward); return CADM_OK; }
     int rc;
-    if ((rc = reward_check(ctx, params, "cadm_set_reward_net"))) return rc;
-    CADM_REQUIRE(W && b && mean && std_inv, "cadm_set_reward_net: W / b / mean / std_inv is null");
-    const int nl = params->n_hidden + 1;
-    for (int l = 0; l < nl; ++l) CADM_REQUIRE(W[l] && b[l], "cadm_set_reward_net: the weights or the biases of layer %d are null", l);
+    if ((rc = reward_check(ctx, params, who))) return rc;
     int dims[MLP_NL + 1];
-    reward_dims(ctx, params, dims);
-    CADM_ON_DEVICE(ctx);
-    if (!ctx->reward) {
-        ctx->reward = new (std::nothrow) RewardNet();
-        if (!ctx->reward) { cadm_set_error("cadm_set_reward_net: out of host memory"); return CADM_ENOMEM; }
-    }
-    RewardNet& net = *ctx->reward;
-    if ((rc = mlp_net_upload(net, dims, nl, W, b, mean, std_inv, (hipStream_t)stream, "cadm_set_reward_net"))) return rc;
-    net.prm = *params;
+    mlp_dims(mlp_shape(params), reward_K(ctx, params->inputs), 1, dims);
+    if ((rc = mlp_register(ctx, ctx->reward, 1, nullptr, dims, params->n_hidden + 1, W, b, mean, std_inv, stream, who))) return rc;
+    ctx->reward->prm = *params;
     return CADM_OK;
 }
 
 extern "C" int cadm_reward_eval(cadm_ctx* ctx, const float* x, int R, float* r_out, void* stream) {
     CADM_REQUIRE(ctx && x && r_out, "cadm_reward_eval: ctx / x / r_out is null");
     CADM_REQUIRE(R >= 1, "cadm_reward_eval: R must be >= 1 (got %d)", R);
-    if (!ctx->reward || !ctx->reward->set) { cadm_set_error("cadm_reward_eval: no reward net is registered (call cadm_set_reward_net)"); return CADM_ESTATE; }
+    if (!mlp_registered(ctx->reward)) { cadm_set_error("cadm_reward_eval: no reward net is registered (call cadm_set_reward_net)"); return CADM_ESTATE; }
     CADM_ON_DEVICE(ctx);
     RewardArgs a{};
     a.x = x; a.n = 1; a.total = (size_t)R; a.rows = (size_t)R; a.r_out = r_out;

@@ -1331,22 +1331,36 @@ class HipEngine:
         self._value_src = HipEngine._set_net(self, "set_value_net", params, self.D, weights, obs_mean, obs_std, "obs_mean", "obs_std")
 
     def _set_net(self, who, params, K, weights, mean, std, mean_name, std_name, N=1):
-        """What `set_value_net`, `set_reward_net` and `set_policy_net` share: the checks of a caller-supplied net K -> hidden -> N against its declared
-        `params` and of its input statistics [K] -- all of them before the library is looked at --, the staging, and the call of
-        cadm_<who>.  Returns what must stay alive until the next net (the copy is enqueued, not done); params None: the net is cleared,
-        and None."""
+        """What `set_value_net`, `set_reward_net` and `set_policy_net` share (and, piece by piece, `set_critic_nets`): the checks of a
+        caller-supplied net K -> hidden -> N against its declared `params` and of its input statistics [K] -- all of them before the
+        library is looked at --, the staging, and the call of cadm_<who>.  Returns what must stay alive until the next net; params
+        None: the net is cleared, and None."""
         if params is None:
             self._check(getattr(self.lib, "cadm_" + who)(self._ctx, None, None, None, None, None, self.stream), "cadm_" + who)
             return None
+        layers = HipEngine._net_layers(self, who, params, weights, K, N)
+        mean, std = HipEngine._net_stats(self, who, K, mean, std, mean_name, std_name)
+        return HipEngine._net_register(self, who, params, layers, mean, std)
+
+    def _net_layers(self, who, params, weights, K, N, critic=None):
+        """The layers [(W, b)] of one caller-supplied net (`value_weights`) checked against the declared K -> hidden -> N of `params`;
+        critic: its index among the nets of `set_critic_nets`, which the messages then name."""
         layers, act = self.value_weights(weights)
         dims = [K] + [int(params.hidden[l]) for l in range(params.n_hidden)] + [N]
         if len(layers) != len(dims) - 1:
-            raise ValueError("%s: %d layers given, the declared net %r has %d" % (who, len(layers), dims, len(dims) - 1))
+            given = "%d layers given" % len(layers) if critic is None else "critic %d has %d layers" % (critic, len(layers))
+            raise ValueError("%s: %s, the declared net %r has %d" % (who, given, dims, len(dims) - 1))
         for l, (w, b) in enumerate(layers):
             if w.shape != (dims[l], dims[l + 1]):
-                raise ValueError("%s: layer %d is %r, the declared net %r needs %r" % (who, l, w.shape, dims, (dims[l], dims[l + 1])))
+                which = "layer %d" % l if critic is None else "layer %d of critic %d" % (l, critic)
+                raise ValueError("%s: %s is %r, the declared net %r needs %r" % (who, which, w.shape, dims, (dims[l], dims[l + 1])))
         if act is not None and _lib.VALUE_ACTS[act] != params.activation:
-            raise ValueError("%s: the module's activation %r is not the declared one" % (who, act))
+            whose = "the module's activation %r" % (act,) if critic is None else "the activation %r of critic %d's module" % (act, critic)
+            raise ValueError("%s: %s is not the declared one" % (who, whose))
+        return layers
+
+    def _net_stats(self, who, K, mean, std, mean_name, std_name):
+        """The input statistics [K] of a caller-supplied net in float64 (None: 0 / 1), checked."""
         mean = np.zeros((K,), np.float64) if mean is None else np.asarray(self._host(mean), dtype=np.float64).reshape(-1)
         std = np.ones((K,), np.float64) if std is None else np.asarray(self._host(std), dtype=np.float64).reshape(-1)
         if mean.shape != (K,) or std.shape != (K,):
@@ -1355,6 +1369,11 @@ class HipEngine:
             raise ValueError("%s: %s must be finite" % (who, mean_name))
         if not np.all(np.isfinite(std) & (std > 0.0)):
             raise ValueError("%s: %s must be finite and > 0" % (who, std_name))
+        return mean, std
+
+    def _net_register(self, who, params, layers, mean, std):
+        """Stages the checked layers (of every net, net by net) and statistics and calls cadm_<who>; returns what must stay alive until
+        the next registration (the copy is enqueued, not done)."""
         dev = [(self._t(w), self._t(b)) for w, b in layers]
         mean_d, inv_d = self._t(mean.astype(np.float32)), self._t((1.0 / std).astype(np.float32))
         nl = len(dev)
@@ -1366,14 +1385,40 @@ class HipEngine:
     def _host(x):
         return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
 
+    def _flat_rows(self, who, x, K, name="states", none="no states"):
+        """What the nets' `*_eval` share: x [..., K] as a device tensor and flattened to [R, K], R >= 1."""
+        x = self._t(x)
+        if x.dim() < 1 or x.shape[-1] != K:
+            raise ValueError("%s: %s %r, expected [..., %d]" % (who, name, tuple(x.shape), K))
+        flat = x.reshape(-1, K).contiguous()
+        if flat.shape[0] < 1:
+            raise ValueError("%s: %s" % (who, none))
+        return x, flat
+
+    def _returns_args(self, who, traj, rows, first, out):
+        """What `value_returns`, `reward_returns` and `critic_returns` share: traj [H,m,n,p,D] and rows [m,n,p] as checked device
+        tensors, first [m,n,p] int32 or None, and out [m,n,p] (None: a new tensor)."""
+        traj, rows = self._t(traj), self._t(rows)
+        if traj.dim() != 5 or not traj.is_contiguous():
+            raise ValueError("%s: traj %r: expected contiguous [H,m,n,p,D]" % (who, tuple(traj.shape)))
+        H, m, n, p, D = traj.shape
+        if (H, p, D) != (self.H, self.p, self.D):
+            raise ValueError("%s: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (who, tuple(traj.shape), self.H, self.p, self.D))
+        if tuple(rows.shape) != (m, n, p) or not rows.is_contiguous():
+            raise ValueError("%s: rows %r, expected contiguous %r" % (who, tuple(rows.shape), (m, n, p)))
+        if first is not None:
+            first = self._t(first, dtype=torch.int32)
+            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
+                raise ValueError("%s: first %r, expected contiguous int32 %r" % (who, tuple(first.shape), (m, n, p)))
+        if out is None:
+            out = torch.empty_like(rows)
+        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rows.device:
+            raise ValueError("%s: out must be a contiguous float32 device tensor %r" % (who, (m, n, p)))
+        return traj, rows, first, out
+
     def value_eval(self, states):
         """`cadm_value_eval`: V of states [..., D] -> [...] (device tensors), through the planner's kernel."""
-        states = self._t(states)
-        if states.dim() < 1 or states.shape[-1] != self.D:
-            raise ValueError("value_eval: states %r, expected [..., %d]" % (tuple(states.shape), self.D))
-        flat = states.reshape(-1, self.D).contiguous()
-        if flat.shape[0] < 1:
-            raise ValueError("value_eval: no states")
+        states, flat = HipEngine._flat_rows(self, "value_eval", states, self.D)
         v = torch.empty((flat.shape[0],), dtype=torch.float32, device=self.device)
         self._check(self.lib.cadm_value_eval(self._ctx, ptr(flat), int(flat.shape[0]), ptr(v), self.stream), "cadm_value_eval")
         return v.reshape(states.shape[:-1])
@@ -1383,22 +1428,8 @@ class HipEngine:
         per row under `params` (`value_params`, describing the registered net).  first [m,n,p] int32 (None: every row):
         `constrain_returns`' first_violation -- a row with first < H keeps its bits.  want_v: (rows_out, v [m,n,p]), v NaN where skipped.
         out: where the new rows go (may be `rows` itself)."""
-        traj, rows = self._t(traj), self._t(rows)
-        if traj.dim() != 5 or not traj.is_contiguous():
-            raise ValueError("value_returns: traj %r: expected contiguous [H,m,n,p,D]" % (tuple(traj.shape),))
+        traj, rows, first, out = HipEngine._returns_args(self, "value_returns", traj, rows, first, out)
         H, m, n, p, D = traj.shape
-        if (H, p, D) != (self.H, self.p, self.D):
-            raise ValueError("value_returns: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (tuple(traj.shape), self.H, self.p, self.D))
-        if tuple(rows.shape) != (m, n, p) or not rows.is_contiguous():
-            raise ValueError("value_returns: rows %r, expected contiguous %r" % (tuple(rows.shape), (m, n, p)))
-        if first is not None:
-            first = self._t(first, dtype=torch.int32)
-            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
-                raise ValueError("value_returns: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
-        if out is None:
-            out = torch.empty_like(rows)
-        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rows.device:
-            raise ValueError("value_returns: out must be a contiguous float32 device tensor %r" % ((m, n, p),))
         v = torch.empty((m, n, p), dtype=torch.float32, device=self.device) if want_v else None
         self._check(self.lib.cadm_value_returns(self._ctx, ct.byref(params), ptr(traj), ptr(first), m, n, ptr(rows), ptr(out), ptr(v),
                                                 self.stream), "cadm_value_returns")
@@ -1479,11 +1510,7 @@ class HipEngine:
         K = getattr(self, "_reward_K", None)
         if K is None:
             raise _lib.CadmError("reward_eval: no reward net is registered (call set_reward_net)")
-        if x.dim() < 1 or x.shape[-1] != K:
-            raise ValueError("reward_eval: x %r, expected [..., %d]" % (tuple(x.shape), K))
-        flat = x.reshape(-1, K).contiguous()
-        if flat.shape[0] < 1:
-            raise ValueError("reward_eval: no inputs")
+        x, flat = HipEngine._flat_rows(self, "reward_eval", x, K, "x", "no inputs")
         r = torch.empty((flat.shape[0],), dtype=torch.float32, device=self.device)
         self._check(self.lib.cadm_reward_eval(self._ctx, ptr(flat), int(flat.shape[0]), ptr(r), self.stream), "cadm_reward_eval")
         return r.reshape(x.shape[:-1])
@@ -1493,27 +1520,15 @@ class HipEngine:
         rollout read), rows [m,n,p] -> rows + weight * S per row under `params` (`reward_params`, describing the registered net), S the
         sum of R over the counted steps in ascending t.  first [m,n,p] int32 (None: every step counts): `constrain_returns`'
         first_violation -- the steps t <= first count.  want_steps: (rows_out, steps [H,m,n,p], S [m,n,p]), steps NaN where not counted;
-        else the step rewards go to a cached workspace.  out: where the new rows go (may be `rows` itself)."""
-        traj, rows, obs, actions = self._t(traj), self._t(rows), self._t(obs), self._t(actions)
-        if traj.dim() != 5 or not traj.is_contiguous():
-            raise ValueError("reward_returns: traj %r: expected contiguous [H,m,n,p,D]" % (tuple(traj.shape),))
+        else the step rewards go to a cached workspace.  out: where the new rows go (may be `rows` itself).  Of several bad arguments
+        traj, rows, first and out are refused before obs and actions (`_returns_args` runs first)."""
+        traj, rows, first, out = HipEngine._returns_args(self, "reward_returns", traj, rows, first, out)
         H, m, n, p, D = traj.shape
-        if (H, p, D) != (self.H, self.p, self.D):
-            raise ValueError("reward_returns: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (tuple(traj.shape), self.H, self.p, self.D))
-        if tuple(rows.shape) != (m, n, p) or not rows.is_contiguous():
-            raise ValueError("reward_returns: rows %r, expected contiguous %r" % (tuple(rows.shape), (m, n, p)))
+        obs, actions = self._t(obs), self._t(actions)
         if tuple(obs.shape) != (m, D) or not obs.is_contiguous():
             raise ValueError("reward_returns: obs %r, expected contiguous %r" % (tuple(obs.shape), (m, D)))
         if tuple(actions.shape) != (m, n, H, self.A) or not actions.is_contiguous():
             raise ValueError("reward_returns: actions %r, expected contiguous %r" % (tuple(actions.shape), (m, n, H, self.A)))
-        if first is not None:
-            first = self._t(first, dtype=torch.int32)
-            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
-                raise ValueError("reward_returns: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
-        if out is None:
-            out = torch.empty_like(rows)
-        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rows.device:
-            raise ValueError("reward_returns: out must be a contiguous float32 device tensor %r" % ((m, n, p),))
         steps = S = ws = None
         if want_steps:
             steps = torch.empty((H, m, n, p), dtype=torch.float32, device=self.device)
@@ -1600,12 +1615,7 @@ class HipEngine:
     def policy_eval(self, states):
         """`cadm_policy_eval`: the registered policy's action of states [..., D] -> [..., A] (device tensors): squash and clip, no
         noise, through the chain of the proposal roll."""
-        states = self._t(states)
-        if states.dim() < 1 or states.shape[-1] != self.D:
-            raise ValueError("policy_eval: states %r, expected [..., %d]" % (tuple(states.shape), self.D))
-        flat = states.reshape(-1, self.D).contiguous()
-        if flat.shape[0] < 1:
-            raise ValueError("policy_eval: no states")
+        states, flat = HipEngine._flat_rows(self, "policy_eval", states, self.D)
         a = torch.empty((flat.shape[0], self.A), dtype=torch.float32, device=self.device)
         self._check(self.lib.cadm_policy_eval(self._ctx, ptr(flat), int(flat.shape[0]), ptr(a), self.stream), "cadm_policy_eval")
         return a.reshape(tuple(states.shape[:-1]) + (self.A,))
@@ -1771,44 +1781,17 @@ class HipEngine:
         nets = list(nets)
         if len(nets) != params.n_critics:
             raise ValueError("%s: %d nets given, %d critics declared" % (who, len(nets), params.n_critics))
-        dims = [K] + [int(params.hidden[l]) for l in range(params.n_hidden)] + [1]
-        dev = []
-        for c, net in enumerate(nets):
-            layers, act = self.value_weights(net)
-            if len(layers) != len(dims) - 1:
-                raise ValueError("%s: critic %d has %d layers, the declared net %r has %d" % (who, c, len(layers), dims, len(dims) - 1))
-            for l, (w, b) in enumerate(layers):
-                if w.shape != (dims[l], dims[l + 1]):
-                    raise ValueError("%s: layer %d of critic %d is %r, the declared net %r needs %r" % (who, l, c, w.shape, dims, (dims[l], dims[l + 1])))
-            if act is not None and _lib.VALUE_ACTS[act] != params.activation:
-                raise ValueError("%s: the activation %r of critic %d's module is not the declared one" % (who, act, c))
-            dev.extend((self._t(w), self._t(b)) for w, b in layers)
-        mean = np.zeros((K,), np.float64) if in_mean is None else np.asarray(self._host(in_mean), dtype=np.float64).reshape(-1)
-        std = np.ones((K,), np.float64) if in_std is None else np.asarray(self._host(in_std), dtype=np.float64).reshape(-1)
-        if mean.shape != (K,) or std.shape != (K,):
-            raise ValueError("%s: in_mean %r / in_std %r, expected [%d]" % (who, mean.shape, std.shape, K))
-        if not np.all(np.isfinite(mean)):
-            raise ValueError("%s: in_mean must be finite" % who)
-        if not np.all(np.isfinite(std) & (std > 0.0)):
-            raise ValueError("%s: in_std must be finite and > 0" % who)
-        mean_d, inv_d = self._t(mean.astype(np.float32)), self._t((1.0 / std).astype(np.float32))
-        nl = len(dev)
-        Wp, bp = (ct.c_void_p * nl)(*[w.data_ptr() for w, _ in dev]), (ct.c_void_p * nl)(*[b.data_ptr() for _, b in dev])
-        self._check(self.lib.cadm_set_critic_nets(self._ctx, ct.byref(params), Wp, bp, ptr(mean_d), ptr(inv_d), self.stream), "cadm_" + who)
+        layers = [wb for c, net in enumerate(nets) for wb in HipEngine._net_layers(self, who, params, net, K, 1, critic=c)]
+        mean, std = HipEngine._net_stats(self, who, K, in_mean, in_std, "in_mean", "in_std")
+        self._critic_src = HipEngine._net_register(self, who, params, layers, mean, std)
         self._critic_n = int(params.n_critics)
-        self._critic_src = (dev, mean_d, inv_d)      # alive until the next critics: the copy is enqueued, not done
 
     def critic_eval(self, states, actions=None, want_each=False, want_actions=False):
         """`cadm_critic_eval`: the reduced Q of states [..., D] -> [...] (device tensors) through the planner's kernel, at the registered
         policy net's action (actions None) or at actions [..., A].  want_each: also every critic's q [C, ...]; want_actions: also the
         action that was used [..., A].  Returns q, or the tuple (q[, each][, actions])."""
-        states = self._t(states)
-        if states.dim() < 1 or states.shape[-1] != self.D:
-            raise ValueError("critic_eval: states %r, expected [..., %d]" % (tuple(states.shape), self.D))
-        flat = states.reshape(-1, self.D).contiguous()
+        states, flat = HipEngine._flat_rows(self, "critic_eval", states, self.D)
         R = int(flat.shape[0])
-        if R < 1:
-            raise ValueError("critic_eval: no states")
         aflat = None
         if actions is not None:
             actions = self._t(actions)
@@ -1833,22 +1816,8 @@ class HipEngine:
         Q_c(s, pi(s)), s = traj[H-1], per row under `params` (`critic_params`, describing the registered critics).  first [m,n,p] int32
         (None: every row): `constrain_returns`' first_violation -- a row with first < H keeps its bits.  want_q: (rows_out, q [m,n,p]),
         q NaN where skipped.  out: where the new rows go (may be `rows` itself)."""
-        traj, rows = self._t(traj), self._t(rows)
-        if traj.dim() != 5 or not traj.is_contiguous():
-            raise ValueError("critic_returns: traj %r: expected contiguous [H,m,n,p,D]" % (tuple(traj.shape),))
+        traj, rows, first, out = HipEngine._returns_args(self, "critic_returns", traj, rows, first, out)
         H, m, n, p, D = traj.shape
-        if (H, p, D) != (self.H, self.p, self.D):
-            raise ValueError("critic_returns: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (tuple(traj.shape), self.H, self.p, self.D))
-        if tuple(rows.shape) != (m, n, p) or not rows.is_contiguous():
-            raise ValueError("critic_returns: rows %r, expected contiguous %r" % (tuple(rows.shape), (m, n, p)))
-        if first is not None:
-            first = self._t(first, dtype=torch.int32)
-            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
-                raise ValueError("critic_returns: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
-        if out is None:
-            out = torch.empty_like(rows)
-        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rows.device:
-            raise ValueError("critic_returns: out must be a contiguous float32 device tensor %r" % ((m, n, p),))
         q = torch.empty((m, n, p), dtype=torch.float32, device=self.device) if want_q else None
         self._check(self.lib.cadm_critic_returns(self._ctx, ct.byref(params), ptr(traj), ptr(first), m, n, ptr(rows), ptr(out), ptr(q),
                                                  self.stream), "cadm_critic_returns")

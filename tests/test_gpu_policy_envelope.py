@@ -29,7 +29,7 @@ Code no other test reaches -> the test here that does:
                 six full groups (A = 24), every one against Philox                                       test_noise_at_24_actions
                 the particle sum at p = 10 and 15 (the division is inexact), D = 45 (D4 = 48), D = 28    test_roll_per_kind
                 policy_step_kernel<2> with obs, p > 1, `states` stores and the q % P noise gate          test_two_row_tile_roll_*
-                nf = nf || policy_nonfinite(v) over particles j >= 1: a row that is partly non-finite     test_partly_non_finite_row
+                nf = nf || mlp_nonfinite(v) over particles j >= 1: a row that is partly non-finite        test_partly_non_finite_row
                 a non-finite context of one member of one env next to clean envs in the tile             test_non_finite_context_of_one_member
                 cur / next beyond two swaps, seqs[(q H + t) A + d] at H = 40, words POLICY_IT + 2 t, t > 1  test_long_roll
                 mid, half, clip, noise and the rollout's own normalisation at bounds -0.5, 2.0           test_bounds_in_the_roll
@@ -322,7 +322,7 @@ def test_partly_non_finite_row(engines, sign):
     """What does make one: a second slim_humanoid engine whose member 2 has the finite bias +-3e38 in its mean head, in the dim with the
     largest delta_std (> 1.14), so that the denormalised delta of member 2's particles overflows to +-inf.  After the first one-step
     rollout SOME particles of every row -- member 2's -- are non-finite and the others are not, particle 0 among the finite ones: the
-    flag comes from the `nf = nf || policy_nonfinite(v)` chain over j >= 1.  Step 0 (it reads `obs`) is the clean engine's bit for bit,
+    flag comes from the `nf = nf || mlp_nonfinite(v)` chain over j >= 1.  Step 0 (it reads `obs`) is the clean engine's bit for bit,
     the finite particles of step 1 have the clean engine's bits, and from step 1 on every action is the fallback, finite."""
     prob, clean_eng = engines("slim")
     prob = br.with_rows(prob, 3)
