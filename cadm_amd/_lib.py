@@ -145,7 +145,15 @@ STREAM_IMAGINE, STREAM_IMAGINE_ACT = 6, 7                                  # csr
 POLICY_IT = 0xFA0000                                                       # csrc/planner.h CADM_POLICY_IT: the roll's one-step rollouts run under POLICY_IT + 2 t
 
 
-class PolicyParams(C.Structure):        # include/cadm_hip.h cadm_policy_params (the layer conventions are the value net's)
+TARGET_VIEWS = 10                                                          # include/cadm_hip.h CADM_TARGET_VIEWS: the outputs cadm_imagine_targets_workspace_bytes reports offsets of
+
+
+class TargetParams(C.Structure):        # include/cadm_hip.h cadm_target_params
+    _fields_ = [("gamma", C.c_float), ("lam", C.c_float), ("penalty", C.c_float), ("max_disagreement", C.c_float), ("var_floor", C.c_float),
+                ("want_steve", C.c_int32)]
+
+
+class PolicyParams(C.Structure):       # include/cadm_hip.h cadm_policy_params (the layer conventions are the value net's)
     _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * MAX_VALUE_LAYERS), ("activation", C.c_int32), ("squash", C.c_int32),
                 ("n_samples", C.c_int32), ("noise_std", C.c_float)]
 
@@ -270,6 +278,8 @@ SIGNATURES = {
     "cadm_imagine": (_i, [_P, _P, _P, _P, _i, _i, _i, C.c_float, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P]),
     "cadm_imagine_select": (_i, [_P, _P, _P, _P, _P, _i, _i, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P, _P,
                                  _P, _P, _P, _P, _P, _P, _P]),
+    "cadm_imagine_targets_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, C.POINTER(C.c_uint64)]),
+    "cadm_imagine_targets": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _i, C.POINTER(TargetParams), _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_train_configure": (_i, [_P, C.POINTER(TrainHParams), _i]),
     "cadm_train_step": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P, _P]),

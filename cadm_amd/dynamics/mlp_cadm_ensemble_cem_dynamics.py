@@ -1015,6 +1015,42 @@ class MLPEnsembleCEMDynamicsModel(object):
             out = {k: (int(v) if k == "n_valid" else v.cpu().numpy()) for k, v in out.items()}
         return out
 
+    def imagine_targets(self, batch, gamma, lam=0.95, bootstrap="auto", penalty=0.0, max_disagreement=None, steve=None, numpy=False):
+        """What a critic is trained on, out of the dict `batch` that `imagine` returned (device tensors are taken as they are, numpy arrays
+        are uploaded) and bootstrap values of its states, in one launch (INTEGRATION.md "Value-expansion targets").  bootstrap: "value" --
+        V of the registered value net on batch["states"] (`cem_terminal_value`); "q" -- the critics at the actor's action
+        (`cem_terminal_q`); a [k+1,m,n] tensor or array -- the caller's own values, e.g. a target network's, on any model; "auto" --
+        value or q, whichever the model declares.  penalty: rew - penalty * disagreement is the step reward (MOPO); max_disagreement: a
+        row is cut in front of the first step whose disagreement exceeds it (M2AC).  Returns a dict of device tensors (numpy=True: numpy
+        copies), k = horizon, n = branches:
+          lambda_return [k,m,n]        the lambda-return of states[t] (Dreamer, TD-MPC); 0 where the step is not used
+          nstep, nstep_ok [k,m,n]      the h = t + 1 step target of the START state and whether it exists (MVE)
+          used [k,m,n] uint8           the steps in front of the row's end: valid and within max_disagreement
+          boot [k+1,m,n]               the bootstrap values that were used
+        and with steve=dict(var_floor=): steve [m], the n-step targets of a start state averaged over the horizons with weights inverse
+        to their variance over the branches (STEVE); steve_weight, steve_mean, steve_var [k,m]; steve_count [k,m] int32;
+        steve_fallback [m] uint8 (no horizon had two targets: steve is boot[0]).  A diverged row bootstraps from its last finite state,
+        a terminated row does not bootstrap.  Draws no noise and moves no counter."""
+        opt = getattr(self, "_opt", None)
+        a = _planner.imagine_targets_args(batch, gamma, lam, bootstrap, penalty, max_disagreement, steve,
+                                          has_value=opt is not None and opt.value_params is not None,
+                                          has_q=opt is not None and opt.critic_params is not None)
+        eng = self.engine
+        if a.bootstrap == "value":
+            self._require_value("imagine_targets", need_net=True)
+            boot = eng.value_eval(batch["states"])
+        elif a.bootstrap == "q":
+            self._require_critics("imagine_targets", need_nets=True, need_actor=True)
+            boot = eng.critic_eval(batch["states"])
+        else:
+            boot = eng._t(bootstrap)
+        out = eng.imagine_targets(eng._t(batch["rew"]), eng._t(batch["valid"], dtype=torch.uint8), eng._t(batch["done"], dtype=torch.uint8),
+                                  eng._t(batch["disagreement"]), boot.contiguous(), a.gamma, a.lam, a.penalty, a.max_disagreement, a.var_floor)
+        out["boot"] = boot
+        if numpy:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        return out
+
     # ------------------------------------------------------------------ learned reward (INTEGRATION.md "Learned reward")
     def _require_reward(self, who, need_net=False):
         opt = getattr(self, "_opt", None)

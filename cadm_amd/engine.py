@@ -1710,6 +1710,39 @@ class HipEngine:
                     "cadm_imagine_select")
         return out
 
+    def imagine_targets(self, rew, valid, done, disagreement, boot, gamma, lam=0.95, penalty=0.0, max_disagreement=None, steve_var_floor=None):
+        """`cadm_imagine_targets`: rew, disagreement [k,m,n] float32, valid, done [k,m,n] uint8 (`imagine`'s outputs) and boot [k+1,m,n],
+        the bootstrap value of states[t] -- device tensors, read only -> a dict of device tensors, views of ONE buffer the call allocates:
+        lambda_return, nstep [k,m,n], nstep_ok, used [k,m,n] uint8 and, with steve_var_floor (a finite number > 0), steve [m],
+        steve_weight, steve_mean, steve_var [k,m], steve_count [k,m] int32, steve_fallback [m] uint8.  gamma, lam, penalty,
+        max_disagreement (None: no bound): include/cadm_hip.h "Value-expansion targets"; the library refuses what is out of range."""
+        k, m, n = (int(v) for v in rew.shape) if isinstance(rew, torch.Tensor) and rew.dim() == 3 else (-1, -1, -1)
+        for name, t, dtype, shape in (("rew", rew, torch.float32, (k, m, n)), ("valid", valid, torch.uint8, (k, m, n)),
+                                      ("done", done, torch.uint8, (k, m, n)), ("disagreement", disagreement, torch.float32, (k, m, n)),
+                                      ("boot", boot, torch.float32, (k + 1, m, n))):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()) or k < 1 or tuple(t.shape) != shape:
+                raise ValueError("imagine_targets: %s must be a contiguous %s device tensor %s, got %s"
+                                 % (name, str(dtype).split(".")[-1], "[k,m,n]" if name == "rew" else list(shape),
+                                    "%r %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__))
+        steve = steve_var_floor is not None
+        prm = _lib.TargetParams(float(gamma), float(lam), float(penalty), float("inf") if max_disagreement is None else float(max_disagreement),
+                                float(steve_var_floor) if steve else 0.0, int(steve))
+        off = (ct.c_uint64 * _lib.TARGET_VIEWS)()
+        need = self.lib.cadm_imagine_targets_workspace_bytes(self._ctx, m, n, k, int(steve), off)
+        buf = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=self.device)      # (need 0: the call below says what is refused)
+        self._check(self.lib.cadm_imagine_targets(self._ctx, ptr(rew), ptr(valid), ptr(done), ptr(disagreement), ptr(boot), m, n, k,
+                                                  ct.byref(prm), ptr(buf), self.stream), "cadm_imagine_targets")
+        views = [("lambda_return", torch.float32, (k, m, n)), ("nstep", torch.float32, (k, m, n)), ("nstep_ok", torch.uint8, (k, m, n)),
+                 ("used", torch.uint8, (k, m, n))]
+        if steve:
+            views += [("steve", torch.float32, (m,)), ("steve_weight", torch.float32, (k, m)), ("steve_mean", torch.float32, (k, m)),
+                      ("steve_var", torch.float32, (k, m)), ("steve_count", torch.int32, (k, m)), ("steve_fallback", torch.uint8, (m,))]
+        out = {}
+        for (name, dtype, shape), o in zip(views, off):
+            nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+            out[name] = buf[int(o):int(o) + nbytes].view(dtype).view(shape)
+        return out
+
     def guided_plan(self, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints,
                     score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0, call=0, out=None,
                     want_best_return=False):

@@ -409,6 +409,82 @@ def imagine_args(obs, cp_obs=None, cp_act=None, horizon=1, branches=1, actions=N
     return ImagineArgs(m, n, k, std, w)
 
 
+TargetArgs = collections.namedtuple("TargetArgs", "m n k gamma lam penalty max_disagreement var_floor bootstrap")
+TARGET_BOOTSTRAPS = ("value", "q", "a [horizon+1,m,branches] tensor or array of the caller's own values")
+
+
+def _target_number(name, v, ok, what):
+    """v as the float32 the library is handed; ValueError unless it is a number for which ok(value) holds"""
+    try:
+        x = float(np.float32(v))
+    except (TypeError, ValueError):
+        x = None
+    if x is None or isinstance(v, (bool, np.bool_)) or not ok(x):
+        raise ValueError("imagine_targets: %s must be %s, got %r" % (name, what, v))
+    return x
+
+
+def imagine_targets_args(batch, gamma, lam=0.95, bootstrap="auto", penalty=0.0, max_disagreement=None, steve=None, *, has_value=False,
+                         has_q=False):
+    """The parsing and the refusals of `model.imagine_targets`' arguments, before anything is launched -> TargetArgs(m, n, k, gamma, lam,
+    penalty, max_disagreement, var_floor, bootstrap): the shape of `batch` (the dict `imagine` returned: rew, valid, done, disagreement
+    [k,m,n] and states [k+1,m,n,D]; numpy or torch), the numbers as the float32 the library is handed (max_disagreement None: +inf;
+    var_floor None: no STEVE outputs) and where the bootstrap values come from -- "value", "q" or "given".  bootstrap "auto" is whichever
+    of value and q the model declares (has_value / has_q: its cem_terminal_value / cem_terminal_q), value where it declares both.
+    ValueError for a batch that lacks a key or whose shapes disagree, gamma outside (0, 1], lam outside [0, 1], a penalty negative or not
+    finite, a max_disagreement not > 0, a steve that is not dict(var_floor= a finite number > 0), steve with fewer than two branches, a
+    bootstrap the model does not declare, or a given one of another shape.  A pure function of its inputs: it draws no noise, moves no
+    counter and does not care how many ranks there are.  Needs no GPU."""
+    need = ("rew", "valid", "done", "disagreement", "states")
+    if not isinstance(batch, dict) or any(key not in batch for key in need):
+        raise ValueError("imagine_targets: batch must be the dict imagine() returned, with %s%s"
+                         % (", ".join(need), "" if not isinstance(batch, dict) else "; it lacks %s" % ", ".join(k_ for k_ in need if k_ not in batch)))
+    shp = tuple(int(v) for v in np.shape(batch["rew"]))
+    if len(shp) != 3 or min(shp) < 1:
+        raise ValueError("imagine_targets: batch['rew'] %r, expected [horizon,m,branches] with every size >= 1" % (shp,))
+    k, m, n = shp
+    for key in ("valid", "done", "disagreement"):
+        if tuple(int(v) for v in np.shape(batch[key])) != shp:
+            raise ValueError("imagine_targets: batch[%r] %r, expected %r as batch['rew']" % (key, tuple(np.shape(batch[key])), shp))
+    st = tuple(int(v) for v in np.shape(batch["states"]))
+    if len(st) != 4 or st[:3] != (k + 1, m, n):
+        raise ValueError("imagine_targets: batch['states'] %r, expected [horizon+1,m,branches,D] = (%d, %d, %d, D)" % (st, k + 1, m, n))
+    g = _target_number("gamma", gamma, lambda x: 0.0 < x <= 1.0, "a number in (0, 1]")
+    l_ = _target_number("lam", lam, lambda x: 0.0 <= x <= 1.0, "a number in [0, 1]")
+    beta = _target_number("penalty", penalty, lambda x: np.isfinite(x) and x >= 0.0, "a finite number >= 0")
+    maxd = float("inf") if max_disagreement is None else _target_number("max_disagreement", max_disagreement, lambda x: x > 0.0,
+                                                                        "None or a number > 0")
+    floor = None
+    if steve is not None:
+        if not isinstance(steve, dict) or set(steve) != {"var_floor"}:
+            raise ValueError("imagine_targets: steve must be None or dict(var_floor=), got %r" % (steve,))
+        floor = _target_number("steve var_floor", steve["var_floor"], lambda x: np.isfinite(x) and x > 0.0, "a finite number > 0")
+        if n < 2:
+            raise ValueError("imagine_targets: steve weighs the horizons by the variance over the branches and needs branches >= 2, "
+                             "the batch has %d" % n)
+    if isinstance(bootstrap, str):
+        if bootstrap not in ("auto", "value", "q"):
+            raise ValueError("imagine_targets: bootstrap must be 'auto' or one of %s, got %r" % (", ".join(map(repr, TARGET_BOOTSTRAPS[:2]))
+                                                                                                + " or " + TARGET_BOOTSTRAPS[2], bootstrap))
+        kind = bootstrap
+        if kind == "auto":
+            kind = "value" if has_value else "q" if has_q else None
+            if kind is None:
+                raise ValueError("imagine_targets: bootstrap='auto' needs a model that declares cem_terminal_value or cem_terminal_q; this "
+                                 "one declares neither.  The choices are 'value' (V of the registered value net), 'q' (the critics at the "
+                                 "actor's action) or %s" % TARGET_BOOTSTRAPS[2])
+        if kind == "value" and not has_value:
+            raise ValueError("imagine_targets: bootstrap='value' needs a model with cem_terminal_value")
+        if kind == "q" and not has_q:
+            raise ValueError("imagine_targets: bootstrap='q' needs a model with cem_terminal_q")
+    else:
+        if bootstrap is None or tuple(int(v) for v in np.shape(bootstrap)) != (k + 1, m, n):
+            raise ValueError("imagine_targets: bootstrap %r, expected 'auto', 'value', 'q' or values of shape [horizon+1,m,branches] = %r"
+                             % (None if bootstrap is None else tuple(np.shape(bootstrap)), (k + 1, m, n)))
+        kind = "given"
+    return TargetArgs(m, n, k, g, l_, beta, maxd, floor, kind)
+
+
 class Shard:
     """Contiguous candidate shard of one rank."""
 

@@ -1008,6 +1008,55 @@ int cadm_imagine_select(cadm_ctx* ctx, const float* next, const float* rows1, co
                         uint32_t call, uint8_t* alive_io, float* state_out, float* rew_out, uint8_t* done_out, uint8_t* valid_out,
                         int32_t* member_out, float* disagreement_out, int32_t* length_io, float* bcast_out, void* stream);
 
+/* Value-expansion targets (csrc/imagine_targets.hip; no reference twin): what a critic is trained on, out of cadm_imagine's transitions
+ * and the caller's bootstrap values of their states, in ONE launch -- lambda-returns on every imagined state (Dreamer, TD-MPC), the n-step
+ * targets of the start state (MVE), their inverse-variance combination over the branches (STEVE), the reward reduced by a multiple of the
+ * disagreement and the rollout cut where it passes a bound (MOPO, M2AC).  rew, valid, done, disagreement are [k,m,n] as cadm_imagine lays
+ * them out; boot [k+1,m,n] is the bootstrap value of states[t].  A row is (start state i, branch j); element t of the row is [t,i,j].
+ * Everything is float32 and every operation is rounded on its own (no fused multiply-add); divisions are correctly rounded;
+ * one_minus_lambda = 1.0f - lambda is computed once on the host.  Per row, in this order:
+ *   L        the number of leading steps with valid[t] && !(disagreement[t] > max_disagreement);   used[t] = t < L
+ *   term     L >= 1 && done[L-1]   (a done in front of the last used step is not read)
+ *   r~_t     rew[t] where penalty == 0 (no multiply, so 0 * inf cannot arise), else rew[t] - penalty * disagreement[t]
+ *   lambda   for t = L-1 down to 0:  t == L-1:  G = term ? r~_t : r~_t + gamma * boot[t+1]
+ *                                    otherwise:  G = r~_t + gamma * (one_minus_lambda * boot[t+1] + lambda * G)
+ *            lambda_return[t] = G for t < L and 0 behind; a non-finite bootstrap propagates
+ *   n-step   acc = 0, disc = 1;  for h = 1 .. L:  acc = acc + disc * r~_{h-1};  disc = disc * gamma;
+ *            x_h = (h == L && term) ? acc : acc + disc * boot[h].   For h > L: x_h = x_L with term (a terminated row is worth its terminal
+ *            return at every longer horizon), no target without.  nstep[h-1] = x_h and nstep_ok[h-1] = 1 where a target exists and is
+ *            finite, otherwise both are 0
+ * So a diverged row (valid 0 without done) bootstraps from boot[L], the value of its last finite state, and a terminated row does not
+ * bootstrap.  Per start state i and horizon h, with want_steve only:
+ *   c = the number of branches with nstep_ok;  mean = c > 0 ? (sum x) / c : 0;  var = c > 0 ? (sum (x - mean) * (x - mean)) / c : 0, both
+ *   sums from 0.0f over those branches in ascending j (two passes);   w_h = c >= 2 ? 1 / (var + var_floor) : 0
+ *   W = sum_h w_h and S = sum_h w_h * mean_h, from 0.0f in ascending h;   steve[i] = W > 0 ? S / W : boot[0,i,0];
+ *   steve_weight[h-1,i] = W > 0 ? w_h / W : 0;   steve_fallback[i] = !(W > 0)
+ * cadm_imagine_targets_workspace_bytes: the bytes of `buffer`; offsets_out [CADM_TARGET_VIEWS] or NULL takes the byte offsets of the
+ * outputs in it, in this order: lambda_return [k,m,n] float, nstep [k,m,n] float, nstep_ok [k,m,n] uint8, used [k,m,n] uint8, and with
+ * want_steve steve [m] float, steve_weight [k,m] float, steve_mean [k,m] float, steve_var [k,m] float, steve_count [k,m] int32,
+ * steve_fallback [m] uint8 (without: these six offsets are 0 and take no bytes).  Every view starts on a multiple of 256 bytes; the
+ * bytes between two views are never written.  0 for a null ctx and for what cadm_imagine_targets refuses of the shape.
+ * cadm_imagine_targets: the inputs are read only and must not overlap `buffer`; prm->want_steve switches the STEVE outputs on and must be
+ * what the buffer was sized with.  The ctx supplies the device and the error channel: no weights are read, nothing of the ctx changes.
+ * Determinism: every output is one thread's chain in the order above, no floating-point atomics, no cross-lane reduction; nothing depends
+ * on the grid, the group size, m, or the position of a row or a start state: the same bits run to run.
+ * Refusals, CADM_EINVAL before any HIP call: null pointers; m, n or k < 1; m * n beyond 2^31 - 1 rows; gamma outside (0, 1]; lambda outside
+ * [0, 1]; a penalty negative or not finite; max_disagreement not > 0 (+inf: no bound); with want_steve a var_floor not finite and > 0,
+ * n < 2, or an n * k whose tile for ONE start state (5 bytes per target and 8 k bytes) is beyond the reduction's 48 KiB LDS budget -- the
+ * scan without the STEVE outputs has no such limit. */
+typedef struct cadm_target_params {
+    float gamma;              /* (0, 1]: the discount */
+    float lambda;             /* [0, 1]: lambda of the lambda-return */
+    float penalty;            /* finite, >= 0: the multiple of disagreement taken off the reward */
+    float max_disagreement;   /* > 0, +inf = none: the bound beyond which a rollout is cut */
+    float var_floor;          /* finite, > 0: added to the branch variance; read only with want_steve */
+    int32_t want_steve;       /* != 0: the STEVE outputs are computed and `buffer` holds their views */
+} cadm_target_params;
+#define CADM_TARGET_VIEWS 10
+size_t cadm_imagine_targets_workspace_bytes(cadm_ctx* ctx, int m, int n, int k, int want_steve, uint64_t* offsets_out);
+int cadm_imagine_targets(cadm_ctx* ctx, const float* rew, const uint8_t* valid, const uint8_t* done, const float* disagreement,
+                         const float* boot, int m, int n, int k, const cadm_target_params* prm, void* buffer, void* stream);
+
 /* One training step =sess.run([mse_loss, back_mse_loss, recon_loss, train_op]) (dynamics.py:505-507):
  * forward of context / forward / backward nets on the [E,B,.] bootstrap batch, losses
  * (dynamics.py:269-314), gradients, TF1-semantics Adam (dynamics.py:316-317) applied IN PLACE to the
