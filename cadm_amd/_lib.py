@@ -179,6 +179,27 @@ class TrainHParams(C.Structure):
 _P = C.c_void_p
 _u32, _i = C.c_uint32, C.c_int
 
+# The nest of opt-in plan exports, inner to outer: what cadm_<level>_plan takes in front of the level below (behind ctx).  Every level
+# ends with the tail of cadm_icem_plan behind its params: obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed,
+# call, workspace, plan_out, best_return_out, stream.
+_PLAN_TAIL = [_P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]
+_PLAN_NEST = (
+    ("scored", [C.POINTER(ScoreParams), _i, C.POINTER(MppiParams)]),          # score, update, prm
+    ("constrained", [C.POINTER(ConstraintParams)]),
+    ("knot", [C.POINTER(KnotParams), _P]),                                    # knots, phase
+    ("tracking", [C.POINTER(TrackParams), _P, _i, _P]),                       # track, targets, T, offset
+    ("actuated", [C.POINTER(ActuatorParams), _P, _P, _i]),                    # act, prev_io, prefix_io, advance
+    ("uncertain", [C.POINTER(UncertaintyParams)]),
+    ("valued", [C.POINTER(ValueParams)]),
+    ("rewarded", [C.POINTER(RewardParams)]),
+    ("guided", [C.POINTER(PolicyParams)]),
+    ("critic", [C.POINTER(CriticParams)]),
+)
+_PLAN_ARGS, _args = {}, _PLAN_TAIL      # level -> argtypes of cadm_<level>_plan: ctx, every level's own arguments from it inwards, the tail
+for _level, _front in _PLAN_NEST:
+    _args = _front + _args
+    _PLAN_ARGS[_level] = [_P] + _args
+
 # name -> (restype, argtypes); must list every symbol include/cadm_hip.h declares
 SIGNATURES = {
     "cadm_last_error": (C.c_char_p, []),
@@ -216,61 +237,43 @@ SIGNATURES = {
     "cadm_mppi_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i]),
     "cadm_mppi_plan": (_i, [_P, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_particle_score": (_i, [_P, _P, _i, _i, C.POINTER(ScoreParams), _P, _P]),
-    "cadm_scored_plan": (_i, [_P, C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_scored_plan": (_i, _PLAN_ARGS["scored"]),
     "cadm_constrain_returns": (_i, [_P, C.POINTER(ConstraintParams), _P, _P, _P, _P, _i, _i, _P, _P, _P, _P]),
     "cadm_constrained_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i]),
-    "cadm_constrained_plan": (_i, [_P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P,
-                                   _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_constrained_plan": (_i, _PLAN_ARGS["constrained"]),
     "cadm_shape_actions": (_i, [_P, C.POINTER(KnotParams), _P, _i, _i, _P, _P]),
-    "cadm_knot_plan": (_i, [_P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P,
-                            _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_knot_plan": (_i, _PLAN_ARGS["knot"]),
     "cadm_tracking_returns": (_i, [_P, C.POINTER(TrackParams), _P, _P, _i, _P, _P, _P, _i, _i, _P, _P, _P]),
     "cadm_tracking_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i]),
-    "cadm_tracking_plan": (_i, [_P, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams),
-                                C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_tracking_plan": (_i, _PLAN_ARGS["tracking"]),
     "cadm_actuate_actions": (_i, [_P, C.POINTER(ActuatorParams), _P, _P, _i, _i, _P, _P, _P]),
     "cadm_actuated_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i]),
-    "cadm_actuated_plan": (_i, [_P, C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P,
-                                C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i,
-                                _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_actuated_plan": (_i, _PLAN_ARGS["actuated"]),
     "cadm_uncertainty_cost": (_i, [_P, C.POINTER(UncertaintyParams), _P, _P, _i, _i, _P, _P, _P]),
     "cadm_uncertain_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i]),
-    "cadm_uncertain_plan": (_i, [_P, C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P,
-                                 C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P,
-                                 _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_uncertain_plan": (_i, _PLAN_ARGS["uncertain"]),
     "cadm_set_value_net": (_i, [_P, C.POINTER(ValueParams), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
     "cadm_value_eval": (_i, [_P, _P, _i, _P, _P]),
     "cadm_value_returns": (_i, [_P, C.POINTER(ValueParams), _P, _P, _i, _i, _P, _P, _P, _P]),
     "cadm_valued_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i]),
-    "cadm_valued_plan": (_i, [_P, C.POINTER(ValueParams), C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i,
-                              C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams),
-                              _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_valued_plan": (_i, _PLAN_ARGS["valued"]),
     "cadm_set_reward_net": (_i, [_P, C.POINTER(RewardParams), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
     "cadm_reward_eval": (_i, [_P, _P, _i, _P, _P]),
     "cadm_reward_workspace_bytes": (C.c_size_t, [_P, _i, _i]),
     "cadm_reward_returns": (_i, [_P, C.POINTER(RewardParams), _P, _P, _P, _P, _i, _i, _P, _P, _P, _P, _P, _P]),
     "cadm_rewarded_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i]),
-    "cadm_rewarded_plan": (_i, [_P, C.POINTER(RewardParams), C.POINTER(ValueParams), C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams),
-                                _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams),
-                                C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P,
-                                _P]),
+    "cadm_rewarded_plan": (_i, _PLAN_ARGS["rewarded"]),
     "cadm_set_policy_net": (_i, [_P, C.POINTER(PolicyParams), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
     "cadm_policy_eval": (_i, [_P, _P, _i, _P, _P]),
     "cadm_policy_workspace_bytes": (C.c_size_t, [_P, _i, _i]),
     "cadm_policy_propose": (_i, [_P, C.POINTER(PolicyParams), _P, _P, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_guided_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "cadm_guided_plan": (_i, [_P, C.POINTER(PolicyParams), C.POINTER(RewardParams), C.POINTER(ValueParams), C.POINTER(UncertaintyParams),
-                              C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P, C.POINTER(KnotParams), _P,
-                              C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P, _P, _P, _P, _P, _P, _P, _i,
-                              _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_guided_plan": (_i, _PLAN_ARGS["guided"]),
     "cadm_set_critic_nets": (_i, [_P, C.POINTER(CriticParams), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
     "cadm_critic_eval": (_i, [_P, _P, _P, _i, _P, _P, _P, _P]),
     "cadm_critic_returns": (_i, [_P, C.POINTER(CriticParams), _P, _P, _i, _i, _P, _P, _P, _P]),
     "cadm_critic_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "cadm_critic_plan": (_i, [_P, C.POINTER(CriticParams), C.POINTER(PolicyParams), C.POINTER(RewardParams), C.POINTER(ValueParams),
-                              C.POINTER(UncertaintyParams), C.POINTER(ActuatorParams), _P, _P, _i, C.POINTER(TrackParams), _P, _i, _P,
-                              C.POINTER(KnotParams), _P, C.POINTER(ConstraintParams), C.POINTER(ScoreParams), _i, C.POINTER(MppiParams), _P,
-                              _P, _P, _P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_critic_plan": (_i, _PLAN_ARGS["critic"]),
     "cadm_set_discount": (_i, [_P, C.c_float, _P]),
     "cadm_discount_weights": (_i, [_P, C.POINTER(C.c_float), C.POINTER(_i)]),
     "cadm_discount_returns": (_i, [_P, _P, _P, _P, _i, _i, _P, _P, _P, _P]),

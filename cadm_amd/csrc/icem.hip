@@ -349,59 +349,52 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
 }
 
 // On a ctx with a discount over the horizon (cadm_set_discount, discount.hip) the loop always records trajectories: every size below is
-// then the one with the trajectory view.  The discount is set BEFORE the workspace is sized.
-static int icem_discounted(const cadm_ctx* ctx) { return ctx->disc != nullptr; }
+// then the one with the trajectory view.  The discount is set BEFORE the workspace is sized.  (A null ctx has none: icem_size refuses it.)
+static int icem_discounted(const cadm_ctx* ctx) { return ctx && ctx->disc != nullptr; }
 
-extern "C" size_t cadm_icem_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, 0, nullptr, nullptr, icem_discounted(ctx));
+// every size export below: 0 for bad arguments (P, the proposals per env, at the levels that have them), else what icem_carve takes under
+// the export's mapping of its flags to the carver's
+static size_t icem_size(const cadm_ctx* ctx, int m, int n, int K, int mppi, int traj, int first = 0, int act = 0, int unc = 0, int rew = 0,
+                        int P = 0) {
+    if (!ctx || m <= 0 || n <= 0 || K < 0 || P < 0) return 0;
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, traj, first, act, unc, rew, P);
 }
 
-extern "C" size_t cadm_mppi_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, 1, nullptr, nullptr, icem_discounted(ctx));
-}
+extern "C" size_t cadm_icem_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) { return icem_size(ctx, m, n, K, 0, icem_discounted(ctx)); }
 
-extern "C" size_t cadm_constrained_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1);
-}
+extern "C" size_t cadm_mppi_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) { return icem_size(ctx, m, n, K, 1, icem_discounted(ctx)); }
+
+extern "C" size_t cadm_constrained_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi) { return icem_size(ctx, m, n, K, mppi, 1); }
 
 extern "C" size_t cadm_tracking_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0);
+    return icem_size(ctx, m, n, K, mppi, 1, terminate != 0);
 }
 
 extern "C" size_t cadm_actuated_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int traj, int terminate) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, traj != 0 || icem_discounted(ctx), traj != 0 && terminate != 0, 1);
+    return icem_size(ctx, m, n, K, mppi, traj != 0 || icem_discounted(ctx), traj != 0 && terminate != 0, 1);
 }
 
 extern "C" size_t cadm_uncertain_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, 1);
+    return icem_size(ctx, m, n, K, mppi, 1, terminate != 0, actuator != 0, 1);
 }
 
 extern "C" size_t cadm_valued_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0);
+    return icem_size(ctx, m, n, K, mppi, 1, terminate != 0, actuator != 0, uncertainty != 0);
 }
 
 extern "C" size_t cadm_rewarded_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0, 1);
-}
-
-// the guided loop's: a terminal Q reads the trajectory view and the first violations the other terms read, and takes no view of its own
-extern "C" size_t cadm_critic_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P) {
-    return cadm_guided_workspace_bytes(ctx, m, n, K, mppi, terminate, actuator, uncertainty, P);
+    return icem_size(ctx, m, n, K, mppi, 1, terminate != 0, actuator != 0, uncertainty != 0, 1);
 }
 
 // enough for every combination of terms: the rewarded loop's views, and with P > 0 behind them the proposals and the roll's workspace
 // (a loop with fewer terms takes fewer views in front of the policy's: it fits)
 extern "C" size_t cadm_guided_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P) {
-    if (!ctx || m <= 0 || n <= 0 || K < 0 || P < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, 1, terminate != 0, actuator != 0, uncertainty != 0, 1, P);
+    return icem_size(ctx, m, n, K, mppi, 1, terminate != 0, actuator != 0, uncertainty != 0, 1, P);
+}
+
+// the guided loop's: a terminal Q reads the trajectory view and the first violations the other terms read, and takes no view of its own
+extern "C" size_t cadm_critic_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P) {
+    return cadm_guided_workspace_bytes(ctx, m, n, K, mppi, terminate, actuator, uncertainty, P);
 }
 
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
@@ -413,46 +406,63 @@ static int icem_n_it(int n, double decay, int it, int num_elites, int K) {
     return ni < n ? ni : n;
 }
 
+// The terms a level of the nest may add to the loop; a value-initialised PlanTerms is "no term", and cadm_scored_plan's launches.  Each
+// export fills the fields it has parameters for.  The ctx's discount over the horizon (cadm_set_discount, discount.hip) is not a term: with
+// a table set every rollout records its trajectories, the env's own return is rewritten as sum_t disc[t] r_t directly behind the rollout
+// (cadm_launch_discount), and every stage below weighs its steps by the same table; a terminal term's weight is multiplied by disc[H].
+// No table: today's launches.
+struct PlanTerms {
+    // state constraints that rewrite the particle returns before the score (constrain.hip); null = none, and today's launches
+    const cadm_constraint_params* constraints;
+    // the grid every candidate is shaped onto before its rollout (knots.hip), phase [m] int32 on the device or null = 0; knots null or
+    // spacing 1 = none, and today's launches.  With a grid, iteration 0's mean is the caller's shaped, in the workspace (init_mean is not written).
+    const cadm_knot_params* knots;
+    const int32_t* phase;
+    // tracking terms whose cost against targets [m, T, K] (offset [m] int32 on the device or null = 0) comes off the particle returns behind
+    // the constraints and before the score (tracking.hip); null = none, and today's launches.  With terms every rollout records its
+    // trajectories, and TERMINATE constraints hand their first violations on: what a terminated trajectory holds behind them is not tracked.
+    const cadm_track_params* terms;
+    const float* targets;
+    int T;
+    const int32_t* offset;
+    // an actuator model (actuator.hip) with the envs' last applied action prev [m, A] and committed steps prefix [m, delay, A] on the
+    // device; null = none, and today's launches.  With it every iteration's candidates are actuated in place behind the knot shaping, their
+    // rate cost comes off the candidate score behind cadm_particle_score, and the plan is actuated once more (n = 1) on a device copy before
+    // it is written to plan_out; advance: then prev <- plan[:, 0], prefix[:, j] <- plan[:, 1 + j].
+    const cadm_actuator_params* act;
+    float* prev_io;
+    float* prefix_io;
+    int advance;
+    // an uncertainty term (uncertainty.hip); null = none, and today's launches.  With it every rollout records its trajectories, TERMINATE
+    // constraints hand their first violations on (with or without terms), and lambda times the cost of the counted steps comes off the
+    // candidate score behind the actuator's: a statistic OVER the particles, so not off the particle rows.
+    const cadm_uncertainty_params* unc;
+    // a terminal value (value.hip) of the net registered with cadm_set_value_net; null = none, and today's launches.  With it every
+    // rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * V(traj[H - 1]) is added to the
+    // particle rows behind the constraints and the tracking terms and before the score: a risk-aware score sees return + value per particle.
+    const cadm_value_params* value;
+    // a learned step reward (reward.hip) of the net registered with cadm_set_reward_net; null = none, and today's launches.  With it
+    // every rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * (the sum of R over the
+    // counted steps) is added to the particle rows behind the constraints and the tracking terms and IN FRONT OF the terminal value.
+    const cadm_reward_params* reward;
+    // a policy prior (policy.hip) of the net registered with cadm_set_policy_net; null = none, and today's launches.  With it ONE
+    // proposal roll behind the context encoder, and in every iteration its P sequences take the slots behind the kept elites and the mean
+    // candidate, in front of the knot shaping and the actuator pass.
+    const cadm_policy_params* policy;
+    // a terminal Q (critic.hip) of the critics registered with cadm_set_critic_nets at the action of the registered policy net; null =
+    // none, and today's launches.  It stands where the terminal value stands and excludes it: weight * reduce_c Q_c(s, pi(s)), s = traj[H - 1],
+    // is added to the particle rows behind the constraints, the tracking terms and the learned reward, before the score.  `policy` may be
+    // null with it: the critic needs the registered net, not the proposals.
+    const cadm_critic_params* critic;
+};
+
 // score: what a candidate's particle returns become before the update sees them (score.hip); null = the particle mean
-// constraints: state constraints that rewrite the particle returns before the score (constrain.hip); null = none, and today's launches
-// knots: the grid every candidate is shaped onto before its rollout (knots.hip), phase [m] int32 on the device or null = 0; knots null or
-// spacing 1 = none, and today's launches.  With a grid, iteration 0's mean is the caller's shaped, in the workspace (init_mean is not written).
-// terms: tracking terms whose cost against targets [m, T, K] (offset [m] int32 on the device or null = 0) comes off the particle returns
-// behind the constraints and before the score (tracking.hip); null = none, and today's launches.  With terms every rollout records its
-// trajectories, and TERMINATE constraints hand their first violations on: what a terminated trajectory holds behind them is not tracked.
-// act: an actuator model (actuator.hip) with the envs' last applied action prev [m, A] and committed steps prefix [m, delay, A] on the
-// device; null = none, and today's launches.  With it every iteration's candidates are actuated in place behind the knot shaping, their
-// rate cost comes off the candidate score behind cadm_particle_score, and the plan is actuated once more (n = 1) on a device copy before
-// it is written to plan_out; advance: then prev <- plan[:, 0], prefix[:, j] <- plan[:, 1 + j].
-// unc: an uncertainty term (uncertainty.hip); null = none, and today's launches.  With it every rollout records its trajectories, TERMINATE
-// constraints hand their first violations on (with or without terms), and lambda times the cost of the counted steps comes off the
-// candidate score behind the actuator's: a statistic OVER the particles, so not off the particle rows.
-// value: a terminal value (value.hip) of the net registered with cadm_set_value_net; null = none, and today's launches.  With it every
-// rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * V(traj[H - 1]) is added to the
-// particle rows behind the constraints and the tracking terms and before the score: a risk-aware score sees return + value per particle.
-// reward: a learned step reward (reward.hip) of the net registered with cadm_set_reward_net; null = none, and today's launches.  With it
-// every rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * (the sum of R over the
-// counted steps) is added to the particle rows behind the constraints and the tracking terms and IN FRONT OF the terminal value.
-// The ctx's discount over the horizon (cadm_set_discount, discount.hip) is not a parameter: with a table set every rollout records its
-// trajectories, the env's own return is rewritten as sum_t disc[t] r_t directly behind the rollout (cadm_launch_discount), and every stage
-// below weighs its steps by the same table; a terminal term's weight is multiplied by disc[H].  No table: today's launches.
-// policy: a policy prior (policy.hip) of the net registered with cadm_set_policy_net; null = none, and today's launches.  With it ONE
-// proposal roll behind the context encoder, and in every iteration its P sequences take the slots behind the kept elites and the mean
-// candidate, in front of the knot shaping and the actuator pass.
-// critic: a terminal Q (critic.hip) of the critics registered with cadm_set_critic_nets at the action of the registered policy net; null =
-// none, and today's launches.  It stands where the terminal value stands and excludes it: weight * reduce_c Q_c(s, pi(s)), s = traj[H - 1],
-// is added to the particle rows behind the constraints, the tracking terms and the learned reward, before the score.  `policy` may be
-// null with it: the critic needs the registered net, not the proposals.
 static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_params* score, const cadm_icem_params* prm, const float* obs,
                      const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
-                     float* best_return_out, void* stream, const cadm_constraint_params* constraints = nullptr,
-                     const cadm_knot_params* knots = nullptr, const int32_t* phase = nullptr, const cadm_track_params* terms = nullptr,
-                     const float* targets = nullptr, int T = 0, const int32_t* offset = nullptr, const cadm_actuator_params* act = nullptr,
-                     float* prev_io = nullptr, float* prefix_io = nullptr, int advance = 0,
-                     const cadm_uncertainty_params* unc = nullptr, const cadm_value_params* value = nullptr,
-                     const cadm_reward_params* reward = nullptr, const cadm_policy_params* policy = nullptr,
-                     const cadm_critic_params* critic = nullptr) {
+                     float* best_return_out, void* stream, const PlanTerms& t) {
+    // (the fields by name, in their order: the body below reads them as it read its parameters)
+    const auto& [constraints, knots, phase, terms, targets, T, offset, act, prev_io, prefix_io, advance, unc, value, reward, policy, critic] = t;
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -594,7 +604,7 @@ extern "C" int cadm_icem_plan(cadm_ctx* ctx, const cadm_icem_params* prm, const 
                               uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
     const PlanUpdate upd{"cadm_icem_plan", 0, 0.0f, 0};
     return icem_loop(ctx, upd, nullptr, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call, workspace,
-                     plan_out, best_return_out, stream);
+                     plan_out, best_return_out, stream, PlanTerms{});
 }
 
 // the same loop with the MPPI update (mppi.hip) in place of the elite refit
@@ -604,64 +614,67 @@ extern "C" int cadm_mppi_plan(cadm_ctx* ctx, const cadm_mppi_params* prm, const 
     CADM_REQUIRE(prm, "cadm_mppi_plan: bad arguments");
     const PlanUpdate upd{"cadm_mppi_plan", 1, prm->temperature, prm->relative};
     return icem_loop(ctx, upd, nullptr, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream);
+                     workspace, plan_out, best_return_out, stream, PlanTerms{});
 }
 
-// the same loop with the update and the candidate score chosen by the caller (score.hip); score null or MEAN: the launches of the two above
+// The nest: ten exports, each the one before it with its own term's parameters in front; a level whose own struct is null enqueues the
+// launches of the level below.  Each fills the leading fields of a PlanTerms -- its own parameters, in the struct's order -- and leaves the
+// rest "no term".  What all ten refuse first, in this order, the update they choose, and the loop:
+static int nest_plan(const char* who, const PlanTerms& t, cadm_ctx* ctx, const cadm_score_params* score, int update, const cadm_mppi_params* prm,
+                     const float* obs, const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                     int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                     float* best_return_out, void* stream) {
+    CADM_REQUIRE(prm, "%s: bad arguments", who);
+    CADM_REQUIRE(update == 0 || update == 1, "%s: update %d is not 0 (elite refit) or 1 (MPPI)", who, update);
+    const PlanUpdate upd{who, update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
+    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
+                     workspace, plan_out, best_return_out, stream, t);
+}
+
+// the innermost: the update and the candidate score chosen by the caller (score.hip); score null or MEAN: the launches of the two above
 extern "C" int cadm_scored_plan(cadm_ctx* ctx, const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs,
                                 const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                                 int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                                 float* best_return_out, void* stream) {
-    CADM_REQUIRE(prm, "cadm_scored_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_scored_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_scored_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream);
+    return nest_plan("cadm_scored_plan", PlanTerms{}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io,
+                     carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out, stream);
 }
 
-// the same loop once more, with state constraints (constrain.hip) between the rollout and the score; constraints null: cadm_scored_plan's launches
+// adds state constraints (constrain.hip) between the rollout and the score; constraints null: cadm_scored_plan's launches
 extern "C" int cadm_constrained_plan(cadm_ctx* ctx, const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
                                      const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
                                      const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                                      uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
-    CADM_REQUIRE(prm, "cadm_constrained_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_constrained_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_constrained_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints);
+    return nest_plan("cadm_constrained_plan", PlanTerms{constraints}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var,
+                     carry_io, carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out, stream);
 }
 
-// and once more, with every candidate shaped onto a grid of knot steps (knots.hip) between the injections and the rollout; knots null or
+// adds the shaping of every candidate onto a grid of knot steps (knots.hip) between the injections and the rollout; knots null or
 // spacing 1: cadm_constrained_plan's launches
 extern "C" int cadm_knot_plan(cadm_ctx* ctx, const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
                               const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs, const float* cp_obs,
                               const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io,
                               int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out,
                               void* stream) {
-    CADM_REQUIRE(prm, "cadm_knot_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_knot_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_knot_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints, knots, phase);
+    return nest_plan("cadm_knot_plan", PlanTerms{constraints, knots, phase}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean,
+                     init_var, carry_io, carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out, stream);
 }
 
-// the outermost of the nest: with the cost of run-time tracking targets (tracking.hip) taken off the particle returns between the
-// constraints and the score; track null: cadm_knot_plan's launches
+// adds the cost of run-time tracking targets (tracking.hip), taken off the particle returns between the constraints and the score;
+// track null: cadm_knot_plan's launches
 extern "C" int cadm_tracking_plan(cadm_ctx* ctx, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
                                   const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
                                   const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs,
                                   const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                                   int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                                   float* best_return_out, void* stream) {
-    CADM_REQUIRE(prm, "cadm_tracking_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_tracking_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_tracking_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset);
+    return nest_plan("cadm_tracking_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset}, ctx, score, update, prm, obs,
+                     cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out,
+                     stream);
 }
 
-// the outermost of the nest: with an actuator model (actuator.hip) between the knot shaping and the rollout, its rate cost behind the score
-// and its last pass over the plan; act null: cadm_tracking_plan's launches
+// adds an actuator model (actuator.hip) between the knot shaping and the rollout, its rate cost behind the score and its last pass over
+// the plan; act null: cadm_tracking_plan's launches
 extern "C" int cadm_actuated_plan(cadm_ctx* ctx, const cadm_actuator_params* act, float* prev_io, float* prefix_io, int advance,
                                   const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
                                   const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
@@ -669,16 +682,13 @@ extern "C" int cadm_actuated_plan(cadm_ctx* ctx, const cadm_actuator_params* act
                                   const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                                   int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                                   float* best_return_out, void* stream) {
-    CADM_REQUIRE(prm, "cadm_actuated_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_actuated_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_actuated_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
-                     advance);
+    return nest_plan("cadm_actuated_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
+                     advance}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed,
+                     call, workspace, plan_out, best_return_out, stream);
 }
 
-// the outermost of the nest: with the ensemble's disagreement about the states a candidate visits (uncertainty.hip) priced off the candidate
-// score, behind the actuator's cost and before the refit; unc null: cadm_actuated_plan's launches
+// adds the price of the ensemble's disagreement about the states a candidate visits (uncertainty.hip), off the candidate score, behind
+// the actuator's cost and before the refit; unc null: cadm_actuated_plan's launches
 extern "C" int cadm_uncertain_plan(cadm_ctx* ctx, const cadm_uncertainty_params* unc, const cadm_actuator_params* act, float* prev_io,
                                    float* prefix_io, int advance, const cadm_track_params* track, const float* targets, int T,
                                    const int32_t* offset, const cadm_knot_params* knots, const int32_t* phase,
@@ -686,16 +696,13 @@ extern "C" int cadm_uncertain_plan(cadm_ctx* ctx, const cadm_uncertainty_params*
                                    const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
                                    const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                                    uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
-    CADM_REQUIRE(prm, "cadm_uncertain_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_uncertain_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_uncertain_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
-                     advance, unc);
+    return nest_plan("cadm_uncertain_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
+                     advance, unc}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed,
+                     call, workspace, plan_out, best_return_out, stream);
 }
 
-// the outermost of the nest: with weight * V of every particle's last state (value.hip, the net of cadm_set_value_net) added to the
-// particle returns, behind the constraints and the tracking terms and before the score; value null: cadm_uncertain_plan's launches
+// adds weight * V of every particle's last state (value.hip, the net of cadm_set_value_net) to the particle returns, behind the
+// constraints and the tracking terms and before the score; value null: cadm_uncertain_plan's launches
 extern "C" int cadm_valued_plan(cadm_ctx* ctx, const cadm_value_params* value, const cadm_uncertainty_params* unc,
                                 const cadm_actuator_params* act, float* prev_io, float* prefix_io, int advance,
                                 const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
@@ -704,16 +711,13 @@ extern "C" int cadm_valued_plan(cadm_ctx* ctx, const cadm_value_params* value, c
                                 const float* cp_act, const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io,
                                 int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out,
                                 void* stream) {
-    CADM_REQUIRE(prm, "cadm_valued_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_valued_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_valued_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
-                     advance, unc, value);
+    return nest_plan("cadm_valued_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io, advance,
+                     unc, value}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed,
+                     call, workspace, plan_out, best_return_out, stream);
 }
 
-// the outermost of the nest: with weight * (the sum over the counted steps of R, reward.hip, the net of cadm_set_reward_net) added to the
-// particle returns, behind the constraints and the tracking terms and in front of the terminal value; reward null: cadm_valued_plan's launches
+// adds weight * (the sum over the counted steps of R, reward.hip, the net of cadm_set_reward_net) to the particle returns, behind the
+// constraints and the tracking terms and in front of the terminal value; reward null: cadm_valued_plan's launches
 extern "C" int cadm_rewarded_plan(cadm_ctx* ctx, const cadm_reward_params* reward, const cadm_value_params* value,
                                   const cadm_uncertainty_params* unc, const cadm_actuator_params* act, float* prev_io, float* prefix_io,
                                   int advance, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
@@ -722,16 +726,13 @@ extern "C" int cadm_rewarded_plan(cadm_ctx* ctx, const cadm_reward_params* rewar
                                   const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                                   int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                                   float* best_return_out, void* stream) {
-    CADM_REQUIRE(prm, "cadm_rewarded_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_rewarded_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_rewarded_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
-                     advance, unc, value, reward);
+    return nest_plan("cadm_rewarded_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io, advance,
+                     unc, value, reward}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n,
+                     seed, call, workspace, plan_out, best_return_out, stream);
 }
 
-// the outermost of the nest: with the proposals of a caller-supplied policy net (policy.hip, the net of cadm_set_policy_net), rolled through
-// the model once per call, among every iteration's candidates; policy null: cadm_rewarded_plan's launches
+// adds the proposals of a caller-supplied policy net (policy.hip, the net of cadm_set_policy_net), rolled through the model once per
+// call, among every iteration's candidates; policy null: cadm_rewarded_plan's launches
 extern "C" int cadm_guided_plan(cadm_ctx* ctx, const cadm_policy_params* policy, const cadm_reward_params* reward,
                                 const cadm_value_params* value, const cadm_uncertainty_params* unc, const cadm_actuator_params* act,
                                 float* prev_io, float* prefix_io, int advance, const cadm_track_params* track, const float* targets, int T,
@@ -740,16 +741,13 @@ extern "C" int cadm_guided_plan(cadm_ctx* ctx, const cadm_policy_params* policy,
                                 const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
                                 const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                                 uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
-    CADM_REQUIRE(prm, "cadm_guided_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_guided_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_guided_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
-                     advance, unc, value, reward, policy);
+    return nest_plan("cadm_guided_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io, advance,
+                     unc, value, reward, policy}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io,
+                     carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out, stream);
 }
 
-// the outermost of the nest: with weight * reduce_c Q_c(s_H, pi(s_H)) of every particle's last state (critic.hip, the critics of
-// cadm_set_critic_nets at the action of the net of cadm_set_policy_net) added to the particle returns where the terminal value would be;
+// the outermost level today: adds weight * reduce_c Q_c(s_H, pi(s_H)) of every particle's last state (critic.hip, the critics of
+// cadm_set_critic_nets at the action of the net of cadm_set_policy_net) to the particle returns where the terminal value would be;
 // critic null: cadm_guided_plan's launches
 extern "C" int cadm_critic_plan(cadm_ctx* ctx, const cadm_critic_params* critic, const cadm_policy_params* policy,
                                 const cadm_reward_params* reward, const cadm_value_params* value, const cadm_uncertainty_params* unc,
@@ -759,10 +757,7 @@ extern "C" int cadm_critic_plan(cadm_ctx* ctx, const cadm_critic_params* critic,
                                 const cadm_mppi_params* prm, const float* obs, const float* cp_obs, const float* cp_act,
                                 const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n,
                                 uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
-    CADM_REQUIRE(prm, "cadm_critic_plan: bad arguments");
-    CADM_REQUIRE(update == 0 || update == 1, "cadm_critic_plan: update %d is not 0 (elite refit) or 1 (MPPI)", update);
-    const PlanUpdate upd{"cadm_critic_plan", update, update ? prm->temperature : 0.0f, update ? prm->relative : 0};
-    return icem_loop(ctx, upd, score, &prm->icem, obs, cp_obs, cp_act, init_mean, init_var, carry_io, carry_valid_io, m, n, seed, call,
-                     workspace, plan_out, best_return_out, stream, constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io,
-                     advance, unc, value, reward, policy, critic);
+    return nest_plan("cadm_critic_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io, advance,
+                     unc, value, reward, policy, critic}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io,
+                     carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out, stream);
 }

@@ -39,6 +39,38 @@ def ctx_param_names(n_cp_hidden):
     return names + ["cp_output_weight", "cp_output_bias"]
 
 
+# The nest of the opt-in loop's entry points, inner to outer.  Per level: the method (its export is cadm_<method>); what that export takes
+# in front of the level below's arguments, in its order -- the method takes the same but "update" (read off the params) and "T" (read off
+# the targets) --; and, for a level with workspace slots of its own, the slot's tag and how many of (terminate, actuator, uncertainty, P)
+# key the slot and size it (cadm_<level>_workspace_bytes).  The levels without a tag share the slots `_loop_workspace` names by what they
+# are given.  From `actuated_plan` outwards a level whose own struct (its first argument) is None hands the call to the level below.
+# A thirteenth term is one row here and one public method of one call; in the library, one export and one field of PlanTerms.
+_PLAN_NEST = (
+    ("scored_plan", ("score", "update", "params"), None, 0),
+    ("constrained_plan", ("constraints",), None, 0),
+    ("knot_plan", ("knots", "phase"), None, 0),
+    ("tracking_plan", ("track", "targets", "T", "offset"), None, 0),
+    ("actuated_plan", ("actuator", "prev", "prefix", "advance"), None, 0),
+    ("uncertain_plan", ("uncertainty",), "unc", 2),
+    ("valued_plan", ("value",), "val", 3),
+    ("rewarded_plan", ("reward",), "rew", 3),
+    ("guided_plan", ("policy",), "pol", 4),
+    ("critic_plan", ("critic",), "crt", 4),
+)
+_PLAN_LEVEL = {row[0]: i for i, row in enumerate(_PLAN_NEST)}
+# how many arguments each level's export takes between ctx and obs, and each level's method in front of obs
+_PLAN_NHEAD = [sum(len(row[1]) for row in _PLAN_NEST[:i + 1]) for i in range(len(_PLAN_NEST))]
+_PLAN_NARGS = [sum(len(set(row[1]) - {"update", "T"}) for row in _PLAN_NEST[:i + 1]) for i in range(len(_PLAN_NEST))]
+# outer to inner: (method, where its own struct stands in the outermost method's arguments); (slot tag, size export) of the levels with one
+_PLAN_ROUTES = tuple((row[0], -n) for row, n in zip(reversed(_PLAN_NEST), reversed(_PLAN_NARGS)))
+_PLAN_SLOTS = tuple((row[2], "cadm_%s_workspace_bytes" % row[0][:-len("_plan")]) for row in reversed(_PLAN_NEST) if row[2])
+_KNOT, _ACTUATED = _PLAN_LEVEL["knot_plan"], _PLAN_LEVEL["actuated_plan"]
+
+
+def _by(struct):
+    return None if struct is None else ct.byref(struct)
+
+
 class HipEngine:
     def __init__(self, env_kind, E, p, D, A, P, C, hidden_sizes, H, deterministic=False, discrete=False,
                  reference_quirks=True, history_length=10, cp_hidden_sizes=(256, 128, 64), back_model=False,
@@ -591,39 +623,51 @@ class HipEngine:
         Arguments as `icem_plan` behind its params.  First of all `rewarded_plan`, when it holds a learned reward, then `valued_plan`, when
         it holds a terminal value, then `uncertain_plan`, when it holds an uncertainty term.  Before all of them `guided_plan`, when it
         holds a policy prior; and before that `critic_plan`, when it holds a terminal Q."""
-        if getattr(opt, "critic_params", None) is not None:
-            return self.critic_plan(opt.critic_params, opt.policy_params, opt.reward_params, opt.value_params, opt.uncertainty_params,
-                                    opt.actuator_params, act_prev, act_prefix, opt.action_advance, opt.track_params, targets, target_offset,
-                                    opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params, *args, **kw)
-        if getattr(opt, "policy_params", None) is not None:
-            return self.guided_plan(opt.policy_params, opt.reward_params, opt.value_params, opt.uncertainty_params, opt.actuator_params,
-                                    act_prev, act_prefix, opt.action_advance, opt.track_params, targets, target_offset, opt.knot_params, phase,
-                                    opt.constraint_params, opt.score_params, opt.params, *args, **kw)
-        if getattr(opt, "reward_params", None) is not None:
-            return self.rewarded_plan(opt.reward_params, opt.value_params, opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix,
-                                      opt.action_advance, opt.track_params, targets, target_offset, opt.knot_params, phase,
-                                      opt.constraint_params, opt.score_params, opt.params, *args, **kw)
-        if getattr(opt, "value_params", None) is not None:
-            return self.valued_plan(opt.value_params, opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix, opt.action_advance,
-                                    opt.track_params, targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params,
-                                    opt.params, *args, **kw)
-        if getattr(opt, "uncertainty_params", None) is not None:
-            return self.uncertain_plan(opt.uncertainty_params, opt.actuator_params, act_prev, act_prefix, opt.action_advance, opt.track_params,
-                                       targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params,
-                                       *args, **kw)
-        if opt.actuator_params is not None:
-            return self.actuated_plan(opt.actuator_params, act_prev, act_prefix, opt.action_advance, opt.track_params, targets, target_offset,
-                                      opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params, *args, **kw)
-        if opt.track_params is not None:
-            return self.tracking_plan(opt.track_params, targets, target_offset, opt.knot_params, phase, opt.constraint_params, opt.score_params,
-                                      opt.params, *args, **kw)
-        if opt.knot_params is not None:
-            return self.knot_plan(opt.knot_params, phase, opt.constraint_params, opt.score_params, opt.params, *args, **kw)
-        if opt.constraint_params is not None:
-            return self.constrained_plan(opt.constraint_params, opt.score_params, opt.params, *args, **kw)
-        if opt.score_params is not None:
-            return self.scored_plan(opt.score_params, opt.params, *args, **kw)
+        full = (getattr(opt, "critic_params", None), getattr(opt, "policy_params", None), getattr(opt, "reward_params", None),
+                getattr(opt, "value_params", None), getattr(opt, "uncertainty_params", None), opt.actuator_params, act_prev, act_prefix,
+                getattr(opt, "action_advance", None), opt.track_params, targets, target_offset, opt.knot_params, phase,
+                opt.constraint_params, opt.score_params, opt.params)      # the outermost method's arguments
+        for method, own in _PLAN_ROUTES:      # the outermost level whose own struct the options hold
+            if full[own] is not None:
+                return getattr(self, method)(*full[own:], *args, **kw)
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
+
+    def _nest_plan(self, level, lead, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return):
+        """What the ten nested `*_plan` methods do (`_PLAN_NEST`); level: the method called, lead: its arguments in front of obs.  Finds
+        the level that answers -- its name is the one in the messages, its export the one called, its slot the workspace --, checks what
+        the host can check, builds the export's arguments between the ctx and obs, and calls `_loop_plan`."""
+        i = _PLAN_LEVEL[level]
+        full = (None,) * (_PLAN_NARGS[-1] - len(lead)) + lead
+        while i >= _ACTUATED and full[-_PLAN_NARGS[i]] is None:
+            i -= 1
+        who, _, tag, nflags = _PLAN_NEST[i]
+        (critic, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score,
+         params) = full
+        mppi, params = self._as_mppi_params(params)
+        m = int(np.shape(obs)[0]) if i >= _KNOT else None      # (the two levels below have nothing per env to check)
+        if actuator is None:
+            prev = prefix = None
+        else:
+            for name, t in (("prev", prev), ("prefix", prefix)):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+                    raise ValueError("%s: %s must be a float32 device tensor (it is moved on in place)" % (who, name))
+            if prev is None or (prefix is None and actuator.delay > 0):
+                raise ValueError("%s: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay" % who)
+            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, who)
+        phase = self._phase(phase, m, who)
+        T = 0
+        if track is None:      # the library's own route to the loop underneath, with that loop's workspace
+            targets = offset = None
+        else:
+            targets, T, offset = self._targets(targets, offset, m, track.n, who)
+        head = (_by(critic), _by(policy), _by(reward), _by(value), _by(uncertainty), _by(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
+                _by(track), ptr(targets), T, ptr(offset), _by(knots), ptr(phase), _by(constraints), _by(score), int(mppi), ct.byref(params))
+        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
+        flags = (terminate, actuator is not None, uncertainty is not None, 0 if policy is None else max(int(policy.n_samples), 0))
+        ws = {tag: flags[:nflags]} if tag else dict(traj=constraints is not None, track=None if track is None else terminate,
+                                                    act=actuator is not None)
+        return self._loop_plan(who, getattr(self.lib, "cadm_" + who), head[-_PLAN_NHEAD[i]:], mppi, params.icem.keep_elites, obs, cp_obs,
+                               cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, **ws)
 
     def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None, crt=None):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
@@ -639,44 +683,25 @@ class HipEngine:
         with a policy prior (`cadm_guided_workspace_bytes`: the rewarded loop's, and behind everything the proposals and the roll's
         workspace).  crt: None, or (terminate, actuator, uncertainty, P) -- the slot of a loop with a terminal Q
         (`cadm_critic_workspace_bytes`: the guided loop's; P = 0 without a policy prior in the same call)."""
-        slot = (bool(mppi), bool(traj)) if track is None else (bool(mppi), "track", bool(track))
-        if act:
-            slot = slot + ("act",)
-        if unc is not None:
-            slot = (bool(mppi), "unc", bool(unc[0]), bool(unc[1]))
-        if val is not None:
-            slot = (bool(mppi), "val", bool(val[0]), bool(val[1]), bool(val[2]))
-        if rew is not None:
-            slot = (bool(mppi), "rew", bool(rew[0]), bool(rew[1]), bool(rew[2]))
-        if pol is not None:
-            slot = (bool(mppi), "pol", bool(pol[0]), bool(pol[1]), bool(pol[2]), int(pol[3]))
-        if crt is not None:
-            slot = (bool(mppi), "crt", bool(crt[0]), bool(crt[1]), bool(crt[2]), int(crt[3]))
+        mppi = bool(mppi)
+        for (tag, size), flags in zip(_PLAN_SLOTS, (crt, pol, rew, val, unc)):      # the outermost term given names the slot and sizes it
+            if flags is not None:
+                flags = tuple(bool(f) for f in flags[:3]) + tuple(int(P) for P in flags[3:])
+                slot = (mppi, tag) + flags
+                break
+        else:                                                  # the levels below: a slot per combination of what they are given
+            slot = (mppi, bool(traj)) if track is None else (mppi, "track", bool(track))
+            if act:
+                slot, size, flags = slot + ("act",), "cadm_actuated_workspace_bytes", (bool(traj) or track is not None, bool(track))
+            elif track is not None:
+                size, flags = "cadm_tracking_workspace_bytes", (bool(track),)
+            elif traj:
+                size, flags = "cadm_constrained_workspace_bytes", ()
+            else:                                              # (the two plain ones take no update flag: one export each)
+                size, flags = "cadm_mppi_workspace_bytes" if mppi else "cadm_icem_workspace_bytes", None
         key, ws = self._loop_ws.get(slot, (None, None))
         if key != (m, n, K):
-            if crt is not None:
-                nbytes = self.lib.cadm_critic_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(crt[0])), int(bool(crt[1])),
-                                                              int(bool(crt[2])), int(crt[3]))
-            elif pol is not None:
-                nbytes = self.lib.cadm_guided_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(pol[0])), int(bool(pol[1])),
-                                                              int(bool(pol[2])), int(pol[3]))
-            elif rew is not None:
-                nbytes = self.lib.cadm_rewarded_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(rew[0])), int(bool(rew[1])),
-                                                                int(bool(rew[2])))
-            elif val is not None:
-                nbytes = self.lib.cadm_valued_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(val[0])), int(bool(val[1])),
-                                                              int(bool(val[2])))
-            elif unc is not None:
-                nbytes = self.lib.cadm_uncertain_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(unc[0])), int(bool(unc[1])))
-            elif act:
-                nbytes = self.lib.cadm_actuated_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(traj) or track is not None),
-                                                                int(bool(track)))
-            elif track is not None:
-                nbytes = self.lib.cadm_tracking_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)), int(bool(track)))
-            elif traj:
-                nbytes = self.lib.cadm_constrained_workspace_bytes(self._ctx, m, n, K, int(bool(mppi)))
-            else:
-                nbytes = (self.lib.cadm_mppi_workspace_bytes if mppi else self.lib.cadm_icem_workspace_bytes)(self._ctx, m, n, K)
+            nbytes = getattr(self.lib, size)(self._ctx, m, n, K, *(() if flags is None else (int(mppi),) + tuple(int(f) for f in flags)))
             ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
             self._loop_ws[slot] = ((m, n, K), ws)
         return ws
@@ -751,10 +776,8 @@ class HipEngine:
         """`cadm_scored_plan`: the loop of `icem_plan` (params from `icem_params`) or of `mppi_plan` (params from `mppi_params`) with
         `score` (`score_params`; None = the mean) in place of the particle mean.  The best return is then the best score.  Arguments as
         `icem_plan`; the workspaces are the ones those two cache."""
-        mppi, params = self._as_mppi_params(params)
-        head = (None if score is None else ct.byref(score), int(mppi), ct.byref(params))
-        return self._loop_plan("scored_plan", self.lib.cadm_scored_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
-                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
+        return self._nest_plan("scored_plan", (score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call,
+                               out, want_best_return)
 
     # ------------------------------------------------------------------ state constraints and termination (opt-in; csrc/constrain.hip)
     @staticmethod
@@ -833,10 +856,8 @@ class HipEngine:
         """`cadm_constrained_plan`: the loop of `scored_plan` with `constraints` (`constraint_params`; None = none, and `scored_plan`'s
         launches) rewriting every iteration's particle returns before the score.  Arguments behind `constraints` as `scored_plan`; with
         constraints the workspace carries the trajectory view (`cadm_constrained_workspace_bytes`), cached apart from the plain ones."""
-        mppi, params = self._as_mppi_params(params)
-        head = (None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi), ct.byref(params))
-        return self._loop_plan("constrained_plan", self.lib.cadm_constrained_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
-                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None)
+        return self._nest_plan("constrained_plan", (constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry,
+                               carry_valid, seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ discount over the horizon (opt-in; csrc/discount.hip)
     def set_discount(self, gamma):
@@ -923,12 +944,8 @@ class HipEngine:
         """`cadm_knot_plan`: the loop of `constrained_plan` with every iteration's candidates shaped onto the grid of `knots`
         (`knot_params`; None = none, and `constrained_plan`'s launches) before the rollout; phase [m] int32 (None: 0 for every env).
         Arguments behind `phase` as `constrained_plan`, and its workspaces."""
-        mppi, params = self._as_mppi_params(params)
-        phase = self._phase(phase, int(np.shape(obs)[0]), "knot_plan")
-        head = (None if knots is None else ct.byref(knots), ptr(phase), None if constraints is None else ct.byref(constraints),
-                None if score is None else ct.byref(score), int(mppi), ct.byref(params))
-        return self._loop_plan("knot_plan", self.lib.cadm_knot_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
-                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None)
+        return self._nest_plan("knot_plan", (knots, phase, constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry,
+                               carry_valid, seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ tracking targets at run time (opt-in; csrc/tracking.hip)
     @staticmethod
@@ -1020,20 +1037,8 @@ class HipEngine:
         against targets [m,T,K] or [m,K] at offset [m] int32 (None: 0 for every env) taken off every iteration's particle returns, behind
         the constraints and before the score.  Arguments behind `offset` as `knot_plan`; with terms the workspace is the tracking slot
         (`cadm_tracking_workspace_bytes`), cached apart from the others."""
-        mppi, params = self._as_mppi_params(params)
-        m = int(np.shape(obs)[0])
-        phase = self._phase(phase, m, "tracking_plan")
-        T = 0
-        if track is None:      # the library's own route to the loop underneath, with that loop's workspace
-            targets = offset = None
-        else:
-            targets, T, offset = self._targets(targets, offset, m, track.n, "tracking_plan")
-        head = (None if track is None else ct.byref(track), ptr(targets), T, ptr(offset), None if knots is None else ct.byref(knots), ptr(phase),
-                None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi), ct.byref(params))
-        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
-        return self._loop_plan("tracking_plan", self.lib.cadm_tracking_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
-                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None,
-                               track=None if track is None else terminate)
+        return self._nest_plan("tracking_plan", (track, targets, offset, knots, phase, constraints, score, params), obs, cp_obs, cp_act,
+                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ actuator model (opt-in; csrc/actuator.hip)
     @staticmethod
@@ -1108,30 +1113,8 @@ class HipEngine:
         score, the plan actuated once more before it is written.  prev [m,A] / prefix [m,delay,A] (prefix may be None with delay 0): the
         envs' actuator state on the device, device tensors that `advance` moves on IN PLACE by one step behind the plan.  Arguments
         behind `advance` as `tracking_plan`; the workspace is the actuated slot (`cadm_actuated_workspace_bytes`)."""
-        if actuator is None:
-            return self.tracking_plan(track, targets, offset, knots, phase, constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var,
-                                      n, carry=carry, carry_valid=carry_valid, seed=seed, call=call, out=out, want_best_return=want_best_return)
-        mppi, params = self._as_mppi_params(params)
-        m = int(np.shape(obs)[0])
-        for name, t in (("prev", prev), ("prefix", prefix)):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-                raise ValueError("actuated_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
-        if prev is None or (prefix is None and actuator.delay > 0):
-            raise ValueError("actuated_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
-        prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "actuated_plan")
-        phase = self._phase(phase, m, "actuated_plan")
-        T = 0
-        if track is None:
-            targets = offset = None
-        else:
-            targets, T, offset = self._targets(targets, offset, m, track.n, "actuated_plan")
-        head = (ct.byref(actuator), ptr(prev), ptr(prefix), int(bool(advance)), None if track is None else ct.byref(track), ptr(targets), T,
-                ptr(offset), None if knots is None else ct.byref(knots), ptr(phase), None if constraints is None else ct.byref(constraints),
-                None if score is None else ct.byref(score), int(mppi), ct.byref(params))
-        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
-        return self._loop_plan("actuated_plan", self.lib.cadm_actuated_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
-                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, traj=constraints is not None,
-                               track=None if track is None else terminate, act=True)
+        return self._nest_plan("actuated_plan", (actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score,
+                               params), obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ pricing model uncertainty (opt-in; csrc/uncertainty.hip)
     @staticmethod
@@ -1210,34 +1193,9 @@ class HipEngine:
         (`uncertainty_params`; None = none, and `actuated_plan`'s launches) taken off every iteration's candidate scores, behind the
         actuator's cost and before the refit.  Arguments behind `uncertainty` as `actuated_plan`; the workspace is the slot of
         `cadm_uncertain_workspace_bytes`, cached apart from the others."""
-        if uncertainty is None:
-            return self.actuated_plan(actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score, params, obs,
-                                      cp_obs, cp_act, init_mean, init_var, n, carry=carry, carry_valid=carry_valid, seed=seed, call=call, out=out,
-                                      want_best_return=want_best_return)
-        mppi, params = self._as_mppi_params(params)
-        m = int(np.shape(obs)[0])
-        if actuator is None:
-            prev = prefix = None
-        else:
-            for name, t in (("prev", prev), ("prefix", prefix)):
-                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-                    raise ValueError("uncertain_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
-            if prev is None or (prefix is None and actuator.delay > 0):
-                raise ValueError("uncertain_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
-            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "uncertain_plan")
-        phase = self._phase(phase, m, "uncertain_plan")
-        T = 0
-        if track is None:
-            targets = offset = None
-        else:
-            targets, T, offset = self._targets(targets, offset, m, track.n, "uncertain_plan")
-        head = (ct.byref(uncertainty), None if actuator is None else ct.byref(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
-                None if track is None else ct.byref(track), ptr(targets), T, ptr(offset), None if knots is None else ct.byref(knots), ptr(phase),
-                None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi), ct.byref(params))
-        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
-        return self._loop_plan("uncertain_plan", self.lib.cadm_uncertain_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
-                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return,
-                               unc=(terminate, actuator is not None))
+        return self._nest_plan("uncertain_plan", (uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase,
+                               constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call,
+                               out, want_best_return)
 
     # ------------------------------------------------------------------ terminal value (opt-in; csrc/value.hip)
     @staticmethod
@@ -1441,35 +1399,9 @@ class HipEngine:
         state added to the particle returns, behind the constraints and the tracking terms and before the score (`value`: a
         `value_params` describing the net of `set_value_net`; None = none, and `uncertain_plan`'s launches).  Arguments behind `value` as
         `uncertain_plan`; the workspace is the slot of `cadm_valued_workspace_bytes`, cached apart from the others."""
-        if value is None:
-            return self.uncertain_plan(uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score,
-                                       params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=carry, carry_valid=carry_valid, seed=seed,
-                                       call=call, out=out, want_best_return=want_best_return)
-        mppi, params = self._as_mppi_params(params)
-        m = int(np.shape(obs)[0])
-        if actuator is None:
-            prev = prefix = None
-        else:
-            for name, t in (("prev", prev), ("prefix", prefix)):
-                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-                    raise ValueError("valued_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
-            if prev is None or (prefix is None and actuator.delay > 0):
-                raise ValueError("valued_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
-            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "valued_plan")
-        phase = self._phase(phase, m, "valued_plan")
-        T = 0
-        if track is None:
-            targets = offset = None
-        else:
-            targets, T, offset = self._targets(targets, offset, m, track.n, "valued_plan")
-        head = (ct.byref(value), None if uncertainty is None else ct.byref(uncertainty), None if actuator is None else ct.byref(actuator),
-                ptr(prev), ptr(prefix), int(bool(advance)), None if track is None else ct.byref(track), ptr(targets), T, ptr(offset),
-                None if knots is None else ct.byref(knots), ptr(phase), None if constraints is None else ct.byref(constraints),
-                None if score is None else ct.byref(score), int(mppi), ct.byref(params))
-        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
-        return self._loop_plan("valued_plan", self.lib.cadm_valued_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act, init_mean,
-                               init_var, n, carry, carry_valid, seed, call, out, want_best_return,
-                               val=(terminate, actuator is not None, uncertainty is not None))
+        return self._nest_plan("valued_plan", (value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase,
+                               constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call,
+                               out, want_best_return)
 
     # ------------------------------------------------------------------ learned reward (opt-in; csrc/reward.hip)
     @staticmethod
@@ -1549,36 +1481,9 @@ class HipEngine:
         particle returns, behind the constraints and the tracking terms and in front of the terminal value (`reward`: a `reward_params`
         describing the net of `set_reward_net`; None = none, and `valued_plan`'s launches).  Arguments behind `reward` as `valued_plan`;
         the workspace is the slot of `cadm_rewarded_workspace_bytes`, cached apart from the others."""
-        if reward is None:
-            return self.valued_plan(value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints,
-                                    score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=carry, carry_valid=carry_valid,
-                                    seed=seed, call=call, out=out, want_best_return=want_best_return)
-        mppi, params = self._as_mppi_params(params)
-        m = int(np.shape(obs)[0])
-        if actuator is None:
-            prev = prefix = None
-        else:
-            for name, t in (("prev", prev), ("prefix", prefix)):
-                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-                    raise ValueError("rewarded_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
-            if prev is None or (prefix is None and actuator.delay > 0):
-                raise ValueError("rewarded_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
-            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "rewarded_plan")
-        phase = self._phase(phase, m, "rewarded_plan")
-        T = 0
-        if track is None:
-            targets = offset = None
-        else:
-            targets, T, offset = self._targets(targets, offset, m, track.n, "rewarded_plan")
-        head = (ct.byref(reward), None if value is None else ct.byref(value), None if uncertainty is None else ct.byref(uncertainty),
-                None if actuator is None else ct.byref(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
-                None if track is None else ct.byref(track), ptr(targets), T, ptr(offset), None if knots is None else ct.byref(knots),
-                ptr(phase), None if constraints is None else ct.byref(constraints), None if score is None else ct.byref(score), int(mppi),
-                ct.byref(params))
-        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
-        return self._loop_plan("rewarded_plan", self.lib.cadm_rewarded_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act,
-                               init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return,
-                               rew=(terminate, actuator is not None, uncertainty is not None))
+        return self._nest_plan("rewarded_plan", (reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots,
+                               phase, constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed,
+                               call, out, want_best_return)
 
     # ------------------------------------------------------------------ policy prior (opt-in; csrc/policy.hip)
     @staticmethod
@@ -1750,34 +1655,9 @@ class HipEngine:
         describing the net of `set_policy_net`; None = none, and `rewarded_plan`'s launches) rolled through the model once and placed
         among every iteration's candidates, behind the kept elites and the mean candidate.  Arguments behind `policy` as
         `rewarded_plan`; the workspace is the slot of `cadm_guided_workspace_bytes`, cached apart from the others."""
-        if policy is None:
-            return self.rewarded_plan(reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase,
-                                      constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=carry,
-                                      carry_valid=carry_valid, seed=seed, call=call, out=out, want_best_return=want_best_return)
-        mppi, params = self._as_mppi_params(params)
-        m = int(np.shape(obs)[0])
-        if actuator is None:
-            prev = prefix = None
-        else:
-            for name, t in (("prev", prev), ("prefix", prefix)):
-                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-                    raise ValueError("guided_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
-            if prev is None or (prefix is None and actuator.delay > 0):
-                raise ValueError("guided_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
-            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "guided_plan")
-        phase = self._phase(phase, m, "guided_plan")
-        T = 0
-        if track is None:
-            targets = offset = None
-        else:
-            targets, T, offset = self._targets(targets, offset, m, track.n, "guided_plan")
-        by = lambda x: None if x is None else ct.byref(x)
-        head = (ct.byref(policy), by(reward), by(value), by(uncertainty), by(actuator), ptr(prev), ptr(prefix), int(bool(advance)), by(track),
-                ptr(targets), T, ptr(offset), by(knots), ptr(phase), by(constraints), by(score), int(mppi), ct.byref(params))
-        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
-        return self._loop_plan("guided_plan", self.lib.cadm_guided_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act, init_mean,
-                               init_var, n, carry, carry_valid, seed, call, out, want_best_return,
-                               pol=(terminate, actuator is not None, uncertainty is not None, max(int(policy.n_samples), 0)))
+        return self._nest_plan("guided_plan", (policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset,
+                               knots, phase, constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid,
+                               seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ terminal value from Q critics (opt-in; csrc/critic.hip)
     @staticmethod
@@ -1864,35 +1744,9 @@ class HipEngine:
         `critic_params` describing the critics of `set_critic_nets`; None = none, and `guided_plan`'s launches).  `policy` may be None
         while a policy net is registered.  Arguments behind `critic` as `guided_plan`; the workspace is the slot of
         `cadm_critic_workspace_bytes`, cached apart from the others."""
-        if critic is None:
-            return self.guided_plan(policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase,
-                                    constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=carry,
-                                    carry_valid=carry_valid, seed=seed, call=call, out=out, want_best_return=want_best_return)
-        mppi, params = self._as_mppi_params(params)
-        m = int(np.shape(obs)[0])
-        if actuator is None:
-            prev = prefix = None
-        else:
-            for name, t in (("prev", prev), ("prefix", prefix)):
-                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-                    raise ValueError("critic_plan: %s must be a float32 device tensor (it is moved on in place)" % name)
-            if prev is None or (prefix is None and actuator.delay > 0):
-                raise ValueError("critic_plan: the actuator model needs prev [m,A], and prefix [m,delay,A] with a delay")
-            prev, prefix = self._actuator_state(prev, prefix, m, actuator.delay, "critic_plan")
-        phase = self._phase(phase, m, "critic_plan")
-        T = 0
-        if track is None:
-            targets = offset = None
-        else:
-            targets, T, offset = self._targets(targets, offset, m, track.n, "critic_plan")
-        by = lambda x: None if x is None else ct.byref(x)
-        head = (ct.byref(critic), by(policy), by(reward), by(value), by(uncertainty), by(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
-                by(track), ptr(targets), T, ptr(offset), by(knots), ptr(phase), by(constraints), by(score), int(mppi), ct.byref(params))
-        terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
-        P = 0 if policy is None else max(int(policy.n_samples), 0)
-        return self._loop_plan("critic_plan", self.lib.cadm_critic_plan, head, mppi, params.icem.keep_elites, obs, cp_obs, cp_act, init_mean,
-                               init_var, n, carry, carry_valid, seed, call, out, want_best_return,
-                               crt=(terminate, actuator is not None, uncertainty is not None, P))
+        return self._nest_plan("critic_plan", (critic, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets,
+                               offset, knots, phase, constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry,
+                               carry_valid, seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

@@ -768,7 +768,7 @@ size_t cadm_reward_workspace_bytes(cadm_ctx* ctx, int m, int n);
 int cadm_reward_returns(cadm_ctx* ctx, const cadm_reward_params* params, const float* traj, const float* obs, const float* actions,
                         const int32_t* first, int m, int n, const float* rows_in, float* rows_out, float* step_out, float* sum_out,
                         void* workspace, void* stream);
-/* The loop of cadm_valued_plan with that term in the particle returns: the outermost entry of the nest.  Every iteration's rollout
+/* The loop of cadm_valued_plan with that term in the particle returns: the next level of the nest.  Every iteration's rollout
  * records its trajectories; TERMINATE constraints write their first violations into the workspace.  Per iteration: rollout ->
  * constraints -> tracking -> rows[q] += weight * S[q] on the particle rows [m,n_it,p] -> the terminal value -> cadm_particle_score (a
  * risk-aware score sees return + learned reward (+ value) per particle) -> the actuator's and the uncertainty term's costs off the
@@ -837,7 +837,7 @@ int cadm_policy_eval(cadm_ctx* ctx, const float* states, int R, float* act_out, 
 size_t cadm_policy_workspace_bytes(cadm_ctx* ctx, int m, int P);
 int cadm_policy_propose(cadm_ctx* ctx, const cadm_policy_params* params, const float* obs, const float* ctx_vec, int m, uint32_t seed,
                         uint32_t call, float* seqs_out, float* states_out, void* workspace, void* stream);
-/* The loop of cadm_rewarded_plan with the policy's proposals among its candidates: the outermost entry of the nest.  Behind the context
+/* The loop of cadm_rewarded_plan with the policy's proposals among its candidates: the next level of the nest.  Behind the context
  * encoder ONE cadm_policy_propose; every iteration then writes the P sequences into the candidate slots [K + (last iteration &&
  * add_mean_last ? 1 : 0), .. + P) -- behind the kept elites and the mean candidate, in front of the knot shaping and the actuator pass,
  * so proposals are shaped and pinned like any other candidate.  policy NULL: exactly the launches of cadm_rewarded_plan.  Refusals: those
@@ -908,7 +908,7 @@ int cadm_critic_eval(cadm_ctx* ctx, const float* states, const float* actions, i
                      void* stream);
 int cadm_critic_returns(cadm_ctx* ctx, const cadm_critic_params* params, const float* traj, const int32_t* first, int m, int n,
                         const float* rows_in, float* rows_out, float* q_out, void* stream);
-/* The loop of cadm_guided_plan with that term in the particle returns: the outermost entry of the nest.  Per iteration the stage runs
+/* The loop of cadm_guided_plan with that term in the particle returns: the outermost level of the nest today.  Per iteration the stage runs
  * where the terminal value's runs: rollout -> constraints -> tracking -> the learned reward -> rows[q] += weight * r[q] on the particle
  * rows [m,n_it,p] -> cadm_particle_score -> the costs off the candidate score -> the refit.  critic NULL: exactly the launches of
  * cadm_guided_plan.  policy may be NULL while a policy net is registered: the term needs the registered net, not the proposals.
