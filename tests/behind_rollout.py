@@ -30,6 +30,21 @@ TERM_ENGINES = {      # name: (env, D, A, E, p, H); "widest" is helpers.corner_s
     "p1": ("halfcheetah", 18, 6, 1, 1, 5),
 }
 
+# tests/test_gpu_critic_envelope.py runs the Q critics' kernel on seven of them, kernel level (nothing is rolled out); tests/test_critic_ref.py
+# reads the shapes from here.  name: the (m, n) of its two launches -- KINDS' own where the kind has one, (3, 11) elsewhere, and one
+# candidate of one env: fewer than 16 rows.  Rows at the engine's p: pend 135 = 8 x 16 + 7 and 5, ant 210 = 13 x 16 + 2 and 10, slim
+# 150 = 9 x 16 + 6 and 15, wide 330 = 20 x 16 + 10 and 10, long and one 165 = 10 x 16 + 5 and 5, p1 33 = 2 x 16 + 1 and 1: every launch
+# ends in a partial tile.
+CRITIC_ROWS = {
+    "pend": [KINDS["pendulum"][4:6], (1, 1)], "ant": [KINDS["ant"][4:6], (1, 1)], "slim": [KINDS["slim_humanoid"][4:6], (1, 1)],
+    "wide": [(3, 11), (1, 1)], "long": [(3, 11), (1, 1)], "one": [(3, 11), (1, 1)], "p1": [(3, 11), (1, 1)],
+}
+CRITIC_GAMMA = 0.97      # "long": the discount the ctx carries, so that the row update multiplies by weight * disc[40]
+# "long": the seed of the poisoned rows and the `first` cuts of the non-finite test.  Of 165 rows with `first` drawn over 0 .. 40 about
+# four stay uncut; under the feature file's seed 13 none of them is a poisoned row, under 17 two poisoned and five clean ones are
+# (the draws are numpy's and do not depend on the device; the test asserts the condition before it launches).
+CRITIC_LONG_SEED = 17
+
 # The engines of tests/test_gpu_policy_envelope.py -- the policy prior's roll and the guided loop off halfcheetah at p in {5, 20}, H <= 5;
 # tests/test_policy_ref.py reads the shapes, the nets and the noise levels from here and shows on the CPU that the restatement alone
 # meets the conditions the GPU tests put on their inputs.  Every built-in kind at hidden 200 x 4 and swish (nothing is built on demand),

@@ -150,11 +150,12 @@ KERNEL_COMBOS = [(C, reduce, squash) for C in (1, 2, 3) for reduce in REDUCES fo
 KERNEL_ROWS = [(3, 11), (3, 1)]      # m, n at p = 5: 165 rows (ten full 16-row tiles and a tail of 5), 15 rows (less than a tile)
 
 
-def kernel_states(m, n, seed, H=3, p=5, D=11, A=3):
-    """(traj [H,m,n,p,D], its last states [m n p, D]) of behind_rollout.synth_traj"""
-    from behind_rollout import synth_traj
-    traj = synth_traj(seed, H, m, n, p, D, A)[0]
-    return traj, traj[-1].reshape(-1, D)
+def kernel_states(m, n, seed, H=3, p=5, D=11, A=3, name=None):
+    """(traj [H,m,n,p,D], its last states [m n p, D]) of behind_rollout.synth_traj; name: at the shape of that one of
+    behind_rollout.TERM_ENGINES (`term_traj`) in the place of H, p, D, A"""
+    from behind_rollout import synth_traj, term_traj
+    traj = synth_traj(seed, H, m, n, p, D, A)[0] if name is None else term_traj(name, m, n, seed)[0]
+    return traj, traj[-1].reshape(-1, traj.shape[-1])
 
 
 def kernel_case(states, A, hidden, phidden, C, act, squash, seed):
@@ -168,3 +169,14 @@ def kernel_case(states, A, hidden, phidden, C, act, squash, seed):
     mean = np.concatenate([(smean - F(0.2)).astype(F), np.full((A,), 0.05, F)])
     std = np.concatenate([(F(0.9) * sstd).astype(F), np.full((A,), 0.6, F)])
     return actor, critics, mean, std
+
+
+# The cases tests/test_gpu_critic_envelope.py runs on behind_rollout.CRITIC_ENGINES and tests/test_critic_ref.py holds to the liveness
+# conditions on the CPU: hidden widths off the multiples of 4 (value_ref.ENVELOPE_NETS: widths 1 and 3, a last 64-unit group of 1 or 2
+# units, four hidden layers) behind actors of one and of five dense layers; C cycles over (1, 4, 5) -- out of step with the actors,
+# which cycle with the same period --, the reduce over (min, mean), the squash over (tanh, none).  Every activation runs every case.
+ENVELOPE_CRITICS = [(1,), (3,), (65,), (130, 66), (50, 30, 70, 18), (37, 37, 37, 37)]
+ENVELOPE_ACTORS = [(), (50, 30, 70, 18), (37, 37, 37, 37)]
+ENVELOPE_CASES = [(hidden, phidden, (1, 4, 5)[(i + i // 3) % 3], REDUCES[i % 2], pref.SQUASH[(i // 2) % 2])
+                  for i, (hidden, phidden) in enumerate((h, ph) for h in ENVELOPE_CRITICS for ph in ENVELOPE_ACTORS)]
+assert all(tuple(h) in vref.ENVELOPE_NETS for h in ENVELOPE_CRITICS + ENVELOPE_ACTORS[1:])

@@ -103,3 +103,33 @@ def run_steps(state0, nexts, rows1s, sels, E, constraints=None, w=None):
     out = {name: np.stack(v) for name, v in cols.items()}
     out.update(states=np.stack(states), length=length, alive=alive)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the stage's groups
+GROUP, LDS_BUDGET = 16, 48 * 1024      # csrc/imagine.hip IMG_GROUP, IMG_LDS_BUDGET
+
+
+def lds_bytes(G, p, D):
+    """csrc/imagine.hip img_lds_bytes: the tile of G p D floats, G D variances and D weights, each padded to 4 floats, and G ints"""
+    pad4 = lambda v: (v + 3) & ~3
+    return 4 * (pad4(G * p * D) + pad4(G * D) + pad4(D) + G)
+
+
+def group(p, D):
+    """csrc/imagine.hip img_group: the rows a workgroup of the select stage owns -- 16, fewer where the tile would not fit 48 KiB
+    (0: not even one row's, and the stage is refused)"""
+    return max(G for G in range(0, GROUP + 1) if G == 0 or lds_bytes(G, p, D) <= LDS_BUDGET)
+
+
+# The kernel-level engines of tests/test_gpu_imagine_envelope.py -- name: (env, D, p, the group, the groups of its 37 rows) -- at which the
+# budget cuts the group below 16; "wide255": one row's tile of 12337 floats is beyond the 12288 of the budget
+STAGE_ENGINES = {
+    "slim35": ("slim_humanoid", 45, 35, 7, [7] * 5 + [2]),      # p D = 1575, odd: group starts of every alignment in one launch
+    "hc50": ("halfcheetah", 18, 50, 13, [13, 13, 11]),          # p D = 900
+    "wide30": ("widest", 48, 30, 8, [8] * 4 + [5]),             # p D = 1440
+    "wide125": ("widest", 48, 125, 2, [2] * 18 + [1]),          # p D = 6000; PE = 25; p > S = 256 / 48: the broadcast walk's carry
+    "wide255": ("widest", 48, 255, 0, None),
+}
+# where the stage test embeds its 37 rows in a batch of 150 so that their place inside a group moves: row 100, which is no multiple of 7, 13
+# or 8 -- and row 101 where the group is 2
+STAGE_AT = {"wide125": 101}

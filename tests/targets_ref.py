@@ -96,3 +96,106 @@ def targets(rew, valid, done, disagreement, boot, gamma, lam=0.95, penalty=0.0, 
         out.update(steve=np.where(any_, S / Wd, boot[0, :, 0]).astype(T), steve_weight=np.where(any_[None], w / Wd[None], T(0)).astype(T),
                    steve_mean=mean, steve_var=var, steve_count=count, steve_fallback=(~any_).astype(np.uint8))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the kernel's shapes
+# What tests/test_gpu_imagine_targets.py launches and tests/test_targets_ref.py shows, on the CPU, to reach every branch of the arithmetic.
+THREADS, LDS_BUDGET = 256, 48 * 1024      # csrc/imagine_targets.hip TGT_THREADS, TGT_LDS_BUDGET
+
+
+def lds_bytes(G, n, k):
+    """csrc/imagine_targets.hip tgt_lds_bytes: a tile of G n k floats and as many flag bytes, padded to 4 elements, and 2 G k floats"""
+    tile = (G * n * k + 3) & ~3
+    return 4 * tile + tile + 2 * G * k * 4
+
+
+def group(m, n, k):
+    """csrc/imagine_targets.hip tgt_group: the start states a workgroup of the STEVE form owns -- as many as give it 256 rows, at least
+    one, at most m, fewer where the tile would not fit 48 KiB (0: not even one's)"""
+    G = min(max(THREADS // n, 1), m)
+    while G > 0 and lds_bytes(G, n, k) > LDS_BUDGET:
+        G -= 1
+    return G
+
+
+# (m, n, k, with the STEVE outputs) -> the group the host takes, the start states of its workgroups
+SHAPES = [(1, 2, 1, True), (3, 4, 5, True), (17, 3, 7, True), (2, 33, 4, True), (5, 2, 64, True), (130, 3, 2, True), (300, 1, 3, False),
+          (1, 700, 20, False),
+          (20, 16, 64, True),      # G = 8, cut from 16 by the budget: cap = G n = 128 under a cut G; groups of 8, 8, 4
+          (9, 100, 20, True),      # G = 2: cap = 200, a partial last group of 1
+          (3, 300, 4, True)]       # G = 1, n > 256: the row loop's second pass while it writes the tile
+GROUPS = {(20, 16, 64): (8, [8, 8, 4]), (9, 100, 20): (2, [2, 2, 2, 2, 1]), (3, 300, 4): (1, [1, 1, 1])}
+# gamma, lam, penalty, max_disagreement: no penalty and no bound (a +inf disagreement is used and never multiplied); both; a bound alone
+MAXD, FLOOR = 1.5, 1e-2
+CONFIGS = [(0.97, 0.9, 0.0, None), (0.99, 0.5, 0.7, MAXD), (1.0, 1.0, 0.0, MAXD)]
+N_FEATURES = 7
+
+
+def plant_row(x, f, i, j, k):
+    """one special case on row (i, j); the row is fully valid with small disagreements unless the case says otherwise"""
+    x["valid"][:, i, j], x["done"][:, i, j] = 1, 0
+    x["disagreement"][:, i, j] = np.minimum(x["disagreement"][:, i, j], np.float32(1.0))
+    e = max(1, k // 2)
+    if f == 0:                                    # L = 0
+        x["valid"][:, i, j] = 0
+    elif f == 1:                                  # L = k
+        pass
+    elif f == 2:                                  # terminated at the last used step
+        x["valid"][e:, i, j] = 0
+        x["done"][e - 1, i, j] = 1
+    elif f == 3:                                  # diverged: the row ends without a done
+        x["valid"][k // 2:, i, j] = 0
+    elif f == 4:                                  # cut by max_disagreement at the last step
+        x["disagreement"][k - 1, i, j] = 3.0
+    elif f == 5:                                  # a +inf disagreement
+        x["disagreement"][k // 2, i, j] = np.inf
+    elif f == 6:                                  # a NaN bootstrap behind the start state
+        x["boot"][1:, i, j] = np.nan
+
+
+def variant(m, n, k, v):
+    """variant v of the seeded inputs of a shape: row r carries special case (v + r) % 7, so over 7 variants every case lands on row 0 of
+    even the smallest shape; in variants 7 and 8 the last start state keeps one live branch (no horizon has two targets: the fallback),
+    or one full and one diverged branch (the longer horizons have one target: weight 0)"""
+    x = make_inputs(m, n, k, 100 * v + m + n + k)
+    for r in range(min(m * n, N_FEATURES)):
+        plant_row(x, (v + r) % N_FEATURES, r // n, r % n, k)
+    if v >= 7 and n >= 2:
+        i = m - 1
+        x["valid"][:, i, :], x["done"][:, i, :] = 0, 0
+        plant_row(x, 1, i, 0, k)
+        if v == 8:
+            plant_row(x, 3, i, 1, k)
+    return x
+
+
+def branches(x, cfg, want, steve):
+    """the branches of the arithmetic that occurred on inputs x under cfg, read off the restatement's outputs `want`, as a set of names;
+    asserts what holds on every input: no NaN target without a NaN bootstrap, no n-step target from one"""
+    k, m, n = x["rew"].shape
+    L, term, valid = want["L"], want["term"], x["valid"]
+    ii, jj = np.meshgrid(np.arange(m), np.arange(n), indexing="ij")
+    nxt = valid[np.minimum(L, k - 1), ii, jj] > 0                 # is the step behind the used ones a valid one?
+    seen = {name for name, hit in (
+        ("L=0", (L == 0).any()), ("L=k", (L == k).any()), ("terminated", (term & (L >= 1)).any()),
+        ("diverged", ((L < k) & ~term & ~nxt).any()), ("truncated", ((L < k) & nxt).any()),
+        ("inf-unpenalised", cfg[2] == 0.0 and (np.isinf(x["disagreement"]) & (want["used"] > 0)).any()),
+        ("nan-boot", np.isnan(want["lambda_return"]).any())) if hit}
+    nan_rows = np.isnan(x["boot"]).any(axis=0)
+    assert not np.isnan(want["lambda_return"][:, ~nan_rows]).any() and not np.isnan(want["nstep"]).any()
+    assert (want["nstep_ok"][:, nan_rows & (L == k) & ~term] == 0).all()
+    if steve:
+        w, cnt = want["steve_weight"], want["steve_count"]
+        if ((w == 0) & (cnt < 2) & (w.sum(axis=0) > 0)[None]).any():
+            seen.add("weight-0")
+        if want["steve_fallback"].any():
+            seen.add("fallback")
+    return seen
+
+
+def needed(k, steve):
+    """the branches a shape must show over its variants and configs"""
+    need = {"L=0", "L=k", "terminated", "diverged", "truncated", "inf-unpenalised", "nan-boot"}
+    if steve:
+        need |= {"fallback"} | ({"weight-0"} if k >= 2 else set())
+    return need

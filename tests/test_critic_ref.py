@@ -4,13 +4,14 @@ chain against the float64 statement at the bar the GPU tests hold the kernel to,
 import numpy as np
 import pytest
 
+import behind_rollout as br
 import critic_ref as cref
 import policy_ref as pref
 import value_ref as vref
 from cadm_amd import _lib
 from cadm_amd.engine import HipEngine
 from cadm_amd.planner import PlanOptions
-from helpers import assert_close
+from helpers import assert_close, floored_rel
 
 F = np.float32
 D, A = 11, 3
@@ -66,6 +67,47 @@ def test_the_gpu_kernel_cases_are_live(act):
                 if gi % 7 == 0:
                     assert_close(cref.emulate32(states, critics, act, reduce, actor, mean=mean, std=std),
                                  cref.q64(states, critics, act, reduce, actor, mean=mean, std=std), what=what)
+
+
+ENVELOPE = [(name, act) for name in br.CRITIC_ROWS for act in cref.ACTS]
+
+
+@pytest.mark.parametrize("name,act", ENVELOPE, ids=["%s-%s" % c for c in ENVELOPE])
+def test_the_envelope_cases_are_live(name, act):
+    """every `critic_ref.ENVELOPE_CASES` entry of tests/test_gpu_critic_envelope.py::test_kernel, on every engine it runs on, meets the
+    liveness conditions (a dead net or a saturated squash would pass anything on the GPU), and the float32 chain meets the float64
+    statement on it at the bar the kernel is held to, for q and for every critic's q"""
+    _, D, A = br.TERM_ENGINES[name][:3]
+    m, n = br.CRITIC_ROWS[name][0]
+    low = dict(units=1.0, unsaturated=1.0, action=np.inf)
+    worst = 0.0
+    for gi, (hidden, phidden, C, reduce, squash) in enumerate(cref.ENVELOPE_CASES, 1):
+        states = cref.kernel_states(m, n, 30 + gi, name=name)[1]
+        assert states.shape[1] == D
+        actor, critics, mean, std = cref.kernel_case(states, A, hidden, phidden, C, act, squash, 10 + gi)
+        what = "%s %s %r behind %r, C = %d, %s, %s" % (name, act, hidden, phidden, C, reduce, squash)
+        live = cref.check_live(states, critics, act, actor, mean, std, what=what)
+        low = {k: min(v, live[k]) for k, v in low.items()}
+        ref, ref_each = cref.q64(states, critics, act, reduce, actor, mean=mean, std=std, want_each=True)
+        got, each = cref.emulate32(states, critics, act, reduce, actor, mean=mean, std=std, want_each=True)
+        worst = max(worst, floored_rel(got, ref) / 1e-5, floored_rel(each, ref_each) / 1e-5)
+        assert_close(got, ref, what=what)
+        assert_close(each, ref_each, what=what + ": each")
+    print("\n[%s %s] smallest live share %.2f, unsaturated share %.2f, action effect %.3g; worst |emulate32 - q64| / (1e-5 of scale) %.3f"
+          % (name, act, low["units"], low["unsaturated"], low["action"], worst))
+
+
+def test_the_envelope_cases_cover_what_they_name():
+    cases = cref.ENVELOPE_CASES
+    assert len(cases) == 18 and {c[0] for c in cases} == set(cref.ENVELOPE_CRITICS) and {c[1] for c in cases} == set(cref.ENVELOPE_ACTORS)
+    assert {c[2] for c in cases} == {1, 4, 5} and {c[3] for c in cases} == set(cref.REDUCES) and {c[4] for c in cases} == set(pref.SQUASH)
+    for phidden in cref.ENVELOPE_ACTORS:      # every actor depth meets every C, both reduces and both squashes
+        mine = [c for c in cases if c[1] == phidden]
+        assert {c[2] for c in mine} == {1, 4, 5} and {c[3] for c in mine} == set(cref.REDUCES) and {c[4] for c in mine} == set(pref.SQUASH)
+    assert any(len(c[0]) == 4 and len(c[1]) == 4 and c[2] == 5 for c in cases), "four hidden layers under five dense ones at C = 5"
+    for name, rows in br.CRITIC_ROWS.items():
+        p = br.TERM_ENGINES[name][4]
+        assert all((m * n * p) % 16 for m, n in rows) and rows[0][0] * rows[0][1] * p > 16 > rows[1][0] * rows[1][1] * p, name
 
 
 def test_reduce_orders():

@@ -5,7 +5,7 @@ the fused loop (`cadm_critic_plan`) against the stepwise one, the class route an
 
 Geometries: the module-scoped engines of tests/test_gpu_tracking.py -- hopper_like (D = 11, A = 3, p = 5, H = 3: K = 14 is no multiple
 of 4), halfcheetah (D = 18, p = 20, H = 8 and p = 5, H = 5); synthetic trajectories from tests/behind_rollout.py; the class route on
-tests/helpers.py's `plan_model`.
+tests/helpers.py's `plan_model`.  tests/test_gpu_critic_envelope.py runs the `check_*` bodies of this file on the other geometries.
 
 The kernel is held to the float64 restatement at the project's bar for fp32 kernels, `helpers.assert_close` at 1e-5 of the output's
 scale.  Measured on an MI355X, worst |err| / (1e-5 x max(|ref|, rms)) over q and every critic's q: relu 0.260, tanh 0.187, swish 0.467;
@@ -61,6 +61,37 @@ def _simple(eng, hidden=(64, 48), phidden=(32,), C=2, act="relu", reduce="min", 
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 1: the kernel
+def check_kernel_cases(eng, act, cases, rows_of, states_of, weight_eff=0.5):
+    """The body of `test_kernel_against_restatement` on any engine: `cases` a list of (hidden, phidden, C, reduce, squash), `rows_of` the
+    (m, n) of the launches of a case (the nets of the first serve the others), `states_of(m, n, seed)` -> (traj, its last states);
+    weight_eff: what the row update multiplies q by -- the declared 0.5, or float32(0.5 disc[H]) on a ctx with a discount.  -> the worst
+    |err| / (1e-5 of scale) over q and every critic's q."""
+    lb, ub = _bounds(eng)
+    worst, gi = 0.0, 0
+    for hidden, phidden, C, reduce, squash in cases:
+        gi += 1
+        what = "%s %r behind %r, C = %d, %s, %s" % (act, hidden, phidden, C, reduce, squash)
+        actor = crt = None
+        for m, n in rows_of:
+            traj, states = states_of(m, n, 30 + gi)
+            if actor is None:      # (the nets of the first case serve the others)
+                actor, critics, mean, std = cref.kernel_case(states, eng.A, hidden, phidden, C, act, squash, 10 + gi)
+                crt, _ = _register(eng, actor, critics, hidden, phidden, act, reduce, 0.5, mean, std)
+            ref, ref_each = cref.q64(states, critics, act, reduce, actor, mean=mean, std=std, lb=lb, ub=ub, want_each=True)
+            q, each, a = (_np(x) for x in eng.critic_eval(states, want_each=True, want_actions=True))
+            assert q.shape == (m * n * eng.p,) and each.shape == (C, m * n * eng.p) and np.isfinite(q).all(), what
+            worst = max(worst, floored_rel(q, ref) / 1e-5, floored_rel(each, ref_each) / 1e-5)
+            assert_close(q, ref, what=what)
+            assert_close(each, ref_each, what=what + ": each")
+            assert_close(a, pref.action64(states, actor["layers"], act, squash, lb, ub, actor["mean"], actor["std"]), what=what + ": action")
+            np.testing.assert_array_equal(_bits(q), _bits(cref.reduce32(each, reduce)), err_msg=what + ": the reduce order")
+            rows = np.random.default_rng(gi).standard_normal((m, n, eng.p)).astype(F)
+            out, qo = eng.critic_returns(traj, rows, crt, want_q=True)
+            np.testing.assert_array_equal(_bits(_np(qo)).reshape(-1), _bits(q), err_msg=what + ": q_out against cadm_critic_eval")
+            np.testing.assert_array_equal(_bits(_np(out)), _bits(cref.update(rows, _np(qo), weight_eff)), err_msg=what)
+    return worst
+
+
 @pytest.mark.parametrize("act", cref.ACTS)
 def test_kernel_against_restatement(engines, act):
     """`cadm_critic_eval` (q, every critic's q, the action used) on hopper_like against the float64 restatement at 1e-5 of scale: every
@@ -69,31 +100,8 @@ def test_kernel_against_restatement(engines, act):
     has the same bits, and the rows are the row update from them.  tests/test_critic_ref.py holds the same cases to the liveness
     conditions on the CPU."""
     _, eng = engines("hopper")
-    lb, ub = _bounds(eng)
-    worst, gi = 0.0, 0
-    for hidden in cref.KERNEL_CRITICS:
-        for phidden in cref.KERNEL_ACTORS:
-            for C, reduce, squash in cref.KERNEL_COMBOS:
-                gi += 1
-                what = "%s %r behind %r, C = %d, %s, %s" % (act, hidden, phidden, C, reduce, squash)
-                actor = crt = None
-                for m, n in cref.KERNEL_ROWS:
-                    traj, states = cref.kernel_states(m, n, 30 + gi)
-                    if actor is None:      # (the nets of the 165-row case serve the 15-row one)
-                        actor, critics, mean, std = cref.kernel_case(states, eng.A, hidden, phidden, C, act, squash, 10 + gi)
-                        crt, _ = _register(eng, actor, critics, hidden, phidden, act, reduce, 0.5, mean, std)
-                    ref, ref_each = cref.q64(states, critics, act, reduce, actor, mean=mean, std=std, lb=lb, ub=ub, want_each=True)
-                    q, each, a = (_np(x) for x in eng.critic_eval(states, want_each=True, want_actions=True))
-                    assert q.shape == (m * n * eng.p,) and each.shape == (C, m * n * eng.p) and np.isfinite(q).all(), what
-                    worst = max(worst, floored_rel(q, ref) / 1e-5, floored_rel(each, ref_each) / 1e-5)
-                    assert_close(q, ref, what=what)
-                    assert_close(each, ref_each, what=what + ": each")
-                    assert_close(a, pref.action64(states, actor["layers"], act, squash, lb, ub, actor["mean"], actor["std"]), what=what + ": action")
-                    np.testing.assert_array_equal(_bits(q), _bits(cref.reduce32(each, reduce)), err_msg=what + ": the reduce order")
-                    rows = np.random.default_rng(gi).standard_normal((m, n, eng.p)).astype(F)
-                    out, qo = eng.critic_returns(traj, rows, crt, want_q=True)
-                    np.testing.assert_array_equal(_bits(_np(qo)).reshape(-1), _bits(q), err_msg=what + ": q_out against cadm_critic_eval")
-                    np.testing.assert_array_equal(_bits(_np(out)), _bits(cref.update(rows, _np(qo), 0.5)), err_msg=what)
+    cases = [(hidden, phidden) + combo for hidden in cref.KERNEL_CRITICS for phidden in cref.KERNEL_ACTORS for combo in cref.KERNEL_COMBOS]
+    worst = check_kernel_cases(eng, act, cases, cref.KERNEL_ROWS, cref.kernel_states)
     print("\n[%s] worst |err| / (1e-5 of scale): %.3f" % (act, worst))
 
 
@@ -113,18 +121,14 @@ def test_kernel_at_the_widest_nets(engines):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 2: equal bits
-@pytest.mark.parametrize("hidden,phidden,act,C,reduce", [((64, 48, 200), (64, 48), "swish", 3, "mean"), ((200, 200), (), "relu", 2, "min"),
-                                                          ((), (64, 48), "tanh", 1, "min")], ids=["unequal-swish", "200x2-relu", "linear"])
-def test_a_state_has_the_same_bits_in_any_batch(engines, hidden, phidden, act, C, reduce):
-    """The action used against `policy_eval`; the fused actor path against `critic_eval(states, actions=policy_eval(states))`; every
-    critic's q at R = 1, 5, 16, 165, with the rows rolled by 7, inside a batch large enough for two row tiles per workgroup (more than
-    2 x 16 x the CU count rows; head and tail), run to run, and from `critic_returns`' q_out: equal bits."""
-    _, eng = engines("hopper")
-    traj, states = cref.kernel_states(3, 11, 41)
+def check_bits_in_any_batch(eng, states, hidden, phidden, act, C, reduce, traj=None):
+    """The body of `test_a_state_has_the_same_bits_in_any_batch` for any engine and any batch `states` [R, D] (R > 16); traj [H,m,n,p,D]:
+    the trajectory whose last states they are, for `critic_returns`' q_out and the call with leading dims (None: neither)."""
+    R = states.shape[0]
     actor, critics, mean, std = cref.kernel_case(states, eng.A, hidden, phidden, C, act, "tanh", 21)
     crt, _ = _register(eng, actor, critics, hidden, phidden, act, reduce, 1.0, mean, std)
     full, each, a = (_np(x) for x in eng.critic_eval(states, want_each=True, want_actions=True))
-    assert full.shape == (165,) and each.shape == (C, 165)
+    assert full.shape == (R,) and each.shape == (C, R)
     pa = _np(eng.policy_eval(states))
     np.testing.assert_array_equal(_bits(a), _bits(pa), err_msg="act_out against policy_eval")
     g, geach, ga = (_np(x) for x in eng.critic_eval(states, actions=pa, want_each=True, want_actions=True))
@@ -134,25 +138,41 @@ def test_a_state_has_the_same_bits_in_any_batch(engines, hidden, phidden, act, C
     again = eng.critic_eval(states, want_each=True)
     np.testing.assert_array_equal(_bits(_np(again[0])), _bits(full), err_msg="run to run")
     np.testing.assert_array_equal(_bits(_np(again[1])), _bits(each), err_msg="run to run")
-    for R in (1, 5, 16):
-        q, e = eng.critic_eval(states[:R], want_each=True)
-        np.testing.assert_array_equal(_bits(_np(q)), _bits(full[:R]), err_msg="R = %d" % R)
-        np.testing.assert_array_equal(_bits(_np(e)), _bits(each[:, :R]), err_msg="R = %d" % R)
+    for r in (1, 5, 16):
+        q, e = eng.critic_eval(states[:r], want_each=True)
+        np.testing.assert_array_equal(_bits(_np(q)), _bits(full[:r]), err_msg="R = %d" % r)
+        np.testing.assert_array_equal(_bits(_np(e)), _bits(each[:, :r]), err_msg="R = %d" % r)
     q, e = eng.critic_eval(np.roll(states, 7, axis=0), want_each=True)
     np.testing.assert_array_equal(_bits(_np(q)), _bits(np.roll(full, 7)), err_msg="rows moved by 7")
     np.testing.assert_array_equal(_bits(_np(e)), _bits(np.roll(each, 7, axis=1)), err_msg="rows moved by 7")
-    reps = 2 * 16 * 256 // 165 + 8
+    cus = torch.cuda.get_device_properties(eng.device).multi_processor_count      # (256 on an MI355X)
+    reps = 2 * 16 * cus // R + 8
     q, e = (_np(x) for x in eng.critic_eval(np.concatenate([states[3:]] + [states] * reps, axis=0), want_each=True))
-    assert q.shape[0] > 2 * 16 * 256
-    np.testing.assert_array_equal(_bits(q[:162]), _bits(full[3:]), err_msg="the two-row-tile launch, head")
-    np.testing.assert_array_equal(_bits(q[-165:]), _bits(full), err_msg="the two-row-tile launch, tail")
-    np.testing.assert_array_equal(_bits(e[:, :162]), _bits(each[:, 3:]))
-    np.testing.assert_array_equal(_bits(e[:, -165:]), _bits(each))
-    _, qo = eng.critic_returns(traj, np.zeros((3, 11, eng.p), F), crt, want_q=True)
+    assert q.shape[0] > 2 * 16 * cus
+    np.testing.assert_array_equal(_bits(q[:R - 3]), _bits(full[3:]), err_msg="the two-row-tile launch, head")
+    np.testing.assert_array_equal(_bits(q[-R:]), _bits(full), err_msg="the two-row-tile launch, tail")
+    np.testing.assert_array_equal(_bits(e[:, :R - 3]), _bits(each[:, 3:]))
+    np.testing.assert_array_equal(_bits(e[:, -R:]), _bits(each))
+    if traj is None:
+        return
+    m, n = traj.shape[1:3]
+    _, qo = eng.critic_returns(traj, np.zeros((m, n, eng.p), F), crt, want_q=True)
     np.testing.assert_array_equal(_bits(_np(qo)).reshape(-1), _bits(full), err_msg="critic_returns' q_out")
-    lead = eng.critic_eval(states.reshape(3, 11, eng.p, eng.D))
-    assert tuple(lead.shape) == (3, 11, eng.p)
+    lead = eng.critic_eval(states.reshape(m, n, eng.p, eng.D))
+    assert tuple(lead.shape) == (m, n, eng.p)
     np.testing.assert_array_equal(_bits(_np(lead)).reshape(-1), _bits(full))
+
+
+@pytest.mark.parametrize("hidden,phidden,act,C,reduce", [((64, 48, 200), (64, 48), "swish", 3, "mean"), ((200, 200), (), "relu", 2, "min"),
+                                                          ((), (64, 48), "tanh", 1, "min")], ids=["unequal-swish", "200x2-relu", "linear"])
+def test_a_state_has_the_same_bits_in_any_batch(engines, hidden, phidden, act, C, reduce):
+    """The action used against `policy_eval`; the fused actor path against `critic_eval(states, actions=policy_eval(states))`; every
+    critic's q at R = 1, 5, 16, 165, with the rows rolled by 7, inside a batch large enough for two row tiles per workgroup (more than
+    2 x 16 x the CU count rows; head and tail), run to run, and from `critic_returns`' q_out: equal bits."""
+    _, eng = engines("hopper")
+    traj, states = cref.kernel_states(3, 11, 41)
+    assert states.shape[0] == 165
+    check_bits_in_any_batch(eng, states, hidden, phidden, act, C, reduce, traj)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 3: against the value net
@@ -231,21 +251,18 @@ def test_row_update(engines, weight):
     assert weight == 0.0 or not np.array_equal(_bits(_np(out)), _bits(rows))
 
 
-@pytest.mark.parametrize("act", ["relu", "tanh"])
-def test_non_finite_terminal_states_and_the_first_cut(engines, act):
-    """NaN and +-inf in single dims of traj[H-1] make those rows' q and return NaN -- under relu too, whose max(NaN, 0) would hide them,
-    and although the actor's fallback action is finite --, garbage in earlier steps reaches nothing, and every other row has the bits it
-    has without its neighbours' poison.  With `first`, rows with first < H keep their input bits, terminal NaN or not, and read NaN in
-    q_out; rows with first == H are valued."""
-    _, eng = engines("hopper")
+def check_non_finite_and_first(eng, act, clean, dims=None, hidden=(48, 48), phidden=(32,), seed=13):
+    """The body of `test_non_finite_terminal_states_and_the_first_cut` on any engine with A >= 3, p >= 3, D >= 4 and H >= 2: clean
+    [H,m,n,p,D] a finite trajectory; dims: the dims the poison is planted in (None: drawn over all D); seed: of the poisoned rows and
+    the cuts (`first` is drawn over 0 .. H: at a long H another seed may be needed for a poisoned row that is not cut)."""
     H, p, D = eng.H, eng.p, eng.D
-    crt, _, _, _ = _simple(eng, (48, 48), (32,), 2, act, "min", 2.0, seed=6)
-    m, n = 3, 11
-    clean = cref.kernel_states(m, n, 12)[0]
+    crt, _, _, _ = _simple(eng, hidden, phidden, 2, act, "min", 2.0, seed=6)
+    m, n = clean.shape[1:3]
+    assert clean.shape == (H, m, n, p, D)
     rows = np.random.default_rng(4).standard_normal((m, n, p)).astype(F)
     ref_out, ref_q = (_np(x) for x in eng.critic_returns(clean, rows, crt, want_q=True))
     assert np.isfinite(ref_q).all()
-    rng = np.random.default_rng(13)
+    rng = np.random.default_rng(seed)
     bad = clean.copy()
     bad[:-1][rng.uniform(size=bad[:-1].shape) < 0.2] = np.nan             # earlier steps: never read
     bad[0, 0, 0, 0, :] = np.inf
@@ -253,7 +270,7 @@ def test_non_finite_terminal_states_and_the_first_cut(engines, act):
     hit[0, 0, 0], hit[0, 0, 1], hit[m - 1, n - 1, p - 1] = True, False, True      # the first row, its neighbour, the tail tile's last row
     mi, ni, j = np.nonzero(hit)
     poison = np.array([np.nan, np.inf, -np.inf], F)[rng.integers(0, 3, mi.size)]
-    bad[H - 1, mi, ni, j, rng.integers(0, D, mi.size)] = poison
+    bad[H - 1, mi, ni, j, rng.integers(0, D, mi.size) if dims is None else np.asarray(dims)[rng.integers(0, len(dims), mi.size)]] = poison
     out, q = (_np(x) for x in eng.critic_returns(bad, rows, crt, want_q=True))
     assert np.isnan(q[hit]).all() and np.isnan(out[hit]).all()
     np.testing.assert_array_equal(_bits(q[~hit]), _bits(ref_q[~hit]), err_msg="a row met its neighbour's poison")
@@ -283,31 +300,38 @@ def test_non_finite_terminal_states_and_the_first_cut(engines, act):
     assert np.isnan(out[~cut & hit]).all() and np.isnan(q[~cut & hit]).all()
 
 
+@pytest.mark.parametrize("act", ["relu", "tanh"])
+def test_non_finite_terminal_states_and_the_first_cut(engines, act):
+    """NaN and +-inf in single dims of traj[H-1] make those rows' q and return NaN -- under relu too, whose max(NaN, 0) would hide them,
+    and although the actor's fallback action is finite --, garbage in earlier steps reaches nothing, and every other row has the bits it
+    has without its neighbours' poison.  With `first`, rows with first < H keep their input bits, terminal NaN or not, and read NaN in
+    q_out; rows with first == H are valued."""
+    _, eng = engines("hopper")
+    check_non_finite_and_first(eng, act, cref.kernel_states(3, 11, 12)[0])
+
+
 # ---------------------------------------------------------------------------------------------------------------------- 5: fused against stepwise
 COMBOS = ["cem", "mppi", "cem-prior", "mppi-prior", "cem-terminate", "mppi-prior-terminate"]
 
 
-@pytest.mark.parametrize("combo", COMBOS)
-def test_fused_equals_stepwise(engines, combo):
-    """`cadm_critic_plan` with device RNG == the same loop one launch at a time (`planner.icem_plan(..., critic=...)`), bit for bit over
-    two consecutive calls at M = 2, N = 24, 3 iterations: the plan, the best return and the carry -- CEM and MPPI, with and without a
-    policy prior in the same call, with TERMINATE constraints; in every stepwise iteration the rows are the row update of the rows
-    before it from the kernel's own q.  Without the term the plan is another."""
+def check_fused_equals_stepwise(prob, eng, combo, cons_dims=(1, 7), hidden=(64, 48), phidden=(32,)):
+    """The body of `test_fused_equals_stepwise` on any engine whose rollout the library carries: cons_dims the dims the TERMINATE
+    constraints bind (`binding_bounds` on iteration 0's trajectory); hidden, phidden: the critics' and the actor's hidden widths."""
     from test_gpu_constraints import binding_bounds, iteration0_traj
     mppi, prior, terminate = "mppi" in combo, "prior" in combo, "terminate" in combo
-    prob, eng = engines("hc5")
     H, A = eng.H, eng.A
-    crt, pol1, _, _ = _simple(eng, (64, 48), (32,), 2, "tanh", "min", 3.0, seed=31)
-    pol = HipEngine.policy_params((32,), "tanh", "tanh", 3, 0.2) if prior else None
+    crt, pol1, _, _ = _simple(eng, hidden, phidden, 2, "tanh", "min", 3.0, seed=31)
+    pol = HipEngine.policy_params(phidden, "tanh", "tanh", 3, 0.2) if prior else None
     K = 2
     icem = dict(noise_beta=1.0 if mppi else 0.0, keep_elites=K, decay=1.25, return_best=terminate, add_mean_last=True)
     prm = HipEngine.mppi_params(temperature=0.5, relative=True, **icem) if mppi else HipEngine.icem_params(**icem)
     cons = None
     if terminate:
-        cons = HipEngine.constraint_params(binding_bounds(iteration0_traj(eng, prob, 0.0, 4, 1), (1, 7), H, "terminal q"), "terminate", 4.0)
+        cons = HipEngine.constraint_params(binding_bounds(iteration0_traj(eng, prob, 0.0, 4, 1), cons_dims, H, "terminal q"), "terminate", 4.0)
     args = (prob["obs"], prob["cp_obs"], prob["cp_act"])
     (ca, va), (cb, vb) = zero_carry(eng, M, K, H), zero_carry(eng, M, K, H)
     mean, var = prob["init_mean"], prob["init_var"]
+    reach = max(abs(v) for v in _bounds(eng))      # (1.0 on every built-in kind)
     for call in (1, 2):
         a, ra = eng.critic_plan(crt, pol, None, None, None, None, None, None, True, None, None, None, None, None, cons, None, prm, *args, mean, var,
                                 N, carry=ca, carry_valid=va, seed=4, call=call, want_best_return=True)
@@ -315,7 +339,7 @@ def test_fused_equals_stepwise(engines, combo):
                                             update="mppi" if mppi else "cem", temperature=0.5, relative=True, constraints=cons, policy=pol,
                                             critic=crt, **icem)
         a = _np(a)
-        assert a.shape == (M, H, A) and np.isfinite(a).all() and 0 < np.abs(a).max() <= 1.0
+        assert a.shape == (M, H, A) and np.isfinite(a).all() and 0 < np.abs(a).max() <= reach
         np.testing.assert_array_equal(_bits(a), _bits(_np(b)), err_msg="plan of call %d" % call)
         np.testing.assert_array_equal(_bits(_np(ra)), _bits(_np(extra["best_ret"])), err_msg="best return of call %d" % call)
         np.testing.assert_array_equal(_bits(_np(ca)), _bits(_np(cb)))
@@ -335,6 +359,17 @@ def test_fused_equals_stepwise(engines, combo):
                                 var, N, *zero_carry(eng, M, K, H), seed=4, call=2))
     assert not np.array_equal(_bits(other), _bits(a))
     assert (mppi, "crt", terminate, False, False, 3 if prior else 0) in eng._loop_ws
+
+
+@pytest.mark.parametrize("combo", COMBOS)
+def test_fused_equals_stepwise(engines, combo):
+    """`cadm_critic_plan` with device RNG == the same loop one launch at a time (`planner.icem_plan(..., critic=...)`), bit for bit over
+    two consecutive calls at M = 2, N = 24, 3 iterations: the plan, the best return and the carry -- CEM and MPPI, with and without a
+    policy prior in the same call, with TERMINATE constraints; in every stepwise iteration the rows are the row update of the rows
+    before it from the kernel's own q.  Without the term the plan is another."""
+    prob, eng = engines("hc5")
+    assert _bounds(eng) == (-1.0, 1.0)
+    check_fused_equals_stepwise(prob, eng, combo)
 
 
 @pytest.mark.parametrize("update", ["cem", "mppi"])

@@ -8,7 +8,9 @@ halfcheetah at p = 20 -- kernel-level engines that are never rolled out; everyth
 200 x 4 kernel, vanilla and with context, through tests/test_gpu_policy.py's engine families whose H = 1 twins share their weights.
 
 The stage owns 16 consecutive rows per workgroup at these sizes, so a group's span of `next` starts 16-byte aligned whenever the
-buffer does; the scalar-load path is reached by handing the stage a buffer that starts one float behind an aligned address."""
+buffer does; the scalar-load path is reached by handing the stage a buffer that starts one float behind an aligned address.
+tests/test_gpu_imagine_envelope.py runs `check_stage` and `check_chain` where the LDS budget cuts the group below 16 and on the other
+built-in kinds."""
 import ctypes as ct
 import math
 
@@ -116,13 +118,8 @@ def _synthetic(eng, R, seed, call, t):
     return nxt, rows1, state, alive, length, sel
 
 
-@pytest.mark.parametrize("name", ["pend", "hopper", "wide", "hc20"])
-def test_stage_against_restatement(engines, name):
-    """`imagine_select` on 37 rows (two full groups of 16 and a tail of 5) of synthetic particles: every output -- states[t + 1], rew,
-    done, valid, member, disagreement, alive, length and the p-fold broadcast -- equals the restatement bit for bit, with and without
-    constraints and per-dim weights, from an aligned buffer (16-byte loads) and from one that starts one float behind (scalar loads; p D
-    is odd at D = 3 and 11), run to run; and the same rows at another position of a larger batch, fed the same sel, give the same bits."""
-    _, eng = engines(name)
+def check_stage(eng, name, at=100):
+    """The body of `test_stage_against_restatement` on any engine; at: the row of a batch of 150 at which the 37 rows are run again."""
     R, seed, call, t = 37, 11, 5, 2
     nxt, rows1, state, alive, length, sel = _synthetic(eng, R, seed, call, t)
     assert len(np.unique(sel)) >= 5
@@ -153,7 +150,7 @@ def test_stage_against_restatement(engines, name):
     np.testing.assert_array_equal(moved["member"][alive > 0], iref.select(iref.words(seed, call, np.arange(R), t + 1), eng.p)[alive > 0] // (eng.p // eng.E))
     # the same rows at rows 100 .. 136 of 150: the draw is keyed by the row index, so the test feeds the sel the rows had at 0 .. 36
     rng = np.random.default_rng(4)
-    big = lambda x, fill: np.concatenate([fill(100), x, fill(13)], axis=0)
+    big = lambda x, fill: np.concatenate([fill(at), x, fill(150 - R - at)], axis=0)
     nb = big(nxt, lambda k: rng.standard_normal((k,) + nxt.shape[1:]).astype(F))
     rb = big(rows1, lambda k: rng.standard_normal((k, eng.p)).astype(F))
     sb = big(state, lambda k: rng.standard_normal((k, eng.D)).astype(F))
@@ -163,10 +160,20 @@ def test_stage_against_restatement(engines, name):
     want = iref.select_step(nxt, rows1, state, alive, sel, eng.E, CONS, w, length)
     moved = _select_np(eng.imagine_select(nb, rb, sb, ab, t=t, sel=selb, constraints=cons, w=w, seed=seed + 1, call=call, length=lb))
     for key in want:
-        _same(moved[key][100:137], want[key], "%s %s at rows 100 .. 136" % (name, key))
+        _same(moved[key][at:at + R], want[key], "%s %s at rows %d .. %d" % (name, key, at, at + R - 1))
     # a sel outside 0 .. p - 1 is clamped, never an index
     wild = _select_np(eng.imagine_select(nxt, rows1, state, alive, t=t, sel=np.where(np.arange(R) % 2 == 0, -7, 1000).astype(np.int32)))
     np.testing.assert_array_equal(wild["member"][alive > 0], np.where(np.arange(R) % 2 == 0, 0, eng.E - 1)[alive > 0])
+
+
+@pytest.mark.parametrize("name", ["pend", "hopper", "wide", "hc20"])
+def test_stage_against_restatement(engines, name):
+    """`imagine_select` on 37 rows (two full groups of 16 and a tail of 5) of synthetic particles: every output -- states[t + 1], rew,
+    done, valid, member, disagreement, alive, length and the p-fold broadcast -- equals the restatement bit for bit, with and without
+    constraints and per-dim weights, from an aligned buffer (16-byte loads) and from one that starts one float behind (scalar loads; p D
+    is odd at D = 3 and 11), run to run; and the same rows at another position of a larger batch, fed the same sel, give the same bits."""
+    _, eng = engines(name)
+    check_stage(eng, name)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 2: the chain, one step at a time
@@ -192,7 +199,7 @@ def check_chain(eng, twin, prob, m, n, k, seed, call, actions=None, noise=0.0, c
     for t in range(k):
         a = out["act"][t]
         if actions is not None:
-            _same(a, np.clip(np.asarray(actions, F)[:, :, t], F(-1), F(1)), "act[%d] is the clipped given action" % t)
+            _same(a, np.clip(np.asarray(actions, F)[:, :, t], F(eng.cfg.lower_bound), F(eng.cfg.upper_bound)), "act[%d] is the clipped given action" % t)
         bro = np.ascontiguousarray(np.broadcast_to(out["states"][t][:, :, None, :], (m, n, p, D)))
         rows, traj = twin.rollout_returns(obs, tv, np.ascontiguousarray(a[:, :, None, :]), obs_rows=bro.reshape(-1, D), seed=seed, call=call,
                                           it=hplanner.IMAGINE_IT + 2 * t, want_traj=True)

@@ -6,7 +6,12 @@ The kernel reads no weights, so the kernel-level engine (pendulum, p = 5) is nev
 compiled-in halfcheetah 200 x 4 kernel with m = 3, branches = 3, horizon = 4.
 
 Every output behind a division (steve, steve_mean, steve_var, steve_weight) is held to the restatement bit for bit as well: the
-kernel's `__fdiv_rn` and numpy's float32 division are both correctly rounded."""
+kernel's `__fdiv_rn` and numpy's float32 division are both correctly rounded.
+
+The shapes, their planted variants and the bookkeeping of the branches are `targets_ref.SHAPES`, `variant` and `branches`:
+tests/test_targets_ref.py runs them on the CPU and holds the restated `tgt_group` to the groups named here.  Three of the STEVE shapes
+have a group the host cuts: (20, 16, 64) G = 8 of 16 by the 48 KiB budget (cap = G n under a cut G), (9, 100, 20) G = 2 with a partial
+last group, (3, 300, 4) G = 1 with two passes of the row loop into the LDS tile."""
 import ctypes as ct
 import math
 
@@ -29,9 +34,7 @@ NAN = float("nan")
 BIG = dict(hidden=(200,) * 4)
 STEVE_KEYS = ("steve", "steve_weight", "steve_mean", "steve_var", "steve_count", "steve_fallback")
 KEYS = ("lambda_return", "nstep", "nstep_ok", "used")
-MAXD, FLOOR = 1.5, 1e-2
-# gamma, lam, penalty, max_disagreement: no penalty and no bound (a +inf disagreement is used and never multiplied); both; a bound alone
-CONFIGS = [(0.97, 0.9, 0.0, None), (0.99, 0.5, 0.7, MAXD), (1.0, 1.0, 0.0, MAXD)]
+MAXD, FLOOR, CONFIGS = tref.MAXD, tref.FLOOR, tref.CONFIGS      # gamma, lam, penalty, max_disagreement of the three parameter sets
 
 
 def _bits(x):
@@ -72,57 +75,22 @@ def _ref(x, cfg, floor=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 1: bit for bit
-N_FEATURES = 7
-
-
-def _plant_row(x, f, i, j, k):
-    """one special case on row (i, j); the row is fully valid with small disagreements unless the case says otherwise"""
-    x["valid"][:, i, j], x["done"][:, i, j] = 1, 0
-    x["disagreement"][:, i, j] = np.minimum(x["disagreement"][:, i, j], F(1.0))
-    e = max(1, k // 2)
-    if f == 0:                                    # L = 0
-        x["valid"][:, i, j] = 0
-    elif f == 1:                                  # L = k
-        pass
-    elif f == 2:                                  # terminated at the last used step
-        x["valid"][e:, i, j] = 0
-        x["done"][e - 1, i, j] = 1
-    elif f == 3:                                  # diverged: the row ends without a done
-        x["valid"][k // 2:, i, j] = 0
-    elif f == 4:                                  # cut by max_disagreement at the last step
-        x["disagreement"][k - 1, i, j] = 3.0
-    elif f == 5:                                  # a +inf disagreement
-        x["disagreement"][k // 2, i, j] = math.inf
-    elif f == 6:                                  # a NaN bootstrap behind the start state
-        x["boot"][1:, i, j] = NAN
-
-
-def _variant(m, n, k, v):
-    """variant v of the seeded inputs of a shape: row r carries special case (v + r) % 7, so over 7 variants every case lands on row 0 of
-    even the smallest shape; in variants 7 and 8 the last start state keeps one live branch (no horizon has two targets: the fallback),
-    or one full and one diverged branch (the longer horizons have one target: weight 0)"""
-    x = tref.make_inputs(m, n, k, 100 * v + m + n + k)
-    for r in range(min(m * n, N_FEATURES)):
-        _plant_row(x, (v + r) % N_FEATURES, r // n, r % n, k)
-    if v >= 7 and n >= 2:
-        i = m - 1
-        x["valid"][:, i, :], x["done"][:, i, :] = 0, 0
-        _plant_row(x, 1, i, 0, k)
-        if v == 8:
-            _plant_row(x, 3, i, 1, k)
-    return x
-
-
-SHAPES = [(1, 2, 1, True), (3, 4, 5, True), (17, 3, 7, True), (2, 33, 4, True), (5, 2, 64, True), (130, 3, 2, True), (300, 1, 3, False),
-          (1, 700, 20, False)]
+_plant_row, _variant, SHAPES = tref.plant_row, tref.variant, tref.SHAPES      # (shared with tests/test_targets_ref.py, which runs them on the CPU)
 
 
 @pytest.mark.parametrize("m,n,k,steve", SHAPES, ids=["m%d-n%d-k%d" % s[:3] for s in SHAPES])
 def test_against_restatement(eng, m, n, k, steve):
     """Every output equals the float32 restatement bit for bit, on 9 planted variants of seeded inputs under 3 parameter sets, run to run;
     and the restatement shows that every branch of the arithmetic the shape admits occurred.  (130, 3, 2) is two workgroups of the STEVE
-    form with a ragged second one; (300, 1, 3) two of the plain form."""
+    form with a ragged second one; (300, 1, 3) two of the plain form.  (20, 16, 64): the 48 KiB budget cuts the group from 16 start
+    states to 8, so the tile's stride is cap = 8 x 16 and the workgroups own 8, 8 and 4; (9, 100, 20): groups of 2 and a last one of 1;
+    (3, 300, 4): one start state a workgroup, whose 300 rows take the row loop twice while it writes the tile -- the group is asserted
+    against `targets_ref.group`, the restated `tgt_group`, before the launch."""
     floor = FLOOR if steve else None
+    if (m, n, k) in tref.GROUPS:
+        G, owned = tref.GROUPS[(m, n, k)]
+        assert steve and tref.group(m, n, k) == G and [min(G, m - i) for i in range(0, m, G)] == owned
+        assert G < min(max(256 // n, 1), m) or n > 256 or m % G, "the shape must cut the group, leave a partial one or take two row passes"
     seen = set()
     for v in range(9):
         x = _variant(m, n, k, v)
@@ -136,26 +104,8 @@ def test_against_restatement(eng, m, n, k, steve):
                 again = _run(eng, x, cfg, floor)
                 for key in got:
                     _same(again[key], got[key], "run to run: %s" % key)
-            L, term, valid = want["L"], want["term"], x["valid"]
-            ii, jj = np.meshgrid(np.arange(m), np.arange(n), indexing="ij")
-            nxt = valid[np.minimum(L, k - 1), ii, jj] > 0                 # is the step behind the used ones a valid one?
-            seen |= {name for name, hit in (
-                ("L=0", (L == 0).any()), ("L=k", (L == k).any()), ("terminated", (term & (L >= 1)).any()),
-                ("diverged", ((L < k) & ~term & ~nxt).any()), ("truncated", ((L < k) & nxt).any()),
-                ("inf-unpenalised", cfg[2] == 0.0 and (np.isinf(x["disagreement"]) & (want["used"] > 0)).any()),
-                ("nan-boot", np.isnan(want["lambda_return"]).any())) if hit}
-            nan_rows = np.isnan(x["boot"]).any(axis=0)
-            assert not np.isnan(want["lambda_return"][:, ~nan_rows]).any() and not np.isnan(want["nstep"]).any()
-            assert (want["nstep_ok"][:, nan_rows & (L == k) & ~term] == 0).all()
-            if steve:
-                w, cnt = want["steve_weight"], want["steve_count"]
-                if ((w == 0) & (cnt < 2) & (w.sum(axis=0) > 0)[None]).any():
-                    seen.add("weight-0")
-                if want["steve_fallback"].any():
-                    seen.add("fallback")
-    need = {"L=0", "L=k", "terminated", "diverged", "truncated", "inf-unpenalised", "nan-boot"}
-    if steve:
-        need |= {"fallback"} | ({"weight-0"} if k >= 2 else set())
+            seen |= tref.branches(x, cfg, want, steve)
+    need = tref.needed(k, steve)
     assert seen >= need, "never occurred: %s" % sorted(need - seen)
 
 
@@ -178,9 +128,10 @@ def test_lds_refusal_and_the_scan_without_steve(eng):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- 2: position
-@pytest.mark.parametrize("m,n,k,shift", [(17, 3, 7, 5), (130, 3, 2, 50)])
+@pytest.mark.parametrize("m,n,k,shift", [(17, 3, 7, 5), (130, 3, 2, 50), (20, 16, 64, 3)])
 def test_positional_independence(eng, m, n, k, shift):
-    """the same start states at another position (rolled along m, across the workgroup boundary at (130, 3, 2)) give the same bits"""
+    """the same start states at another position (rolled along m, across the workgroup boundary at (130, 3, 2); by 3 at (20, 16, 64),
+    whose groups of 8 a start state then crosses) give the same bits"""
     x = _variant(m, n, k, 8)
     rolled = {key: np.ascontiguousarray(np.roll(v, shift, axis=1)) for key, v in x.items()}
     a, b = _run(eng, x, CONFIGS[1], FLOOR), _run(eng, rolled, CONFIGS[1], FLOOR)

@@ -556,25 +556,28 @@ def _everything(eng, prob, name, mppi):
     return e
 
 
-def _fused(eng, e, args, state, carry, call, off=(), policy=None, **kw):
+def _fused(eng, e, args, state, carry, call, off=(), policy=None, critic=None, **kw):
     """`cadm_rewarded_plan` with everything of `e` on but the terms named in `off`; policy: a `policy_params` of the engine's registered
-    policy net -- then `cadm_guided_plan` with its proposals next to them (tests/test_gpu_policy_envelope.py)"""
+    policy net -- then `cadm_guided_plan` with its proposals next to them (tests/test_gpu_policy_envelope.py); critic: a `critic_params`
+    of the registered critics -- then `cadm_critic_plan` (tests/test_gpu_critic_envelope.py; "value" must be in `off`: one terminal term)"""
     g = lambda k: None if k in off else e[k]
     prev, prefix = (None, None) if "act" in off else state
     plan = eng.rewarded_plan if policy is None else (lambda *a, **k: eng.guided_plan(policy, *a, **k))
+    if critic is not None:
+        plan = lambda *a, **k: eng.critic_plan(critic, policy, *a, **k)
     return plan(g("reward"), g("value"), g("unc"), g("act"), prev, prefix, True, g("track"), e["targets"], e["offset"], g("knots"),
                 None if "knots" in off else e["phase"], e["cons"], e["score"], e["prm"], *args, N, carry=carry[0],
                 carry_valid=carry[1], seed=4, call=call, **kw)
 
 
-def _stepwise(eng, e, args, state, carry, call, mppi, off=(), policy=None, **kw):
+def _stepwise(eng, e, args, state, carry, call, mppi, off=(), policy=None, critic=None, **kw):
     """the same loop one launch at a time"""
     g = lambda k: None if k in off else e[k]
     return hplanner.icem_plan(eng, *args, N, carry=carry[0], carry_valid=carry[1], seed=4, call=call, update="mppi" if mppi else "cem",
                               temperature=0.5, relative=True, score=e["score"], constraints=e["cons"], knots=g("knots"),
                               phase=None if "knots" in off else e["phase"], tracking=None if "track" in off else (e["track"], e["targets"], e["offset"]),
                               actuator=None if "act" in off else (e["act"], state[0], state[1]), action_advance=True, uncertainty=g("unc"),
-                              value=g("value"), reward=g("reward"), policy=policy, **e["icem"], **kw)
+                              value=g("value"), reward=g("reward"), policy=policy, critic=critic, **e["icem"], **kw)
 
 
 LOOP = [(e, u) for e in ("slim", "pend") for u in ("mppi", "cem")]

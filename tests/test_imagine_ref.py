@@ -19,6 +19,30 @@ def _src(*parts):
     return open(os.path.join(ROOT, *parts)).read()
 
 
+# ---------------------------------------------------------------------------------------------------------------------- the stage's groups
+def test_group_rule():
+    """`imagine_ref.group` / `lds_bytes`, the restated `img_group` / `img_lds_bytes` of csrc/imagine.hip (whose constants the restatement
+    carries), on the engines of tests/test_gpu_imagine_envelope.py: the budget of 12288 floats cuts the group to 7, 13, 8 and 2, the 37
+    rows of the stage test fall into the groups the table names -- every one with a partial last group --, p = 255 at D = 48 fits no
+    row; and the engines of tests/test_gpu_imagine.py keep the full 16."""
+    src = _src("cadm_amd", "csrc", "imagine.hip")
+    assert int(re.search(r"IMG_GROUP = (\d+);", src).group(1)) == iref.GROUP
+    assert re.search(r"IMG_LDS_BUDGET = 48 \* 1024;", src) and iref.LDS_BUDGET == 48 * 1024
+    for name, (_, D, p, G, groups) in iref.STAGE_ENGINES.items():
+        assert iref.group(p, D) == G, name
+        if G:
+            assert iref.lds_bytes(G, p, D) <= iref.LDS_BUDGET < iref.lds_bytes(G + 1, p, D) and G < iref.GROUP
+            assert [min(G, 37 - r) for r in range(0, 37, G)] == groups and sum(groups) == 37 and groups[-1] < G and iref.STAGE_AT.get(name, 100) % G != 0
+    floats = lambda G, p, D: iref.lds_bytes(G, p, D) // 4
+    assert (floats(7, 35, 45), floats(13, 50, 18), floats(8, 30, 48), floats(2, 125, 48)) == (11399, 11969, 11960, 12146)
+    assert floats(1, 255, 48) == 12337 > 12288 == iref.LDS_BUDGET // 4
+    assert 35 * 45 % 2 == 1 and sorted({(r * 35 * 45) % 4 for r in range(0, 37, 7)}) == [0, 1, 2, 3], "slim35: group starts of every alignment"
+    assert 125 > 256 // 48 and 50 > 256 // 18 and 30 > 256 // 48 and 35 > 256 // 45, "p > S: the broadcast walk carries"
+    for p, D in ((5, 3), (5, 11), (5, 48), (20, 18)):
+        assert iref.group(p, D) == 16
+    assert iref.group(685, 18) == 0 and iref.group(680, 18) == 1      # halfcheetah: the first p (a multiple of E = 5) that fits no row
+
+
 # ---------------------------------------------------------------------------------------------------------------------- the draw
 @pytest.mark.parametrize("p", [1, 5, 20])
 def test_draw_is_in_range(p):

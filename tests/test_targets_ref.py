@@ -164,7 +164,38 @@ def test_float32_steve_against_float64():
     assert worst <= 4.0 * STEVE_MEASURED
 
 
-# ---------------------------------------------------------------------------------------------------------------------- 4: the parser
+# ---------------------------------------------------------------------------------------------------------------------- 4: the GPU test's shapes
+def test_group_rule():
+    """`targets_ref.group` / `lds_bytes`, the restated `tgt_group` / `tgt_lds_bytes` of csrc/imagine_targets.hip, on the shapes
+    tests/test_gpu_imagine_targets.py launches: the three whose group the 48 KiB budget or m cuts, the shapes it leaves alone, and
+    the refusal"""
+    assert tref.lds_bytes(8, 16, 64) == 8 * 5632 <= 48 * 1024 < tref.lds_bytes(9, 16, 64)
+    for (m, n, k), (G, owned) in tref.GROUPS.items():
+        assert tref.group(m, n, k) == G and [min(G, m - i) for i in range(0, m, G)] == owned and sum(owned) == m
+    assert tref.group(20, 16, 64) < 256 // 16 and tref.group(9, 100, 20) == 256 // 100 and tref.group(3, 300, 4) == 1 and 300 > tref.THREADS
+    # the shapes from before: none is cut by the budget
+    for m, n, k, steve in tref.SHAPES:
+        if steve and (m, n, k) not in tref.GROUPS:
+            assert tref.group(m, n, k) == min(max(256 // n, 1), m), (m, n, k)
+    assert tref.group(1, 700, 20) == 0 and tref.group(2, 700, 14) == 1 and tref.lds_bytes(1, 700, 14) == 5 * 9800 + 8 * 14
+
+
+@pytest.mark.parametrize("m,n,k,steve", tref.SHAPES, ids=["m%d-n%d-k%d" % s[:3] for s in tref.SHAPES])
+def test_every_branch_occurs_at_every_shape(m, n, k, steve):
+    """over the 9 variants and 3 parameter sets tests/test_gpu_imagine_targets.py::test_against_restatement runs at a shape, the
+    restatement reaches every branch of the arithmetic the shape admits -- what a bit-equal kernel is then known to have computed"""
+    seen = set()
+    for v in range(9):
+        x = tref.variant(m, n, k, v)
+        for cfg in tref.CONFIGS:
+            gamma, lam, beta, maxd = cfg
+            want = tref.targets(**x, gamma=gamma, lam=lam, penalty=beta, max_disagreement=maxd, var_floor=tref.FLOOR if steve else None)
+            seen |= tref.branches(x, cfg, want, steve)
+    need = tref.needed(k, steve)
+    assert seen >= need, "never occurred: %s" % sorted(need - seen)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- 5: the parser
 def _batch(k=3, m=2, n=2, D=5):
     z = np.zeros((k, m, n), F)
     return dict(rew=z, valid=np.ones((k, m, n), np.uint8), done=np.zeros((k, m, n), np.uint8), disagreement=z, states=np.zeros((k + 1, m, n, D), F))
