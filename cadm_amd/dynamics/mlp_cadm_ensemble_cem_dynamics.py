@@ -96,7 +96,7 @@ Differences a caller can see (all opt-in except the first):
     prediction of every ensemble member (the reference has no public predict).
 """
 import time
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import joblib
 import numpy as np
@@ -208,6 +208,53 @@ def calibration_summary(out):
         cdf = csum[..., 1:] / n[:, :, None]
         res["calibration_error"] = np.abs(cdf - np.arange(1, p + 2) / (p + 1.0)).max(axis=-1).mean(axis=-1)
     return res
+
+
+# The four nets a caller hands a model at run time: the PlanOptions field that declares one, the kwarg behind that field, the model's
+# "the engine holds one" attribute, what the messages call it, its setter, and the engine method that registers it (None clears it).
+_Net = namedtuple("_Net", "field kwarg flag noun setter register")
+_NETS = dict(value=_Net("value_params", "cem_terminal_value", "_value_set", "value net", "set_terminal_value", "set_value_net"),
+             reward=_Net("reward_params", "cem_reward_net", "_reward_set", "reward net", "set_reward_net", "set_reward_net"),
+             policy=_Net("policy_params", "cem_policy_prior", "_policy_set", "policy net", "set_policy", "set_policy_net"),
+             critics=_Net("critic_params", "cem_terminal_q", "_critics_set", "critics", "set_critics", "set_critic_nets"))
+
+
+def _need_net(model, net, who, under=None):
+    """Refuse for `who` while the model holds no `net`; under: the option the call plans under (get_action's wording)."""
+    row = _NETS[net]
+    if not getattr(model, row.flag):
+        raise RuntimeError("%s: this model %shas no %s (call %s first)" % (who, "plans under %s and " % under if under else "", row.noun, row.setter))
+
+
+def _require_net(model, net, who, need_net=False, need_actor=False):
+    """The model's options, for a method of `net` -- refused without the option that declares it, with need_net while none is
+    registered, with need_actor while no policy net is.  (Functions of the model: a refusal reads `_opt` and the flags alone.)"""
+    opt = getattr(model, "_opt", None)
+    if opt is None or getattr(opt, _NETS[net].field) is None:
+        raise ValueError("%s: this model has no %s" % (who, _NETS[net].kwarg))
+    if need_net:
+        _need_net(model, net, who)
+    if need_actor:
+        _need_net(model, "policy", who)
+    return opt
+
+
+def _require_policy(model, who, need_net=False):
+    """`_require_net` for the methods of the policy net that need no prior: the actor of `cem_terminal_q` will do, and so will the
+    one of `imagine_policy` (no planner option: the options may then be None)."""
+    opt = getattr(model, "_opt", None)
+    declared = opt is not None and (opt.policy_params is not None or opt.critic_params is not None)
+    if not declared and getattr(model, "_imagine_policy", None) is None:
+        raise ValueError("%s: this model has no cem_policy_prior and no cem_terminal_q (and no imagine_policy)" % who)
+    if need_net:
+        _need_net(model, "policy", who)
+    return opt
+
+
+def _register_net(model, net, params, *given):
+    """`set_*` (params and what the caller gave: weights, mean, std) and `clear_*` (None) of a net: the engine's copy and the flag."""
+    getattr(model.engine, _NETS[net].register)(params, *given)
+    setattr(model, _NETS[net].flag, params is not None)
 
 
 class MLPEnsembleCEMDynamicsModel(object):
@@ -454,25 +501,11 @@ class MLPEnsembleCEMDynamicsModel(object):
         `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.  On a model with
         `cem_discount` the cost and the returns are the discounted ones; step stays undiscounted."""
         self._require_uncertainty("uncertainty_cost")
-        self._push_stats()
-        opt = self._opt
-        cp_obs, cp_act = self._rollout_inputs("uncertainty_cost", obs, actions, cp_obs, cp_act)
-        eng = self.engine
-        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
-        acts = eng._t(actions)
-        squeeze = acts.dim() == 3
-        acts = (acts[:, None] if squeeze else acts).contiguous()
-        obs = eng._t(obs)
-        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
-                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
-        first = None
-        if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
-            _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
-        step, cost = eng.uncertainty_cost(traj, opt.uncertainty_params, first=first, want_steps=True)
-        res = dict(step=step.cpu().numpy(), cost=cost.cpu().numpy(), returns=self._env_rows(traj, obs, acts, rows).cpu().numpy())
-        if squeeze:
-            res = {k: v[:, 0] for k, v in res.items()}
-        return res
+        obs, acts, rows, traj, squeeze = self._replay("uncertainty_cost", obs, actions, cp_obs, cp_act, seed)
+        # (the options are read behind the replay: its push of new statistics replaces them with the ones that hold the delta_std weights)
+        step, cost = self.engine.uncertainty_cost(traj, self._opt.uncertainty_params, first=self._terminate_first(traj, rows, obs, acts),
+                                                  want_steps=True)
+        return self._result(squeeze, step=step, cost=cost, returns=self._env_rows(traj, obs, acts, rows))
 
     def _next_call(self):
         self._call += 1
@@ -625,16 +658,11 @@ class MLPEnsembleCEMDynamicsModel(object):
         if self._opt.actuator_params is not None:      # first call, or another number of envs: nothing applied, nothing committed; the
             self._actuator_tensors(m)                  # library moves both on behind the plan, on the engine's stream (cem_action_advance)
             extra.update(act_prev=self._act_prev, act_prefix=self._act_prefix)
-        if self._opt.value_params is not None and not self._value_set:
-            raise RuntimeError("get_action: this model plans under cem_terminal_value and has no value net (call set_terminal_value first)")
-        if self._opt.reward_params is not None and not self._reward_set:
-            raise RuntimeError("get_action: this model plans under cem_reward_net and has no reward net (call set_reward_net first)")
-        if self._opt.policy_params is not None and not self._policy_set:
-            raise RuntimeError("get_action: this model plans under cem_policy_prior and has no policy net (call set_policy first)")
-        if self._opt.critic_params is not None and not self._critics_set:
-            raise RuntimeError("get_action: this model plans under cem_terminal_q and has no critics (call set_critics first)")
-        if self._opt.critic_params is not None and not self._policy_set:
-            raise RuntimeError("get_action: this model plans under cem_terminal_q and has no policy net (call set_policy first)")
+        for net, row in _NETS.items():      # value, reward, policy, critics: every declared net is registered ...
+            if getattr(self._opt, row.field) is not None:
+                _need_net(self, net, "get_action", under=row.kwarg)
+        if self._opt.critic_params is not None:      # ... and so is the actor the critics are evaluated at
+            _need_net(self, "policy", "get_action", under="cem_terminal_q")
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
@@ -762,52 +790,30 @@ class MLPEnsembleCEMDynamicsModel(object):
             raise ValueError("tracking_cost: this model has no cem_tracking")
         if self._targets is None:
             raise RuntimeError("tracking_cost: this model has no targets (call set_targets first)")
-        self._push_stats()
-        cp_obs, cp_act = self._rollout_inputs("tracking_cost", obs, actions, cp_obs, cp_act)
-        eng = self.engine
-        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
-        acts = eng._t(actions)
-        squeeze = acts.dim() == 3
-        acts = (acts[:, None] if squeeze else acts).contiguous()
-        obs = eng._t(obs)
-        raw, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
-                                        call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
+        obs, acts, raw, traj, squeeze = self._replay("tracking_cost", obs, actions, cp_obs, cp_act, seed)
         raw = self._env_rows(traj, obs, acts, raw)
-        rows, cost = eng.tracking_returns(traj, raw, self._opt.track_params, self._targets, offset=self._target_offset, want_cost=True)
-        res = dict(cost=cost.cpu().numpy(), returns=rows.cpu().numpy(), returns_untracked=raw.cpu().numpy())
-        if squeeze:
-            res = {k: v[:, 0] for k, v in res.items()}
-        return res
+        rows, cost = self.engine.tracking_returns(traj, raw, self._opt.track_params, self._targets, offset=self._target_offset, want_cost=True)
+        return self._result(squeeze, cost=cost, returns=rows, returns_untracked=raw)
 
     # ------------------------------------------------------------------ terminal value (INTEGRATION.md "Terminal value")
-    def _require_value(self, who, need_net=False):
-        opt = getattr(self, "_opt", None)
-        if opt is None or opt.value_params is None:
-            raise ValueError("%s: this model has no cem_terminal_value" % who)
-        if need_net and not self._value_set:
-            raise RuntimeError("%s: this model has no value net (call set_terminal_value first)" % who)
-        return opt
-
     def set_terminal_value(self, weights, obs_mean=None, obs_std=None):
         """The value net of `cem_terminal_value` from the next call on: `weights` a list of (W [in,out], b [out]) per layer, numpy or
         torch, or a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules (Linear.weight is transposed on import) -- of the
         declared layer sizes and activation, else it is refused; obs_mean / obs_std [D] (None: 0 / 1, std finite and > 0): the net reads
         (obs - obs_mean) / obs_std of the raw observation.  Everything is copied: a later edit of the caller's tensors changes no plan.
         Replacing the net rebuilds nothing."""
-        opt = self._require_value("set_terminal_value")
-        self.engine.set_value_net(opt.value_params, weights, obs_mean=obs_mean, obs_std=obs_std)
-        self._value_set = True
+        opt = _require_net(self, "value", "set_terminal_value")
+        _register_net(self, "value", opt.value_params, weights, obs_mean, obs_std)
 
     def clear_terminal_value(self):
         """Remove the value net: get_action on a model with `cem_terminal_value` then raises until `set_terminal_value` is called."""
-        self._require_value("clear_terminal_value")
-        self.engine.set_value_net(None)
-        self._value_set = False
+        _require_net(self, "value", "clear_terminal_value")
+        _register_net(self, "value", None)
 
     def terminal_value(self, states):
         """V of raw observations `states` [..., D] (numpy or tensor) through the planner's kernel -> numpy [...]; NaN for a state with a
         non-finite value."""
-        self._require_value("terminal_value", need_net=True)
+        _require_net(self, "value", "terminal_value", need_net=True)
         return self.engine.value_eval(states).cpu().numpy()
 
     def plan_terminal_value(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
@@ -819,57 +825,31 @@ class MLPEnsembleCEMDynamicsModel(object):
           first [m,n,p]     with `cem_constraints` in terminate mode their first violations (a particle with first < H gets no value), else None
         The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.
         On a model with `cem_discount` the planner adds weight * gamma^H * value (`plan_returns`' weights[H]); value itself is V."""
-        opt = self._require_value("plan_terminal_value", need_net=True)
-        self._push_stats()
-        cp_obs, cp_act = self._rollout_inputs("plan_terminal_value", obs, actions, cp_obs, cp_act)
-        eng = self.engine
-        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
-        acts = eng._t(actions)
-        squeeze = acts.dim() == 3
-        acts = (acts[:, None] if squeeze else acts).contiguous()
-        obs = eng._t(obs)
-        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
-                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
-        first = None
-        if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
-            _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
-        _, v = eng.value_returns(traj, rows, opt.value_params, first=first, want_v=True)
-        res = dict(value=v.cpu().numpy(), first=None if first is None else first.cpu().numpy())
-        if squeeze:
-            res = {k: None if x is None else x[:, 0] for k, x in res.items()}
-        return res
+        opt = _require_net(self, "value", "plan_terminal_value", need_net=True)
+        obs, acts, rows, traj, squeeze = self._replay("plan_terminal_value", obs, actions, cp_obs, cp_act, seed)
+        first = self._terminate_first(traj, rows, obs, acts)
+        _, v = self.engine.value_returns(traj, rows, opt.value_params, first=first, want_v=True)
+        return self._result(squeeze, value=v, first=first)
 
     # ------------------------------------------------------------------ terminal value from Q critics (INTEGRATION.md "Terminal value from Q critics")
-    def _require_critics(self, who, need_nets=False, need_actor=False):
-        opt = getattr(self, "_opt", None)
-        if opt is None or opt.critic_params is None:
-            raise ValueError("%s: this model has no cem_terminal_q" % who)
-        if need_nets and not self._critics_set:
-            raise RuntimeError("%s: this model has no critics (call set_critics first)" % who)
-        if need_actor and not self._policy_set:
-            raise RuntimeError("%s: this model has no policy net (call set_policy first)" % who)
-        return opt
-
     def set_critics(self, nets, in_mean=None, in_std=None):
         """The Q critics of `cem_terminal_q` from the next call on: `nets` a list of n_critics nets, each what `set_terminal_value` takes
         (a list of (W [in,out], b [out]) per layer or a torch.nn.Sequential) with D + A inputs -- of the declared layer sizes and
         activation, else it is refused; in_mean / in_std [D + A] (None: 0 / 1): every critic reads ([obs ; act] - in_mean) / in_std of
         the raw observation and the actor's clipped action.  Everything is copied; replacing the critics rebuilds nothing."""
-        opt = self._require_critics("set_critics")
-        self.engine.set_critic_nets(opt.critic_params, nets, in_mean=in_mean, in_std=in_std)
-        self._critics_set = True
+        opt = _require_net(self, "critics", "set_critics")
+        _register_net(self, "critics", opt.critic_params, nets, in_mean, in_std)
 
     def clear_critics(self):
         """Remove the critics: get_action on a model with `cem_terminal_q` then raises until `set_critics` is called."""
-        self._require_critics("clear_critics")
-        self.engine.set_critic_nets(None)
-        self._critics_set = False
+        _require_net(self, "critics", "clear_critics")
+        _register_net(self, "critics", None)
 
     def q_value(self, states, actions=None, return_each=False):
         """The reduced Q of raw observations `states` [..., D] (numpy or tensor) through the planner's kernel -> numpy [...]: at the
         policy net's action (actions None; `set_policy` first), or at `actions` [..., A].  NaN for a state (or action) with a non-finite
         value.  return_each: (q, each [n_critics, ...]), every critic's own value."""
-        self._require_critics("q_value", need_nets=True, need_actor=actions is None)
+        _require_net(self, "critics", "q_value", need_net=True, need_actor=actions is None)
         out = self.engine.critic_eval(states, actions, want_each=return_each)
         return (out[0].cpu().numpy(), out[1].cpu().numpy()) if return_each else out.cpu().numpy()
 
@@ -882,39 +862,13 @@ class MLPEnsembleCEMDynamicsModel(object):
           first [m,n,p]     with `cem_constraints` in terminate mode their first violations (a particle with first < H gets no q), else None
         The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.
         On a model with `cem_discount` the planner adds weight * gamma^H * q (`plan_returns`' weights[H]); q itself is the reduced Q."""
-        opt = self._require_critics("plan_terminal_q", need_nets=True, need_actor=True)
-        self._push_stats()
-        cp_obs, cp_act = self._rollout_inputs("plan_terminal_q", obs, actions, cp_obs, cp_act)
-        eng = self.engine
-        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
-        acts = eng._t(actions)
-        squeeze = acts.dim() == 3
-        acts = (acts[:, None] if squeeze else acts).contiguous()
-        obs = eng._t(obs)
-        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
-                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
-        first = None
-        if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
-            _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
-        _, q = eng.critic_returns(traj, rows, opt.critic_params, first=first, want_q=True)
-        res = dict(q=q.cpu().numpy(), first=None if first is None else first.cpu().numpy())
-        if squeeze:
-            res = {k: None if x is None else x[:, 0] for k, x in res.items()}
-        return res
+        opt = _require_net(self, "critics", "plan_terminal_q", need_net=True, need_actor=True)
+        obs, acts, rows, traj, squeeze = self._replay("plan_terminal_q", obs, actions, cp_obs, cp_act, seed)
+        first = self._terminate_first(traj, rows, obs, acts)
+        _, q = self.engine.critic_returns(traj, rows, opt.critic_params, first=first, want_q=True)
+        return self._result(squeeze, q=q, first=first)
 
     # ------------------------------------------------------------------ policy prior (INTEGRATION.md "Policy prior")
-    def _require_policy(self, who, need_net=False, prior_or_q=False):
-        opt = getattr(self, "_opt", None)
-        if prior_or_q and getattr(self, "_imagine_policy", None) is not None:      # (the actor of `imagine` alone: no planner option)
-            if need_net and not self._policy_set:
-                raise RuntimeError("%s: this model has no policy net (call set_policy first)" % who)
-            return opt
-        if opt is None or (opt.policy_params is None and not (prior_or_q and opt.critic_params is not None)):
-            raise ValueError("%s: this model has no cem_policy_prior%s" % (who, " and no cem_terminal_q (and no imagine_policy)" if prior_or_q else ""))
-        if need_net and not self._policy_set:
-            raise RuntimeError("%s: this model has no policy net (call set_policy first)" % who)
-        return opt
-
     def _actor_params(self):
         """the `PolicyParams` this model's actor is registered under: the planner's declaration, else `imagine_policy`'s; None without one"""
         opt = getattr(self, "_opt", None)
@@ -926,39 +880,34 @@ class MLPEnsembleCEMDynamicsModel(object):
         b [out]) per layer or a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules, the last Linear with A outputs) -- of the
         declared layer sizes and activation, else it is refused; obs_mean / obs_std [D] (None: 0 / 1): the net reads (obs - obs_mean) /
         obs_std of the raw observation.  Everything is copied; replacing the net rebuilds nothing."""
-        self._require_policy("set_policy", prior_or_q=True)      # (the actor of cem_terminal_q or imagine_policy alone: registered with n_samples = 1)
-        self.engine.set_policy_net(self._actor_params(), weights, obs_mean=obs_mean, obs_std=obs_std)
-        self._policy_set = True
+        _require_policy(self, "set_policy")      # (the actor of cem_terminal_q or imagine_policy alone: registered with n_samples = 1)
+        _register_net(self, "policy", self._actor_params(), weights, obs_mean, obs_std)
 
     def clear_policy(self):
         """Remove the policy net: get_action on a model with `cem_policy_prior` then raises until `set_policy` is called."""
-        self._require_policy("clear_policy", prior_or_q=True)
-        self.engine.set_policy_net(None)
-        self._policy_set = False
+        _require_policy(self, "clear_policy")
+        _register_net(self, "policy", None)
 
     def policy_action(self, states):
         """The policy's action of raw observations `states` [..., D] (numpy or tensor) through the planner's kernel -> numpy [..., A]:
         squashed and clipped to the action bounds, no noise; clip(0, lb, ub) for a state with a non-finite value."""
-        self._require_policy("policy_action", need_net=True, prior_or_q=True)
+        _require_policy(self, "policy_action", need_net=True)
         return self.engine.policy_eval(states).cpu().numpy()
 
     def policy_proposals(self, obs, cp_obs=None, cp_act=None, seed=None, return_states=False):
         """The sequences the policy prior would inject for `obs` [m,D] (with a context model its history cp_obs / cp_act) -> numpy
         [m,n_samples,H,A]: the context encoder and the proposal roll, drawn under (seed, the last get_action's call); no counter moves.
         return_states: (proposals, states [H,m,n_samples,p,D]), the particle states every step's actions were computed from."""
-        opt = self._require_policy("policy_proposals", need_net=True)
+        opt = _require_net(self, "policy", "policy_proposals", need_net=True)
         self._push_stats()
         D, m = self.obs_space_dims, int(np.shape(obs)[0])
         if tuple(np.shape(obs)) != (m, D) or m == 0:
             raise ValueError("policy_proposals: obs %r, expected [m,%d] with m >= 1" % (tuple(np.shape(obs)), D))
-        ctx_vec = None
+        if self.context_out_dim > 0 and (cp_obs is None or cp_act is None):
+            raise ValueError("policy_proposals: cp_obs and cp_act are required for a context model")
         eng = self.engine
-        if self.context_out_dim > 0:
-            if cp_obs is None or cp_act is None:
-                raise ValueError("policy_proposals: cp_obs and cp_act are required for a context model")
-            ctx_vec = eng.context_forward(cp_obs, cp_act)
-        out = eng.policy_propose(opt.policy_params, eng._t(obs).contiguous(), ctx_vec, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
-                                 call=self._call & 0xFFFFFFFF, want_states=return_states)
+        out = eng.policy_propose(opt.policy_params, eng._t(obs).contiguous(), self._context_vec(cp_obs, cp_act), want_states=return_states,
+                                 **self._replay_key(seed))
         return (out[0].cpu().numpy(), out[1].cpu().numpy()) if return_states else out.cpu().numpy()
 
     # ------------------------------------------------------------------ imagined rollouts (INTEGRATION.md "Imagined rollouts for a learner")
@@ -1037,10 +986,10 @@ class MLPEnsembleCEMDynamicsModel(object):
                                           has_q=opt is not None and opt.critic_params is not None)
         eng = self.engine
         if a.bootstrap == "value":
-            self._require_value("imagine_targets", need_net=True)
+            _require_net(self, "value", "imagine_targets", need_net=True)
             boot = eng.value_eval(batch["states"])
         elif a.bootstrap == "q":
-            self._require_critics("imagine_targets", need_nets=True, need_actor=True)
+            _require_net(self, "critics", "imagine_targets", need_net=True, need_actor=True)
             boot = eng.critic_eval(batch["states"])
         else:
             boot = eng._t(bootstrap)
@@ -1052,34 +1001,24 @@ class MLPEnsembleCEMDynamicsModel(object):
         return out
 
     # ------------------------------------------------------------------ learned reward (INTEGRATION.md "Learned reward")
-    def _require_reward(self, who, need_net=False):
-        opt = getattr(self, "_opt", None)
-        if opt is None or opt.reward_params is None:
-            raise ValueError("%s: this model has no cem_reward_net" % who)
-        if need_net and not self._reward_set:
-            raise RuntimeError("%s: this model has no reward net (call set_reward_net first)" % who)
-        return opt
-
     def set_reward_net(self, weights, in_mean=None, in_std=None):
         """The reward net of `cem_reward_net` from the next call on: `weights` as `set_terminal_value` takes them (a list of (W [in,out],
         b [out]) per layer, or a torch.nn.Sequential of Linear and ReLU / Tanh / SiLU modules) -- of the declared input, layer sizes and
         activation, else it is refused; in_mean / in_std [K] over the concatenated input (None: 0 / 1, std finite and > 0): the net reads
         (input - in_mean) / in_std of the raw observations and actions.  Everything is copied; replacing the net rebuilds nothing."""
-        opt = self._require_reward("set_reward_net")
-        self.engine.set_reward_net(opt.reward_params, weights, in_mean=in_mean, in_std=in_std)
-        self._reward_set = True
+        opt = _require_net(self, "reward", "set_reward_net")
+        _register_net(self, "reward", opt.reward_params, weights, in_mean, in_std)
 
     def clear_reward_net(self):
         """Remove the reward net: get_action on a model with `cem_reward_net` then raises until `set_reward_net` is called."""
-        self._require_reward("clear_reward_net")
-        self.engine.set_reward_net(None)
-        self._reward_set = False
+        _require_net(self, "reward", "clear_reward_net")
+        _register_net(self, "reward", None)
 
     def reward_net(self, obs=None, act=None, next_obs=None):
         """R of raw transitions through the planner's kernel -> numpy [...]: obs [..., D], act [..., A], next_obs [..., D] (numpy or
         tensor), of which the declared `inputs` says which are read and concatenated (the others may be None); NaN for an input with a
         non-finite value."""
-        opt = self._require_reward("reward_net", need_net=True)
+        opt = _require_net(self, "reward", "reward_net", need_net=True)
         eng = self.engine
         need = {"next_obs": (("next_obs", next_obs, eng.D),), "obs_act": (("obs", obs, eng.D), ("act", act, eng.A)),
                 "obs_act_next_obs": (("obs", obs, eng.D), ("act", act, eng.A), ("next_obs", next_obs, eng.D))}[opt.reward[0]]
@@ -1101,26 +1040,11 @@ class MLPEnsembleCEMDynamicsModel(object):
           first [m,n,p]     with `cem_constraints` in terminate mode their first violations (steps t <= first count), else None
         The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.
         On a model with `cem_discount` total is the discounted sum (gamma^t * R_t); reward stays undiscounted."""
-        opt = self._require_reward("plan_rewards", need_net=True)
-        self._push_stats()
-        cp_obs, cp_act = self._rollout_inputs("plan_rewards", obs, actions, cp_obs, cp_act)
-        eng = self.engine
-        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
-        acts = eng._t(actions)
-        squeeze = acts.dim() == 3
-        acts = (acts[:, None] if squeeze else acts).contiguous()
-        obs = eng._t(obs)
-        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
-                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
-        first = None
-        if opt.constraint_params is not None and opt.constraint_params.mode == _planner._lib.CONSTRAIN_MODES["terminate"]:
-            _, first, _ = eng.constrain_returns(traj, rows, opt.constraint_params, obs=obs, actions=acts)
-        _, steps, total = eng.reward_returns(traj, obs, acts, rows, opt.reward_params, first=first, want_steps=True)
-        res = dict(reward=steps.permute(1, 2, 3, 0).cpu().numpy(), total=total.cpu().numpy(),
-                   first=None if first is None else first.cpu().numpy())
-        if squeeze:
-            res = {k: None if x is None else x[:, 0] for k, x in res.items()}
-        return res
+        opt = _require_net(self, "reward", "plan_rewards", need_net=True)
+        obs, acts, rows, traj, squeeze = self._replay("plan_rewards", obs, actions, cp_obs, cp_act, seed)
+        first = self._terminate_first(traj, rows, obs, acts)
+        _, steps, total = self.engine.reward_returns(traj, obs, acts, rows, opt.reward_params, first=first, want_steps=True)
+        return self._result(squeeze, reward=steps.permute(1, 2, 3, 0), total=total, first=first)
 
     def _get_action_opt_in(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var):
         """The opt-in route of get_action: `_plan_opt_in` into the pinned host buffer."""
@@ -1154,22 +1078,9 @@ class MLPEnsembleCEMDynamicsModel(object):
         opt = getattr(self, "_opt", None)
         if opt is None or opt.discount == 1.0:
             raise ValueError("plan_returns: this model has no cem_discount")
-        self._push_stats()
-        cp_obs, cp_act = self._rollout_inputs("plan_returns", obs, actions, cp_obs, cp_act)
-        eng = self.engine
-        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
-        acts = eng._t(actions)
-        squeeze = acts.dim() == 3
-        acts = (acts[:, None] if squeeze else acts).contiguous()
-        obs = eng._t(obs)
-        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
-                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
-        out, steps = eng.discount_returns(traj, obs, acts, rows, want_steps=True)
-        res = dict(returns=out.cpu().numpy(), step_rewards=steps.permute(1, 2, 0, 3).cpu().numpy())
-        if squeeze:
-            res = {k: v[:, 0] for k, v in res.items()}
-        res["weights"] = eng.discount_weights()
-        return res
+        obs, acts, rows, traj, squeeze = self._replay("plan_returns", obs, actions, cp_obs, cp_act, seed)
+        out, steps = self.engine.discount_returns(traj, obs, acts, rows, want_steps=True)
+        return dict(self._result(squeeze, returns=out, step_rewards=steps.permute(1, 2, 0, 3)), weights=self.engine.discount_weights())
 
     # ------------------------------------------------------------------ forecast of a plan (INTEGRATION.md "Forecasting a plan")
     def _forecast_refuse(self, what):
@@ -1182,10 +1093,47 @@ class MLPEnsembleCEMDynamicsModel(object):
         if cem_init_mean is None:
             raise ValueError("get_action(return_forecast=True): the random-shooting route returns one action, not a plan to forecast")
         plan = MLPEnsembleCEMDynamicsModel.get_action(self, obs, cp_obs, cp_act, cem_init_mean, cem_init_var)      # (not a subclass's signature)
-        return plan, self._forecast(obs, plan, cp_obs, cp_act, 1, self.seed, self._call & 0xFFFFFFFF)
+        return plan, self._forecast(obs, plan, cp_obs, cp_act, 1, **self._replay_key())
+
+    def _replay_key(self, seed=None):
+        """The words a diagnostic's noise is keyed by: `seed`, the model's by default, and the last get_action's call.  No counter moves."""
+        return dict(seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF, call=self._call & 0xFFFFFFFF)
+
+    def _context_vec(self, cp_obs, cp_act):
+        """The context encoder's output for a checked history; None for a model without context, whatever history it was given."""
+        return self.engine.context_forward(cp_obs, cp_act) if self.context_out_dim > 0 else None
+
+    def _replay(self, who, obs, actions, cp_obs, cp_act, seed):
+        """What the plan companions share: the statistics pushed, the inputs checked and staged, the context encoder and ONE rollout of
+        `actions` that records its trajectories, drawn as `forecast` draws it -> (obs [m,D], actions [m,n,H,A], rows [m,n,p], traj
+        [H,m,n,p,D], squeeze: the input was [m,H,A] and the results drop their n axis).  The push may replace `self._opt`."""
+        self._push_stats()
+        cp_obs, cp_act = self._rollout_inputs(who, obs, actions, cp_obs, cp_act)
+        eng = self.engine
+        ctx_vec = self._context_vec(cp_obs, cp_act)
+        acts = eng._t(actions)
+        squeeze = acts.dim() == 3
+        acts = (acts[:, None] if squeeze else acts).contiguous()
+        obs = eng._t(obs)
+        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, it=_planner.FORECAST_IT, want_traj=True, **self._replay_key(seed))
+        return obs, acts, rows, traj, squeeze
+
+    def _terminate_first(self, traj, rows, obs, acts):
+        """The first violations [m,n,p] of a replay under this model's `cem_constraints` in terminate mode -- what cuts a term's sum, as in
+        the loop --, else None."""
+        prm = self._opt.constraint_params
+        if prm is None or prm.mode != _planner._lib.CONSTRAIN_MODES["terminate"]:
+            return None
+        return self.engine.constrain_returns(traj, rows, prm, obs=obs, actions=acts)[1]
+
+    @staticmethod
+    def _result(squeeze, **tensors):
+        """A companion's result: its device tensors [m,n,...] as numpy arrays, without the n axis for [m,H,A] input; None stays None."""
+        res = {k: None if v is None else v.cpu().numpy() for k, v in tensors.items()}
+        return {k: None if v is None else v[:, 0] for k, v in res.items()} if squeeze else res
 
     def _rollout_inputs(self, who, obs, actions, cp_obs, cp_act):
-        """The input checks `forecast` and `constraint_check` share -> (cp_obs, cp_act), None for a model without context."""
+        """The input checks `forecast` and the plan companions (`_replay`) share -> (cp_obs, cp_act), None for a model without context."""
         D, A, H = self.obs_space_dims, self.action_space_dims, self.n_forwards
         shp = tuple(int(v) for v in np.shape(actions))
         m = int(np.shape(obs)[0])
@@ -1208,7 +1156,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         eng = self.engine
         acts = eng._t(actions)
         squeeze = acts.dim() == 3
-        out = eng.plan_forecast(obs, cp_obs, cp_act, acts[:, None] if squeeze else acts, band_k=band_k, seed=int(seed) & 0xFFFFFFFF, call=call)
+        out = eng.plan_forecast(obs, cp_obs, cp_act, acts[:, None] if squeeze else acts, band_k=band_k, seed=seed, call=call)
         r = {k: v.cpu().numpy() for k, v in out.items()}
         res = dict(mean=r["mean"], member_mean=r["member_mean"], std_total=np.sqrt(r["var_total"]), std_epistemic=np.sqrt(r["var_epistemic"]),
                    std_aleatoric=np.sqrt(r["var_aleatoric"]), lo=r["lo"], hi=r["hi"], reward_mean=r["reward_mean"],
@@ -1232,7 +1180,7 @@ class MLPEnsembleCEMDynamicsModel(object):
         iteration word no planner loop uses.  The planner's call counter does not move: planning is the same with or without forecasts
         in between, and `forecast` of the plan `get_action` just returned reproduces `get_action(..., return_forecast=True)`'s."""
         self._forecast_refuse("forecast")
-        return self._forecast(obs, actions, cp_obs, cp_act, band_k, self.seed if seed is None else seed, self._call & 0xFFFFFFFF)
+        return self._forecast(obs, actions, cp_obs, cp_act, band_k, **self._replay_key(seed))
 
     def constraint_check(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
         """Which particles of `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) leave the region this model's `cem_constraints` declare
@@ -1245,21 +1193,11 @@ class MLPEnsembleCEMDynamicsModel(object):
         call counter does not move.  On a model with `cem_discount` the returns and the penalty are the discounted ones."""
         if self._opt is None or self._opt.constraint_params is None:
             raise ValueError("constraint_check: this model has no cem_constraints")
-        self._push_stats()
-        cp_obs, cp_act = self._rollout_inputs("constraint_check", obs, actions, cp_obs, cp_act)
-        eng = self.engine
-        ctx_vec = eng.context_forward(cp_obs, cp_act) if cp_obs is not None else None
-        acts = eng._t(actions)
-        squeeze = acts.dim() == 3
-        acts = (acts[:, None] if squeeze else acts).contiguous()
-        obs = eng._t(obs)
-        rows, traj = eng.rollout_returns(obs, ctx_vec, acts, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF,
-                                         call=self._call & 0xFFFFFFFF, it=_planner.FORECAST_IT, want_traj=True)
-        rows, first, viol = eng.constrain_returns(traj, self._env_rows(traj, obs, acts, rows), self._opt.constraint_params, obs=obs, actions=acts)
-        res = dict(first_violation=first.cpu().numpy(), violations=viol.cpu().numpy(), returns=rows.cpu().numpy())
+        obs, acts, rows, traj, squeeze = self._replay("constraint_check", obs, actions, cp_obs, cp_act, seed)
+        rows, first, viol = self.engine.constrain_returns(traj, self._env_rows(traj, obs, acts, rows), self._opt.constraint_params, obs=obs,
+                                                          actions=acts)
+        res = self._result(squeeze, first_violation=first, violations=viol, returns=rows)
         res["violation_fraction"] = (res["violations"] > 0).mean(axis=-1)
-        if squeeze:
-            res = {k: v[:, 0] for k, v in res.items()}
         return res
 
     def reset_plan_carry(self, mask=None):

@@ -832,7 +832,7 @@ class HipEngine:
         traj, rows = self._t(traj), self._t(rows)
         obs = None if obs is None else self._t(obs)
         actions = None if actions is None else self._t(actions)
-        if traj.dim() != 5 or rows.dim() != 3 or not traj.is_contiguous() or not rows.is_contiguous():
+        if traj.dim() != 5 or rows.dim() != 3:
             raise ValueError("constrain_returns: traj %r, rows %r: expected contiguous [H,m,n,p,D] and [m,n,p]" % (tuple(traj.shape), tuple(rows.shape)))
         H, m, n, p, D = traj.shape
         if (H, p, D) != (self.H, self.p, self.D) or tuple(rows.shape) != (m, n, p):
@@ -1000,7 +1000,7 @@ class HipEngine:
         targets = targets.contiguous()
         if offset is not None:
             offset = self._t(offset, dtype=torch.int32)
-            if tuple(offset.shape) != (m,) or not offset.is_contiguous():
+            if tuple(offset.shape) != (m,):
                 raise ValueError("%s: offset %r, expected [%d] int32" % (who, tuple(offset.shape), m))
         return targets, int(targets.shape[1]), offset
 
@@ -1010,22 +1010,9 @@ class HipEngine:
         result, or the list it takes.  targets [m,T,K] or [m,K]; offset [m] int32 (None: 0); first [m,n,p] int32 (None: every step
         counts): `constrain_returns`' first_violation -- steps behind it are not counted.  out: where rows' go (may be `rows` itself)."""
         prm = track if isinstance(track, _lib.TrackParams) else self.track_params(track)
-        traj, rows = self._t(traj), self._t(rows)
-        if traj.dim() != 5 or rows.dim() != 3 or not traj.is_contiguous() or not rows.is_contiguous():
-            raise ValueError("tracking_returns: traj %r, rows %r: expected contiguous [H,m,n,p,D] and [m,n,p]" % (tuple(traj.shape), tuple(rows.shape)))
+        traj, rows, first, out = HipEngine._returns_args(self, "tracking_returns", traj, rows, first, out)
         H, m, n, p, D = traj.shape
-        if (H, p, D) != (self.H, self.p, self.D) or tuple(rows.shape) != (m, n, p):
-            raise ValueError("tracking_returns: traj %r, rows %r do not agree with the engine (H=%d, p=%d, D=%d)"
-                             % (tuple(traj.shape), tuple(rows.shape), self.H, self.p, self.D))
         targets, T, offset = self._targets(targets, offset, m, prm.n, "tracking_returns")
-        if first is not None:
-            first = self._t(first, dtype=torch.int32)
-            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
-                raise ValueError("tracking_returns: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
-        if out is None:
-            out = torch.empty_like(rows)
-        elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("tracking_returns: out %r, expected contiguous float32 %r" % (tuple(out.shape), (m, n, p)))
         cost = torch.empty((m, n, p), dtype=torch.float32, device=self.device) if want_cost else None
         self._check(self.lib.cadm_tracking_returns(self._ctx, ct.byref(prm), ptr(traj), ptr(targets), T, ptr(offset), ptr(first), ptr(rows), m, n,
                                                    ptr(out), ptr(cost), self.stream), "cadm_tracking_returns")
@@ -1171,16 +1158,8 @@ class HipEngine:
         `params` (`uncertainty_params`) added over the counted steps; with want_steps (step [m,n,H], cost): u_t of every step, counted
         or not.  first [m,n,p] int32 (None: every step counts): `constrain_returns`' first_violation -- steps behind the smallest one of a
         candidate's particles are not counted.  lambda is not applied."""
-        traj = self._t(traj)
-        if traj.dim() != 5 or not traj.is_contiguous():
-            raise ValueError("uncertainty_cost: traj %r: expected contiguous [H,m,n,p,D]" % (tuple(traj.shape),))
+        traj, _, first, _ = HipEngine._returns_args(self, "uncertainty_cost", traj, None, first, None)
         H, m, n, p, D = traj.shape
-        if (H, p, D) != (self.H, self.p, self.D):
-            raise ValueError("uncertainty_cost: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (tuple(traj.shape), self.H, self.p, self.D))
-        if first is not None:
-            first = self._t(first, dtype=torch.int32)
-            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
-                raise ValueError("uncertainty_cost: first %r, expected contiguous int32 %r" % (tuple(first.shape), (m, n, p)))
         step = torch.empty((m, n, H), dtype=torch.float32, device=self.device) if want_steps else None
         cost = torch.empty((m, n), dtype=torch.float32, device=self.device)
         self._check(self.lib.cadm_uncertainty_cost(self._ctx, ct.byref(params), ptr(traj), ptr(first), m, n, ptr(step), ptr(cost), self.stream),
@@ -1354,20 +1333,24 @@ class HipEngine:
         return x, flat
 
     def _returns_args(self, who, traj, rows, first, out):
-        """What `value_returns`, `reward_returns` and `critic_returns` share: traj [H,m,n,p,D] and rows [m,n,p] as checked device
-        tensors, first [m,n,p] int32 or None, and out [m,n,p] (None: a new tensor)."""
-        traj, rows = self._t(traj), self._t(rows)
-        if traj.dim() != 5 or not traj.is_contiguous():
+        """What the stand-alone stage calls behind a rollout share: traj [H,m,n,p,D] and rows [m,n,p] as checked device tensors, first
+        [m,n,p] int32 or None, and out [m,n,p] (None: a new tensor).  rows None (`uncertainty_cost` reads none): no rows, no out."""
+        traj = self._t(traj)
+        if traj.dim() != 5:
             raise ValueError("%s: traj %r: expected contiguous [H,m,n,p,D]" % (who, tuple(traj.shape)))
         H, m, n, p, D = traj.shape
         if (H, p, D) != (self.H, self.p, self.D):
             raise ValueError("%s: traj %r does not agree with the engine (H=%d, p=%d, D=%d)" % (who, tuple(traj.shape), self.H, self.p, self.D))
-        if tuple(rows.shape) != (m, n, p) or not rows.is_contiguous():
-            raise ValueError("%s: rows %r, expected contiguous %r" % (who, tuple(rows.shape), (m, n, p)))
+        if rows is not None:
+            rows = self._t(rows)
+            if tuple(rows.shape) != (m, n, p):
+                raise ValueError("%s: rows %r, expected contiguous %r" % (who, tuple(rows.shape), (m, n, p)))
         if first is not None:
             first = self._t(first, dtype=torch.int32)
-            if tuple(first.shape) != (m, n, p) or not first.is_contiguous():
+            if tuple(first.shape) != (m, n, p):
                 raise ValueError("%s: first %r, expected contiguous int32 %r" % (who, tuple(first.shape), (m, n, p)))
+        if rows is None:
+            return traj, None, first, None
         if out is None:
             out = torch.empty_like(rows)
         elif tuple(out.shape) != (m, n, p) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rows.device:
@@ -1457,9 +1440,9 @@ class HipEngine:
         traj, rows, first, out = HipEngine._returns_args(self, "reward_returns", traj, rows, first, out)
         H, m, n, p, D = traj.shape
         obs, actions = self._t(obs), self._t(actions)
-        if tuple(obs.shape) != (m, D) or not obs.is_contiguous():
+        if tuple(obs.shape) != (m, D):
             raise ValueError("reward_returns: obs %r, expected contiguous %r" % (tuple(obs.shape), (m, D)))
-        if tuple(actions.shape) != (m, n, H, self.A) or not actions.is_contiguous():
+        if tuple(actions.shape) != (m, n, H, self.A):
             raise ValueError("reward_returns: actions %r, expected contiguous %r" % (tuple(actions.shape), (m, n, H, self.A)))
         steps = S = ws = None
         if want_steps:
@@ -1762,45 +1745,60 @@ class HipEngine:
         same bits (tests, tools).  `E`: the number of members the p particles split into (default: the engine's; the kernel reads no
         model).  `truth_ld`: floats between the truth rows of consecutive windows (default F * D); truth is then [m, truth_ld],
         a window's F * D values first."""
+        return self._window_stats("horizon_error", traj, truth, mask, calls, E, truth_ld, False, lambda E, D: (2 + E) * D + 2, self._horizon_out)
+
+    def _horizon_out(self, F, D, p, E):
+        """(the dict of `horizon_error`, what its two exports take for it: the five pointers, in the dict's order)"""
+        out = self._horizon_outputs(F, D, E)
+        return out, [ptr(v) for v in out.values()]
+
+    def _window_stats(self, who, traj, truth, mask, calls, E, truth_ld, split, floats, outputs):
+        """What `horizon_error` and `calibration_stats` share: `cadm_<who>` over the windows, in one stage-1 launch or one per entry of
+        `calls`.  split: the members must divide the particles (and the refusal names E); floats(E, D): the partial sums of one block at
+        one step; outputs(F, D, p, E) -> (the result dict, the export's arguments for it)."""
         traj, truth, mask = self._t(traj), self._t(truth), self._t(mask)
         F, m, p, D = traj.shape[0], traj.shape[1], traj.shape[-2], traj.shape[-1]
         E = self.E if E is None else int(E)
         ld = F * D if truth_ld is None else int(truth_ld)
         if (tuple(truth.shape) != ((m, F, D) if truth_ld is None else (m, ld)) or tuple(mask.shape) != (m, F) or traj.numel() != F * m * p * D
-                or E < 1):
-            raise ValueError("horizon_error: traj %r, truth %r, mask %r do not agree" % (tuple(traj.shape), tuple(truth.shape), tuple(mask.shape)))
+                or E < 1 or split and p % E):
+            raise ValueError("%s: traj %r, truth %r, mask %r%s do not agree"
+                             % (who, tuple(traj.shape), tuple(truth.shape), tuple(mask.shape), ", E %d" % E if split else ""))
         blocks = (m + 63) // 64
-        partials = torch.empty((blocks * F * ((2 + E) * D + 2),), dtype=torch.float32, device=self.device)
-        out = self._horizon_outputs(F, D, E)
-        w0 = 0
+        partials = torch.empty((blocks * F * floats(E, D),), dtype=torch.float32, device=self.device)
+        out, outs = outputs(F, D, p, E)
+        export, w0 = getattr(self.lib, "cadm_" + who), 0
         for n in (calls or [m]):
             # a launch reads its windows' [F, n, p, D] slice as one tensor
             part = traj if n == m else traj.reshape(F, m, p, D)[:, w0:w0 + n].contiguous()
-            self._check(self.lib.cadm_horizon_error(ptr(part), ptr(truth[w0:]), ld, ptr(mask[w0:]), n, F, p, E, D, w0, ptr(partials),
-                                                    blocks, ptr(out["se"]), ptr(out["spread"]), ptr(out["se_member"]), ptr(out["count"]),
-                                                    ptr(out["diverged"]), int(w0 + n >= m), self.stream), "cadm_horizon_error")
+            self._check(export(ptr(part), ptr(truth[w0:]), ld, ptr(mask[w0:]), n, F, p, E, D, w0, ptr(partials), blocks, *outs,
+                               int(w0 + n >= m), self.stream), "cadm_" + who)
             w0 += n
         if w0 != m:
-            raise ValueError("horizon_error: calls %r do not add up to %d windows" % (calls, m))
+            raise ValueError("%s: calls %r do not add up to %d windows" % (who, calls, m))
         return out
 
     def eval_horizon(self, dev, N, F, chunk=4096, seed=0, call=0, eps=None):
         """`cadm_eval_horizon` on the device-resident windowed dataset `dev` (what `fit` uploads: obs / obs_next [N,F*D], act
         [N,F*A], cp_obs / cp_act [N,.], plus future_bool [N,F] float32) -> the dict of `horizon_error`.  eps: injected noise
         [F,N,1,p,D] (parity tests)."""
+        return self._eval_windows("eval_horizon", "cadm_eval_workspace_bytes", self._horizon_out, dev, N, F, chunk, seed, call, eps)
+
+    def _eval_windows(self, who, sizer, outputs, dev, N, F, chunk, seed, call, eps):
+        """What `eval_horizon` and `eval_calibration` share: `cadm_<who>` over the dataset in chunks, on a workspace of `sizer` bytes;
+        outputs: as `_window_stats` takes it."""
         if chunk <= 0 or chunk % 64:
-            raise ValueError("eval_horizon: chunk must be a positive multiple of 64, got %r" % (chunk,))
+            raise ValueError("%s: chunk must be a positive multiple of 64, got %r" % (who, chunk))
         eps = None if eps is None else self._t(eps)
         mc = min(int(chunk), (N + 63) // 64 * 64)
         self.ensure_rollout(_lib.NOISE_NONE if self.deterministic else _lib.NOISE_INJECT if eps is not None else _lib.NOISE_PHILOX, min(mc, N), 1)
-        nbytes = self.lib.cadm_eval_workspace_bytes(self._ctx, int(N), int(F), int(chunk))
+        nbytes = getattr(self.lib, sizer)(self._ctx, int(N), int(F), int(chunk))
         ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
-        out = self._horizon_outputs(F, self.D)
+        out, outs = outputs(F, self.D, self.p, self.E)
         g = lambda k: ptr(dev.get(k))
-        self._check(self.lib.cadm_eval_horizon(self._ctx, g("obs"), g("act"), g("obs_next"), g("cp_obs") if self.C > 0 else None,
-                                               g("cp_act") if self.C > 0 else None, g("future_bool"), int(N), int(F), int(chunk), seed, call,
-                                               ptr(eps), ptr(ws), ptr(out["se"]), ptr(out["spread"]), ptr(out["se_member"]), ptr(out["count"]),
-                                               ptr(out["diverged"]), self.stream), "cadm_eval_horizon")
+        self._check(getattr(self.lib, "cadm_" + who)(self._ctx, g("obs"), g("act"), g("obs_next"), g("cp_obs") if self.C > 0 else None,
+                                                     g("cp_act") if self.C > 0 else None, g("future_bool"), int(N), int(F), int(chunk), seed,
+                                                     call, ptr(eps), ptr(ws), *outs, self.stream), "cadm_" + who)
         return out
 
     # ------------------------------------------------------------------ calibration of the predictive distribution (csrc/calibration.hip)
@@ -1818,44 +1816,18 @@ class HipEngine:
         """`cadm_calibration_stats` on device tensors: the arguments of `horizon_error` -> dict of device tensors rank_hist [F,D,p+1],
         rank_hist_member [E,F,D,p/E+1], ties / degenerate [F,D], count / diverged [F] (int32 counts) and crps / z2 / nll [F,D] (float32
         SUMS over the counted windows; z2 and nll leave the degenerate ones out)."""
-        traj, truth, mask = self._t(traj), self._t(truth), self._t(mask)
-        F, m, p, D = traj.shape[0], traj.shape[1], traj.shape[-2], traj.shape[-1]
-        E = self.E if E is None else int(E)
-        ld = F * D if truth_ld is None else int(truth_ld)
-        if (tuple(truth.shape) != ((m, F, D) if truth_ld is None else (m, ld)) or tuple(mask.shape) != (m, F) or traj.numel() != F * m * p * D
-                or E < 1 or p % E):
-            raise ValueError("calibration_stats: traj %r, truth %r, mask %r, E %d do not agree"
-                             % (tuple(traj.shape), tuple(truth.shape), tuple(mask.shape), E))
-        blocks = (m + 63) // 64
-        partials = torch.empty((blocks * F * 3 * D,), dtype=torch.float32, device=self.device)
+        return self._window_stats("calibration_stats", traj, truth, mask, calls, E, truth_ld, True, lambda E, D: 3 * D, self._calibration_out)
+
+    def _calibration_out(self, F, D, p, E):
+        """(the dict of `calibration_stats`, what its two exports take for it: the struct of its pointers)"""
         out, c = self._calibration_outputs(F, D, p, E)
-        w0 = 0
-        for n in (calls or [m]):
-            # a launch reads its windows' [F, n, p, D] slice as one tensor
-            part = traj if n == m else traj.reshape(F, m, p, D)[:, w0:w0 + n].contiguous()
-            self._check(self.lib.cadm_calibration_stats(ptr(part), ptr(truth[w0:]), ld, ptr(mask[w0:]), n, F, p, E, D, w0, ptr(partials), blocks,
-                                                        ct.byref(c), int(w0 + n >= m), self.stream), "cadm_calibration_stats")
-            w0 += n
-        if w0 != m:
-            raise ValueError("calibration_stats: calls %r do not add up to %d windows" % (calls, m))
-        return out
+        return out, [ct.byref(c)]
 
     def eval_calibration(self, dev, N, F, chunk=4096, seed=0, call=0, eps=None):
         """`cadm_eval_calibration` on the device-resident windowed dataset `dev` (see `eval_horizon`: the same arguments, rollouts
         and noise keys) -> the dict of `calibration_stats`."""
-        if chunk <= 0 or chunk % 64:
-            raise ValueError("eval_calibration: chunk must be a positive multiple of 64, got %r" % (chunk,))
-        eps = None if eps is None else self._t(eps)
-        mc = min(int(chunk), (N + 63) // 64 * 64)
-        self.ensure_rollout(_lib.NOISE_NONE if self.deterministic else _lib.NOISE_INJECT if eps is not None else _lib.NOISE_PHILOX, min(mc, N), 1)
-        nbytes = self.lib.cadm_eval_calibration_workspace_bytes(self._ctx, int(N), int(F), int(chunk))
-        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
-        out, c = self._calibration_outputs(F, self.D, self.p, self.E)
-        g = lambda k: ptr(dev.get(k))
-        self._check(self.lib.cadm_eval_calibration(self._ctx, g("obs"), g("act"), g("obs_next"), g("cp_obs") if self.C > 0 else None,
-                                                   g("cp_act") if self.C > 0 else None, g("future_bool"), int(N), int(F), int(chunk), seed, call,
-                                                   ptr(eps), ptr(ws), ct.byref(c), self.stream), "cadm_eval_calibration")
-        return out
+        return self._eval_windows("eval_calibration", "cadm_eval_calibration_workspace_bytes", self._calibration_out, dev, N, F, chunk, seed,
+                                  call, eps)
 
     # ------------------------------------------------------------------ forecast of a plan (opt-in; csrc/forecast.hip)
     def _forecast_outputs(self, m, n, H, p, E, rollout_returns=False):
