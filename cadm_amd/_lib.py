@@ -158,6 +158,17 @@ class PolicyParams(C.Structure):       # include/cadm_hip.h cadm_policy_params (
                 ("n_samples", C.c_int32), ("noise_std", C.c_float)]
 
 
+HEAD_KINDS = {"gaussian": 1}                                               # CADM_HEAD_GAUSSIAN
+LOGSTD_BOUNDS = {"clamp": 0, "tanh": 1}                                    # CADM_LOGSTD_CLAMP / _TANH
+LOGSTD_MAX = 10.0                                                          # the largest log_std_max a head takes: expf stays finite with a margin
+STREAM_POLICY_SAMPLE = 8                                                   # csrc/common.h: the Philox stream word of the Gaussian head's draws
+IMAGINE_SAMPLED_VIEWS = 10                                                 # include/cadm_hip.h CADM_IMAGINE_SAMPLED_VIEWS: cadm_imagine's nine, then logp
+
+
+class PolicyHeadParams(C.Structure):   # include/cadm_hip.h cadm_policy_head_params
+    _fields_ = [("kind", C.c_int32), ("bound", C.c_int32), ("log_std_min", C.c_float), ("log_std_max", C.c_float)]
+
+
 MAX_CRITICS = 5                                                            # CADM_MAX_CRITICS
 CRITIC_REDUCES = {"min": 0, "mean": 1}                                     # CADM_CRITIC_MIN / _MEAN
 
@@ -281,6 +292,10 @@ SIGNATURES = {
     "cadm_imagine": (_i, [_P, _P, _P, _P, _i, _i, _i, C.c_float, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P]),
     "cadm_imagine_select": (_i, [_P, _P, _P, _P, _P, _i, _i, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P, _P,
                                  _P, _P, _P, _P, _P, _P, _P]),
+    "cadm_set_policy_head": (_i, [_P, C.POINTER(PolicyHeadParams), _P, _P, _P]),
+    "cadm_policy_sample": (_i, [_P, _P, _i, _u32, _i, _u32, _u32, _P, _P, _P, _P]),
+    "cadm_imagine_sampled_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, C.POINTER(C.c_uint64)]),
+    "cadm_imagine_sampled": (_i, [_P, _P, _P, _i, _i, _i, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P]),
     "cadm_imagine_targets_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, C.POINTER(C.c_uint64)]),
     "cadm_imagine_targets": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _i, C.POINTER(TargetParams), _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),

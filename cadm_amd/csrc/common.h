@@ -62,6 +62,7 @@ void cadm_set_error(const char* fmt, ...);
 #define CADM_STREAM_POLICY 5u // exploration noise of the policy prior's proposals (policy.hip)
 #define CADM_STREAM_IMAGINE 6u      // the particle draw of an imagined transition (imagine.hip)
 #define CADM_STREAM_IMAGINE_ACT 7u  // exploration noise of an imagined rollout's actions (imagine.hip, through policy.hip's step)
+#define CADM_STREAM_POLICY_SAMPLE 8u  // the draws of the stochastic actor head (policy_gauss.hip)
 
 // ---------------------------------------------------------------------------------------------
 // planner weight-stream geometry (see DESIGN.md "weight streams")
@@ -108,6 +109,7 @@ struct ValueNet;  // value.hip
 struct RewardNet;  // reward.hip
 struct PolicyNet;  // policy.hip
 struct CriticNets;  // critic.hip
+struct PolicyHead;  // policy_gauss.hip
 
 struct cadm_ctx {
     cadm_config cfg;
@@ -187,6 +189,9 @@ struct cadm_ctx {
     float* disc = nullptr;
     float* disc_buf = nullptr;
     std::vector<float> disc_host;
+    // the Gaussian head on the registered policy net (cadm_set_policy_head, policy_gauss.hip): a packed copy of its log-std layer the
+    // ctx owns; null before the first one; dropped with every cadm_set_policy_net
+    PolicyHead* policy_head = nullptr;
 };
 
 // Entry points launch on the ctx's device whatever device the caller's thread has current (two engines on different GPUs in
@@ -220,6 +225,7 @@ void cadm_train_free(cadm_ctx* ctx);
 void cadm_value_free(cadm_ctx* ctx);      // value.hip
 void cadm_reward_free(cadm_ctx* ctx);     // reward.hip
 void cadm_policy_free(cadm_ctx* ctx);     // policy.hip
+void cadm_policy_head_free(cadm_ctx* ctx);      // policy_gauss.hip
 void cadm_critic_free(cadm_ctx* ctx);     // critic.hip
 void cadm_discount_free(cadm_ctx* ctx);   // discount.hip
 // (developer library: dev/dev_api.hip) Adam moment buffers of one trained tensor; layer as in cadm_set_weights, is_bias 0 / 1;

@@ -219,11 +219,13 @@ struct ImagineWs {
     int32_t* length;
     uint8_t* alive;
     float *rows1, *cur, *next;
-    size_t off[CADM_IMAGINE_VIEWS];
+    float* logp;               // [k, rows] on the sampled route, else null
+    size_t off[CADM_IMAGINE_SAMPLED_VIEWS];
 };
 
-// outputs first, in the order of include/cadm_hip.h, then the chain's own views: ONE layout for the size, the offsets and the launches
-size_t imagine_carve(const cadm_ctx* ctx, int m, int n, int k, char* base, ImagineWs* w) {
+// outputs first, in the order of include/cadm_hip.h, then the chain's own views: ONE layout for the size, the offsets and the launches.
+// sampled (cadm_imagine_sampled): logp follows cadm_imagine's nine outputs, in front of the chain's views
+size_t imagine_carve(const cadm_ctx* ctx, int m, int n, int k, bool sampled, char* base, ImagineWs* w) {
     Carver c{base};
     ImagineWs t{};
     const size_t rows = (size_t)m * n;
@@ -237,6 +239,7 @@ size_t imagine_carve(const cadm_ctx* ctx, int m, int n, int k, char* base, Imagi
     *o++ = c.off; t.disag = c.take<float>((size_t)k * rows);
     *o++ = c.off; t.length = c.take<int32_t>(rows);
     *o++ = c.off; t.alive = c.take<uint8_t>(rows);
+    if (sampled) { *o++ = c.off; t.logp = c.take<float>((size_t)k * rows); }
     t.rows1 = c.take<float>(rows * ctx->p);
     t.cur = c.take<float>(rows * ctx->p * ctx->D);
     t.next = c.take<float>(rows * ctx->p * ctx->D);
@@ -288,12 +291,13 @@ int cadm_imagine_check(const cadm_ctx* ctx, int m, int n, int k, const cadm_cons
 
 // the chain: per step the action (the registered actor on states[t], or the given one), a one-step rollout under the even iteration word
 // CADM_IMAGINE_IT + 2 t (the context layout of iteration 0; the head noise is drawn at the rollout's own t = 0, so the word is what
-// tells the steps apart), and the select stage.  Nothing is evaluated behind the last step's record.
+// tells the steps apart), and the select stage.  Nothing is evaluated behind the last step's record.  sampled: the action launch is the
+// Gaussian head's step (policy_gauss.hip) in the place of policy.hip's, and logp[t] its second output; every other launch is the same.
 int cadm_launch_imagine(cadm_ctx* ctx, const float* obs, const float* ctx_vec, const float* actions, int m, int n, int k, float noise_std,
                         const cadm_constraint_params* cons, const cadm_uncertainty_params* dis, uint32_t seed, uint32_t call, void* buffer,
-                        hipStream_t s, const char* who) {
+                        hipStream_t s, const char* who, bool sampled) {
     ImagineWs w;
-    imagine_carve(ctx, m, n, k, (char*)buffer, &w);
+    imagine_carve(ctx, m, n, k, sampled, (char*)buffer, &w);
     ImagineArgs a{};
     int rc;
     if ((rc = imagine_fill(ctx, cons, dis, who, &a))) return rc;
@@ -313,7 +317,9 @@ int cadm_launch_imagine(cadm_ctx* ctx, const float* obs, const float* ctx_vec, c
     for (int t = 0; t < k; ++t) {
         float* act_t = w.act + (size_t)t * rows * A;
         const float* st = w.states + (size_t)t * rows * D;
-        if (!actions && (rc = cadm_launch_policy_step(ctx, st, rows, t, noise_std, seed, call, CADM_STREAM_IMAGINE_ACT, act_t, s, who))) return rc;
+        if (sampled) rc = cadm_launch_policy_gauss_step(ctx, st, rows, t, seed, call, act_t, w.logp + (size_t)t * rows, s, who);
+        else rc = actions ? CADM_OK : cadm_launch_policy_step(ctx, st, rows, t, noise_std, seed, call, CADM_STREAM_IMAGINE_ACT, act_t, s, who);
+        if (rc) return rc;
         if ((rc = cadm_launch_rollout(ctx, obs, t ? w.cur : nullptr, ctx_vec, act_t, nullptr, 1, seed, call, CADM_IMAGINE_IT + 2 * t, 0, n, m, n,
                                       w.rows1, w.next, s, 0, -1, /*horizon=*/1))) return rc;
         a.t = t; a.state = st; a.state_out = w.states + (size_t)(t + 1) * rows * D;
@@ -328,10 +334,34 @@ int cadm_launch_imagine(cadm_ctx* ctx, const float* obs, const float* ctx_vec, c
 extern "C" size_t cadm_imagine_workspace_bytes(cadm_ctx* ctx, int m, int n, int k, uint64_t* offsets_out) {
     if (!ctx || m <= 0 || n <= 0 || k <= 0) return 0;
     ImagineWs w;
-    const size_t bytes = imagine_carve(ctx, m, n, k, nullptr, &w);
+    const size_t bytes = imagine_carve(ctx, m, n, k, false, nullptr, &w);
     if (offsets_out)
         for (int i = 0; i < CADM_IMAGINE_VIEWS; ++i) offsets_out[i] = (uint64_t)w.off[i];
     return bytes;
+}
+
+extern "C" size_t cadm_imagine_sampled_workspace_bytes(cadm_ctx* ctx, int m, int n, int k, uint64_t* offsets_out) {
+    if (!ctx || m <= 0 || n <= 0 || k <= 0) return 0;
+    ImagineWs w;
+    const size_t bytes = imagine_carve(ctx, m, n, k, true, nullptr, &w);
+    if (offsets_out)
+        for (int i = 0; i < CADM_IMAGINE_SAMPLED_VIEWS; ++i) offsets_out[i] = (uint64_t)w.off[i];
+    return bytes;
+}
+
+extern "C" int cadm_imagine_sampled(cadm_ctx* ctx, const float* obs, const float* ctx_vec, int m, int n, int k,
+                                    const cadm_constraint_params* constraints, const cadm_uncertainty_params* disagreement, uint32_t seed,
+                                    uint32_t call, void* buffer, void* stream) {
+    const char* who = "cadm_imagine_sampled";
+    CADM_REQUIRE(ctx && obs && buffer, "%s: ctx / obs / buffer is null", who);
+    int rc;
+    if ((rc = cadm_imagine_check(ctx, m, n, k, constraints, disagreement, who))) return rc;
+    CADM_REQUIRE(ctx->C == 0 || ctx_vec, "%s: ctx_vec required for a context model", who);
+    if ((rc = cadm_policy_gauss_check(ctx, who))) return rc;
+    if ((rc = cadm_require_ready(ctx, who))) return rc;
+    CADM_ON_DEVICE(ctx);
+    return cadm_launch_imagine(ctx, obs, ctx_vec, nullptr, m, n, k, 0.0f, constraints, disagreement, seed, call, buffer, (hipStream_t)stream, who,
+                               true);
 }
 
 extern "C" int cadm_imagine(cadm_ctx* ctx, const float* obs, const float* ctx_vec, const float* actions, int m, int n, int k, float noise_std,

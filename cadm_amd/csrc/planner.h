@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, critic.hip, discount.hip, imagine.hip, imagine_targets.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, policy_gauss.hip, critic.hip, discount.hip, imagine.hip, imagine_targets.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -137,6 +137,17 @@ int cadm_launch_policy_step(cadm_ctx* ctx, const float* x, size_t total, int t, 
 // kernel's arguments (mlp_chain.h) and `squash` (or null) its squash
 struct MlpDev;
 bool cadm_policy_dev(const cadm_ctx* ctx, MlpDev* d, int* squash);
+// policy.hip, for policy_gauss.hip: the refusals of a policy net's description alone (cadm_policy_plan_check's first half)
+int cadm_policy_check(const cadm_ctx* ctx, const cadm_policy_params* policy, const char* who);
+// policy_gauss.hip: the stochastic actor head on the registered net (include/cadm_hip.h, "Stochastic actor head").  For policy.hip:
+// cadm_set_policy_net drops the head (the last hidden width may have changed); the packed copy stays allocated.  For imagine.hip: the
+// refusals of a sampled step before any HIP call (no registered net, or no head on it: CADM_ESTATE; what cadm_policy_check refuses, lb >=
+// ub, the kernel's LDS), and ONE sampling step on states x [total, D], one state per row, under counter (row, t, g,
+// CADM_STREAM_POLICY_SAMPLE): a1 [total, A] the sampled action, logp [total] its log-density
+void cadm_policy_head_drop(cadm_ctx* ctx);
+int cadm_policy_gauss_check(const cadm_ctx* ctx, const char* who);
+int cadm_launch_policy_gauss_step(cadm_ctx* ctx, const float* x, size_t total, int t, uint32_t seed, uint32_t call, float* a1, float* logp,
+                                  hipStream_t s, const char* who);
 // critic.hip: the refusals of a terminal Q (null parameters, a layer count outside 0 .. 4, a width outside 1 .. 512, an unknown
 // activation or reduce, a critic count outside 1 .. 5, a weight that is not finite, D or A beyond the nets' dims, a discrete / sharded
 // ctx, the input tile and the activation tiles beyond the LDS; no registered critics or no registered policy net: CADM_ESTATE;
@@ -158,9 +169,10 @@ int cadm_launch_discount(cadm_ctx* ctx, const float* traj, const float* obs, con
 // before any HIP call; and the chain itself over the buffer of cadm_imagine_workspace_bytes(ctx, m, n, k)
 int cadm_imagine_check(const cadm_ctx* ctx, int m, int n, int k, const cadm_constraint_params* constraints,
                        const cadm_uncertainty_params* disagreement, const char* who);
+// sampled: the buffer is cadm_imagine_sampled_workspace_bytes', and every step's action is the Gaussian head's draw with its logp
 int cadm_launch_imagine(cadm_ctx* ctx, const float* obs, const float* ctx_vec, const float* actions, int m, int n, int k, float noise_std,
                         const cadm_constraint_params* constraints, const cadm_uncertainty_params* disagreement, uint32_t seed, uint32_t call,
-                        void* buffer, hipStream_t s, const char* who);
+                        void* buffer, hipStream_t s, const char* who, bool sampled = false);
 // what the reference-path loops (plan.hip) answer on a discounted ctx: they sum the step rewards inside the rollout kernel
 inline int cadm_refuse_discounted(const cadm_ctx* ctx, const char* who) {
     if (!ctx->disc) return CADM_OK;

@@ -244,12 +244,14 @@ extern "C" int cadm_set_policy_net(cadm_ctx* ctx, const cadm_policy_params* para
                                    const float* mean, const float* std_inv, void* stream) {
     const char* who = "cadm_set_policy_net";
     CADM_REQUIRE(ctx, "%s: ctx is null", who);
-    if (!params) { mlp_clear(ctx->policy); return CADM_OK; }
+    if (!params) { mlp_clear(ctx->policy); cadm_policy_head_drop(ctx); return CADM_OK; }
     int rc;
     if ((rc = cadm_policy_check(ctx, params, who))) return rc;
     int dims[MLP_NL + 1];
     policy_dims(ctx, params, dims);
-    if ((rc = mlp_register(ctx, ctx->policy, 1, nullptr, dims, params->n_hidden + 1, W, b, mean, std_inv, stream, who))) return rc;
+    rc = mlp_register(ctx, ctx->policy, 1, nullptr, dims, params->n_hidden + 1, W, b, mean, std_inv, stream, who);
+    if (rc != CADM_EINVAL) cadm_policy_head_drop(ctx);      // (a refusal touched nothing; anything else touched the net the head hangs on)
+    if (rc) return rc;
     ctx->policy->prm = *params;
     return CADM_OK;
 }

@@ -85,6 +85,10 @@ Differences a caller can see (all opt-in except the first):
     that net); `set_critics(nets, in_mean=None, in_std=None)` hands over the C critics (each as `set_terminal_value` takes a net, with
     D + A inputs) and `set_policy(...)` the actor, at run time and with nothing rebuilt; `clear_critics()`, `q_value(states,
     actions=None)`, `plan_terminal_q(obs, actions, ...)`.  Not together with `cem_terminal_value`.  It alone takes the opt-in route;
+  * `policy_head=dict(kind="gaussian", log_std_bounds=(-5.0, 2.0), log_std_bound="clamp" | "tanh")`: the model's one actor
+    (whichever option declares it) is a SAC actor (INTEGRATION.md "Stochastic actor head") -- `set_policy` then takes a net whose last
+    layer has 2 A outputs, the mean and the log standard deviation; the planner and `policy_action` keep the mode action, bit for bit;
+    `imagine(...)` draws its actions from the policy and returns their `logp`, `policy_sample(states)` draws for given states;
   * `cem_discount=gamma` in (0, 1]: a discount over the horizon in that loop (INTEGRATION.md "Discount over the horizon") -- every
     quantity that enters a candidate's score is weighted by gamma^t at step t: the env's own step rewards, the constraint penalty, the
     tracking, uncertainty and rate costs and the learned reward, and a terminal value or Q by gamma^H on top of its `weight` (which
@@ -324,6 +328,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_terminal_q=None,
                  cem_discount=1.0,
                  imagine_policy=None,
+                 policy_head=None,
                  engine_lib=None,
                  ):
         self.env = env
@@ -407,6 +412,15 @@ class MLPEnsembleCEMDynamicsModel(object):
         # get_action of such a model stays on the route its cem_* kwargs select
         self._imagine_policy = _planner.imagine_policy_params(imagine_policy, self._opt, obs_dim=obs_space_dims,
                                                               action_dim=self.action_space_dims, discrete=self.discrete)
+        # the Gaussian head of that one actor (planner.policy_head_params): None, and every path is as it is without the kwarg
+        world = 1
+        if process_group is not None and policy_head is not None:
+            import torch.distributed as dist
+            world = dist.get_world_size(process_group)
+        self._policy_head = _planner.policy_head_params(policy_head, has_actor=self._actor_params() is not None, discrete=self.discrete,
+                                                        world=world)
+        self._head_set = False                                # whether the engine holds the head's log-std layer: `set_policy`
+        self._sample_call = 0           # policy_sample's own noise counter, as imagine's
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
         self._plan_phase = None                               # device tensor [m] int32: the knot grid's phase (cem_knot_anchor="episode")
         self._targets = self._target_offset = None            # device tensors [m,T,K] float32 / [m] int32 (cem_tracking): `set_targets`
@@ -881,18 +895,45 @@ class MLPEnsembleCEMDynamicsModel(object):
         declared layer sizes and activation, else it is refused; obs_mean / obs_std [D] (None: 0 / 1): the net reads (obs - obs_mean) /
         obs_std of the raw observation.  Everything is copied; replacing the net rebuilds nothing."""
         _require_policy(self, "set_policy")      # (the actor of cem_terminal_q or imagine_policy alone: registered with n_samples = 1)
-        _register_net(self, "policy", self._actor_params(), weights, obs_mean, obs_std)
+        head = getattr(self, "_policy_head", None)
+        if head is None:
+            _register_net(self, "policy", self._actor_params(), weights, obs_mean, obs_std)
+            return
+        # a SAC actor: the mean columns are the mode actor every existing path reads, the log-std columns hang on it as the head
+        prm = self._actor_params()
+        layers, act = HipEngine.value_weights(weights)
+        if act is not None and _planner._lib.VALUE_ACTS[act] != prm.activation:
+            raise ValueError("set_policy: the module's activation %r is not the declared one" % (act,))
+        mean_layers, W_ls, b_ls = _planner.split_gaussian_layers(layers, self.action_space_dims)
+        self._head_set = False
+        _register_net(self, "policy", prm, mean_layers, obs_mean, obs_std)
+        self.engine.set_policy_head(head, W_ls, b_ls)
+        self._head_set = True
 
     def clear_policy(self):
         """Remove the policy net: get_action on a model with `cem_policy_prior` then raises until `set_policy` is called."""
         _require_policy(self, "clear_policy")
-        _register_net(self, "policy", None)
+        _register_net(self, "policy", None)      # (the library drops the head with the net)
+        self._head_set = False
 
     def policy_action(self, states):
         """The policy's action of raw observations `states` [..., D] (numpy or tensor) through the planner's kernel -> numpy [..., A]:
         squashed and clipped to the action bounds, no noise; clip(0, lb, ub) for a state with a non-finite value."""
         _require_policy(self, "policy_action", need_net=True)
         return self.engine.policy_eval(states).cpu().numpy()
+
+    def policy_sample(self, states, seed=None, numpy=True):
+        """Actions drawn from the stochastic actor (`policy_head`) for raw observations `states` [..., D] -> dict(act [..., A], logp
+        [...], mode [..., A]): a ~ pi(. | s) squashed and clipped as the actor is, its log-density (the unclipped Gaussian's for
+        squash="none"), and `policy_action`'s action.  A state with a non-finite value: act = mode = clip(0, lb, ub), logp = NaN.  The
+        draws are keyed (seed, a counter of policy_sample's own): get_action's and imagine's draws never move."""
+        _require_policy(self, "policy_sample", need_net=True)
+        if getattr(self, "_policy_head", None) is None or not getattr(self, "_head_set", False):
+            raise ValueError("policy_sample: this model has no registered Gaussian head (declare policy_head, then set_policy)")
+        call = self._sample_call & 0xFFFFFFFF
+        self._sample_call += 1
+        out = self.engine.policy_sample(states, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF, call=call)
+        return {k: v.cpu().numpy() for k, v in out.items()} if numpy else out
 
     def policy_proposals(self, obs, cp_obs=None, cp_act=None, seed=None, return_states=False):
         """The sequences the policy prior would inject for `obs` [m,D] (with a context model its history cp_obs / cp_act) -> numpy
@@ -912,7 +953,7 @@ class MLPEnsembleCEMDynamicsModel(object):
 
     # ------------------------------------------------------------------ imagined rollouts (INTEGRATION.md "Imagined rollouts for a learner")
     def imagine(self, obs, cp_obs=None, cp_act=None, horizon=1, branches=1, actions=None, noise_std=0.0, disagreement_w=None, seed=None,
-                numpy=False):
+                numpy=False, sample=None):
         """Model-generated experience for a learner (MBPO / Dyna): `branches` independent rollouts of `horizon` steps from each start state
         obs [m,D] (with a context model each state's own history cp_obs / cp_act, as `policy_proposals` takes them), as transitions.
         Actions: the registered actor (`set_policy`) on every row's own state, perturbed by noise_std * xi and clipped on EVERY row; or
@@ -932,13 +973,17 @@ class MLPEnsembleCEMDynamicsModel(object):
         `cem_constraints` (either mode) define termination; `cem_reward_net` with a registered net adds weight * R(s, a, s') to rew, and the
         dict then also holds rew_env and rew_net (0 where not valid).  The other planner options -- knots, tracking, the actuator model,
         uncertainty pricing, the discount, the terminal value or Q -- change nothing here.  A deterministic model draws no head noise and
-        still draws the kept particle.  The noise is keyed (seed, a counter of imagine's own): get_action's draws never move."""
+        still draws the kept particle.  The noise is keyed (seed, a counter of imagine's own): get_action's draws never move.
+        sample (models with `policy_head`): None -- True exactly when a head is declared and `actions` is None; True: every action is
+        drawn from the actor's Gaussian head on the row's own state, and the dict also holds logp [k,m,n], the log-density of act[t] at
+        states[t] (computed on every row, meaningful where valid); False: the mode action plus noise_std, as without a head."""
         import torch.distributed as dist
         world = dist.get_world_size(self._group) if self._group is not None else 1
         a = _planner.imagine_args(obs, cp_obs, cp_act, horizon, branches, actions, noise_std, disagreement_w, obs_dim=self.obs_space_dims,
                                   action_dim=self.action_space_dims, n_particles=self.n_particles, context=self.context_out_dim > 0,
                                   history_length=self.history_length, discrete=self.discrete, world=world,
-                                  policy_registered=self._policy_set)
+                                  policy_registered=self._policy_set, sample=sample,
+                                  head_declared=getattr(self, "_policy_head", None) is not None, head_registered=getattr(self, "_head_set", False))
         self._push_stats()
         eng, opt = self.engine, getattr(self, "_opt", None)
         w = a.w
@@ -949,7 +994,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         call = self._imagine_call & 0xFFFFFFFF
         self._imagine_call += 1
         out = eng.imagine(eng._t(obs).contiguous(), ctx_vec, a.k, a.n, actions, a.noise_std,
-                          None if opt is None else opt.constraint_params, w, int(self.seed if seed is None else seed) & 0xFFFFFFFF, call)
+                          None if opt is None else opt.constraint_params, w, int(self.seed if seed is None else seed) & 0xFFFFFFFF, call,
+                          sample=a.sample)
         out.pop("alive")
         out["obs"], out["next_obs"] = out["states"][:-1], out["states"][1:]
         out["n_valid"] = out["valid"].sum()

@@ -1508,6 +1508,41 @@ class HipEngine:
         self._check(self.lib.cadm_policy_eval(self._ctx, ptr(flat), int(flat.shape[0]), ptr(a), self.stream), "cadm_policy_eval")
         return a.reshape(tuple(states.shape[:-1]) + (self.A,))
 
+    def set_policy_head(self, params, W_ls=None, b_ls=None):
+        """`cadm_set_policy_head`: the Gaussian head of the registered policy net -- `params` a `_lib.PolicyHeadParams`
+        (`planner.policy_head_params`), W_ls [h_L, A] (a linear policy: [D, A]) and b_ls [A] the log-std layer on the net's last hidden
+        layer, numpy or torch, finite.  The library packs a copy of its own; `set_policy_net` drops the head.  params None: cleared."""
+        if params is None:
+            self._check(self.lib.cadm_set_policy_head(self._ctx, None, None, None, self.stream), "cadm_set_policy_head")
+            self._policy_head_src = None
+            return
+        W = np.ascontiguousarray(self._host(W_ls), dtype=np.float32)
+        b = np.ascontiguousarray(self._host(b_ls), dtype=np.float32)
+        if W.ndim != 2 or W.shape[1] != self.A or b.shape != (self.A,):
+            raise ValueError("set_policy_head: W_ls %r and b_ls %r, expected [h_L, %d] and [%d]" % (W.shape, b.shape, self.A, self.A))
+        src = getattr(self, "_policy_src", None)
+        if src is not None and tuple(src[0][-1][0].shape)[0] != W.shape[0]:
+            raise ValueError("set_policy_head: W_ls has %d rows, the registered net's last layer reads %d" % (W.shape[0], src[0][-1][0].shape[0]))
+        if not (np.all(np.isfinite(W)) and np.all(np.isfinite(b))):
+            raise ValueError("set_policy_head: the log-std layer holds a weight or a bias that is not finite")
+        Wd, bd = self._t(W), self._t(b)
+        self._check(self.lib.cadm_set_policy_head(self._ctx, ct.byref(params), ptr(Wd), ptr(bd), self.stream), "cadm_set_policy_head")
+        self._policy_head_src = (Wd, bd)      # (the copy is enqueued, not done)
+
+    def policy_sample(self, states, row0=0, t=0, seed=0, call=0):
+        """`cadm_policy_sample`: states [..., D] -> dict(act [..., A], logp [...], mode [..., A]) (device tensors): an action drawn from
+        the registered net's Gaussian head, its log-density, and `policy_eval`'s action.  Flattened row r draws as row row0 + r of step
+        t under the Philox key (seed, call)."""
+        states, flat = HipEngine._flat_rows(self, "policy_sample", states, self.D)
+        R = int(flat.shape[0])
+        act = torch.empty((R, self.A), dtype=torch.float32, device=self.device)
+        mode = torch.empty((R, self.A), dtype=torch.float32, device=self.device)
+        logp = torch.empty((R,), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_policy_sample(self._ctx, ptr(flat), R, int(row0), int(t), seed, call, ptr(act), ptr(logp), ptr(mode),
+                                                self.stream), "cadm_policy_sample")
+        lead = tuple(states.shape[:-1])
+        return dict(act=act.reshape(lead + (self.A,)), logp=logp.reshape(lead), mode=mode.reshape(lead + (self.A,)))
+
     def policy_propose(self, params, obs, ctx_vec=None, seed=0, call=0, want_states=False):
         """`cadm_policy_propose`: obs [m,D], ctx_vec the context encoder's output (`context_forward`; None for a model without one) ->
         the P = params.n_samples proposal sequences per env [m,P,H,A]: the registered policy rolled through the model on the particle
@@ -1537,13 +1572,18 @@ class HipEngine:
             return w
         return HipEngine.uncertainty_params("epistemic", 1.0, w, "var", None, obs_dim=self.D)
 
-    def imagine(self, obs, ctx_vec=None, horizon=1, branches=1, actions=None, noise_std=0.0, constraints=None, w=None, seed=0, call=0):
+    def imagine(self, obs, ctx_vec=None, horizon=1, branches=1, actions=None, noise_std=0.0, constraints=None, w=None, seed=0, call=0,
+                sample=False):
         """`cadm_imagine`: n = branches rollouts of k = horizon one-step rollouts from each of obs [m,D] (ctx_vec: the context encoder's
         output for them, None without one), under actions [m,n,k,A] (raw, clipped) or, with None, the registered policy net perturbed by
         noise_std * xi on every row -> a dict of device tensors, views of ONE buffer the call allocates: states [k+1,m,n,D], act
         [k,m,n,A], rew [k,m,n], done / valid [k,m,n] uint8, member [k,m,n] int32, disagreement [k,m,n], length [m,n] int32, alive [m,n]
         uint8.  constraints: a `ConstraintParams` (a violated one ends the row) or None; w: None, [D] weights or an
-        `UncertaintyParams` of the disagreement.  (seed, call): the Philox key of the head noise, the particle draws and the action noise."""
+        `UncertaintyParams` of the disagreement.  (seed, call): the Philox key of the head noise, the particle draws and the action noise.
+        sample: `cadm_imagine_sampled` -- the actions are drawn from the registered net's Gaussian head (`set_policy_head`; no actions,
+        no noise_std), and the dict also holds logp [k,m,n], the log-density of act[t,row] at states[t,row]."""
+        if sample and (actions is not None or float(noise_std) != 0.0):
+            raise ValueError("imagine: sample=True takes neither actions nor a noise_std")
         obs = self._t(obs)
         if obs.dim() != 2 or obs.shape[1] != self.D or not obs.is_contiguous():
             raise ValueError("imagine: obs %r, expected contiguous [m, %d]" % (tuple(obs.shape), self.D))
@@ -1556,15 +1596,24 @@ class HipEngine:
         w = self._imagine_w(w)
         if m >= 1 and n >= 1:
             self.ensure_rollout(None, m, n)
-        off = (ct.c_uint64 * _lib.IMAGINE_VIEWS)()
-        need = self.lib.cadm_imagine_workspace_bytes(self._ctx, m, n, k, off)
-        buf = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=self.device)
-        self._check(self.lib.cadm_imagine(self._ctx, ptr(obs), ptr(ctx_vec), ptr(actions), m, n, k, float(noise_std),
-                                          None if constraints is None else ct.byref(constraints), None if w is None else ct.byref(w),
-                                          seed, call, ptr(buf), self.stream), "cadm_imagine")
+        cons, wref = None if constraints is None else ct.byref(constraints), None if w is None else ct.byref(w)
+        if sample:
+            off = (ct.c_uint64 * _lib.IMAGINE_SAMPLED_VIEWS)()
+            need = self.lib.cadm_imagine_sampled_workspace_bytes(self._ctx, m, n, k, off)
+            buf = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.cadm_imagine_sampled(self._ctx, ptr(obs), ptr(ctx_vec), m, n, k, cons, wref, seed, call, ptr(buf), self.stream),
+                        "cadm_imagine_sampled")
+        else:
+            off = (ct.c_uint64 * _lib.IMAGINE_VIEWS)()
+            need = self.lib.cadm_imagine_workspace_bytes(self._ctx, m, n, k, off)
+            buf = torch.empty((max(int(need), 1),), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.cadm_imagine(self._ctx, ptr(obs), ptr(ctx_vec), ptr(actions), m, n, k, float(noise_std), cons, wref,
+                                              seed, call, ptr(buf), self.stream), "cadm_imagine")
         views = (("states", torch.float32, (k + 1, m, n, self.D)), ("act", torch.float32, (k, m, n, self.A)), ("rew", torch.float32, (k, m, n)),
                  ("done", torch.uint8, (k, m, n)), ("valid", torch.uint8, (k, m, n)), ("member", torch.int32, (k, m, n)),
                  ("disagreement", torch.float32, (k, m, n)), ("length", torch.int32, (m, n)), ("alive", torch.uint8, (m, n)))
+        if sample:
+            views += (("logp", torch.float32, (k, m, n)),)
         out = {}
         for (name, dtype, shape), o in zip(views, off):
             nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()

@@ -345,16 +345,72 @@ def imagine_policy_params(imagine_policy, opt=None, obs_dim=None, action_dim=Non
     return HipEngine.policy_params(q["hidden_sizes"], q["activation"], q["squash"], 1, 0.0)
 
 
+def policy_head_params(policy_head, has_actor=False, discrete=False, world=1):
+    """What a model's `policy_head` kwarg means -> the `PolicyHeadParams` the actor's log-std layer is registered under (`set_policy`),
+    or None for None.  policy_head: dict(kind="gaussian", log_std_bounds=(lo, hi), log_std_bound="clamp" | "tanh") -- the model's one
+    actor (has_actor: `cem_policy_prior`, `cem_terminal_q`'s policy or `imagine_policy` declares it) is then a SAC actor whose last layer
+    has 2 A outputs, the mean and the log standard deviation; log_std_bound says how the raw log-std reaches (lo, hi): clamped, or lo +
+    0.5 (hi - lo) (tanh(l) + 1).  ValueError for a model without an actor, unknown keys, an unknown kind or bound, bounds that are not
+    finite, lo >= hi, hi > 10 (exp must stay finite with a margin); NotImplementedError for discrete actions and for more than one rank,
+    as `imagine_policy`.  Touches no planner option.  Needs no GPU."""
+    if policy_head is None:
+        return None
+    if not isinstance(policy_head, dict) or set(policy_head) - {"kind", "log_std_bounds", "log_std_bound"}:
+        raise ValueError("policy_head must be dict(kind=, log_std_bounds=, log_std_bound=), got %r" % (policy_head,))
+    if discrete:
+        raise NotImplementedError("policy_head declares a continuous stochastic actor: this env's action space is discrete")
+    if int(world) > 1:
+        raise NotImplementedError("policy_head is not supported on a process group of more than one rank")
+    if not has_actor:
+        raise ValueError("policy_head needs a declared actor (cem_policy_prior, cem_terminal_q's policy or imagine_policy): it is that net's head")
+    q = dict(kind="gaussian", log_std_bounds=(-5.0, 2.0), log_std_bound="clamp")
+    q.update(policy_head)
+    if not isinstance(q["kind"], str) or q["kind"] not in _lib.HEAD_KINDS:
+        raise ValueError("policy_head kind must be %s, got %r" % (" or ".join(repr(k) for k in _lib.HEAD_KINDS), q["kind"]))
+    if not isinstance(q["log_std_bound"], str) or q["log_std_bound"] not in _lib.LOGSTD_BOUNDS:
+        raise ValueError("policy_head log_std_bound must be %s, got %r" % (" or ".join(repr(k) for k in _lib.LOGSTD_BOUNDS), q["log_std_bound"]))
+    try:
+        lo, hi = (float(np.float32(v)) for v in q["log_std_bounds"])
+    except (TypeError, ValueError):
+        raise ValueError("policy_head log_std_bounds must be two finite numbers (lo, hi), got %r" % (q["log_std_bounds"],)) from None
+    if any(isinstance(v, (bool, np.bool_)) for v in q["log_std_bounds"]) or not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError("policy_head log_std_bounds must be two finite numbers (lo, hi), got %r" % (q["log_std_bounds"],))
+    if not lo < hi:
+        raise ValueError("policy_head log_std_bounds need lo < hi, got %r" % (q["log_std_bounds"],))
+    if hi > _lib.LOGSTD_MAX:
+        raise ValueError("policy_head log_std_bounds: hi %r is beyond %g (exp must stay finite with a margin)" % (hi, _lib.LOGSTD_MAX))
+    prm = _lib.PolicyHeadParams()
+    prm.kind, prm.bound, prm.log_std_min, prm.log_std_max = _lib.HEAD_KINDS[q["kind"]], _lib.LOGSTD_BOUNDS[q["log_std_bound"]], lo, hi
+    return prm
+
+
+def split_gaussian_layers(layers, A):
+    """The layers [(W [in,out], b [out])] of a SAC actor whose last layer has 2 A outputs -> (the mode actor's layers: the mean columns
+    [0, A) of the last layer; W_ls, b_ls: its log-std columns [A, 2 A)) -- torch's chunk(2, -1), as contiguous float32 arrays."""
+    if not layers:
+        raise ValueError("set_policy: no layers given")
+    W, b = layers[-1]
+    if W.ndim != 2 or W.shape[1] != 2 * A or b.shape != (2 * A,):
+        raise ValueError("set_policy: with a policy_head the last layer has 2 A = %d outputs (mean, then log-std), got W %r and b %r"
+                         % (2 * A, tuple(W.shape), tuple(b.shape)))
+    mean = list(layers[:-1]) + [(np.ascontiguousarray(W[:, :A]), np.ascontiguousarray(b[:A]))]
+    return mean, np.ascontiguousarray(W[:, A:]), np.ascontiguousarray(b[A:])
+
+
 IMAGINE_IT = _lib.IMAGINE_IT      # the iteration word of imagine's first one-step rollout: csrc/planner.h CADM_IMAGINE_IT
 IMAGINE_MAX_STEPS = (POLICY_IT - IMAGINE_IT) // 2      # steps whose even words IMAGINE_IT + 2 t stay below the proposal roll's
-ImagineArgs = collections.namedtuple("ImagineArgs", "m n k noise_std w")
+ImagineArgs = collections.namedtuple("ImagineArgs", "m n k noise_std w sample", defaults=(False,))
 
 
-def imagine_args(obs, cp_obs=None, cp_act=None, horizon=1, branches=1, actions=None, noise_std=0.0, disagreement_w=None, *, obs_dim, action_dim,
-                 n_particles, context=False, history_length=0, discrete=False, world=1, policy_registered=False):
-    """The parsing and the refusals of `model.imagine`'s arguments, before anything is launched -> ImagineArgs(m, n, k, noise_std, w): m start
-    states, n branches, k steps, the noise as the float32 the library is handed, and w -- None (1 for every dim), "delta_std", or the
-    float32 [D] weights of the disagreement.  Arrays may be numpy or torch.  ValueError for horizon / branches < 1, neither a registered
+def imagine_args(obs, cp_obs=None, cp_act=None, horizon=1, branches=1, actions=None, noise_std=0.0, disagreement_w=None, sample=None, *, obs_dim,
+                 action_dim, n_particles, context=False, history_length=0, discrete=False, world=1, policy_registered=False, head_declared=False,
+                 head_registered=False):
+    """The parsing and the refusals of `model.imagine`'s arguments, before anything is launched -> ImagineArgs(m, n, k, noise_std, w, sample): m
+    start states, n branches, k steps, the noise as the float32 the library is handed, w -- None (1 for every dim), "delta_std", or the
+    float32 [D] weights of the disagreement --, and sample: whether the actions are drawn from the actor's Gaussian head (`policy_head`).
+    sample None means True exactly when a head is declared and actions is None; True with noise_std > 0, with actions or without a
+    registered head is a ValueError; False on a model with a head is the mode action plus noise_std.
+    Arrays may be numpy or torch.  ValueError for horizon / branches < 1, neither a registered
     policy nor actions or both, wrong shapes, non-finite obs, a missing history on a context model, m * n * p rows beyond one rollout
     launch, k beyond the iteration words; NotImplementedError for a discrete action space or more than one rank.  Needs no GPU."""
     D, A, p = int(obs_dim), int(action_dim), int(n_particles)
@@ -406,7 +462,17 @@ def imagine_args(obs, cp_obs=None, cp_act=None, horizon=1, branches=1, actions=N
         w = np.asarray(w, dtype=np.float32)
         if w.shape != (D,) or not bool(np.all(np.isfinite(w) & (w >= 0.0))) or not bool(np.any(w > 0.0)):
             raise ValueError("imagine: disagreement_w must be [%d] finite numbers >= 0 with at least one > 0" % D)
-    return ImagineArgs(m, n, k, std, w)
+    if sample is not None and not isinstance(sample, (bool, np.bool_)):
+        raise ValueError("imagine: sample must be None, True or False, got %r" % (sample,))
+    sample = bool(head_declared and actions is None) if sample is None else bool(sample)
+    if sample:
+        if actions is not None:
+            raise ValueError("imagine: sample=True draws the actions from the actor's head; open-loop actions are taken as given")
+        if not head_registered:
+            raise ValueError("imagine: sample=True needs a registered Gaussian head (declare policy_head, then set_policy)")
+        if std != 0.0:
+            raise ValueError("imagine: sample=True draws from the policy itself; noise_std perturbs the mode action (sample=False)")
+    return ImagineArgs(m, n, k, std, w, sample)
 
 
 TargetArgs = collections.namedtuple("TargetArgs", "m n k gamma lam penalty max_disagreement var_floor bootstrap")

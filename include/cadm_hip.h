@@ -1008,6 +1008,49 @@ int cadm_imagine_select(cadm_ctx* ctx, const float* next, const float* rows1, co
                         uint32_t call, uint8_t* alive_io, float* state_out, float* rew_out, uint8_t* done_out, uint8_t* valid_out,
                         int32_t* member_out, float* disagreement_out, int32_t* length_io, float* bcast_out, void* stream);
 
+/* Stochastic actor head (csrc/policy_gauss.hip; no reference twin): the registered policy net read as a SAC actor -- a diagonal Gaussian
+ * whose mean mu [A] is the net's own output layer (so cadm_policy_eval, cadm_policy_propose and the critics' actor are the MODE actor,
+ * unchanged) and whose log standard deviation l [A] is a second linear layer on the same last hidden tile: W_ls [h_L, A] (L = 0: [D, A]),
+ * b_ls [A], device pointers, a packed copy the ctx owns.  The head hangs on the registered net: cadm_set_policy_head without one is
+ * CADM_ESTATE; every cadm_set_policy_net (a new net or a clear) drops it; params NULL clears it; a second call replaces it.
+ * Per row q = row0 + r and action dim d, all float32, every operation rounded on its own, no fma outside the matrix pipe:
+ *   ls_d   CADM_LOGSTD_CLAMP: fminf(fmaxf(l_d, lo), hi)      CADM_LOGSTD_TANH: lo + (0.5f * (hi - lo)) * (tanhf(l_d) + 1.0f)
+ *   sig_d  = expf(ls_d)
+ *   xi_d   Philox4x32-10 keyed (seed, call), counter (q, t, d >> 2, 8), words to dims through Box-Muller exactly as cadm_policy_propose's
+ *          noise (words 0, 1 -> dims 4 g, 4 g + 1; words 2, 3 -> 4 g + 2, 4 g + 3)
+ *   u_d    = mu_d + sig_d * xi_d                              (one multiply, one add)
+ *   CADM_POLICY_TANH:  a_d = mid + half * tanhf(u_d);   J_d = logf(half) + 2 * ((LN2 - u_d) - softplus(-2 * u_d)),
+ *                      softplus(x) = fmaxf(x, 0) + log1pf(expf(-fabsf(x))),  LN2 = 0.6931472f      (no epsilon inside a log)
+ *   CADM_POLICY_NONE:  a_d = u_d;   J_d = 0      (logp is the UNCLIPPED Gaussian's density: the clip below is not part of it)
+ *   a_d    = fminf(fmaxf(a_d, lb), ub)
+ *   term_d = (((-0.5f * xi_d) * xi_d - ls_d) - 0.9189385f) - J_d
+ *   logp   = term_0 + term_1 + ..  in ascending d from term_0, one thread per row
+ *   mode_d = exactly cadm_policy_eval's action of the row (the squash of mu_d, the clip)
+ * A row with a non-finite value in its state: act = mode = clip(0, lb, ub) in every dim, logp = NaN.  half > 0 (lb < ub) is required.
+ * cadm_policy_sample: states [R,D] -> act_out [R,A], logp_out [R], mode_out [R,A] or NULL; row r draws as row row0 + r, so a batch cut
+ * into calls draws what one call draws.  cadm_imagine_sampled: cadm_imagine with actions NULL whose per-step action launch is this draw
+ * under counter (row, t, g, 8) on states[t] -- act[t] the sampled action, logp[t,row] its log-density at states[t,row], computed on every
+ * row (static shapes) and meaningful where valid; every other launch and output is cadm_imagine's.
+ * cadm_imagine_sampled_workspace_bytes: cadm_imagine's nine views first, in their order, then logp [k,m,n] float, then the chain's own.
+ * Determinism: every output is one thread's chain in the stated order, no floating-point atomics; nothing depends on the row tiles, the
+ * grid, R or the row's position for the same q: the same bits run to run.
+ * Refusals, before any HIP call: CADM_EINVAL for null pointers, an unknown kind or bound, log-std bounds that are not finite, lo >= hi,
+ * hi > 10 (expf stays finite with a margin), R < 1, t < 0, row0 + R beyond 2^32, what cadm_set_policy_net refuses of the registered net's
+ * description, lb >= ub, activation tiles beyond the 160 KiB of LDS at one row tile, and for cadm_imagine_sampled what cadm_imagine
+ * refuses; no registered net (call cadm_set_policy_net) or no head (call cadm_set_policy_head): CADM_ESTATE. */
+#define CADM_HEAD_GAUSSIAN 1
+#define CADM_LOGSTD_CLAMP 0
+#define CADM_LOGSTD_TANH 1
+typedef struct cadm_policy_head_params { int32_t kind, bound; float log_std_min, log_std_max; } cadm_policy_head_params;
+int cadm_set_policy_head(cadm_ctx* ctx, const cadm_policy_head_params* params /* NULL: clear */, const float* W_ls /* [h_L, A]; L = 0: [D, A] */,
+                         const float* b_ls /* [A] */, void* stream);
+int cadm_policy_sample(cadm_ctx* ctx, const float* states /* [R,D] */, int R, uint32_t row0, int t, uint32_t seed, uint32_t call,
+                       float* act_out /* [R,A] */, float* logp_out /* [R] */, float* mode_out /* [R,A] or NULL */, void* stream);
+#define CADM_IMAGINE_SAMPLED_VIEWS 10   /* cadm_imagine's nine, then logp [k,m,n] float */
+size_t cadm_imagine_sampled_workspace_bytes(cadm_ctx* ctx, int m, int n, int k, uint64_t* offsets_out);
+int cadm_imagine_sampled(cadm_ctx* ctx, const float* obs, const float* ctx_vec, int m, int n, int k, const cadm_constraint_params* constraints,
+                         const cadm_uncertainty_params* disagreement, uint32_t seed, uint32_t call, void* buffer, void* stream);
+
 /* Value-expansion targets (csrc/imagine_targets.hip; no reference twin): what a critic is trained on, out of cadm_imagine's transitions
  * and the caller's bootstrap values of their states, in ONE launch -- lambda-returns on every imagined state (Dreamer, TD-MPC), the n-step
  * targets of the start state (MVE), their inverse-variance combination over the branches (STEVE), the reward reduced by a multiple of the
