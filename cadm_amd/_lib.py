@@ -162,6 +162,7 @@ HEAD_KINDS = {"gaussian": 1}                                               # CAD
 LOGSTD_BOUNDS = {"clamp": 0, "tanh": 1}                                    # CADM_LOGSTD_CLAMP / _TANH
 LOGSTD_MAX = 10.0                                                          # the largest log_std_max a head takes: expf stays finite with a margin
 STREAM_POLICY_SAMPLE = 8                                                   # csrc/common.h: the Philox stream word of the Gaussian head's draws
+PROPOSALS = {"noise": 0, "head": 1}                                        # CADM_PROPOSE_NOISE / _HEAD: where the policy prior's proposals come from
 IMAGINE_SAMPLED_VIEWS = 10                                                 # include/cadm_hip.h CADM_IMAGINE_SAMPLED_VIEWS: cadm_imagine's nine, then logp
 
 
@@ -296,6 +297,7 @@ SIGNATURES = {
     "cadm_policy_sample": (_i, [_P, _P, _i, _u32, _i, _u32, _u32, _P, _P, _P, _P]),
     "cadm_imagine_sampled_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, C.POINTER(C.c_uint64)]),
     "cadm_imagine_sampled": (_i, [_P, _P, _P, _i, _i, _i, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P]),
+    "cadm_set_policy_proposals": (_i, [_P, C.c_int32, C.c_float]),
     "cadm_imagine_targets_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, C.POINTER(C.c_uint64)]),
     "cadm_imagine_targets": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _i, C.POINTER(TargetParams), _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),

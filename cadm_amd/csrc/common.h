@@ -192,6 +192,11 @@ struct cadm_ctx {
     // the Gaussian head on the registered policy net (cadm_set_policy_head, policy_gauss.hip): a packed copy of its log-std layer the
     // ctx owns; null before the first one; dropped with every cadm_set_policy_net
     PolicyHead* policy_head = nullptr;
+    // where the policy prior's proposals come from (cadm_set_policy_proposals, policy_gauss.hip): CADM_PROPOSE_NOISE, the mode action plus
+    // the call's noise_std, or CADM_PROPOSE_HEAD, draws of the head at propose_scale times its own standard deviation.  A planner
+    // option, not part of a net: it survives cadm_set_policy_net and cadm_set_policy_head
+    int propose_source = CADM_PROPOSE_NOISE;
+    float propose_scale = 1.0f;
 };
 
 // Entry points launch on the ctx's device whatever device the caller's thread has current (two engines on different GPUs in

@@ -148,6 +148,12 @@ void cadm_policy_head_drop(cadm_ctx* ctx);
 int cadm_policy_gauss_check(const cadm_ctx* ctx, const char* who);
 int cadm_launch_policy_gauss_step(cadm_ctx* ctx, const float* x, size_t total, int t, uint32_t seed, uint32_t call, float* a1, float* logp,
                                   hipStream_t s, const char* who);
+// policy_gauss.hip, for policy.hip: proposals drawn from the head (cadm_set_policy_proposals; include/cadm_hip.h).  The refusals a plan
+// check adds under CADM_PROPOSE_HEAD (a noise_std > 0, lb >= ub, the kernel's LDS; no head: CADM_ESTATE; CADM_OK under
+// CADM_PROPOSE_NOISE), and ONE policy step of the roll with the head's draws: the arguments of policy.hip's own step launch
+int cadm_policy_proposals_check(const cadm_ctx* ctx, const cadm_policy_params* policy, const char* who);
+int cadm_launch_policy_gauss_roll(cadm_ctx* ctx, const float* obs, const float* x, int P, int p, int t, uint32_t seed, uint32_t call, float* seqs,
+                                  float* a1, float* states, size_t total, hipStream_t s, const char* who);
 // critic.hip: the refusals of a terminal Q (null parameters, a layer count outside 0 .. 4, a width outside 1 .. 512, an unknown
 // activation or reduce, a critic count outside 1 .. 5, a weight that is not finite, D or A beyond the nets' dims, a discrete / sharded
 // ctx, the input tile and the activation tiles beyond the LDS; no registered critics or no registered policy net: CADM_ESTATE;

@@ -186,7 +186,8 @@ int cadm_policy_plan_check(const cadm_ctx* ctx, const cadm_policy_params* p, con
     CADM_REQUIRE(ctx->cfg.num_cem_iters <= CADM_POLICY_IT && CADM_POLICY_IT + 2 * (long long)ctx->H < CADM_FORECAST_IT,
                  "%s: num_cem_iters (%d) or the horizon (%d) reaches the iteration words %d .. of the proposal roll", who,
                  ctx->cfg.num_cem_iters, ctx->H, CADM_POLICY_IT);
-    return policy_match(ctx, p, who);
+    if ((rc = policy_match(ctx, p, who))) return rc;
+    return cadm_policy_proposals_check(ctx, p, who);      // (proposals drawn from the head: what that source asks on top)
 }
 
 // one policy step over `total` rows: obs [m, D] (t == 0) or x [total, p, D]; seqs [total, H, A] or null; a1 [total, A]; states or null
@@ -221,9 +222,12 @@ int cadm_launch_policy_propose(cadm_ctx* ctx, const cadm_policy_params* prm, con
     int rc;
     if (!ctx->packed && (rc = cadm_pack_streams(ctx, s))) return rc;
     float *cur = w.cur, *next = w.next;
+    const bool head = ctx->propose_source == CADM_PROPOSE_HEAD;      // (cadm_set_policy_proposals: every step is policy_gauss.hip's launch)
     for (int t = 0; t < H; ++t) {
-        if ((rc = policy_launch(ctx, t ? nullptr : obs, t ? cur : nullptr, P, ctx->p, t, prm->noise_std, seed, call, seqs_out, w.a1,
-                                states_out ? states_out + (size_t)t * srows : nullptr, total, s, who))) return rc;
+        float* st = states_out ? states_out + (size_t)t * srows : nullptr;
+        rc = head ? cadm_launch_policy_gauss_roll(ctx, t ? nullptr : obs, t ? cur : nullptr, P, ctx->p, t, seed, call, seqs_out, w.a1, st, total, s, who)
+                  : policy_launch(ctx, t ? nullptr : obs, t ? cur : nullptr, P, ctx->p, t, prm->noise_std, seed, call, seqs_out, w.a1, st, total, s, who);
+        if (rc) return rc;
         if (t + 1 < H) {
             if ((rc = cadm_launch_rollout(ctx, obs, t ? cur : nullptr, ctx_vec, w.a1, nullptr, 1, seed, call, CADM_POLICY_IT + 2 * t, 0, P, m, P,
                                           w.rows1, next, s, 0, -1, /*horizon=*/1))) return rc;

@@ -71,8 +71,9 @@ Differences a caller can see (all opt-in except the first):
     over the net at run time (a list of (W [in,out], b [out]) or a torch.nn.Sequential) with nothing rebuilt, `clear_reward_net()`
     removes it, `reward_net(obs, act, next_obs)` evaluates R through the planner's kernel, `plan_rewards(obs, actions, ...)`: the step
     rewards of given plans.  It alone takes the opt-in route;
-  * `cem_policy_prior=dict(hidden_sizes=(256, 256), activation="relu", squash="tanh" | "none", n_samples=24, noise_std=0.0)`: the
-    learner's actor as a prior in that loop (INTEGRATION.md "Policy prior") -- once per call the policy is rolled through the model
+  * `cem_policy_prior=dict(hidden_sizes=(256, 256), activation="relu", squash="tanh" | "none", n_samples=24, noise_std=0.0,
+    proposals="noise" | "head", std_scale=1.0)`: the learner's actor as a prior in that loop (INTEGRATION.md "Policy prior";
+    "Proposals drawn from the head" for the last two keys) -- once per call the policy is rolled through the model
     on `n_samples` sequences per env (sequence 0 without noise), and every iteration's candidates hold those sequences behind the kept
     elites and the mean candidate.  The kwarg declares the net's shape; `set_policy(weights, obs_mean=None, obs_std=None)` hands over
     an actor at run time (a list of (W [in,out], b [out]) or a torch.nn.Sequential) with nothing rebuilt, `clear_policy()` removes it,
@@ -87,7 +88,9 @@ Differences a caller can see (all opt-in except the first):
     actions=None)`, `plan_terminal_q(obs, actions, ...)`.  Not together with `cem_terminal_value`.  It alone takes the opt-in route;
   * `policy_head=dict(kind="gaussian", log_std_bounds=(-5.0, 2.0), log_std_bound="clamp" | "tanh")`: the model's one actor
     (whichever option declares it) is a SAC actor (INTEGRATION.md "Stochastic actor head") -- `set_policy` then takes a net whose last
-    layer has 2 A outputs, the mean and the log standard deviation; the planner and `policy_action` keep the mode action, bit for bit;
+    layer has 2 A outputs, the mean and the log standard deviation; the planner and `policy_action` keep the mode action, bit for bit
+    (with `cem_policy_prior`'s `proposals="head"` the prior's sequences 1 .. P - 1 are trajectories of the policy itself, drawn at
+    std_scale times the standard deviation the head predicts at every state, instead of the mode plus `noise_std`);
     `imagine(...)` draws its actions from the policy and returns their `logp`, `policy_sample(states)` draws for given states;
   * `cem_discount=gamma` in (0, 1]: a discount over the horizon in that loop (INTEGRATION.md "Discount over the horizon") -- every
     quantity that enters a candidate's score is weighted by gamma^t at step t: the env's own step rewards, the constraint penalty, the
@@ -419,6 +422,8 @@ class MLPEnsembleCEMDynamicsModel(object):
             world = dist.get_world_size(process_group)
         self._policy_head = _planner.policy_head_params(policy_head, has_actor=self._actor_params() is not None, discrete=self.discrete,
                                                         world=world)
+        # where the policy prior's proposals come from (planner.policy_proposals_setting): None without a prior; "head" needs the head
+        self._proposals = _planner.policy_proposals_setting(self._opt, head_declared=self._policy_head is not None)
         self._head_set = False                                # whether the engine holds the head's log-std layer: `set_policy`
         self._sample_call = 0           # policy_sample's own noise counter, as imagine's
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
@@ -452,6 +457,8 @@ class MLPEnsembleCEMDynamicsModel(object):
         self.engine.init_weights(np.random.default_rng(self.seed))
         if self._opt is not None and self._opt.discount != 1.0:
             self.engine.set_discount(self._opt.discount)      # state of the engine, set once: every stage and diagnostic reads it there
+        if self._proposals is not None:
+            self.engine.set_policy_proposals(*self._proposals)      # likewise: the roll of every plan and of `policy_proposals` reads it there
         self._train_ready = False
         self._stats_dirty = True
         self._dist_failed = False

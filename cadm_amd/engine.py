@@ -1529,6 +1529,27 @@ class HipEngine:
         self._check(self.lib.cadm_set_policy_head(self._ctx, ct.byref(params), ptr(Wd), ptr(bd), self.stream), "cadm_set_policy_head")
         self._policy_head_src = (Wd, bd)      # (the copy is enqueued, not done)
 
+    @staticmethod
+    def policy_proposals_args(source="noise", std_scale=1.0):
+        """What `set_policy_proposals` takes, checked -> (the CADM_PROPOSE_* number, std_scale as the float32 the library is handed):
+        source "noise" | "head"; std_scale a finite number >= 0, no bool.  Needs no GPU."""
+        if not isinstance(source, str) or source not in _lib.PROPOSALS:
+            raise ValueError("policy proposals must be %s, got %r" % (" or ".join(repr(k) for k in _lib.PROPOSALS), source))
+        if isinstance(std_scale, (bool, np.bool_)) or not isinstance(std_scale, (int, float, np.integer, np.floating)):
+            raise ValueError("policy std_scale must be a finite number >= 0, got %r" % (std_scale,))
+        scale = float(np.float32(std_scale))
+        if not math.isfinite(scale) or scale < 0.0:
+            raise ValueError("policy std_scale must be a finite number >= 0, got %r" % (std_scale,))
+        return _lib.PROPOSALS[source], scale
+
+    def set_policy_proposals(self, source="noise", std_scale=1.0):
+        """`cadm_set_policy_proposals`: where sequences 1 .. P - 1 of `policy_propose` (and of `guided_plan` / `critic_plan`) come from --
+        "noise": the mode action plus the call's noise_std (the default); "head": draws of the registered net's Gaussian head
+        (`set_policy_head`) at std_scale times the standard deviation it predicts at every state.  State of the engine, as the discount
+        is: it survives `set_policy_net` and `set_policy_head`."""
+        src, scale = HipEngine.policy_proposals_args(source, std_scale)
+        self._check(self.lib.cadm_set_policy_proposals(self._ctx, src, scale), "cadm_set_policy_proposals")
+
     def policy_sample(self, states, row0=0, t=0, seed=0, call=0):
         """`cadm_policy_sample`: states [..., D] -> dict(act [..., A], logp [...], mode [..., A]) (device tensors): an action drawn from
         the registered net's Gaussian head, its log-density, and `policy_eval`'s action.  Flattened row r draws as row row0 + r of step

@@ -32,9 +32,9 @@ FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/p
 
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
                                                        "params score_params constraints constraint_params knots knot_params actuator actuator_params "
-                                                       "action_advance discount critic critic_params policy policy_params reward reward_params value value_params uncertainty "
+                                                       "action_advance proposals std_scale discount critic critic_params policy policy_params reward reward_params value value_params uncertainty "
                                                        "uncertainty_params tracking track_params target_advance",
-                                                       defaults=(None, None, None, None, True, 1.0, None, None, None, None, None, None, None, None, None, None,
+                                                       defaults=(None, None, None, None, True, "noise", 1.0, 1.0, None, None, None, None, None, None, None, None, None, None,
                                                                  None, None, True))):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
@@ -54,7 +54,10 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
     `reward`: None, or (inputs name, the tuple of hidden widths, activation name, weight), with `reward_params` the `RewardParams` built
     from it (None: no learned reward); the net is registered at run time too (`set_reward_net`).
     `policy`: None, or (the tuple of hidden widths, activation name, squash name, n_samples, noise_std), with `policy_params` the
-    `PolicyParams` built from it (None: no policy prior); the net is registered at run time too (`set_policy`).
+    `PolicyParams` built from it (None: no policy prior); the net is registered at run time too (`set_policy`).  `proposals` / `std_scale`:
+    where the prior's sequences 1 .. P - 1 come from -- "noise", the mode action plus noise_std, or "head", draws of the actor's Gaussian
+    head at std_scale times its own standard deviation (a model hands both to its engine once, `HipEngine.set_policy_proposals`;
+    `policy_proposals_setting` is the check against the model's `policy_head`).
     `critic`: None, or (the tuple of hidden widths, activation name, n_critics, reduce name, weight, actor), with `critic_params` the
     `CriticParams` built from it (None: no terminal Q); actor = (the tuple of hidden widths, activation name, squash name) of the policy
     net the critics are evaluated at -- the policy prior's when one is declared (`actor_params` builds its `PolicyParams`); critics
@@ -90,9 +93,12 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
         weight=1.0) (`HipEngine.value_params`): the shape of the value net a model is given at run time.  cem_reward_net: None, or
         dict(inputs="next_obs" | "obs_act" | "obs_act_next_obs", hidden_sizes=(..), activation=, weight=1.0) (`HipEngine.reward_params`):
         the shape of the reward net a model is given at run time; obs_dim / action_dim: what its input dims are checked against.
-        cem_policy_prior: None, or dict(hidden_sizes=(..), activation=, squash="tanh" | "none", n_samples=24, noise_std=0.0)
-        (`HipEngine.policy_params`): the shape of the policy net a model is given at run time and how many proposals it makes (whether
-        they fit the smallest iteration's candidates is the model's check, once it knows its engine's elites: `policy_min_candidates`).
+        cem_policy_prior: None, or dict(hidden_sizes=(..), activation=, squash="tanh" | "none", n_samples=24, noise_std=0.0,
+        proposals="noise" | "head", std_scale=1.0) (`HipEngine.policy_params`, `HipEngine.policy_proposals_args`): the shape of the
+        policy net a model is given at run time, how many proposals it makes (whether they fit the smallest iteration's candidates is
+        the model's check, once it knows its engine's elites: `policy_min_candidates`) and where they come from: "head" draws them from
+        the actor's Gaussian head at std_scale times its standard deviation (no noise_std with it: one source; std_scale belongs to
+        "head" alone; whether the model declares a `policy_head` is the model's check: `policy_proposals_setting`).
         cem_terminal_q: None, or dict(hidden_sizes=(256, 256), activation="relu", n_critics=2, reduce="min" | "mean", weight=1.0,
         policy=dict(hidden_sizes=, activation=, squash=)) (`HipEngine.critic_params`): the shape of the Q critics and of the actor they
         are evaluated at; `policy` may be left out when cem_policy_prior is declared (the actor is then that net; given both, they must
@@ -141,17 +147,26 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
             value = (tuple(int(vparams.hidden[l]) for l in range(vparams.n_hidden)),
                      [k for k, x in _lib.VALUE_ACTS.items() if x == vparams.activation][0], float(vparams.weight))
         policy = pparams = None
+        proposals, std_scale = "noise", 1.0
         if cem_policy_prior is not None:
-            if not isinstance(cem_policy_prior, dict) or set(cem_policy_prior) - {"hidden_sizes", "activation", "squash", "n_samples", "noise_std"}:
-                raise ValueError("cem_policy_prior must be dict(hidden_sizes=, activation=, squash=, n_samples=, noise_std=), got %r"
-                                 % (cem_policy_prior,))
+            if not isinstance(cem_policy_prior, dict) or set(cem_policy_prior) - {"hidden_sizes", "activation", "squash", "n_samples", "noise_std",
+                                                                                  "proposals", "std_scale"}:
+                raise ValueError("cem_policy_prior must be dict(hidden_sizes=, activation=, squash=, n_samples=, noise_std=, proposals=, "
+                                 "std_scale=), got %r" % (cem_policy_prior,))
             if obs_dim is not None and not 1 <= int(obs_dim) <= _lib.MAX_VALUE_DIMS:
                 raise ValueError("a policy net reads up to %d observation dims, got %r" % (_lib.MAX_VALUE_DIMS, obs_dim))
             if action_dim is not None and not 1 <= int(action_dim) <= _lib.MAX_POLICY_ACTIONS:
                 raise ValueError("a policy net writes up to %d action dims, got %r" % (_lib.MAX_POLICY_ACTIONS, action_dim))
-            q = dict(hidden_sizes=(256, 256), activation="relu", squash="tanh", n_samples=24, noise_std=0.0)
+            q = dict(hidden_sizes=(256, 256), activation="relu", squash="tanh", n_samples=24, noise_std=0.0, proposals="noise", std_scale=1.0)
             q.update(cem_policy_prior)
             pparams = HipEngine.policy_params(q["hidden_sizes"], q["activation"], q["squash"], q["n_samples"], q["noise_std"])
+            proposals, std_scale = q["proposals"], HipEngine.policy_proposals_args(q["proposals"], q["std_scale"])[1]
+            if proposals == "head" and pparams.noise_std > 0.0:
+                raise ValueError("cem_policy_prior: proposals=\"head\" draws the proposals from the policy itself; noise_std=%r perturbs the "
+                                 "mode action (proposals=\"noise\"): one source of proposals" % (q["noise_std"],))
+            if proposals == "noise" and std_scale != 1.0:
+                raise ValueError("cem_policy_prior: std_scale=%r scales the head's standard deviation (proposals=\"head\"); the noise route's "
+                                 "scale is noise_std" % (q["std_scale"],))
             policy = (tuple(int(pparams.hidden[l]) for l in range(pparams.n_hidden)),
                       [k for k, x in _lib.VALUE_ACTS.items() if x == pparams.activation][0],
                       [k for k, x in _lib.POLICY_SQUASH.items() if x == pparams.squash][0], int(pparams.n_samples), float(pparams.noise_std))
@@ -305,7 +320,8 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                            knot_params=None if knots is None else HipEngine.knot_params(knots[0], knots[1]), tracking=tracking,
                            track_params=tparams, target_advance=bool(cem_target_advance), actuator=actuator, actuator_params=aparams,
                            action_advance=bool(cem_action_advance), uncertainty=uncertainty, uncertainty_params=uparams, value=value, value_params=vparams, reward=reward,
-                           reward_params=rparams, policy=policy, policy_params=pparams, critic=critic, critic_params=qparams, discount=discount, **mppi, **icem)
+                           reward_params=rparams, policy=policy, policy_params=pparams, critic=critic, critic_params=qparams, discount=discount, proposals=proposals,
+                           std_scale=std_scale, **mppi, **icem)
 
 
 def policy_slot(keep_elites, last, add_mean_last):
@@ -320,6 +336,18 @@ def policy_min_candidates(n, decay, num_elites, keep_elites, iters=5):
     + n_samples of a policy prior must fit."""
     d = float(np.float32(decay))
     return min(min(int(n), max(int(np.floor(float(n) / d ** it)), 2 * int(num_elites), int(keep_elites) + 1)) for it in range(int(iters)))
+
+
+def policy_proposals_setting(opt, head_declared=False):
+    """What a model hands `HipEngine.set_policy_proposals` once, at construction -> (source name, std_scale), or None for a model without
+    a policy prior (nothing is set: the engine's default is the noise route).  opt: the model's `PlanOptions` (or None); head_declared:
+    whether the model declares a `policy_head`.  proposals="head" without one is a ValueError: there is no head to draw from.  Needs no
+    GPU."""
+    if opt is None or opt.policy_params is None:
+        return None
+    if opt.proposals == "head" and not head_declared:
+        raise ValueError("cem_policy_prior: proposals=\"head\" draws the proposals from the actor's Gaussian head: declare policy_head")
+    return opt.proposals, float(opt.std_scale)
 
 
 def imagine_policy_params(imagine_policy, opt=None, obs_dim=None, action_dim=None, discrete=False):

@@ -1050,6 +1050,40 @@ int cadm_policy_sample(cadm_ctx* ctx, const float* states /* [R,D] */, int R, ui
 size_t cadm_imagine_sampled_workspace_bytes(cadm_ctx* ctx, int m, int n, int k, uint64_t* offsets_out);
 int cadm_imagine_sampled(cadm_ctx* ctx, const float* obs, const float* ctx_vec, int m, int n, int k, const cadm_constraint_params* constraints,
                          const cadm_uncertainty_params* disagreement, uint32_t seed, uint32_t call, void* buffer, void* stream);
+/* Proposals of the policy prior drawn from the head (csrc/policy_gauss.hip; no reference twin, OPT-IN): cadm_set_policy_proposals chooses
+ * where sequences 1 .. P - 1 of cadm_policy_propose (and so of cadm_guided_plan and cadm_critic_plan) come from.  CADM_PROPOSE_NOISE, the
+ * default: the mode action plus the call's noise_std behind the squash, as described at "Policy prior".  CADM_PROPOSE_HEAD: trajectories
+ * of pi itself (TD-MPC's policy trajectories, LOOP on SAC), the standard deviation the head predicts at every state times std_scale.
+ * Sequence 0 stays the mode trajectory.  The setting is state of the ctx, a planner option and not part of a net: no plan entry point
+ * gains an argument, the default is NOISE with scale 1, and it survives cadm_set_policy_net and cadm_set_policy_head.  Under HEAD every
+ * policy step of the roll is one launch of the kernel below; the one-step rollouts between the steps, their iteration words
+ * CADM_POLICY_IT + 2 t, the workspace and the injection into the candidates are the noise route's.
+ * A row is (env mi, sequence j), q = mi * P + j, at step t; all float32, every operation rounded on its own, no fma outside the matrix pipe:
+ *   state   exactly cadm_policy_propose's estimate: obs[mi] at t = 0; at t >= 1 the sequential particle sum in ascending order, then one
+ *           IEEE division by (float)p; the non-finite flag, the normalisation and the states_out copies are the same
+ *   mu_d, l_d   the hidden layers on the registered net's packed copy, then the two output layers on the last hidden tile, as
+ *           cadm_policy_sample reads them
+ *   ls_d    by the registered head's bound:  CADM_LOGSTD_CLAMP: fminf(fmaxf(l_d, lo), hi);  CADM_LOGSTD_TANH: lo + (0.5f * (hi - lo)) *
+ *           (tanhf(l_d) + 1.0f)
+ *   sig_d   = expf(ls_d);   s_d = std_scale * sig_d                      (one multiply)
+ *   xi_d    Philox4x32-10 keyed (seed, call), counter (q, t, d >> 2, 5): the counter, the stream word and the word-to-dim mapping of the
+ *           noise route.  A call has one source of proposals, so nothing is drawn twice; xi is bit for bit the noise route's
+ *   j == 0, or std_scale == 0:  no draw, u_d = mu_d;   else  u_d = mu_d + s_d * xi_d      (one multiply, one add)
+ *   CADM_POLICY_TANH: a_d = mid + half * tanhf(u_d);   CADM_POLICY_NONE: a_d = u_d;   always last: a_d = fminf(fmaxf(a_d, lb), ub)
+ *           (the noise sits BEFORE the squash, as in cadm_policy_sample, not behind it as on the noise route)
+ * A row with a non-finite value in any particle of its state takes clip(0, lb, ub) in every dim.  No log-density is computed: proposals
+ * are candidates, nothing reads their density.
+ * Determinism: the reduction contract of the two kernels it is made of -- one thread's chain per output in the stated order, no
+ * floating-point atomics, nothing depends on the row tiles, the grid, m, P or the row's position: the same bits run to run.  Sequence 0 has
+ * cadm_policy_eval's bits on its state estimate.
+ * Refusals, before any HIP call.  cadm_set_policy_proposals: CADM_EINVAL for a null ctx, an unknown source, a std_scale negative or not
+ * finite.  cadm_policy_propose, cadm_guided_plan (with a policy) and cadm_critic_plan (with a policy) under HEAD, behind their own
+ * refusals: CADM_EINVAL for a noise_std > 0 in the call's params (one source per call), lb >= ub, activation tiles beyond the 160 KiB of
+ * LDS at one row tile; no head on the registered net: CADM_ESTATE (every cadm_set_policy_net drops the head, so HEAD is refused from
+ * then until cadm_set_policy_head is called again). */
+#define CADM_PROPOSE_NOISE 0
+#define CADM_PROPOSE_HEAD 1
+int cadm_set_policy_proposals(cadm_ctx* ctx, int32_t source, float std_scale);
 
 /* Value-expansion targets (csrc/imagine_targets.hip; no reference twin): what a critic is trained on, out of cadm_imagine's transitions
  * and the caller's bootstrap values of their states, in ONE launch -- lambda-returns on every imagined state (Dreamer, TD-MPC), the n-step
