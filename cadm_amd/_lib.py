@@ -170,6 +170,15 @@ class PolicyHeadParams(C.Structure):   # include/cadm_hip.h cadm_policy_head_par
     _fields_ = [("kind", C.c_int32), ("bound", C.c_int32), ("log_std_min", C.c_float), ("log_std_max", C.c_float)]
 
 
+LOGP_SPACES = {"action": 0, "pre_squash": 1}                               # CADM_LOGP_ACTION / _PRE_SQUASH
+LOGP_YMAX = 0.999999                                                       # CADM_LOGP_YMAX: where |y| is clamped before atanh
+LOGSTD_MIN = -10.0                                                         # the smallest log_std_min the log-density takes: expf(-ls) stays finite with a margin
+
+
+class PolicyLogpParams(C.Structure):   # include/cadm_hip.h cadm_policy_logp_params
+    _fields_ = [("weight", C.c_float), ("space", C.c_int32)]
+
+
 MAX_CRITICS = 5                                                            # CADM_MAX_CRITICS
 CRITIC_REDUCES = {"min": 0, "mean": 1}                                     # CADM_CRITIC_MIN / _MEAN
 
@@ -206,6 +215,7 @@ _PLAN_NEST = (
     ("rewarded", [C.POINTER(RewardParams)]),
     ("guided", [C.POINTER(PolicyParams)]),
     ("critic", [C.POINTER(CriticParams)]),
+    ("anchored", [C.POINTER(PolicyLogpParams)]),
 )
 _PLAN_ARGS, _args = {}, _PLAN_TAIL      # level -> argtypes of cadm_<level>_plan: ctx, every level's own arguments from it inwards, the tail
 for _level, _front in _PLAN_NEST:
@@ -298,6 +308,11 @@ SIGNATURES = {
     "cadm_imagine_sampled_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, C.POINTER(C.c_uint64)]),
     "cadm_imagine_sampled": (_i, [_P, _P, _P, _i, _i, _i, C.POINTER(ConstraintParams), C.POINTER(UncertaintyParams), _u32, _u32, _P, _P]),
     "cadm_set_policy_proposals": (_i, [_P, C.c_int32, C.c_float]),
+    "cadm_policy_logp": (_i, [_P, _P, _P, _i, _i, _P, _P]),
+    "cadm_policy_logp_workspace_bytes": (C.c_size_t, [_P, _i, _i]),
+    "cadm_policy_logp_returns": (_i, [_P, C.POINTER(PolicyLogpParams), _P, _P, _P, _P, _i, _i, _P, _P, _P, _P, _P, _P]),
+    "cadm_anchored_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "cadm_anchored_plan": (_i, _PLAN_ARGS["anchored"]),
     "cadm_imagine_targets_workspace_bytes": (C.c_size_t, [_P, _i, _i, _i, _i, C.POINTER(C.c_uint64)]),
     "cadm_imagine_targets": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _i, C.POINTER(TargetParams), _P, _P]),
     "cadm_rs_plan": (_i, [_P, _P, _P, _P, _i, _i, _u32, _u32, _P, _P, _P, _P]),

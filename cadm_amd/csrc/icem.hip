@@ -18,7 +18,9 @@
 // cadm_guided_plan also rolls a caller-supplied policy net through the model once per call (policy.hip) and places its proposal
 // sequences among every iteration's candidates;
 // cadm_critic_plan also adds weight * reduce_c Q_c(s_H, pi(s_H)) of caller-supplied critics at the registered actor's action (critic.hip) to
-// the particle returns, in the place of the terminal value.
+// the particle returns, in the place of the terminal value;
+// cadm_anchored_plan also adds weight * sum_t log pi(a_t | s_t) of the registered actor's Gaussian head (policy_logp.hip) to the particle
+// returns, behind the learned reward.
 #include <math.h>
 
 #include "planner.h"
@@ -305,11 +307,12 @@ struct IcemWs {
     float *acost, *aplan;            // actuated only, behind traj: the candidates' rate cost [m, n]; the plan [m, H, A] before its last actuate pass
     float *ustep, *ucost;            // uncertainty term only, behind everything before: the step costs u [m, n, H]; the candidates' cost [m, n]
     float* rstep;                    // learned reward only, behind everything before: the step rewards [H, m, n, p]
-    float* pseqs; char* pws;         // policy prior only, behind everything else: the proposals [m, P, H, A]; the roll's workspace
+    float* pseqs; char* pws;         // policy prior only, behind everything before: the proposals [m, P, H, A]; the roll's workspace
+    float* lstep;                    // actor's log-density only, behind everything else: the step log-densities [H, m, n, p]
 };
 
 static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, char* base, IcemWs* w, int traj = 0, int first = 0, int act = 0,
-                         int unc = 0, int rew = 0, int pol = 0) {
+                         int unc = 0, int rew = 0, int pol = 0, int lgp = 0) {
     Carver c{base};
     const size_t HA = (size_t)ctx->H * ctx->A;
     IcemWs t{};
@@ -344,6 +347,7 @@ static size_t icem_carve(const cadm_ctx* ctx, int m, int n, int K, int mppi, cha
         t.pseqs = c.take<float>((size_t)m * pol * HA);
         t.pws = c.take<char>(cadm_policy_workspace_bytes(const_cast<cadm_ctx*>(ctx), m, pol));
     }
+    if (lgp) t.lstep = c.take<float>((size_t)ctx->H * m * n * ctx->p);
     if (w) *w = t;
     return c.off;
 }
@@ -355,9 +359,9 @@ static int icem_discounted(const cadm_ctx* ctx) { return ctx && ctx->disc != nul
 // every size export below: 0 for bad arguments (P, the proposals per env, at the levels that have them), else what icem_carve takes under
 // the export's mapping of its flags to the carver's
 static size_t icem_size(const cadm_ctx* ctx, int m, int n, int K, int mppi, int traj, int first = 0, int act = 0, int unc = 0, int rew = 0,
-                        int P = 0) {
+                        int P = 0, int lgp = 0) {
     if (!ctx || m <= 0 || n <= 0 || K < 0 || P < 0) return 0;
-    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, traj, first, act, unc, rew, P);
+    return icem_carve(ctx, m, n, K, mppi != 0, nullptr, nullptr, traj, first, act, unc, rew, P, lgp);
 }
 
 extern "C" size_t cadm_icem_workspace_bytes(cadm_ctx* ctx, int m, int n, int K) { return icem_size(ctx, m, n, K, 0, icem_discounted(ctx)); }
@@ -395,6 +399,12 @@ extern "C" size_t cadm_guided_workspace_bytes(cadm_ctx* ctx, int m, int n, int K
 // the guided loop's: a terminal Q reads the trajectory view and the first violations the other terms read, and takes no view of its own
 extern "C" size_t cadm_critic_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P) {
     return cadm_guided_workspace_bytes(ctx, m, n, K, mppi, terminate, actuator, uncertainty, P);
+}
+
+// the critic loop's, and behind everything the step log-densities [H, m, n, p] of the actor's log-density term (the views in front keep
+// their places: a loop without the term carves what cadm_critic_plan carves)
+extern "C" size_t cadm_anchored_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P) {
+    return icem_size(ctx, m, n, K, mppi, 1, terminate != 0, actuator != 0, uncertainty != 0, 1, P, 1);
 }
 
 // candidates of iteration `it`: max(floor(n / decay^it), 2 num_elites, K + 1), never more than the n the workspace holds
@@ -454,6 +464,11 @@ struct PlanTerms {
     // is added to the particle rows behind the constraints, the tracking terms and the learned reward, before the score.  `policy` may be
     // null with it: the critic needs the registered net, not the proposals.
     const cadm_critic_params* critic;
+    // the actor's log-density (policy_logp.hip) of the registered policy net and its Gaussian head; null = none, and today's launches.
+    // With it every rollout records its trajectories, TERMINATE constraints hand their first violations on, and weight * (the sum of
+    // log pi(a_t | s_t) over the counted steps) is added to the particle rows behind the learned reward and IN FRONT OF the terminal value /
+    // Q: a risk-aware score sees it per particle.  `policy` may be null with it, as for the critic.
+    const cadm_policy_logp_params* logp;
 };
 
 // score: what a candidate's particle returns become before the update sees them (score.hip); null = the particle mean
@@ -462,7 +477,7 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
                      float* best_return_out, void* stream, const PlanTerms& t) {
     // (the fields by name, in their order: the body below reads them as it read its parameters)
-    const auto& [constraints, knots, phase, terms, targets, T, offset, act, prev_io, prefix_io, advance, unc, value, reward, policy, critic] = t;
+    const auto& [constraints, knots, phase, terms, targets, T, offset, act, prev_io, prefix_io, advance, unc, value, reward, policy, critic, logp] = t;
     const char* who = upd.who;
     CADM_REQUIRE(ctx && prm && obs && init_mean && init_var && workspace && plan_out && m > 0 && n > 0, "%s: bad arguments", who);
     CADM_REQUIRE(!cadm_sharded(ctx), "%s: candidate-sharded planning is not supported (carried elites cannot be regenerated by id)", who);
@@ -493,6 +508,7 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         CADM_REQUIRE(!value, "%s: a terminal Q and a terminal value are both given: a plan has one terminal term", who);
         if ((rc = cadm_critic_plan_check(ctx, critic, who))) return rc;
     }
+    if (logp && (rc = cadm_policy_logp_plan_check(ctx, logp, who))) return rc;
     const bool disc = ctx->disc != nullptr;
     if (disc && (rc = cadm_discount_check(ctx, who))) return rc;
     const int P = policy ? policy->n_samples : 0;
@@ -507,12 +523,12 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
     CADM_ON_DEVICE(ctx);
     hipStream_t s = (hipStream_t)stream;
     IcemWs w;
-    // (w.traj: null without constraints, terms, an uncertainty term, a value, a reward, a critic and a discount; w.first: null unless terms, an
-    // uncertainty term, a value, a reward or a critic follow TERMINATE constraints)
-    const bool reads_traj = terms != nullptr || unc != nullptr || value != nullptr || reward != nullptr || critic != nullptr;
+    // (w.traj: null without constraints, terms, an uncertainty term, a value, a reward, a critic, a log-density and a discount; w.first: null
+    // unless terms, an uncertainty term, a value, a reward, a critic or a log-density follow TERMINATE constraints)
+    const bool reads_traj = terms != nullptr || unc != nullptr || value != nullptr || reward != nullptr || critic != nullptr || logp != nullptr;
     icem_carve(ctx, m, n, K, upd.mppi, (char*)workspace, &w, constraints != nullptr || reads_traj || disc,
                reads_traj && constraints != nullptr && constraints->mode == CADM_CONSTRAIN_TERMINATE, act != nullptr, unc != nullptr,
-               reward != nullptr, P);
+               reward != nullptr, P, logp != nullptr);
     const int HA = ctx->H * ctx->A;
     const bool track = prm->return_best != 0 || best_return_out != nullptr;
     if (ctx->C > 0 && (rc = cadm_context_forward(ctx, cp_obs, cp_act, m, 0, w.ctxv, stream))) return rc;
@@ -562,6 +578,8 @@ static int icem_loop(cadm_ctx* ctx, const PlanUpdate& upd, const cadm_score_para
         if (terms && (rc = cadm_tracking_returns(ctx, terms, w.traj, targets, T, offset, w.first, w.rows, m, ni, w.rows, nullptr, stream))) return rc;
         // what the env's own reward does not say: rows += weight * (the sum of R over the counted steps), of this iteration's ni packed candidates
         if (reward && (rc = cadm_launch_reward(ctx, reward, w.traj, obs, w.actions, w.first, m, ni, w.rows, w.rstep, s))) return rc;
+        // what the actor would do: rows += weight * (the sum of log pi(a_t | s_t) over the counted steps), of this iteration's ni packed candidates
+        if (logp && (rc = cadm_launch_policy_logp(ctx, logp, w.traj, obs, w.actions, w.first, m, ni, w.rows, w.lstep, s))) return rc;
         // what lies behind the horizon: rows += weight * V(last state), of this iteration's ni packed candidates
         if (value && (rc = cadm_launch_value(ctx, value, w.traj, w.first, m, ni, w.rows, s))) return rc;
         // or, from a learner without a V: rows += weight * reduce_c Q_c(last state, pi(last state)), one launch
@@ -617,9 +635,9 @@ extern "C" int cadm_mppi_plan(cadm_ctx* ctx, const cadm_mppi_params* prm, const 
                      workspace, plan_out, best_return_out, stream, PlanTerms{});
 }
 
-// The nest: ten exports, each the one before it with its own term's parameters in front; a level whose own struct is null enqueues the
+// The nest: eleven exports, each the one before it with its own term's parameters in front; a level whose own struct is null enqueues the
 // launches of the level below.  Each fills the leading fields of a PlanTerms -- its own parameters, in the struct's order -- and leaves the
-// rest "no term".  What all ten refuse first, in this order, the update they choose, and the loop:
+// rest "no term".  What all eleven refuse first, in this order, the update they choose, and the loop:
 static int nest_plan(const char* who, const PlanTerms& t, cadm_ctx* ctx, const cadm_score_params* score, int update, const cadm_mppi_params* prm,
                      const float* obs, const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
                      int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
@@ -746,7 +764,7 @@ extern "C" int cadm_guided_plan(cadm_ctx* ctx, const cadm_policy_params* policy,
                      carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out, stream);
 }
 
-// the outermost level today: adds weight * reduce_c Q_c(s_H, pi(s_H)) of every particle's last state (critic.hip, the critics of
+// adds weight * reduce_c Q_c(s_H, pi(s_H)) of every particle's last state (critic.hip, the critics of
 // cadm_set_critic_nets at the action of the net of cadm_set_policy_net) to the particle returns where the terminal value would be;
 // critic null: cadm_guided_plan's launches
 extern "C" int cadm_critic_plan(cadm_ctx* ctx, const cadm_critic_params* critic, const cadm_policy_params* policy,
@@ -759,5 +777,22 @@ extern "C" int cadm_critic_plan(cadm_ctx* ctx, const cadm_critic_params* critic,
                                 uint32_t seed, uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream) {
     return nest_plan("cadm_critic_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io, advance,
                      unc, value, reward, policy, critic}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io,
+                     carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out, stream);
+}
+
+// the outermost level today: adds weight * (the sum over the counted steps of log pi(a_t | s_t), policy_logp.hip, the net of
+// cadm_set_policy_net with the head of cadm_set_policy_head) to the particle returns, behind the learned reward and in front of the
+// terminal value / Q; logp null: cadm_critic_plan's launches
+extern "C" int cadm_anchored_plan(cadm_ctx* ctx, const cadm_policy_logp_params* logp, const cadm_critic_params* critic,
+                                  const cadm_policy_params* policy, const cadm_reward_params* reward, const cadm_value_params* value,
+                                  const cadm_uncertainty_params* unc, const cadm_actuator_params* act, float* prev_io, float* prefix_io,
+                                  int advance, const cadm_track_params* track, const float* targets, int T, const int32_t* offset,
+                                  const cadm_knot_params* knots, const int32_t* phase, const cadm_constraint_params* constraints,
+                                  const cadm_score_params* score, int update, const cadm_mppi_params* prm, const float* obs,
+                                  const float* cp_obs, const float* cp_act, const float* init_mean, const float* init_var, float* carry_io,
+                                  int32_t* carry_valid_io, int m, int n, uint32_t seed, uint32_t call, void* workspace, float* plan_out,
+                                  float* best_return_out, void* stream) {
+    return nest_plan("cadm_anchored_plan", PlanTerms{constraints, knots, phase, track, targets, T, offset, act, prev_io, prefix_io, advance,
+                     unc, value, reward, policy, critic, logp}, ctx, score, update, prm, obs, cp_obs, cp_act, init_mean, init_var, carry_io,
                      carry_valid_io, m, n, seed, call, workspace, plan_out, best_return_out, stream);
 }

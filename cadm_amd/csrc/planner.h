@@ -1,4 +1,4 @@
-// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, policy_gauss.hip, critic.hip, discount.hip, imagine.hip, imagine_targets.hip): the loops' types, ONE declaration
+// Internal header of the planner's host side (capi.hip, plan.hip, cem.hip, icem.hip, mppi.hip, score.hip, context.hip, horizon.hip, calibration.hip, forecast.hip, constrain.hip, knots.hip, tracking.hip, actuator.hip, uncertainty.hip, value.hip, reward.hip, policy.hip, policy_gauss.hip, policy_logp.hip, critic.hip, discount.hip, imagine.hip, imagine_targets.hip): the loops' types, ONE declaration
 // of every launcher another file calls, and the helpers the loops share.  Not part of a JIT rollout module (rollout_jit.hip sees common.h only).
 #pragma once
 #include "common.h"
@@ -154,6 +154,17 @@ int cadm_launch_policy_gauss_step(cadm_ctx* ctx, const float* x, size_t total, i
 int cadm_policy_proposals_check(const cadm_ctx* ctx, const cadm_policy_params* policy, const char* who);
 int cadm_launch_policy_gauss_roll(cadm_ctx* ctx, const float* obs, const float* x, int P, int p, int t, uint32_t seed, uint32_t call, float* seqs,
                                   float* a1, float* states, size_t total, hipStream_t s, const char* who);
+// policy_gauss.hip, for policy_logp.hip: false while the registered net has no head; else the head's packed layer h_L -> A (mlp_chain.h's
+// layout) and its description, each where asked for (null: not wanted)
+bool cadm_policy_head_dev(const cadm_ctx* ctx, const float** W_ls, const float** b_ls, cadm_policy_head_params* prm);
+// policy_logp.hip: the refusals of the actor's log-density as a term of the score (an unknown space, a weight that is not finite, what
+// cadm_policy_gauss_check refuses, a head whose log_std_min < -10, activation tiles beyond the LDS; no registered net or no head on it:
+// CADM_ESTATE), before any HIP call; and the two launches behind a rollout's traj [H, m, n, p, D] (n the PACKED candidate count; first
+// [m, n, p] or null): step [H, m, n, p] = log pi(a_t | s_t) of every (step, row), NaN where not counted, then rows[q] += weight * (the
+// sum of the counted steps in ascending t) in place
+int cadm_policy_logp_plan_check(const cadm_ctx* ctx, const cadm_policy_logp_params* logp, const char* who);
+int cadm_launch_policy_logp(cadm_ctx* ctx, const cadm_policy_logp_params* logp, const float* traj, const float* obs, const float* actions,
+                            const int32_t* first, int m, int n, float* rows, float* step, hipStream_t s);
 // critic.hip: the refusals of a terminal Q (null parameters, a layer count outside 0 .. 4, a width outside 1 .. 512, an unknown
 // activation or reduce, a critic count outside 1 .. 5, a weight that is not finite, D or A beyond the nets' dims, a discrete / sharded
 // ctx, the input tile and the activation tiles beyond the LDS; no registered critics or no registered policy net: CADM_ESTATE;

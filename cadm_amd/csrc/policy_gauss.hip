@@ -320,6 +320,15 @@ void cadm_policy_head_free(cadm_ctx* ctx) {
     ctx->policy_head = nullptr;
 }
 
+// policy_logp.hip's view of the head: false while the registered net has none; else the packed layer and its description, where asked for
+bool cadm_policy_head_dev(const cadm_ctx* ctx, const float** W_ls, const float** b_ls, cadm_policy_head_params* prm) {
+    if (!(ctx->policy_head && ctx->policy_head->set)) return false;
+    if (W_ls) *W_ls = ctx->policy_head->net.W[0];
+    if (b_ls) *b_ls = ctx->policy_head->net.b[0];
+    if (prm) *prm = ctx->policy_head->prm;
+    return true;
+}
+
 // imagine.hip's sampled step: the refusals (CADM_ESTATE without a net or a head), before any HIP call ..
 int cadm_policy_gauss_check(const cadm_ctx* ctx, const char* who) {
     MlpDev d;

@@ -91,7 +91,13 @@ Differences a caller can see (all opt-in except the first):
     layer has 2 A outputs, the mean and the log standard deviation; the planner and `policy_action` keep the mode action, bit for bit
     (with `cem_policy_prior`'s `proposals="head"` the prior's sequences 1 .. P - 1 are trajectories of the policy itself, drawn at
     std_scale times the standard deviation the head predicts at every state, instead of the mode plus `noise_std`);
-    `imagine(...)` draws its actions from the policy and returns their `logp`, `policy_sample(states)` draws for given states;
+    `imagine(...)` draws its actions from the policy and returns their `logp`, `policy_sample(states)` draws for given states,
+    `policy_log_prob(states, actions)` is the density of actions the caller brings;
+  * `cem_policy_logp=dict(weight=1.0, space="action" | "pre_squash", policy=dict(hidden_sizes=, activation=, squash=))`: the actor as
+    a preference, not only a source of candidates (INTEGRATION.md "Actor-regularised planning") -- weight * sum_t log pi(a_t | s_t) on
+    every step of every particle joins the particle's return.  Needs `policy_head`; `policy` may be left out beside
+    `cem_policy_prior` or `cem_terminal_q`'s policy (one actor).  `plan_policy_log_prob(obs, actions, ...)`: the term of given plans.
+    It alone takes the opt-in route;
   * `cem_discount=gamma` in (0, 1]: a discount over the horizon in that loop (INTEGRATION.md "Discount over the horizon") -- every
     quantity that enters a candidate's score is weighted by gamma^t at step t: the env's own step rewards, the constraint penalty, the
     tracking, uncertainty and rate costs and the learned reward, and a terminal value or Q by gamma^H on top of its `weight` (which
@@ -250,7 +256,7 @@ def _require_policy(model, who, need_net=False):
     """`_require_net` for the methods of the policy net that need no prior: the actor of `cem_terminal_q` will do, and so will the
     one of `imagine_policy` (no planner option: the options may then be None)."""
     opt = getattr(model, "_opt", None)
-    declared = opt is not None and (opt.policy_params is not None or opt.critic_params is not None)
+    declared = opt is not None and (opt.policy_params is not None or opt.critic_params is not None or opt.logp_params is not None)
     if not declared and getattr(model, "_imagine_policy", None) is None:
         raise ValueError("%s: this model has no cem_policy_prior and no cem_terminal_q (and no imagine_policy)" % who)
     if need_net:
@@ -330,6 +336,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                  cem_policy_prior=None,
                  cem_terminal_q=None,
                  cem_discount=1.0,
+                 cem_policy_logp=None,
                  imagine_policy=None,
                  policy_head=None,
                  engine_lib=None,
@@ -402,7 +409,7 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                      cem_uncertainty=cem_uncertainty, obs_dim=obs_space_dims,
                                                      cem_terminal_value=cem_terminal_value, cem_reward_net=cem_reward_net,
                                                      cem_policy_prior=cem_policy_prior, cem_terminal_q=cem_terminal_q,
-                                                     cem_discount=cem_discount)
+                                                     cem_discount=cem_discount, cem_policy_logp=cem_policy_logp)
         if self._opt is not None and self._opt.constraint_params is not None:
             cp = self._opt.constraint_params
             if max(cp.dim[:cp.n]) >= obs_space_dims:
@@ -424,6 +431,8 @@ class MLPEnsembleCEMDynamicsModel(object):
                                                         world=world)
         # where the policy prior's proposals come from (planner.policy_proposals_setting): None without a prior; "head" needs the head
         self._proposals = _planner.policy_proposals_setting(self._opt, head_declared=self._policy_head is not None)
+        # the actor's log-density as a term of the score (planner.policy_logp_setting): None without cem_policy_logp; it needs the head
+        _planner.policy_logp_setting(self._opt, head_declared=self._policy_head is not None, head=self._policy_head)
         self._head_set = False                                # whether the engine holds the head's log-std layer: `set_policy`
         self._sample_call = 0           # policy_sample's own noise counter, as imagine's
         self._plan_carry = self._plan_carry_valid = None      # device tensors [m,K,H,A] float32 / [m] int32 (keep_elites > 0)
@@ -684,6 +693,10 @@ class MLPEnsembleCEMDynamicsModel(object):
                 _need_net(self, net, "get_action", under=row.kwarg)
         if self._opt.critic_params is not None:      # ... and so is the actor the critics are evaluated at
             _need_net(self, "policy", "get_action", under="cem_terminal_q")
+        if self._opt.logp_params is not None:        # ... and the actor whose density scores the plans, with its head
+            _need_net(self, "policy", "get_action", under="cem_policy_logp")
+            if not self._head_set:
+                raise RuntimeError("get_action: this model plans under cem_policy_logp and has no registered Gaussian head (call set_policy first)")
         call = self._next_call()
         if not any(isinstance(x, torch.Tensor) for x in (obs, cp_obs, cp_act, cem_init_mean, cem_init_var)):
             obs, cp_obs, cp_act, cem_init_mean, cem_init_var = eng.stage((obs, cp_obs, cp_act, cem_init_mean, cem_init_var))
@@ -941,6 +954,42 @@ class MLPEnsembleCEMDynamicsModel(object):
         self._sample_call += 1
         out = self.engine.policy_sample(states, seed=int(self.seed if seed is None else seed) & 0xFFFFFFFF, call=call)
         return {k: v.cpu().numpy() for k, v in out.items()} if numpy else out
+
+    def _require_head(self, who):
+        """Refuse for `who` while the model has no actor with a registered Gaussian head."""
+        _require_policy(self, who, need_net=True)
+        if getattr(self, "_policy_head", None) is None or not getattr(self, "_head_set", False):
+            raise ValueError("%s: this model has no registered Gaussian head (declare policy_head, then set_policy)" % who)
+
+    def policy_log_prob(self, states, actions, space="action", numpy=True):
+        """log pi(a | s) of GIVEN `actions` [..., A] at raw observations `states` [..., D] under the stochastic actor (`policy_head`)
+        -> [...]: the density `policy_sample` reports for its own draws, evaluated at actions the caller brings (stored transitions
+        under the current actor, a planner's actions before they are distilled).  space "action": the squashed actor's density;
+        "pre_squash": the Gaussian's density of atanh of the normalised action, without the Jacobian (for squash="none" the two agree).
+        An action on or beyond a bound is clamped to |y| = 0.999999 first.  NaN for a row with a non-finite state or action.  Works on
+        any model with a registered head, with or without `cem_policy_logp`; nothing is drawn and no counter moves."""
+        self._require_head("policy_log_prob")
+        out = self.engine.policy_log_prob(states, actions, space)
+        return out.cpu().numpy() if numpy else out
+
+    def plan_policy_log_prob(self, obs, actions, cp_obs=None, cp_act=None, seed=None):
+        """The actor's log-density along `actions` ([m,H,A], or [m,n,H,A]; numpy or tensor) -- the companion of `plan_rewards` for
+        `cem_policy_logp`: the context encoder, one rollout that records its trajectories and the log-density kernels, as numpy arrays
+        (for [m,H,A] input the n axis is dropped):
+          logp [m,n,p,H]    log pi(a_t | s_t) of every step of every particle (NaN: a step with a non-finite state or action, or one
+                            behind a particle's first violation)
+          total [m,n,p]     the sum over the counted steps in ascending t; the planner adds weight * total to the particle's return
+          first [m,n,p]     with `cem_constraints` in terminate mode their first violations (steps t <= first count), else None
+        The noise is drawn as `forecast` draws it: (seed, the last get_action's call) under the forecast's iteration word; no counter moves.
+        On a model with `cem_discount` total is the discounted sum (gamma^t * logp_t); logp stays undiscounted."""
+        opt = getattr(self, "_opt", None)
+        if opt is None or opt.logp_params is None:
+            raise ValueError("plan_policy_log_prob: this model has no cem_policy_logp")
+        self._require_head("plan_policy_log_prob")
+        obs, acts, rows, traj, squeeze = self._replay("plan_policy_log_prob", obs, actions, cp_obs, cp_act, seed)
+        first = self._terminate_first(traj, rows, obs, acts)
+        _, steps, total = self.engine.policy_logp_returns(traj, obs, acts, rows, self._opt.logp_params, first=first, want_steps=True)
+        return self._result(squeeze, logp=steps.permute(1, 2, 3, 0), total=total, first=first)
 
     def policy_proposals(self, obs, cp_obs=None, cp_act=None, seed=None, return_states=False):
         """The sequences the policy prior would inject for `obs` [m,D] (with a context model its history cp_obs / cp_act) -> numpy

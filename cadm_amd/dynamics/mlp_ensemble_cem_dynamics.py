@@ -65,6 +65,10 @@ class MLPEnsembleCEMDynamicsModel(_CaDMModel):
         """What this model's `cem_terminal_q` adds for `actions` (see the CaDM class; a vanilla model has no history)."""
         return super().plan_terminal_q(obs, actions, None, None, seed=seed)
 
+    def plan_policy_log_prob(self, obs, actions, seed=None):
+        """The actor's log-density along `actions` under this model's `cem_policy_logp` (see the CaDM class; a vanilla model has no history)."""
+        return super().plan_policy_log_prob(obs, actions, None, None, seed=seed)
+
     def plan_returns(self, obs, actions, seed=None):
         """The discounted env returns of `actions` under this model's `cem_discount` (see the CaDM class; a vanilla model has no history)."""
         return super().plan_returns(obs, actions, None, None, seed=seed)

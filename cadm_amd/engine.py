@@ -44,7 +44,7 @@ def ctx_param_names(n_cp_hidden):
 # the targets) --; and, for a level with workspace slots of its own, the slot's tag and how many of (terminate, actuator, uncertainty, P)
 # key the slot and size it (cadm_<level>_workspace_bytes).  The levels without a tag share the slots `_loop_workspace` names by what they
 # are given.  From `actuated_plan` outwards a level whose own struct (its first argument) is None hands the call to the level below.
-# A thirteenth term is one row here and one public method of one call; in the library, one export and one field of PlanTerms.
+# A further term is one row here and one public method of one call; in the library, one export and one field of PlanTerms.
 _PLAN_NEST = (
     ("scored_plan", ("score", "update", "params"), None, 0),
     ("constrained_plan", ("constraints",), None, 0),
@@ -56,6 +56,7 @@ _PLAN_NEST = (
     ("rewarded_plan", ("reward",), "rew", 3),
     ("guided_plan", ("policy",), "pol", 4),
     ("critic_plan", ("critic",), "crt", 4),
+    ("anchored_plan", ("logp",), "anc", 4),
 )
 _PLAN_LEVEL = {row[0]: i for i, row in enumerate(_PLAN_NEST)}
 # how many arguments each level's export takes between ctx and obs, and each level's method in front of obs
@@ -592,13 +593,14 @@ class HipEngine:
                                init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return)
 
     def _loop_plan(self, who, export, head, mppi, K, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out,
-                   want_best_return, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None, crt=None):
+                   want_best_return, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None, crt=None, anc=None):
         """What `icem_plan`, `mppi_plan` and `scored_plan` share: staging, the carry check, the workspace, the outputs and the call of
         `export` (cadm_<who>) -- head: its arguments between the ctx and obs; mppi: which update's workspace; K: keep_elites; traj: the
         workspace with the trajectory view behind it (a constrained loop); track: as in `_loop_workspace` (a tracked loop); act: the workspace of an actuated loop;
         unc: None, or the (terminate, actuator) of a loop with an uncertainty term, whose slot it is; val: None, or the (terminate, actuator,
         uncertainty) of a loop with a terminal value, whose slot it is; rew: likewise for a loop with a learned reward; pol: None, or the
-        (terminate, actuator, uncertainty, P) of a loop with a policy prior, whose slot it is; crt: likewise for a loop with a terminal Q."""
+        (terminate, actuator, uncertainty, P) of a loop with a policy prior, whose slot it is; crt: likewise for a loop with a terminal Q;
+        anc: likewise for a loop with the actor's log-density."""
         obs, init_mean, init_var = self._t(obs), self._t(init_mean), self._t(init_var)
         cp_obs = None if cp_obs is None else self._t(cp_obs)
         cp_act = None if cp_act is None else self._t(cp_act)
@@ -607,7 +609,7 @@ class HipEngine:
                       or tuple(carry_valid.shape) != (m,) or carry_valid.dtype != torch.int32 or not carry.is_contiguous()):
             raise ValueError("%s: keep_elites=%d needs carry [%d,%d,%d,%d] float32 and carry_valid [%d] int32" % (who, K, m, K, self.H, self.A, m))
         self.ensure_rollout(None, m, n)
-        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val, rew=rew, pol=pol, crt=crt)
+        ws = self._loop_workspace(mppi, m, n, K, traj=traj, track=track, act=act, unc=unc, val=val, rew=rew, pol=pol, crt=crt, anc=anc)
         if out is None:
             out = torch.empty((m, self.H, self.A), dtype=torch.float32, device=self.device)
         best = torch.empty((m,), dtype=torch.float32, device=self.device) if want_best_return else None
@@ -622,8 +624,9 @@ class HipEngine:
         `constrained_plan` when it holds constraints, `scored_plan` when it holds a score, else `mppi_plan` or `icem_plan` by its update.
         Arguments as `icem_plan` behind its params.  First of all `rewarded_plan`, when it holds a learned reward, then `valued_plan`, when
         it holds a terminal value, then `uncertain_plan`, when it holds an uncertainty term.  Before all of them `guided_plan`, when it
-        holds a policy prior; and before that `critic_plan`, when it holds a terminal Q."""
-        full = (getattr(opt, "critic_params", None), getattr(opt, "policy_params", None), getattr(opt, "reward_params", None),
+        holds a policy prior; and before that `critic_plan`, when it holds a terminal Q; outermost `anchored_plan`, when it holds the
+        actor's log-density."""
+        full = (getattr(opt, "logp_params", None), getattr(opt, "critic_params", None), getattr(opt, "policy_params", None), getattr(opt, "reward_params", None),
                 getattr(opt, "value_params", None), getattr(opt, "uncertainty_params", None), opt.actuator_params, act_prev, act_prefix,
                 getattr(opt, "action_advance", None), opt.track_params, targets, target_offset, opt.knot_params, phase,
                 opt.constraint_params, opt.score_params, opt.params)      # the outermost method's arguments
@@ -633,7 +636,7 @@ class HipEngine:
         return (self.mppi_plan if opt.update == "mppi" else self.icem_plan)(opt.params, *args, **kw)
 
     def _nest_plan(self, level, lead, obs, cp_obs, cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return):
-        """What the ten nested `*_plan` methods do (`_PLAN_NEST`); level: the method called, lead: its arguments in front of obs.  Finds
+        """What the eleven nested `*_plan` methods do (`_PLAN_NEST`); level: the method called, lead: its arguments in front of obs.  Finds
         the level that answers -- its name is the one in the messages, its export the one called, its slot the workspace --, checks what
         the host can check, builds the export's arguments between the ctx and obs, and calls `_loop_plan`."""
         i = _PLAN_LEVEL[level]
@@ -641,8 +644,8 @@ class HipEngine:
         while i >= _ACTUATED and full[-_PLAN_NARGS[i]] is None:
             i -= 1
         who, _, tag, nflags = _PLAN_NEST[i]
-        (critic, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints, score,
-         params) = full
+        (logp, critic, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots, phase, constraints,
+         score, params) = full
         mppi, params = self._as_mppi_params(params)
         m = int(np.shape(obs)[0]) if i >= _KNOT else None      # (the two levels below have nothing per env to check)
         if actuator is None:
@@ -660,7 +663,7 @@ class HipEngine:
             targets = offset = None
         else:
             targets, T, offset = self._targets(targets, offset, m, track.n, who)
-        head = (_by(critic), _by(policy), _by(reward), _by(value), _by(uncertainty), _by(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
+        head = (_by(logp), _by(critic), _by(policy), _by(reward), _by(value), _by(uncertainty), _by(actuator), ptr(prev), ptr(prefix), int(bool(advance)),
                 _by(track), ptr(targets), T, ptr(offset), _by(knots), ptr(phase), _by(constraints), _by(score), int(mppi), ct.byref(params))
         terminate = constraints is not None and constraints.mode == _lib.CONSTRAIN_MODES["terminate"]
         flags = (terminate, actuator is not None, uncertainty is not None, 0 if policy is None else max(int(policy.n_samples), 0))
@@ -669,7 +672,7 @@ class HipEngine:
         return self._loop_plan(who, getattr(self.lib, "cadm_" + who), head[-_PLAN_NHEAD[i]:], mppi, params.icem.keep_elites, obs, cp_obs,
                                cp_act, init_mean, init_var, n, carry, carry_valid, seed, call, out, want_best_return, **ws)
 
-    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None, crt=None):
+    def _loop_workspace(self, mppi, m, n, K, traj=False, track=None, act=False, unc=None, val=None, rew=None, pol=None, crt=None, anc=None):
         """The opt-in loop's workspace, cached per (m, n, K): one for the elite refit, a larger one for the MPPI update, and -- only for a
         constrained loop -- each of them with the trajectory view behind it (an unconstrained model never allocates that).  track: None,
         or whether a tracked loop runs under TERMINATE constraints -- the tracking slot (`cadm_tracking_workspace_bytes`: the trajectory
@@ -682,9 +685,11 @@ class HipEngine:
         valued loop's, and behind everything the step rewards).  pol: None, or (terminate, actuator, uncertainty, P) -- the slot of a loop
         with a policy prior (`cadm_guided_workspace_bytes`: the rewarded loop's, and behind everything the proposals and the roll's
         workspace).  crt: None, or (terminate, actuator, uncertainty, P) -- the slot of a loop with a terminal Q
-        (`cadm_critic_workspace_bytes`: the guided loop's; P = 0 without a policy prior in the same call)."""
+        (`cadm_critic_workspace_bytes`: the guided loop's; P = 0 without a policy prior in the same call).  anc: likewise -- the slot of
+        a loop with the actor's log-density (`cadm_anchored_workspace_bytes`: the critic loop's, and behind everything the step
+        log-densities)."""
         mppi = bool(mppi)
-        for (tag, size), flags in zip(_PLAN_SLOTS, (crt, pol, rew, val, unc)):      # the outermost term given names the slot and sizes it
+        for (tag, size), flags in zip(_PLAN_SLOTS, (anc, crt, pol, rew, val, unc)):      # the outermost term given names the slot and sizes it
             if flags is not None:
                 flags = tuple(bool(f) for f in flags[:3]) + tuple(int(P) for P in flags[3:])
                 slot = (mppi, tag) + flags
@@ -1800,6 +1805,83 @@ class HipEngine:
         return self._nest_plan("critic_plan", (critic, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets,
                                offset, knots, phase, constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n, carry,
                                carry_valid, seed, call, out, want_best_return)
+
+    # ------------------------------------------------------------------ the actor's log-density (opt-in; csrc/policy_logp.hip)
+    @staticmethod
+    def policy_logp_params(weight=1.0, space="action"):
+        """`cadm_policy_logp_params`: weight -- what the step sum of log pi(a_t | s_t) is multiplied by before it is added to a return
+        (beta of return + beta * sum_t log pi), a finite number, no bool; space -- "action" (the squashed actor's density, with the tanh
+        Jacobian) or "pre_squash" (the Gaussian's density of u = atanh(y), no Jacobian), or its CADM_LOGP_* number.  Needs no GPU."""
+        prm = _lib.PolicyLogpParams()
+        prm.space = HipEngine.policy_logp_space(space)
+        if isinstance(weight, (bool, np.bool_)) or not isinstance(weight, (int, float, np.integer, np.floating)):
+            raise ValueError("policy log-density weight must be a finite number, got %r" % (weight,))
+        w = float(np.float32(weight))
+        if not math.isfinite(w):
+            raise ValueError("policy log-density weight must be a finite number, got %r" % (weight,))
+        prm.weight = w
+        return prm
+
+    @staticmethod
+    def policy_logp_space(space):
+        """The CADM_LOGP_* number of space "action" | "pre_squash" (or of the number itself); anything else is a ValueError."""
+        if isinstance(space, str) and space in _lib.LOGP_SPACES:
+            return _lib.LOGP_SPACES[space]
+        if not isinstance(space, (bool, str)) and isinstance(space, (int, np.integer)) and int(space) in _lib.LOGP_SPACES.values():
+            return int(space)
+        raise ValueError("policy log-density space must be %s, got %r" % (" or ".join(repr(k) for k in _lib.LOGP_SPACES), space))
+
+    def policy_log_prob(self, states, actions, space="action"):
+        """`cadm_policy_logp`: log pi(a | s) of states [..., D] and actions [..., A] -> [...] (device tensors) under the registered
+        policy net and its Gaussian head, through the planner's kernel; NaN for a row with a non-finite value in its state or action."""
+        sp = HipEngine.policy_logp_space(space)
+        states, flat = HipEngine._flat_rows(self, "policy_log_prob", states, self.D)
+        actions = self._t(actions)
+        if tuple(actions.shape) != tuple(states.shape[:-1]) + (self.A,):
+            raise ValueError("policy_log_prob: actions %r, expected %r" % (tuple(actions.shape), tuple(states.shape[:-1]) + (self.A,)))
+        aflat = actions.reshape(-1, self.A).contiguous()
+        R = int(flat.shape[0])
+        logp = torch.empty((R,), dtype=torch.float32, device=self.device)
+        self._check(self.lib.cadm_policy_logp(self._ctx, ptr(flat), ptr(aflat), R, sp, ptr(logp), self.stream), "cadm_policy_logp")
+        return logp.reshape(tuple(states.shape[:-1]))
+
+    def policy_logp_returns(self, traj, obs, actions, rows, params, first=None, want_steps=False, out=None):
+        """`cadm_policy_logp_returns` on device tensors, `reward_returns`' twin: traj [H,m,n,p,D] (a rollout's `traj_out`), obs [m,D],
+        actions [m,n,H,A] (what the rollout read), rows [m,n,p] -> rows + weight * S per row under `params` (`policy_logp_params`), S
+        the sum of log pi(a_t | s_t) over the counted steps in ascending t.  first [m,n,p] int32 (None: every step counts):
+        `constrain_returns`' first_violation -- the steps t <= first count.  want_steps: (rows_out, steps [H,m,n,p], S [m,n,p]), steps
+        NaN where not counted; else the steps go to a cached workspace.  out: where the new rows go (may be `rows` itself)."""
+        traj, rows, first, out = HipEngine._returns_args(self, "policy_logp_returns", traj, rows, first, out)
+        H, m, n, p, D = traj.shape
+        obs, actions = self._t(obs), self._t(actions)
+        if tuple(obs.shape) != (m, D):
+            raise ValueError("policy_logp_returns: obs %r, expected contiguous %r" % (tuple(obs.shape), (m, D)))
+        if tuple(actions.shape) != (m, n, H, self.A):
+            raise ValueError("policy_logp_returns: actions %r, expected contiguous %r" % (tuple(actions.shape), (m, n, H, self.A)))
+        steps = S = ws = None
+        if want_steps:
+            steps = torch.empty((H, m, n, p), dtype=torch.float32, device=self.device)
+            S = torch.empty((m, n, p), dtype=torch.float32, device=self.device)
+        else:
+            need = self.lib.cadm_policy_logp_workspace_bytes(self._ctx, m, n)
+            ws = getattr(self, "_logp_ws", None)
+            if ws is None or ws.numel() < need:
+                ws = self._logp_ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.cadm_policy_logp_returns(self._ctx, ct.byref(params), ptr(traj), ptr(obs), ptr(actions), ptr(first), m, n,
+                                                      ptr(rows), ptr(out), ptr(steps), ptr(S), ptr(ws), self.stream), "cadm_policy_logp_returns")
+        return (out, steps, S) if want_steps else out
+
+    def anchored_plan(self, logp, critic, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track, targets, offset, knots,
+                      phase, constraints, score, params, obs, cp_obs, cp_act, init_mean, init_var, n, carry=None, carry_valid=None, seed=0,
+                      call=0, out=None, want_best_return=False):
+        """`cadm_anchored_plan`: the loop of `critic_plan` with `logp.weight` times the step sum of the registered actor's log-density
+        log pi(a_t | s_t) added to the particle returns, behind the learned reward and in front of the terminal value / Q (`logp`: a
+        `policy_logp_params`; None = none, and `critic_plan`'s launches).  `policy` may be None while a policy net and its head are
+        registered.  Arguments behind `logp` as `critic_plan`; the workspace is the slot of `cadm_anchored_workspace_bytes`, cached
+        apart from the others."""
+        return self._nest_plan("anchored_plan", (logp, critic, policy, reward, value, uncertainty, actuator, prev, prefix, advance, track,
+                               targets, offset, knots, phase, constraints, score, params), obs, cp_obs, cp_act, init_mean, init_var, n,
+                               carry, carry_valid, seed, call, out, want_best_return)
 
     # ------------------------------------------------------------------ open-loop prediction error along the horizon
     def _horizon_outputs(self, F, D, E=None):

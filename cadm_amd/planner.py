@@ -12,7 +12,7 @@ What is left here:
   * `Shard`: a rank's contiguous candidate range;  `check_replicated`: the host-side guard of the first sharded calls;
   * `ExternalAllGather`: the host-supplied collective;
   * `PlanOptions`: what a model's `cem_*` kwargs mean -- their checks, the switches, and the ctypes structs `HipEngine.opt_in_plan` hands to the library;
-  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`; `actuator=`: `cadm_actuated_plan`; `uncertainty=`: `cadm_uncertain_plan`; `value=`: `cadm_valued_plan`; `reward=`: `cadm_rewarded_plan`; `policy=`: `cadm_guided_plan`; `critic=`: `cadm_critic_plan`) one launch at a time, for the same purposes;
+  * `icem_plan`: the opt-in iCEM loop (`cadm_icem_plan`, csrc/icem.hip; `update="mppi"`: `cadm_mppi_plan`; `score=`: `cadm_scored_plan`; `constraints=`: `cadm_constrained_plan`; `knots=`: `cadm_knot_plan`; `tracking=`: `cadm_tracking_plan`; `actuator=`: `cadm_actuated_plan`; `uncertainty=`: `cadm_uncertain_plan`; `value=`: `cadm_valued_plan`; `reward=`: `cadm_rewarded_plan`; `policy=`: `cadm_guided_plan`; `critic=`: `cadm_critic_plan`; `policy_logp=`: `cadm_anchored_plan`) one launch at a time, for the same purposes;
   * `cem_plan` / `rs_plan`: the per-iteration, SINGLE-RANK form over the engine's primitives, for parity tests with injected ``z`` /
     ``eps`` and for diagnostics (`return_info`) -- the reference's TF RNG streams are unseeded.
 Reference: /root/reference/cadm/dynamics/core/utils.py:398-488 (CEM), :490-561 (RS).
@@ -32,9 +32,9 @@ FORECAST_IT = 0xFC0000      # the iteration word of a forecast's rollout: csrc/p
 
 class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites decay return_best add_mean_last update temperature relative score "
                                                        "params score_params constraints constraint_params knots knot_params actuator actuator_params "
-                                                       "action_advance proposals std_scale discount critic critic_params policy policy_params reward reward_params value value_params uncertainty "
+                                                       "action_advance proposals std_scale discount logp logp_params critic critic_params policy policy_params reward reward_params value value_params uncertainty "
                                                        "uncertainty_params tracking track_params target_advance",
-                                                       defaults=(None, None, None, None, True, "noise", 1.0, 1.0, None, None, None, None, None, None, None, None, None, None,
+                                                       defaults=(None, None, None, None, True, "noise", 1.0, 1.0, None, None, None, None, None, None, None, None, None, None, None, None,
                                                                  None, None, True))):
     """The opt-in planner's switches (a model's `cem_*` kwargs), immutable, with the structs the library reads built once: `params` -- an
     `IcemParams` (update "cem") or a `MppiParams` ("mppi") -- and `score_params` (a `ScoreParams`, or None: the particle mean).
@@ -62,18 +62,25 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
     `CriticParams` built from it (None: no terminal Q); actor = (the tuple of hidden widths, activation name, squash name) of the policy
     net the critics are evaluated at -- the policy prior's when one is declared (`actor_params` builds its `PolicyParams`); critics
     and actor are registered at run time (`set_critics`, `set_policy`).
+    `logp`: None, or (weight, space name, actor), with `logp_params` the `PolicyLogpParams` built from it (None: the actor's log-density
+    is no term of the score); actor = (the tuple of hidden widths, activation name, squash name) of the policy net whose density it is
+    -- the one actor of the model, as `critic`'s.
     `discount`: gamma in (0, 1], the discount over the horizon every term of a candidate's score is weighted by per step (1.0: none); a
     model hands it to its engine once (`HipEngine.set_discount`), it is not a parameter of a plan call."""
     __slots__ = ()
 
     def actor_params(self):
         """The `PolicyParams` a model registers its actor under: the policy prior's, or -- for a model whose only actor declaration is
-        `cem_terminal_q`'s `policy` -- one built from it with n_samples = 1 (the value is not used); None without either."""
+        `cem_terminal_q`'s or `cem_policy_logp`'s `policy` -- one built from it with n_samples = 1 (the value is not used); None without
+        any."""
         if self.policy_params is not None:
             return self.policy_params
-        if self.critic is None:
+        if self.critic is not None:
+            hs, act, squash = self.critic[5]
+        elif self.logp is not None:
+            hs, act, squash = self.logp[2]
+        else:
             return None
-        hs, act, squash = self.critic[5]
         return HipEngine.policy_params(hs, act, squash, 1, 0.0)
 
     @staticmethod
@@ -83,7 +90,7 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                     cem_knots=1, cem_knot_interp="hold", cem_knot_anchor="call", cem_tracking=None, cem_target_advance=True,
                     cem_action_delay=0, cem_action_rate_limit=None, cem_action_rate_cost=None, cem_action_advance=True, n_forwards=None,
                     action_dim=None, cem_uncertainty=None, obs_dim=None, cem_terminal_value=None, cem_reward_net=None,
-                    cem_policy_prior=None, cem_terminal_q=None, cem_discount=1.0):
+                    cem_policy_prior=None, cem_terminal_q=None, cem_discount=1.0, cem_policy_logp=None):
         """None when every `cem_*` kwarg is at its default (the reference's CEM: nothing else is looked at); else the kwargs checked --
         everything that needs no engine -- and folded into a `PlanOptions`.  n_forwards / action_dim: the model's horizon and action
         dims, what `cem_action_delay` and the lengths of `cem_action_rate_limit` / `cem_action_rate_cost` are checked against (None: the
@@ -104,7 +111,11 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
         are evaluated at; `policy` may be left out when cem_policy_prior is declared (the actor is then that net; given both, they must
         agree); not together with cem_terminal_value: a plan has one terminal term.  cem_discount: gamma in (0, 1], the discount over
         the horizon (`HipEngine.set_discount`); 1.0: none.  With it the `weight` of cem_terminal_value / cem_terminal_q no longer carries
-        gamma ** n_forwards: the library multiplies it in."""
+        gamma ** n_forwards: the library multiplies it in.
+        cem_policy_logp: None, or dict(weight=1.0, space="action" | "pre_squash", policy=dict(hidden_sizes=, activation=, squash=))
+        (`HipEngine.policy_logp_params`): weight * sum_t log pi(a_t | s_t) of the model's actor joins every particle's return; `policy`
+        may be left out beside cem_policy_prior or cem_terminal_q's policy (one actor: given both, they must agree).  Whether the model
+        declares the `policy_head` the density needs is the model's check: `policy_logp_setting`."""
         if isinstance(cem_discount, (bool, np.bool_)) or not isinstance(cem_discount, (int, float, np.integer, np.floating)) \
                 or not 0.0 < float(cem_discount) <= 1.0:      # (NaN: false)
             raise ValueError("cem_discount must be a number in (0, 1] (1.0: no discount over the horizon), got %r" % (cem_discount,))
@@ -119,12 +130,13 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                 and (cem_knot_interp, cem_knot_anchor) == ("hold", "call") and isinstance(cem_knots, (int, np.integer)) \
                 and not isinstance(cem_knots, bool) and int(cem_knots) == 1 and cem_tracking is None and cem_target_advance is True \
                 and act_off and cem_action_advance is True and cem_uncertainty is None and cem_terminal_value is None \
-                and cem_reward_net is None and cem_policy_prior is None and cem_terminal_q is None and float(cem_discount) == 1.0:
+                and cem_reward_net is None and cem_policy_prior is None and cem_terminal_q is None and float(cem_discount) == 1.0 \
+                and cem_policy_logp is None:
             return None
         if not use_cem:
             raise ValueError("cem_noise_beta / cem_keep_elites / cem_decay / cem_return / cem_add_mean / cem_update / cem_temperature / "
                              "cem_score / cem_risk / cem_constraints / cem_knots / cem_tracking / cem_action_delay / cem_action_rate_limit / "
-                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net / cem_policy_prior / cem_terminal_q / cem_discount configure the CEM planner: they need "
+                             "cem_action_rate_cost / cem_uncertainty / cem_terminal_value / cem_reward_net / cem_policy_prior / cem_terminal_q / cem_discount / cem_policy_logp configure the CEM planner: they need "
                              "use_cem=True")
         if float(cem_discount) != 1.0:
             if discrete:
@@ -204,6 +216,36 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
             critic = (tuple(int(qparams.hidden[l]) for l in range(qparams.n_hidden)),
                       [k for k, x in _lib.VALUE_ACTS.items() if x == qparams.activation][0], int(qparams.n_critics),
                       [k for k, x in _lib.CRITIC_REDUCES.items() if x == qparams.reduce][0], float(qparams.weight), actor)
+        logp = lparams = None
+        if cem_policy_logp is not None:
+            if not isinstance(cem_policy_logp, dict) or set(cem_policy_logp) - {"weight", "space", "policy"}:
+                raise ValueError("cem_policy_logp must be dict(weight=, space=, policy=), got %r" % (cem_policy_logp,))
+            if obs_dim is not None and not 1 <= int(obs_dim) <= _lib.MAX_VALUE_DIMS:
+                raise ValueError("a policy net reads up to %d observation dims, got %r" % (_lib.MAX_VALUE_DIMS, obs_dim))
+            if action_dim is not None and not 1 <= int(action_dim) <= _lib.MAX_POLICY_ACTIONS:
+                raise ValueError("a policy net writes up to %d action dims, got %r" % (_lib.MAX_POLICY_ACTIONS, action_dim))
+            g = dict(weight=1.0, space="action", policy=None)
+            g.update(cem_policy_logp)
+            lparams = HipEngine.policy_logp_params(g["weight"], g["space"])
+            lactor = None
+            if g["policy"] is not None:
+                if not isinstance(g["policy"], dict) or set(g["policy"]) - {"hidden_sizes", "activation", "squash"}:
+                    raise ValueError("cem_policy_logp: policy must be dict(hidden_sizes=, activation=, squash=), got %r" % (g["policy"],))
+                a = dict(hidden_sizes=(256, 256), activation="relu", squash="tanh")
+                a.update(g["policy"])
+                ap = HipEngine.policy_params(a["hidden_sizes"], a["activation"], a["squash"], 1, 0.0)
+                lactor = (tuple(int(ap.hidden[l]) for l in range(ap.n_hidden)), [k for k, x in _lib.VALUE_ACTS.items() if x == ap.activation][0],
+                          [k for k, x in _lib.POLICY_SQUASH.items() if x == ap.squash][0])
+            declared = policy[:3] if policy is not None else None if critic is None else critic[5]      # the model's one actor, so far
+            if declared is not None:
+                if lactor is not None and lactor != declared:
+                    raise ValueError("cem_policy_logp: policy %r does not agree with the actor %r that cem_policy_prior / cem_terminal_q "
+                                     "declare (one actor: hidden_sizes, activation and squash must be the same)" % (lactor, declared))
+                lactor = declared
+            if lactor is None:
+                raise ValueError("cem_policy_logp needs policy=dict(hidden_sizes=, activation=, squash=), the actor whose density it is "
+                                 "(or a cem_policy_prior / cem_terminal_q, whose actor it then is)")
+            logp = (float(lparams.weight), [k for k, x in _lib.LOGP_SPACES.items() if x == lparams.space][0], lactor)
         reward = rparams = None
         if cem_reward_net is not None:
             if not isinstance(cem_reward_net, dict) or set(cem_reward_net) - {"inputs", "hidden_sizes", "activation", "weight"}:
@@ -321,7 +363,7 @@ class PlanOptions(collections.namedtuple("PlanOptions", "noise_beta keep_elites 
                            track_params=tparams, target_advance=bool(cem_target_advance), actuator=actuator, actuator_params=aparams,
                            action_advance=bool(cem_action_advance), uncertainty=uncertainty, uncertainty_params=uparams, value=value, value_params=vparams, reward=reward,
                            reward_params=rparams, policy=policy, policy_params=pparams, critic=critic, critic_params=qparams, discount=discount, proposals=proposals,
-                           std_scale=std_scale, **mppi, **icem)
+                           std_scale=std_scale, logp=logp, logp_params=lparams, **mppi, **icem)
 
 
 def policy_slot(keep_elites, last, add_mean_last):
@@ -348,6 +390,21 @@ def policy_proposals_setting(opt, head_declared=False):
     if opt.proposals == "head" and not head_declared:
         raise ValueError("cem_policy_prior: proposals=\"head\" draws the proposals from the actor's Gaussian head: declare policy_head")
     return opt.proposals, float(opt.std_scale)
+
+
+def policy_logp_setting(opt, head_declared=False, head=None):
+    """The model's check of `cem_policy_logp` against its `policy_head` -> the options' `PolicyLogpParams`, or None for a model without
+    the term.  opt: the model's `PlanOptions` (or None); head_declared: whether the model declares a `policy_head`; head: its
+    `PolicyHeadParams` when the caller has them.  Without a head there is no density to evaluate, and a head whose log_std lower bound
+    is below -10 is refused as the library refuses it (exp(-log_std) must stay finite with a margin): both ValueError.  Needs no GPU."""
+    if opt is None or opt.logp_params is None:
+        return None
+    if not head_declared:
+        raise ValueError("cem_policy_logp scores plans by the density of the actor's Gaussian head: declare policy_head")
+    if head is not None and head.log_std_min < _lib.LOGSTD_MIN:
+        raise ValueError("cem_policy_logp: policy_head log_std_bounds: lo %r is below %g (exp(-log_std) must stay finite with a margin)"
+                         % (head.log_std_min, _lib.LOGSTD_MIN))
+    return opt.logp_params
 
 
 def imagine_policy_params(imagine_policy, opt=None, obs_dim=None, action_dim=None, discrete=False):
@@ -703,7 +760,7 @@ def rs_plan(engine, obs, cp_obs, cp_act, n, seed=0, call=0, actions=None, raw=No
 def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.0, keep_elites=0, decay=1.0, return_best=False,
               add_mean_last=False, carry=None, carry_valid=None, seed=0, call=0, z=None, xi=None, eps=None, return_info=False,
               update="cem", temperature=1.0, relative=False, score=None, constraints=None, knots=None, phase=None, tracking=None, actuator=None,
-              action_advance=False, uncertainty=None, value=None, reward=None, policy=None, critic=None):
+              action_advance=False, uncertainty=None, value=None, reward=None, policy=None, critic=None, policy_logp=None):
     """The iCEM loop of `cadm_icem_plan` (csrc/icem.hip) one launch at a time over the engine's primitives, single rank: for parity
     tests with injected draws and for diagnostics.  update="mppi": the loop of `cadm_mppi_plan` -- the elite ids come from an elite
     refit into copies of mean / var, the distribution from `mppi_refit`.  score: a `HipEngine.score_params` (`cadm_scored_plan`; None: the
@@ -740,6 +797,10 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
     every rollout then records its trajectories and `critic_returns` adds weight * reduce_c Q_c(s, pi(s)) of the last state to the
     particle rows behind the reward stage, before the score; `return_info` carries `q` [m,n_it,p] (NaN where skipped) and `q_rows`, the
     rows before the addition.
+    policy_logp: a `HipEngine.policy_logp_params` (`cadm_anchored_plan`; None: none) -- every rollout then records its trajectories and
+    `policy_logp_returns` adds weight * (the sum of log pi(a_t | s_t) over the counted steps) to the particle rows behind the learned
+    reward and in front of the terminal value / Q; `return_info` carries `logp_steps` [H,m,n_it,p] (NaN where not counted), `logp_sum`
+    [m,n_it,p] and `logp_rows`, the rows before the addition.
     On an engine with a discount over the horizon (`HipEngine.set_discount`) every rollout records its trajectories and
     `discount_returns` rewrites `rows` directly behind it, in front of the constraints; the stage calls above pick the engine's table up
     themselves; `return_info` carries `rows_undiscounted`, the rollout's own sums, and `rows_discounted` (`rows_raw` is then the
@@ -782,7 +843,7 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
             _, action_cost = engine.actuate_actions(actions, actuator[0], prev=actuator[1], prefix=actuator[2], want_cost=True)
         extra = {}
         if constraints is None and tracking is None and uncertainty is None and value is None and reward is None and critic is None \
-                and not discounted:
+                and policy_logp is None and not discounted:
             rows = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it)
         else:
             rows, traj = engine.rollout_returns(obs, ctx_vec, actions, eps=None if eps is None else eps[it], seed=seed, call=call, it=it,
@@ -806,6 +867,10 @@ def icem_plan(engine, obs, cp_obs, cp_act, init_mean, init_var, n, noise_beta=0.
                 unrewarded = rows
                 rows, steps, rsum = engine.reward_returns(traj, obs, actions, unrewarded, reward, first=first, want_steps=True)
                 extra.update(traj=traj, reward_steps=steps, reward_sum=rsum, reward_rows=unrewarded)
+            if policy_logp is not None:
+                logp_rows = rows
+                rows, lsteps, lsum = engine.policy_logp_returns(traj, obs, actions, logp_rows, policy_logp, first=first, want_steps=True)
+                extra.update(traj=traj, logp_steps=lsteps, logp_sum=lsum, logp_rows=logp_rows)
             if value is not None:
                 unvalued = rows
                 rows, v = engine.value_returns(traj, unvalued, value, first=first, want_v=True)

@@ -908,7 +908,7 @@ int cadm_critic_eval(cadm_ctx* ctx, const float* states, const float* actions, i
                      void* stream);
 int cadm_critic_returns(cadm_ctx* ctx, const cadm_critic_params* params, const float* traj, const int32_t* first, int m, int n,
                         const float* rows_in, float* rows_out, float* q_out, void* stream);
-/* The loop of cadm_guided_plan with that term in the particle returns: the outermost level of the nest today.  Per iteration the stage runs
+/* The loop of cadm_guided_plan with that term in the particle returns (cadm_anchored_plan is the level above).  Per iteration the stage runs
  * where the terminal value's runs: rollout -> constraints -> tracking -> the learned reward -> rows[q] += weight * r[q] on the particle
  * rows [m,n_it,p] -> cadm_particle_score -> the costs off the candidate score -> the refit.  critic NULL: exactly the launches of
  * cadm_guided_plan.  policy may be NULL while a policy net is registered: the term needs the registered net, not the proposals.
@@ -932,7 +932,7 @@ int cadm_critic_plan(cadm_ctx* ctx, const cadm_critic_params* critic, const cadm
  * discount: the table is then null and every launch of the library is the undiscounted one.  Otherwise the ctx owns a device table
  *   disc[t] = (float)pow((double)gamma, (double)t),  t = 0 .. H,  disc[0] = 1 exactly,
  * built on the host and copied on `stream`.  Set the discount BEFORE a workspace is sized: with a discount the loop always records
- * trajectories, and every cadm_*_workspace_bytes(ctx, ..) of the nest from cadm_icem_workspace_bytes to cadm_critic_workspace_bytes
+ * trajectories, and every cadm_*_workspace_bytes(ctx, ..) of the nest from cadm_icem_workspace_bytes to cadm_anchored_workspace_bytes
  * returns the size with the trajectory view.  Refusals of a gamma < 1: a discrete ctx (cartpole), a candidate-sharded ctx, a D whose two
  * tiles of 64 x D floats and the table exceed 48 KiB of LDS (CADM_EINVAL); a CADM_ENV_SPEC ctx whose spec is not set (CADM_ESTATE).
  * cadm_discount_weights: *set_out = 1 and host_out[0 .. H] = the same floats the kernels read (host_out may be NULL), or *set_out = 0.
@@ -1084,6 +1084,68 @@ int cadm_imagine_sampled(cadm_ctx* ctx, const float* obs, const float* ctx_vec, 
 #define CADM_PROPOSE_NOISE 0
 #define CADM_PROPOSE_HEAD 1
 int cadm_set_policy_proposals(cadm_ctx* ctx, int32_t source, float std_scale);
+
+/* Log-density of given actions (csrc/policy_logp.hip; no reference twin, OPT-IN): log pi(a | s) of the stochastic actor above at an action
+ * the CALLER brings -- cadm_policy_sample returns the density of an action it drew itself.  Two uses of one kernel.  cadm_policy_logp: x
+ * [R,D], act [R,A] -> logp_out [R], for a learner that re-weights stored transitions under its current actor.  cadm_policy_logp_returns
+ * and the cadm_anchored_plan level of the nest: the actor-regularised score of LOOP / MBOP / KL-regularised MPC,
+ *   rows' = rows + weight * S,   S = ((0 + logp_0) + logp_1) + ..  over the counted steps of a particle's trajectory,
+ * with logp_t = log pi(a_t | s_t), s_t = obs[mi] at t = 0 and traj[t-1, q] after it, a_t = actions[mi, ni, t, :] raw, as the rollout
+ * read them (behind knot shaping and the actuator pass).  Every (step, particle) pair is a row: e = t * (m n p) + q, cadm_reward_returns'
+ * row space.  With `first` (cadm_constrain_returns' first_violation) the counted steps are t <= first[q]; the others are not loaded and
+ * read NaN in step_out.
+ * Per counted row and action dim d, all float32, every operation rounded on its own, no fma outside the matrix pipe:
+ *   x, the hidden layers, mu_d, l_d   exactly cadm_policy_sample's walk, on the registered net's packed copy and the head's layer
+ *   ls_d   the registered head's bound, as cadm_policy_sample:  CADM_LOGSTD_CLAMP: fminf(fmaxf(l_d, lo), hi);  CADM_LOGSTD_TANH: lo +
+ *          (0.5f * (hi - lo)) * (tanhf(l_d) + 1.0f)
+ *   CADM_POLICY_TANH:  y = (a_d - mid) / half       one subtraction, one correctly rounded division; mid = 0.5f * (ub + lb), half =
+ *                                                    0.5f * (ub - lb), as the policy kernels define them
+ *                      y = fminf(fmaxf(y, -CADM_LOGP_YMAX), CADM_LOGP_YMAX)
+ *                      lp = log1pf(y);  lm = log1pf(-y);  u = 0.5f * (lp - lm);  J = logf(half) + (lp + lm)      (= log(half (1 - y^2)))
+ *   CADM_POLICY_NONE:  u = a_d;  J = 0
+ *   xi     = (u - mu_d) * expf(-ls_d)
+ *   g_d    = ((-0.5f * xi) * xi - ls_d) - 0.9189385f
+ *   term_d = space == CADM_LOGP_ACTION ? g_d - J : g_d      (CADM_LOGP_PRE_SQUASH: the Gaussian's density of u, with no Jacobian)
+ *   logp   = term_0 + term_1 + ..  in ascending d from term_0, one thread per row
+ * A counted row with a non-finite value in its state or in its action gets logp = NaN explicitly (the clamp would hide an infinite
+ * action).  Nothing is drawn and no counter moves.  An action on or beyond a bound sits at |y| = CADM_LOGP_YMAX, |u| = atanh(YMAX) ~ 7.25:
+ * in action space that is the tanh-Gaussian's own spike at the bounds, which a narrow policy prices at thousands of nats;
+ * CADM_LOGP_PRE_SQUASH is the quadratic form without the Jacobian.
+ * Step sum and row update, cadm_reward_returns' arithmetic: S as above in ascending t; on a ctx with a discount over the horizon S = S +
+ * disc[t] * logp_t (step_out stays undiscounted); rows_out = rows_in + weight * S, one multiply and then one add.  step_out [H,m,n,p]
+ * or NULL (then workspace: cadm_policy_logp_workspace_bytes(ctx, m, n) bytes), sum_out [m,n,p] or NULL; rows_out may be rows_in.
+ * Determinism: every output is one thread's chain in the stated order, no floating-point atomics; nothing depends on the row tiles, the
+ * grid, m, n, p or the row's position: the same bits run to run, in any batch, and from cadm_policy_logp as from the planner stage.
+ * cadm_anchored_plan: the loop of cadm_critic_plan with that term in the particle returns, the outermost level of the nest today.  Per
+ * iteration: rollout -> constraints -> tracking -> the learned reward -> rows[q] += weight * S[q] -> the terminal value / Q ->
+ * cadm_particle_score (a risk-aware score sees the term per particle) -> the costs off the candidate score -> the refit.  logp NULL:
+ * exactly the launches of cadm_critic_plan.  policy may be NULL while a policy net is registered: the term needs the registered net and
+ * its head, not the proposals.  workspace: cadm_anchored_workspace_bytes(..) -- that of cadm_critic_workspace_bytes, and behind it the
+ * step log-densities [H,m,n,p] (rounded up to 256 bytes); the views in front keep their places.
+ * Refusals, before any HIP call: CADM_EINVAL for null pointers, R, m or n < 1, an unknown space, a weight that is not finite, lb >= ub, a
+ * head whose log_std_min < -10 (the mirror of log_std_max > 10: expf(-ls) stays finite with a margin), a discrete or candidate-sharded
+ * ctx, what cadm_set_policy_net refuses of the registered net's description, activation tiles beyond the 160 KiB of LDS at one row tile;
+ * no registered net (call cadm_set_policy_net) or no head on it (call cadm_set_policy_head; every cadm_set_policy_net drops the head):
+ * CADM_ESTATE; for cadm_anchored_plan also what cadm_critic_plan refuses. */
+#define CADM_LOGP_ACTION 0
+#define CADM_LOGP_PRE_SQUASH 1
+#define CADM_LOGP_YMAX 0.999999f   /* where |y| is clamped before atanh: the value SAC implementations clamp at */
+typedef struct cadm_policy_logp_params { float weight; /* finite */ int32_t space; /* CADM_LOGP_ACTION | CADM_LOGP_PRE_SQUASH */ } cadm_policy_logp_params;
+int cadm_policy_logp(cadm_ctx* ctx, const float* x /* [R,D] */, const float* act /* [R,A] */, int R, int space, float* logp_out /* [R] */,
+                     void* stream);
+size_t cadm_policy_logp_workspace_bytes(cadm_ctx* ctx, int m, int n);
+int cadm_policy_logp_returns(cadm_ctx* ctx, const cadm_policy_logp_params* params, const float* traj, const float* obs, const float* actions,
+                             const int32_t* first, int m, int n, const float* rows_in, float* rows_out, float* step_out, float* sum_out,
+                             void* workspace, void* stream);
+size_t cadm_anchored_workspace_bytes(cadm_ctx* ctx, int m, int n, int K, int mppi, int terminate, int actuator, int uncertainty, int P);
+int cadm_anchored_plan(cadm_ctx* ctx, const cadm_policy_logp_params* logp, const cadm_critic_params* critic, const cadm_policy_params* policy,
+                       const cadm_reward_params* params, const cadm_value_params* value, const cadm_uncertainty_params* uncertainty,
+                       const cadm_actuator_params* actuator, float* prev_io, float* prefix_io, int advance, const cadm_track_params* track,
+                       const float* targets, int T, const int32_t* offset, const cadm_knot_params* knots, const int32_t* phase,
+                       const cadm_constraint_params* constraints, const cadm_score_params* score, int update,
+                       const cadm_mppi_params* mppi_params, const float* obs, const float* cp_obs, const float* cp_act,
+                       const float* init_mean, const float* init_var, float* carry_io, int32_t* carry_valid_io, int m, int n, uint32_t seed,
+                       uint32_t call, void* workspace, float* plan_out, float* best_return_out, void* stream);
 
 /* Value-expansion targets (csrc/imagine_targets.hip; no reference twin): what a critic is trained on, out of cadm_imagine's transitions
  * and the caller's bootstrap values of their states, in ONE launch -- lambda-returns on every imagined state (Dreamer, TD-MPC), the n-step
